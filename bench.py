@@ -16,7 +16,11 @@ resident in HBM before the timed region.
 `python bench.py --gpus N` from a bare shell (no WORLD_SIZE in the environment) starts the N ranks itself, as child
 processes under torch.distributed.run, BEFORE this process touches the GPU, and relays rank 0's JSON line.
 
-roofline.frac is quoted on the frame's launch running ALONE on the chip (HIP events around single launches, one at a
+A plain run sets up, warms up, times --steps steps and prints the headline figure (value, ms_per_step).  --full adds the side
+measurements after the timed steps: the frame's launch alone, the poses, the path-tracing frame, the CPU baseline and the
+roofline.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
+
+roofline.frac (--full) is quoted on the frame's launch running ALONE on the chip (HIP events around single launches, one at a
 time); the throughput-derived figure with several frames in flight is reported beside it as frac_overlapped.
 """
 from __future__ import annotations
@@ -34,6 +38,7 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+DUMP_PIXELS = 1 << 20      # --dump-outputs: pixels sampled from a larger frame, 48 B each as written (50 MB)
 
 
 def parse():
@@ -68,9 +73,15 @@ def parse():
     ap.add_argument("--list-classes", type=int, default=1, help="list launches: order the walk by the previous frame's measured cost in four classes (0 = the order the searches finish in)")
     ap.add_argument("--orbit", type=float, default=0.0, help="degrees the camera turns around the world's centre per frame (0 = static camera)")
     ap.add_argument("--dense-dda", action="store_true", help="BASELINE configs[1]: upload the scene as a dense id grid and trace with the dense-grid kernel (N = 1, --n <= 512)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-paths", action="store_true", help="skip the 64-spp path-tracing side measurement")
-    ap.add_argument("--no-poses", action="store_true", help="skip the per-pose side measurements (poses A, B, C)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the side measurements: the frame's launch alone (at rest, moving, alternating, "
+                    "cold: config.kernel_ms_alone*, roofline), poses A, B, C, the 64-spp path-tracing frame, the oracle's byte counts and the CPU baseline.  "
+                    "Without it the run sets up, warms up, times the steps and prints the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy: the first-hit records' "
+                    "fields (hits_*, N = 1 only) and the RGBA8 framebuffer's channels (framebuffer_rgba), widened exactly to float32 / float64, at a fixed "
+                    "sample of %d pixels when the frame has more" % DUMP_PIXELS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle's byte counts (and with them the roofline)")
+    ap.add_argument("--no-paths", action="store_true", help="--full: skip the 64-spp path-tracing side measurement")
+    ap.add_argument("--no-poses", action="store_true", help="--full: skip the per-pose side measurements (poses A, B, C)")
     ap.add_argument("--gather-frames", type=int, default=0, help="N > 1: consecutive frames a rank traces in one launch pair and exchanges in one collective (0 = N, at most 8: every launch pair then has the size of a single-GPU frame)")
     ap.add_argument("--sparse-gather", type=int, default=2, help="N > 1: 0 = dense RGBA8 gather + un-permute; 1 = only the tiles with a non-sky pixel travel, as RGBA8; "
                     "2 = those tiles as 16-bit (material, face) codes that the root expands with the material table (half the bytes; falls back to 1 for very large tables)")
@@ -195,6 +206,28 @@ def cpu_baseline(packed, cam, width, height, stride, min_core_seconds=12.0):
     }
 
 
+def dump_outputs(out_dir, hits, rgba):
+    """--dump-outputs: what the timed path hands its caller for its last step.  `hits` (N = 1: the frame's 16-B first-hit records, else
+    None) as one file per field of blok_hit — t as float32, material_id as float64, voxel, face and hit as float32, all exact — and `rgba`
+    (rank 0: the RGBA8 framebuffer) as float32 channels in R, G, B, A order.  A frame of more than DUMP_PIXELS pixels is sampled at a
+    fixed set of pixels (default_rng(0), ascending), the same for every run of the same size."""
+    import torch
+    from blok_amd._ffi import HIT
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n_px = rgba.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n_px, DUMP_PIXELS, replace=False)) if n_px > DUMP_PIXELS else np.arange(n_px)
+    pick = torch.from_numpy(idx).to(rgba.device)
+    arrays = {"framebuffer_rgba": rgba[pick].cpu().numpy().view(np.uint8).reshape(-1, 4).astype(np.float32)}
+    if hits is not None:
+        rec = np.ascontiguousarray(hits[pick].cpu().numpy()).view(HIT).reshape(-1)
+        arrays.update({"hits_t": rec["t"].astype(np.float32), "hits_material_id": rec["material_id"].astype(np.float64),
+                       "hits_voxel": rec["voxel"].astype(np.float32), "hits_face": rec["face"].astype(np.float32),
+                       "hits_hit": rec["hit"].astype(np.float32)})
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -298,6 +331,8 @@ def main():
         t = torch.tensor([elapsed, device_ms], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, device_ms = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe.hits if world_size == 1 else None, pipe.frame_rgba)
 
     # the frame's launch running ALONE: HIP events around single launches on one stream, one at a time (what a rocprofv3
     # kernel trace of `--frames-in-flight 1` shows; profiles/README.md).  One launch (frame_kernel) per frame in the
@@ -320,16 +355,16 @@ def main():
         return float(np.mean(ms))
 
     gave_up = tracer.frame_queue_stalls()        # joint launches: walk waves that stopped waiting for their tile's search (they start at the ray origin: same frame, more work)
-    kernel_ms_avg = solitary_ms(pipe.backend, min(args.steps, 20))
+    kernel_ms_avg = solitary_ms(pipe.backend, min(args.steps, 20)) if args.full else None
     # ... and for a camera in motion (1 degree per frame around the world's centre): no order from earlier frames applies there
     kernel_ms_moving = None
-    if world_size == 1 and args.orbit == 0.0 and not args.dense_dda:
+    if args.full and world_size == 1 and args.orbit == 0.0 and not args.dense_dda:
         moving = HipBackend(tracer, cam)
         kernel_ms_moving = solitary_ms(moving, 16, orbit_arc(1.0))
     # ... for a caller that alternates between two fixed views (stereo eyes, a cut back and forth): each view has its own cached order from its
     # second appearance on (round 4) — and for the first frame of a view never seen before (no scheduling state at all: row-major order)
     kernel_ms_alternating = kernel_ms_cold = None
-    if world_size == 1 and args.orbit == 0.0 and not args.dense_dda:
+    if args.full and world_size == 1 and args.orbit == 0.0 and not args.dense_dda:
         two = [cam, orbit_arc(6.0)[1]]
         alt = HipBackend(tracer, cam)
         solitary_ms(alt, 10, two)                                  # each view a few times, its sort, its adoption: untimed, like --settle for the one view
@@ -369,7 +404,7 @@ def main():
 
     # the other camera poses of SURVEY.md §8(d), same world and frame: a short pipelined run and the solitary launch each
     poses = {}
-    if world_size == 1 and not args.no_poses:
+    if args.full and world_size == 1 and not args.no_poses:
         for pose in (0, 1, 2):
             pcam = W.scene_camera(args.n, pose, W_, H_, args.seed)
             pb = HipBackend(tracer, pcam)
@@ -397,7 +432,7 @@ def main():
     # side measurement (not the headline value): BASELINE.json configs[4], the reference's sample/bounce loop at
     # 64 spp, 2 bounces, over the same world and frame — two frames, HIP events around the kernel
     paths = None
-    if world_size == 1 and not args.no_paths:
+    if args.full and world_size == 1 and not args.no_paths:
         color = torch.empty((H_ * W_, 4), dtype=torch.float32, device="cuda")
         tracer.set_timing(True)
         ms = []
@@ -462,10 +497,10 @@ def main():
                        "ranks": ranks_info, "process_group": backend_info,
                        "camera_orbit_deg_per_frame": args.orbit,
                        "frames_in_flight": args.frames_in_flight, "settle_frames": args.settle, "walk_waves_that_gave_up_waiting": gave_up, "device_ms_per_step": device_ms / args.steps, "kernel_ms_alone": kernel_ms_avg, "kernel_ms_alone_moving": kernel_ms_moving, "beam_tile": args.beam,
-                       "poses": poses, "also_measured_paths": paths},
+                       "poses": poses, "also_measured_paths": paths, "full": args.full},
         }
         alg = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             alg = oracle_counters(packed, cam, W_, H_, 1 if world_size == 1 else 4)
             if world_size == 1:
                 out["cpu_baseline"] = cpu_baseline(packed, cam, W_, H_, args.cpu_stride)

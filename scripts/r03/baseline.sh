@@ -4,8 +4,8 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03_base; rm -rf $OUT; mkdir -p $OUT
 echo "== tests" && timeout -k 10 400 python3 -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1; echo "tests rc=$?"; tail -3 $OUT/tests.log
-echo "== bench" && timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"
-echo "== bench orbit" && timeout -k 10 200 python3 bench.py --steps 60 --warmup 5 --orbit 1 --settle 0 --no-poses --no-paths --no-cpu-baseline > $OUT/bench_orbit.json 2> $OUT/bench_orbit.err; echo "rc=$?"
+echo "== bench" && timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"
+echo "== bench orbit" && timeout -k 10 200 python3 bench.py --full --steps 60 --warmup 5 --orbit 1 --settle 0 --no-poses --no-paths --no-cpu-baseline > $OUT/bench_orbit.json 2> $OUT/bench_orbit.err; echo "rc=$?"
 echo "== paths trace" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/paths_trace -o paths -- python3 scripts/r03/profile_paths64.py 64 3 > $OUT/paths_trace.log 2>&1; echo "rc=$?"
 i=0
 for PMC in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SMEM" \

@@ -9,11 +9,11 @@ print('$1:', round(d['value']), 'Mrays/s', round(d['ms_per_step'], 4), 'ms/frame
 for form in 4 5 2 0; do
   for cls in 1 0; do
     [ $cls = 0 ] && [ $form != 4 ] && [ $form != 5 ] && continue
-    timeout -k 10 120 python3 bench.py --steps 60 --warmup 5 --fused $form --list-classes $cls --frames-in-flight 1 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "form $form classes $cls static, 1 in flight"
-    timeout -k 10 120 python3 bench.py --steps 60 --warmup 5 --fused $form --list-classes $cls --frames-in-flight 1 --orbit 1 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "form $form classes $cls orbit 1, 1 in flight"
+    timeout -k 10 120 python3 bench.py --full --steps 60 --warmup 5 --fused $form --list-classes $cls --frames-in-flight 1 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "form $form classes $cls static, 1 in flight"
+    timeout -k 10 120 python3 bench.py --full --steps 60 --warmup 5 --fused $form --list-classes $cls --frames-in-flight 1 --orbit 1 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "form $form classes $cls orbit 1, 1 in flight"
   done
 done
-timeout -k 10 200 python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-paths 2>/dev/null | show "default (form 3), 3 in flight"
-timeout -k 10 200 python3 bench.py --steps 100 --warmup 10 --orbit 1 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "default (form 3), 3 in flight, orbit 1"
-timeout -k 10 200 python3 bench.py --steps 100 --warmup 10 --fused 0 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "form 0, 3 in flight"
+timeout -k 10 200 python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-paths 2>/dev/null | show "default (form 3), 3 in flight"
+timeout -k 10 200 python3 bench.py --full --steps 100 --warmup 10 --orbit 1 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "default (form 3), 3 in flight, orbit 1"
+timeout -k 10 200 python3 bench.py --full --steps 100 --warmup 10 --fused 0 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | show "form 0, 3 in flight"
 } 2>&1 | tee gpurun_out/r03/list_classes_ab.txt

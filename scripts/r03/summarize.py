@@ -69,7 +69,7 @@ def derive(kernel, c, dur_ns):
 head = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip()
 dirty = bool(subprocess.run(["git", "status", "--porcelain", "--", "blok_amd", "include", "bench.py"], cwd=ROOT, capture_output=True, text=True).stdout.strip())
 summary = {"tag": tag, "commit": head + ("+uncommitted changes" if dirty else ""),
-           "command": "python3 bench.py --steps 60 --warmup 10 --settle 32 --frames-in-flight 1 --no-cpu-baseline --no-paths --no-poses (scripts/r03/profile.sh)",
+           "command": "python3 bench.py --full --steps 60 --warmup 10 --settle 32 --frames-in-flight 1 --no-cpu-baseline --no-paths --no-poses (scripts/r03/profile.sh)",
            "kernels": {}, "paths": {}}
 raw = {}
 dur = durations("trace")

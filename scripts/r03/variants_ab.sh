@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/r03
 for rep in 1 2; do
 for lib in blok_amd/libblok_hip.so blok_amd/variants/*.so; do
-  BLOK_HIP_LIB=$PWD/$lib timeout -k 10 200 python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-paths ${EXTRA} 2>/dev/null | python3 -c "
+  BLOK_HIP_LIB=$PWD/$lib timeout -k 10 200 python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-paths ${EXTRA} 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); c = d['config']
 print('$lib rep$rep:', round(d['value']), 'Mrays/s; alone', round(c['kernel_ms_alone'], 4), 'ms;', {k: (round(v['Mrays_per_s']), round(v['ms_per_frame_alone'], 4)) for k, v in c['poses'].items()})"

@@ -9,7 +9,7 @@ for rep in 1 2; do
   for lib in "$@"; do
     for a in "--steps 200 --warmup 10" ${ONLY_LONG:+__skip__} "--steps 20 --warmup 5"; do
       [ "$a" = "__skip__" ] && break
-      BLOK_HIP_LIB=$PWD/$lib python3 bench.py $a --no-cpu-baseline --no-paths --no-poses 2>/dev/null | python3 -c "
+      BLOK_HIP_LIB=$PWD/$lib python3 bench.py --full $a --no-cpu-baseline --no-paths --no-poses 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 print('$lib', '$a', 'Mrays/s %.0f' % d['value'], 'ms/step %.4f' % d['ms_per_step'], 'alone %.4f' % d['config']['kernel_ms_alone'], 'moving %.4f' % d['config']['kernel_ms_alone_moving'])" | tee -a $OUT || exit 1

@@ -6,7 +6,7 @@ mkdir -p gpurun_out/r04
 OUT=gpurun_out/r04/ab_poses_$TAG.txt; : > $OUT
 for rep in 1 2; do
   for lib in "$@"; do
-    BLOK_HIP_LIB=$PWD/$lib python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-paths 2>/dev/null | python3 -c "
+    BLOK_HIP_LIB=$PWD/$lib python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-paths 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 p = d['config']['poses']

@@ -7,7 +7,7 @@ for rep in 1 2; do
 for lib in blok_amd/variants/libblok_hip_r3.so blok_amd/libblok_hip.so; do
   echo "== $lib rep $rep"
   BLOK_HIP_LIB=$PWD/$lib timeout -k 10 200 python3 scripts/r03/solitary_orbit.py 1 64 1 2>&1 | grep -v amdgpu.ids | tail -3
-  BLOK_HIP_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | python3 -c "
+  BLOK_HIP_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-paths --no-poses 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); r = d['roofline']
 print('bench:', round(d['value']), 'Mrays/s', round(d['ms_per_step'], 4), 'ms/frame; alone', round(r['kernel_ms'], 4), 'moving', round(r['kernel_ms_moving'], 4), 'alternating', r.get('kernel_ms_alternating'), 'cold', r.get('kernel_ms_cold'))"

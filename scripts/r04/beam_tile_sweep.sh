@@ -5,7 +5,7 @@ mkdir -p gpurun_out/r04
 OUT=gpurun_out/r04/beam_tile_sweep.txt; : > $OUT
 for rep in 1 2; do
   for b in 32 16 64; do
-    python3 bench.py --steps 100 --warmup 10 --beam $b --no-cpu-baseline --no-paths 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 100 --warmup 10 --beam $b --no-cpu-baseline --no-paths 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 p = d['config']['poses']

@@ -12,6 +12,11 @@
   regression pin of the restatement, generated with this image's libm).
 * first_hit_64.npz       — oracle first-hit records, 64^3 scene, 256x256 (BASELINE.json configs[0]): a 64x64
   centre crop of each pose + SHA-256 of the full buffers.
+* morton_live_reference.npz — the reference's morton.hpp (oracle/_ref/libref_morton.so) on 2000 random points of
+  default_rng(11): codes and octants at depth 7.
+* vox_default_palette.json and vox_reference_models.tar.xz — the reference's default .vox palette (the 256 words of
+  DEFAULT_PALETTE in blok/src/vox_loader.cpp) and its MagicaVoxel models (assets/models/*.vox), byte for byte.  Written only
+  when the path of a reference checkout is given: `python tests/golden/make_golden.py <reference tree>`.
 The fixtures are data (inputs + expected outputs); no reference source text is stored.
 """
 import hashlib
@@ -46,6 +51,40 @@ def morton():
         vec.append({"xyz": [x, y, z], "code": f"{code:#018x}", "octants_depth7": octs})
     (OUT / "morton_reference.json").write_text(json.dumps({"source": "blok/include/morton.hpp compiled in place",
                                                            "vectors": vec}, indent=0))
+
+
+def morton_live():
+    ref = O.ref_morton()
+    if ref is None:
+        print("oracle/_ref/libref_morton.so missing: keeping existing morton_live_reference.npz")
+        return
+    xyz = np.random.default_rng(11).integers(-(1 << 20), 1 << 20, size=(2000, 3))
+    code = np.array([int(ref.ref_morton_encode(int(x), int(y), int(z))) for x, y, z in xyz], dtype=np.uint64)
+    octants = np.array([[int(ref.ref_morton_octant(int(c), 7, lvl)) for lvl in range(7)] for c in code], dtype=np.int32)
+    np.savez_compressed(OUT / "morton_live_reference.npz", xyz=xyz, code=code, octants=octants)
+
+
+def vox_reference(tree):
+    import re
+    import tarfile
+    if tree is None:
+        print("no reference tree given: keeping existing vox_default_palette.json and vox_reference_models.tar.xz")
+        return
+    text = (tree / "blok/src/vox_loader.cpp").read_text()
+    body = text[text.index("DEFAULT_PALETTE[256]"):]
+    body = body[body.index("{") + 1:body.index("};")]
+    table = re.findall(r"0x[0-9a-fA-F]{8}", body)
+    assert len(table) == 256
+    (OUT / "vox_default_palette.json").write_text(json.dumps({"source": "DEFAULT_PALETTE in blok/src/vox_loader.cpp", "palette": table}, indent=0))
+    with tarfile.open(OUT / "vox_reference_models.tar.xz", "w:xz", preset=9) as tar:
+        for f in sorted((tree / "assets/models").glob("*.vox")):
+            info = tar.gettarinfo(f, arcname=f.name)
+            info.uid = info.gid = 0
+            info.uname = info.gname = ""
+            info.mtime = 0
+            info.mode = 0o644
+            with open(f, "rb") as fh:
+                tar.addfile(info, fh)
 
 
 def svo_builder():
@@ -123,6 +162,8 @@ def post_chain():
 
 if __name__ == "__main__":
     morton()
+    morton_live()
+    vox_reference(Path(sys.argv[1]) if len(sys.argv) > 1 else None)
     svo_builder()
     first_hit()
     post_chain()

@@ -24,6 +24,9 @@ def test_hip_library_exports_every_declared_symbol():
     debug = declared_functions(ROOT / "include" / "blok_hip_debug.h")
     assert len(names) >= 18 and len(debug) >= 6
     assert not set(names) & set(debug), "declared in both headers"
+    # through _ffi.hip_lib() first, which imports torch before the library: opened bare, the library would pull the ROCm install's
+    # libamdhip64 in beside torch's, a second HIP runtime in this process that the GPU tests after this one would bind to and find no device
+    _ffi.hip_lib()
     lib = C.CDLL(str(_ffi.HIP_LIB))
     for n in names + debug:
         assert hasattr(lib, n), f"libblok_hip.so does not export {n}"

@@ -1,10 +1,12 @@
 """bench.py's command line: the help text renders (argparse expands % in help strings), the defaults are the contract's, and — on a
-GPU — every combination of the side-measurement switches still prints its one JSON line (a stray variable once made --no-poses fail)."""
+GPU — every combination of the side-measurement switches still prints its one JSON line (a stray variable once made --no-poses fail),
+and a plain run prints the headline figure alone and dumps what its last step computed."""
 import json
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -13,6 +15,7 @@ ROOT = Path(__file__).resolve().parent.parent
 def test_help_and_defaults():
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout, out.stderr
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
     sys.path.insert(0, str(ROOT))
     import importlib
     bench = importlib.import_module("bench")
@@ -23,13 +26,45 @@ def test_help_and_defaults():
         sys.argv = argv
     assert (a.gpus, a.n, a.width, a.height, a.pose, a.settle, a.orbit) == (1, 1024, 3840, 2160, 0, 32, 0.0)
     assert a.steps > 0 and a.warmup >= 0 and a.fused == 3
+    assert a.full is False and a.dump_outputs is None
+
+
+def test_dump_outputs_sample_is_fixed_exact_and_small(tmp_path):
+    """A 4K frame is written at a fixed sample of pixels, every field widened exactly, under 64 MB in all."""
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from blok_amd._ffi import HIT
+    n = 3840 * 2160
+    rng = np.random.default_rng(3)
+    rec = np.zeros(n, dtype=HIT)
+    rec["t"] = rng.uniform(0, 2000, n).astype(np.float32)
+    rec["material_id"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    rec["voxel"] = rng.integers(-(1 << 15), 1 << 15, (n, 3)).astype(np.int16)
+    rec["face"] = rng.integers(0, 6, n)
+    rec["hit"] = rng.integers(0, 2, n)
+    rgba = rng.integers(-(1 << 31), 1 << 31, n, dtype=np.int64).astype(np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, torch.from_numpy(rec.view(np.int32).reshape(n, 4)), torch.from_numpy(rgba))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["framebuffer_rgba.npy", "hits_face.npy", "hits_hit.npy", "hits_material_id.npy", "hits_t.npy", "hits_voxel.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f[:-4]].dtype in (np.float32, np.float64) and np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+    idx = np.sort(np.random.default_rng(0).choice(n, bench.DUMP_PIXELS, replace=False))
+    sample = rec[idx]
+    assert np.array_equal(got["hits_t"], sample["t"]) and np.array_equal(got["hits_material_id"], sample["material_id"])
+    assert np.array_equal(got["hits_voxel"], sample["voxel"]) and np.array_equal(got["hits_face"], sample["face"])
+    assert np.array_equal(got["hits_hit"], sample["hit"])
+    assert np.array_equal(got["framebuffer_rgba"], rgba[idx].view(np.uint8).reshape(-1, 4))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [[], ["--no-poses"], ["--no-paths"], ["--no-cpu-baseline"], ["--no-poses", "--no-paths"], ["--no-poses", "--no-cpu-baseline"],
                                    ["--no-paths", "--no-cpu-baseline", "--orbit", "1"], ["--fused", "4", "--no-paths"], ["--fused", "0", "--tile-ordering", "0", "--no-paths", "--no-poses"]])
 def test_flag_combinations_print_one_line(flags):
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--n", "64", "--width", "512", "--height", "256", "--steps", "3", "--warmup", "1", "--cpu-stride", "4", *flags]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--n", "64", "--width", "512", "--height", "256", "--steps", "3", "--warmup", "1", "--cpu-stride", "4", "--full", *flags]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -40,3 +75,37 @@ def test_flag_combinations_print_one_line(flags):
     assert ("roofline" in d) == ("--no-cpu-baseline" not in flags)
     assert (d["config"]["also_measured_paths"] is None) == ("--no-paths" in flags)
     assert (d["config"]["poses"] == {}) == ("--no-poses" in flags)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full: the headline line and nothing measured besides it; --dump-outputs holds the last timed frame, whose first-hit
+    records are the oracle's bit for bit."""
+    from blok_amd import world as W
+    from tests import oracle_ffi as O
+    from tests.conftest import SEED
+    n, w, h = 64, 512, 256
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--n", str(n), "--width", str(w), "--height", str(h), "--steps", "7", "--warmup", "2",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 7 and d["value"] > 0
+    assert d["ms_per_step"] > 0 and abs(d["value"] - w * h / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and "roofline" not in d
+    c = d["config"]
+    assert c["full"] is False and c["kernel_ms_alone"] is None and c["poses"] == {} and c["also_measured_paths"] is None
+    cm = W.ChunkManager(128, 1.0)
+    cm.generate_scene(n, SEED)
+    cm.rebuild_dirty_chunks()
+    pw = cm.pack_chunks_to_gpu_svo(W.scene_materials(SEED))
+    ref, _ = O.Lattice(pw.nodes, pw.sub_chunks).trace(O.primary_rays(W.scene_camera(n, 0, w, h, SEED), w, h), threads=8)
+    assert np.array_equal(np.load(tmp_path / "hits_t.npy"), ref["t"])
+    assert np.array_equal(np.load(tmp_path / "hits_material_id.npy"), ref["material_id"])
+    assert np.array_equal(np.load(tmp_path / "hits_voxel.npy"), ref["voxel"])
+    assert np.array_equal(np.load(tmp_path / "hits_face.npy"), ref["face"])
+    assert np.array_equal(np.load(tmp_path / "hits_hit.npy"), ref["hit"])
+    rgba = np.load(tmp_path / "framebuffer_rgba.npy")
+    assert rgba.shape == (w * h, 4) and int((rgba != [160, 200, 230, 255]).any(axis=1).sum()) == c["framebuffer_pixels_hit"]

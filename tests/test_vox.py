@@ -1,8 +1,9 @@
 """MagicaVoxel .vox import + material library, product vs oracle restatement
-(reference blok/src/vox_loader.cpp, blok/src/material.cpp).  Files are synthesised here; the reference's own
-.vox assets are only read (never copied) when the reference tree is present."""
-import re
+(reference blok/src/vox_loader.cpp, blok/src/material.cpp).  Files are synthesised here; the reference's default palette
+and its own .vox assets are stored as data fixtures under tests/golden/ (tests/golden/make_golden.py)."""
+import json
 import struct
+import tarfile
 from pathlib import Path
 
 import numpy as np
@@ -13,7 +14,7 @@ from blok_amd import world as W
 from blok_amd._ffi import BlokError
 from tests import oracle_ffi as O
 
-REF = Path("/root/reference")
+GOLDEN = Path(__file__).resolve().parent / "golden"
 
 
 def chunk(cid: bytes, content: bytes = b"", children: bytes = b"") -> bytes:
@@ -168,22 +169,19 @@ def test_load_and_import_file(tmp_path, sample_file):
         V.load_and_import_vox(tmp_path / "missing.vox", cm, lib)
 
 
-@pytest.mark.skipif(not (REF / "blok/src/vox_loader.cpp").exists(), reason="reference tree not present")
 def test_default_palette_equals_reference_table_read_as_text():
-    text = (REF / "blok/src/vox_loader.cpp").read_text()
-    body = text[text.index("DEFAULT_PALETTE[256]"):]
-    body = body[body.index("{") + 1:body.index("};")]
-    table = np.array([int(t, 16) for t in re.findall(r"0x[0-9a-fA-F]{8}", body)], dtype=np.uint32)
+    table = np.array([int(t, 16) for t in json.loads((GOLDEN / "vox_default_palette.json").read_text())["palette"]], dtype=np.uint32)
     assert len(table) == 256
     assert np.array_equal(table, O.default_palette())
     rng = np.random.default_rng(1)
     assert np.array_equal(table, V.VoxFile.load_memory(make_vox([((2, 2, 2), random_model(rng, 2, 3))])).palette())
 
 
-@pytest.mark.skipif(not (REF / "assets/models").exists(), reason="reference assets not present")
-def test_reference_assets_parse_identically():
-    files = sorted((REF / "assets/models").glob("*.vox"))
-    assert files
+def test_reference_assets_parse_identically(tmp_path):
+    with tarfile.open(GOLDEN / "vox_reference_models.tar.xz") as tar:
+        tar.extractall(tmp_path)
+    files = sorted(tmp_path.glob("*.vox"))
+    assert len(files) == 7
     for f in files:
         data = f.read_bytes()
         pv, ov = V.VoxFile.load_file(f), O.OracleVox(data)
