@@ -120,16 +120,25 @@ BLOK_DEV float plane_t(const Axis& a, float f) {
 BLOK_DEV float cell_size(uint32_t lvl) { return __uint_as_float(0x3F800000u + (lvl << 24)); }
 
 // One axis of "enter a node" whose near corner is f and whose children have size s: how many of the three
-// interior planes have T <= tS (binary search, T is monotone in q), i.e. which child slab holds the ray at tS,
-// and the T of that slab's far plane.  t_far comes in as the node's own far plane.  s2 = 2 s, s3 = 3 s.
-BLOK_DEV void enter_axis(const Axis& a, float& f, float& t_far, float s, float s2, float s3, float tS) {
-    const float m2 = plane_t(a, f + s2);
-    const bool g = m2 <= tS;
-    const float mq = plane_t(a, f + (g ? s3 : s));
-    const bool g2 = mq <= tS;
-    const float inner = g ? t_far : m2;          // far plane if mq is already crossed
-    t_far = g2 ? inner : mq;
-    f += (g ? s2 : 0.0f) + (g2 ? s : 0.0f);
+// interior planes have T <= tS (binary search, T is monotone in q), i.e. which child slab holds the ray at tS; f advances to
+// that slab's near corner.  s2 = 2 s.
+//
+// The slab's far plane is left to the caller's  plane_t(a, f + s)  with the advanced f.  That is the plane the binary search
+// would have picked among the node's far plane and its two probes, in every case (g: the probe at f + 2s is crossed, g2: the second
+// probe is; f is the node's corner on entry):
+//   g = 0, g2 = 0:  the slab at f,      far plane at f + s   (the second probe)
+//   g = 0, g2 = 1:  the slab at f + s,  far plane at f + 2s  (the first probe)
+//   g = 1, g2 = 0:  the slab at f + 2s, far plane at f + 3s  (the second probe)
+//   g = 1, g2 = 1:  the slab at f + 3s, far plane at f + 4s  (the node's own far plane: plane_t(f_parent + 4 s) in the loop, the world's
+//                   fW = 2^23 + 4^L at the root)
+// Every coordinate is an integer inside the 2^23 mantissa field, so each sum is exact and the float argument of plane_t is the same
+// number either way: the same bits.  So walk_loop evaluates the far planes once at the bottom of a trip for the descend path and the
+// step path alike, instead of choosing among three candidates with selects on the descend path.
+BLOK_DEV void enter_axis(const Axis& a, float& f, float s, float s2, float tS) {
+    const bool g = plane_t(a, f + s2) <= tS;
+    f += g ? s2 : 0.0f;
+    const bool g2 = plane_t(a, f + s) <= tS;
+    f += g2 ? s : 0.0f;
 }
 
 // What closest-hit sees of a procedural hit (intersect.rint:138-141, hit.rchit:58-74), in registers.
@@ -189,10 +198,11 @@ BLOK_DEV void walk_enter(const TraceArgs& A, const WalkRay& R, float tmin, float
     if (!s.walking) return;
     const uint4 q = A.nodes[0];
     s.node.lo = q.x; s.node.hi = q.y; s.node.base = q.z;
-    const float s2 = s.size + s.size, s3 = s2 + s.size;
-    enter_axis(R.ax, s.fx, s.tFx, s.size, s2, s3, s.tCur);
-    enter_axis(R.ay, s.fy, s.tFy, s.size, s2, s3, s.tCur);
-    enter_axis(R.az, s.fz, s.tFz, s.size, s2, s3, s.tCur);
+    const float s2 = s.size + s.size;
+    enter_axis(R.ax, s.fx, s.size, s2, s.tCur);
+    enter_axis(R.ay, s.fy, s.size, s2, s.tCur);
+    enter_axis(R.az, s.fz, s.size, s2, s.tCur);
+    s.tFx = plane_t(R.ax, s.fx + s.size); s.tFy = plane_t(R.ay, s.fy + s.size); s.tFz = plane_t(R.az, s.fz + s.size);
 }
 
 // The loop: from the state walk_enter left to the first reported voxel, the end of the interval or the world's far side.
@@ -227,38 +237,38 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
             node.lo = c.x; node.hi = c.y; node.base = c.z;
             lvl -= 1;
             size *= 0.25f;
-            const float s2 = size + size, s3 = s2 + size;
-            enter_axis(R.ax, fx, tFx, size, s2, s3, tCur);     // tCur >= tmin always (see the invariant above the loop)
-            enter_axis(R.ay, fy, tFy, size, s2, s3, tCur);
-            enter_axis(R.az, fz, tFz, size, s2, s3, tCur);
-            continue;
-        }
-        const float tExit = fminf(fminf(tFx, tFy), tFz);
-        if (occupied) {
+            const float s2 = size + size;
+            enter_axis(R.ax, fx, size, s2, tCur);     // tCur >= tmin always (see the invariant above the loop)
+            enter_axis(R.ay, fy, size, s2, tCur);
+            enter_axis(R.az, fz, size, s2, tCur);
+        } else {
+            const float tExit = fminf(fminf(tFx, tFy), tFz);
             // a filled voxel: reported iff its clipped interval is non-empty (intersect.rint:189-193)
-            if (tCur < fminf(tExit, tmax)) { found = true; break; }
+            if (occupied && tCur < fminf(tExit, tmax)) { found = true; break; }
+            // step: cross the nearest far plane (x, then y, then z on ties)
+            BLOK_STAT(2, lvl);
+            tCur = tExit;
+            if (!(tCur < tmax)) break;
+            const bool sx = tFx == tExit;
+            const bool sy = !sx && tFy == tExit;
+            const bool sz = !sx && !sy;
+            fx += sx ? size : 0.0f; fy += sy ? size : 0.0f; fz += sz ? size : 0.0f;
+            // the stepped coordinate is now a multiple of 4^k for the level k whose cell boundary was crossed (its mantissa
+            // field is q > 0, so the lowest set bit of the float's bits is the lowest set bit of q)
+            const uint32_t up = static_cast<uint32_t>(__ffs(static_cast<int>(__float_as_uint(sx ? fx : (sy ? fy : fz)))) - 1) >> 1;
+            if (up != lvl) {
+                BLOK_STAT(3, lvl);
+                if (up >= L) break;                                    // left the world box
+                lvl = up;
+                size = cell_size(lvl);
+                const uint32_t keep = ~((1u << (2 * up)) - 1u);        // clears mantissa bits only: the exponent field stays
+                fx = __uint_as_float(__float_as_uint(fx) & keep); fy = __uint_as_float(__float_as_uint(fy) & keep); fz = __uint_as_float(__float_as_uint(fz) & keep);
+                const uint4 c = stk[(lvl - 1) * kBlock];               // node of level lvl+1
+                node.lo = c.x; node.hi = c.y; node.base = c.z;
+            }
         }
-        // step: cross the nearest far plane (x, then y, then z on ties)
-        BLOK_STAT(2, lvl);
-        tCur = tExit;
-        if (!(tCur < tmax)) break;
-        const bool sx = tFx == tExit;
-        const bool sy = !sx && tFy == tExit;
-        const bool sz = !sx && !sy;
-        fx += sx ? size : 0.0f; fy += sy ? size : 0.0f; fz += sz ? size : 0.0f;
-        // the stepped coordinate is now a multiple of 4^k for the level k whose cell boundary was crossed (its mantissa
-        // field is q > 0, so the lowest set bit of the float's bits is the lowest set bit of q)
-        const uint32_t up = static_cast<uint32_t>(__ffs(static_cast<int>(__float_as_uint(sx ? fx : (sy ? fy : fz)))) - 1) >> 1;
-        if (up != lvl) {
-            BLOK_STAT(3, lvl);
-            if (up >= L) break;                                    // left the world box
-            lvl = up;
-            size = cell_size(lvl);
-            const uint32_t keep = ~((1u << (2 * up)) - 1u);        // clears mantissa bits only: the exponent field stays
-            fx = __uint_as_float(__float_as_uint(fx) & keep); fy = __uint_as_float(__float_as_uint(fy) & keep); fz = __uint_as_float(__float_as_uint(fz) & keep);
-            const uint4 c = stk[(lvl - 1) * kBlock];               // node of level lvl+1
-            node.lo = c.x; node.hi = c.y; node.base = c.z;
-        }
+        // the far planes of the cell the trip ends in, one evaluation for both paths (enter_axis: after a descent they are the planes the
+        // child slab search would have chosen, bit for bit)
         tFx = plane_t(R.ax, fx + size); tFy = plane_t(R.ay, fy + size); tFz = plane_t(R.az, fz + size);
     }
     s.fx = fx; s.fy = fy; s.fz = fz; s.tCur = tCur; s.bit = bit; s.node = node; s.found = found;

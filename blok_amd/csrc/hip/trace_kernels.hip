@@ -335,6 +335,13 @@ __global__ __launch_bounds__(kBlock) void trace_frames_kernel(const TraceArgs A,
     trace_block<RayMode::Tiles>(L, blockIdx.x - f * F.blocks_per_frame, F.blocks_per_frame, lds_stack);
 }
 
+// The kernel's TraceArgs where the launch put them, in the kernel argument segment (the first argument sits at offset 0): fields read
+// through this are scalar loads at their point of use.  A by-value TraceArgs is loaded whole at the kernel's entry instead, and in the
+// search kernels the fields read only after the search stayed live across it, spilled into VGPR lanes.
+__device__ __forceinline__ const TraceArgs& kernel_args() {
+    return *(const TraceArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
 // One wave per beam tile: TraceArgs::beam[tile] = conservative start parameter of the tile's rays, or kBeamNone.
 // list_search / list_task_base (list launches): this search's index in the launch and the first task id of its frame.
 // lds_stack: the walk's stack for the wave tiles a search walks itself (launches over a prefix of the order, TraceArgs::rank_of), else null.
@@ -364,8 +371,9 @@ __device__ __forceinline__ void beam_block(const TraceArgs& A, const uint32_t b,
         px_end = px + B; py_end = py + B;
     }
     uint32_t visits = 0;
+    // (the count is always taken, one scalar subtraction: through a pointer that may be null it was a variable in scratch memory)
     const float t0 = padding ? kBeamNone : beam_start(A, static_cast<float>(px), static_cast<float>(py), static_cast<float>(px_end), static_cast<float>(py_end), lane, kBeamNone,
-                                                      A.debug_visits ? &visits : nullptr);
+                                                      &visits);
     if (A.debug_visits && lane == 0) A.debug_visits[b] = visits;
     if (A.list.entries) list_publish<MODE>(A, list_search, list_task_base, b, t0, lane);      // list launches: the live wave tiles go onto the frame's list
     else if (lane == 0) { if (A.beam_slots) publish_beam(A.beam_slots + b, A.beam_serial, t0); else A.beam[b] = t0; }
@@ -433,8 +441,9 @@ __device__ __forceinline__ void beam_block(const TraceArgs& A, const uint32_t b,
 }
 
 template <RayMode MODE>
-__global__ __launch_bounds__(64) void beam_kernel(const TraceArgs A, const uint32_t n_beam_tiles) {
+__global__ __launch_bounds__(64) void beam_kernel(const TraceArgs, const uint32_t n_beam_tiles) {
     extern __shared__ uint4 lds_stack[];       // launch_beam sizes it whenever the searches may walk (TraceArgs::rank_of), else 0 bytes and unused
+    const TraceArgs& A = kernel_args();
     beam_block<MODE>(A, blockIdx.x, n_beam_tiles, A.rank_of ? lds_stack : nullptr, blockIdx.x, 0u);
 }
 
@@ -449,7 +458,7 @@ template <RayMode MODE>
 __global__ __launch_bounds__(kBlock) void joint_kernel(const TraceArgs A, const uint32_t n_beam_tiles) {
     extern __shared__ uint4 lds_stack[];
     if (blockIdx.x < n_beam_tiles) {
-        if (threadIdx.x < 64u) beam_block<MODE>(A, blockIdx.x, n_beam_tiles, lds_stack);
+        if (threadIdx.x < 64u) beam_block<MODE>(kernel_args(), blockIdx.x, n_beam_tiles, lds_stack);
         return;
     }
     trace_block<MODE>(A, blockIdx.x - n_beam_tiles, gridDim.x - n_beam_tiles, lds_stack);
