@@ -40,8 +40,11 @@ CAMERA = np.dtype([("pos", "<f4", 3), ("fwd", "<f4", 3), ("right", "<f4", 3), ("
                    ("tan_half_fov", "<f4"), ("aspect", "<f4")])
 HIT = np.dtype([("t", "<f4"), ("material_id", "<u4"), ("voxel", "<i2", 3), ("face", "u1"), ("hit", "u1")])
 RAY = np.dtype([("org", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")])
+# = blok_instance: a placed model (lattice offset, axis-aligned orientation), 32 bytes
+INSTANCE = np.dtype([("model", "<u4"), ("offset", "<i4", 3), ("axis", "u1", 3), ("flip", "u1"), ("reserved", "<u4", 3)])
+INSTANCE_NONE = 0xFFFFFFFF
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
-assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32
+assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32
 
 
 class GBuffer(C.Structure):
@@ -248,6 +251,13 @@ HIP_SYMBOLS = {
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_abi_version": (C.c_uint32, []),
+    "blok_hip_model_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "blok_hip_model_destroy": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "blok_hip_check_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "blok_hip_trace_primary_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4),
+    "blok_hip_trace_primary_instanced": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3),
+    "blok_hip_trace_rays_instanced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_hip_trace_rays_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -307,7 +307,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 0u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 1u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -360,7 +360,8 @@ int blok_hip_resize(blok_hip_ctx* ctx, uint32_t width, uint32_t height) {
 
 static void free_stream_scratch(blok_hip_ctx::StreamScratch& sc) {
     for (void* p : {static_cast<void*>(sc.beam), static_cast<void*>(sc.ctl), static_cast<void*>(sc.entries), static_cast<void*>(sc.tile_map),
-                    static_cast<void*>(sc.slots), static_cast<void*>(sc.gave_up), static_cast<void*>(sc.list_entries), static_cast<void*>(sc.list_ctl), sc.tail_pool})
+                    static_cast<void*>(sc.slots), static_cast<void*>(sc.gave_up), static_cast<void*>(sc.list_entries), static_cast<void*>(sc.list_ctl), sc.tail_pool,
+                    static_cast<void*>(sc.inst_bins), static_cast<void*>(sc.inst_hits)})
         if (p) (void)hipFree(p);
     if (sc.list_hint) (void)hipHostFree(sc.list_hint);
     sc = blok_hip_ctx::StreamScratch{};
@@ -382,6 +383,7 @@ void blok_hip_destroy(blok_hip_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     free_world(ctx);
+    free_models(ctx);
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     free_post(ctx);
     if (ctx->has_volume) blok::gpu_volume_destroy(&ctx->volume);

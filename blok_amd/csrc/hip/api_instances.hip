@@ -1,0 +1,312 @@
+// Instanced voxel models (include/blok_hip.h, instance_core.h): the model store on the context and the instanced trace entries.
+#include "api_internal.h"
+
+#include <algorithm>
+#include <limits>
+
+namespace blok_api {
+
+void free_models(blok_hip_ctx* ctx) {
+    for (auto& m : ctx->models.desc) {
+        if (m.nodes) (void)hipFree(const_cast<uint4*>(m.nodes));
+        if (m.materials) (void)hipFree(const_cast<uint32_t*>(m.materials));
+    }
+    if (ctx->models.d_desc) (void)hipFree(ctx->models.d_desc);
+    ctx->models = blok_hip_ctx::Models{};
+}
+
+namespace {
+
+// The device copy of the descriptors after a change (the callers have synchronised the device), and the LDS stack the kernels need.
+int upload_models(blok_hip_ctx* ctx) {
+    auto& M = ctx->models;
+    if (M.d_capacity < M.desc.size()) {
+        if (M.d_desc) (void)hipFree(M.d_desc);
+        M.d_desc = nullptr; M.d_capacity = 0;
+        const size_t cap = std::max<size_t>(16, M.desc.size() * 2);
+        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&M.d_desc), cap * sizeof(blok::ModelDesc)));
+        M.d_capacity = cap;
+    }
+    if (!M.desc.empty())
+        BLOK_HIP_TRY(ctx, hipMemcpy(M.d_desc, M.desc.data(), M.desc.size() * sizeof(blok::ModelDesc), hipMemcpyHostToDevice));
+    uint32_t slots = 1;
+    for (const auto& m : M.desc)
+        if (m.nodes && m.levels > 1) slots = std::max(slots, m.levels - 1u);
+    M.stack_levels = slots;
+    return BLOK_OK;
+}
+
+// The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.
+int check_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) {
+    if (n && !inst) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    for (uint32_t i = 0; i < n; ++i) {
+        const blok_instance& I = inst[i];
+        const std::string at = "instance " + std::to_string(i) + ": ";
+        if (!blok::instance_well_formed(I)) {
+            if (I.reserved[0] | I.reserved[1] | I.reserved[2]) return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "reserved field is not zero");
+            if (I.flip >= 8u) return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "flip has bits above the three axes");
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "axis is not a permutation of 0, 1, 2");
+        }
+        if (I.model >= ctx->models.desc.size() || !ctx->models.desc[I.model].nodes)
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "unknown model " + std::to_string(I.model));
+        if (!blok::instance_usable(I, ctx->models.desc[I.model]))
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "world box outside the int16 lattice of hit records");
+    }
+    return BLOK_OK;
+}
+
+// Where the camera's basis puts a world point on screen (instance_core.h: BinView).
+blok::BinView bin_view(const blok_hip_ctx* ctx, const blok_camera& c) {
+    blok::BinView V{};
+    auto cross = [](const float* a, const float* b, float* o) {
+        o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    float ru[3], uf[3], fr[3];
+    cross(c.right, c.up, ru); cross(c.up, c.fwd, uf); cross(c.fwd, c.right, fr);
+    const float det = c.fwd[0] * ru[0] + c.fwd[1] * ru[1] + c.fwd[2] * ru[2];
+    auto norm = [](const float* a) { return std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); };
+    const float scale = norm(c.fwd) * norm(c.right) * norm(c.up);
+    V.usable = std::isfinite(det) && std::fabs(det) > 1e-6f * scale;
+    if (!V.usable) return V;
+    for (int k = 0; k < 3; ++k) {
+        V.pos[k] = c.pos[k];
+        V.cl[k] = ru[k] / det; V.cu[k] = uf[k] / det; V.cv[k] = fr[k] / det;
+    }
+    // camera_plane_uv (trace_core.h) inverted: pixel index x (centre at x + 0.5 in frame units) of camera-plane u, y of v
+    const float W = static_cast<float>(ctx->width), H = static_cast<float>(ctx->height);
+    const float jx = (2.0f * ctx->jitter_px[0]) / W, jy = (2.0f * ctx->jitter_px[1]) / H;
+    V.sx = W / (2.0f * c.tan_half_fov * c.aspect);
+    V.bx = (1.0f - jx) * 0.5f * W - 0.5f;
+    V.sy = -H / (2.0f * c.tan_half_fov);
+    V.by = (1.0f - jy) * 0.5f * H - 0.5f;
+    return V;
+}
+
+// Per-stream scratch grown to n elements (a buffer still in use by earlier launches on the stream is freed after them).
+template <class T>
+int stream_buffer(blok_hip_ctx* ctx, hipStream_t stream, T*& buf, size_t& have, size_t n) {
+    if (have >= n) return BLOK_OK;
+    if (buf) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(buf); }
+    buf = nullptr; have = 0;
+    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&buf), n * sizeof(T)));
+    have = n;
+    return BLOK_OK;
+}
+
+blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs& world, const blok_instance* inst, uint32_t n, blok_hit* hits,
+                                 uint32_t* rgba, uint32_t* ids) {
+    blok::InstanceArgs P{};
+    P.world = world;
+    P.instances = inst; P.n_instances = n;
+    P.models = ctx->models.d_desc; P.n_models = static_cast<uint32_t>(ctx->models.desc.size());
+    P.hits = hits; P.rgba = rgba; P.ids = ids;
+    P.stack_levels = ctx->models.stack_levels;
+    return P;
+}
+
+}  // namespace
+}  // namespace blok_api
+
+using namespace blok_api;
+
+extern "C" {
+
+int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t* material_ids, size_t n, uint32_t* out_model) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!xyz || !material_ids || !out_model || n == 0) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model needs at least one voxel and an output id");
+    if (ctx->models.desc.size() >= std::numeric_limits<uint32_t>::max() - 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model ids exhausted");
+    std::vector<blok::VoxelRec> voxels(n);
+    int32_t lo[3] = {std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::max(), std::numeric_limits<int32_t>::max()};
+    int32_t hi[3] = {std::numeric_limits<int32_t>::min(), std::numeric_limits<int32_t>::min(), std::numeric_limits<int32_t>::min()};
+    for (size_t i = 0; i < n; ++i) {
+        voxels[i] = blok::VoxelRec{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], material_ids[i]};
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], xyz[3 * i + a]); hi[a] = std::max(hi[a], xyz[3 * i + a]); }
+    }
+    blok::HostTree tree;
+    const char* why = "";
+    if (!blok::build_tree(voxels, tree, &why)) return set_error(ctx, BLOK_ERR_UNSUPPORTED, std::string("model: ") + why);
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    blok::ModelDesc m{};
+    const size_t node_bytes = tree.nodes.size() * sizeof(blok::TreeNode), mat_bytes = tree.materials.size() * sizeof(uint32_t);
+    uint4* nodes = nullptr; uint32_t* mats = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nodes), node_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&mats), mat_bytes);
+    if (e == hipSuccess) e = hipMemcpy(nodes, tree.nodes.data(), node_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mats, tree.materials.data(), mat_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (nodes) (void)hipFree(nodes);
+        if (mats) (void)hipFree(mats);
+        return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("model upload: ") + hipGetErrorString(e));
+    }
+    m.nodes = nodes; m.materials = mats; m.levels = tree.levels;
+    for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = lo[a]; m.hi[a] = hi[a] + 1; }
+    // frames in flight may read the descriptor array that the upload replaces
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->models.desc.push_back(m);
+    const int rc = upload_models(ctx);
+    if (rc != BLOK_OK) return rc;
+    *out_model = static_cast<uint32_t>(ctx->models.desc.size() - 1u);
+    return BLOK_OK;
+}
+
+int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());           // frames in flight may still walk it
+    blok::ModelDesc& m = ctx->models.desc[model];
+    (void)hipFree(const_cast<uint4*>(m.nodes));
+    (void)hipFree(const_cast<uint32_t*>(m.materials));
+    m = blok::ModelDesc{};                               // the id stays taken and unknown
+    return upload_models(ctx);
+}
+
+int blok_hip_check_instances(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n_instances) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    return check_table(ctx, instances_host, n_instances);
+}
+
+int blok_hip_trace_primary_instanced_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                            const blok_instance* instances_dev, uint32_t n_instances,
+                                            void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, void* hip_stream) {
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if ((!out_hits_dev && !out_rgba_dev && !out_instance_dev) || !rect_inside(ctx, x0, y0, w, h))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
+    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const size_t n_pixels = static_cast<size_t>(w) * h;
+    blok_hit* hits = static_cast<blok_hit*>(out_hits_dev);
+    if (n_instances && !hits) {                          // the instance pass needs the world records
+        auto& sc = ctx->beam_buffers[stream];
+        rc = stream_buffer(ctx, stream, sc.inst_hits, sc.n_inst_hits, n_pixels);
+        if (rc != BLOK_OK) return rc;
+        hits = sc.inst_hits;
+    }
+    // the world pass: blok_hip_trace_primary_device's launch, unchanged
+    if (hits || out_rgba_dev) {
+        rc = blok_hip_trace_primary_device(ctx, cam, x0, y0, w, h, hits, out_rgba_dev, hip_stream);
+        if (rc != BLOK_OK) return rc;
+    }
+    if (!n_instances) {
+        if (out_instance_dev) BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, n_pixels * sizeof(uint32_t), stream));
+        return BLOK_OK;
+    }
+    blok::TraceArgs world = base_args(ctx, cam);
+    world.x0 = x0; world.y0 = y0; world.w = w; world.h = h;
+    blok::InstanceArgs P = instance_args(ctx, world, instances_dev, n_instances, hits, static_cast<uint32_t*>(out_rgba_dev), out_instance_dev);
+    P.bins_x = (w + blok::kBinPixels - 1u) / blok::kBinPixels;
+    P.bins_y = (h + blok::kBinPixels - 1u) / blok::kBinPixels;
+    P.view = bin_view(ctx, *cam);
+    auto& sc = ctx->beam_buffers[stream];
+    rc = stream_buffer(ctx, stream, sc.inst_bins, sc.n_inst_bins, static_cast<size_t>(P.bins_x) * P.bins_y * blok::kBinWords);
+    if (rc != BLOK_OK) return rc;
+    P.bins = sc.inst_bins;
+    blok::launch_instance_bins(P, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    blok::launch_instance_pass(P, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    return BLOK_OK;
+}
+
+int blok_hip_trace_primary_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                     const blok_instance* instances_host, uint32_t n_instances,
+                                     blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host) {
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if ((!out_hits_host && !out_rgba_host && !out_instance_host) || !rect_inside(ctx, x0, y0, w, h))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
+    rc = check_table(ctx, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    // one device block: instances, records, RGBA8, ids
+    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
+    const size_t bytes = inst_bytes + n * (sizeof(blok_hit) + 2u * sizeof(uint32_t));
+    unsigned char* d = nullptr;
+    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d);
+    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d + inst_bytes);
+    uint32_t* d_rgba = reinterpret_cast<uint32_t*>(d_hits + n);
+    uint32_t* d_ids = d_rgba + n;
+    hipError_t e = n_instances ? hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) {
+        rc = blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, d_inst, n_instances, d_hits, out_rgba_host ? d_rgba : nullptr,
+                                                     out_instance_host ? d_ids : nullptr, nullptr);
+        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_rgba_host) e = hipMemcpy(out_rgba_host, d_rgba, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d);
+    if (rc != BLOK_OK) return rc;
+    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_primary_instanced: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev,
+                                         uint32_t n_instances, blok_hit* out_hits_dev, uint32_t* out_instance_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
+    if (n == 0) return BLOK_OK;
+    if (!rays_dev || (!out_hits_dev && !out_instance_dev) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
+    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (!n_instances && !out_hits_dev) {
+        BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, n * sizeof(uint32_t), stream));
+        return BLOK_OK;
+    }
+    blok_hit* hits = out_hits_dev;
+    if (!hits) {
+        auto& sc = ctx->beam_buffers[stream];
+        const int rc = stream_buffer(ctx, stream, sc.inst_hits, sc.n_inst_hits, n);
+        if (rc != BLOK_OK) return rc;
+        hits = sc.inst_hits;
+    }
+    blok::TraceArgs world = base_args(ctx, nullptr);
+    world.rays = rays_dev; world.n_rays = static_cast<uint32_t>(n); world.out = hits;
+    int rc = launch_timed(ctx, blok::RayMode::Rays, world, static_cast<uint32_t>((n + blok::kBlock - 1) / blok::kBlock), stream);
+    if (rc != BLOK_OK) return rc;
+    if (!n_instances) {
+        if (out_instance_dev) BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, n * sizeof(uint32_t), stream));
+        return BLOK_OK;
+    }
+    world.out = nullptr;
+    blok::launch_instance_rays(instance_args(ctx, world, instances_dev, n_instances, hits, nullptr, out_instance_dev), stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    return BLOK_OK;
+}
+
+int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, const blok_instance* instances_host,
+                                  uint32_t n_instances, blok_hit* out_hits_host, uint32_t* out_instance_host) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
+    if (n == 0) return BLOK_OK;
+    if (!rays_host || (!out_hits_host && !out_instance_host) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
+    int rc = check_table(ctx, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
+    const size_t bytes = inst_bytes + n * (sizeof(blok_ray) + sizeof(blok_hit) + sizeof(uint32_t));
+    unsigned char* d = nullptr;
+    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d);
+    blok_ray* d_rays = reinterpret_cast<blok_ray*>(d + inst_bytes);
+    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d_rays + n);
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_hits + n);
+    hipError_t e = hipMemcpy(d_rays, rays_host, n * sizeof(blok_ray), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_instances) e = hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = blok_hip_trace_rays_instanced_device(ctx, d_rays, n, d_inst, n_instances, d_hits, out_instance_host ? d_ids : nullptr, nullptr);
+        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d);
+    if (rc != BLOK_OK) return rc;
+    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays_instanced: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+}  // extern "C"

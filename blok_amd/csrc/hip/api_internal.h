@@ -28,6 +28,7 @@
 #include "tile_order.h"
 #include "path_args.h"
 #include "tree.h"
+#include "instance_core.h"
 
 struct blok_hip_ctx {
     int device = 0;
@@ -115,6 +116,8 @@ struct blok_hip_ctx {
         uint32_t* list_hint = nullptr; bool list_hint_valid = false; uint32_t list_hint_key = 0;
         uint32_t* tile_map = nullptr; size_t n_tile_map = 0;            // sparse exchange, root: frame tile -> record (zero between launches)
         void* tail_pool = nullptr; size_t tail_pool_bytes = 0;           // path launches: the bounce rounds' tail pool (path_core.h: TailRecord[blocks][kTailCapacity]), grown on demand
+        uint32_t* inst_bins = nullptr; size_t n_inst_bins = 0;          // instanced frames: the binning kernel's lists (instance_core.h: kBinWords words per bin), grown on demand
+        blok_hit* inst_hits = nullptr; size_t n_inst_hits = 0;          // instanced frames without a record output: the world records the instance pass reads
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
     // Longest-first scheduling of the walk for a camera at rest (tile_order.h; rectangle launches of the static forms): every walk wave
@@ -180,6 +183,13 @@ struct blok_hip_ctx {
     // TAA jitter of the next frames' primary rays, in pixels (blok_hip_set_taa_jitter); blok_hip_draw_frame_rt sets it per frame
     float jitter_px[2] = {0.0f, 0.0f};
     bool rt_taa_jitter = true;          // PostProcess::Settings::enableTAA (renderer_postprocess.hpp:103)
+    // instanced voxel models (api_instances.hip): descriptors indexed by model id (a destroyed model keeps its slot with nodes == null),
+    // their device copy, and the LDS stack slots the deepest live model needs
+    struct Models {
+        std::vector<blok::ModelDesc> desc;
+        blok::ModelDesc* d_desc = nullptr; size_t d_capacity = 0;
+        uint32_t stack_levels = 1;
+    } models;
     // timing
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     bool timing = false, timed = false;
@@ -216,6 +226,8 @@ int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream);
 int live_list(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_searches, uint32_t per_search);
 int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, uint32_t blocks, hipStream_t stream, uint32_t tiles_of_rank = 0,
                  const blok::TileFrames* frames = nullptr);
+// api_instances.hip
+void free_models(blok_hip_ctx* ctx);
 void forget_device_activity(const blok_hip_ctx* ctx, bool one_stream = false, hipStream_t stream = nullptr);
 bool rect_inside(const blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
 // The root's assembly of a sparse exchange (blok_hip_scatter_*_tile_frames_device): the ranks' buffers either side by side in

@@ -1,0 +1,212 @@
+// Instanced voxel models (include/blok_hip.h: blok_instance): the device math of the instance kernels (instance_kernels.hip).
+//
+// An instance places a model — its own 64-tree in its own local lattice — at a lattice offset with an axis-aligned orientation (a
+// signed permutation of the axes).  Such a transform moves a ray into local space with ONE rounding per axis (the subtraction of the
+// offset; a sign change and a permutation are exact), so the local walk is the canonical walk of trace_core.h on a transformed ray and
+// the composed record is specified bit for bit:
+//   o'_k = s_k * fl(o[axis[k]] - offset[axis[k]] * vs),   d'_k = s_k * d[axis[k]],   tmin, tmax unchanged      (s_k = flip bit k ? -1 : +1)
+//   world voxel  w[axis[k]] = flip_k ? offset[axis[k]] - 1 - v'_k : offset[axis[k]] + v'_k;   face 2k + n -> 2 axis[k] + (n ^ flip_k)
+// Candidates are taken world first, then instance 0, 1, ...; one replaces the record only with a strictly smaller t, which is what a
+// walk with tmax = the best t so far does (the walk's acceptance test is t < tmax).
+//
+// tests/test_instances_cpu.py compiles this header with trace_core.h for the host (BLOK_TRACE_HOST_HARNESS) through its own shim.
+#ifndef BLOK_INSTANCE_CORE_H
+#define BLOK_INSTANCE_CORE_H
+
+#include "trace_core.h"
+
+// The limits are checked by the host entries too.
+#ifdef BLOK_TRACE_HOST_HARNESS
+#define BLOK_HD inline
+#else
+#define BLOK_HD __host__ __device__ __forceinline__
+#endif
+
+namespace blok {
+
+// A model as the kernels see it: its tree (tree.h) and its local box of filled voxels [lo, hi) (local voxel coordinates).
+// nodes == null: a destroyed model (any instance of it is skipped).
+struct ModelDesc {
+    const uint4*    nodes;
+    const uint32_t* materials;
+    uint32_t levels;
+    int32_t  origin[3];
+    int32_t  lo[3], hi[3];
+    uint32_t pad[2];
+};
+static_assert(sizeof(ModelDesc) == 64, "one model descriptor is 64 bytes");
+static_assert(sizeof(blok_instance) == 32, "one instance record is 32 bytes");
+
+constexpr uint32_t kInstanceNone = 0xFFFFFFFFu;
+// A hit record's voxel is int16: every instance's world box must lie in [kLatticeMin, kLatticeMax) on every axis.
+constexpr int64_t kLatticeMin = -32768, kLatticeMax = 32768;
+
+// Component `a` (0, 1, 2) of a triple, by selects: the permutation is data, and an array indexed by it would live in scratch.
+BLOK_HD float pick3(uint32_t a, float x, float y, float z) { return a == 0u ? x : (a == 1u ? y : z); }
+BLOK_HD int32_t pick3(uint32_t a, int32_t x, int32_t y, int32_t z) { return a == 0u ? x : (a == 1u ? y : z); }
+// The local axis k with axis[k] == a.
+BLOK_HD uint32_t local_axis(const blok_instance& I, uint32_t a) { return I.axis[0] == a ? 0u : (I.axis[1] == a ? 1u : 2u); }
+
+// The instance's world box in voxels along world axis a: [lo, hi).
+BLOK_HD void instance_world_span(const blok_instance& I, const ModelDesc& M, uint32_t a, int64_t& lo, int64_t& hi) {
+    const uint32_t k = local_axis(I, a);
+    const int64_t o = pick3(a, I.offset[0], I.offset[1], I.offset[2]);
+    const int64_t mlo = pick3(k, M.lo[0], M.lo[1], M.lo[2]), mhi = pick3(k, M.hi[0], M.hi[1], M.hi[2]);
+    const bool f = (I.flip >> k) & 1u;
+    lo = f ? o - mhi : o + mlo;
+    hi = f ? o - mlo : o + mhi;
+}
+
+// The record itself is well formed: axis a permutation of 0, 1, 2, only the three flip bits, reserved words zero.
+BLOK_HD bool instance_well_formed(const blok_instance& I) {
+    const uint32_t a0 = I.axis[0], a1 = I.axis[1], a2 = I.axis[2];
+    const bool perm = a0 < 3u && a1 < 3u && a2 < 3u && ((1u << a0) | (1u << a1) | (1u << a2)) == 7u;
+    return perm && I.flip < 8u && (I.reserved[0] | I.reserved[1] | I.reserved[2]) == 0u;
+}
+
+// Everything the blocking entries check, for the kernels (an instance of the device entries that fails it is skipped).
+BLOK_HD bool instance_usable(const blok_instance& I, const ModelDesc& M) {
+    if (!instance_well_formed(I) || !M.nodes) return false;
+    for (uint32_t a = 0; a < 3u; ++a) {
+        int64_t lo, hi;
+        instance_world_span(I, M, a, lo, hi);
+        if (lo < kLatticeMin || hi > kLatticeMax) return false;
+    }
+    return true;
+}
+
+// The ray in the model's local space (one rounding per axis: the subtraction).  vs: the world's voxel size.
+BLOK_DEV float local_origin(const blok_instance& I, float vs, const RayIn& r, uint32_t k) {
+    const uint32_t a = I.axis[k];
+    // offset * vs: exact (|offset| <= 2^16, vs a power of two)
+    const float rel = rn_sub(pick3(a, r.ox, r.oy, r.oz), rn_mul(static_cast<float>(pick3(a, I.offset[0], I.offset[1], I.offset[2])), vs));
+    return ((I.flip >> k) & 1u) ? -rel : rel;
+}
+BLOK_DEV float local_dir(const blok_instance& I, const RayIn& r, uint32_t k) {
+    const float d = pick3(I.axis[k], r.dx, r.dy, r.dz);
+    return ((I.flip >> k) & 1u) ? -d : d;
+}
+BLOK_DEV RayIn instance_ray(const blok_instance& I, float vs, const RayIn& r) {
+    RayIn t;
+    t.ox = local_origin(I, vs, r, 0u); t.oy = local_origin(I, vs, r, 1u); t.oz = local_origin(I, vs, r, 2u);
+    t.dx = local_dir(I, r, 0u); t.dy = local_dir(I, r, 1u); t.dz = local_dir(I, r, 2u);
+    t.tmin = r.tmin; t.tmax = r.tmax;
+    return t;
+}
+
+// Does the local ray's interval [tmin, tmax) meet the model's box [lo, hi) * vs?  The planes' T are the walk's own formula
+// (trace_kernels.h: T = fl(fl(p - o) * inv)), and every voxel's planes lie between the box planes, so a reported voxel's interval is
+// inside the box's: the test never rejects a ray the walk would report a voxel for.
+BLOK_DEV void box_axis(int32_t lo, int32_t hi, float vs, float o, float d, float& enter, float& leave) {
+    const float inv = safe_inv(d);
+    const float t0 = rn_mul(rn_sub(rn_mul(static_cast<float>(lo), vs), o), inv);
+    const float t1 = rn_mul(rn_sub(rn_mul(static_cast<float>(hi), vs), o), inv);
+    enter = fmaxf(enter, fminf(t0, t1));
+    leave = fminf(leave, fmaxf(t0, t1));
+}
+BLOK_DEV bool instance_box_entered(const ModelDesc& M, float vs, const RayIn& r) {
+    float enter = r.tmin, leave = r.tmax;
+    box_axis(M.lo[0], M.hi[0], vs, r.ox, r.dx, enter, leave);
+    box_axis(M.lo[1], M.hi[1], vs, r.oy, r.dy, enter, leave);
+    box_axis(M.lo[2], M.hi[2], vs, r.oz, r.dz, enter, leave);
+    return enter < leave;
+}
+
+// The walk's arguments for a model (world voxel size and material table; no camera, no outputs).
+BLOK_DEV TraceArgs model_args(const ModelDesc& M, float vs, float inv_vs) {
+    TraceArgs a{};
+    a.nodes = M.nodes;
+    a.materials = M.materials;
+    a.origin[0] = M.origin[0]; a.origin[1] = M.origin[1]; a.origin[2] = M.origin[2];
+    a.levels = M.levels;
+    a.voxel_size = vs; a.inv_voxel_size = inv_vs;
+    return a;
+}
+
+// A local hit as a world record (the 16-byte blok_hit layout, trace_core.h: trace_one).
+BLOK_DEV int32_t world_voxel(const blok_instance& I, const HitInfo& h, uint32_t a) {
+    const uint32_t k = local_axis(I, a);
+    const int32_t v = pick3(k, h.vx, h.vy, h.vz), o = pick3(a, I.offset[0], I.offset[1], I.offset[2]);
+    return ((I.flip >> k) & 1u) ? o - 1 - v : o + v;
+}
+BLOK_DEV uint4 instance_record(const blok_instance& I, const HitInfo& h) {
+    const uint32_t fk = h.face >> 1, fn = h.face & 1u;
+    const uint32_t face = 2u * pick3(fk, int32_t(I.axis[0]), int32_t(I.axis[1]), int32_t(I.axis[2])) + (fn ^ ((I.flip >> fk) & 1u));
+    uint4 rec;
+    rec.x = __float_as_uint(h.t);
+    rec.y = h.material;
+    rec.z = (static_cast<uint32_t>(world_voxel(I, h, 0u)) & 0xFFFFu) | (static_cast<uint32_t>(world_voxel(I, h, 1u)) << 16);
+    rec.w = (static_cast<uint32_t>(world_voxel(I, h, 2u)) & 0xFFFFu) | (face << 16) | (1u << 24);
+    return rec;
+}
+
+// One candidate: the instance's walk of world ray r with tmax = best_t.  true (and rec) iff it reports a voxel, whose t is then < best_t.
+BLOK_DEV bool instance_candidate(const blok_instance& I, const ModelDesc& M, float vs, float inv_vs, const RayIn& r, float best_t,
+                                 uint4* stk, uint4& rec) {
+    RayIn l = instance_ray(I, vs, r);
+    l.tmax = best_t;
+    if (!instance_box_entered(M, vs, l)) return false;
+    const HitInfo h = walk(model_args(M, vs, inv_vs), l, stk);
+    if (!h.found) return false;
+    rec = instance_record(I, h);
+    return true;
+}
+
+// ---- screen bins (binning kernel) -----------------------------------------------------------------------------------------------
+// Where a world point lands on screen: the solution of  p - pos = lambda fwd + mu right + nu up  (the camera basis need not be orthonormal)
+// is lambda = dot(p - pos, cl), mu = dot(p - pos, cu), nu = dot(p - pos, cv) with the rows of the basis' inverse; the pixel of
+// (u, v) = (mu, nu) / lambda inverts camera_plane_uv (trace_core.h).
+struct BinView {
+    float pos[3], cl[3], cu[3], cv[3];
+    float sx, bx, sy, by;        // pixel x = u * sx + bx, pixel y = v * sy + by (pixel index space: pixel i's centre at i)
+    uint32_t usable;             // 0: the basis is degenerate, every instance covers every bin
+};
+
+// The pixel rectangle [x0, x1] x [y0, y1] (inclusive, frame pixels, with a 1-pixel margin) that a world box [lo, hi) * vs may cover;
+// false: some corner is at or behind the camera plane (the box may cover anything).
+BLOK_DEV bool project_box(const BinView& V, const float lo[3], const float hi[3], float& x0, float& y0, float& x1, float& y1) {
+    x0 = y0 = 3.0e38f; x1 = y1 = -3.0e38f;
+    for (int c = 0; c < 8; ++c) {
+        const float px = ((c & 1) ? hi[0] : lo[0]) - V.pos[0];
+        const float py = ((c & 2) ? hi[1] : lo[1]) - V.pos[1];
+        const float pz = ((c & 4) ? hi[2] : lo[2]) - V.pos[2];
+        const float l = px * V.cl[0] + py * V.cl[1] + pz * V.cl[2];
+        const float len = fabsf(px) + fabsf(py) + fabsf(pz);
+        if (!(l > 1e-5f * len)) return false;               // at, behind or next to the camera plane (NaN included)
+        const float inv = 1.0f / l;
+        const float u = (px * V.cu[0] + py * V.cu[1] + pz * V.cu[2]) * inv;
+        const float v = (px * V.cv[0] + py * V.cv[1] + pz * V.cv[2]) * inv;
+        const float x = u * V.sx + V.bx, y = v * V.sy + V.by;
+        x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+    }
+    x0 -= 1.0f; y0 -= 1.0f; x1 += 1.0f; y1 += 1.0f;        // the margin: rounding of both the rays and this projection stays far below a pixel
+    return true;
+}
+
+// Arguments of the three instance kernels (instance_kernels.hip).  Bins: one per kBinPixels x kBinPixels pixels of the launch rectangle,
+// kBinWords words each: word 0 = the number of instances listed (kBinOverflow: more than kBinCapacity, the bin's pixels test every
+// instance), then the instance indices in ascending order.
+constexpr uint32_t kBinPixels = 32, kBinWords = 64, kBinCapacity = kBinWords - 1, kBinOverflow = 0xFFFFFFFFu;
+struct InstanceArgs {
+    TraceArgs world;                     // camera, frame and rectangle, material table, voxel size, tmin / tmax; rays / n_rays (rays kernel)
+    const blok_instance* instances;      // device memory, n_instances records
+    uint32_t n_instances;
+    const ModelDesc* models;             // the context's model store
+    uint32_t n_models;
+    uint32_t* bins;                      // bins_x * bins_y bins of kBinWords words (per-stream scratch)
+    uint32_t bins_x, bins_y;
+    BinView view;
+    blok_hit* hits;                      // the world pass's records in, the composed records out (never null)
+    uint32_t* rgba;                      // may be null: RGBA8 of the pixels an instance won (the world pass wrote the others)
+    uint32_t* ids;                       // may be null: the winning instance per pixel / ray, kInstanceNone for the world or a miss
+    uint32_t stack_levels;               // LDS stack slots per lane: the deepest live model's levels - 1 (>= 1)
+};
+
+#ifndef BLOK_TRACE_HOST_HARNESS
+void launch_instance_bins(const InstanceArgs& args, hipStream_t stream);
+void launch_instance_pass(const InstanceArgs& args, hipStream_t stream);
+void launch_instance_rays(const InstanceArgs& args, hipStream_t stream);
+#endif
+
+}  // namespace blok
+#endif

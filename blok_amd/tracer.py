@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import BlokError, CAMERA, GBuffer, HIT, MATERIAL, RAY, SUB_CHUNK, SVO_NODE, WorldStats
+from ._ffi import BlokError, CAMERA, GBuffer, HIT, INSTANCE, MATERIAL, RAY, SUB_CHUNK, SVO_NODE, WorldStats
 
 
 class HipTracer:
@@ -413,6 +413,55 @@ class HipTracer:
         hits = np.zeros(len(rays), dtype=HIT)
         self._check(self._lib.blok_hip_trace_rays(self._ctx, _ffi.ptr(rays), len(rays), _ffi.ptr(hits)))
         return hits
+
+    # -- instanced voxel models (blok_hip.h) ------------------------------------------------------------------------
+    def model_create(self, xyz, material_ids) -> int:
+        """Uploads a model (n voxels of its local lattice, one material id each); returns its id.  May synchronise the device."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)
+        mats = np.ascontiguousarray(material_ids, dtype=np.uint32).reshape(-1)
+        if len(mats) != len(xyz):
+            raise ValueError("one material id per voxel")
+        out = C.c_uint32()
+        self._check(self._lib.blok_hip_model_create(self._ctx, _ffi.ptr(xyz), _ffi.ptr(mats), len(mats), C.byref(out)))
+        return int(out.value)
+
+    def model_destroy(self, model: int):
+        self._check(self._lib.blok_hip_model_destroy(self._ctx, int(model)))
+
+    def check_instances(self, instances: np.ndarray):
+        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
+        self._check(self._lib.blok_hip_check_instances(self._ctx, _ffi.ptr(inst), len(inst)))
+
+    def trace_primary_instanced(self, cam: np.ndarray, instances: np.ndarray, rect=None):
+        """(hits (h, w), instance ids (h, w), RGBA8 (h, w)) of the frame (or rect) over the world plus `instances` (INSTANCE records)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
+        hits = np.zeros(w * h, dtype=HIT)
+        ids = np.zeros(w * h, dtype=np.uint32)
+        rgba = np.zeros(w * h, dtype=np.uint32)
+        self._check(self._lib.blok_hip_trace_primary_instanced(self._ctx, _ffi.ptr(cam), x0, y0, w, h, _ffi.ptr(inst), len(inst),
+                                                               _ffi.ptr(hits), _ffi.ptr(rgba), _ffi.ptr(ids)))
+        return hits.reshape(h, w), ids.reshape(h, w), rgba.reshape(h, w)
+
+    def trace_primary_instanced_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, hits_ptr: int = 0, rgba_ptr: int = 0,
+                                       ids_ptr: int = 0, rect=None, stream: int = 0):
+        """Asynchronous: device instance table and outputs (any output pointer may be 0, not all)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        self._check(self._lib.blok_hip_trace_primary_instanced_device(self._ctx, _ffi.ptr(cam), x0, y0, w, h, C.c_void_p(instances_ptr),
+                                                                      int(n_instances), C.c_void_p(hits_ptr), C.c_void_p(rgba_ptr),
+                                                                      C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def trace_rays_instanced(self, rays: np.ndarray, instances: np.ndarray):
+        """(records, instance ids) of explicit rays over the world plus `instances`."""
+        rays = np.ascontiguousarray(rays, dtype=RAY)
+        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
+        hits = np.zeros(len(rays), dtype=HIT)
+        ids = np.zeros(len(rays), dtype=np.uint32)
+        self._check(self._lib.blok_hip_trace_rays_instanced(self._ctx, _ffi.ptr(rays), len(rays), _ffi.ptr(inst), len(inst),
+                                                            _ffi.ptr(hits), _ffi.ptr(ids)))
+        return hits, ids
 
     def trace_paths(self, cam: np.ndarray, spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None):
         """raygen.rgen's sample/bounce loop: dict of (h, w, 4) float32 planes

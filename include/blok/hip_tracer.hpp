@@ -247,6 +247,33 @@ public:
         check(blok_hip_sharpen_device(m_ctx, rgba8Dev, strength, outRgba8Dev, stream));
     }
 
+    // ---- instanced voxel models (blok_hip.h): models uploaded once, placed per frame by an instance table
+    uint32_t createModel(const std::vector<int32_t>& xyz, const std::vector<uint32_t>& materialIds) {
+        if (xyz.size() != 3 * materialIds.size()) throw std::invalid_argument("HipTracer::createModel: three coordinates per voxel");
+        uint32_t id = 0;
+        check(blok_hip_model_create(m_ctx, xyz.data(), materialIds.data(), materialIds.size(), &id));
+        return id;
+    }
+    void destroyModel(uint32_t model) { check(blok_hip_model_destroy(m_ctx, model)); }
+    // drawFrame over the world plus instances: records in hits(), the winning instance per pixel in instanceIds()
+    void drawFrameInstanced(Camera& cam, const std::vector<blok_instance>& instances) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_instanceIds.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_trace_primary_instanced(m_ctx, &c, 0, 0, m_width, m_height, instances.data(), static_cast<uint32_t>(instances.size()),
+                                               m_hits.data(), nullptr, m_instanceIds.data()));
+        cam.cameraChanged = false;
+        ++m_frameIndex;
+    }
+    // picking / line of sight: records and instance ids of explicit rays
+    void traceRaysInstanced(const std::vector<blok_ray>& rays, const std::vector<blok_instance>& instances, std::vector<blok_hit>& outHits,
+                            std::vector<uint32_t>& outInstanceIds) {
+        outHits.resize(rays.size());
+        outInstanceIds.resize(rays.size());
+        check(blok_hip_trace_rays_instanced(m_ctx, rays.data(), rays.size(), instances.data(), static_cast<uint32_t>(instances.size()),
+                                            outHits.data(), outInstanceIds.data()));
+    }
+    const std::vector<uint32_t>& instanceIds() const { return m_instanceIds; }
+
     const std::vector<blok_hit>& hits() const { return m_hits; }     // output accessor (getGLTex analogue)
     unsigned int width() const { return m_width; }
     unsigned int height() const { return m_height; }
@@ -267,6 +294,7 @@ private:
     uint32_t m_frameIndex = 0;
     std::vector<blok_hit> m_hits;
     std::vector<uint32_t> m_pixels;
+    std::vector<uint32_t> m_instanceIds;
 };
 
 // Several devices of one node, one process (blok_hip_multi_*, blok_hip.h): the frame is cut into tile x tile screen tiles dealt

@@ -441,8 +441,64 @@ int blok_hip_set_rt_taa_jitter(blok_hip_ctx* ctx, int enabled);
  * enqueued by the *_device entries). */
 int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
-/* Library/ABI version: (major<<16)|minor. */
+/* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below). */
 uint32_t blok_hip_abi_version(void);
+
+/* ------------------------------------------------------------- instanced voxel models
+ * No reference counterpart yet: the reference's TLAS holds one instance with an identity transform
+ * (blok/src/renderer_raytracing.cpp:142-157) and its todo list asks for "one BLAS per chunk, multiple TLAS instances".
+ *
+ * Model.  A voxel set with material ids, uploaded once and kept in HBM as its own 64-tree in its own local lattice.  It uses the
+ *   world's material table and the world's voxel size (vs).
+ * Instance.  blok_instance below: {model, offset (voxels), axis (a permutation of 0, 1, 2), flip (3 bits)}, 32 bytes.
+ * Ray into local space.  With s_k = -1 if flip bit k is set, else +1, for local axis k:
+ *     o'_k = s_k * fl(o[axis[k]] - offset[axis[k]] * vs),   d'_k = s_k * d[axis[k]],   tmin and tmax unchanged.
+ * Walk.  The transformed ray walks the model's tree by the canonical rule of DESIGN.md §3 (unchanged).
+ * Record back to world space.  t and material_id unchanged; world voxel w[axis[k]] = offset[axis[k]] + v'_k if flip bit k is clear,
+ *   offset[axis[k]] - 1 - v'_k if it is set; local face 2k + n becomes world face 2 * axis[k] + (n XOR flip_k).
+ * Composition.  Candidates in the order: the world, then instance 0, 1, 2, ...; a candidate replaces the current record only if its t
+ *   is strictly smaller.  A tie goes to the world, then to the lowest instance index.  (Each instance walks with tmax = the best t so
+ *   far, and the walk accepts t < tmax: the order falls out of the walk.)
+ * Limits.  Every instance's world box must lie in the int16 lattice of the hit records ([-32768, 32768) on every axis); axis must be a
+ *   permutation, flip < 8, the reserved words zero, the model id one that exists.  The entries with host instance tables fail with
+ *   BLOK_ERR_INVALID_ARG otherwise; the device entries cannot look at their table without a host synchronise, so their kernels skip
+ *   any instance that fails these checks (check a table with blok_hip_check_instances).
+ * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
+ * Scope.  The primary frame and explicit rays only: the path tracer, the sun map, the tile and multi-GPU entries and the post chain stay
+ *   world-only (they never receive an instance table). */
+typedef struct blok_instance {
+    uint32_t model;
+    int32_t  offset[3];   /* voxels, world lattice */
+    uint8_t  axis[3];     /* local axis k is world axis axis[k] */
+    uint8_t  flip;        /* bit k: local axis k runs against world axis axis[k] */
+    uint32_t reserved[3]; /* zero */
+} blok_instance;
+#define BLOK_INSTANCE_NONE 0xFFFFFFFFu
+
+/* Builds a model from n voxels (xyz[3*i..], local lattice; duplicates: the last one wins) and
+ * uploads it (every listed voxel is filled); *out_model is its id (ids are never reused).  Both calls may synchronise the device. */
+int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t* material_ids, size_t n, uint32_t* out_model);
+int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model);
+/* BLOK_OK if every instance of a host table passes the limits above, else BLOK_ERR_INVALID_ARG naming the first that does not. */
+int blok_hip_check_instances(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n_instances);
+
+/* The primary frame of blok_hip_trace_primary_device composed with instances.  The world pass is that entry's launch, unchanged; then,
+ * on the same stream and only if n_instances > 0, a binning kernel (instances per 32x32-pixel bin of the rectangle) and a kernel that
+ * walks each pixel's candidate instances.  instances_dev: n_instances records in device memory, read in stream order (a caller may
+ * change the table every frame without a host synchronise).  Outputs as blok_hip_trace_primary_device plus out_instance_dev (w*h
+ * uint32): any may be NULL, not all.  After the first call at a given size the call allocates nothing and does not synchronise. */
+int blok_hip_trace_primary_instanced_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                            const blok_instance* instances_dev, uint32_t n_instances,
+                                            void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, void* hip_stream);
+/* Blocking form with host arrays (the table is checked first); any output may be NULL, not all. */
+int blok_hip_trace_primary_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                     const blok_instance* instances_host, uint32_t n_instances,
+                                     blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host);
+/* Explicit rays against world plus instances (picking, line of sight, secondary rays): n rays in, n records and/or n instance ids out. */
+int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, const blok_instance* instances_host,
+                                  uint32_t n_instances, blok_hit* out_hits_host, uint32_t* out_instance_host);
+int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev,
+                                         uint32_t n_instances, blok_hit* out_hits_dev, uint32_t* out_instance_dev, void* hip_stream);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference
