@@ -307,7 +307,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 1u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 2u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -361,7 +361,7 @@ int blok_hip_resize(blok_hip_ctx* ctx, uint32_t width, uint32_t height) {
 static void free_stream_scratch(blok_hip_ctx::StreamScratch& sc) {
     for (void* p : {static_cast<void*>(sc.beam), static_cast<void*>(sc.ctl), static_cast<void*>(sc.entries), static_cast<void*>(sc.tile_map),
                     static_cast<void*>(sc.slots), static_cast<void*>(sc.gave_up), static_cast<void*>(sc.list_entries), static_cast<void*>(sc.list_ctl), sc.tail_pool,
-                    static_cast<void*>(sc.inst_bins), static_cast<void*>(sc.inst_hits)})
+                    static_cast<void*>(sc.inst_bins), static_cast<void*>(sc.inst_hits), sc.tlas})
         if (p) (void)hipFree(p);
     if (sc.list_hint) (void)hipHostFree(sc.list_hint);
     sc = blok_hip_ctx::StreamScratch{};
@@ -384,6 +384,7 @@ void blok_hip_destroy(blok_hip_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     free_world(ctx);
     free_models(ctx);
+    if (ctx->rt_instances) (void)hipFree(ctx->rt_instances);
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     free_post(ctx);
     if (ctx->has_volume) blok::gpu_volume_destroy(&ctx->volume);
@@ -807,9 +808,13 @@ int blok_hip_shade_rgba8(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0,
     return BLOK_OK;
 }
 
-// Launch of the path kernel (pre-pass first) for either plane set; `planes` carries the output pointers and prev_view_proj.
-static int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
-                             uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream) {
+}  // extern "C"
+
+// Launch of the path kernel (pre-pass first) for either plane set; `planes` carries the output pointers and prev_view_proj.  With
+// instances (inst->n > 0): the instance BVH is built on the stream first (up to kTlasMax instances; above, the kernel loops over the table),
+// then the instanced path kernel runs without the tail pool; inst->n == 0 is the world-only launch plus the id plane.
+int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst) {
     int rc = check_trace(ctx, cam);
     if (rc != BLOK_OK) return rc;
     if (!rect_inside(ctx, x0, y0, w, h) || !spp || !max_bounces)
@@ -840,7 +845,9 @@ static int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t
     // the bounce rounds' tail pool (path_core.h: shade_pixel): with the rounds taken sample by sample, two bounces or more, rays from the root
     p.tail_pool = nullptr;
     // (from four samples per pixel on: with fewer a wave's pool never fills, and the rays parked wait for the end: 1 spp 0.82 -> 0.93 ms, 4 spp 2.78 -> 2.54)
-    if (ctx->ray_batching >= 3u && max_bounces >= 2u && spp >= 4u && !ctx->path_resume && blok::kBlock == 64) {
+    const bool instanced = inst != nullptr && inst->n != 0u;
+    if (instanced) p.resume_secondary = 0u;                 // (the instanced kernel is built without walk_resume)
+    if (ctx->ray_batching >= 3u && max_bounces >= 2u && spp >= 4u && !ctx->path_resume && blok::kBlock == 64 && !instanced) {
         const size_t bytes = static_cast<size_t>(path_blocks) * blok::kTailCapacity * sizeof(blok::TailRecord);
         auto& scratch = ctx->beam_buffers[stream];             // per launch stream: launches on two streams may be in flight together
         if (bytes > scratch.tail_pool_bytes) {
@@ -851,13 +858,35 @@ static int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t
         p.tail_pool = static_cast<blok::TailRecord*>(scratch.tail_pool);
         p.tail_cap = ctx->tail_cap; p.tail_cap_parked = ctx->tail_cap_parked;
     }
+    blok::TlasScene scene{};
+    if (instanced) {
+        scene.instances = inst->table; scene.n_instances = inst->n; scene.ids = inst->ids;
+        scene.models = ctx->models.d_desc; scene.n_models = static_cast<uint32_t>(ctx->models.desc.size());
+        if (inst->n <= blok::kTlasMax) {
+            auto& scratch = ctx->beam_buffers[stream];
+            const size_t need = blok::tlas_nodes(inst->n);
+            if (need > scratch.n_tlas) {
+                if (scratch.tlas) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(scratch.tlas); scratch.tlas = nullptr; scratch.n_tlas = 0; }
+                BLOK_HIP_TRY(ctx, hipMalloc(&scratch.tlas, need * sizeof(blok::TlasNode)));
+                scratch.n_tlas = need;
+            }
+            scene.nodes = static_cast<const blok::TlasNode*>(scratch.tlas);
+        }
+    }
     if (ctx->timing) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, stream));
+    if (instanced && scene.nodes)
+        blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas), stream);
     if (n_beams) blok::launch_beam(blok::RayMode::Rect, p.trace, n_beams, stream);
-    blok::launch_paths(p, path_blocks, stream);
+    if (instanced) blok::launch_paths_instanced(p, scene, ctx->models.stack_levels, path_blocks, stream);
+    else blok::launch_paths(p, path_blocks, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
+    if (inst != nullptr && !instanced && inst->ids)
+        BLOK_HIP_TRY(ctx, hipMemsetAsync(inst->ids, 0xFF, static_cast<size_t>(w) * h * sizeof(uint32_t), stream));
     if (ctx->timing) { BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_end, stream)); ctx->timed = true; }
     return BLOK_OK;
 }
+
+extern "C" {
 
 int blok_hip_trace_paths_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w,
                                 uint32_t h, uint32_t spp, uint32_t max_bounces, uint32_t frame_index,

@@ -309,4 +309,89 @@ int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, 
     return BLOK_OK;
 }
 
+// ---- path-traced frames with instances (tlas_core.h) ----------------------------------------------------------------------------
+
+int blok_hip_trace_paths_instanced_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                          uint32_t spp, uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev,
+                                          uint32_t n_instances, const blok_gbuffer* planes_dev, uint32_t* out_instance_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad path-trace arguments");
+    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    blok::PathArgs p{};
+    p.color = planes_dev->color; p.world_pos = planes_dev->world_pos;
+    p.normal_roughness = planes_dev->normal_roughness; p.albedo_metallic = planes_dev->albedo_metallic;
+    const PathInstances inst{instances_dev, n_instances, out_instance_dev};
+    return launch_path_frame(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, p, hip_stream, &inst);
+}
+
+int blok_hip_trace_paths_instanced_ref_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                              uint32_t spp, uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev,
+                                              uint32_t n_instances, const float prev_view_proj[16], const blok_gbuffer_ref* planes_dev,
+                                              uint32_t* out_instance_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes_dev || (planes_dev->motion && !prev_view_proj))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad path-trace arguments (a motion plane needs prevViewProj)");
+    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    blok::PathArgs p{};
+    p.color = planes_dev->color; p.world_pos = planes_dev->world_pos;
+    p.normal_roughness_h = planes_dev->normal_roughness; p.albedo_metallic_u8 = planes_dev->albedo_metallic; p.motion_h = planes_dev->motion;
+    if (prev_view_proj) for (int k = 0; k < 16; ++k) p.prev_view_proj[k] = prev_view_proj[k];
+    const PathInstances inst{instances_dev, n_instances, out_instance_dev};
+    return launch_path_frame(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, p, hip_stream, &inst);
+}
+
+int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                   uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_host, uint32_t n_instances,
+                                   const blok_gbuffer* planes_host, uint32_t* out_instance_host) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null planes");
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if (!rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame");
+    rc = check_table(ctx, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    const size_t n = static_cast<size_t>(w) * h, plane_bytes = n * 4 * sizeof(float);
+    // one device block: instances, four planes, ids
+    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
+    unsigned char* d = nullptr;
+    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), inst_bytes + 4 * plane_bytes + n * sizeof(uint32_t)));
+    float* host[4] = {planes_host->color, planes_host->world_pos, planes_host->normal_roughness, planes_host->albedo_metallic};
+    float* dev[4];
+    for (int i = 0; i < 4; ++i) dev[i] = host[i] ? reinterpret_cast<float*>(d + inst_bytes + i * plane_bytes) : nullptr;
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(d + inst_bytes + 4 * plane_bytes);
+    hipError_t e = n_instances ? hipMemcpy(d, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) {
+        const blok_gbuffer planes_dev{dev[0], dev[1], dev[2], dev[3]};
+        rc = blok_hip_trace_paths_instanced_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, reinterpret_cast<const blok_instance*>(d),
+                                                   n_instances, &planes_dev, out_instance_host ? d_ids : nullptr, nullptr);
+        for (int i = 0; i < 4 && rc == BLOK_OK && e == hipSuccess; ++i)
+            if (host[i]) e = hipMemcpy(host[i], dev[i], plane_bytes, hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d);
+    if (rc != BLOK_OK) return rc;
+    if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("trace_paths_instanced: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_dev, uint32_t n_instances, void* out_nodes_host, size_t capacity,
+                              uint32_t* out_count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!n_instances || n_instances > blok::kTlasMax || !instances_dev || !out_nodes_host)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "the tree needs 1 .. kTlasMax instances and an output");
+    const uint32_t count = blok::tlas_nodes(n_instances);
+    if (out_count) *out_count = count;
+    if (capacity < count) return set_error(ctx, BLOK_ERR_INVALID_ARG, "output too small for " + std::to_string(count) + " nodes");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    blok::TlasNode* d = nullptr;
+    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), count * sizeof(blok::TlasNode)));
+    blok::launch_tlas_build(instances_dev, n_instances, ctx->models.d_desc, static_cast<uint32_t>(ctx->models.desc.size()), d, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out_nodes_host, d, count * sizeof(blok::TlasNode), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("build_tlas: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
 }  // extern "C"

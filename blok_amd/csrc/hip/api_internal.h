@@ -84,6 +84,9 @@ struct blok_hip_ctx {
         uint32_t rt_frame = 0;
         blok_camera rt_prev_cam{};
     } post;
+    // blok_hip_draw_frame_rt_instanced: the frame's instance table in device memory (records), grown on demand; outside `post`, which
+    // ensure_post may reallocate after the upload
+    blok_instance* rt_instances = nullptr; size_t n_rt_instances = 0;
     // device-resident dense store (gpu_build.h: GpuVolume)
     blok::GpuVolume volume;
     bool has_volume = false;
@@ -118,6 +121,7 @@ struct blok_hip_ctx {
         void* tail_pool = nullptr; size_t tail_pool_bytes = 0;           // path launches: the bounce rounds' tail pool (path_core.h: TailRecord[blocks][kTailCapacity]), grown on demand
         uint32_t* inst_bins = nullptr; size_t n_inst_bins = 0;          // instanced frames: the binning kernel's lists (instance_core.h: kBinWords words per bin), grown on demand
         blok_hit* inst_hits = nullptr; size_t n_inst_hits = 0;          // instanced frames without a record output: the world records the instance pass reads
+        void* tlas = nullptr; size_t n_tlas = 0;                          // instanced path launches: the instance BVH (tlas_core.h: TlasNode), nodes, grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
     // Longest-first scheduling of the walk for a camera at rest (tile_order.h; rectangle launches of the static forms): every walk wave
@@ -219,6 +223,10 @@ blok::TraceArgs base_args(const blok_hip_ctx* ctx, const blok_camera* cam);
 int prepare_beam(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, uint32_t tiles_of_rank, uint32_t* n_beams);
 int prepare_queue(blok_hip_ctx* ctx, blok::RayMode mode, const blok::TraceArgs& args, hipStream_t stream, uint32_t n_beams, blok::FrameQueue* queue, uint32_t* n_blocks);
 int check_trace(blok_hip_ctx* ctx, const blok_camera* cam);
+// The instances of an instanced path launch (null: world only): a device table of n records and the optional id plane.
+struct PathInstances { const blok_instance* table; uint32_t n; uint32_t* ids; };
+int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst = nullptr);
 // api_launch.hip
 int beam_buffer(blok_hip_ctx* ctx, hipStream_t stream, size_t n, float** out);
 void free_order(blok_hip_ctx* ctx);

@@ -210,8 +210,11 @@ void view_proj_of(const blok_camera& c, float M[16]) {
 
 void blok_camera_view_proj(const blok_camera* cam, float out_view_proj[16]) { if (cam && out_view_proj) view_proj_of(*cam, out_view_proj); }
 
-int blok_hip_draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
-                           const blok_denoise_settings* settings, uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+namespace {
+// blok_hip_draw_frame_rt(_instanced): the path pass (with the device table instances_dev of n records, or world-only when null), then the
+// post chain; one post state and one frame counter for both.
+int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces, const blok_denoise_settings* settings,
+                  const blok_instance* instances_dev, uint32_t n_instances, uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
     int rc = check_trace(ctx, cam);
     if (rc != BLOK_OK) return rc;
     if (!spp || !max_bounces) return set_error(ctx, BLOK_ERR_INVALID_ARG, "spp and bounces must be positive");
@@ -241,7 +244,9 @@ int blok_hip_draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t s
     // (renderer_draw.cpp:313-328 passes the base matrices)
     const float saved_jitter[2] = {ctx->jitter_px[0], ctx->jitter_px[1]};
     if (ctx->rt_taa_jitter) blok::taa_jitter_px(frame, ctx->jitter_px);
-    rc = blok_hip_trace_paths_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, prev_vp, &planes, nullptr);
+    rc = instances_dev ? blok_hip_trace_paths_instanced_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev,
+                                                                   n_instances, prev_vp, &planes, nullptr, nullptr)
+                       : blok_hip_trace_paths_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, prev_vp, &planes, nullptr);
     ctx->jitter_px[0] = saved_jitter[0]; ctx->jitter_px[1] = saved_jitter[1];
     if (rc == BLOK_OK) rc = blok_hip_denoise_ref_device(ctx, &planes, prev_vp, frame, settings, P.rt_denoised, nullptr);
     if (rc == BLOK_OK) rc = blok_hip_taa_device(ctx, P.rt_denoised, nullptr, 0.93f, 0.98f, frame, P.rt_resolved, nullptr);       // renderer_postprocess.hpp:104-106
@@ -254,6 +259,31 @@ int blok_hip_draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t s
     if (out_rgba8_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_rgba8_host, P.rt_final, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     else BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     return BLOK_OK;
+}
+}  // namespace
+
+int blok_hip_draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                           const blok_denoise_settings* settings, uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+    return draw_frame_rt(ctx, cam, spp, max_bounces, settings, nullptr, 0u, out_rgba8_host, out_frame_count);
+}
+
+int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                     const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                     uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    rc = blok_hip_check_instances(ctx, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    // the table in the context's device buffer (the previous frame's call ended with a synchronising copy or a device synchronise)
+    const size_t need = n_instances ? n_instances : 1u;
+    if (ctx->n_rt_instances < need) {
+        if (ctx->rt_instances) (void)hipFree(ctx->rt_instances);
+        ctx->rt_instances = nullptr; ctx->n_rt_instances = 0;
+        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->rt_instances), need * sizeof(blok_instance)));
+        ctx->n_rt_instances = need;
+    }
+    if (n_instances) BLOK_HIP_TRY(ctx, hipMemcpy(ctx->rt_instances, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice));
+    return draw_frame_rt(ctx, cam, spp, max_bounces, settings, ctx->rt_instances, n_instances, out_rgba8_host, out_frame_count);
 }
 
 int blok_hip_post_reset(blok_hip_ctx* ctx) {

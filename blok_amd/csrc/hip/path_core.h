@@ -17,6 +17,7 @@
 #define BLOK_PATH_CORE_H
 
 #include "trace_core.h"
+#include "tlas_core.h"
 #include "half_bits.h"
 
 #if defined(__clang__)
@@ -189,9 +190,13 @@ BLOK_DEV void store_narrow(const PathArgs& P, size_t index, uint32_t px, uint32_
 // kResume: compiled with the anchor machinery (walk_resume); the build without it is the one without its register pressure.
 // kSkyOnly: for a pixel of a tile whose frustum meets no voxel (the caller has checked t0 >= kBeamNone): only the sky path below is compiled, a
 // function of a few registers — in the full one, values spilled at its head were written out by three quarters of a frame's waves for nothing.
-template <bool kResume = true, bool kSkyOnly = false>
+// kInstanced: every ray is composed with the instances of `scene` (tlas_core.h) right after the world walk.  Such a launch
+// runs without the anchor machinery (kResume false), the tail pool and the sky-tile shortcut (the beam pre-pass knows only the world).
+template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false>
 BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t index, uint4* stk, float t0 = 0.0f, uint2* keep_lohi = nullptr, uint32_t* keep_base = nullptr,
-                          [[maybe_unused]] TailRecord* pool = nullptr, [[maybe_unused]] TailAnswer* tail_results = nullptr) {
+                          [[maybe_unused]] TailRecord* pool = nullptr, [[maybe_unused]] TailAnswer* tail_results = nullptr,
+                          [[maybe_unused]] const TlasScene* scene = nullptr) {
+    static_assert(!kInstanced || (!kResume && !kSkyOnly), "instanced launches run without walk_resume and the sky-only build");
     const TraceArgs& A = P.trace;
     const blok_camera& cam = A.cam;
     const V3 cam_pos = v3(cam.pos[0], cam.pos[1], cam.pos[2]);
@@ -208,6 +213,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
         store4(P.normal_roughness, index, 0.0f, 1.0f, 0.0f, 0.0f);
         store4(P.albedo_metallic, index, sky_albedo.x, sky_albedo.y, sky_albedo.z, 0.0f);
         store_narrow(P, index, px, py, sky_pos, 10000.0f, false, v3(0.0f, 1.0f, 0.0f), 0.0f, sky_albedo, 0.0f);
+        if constexpr (kInstanced) { if (scene->ids) scene->ids[index] = kInstanceNone; }
     }
     V3 accumulated = v3(0, 0, 0);
     const V3 sun_dir = sun_direction();
@@ -251,7 +257,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
     // A tile whose frustum meets no voxel (beam.h: the start parameter says "none"; sub-pixel jitter stays inside the grown frustum): every
     // primary ray of every sample misses, so a sample is its camera ray's sky colour — the same sums in the same order as below, without the
     // ray set-up (three divisions), the empty walk and the round's bookkeeping.  Three quarters of the benchmark frame's wave tiles.
-    if (t0 >= kBeamNone && P.max_bounces != 0u) {
+    if (!kInstanced && t0 >= kBeamNone && P.max_bounces != 0u) {        // (an instance may float in such a tile)
         while (s < P.spp) {
             radiance = vadd(radiance, vmul(throughput, sky_color(ray_dir)));                  // :232-235, miss.rmiss
             accumulated = vadd(accumulated, radiance);                                        // :379
@@ -426,6 +432,27 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 for (uint32_t j = 0; j + 2u < A.levels; ++j) { const uint4 c = stk[j * kBlock]; keep_lohi[j * kBlock] = make_uint2(c.x, c.y); keep_base[j * kBlock] = c.z; }
                 anchored = true; stack_is_anchor = true;
             }
+        }
+        if constexpr (kInstanced) {
+            // The instances, on the ray's own interval: the beam pre-pass' start parameter and the sun map's cap describe the world alone.
+            // Primary and bounce rays: the closest hit of world and instances by the composition rule (the world's t bounds the query;
+            // shading reads t, face and material only, so a composed record takes the world hit's place).  Shadow rays: any hit, asked
+            // only when the world walk found nothing, up to the uncapped tmax (:294-296).
+            RayIn q = r;
+            q.tmin = 0.001f;                                                                  // :225, :294
+            if (shadow_phase) {
+                q.tmax = 1000.0f;                                                             // :296
+                if (!hit.found && tlas_any(*scene, A.voxel_size, A.inv_voxel_size, q, stk)) hit.found = true;
+            } else {
+                q.tmax = hit.found ? hit.t : 10000.0f;                                        // :227
+                uint4 rec;
+                const uint32_t won = tlas_closest(*scene, A.voxel_size, A.inv_voxel_size, q, q.tmax, stk, rec);
+                if (won != kInstanceNone) {
+                    hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
+                }
+                if (bounce == 0u && s == 0u && scene->ids) scene->ids[index] = won;          // the first hit's instance (G-buffer)
+            }
+            stack_is_anchor = false;                                                          // the model walks overwrote the stack
         }
 #ifdef BLOK_PATH_CLOCKS
         {   // diagnostic build (scripts/r03/paths_kind_clocks.py): the round's clocks are booked by its first active lane, under the kind of that lane

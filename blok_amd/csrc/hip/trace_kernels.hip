@@ -808,6 +808,38 @@ __global__ __launch_bounds__(64) void sun_map_raise_kernel(const SunMapArgs a, c
 // scratch loads land INSIDE the walk loop (37.2 / 82.6 ms), at 6 (80 VGPRs, 49 spilled) the loop is clean: 29.6 / 67.6; 5: 30.8 / 70.6 (profiles/r04_tail_pool_ab.txt)
 #define BLOK_PATH_WAVES 6
 #endif
+// path_kernel's prologue for path_kernel_instanced: this lane's pixel (rx, ry) of the rectangle, same 16x16 / 8x8 mapping as the trace
+// kernel, and the start parameter t0 of its primary rays (beam.h; 0 = none).  false: the lane has no pixel.  path_kernel keeps these
+// lines inline: called there, the helper moves its SGPR spills (71 -> 73 at kResume false, 99 -> 103 at true), and its code object is
+// kept as it was.  An edit here belongs in path_kernel too.
+__device__ __forceinline__ bool path_pixel(const PathArgs& P, uint32_t tid, uint32_t& rx, uint32_t& ry, float& t0) {
+    const TraceArgs& A = P.trace;
+    const uint32_t wave = tid >> 6, lane = tid & 63u;
+    const uint32_t lx = (wave & 1u) * kWaveW + (lane % kWaveW);
+    const uint32_t ly = (wave >> 1) * kWaveH + (lane / kWaveW);
+    const uint32_t bx_count = (A.w + kTileW - 1u) / kTileW, by_count = (A.h + kTileH - 1u) / kTileH;
+    uint32_t bx, by;
+    if (!block_to_tile(blockIdx.x, gridDim.x, bx_count, by_count, bx, by)) return false;
+    rx = bx * kTileW + lx; ry = by * kTileH + ly;
+    t0 = 0.0f;
+    if (A.beam) {
+        const uint32_t wx = rx - lane % kWaveW, wy = ry - lane / kWaveW;          // the wave's 8x8 pixels start here (wave-uniform, inside the rectangle)
+        t0 = A.beam[__builtin_amdgcn_readfirstlane((wy / A.beam_tile) * A.beam_bx + wx / A.beam_tile)];
+        // The wave tile's OWN start parameter: the same cooperative search over its 8x8 pixels (all 64 lanes, before any leaves), looking
+        // only beyond what the beam tile found.  For one primary ray per pixel it costs what it saves (fine bounds);
+        // here every pixel sends spp primary rays through it.  Exact for the same reason as the beam tile's (beam.h): the frustum is
+        // the tile grown by a pixel, the sub-pixel jitter stays inside.
+        // (from 8 samples per pixel on: 2 spp 1.68 -> 1.82 ms with it, 8 spp 6.06 -> 5.90 (pose A) / 12.51 -> 12.61 (B), 64 spp 46.7 -> 44.5)
+        if (P.fine_beam != 0u && t0 < kBeamNone && P.spp >= 8u) {
+            const uint32_t fx0 = A.x0 + wx, fy0 = A.y0 + wy;
+            const float fine = beam_start(A, static_cast<float>(fx0), static_cast<float>(fy0), static_cast<float>(min(fx0 + kWaveW, A.x0 + A.w)),
+                                          static_cast<float>(min(fy0 + kWaveH, A.y0 + A.h)), lane);
+            t0 = fmaxf(t0, fine);                                                   // (kBeamNone: no ray of this wave tile can hit anything)
+        }
+    }
+    return rx < A.w && ry < A.h;
+}
+
 // kResume: PathArgs::resume_secondary honoured (two kernels, so that the default — off, it measures slower — carries none of its state).
 template <bool kResume>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PATH_WAVES, BLOK_PATH_WAVES))) void path_kernel(const PathArgs P) {
@@ -858,6 +890,58 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PAT
     }
     if (t0 >= kBeamNone && P.max_bounces != 0u) shade_pixel<kResume, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0);      // (wave-uniform)
     else shade_pixel<kResume>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, keep_lohi, keep_base, pool, tail_results);
+}
+
+// The instanced path frame (tlas_core.h): path_kernel<false>'s pixel mapping, every pixel through the full shade_pixel
+// (an instance may float in a tile the beam pre-pass found empty; its primary rays still get the world walk's empty interval), no side
+// area, no tail pool.  The LDS stack has max(world levels - 1, the deepest model's levels - 1) slots per lane.
+// Waves per SIMD of the instanced kernel.  At path_kernel's 6 (80 VGPRs) it spills 130 VGPRs and two reloads land inside the model walk's
+// loop; at 5 (96 VGPRs, 78 spilled) every walk loop (world, closest-hit models, any-hit models) is free of scratch access; at 4 (128 VGPRs,
+// 12 spilled) too.  Measured: DESIGN.md §11.
+#ifndef BLOK_PATH_INSTANCED_WAVES
+#define BLOK_PATH_INSTANCED_WAVES 5
+#endif
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PATH_INSTANCED_WAVES, BLOK_PATH_INSTANCED_WAVES))) void path_kernel_instanced(const PathArgs P, const TlasScene S) {
+    extern __shared__ uint4 lds_stack[];
+    const TraceArgs& A = P.trace;
+    const uint32_t tid = threadIdx.x;
+    uint32_t rx, ry;
+    float t0;
+    if (!path_pixel(P, tid, rx, ry, t0)) return;
+    shade_pixel<false, false, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S);
+}
+
+// One workgroup builds the instance BVH of n <= kTlasMax instances (tlas_core.h): sort keys, a bitonic sort in LDS, the leaves, the refit
+// level by level (each level reads the one below it from global memory behind a fence and a barrier), the header.  No atomics.
+__global__ __launch_bounds__(kTlasBuildThreads) void tlas_build_kernel(const blok_instance* inst, uint32_t n, const ModelDesc* models, uint32_t n_models,
+                                                                       TlasNode* nodes) {
+    __shared__ uint64_t keys[kTlasMax];
+    const uint32_t P = tlas_slots(n), tid = threadIdx.x;
+    for (uint32_t i = tid; i < P; i += kTlasBuildThreads) keys[i] = i < n ? tlas_key(inst, models, n_models, i) : ~0ull;
+    __syncthreads();
+    for (uint32_t size = 2u; size <= P; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0u; stride >>= 1) {
+            for (uint32_t t = tid; t < P / 2u; t += kTlasBuildThreads) {
+                const uint32_t i = 2u * t - (t & (stride - 1u)), j = i + stride;
+                const uint64_t a = keys[i], b = keys[j];
+                if ((a > b) == ((i & size) == 0u)) { keys[i] = b; keys[j] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t j = tid; j < P; j += kTlasBuildThreads) {
+        nodes[P + j] = tlas_leaf(inst, models, P, j, keys[j]);
+        const bool last_usable = tlas_key_usable(keys[j]) && (j + 1u == P || !tlas_key_usable(keys[j + 1u]));
+        if (last_usable) nodes[0] = tlas_header(P, j + 1u);
+        if (j == 0u && !tlas_key_usable(keys[0])) nodes[0] = tlas_header(P, 0u);
+    }
+    __threadfence();
+    __syncthreads();
+    for (uint32_t L = P >> 1; L >= 1u; L >>= 1) {
+        for (uint32_t k = L + tid; k < 2u * L; k += kTlasBuildThreads) nodes[k] = tlas_internal(k, nodes[2u * k], nodes[2u * k + 1u]);
+        __threadfence();
+        __syncthreads();
+    }
 }
 
 __global__ __launch_bounds__(256) void tonemap_kernel(const TonemapArgs T) {
@@ -1100,6 +1184,19 @@ void launch_paths(const PathArgs& args, uint32_t n_blocks, hipStream_t stream) {
         lds += (static_cast<size_t>(levels - 2) * kBlock * (sizeof(uint2) + sizeof(uint32_t)) + 15u) / 16u * 16u;      // the anchors' side area
         hipLaunchKernelGGL(path_kernel<true>, dim3(n_blocks), dim3(kBlock), lds + tail_lds, stream, args);
     } else hipLaunchKernelGGL(path_kernel<false>, dim3(n_blocks), dim3(kBlock), lds + tail_lds, stream, args);
+}
+
+void launch_paths_instanced(const PathArgs& args, const TlasScene& scene, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream) {
+    if (n_blocks == 0) return;
+    const uint32_t levels = args.trace.levels;
+    uint32_t slots = levels > 1 ? levels - 1 : 1;
+    if (stack_slots > slots) slots = stack_slots;
+    hipLaunchKernelGGL(path_kernel_instanced, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene);
+}
+
+void launch_tlas_build(const blok_instance* instances, uint32_t n, const ModelDesc* models, uint32_t n_models, TlasNode* nodes, hipStream_t stream) {
+    if (n == 0u || n > kTlasMax) return;
+    hipLaunchKernelGGL(tlas_build_kernel, dim3(1), dim3(kTlasBuildThreads), 0, stream, instances, n, models, n_models, nodes);
 }
 
 void launch_tonemap(const TonemapArgs& args, hipStream_t stream) {

@@ -463,6 +463,62 @@ class HipTracer:
                                                             _ffi.ptr(hits), _ffi.ptr(ids)))
         return hits, ids
 
+    def trace_paths_instanced(self, cam: np.ndarray, instances: np.ndarray, spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None):
+        """trace_paths over the world plus `instances` (INSTANCE records): the planes dict plus "ids", the instance of each pixel's
+        first hit ((h, w) uint32, INSTANCE_NONE for the world or the sky)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
+        planes = {k: np.zeros((h, w, 4), dtype=np.float32) for k in ("color", "world_pos", "normal_roughness", "albedo_metallic")}
+        planes["ids"] = np.zeros((h, w), dtype=np.uint32)
+        g = GBuffer(*[planes[k].ctypes.data for k in ("color", "world_pos", "normal_roughness", "albedo_metallic")])
+        self._check(self._lib.blok_hip_trace_paths_instanced(self._ctx, _ffi.ptr(cam), x0, y0, w, h, spp, max_bounces, frame_index,
+                                                             _ffi.ptr(inst), len(inst), C.byref(g), _ffi.ptr(planes["ids"])))
+        return planes
+
+    def trace_paths_instanced_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, color_ptr: int = 0, world_pos_ptr: int = 0,
+                                     normal_roughness_ptr: int = 0, albedo_metallic_ptr: int = 0, ids_ptr: int = 0, spp: int = 8,
+                                     max_bounces: int = 2, frame_index: int = 0, rect=None, stream: int = 0):
+        """Asynchronous: device instance table, float4 device planes and id plane (any may be 0)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        g = GBuffer(color_ptr, world_pos_ptr, normal_roughness_ptr, albedo_metallic_ptr)
+        self._check(self._lib.blok_hip_trace_paths_instanced_device(self._ctx, _ffi.ptr(cam), x0, y0, w, h, spp, max_bounces, frame_index,
+                                                                    C.c_void_p(instances_ptr), int(n_instances), C.byref(g),
+                                                                    C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def trace_paths_instanced_ref_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, color_ptr: int = 0, world_pos_ptr: int = 0,
+                                         normal_roughness_h_ptr: int = 0, albedo_metallic_u8_ptr: int = 0, motion_h_ptr: int = 0,
+                                         prev_view_proj=None, ids_ptr: int = 0, spp: int = 8, max_bounces: int = 2, frame_index: int = 0,
+                                         rect=None, stream: int = 0):
+        """trace_paths_ref_device over the world plus a device instance table; ids_ptr: the id plane (may be 0)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        g = _ffi.GBufferRef(color_ptr, world_pos_ptr, normal_roughness_h_ptr, albedo_metallic_u8_ptr, motion_h_ptr)
+        m = None if prev_view_proj is None else (C.c_float * 16)(*[float(v) for v in np.asarray(prev_view_proj, dtype=np.float32).reshape(-1)])
+        self._check(self._lib.blok_hip_trace_paths_instanced_ref_device(self._ctx, _ffi.ptr(cam), x0, y0, w, h, spp, max_bounces, frame_index,
+                                                                        C.c_void_p(instances_ptr), int(n_instances), m, C.byref(g),
+                                                                        C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def draw_frame_rt_instanced(self, cam: np.ndarray, instances: np.ndarray, spp: int = 8, max_bounces: int = 2, settings=None):
+        """draw_frame_rt with the path pass over the world plus `instances`: (RGBA8 (h, w) uint32, frames rendered so far)."""
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        frames = C.c_uint32()
+        self._check(self._lib.blok_hip_draw_frame_rt_instanced(self._ctx, _ffi.ptr(cam), spp, max_bounces,
+                                                               C.byref(settings) if settings is not None else None, _ffi.ptr(inst), len(inst),
+                                                               _ffi.ptr(out), C.byref(frames)))
+        return out, frames.value
+
+    def debug_build_tlas(self, instances_ptr: int, n_instances: int) -> np.ndarray:
+        """The instance BVH of a device table (tlas_core.h: TlasNode), as an (nodes, 8) int32 array."""
+        count = C.c_uint32()
+        cap = 2 * (1 << max(0, int(n_instances) - 1).bit_length())
+        out = np.zeros((cap, 8), dtype=np.int32)
+        self._check(self._lib.blok_hip_debug_build_tlas(self._ctx, C.c_void_p(instances_ptr), int(n_instances), _ffi.ptr(out), cap, C.byref(count)))
+        return out[:count.value]
+
     def trace_paths(self, cam: np.ndarray, spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None):
         """raygen.rgen's sample/bounce loop: dict of (h, w, 4) float32 planes
         color, world_pos, normal_roughness, albedo_metallic."""

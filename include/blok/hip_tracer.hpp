@@ -243,6 +243,24 @@ public:
         cam.cameraChanged = false;
         return m_pixels;
     }
+    // drawFrameRT over the world plus instances (the same post state and frame counter)
+    const std::vector<uint32_t>& drawFrameRTInstanced(Camera& cam, const std::vector<blok_instance>& instances, uint32_t sampleCount = 8,
+                                                      uint32_t maxBounces = 2) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_pixels.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_draw_frame_rt_instanced(m_ctx, &c, sampleCount, maxBounces, nullptr, instances.data(), static_cast<uint32_t>(instances.size()),
+                                               m_pixels.data(), &m_frameIndex));
+        cam.cameraChanged = false;
+        return m_pixels;
+    }
+    // path-traced planes (host, any may be null) over the world plus instances; the first hit's instance per pixel in instanceIds()
+    void tracePathsInstanced(Camera& cam, const std::vector<blok_instance>& instances, const blok_gbuffer& planesHost, uint32_t sampleCount = 8,
+                             uint32_t maxBounces = 2, uint32_t frameIndex = 0) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_instanceIds.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_trace_paths_instanced(m_ctx, &c, 0, 0, m_width, m_height, sampleCount, maxBounces, frameIndex, instances.data(),
+                                             static_cast<uint32_t>(instances.size()), &planesHost, m_instanceIds.data()));
+    }
     void sharpen(const uint32_t* rgba8Dev, uint32_t* outRgba8Dev, float strength = 0.5f, void* stream = nullptr) {
         check(blok_hip_sharpen_device(m_ctx, rgba8Dev, strength, outRgba8Dev, stream));
     }

@@ -441,7 +441,7 @@ int blok_hip_set_rt_taa_jitter(blok_hip_ctx* ctx, int enabled);
  * enqueued by the *_device entries). */
 int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
-/* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below). */
+/* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -464,8 +464,9 @@ uint32_t blok_hip_abi_version(void);
  *   BLOK_ERR_INVALID_ARG otherwise; the device entries cannot look at their table without a host synchronise, so their kernels skip
  *   any instance that fails these checks (check a table with blok_hip_check_instances).
  * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
- * Scope.  The primary frame and explicit rays only: the path tracer, the sun map, the tile and multi-GPU entries and the post chain stay
- *   world-only (they never receive an instance table). */
+ * Scope.  The primary frame, explicit rays and the path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced
+ *   below); the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay world-only (they never receive an
+ *   instance table). */
 typedef struct blok_instance {
     uint32_t model;
     int32_t  offset[3];   /* voxels, world lattice */
@@ -499,6 +500,32 @@ int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, 
                                   uint32_t n_instances, blok_hit* out_hits_host, uint32_t* out_instance_host);
 int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev,
                                          uint32_t n_instances, blok_hit* out_hits_dev, uint32_t* out_instance_dev, void* hip_stream);
+
+/* Path-traced frames with instances: blok_hip_trace_paths* with every ray of the path loop composed with the instances by the rule above.
+ *   Primary and bounce rays: the closest hit of world and instances.  Shadow rays: any hit; the instances are asked only when the world
+ *   walk found nothing, and over the shadow ray's whole interval (the sun map caps the world walk alone).  The G-buffer is the composed
+ *   first hit (sample 0, bounce 0); out_instance (w*h uint32, may be NULL) holds that hit's instance or BLOK_INSTANCE_NONE.
+ * Each launch first builds a BVH over the table on the stream (one workgroup; up to 4096 instances, above that every ray loops over the
+ *   table — slower, same result), so the table may change every frame without a host synchronise.  Off for such launches: the bounce
+ *   rounds' tail pool (ray batching mode 3 behaves as mode 2) and blok_hip_set_path_start's resume.  Motion vectors stay camera-only: an
+ *   instance that moves between frames gets no object motion, so the denoiser and TAA may ghost behind it.
+ * n_instances == 0 is blok_hip_trace_paths*'s launch, unchanged, plus out_instance filled with BLOK_INSTANCE_NONE.  Device entries skip
+ *   instances that fail the limits; the host entries check the table first. */
+int blok_hip_trace_paths_instanced_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                          uint32_t spp, uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev,
+                                          uint32_t n_instances, const blok_gbuffer* planes_dev, uint32_t* out_instance_dev, void* hip_stream);
+int blok_hip_trace_paths_instanced_ref_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                              uint32_t spp, uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev,
+                                              uint32_t n_instances, const float prev_view_proj[16], const blok_gbuffer_ref* planes_dev,
+                                              uint32_t* out_instance_dev, void* hip_stream);
+/* Blocking form with host planes and a host table (checked first). */
+int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                   uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_host, uint32_t n_instances,
+                                   const blok_gbuffer* planes_host, uint32_t* out_instance_host);
+/* blok_hip_draw_frame_rt with the path pass above (host table, checked first): the same post state and frame counter. */
+int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                     const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                     uint32_t* out_rgba8_host, uint32_t* out_frame_count);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -184,6 +184,11 @@ int blok_hip_set_list_classes(blok_hip_ctx* ctx, int enabled);
  * call takes the dense exchange over blok_hip_multi_transport); 0 = back to what the node really offers.  The frames are the same. */
 int blok_hip_multi_debug_deny_peer_access(blok_hip_multi* m, int deny);
 
+/* The instance BVH of the instanced path frame (tlas_core.h: TlasNode, 32 bytes each) for a device table of 1 .. 4096 instances: built on
+ * the default stream and downloaded.  *out_count = the node count (header included); fails if capacity (nodes) is smaller. */
+int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_dev, uint32_t n_instances, void* out_nodes_host, size_t capacity,
+                              uint32_t* out_count);
+
 #ifdef __cplusplus
 }
 #endif
