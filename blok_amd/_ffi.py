@@ -264,6 +264,14 @@ HIP_SYMBOLS = {
     "blok_hip_trace_paths_instanced": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.POINTER(GBuffer), C.c_void_p]),
     "blok_hip_draw_frame_rt_instanced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                    C.POINTER(C.c_uint32)]),
+    "blok_hip_instance_motion_device": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                                       C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blok_hip_denoise_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_hip_denoise_instanced_ref_device": (C.c_int, [C.c_void_p, C.POINTER(GBufferRef), C.POINTER(C.c_float), C.c_uint32, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_hip_draw_frame_rt_instanced_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                          C.c_void_p, C.POINTER(C.c_uint32)]),
     "blok_hip_debug_build_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 

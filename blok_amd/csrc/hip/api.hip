@@ -22,7 +22,8 @@ void free_post(blok_hip_ctx* ctx) {
     for (void* p : {static_cast<void*>(P.motion), static_cast<void*>(P.variance), static_cast<void*>(P.ping), static_cast<void*>(P.pong), static_cast<void*>(P.widen),
                     static_cast<void*>(P.rt_planes[0]), static_cast<void*>(P.rt_planes[1]), static_cast<void*>(P.rt_planes[2]), static_cast<void*>(P.rt_planes[3]),
                     static_cast<void*>(P.rt_denoised), static_cast<void*>(P.rt_resolved), static_cast<void*>(P.rt_ldr), static_cast<void*>(P.rt_final),
-                    static_cast<void*>(P.rt_normal_roughness_h), static_cast<void*>(P.rt_motion_h), static_cast<void*>(P.rt_albedo_metallic_u8)})
+                    static_cast<void*>(P.rt_normal_roughness_h), static_cast<void*>(P.rt_motion_h), static_cast<void*>(P.rt_albedo_metallic_u8),
+                    static_cast<void*>(P.rt_ids)})
         if (p) (void)hipFree(p);
     P = blok_hip_ctx::Post{};
 }
@@ -307,7 +308,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 2u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 3u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -385,6 +386,7 @@ void blok_hip_destroy(blok_hip_ctx* ctx) {
     free_world(ctx);
     free_models(ctx);
     if (ctx->rt_instances) (void)hipFree(ctx->rt_instances);
+    if (ctx->rt_prev_instances) (void)hipFree(ctx->rt_prev_instances);
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     free_post(ctx);
     if (ctx->has_volume) blok::gpu_volume_destroy(&ctx->volume);

@@ -105,6 +105,18 @@ blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs&
 }
 
 }  // namespace
+
+blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
+                                 uint32_t n_prev) {
+    blok::MotionTables M{};
+    M.ids = ids;
+    M.cur = cur; M.n_cur = n_cur;
+    M.prev = prev; M.n_prev = n_prev;
+    M.models = ctx->models.d_desc; M.n_models = ctx->models.d_desc ? static_cast<uint32_t>(ctx->models.desc.size()) : 0u;
+    M.vs = ctx->world_voxel_size;
+    return M;
+}
+
 }  // namespace blok_api
 
 using namespace blok_api;
@@ -372,6 +384,30 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
     (void)hipFree(d);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("trace_paths_instanced: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+// ---- object motion of moving instances (instance_motion.h) -----------------------------------------------------------------------
+
+int blok_hip_instance_motion_device(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev,
+                                    const uint32_t* instance_ids_dev, const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev,
+                                    uint32_t n_prev, const float prev_view_proj[16], uint16_t* motion_h_dev, float* motion_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!world_pos_dev || !instance_ids_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance motion: world position and id planes are required");
+    if ((n_cur && !cur_dev) || (n_prev && !prev_dev)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    if (!motion_h_dev && !motion_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance motion: no motion output");
+    if (!rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame");
+    if (!prev_view_proj) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance motion: prevViewProj is required");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!n_cur || !n_prev) return BLOK_OK;                       // nothing is tracked
+    blok::InstanceMotionArgs a{};
+    a.m = motion_tables(ctx, instance_ids_dev, cur_dev, n_cur, prev_dev, n_prev);
+    a.world_pos = world_pos_dev;
+    a.x0 = x0; a.y0 = y0; a.w = w; a.h = h; a.frame_w = ctx->width; a.frame_h = ctx->height;
+    for (int k = 0; k < 16; ++k) a.prev_view_proj[k] = prev_view_proj[k];
+    a.motion_h = motion_h_dev; a.motion = motion_dev;
+    blok::launch_instance_motion(a, static_cast<hipStream_t>(hip_stream));
+    BLOK_HIP_TRY(ctx, hipGetLastError());
     return BLOK_OK;
 }
 

@@ -83,10 +83,15 @@ struct blok_hip_ctx {
         uint32_t *rt_ldr = nullptr, *rt_final = nullptr;
         uint32_t rt_frame = 0;
         blok_camera rt_prev_cam{};
+        // blok_hip_draw_frame_rt_instanced_motion: the first-hit instance plane, and the number of records of the previous frame's table
+        // (rt_prev_instances; 0 after a reset or a frame without object motion)
+        uint32_t* rt_ids = nullptr;
+        uint32_t rt_prev_n = 0;
     } post;
-    // blok_hip_draw_frame_rt_instanced: the frame's instance table in device memory (records), grown on demand; outside `post`, which
-    // ensure_post may reallocate after the upload
+    // blok_hip_draw_frame_rt_instanced(_motion): the frame's instance table in device memory (records), grown on demand, and the previous
+    // frame's (the motion entry swaps the two after each frame); outside `post`, which ensure_post may reallocate after the upload
     blok_instance* rt_instances = nullptr; size_t n_rt_instances = 0;
+    blok_instance* rt_prev_instances = nullptr; size_t n_rt_prev_instances = 0;
     // device-resident dense store (gpu_build.h: GpuVolume)
     blok::GpuVolume volume;
     bool has_volume = false;
@@ -236,6 +241,9 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
                  const blok::TileFrames* frames = nullptr);
 // api_instances.hip
 void free_models(blok_hip_ctx* ctx);
+// The id plane and both tables of an object-motion pass (instance_motion.h) with the context's model store and voxel size.
+blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
+                                 uint32_t n_prev);
 void forget_device_activity(const blok_hip_ctx* ctx, bool one_stream = false, hipStream_t stream = nullptr);
 bool rect_inside(const blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
 // The root's assembly of a sparse exchange (blok_hip_scatter_*_tile_frames_device): the ranks' buffers either side by side in

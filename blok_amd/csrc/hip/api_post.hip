@@ -56,9 +56,10 @@ void blok_denoise_settings_default(blok_denoise_settings* s) {       // renderer
 }
 
 // One frame through temporal accumulation, variance and the a-trous iterations; the frame's planes come in `in` (float4 planes,
-// or the reference-format halves of normal + roughness / motion).
+// or the reference-format halves of normal + roughness / motion).  inst: the id plane and tables of a frame with instances (the
+// instanced temporal pass), or null.
 static int denoise_frame(blok_hip_ctx* ctx, const blok::TemporalArgs& in, const float prev_view_proj[16], uint32_t frame_count,
-                         const blok_denoise_settings* settings, float* out_color_dev, void* hip_stream) {
+                         const blok_denoise_settings* settings, float* out_color_dev, void* hip_stream, const blok::MotionTables* inst = nullptr) {
     if (!in.color || !in.world_pos || (!in.normal_roughness && !in.normal_roughness_h) || !prev_view_proj || !out_color_dev)
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: colour, world position and normal planes, prevViewProj and an output are required");
     blok_denoise_settings def;
@@ -82,7 +83,13 @@ static int denoise_frame(blok_hip_ctx* ctx, const blok::TemporalArgs& in, const 
     t.prev_hist_len = P.hist_len[prev]; t.prev_unit_normals = P.unit_normals[prev];
     t.out_color = P.hist_color[cur]; t.out_moments = P.moments[cur]; t.hist_world_pos = P.world_pos[cur];
     t.out_hist_len = P.hist_len[cur]; t.unit_normals = P.unit_normals[cur]; t.motion = P.motion;
-    blok::launch_temporal(t, stream);
+    if (inst) {
+        blok::TemporalInstancedArgs ti{};
+        ti.t = t; ti.m = *inst;
+        blok::launch_temporal_instanced(ti, stream);
+    } else {
+        blok::launch_temporal(t, stream);
+    }
 
     blok::VarianceArgs v{};
     v.f = f;
@@ -124,6 +131,41 @@ int blok_hip_denoise_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_ref* plane
     blok::TemporalArgs t{};
     t.color = planes->color; t.world_pos = planes->world_pos; t.normal_roughness_h = planes->normal_roughness; t.motion_in_h = planes->motion;
     return denoise_frame(ctx, t, prev_view_proj, frame_count, settings, out_color_dev, hip_stream);
+}
+
+// The instanced entries' own arguments (a null id plane or table is refused before any other check).
+static int check_instanced(blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev, uint32_t n_prev) {
+    if (!ids) return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: null instance id plane");
+    if ((n_cur && !cur) || (n_prev && !prev)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    return BLOK_OK;
+}
+
+int blok_hip_denoise_instanced_device(blok_hip_ctx* ctx, const blok_gbuffer* planes, const float* motion_dev, const float prev_view_proj[16],
+                                      uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* instance_ids_dev,
+                                      const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                      float* out_color_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: null planes");
+    const int rc = check_instanced(ctx, instance_ids_dev, cur_dev, n_cur, prev_dev, n_prev);
+    if (rc != BLOK_OK) return rc;
+    blok::TemporalArgs t{};
+    t.color = planes->color; t.world_pos = planes->world_pos; t.normal_roughness = planes->normal_roughness; t.motion_in = motion_dev;
+    const blok::MotionTables M = motion_tables(ctx, instance_ids_dev, cur_dev, n_cur, prev_dev, n_prev);
+    return denoise_frame(ctx, t, prev_view_proj, frame_count, settings, out_color_dev, hip_stream, &M);
+}
+
+int blok_hip_denoise_instanced_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_ref* planes, const float prev_view_proj[16],
+                                          uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* instance_ids_dev,
+                                          const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                          float* out_color_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: null planes");
+    const int rc = check_instanced(ctx, instance_ids_dev, cur_dev, n_cur, prev_dev, n_prev);
+    if (rc != BLOK_OK) return rc;
+    blok::TemporalArgs t{};
+    t.color = planes->color; t.world_pos = planes->world_pos; t.normal_roughness_h = planes->normal_roughness; t.motion_in_h = planes->motion;
+    const blok::MotionTables M = motion_tables(ctx, instance_ids_dev, cur_dev, n_cur, prev_dev, n_prev);
+    return denoise_frame(ctx, t, prev_view_proj, frame_count, settings, out_color_dev, hip_stream, &M);
 }
 
 int blok_hip_denoise_state(blok_hip_ctx* ctx, float* history_color, float* moments, float* history_length, float* variance, float* motion) {
@@ -211,10 +253,13 @@ void view_proj_of(const blok_camera& c, float M[16]) {
 void blok_camera_view_proj(const blok_camera* cam, float out_view_proj[16]) { if (cam && out_view_proj) view_proj_of(*cam, out_view_proj); }
 
 namespace {
-// blok_hip_draw_frame_rt(_instanced): the path pass (with the device table instances_dev of n records, or world-only when null), then the
-// post chain; one post state and one frame counter for both.
+// blok_hip_draw_frame_rt(_instanced(_motion)): the path pass (with the device table instances_dev of n records, or world-only when null), then
+// the post chain; one post state and one frame counter for all.  object_motion (and n_instances > 0): the path pass also writes the id
+// plane, the motion of tracked instance pixels is corrected against the previous frame's table (ctx->rt_prev_instances, rt_prev_n
+// records) and the temporal pass is the instanced one.
 int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces, const blok_denoise_settings* settings,
-                  const blok_instance* instances_dev, uint32_t n_instances, uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+                  const blok_instance* instances_dev, uint32_t n_instances, uint32_t* out_rgba8_host, uint32_t* out_frame_count,
+                  bool object_motion = false) {
     int rc = check_trace(ctx, cam);
     if (rc != BLOK_OK) return rc;
     if (!spp || !max_bounces) return set_error(ctx, BLOK_ERR_INVALID_ARG, "spp and bounces must be positive");
@@ -235,6 +280,11 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
         if (rc != BLOK_OK) { free_post(ctx); return rc; }
         P.rt_frame = 0;
     }
+    const bool motion = object_motion && instances_dev && n_instances;
+    if (motion && !P.rt_ids) {
+        rc = post_alloc(ctx, &P.rt_ids, n);
+        if (rc != BLOK_OK) { free_post(ctx); return rc; }
+    }
     const uint32_t frame = P.rt_frame;
     float prev_vp[16];
     view_proj_of(frame ? P.rt_prev_cam : *cam, prev_vp);            // Denoiser::updatePreviousFrameData: last frame's matrices
@@ -245,16 +295,27 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
     const float saved_jitter[2] = {ctx->jitter_px[0], ctx->jitter_px[1]};
     if (ctx->rt_taa_jitter) blok::taa_jitter_px(frame, ctx->jitter_px);
     rc = instances_dev ? blok_hip_trace_paths_instanced_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev,
-                                                                   n_instances, prev_vp, &planes, nullptr, nullptr)
+                                                                   n_instances, prev_vp, &planes, motion ? P.rt_ids : nullptr, nullptr)
                        : blok_hip_trace_paths_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, prev_vp, &planes, nullptr);
     ctx->jitter_px[0] = saved_jitter[0]; ctx->jitter_px[1] = saved_jitter[1];
-    if (rc == BLOK_OK) rc = blok_hip_denoise_ref_device(ctx, &planes, prev_vp, frame, settings, P.rt_denoised, nullptr);
+    if (motion) {
+        const uint32_t n_prev = P.rt_prev_n;
+        if (rc == BLOK_OK)
+            rc = blok_hip_instance_motion_device(ctx, 0, 0, ctx->width, ctx->height, P.rt_planes[1], P.rt_ids, instances_dev, n_instances,
+                                                 ctx->rt_prev_instances, n_prev, prev_vp, P.rt_motion_h, nullptr, nullptr);
+        if (rc == BLOK_OK)
+            rc = blok_hip_denoise_instanced_ref_device(ctx, &planes, prev_vp, frame, settings, P.rt_ids, instances_dev, n_instances,
+                                                       ctx->rt_prev_instances, n_prev, P.rt_denoised, nullptr);
+    } else if (rc == BLOK_OK) {
+        rc = blok_hip_denoise_ref_device(ctx, &planes, prev_vp, frame, settings, P.rt_denoised, nullptr);
+    }
     if (rc == BLOK_OK) rc = blok_hip_taa_device(ctx, P.rt_denoised, nullptr, 0.93f, 0.98f, frame, P.rt_resolved, nullptr);       // renderer_postprocess.hpp:104-106
     if (rc == BLOK_OK) rc = blok_hip_tonemap_device(ctx, P.rt_resolved, static_cast<uint32_t>(n), 1.0f, 1.15f, 1, P.rt_ldr, nullptr);   // :110-113
     if (rc == BLOK_OK) rc = blok_hip_sharpen_device(ctx, P.rt_ldr, 0.5f, P.rt_final, nullptr);                                     // :117-118
     if (rc != BLOK_OK) return rc;
     P.rt_prev_cam = *cam;
     P.rt_frame = frame + 1;
+    P.rt_prev_n = object_motion ? n_instances : 0u;        // the table itself: the motion entry swaps the buffers after this call
     if (out_frame_count) *out_frame_count = P.rt_frame;
     if (out_rgba8_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_rgba8_host, P.rt_final, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     else BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
@@ -267,14 +328,14 @@ int blok_hip_draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t s
     return draw_frame_rt(ctx, cam, spp, max_bounces, settings, nullptr, 0u, out_rgba8_host, out_frame_count);
 }
 
-int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
-                                     const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
-                                     uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+namespace {
+// The host table, checked, in the context's device buffer rt_instances (the previous frame's call ended with a synchronising copy or a
+// device synchronise).
+int upload_rt_table(blok_hip_ctx* ctx, const blok_camera* cam, const blok_instance* instances_host, uint32_t n_instances) {
     int rc = check_trace(ctx, cam);
     if (rc != BLOK_OK) return rc;
     rc = blok_hip_check_instances(ctx, instances_host, n_instances);
     if (rc != BLOK_OK) return rc;
-    // the table in the context's device buffer (the previous frame's call ended with a synchronising copy or a device synchronise)
     const size_t need = n_instances ? n_instances : 1u;
     if (ctx->n_rt_instances < need) {
         if (ctx->rt_instances) (void)hipFree(ctx->rt_instances);
@@ -283,7 +344,29 @@ int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, 
         ctx->n_rt_instances = need;
     }
     if (n_instances) BLOK_HIP_TRY(ctx, hipMemcpy(ctx->rt_instances, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice));
+    return BLOK_OK;
+}
+}  // namespace
+
+int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                     const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                     uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+    const int rc = upload_rt_table(ctx, cam, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
     return draw_frame_rt(ctx, cam, spp, max_bounces, settings, ctx->rt_instances, n_instances, out_rgba8_host, out_frame_count);
+}
+
+int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                            const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                            uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+    const int rc = upload_rt_table(ctx, cam, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    const int drawn = draw_frame_rt(ctx, cam, spp, max_bounces, settings, ctx->rt_instances, n_instances, out_rgba8_host, out_frame_count, true);
+    if (drawn != BLOK_OK) return drawn;
+    // this frame's table becomes the previous one (the frame ended with a synchronise; the next upload overwrites the older buffer)
+    std::swap(ctx->rt_instances, ctx->rt_prev_instances);
+    std::swap(ctx->n_rt_instances, ctx->n_rt_prev_instances);
+    return BLOK_OK;
 }
 
 int blok_hip_post_reset(blok_hip_ctx* ctx) {

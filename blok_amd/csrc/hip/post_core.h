@@ -27,6 +27,7 @@
 #define BLOK_POST_CORE_H
 
 #include "path_core.h"
+#include "instance_motion.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -115,7 +116,12 @@ BLOK_DEV F4 load_nr16(const TemporalArgs& T, size_t i) {
     return r;
 }
 
-BLOK_DEV void temporal_pixel(const TemporalArgs& T, int cx, int cy) {
+// kInstanced (temporal_pixel_instanced below): the pixels whose first hit is an instance (M->ids) are compared with the history where their
+// surface point was one frame earlier (instance_motion.h): for a tracked instance, the motion when no plane is given is the object
+// motion, and p_prev / n_prev take the place of world / normal in the small-motion reprojection, pos_ok and normal_ok; an untracked
+// instance's pixels use no history.  Every other pixel runs the code of temporal_pixel.
+template <bool kInstanced>
+BLOK_DEV void temporal_body(const TemporalArgs& T, [[maybe_unused]] const MotionTables* M, int cx, int cy) {
     const int w = static_cast<int>(T.f.w), h = static_cast<int>(T.f.h);
     const size_t i = static_cast<size_t>(cy) * w + cx;
     const V3 current = load3(T.color, i);
@@ -130,32 +136,48 @@ BLOK_DEV void temporal_pixel(const TemporalArgs& T, int cx, int cy) {
     store4(T.unit_normals, i, normal, nr.w);
     store4(T.hist_world_pos, i, world, depth);
 
+    // where the history of this surface point is looked for: the point itself, or for an instance its place one frame earlier
+    V3 was = world, was_normal = normal;
+    bool history_usable = true;
+    if constexpr (kInstanced) {
+        const uint32_t id = M->ids[i];
+        if (id != kInstanceNone) {
+            if (instance_tracked(*M, id)) {
+                const blok_instance C = M->cur[id], P = M->prev[id];
+                was = map_point(C, P, M->vs, world);
+                was_normal = map_normal(C, P, normal);
+            } else {
+                history_usable = false;
+            }
+        }
+    }
+
     // motion vector (raygen.rgen:409-413), held as half2
     float mu = 0.0f, mv = 0.0f;
     if (T.motion_in_h) { mu = h2f(T.motion_in_h[2 * i]); mv = h2f(T.motion_in_h[2 * i + 1]); }
     else if (T.motion_in) { mu = T.motion_in[2 * i]; mv = T.motion_in[2 * i + 1]; }
-    else if (depth < 9999.0f) { float pu, pv; project_prev(T.f.prev_view_proj, world, pu, pv); mu = cu - pu; mv = cv - pv; }
+    else if (depth < 9999.0f) { float pu, pv; project_prev(T.f.prev_view_proj, was, pu, pv); mu = cu - pu; mv = cv - pv; }
     const uint16_t hu = f2h(mu), hv = f2h(mv);
     T.motion[2 * i] = hu; T.motion[2 * i + 1] = hv;
     mu = h2f(hu); mv = h2f(hv);
 
     float pu, pv;                                                                         // :217-226
     if (rn_sqrt(mu * mu + mv * mv) > 0.0001f) { pu = cu - mu; pv = cv - mv; }
-    else project_prev(T.f.prev_view_proj, world, pu, pv);
+    else project_prev(T.f.prev_view_proj, was, pu, pv);
 
     V3 out = current;                                                                     // :228-232
     const float lum = lum709(current);
     float m1o = lum, m2o = lum * lum, hist_len = 1.0f;
 
-    if (pu >= 0.0f && pu <= 1.0f && pv >= 0.0f && pv <= 1.0f && T.f.frame_count > 0u) {   // :235-237
+    if (pu >= 0.0f && pu <= 1.0f && pv >= 0.0f && pv <= 1.0f && T.f.frame_count > 0u && history_usable) {   // :235-237
         const V3 history = bilinear3(T.prev_color, w, h, pu, pv);
         const int px = clampi(static_cast<int>(pu * static_cast<float>(w)), 0, w - 1), py = clampi(static_cast<int>(pv * static_cast<float>(h)), 0, h - 1);
         const size_t p = static_cast<size_t>(py) * w + px;
         const F4 pwp = load4(T.prev_world_pos, p);
         const V3 prev_normal = load3(T.prev_unit_normals, p);
         const bool depth_ok = fabsf(depth - pwp.w) < T.f.s.depth_threshold * depth + 0.5f;              // :252-255
-        const bool normal_ok = vdot(normal, prev_normal) > T.f.s.normal_threshold;                       // :258-259
-        const bool pos_ok = vlength(vsub(world, xyz(pwp))) < 2.0f;                                       // :262-264
+        const bool normal_ok = vdot(was_normal, prev_normal) > T.f.s.normal_threshold;                   // :258-259
+        const bool pos_ok = vlength(vsub(was, xyz(pwp))) < 2.0f;                                         // :262-264
         if (depth_ok && normal_ok && pos_ok) {
             // neighbourhood statistics in YCoCg over the 3x3 pixels on the same surface (:120-193)
             // (the nine taps' planes are fetched before any is used: memory-level parallelism, as in variance_pixel)
@@ -218,6 +240,40 @@ BLOK_DEV void temporal_pixel(const TemporalArgs& T, int cx, int cy) {
     store4(T.out_color, i, v3(clampf(out.x, 0.0f, 100.0f), clampf(out.y, 0.0f, 100.0f), clampf(out.z, 0.0f, 100.0f)), 1.0f);
     T.out_moments[2 * i] = clampf(m1o, 0.0f, 10000.0f); T.out_moments[2 * i + 1] = clampf(m2o, 0.0f, 10000.0f);
     T.out_hist_len[i] = f2h(hist_len);
+}
+
+BLOK_DEV void temporal_pixel(const TemporalArgs& T, int cx, int cy) { temporal_body<false>(T, nullptr, cx, cy); }
+
+// The temporal pass of a frame with instances (blok_hip_denoise_instanced*): ids, tables and models in `m`, the id plane full-frame.
+struct TemporalInstancedArgs {
+    TemporalArgs t;
+    MotionTables m;
+};
+BLOK_DEV void temporal_pixel_instanced(const TemporalInstancedArgs& A, int cx, int cy) { temporal_body<true>(A.t, &A.m, cx, cy); }
+
+// ---------------------------------------------------------------------------------------------- object motion
+// blok_hip_instance_motion_device: the motion of the pixels of a rectangle whose first hit is a tracked instance becomes its object motion
+// (instance_motion.h); every other pixel of the planes is left as it is.  Planes and the id plane: w x h, the rectangle's own.
+struct InstanceMotionArgs {
+    MotionTables m;
+    const float* world_pos;            // float4
+    uint32_t x0, y0, w, h, frame_w, frame_h;
+    float prev_view_proj[16];
+    uint16_t* motion_h;                // RG16F, may be null
+    float* motion;                     // float2, may be null
+};
+BLOK_DEV void instance_motion_pixel(const InstanceMotionArgs& A, int x, int y) {
+    const size_t i = static_cast<size_t>(y) * A.w + x;
+    const uint32_t id = A.m.ids[i];
+    if (id == kInstanceNone || !instance_tracked(A.m, id)) return;
+    const V3 was = map_point(A.m.cur[id], A.m.prev[id], A.m.vs, load3(A.world_pos, i));
+    float pu, pv;
+    project_prev(A.prev_view_proj, was, pu, pv);
+    const float cu = (static_cast<float>(A.x0 + static_cast<uint32_t>(x)) + 0.5f) / static_cast<float>(A.frame_w);
+    const float cv = (static_cast<float>(A.y0 + static_cast<uint32_t>(y)) + 0.5f) / static_cast<float>(A.frame_h);
+    const float mu = cu - pu, mv = cv - pv;
+    if (A.motion_h) { A.motion_h[2 * i] = f2h(mu); A.motion_h[2 * i + 1] = f2h(mv); }
+    if (A.motion) { A.motion[2 * i] = mu; A.motion[2 * i + 1] = mv; }
 }
 
 // ---------------------------------------------------------------------------------------------- variance

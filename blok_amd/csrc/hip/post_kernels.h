@@ -11,7 +11,11 @@ struct VarianceArgs;
 struct AtrousArgs;
 struct TaaArgs;
 struct SharpenArgs;
+struct TemporalInstancedArgs;
+struct InstanceMotionArgs;
 void launch_temporal(const TemporalArgs& a, hipStream_t stream);
+void launch_temporal_instanced(const TemporalInstancedArgs& a, hipStream_t stream);   // the temporal pass of a frame with instances
+void launch_instance_motion(const InstanceMotionArgs& a, hipStream_t stream);         // object motion of tracked instance pixels
 void launch_variance(const VarianceArgs& a, hipStream_t stream);
 void launch_atrous(const AtrousArgs& a, hipStream_t stream);
 void launch_taa(const TaaArgs& a, hipStream_t stream);

@@ -28,6 +28,12 @@ __global__ __launch_bounds__(kPostBx * kPostBy) void sharpen_kernel(const Sharpe
     if (x < a.w && y < a.h) sharpen_pixel(a, static_cast<int>(x), static_cast<int>(y), lut);
 }
 
+// One lane per pixel of the rectangle; only the lanes of tracked instance pixels read more than the id plane (instance_motion.h)
+__global__ __launch_bounds__(kPostBx * kPostBy) void instance_motion_kernel(const InstanceMotionArgs a) {
+    const uint32_t x = blockIdx.x * kPostBx + threadIdx.x, y = blockIdx.y * kPostBy + threadIdx.y;
+    if (x < a.w && y < a.h) instance_motion_pixel(a, static_cast<int>(x), static_cast<int>(y));
+}
+
 __global__ __launch_bounds__(256) void widen_kernel(const uint16_t* src, float* dst, size_t n) {
     const size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
     if (i < n) dst[i] = h2f(src[i]);
@@ -42,6 +48,12 @@ void launch_pixels(const Args& a, uint32_t w, uint32_t h, hipStream_t stream) {
 }  // namespace
 
 void launch_temporal(const TemporalArgs& a, hipStream_t s) { launch_pixels<TemporalArgs, temporal_pixel>(a, a.f.w, a.f.h, s); }
+void launch_temporal_instanced(const TemporalInstancedArgs& a, hipStream_t s) {
+    launch_pixels<TemporalInstancedArgs, temporal_pixel_instanced>(a, a.t.f.w, a.t.f.h, s);
+}
+void launch_instance_motion(const InstanceMotionArgs& a, hipStream_t s) {
+    if (a.w && a.h) hipLaunchKernelGGL(instance_motion_kernel, dim3((a.w + kPostBx - 1) / kPostBx, (a.h + kPostBy - 1) / kPostBy), dim3(kPostBx, kPostBy), 0, s, a);
+}
 void launch_variance(const VarianceArgs& a, hipStream_t s) { launch_pixels<VarianceArgs, variance_pixel>(a, a.f.w, a.f.h, s); }
 void launch_atrous(const AtrousArgs& a, hipStream_t s) { launch_pixels<AtrousArgs, atrous_pixel>(a, a.w, a.h, s); }
 void launch_taa(const TaaArgs& a, hipStream_t s) { launch_pixels<TaaArgs, taa_pixel>(a, a.w, a.h, s); }

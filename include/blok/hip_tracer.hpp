@@ -253,6 +253,16 @@ public:
         cam.cameraChanged = false;
         return m_pixels;
     }
+    // drawFrameRTInstanced with object motion: instance i keeps its history while its index and model stay the same from frame to frame
+    const std::vector<uint32_t>& drawFrameRTInstancedMotion(Camera& cam, const std::vector<blok_instance>& instances, uint32_t sampleCount = 8,
+                                                            uint32_t maxBounces = 2) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_pixels.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_draw_frame_rt_instanced_motion(m_ctx, &c, sampleCount, maxBounces, nullptr, instances.data(),
+                                                      static_cast<uint32_t>(instances.size()), m_pixels.data(), &m_frameIndex));
+        cam.cameraChanged = false;
+        return m_pixels;
+    }
     // path-traced planes (host, any may be null) over the world plus instances; the first hit's instance per pixel in instanceIds()
     void tracePathsInstanced(Camera& cam, const std::vector<blok_instance>& instances, const blok_gbuffer& planesHost, uint32_t sampleCount = 8,
                              uint32_t maxBounces = 2, uint32_t frameIndex = 0) {

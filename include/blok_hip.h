@@ -441,7 +441,8 @@ int blok_hip_set_rt_taa_jitter(blok_hip_ctx* ctx, int enabled);
  * enqueued by the *_device entries). */
 int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
-/* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances. */
+/* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances.
+ * 1.3: object motion vectors for moving instances. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -507,8 +508,9 @@ int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays
  *   first hit (sample 0, bounce 0); out_instance (w*h uint32, may be NULL) holds that hit's instance or BLOK_INSTANCE_NONE.
  * Each launch first builds a BVH over the table on the stream (one workgroup; up to 4096 instances, above that every ray loops over the
  *   table — slower, same result), so the table may change every frame without a host synchronise.  Off for such launches: the bounce
- *   rounds' tail pool (ray batching mode 3 behaves as mode 2) and blok_hip_set_path_start's resume.  Motion vectors stay camera-only: an
- *   instance that moves between frames gets no object motion, so the denoiser and TAA may ghost behind it.
+ *   rounds' tail pool (ray batching mode 3 behaves as mode 2) and blok_hip_set_path_start's resume.  The motion plane of these entries
+ *   stays camera-only, and so does blok_hip_draw_frame_rt_instanced: an instance that moves between frames gets no object motion there,
+ *   so the denoiser and TAA may ghost behind it.  Object motion comes from the entries of the next block.
  * n_instances == 0 is blok_hip_trace_paths*'s launch, unchanged, plus out_instance filled with BLOK_INSTANCE_NONE.  Device entries skip
  *   instances that fail the limits; the host entries check the table first. */
 int blok_hip_trace_paths_instanced_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -526,6 +528,44 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
 int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
                                      const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
                                      uint32_t* out_rgba8_host, uint32_t* out_frame_count);
+
+/* Object motion for moving instances (ABI 1.3).
+ * Tracking.  Instance i of this frame's table `cur` is tracked when i < n_prev, prev[i].model == cur[i].model and both records pass the
+ *   limits above with that model; otherwise it is untracked (it appeared this frame or changed model).
+ * The map.  A first-hit point p (world_pos plane) on a tracked instance was, one frame earlier, at p_prev with normal n_prev: for each local
+ *   axis k, with a = cur.axis[k], b = prev.axis[k] and c = s * s' (the signs of cur's and prev's flip bit k),
+ *     p_prev[b] = fl(c * p[a] + float(prev.offset[b] - c * cur.offset[a]) * voxel_size)      n_prev[b] = c * n[a]
+ *   (one rounding per axis; equal offset, axis and flip: p_prev = p and n_prev = n with no arithmetic, so a stationary instance gets
+ *   exactly the camera-only motion).  Object motion = (px + 0.5) / width - uv of prev_view_proj * (p_prev, 1), and the same in y: the
+ *   operations of the path kernel's motion plane.
+ * blok_hip_instance_motion_device: the pixels of a rectangle whose first hit is a tracked instance get their object motion, in motion_h_dev
+ *   (RG16F, binary16 round to nearest even) and/or motion_dev (float2); it runs after blok_hip_trace_paths_instanced_ref_device to correct
+ *   that entry's motion plane.  Every other pixel (world, sky, untracked instance) is left untouched.  Planes and the id plane are w*h,
+ *   the rectangle's own; cur_dev / prev_dev are device tables read in stream order.
+ * blok_hip_denoise_instanced_device / _ref_device: blok_hip_denoise_device / _ref_device with the frame's id plane (width*height) and both
+ *   tables; the same post state and frame counter.  World pixels are denoised exactly as before.  A tracked instance's pixel: without a
+ *   motion plane its motion is the object motion; its history is compared at p_prev / n_prev in place of the pixel's position and normal
+ *   (the small-motion reprojection, the position and the normal tests).  An untracked instance's pixel uses no history (length 1).
+ * blok_hip_draw_frame_rt_instanced_motion: blok_hip_draw_frame_rt_instanced with object motion: path pass (with an id plane), motion
+ *   correction, the instanced temporal pass, then the rest of the chain unchanged.  The context keeps the previous frame's table; it is
+ *   empty after blok_hip_post_reset and after a frame drawn by blok_hip_draw_frame_rt or blok_hip_draw_frame_rt_instanced.  With no
+ *   instances the frame is blok_hip_draw_frame_rt's.
+ * Errors: BLOK_ERR_INVALID_ARG for a null id plane, a null table with a non-zero count, no motion output, a rectangle outside the frame or
+ *   no prev_view_proj; host tables are checked like the other host entries; device entries treat records that fail the limits as untracked. */
+int blok_hip_instance_motion_device(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev,
+                                    const uint32_t* instance_ids_dev, const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev,
+                                    uint32_t n_prev, const float prev_view_proj[16], uint16_t* motion_h_dev, float* motion_dev, void* hip_stream);
+int blok_hip_denoise_instanced_device(blok_hip_ctx* ctx, const blok_gbuffer* planes_dev, const float* motion_dev, const float prev_view_proj[16],
+                                      uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* instance_ids_dev,
+                                      const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                      float* out_color_dev, void* hip_stream);
+int blok_hip_denoise_instanced_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_ref* planes_dev, const float prev_view_proj[16],
+                                          uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* instance_ids_dev,
+                                          const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                          float* out_color_dev, void* hip_stream);
+int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                            const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                            uint32_t* out_rgba8_host, uint32_t* out_frame_count);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference
