@@ -105,6 +105,14 @@ HOST_SYMBOLS = {
     "blok_material_library_from_color": (C.c_uint32, [C.c_void_p, C.c_uint8, C.c_uint8, C.c_uint8]),
     "blok_material_library_set_vox_palette": (None, [C.c_void_p, C.c_uint8, C.c_uint32]),
     "blok_material_library_from_vox_palette": (C.c_uint32, [C.c_void_p, C.c_uint8]),
+    "blok_obj_load_file": (C.c_int, [C.c_char_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
+    "blok_obj_load_memory": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
+    "blok_mesh_free": (None, [C.c_void_p]),
+    "blok_mesh_vertex_count": (C.c_size_t, [C.c_void_p]),
+    "blok_mesh_triangle_count": (C.c_size_t, [C.c_void_p]),
+    "blok_mesh_positions": (C.c_void_p, [C.c_void_p]),
+    "blok_mesh_triangles": (C.c_void_p, [C.c_void_p]),
+    "blok_mesh_materials": (C.c_void_p, [C.c_void_p]),
     "blok_material_library_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "blok_material_library_clear": (None, [C.c_void_p]),
     "blok_world_set_material_library": (None, [C.c_void_p, C.c_void_p]),
@@ -248,6 +256,8 @@ HIP_SYMBOLS = {
     "blok_hip_volume_set_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "blok_hip_volume_apply_brush": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int]),
     "blok_hip_volume_rebuild": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "blok_hip_volume_voxelize_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_float,
+                                               C.c_int, C.POINTER(C.c_uint64)]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_abi_version": (C.c_uint32, []),

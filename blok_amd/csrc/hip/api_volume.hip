@@ -84,6 +84,22 @@ int blok_hip_volume_apply_brush(blok_hip_ctx* ctx, const float center[3], float 
     return volume_status(ctx, blok::gpu_volume_brush(&ctx->volume, center, radius, value, mode, &why), why);
 }
 
+int blok_hip_volume_voxelize_mesh(blok_hip_ctx* ctx, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
+                                  const uint32_t* triangle_materials, uint32_t material, float density, int mode, uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if ((n_vertices && !positions) || (n_triangles && !triangles)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "voxelize: null array with a non-zero count");
+    if (!std::isfinite(density) || !(density > 0.0f)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "voxelize: density must be finite and > 0");
+    if (mode != BLOK_VOXELIZE_SURFACE && mode != BLOK_VOXELIZE_SOLID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "voxelize: unknown mode");
+    std::string why;
+    bool invalid = false;
+    const blok::GpuBuildStatus st = blok::gpu_volume_voxelize(&ctx->volume, positions, n_vertices, triangles, n_triangles, triangle_materials, material, density,
+                                                               mode == BLOK_VOXELIZE_SOLID, out_n_voxels, &invalid, &why);
+    if (invalid) return set_error(ctx, BLOK_ERR_INVALID_ARG, why);
+    return volume_status(ctx, st, why);
+}
+
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;

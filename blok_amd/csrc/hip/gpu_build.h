@@ -88,6 +88,14 @@ GpuBuildStatus gpu_volume_download(const GpuVolume* v, float* density, uint32_t*
 // = ChunkManager::setVoxelMaterial for n world voxels (later entries win); voxels outside the box -> Unsupported.
 GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uint32_t* material, const float* density, size_t n,
                                      std::string* why);
+// Masks, occupancy words and dirty flags of the bricks that hold voxels [lo, hi) (box-local), from the dense store, and the edited box:
+// what every edit above does after writing the store (voxelize_kernels.hip writes the store itself).
+GpuBuildStatus gpu_volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why);
+// = blok_hip_volume_voxelize_mesh (include/blok_hip.h; voxelize_kernels.hip).  Host arrays.  *invalid: a referenced vertex, an index or a
+// triangle's extent is out of the limits (nothing written).
+GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
+                                   const uint32_t* triangle_materials, uint32_t material, float density, bool solid, uint64_t* out_n_voxels,
+                                   bool* invalid, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

@@ -905,6 +905,10 @@ GpuBuildStatus gpu_volume_download(const GpuVolume* v, float* density, uint32_t*
     return GpuBuildStatus::Ok;
 }
 
+GpuBuildStatus gpu_volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
+    return volume_refresh(v, lo, hi, why);
+}
+
 GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uint32_t* material, const float* density, size_t n,
                                      std::string* why) {
     if (!n) return GpuBuildStatus::Ok;

@@ -93,6 +93,20 @@ class HipTracer:
         c = (C.c_float * 3)(*[float(v) for v in center])
         self._check(self._lib.blok_hip_volume_apply_brush(self._ctx, c, float(radius), float(value), int(mode)))
 
+    def volume_voxelize_mesh(self, positions, triangles, materials=None, material: int = 1, density: float = 1.0, solid: bool = False) -> int:
+        """Voxelize a triangle mesh into the resident volume (blok_hip.h: blok_hip_volume_voxelize_mesh): positions (n, 3) float32 in world
+        units, triangles (m, 3) vertex indices, materials (m,) per-triangle ids or None (then `material`).  Returns the voxels written."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        mats = None if materials is None else np.ascontiguousarray(materials, dtype=np.uint32).reshape(-1)
+        if mats is not None and len(mats) != len(tri):
+            raise ValueError(f"one material id per triangle: {len(mats)} ids for {len(tri)} triangles")
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_voxelize_mesh(self._ctx, _ffi.ptr(pos) if len(pos) else None, len(pos), _ffi.ptr(tri) if len(tri) else None, len(tri),
+                                                            None if mats is None else _ffi.ptr(mats), int(material), float(density), 1 if solid else 0,
+                                                            C.byref(n)))
+        return int(n.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

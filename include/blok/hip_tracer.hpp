@@ -224,6 +224,19 @@ public:
     void applyBrush(const Brush& brush) {
         check(blok_hip_volume_apply_brush(m_ctx, brush.centerWS, brush.radiusWS, brush.value, brush.mode == Brush::ADD ? 0 : 1));
     }
+    // Mesh voxelization into the volume (blok_hip_volume_voxelize_mesh): positions xyz per vertex, three indices per triangle, per-triangle
+    // material ids (empty: `material` for all).  Returns the voxels written.
+    uint64_t voxelizeMesh(const std::vector<float>& positions, const std::vector<uint32_t>& triangles, const std::vector<uint32_t>& triangleMaterials,
+                          uint32_t material = 1, float density = 1.0f, bool solid = false) {
+        if (positions.size() % 3 || triangles.size() % 3) throw std::invalid_argument("voxelizeMesh: positions and triangles come in threes");
+        if (!triangleMaterials.empty() && triangleMaterials.size() != triangles.size() / 3)
+            throw std::invalid_argument("voxelizeMesh: one material id per triangle");
+        uint64_t n = 0;
+        check(blok_hip_volume_voxelize_mesh(m_ctx, positions.data(), positions.size() / 3, triangles.data(), triangles.size() / 3,
+                                            triangleMaterials.empty() ? nullptr : triangleMaterials.data(), material, density,
+                                            solid ? BLOK_VOXELIZE_SOLID : BLOK_VOXELIZE_SURFACE, &n));
+        return n;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -429,6 +429,36 @@ int blok_hip_volume_apply_brush(blok_hip_ctx* ctx, const float center[3], float 
  * density > 0 and their material ids, with the given material table. */
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials);
 
+/* ---- mesh voxelization into the resident volume (ABI 1.4) ----
+ * Writes a triangle mesh into the box.  Host arrays: positions xyz per vertex (world units; the volume's voxel_size is 1), three
+ * vertex indices per triangle, one material id per triangle or NULL (then `material` for all).
+ *  - Snapping: every coordinate becomes q = rint(x * 256) (round half to even), a 64-bit integer; the box origin is origin * 256.  All
+ *    later decisions are exact integer arithmetic on q, relative to each triangle's first vertex.  Shared vertices snap alike, so a
+ *    closed mesh stays closed.
+ *  - Limits (BLOK_ERR_INVALID_ARG, nothing written): a non-finite coordinate or |x| > 2^23 in a referenced vertex; an index >=
+ *    n_vertices; a triangle whose snapped extent on an axis exceeds 2048 voxels; density not finite or <= 0; an unknown mode; a null
+ *    array with a non-zero count.  With extents <= 2048 voxels (2^19 snapped units), edges are below 2^19, the normal's components below
+ *    2^39, and the plane test's largest term below 3 * 2^39 * (2^20 + 2^13) < 2^61: int64 holds every product.  Volumes above 2^32 cells
+ *    are refused (BLOK_ERR_UNSUPPORTED), as blok_hip_volume_set_voxels refuses them.  No volume: BLOK_ERR_NO_WORLD.
+ *  - Surface set S: voxel (i, j, k) iff its closed cube [i, i+1] x [j, j+1] x [k, k+1] meets the closed snapped triangle (exact
+ *    separating-axis test; a zero axis never separates, so a degenerate triangle is voxelized as the segment or point it is).  A
+ *    triangle lying exactly in a lattice plane marks both neighbouring layers.
+ *  - Interior set I (BLOK_VOXELIZE_SOLID only): voxel (i, j, k) iff an odd number of triangles cross its column (j + 1/2, k + 1/2) at
+ *    x <= i + 1/2.  Triangles whose yz projection has zero area never count.  A column point on a projected edge or vertex counts for
+ *    a triangle iff it would for the point moved by (+e, -e^2), e -> 0, after orienting the projection counter-clockwise (a top-left
+ *    rule: a point on an edge (dy, dz) counts iff dz < 0, or dz == 0 and dy < 0).  A column through an edge or vertex shared by a
+ *    closed edge-manifold mesh therefore counts like a column beside it.  Crossings left of the box count.  Open meshes get whatever
+ *    the parity gives: the columns right of an unpaired crossing are filled up to the end of the box.
+ *  - Written: S (surface mode) or S u I (solid mode), inside the box; other voxels are untouched (setVoxelMaterial's set semantics).
+ *    A written voxel gets `density` and, on S, the material of the lowest-indexed triangle that overlaps it; interior-only voxels get
+ *    `material`.  S and I depend neither on triangle order nor on vertex order or winding; the result is bit-identical from run to run.
+ *  - Afterwards the masks, occupancy words and dirty flags are those blok_hip_volume_set_voxels leaves for the same writes; the next
+ *    blok_hip_volume_rebuild installs the world.  Blocking.  out_n_voxels (may be NULL): voxels written. */
+#define BLOK_VOXELIZE_SURFACE 0
+#define BLOK_VOXELIZE_SOLID   1
+int blok_hip_volume_voxelize_mesh(blok_hip_ctx* ctx, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
+                                  const uint32_t* triangle_materials, uint32_t material, float density, int mode, uint64_t* out_n_voxels);
+
 /* TAA jitter of the primary rays of all following frames, in pixels (each within +-0.5; NULL or {0,0} = none, the default and
  * the parity / benchmark contract).  The reference applies its Halton(2,3) - 0.5 sequence through the projection matrix
  * (getJitteredProjection, blok/src/renderer_postprocess.cpp:254-268: proj[2][0..1] += 2 j / size, handed to raygen.rgen as
@@ -442,7 +472,7 @@ int blok_hip_set_rt_taa_jitter(blok_hip_ctx* ctx, int enabled);
 int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
 /* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances.
- * 1.3: object motion vectors for moving instances. */
+ * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

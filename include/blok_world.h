@@ -126,6 +126,26 @@ int  blok_vox_get_material(const blok_vox* v, uint8_t palette_index, blok_materi
 int  blok_vox_import_materials(const blok_vox* v, blok_material_library* lib, uint32_t palette_to_material[256]);
 /* = importVoxToChunks (reference blok/src/vox_loader.cpp:390-430): VOX z is up -> world y. Returns voxels imported. */
 uint32_t blok_vox_import_to_world(const blok_vox* v, blok_world* w, const float world_offset[3], uint32_t model_index);
+
+/* -------------------------------------------------------------- Wavefront OBJ / MTL meshes (obj.cpp)
+ * Triangles for blok_hip_volume_voxelize_mesh.  Geometry: `v x y z [w]` (w ignored); `f` with i, i/t, i//n or i/t/n and negative
+ * (relative) indices, referring to vertices defined before the face; polygons are fan-triangulated from their first vertex.  vt, vn, o,
+ * g, s, l, p and unknown statements are ignored; CRLF endings and a missing final newline are accepted.  Materials: the first `mtllib`,
+ * resolved relative to the .obj's directory (load_memory: the given MTL text instead; NULL = none); `usemtl` selects the material of the
+ * faces that follow.  From the MTL: newmtl -> name, Kd -> albedo, a non-zero Ke -> emission (type emissive, power 1), Pr -> roughness,
+ * Pm -> metallic; each goes through blok_material_library_add_or_find.  Faces before any usemtl or naming an undefined material get id 0;
+ * lib == NULL gives all zeros.  Errors (BLOK_ERR_INVALID_ARG, the line number in err): malformed numbers, index 0, out-of-range
+ * indices, faces with fewer than three vertices, a missing MTL file. */
+typedef struct blok_mesh blok_mesh;
+int  blok_obj_load_file(const char* path, blok_material_library* lib, blok_mesh** out, char* err, size_t err_len);
+int  blok_obj_load_memory(const char* obj, size_t obj_len, const char* mtl, size_t mtl_len, blok_material_library* lib, blok_mesh** out,
+                          char* err, size_t err_len);
+void blok_mesh_free(blok_mesh* m);
+size_t blok_mesh_vertex_count(const blok_mesh* m);
+size_t blok_mesh_triangle_count(const blok_mesh* m);
+const float*    blok_mesh_positions(const blok_mesh* m);      /* xyz per vertex */
+const uint32_t* blok_mesh_triangles(const blok_mesh* m);      /* three vertex indices per triangle */
+const uint32_t* blok_mesh_materials(const blok_mesh* m);      /* one material id per triangle */
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

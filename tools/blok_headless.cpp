@@ -1,13 +1,17 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]]
+//   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
+//          (surface shell, or filled with --solid), then rebuilt with the library's materials
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
 //   --no-rccl: peer copies even when RCCL is there
 //   --dense-exchange: whole RGBA8 tiles travel (RCCL / peer copies) instead of the root reading the ranks' sparse code records
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +30,9 @@ struct Options {
     bool rt = false;                      // full ray-tracing path per frame instead of first-hit frames
     uint32_t spp = 8;                     // samples per pixel and frame in --rt mode (the reference forces 8)
     std::string vox;                      // optional .vox model instead of the synthetic scene (app.cpp:105-113)
+    std::string obj;                      // optional .obj mesh, voxelized into a resident volume
+    uint32_t obj_size = 256;
+    bool solid = false;
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
     bool rccl = true;
@@ -43,6 +50,7 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
+                if (!m_opt.obj.empty()) { initObj(); break; }
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -81,6 +89,40 @@ private:
             default:
                 throw std::runtime_error("this driver only carries the HIP backend");
         }
+    }
+    // The mesh's bounding box fitted into obj_size voxels (half a voxel from the faces), voxelized into a volume of that box, rebuilt.
+    void initObj() {
+        if (m_opt.devices.size() > 1) throw std::runtime_error("--obj renders on one device");
+        char err[512] = {0};
+        blok_mesh* mesh = nullptr;
+        if (blok_obj_load_file(m_opt.obj.c_str(), m_materials.handle(), &mesh, err, sizeof(err)) != BLOK_OK)
+            throw std::runtime_error(std::string("Failed to load OBJ: ") + err);
+        const size_t nv = blok_mesh_vertex_count(mesh), nt = blok_mesh_triangle_count(mesh);
+        std::vector<float> pos(blok_mesh_positions(mesh), blok_mesh_positions(mesh) + 3 * nv);
+        std::vector<uint32_t> tri(blok_mesh_triangles(mesh), blok_mesh_triangles(mesh) + 3 * nt);
+        std::vector<uint32_t> mat(blok_mesh_materials(mesh), blok_mesh_materials(mesh) + nt);
+        blok_mesh_free(mesh);
+        if (nt == 0) throw std::runtime_error("the OBJ has no faces");
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        for (size_t i = 0; i < nv; ++i)
+            for (int a = 0; a < 3; ++a) { lo[a] = std::min<double>(lo[a], pos[3 * i + a]); hi[a] = std::max<double>(hi[a], pos[3 * i + a]); }
+        const double extent = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+        const double n = m_opt.obj_size, scale = extent > 0 ? (n - 1.0) / extent : 1.0;
+        for (size_t i = 0; i < nv; ++i)
+            for (int a = 0; a < 3; ++a) pos[3 * i + a] = static_cast<float>((pos[3 * i + a] - (lo[a] + hi[a]) / 2.0) * scale + n / 2.0);
+        const int32_t origin[3] = {0, 0, 0};
+        m_tracer->createVolume(origin, m_opt.obj_size, m_opt.obj_size, m_opt.obj_size);
+        const uint64_t written = m_tracer->voxelizeMesh(pos, tri, mat, 1, 1.0f, m_opt.solid);
+        m_tracer->rebuildVolume(m_materials.packForGpu());
+        const blok_world_stats s = m_tracer->worldStats();
+        std::cout << "mesh: " << nv << " vertices, " << nt << " triangles -> " << written << " voxels written (" << (m_opt.solid ? "solid" : "surface")
+                  << "); world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
+        const float eye[3] = {static_cast<float>(-0.35 * n), static_cast<float>(1.15 * n), static_cast<float>(-0.45 * n)};
+        float f[3] = {static_cast<float>(n / 2) - eye[0], static_cast<float>(n / 2) - eye[1], static_cast<float>(n / 2) - eye[2]};
+        const float len = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+        for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a]; }
+        m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
+        m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
     }
     void update() {
         using clock = std::chrono::steady_clock;
@@ -137,6 +179,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--frames")) opt.frames = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--out")) opt.out = next();
         else if (!std::strcmp(argv[i], "--vox")) opt.vox = next();
+        else if (!std::strcmp(argv[i], "--obj")) opt.obj = next();
+        else if (!std::strcmp(argv[i], "--obj-size")) opt.obj_size = std::strtoul(next(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--solid")) opt.solid = true;
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
