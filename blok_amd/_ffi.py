@@ -66,6 +66,15 @@ class DenoiseSettings(C.Structure):
                 ("variance_boost", C.c_float), ("min_history_length", C.c_int32)]
 
 
+class TerrainParams(C.Structure):
+    """= blok_terrain_params (include/blok_hip.h)."""
+    _fields_ = [("seed", C.c_uint32), ("base_height", C.c_int32), ("amplitude", C.c_uint32), ("height_cell_log2", C.c_uint32),
+                ("height_octaves", C.c_uint32), ("cave_cell_log2", C.c_uint32), ("cave_octaves", C.c_uint32), ("cave_threshold", C.c_uint32),
+                ("cave_roof", C.c_uint32), ("soil_depth", C.c_uint32), ("ore_cell_log2", C.c_uint32), ("ore_threshold", C.c_uint32),
+                ("surface_material", C.c_uint32), ("soil_material", C.c_uint32), ("rock_material", C.c_uint32), ("ore_material", C.c_uint32),
+                ("density", C.c_float), ("flags", C.c_uint32)]
+
+
 class WorldStats(C.Structure):
     _fields_ = [("n_voxels", C.c_uint64), ("n_ref_nodes", C.c_uint64), ("n_sub_chunks", C.c_uint64),
                 ("n_tree_nodes", C.c_uint64), ("tree_bytes", C.c_uint64), ("levels", C.c_uint32),
@@ -140,6 +149,10 @@ HOST_SYMBOLS = {
     "blok_taa_jitter": (None, [C.c_uint32, C.POINTER(C.c_float)]),
     "blok_taa_jitter_clip": (None, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "blok_jittered_projection": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "blok_terrain_default_params": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_terrain_validate": (C.c_int, [C.c_void_p]),
+    "blok_terrain_height": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "blok_terrain_eval": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -258,6 +271,7 @@ HIP_SYMBOLS = {
     "blok_hip_volume_rebuild": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "blok_hip_volume_voxelize_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_float,
                                                C.c_int, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_generate_terrain": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_abi_version": (C.c_uint32, []),

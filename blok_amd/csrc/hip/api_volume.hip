@@ -1,5 +1,6 @@
 // C ABI, device-resident dense voxel store (include/blok_hip.h: blok_hip_volume_*; kernels in gpu_build.hip).
 #include "api_internal.h"
+#include "../common/terrain_core.h"
 #include <chrono>
 #include <cstdlib>
 
@@ -98,6 +99,29 @@ int blok_hip_volume_voxelize_mesh(blok_hip_ctx* ctx, const float* positions, siz
                                                                mode == BLOK_VOXELIZE_SOLID, out_n_voxels, &invalid, &why);
     if (invalid) return set_error(ctx, BLOK_ERR_INVALID_ARG, why);
     return volume_status(ctx, st, why);
+}
+
+int blok_hip_volume_generate_terrain(blok_hip_ctx* ctx, const blok_terrain_params* params, const int32_t region_lo[3], const int32_t region_hi[3],
+                                     uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (!params) return set_error(ctx, BLOK_ERR_INVALID_ARG, "generate_terrain: null parameters");
+    static const char* const kRules[] = {"", "height octaves / cell", "cave octaves / cell", "ore cell", "a threshold above 65536", "amplitude above 65536",
+                                         "|base_height| above 2^24", "density not finite or <= 0", "unknown flag bits", "CLOSE_SIDES without SHELL"};
+    if (const int rule = blok::terrain::check_params(*params)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("generate_terrain: ") + kRules[rule]);
+    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "generate_terrain: one region pointer is null");
+    const blok::GpuVolume& v = ctx->volume;
+    const int64_t dims[3] = {v.nx, v.ny, v.nz};
+    uint32_t lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
+        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "generate_terrain: region_lo above region_hi");
+        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "generate_terrain: region leaves the resident volume");
+        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
+    }
+    std::string why;
+    return volume_status(ctx, blok::gpu_volume_generate_terrain(&ctx->volume, *params, lo, hi, out_n_voxels, &why), why);
 }
 
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {

@@ -96,6 +96,10 @@ GpuBuildStatus gpu_volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint
 GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
                                    const uint32_t* triangle_materials, uint32_t material, float density, bool solid, uint64_t* out_n_voxels,
                                    bool* invalid, std::string* why);
+// = blok_hip_volume_generate_terrain (include/blok_hip.h; terrain_kernels.hip) over the box-local region [lo, hi); the parameters have
+// passed terrain::check_params.
+GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_params& params, const uint32_t lo[3], const uint32_t hi[3],
+                                           uint64_t* out_n_voxels, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

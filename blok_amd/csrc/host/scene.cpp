@@ -8,6 +8,7 @@
 // Scene: not reference behaviour.  Integer-only, seedable, identical on every host.
 #include "blok_world.h"
 #include "../common/taa_jitter.h"
+#include "../common/terrain_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,13 +26,7 @@ inline V3 unit(V3 v) {
 constexpr float kDegToRad = 0.01745329251994329576923690768489f;  // glm::radians factor
 
 // ---- scene -------------------------------------------------------------------------------
-inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-inline uint32_t hash3(uint32_t x, uint32_t y, uint32_t z, uint32_t s) {
-    return fmix32(x * 0x9E3779B1u ^ y * 0x85EBCA77u ^ z * 0xC2B2AE3Du ^ s);
-}
+using blok::hash3;      // ../common/terrain_core.h: shared with the procedural terrain
 
 struct Terrain {
     uint32_t n, seed;

@@ -107,6 +107,15 @@ class HipTracer:
                                                             C.byref(n)))
         return int(n.value)
 
+    def volume_generate_terrain(self, params, region_lo=None, region_hi=None) -> int:
+        """Procedural terrain into the resident volume (blok_hip.h: blok_hip_volume_generate_terrain): params a blok_amd.terrain.TerrainParams,
+        the region in world voxels, half-open (both None = the whole box).  Returns the filled voxels written."""
+        lo = None if region_lo is None else (C.c_int32 * 3)(*[int(c) for c in region_lo])
+        hi = None if region_hi is None else (C.c_int32 * 3)(*[int(c) for c in region_hi])
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_generate_terrain(self._ctx, C.byref(params), lo, hi, C.byref(n)))
+        return int(n.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

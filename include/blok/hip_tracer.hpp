@@ -237,6 +237,13 @@ public:
                                             solid ? BLOK_VOXELIZE_SOLID : BLOK_VOXELIZE_SURFACE, &n));
         return n;
     }
+    // Procedural terrain into the volume (blok_hip_volume_generate_terrain): the region in world voxels, half-open (both null = the whole
+    // box).  blok_terrain_default_params gives a starting landscape, blok_terrain_height the ground under a point.  Returns the filled voxels.
+    uint64_t generateTerrain(const blok_terrain_params& params, const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr) {
+        uint64_t n = 0;
+        check(blok_hip_volume_generate_terrain(m_ctx, &params, regionLo, regionHi, &n));
+        return n;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -459,6 +459,54 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
 int blok_hip_volume_voxelize_mesh(blok_hip_ctx* ctx, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
                                   const uint32_t* triangle_materials, uint32_t material, float density, int mode, uint64_t* out_n_voxels);
 
+/* ---- procedural terrain into the resident volume (ABI 1.5) ----
+ * A pure integer function of the world voxel coordinate (X, Y, Z): bit-identical on the host (blok_terrain_eval, blok_world.h) and on the
+ * device, seamless across regions and boxes at any origin.  All arithmetic is unsigned 64-bit unless said otherwise; `>>` on a signed
+ * coordinate is an arithmetic shift (floor), `&` takes its two's-complement low bits.  fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B;
+ * h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16 (32-bit).  hash3(x, y, z, s) = fmix32(x * 0x9E3779B1 ^ y * 0x85EBCA77 ^ z * 0xC2B2AE3D ^ s),
+ * 32-bit, coordinates as their low 32 bits.
+ *  - fade(f, c): t = f << (16 - c); s = (t * t * (196608 - 2 t)) >> 32.   lerp16(a, b, s) = (a * (65536 - s) + b * s) >> 16.
+ *  - 2-D value noise, cell 2^c, salt k: i = X >> c, j = Z >> c, sx = fade(X & (2^c - 1), c), sz alike; lattice value
+ *    g(i, j) = hash3(i, 0x100 + k, j, seed) & 0xFFFF; v2 = lerp16(lerp16(g(i,j), g(i+1,j), sx), lerp16(g(i,j+1), g(i+1,j+1), sx), sz).
+ *  - 3-D value noise, cell 2^c, salt word w: g(i, j, k) = hash3(i, j, k, seed ^ w) & 0xFFFF, indices (X, Y, Z) >> c; lerp16 along x,
+ *    then y, then z, each with its axis' fade.
+ *  - fBm of K octaves from cell 2^c: octave k = 0..K-1 has cell 2^(c-k) and weight 2^(K-1-k); fbm = (sum weight * value) / (2^K - 1).
+ *  - H(X, Z) = base_height + ((fbm2(height_octaves, height_cell_log2; salts 0..K-1) * amplitude) >> 16), int32.
+ *  - cave(X, Y, Z): cave_octaves > 0 and Y <= H - cave_roof and fbm3(cave_octaves, cave_cell_log2; salt words 0x51ED0000 + k) <
+ *    cave_threshold.   solid(X, Y, Z) = Y <= H(X, Z) and not cave.  Nothing bounds it below.
+ *  - material, d = H - Y: d == 0 surface; d <= soil_depth soil; else ore if the one-octave 3-D noise (cell 2^ore_cell_log2, salt word
+ *    0x0BE00000) > ore_threshold, else rock.
+ *  - Written, for every voxel of the region (world voxels, half-open; both NULL = the whole box): without flags a solid voxel gets
+ *    (density, material) and every other voxel (0.0f, 0).  SHELL: "solid" becomes "solid with at least one of its six neighbours not
+ *    solid", neighbours judged by the function (not by the store or the region).  CLOSE_SIDES: an x or z neighbour outside the region
+ *    counts as not solid (y is not closed).  ADD: voxels that would get (0, 0) are not touched.
+ *  - BLOK_ERR_INVALID_ARG, nothing written: height_octaves not in 1..8 or > height_cell_log2 + 1; height_cell_log2 > 12; cave_octaves > 4
+ *    or > cave_cell_log2 + 1; cave_cell_log2 > 12; ore_cell_log2 > 12; a threshold > 65536; amplitude > 65536; |base_height| > 2^24;
+ *    density not finite or <= 0; unknown flag bits; CLOSE_SIDES without SHELL; exactly one region pointer NULL; lo > hi on an axis.  A
+ *    region that leaves the box, or a volume above 2^32 cells: BLOK_ERR_UNSUPPORTED, as the other edits answer.  No volume:
+ *    BLOK_ERR_NO_WORLD.  An empty region is BLOK_OK.
+ *  - Afterwards masks, occupancy words, dirty flags and the edited box are those blok_hip_volume_set_voxels leaves for the same writes;
+ *    the next blok_hip_volume_rebuild installs the world.  Blocking.  out_n_voxels (may be NULL): filled voxels written. */
+typedef struct blok_terrain_params {
+    uint32_t seed;
+    int32_t  base_height;                 /* world y of the lowest possible surface voxel */
+    uint32_t amplitude;                   /* the surface lies in [base_height, base_height + amplitude) */
+    uint32_t height_cell_log2, height_octaves;
+    uint32_t cave_cell_log2, cave_octaves;      /* cave_octaves 0 = no caves */
+    uint32_t cave_threshold;              /* 0..65536 */
+    uint32_t cave_roof;                   /* caves only where y <= H - cave_roof */
+    uint32_t soil_depth;
+    uint32_t ore_cell_log2, ore_threshold;      /* ore_threshold 65536 = no ore */
+    uint32_t surface_material, soil_material, rock_material, ore_material;
+    float    density;                     /* written into filled voxels; finite and > 0 */
+    uint32_t flags;
+} blok_terrain_params;
+#define BLOK_TERRAIN_SHELL        1u   /* write only filled voxels that have an empty 6-neighbour */
+#define BLOK_TERRAIN_CLOSE_SIDES  2u   /* with SHELL: x/z neighbours outside the region count as empty */
+#define BLOK_TERRAIN_ADD          4u   /* write filled voxels only; leave every other voxel as it is */
+int blok_hip_volume_generate_terrain(blok_hip_ctx* ctx, const blok_terrain_params* params, const int32_t region_lo[3],
+                                     const int32_t region_hi[3], uint64_t* out_n_voxels);
+
 /* TAA jitter of the primary rays of all following frames, in pixels (each within +-0.5; NULL or {0,0} = none, the default and
  * the parity / benchmark contract).  The reference applies its Halton(2,3) - 0.5 sequence through the projection matrix
  * (getJitteredProjection, blok/src/renderer_postprocess.cpp:254-268: proj[2][0..1] += 2 j / size, handed to raygen.rgen as
@@ -472,7 +520,8 @@ int blok_hip_set_rt_taa_jitter(blok_hip_ctx* ctx, int enabled);
 int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
 /* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances.
- * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume. */
+ * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume.
+ * 1.5: procedural terrain into the resident volume. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

@@ -146,6 +146,18 @@ size_t blok_mesh_triangle_count(const blok_mesh* m);
 const float*    blok_mesh_positions(const blok_mesh* m);      /* xyz per vertex */
 const uint32_t* blok_mesh_triangles(const blok_mesh* m);      /* three vertex indices per triangle */
 const uint32_t* blok_mesh_materials(const blok_mesh* m);      /* one material id per triangle */
+/* -------------------------------------------------------------- procedural terrain on the host (terrain.cpp)
+ * The function of blok_hip_volume_generate_terrain (blok_hip.h has the contract), evaluated by the same code on the CPU.
+ * default_params: a landscape for an n^3 box at the origin (surface between n/8 and n/2, caves, four materials 1..4): the values a user
+ * starts from.  validate: BLOK_OK or BLOK_ERR_INVALID_ARG by the contract's limits.  height: H(x, z) for n (x, z) pairs, e.g. to put a
+ * camera or a model on the ground.  eval: the region [lo, hi) of world voxels into the caller's arrays of exactly that region, x fastest
+ * (flags honoured; for ADD the caller pre-fills them); out_n_voxels (may be NULL): filled voxels written. */
+int blok_terrain_default_params(uint32_t n, uint32_t seed, blok_terrain_params* out);
+int blok_terrain_validate(const blok_terrain_params* params);
+int blok_terrain_height(const blok_terrain_params* params, const int32_t* xz, size_t n, int32_t* out);
+int blok_terrain_eval(const blok_terrain_params* params, const int32_t region_lo[3], const int32_t region_hi[3], float* density,
+                      uint32_t* material_ids, uint64_t* out_n_voxels);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

@@ -1,0 +1,126 @@
+"""Independent reference of the terrain function (include/blok_hip.h: blok_hip_volume_generate_terrain), written from the header's text in
+vectorised numpy: Python-side uint64 arithmetic everywhere, signed coordinates as int64 whose low 32 bits feed the hash.  No code shared
+with blok_amd/csrc/common/terrain_core.h."""
+from __future__ import annotations
+
+import numpy as np
+
+U = np.uint64
+M32 = U(0xFFFFFFFF)
+SHELL, CLOSE_SIDES, ADD = 1, 2, 4
+
+
+def _fmix32(h):
+    h = h & M32
+    h = h ^ (h >> U(16))
+    h = (h * U(0x85EBCA6B)) & M32
+    h = h ^ (h >> U(13))
+    h = (h * U(0xC2B2AE35)) & M32
+    return h ^ (h >> U(16))
+
+
+def _low32(a):
+    return np.asarray(a, dtype=np.int64).astype(np.uint64) & M32
+
+
+def hash3(x, y, z, s):
+    return _fmix32(((_low32(x) * U(0x9E3779B1)) & M32) ^ ((_low32(y) * U(0x85EBCA77)) & M32) ^ ((_low32(z) * U(0xC2B2AE3D)) & M32) ^ U(s & 0xFFFFFFFF))
+
+
+def fade(f, c):
+    t = f.astype(np.uint64) << U(16 - c)
+    return (t * t * (U(196608) - U(2) * t)) >> U(32)
+
+
+def lerp16(a, b, s):
+    return (a * (U(65536) - s) + b * s) >> U(16)
+
+
+def noise2(X, Z, c, salt, seed):
+    i, j = X >> c, Z >> c                                   # int64 arithmetic shift = floor
+    sx, sz = fade(X & ((1 << c) - 1), c), fade(Z & ((1 << c) - 1), c)
+
+    def g(a, b):
+        return hash3(a, 0x100 + salt, b, seed) & U(0xFFFF)
+    return lerp16(lerp16(g(i, j), g(i + 1, j), sx), lerp16(g(i, j + 1), g(i + 1, j + 1), sx), sz)
+
+
+def noise3(X, Y, Z, c, word, seed):
+    i, j, k = X >> c, Y >> c, Z >> c
+    m = (1 << c) - 1
+    sx, sy, sz = fade(X & m, c), fade(Y & m, c), fade(Z & m, c)
+
+    def g(a, b, d):
+        return hash3(a, b, d, seed ^ word) & U(0xFFFF)
+
+    def plane(d):
+        return lerp16(lerp16(g(i, j, d), g(i + 1, j, d), sx), lerp16(g(i, j + 1, d), g(i + 1, j + 1, d), sx), sy)
+    return lerp16(plane(k), plane(k + 1), sz)
+
+
+def _fbm(octave, K, c):
+    acc = U(0)
+    for k in range(K):
+        acc = acc + octave(c - k, k) * U(1 << (K - 1 - k))
+    return acc // U((1 << K) - 1)
+
+
+def height(p, X, Z):
+    X, Z = np.asarray(X, np.int64), np.asarray(Z, np.int64)
+    n = _fbm(lambda c, k: noise2(X, Z, c, k, p["seed"]), p["height_octaves"], p["height_cell_log2"])
+    return p["base_height"] + ((n * U(p["amplitude"])) >> U(16)).astype(np.int64)
+
+
+def solid(p, X, Y, Z, H):
+    s = Y <= H
+    if p["cave_octaves"]:
+        n = _fbm(lambda c, k: noise3(X, Y, Z, c, 0x51ED0000 + k, p["seed"]), p["cave_octaves"], p["cave_cell_log2"])
+        s = s & ~((Y <= H - p["cave_roof"]) & (n < U(p["cave_threshold"])))
+    return s
+
+
+def material(p, X, Y, Z, H):
+    d = H - Y
+    ore = noise3(X, Y, Z, p["ore_cell_log2"], 0x0BE00000, p["seed"]) > U(p["ore_threshold"])
+    return np.where(d == 0, p["surface_material"], np.where(d <= p["soil_depth"], p["soil_material"],
+                                                          np.where(ore, p["ore_material"], p["rock_material"]))).astype(np.uint32)
+
+
+def _grid(lo, hi):
+    ax = [np.arange(lo[a], hi[a], dtype=np.int64) for a in range(3)]
+    Z, Y, X = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return X, Y, Z
+
+
+def solid_box(p, lo, hi):
+    """solid() over [lo, hi) as a [z][y][x] boolean array, with the heights as [z][1][x]."""
+    X, Y, Z = _grid(lo, hi)
+    H = height(p, X[:, :1, :], Z[:, :1, :])
+    return solid(p, X, Y, Z, H), H
+
+
+def eval_box(p, lo, hi, density=None, ids=None):
+    """What the entry writes into [lo, hi): (density, ids) as [z][y][x] arrays (prior content given for ADD)."""
+    lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+    shape = (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0])
+    flags = p["flags"]
+    if flags & SHELL:
+        S, _ = solid_box(p, [v - 1 for v in lo], [v + 1 for v in hi])
+        if flags & CLOSE_SIDES:
+            S[0, :, :] = S[-1, :, :] = False
+            S[:, :, 0] = S[:, :, -1] = False
+        c = S[1:-1, 1:-1, 1:-1]
+        inner = S[1:-1, 1:-1, :-2] & S[1:-1, 1:-1, 2:] & S[1:-1, :-2, 1:-1] & S[1:-1, 2:, 1:-1] & S[:-2, 1:-1, 1:-1] & S[2:, 1:-1, 1:-1]
+        fill = c & ~inner
+    else:
+        fill, _ = solid_box(p, lo, hi)
+    X, Y, Z = _grid(lo, hi)
+    H = height(p, X[:, :1, :], Z[:, :1, :])
+    mat = material(p, X, Y, Z, H)
+    if flags & ADD:
+        d = np.zeros(shape, np.float32) if density is None else np.array(density, np.float32).reshape(shape)
+        m = np.zeros(shape, np.uint32) if ids is None else np.array(ids, np.uint32).reshape(shape)
+        d[fill] = np.float32(p["density"])
+        m[fill] = mat[fill]
+        return d, m
+    return np.where(fill, np.float32(p["density"]), np.float32(0.0)).astype(np.float32), np.where(fill, mat, 0).astype(np.uint32)

@@ -1,9 +1,12 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]]
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
+//   --terrain: procedural terrain generated on the device into a resident volume of --terrain-size^3 voxels (blok_hip_volume_generate_terrain),
+//          rebuilt with grass, soil, rock and an emissive ore; the camera stands on blok_terrain_height.  With --obj the mesh is voxelized on
+//          top of it, a quarter of the box tall, standing on the ground at the box centre
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -33,6 +36,8 @@ struct Options {
     std::string obj;                      // optional .obj mesh, voxelized into a resident volume
     uint32_t obj_size = 256;
     bool solid = false;
+    bool terrain = false;                 // procedural terrain generated on the device
+    uint32_t terrain_seed = 0, terrain_size = 256;
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
     bool rccl = true;
@@ -50,6 +55,7 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
+                if (m_opt.terrain) { initTerrain(); break; }
                 if (!m_opt.obj.empty()) { initObj(); break; }
                 if (!m_opt.vox.empty()) {
                     std::string err;
@@ -89,6 +95,66 @@ private:
             default:
                 throw std::runtime_error("this driver only carries the HIP backend");
         }
+    }
+    // Terrain generated into an N^3 volume, an optional mesh voxelized on top of it, the camera on the ground near a corner.
+    void initTerrain() {
+        if (m_opt.devices.size() > 1) throw std::runtime_error("--terrain renders on one device");
+        const uint32_t N = m_opt.terrain_size;
+        blok_terrain_params p{};
+        if (blok_terrain_default_params(N, m_opt.terrain_seed, &p) != BLOK_OK) throw std::runtime_error("--terrain-size must be in 1..65536");
+        const struct { const char* name; float rgb[3]; float emission; } table[4] = {
+            {"grass", {0.25f, 0.62f, 0.20f}, 0.0f}, {"soil", {0.45f, 0.30f, 0.16f}, 0.0f}, {"rock", {0.50f, 0.50f, 0.52f}, 0.0f}, {"ore", {1.0f, 0.55f, 0.10f}, 4.0f}};
+        uint32_t ids[4];
+        for (int k = 0; k < 4; ++k) {
+            blok_material_desc m;
+            blok_material_desc_init(&m);
+            for (int a = 0; a < 3; ++a) m.albedo[a] = table[k].rgb[a];
+            if (table[k].emission > 0.0f) { for (int a = 0; a < 3; ++a) m.emission[a] = table[k].rgb[a]; m.emission_power = table[k].emission; m.type = 3; }
+            std::snprintf(m.name, sizeof(m.name), "%s", table[k].name);
+            ids[k] = m_materials.addMaterial(m);
+        }
+        p.surface_material = ids[0]; p.soil_material = ids[1]; p.rock_material = ids[2]; p.ore_material = ids[3];
+        const int32_t origin[3] = {0, 0, 0};
+        m_tracer->createVolume(origin, N, N, N);
+        const uint64_t filled = m_tracer->generateTerrain(p);
+        std::cout << "terrain: seed " << m_opt.terrain_seed << ", " << N << "^3 -> " << filled << " voxels filled\n";
+        const int32_t centre[2] = {static_cast<int32_t>(N / 2), static_cast<int32_t>(N / 2)};
+        int32_t ground = 0;
+        blok_terrain_height(&p, centre, 1, &ground);
+        if (!m_opt.obj.empty()) {
+            char err[512] = {0};
+            blok_mesh* mesh = nullptr;
+            if (blok_obj_load_file(m_opt.obj.c_str(), m_materials.handle(), &mesh, err, sizeof(err)) != BLOK_OK)
+                throw std::runtime_error(std::string("Failed to load OBJ: ") + err);
+            const size_t nv = blok_mesh_vertex_count(mesh), nt = blok_mesh_triangle_count(mesh);
+            std::vector<float> pos(blok_mesh_positions(mesh), blok_mesh_positions(mesh) + 3 * nv);
+            std::vector<uint32_t> tri(blok_mesh_triangles(mesh), blok_mesh_triangles(mesh) + 3 * nt);
+            std::vector<uint32_t> mat(blok_mesh_materials(mesh), blok_mesh_materials(mesh) + nt);
+            blok_mesh_free(mesh);
+            if (nt == 0) throw std::runtime_error("the OBJ has no faces");
+            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+            for (size_t i = 0; i < nv; ++i)
+                for (int a = 0; a < 3; ++a) { lo[a] = std::min<double>(lo[a], pos[3 * i + a]); hi[a] = std::max<double>(hi[a], pos[3 * i + a]); }
+            const double extent = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+            const double scale = extent > 0 ? (N / 4.0) / extent : 1.0;
+            for (size_t i = 0; i < nv; ++i) {                    // x, z centred on the box centre; the lowest vertex on top of the ground voxel
+                pos[3 * i + 0] = static_cast<float>((pos[3 * i + 0] - (lo[0] + hi[0]) / 2.0) * scale + N / 2.0);
+                pos[3 * i + 1] = static_cast<float>((pos[3 * i + 1] - lo[1]) * scale + ground + 1.25);
+                pos[3 * i + 2] = static_cast<float>((pos[3 * i + 2] - (lo[2] + hi[2]) / 2.0) * scale + N / 2.0);
+            }
+            const uint64_t written = m_tracer->voxelizeMesh(pos, tri, mat, 1, 1.0f, m_opt.solid);
+            std::cout << "mesh: " << nv << " vertices, " << nt << " triangles -> " << written << " voxels written on the ground at y = " << ground << "\n";
+        }
+        m_tracer->rebuildVolume(m_materials.packForGpu());
+        const blok_world_stats s = m_tracer->worldStats();
+        std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
+        // the camera: a few voxels above the highest possible surface over a corner column, looking at a point a little above the ground at the box centre (sky in the upper part of the frame)
+        const float eye[3] = {0.12f * N, static_cast<float>(p.base_height + static_cast<int32_t>(p.amplitude)) + 0.08f * N, 0.10f * N};
+        float f[3] = {N / 2.0f - eye[0], static_cast<float>(ground) + 0.15f * N - eye[1], N / 2.0f - eye[2]};
+        const float len = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+        for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a]; }
+        m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
+        m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
     }
     // The mesh's bounding box fitted into obj_size voxels (half a voxel from the faces), voxelized into a volume of that box, rebuilt.
     void initObj() {
@@ -182,6 +248,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--obj")) opt.obj = next();
         else if (!std::strcmp(argv[i], "--obj-size")) opt.obj_size = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--solid")) opt.solid = true;
+        else if (!std::strcmp(argv[i], "--terrain")) { opt.terrain = true; opt.terrain_seed = static_cast<uint32_t>(std::strtoul(next(), nullptr, 0)); }
+        else if (!std::strcmp(argv[i], "--terrain-size")) opt.terrain_size = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
