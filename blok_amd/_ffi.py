@@ -43,8 +43,11 @@ RAY = np.dtype([("org", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", 
 # = blok_instance: a placed model (lattice offset, axis-aligned orientation), 32 bytes
 INSTANCE = np.dtype([("model", "<u4"), ("offset", "<i4", 3), ("axis", "u1", 3), ("flip", "u1"), ("reserved", "<u4", 3)])
 INSTANCE_NONE = 0xFFFFFFFF
+# = blok_quad: one merged quad of a volume's surface, 32 bytes
+QUAD = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("reserved", "<u4")])
+QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
-assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32
+assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
 
 
 class GBuffer(C.Structure):
@@ -153,6 +156,9 @@ HOST_SYMBOLS = {
     "blok_terrain_validate": (C.c_int, [C.c_void_p]),
     "blok_terrain_height": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_terrain_eval": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "blok_quads_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "blok_quads_write_obj": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -272,6 +278,9 @@ HIP_SYMBOLS = {
     "blok_hip_volume_voxelize_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_float,
                                                C.c_int, C.POINTER(C.c_uint64)]),
     "blok_hip_volume_generate_terrain": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_extract_quads": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_quads_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_abi_version": (C.c_uint32, []),

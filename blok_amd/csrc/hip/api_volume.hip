@@ -18,6 +18,10 @@ int volume_status(blok_hip_ctx* ctx, blok::GpuBuildStatus st, const std::string&
         default: return set_error(ctx, BLOK_ERR_INVALID_ARG, why.empty() ? "volume operation not applicable" : why);
     }
 }
+void drop_quads(blok_hip_ctx* ctx) {
+    if (ctx->d_quads) (void)hipFree(ctx->d_quads);
+    ctx->d_quads = nullptr; ctx->n_quads = 0; ctx->has_quads = false;
+}
 int need_volume(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (!ctx->has_volume) return set_error(ctx, BLOK_ERR_NO_WORLD, "no resident volume (blok_hip_volume_create)");
@@ -31,6 +35,7 @@ int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t 
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->has_volume) { if (ctx->tree_owned_by_volume) { BLOK_HIP_TRY(ctx, hipDeviceSynchronize()); free_world(ctx); } blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false; }
+    drop_quads(ctx);
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
     std::string why;
     const blok::GpuBuildStatus st = blok::gpu_volume_create(o, nx, ny, nz, chunk_size, voxel_size, &ctx->volume, &why, ctx->volume_keyed_layout);
@@ -51,6 +56,7 @@ int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
         if (ctx->tree_owned_by_volume) { (void)hipDeviceSynchronize(); free_world(ctx); }      // the installed world lives in the volume's arrays: it goes with them
         blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false;
     }
+    drop_quads(ctx);
     return BLOK_OK;
 }
 
@@ -122,6 +128,49 @@ int blok_hip_volume_generate_terrain(blok_hip_ctx* ctx, const blok_terrain_param
     }
     std::string why;
     return volume_status(ctx, blok::gpu_volume_generate_terrain(&ctx->volume, *params, lo, hi, out_n_voxels, &why), why);
+}
+
+int blok_hip_volume_extract_quads(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                                  uint64_t* out_n_quads, uint64_t* out_n_faces) {
+    if (out_n_quads) *out_n_quads = 0;
+    if (out_n_faces) *out_n_faces = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags & ~(BLOK_QUADS_IGNORE_MATERIAL | BLOK_QUADS_COUNT_ONLY)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "extract_quads: unknown flag bits");
+    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "extract_quads: one region pointer is null");
+    const blok::GpuVolume& v = ctx->volume;
+    const int64_t dims[3] = {v.nx, v.ny, v.nz};
+    uint32_t lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
+        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "extract_quads: region_lo above region_hi");
+        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "extract_quads: region leaves the resident volume");
+        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
+    }
+    std::string why;
+    blok_quad* quads = nullptr;
+    uint64_t n_quads = 0, n_faces = 0;
+    // (edits are enqueued on the null stream, and so is this: it reads what they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_extract_quads(&ctx->volume, lo, hi, flags, &quads, &n_quads, &n_faces, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    if (!(flags & BLOK_QUADS_COUNT_ONLY)) {
+        drop_quads(ctx);
+        ctx->d_quads = quads; ctx->n_quads = n_quads; ctx->has_quads = true;
+    }
+    if (out_n_quads) *out_n_quads = n_quads;
+    if (out_n_faces) *out_n_faces = n_faces;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_quads_download(blok_hip_ctx* ctx, blok_quad* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_quads) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: no snapshot (blok_hip_volume_extract_quads)");
+    if (first > ctx->n_quads || count > ctx->n_quads - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->d_quads + first, count * sizeof(blok_quad), hipMemcpyDeviceToHost));
+    return BLOK_OK;
 }
 
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {

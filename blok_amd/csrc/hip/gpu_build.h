@@ -100,6 +100,10 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
 // passed terrain::check_params.
 GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_params& params, const uint32_t lo[3], const uint32_t hi[3],
                                            uint64_t* out_n_voxels, std::string* why);
+// = blok_hip_volume_extract_quads (include/blok_hip.h; quads_kernels.hip) over the box-local region [lo, hi).  Reads the store, changes
+// nothing.  Without BLOK_QUADS_COUNT_ONLY *out_quads is a new device array of *out_n_quads records (null for none), the caller's to free.
+GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, blok_quad** out_quads,
+                                        uint64_t* out_n_quads, uint64_t* out_n_faces, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

@@ -116,6 +116,30 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_generate_terrain(self._ctx, C.byref(params), lo, hi, C.byref(n)))
         return int(n.value)
 
+    def volume_extract_quads(self, lo=None, hi=None, ignore_material: bool = False, count_only: bool = False, page: int = 1 << 22):
+        """The volume's surface as merged quads (blok_hip.h: blok_hip_volume_extract_quads): the region in world voxels, half-open (both
+        None = the whole box).  Returns the records as a structured array of _ffi.QUAD in canonical order, fetched `page` records at a
+        time; with count_only the pair (n_quads, n_faces) and nothing is kept."""
+        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
+        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        flags = (_ffi.QUADS_IGNORE_MATERIAL if ignore_material else 0) | (_ffi.QUADS_COUNT_ONLY if count_only else 0)
+        n_quads, n_faces = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_extract_quads(self._ctx, rlo, rhi, flags, C.byref(n_quads), C.byref(n_faces)))
+        self.last_quad_faces = int(n_faces.value)
+        if count_only:
+            return int(n_quads.value), int(n_faces.value)
+        return self.volume_quads_download(0, int(n_quads.value), page)
+
+    def volume_quads_download(self, first: int, count: int, page: int = 1 << 22) -> np.ndarray:
+        """Records [first, first + count) of the last extraction's snapshot."""
+        out = np.zeros(int(count), dtype=_ffi.QUAD)
+        if count == 0:
+            self._check(self._lib.blok_hip_volume_quads_download(self._ctx, None, int(first), 0))
+        for at in range(0, int(count), int(page)):
+            n = min(int(page), int(count) - at)
+            self._check(self._lib.blok_hip_volume_quads_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
+        return out
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

@@ -13,6 +13,7 @@
 #ifndef BLOK_HIP_TRACER_HPP
 #define BLOK_HIP_TRACER_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -243,6 +244,17 @@ public:
         uint64_t n = 0;
         check(blok_hip_volume_generate_terrain(m_ctx, &params, regionLo, regionHi, &n));
         return n;
+    }
+    // The volume's surface as merged quads in canonical order (blok_hip_volume_extract_quads, then the snapshot fetched `page` records at
+    // a time): the region in world voxels, half-open (both null = the whole box).  outFaces: the exposed unit faces.
+    std::vector<blok_quad> extractQuads(const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr, bool ignoreMaterial = false,
+                                        uint64_t* outFaces = nullptr, uint64_t page = uint64_t(1) << 22) {
+        uint64_t n = 0, faces = 0;
+        check(blok_hip_volume_extract_quads(m_ctx, regionLo, regionHi, ignoreMaterial ? BLOK_QUADS_IGNORE_MATERIAL : 0u, &n, &faces));
+        if (outFaces) *outFaces = faces;
+        std::vector<blok_quad> quads(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_quads_download(m_ctx, quads.data() + at, at, std::min(page, n - at)));
+        return quads;
     }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 

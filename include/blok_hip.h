@@ -507,6 +507,52 @@ typedef struct blok_terrain_params {
 int blok_hip_volume_generate_terrain(blok_hip_ctx* ctx, const blok_terrain_params* params, const int32_t region_lo[3],
                                      const int32_t region_hi[3], uint64_t* out_n_voxels);
 
+/* ---- the volume's surface as merged quads (ABI 1.6) ----
+ * Integer arithmetic on the two arrays of the volume: the result is a pure function of (arrays, box origin, region, flags), bit-identical
+ * on the host (blok_quads_extract, blok_world.h) and on the device.
+ *  - Filled: a voxel is filled iff its density > 0 (the rebuild's rule; NaN and negative densities are empty).
+ *  - Exposed face: faces are numbered as blok_hit::face (0:+X 1:-X 2:+Y 3:-Y 4:+Z 5:-Z).  Face f of a filled voxel p inside the region is
+ *    exposed iff the neighbour p + n_f is not filled.  A neighbour outside the region but inside the box is judged by the store, so
+ *    regions extracted side by side give exactly the faces of one extraction over their union.  A neighbour outside the box is empty.
+ *  - Key: the voxel's material id; with BLOK_QUADS_IGNORE_MATERIAL 0 for every face (collider meshes).
+ *  - Plane axes: for a face with normal axis a, u is the lower of the two other axes and v the higher: x -> (y, z), y -> (x, z),
+ *    z -> (x, y).
+ *  - Runs: for one face number, plane (the voxel coordinate along a) and row v, a run is a maximal set of cells consecutive along u,
+ *    inside the region, that are all exposed with the same key.
+ *  - Quads: two runs in rows v and v + 1 of the same face number and plane are identical iff they have the same first cell, last cell
+ *    and key.  A quad is a maximal stack of identical runs in consecutive rows.  A row holds at most one run starting at a given cell,
+ *    so stacks are unique: run-length merging plus vertical merging of equal runs.  (Not the sequential "greedy" rectangle cover: this
+ *    rule is order-free, has one answer, and both the origin and the extent of a quad are local predicates.)
+ *  - Corners: the rectangle is lo + [0, du] e_u + [0, dv] e_v.  Counter-clockwise seen from outside: c0 = lo, c1 = lo + du e_u,
+ *    c2 = c1 + dv e_v, c3 = lo + dv e_v when (e_u x e_v) . n_f > 0 (faces 0, 3, 4), otherwise c0, c3, c2, c1.  The triangles are
+ *    (c0, c1, c2) and (c0, c2, c3) of that order.
+ *  - Order: quads are sorted by (face, lo[a], lo[v], lo[u]) ascending; with the rules above this order is total.
+ *  - Counts: n_faces is the number of exposed unit faces and equals the sum of du * dv over the quads.  Both counts are 64-bit.
+ *  - Bounds: quads <= exposed faces <= 6 * filled voxels.  The worst case is a checkerboard, 3 quads per cell of the region, so the
+ *    result is sized by a counting pass, never by a bound.
+ *  - blok_hip_volume_extract_quads: the region is in world voxels, half open; both pointers NULL = the whole box.  Blocking.  The quad
+ *    array stays in device memory, owned by the context: a snapshot that later edits do not touch.  The next extraction replaces it;
+ *    blok_hip_volume_destroy, a new blok_hip_volume_create and blok_hip_destroy free it.  With BLOK_QUADS_COUNT_ONLY only the two counts
+ *    are produced and nothing is kept (an earlier snapshot stays).  Either count pointer may be NULL.
+ *  - blok_hip_volume_quads_download copies records [first, first + count) of the snapshot, so a large result can be fetched in pieces.
+ *  - Errors, each leaving the previous snapshot as it was.  BLOK_ERR_INVALID_ARG: unknown flag bits, exactly one region pointer NULL,
+ *    lo > hi on an axis.  BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume above 2^32 cells, a region with 2^31 or more
+ *    rows in total over the six face numbers.  BLOK_ERR_NO_WORLD: no volume.  An empty region is BLOK_OK with zero counts (and, without
+ *    COUNT_ONLY, an empty snapshot).  BLOK_ERR_OOM: a failed device allocation.  The download answers BLOK_ERR_INVALID_ARG when there is
+ *    no snapshot, the range goes past its end, or out_host is NULL with count > 0. */
+typedef struct blok_quad {
+    int32_t  lo[3];     /* lowest LATTICE corner, world units: lo[a] = voxel coordinate (+1 for faces 0, 2, 4), lo[u], lo[v] = first cell */
+    uint32_t du, dv;    /* extent in cells along u and v, both >= 1 */
+    uint32_t material;  /* the key */
+    uint32_t face;      /* 0..5 */
+    uint32_t reserved;  /* 0 */
+} blok_quad;
+#define BLOK_QUADS_IGNORE_MATERIAL 1u   /* key 0 for every face */
+#define BLOK_QUADS_COUNT_ONLY      2u   /* produce the counts only; keep nothing */
+int blok_hip_volume_extract_quads(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                                  uint64_t* out_n_quads, uint64_t* out_n_faces);
+int blok_hip_volume_quads_download(blok_hip_ctx* ctx, blok_quad* out_host, uint64_t first, uint64_t count);
+
 /* TAA jitter of the primary rays of all following frames, in pixels (each within +-0.5; NULL or {0,0} = none, the default and
  * the parity / benchmark contract).  The reference applies its Halton(2,3) - 0.5 sequence through the projection matrix
  * (getJitteredProjection, blok/src/renderer_postprocess.cpp:254-268: proj[2][0..1] += 2 j / size, handed to raygen.rgen as
@@ -521,7 +567,7 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
 /* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances.
  * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume.
- * 1.5: procedural terrain into the resident volume. */
+ * 1.5: procedural terrain into the resident volume.  1.6: the volume's surface as merged quads. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

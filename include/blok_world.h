@@ -158,6 +158,24 @@ int blok_terrain_height(const blok_terrain_params* params, const int32_t* xz, si
 int blok_terrain_eval(const blok_terrain_params* params, const int32_t region_lo[3], const int32_t region_hi[3], float* density,
                       uint32_t* material_ids, uint64_t* out_n_voxels);
 
+/* -------------------------------------------------------------- a volume's surface as merged quads on the host (quads.cpp)
+ * extract: the contract of blok_hip_volume_extract_quads (blok_hip.h) over host arrays density[x + y*nx + z*nx*ny] / material_ids of a
+ * box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0); the region in world voxels, half open, both NULL = the whole box.
+ * Writes at most `capacity` records in canonical order (a prefix when there are more; none under BLOK_QUADS_COUNT_ONLY) and always
+ * reports the totals (either pointer may be NULL).  Errors as the device entry: BLOK_ERR_INVALID_ARG for unknown flag bits, exactly one
+ * region pointer NULL, lo > hi on an axis, a NULL array the call would use; BLOK_ERR_UNSUPPORTED for a region that leaves the box or a
+ * box above 2^32 cells; an empty region is BLOK_OK with zero counts.
+ * write_obj: n quads as a Wavefront OBJ: integer `v` lines, vertices shared between quads and numbered by first use (quads in the given
+ * order, corners in winding order, each `v` line just before the first face that uses it), one four-index `f` line per quad, a
+ * `usemtl m<id>` line before the first face and whenever the material changes.  With a library: a `mtllib` line and a sibling file (the
+ * path with its extension replaced by .mtl) whose `newmtl m<id>` entries carry the material's albedo as `Kd`.  blok_obj_load_file reads
+ * the result back: two triangles per quad, (c0, c1, c2) and (c0, c2, c3).  BLOK_ERR_INVALID_ARG (text in err): a file that cannot be
+ * written, a record with face > 5 or a zero extent. */
+int blok_quads_extract(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                       const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags, blok_quad* out, uint64_t capacity,
+                       uint64_t* out_n_quads, uint64_t* out_n_faces);
+int blok_quads_write_obj(const char* path, const blok_quad* quads, uint64_t n, const blok_material_library* lib, char* err, size_t err_len);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

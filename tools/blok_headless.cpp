@@ -1,12 +1,14 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj]
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
 //   --terrain: procedural terrain generated on the device into a resident volume of --terrain-size^3 voxels (blok_hip_volume_generate_terrain),
 //          rebuilt with grass, soil, rock and an emissive ore; the camera stands on blok_terrain_height.  With --obj the mesh is voxelized on
 //          top of it, a quarter of the box tall, standing on the ground at the box centre
+//   --export-obj: with --terrain or --obj, the resident volume's surface as merged quads (blok_hip_volume_extract_quads over the whole box),
+//          written as an OBJ with a sibling .mtl of the library's albedos (blok_quads_write_obj)
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -38,6 +40,7 @@ struct Options {
     bool solid = false;
     bool terrain = false;                 // procedural terrain generated on the device
     uint32_t terrain_seed = 0, terrain_size = 256;
+    std::string export_obj;               // write the resident volume's surface here
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
     bool rccl = true;
@@ -55,8 +58,9 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
-                if (m_opt.terrain) { initTerrain(); break; }
-                if (!m_opt.obj.empty()) { initObj(); break; }
+                if (m_opt.terrain) { initTerrain(); exportObj(); break; }
+                if (!m_opt.obj.empty()) { initObj(); exportObj(); break; }
+                if (!m_opt.export_obj.empty()) throw std::runtime_error("--export-obj needs a resident volume: --terrain or --obj");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -190,6 +194,17 @@ private:
         m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
         m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
     }
+    // The whole box of the resident volume as merged quads, written as an OBJ beside the library's albedos.
+    void exportObj() {
+        if (m_opt.export_obj.empty()) return;
+        uint64_t faces = 0;
+        const std::vector<blok_quad> quads = m_tracer->extractQuads(nullptr, nullptr, false, &faces);
+        char err[512] = {0};
+        if (blok_quads_write_obj(m_opt.export_obj.c_str(), quads.data(), quads.size(), m_materials.handle(), err, sizeof(err)) != BLOK_OK)
+            throw std::runtime_error(std::string("Failed to write OBJ: ") + err);
+        std::cout << "surface: " << faces << " exposed faces -> " << quads.size() << " quads (" << quads.size() * sizeof(blok_quad) / 1e6
+                  << " MB) -> " << m_opt.export_obj << "\n";
+    }
     void update() {
         using clock = std::chrono::steady_clock;
         for (uint32_t f = 0; f < m_opt.frames; ++f) {
@@ -250,6 +265,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--solid")) opt.solid = true;
         else if (!std::strcmp(argv[i], "--terrain")) { opt.terrain = true; opt.terrain_seed = static_cast<uint32_t>(std::strtoul(next(), nullptr, 0)); }
         else if (!std::strcmp(argv[i], "--terrain-size")) opt.terrain_size = std::strtoul(next(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--export-obj")) opt.export_obj = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
