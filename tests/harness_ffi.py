@@ -109,3 +109,88 @@ class HostKernel:
                               width, height, spp, max_bounces, frame_index,
                               *[C.c_void_p(planes[k].ctypes.data) for k in ("color", "world_pos", "normal_roughness", "albedo_metallic")])
         return planes
+
+
+# ---- the dense-grid kernel's body (blok_amd/csrc/hip/dense_core.h) through tests/host_harness/dense_shim.cpp ------------------------
+def build_dense(sanitize: bool = False) -> Path:
+    out = SRC / ("libdense_shim_asan.so" if sanitize else "libdense_shim.so")
+    deps = [SRC / "dense_shim.cpp", SRC / "host_harness_shims.h", ROOT / "blok_amd/csrc/hip/dense_core.h",
+            ROOT / "blok_amd/csrc/hip/trace_core.h", ROOT / "blok_amd/csrc/hip/trace_kernels.h", ROOT / "blok_amd/csrc/hip/tree.h"]
+    if out.exists() and all(d.stat().st_mtime <= out.stat().st_mtime for d in deps):
+        return out
+    cmd = ["g++", "-O1", "-g", "-std=c++20", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", f"-I{ROOT / 'include'}",
+           f"-I{ROOT / 'blok_amd/csrc/hip'}", f"-I{SRC}", "-shared", "-o", os.fspath(out), os.fspath(SRC / "dense_shim.cpp")]
+    if sanitize:
+        cmd[1:1] = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer"]
+    subprocess.run(cmd, check=True)
+    return out
+
+
+def load_dense(path) -> C.CDLL:
+    L = C.CDLL(os.fspath(path))
+    L.ds_new.restype = C.c_void_p
+    L.ds_new.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.ds_free.argtypes = [C.c_void_p]
+    L.ds_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    L.ds_trace_primary.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    L.ds_out_of_grid.restype = C.c_uint64
+    L.ds_trace_steps.restype = C.c_uint32
+    L.ds_trace_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    return L
+
+
+_dense_lib = None
+
+
+class HostDense:
+    """ids[z][y][x] (0 = empty) at `origin`, tiled on the host; global_bits=True reads the occupancy words as the kernel does when
+    they do not fit LDS (the global array), False as it does from its LDS copy.  lib: another build of the shim (the sanitizer one)."""
+
+    def __init__(self, ids: np.ndarray, origin=(0, 0, 0), global_bits: bool = False, lib=None):
+        global _dense_lib
+        if lib is None:
+            if _dense_lib is None:
+                _dense_lib = load_dense(build_dense())
+            lib = _dense_lib
+        self.L = lib
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        nz, ny, nx = ids.shape
+        o = np.asarray(origin, dtype=np.int32)
+        self.global_bits = bool(global_bits)
+        self.h = C.c_void_p(self.L.ds_new(C.c_void_p(ids.ctypes.data), nx, ny, nz, C.c_void_p(o.ctypes.data)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.ds_free(self.h)
+            self.h = None
+
+    def trace_rays(self, rays: np.ndarray) -> np.ndarray:
+        rays = np.ascontiguousarray(rays)
+        out = np.zeros(len(rays), dtype=HIT)
+        self.L.ds_trace_rays(self.h, C.c_void_p(rays.ctypes.data), len(rays), int(self.global_bits), C.c_void_p(out.ctypes.data))
+        self._inside()
+        return out
+
+    def _inside(self):
+        n = self.L.ds_out_of_grid()
+        if n:
+            raise AssertionError(f"{n} walks addressed a tile outside the grid")
+
+    def trace_steps(self, ray: np.ndarray, cap: int = 4096):
+        """(record, axes of the steps in order) of one ray."""
+        ray = np.ascontiguousarray(ray).reshape(1)
+        out = np.zeros(1, dtype=HIT)
+        steps = np.zeros(cap, dtype=np.uint8)
+        n = self.L.ds_trace_steps(self.h, C.c_void_p(ray.ctypes.data), int(self.global_bits), C.c_void_p(steps.ctypes.data), cap, C.c_void_p(out.ctypes.data))
+        self._inside()
+        assert n <= cap
+        return out[0], steps[:n]
+
+    def trace_primary(self, cam: np.ndarray, width: int, height: int, jitter_clip=None) -> np.ndarray:
+        cam = np.ascontiguousarray(cam)
+        out = np.zeros(width * height, dtype=HIT)
+        j = None if jitter_clip is None else np.asarray(jitter_clip, dtype=np.float32)
+        self.L.ds_trace_primary(self.h, C.c_void_p(cam.ctypes.data), width, height, C.c_void_p(j.ctypes.data) if j is not None else None,
+                                int(self.global_bits), C.c_void_p(out.ctypes.data))
+        self._inside()
+        return out
