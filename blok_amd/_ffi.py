@@ -305,6 +305,7 @@ HIP_SYMBOLS = {
                                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_hip_draw_frame_rt_instanced_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                           C.c_void_p, C.POINTER(C.c_uint32)]),
+    "blok_hip_volume_refresh_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_debug_build_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 

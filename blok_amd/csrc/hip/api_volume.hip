@@ -49,6 +49,14 @@ int blok_hip_set_volume_layout(blok_hip_ctx* ctx, int keyed) {
     return BLOK_OK;
 }
 
+int blok_hip_volume_refresh_counts(blok_hip_ctx* ctx, uint64_t out_counts[3]) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (!out_counts) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null output");
+    for (int i = 0; i < 3; ++i) out_counts[i] = ctx->volume.refreshes[i];
+    return BLOK_OK;
+}
+
 int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (ctx->has_volume) {

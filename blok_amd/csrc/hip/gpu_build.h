@@ -76,6 +76,7 @@ struct GpuVolume {
     } scratch;
     // voxels edited since the last build (box-local, half-open); empty = lo > hi
     uint32_t edit_lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, edit_hi[3] = {0, 0, 0};
+    uint64_t refreshes[3] = {0, 0, 0};           // diagnostic: mask refreshes since creation — keyed, an edit's path (a wave per brick, the pyramid in one workgroup); keyed, an upload's path (a lane per brick, a launch per level); general layout
     bool edit_may_add = false;                   // ... and one of those edits may have FILLED a voxel (an ADD brush with a positive value, setVoxel): what the shadow rays' map has to know
 };
 

@@ -443,6 +443,7 @@ GpuBuildStatus volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t
     d.rbx = (hi[0] + 3u) / 4u - d.rx0; d.rby = (hi[1] + 3u) / 4u - d.ry0; d.rbz = (hi[2] + 3u) / 4u - d.rz0;
     const uint64_t total = static_cast<uint64_t>(d.rbx) * d.rby * d.rbz;
     if (!total) return GpuBuildStatus::Ok;
+    ++v->refreshes[2];
     hipLaunchKernelGGL(dense_brick_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, total, v->d_masks, v->d_flag);
     GB_TRY(hipGetLastError());
     return GpuBuildStatus::Ok;
@@ -703,6 +704,7 @@ GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t 
     }
     // an edit (few bricks): a wave per brick, then every level above in one workgroup; an upload (the whole box): a lane per brick, a launch per level
     const bool small = totals[1] <= 65536u && (v->levels < 2 || totals[2] <= 4096u);
+    ++v->refreshes[small ? 0 : 1];
     if (small) {
         hipLaunchKernelGGL(keyed_brick_wave_kernel, dim3(static_cast<uint32_t>(totals[1])), dim3(64), 0, nullptr, k, ranges[1]);
         GB_TRY(hipGetLastError());

@@ -66,6 +66,12 @@ class HipTracer:
         """Diagnostic (blok_hip.h): whether the next volume_create may use the keyed brick layout (default) or the row-major one."""
         self._check(self._lib.blok_hip_set_volume_layout(self._ctx, 1 if keyed else 0))
 
+    def volume_refresh_counts(self):
+        """Diagnostic (blok_hip_debug.h): mask refreshes since volume_create as (keyed edit path, keyed upload path, general layout)."""
+        out = (C.c_uint64 * 3)()
+        self._check(self._lib.blok_hip_volume_refresh_counts(self._ctx, out))
+        return tuple(int(v) for v in out)
+
     def volume_destroy(self):
         self._check(self._lib.blok_hip_volume_destroy(self._ctx))
 

@@ -32,6 +32,11 @@ int blok_hip_download_tree(const blok_hip_ctx* ctx, void* nodes_out, size_t node
  * words, rebuilt by scans over the pyramid (~0.2 ms), whenever the box's 64^(levels-1) mask words are affordable.  Both give the same
  * node and material arrays, byte for byte (tests/test_brush.py). */
 int blok_hip_set_volume_layout(blok_hip_ctx* ctx, int keyed);
+/* Diagnostic / test hook: how the resident volume's brick masks have been refreshed since blok_hip_volume_create, one count per refresh
+ * (an upload, a brush, a set_voxels call, ...): [0] keyed layout, the path of an edit — a wave per brick of the edit's range and the
+ * occupancy words above it in one workgroup — [1] keyed layout, the path of a range of more than 65 536 bricks or 4096 level-2 cells —
+ * a lane per brick, a launch per level — [2] general layout.  Every path computes the same masks (tests/test_volume_rebuild_gpu.py). */
+int blok_hip_volume_refresh_counts(blok_hip_ctx* ctx, uint64_t out_counts[3]);
 
 /* ------------------------------------------------------------ path kernel */
 /* Scheduling knob of the path kernel (no reference counterpart): 0 = every lane walks whatever ray it has pending; 1 = a wave walks

@@ -90,6 +90,16 @@ class HostKernel:
             lib().hh_free(self.h)
             self.h = None
 
+    def tree_nodes(self):
+        """(nodes as (n, 4) uint32, origin) of the host builder's tree (copies)."""
+        L = lib()
+        L.hh_tree_nodes.restype = C.c_void_p
+        L.hh_tree_nodes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+        count, origin = C.c_size_t(), (C.c_int32 * 3)()
+        p = L.hh_tree_nodes(self.h, C.byref(count), origin)
+        buf = (C.c_char * (count.value * 16)).from_address(p)
+        return np.frombuffer(buf, dtype=np.uint32).reshape(-1, 4).copy(), tuple(origin)
+
     def trace_rays(self, rays: np.ndarray) -> np.ndarray:
         out = np.zeros(len(rays), dtype=HIT)
         lib().hh_trace_rays(self.h, C.c_void_p(rays.ctypes.data), len(rays), C.c_void_p(out.ctypes.data))
