@@ -46,6 +46,8 @@ INSTANCE_NONE = 0xFFFFFFFF
 # = blok_quad: one merged quad of a volume's surface, 32 bytes
 QUAD = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("reserved", "<u4")])
 QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
+STAMP_SET, STAMP_KEEP, STAMP_ERASE = 0, 1, 2      # = BLOK_STAMP_*
+CAPTURE_CUT = 1                                   # = BLOK_CAPTURE_CUT
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
 
@@ -76,6 +78,12 @@ class TerrainParams(C.Structure):
                 ("cave_roof", C.c_uint32), ("soil_depth", C.c_uint32), ("ore_cell_log2", C.c_uint32), ("ore_threshold", C.c_uint32),
                 ("surface_material", C.c_uint32), ("soil_material", C.c_uint32), ("rock_material", C.c_uint32), ("ore_material", C.c_uint32),
                 ("density", C.c_float), ("flags", C.c_uint32)]
+
+
+class ModelInfo(C.Structure):
+    """= blok_model_info (include/blok_hip_debug.h)."""
+    _fields_ = [("levels", C.c_uint32), ("origin", C.c_int32 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("n_nodes", C.c_uint64), ("n_materials", C.c_uint64)]
 
 
 class WorldStats(C.Structure):
@@ -159,6 +167,10 @@ HOST_SYMBOLS = {
     "blok_quads_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "blok_quads_write_obj": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
+    "blok_capture_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -281,6 +293,10 @@ HIP_SYMBOLS = {
     "blok_hip_volume_extract_quads": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint64),
                                                 C.POINTER(C.c_uint64)]),
     "blok_hip_volume_quads_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_stamp_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_capture_model": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint32),
+                                                C.POINTER(C.c_uint64)]),
+    "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_abi_version": (C.c_uint32, []),

@@ -29,6 +29,24 @@ int blok_hip_download_tree(const blok_hip_ctx* ctx, void* nodes_out, size_t node
     return BLOK_OK;
 }
 
+int blok_hip_download_model(blok_hip_ctx* ctx, uint32_t model, void* nodes_out, size_t node_capacity, uint32_t* materials_out, size_t material_capacity,
+                            blok_model_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    const blok::ModelDesc& m = ctx->models.desc[model];
+    if ((nodes_out && node_capacity < m.n_nodes) || (materials_out && material_capacity < m.n_materials))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "download_model: output smaller than the model's array");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (nodes_out && m.n_nodes) BLOK_HIP_TRY(ctx, hipMemcpy(nodes_out, m.nodes, m.n_nodes * sizeof(blok::TreeNode), hipMemcpyDeviceToHost));
+    if (materials_out && m.n_materials) BLOK_HIP_TRY(ctx, hipMemcpy(materials_out, m.materials, m.n_materials * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_info) {
+        out_info->levels = m.levels;
+        for (int a = 0; a < 3; ++a) { out_info->origin[a] = m.origin[a]; out_info->lo[a] = m.lo[a]; out_info->hi[a] = m.hi[a]; }
+        out_info->n_nodes = m.n_nodes; out_info->n_materials = m.n_materials;
+    }
+    return BLOK_OK;
+}
+
 // The pre-pass alone: start parameter (and node visits) per beam tile of the rectangle, to the host.
 int blok_hip_beam_prepass(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                           float* out_t0_host, uint32_t* out_visits_host, size_t capacity) {

@@ -36,7 +36,6 @@ int upload_models(blok_hip_ctx* ctx) {
     return BLOK_OK;
 }
 
-// The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.
 int check_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) {
     if (n && !inst) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
     for (uint32_t i = 0; i < n; ++i) {
@@ -106,6 +105,27 @@ blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs&
 
 }  // namespace
 
+int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) { return check_table(ctx, inst, n); }
+
+int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, uint32_t* out_model) {
+    // frames in flight may read the descriptor array that the upload replaces
+    hipError_t e = hipDeviceSynchronize();
+    int rc = BLOK_OK;
+    if (e != hipSuccess) rc = set_error(ctx, BLOK_ERR_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
+    if (rc == BLOK_OK) {
+        ctx->models.desc.push_back(m);
+        rc = upload_models(ctx);
+        if (rc != BLOK_OK) ctx->models.desc.pop_back();
+    }
+    if (rc != BLOK_OK) {
+        (void)hipFree(const_cast<uint4*>(m.nodes));
+        (void)hipFree(const_cast<uint32_t*>(m.materials));
+        return rc;
+    }
+    *out_model = static_cast<uint32_t>(ctx->models.desc.size() - 1u);
+    return BLOK_OK;
+}
+
 blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
                                  uint32_t n_prev) {
     blok::MotionTables M{};
@@ -151,14 +171,9 @@ int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t*
         return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("model upload: ") + hipGetErrorString(e));
     }
     m.nodes = nodes; m.materials = mats; m.levels = tree.levels;
+    m.n_nodes = static_cast<uint32_t>(tree.nodes.size()); m.n_materials = static_cast<uint32_t>(tree.materials.size());
     for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = lo[a]; m.hi[a] = hi[a] + 1; }
-    // frames in flight may read the descriptor array that the upload replaces
-    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
-    ctx->models.desc.push_back(m);
-    const int rc = upload_models(ctx);
-    if (rc != BLOK_OK) return rc;
-    *out_model = static_cast<uint32_t>(ctx->models.desc.size() - 1u);
-    return BLOK_OK;
+    return add_model(ctx, m, out_model);
 }
 
 int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {

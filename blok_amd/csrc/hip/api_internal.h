@@ -243,6 +243,12 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
                  const blok::TileFrames* frames = nullptr);
 // api_instances.hip
 void free_models(blok_hip_ctx* ctx);
+// The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.
+int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n);
+// The tail of every entry that makes a model (blok_hip_model_create, blok_hip_volume_capture_model): takes the two device arrays into the
+// store under the next id, refreshes the device copy of the descriptors and the stack depth the kernels need.  Synchronises the device.
+// On failure the arrays are freed and no id is consumed.
+int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, uint32_t* out_model);
 // The id plane and both tables of an object-motion pass (instance_motion.h) with the context's model store and voxel size.
 blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
                                  uint32_t n_prev);

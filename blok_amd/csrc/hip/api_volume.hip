@@ -1,8 +1,10 @@
 // C ABI, device-resident dense voxel store (include/blok_hip.h: blok_hip_volume_*; kernels in gpu_build.hip).
 #include "api_internal.h"
 #include "../common/terrain_core.h"
+#include "../common/stamp_core.h"
 #include <chrono>
 #include <cstdlib>
+#include <limits>
 
 using namespace blok_api;
 
@@ -178,6 +180,69 @@ int blok_hip_volume_quads_download(blok_hip_ctx* ctx, blok_quad* out_host, uint6
     if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: null output");
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->d_quads + first, count * sizeof(blok_quad), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placements_host, uint32_t n_placements, int mode, float density,
+                                 uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    rc = check_instance_table(ctx, placements_host, n_placements);
+    if (rc != BLOK_OK) return rc;
+    if (!blok::stamp::mode_known(mode)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_models: unknown mode");
+    if (mode != BLOK_STAMP_ERASE && (!std::isfinite(density) || !(density > 0.0f)))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_models: density must be finite and > 0");
+    std::vector<blok::StampModel> models(n_placements);
+    for (uint32_t i = 0; i < n_placements; ++i) {
+        const blok::ModelDesc& d = ctx->models.desc[placements_host[i].model];
+        blok::StampModel& m = models[i];
+        m.nodes = d.nodes; m.materials = d.materials; m.levels = d.levels;
+        for (int a = 0; a < 3; ++a) { m.origin[a] = d.origin[a]; m.lo[a] = d.lo[a]; m.hi[a] = d.hi[a]; }
+    }
+    std::string why;
+    // (edits are enqueued on the null stream, and so is this: placement after placement, in stream order)
+    return volume_status(ctx, blok::gpu_volume_stamp(&ctx->volume, models.data(), placements_host, n_placements, mode, density, out_n_voxels, &why), why);
+}
+
+int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags, uint32_t* out_model,
+                                  uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags & ~BLOK_CAPTURE_CUT) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: unknown flag bits");
+    if (!out_model) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: null output id");
+    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: one region pointer is null");
+    if (ctx->models.desc.size() >= std::numeric_limits<uint32_t>::max() - 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model ids exhausted");
+    blok::GpuVolume& v = ctx->volume;
+    const int64_t dims[3] = {v.nx, v.ny, v.nz};
+    uint32_t lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
+        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: region_lo above region_hi");
+        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "capture_model: region leaves the resident volume");
+        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
+    }
+    std::string why;
+    blok::GpuTree tree;
+    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+    uint64_t n_voxels = 0;
+    const blok::GpuBuildStatus st = blok::gpu_volume_capture(&v, lo, hi, &tree, box_lo, box_hi, &n_voxels, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    if (!n_voxels) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "capture_model: the region holds no filled voxel");
+    blok::ModelDesc m{};
+    m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
+    m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
+    for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
+    rc = add_model(ctx, m, out_model);
+    if (rc != BLOK_OK) return rc;                      // (nothing is cut when there is no model)
+    if (out_n_voxels) *out_n_voxels = n_voxels;
+    if (flags & BLOK_CAPTURE_CUT) {
+        // the captured voxels are the filled voxels of the region, and all of them lie in the model's box
+        uint32_t clo[3], chi[3];
+        for (int a = 0; a < 3; ++a) { clo[a] = lo[a] + static_cast<uint32_t>(box_lo[a]); chi[a] = lo[a] + static_cast<uint32_t>(box_hi[a]); }
+        return volume_status(ctx, blok::gpu_volume_clear_filled(&v, clo, chi, &why), why);
+    }
     return BLOK_OK;
 }
 

@@ -105,6 +105,24 @@ GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_para
 // nothing.  Without BLOK_QUADS_COUNT_ONLY *out_quads is a new device array of *out_n_quads records (null for none), the caller's to free.
 GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, blok_quad** out_quads,
                                         uint64_t* out_n_quads, uint64_t* out_n_faces, std::string* why);
+// = blok_hip_volume_stamp_models (include/blok_hip.h; stamp_kernels.hip).  The placements have passed the entry's checks; models[i] is
+// the model of placements[i], read in device memory through its tree.  One launch and one refresh per placement, in table order on the
+// null stream; the only wait is the one for the count at the end.
+struct StampModel {
+    const uint4* nodes; const uint32_t* materials;      // tree.h, device memory
+    uint32_t levels;
+    int32_t origin[3], lo[3], hi[3];                    // the tree's corner and the box of its voxels, local coordinates
+};
+GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements, int mode,
+                                float density, uint64_t* out_n_voxels, std::string* why);
+// = blok_hip_volume_capture_model (include/blok_hip.h) over the box-local region [lo, hi): the tree of the region's filled voxels in the
+// lattice whose voxel (0, 0, 0) is the region's corner, built on the device.  On Ok with *out_n_voxels > 0, out->d_nodes /
+// d_materials are new device arrays, the caller's to free, and box_lo / box_hi the tight box of the voxels (half open, model
+// coordinates); with *out_n_voxels == 0 (nothing filled) there is no tree.  Reads the store, changes nothing.
+GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3],
+                                  int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why);
+// Clears (density 0, id 0) the filled voxels of the box-local box [lo, hi) and refreshes it: BLOK_CAPTURE_CUT.
+GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

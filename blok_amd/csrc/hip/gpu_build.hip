@@ -325,6 +325,7 @@ struct DenseCtx {
     uint32_t bx, by, bz;          // bricks per axis
     uint32_t levels;
     uint32_t rx0, ry0, rz0, rbx, rby, rbz;   // brick sub-range handled by dense_brick_kernel (whole grid: 0,0,0,bx,by,bz)
+    uint32_t ox, oy, oz;          // voxel (0,0,0) of the brick grid in the arrays (0 but for a captured region, whose grid is the model's own)
 };
 
 __device__ __forceinline__ bool dense_filled(const DenseCtx& d, size_t i) {
@@ -376,7 +377,7 @@ __global__ __launch_bounds__(256) void dense_material_kernel(const DenseCtx d, c
     if (!((mask >> bit) & 1ull)) return;
     const uint32_t g = src_sorted[i];
     const uint32_t vx = (g % d.bx) * 4u + (bit & 3u), vy = ((g / d.bx) % d.by) * 4u + ((bit >> 2) & 3u), vz = (g / (d.bx * d.by)) * 4u + (bit >> 4);
-    materials[mat_base[i] + __popcll(mask & ((1ull << bit) - 1ull))] = d.ids[(static_cast<size_t>(vz) * d.ny + vy) * d.nx + vx];
+    materials[mat_base[i] + __popcll(mask & ((1ull << bit) - 1ull))] = d.ids[(static_cast<size_t>(d.oz + vz) * d.ny + (d.oy + vy)) * d.nx + d.ox + vx];
 }
 
 }  // namespace
@@ -970,6 +971,148 @@ GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radiu
     hipLaunchKernelGGL(volume_brush_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, b);
     GB_TRY(hipGetLastError());
     return volume_refresh(v, lo, hi, why);
+}
+
+// ---- a region of the volume as a model (gpu_build.h: gpu_volume_capture) ------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kBoundSlots = 16, kBoundWords = 16;      // per slot: min x y z, max x y z (region-local voxels), 64-bit count at words 6..7; 64 bytes apart
+
+struct RegionCtx {
+    const float* density;
+    uint32_t nx, ny;                 // the volume's row and slice
+    uint32_t lo[3], ext[3];          // the region: box-local corner and extent
+};
+
+// Tight bounds and count of the region's filled voxels.  A wave takes rows (64 consecutive x of one (y, z)) in a grid-stride loop and keeps
+// its bounds in registers — a row's x bounds are the ends of its ballot — so a wave issues at most seven atomics, at the end, to its slot.
+__global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, uint64_t n_rows, uint32_t segs, uint32_t* bounds) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * 4u + (threadIdx.x >> 6), n_waves = static_cast<uint64_t>(gridDim.x) * 4u;
+    uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
+    uint64_t count = 0;
+    for (uint64_t row = wave; row < n_rows; row += n_waves) {
+        const uint32_t seg = static_cast<uint32_t>(row % segs), y = static_cast<uint32_t>((row / segs) % r.ext[1]), z = static_cast<uint32_t>(row / (static_cast<uint64_t>(segs) * r.ext[1]));
+        const uint32_t x = seg * 64u + lane;
+        const bool filled = x < r.ext[0] && r.density[(static_cast<size_t>(r.lo[2] + z) * r.ny + (r.lo[1] + y)) * r.nx + r.lo[0] + x] > 0.0f;
+        const uint64_t votes = __ballot(filled);
+        if (!votes) continue;
+        mn[0] = min(mn[0], seg * 64u + static_cast<uint32_t>(__ffsll(static_cast<unsigned long long>(votes)) - 1));
+        mx[0] = max(mx[0], seg * 64u + 63u - static_cast<uint32_t>(__clzll(static_cast<long long>(votes))));
+        mn[1] = min(mn[1], y); mx[1] = max(mx[1], y); mn[2] = min(mn[2], z); mx[2] = max(mx[2], z);
+        count += static_cast<uint64_t>(__popcll(votes));
+    }
+    if (lane != 0u || !count) return;
+    uint32_t* slot = bounds + (wave % kBoundSlots) * kBoundWords;
+    for (int a = 0; a < 3; ++a) { atomicMin(slot + a, mn[a]); atomicMax(slot + 3 + a, mx[a]); }
+    atomicAdd(reinterpret_cast<unsigned long long*>(slot + 6), static_cast<unsigned long long>(count));
+}
+
+// One wave per brick of the MODEL's 4-grid (in general not the volume's brick grid), lane b = voxel b: the brick's mask from the voxels that
+// are filled and inside the tight box [t0, t1) of the region's filled voxels (grid voxels, i.e. from the tree's corner).
+__global__ __launch_bounds__(64) void region_brick_kernel(const DenseCtx d, uint32_t t0x, uint32_t t0y, uint32_t t0z, uint32_t t1x, uint32_t t1y, uint32_t t1z,
+                                                          uint64_t* masks, uint32_t* non_empty) {
+    const uint32_t b = threadIdx.x;
+    const uint32_t vx = blockIdx.x * 4u + (b & 3u), vy = blockIdx.y * 4u + ((b >> 2) & 3u), vz = blockIdx.z * 4u + (b >> 4);
+    const bool inside = vx >= t0x && vx < t1x && vy >= t0y && vy < t1y && vz >= t0z && vz < t1z;
+    const bool filled = inside && d.density[(static_cast<size_t>(d.oz + vz) * d.ny + (d.oy + vy)) * d.nx + d.ox + vx] > 0.0f;
+    const uint64_t mask = __ballot(filled);
+    if (b == 0u) {
+        const size_t g = blockIdx.x + (static_cast<size_t>(blockIdx.z) * d.by + blockIdx.y) * d.bx;
+        masks[g] = mask;
+        non_empty[g] = mask != 0ull;
+    }
+}
+
+// One lane per voxel of the box: a filled voxel becomes (0, 0).
+__global__ __launch_bounds__(256) void clear_filled_kernel(float* density, uint32_t* ids, uint32_t nx, uint32_t ny, uint32_t x0, uint32_t y0, uint32_t z0,
+                                                           uint32_t ex, uint32_t ey, uint64_t total) {
+    const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (tid >= total) return;
+    const uint32_t x = x0 + static_cast<uint32_t>(tid % ex), y = y0 + static_cast<uint32_t>((tid / ex) % ey), z = z0 + static_cast<uint32_t>(tid / (static_cast<uint64_t>(ex) * ey));
+    const size_t i = (static_cast<size_t>(z) * ny + y) * nx + x;
+    if (density[i] > 0.0f) { density[i] = 0.0f; ids[i] = 0u; }
+}
+
+}  // namespace
+
+GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
+                                  uint64_t* out_n_voxels, std::string* why) {
+    *out = GpuTree{};
+    *out_n_voxels = 0;
+    if (v->cells() > 0xFFFFFFFFull) { *why = "capture_model: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
+    DeviceBuffers mem;
+    // 1. the tight box of the region's filled voxels
+    RegionCtx r{};
+    r.density = v->d_density; r.nx = v->nx; r.ny = v->ny;
+    for (int a = 0; a < 3; ++a) { r.lo[a] = lo[a]; r.ext[a] = hi[a] - lo[a]; }
+    uint32_t* d_bounds;
+    GB_TRY(mem.alloc(&d_bounds, kBoundSlots * kBoundWords));
+    std::vector<uint32_t> bounds(kBoundSlots * kBoundWords, 0u);
+    for (uint32_t s = 0; s < kBoundSlots; ++s) for (int a = 0; a < 3; ++a) bounds[s * kBoundWords + a] = 0xFFFFFFFFu;
+    GB_TRY(hipMemcpy(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const uint32_t segs = (r.ext[0] + 63u) / 64u;
+    const uint64_t n_rows = static_cast<uint64_t>(segs) * r.ext[1] * r.ext[2];
+    hipLaunchKernelGGL(region_bounds_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r, n_rows, segs, d_bounds);
+    GB_TRY(hipGetLastError());
+    GB_TRY(hipMemcpy(bounds.data(), d_bounds, bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t t0[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, t1[3] = {0u, 0u, 0u};
+    uint64_t count = 0;
+    for (uint32_t s = 0; s < kBoundSlots; ++s) {
+        const uint32_t* w = bounds.data() + s * kBoundWords;
+        for (int a = 0; a < 3; ++a) { t0[a] = std::min(t0[a], w[a]); t1[a] = std::max(t1[a], w[3 + a]); }
+        count += static_cast<uint64_t>(w[6]) | (static_cast<uint64_t>(w[7]) << 32);
+    }
+    if (!count) return GpuBuildStatus::Ok;                       // nothing filled: no tree
+    // 2. the model's lattice, as the host builder lays it out (tree_build.cpp): corner at the multiple of 16 below the lowest voxel.
+    //    (A volume spans at most 4^7 = 16 384 voxels per axis, gpu_volume_create, so region-local coordinates stay below the host builder's
+    //    int16 limit and capture refuses nothing that blok_hip_model_create would accept or the other way round.)
+    int32_t origin[3];
+    int64_t extent = 1;
+    for (int a = 0; a < 3; ++a) {
+        origin[a] = static_cast<int32_t>(t0[a] & ~15u);          // region-local coordinates are never negative
+        extent = std::max<int64_t>(extent, int64_t(t1[a]) - origin[a] + 1);
+        box_lo[a] = static_cast<int32_t>(t0[a]); box_hi[a] = static_cast<int32_t>(t1[a]) + 1;
+    }
+    uint32_t levels = 1;
+    while ((int64_t(1) << (2 * levels)) < extent) ++levels;
+    if (levels > kMaxLevels) { *why = "world extent exceeds 4^7 voxels per axis"; return GpuBuildStatus::Unsupported; }
+    // 3. brick masks on the model's own 4-grid, then the common tail of the builders
+    DenseCtx d = volume_ctx(*v);
+    d.levels = levels;
+    d.bx = (t1[0] - origin[0]) / 4u + 1u; d.by = (t1[1] - origin[1]) / 4u + 1u; d.bz = (t1[2] - origin[2]) / 4u + 1u;
+    d.rbx = d.bx; d.rby = d.by; d.rbz = d.bz;
+    d.ox = lo[0] + origin[0]; d.oy = lo[1] + origin[1]; d.oz = lo[2] + origin[2];
+    const uint64_t total = static_cast<uint64_t>(d.bx) * d.by * d.bz;
+    uint64_t* d_masks; uint32_t *d_flag, *d_slot;
+    GB_TRY(mem.alloc(&d_masks, total)); GB_TRY(mem.alloc(&d_flag, total + 1)); GB_TRY(mem.alloc(&d_slot, total + 1));
+    GB_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
+    hipLaunchKernelGGL(region_brick_kernel, dim3(d.bx, d.by, d.bz), dim3(64), 0, nullptr, d, t0[0] - origin[0], t0[1] - origin[1], t0[2] - origin[2],
+                       t1[0] - origin[0] + 1u, t1[1] - origin[1] + 1u, t1[2] - origin[2] + 1u, d_masks, d_flag);
+    GB_TRY(hipGetLastError());
+    const GpuBuildStatus st = finish_from_masks(mem, total, d_masks, d_flag, d_slot, levels, origin,
+        [&](const uint32_t* slot, uint64_t* keys, uint32_t* src) {
+            hipLaunchKernelGGL(dense_key_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, d_masks, slot, total, keys, src);
+        },
+        [&](const uint64_t* masks_sorted, const uint32_t* src_sorted, const uint32_t* mat_base, uint32_t n_bricks, uint32_t* materials) {
+            hipLaunchKernelGGL(dense_material_kernel, dim3(blocks_for(static_cast<uint64_t>(n_bricks) * 64u)), dim3(256), 0, nullptr,
+                               d, masks_sorted, src_sorted, mat_base, n_bricks, materials);
+        }, out, why);
+    if (st == GpuBuildStatus::UseHostBuilder) { *why = "capture_model: the device build found no brick in a region that holds voxels"; return GpuBuildStatus::HipError; }
+    if (st == GpuBuildStatus::Ok) *out_n_voxels = out->n_voxels;
+    return st;
+}
+
+GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
+    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
+    const uint32_t ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+    const uint64_t total = static_cast<uint64_t>(ex) * ey * ez;
+    hipLaunchKernelGGL(clear_filled_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, v->d_density, v->d_ids, v->nx, v->ny, lo[0], lo[1], lo[2], ex, ey, total);
+    GB_TRY(hipGetLastError());
+    const GpuBuildStatus st = volume_refresh(v, lo, hi, why);      // (clearing never fills: edit_may_add stays as it was)
+    GB_TRY(hipDeviceSynchronize());                                // blocking, as gpu_volume_set_voxels is
+    return st;
 }
 
 GpuBuildStatus gpu_volume_build(GpuVolume* v, GpuTree* out, std::string* why) {

@@ -14,6 +14,7 @@
 #define BLOK_INSTANCE_CORE_H
 
 #include "trace_core.h"
+#include "../common/stamp_core.h"
 
 // The limits are checked by the host entries too.
 #ifdef BLOK_TRACE_HOST_HARNESS
@@ -32,7 +33,7 @@ struct ModelDesc {
     uint32_t levels;
     int32_t  origin[3];
     int32_t  lo[3], hi[3];
-    uint32_t pad[2];
+    uint32_t n_nodes, n_materials;   // lengths of the two arrays (the kernels never look at them; blok_hip_download_model does)
 };
 static_assert(sizeof(ModelDesc) == 64, "one model descriptor is 64 bytes");
 static_assert(sizeof(blok_instance) == 32, "one instance record is 32 bytes");
@@ -58,11 +59,7 @@ BLOK_HD void instance_world_span(const blok_instance& I, const ModelDesc& M, uin
 }
 
 // The record itself is well formed: axis a permutation of 0, 1, 2, only the three flip bits, reserved words zero.
-BLOK_HD bool instance_well_formed(const blok_instance& I) {
-    const uint32_t a0 = I.axis[0], a1 = I.axis[1], a2 = I.axis[2];
-    const bool perm = a0 < 3u && a1 < 3u && a2 < 3u && ((1u << a0) | (1u << a1) | (1u << a2)) == 7u;
-    return perm && I.flip < 8u && (I.reserved[0] | I.reserved[1] | I.reserved[2]) == 0u;
-}
+BLOK_HD bool instance_well_formed(const blok_instance& I) { return stamp::well_formed(I); }
 
 // Everything the blocking entries check, for the kernels (an instance of the device entries that fails it is skipped).
 BLOK_HD bool instance_usable(const blok_instance& I, const ModelDesc& M) {

@@ -146,6 +146,26 @@ class HipTracer:
             self._check(self._lib.blok_hip_volume_quads_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
         return out
 
+    def volume_stamp_models(self, placements, mode: int = _ffi.STAMP_SET, density: float = 1.0) -> int:
+        """Stamps placed models into the resident volume (blok_hip.h: blok_hip_volume_stamp_models): placements are INSTANCE records
+        (blok_amd.stamp.placement), applied in table order; mode _ffi.STAMP_SET / STAMP_KEEP / STAMP_ERASE.  Returns the voxels written.
+        The next volume_rebuild installs the world."""
+        inst = np.ascontiguousarray(placements, dtype=INSTANCE).reshape(-1)
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_stamp_models(self._ctx, _ffi.ptr(inst) if len(inst) else None, len(inst), int(mode), float(density), C.byref(n)))
+        return int(n.value)
+
+    def volume_capture_model(self, lo=None, hi=None, cut: bool = False) -> int:
+        """A region of the resident volume (world voxels, half open; both None = the whole box) as a new model, in the lattice whose voxel
+        (0, 0, 0) is the region's corner (blok_hip.h: blok_hip_volume_capture_model); cut = also clear the captured voxels.  Returns the
+        model id; the model's voxel count is in last_capture_voxels."""
+        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
+        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        model, n = C.c_uint32(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_capture_model(self._ctx, rlo, rhi, _ffi.CAPTURE_CUT if cut else 0, C.byref(model), C.byref(n)))
+        self.last_capture_voxels = int(n.value)
+        return int(model.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))
@@ -480,6 +500,16 @@ class HipTracer:
 
     def model_destroy(self, model: int):
         self._check(self._lib.blok_hip_model_destroy(self._ctx, int(model)))
+
+    def model_download(self, model: int):
+        """Diagnostic (blok_hip_debug.h: blok_hip_download_model): (nodes as (n, 4) uint32, material ids, info) of a model as it lies in
+        device memory; info is a dict of levels, origin, lo, hi."""
+        info = _ffi.ModelInfo()
+        self._check(self._lib.blok_hip_download_model(self._ctx, int(model), None, 0, None, 0, C.byref(info)))
+        nodes = np.zeros((int(info.n_nodes), 4), dtype=np.uint32)
+        mats = np.zeros(int(info.n_materials), dtype=np.uint32)
+        self._check(self._lib.blok_hip_download_model(self._ctx, int(model), _ffi.ptr(nodes), len(nodes), _ffi.ptr(mats) if len(mats) else None, len(mats), None))
+        return nodes, mats, {"levels": int(info.levels), "origin": tuple(info.origin), "lo": tuple(info.lo), "hi": tuple(info.hi)}
 
     def check_instances(self, instances: np.ndarray):
         inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)

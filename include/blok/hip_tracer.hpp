@@ -256,6 +256,20 @@ public:
         for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_quads_download(m_ctx, quads.data() + at, at, std::min(page, n - at)));
         return quads;
     }
+    // Placed models written into the resident volume, in table order (blok_hip_volume_stamp_models; mode BLOK_STAMP_SET / KEEP / ERASE):
+    // returns the voxels written.  A later rebuildVolume installs the world.
+    uint64_t stampModels(const std::vector<blok_instance>& placements, int mode = BLOK_STAMP_SET, float density = 1.0f) {
+        uint64_t n = 0;
+        check(blok_hip_volume_stamp_models(m_ctx, placements.data(), static_cast<uint32_t>(placements.size()), mode, density, &n));
+        return n;
+    }
+    // A region of the resident volume (world voxels, half-open; both null = the whole box) as a new model whose voxel (0, 0, 0) is the
+    // region's corner (blok_hip_volume_capture_model): returns the model id.  cut: the captured voxels are cleared in the volume.
+    uint32_t captureModel(const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr, bool cut = false, uint64_t* outVoxels = nullptr) {
+        uint32_t model = 0;
+        check(blok_hip_volume_capture_model(m_ctx, regionLo, regionHi, cut ? BLOK_CAPTURE_CUT : 0u, &model, outVoxels));
+        return model;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -567,7 +567,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 
 /* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances.
  * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume.
- * 1.5: procedural terrain into the resident volume.  1.6: the volume's surface as merged quads. */
+ * 1.5: procedural terrain into the resident volume.  1.6: the volume's surface as merged quads.
+ * 1.7: models stamped into the resident volume, regions of it captured as models. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -592,7 +593,7 @@ uint32_t blok_hip_abi_version(void);
  * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
  * Scope.  The primary frame, explicit rays and the path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced
  *   below); the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay world-only (they never receive an
- *   instance table). */
+ *   instance table); an instance that has stopped moving can be baked into the resident volume (blok_hip_volume_stamp_models below). */
 typedef struct blok_instance {
     uint32_t model;
     int32_t  offset[3];   /* voxels, world lattice */
@@ -691,6 +692,46 @@ int blok_hip_denoise_instanced_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_
 int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
                                             const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
                                             uint32_t* out_rgba8_host, uint32_t* out_frame_count);
+
+/* ------------------------------------------------------------- models into the resident volume and back (ABI 1.7)
+ * The two stores of voxel data in HBM — the resident volume and the instanced models — joined on the device.  Integer arithmetic only: one
+ * right answer, bit-identical on the host (blok_stamp_voxels / blok_capture_voxels, blok_world.h) and on the device.  Both calls block.
+ *
+ * blok_hip_volume_stamp_models writes placed models into the volume.  The model is read where it lives (its tree), never as a voxel list.
+ *  - Placement: a blok_instance.  A filled model voxel v' (local lattice, the coordinates given to blok_hip_model_create) lands on the world
+ *    voxel of "Record back to world space" above: w[axis[k]] = offset[axis[k]] + v'_k, or offset[axis[k]] - 1 - v'_k when flip bit k is set.
+ *    A baked instance therefore lies exactly where the traced one was seen.  The sums are 64-bit before clipping.
+ *  - Written set: the mapped filled voxels inside the volume's box; voxels outside are clipped silently, a placement wholly outside writes
+ *    nothing.  BLOK_STAMP_SET: density[w] = density, ids[w] = the model voxel's material.  BLOK_STAMP_KEEP: the same, only where the
+ *    volume's voxel is empty (density > 0 is false: 0, negative and NaN are empty).  BLOK_STAMP_ERASE: density[w] = 0.0f, ids[w] = 0 (the
+ *    density argument is ignored).  Empty model cells never touch the volume.
+ *  - Order: the result equals n_placements successive calls in table order (a later placement wins over an earlier one).
+ *  - out_n_voxels (may be NULL): voxels written, summed over the placements; for KEEP the voxels that were empty and got filled.
+ *  - Afterwards masks, occupancy words and dirty flags are those blok_hip_volume_set_voxels leaves for the same writes, refreshed over each
+ *    placement's clipped box (never over their union); the next blok_hip_volume_rebuild installs the world.
+ *  - Errors, nothing written.  BLOK_ERR_INVALID_ARG: a placement that fails what blok_hip_check_instances checks (same messages), an
+ *    unknown mode, for SET and KEEP a density that is not finite or <= 0, a null table with a non-zero count.  BLOK_ERR_NO_WORLD: no
+ *    volume.  BLOK_ERR_UNSUPPORTED: a volume above 2^32 cells.  n_placements == 0 is BLOK_OK.
+ *
+ * blok_hip_volume_capture_model makes a region of the volume a model, without downloading it.
+ *  - Region: world voxels, half open; both pointers NULL = the whole box (the convention of blok_hip_volume_extract_quads).
+ *  - The new model is exactly the one blok_hip_model_create builds from the list {(w - region_lo, ids[w]) : w in region, density[w] > 0}
+ *    (with NULL pointers region_lo is the box's origin): the same node and material arrays byte for byte, the same levels, origin and box.
+ *    A filled voxel with material id 0 is a filled voxel.  *out_model is the next model id.
+ *  - out_n_voxels (may be NULL): the model's voxels.
+ *  - BLOK_CAPTURE_CUT: after the model exists the captured voxels are cleared in the volume (density 0, id 0) and the masks refreshed.  If
+ *    the model cannot be built, nothing is cut.
+ *  - Errors.  BLOK_ERR_INVALID_ARG: exactly one region pointer NULL, lo > hi on an axis, unknown flag bits, out_model NULL.
+ *    BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume above 2^32 cells, or a region that holds no filled voxel (then no model
+ *    is created, no id consumed, *out_n_voxels = 0).  BLOK_ERR_NO_WORLD: no volume. */
+#define BLOK_STAMP_SET   0   /* write every filled model voxel */
+#define BLOK_STAMP_KEEP  1   /* ... only where the volume is empty */
+#define BLOK_STAMP_ERASE 2   /* clear the volume where the model is filled */
+int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placements_host, uint32_t n_placements,
+                                 int mode, float density, uint64_t* out_n_voxels);
+#define BLOK_CAPTURE_CUT 1u   /* afterwards clear the captured voxels in the volume (density 0, id 0) */
+int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                                  uint32_t* out_model, uint64_t* out_n_voxels);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -194,6 +194,19 @@ int blok_hip_multi_debug_deny_peer_access(blok_hip_multi* m, int deny);
 int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_dev, uint32_t n_instances, void* out_nodes_host, size_t capacity,
                               uint32_t* out_count);
 
+/* Read-back of an instanced model (blok_hip_model_create, blok_hip_volume_capture_model), for the tests that pin a captured model byte for
+ * byte: the node array (16 bytes per node, root first) and the material array (one id per voxel) as they lie in device memory, and the
+ * model's lattice.  Either array pointer may be NULL (then its capacity is not looked at); out_info may be NULL.  BLOK_ERR_INVALID_ARG: an
+ * unknown or destroyed model, or a capacity (in elements) below the model's count.  Blocking. */
+typedef struct blok_model_info {
+    uint32_t levels;              /* the tree covers 4^levels voxels per axis from origin */
+    int32_t  origin[3];           /* local coordinate of the tree's corner */
+    int32_t  lo[3], hi[3];        /* the box of the model's voxels, half open, local coordinates */
+    uint64_t n_nodes, n_materials;
+} blok_model_info;
+int blok_hip_download_model(blok_hip_ctx* ctx, uint32_t model, void* nodes_out, size_t node_capacity, uint32_t* materials_out,
+                            size_t material_capacity, blok_model_info* out_info);
+
 #ifdef __cplusplus
 }
 #endif

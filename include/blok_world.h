@@ -176,6 +176,24 @@ int blok_quads_extract(const float* density, const uint32_t* material_ids, const
                        uint64_t* out_n_quads, uint64_t* out_n_faces);
 int blok_quads_write_obj(const char* path, const blok_quad* quads, uint64_t n, const blok_material_library* lib, char* err, size_t err_len);
 
+/* -------------------------------------------------------------- models into a volume and back on the host (stamp.cpp)
+ * The contracts of blok_hip_volume_stamp_models and blok_hip_volume_capture_model (blok_hip.h) over host arrays density[x + y*nx + z*nx*ny]
+ * / material_ids of a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the arithmetic the kernel uses.
+ * stamp_voxels: the model is the list of n voxels model_xyz[3*i..] (local lattice) with model_materials[i]; duplicates follow
+ * blok_hip_model_create's rule, the last one wins.  One placement (its `model` field is not looked at), mode BLOK_STAMP_*, `value` the
+ * density written by SET and KEEP.  out_n_voxels (may be NULL): voxels written.  BLOK_ERR_INVALID_ARG, nothing written: a NULL or
+ * malformed placement, an unknown mode, for SET and KEEP a value that is not finite or <= 0, a NULL array the call would use;
+ * BLOK_ERR_UNSUPPORTED: a box above 2^32 cells.
+ * capture_voxels: the filled voxels (density > 0) of the region (world voxels, half open; both NULL = the whole box) as the list
+ * {(w - region_lo, ids[w])}, x fastest, then y, then z: at most `capacity` records into xyz_out / materials_out (a prefix when there are
+ * more; xyz_out NULL = count only), the total in *out_n.  Errors as blok_quads_extract. */
+int blok_stamp_voxels(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                      const int32_t* model_xyz, const uint32_t* model_materials, size_t n,
+                      const blok_instance* placement, int mode, float value, uint64_t* out_n_voxels);
+int blok_capture_voxels(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                        const int32_t region_lo[3], const int32_t region_hi[3], int32_t* xyz_out, uint32_t* materials_out,
+                        uint64_t capacity, uint64_t* out_n);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);
