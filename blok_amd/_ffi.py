@@ -48,8 +48,13 @@ QUAD = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<
 QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
 STAMP_SET, STAMP_KEEP, STAMP_ERASE = 0, 1, 2      # = BLOK_STAMP_*
 CAPTURE_CUT = 1                                   # = BLOK_CAPTURE_CUT
+# = blok_component: one connected component of a labelled region, 40 bytes
+COMPONENT = np.dtype([("label", "<u4"), ("touches", "<u4"), ("n_voxels", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)])
+LABEL_EMPTY = 0xFFFFFFFF                          # = BLOK_LABEL_EMPTY
+COMPONENT_CUT = 1                                 # = BLOK_COMPONENT_CUT
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
+assert COMPONENT.itemsize == 40
 
 
 class GBuffer(C.Structure):
@@ -171,6 +176,8 @@ HOST_SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_capture_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "blok_components_label": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -296,6 +303,12 @@ HIP_SYMBOLS = {
     "blok_hip_volume_stamp_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_hip_volume_capture_model": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint32),
                                                 C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_label_components": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_components_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_labels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_capture_component": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_uint64)]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

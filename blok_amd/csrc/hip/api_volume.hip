@@ -24,6 +24,10 @@ void drop_quads(blok_hip_ctx* ctx) {
     if (ctx->d_quads) (void)hipFree(ctx->d_quads);
     ctx->d_quads = nullptr; ctx->n_quads = 0; ctx->has_quads = false;
 }
+void drop_components(blok_hip_ctx* ctx) {
+    blok::gpu_components_free(&ctx->components);
+    ctx->has_components = false;
+}
 int need_volume(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (!ctx->has_volume) return set_error(ctx, BLOK_ERR_NO_WORLD, "no resident volume (blok_hip_volume_create)");
@@ -38,6 +42,7 @@ int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t 
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->has_volume) { if (ctx->tree_owned_by_volume) { BLOK_HIP_TRY(ctx, hipDeviceSynchronize()); free_world(ctx); } blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false; }
     drop_quads(ctx);
+    drop_components(ctx);
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
     std::string why;
     const blok::GpuBuildStatus st = blok::gpu_volume_create(o, nx, ny, nz, chunk_size, voxel_size, &ctx->volume, &why, ctx->volume_keyed_layout);
@@ -67,6 +72,7 @@ int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
         blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false;
     }
     drop_quads(ctx);
+    drop_components(ctx);
     return BLOK_OK;
 }
 
@@ -243,6 +249,94 @@ int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3],
         for (int a = 0; a < 3; ++a) { clo[a] = lo[a] + static_cast<uint32_t>(box_lo[a]); chi[a] = lo[a] + static_cast<uint32_t>(box_hi[a]); }
         return volume_status(ctx, blok::gpu_volume_clear_filled(&v, clo, chi, &why), why);
     }
+    return BLOK_OK;
+}
+
+int blok_hip_volume_label_components(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                                     uint64_t* out_n_components, uint64_t* out_n_voxels) {
+    if (out_n_components) *out_n_components = 0;
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "label_components: unknown flag bits");
+    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "label_components: one region pointer is null");
+    const blok::GpuVolume& v = ctx->volume;
+    const int64_t dims[3] = {v.nx, v.ny, v.nz};
+    uint32_t lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
+        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "label_components: region_lo above region_hi");
+        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "label_components: region leaves the resident volume");
+        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
+    }
+    std::string why;
+    blok::GpuComponents snapshot;
+    const blok::GpuBuildStatus st = blok::gpu_volume_label_components(&ctx->volume, lo, hi, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    drop_components(ctx);
+    ctx->components = snapshot; ctx->has_components = true;
+    if (out_n_components) *out_n_components = snapshot.n_components;
+    if (out_n_voxels) *out_n_voxels = snapshot.n_voxels;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_components_download(blok_hip_ctx* ctx, blok_component* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_components) return set_error(ctx, BLOK_ERR_INVALID_ARG, "components_download: no snapshot (blok_hip_volume_label_components)");
+    const uint64_t n = ctx->components.n_components;
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "components_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "components_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->components.d_records + first, count * sizeof(blok_component), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_labels_download(blok_hip_ctx* ctx, uint32_t* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_components) return set_error(ctx, BLOK_ERR_INVALID_ARG, "labels_download: no snapshot (blok_hip_volume_label_components)");
+    const uint64_t n = ctx->components.n_cells;
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "labels_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "labels_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->components.d_labels + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_t flags, uint32_t* out_model, int32_t out_origin[3],
+                                      uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags & ~BLOK_COMPONENT_CUT) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: unknown flag bits");
+    if (!out_model) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: null output id");
+    if (!ctx->has_components) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: no snapshot (blok_hip_volume_label_components)");
+    if (ctx->models.desc.size() >= std::numeric_limits<uint32_t>::max() - 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model ids exhausted");
+    std::string why;
+    blok_component rec{};
+    bool found = false;
+    blok::GpuBuildStatus st = blok::gpu_components_find(&ctx->components, label, &rec, &found, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    if (!found) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: no component of the snapshot has this label");
+    blok::GpuVolume& v = ctx->volume;
+    uint32_t lo[3], hi[3];                             // the record's box, box-local: inside the labelled region, which lies inside the box
+    for (int a = 0; a < 3; ++a) { lo[a] = static_cast<uint32_t>(rec.lo[a] - v.origin[a]); hi[a] = static_cast<uint32_t>(rec.hi[a] - v.origin[a]); }
+    blok::GpuTree tree;
+    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+    uint64_t n_voxels = 0;
+    st = blok::gpu_volume_capture_labelled(&v, &ctx->components, label, lo, hi, &tree, box_lo, box_hi, &n_voxels, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    if (!n_voxels) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "capture_component: none of the component's voxels is still filled");
+    blok::ModelDesc m{};
+    m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
+    m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
+    for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
+    rc = add_model(ctx, m, out_model);
+    if (rc != BLOK_OK) return rc;                      // (nothing is cut when there is no model)
+    if (out_n_voxels) *out_n_voxels = n_voxels;
+    if (out_origin) for (int a = 0; a < 3; ++a) out_origin[a] = rec.lo[a];
+    if (flags & BLOK_COMPONENT_CUT) return volume_status(ctx, blok::gpu_volume_clear_labelled(&v, &ctx->components, label, lo, hi, &why), why);
     return BLOK_OK;
 }
 

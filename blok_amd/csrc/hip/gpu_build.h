@@ -123,6 +123,32 @@ GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], cons
                                   int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why);
 // Clears (density 0, id 0) the filled voxels of the box-local box [lo, hi) and refreshes it: BLOK_CAPTURE_CUT.
 GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why);
+// ---- connected components (include/blok_hip.h: blok_hip_volume_label_components; components_kernels.hip) ----
+// The snapshot of one labelling, device memory owned by the holder: the label array of the region's cells, the records sorted by label,
+// and — to find a label's record without a search — per row of 64 cells the bits of the cells that are roots and, packed in one word,
+// the exclusive sums over the rows of (filled cells) << 32 | roots: record of root r = low word of d_row_base[r / 64] + popcount of
+// d_root_bits[r / 64] below bit r % 64.
+struct GpuComponents {
+    uint32_t* d_labels = nullptr;
+    blok_component* d_records = nullptr;
+    uint64_t* d_root_bits = nullptr;
+    uint64_t* d_row_base = nullptr;
+    uint64_t n_cells = 0, n_components = 0, n_voxels = 0;
+    uint32_t lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0};      // the region, box-local
+};
+void gpu_components_free(GpuComponents* c);
+// Labels the box-local region [lo, hi) from the brick masks (which every edit leaves equal to density > 0).  Reads the store, changes
+// nothing; *out is a new snapshot, the caller's to free (empty, all pointers null, when the region has no cell).  Blocking.
+GpuBuildStatus gpu_volume_label_components(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuComponents* out, std::string* why);
+// The record of `label` in the snapshot; *found = false when no record has that label.
+GpuBuildStatus gpu_components_find(const GpuComponents* c, uint32_t label, blok_component* out, bool* found, std::string* why);
+// = blok_hip_volume_capture_component: gpu_volume_capture over the record's box [lo, hi) (box-local), restricted to the voxels whose
+// cell in the snapshot holds `label`; model coordinates are relative to lo.
+GpuBuildStatus gpu_volume_capture_labelled(const GpuVolume* v, const GpuComponents* c, uint32_t label, const uint32_t lo[3], const uint32_t hi[3],
+                                           GpuTree* out, int32_t box_lo[3], int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why);
+// gpu_volume_clear_filled under the same restriction: BLOK_COMPONENT_CUT.
+GpuBuildStatus gpu_volume_clear_labelled(GpuVolume* v, const GpuComponents* c, uint32_t label, const uint32_t lo[3], const uint32_t hi[3],
+                                         std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

@@ -984,9 +984,22 @@ struct RegionCtx {
     uint32_t lo[3], ext[3];          // the region: box-local corner and extent
 };
 
+// The further condition of blok_hip_volume_capture_component: the voxel's cell in a labelling's snapshot (gpu_build.h: GpuComponents) holds
+// `label`.  kLabelled = false is blok_hip_volume_capture_model: nothing of this is read.
+struct LabelPred {
+    const uint32_t* labels; uint32_t label;
+    uint32_t o[3], rx, ry;           // the labelled region: box-local corner, row and slice
+};
+template <bool kLabelled>
+__device__ __forceinline__ bool member(const LabelPred& p, uint32_t x, uint32_t y, uint32_t z) {      // (x, y, z) box-local, inside the labelled region
+    if (!kLabelled) return true;
+    return p.labels[(x - p.o[0]) + (static_cast<uint64_t>(y - p.o[1]) + static_cast<uint64_t>(z - p.o[2]) * p.ry) * p.rx] == p.label;
+}
+
 // Tight bounds and count of the region's filled voxels.  A wave takes rows (64 consecutive x of one (y, z)) in a grid-stride loop and keeps
 // its bounds in registers — a row's x bounds are the ends of its ballot — so a wave issues at most seven atomics, at the end, to its slot.
-__global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, uint64_t n_rows, uint32_t segs, uint32_t* bounds) {
+template <bool kLabelled>
+__global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, const LabelPred p, uint64_t n_rows, uint32_t segs, uint32_t* bounds) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * 4u + (threadIdx.x >> 6), n_waves = static_cast<uint64_t>(gridDim.x) * 4u;
     uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
@@ -994,7 +1007,8 @@ __global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, u
     for (uint64_t row = wave; row < n_rows; row += n_waves) {
         const uint32_t seg = static_cast<uint32_t>(row % segs), y = static_cast<uint32_t>((row / segs) % r.ext[1]), z = static_cast<uint32_t>(row / (static_cast<uint64_t>(segs) * r.ext[1]));
         const uint32_t x = seg * 64u + lane;
-        const bool filled = x < r.ext[0] && r.density[(static_cast<size_t>(r.lo[2] + z) * r.ny + (r.lo[1] + y)) * r.nx + r.lo[0] + x] > 0.0f;
+        const bool filled = x < r.ext[0] && r.density[(static_cast<size_t>(r.lo[2] + z) * r.ny + (r.lo[1] + y)) * r.nx + r.lo[0] + x] > 0.0f &&
+                            member<kLabelled>(p, r.lo[0] + x, r.lo[1] + y, r.lo[2] + z);
         const uint64_t votes = __ballot(filled);
         if (!votes) continue;
         mn[0] = min(mn[0], seg * 64u + static_cast<uint32_t>(__ffsll(static_cast<unsigned long long>(votes)) - 1));
@@ -1010,12 +1024,14 @@ __global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, u
 
 // One wave per brick of the MODEL's 4-grid (in general not the volume's brick grid), lane b = voxel b: the brick's mask from the voxels that
 // are filled and inside the tight box [t0, t1) of the region's filled voxels (grid voxels, i.e. from the tree's corner).
-__global__ __launch_bounds__(64) void region_brick_kernel(const DenseCtx d, uint32_t t0x, uint32_t t0y, uint32_t t0z, uint32_t t1x, uint32_t t1y, uint32_t t1z,
+template <bool kLabelled>
+__global__ __launch_bounds__(64) void region_brick_kernel(const DenseCtx d, const LabelPred p, uint32_t t0x, uint32_t t0y, uint32_t t0z, uint32_t t1x, uint32_t t1y, uint32_t t1z,
                                                           uint64_t* masks, uint32_t* non_empty) {
     const uint32_t b = threadIdx.x;
     const uint32_t vx = blockIdx.x * 4u + (b & 3u), vy = blockIdx.y * 4u + ((b >> 2) & 3u), vz = blockIdx.z * 4u + (b >> 4);
     const bool inside = vx >= t0x && vx < t1x && vy >= t0y && vy < t1y && vz >= t0z && vz < t1z;
-    const bool filled = inside && d.density[(static_cast<size_t>(d.oz + vz) * d.ny + (d.oy + vy)) * d.nx + d.ox + vx] > 0.0f;
+    const bool filled = inside && d.density[(static_cast<size_t>(d.oz + vz) * d.ny + (d.oy + vy)) * d.nx + d.ox + vx] > 0.0f &&
+                        member<kLabelled>(p, d.ox + vx, d.oy + vy, d.oz + vz);
     const uint64_t mask = __ballot(filled);
     if (b == 0u) {
         const size_t g = blockIdx.x + (static_cast<size_t>(blockIdx.z) * d.by + blockIdx.y) * d.bx;
@@ -1025,19 +1041,26 @@ __global__ __launch_bounds__(64) void region_brick_kernel(const DenseCtx d, uint
 }
 
 // One lane per voxel of the box: a filled voxel becomes (0, 0).
-__global__ __launch_bounds__(256) void clear_filled_kernel(float* density, uint32_t* ids, uint32_t nx, uint32_t ny, uint32_t x0, uint32_t y0, uint32_t z0,
+template <bool kLabelled>
+__global__ __launch_bounds__(256) void clear_filled_kernel(float* density, uint32_t* ids, const LabelPred p, uint32_t nx, uint32_t ny, uint32_t x0, uint32_t y0, uint32_t z0,
                                                            uint32_t ex, uint32_t ey, uint64_t total) {
     const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
     if (tid >= total) return;
     const uint32_t x = x0 + static_cast<uint32_t>(tid % ex), y = y0 + static_cast<uint32_t>((tid / ex) % ey), z = z0 + static_cast<uint32_t>(tid / (static_cast<uint64_t>(ex) * ey));
     const size_t i = (static_cast<size_t>(z) * ny + y) * nx + x;
-    if (density[i] > 0.0f) { density[i] = 0.0f; ids[i] = 0u; }
+    if (density[i] > 0.0f && member<kLabelled>(p, x, y, z)) { density[i] = 0.0f; ids[i] = 0u; }
 }
 
-}  // namespace
+LabelPred label_pred(const GpuComponents* c, uint32_t label) {
+    LabelPred p{};
+    p.labels = c->d_labels; p.label = label; p.rx = c->ext[0]; p.ry = c->ext[1];
+    for (int a = 0; a < 3; ++a) p.o[a] = c->lo[a];
+    return p;
+}
 
-GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
-                                  uint64_t* out_n_voxels, std::string* why) {
+template <bool kLabelled>
+GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3],
+                              int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why) {
     *out = GpuTree{};
     *out_n_voxels = 0;
     if (v->cells() > 0xFFFFFFFFull) { *why = "capture_model: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
@@ -1054,7 +1077,7 @@ GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], cons
     GB_TRY(hipMemcpy(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     const uint32_t segs = (r.ext[0] + 63u) / 64u;
     const uint64_t n_rows = static_cast<uint64_t>(segs) * r.ext[1] * r.ext[2];
-    hipLaunchKernelGGL(region_bounds_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r, n_rows, segs, d_bounds);
+    hipLaunchKernelGGL(region_bounds_kernel<kLabelled>, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r, pred, n_rows, segs, d_bounds);
     GB_TRY(hipGetLastError());
     GB_TRY(hipMemcpy(bounds.data(), d_bounds, bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     uint32_t t0[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, t1[3] = {0u, 0u, 0u};
@@ -1088,7 +1111,7 @@ GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], cons
     uint64_t* d_masks; uint32_t *d_flag, *d_slot;
     GB_TRY(mem.alloc(&d_masks, total)); GB_TRY(mem.alloc(&d_flag, total + 1)); GB_TRY(mem.alloc(&d_slot, total + 1));
     GB_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
-    hipLaunchKernelGGL(region_brick_kernel, dim3(d.bx, d.by, d.bz), dim3(64), 0, nullptr, d, t0[0] - origin[0], t0[1] - origin[1], t0[2] - origin[2],
+    hipLaunchKernelGGL(region_brick_kernel<kLabelled>, dim3(d.bx, d.by, d.bz), dim3(64), 0, nullptr, d, pred, t0[0] - origin[0], t0[1] - origin[1], t0[2] - origin[2],
                        t1[0] - origin[0] + 1u, t1[1] - origin[1] + 1u, t1[2] - origin[2] + 1u, d_masks, d_flag);
     GB_TRY(hipGetLastError());
     const GpuBuildStatus st = finish_from_masks(mem, total, d_masks, d_flag, d_slot, levels, origin,
@@ -1104,15 +1127,37 @@ GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], cons
     return st;
 }
 
-GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
+template <bool kLabelled>
+GpuBuildStatus clear_region(GpuVolume* v, const LabelPred& pred, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
     if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
     const uint32_t ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
     const uint64_t total = static_cast<uint64_t>(ex) * ey * ez;
-    hipLaunchKernelGGL(clear_filled_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, v->d_density, v->d_ids, v->nx, v->ny, lo[0], lo[1], lo[2], ex, ey, total);
+    hipLaunchKernelGGL(clear_filled_kernel<kLabelled>, dim3(blocks_for(total)), dim3(256), 0, nullptr, v->d_density, v->d_ids, pred, v->nx, v->ny, lo[0], lo[1], lo[2], ex, ey, total);
     GB_TRY(hipGetLastError());
     const GpuBuildStatus st = volume_refresh(v, lo, hi, why);      // (clearing never fills: edit_may_add stays as it was)
     GB_TRY(hipDeviceSynchronize());                                // blocking, as gpu_volume_set_voxels is
     return st;
+}
+
+}  // namespace
+
+GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
+                                  uint64_t* out_n_voxels, std::string* why) {
+    return capture_region<false>(v, LabelPred{}, lo, hi, out, box_lo, box_hi, out_n_voxels, why);
+}
+
+GpuBuildStatus gpu_volume_capture_labelled(const GpuVolume* v, const GpuComponents* c, uint32_t label, const uint32_t lo[3], const uint32_t hi[3],
+                                           GpuTree* out, int32_t box_lo[3], int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why) {
+    return capture_region<true>(v, label_pred(c, label), lo, hi, out, box_lo, box_hi, out_n_voxels, why);
+}
+
+GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
+    return clear_region<false>(v, LabelPred{}, lo, hi, why);
+}
+
+GpuBuildStatus gpu_volume_clear_labelled(GpuVolume* v, const GpuComponents* c, uint32_t label, const uint32_t lo[3], const uint32_t hi[3],
+                                         std::string* why) {
+    return clear_region<true>(v, label_pred(c, label), lo, hi, why);
 }
 
 GpuBuildStatus gpu_volume_build(GpuVolume* v, GpuTree* out, std::string* why) {

@@ -166,6 +166,48 @@ class HipTracer:
         self.last_capture_voxels = int(n.value)
         return int(model.value)
 
+    def volume_label_components(self, lo=None, hi=None):
+        """Labels the connected components (6-neighbour) of a region of the resident volume (blok_hip.h: blok_hip_volume_label_components):
+        the region in world voxels, half open (both None = the whole box).  The snapshot stays on the device until the next labelling;
+        volume_labels_download / volume_components_download fetch it.  Returns (n_components, n_voxels)."""
+        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
+        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        n_components, n_voxels = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_label_components(self._ctx, rlo, rhi, 0, C.byref(n_components), C.byref(n_voxels)))
+        return int(n_components.value), int(n_voxels.value)
+
+    def volume_components_download(self, first: int, count: int, page: int = 1 << 22) -> np.ndarray:
+        """Records [first, first + count) of the last labelling's snapshot: a structured array of _ffi.COMPONENT, sorted by label."""
+        out = np.zeros(int(count), dtype=_ffi.COMPONENT)
+        if count == 0:
+            self._check(self._lib.blok_hip_volume_components_download(self._ctx, None, int(first), 0))
+        for at in range(0, int(count), int(page)):
+            n = min(int(page), int(count) - at)
+            self._check(self._lib.blok_hip_volume_components_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
+        return out
+
+    def volume_labels_download(self, first: int, count: int, page: int = 1 << 24) -> np.ndarray:
+        """Cells [first, first + count) of the last labelling's label array (region index order; _ffi.LABEL_EMPTY = empty cell)."""
+        out = np.zeros(int(count), dtype=np.uint32)
+        if count == 0:
+            self._check(self._lib.blok_hip_volume_labels_download(self._ctx, None, int(first), 0))
+        for at in range(0, int(count), int(page)):
+            n = min(int(page), int(count) - at)
+            self._check(self._lib.blok_hip_volume_labels_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
+        return out
+
+    def volume_capture_component(self, label: int, cut: bool = False):
+        """The voxels of the snapshot's component `label` that are still filled, as a new model in the lattice whose voxel (0, 0, 0) is the
+        record's lo (blok_hip.h: blok_hip_volume_capture_component); cut = also clear them in the volume.  Returns (model id, origin):
+        an instance {model, offset = origin, identity} shows the piece where it was.  The voxel count is in last_capture_voxels."""
+        model, n = C.c_uint32(0), C.c_uint64(0)
+        origin = (C.c_int32 * 3)(0, 0, 0)
+        self.last_capture_voxels = 0
+        self._check(self._lib.blok_hip_volume_capture_component(self._ctx, int(label), _ffi.COMPONENT_CUT if cut else 0, C.byref(model), origin,
+                                                                C.byref(n)))
+        self.last_capture_voxels = int(n.value)
+        return int(model.value), (int(origin[0]), int(origin[1]), int(origin[2]))
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

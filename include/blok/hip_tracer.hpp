@@ -270,6 +270,31 @@ public:
         check(blok_hip_volume_capture_model(m_ctx, regionLo, regionHi, cut ? BLOK_CAPTURE_CUT : 0u, &model, outVoxels));
         return model;
     }
+    // The connected components (6-neighbour) of a region of the resident volume (blok_hip_volume_label_components; world voxels, half-open,
+    // both null = the whole box): the records sorted by label, fetched `page` at a time.  The snapshot stays on the device until the next
+    // call.  outVoxels: the filled voxels.
+    std::vector<blok_component> labelComponents(const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr, uint64_t* outVoxels = nullptr,
+                                                uint64_t page = uint64_t(1) << 22) {
+        uint64_t n = 0;
+        check(blok_hip_volume_label_components(m_ctx, regionLo, regionHi, 0u, &n, outVoxels));
+        std::vector<blok_component> records(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_components_download(m_ctx, records.data() + at, at, std::min(page, n - at)));
+        return records;
+    }
+    // Cells [first, first + count) of that snapshot's label array: one per region voxel, x fastest; BLOK_LABEL_EMPTY for an empty cell.
+    std::vector<uint32_t> componentLabels(uint64_t first, uint64_t count) {
+        std::vector<uint32_t> labels(count);
+        check(blok_hip_volume_labels_download(m_ctx, labels.data(), first, count));
+        return labels;
+    }
+    // The still-filled voxels of the last labelling's component `label` as a new model whose voxel (0, 0, 0) is the record's lo, returned
+    // in outOrigin (blok_hip_volume_capture_component): an instance {model, offset = outOrigin, identity} shows the piece where it was.
+    // cut: those voxels are cleared in the volume.
+    uint32_t captureComponent(uint32_t label, bool cut = false, int32_t outOrigin[3] = nullptr, uint64_t* outVoxels = nullptr) {
+        uint32_t model = 0;
+        check(blok_hip_volume_capture_component(m_ctx, label, cut ? BLOK_COMPONENT_CUT : 0u, &model, outOrigin, outVoxels));
+        return model;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

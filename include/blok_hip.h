@@ -568,7 +568,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
 /* Library/ABI version: (major<<16)|minor.  1.1: instanced voxel models (below).  1.2: path-traced frames with instances.
  * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume.
  * 1.5: procedural terrain into the resident volume.  1.6: the volume's surface as merged quads.
- * 1.7: models stamped into the resident volume, regions of it captured as models. */
+ * 1.7: models stamped into the resident volume, regions of it captured as models.
+ * 1.8: connected components of the resident volume, one of them captured as a model. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -732,6 +733,55 @@ int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placeme
 #define BLOK_CAPTURE_CUT 1u   /* afterwards clear the captured voxels in the volume (density 0, id 0) */
 int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
                                   uint32_t* out_model, uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- connected components of the resident volume (ABI 1.8)
+ * Which voxels hang together, answered on the device, and one such piece lifted out as a model.  Integer arithmetic only: one right
+ * answer, bit-identical on the host (blok_components_label, blok_world.h) and on the device.  All calls block.
+ *  - Filled: a voxel is filled iff its density > 0 (the rebuild's rule; 0, negative and NaN densities are empty).
+ *  - Adjacency: two filled voxels of the region are adjacent iff they differ by one in exactly one coordinate (face adjacency, 6
+ *    neighbours).  Voxels touching only by an edge or a corner are not adjacent.  Voxels outside the region connect nothing: two pieces
+ *    joined only through a voxel outside the region are two components.
+ *  - Component: a class of the transitive closure of adjacency over the region's filled voxels.
+ *  - Index and label: a region voxel has the linear index r = (x - lo.x) + (y - lo.y) rx + (z - lo.z) rx ry (x fastest, as in the
+ *    arrays; rx, ry the region's extents).  The label of a component is the smallest r among its voxels.  The label array holds, per
+ *    region cell in index order, the cell's component label; empty cells hold BLOK_LABEL_EMPTY.
+ *  - Records: one blok_component per component, sorted by label ascending (labels are distinct, so the order is total).  `touches` is how
+ *    a caller decides what is anchored: for a region standing on its floor "floating" is !(touches & 1 << 3); for a region inside a larger
+ *    world it is "touches none of the five faces that continue into the world".  Bit f is set iff the bounds reach the region's side f.
+ *  - blok_hip_volume_label_components: the region is in world voxels, half open; both pointers NULL = the whole box (the convention of
+ *    blok_hip_volume_extract_quads).  flags must be 0.  Either count pointer may be NULL.  The snapshot — label array, record table and
+ *    region — stays in device memory, owned by the context; later edits do not touch it.  The next labelling replaces it;
+ *    blok_hip_volume_destroy, a new blok_hip_volume_create and blok_hip_destroy free it.
+ *  - blok_hip_volume_components_download copies records [first, first + count), blok_hip_volume_labels_download cells
+ *    [first, first + count) of the region, so a large snapshot can be fetched in pieces.
+ *  - blok_hip_volume_capture_component makes a model of the snapshot's voxels with this label that are still filled in the volume NOW,
+ *    with the volume's current material ids: exactly the model blok_hip_model_create builds from the list
+ *    {(w - rec.lo, ids[w]) : label[w] == label, density[w] > 0}, rec.lo being the record's lo, returned in out_origin (may be NULL): the
+ *    same node and material arrays byte for byte, the same levels, origin and box.  An instance {model, offset = out_origin, identity}
+ *    shows the piece exactly where it was.  Membership is judged against the current volume, so there is no staleness rule: after a CUT
+ *    of one component the snapshot still serves the others.  BLOK_COMPONENT_CUT then clears those voxels (density 0, id 0) and refreshes
+ *    masks, occupancy words and dirty flags over the record's box, as BLOK_CAPTURE_CUT does.  If the model cannot be built, nothing is cut.
+ *  - Errors, each leaving the previous snapshot and the volume as they were.  BLOK_ERR_INVALID_ARG: unknown flag bits, exactly one region
+ *    pointer NULL, lo > hi on an axis; for the downloads no snapshot, a range past the end, or NULL with count > 0; for the capture no
+ *    snapshot, out_model NULL, or a label that is not a record's label.  BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume
+ *    above 2^32 cells, a region of 2^32 cells (the sentinel would be an index); for the capture none of the component's voxels still
+ *    filled (then no model is made, no id consumed, *out_n_voxels = 0).  BLOK_ERR_NO_WORLD: no volume.  BLOK_ERR_OOM: a failed
+ *    allocation.  An empty region, or one without filled voxels, is BLOK_OK with zero counts and an empty snapshot. */
+#define BLOK_LABEL_EMPTY 0xFFFFFFFFu
+typedef struct blok_component {
+    uint32_t label;        /* = index of the component's first voxel in x-fastest order */
+    uint32_t touches;      /* bit f (blok_hit::face numbering 0:+X 1:-X 2:+Y 3:-Y 4:+Z 5:-Z): the component has a voxel in the region's
+                              outermost layer on that side */
+    uint64_t n_voxels;
+    int32_t  lo[3], hi[3]; /* tight bounds of its voxels, world voxels, half open */
+} blok_component;          /* 40 bytes */
+int blok_hip_volume_label_components(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                                     uint64_t* out_n_components, uint64_t* out_n_voxels);
+int blok_hip_volume_components_download(blok_hip_ctx* ctx, blok_component* out_host, uint64_t first, uint64_t count);
+int blok_hip_volume_labels_download(blok_hip_ctx* ctx, uint32_t* out_host, uint64_t first, uint64_t count);
+#define BLOK_COMPONENT_CUT 1u   /* afterwards clear the captured voxels in the volume (density 0, id 0) */
+int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_t flags, uint32_t* out_model, int32_t out_origin[3],
+                                      uint64_t* out_n_voxels);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -194,6 +194,19 @@ int blok_capture_voxels(const float* density, const uint32_t* material_ids, cons
                         const int32_t region_lo[3], const int32_t region_hi[3], int32_t* xyz_out, uint32_t* materials_out,
                         uint64_t capacity, uint64_t* out_n);
 
+/* -------------------------------------------------------------- a volume's connected components on the host (components.cpp)
+ * label: the contract of blok_hip_volume_label_components (blok_hip.h; blok_component is declared there) over the host array
+ * density[x + y*nx + z*nx*ny] of a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the union-find the kernels
+ * use, run serially; the region in world voxels, half open, both NULL = the whole box; flags must be 0.  Writes at most `label_capacity`
+ * cells of the label array into labels_out and at most `component_capacity` records into components_out (prefixes when there are more;
+ * either pointer NULL = that output is not written) and always reports the totals (either pointer may be NULL).  Errors as the device
+ * entry: BLOK_ERR_INVALID_ARG for unknown flag bits, exactly one region pointer NULL, lo > hi on an axis, a NULL density the call would
+ * read; BLOK_ERR_UNSUPPORTED for a region that leaves the box or a box above 2^32 cells; an empty region is BLOK_OK with zero counts. */
+int blok_components_label(const float* density, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                          const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                          uint32_t* labels_out, uint64_t label_capacity, blok_component* components_out, uint64_t component_capacity,
+                          uint64_t* out_n_components, uint64_t* out_n_voxels);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components]
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
 //   --terrain: procedural terrain generated on the device into a resident volume of --terrain-size^3 voxels (blok_hip_volume_generate_terrain),
@@ -9,6 +9,8 @@
 //          top of it, a quarter of the box tall, standing on the ground at the box centre
 //   --export-obj: with --terrain or --obj, the resident volume's surface as merged quads (blok_hip_volume_extract_quads over the whole box),
 //          written as an OBJ with a sibling .mtl of the library's albedos (blok_quads_write_obj)
+//   --components: with --terrain or --obj, the connected components of the whole box (blok_hip_volume_label_components): how many there
+//          are, the largest, and how many do not touch the box's floor (floating pieces)
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -41,6 +43,7 @@ struct Options {
     bool terrain = false;                 // procedural terrain generated on the device
     uint32_t terrain_seed = 0, terrain_size = 256;
     std::string export_obj;               // write the resident volume's surface here
+    bool components = false;              // label the resident volume's connected components and print their counts
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
     bool rccl = true;
@@ -58,9 +61,10 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
-                if (m_opt.terrain) { initTerrain(); exportObj(); break; }
-                if (!m_opt.obj.empty()) { initObj(); exportObj(); break; }
+                if (m_opt.terrain) { initTerrain(); exportObj(); components(); break; }
+                if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); break; }
                 if (!m_opt.export_obj.empty()) throw std::runtime_error("--export-obj needs a resident volume: --terrain or --obj");
+                if (m_opt.components) throw std::runtime_error("--components needs a resident volume: --terrain or --obj");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -205,6 +209,18 @@ private:
         std::cout << "surface: " << faces << " exposed faces -> " << quads.size() << " quads (" << quads.size() * sizeof(blok_quad) / 1e6
                   << " MB) -> " << m_opt.export_obj << "\n";
     }
+    // The connected components of the whole box: their number, the largest, and those that do not reach the box's floor.
+    void components() {
+        if (!m_opt.components) return;
+        uint64_t voxels = 0, largest = 0, floating = 0, floating_voxels = 0;
+        const std::vector<blok_component> records = m_tracer->labelComponents(nullptr, nullptr, &voxels);
+        for (const blok_component& c : records) {
+            largest = std::max<uint64_t>(largest, c.n_voxels);
+            if (!(c.touches & (1u << 3))) { ++floating; floating_voxels += c.n_voxels; }
+        }
+        std::cout << "components: " << records.size() << " over " << voxels << " voxels, largest " << largest << " voxels, " << floating
+                  << " not touching the floor (" << floating_voxels << " voxels)\n";
+    }
     void update() {
         using clock = std::chrono::steady_clock;
         for (uint32_t f = 0; f < m_opt.frames; ++f) {
@@ -266,6 +282,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--terrain")) { opt.terrain = true; opt.terrain_seed = static_cast<uint32_t>(std::strtoul(next(), nullptr, 0)); }
         else if (!std::strcmp(argv[i], "--terrain-size")) opt.terrain_size = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--export-obj")) opt.export_obj = next();
+        else if (!std::strcmp(argv[i], "--components")) opt.components = true;
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
