@@ -52,9 +52,12 @@ CAPTURE_CUT = 1                                   # = BLOK_CAPTURE_CUT
 COMPONENT = np.dtype([("label", "<u4"), ("touches", "<u4"), ("n_voxels", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)])
 LABEL_EMPTY = 0xFFFFFFFF                          # = BLOK_LABEL_EMPTY
 COMPONENT_CUT = 1                                 # = BLOK_COMPONENT_CUT
+# = blok_sweep_result: one placement swept against the volume, 16 bytes
+SWEEP_RESULT = np.dtype([("n_overlap", "<u8"), ("travel", "<u4"), ("blocked", "<u4")])
+SWEEP_BOX_IS_SOLID = 1                            # = BLOK_SWEEP_BOX_IS_SOLID
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
-assert COMPONENT.itemsize == 40
+assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16
 
 
 class GBuffer(C.Structure):
@@ -178,6 +181,8 @@ HOST_SYMBOLS = {
                                       C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "blok_components_label": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "blok_sweep_voxels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, C.c_void_p]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -309,6 +314,7 @@ HIP_SYMBOLS = {
     "blok_hip_volume_labels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_capture_component": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
                                                     C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_sweep_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

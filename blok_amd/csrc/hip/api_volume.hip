@@ -2,6 +2,7 @@
 #include "api_internal.h"
 #include "../common/terrain_core.h"
 #include "../common/stamp_core.h"
+#include "../common/sweep_core.h"
 #include <chrono>
 #include <cstdlib>
 #include <limits>
@@ -33,6 +34,17 @@ int need_volume(blok_hip_ctx* ctx) {
     if (!ctx->has_volume) return set_error(ctx, BLOK_ERR_NO_WORLD, "no resident volume (blok_hip_volume_create)");
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return BLOK_OK;
+}
+// The models of a table that has passed check_instance_table, as the stamp and the sweep read them.
+std::vector<blok::StampModel> placed_models(const blok_hip_ctx* ctx, const blok_instance* placements, uint32_t n) {
+    std::vector<blok::StampModel> models(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const blok::ModelDesc& d = ctx->models.desc[placements[i].model];
+        blok::StampModel& m = models[i];
+        m.nodes = d.nodes; m.materials = d.materials; m.levels = d.levels;
+        for (int a = 0; a < 3; ++a) { m.origin[a] = d.origin[a]; m.lo[a] = d.lo[a]; m.hi[a] = d.hi[a]; }
+    }
+    return models;
 }
 }  // namespace
 
@@ -199,13 +211,7 @@ int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placeme
     if (!blok::stamp::mode_known(mode)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_models: unknown mode");
     if (mode != BLOK_STAMP_ERASE && (!std::isfinite(density) || !(density > 0.0f)))
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_models: density must be finite and > 0");
-    std::vector<blok::StampModel> models(n_placements);
-    for (uint32_t i = 0; i < n_placements; ++i) {
-        const blok::ModelDesc& d = ctx->models.desc[placements_host[i].model];
-        blok::StampModel& m = models[i];
-        m.nodes = d.nodes; m.materials = d.materials; m.levels = d.levels;
-        for (int a = 0; a < 3; ++a) { m.origin[a] = d.origin[a]; m.lo[a] = d.lo[a]; m.hi[a] = d.hi[a]; }
-    }
+    const std::vector<blok::StampModel> models = placed_models(ctx, placements_host, n_placements);
     std::string why;
     // (edits are enqueued on the null stream, and so is this: placement after placement, in stream order)
     return volume_status(ctx, blok::gpu_volume_stamp(&ctx->volume, models.data(), placements_host, n_placements, mode, density, out_n_voxels, &why), why);
@@ -338,6 +344,22 @@ int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_
     if (out_origin) for (int a = 0; a < 3; ++a) out_origin[a] = rec.lo[a];
     if (flags & BLOK_COMPONENT_CUT) return volume_status(ctx, blok::gpu_volume_clear_labelled(&v, &ctx->components, label, lo, hi, &why), why);
     return BLOK_OK;
+}
+
+int blok_hip_volume_sweep_models(blok_hip_ctx* ctx, const blok_instance* placements_host, uint32_t n_placements, uint32_t direction,
+                                 uint32_t max_distance, uint32_t flags, blok_sweep_result* out_results_host) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    rc = check_instance_table(ctx, placements_host, n_placements);      // the stamp's check, with its messages
+    if (rc != BLOK_OK) return rc;
+    if (!blok::sweep::direction_known(direction)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sweep_models: direction above 5");
+    if (!blok::sweep::flags_known(flags)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sweep_models: unknown flag bits");
+    if (n_placements && !out_results_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sweep_models: null result array with non-zero count");
+    const std::vector<blok::StampModel> models = placed_models(ctx, placements_host, n_placements);
+    std::string why;
+    // (on the null stream, behind every edit enqueued so far; reads only, so no snapshot and no edit state is touched)
+    return volume_status(ctx, blok::gpu_volume_sweep(&ctx->volume, models.data(), placements_host, n_placements, direction, max_distance, flags,
+                                                     out_results_host, &why), why);
 }
 
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {

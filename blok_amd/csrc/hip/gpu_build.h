@@ -149,6 +149,11 @@ GpuBuildStatus gpu_volume_capture_labelled(const GpuVolume* v, const GpuComponen
 // gpu_volume_clear_filled under the same restriction: BLOK_COMPONENT_CUT.
 GpuBuildStatus gpu_volume_clear_labelled(GpuVolume* v, const GpuComponents* c, uint32_t label, const uint32_t lo[3], const uint32_t hi[3],
                                          std::string* why);
+// = blok_hip_volume_sweep_models (include/blok_hip.h; sweep_kernels.hip).  The placements, direction and flags have passed the entry's
+// checks; models[i] is the model of placements[i].  Reads the brick masks and the models' trees, changes nothing.  One upload, one launch
+// for the whole table on the null stream, one download (the call's wait); out_results has n_placements records, host memory.
+GpuBuildStatus gpu_volume_sweep(const GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements,
+                                uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_results, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

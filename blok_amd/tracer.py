@@ -208,6 +208,17 @@ class HipTracer:
         self.last_capture_voxels = int(n.value)
         return int(model.value), (int(origin[0]), int(origin[1]), int(origin[2]))
 
+    def volume_sweep_models(self, placements, direction: int, max_distance: int, flags: int = 0) -> np.ndarray:
+        """Sweeps placed models against the resident volume (blok_hip.h: blok_hip_volume_sweep_models): for each INSTANCE record
+        (blok_amd.stamp.placement) how many of the model's voxels land on filled cells and how far the model can travel along
+        `direction` (0 +X, 1 -X, 2 +Y, 3 -Y, 4 +Z, 5 -Z) before one does, at most max_distance; flags _ffi.SWEEP_BOX_IS_SOLID.  Each
+        placement on its own, the volume unchanged.  Returns a structured array of _ffi.SWEEP_RESULT, one per placement."""
+        inst = np.ascontiguousarray(placements, dtype=INSTANCE).reshape(-1)
+        out = np.zeros(len(inst), dtype=_ffi.SWEEP_RESULT)
+        self._check(self._lib.blok_hip_volume_sweep_models(self._ctx, _ffi.ptr(inst) if len(inst) else None, len(inst), int(direction),
+                                                           int(max_distance), int(flags), _ffi.ptr(out) if len(out) else None))
+        return out
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

@@ -295,6 +295,16 @@ public:
         check(blok_hip_volume_capture_component(m_ctx, label, cut ? BLOK_COMPONENT_CUT : 0u, &model, outOrigin, outVoxels));
         return model;
     }
+    // Placed models swept against the resident volume (blok_hip_volume_sweep_models): per placement the voxels that overlap filled cells
+    // and the free travel along `direction` (blok_hit::face numbering, 3 = down), at most maxDistance.  Each placement on its own; the
+    // volume is not changed.  boxIsSolid: cells outside the volume's box stop the model.
+    std::vector<blok_sweep_result> sweepModels(const std::vector<blok_instance>& placements, uint32_t direction, uint32_t maxDistance,
+                                               bool boxIsSolid = false) {
+        std::vector<blok_sweep_result> results(placements.size());
+        check(blok_hip_volume_sweep_models(m_ctx, placements.data(), static_cast<uint32_t>(placements.size()), direction, maxDistance,
+                                           boxIsSolid ? BLOK_SWEEP_BOX_IS_SOLID : 0u, results.data()));
+        return results;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -569,7 +569,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.3: object motion vectors for moving instances.  1.4: mesh voxelization into the resident volume.
  * 1.5: procedural terrain into the resident volume.  1.6: the volume's surface as merged quads.
  * 1.7: models stamped into the resident volume, regions of it captured as models.
- * 1.8: connected components of the resident volume, one of them captured as a model. */
+ * 1.8: connected components of the resident volume, one of them captured as a model.
+ * 1.9: placed models swept against the resident volume (overlap, free travel along an axis). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -782,6 +783,38 @@ int blok_hip_volume_labels_download(blok_hip_ctx* ctx, uint32_t* out_host, uint6
 #define BLOK_COMPONENT_CUT 1u   /* afterwards clear the captured voxels in the volume (density 0, id 0) */
 int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_t flags, uint32_t* out_model, int32_t out_origin[3],
                                       uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- placed models swept against the resident volume (ABI 1.9)
+ * Where a model may move: does it, placed here, hit anything, and how far can it travel along an axis before it does?  Answered from the
+ * models' trees and the volume's brick masks where they lie in HBM.  Integer arithmetic only: one right answer, bit-identical on the host
+ * (blok_sweep_voxels, blok_world.h) and on the device.  The call blocks.
+ *  - Placement: a blok_instance.  A filled model voxel v' (local lattice) lands on the world voxel w(v') of "Record back to world space"
+ *    above — the stamp's mapping, so a piece stamped at a swept position lies exactly where the sweep saw it.  The sums are 64-bit.
+ *  - Direction: blok_hit::face numbering, 0 +X, 1 -X, 2 +Y, 3 -Y, 4 +Z, 5 -Z; e is its unit vector.
+ *  - Filled cell: inside the volume's box a cell is filled iff its density > 0 (0, negative and NaN densities are empty).  Outside the
+ *    box a cell is empty; with BLOK_SWEEP_BOX_IS_SOLID it is filled (the box's walls and floor stop the model).
+ *  - n_overlap: the number of filled model voxels v' whose cell w(v') is filled: what the placement itself intersects.
+ *  - free(v'): the largest k <= max_distance such that the cells w(v') + s e, s = 1 .. k, are all empty.  The start cell w(v') itself is
+ *    not looked at.
+ *  - travel: the minimum of free(v') over the model's filled voxels.  The model translated by any s in 1 .. travel overlaps nothing; if
+ *    `blocked` (travel < max_distance), the translate by travel + 1 overlaps something.  max_distance == 0 is the pure overlap test;
+ *    any uint32 is a legal max_distance: once a column has left the box it is all empty (or all filled, with the flag), so the work is
+ *    bounded by the box.
+ *  - Independence: each placement is swept against the volume as it is now, independently of the other placements (model against model is
+ *    not tested); out_results_host[i] belongs to placements_host[i].  The number of kernel launches does not depend on n_placements.
+ *  - Side effects: none on the volume — arrays, masks, occupancy words, dirty flags, the edited box stay as they are — and none on a
+ *    components or quads snapshot.
+ *  - Errors, nothing written to out_results_host.  BLOK_ERR_INVALID_ARG: a placement that fails what blok_hip_check_instances checks (same
+ *    messages), direction > 5, unknown flag bits, a null table or a null result array with a non-zero count.  BLOK_ERR_NO_WORLD: no
+ *    volume.  BLOK_ERR_UNSUPPORTED: a volume above 2^32 cells.  n_placements == 0 is BLOK_OK. */
+#define BLOK_SWEEP_BOX_IS_SOLID 1u   /* cells outside the volume's box count as filled (default: as empty) */
+typedef struct blok_sweep_result {
+    uint64_t n_overlap;   /* filled model voxels that land on a filled cell at the placement itself */
+    uint32_t travel;      /* 0 .. max_distance */
+    uint32_t blocked;     /* 1 iff travel < max_distance */
+} blok_sweep_result;      /* 16 bytes */
+int blok_hip_volume_sweep_models(blok_hip_ctx* ctx, const blok_instance* placements_host, uint32_t n_placements,
+                                 uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_results_host);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -207,6 +207,16 @@ int blok_components_label(const float* density, const int32_t origin[3], uint32_
                           uint32_t* labels_out, uint64_t label_capacity, blok_component* components_out, uint64_t component_capacity,
                           uint64_t* out_n_components, uint64_t* out_n_voxels);
 
+/* -------------------------------------------------------------- a placed model swept against a volume on the host (sweep.cpp)
+ * The contract of blok_hip_volume_sweep_models (blok_hip.h; blok_sweep_result and BLOK_SWEEP_BOX_IS_SOLID are declared there) over the
+ * host array density[x + y*nx + z*nx*ny] of a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the arithmetic the
+ * kernel uses, voxel by voxel.  The model is the list of n distinct voxels model_xyz[3*i..] (local lattice; a voxel listed twice is
+ * counted twice in n_overlap).  One placement (its `model` field is not looked at), direction 0..5 in blok_hit::face numbering.  An empty
+ * list gives {0, max_distance, 0}.  BLOK_ERR_INVALID_ARG, nothing written: a NULL or malformed placement, direction > 5, unknown flag
+ * bits, a NULL result, a NULL array the call would read; BLOK_ERR_UNSUPPORTED: a box above 2^32 cells. */
+int blok_sweep_voxels(const float* density, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const int32_t* model_xyz, size_t n,
+                      const blok_instance* placement, uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_result);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

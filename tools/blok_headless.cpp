@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle]
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
 //   --terrain: procedural terrain generated on the device into a resident volume of --terrain-size^3 voxels (blok_hip_volume_generate_terrain),
@@ -11,6 +11,10 @@
 //          written as an OBJ with a sibling .mtl of the library's albedos (blok_quads_write_obj)
 //   --components: with --terrain or --obj, the connected components of the whole box (blok_hip_volume_label_components): how many there
 //          are, the largest, and how many do not touch the box's floor (floating pieces)
+//   --settle: with --terrain or --obj, after --components' pass: every component that does not touch the box's floor is lifted out
+//          (blok_hip_volume_capture_component with CUT), swept down against what remains (blok_hip_volume_sweep_models, the box's walls
+//          and floor solid) and stamped where it comes to rest (blok_hip_volume_stamp_models); lowest pieces first, pass after pass until
+//          nothing floats (at most 8 passes).  The frames show the settled world
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -44,6 +48,7 @@ struct Options {
     uint32_t terrain_seed = 0, terrain_size = 256;
     std::string export_obj;               // write the resident volume's surface here
     bool components = false;              // label the resident volume's connected components and print their counts
+    bool settle = false;                  // let the components that do not touch the floor fall
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
     bool rccl = true;
@@ -61,10 +66,11 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
-                if (m_opt.terrain) { initTerrain(); exportObj(); components(); break; }
-                if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); break; }
+                if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); break; }
+                if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); settle(); break; }
                 if (!m_opt.export_obj.empty()) throw std::runtime_error("--export-obj needs a resident volume: --terrain or --obj");
                 if (m_opt.components) throw std::runtime_error("--components needs a resident volume: --terrain or --obj");
+                if (m_opt.settle) throw std::runtime_error("--settle needs a resident volume: --terrain or --obj");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -221,6 +227,38 @@ private:
         std::cout << "components: " << records.size() << " over " << voxels << " voxels, largest " << largest << " voxels, " << floating
                   << " not touching the floor (" << floating_voxels << " voxels)\n";
     }
+    // Floating pieces fall: label, lift each piece that does not reach the floor out of the volume (lowest first), sweep it down against
+    // what remains, stamp it where it comes to rest; again until nothing floats (a piece may land on one that falls later in the pass).
+    void settle() {
+        if (!m_opt.settle) return;
+        const uint32_t height = m_opt.terrain ? m_opt.terrain_size : m_opt.obj_size;
+        uint64_t pieces = 0, voxels = 0, total = 0, longest = 0;
+        for (int pass = 0; pass < 8; ++pass) {
+            std::vector<blok_component> floating;
+            for (const blok_component& c : m_tracer->labelComponents())
+                if (!(c.touches & (1u << 3))) floating.push_back(c);
+            if (floating.empty()) break;
+            std::sort(floating.begin(), floating.end(), [](const blok_component& a, const blok_component& b) {
+                return a.lo[1] != b.lo[1] ? a.lo[1] < b.lo[1] : a.label < b.label; });
+            for (const blok_component& c : floating) {
+                blok_instance piece{};
+                uint64_t n = 0;
+                piece.model = m_tracer->captureComponent(c.label, true, piece.offset, &n);
+                piece.axis[0] = 0; piece.axis[1] = 1; piece.axis[2] = 2;
+                const blok_sweep_result fall = m_tracer->sweepModels({piece}, 3u, height, true)[0];
+                piece.offset[1] -= static_cast<int32_t>(fall.travel);
+                m_tracer->stampModels({piece}, BLOK_STAMP_SET, 1.0f);
+                m_tracer->destroyModel(piece.model);
+                ++pieces; voxels += n; total += fall.travel; longest = std::max<uint64_t>(longest, fall.travel);
+            }
+        }
+        m_tracer->rebuildVolume(m_materials.packForGpu());
+        uint64_t left = 0;
+        const std::vector<blok_component> records = m_tracer->labelComponents();
+        for (const blok_component& c : records) left += !(c.touches & (1u << 3));
+        std::cout << "settle: " << pieces << " pieces, " << voxels << " voxels, travel " << total << " in total, longest " << longest << "; "
+                  << records.size() << " components after, " << left << " not touching the floor\n";
+    }
     void update() {
         using clock = std::chrono::steady_clock;
         for (uint32_t f = 0; f < m_opt.frames; ++f) {
@@ -283,6 +321,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--terrain-size")) opt.terrain_size = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--export-obj")) opt.export_obj = next();
         else if (!std::strcmp(argv[i], "--components")) opt.components = true;
+        else if (!std::strcmp(argv[i], "--settle")) opt.settle = true;
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
