@@ -46,6 +46,27 @@ std::vector<blok::StampModel> placed_models(const blok_hip_ctx* ctx, const blok_
     }
     return models;
 }
+// The box-local region [lo, hi) of an entry's world region_lo / region_hi (both null: the whole box), with the entry's name in the messages.
+int volume_region(blok_hip_ctx* ctx, const char* op, const int32_t* region_lo, const int32_t* region_hi, uint32_t lo[3], uint32_t hi[3]) {
+    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(op) + ": one region pointer is null");
+    const blok::GpuVolume& v = ctx->volume;
+    const int64_t dims[3] = {v.nx, v.ny, v.nz};
+    for (int a = 0; a < 3; ++a) {
+        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
+        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(op) + ": region_lo above region_hi");
+        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, std::string(op) + ": region leaves the resident volume");
+        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
+    }
+    return BLOK_OK;
+}
+// A tree built on the device (gpu_volume_capture*) into the model store; box_lo / box_hi: the box of its voxels, model coordinates.
+int add_captured_model(blok_hip_ctx* ctx, const blok::GpuTree& tree, const int32_t box_lo[3], const int32_t box_hi[3], uint32_t* out_model) {
+    blok::ModelDesc m{};
+    m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
+    m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
+    for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
+    return add_model(ctx, m, out_model);
+}
 }  // namespace
 
 int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
@@ -144,16 +165,9 @@ int blok_hip_volume_generate_terrain(blok_hip_ctx* ctx, const blok_terrain_param
     static const char* const kRules[] = {"", "height octaves / cell", "cave octaves / cell", "ore cell", "a threshold above 65536", "amplitude above 65536",
                                          "|base_height| above 2^24", "density not finite or <= 0", "unknown flag bits", "CLOSE_SIDES without SHELL"};
     if (const int rule = blok::terrain::check_params(*params)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("generate_terrain: ") + kRules[rule]);
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "generate_terrain: one region pointer is null");
-    const blok::GpuVolume& v = ctx->volume;
-    const int64_t dims[3] = {v.nx, v.ny, v.nz};
     uint32_t lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
-        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "generate_terrain: region_lo above region_hi");
-        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "generate_terrain: region leaves the resident volume");
-        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
-    }
+    rc = volume_region(ctx, "generate_terrain", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
     std::string why;
     return volume_status(ctx, blok::gpu_volume_generate_terrain(&ctx->volume, *params, lo, hi, out_n_voxels, &why), why);
 }
@@ -165,16 +179,9 @@ int blok_hip_volume_extract_quads(blok_hip_ctx* ctx, const int32_t region_lo[3],
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
     if (flags & ~(BLOK_QUADS_IGNORE_MATERIAL | BLOK_QUADS_COUNT_ONLY)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "extract_quads: unknown flag bits");
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "extract_quads: one region pointer is null");
-    const blok::GpuVolume& v = ctx->volume;
-    const int64_t dims[3] = {v.nx, v.ny, v.nz};
     uint32_t lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
-        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "extract_quads: region_lo above region_hi");
-        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "extract_quads: region leaves the resident volume");
-        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
-    }
+    rc = volume_region(ctx, "extract_quads", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
     std::string why;
     blok_quad* quads = nullptr;
     uint64_t n_quads = 0, n_faces = 0;
@@ -224,17 +231,11 @@ int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3],
     if (rc != BLOK_OK) return rc;
     if (flags & ~BLOK_CAPTURE_CUT) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: unknown flag bits");
     if (!out_model) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: null output id");
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: one region pointer is null");
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "capture_model", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
     if (ctx->models.desc.size() >= std::numeric_limits<uint32_t>::max() - 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model ids exhausted");
     blok::GpuVolume& v = ctx->volume;
-    const int64_t dims[3] = {v.nx, v.ny, v.nz};
-    uint32_t lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
-        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_model: region_lo above region_hi");
-        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "capture_model: region leaves the resident volume");
-        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
-    }
     std::string why;
     blok::GpuTree tree;
     int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
@@ -242,11 +243,7 @@ int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3],
     const blok::GpuBuildStatus st = blok::gpu_volume_capture(&v, lo, hi, &tree, box_lo, box_hi, &n_voxels, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
     if (!n_voxels) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "capture_model: the region holds no filled voxel");
-    blok::ModelDesc m{};
-    m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
-    m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
-    for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
-    rc = add_model(ctx, m, out_model);
+    rc = add_captured_model(ctx, tree, box_lo, box_hi, out_model);
     if (rc != BLOK_OK) return rc;                      // (nothing is cut when there is no model)
     if (out_n_voxels) *out_n_voxels = n_voxels;
     if (flags & BLOK_CAPTURE_CUT) {
@@ -265,16 +262,9 @@ int blok_hip_volume_label_components(blok_hip_ctx* ctx, const int32_t region_lo[
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
     if (flags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "label_components: unknown flag bits");
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "label_components: one region pointer is null");
-    const blok::GpuVolume& v = ctx->volume;
-    const int64_t dims[3] = {v.nx, v.ny, v.nz};
     uint32_t lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
-        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, "label_components: region_lo above region_hi");
-        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "label_components: region leaves the resident volume");
-        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
-    }
+    rc = volume_region(ctx, "label_components", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
     std::string why;
     blok::GpuComponents snapshot;
     const blok::GpuBuildStatus st = blok::gpu_volume_label_components(&ctx->volume, lo, hi, &snapshot, &why);
@@ -334,11 +324,7 @@ int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_
     st = blok::gpu_volume_capture_labelled(&v, &ctx->components, label, lo, hi, &tree, box_lo, box_hi, &n_voxels, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
     if (!n_voxels) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "capture_component: none of the component's voxels is still filled");
-    blok::ModelDesc m{};
-    m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
-    m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
-    for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
-    rc = add_model(ctx, m, out_model);
+    rc = add_captured_model(ctx, tree, box_lo, box_hi, out_model);
     if (rc != BLOK_OK) return rc;                      // (nothing is cut when there is no model)
     if (out_n_voxels) *out_n_voxels = n_voxels;
     if (out_origin) for (int a = 0; a < 3; ++a) out_origin[a] = rec.lo[a];

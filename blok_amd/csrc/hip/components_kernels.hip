@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include "../common/components_core.h"
 
 namespace blok {
@@ -33,28 +34,10 @@ namespace {
 namespace K = components;
 
 struct LabelArgs {
-    const uint64_t* masks;
-    uint32_t nbx, nby;
-    uint32_t key_digits;                // keyed brick layout: digits of a brick's key (levels - 1); 0 = row-major
+    BrickMasks bricks;
     K::Region g;
     uint32_t b0[3], nb[3];              // the bricks that meet the region: [b0, b0 + nb)
     uint32_t* labels;
-};
-
-#define CK_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
-
-struct DeviceMem {                      // frees what it still owns on scope exit
-    std::vector<void*> ptrs;
-    ~DeviceMem() { for (void* p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, uint64_t count) {
-        void* raw = nullptr;
-        const hipError_t e = hipMalloc(&raw, std::max<uint64_t>(count, 1u) * sizeof(T));
-        if (e != hipSuccess) { (void)hipGetLastError(); return e; }
-        ptrs.push_back(raw); *p = static_cast<T*>(raw);
-        return hipSuccess;
-    }
-    void release(void* p) { for (void*& q : ptrs) if (q == p) q = nullptr; }
 };
 
 // The parent array as the kernels reach it while other waves change it: both accesses go to the device's point of coherence.
@@ -63,16 +46,6 @@ struct DeviceCells {
     __device__ __forceinline__ uint32_t load(uint32_t i) const { return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     __device__ __forceinline__ uint32_t fetch_min(uint32_t i, uint32_t v) const { return atomicMin(parent + i, v); }
 };
-
-// The mask word of brick (bx, by, bz), in either layout of GpuVolume::d_masks (the keyed index is gpu_build.hip's cell_key: 2-bit digit
-// triples x | y << 2 | z << 4, least significant level first).
-__device__ __forceinline__ uint64_t brick_mask(const LabelArgs& a, uint32_t bx, uint32_t by, uint32_t bz) {
-    if (a.key_digits == 0u) return a.masks[bx + (static_cast<size_t>(bz) * a.nby + by) * a.nbx];
-    uint64_t key = 0;
-    for (uint32_t j = 0; j < a.key_digits; ++j)
-        key |= static_cast<uint64_t>(((bx >> (2u * j)) & 3u) | (((by >> (2u * j)) & 3u) << 2) | (((bz >> (2u * j)) & 3u) << 4)) << (6u * j);
-    return a.masks[key];
-}
 
 // The bits of brick (bx, by, bz) whose voxels lie inside the region: one 4-bit mask per axis, spread over the word.
 __device__ __forceinline__ uint64_t region_cut(const K::Region& g, uint32_t bx, uint32_t by, uint32_t bz) {
@@ -83,13 +56,6 @@ __device__ __forceinline__ uint64_t region_cut(const K::Region& g, uint32_t bx, 
         if (bz * 4u + i - g.lo[2] < g.ext[2]) Z |= 0xFFFFull << (16u * i);
     }
     return X & Y & Z;
-}
-
-// (the builtin returns int: each half goes through uint32_t, or a low word with bit 31 set would sign-extend over the high word)
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)));
-    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32)));
-    return static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32);
 }
 
 // One step of the flood: every set bit spreads to its six face neighbours inside the brick (the masks stop the shifts from wrapping
@@ -112,7 +78,7 @@ __global__ __launch_bounds__(256) void brick_label_kernel(const LabelArgs a, uin
     uint32_t bx, by, bz;
     if (!brick_of_wave(a, n_bricks, bx, by, bz)) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t m = uniform64(brick_mask(a, bx, by, bz) & region_cut(a.g, bx, by, bz));
+    const uint64_t m = uniform64(a.bricks.at(bx, by, bz) & region_cut(a.g, bx, by, bz));
     uint32_t first = 0u;                                         // bit of the lowest voxel of this lane's in-brick component
     if (m != ~0ull) {                                            // (a full brick is one component: no loop)
         uint64_t rest = m;
@@ -137,11 +103,11 @@ __global__ __launch_bounds__(256) void brick_merge_kernel(const LabelArgs a, uin
     uint32_t bx, by, bz;
     if (!brick_of_wave(a, n_bricks, bx, by, bz)) return;
     const uint32_t lane = threadIdx.x & 63u, d = lane >> 4, j = lane & 15u;
-    const uint64_t m = uniform64(brick_mask(a, bx, by, bz) & region_cut(a.g, bx, by, bz));
+    const uint64_t m = uniform64(a.bricks.at(bx, by, bz) & region_cut(a.g, bx, by, bz));
     if (!m || d == 3u) return;
     const uint32_t qx = bx + (d == 0u ? 1u : 0u), qy = by + (d == 1u ? 1u : 0u), qz = bz + (d == 2u ? 1u : 0u);
     if (qx >= a.b0[0] + a.nb[0] || qy >= a.b0[1] + a.nb[1] || qz >= a.b0[2] + a.nb[2]) return;      // no brick of the region on that side
-    const uint64_t mq = brick_mask(a, qx, qy, qz) & region_cut(a.g, qx, qy, qz);
+    const uint64_t mq = a.bricks.at(qx, qy, qz) & region_cut(a.g, qx, qy, qz);
     // voxel j of the side: the two coordinates other than d, lower axis first
     const uint32_t u = j & 3u, w = j >> 2;
     const uint32_t x = d == 0u ? 3u : u, y = d == 1u ? 3u : (d == 0u ? u : w), z = d == 2u ? 3u : w;
@@ -275,48 +241,47 @@ GpuBuildStatus gpu_volume_label_components(const GpuVolume* v, const uint32_t lo
     const uint64_t n = K::cells(a.g);
     if (n > 0xFFFFFFFFull) { *why = "label_components: region of 2^32 cells"; return GpuBuildStatus::Unsupported; }
     if (n == 0) { out->ext[0] = out->ext[1] = out->ext[2] = 0u; return GpuBuildStatus::Ok; }
-    a.masks = v->d_masks; a.nbx = v->nbx; a.nby = v->nby;
-    a.key_digits = v->keyed ? v->levels - 1u : 0u;
+    a.bricks = brick_masks_of(*v);
     for (int k = 0; k < 3; ++k) { a.b0[k] = lo[k] / 4u; a.nb[k] = (hi[k] + 3u) / 4u - a.b0[k]; }
     const uint64_t n_bricks = static_cast<uint64_t>(a.nb[0]) * a.nb[1] * a.nb[2];
     const uint64_t n_rows = (n + 63u) / 64u;
     DeviceMem mem;
     uint64_t *d_root_bits, *d_packed, *d_row_base;
-    CK_TRY(mem.alloc(&a.labels, n));
-    CK_TRY(mem.alloc(&d_root_bits, n_rows));
-    CK_TRY(mem.alloc(&d_packed, n_rows + 1u));
-    CK_TRY(mem.alloc(&d_row_base, n_rows + 1u));
-    CK_TRY(hipMemsetAsync(d_packed + n_rows, 0, sizeof(uint64_t), nullptr));
+    BLOK_GPU_TRY(mem.alloc(&a.labels, n));
+    BLOK_GPU_TRY(mem.alloc(&d_root_bits, n_rows));
+    BLOK_GPU_TRY(mem.alloc(&d_packed, n_rows + 1u));
+    BLOK_GPU_TRY(mem.alloc(&d_row_base, n_rows + 1u));
+    BLOK_GPU_TRY(hipMemsetAsync(d_packed + n_rows, 0, sizeof(uint64_t), nullptr));
     // (edits are enqueued on the null stream, and so is this: it reads the masks they leave)
     const dim3 brick_grid(static_cast<uint32_t>((n_bricks + 3u) / 4u));
     hipLaunchKernelGGL(brick_label_kernel, brick_grid, dim3(256), 0, nullptr, a, n_bricks);
-    CK_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     hipLaunchKernelGGL(brick_merge_kernel, brick_grid, dim3(256), 0, nullptr, a, n_bricks);
-    CK_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, a.labels, n, n_rows, d_root_bits, d_packed);
-    CK_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     size_t temp_bytes = 0;
-    CK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_packed, d_row_base, static_cast<int>(n_rows + 1u)));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_packed, d_row_base, static_cast<int>(n_rows + 1u)));
     uint8_t* d_temp;
-    CK_TRY(mem.alloc(&d_temp, temp_bytes));
-    CK_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_packed, d_row_base, static_cast<int>(n_rows + 1u)));
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_packed, d_row_base, static_cast<int>(n_rows + 1u)));
     uint64_t totals = 0;
-    CK_TRY(hipMemcpy(&totals, d_row_base + n_rows, sizeof(totals), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&totals, d_row_base + n_rows, sizeof(totals), hipMemcpyDeviceToHost));
     const uint64_t n_components = totals & 0xFFFFFFFFull, n_voxels = totals >> 32;
     blok_component* d_records = nullptr;
     if (n_components) {
-        CK_TRY(mem.alloc(&d_records, n_components));
+        BLOK_GPU_TRY(mem.alloc(&d_records, n_components));
         hipLaunchKernelGGL(record_init_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, d_root_bits, d_row_base, n, d_records);
-        CK_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
         RecordArgs r{};
         r.labels = a.labels; r.root_bits = d_root_bits; r.row_base = d_row_base; r.g = a.g; r.n = n; r.n_rows = n_rows; r.records = d_records;
         hipLaunchKernelGGL(record_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r);
-        CK_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
         hipLaunchKernelGGL(record_finish_kernel, dim3(blocks_for(n_components)), dim3(256), 0, nullptr, d_records, n_components, a.g,
                            v->origin[0], v->origin[1], v->origin[2]);
-        CK_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
     }
-    CK_TRY(hipDeviceSynchronize());
+    BLOK_GPU_TRY(hipDeviceSynchronize());
     mem.release(a.labels); mem.release(d_root_bits); mem.release(d_row_base); mem.release(d_records);
     out->d_labels = a.labels; out->d_root_bits = d_root_bits; out->d_row_base = d_row_base; out->d_records = d_records;
     out->n_cells = n; out->n_components = n_components; out->n_voxels = n_voxels;
@@ -327,13 +292,13 @@ GpuBuildStatus gpu_components_find(const GpuComponents* c, uint32_t label, blok_
     *found = false;
     if (label >= c->n_cells) return GpuBuildStatus::Ok;
     uint32_t at = 0;
-    CK_TRY(hipMemcpy(&at, c->d_labels + label, sizeof(at), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&at, c->d_labels + label, sizeof(at), hipMemcpyDeviceToHost));
     if (at != label) return GpuBuildStatus::Ok;                  // not a root: no record carries this label
     uint64_t bits = 0, base = 0;
-    CK_TRY(hipMemcpy(&bits, c->d_root_bits + (label >> 6), sizeof(bits), hipMemcpyDeviceToHost));
-    CK_TRY(hipMemcpy(&base, c->d_row_base + (label >> 6), sizeof(base), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&bits, c->d_root_bits + (label >> 6), sizeof(bits), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&base, c->d_row_base + (label >> 6), sizeof(base), hipMemcpyDeviceToHost));
     const uint64_t rank = (base & 0xFFFFFFFFull) + static_cast<uint64_t>(__builtin_popcountll(bits & ((1ull << (label & 63u)) - 1ull)));
-    CK_TRY(hipMemcpy(out, c->d_records + rank, sizeof(*out), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(out, c->d_records + rank, sizeof(*out), hipMemcpyDeviceToHost));
     *found = true;
     return GpuBuildStatus::Ok;
 }

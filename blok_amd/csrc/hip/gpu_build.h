@@ -7,6 +7,7 @@
 
 #include "blok_hip.h"
 #include "tree.h"
+#include "volume_device.h"
 
 namespace blok {
 
@@ -80,6 +81,9 @@ struct GpuVolume {
     bool edit_may_add = false;                   // ... and one of those edits may have FILLED a voxel (an ADD brush with a positive value, setVoxel): what the shadow rays' map has to know
 };
 
+// The volume's brick masks as a kernel reads them, in whichever layout the volume has (volume_device.h).
+inline BrickMasks brick_masks_of(const GpuVolume& v) { return BrickMasks{v.d_masks, v.nbx, v.nby, v.keyed ? v.levels - 1u : 0u}; }
+
 GpuBuildStatus gpu_volume_create(const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, uint32_t chunk, float voxel_size,
                                  GpuVolume* out, std::string* why, bool allow_keyed = true);
 void gpu_volume_destroy(GpuVolume* v);
@@ -113,6 +117,13 @@ struct StampModel {
     uint32_t levels;
     int32_t origin[3], lo[3], hi[3];                    // the tree's corner and the box of its voxels, local coordinates
 };
+// The bricks of the model's tree, counted from its corner, that hold the voxels of the non-empty local box [clo, chi): [b0, b0 + nb).
+inline void placed_brick_range(const StampModel& M, const int64_t clo[3], const int64_t chi[3], uint32_t b0[3], uint32_t nb[3]) {
+    for (int k = 0; k < 3; ++k) {
+        b0[k] = static_cast<uint32_t>((clo[k] - M.origin[k]) >> 2);
+        nb[k] = static_cast<uint32_t>((chi[k] - 1 - M.origin[k]) >> 2) - b0[k] + 1u;
+    }
+}
 GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements, int mode,
                                 float density, uint64_t* out_n_voxels, std::string* why);
 // = blok_hip_volume_capture_model (include/blok_hip.h) over the box-local region [lo, hi): the tree of the region's filled voxels in the

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -97,7 +98,8 @@ __global__ __launch_bounds__(256) void brick_mask_kernel(const WalkCtx c, uint64
 
 struct KeyCtx { int32_t origin[3]; uint32_t levels; };
 
-// Key of a brick: the 2-bit digit triples of levels 1..L-1 of its corner, least significant level first.
+// Key of a brick: the 2-bit digit triples of levels 1..L-1 of its corner, least significant level first: cell_key (volume_device.h) of the
+// brick's coordinates, written out over the VOXEL coordinates here and in dense_key_kernel (through cell_key, brick_key_kernel takes a register more).
 __global__ __launch_bounds__(256) void brick_key_kernel(const WalkCtx c, const KeyCtx k, const uint64_t* masks,
                                                         const uint32_t* slot_of, uint64_t total, uint64_t* keys, uint32_t* src) {
     const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
@@ -156,80 +158,65 @@ __global__ __launch_bounds__(256) void brick_node_kernel(const uint64_t* masks_s
     out[i] = make_uint4(static_cast<uint32_t>(m), static_cast<uint32_t>(m >> 32), mat_base[i], 0u);
 }
 
-struct DeviceBuffers {          // frees everything it still owns on scope exit
-    std::vector<void*> ptrs;
-    ~DeviceBuffers() { for (void* p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t count) {
-        *p = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    void release(void* p) { for (void*& q : ptrs) if (q == p) q = nullptr; }
-};
-
-#define GB_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
-
 inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255u) / 256u); }
 
 // Common tail of the builders: compaction of the non-empty bricks, keys, radix sort, material offsets, material
 // ids, upper levels, final node array.  `launch_keys` / `launch_materials` enqueue the source-specific kernels.
 template <class KeyLauncher, class MaterialLauncher>
-GpuBuildStatus finish_from_masks(DeviceBuffers& mem, uint64_t total, const uint64_t* d_masks, uint32_t* d_flag, uint32_t* d_slot,
+GpuBuildStatus finish_from_masks(DeviceMem& mem, uint64_t total, const uint64_t* d_masks, uint32_t* d_flag, uint32_t* d_slot,
                                  uint32_t levels, const int32_t lo[3], KeyLauncher launch_keys, MaterialLauncher launch_materials,
                                  GpuTree* out, std::string* why) {
     size_t temp_bytes = 0;
-    GB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_flag, d_slot, static_cast<int>(total + 1)));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_flag, d_slot, static_cast<int>(total + 1)));
     size_t scan_bytes = temp_bytes;
     uint8_t* d_scratch;
-    GB_TRY(mem.alloc(&d_scratch, scan_bytes));
-    GB_TRY(hipcub::DeviceScan::ExclusiveSum(d_scratch, temp_bytes, d_flag, d_slot, static_cast<int>(total + 1)));
+    BLOK_GPU_TRY(mem.alloc(&d_scratch, scan_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_scratch, temp_bytes, d_flag, d_slot, static_cast<int>(total + 1)));
     uint32_t n_bricks = 0;
-    GB_TRY(hipMemcpy(&n_bricks, d_slot + total, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&n_bricks, d_slot + total, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (n_bricks == 0) return GpuBuildStatus::UseHostBuilder;
 
     uint64_t *d_keys, *d_keys_sorted, *d_masks_sorted; uint32_t *d_src, *d_src_sorted, *d_counts, *d_mat_base;
-    GB_TRY(mem.alloc(&d_keys, n_bricks)); GB_TRY(mem.alloc(&d_keys_sorted, n_bricks));
-    GB_TRY(mem.alloc(&d_src, n_bricks)); GB_TRY(mem.alloc(&d_src_sorted, n_bricks));
-    GB_TRY(mem.alloc(&d_masks_sorted, n_bricks));
-    GB_TRY(mem.alloc(&d_counts, n_bricks + 1)); GB_TRY(mem.alloc(&d_mat_base, n_bricks + 1));
+    BLOK_GPU_TRY(mem.alloc(&d_keys, n_bricks)); BLOK_GPU_TRY(mem.alloc(&d_keys_sorted, n_bricks));
+    BLOK_GPU_TRY(mem.alloc(&d_src, n_bricks)); BLOK_GPU_TRY(mem.alloc(&d_src_sorted, n_bricks));
+    BLOK_GPU_TRY(mem.alloc(&d_masks_sorted, n_bricks));
+    BLOK_GPU_TRY(mem.alloc(&d_counts, n_bricks + 1)); BLOK_GPU_TRY(mem.alloc(&d_mat_base, n_bricks + 1));
     launch_keys(d_slot, d_keys, d_src);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     const int key_bits = std::max(1, static_cast<int>(6 * (levels - 1)));
     temp_bytes = 0;
-    GB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys, d_keys_sorted, d_src, d_src_sorted, static_cast<int>(n_bricks), 0, key_bits));
+    BLOK_GPU_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys, d_keys_sorted, d_src, d_src_sorted, static_cast<int>(n_bricks), 0, key_bits));
     uint8_t* d_sort_scratch;
-    GB_TRY(mem.alloc(&d_sort_scratch, temp_bytes));
-    GB_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_scratch, temp_bytes, d_keys, d_keys_sorted, d_src, d_src_sorted, static_cast<int>(n_bricks), 0, key_bits));
+    BLOK_GPU_TRY(mem.alloc(&d_sort_scratch, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_scratch, temp_bytes, d_keys, d_keys_sorted, d_src, d_src_sorted, static_cast<int>(n_bricks), 0, key_bits));
     hipLaunchKernelGGL(gather_mask_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, nullptr, d_masks, d_src_sorted, n_bricks, d_masks_sorted, d_counts);
-    GB_TRY(hipGetLastError());
-    GB_TRY(hipMemset(d_counts + n_bricks, 0, sizeof(uint32_t)));
+    BLOK_GPU_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipMemset(d_counts + n_bricks, 0, sizeof(uint32_t)));
     temp_bytes = 0;
-    GB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_counts, d_mat_base, static_cast<int>(n_bricks + 1)));
-    if (temp_bytes > scan_bytes) { GB_TRY(mem.alloc(&d_scratch, temp_bytes)); scan_bytes = temp_bytes; }
-    GB_TRY(hipcub::DeviceScan::ExclusiveSum(d_scratch, temp_bytes, d_counts, d_mat_base, static_cast<int>(n_bricks + 1)));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_counts, d_mat_base, static_cast<int>(n_bricks + 1)));
+    if (temp_bytes > scan_bytes) { BLOK_GPU_TRY(mem.alloc(&d_scratch, temp_bytes)); scan_bytes = temp_bytes; }
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_scratch, temp_bytes, d_counts, d_mat_base, static_cast<int>(n_bricks + 1)));
     uint32_t n_voxels = 0;
-    GB_TRY(hipMemcpy(&n_voxels, d_mat_base + n_bricks, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&n_voxels, d_mat_base + n_bricks, sizeof(uint32_t), hipMemcpyDeviceToHost));
 
     uint32_t* d_materials;
-    GB_TRY(mem.alloc(&d_materials, n_voxels));
+    BLOK_GPU_TRY(mem.alloc(&d_materials, n_voxels));
     launch_materials(d_masks_sorted, d_src_sorted, d_mat_base, n_bricks, d_materials);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
 
     // the levels above the bricks, on the host, from the sorted keys
     std::vector<uint64_t> keys(n_bricks);
-    GB_TRY(hipMemcpy(keys.data(), d_keys_sorted, n_bricks * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(keys.data(), d_keys_sorted, n_bricks * sizeof(uint64_t), hipMemcpyDeviceToHost));
     std::vector<TreeNode> upper;
     if (!build_upper_levels(keys, levels, upper)) return GpuBuildStatus::UseHostBuilder;    // duplicate bricks: general path
     uint4* d_tree;
     const size_t n_tree = upper.size() + n_bricks;
-    GB_TRY(mem.alloc(&d_tree, n_tree));
-    GB_TRY(hipMemcpy(d_tree, upper.data(), upper.size() * sizeof(TreeNode), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(mem.alloc(&d_tree, n_tree));
+    BLOK_GPU_TRY(hipMemcpy(d_tree, upper.data(), upper.size() * sizeof(TreeNode), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(brick_node_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, nullptr, d_masks_sorted, d_mat_base, n_bricks,
                        d_tree + upper.size());
-    GB_TRY(hipGetLastError());
-    GB_TRY(hipDeviceSynchronize());
+    BLOK_GPU_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipDeviceSynchronize());
 
     mem.release(d_tree); mem.release(d_materials);
     out->d_nodes = d_tree; out->d_materials = d_materials;
@@ -284,24 +271,24 @@ GpuBuildStatus gpu_build_tree(const blok_svo_node* nodes, size_t n_nodes, const 
     const uint64_t total = static_cast<uint64_t>(n_subs) * c.bricks_per_sub;
     if (total > 0x7FFFFFFFull) return GpuBuildStatus::UseHostBuilder;
 
-    DeviceBuffers mem;
+    DeviceMem mem;
     blok_svo_node* d_nodes_ref; blok_sub_chunk* d_subs; uint64_t* d_masks; uint32_t *d_flag, *d_slot, *d_error;
-    GB_TRY(mem.alloc(&d_nodes_ref, n_nodes));
-    GB_TRY(mem.alloc(&d_subs, n_subs));
-    GB_TRY(mem.alloc(&d_masks, total));
-    GB_TRY(mem.alloc(&d_flag, total + 1));
-    GB_TRY(mem.alloc(&d_slot, total + 1));
-    GB_TRY(mem.alloc(&d_error, 1));
-    GB_TRY(hipMemcpy(d_nodes_ref, nodes, n_nodes * sizeof(blok_svo_node), hipMemcpyHostToDevice));
-    GB_TRY(hipMemcpy(d_subs, subs, n_subs * sizeof(blok_sub_chunk), hipMemcpyHostToDevice));
-    GB_TRY(hipMemset(d_error, 0, sizeof(uint32_t)));
-    GB_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
+    BLOK_GPU_TRY(mem.alloc(&d_nodes_ref, n_nodes));
+    BLOK_GPU_TRY(mem.alloc(&d_subs, n_subs));
+    BLOK_GPU_TRY(mem.alloc(&d_masks, total));
+    BLOK_GPU_TRY(mem.alloc(&d_flag, total + 1));
+    BLOK_GPU_TRY(mem.alloc(&d_slot, total + 1));
+    BLOK_GPU_TRY(mem.alloc(&d_error, 1));
+    BLOK_GPU_TRY(hipMemcpy(d_nodes_ref, nodes, n_nodes * sizeof(blok_svo_node), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(hipMemcpy(d_subs, subs, n_subs * sizeof(blok_sub_chunk), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(hipMemset(d_error, 0, sizeof(uint32_t)));
+    BLOK_GPU_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
     c.nodes = d_nodes_ref; c.subs = d_subs;
 
     hipLaunchKernelGGL(brick_mask_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, c, d_masks, d_flag, d_error);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     uint32_t error = 0;
-    GB_TRY(hipMemcpy(&error, d_error, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&error, d_error, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (error & kErrLeafAboveVoxel) { *why = "filled leaf above voxel level (not produced by SvoTree::insertVoxel)"; return GpuBuildStatus::Unsupported; }
     if (error & kErrInteriorBelowVoxel) { *why = "interior node below voxel level"; return GpuBuildStatus::Unsupported; }
     KeyCtx k{}; for (int a = 0; a < 3; ++a) k.origin[a] = lo[a]; k.levels = levels;
@@ -401,17 +388,17 @@ GpuBuildStatus gpu_build_tree_dense(const uint32_t* ids, uint32_t nx, uint32_t n
     d.rbx = d.bx; d.rby = d.by; d.rbz = d.bz;
     const uint64_t total = static_cast<uint64_t>(d.bx) * d.by * d.bz;
     if (total > 0x7FFFFFFFull) return GpuBuildStatus::UseHostBuilder;
-    DeviceBuffers mem;
+    DeviceMem mem;
     uint32_t* d_ids; uint64_t* d_masks; uint32_t *d_flag, *d_slot;
-    GB_TRY(mem.alloc(&d_ids, cells));
-    GB_TRY(mem.alloc(&d_masks, total));
-    GB_TRY(mem.alloc(&d_flag, total + 1));
-    GB_TRY(mem.alloc(&d_slot, total + 1));
-    GB_TRY(hipMemcpy(d_ids, ids, cells * sizeof(uint32_t), hipMemcpyHostToDevice));
-    GB_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
+    BLOK_GPU_TRY(mem.alloc(&d_ids, cells));
+    BLOK_GPU_TRY(mem.alloc(&d_masks, total));
+    BLOK_GPU_TRY(mem.alloc(&d_flag, total + 1));
+    BLOK_GPU_TRY(mem.alloc(&d_slot, total + 1));
+    BLOK_GPU_TRY(hipMemcpy(d_ids, ids, cells * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
     d.ids = d_ids;
     hipLaunchKernelGGL(dense_brick_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, total, d_masks, d_flag);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     const int32_t lo[3] = {origin[0], origin[1], origin[2]};
     return finish_from_masks(mem, total, d_masks, d_flag, d_slot, levels, lo,
         [&](const uint32_t* slot, uint64_t* keys, uint32_t* src) {
@@ -446,7 +433,7 @@ GpuBuildStatus volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t
     if (!total) return GpuBuildStatus::Ok;
     ++v->refreshes[2];
     hipLaunchKernelGGL(dense_brick_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, total, v->d_masks, v->d_flag);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     return GpuBuildStatus::Ok;
 }
 
@@ -494,23 +481,7 @@ __global__ __launch_bounds__(256) void volume_brush_kernel(const BrushCtx b) {
 }
 
 
-// ---- keyed layout (gpu_build.h: GpuVolume::keyed) -------------------------------------------------------------------------------
-// Key of a cell from its coordinates in units of its own size: `digits` 2-bit digit triples, least significant level first
-// (x | y << 2 | z << 4 per digit, the tree's child bit order).  A brick's key has levels-1 digits, a level-l cell's levels-l.
-__host__ __device__ inline uint64_t cell_key(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t digits) {
-    uint64_t key = 0;
-    for (uint32_t j = 0; j < digits; ++j)
-        key |= static_cast<uint64_t>(((cx >> (2u * j)) & 3u) | (((cy >> (2u * j)) & 3u) << 2) | (((cz >> (2u * j)) & 3u) << 4)) << (6u * j);
-    return key;
-}
-__device__ inline void key_cell(uint64_t key, uint32_t digits, uint32_t& cx, uint32_t& cy, uint32_t& cz) {
-    cx = cy = cz = 0;
-    for (uint32_t j = 0; j < digits; ++j) {
-        const uint32_t d = static_cast<uint32_t>(key >> (6u * j)) & 63u;
-        cx |= (d & 3u) << (2u * j); cy |= ((d >> 2) & 3u) << (2u * j); cz |= (d >> 4) << (2u * j);
-    }
-}
-
+// ---- keyed layout (gpu_build.h: GpuVolume::keyed; the key itself is volume_device.h: cell_key) ---------------------------------------
 struct KeyedCtx {
     const float* density; const uint32_t* ids;
     uint32_t nx, ny, nz, levels;
@@ -708,19 +679,19 @@ GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t 
     ++v->refreshes[small ? 0 : 1];
     if (small) {
         hipLaunchKernelGGL(keyed_brick_wave_kernel, dim3(static_cast<uint32_t>(totals[1])), dim3(64), 0, nullptr, k, ranges[1]);
-        GB_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
         if (v->levels >= 2) {
             OccLevels o{};
             o.first = 2; o.last = v->levels;
             for (uint32_t l = 2; l <= v->levels; ++l) { o.below[l] = l == 2 ? v->d_masks : v->d_occ[l - 1]; o.occ[l] = v->d_occ[l]; o.digits[l] = v->levels - l; o.range[l] = ranges[l]; }
             hipLaunchKernelGGL(occupancy_levels_kernel, dim3(1), dim3(256), 0, nullptr, o);
-            GB_TRY(hipGetLastError());
+            BLOK_GPU_TRY(hipGetLastError());
         }
     } else {
         for (uint32_t l = 1; l <= v->levels; ++l) {
             if (l == 1) hipLaunchKernelGGL(keyed_brick_kernel, dim3(blocks_for(totals[l])), dim3(256), 0, nullptr, k, ranges[l]);
             else hipLaunchKernelGGL(occupancy_kernel, dim3(blocks_for(totals[l])), dim3(256), 0, nullptr, l == 2 ? v->d_masks : v->d_occ[l - 1], v->d_occ[l], v->levels - l, ranges[l]);
-            GB_TRY(hipGetLastError());
+            BLOK_GPU_TRY(hipGetLastError());
         }
     }
     for (int a = 0; a < 3; ++a) { v->edit_lo[a] = std::min(v->edit_lo[a], lo[a]); v->edit_hi[a] = std::max(v->edit_hi[a], hi[a]); }
@@ -753,26 +724,26 @@ GpuBuildStatus keyed_build(GpuVolume* v, GpuTree* out, std::string* why) {
     for (uint32_t l = 2; l <= L; ++l) cells[l] = 1ull << (6u * (L - l));
     // 1. per level: (word != 0) << 32 | popcount, exclusively scanned, totals in the extra element — levels of <= 4096 cells all in one
     //    workgroup, larger ones with a device-wide scan each
-    if (!S.d_info) GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_info), 32 * sizeof(uint64_t)));
+    if (!S.d_info) BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_info), 32 * sizeof(uint64_t)));
     SmallLevels small{};
     small.first = 8; small.last = 0;
     for (uint32_t l = 2; l <= L; ++l) {
-        if (!S.d_packed[l]) { GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_packed[l]), (cells[l] + 1u) * sizeof(uint64_t))); GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_scanned[l]), (cells[l] + 1u) * sizeof(uint64_t))); }
+        if (!S.d_packed[l]) { BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_packed[l]), (cells[l] + 1u) * sizeof(uint64_t))); BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_scanned[l]), (cells[l] + 1u) * sizeof(uint64_t))); }
         if (cells[l] <= 4096u) { small.occ[l] = v->d_occ[l]; small.scanned[l] = S.d_scanned[l]; small.cells[l] = cells[l]; small.first = std::min(small.first, l); small.last = std::max(small.last, l); continue; }
         hipLaunchKernelGGL(pack_kernel, dim3(blocks_for(cells[l] + 1u)), dim3(256), 0, nullptr, v->d_occ[l], cells[l], S.d_packed[l]);
-        GB_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
         size_t need = 0;
-        GB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, S.d_packed[l], S.d_scanned[l], static_cast<int>(cells[l] + 1u)));
-        if (need > S.scan_temp_bytes) { if (S.d_scan_temp) { GB_TRY(hipDeviceSynchronize()); (void)hipFree(S.d_scan_temp); } S.d_scan_temp = nullptr; GB_TRY(hipMalloc(&S.d_scan_temp, need * 2 + 256)); S.scan_temp_bytes = need * 2 + 256; }
+        BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, S.d_packed[l], S.d_scanned[l], static_cast<int>(cells[l] + 1u)));
+        if (need > S.scan_temp_bytes) { if (S.d_scan_temp) { BLOK_GPU_TRY(hipDeviceSynchronize()); (void)hipFree(S.d_scan_temp); } S.d_scan_temp = nullptr; BLOK_GPU_TRY(hipMalloc(&S.d_scan_temp, need * 2 + 256)); S.scan_temp_bytes = need * 2 + 256; }
         size_t bytes = S.scan_temp_bytes;
-        GB_TRY(hipcub::DeviceScan::ExclusiveSum(S.d_scan_temp, bytes, S.d_packed[l], S.d_scanned[l], static_cast<int>(cells[l] + 1u)));
+        BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(S.d_scan_temp, bytes, S.d_packed[l], S.d_scanned[l], static_cast<int>(cells[l] + 1u)));
         small.big_total[l] = S.d_scanned[l] + cells[l];
     }
     hipLaunchKernelGGL(small_levels_kernel, dim3(1), dim3(1024), 0, nullptr, small, S.d_info);      // (small.first > small.last: just the big levels' totals)
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     clock.mark("scans-enqueued");
     uint64_t totals[8] = {};
-    GB_TRY(hipMemcpy(totals, S.d_info, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(totals, S.d_info, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     clock.mark("totals-read");              // the one wait in the middle: the launch sizes below
     uint32_t n_nodes[9] = {};                                               // nodes per level; n_nodes[1] = bricks
     for (uint32_t l = 2; l <= L; ++l) { n_nodes[l] = static_cast<uint32_t>(totals[l] >> 32); if (l == 2) n_nodes[1] = static_cast<uint32_t>(totals[l]); }
@@ -782,36 +753,36 @@ GpuBuildStatus keyed_build(GpuVolume* v, GpuTree* out, std::string* why) {
     { uint64_t at = 0; for (uint32_t l = L; l >= 1; --l) { start[l] = static_cast<uint32_t>(at); at += n_nodes[l]; } if (at > 0xFFFFFFFFull) { *why = "volume: more than 2^32 tree nodes"; return GpuBuildStatus::Unsupported; } }
     const uint64_t n_tree = static_cast<uint64_t>(start[1]) + n_bricks;
     const int next = S.current == 0 ? 1 : 0;
-    GB_TRY(grow(&S.d_tree[next], &S.tree_capacity[next], n_tree));
+    BLOK_GPU_TRY(grow(&S.d_tree[next], &S.tree_capacity[next], n_tree));
     // by its bound (no wait for the voxel count), with a sixteenth to spare: sized exactly, every edit that added a brick re-allocated 59 MB —
     // a device-wide wait, a free and a malloc, 210 us of the 0.44 ms a radius-8 brush took to become a tree (BLOK_VOLUME_TIMING, round 4)
-    GB_TRY(grow(&S.d_materials[next], &S.material_capacity[next], static_cast<uint64_t>(n_bricks) * 64u, 17, 16));
+    BLOK_GPU_TRY(grow(&S.d_materials[next], &S.material_capacity[next], static_cast<uint64_t>(n_bricks) * 64u, 17, 16));
     if (S.brick_capacity < n_bricks + 1ull) {
-        GB_TRY(hipDeviceSynchronize());
+        BLOK_GPU_TRY(hipDeviceSynchronize());
         for (void* p : {static_cast<void*>(S.d_masks_sorted), static_cast<void*>(S.d_src), static_cast<void*>(S.d_counts), static_cast<void*>(S.d_mat_base)}) if (p) (void)hipFree(p);
         const uint64_t want = (n_bricks + 1ull) * 5u / 4u + 64u;
-        GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_masks_sorted), want * sizeof(uint64_t))); GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_src), want * sizeof(uint32_t)));
-        GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_counts), want * sizeof(uint32_t))); GB_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_mat_base), want * sizeof(uint32_t)));
+        BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_masks_sorted), want * sizeof(uint64_t))); BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_src), want * sizeof(uint32_t)));
+        BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_counts), want * sizeof(uint32_t))); BLOK_GPU_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_mat_base), want * sizeof(uint32_t)));
         S.brick_capacity = want;
     }
-    GB_TRY(grow(&S.d_cells2, &S.cells2_capacity, n_nodes[2]));
+    BLOK_GPU_TRY(grow(&S.d_cells2, &S.cells2_capacity, n_nodes[2]));
     clock.mark("grown");
     // 2. nodes of levels L .. 2, the list of non-empty level-2 cells
     for (uint32_t l = L; l >= 2; --l) {
         hipLaunchKernelGGL(level_nodes_kernel, dim3(blocks_for(cells[l])), dim3(256), 0, nullptr, v->d_occ[l], S.d_scanned[l], cells[l], start[l], start[l - 1],
                            S.d_tree[next], l == 2 ? S.d_cells2 : nullptr);
-        GB_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
     }
     clock.mark("level-nodes");
     // 3. the non-empty bricks in key order, their voxel counts, the material offsets
     hipLaunchKernelGGL(gather_bricks_kernel, dim3(n_nodes[2]), dim3(64), 0, nullptr, v->d_occ[2], S.d_scanned[2], S.d_cells2, v->d_masks, S.d_masks_sorted, S.d_src, S.d_counts, n_bricks);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     {
         size_t need = 0;
-        GB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, S.d_counts, S.d_mat_base, static_cast<int>(n_bricks + 1u)));
-        if (need > S.scan_temp_bytes) { GB_TRY(hipDeviceSynchronize()); if (S.d_scan_temp) (void)hipFree(S.d_scan_temp); S.d_scan_temp = nullptr; GB_TRY(hipMalloc(&S.d_scan_temp, need * 2 + 256)); S.scan_temp_bytes = need * 2 + 256; }
+        BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, S.d_counts, S.d_mat_base, static_cast<int>(n_bricks + 1u)));
+        if (need > S.scan_temp_bytes) { BLOK_GPU_TRY(hipDeviceSynchronize()); if (S.d_scan_temp) (void)hipFree(S.d_scan_temp); S.d_scan_temp = nullptr; BLOK_GPU_TRY(hipMalloc(&S.d_scan_temp, need * 2 + 256)); S.scan_temp_bytes = need * 2 + 256; }
         size_t bytes = S.scan_temp_bytes;
-        GB_TRY(hipcub::DeviceScan::ExclusiveSum(S.d_scan_temp, bytes, S.d_counts, S.d_mat_base, static_cast<int>(n_bricks + 1u)));
+        BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(S.d_scan_temp, bytes, S.d_counts, S.d_mat_base, static_cast<int>(n_bricks + 1u)));
     }
     clock.mark("gather+scan");
     // 4. material ids (untouched bricks from the previous build's array), brick nodes
@@ -819,13 +790,13 @@ GpuBuildStatus keyed_build(GpuVolume* v, GpuTree* out, std::string* why) {
     const uint32_t* previous = S.have_previous_materials && S.current >= 0 ? S.d_materials[S.current] : nullptr;
     hipLaunchKernelGGL(keyed_material_kernel, dim3(blocks_for(static_cast<uint64_t>(n_bricks) * 16u)), dim3(256), 0, nullptr, k, S.d_masks_sorted, S.d_src, S.d_mat_base,
                        n_bricks, S.d_old_base, previous, S.d_materials[next]);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     hipLaunchKernelGGL(keyed_brick_nodes_kernel, dim3(blocks_for(n_bricks)), dim3(256), 0, nullptr, S.d_masks_sorted, S.d_src, S.d_mat_base, n_bricks, S.d_tree[next] + start[1],
                        S.d_old_base, v->d_dirty);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     clock.mark("nodes-enqueued");
     uint32_t n_voxels = 0;
-    GB_TRY(hipMemcpy(&n_voxels, S.d_mat_base + n_bricks, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&n_voxels, S.d_mat_base + n_bricks, sizeof(uint32_t), hipMemcpyDeviceToHost));
     clock.mark("count-read");      // also: everything above has completed
     S.current = next; S.have_previous_materials = true;
     out->d_nodes = S.d_tree[next]; out->d_materials = S.d_materials[next]; out->owned_by_volume = true;
@@ -857,25 +828,25 @@ GpuBuildStatus gpu_volume_create(const int32_t origin[3], uint32_t nx, uint32_t 
     // volumes that fill most of their cube
     v.n_keys = levels >= 2 ? 1ull << (6u * (levels - 1u)) : 0;
     v.keyed = allow_keyed && levels >= 2 && v.n_keys <= std::max<uint64_t>(1ull << 24, 8ull * v.bricks()) && v.n_keys <= 0x7FFFFFFFull;
-    DeviceBuffers mem;
-    GB_TRY(mem.alloc(&v.d_density, v.cells())); GB_TRY(mem.alloc(&v.d_ids, v.cells()));
-    GB_TRY(hipMemset(v.d_density, 0, v.cells() * sizeof(float))); GB_TRY(hipMemset(v.d_ids, 0, v.cells() * sizeof(uint32_t)));
+    DeviceMem mem;
+    BLOK_GPU_TRY(mem.alloc(&v.d_density, v.cells())); BLOK_GPU_TRY(mem.alloc(&v.d_ids, v.cells()));
+    BLOK_GPU_TRY(hipMemset(v.d_density, 0, v.cells() * sizeof(float))); BLOK_GPU_TRY(hipMemset(v.d_ids, 0, v.cells() * sizeof(uint32_t)));
     std::vector<void*> keep = {v.d_density, v.d_ids};
     if (v.keyed) {
-        GB_TRY(mem.alloc(&v.d_masks, v.n_keys)); GB_TRY(mem.alloc(&v.d_dirty, v.n_keys)); GB_TRY(mem.alloc(&v.scratch.d_old_base, v.n_keys));
-        GB_TRY(hipMemset(v.d_masks, 0, v.n_keys * sizeof(uint64_t))); GB_TRY(hipMemset(v.d_dirty, 1, v.n_keys)); GB_TRY(hipMemset(v.scratch.d_old_base, 0xFF, v.n_keys * sizeof(uint32_t)));
+        BLOK_GPU_TRY(mem.alloc(&v.d_masks, v.n_keys)); BLOK_GPU_TRY(mem.alloc(&v.d_dirty, v.n_keys)); BLOK_GPU_TRY(mem.alloc(&v.scratch.d_old_base, v.n_keys));
+        BLOK_GPU_TRY(hipMemset(v.d_masks, 0, v.n_keys * sizeof(uint64_t))); BLOK_GPU_TRY(hipMemset(v.d_dirty, 1, v.n_keys)); BLOK_GPU_TRY(hipMemset(v.scratch.d_old_base, 0xFF, v.n_keys * sizeof(uint32_t)));
         keep.insert(keep.end(), {static_cast<void*>(v.d_masks), static_cast<void*>(v.d_dirty), static_cast<void*>(v.scratch.d_old_base)});
         for (uint32_t l = 2; l <= levels; ++l) {
             const uint64_t n = 1ull << (6u * (levels - l));
-            GB_TRY(mem.alloc(&v.d_occ[l], n)); GB_TRY(hipMemset(v.d_occ[l], 0, n * sizeof(uint64_t)));
+            BLOK_GPU_TRY(mem.alloc(&v.d_occ[l], n)); BLOK_GPU_TRY(hipMemset(v.d_occ[l], 0, n * sizeof(uint64_t)));
             keep.push_back(v.d_occ[l]);
         }
     } else {
-        GB_TRY(mem.alloc(&v.d_masks, v.bricks())); GB_TRY(mem.alloc(&v.d_flag, v.bricks() + 1)); GB_TRY(mem.alloc(&v.d_slot, v.bricks() + 1));
-        GB_TRY(hipMemset(v.d_masks, 0, v.bricks() * sizeof(uint64_t))); GB_TRY(hipMemset(v.d_flag, 0, (v.bricks() + 1) * sizeof(uint32_t)));
+        BLOK_GPU_TRY(mem.alloc(&v.d_masks, v.bricks())); BLOK_GPU_TRY(mem.alloc(&v.d_flag, v.bricks() + 1)); BLOK_GPU_TRY(mem.alloc(&v.d_slot, v.bricks() + 1));
+        BLOK_GPU_TRY(hipMemset(v.d_masks, 0, v.bricks() * sizeof(uint64_t))); BLOK_GPU_TRY(hipMemset(v.d_flag, 0, (v.bricks() + 1) * sizeof(uint32_t)));
         keep.insert(keep.end(), {static_cast<void*>(v.d_masks), static_cast<void*>(v.d_flag), static_cast<void*>(v.d_slot)});
     }
-    GB_TRY(hipDeviceSynchronize());
+    BLOK_GPU_TRY(hipDeviceSynchronize());
     for (void* p : keep) mem.release(p);
     *out = v;
     return GpuBuildStatus::Ok;
@@ -894,17 +865,17 @@ void gpu_volume_destroy(GpuVolume* v) {
 }
 
 GpuBuildStatus gpu_volume_upload(GpuVolume* v, const float* density, const uint32_t* ids, std::string* why) {
-    if (density) GB_TRY(hipMemcpy(v->d_density, density, v->cells() * sizeof(float), hipMemcpyHostToDevice));
-    else GB_TRY(hipMemset(v->d_density, 0, v->cells() * sizeof(float)));
-    if (ids) GB_TRY(hipMemcpy(v->d_ids, ids, v->cells() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    else GB_TRY(hipMemset(v->d_ids, 0, v->cells() * sizeof(uint32_t)));
+    if (density) BLOK_GPU_TRY(hipMemcpy(v->d_density, density, v->cells() * sizeof(float), hipMemcpyHostToDevice));
+    else BLOK_GPU_TRY(hipMemset(v->d_density, 0, v->cells() * sizeof(float)));
+    if (ids) BLOK_GPU_TRY(hipMemcpy(v->d_ids, ids, v->cells() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    else BLOK_GPU_TRY(hipMemset(v->d_ids, 0, v->cells() * sizeof(uint32_t)));
     const uint32_t lo[3] = {0, 0, 0}, hi[3] = {v->nx, v->ny, v->nz};
     return volume_refresh(v, lo, hi, why);
 }
 
 GpuBuildStatus gpu_volume_download(const GpuVolume* v, float* density, uint32_t* ids, std::string* why) {
-    if (density) GB_TRY(hipMemcpy(density, v->d_density, v->cells() * sizeof(float), hipMemcpyDeviceToHost));
-    if (ids) GB_TRY(hipMemcpy(ids, v->d_ids, v->cells() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (density) BLOK_GPU_TRY(hipMemcpy(density, v->d_density, v->cells() * sizeof(float), hipMemcpyDeviceToHost));
+    if (ids) BLOK_GPU_TRY(hipMemcpy(ids, v->d_ids, v->cells() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return GpuBuildStatus::Ok;
 }
 
@@ -933,15 +904,15 @@ GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uin
     std::stable_sort(edits.begin(), edits.end(), [](const VoxelEdit& a, const VoxelEdit& b) { return a.index < b.index; });
     size_t m = 0;
     for (size_t i = 0; i < n; ++i) { if (i + 1 < n && edits[i + 1].index == edits[i].index) continue; edits[m++] = edits[i]; }
-    DeviceBuffers mem;
+    DeviceMem mem;
     VoxelEdit* d_edits;
-    GB_TRY(mem.alloc(&d_edits, m));
-    GB_TRY(hipMemcpy(d_edits, edits.data(), m * sizeof(VoxelEdit), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(mem.alloc(&d_edits, m));
+    BLOK_GPU_TRY(hipMemcpy(d_edits, edits.data(), m * sizeof(VoxelEdit), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(volume_set_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, v->d_density, v->d_ids, d_edits, static_cast<uint32_t>(m));
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     v->edit_may_add = true;                               // (a written density may be positive)
     const GpuBuildStatus st = volume_refresh(v, lo, hi, why);
-    GB_TRY(hipDeviceSynchronize());
+    BLOK_GPU_TRY(hipDeviceSynchronize());
     return st;
 }
 
@@ -969,7 +940,7 @@ GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radiu
     const uint64_t total = static_cast<uint64_t>(b.ex) * b.ey * b.ez;
     if (!total) return GpuBuildStatus::Ok;
     hipLaunchKernelGGL(volume_brush_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, b);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     return volume_refresh(v, lo, hi, why);
 }
 
@@ -1065,21 +1036,21 @@ GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const u
     *out_n_voxels = 0;
     if (v->cells() > 0xFFFFFFFFull) { *why = "capture_model: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
     if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
-    DeviceBuffers mem;
+    DeviceMem mem;
     // 1. the tight box of the region's filled voxels
     RegionCtx r{};
     r.density = v->d_density; r.nx = v->nx; r.ny = v->ny;
     for (int a = 0; a < 3; ++a) { r.lo[a] = lo[a]; r.ext[a] = hi[a] - lo[a]; }
     uint32_t* d_bounds;
-    GB_TRY(mem.alloc(&d_bounds, kBoundSlots * kBoundWords));
+    BLOK_GPU_TRY(mem.alloc(&d_bounds, kBoundSlots * kBoundWords));
     std::vector<uint32_t> bounds(kBoundSlots * kBoundWords, 0u);
     for (uint32_t s = 0; s < kBoundSlots; ++s) for (int a = 0; a < 3; ++a) bounds[s * kBoundWords + a] = 0xFFFFFFFFu;
-    GB_TRY(hipMemcpy(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(hipMemcpy(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     const uint32_t segs = (r.ext[0] + 63u) / 64u;
     const uint64_t n_rows = static_cast<uint64_t>(segs) * r.ext[1] * r.ext[2];
     hipLaunchKernelGGL(region_bounds_kernel<kLabelled>, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r, pred, n_rows, segs, d_bounds);
-    GB_TRY(hipGetLastError());
-    GB_TRY(hipMemcpy(bounds.data(), d_bounds, bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipMemcpy(bounds.data(), d_bounds, bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     uint32_t t0[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, t1[3] = {0u, 0u, 0u};
     uint64_t count = 0;
     for (uint32_t s = 0; s < kBoundSlots; ++s) {
@@ -1109,11 +1080,11 @@ GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const u
     d.ox = lo[0] + origin[0]; d.oy = lo[1] + origin[1]; d.oz = lo[2] + origin[2];
     const uint64_t total = static_cast<uint64_t>(d.bx) * d.by * d.bz;
     uint64_t* d_masks; uint32_t *d_flag, *d_slot;
-    GB_TRY(mem.alloc(&d_masks, total)); GB_TRY(mem.alloc(&d_flag, total + 1)); GB_TRY(mem.alloc(&d_slot, total + 1));
-    GB_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
+    BLOK_GPU_TRY(mem.alloc(&d_masks, total)); BLOK_GPU_TRY(mem.alloc(&d_flag, total + 1)); BLOK_GPU_TRY(mem.alloc(&d_slot, total + 1));
+    BLOK_GPU_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
     hipLaunchKernelGGL(region_brick_kernel<kLabelled>, dim3(d.bx, d.by, d.bz), dim3(64), 0, nullptr, d, pred, t0[0] - origin[0], t0[1] - origin[1], t0[2] - origin[2],
                        t1[0] - origin[0] + 1u, t1[1] - origin[1] + 1u, t1[2] - origin[2] + 1u, d_masks, d_flag);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     const GpuBuildStatus st = finish_from_masks(mem, total, d_masks, d_flag, d_slot, levels, origin,
         [&](const uint32_t* slot, uint64_t* keys, uint32_t* src) {
             hipLaunchKernelGGL(dense_key_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, d_masks, slot, total, keys, src);
@@ -1133,9 +1104,9 @@ GpuBuildStatus clear_region(GpuVolume* v, const LabelPred& pred, const uint32_t 
     const uint32_t ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
     const uint64_t total = static_cast<uint64_t>(ex) * ey * ez;
     hipLaunchKernelGGL(clear_filled_kernel<kLabelled>, dim3(blocks_for(total)), dim3(256), 0, nullptr, v->d_density, v->d_ids, pred, v->nx, v->ny, lo[0], lo[1], lo[2], ex, ey, total);
-    GB_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     const GpuBuildStatus st = volume_refresh(v, lo, hi, why);      // (clearing never fills: edit_may_add stays as it was)
-    GB_TRY(hipDeviceSynchronize());                                // blocking, as gpu_volume_set_voxels is
+    BLOK_GPU_TRY(hipDeviceSynchronize());                                // blocking, as gpu_volume_set_voxels is
     return st;
 }
 
@@ -1165,7 +1136,7 @@ GpuBuildStatus gpu_volume_build(GpuVolume* v, GpuTree* out, std::string* why) {
     if (v->keyed) return keyed_build(v, out, why);
     const DenseCtx d = volume_ctx(*v);
     const uint64_t total = v->bricks();
-    DeviceBuffers mem;
+    DeviceMem mem;
     return finish_from_masks(mem, total, v->d_masks, v->d_flag, v->d_slot, v->levels, v->origin,
         [&](const uint32_t* slot, uint64_t* keys, uint32_t* src) {
             hipLaunchKernelGGL(dense_key_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, v->d_masks, slot, total, keys, src);

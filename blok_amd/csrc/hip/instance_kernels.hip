@@ -1,33 +1,11 @@
 // gfx950 kernels of the instanced primary frame and rays (instance_core.h has the semantics and the per-ray math).  They run after the
 // world pass on its stream and compose its records with the instances' in place.
 #include "instance_core.h"
+#include "volume_device.h"      // uniform_record, uniform_word
 
 namespace blok {
 
 namespace {
-
-// A record of a wave-uniform index through the scalar cache (s_load): the instance table and the model store are read-only while the
-// kernels run, and the compiler cannot know that next to the kernels' stores (trace_core.h: walk_enter_wave does the same for nodes).
-template <class T>
-__device__ __forceinline__ T uniform_record(const T* base, uint32_t index) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef uint32_t Words __attribute__((ext_vector_type(sizeof(T) / 4)));
-    const Words w = reinterpret_cast<const __attribute__((address_space(4))) Words*>(reinterpret_cast<uintptr_t>(base))[__builtin_amdgcn_readfirstlane(index)];
-    T out;
-    __builtin_memcpy(&out, &w, sizeof(T));
-    return out;
-#else
-    return base[index];
-#endif
-}
-
-__device__ __forceinline__ uint32_t uniform_word(const uint32_t* base, uint32_t index) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(reinterpret_cast<uintptr_t>(base))[__builtin_amdgcn_readfirstlane(index)];
-#else
-    return base[index];
-#endif
-}
 
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));

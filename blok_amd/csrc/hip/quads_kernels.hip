@@ -22,7 +22,9 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include "../common/quads_core.h"
+#include "../common/sweep_core.h"      // brick_bit
 
 namespace blok {
 
@@ -39,9 +41,8 @@ struct FaceDims {
 };
 
 struct QuadArgs {
-    const uint64_t* masks; const uint32_t* ids;
-    uint32_t nx, ny, nz, nbx, nby;
-    uint32_t key_digits;                // keyed brick layout: digits of a brick's key (levels - 1); 0 = row-major
+    BrickMasks bricks; const uint32_t* ids;
+    uint32_t nx, ny, nz;
     int32_t origin[3];
     uint32_t lo[3], hi[3];              // region, box-local, half-open
     uint32_t ignore_material;
@@ -53,47 +54,21 @@ struct QuadArgs {
     blok_quad* out;
 };
 
-#define QK_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
-
-struct DeviceMem {                      // frees what it still owns on scope exit
-    std::vector<void*> ptrs;
-    ~DeviceMem() { for (void* p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, uint64_t count) {
-        void* raw = nullptr;
-        const hipError_t e = hipMalloc(&raw, std::max<uint64_t>(count, 1u) * sizeof(T));
-        if (e != hipSuccess) { (void)hipGetLastError(); return e; }
-        ptrs.push_back(raw); *p = static_cast<T*>(raw);
-        return hipSuccess;
-    }
-    void release(void* p) { for (void*& q : ptrs) if (q == p) q = nullptr; }
-};
-
-// The mask word of brick (bx, by, bz), in either layout of GpuVolume::d_masks (the keyed index is gpu_build.hip's cell_key: 2-bit digit
-// triples x | y << 2 | z << 4, least significant level first).
-__device__ __forceinline__ uint64_t brick_mask(const QuadArgs& a, uint32_t bx, uint32_t by, uint32_t bz) {
-    if (a.key_digits == 0u) return a.masks[bx + (static_cast<size_t>(bz) * a.nby + by) * a.nbx];
-    uint64_t key = 0;
-    for (uint32_t j = 0; j < a.key_digits; ++j)
-        key |= static_cast<uint64_t>(((bx >> (2u * j)) & 3u) | (((by >> (2u * j)) & 3u) << 2) | (((bz >> (2u * j)) & 3u) << 4)) << (6u * j);
-    return a.masks[key];
-}
-
 // Face kFace of the voxel (x, y, z), box-local; `inside`: the voxel lies in the region (otherwise nothing is read).
 template <uint32_t kFace>
 __device__ __forceinline__ Q::Cell face_cell(const QuadArgs& a, uint32_t x, uint32_t y, uint32_t z, bool inside) {
     Q::Cell none; none.exposed = 0u; none.key = 0u;
     if (!inside) return none;
-    const uint64_t m = brick_mask(a, x >> 2, y >> 2, z >> 2);
-    if (!((m >> ((x & 3u) | ((y & 3u) << 2) | ((z & 3u) << 4))) & 1ull)) return none;
+    const uint64_t m = a.bricks.at(x >> 2, y >> 2, z >> 2);
+    if (!((m >> sweep::brick_bit(x & 3u, y & 3u, z & 3u)) & 1ull)) return none;
     constexpr int A = static_cast<int>(kFace >> 1);
     constexpr uint32_t step = (kFace & 1u) ? 0xFFFFFFFFu : 1u;      // (-1 wraps: a coordinate below 0 fails the box test as one above does)
     const uint32_t qx = x + (A == 0 ? step : 0u), qy = y + (A == 1 ? step : 0u), qz = z + (A == 2 ? step : 0u);
     bool neighbour = false;
     if (qx < a.nx && qy < a.ny && qz < a.nz) {
         const bool same_brick = (qx >> 2) == (x >> 2) && (qy >> 2) == (y >> 2) && (qz >> 2) == (z >> 2);
-        const uint64_t mq = same_brick ? m : brick_mask(a, qx >> 2, qy >> 2, qz >> 2);
-        neighbour = (mq >> ((qx & 3u) | ((qy & 3u) << 2) | ((qz & 3u) << 4))) & 1ull;
+        const uint64_t mq = same_brick ? m : a.bricks.at(qx >> 2, qy >> 2, qz >> 2);
+        neighbour = (mq >> sweep::brick_bit(qx & 3u, qy & 3u, qz & 3u)) & 1ull;
     }
     if (neighbour) return none;
     const uint32_t material = a.ignore_material ? 0u : a.ids[(static_cast<size_t>(z) * a.ny + y) * a.nx + x];
@@ -229,9 +204,8 @@ GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3]
     if (v->cells() > 0xFFFFFFFFull) { *why = "extract_quads: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
     if (lo[0] >= hi[0] || lo[1] >= hi[1] || lo[2] >= hi[2]) return GpuBuildStatus::Ok;
     QuadArgs a{};
-    a.masks = v->d_masks; a.ids = v->d_ids;
-    a.nx = v->nx; a.ny = v->ny; a.nz = v->nz; a.nbx = v->nbx; a.nby = v->nby;
-    a.key_digits = v->keyed ? v->levels - 1u : 0u;
+    a.bricks = brick_masks_of(*v); a.ids = v->d_ids;
+    a.nx = v->nx; a.ny = v->ny; a.nz = v->nz;
     a.ignore_material = (flags & BLOK_QUADS_IGNORE_MATERIAL) ? 1u : 0u;
     const uint32_t ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
     for (int c = 0; c < 3; ++c) { a.origin[c] = v->origin[c]; a.lo[c] = lo[c]; a.hi[c] = hi[c]; }
@@ -249,34 +223,34 @@ GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3]
     a.row_base[6] = static_cast<uint32_t>(rows);
     DeviceMem mem;
     uint64_t* d_words;
-    QK_TRY(mem.alloc(&d_words, 3u * words));
+    BLOK_GPU_TRY(mem.alloc(&d_words, 3u * words));
     a.S = d_words; a.T = d_words + words; a.D = d_words + 2u * words;
-    QK_TRY(mem.alloc(&a.counts, rows + 1u));
-    QK_TRY(mem.alloc(&a.n_faces, kSpread));
-    QK_TRY(hipMemsetAsync(d_words, 0, 3u * words * sizeof(uint64_t), nullptr));
-    QK_TRY(hipMemsetAsync(a.counts + rows, 0, sizeof(unsigned long long), nullptr));
-    QK_TRY(hipMemsetAsync(a.n_faces, 0, kSpread * sizeof(unsigned long long), nullptr));
+    BLOK_GPU_TRY(mem.alloc(&a.counts, rows + 1u));
+    BLOK_GPU_TRY(mem.alloc(&a.n_faces, kSpread));
+    BLOK_GPU_TRY(hipMemsetAsync(d_words, 0, 3u * words * sizeof(uint64_t), nullptr));
+    BLOK_GPU_TRY(hipMemsetAsync(a.counts + rows, 0, sizeof(unsigned long long), nullptr));
+    BLOK_GPU_TRY(hipMemsetAsync(a.n_faces, 0, kSpread * sizeof(unsigned long long), nullptr));
     launch_face<0>(a); launch_face<1>(a); launch_face<2>(a); launch_face<3>(a); launch_face<4>(a); launch_face<5>(a);
-    QK_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     const dim3 row_grid(static_cast<uint32_t>((rows + 255u) / 256u));
     hipLaunchKernelGGL((quad_row_kernel<false>), row_grid, dim3(256), 0, nullptr, a);
-    QK_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipGetLastError());
     size_t temp_bytes = 0;
-    QK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, a.counts, a.counts, static_cast<int>(rows + 1u)));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, a.counts, a.counts, static_cast<int>(rows + 1u)));
     uint8_t* d_temp;
-    QK_TRY(mem.alloc(&d_temp, temp_bytes));
-    QK_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, a.counts, a.counts, static_cast<int>(rows + 1u)));
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, a.counts, a.counts, static_cast<int>(rows + 1u)));
     unsigned long long total = 0;
     std::vector<unsigned long long> faces(kSpread);
-    QK_TRY(hipMemcpy(&total, a.counts + rows, sizeof(total), hipMemcpyDeviceToHost));
-    QK_TRY(hipMemcpy(faces.data(), a.n_faces, kSpread * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&total, a.counts + rows, sizeof(total), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(faces.data(), a.n_faces, kSpread * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     uint64_t n_faces = 0;
     for (const unsigned long long n : faces) n_faces += n;
     if (!(flags & BLOK_QUADS_COUNT_ONLY) && total) {
-        QK_TRY(mem.alloc(&a.out, total));
+        BLOK_GPU_TRY(mem.alloc(&a.out, total));
         hipLaunchKernelGGL((quad_row_kernel<true>), row_grid, dim3(256), 0, nullptr, a);
-        QK_TRY(hipGetLastError());
-        QK_TRY(hipDeviceSynchronize());
+        BLOK_GPU_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipDeviceSynchronize());
         mem.release(a.out);
         *out_quads = a.out;
     }

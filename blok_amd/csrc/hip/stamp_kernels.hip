@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include "../common/stamp_core.h"
 
 namespace blok {
@@ -36,33 +37,18 @@ struct StampArgs {
     unsigned long long* counts;     // kCountSlots * kSlotWords
 };
 
-// A node of a wave-uniform index through the scalar cache: the model's arrays are read-only while the kernel runs, which the compiler
-// cannot know next to the kernel's stores (instance_kernels.hip: uniform_record).
-__device__ __forceinline__ uint4 uniform_node(const uint4* base, uint32_t index) {
-    typedef uint32_t Words __attribute__((ext_vector_type(4)));
-    const Words w = reinterpret_cast<const __attribute__((address_space(4))) Words*>(reinterpret_cast<uintptr_t>(base))[__builtin_amdgcn_readfirstlane(index)];
-    return make_uint4(w.x, w.y, w.z, w.w);
-}
-
 __global__ __launch_bounds__(256) void stamp_kernel(const StampArgs a) {
     const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const uint32_t ix = blockIdx.x * 4u + wave_in_block;
     if (ix >= a.nb[0]) return;
     const uint32_t bx = a.b0[0] + ix, by = a.b0[1] + blockIdx.y, bz = a.b0[2] + blockIdx.z;
-    // root to brick: digit l - 1 of the voxel coordinate is digit l - 2 of the brick coordinate
-    uint4 node = uniform_node(a.nodes, 0u);
-    for (uint32_t l = a.levels; l >= 2u; --l) {
-        const uint32_t s = 2u * (l - 2u);
-        const uint32_t bit = ((bx >> s) & 3u) | (((by >> s) & 3u) << 2) | (((bz >> s) & 3u) << 4);
-        const uint64_t mask = static_cast<uint64_t>(node.x) | (static_cast<uint64_t>(node.y) << 32);
-        if (!((mask >> bit) & 1ull)) return;                      // an empty cell of the model: nothing below it
-        node = uniform_node(a.nodes, node.z + static_cast<uint32_t>(__popcll(mask & ((1ull << bit) - 1ull))));
-    }
-    const uint64_t mask = static_cast<uint64_t>(node.x) | (static_cast<uint64_t>(node.y) << 32);
+    uint4 node;
+    if (!model_brick(a.nodes, a.levels, bx, by, bz, node)) return;      // an empty cell of the model: nothing below it
+    const uint64_t mask = node_mask(node);
     bool wrote = false;
     if ((mask >> lane) & 1ull) {
-        const int64_t v[3] = {int64_t(a.origin[0]) + int64_t(bx * 4u + (lane & 3u)), int64_t(a.origin[1]) + int64_t(by * 4u + ((lane >> 2) & 3u)),
-                              int64_t(a.origin[2]) + int64_t(bz * 4u + (lane >> 4))};
+        int64_t v[3];
+        brick_lane_voxel(a.origin, bx, by, bz, lane, v);
         // box-local world coordinates of the three LOCAL axes, and the cell's index through the strides of their world axes
         bool inside = true;
         uint64_t cell = 0;
@@ -88,9 +74,6 @@ __global__ __launch_bounds__(256) void stamp_kernel(const StampArgs a) {
     }
 }
 
-#define ST_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); if (d_counts) (void)hipFree(d_counts); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
-
 }  // namespace
 
 GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements, int mode,
@@ -98,9 +81,10 @@ GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const bl
     if (out_n_voxels) *out_n_voxels = 0;
     if (v->cells() > 0xFFFFFFFFull) { *why = "stamp_models: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
     if (n_placements == 0) return GpuBuildStatus::Ok;
-    unsigned long long* d_counts = nullptr;
-    ST_TRY(hipMalloc(reinterpret_cast<void**>(&d_counts), kCountSlots * kSlotWords * sizeof(unsigned long long)));
-    ST_TRY(hipMemsetAsync(d_counts, 0, kCountSlots * kSlotWords * sizeof(unsigned long long), nullptr));
+    DeviceMem mem;
+    unsigned long long* d_counts;
+    BLOK_GPU_TRY(mem.alloc(&d_counts, kCountSlots * kSlotWords));
+    BLOK_GPU_TRY(hipMemsetAsync(d_counts, 0, kCountSlots * kSlotWords * sizeof(unsigned long long), nullptr));
     const int64_t dims[3] = {v->nx, v->ny, v->nz};
     for (uint32_t i = 0; i < n_placements; ++i) {
         const blok_instance& I = placements[i];
@@ -122,25 +106,20 @@ GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const bl
         if (empty) continue;                                      // wholly outside: nothing written, not an error
         StampArgs a{};
         a.nodes = M.nodes; a.materials = M.materials; a.levels = M.levels;
-        for (int k = 0; k < 3; ++k) {
-            a.origin[k] = M.origin[k];
-            a.b0[k] = static_cast<uint32_t>((clo[k] - M.origin[k]) >> 2);
-            a.nb[k] = static_cast<uint32_t>((chi[k] - 1 - M.origin[k]) >> 2) - a.b0[k] + 1u;
-            a.box_origin[k] = v->origin[k];
-        }
+        placed_brick_range(M, clo, chi, a.b0, a.nb);
+        for (int k = 0; k < 3; ++k) { a.origin[k] = M.origin[k]; a.box_origin[k] = v->origin[k]; }
         a.place = I;
         a.nx = v->nx; a.ny = v->ny; a.nz = v->nz;
         a.density = v->d_density; a.ids = v->d_ids; a.mode = mode; a.value = density; a.counts = d_counts;
         hipLaunchKernelGGL(stamp_kernel, dim3((a.nb[0] + 3u) / 4u, a.nb[1], a.nb[2]), dim3(256), 0, nullptr, a);
-        ST_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
         if (mode != BLOK_STAMP_ERASE) v->edit_may_add = true;    // what the shadow rays' map has to know (gpu_build.h)
         // this placement's box alone: two far-apart stamps must not refresh what lies between them
         const GpuBuildStatus st = gpu_volume_refresh(v, wlo, whi, why);
-        if (st != GpuBuildStatus::Ok) { (void)hipFree(d_counts); return st; }
+        if (st != GpuBuildStatus::Ok) return st;
     }
     std::vector<unsigned long long> counts(kCountSlots * kSlotWords);
-    ST_TRY(hipMemcpy(counts.data(), d_counts, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));      // the call's one wait: behind every launch above
-    (void)hipFree(d_counts);
+    BLOK_GPU_TRY(hipMemcpy(counts.data(), d_counts, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));      // the call's one wait: behind every launch above
     uint64_t written = 0;
     for (uint32_t s = 0; s < kCountSlots; ++s) written += counts[s * kSlotWords];
     if (out_n_voxels) *out_n_voxels = written;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include "../common/sweep_core.h"
 
 namespace blok {
@@ -44,44 +45,11 @@ struct SweepArgs {
     blok_sweep_result* results;     // travel starts at max_distance, n_overlap at 0
     uint32_t n_places;
     uint64_t wave_base, n_waves;    // this launch's first wave of the table's n_waves
-    const uint64_t* masks;
-    uint32_t nbx, nby, key_digits;  // key_digits: keyed brick layout, digits of a brick's key (levels - 1); 0 = row-major
+    BrickMasks bricks;
     int32_t box_origin[3];
     uint32_t n[3];
     uint32_t direction, max_distance, flags;
 };
-
-typedef uint32_t Words4 __attribute__((ext_vector_type(4)));
-typedef uint32_t Words2 __attribute__((ext_vector_type(2)));
-
-// Wave-uniform reads through the scalar cache: the model's arrays, the placement records and the prefix are read-only while the kernel
-// runs, which the compiler cannot know next to the kernel's atomics (stamp_kernels.hip: uniform_node).
-__device__ __forceinline__ uint4 uniform_node(const uint4* base, uint32_t index) {
-    const Words4 w = reinterpret_cast<const __attribute__((address_space(4))) Words4*>(reinterpret_cast<uintptr_t>(base))[__builtin_amdgcn_readfirstlane(index)];
-    return make_uint4(w.x, w.y, w.z, w.w);
-}
-__device__ __forceinline__ uint64_t uniform_u64(const uint64_t* base, uint32_t index) {
-    const Words2 w = reinterpret_cast<const __attribute__((address_space(4))) Words2*>(reinterpret_cast<uintptr_t>(base))[__builtin_amdgcn_readfirstlane(index)];
-    return static_cast<uint64_t>(w.x) | (static_cast<uint64_t>(w.y) << 32);
-}
-__device__ __forceinline__ SweepPlace uniform_place(const SweepPlace* base, uint32_t index) {
-    const auto* q = reinterpret_cast<const __attribute__((address_space(4))) Words4*>(reinterpret_cast<uintptr_t>(base + __builtin_amdgcn_readfirstlane(index)));
-    Words4 w[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) w[i] = q[i];
-    SweepPlace p;
-    __builtin_memcpy(&p, w, sizeof(p));
-    return p;
-}
-
-// The mask word of the volume's brick (bx, by, bz) in either layout of GpuVolume::d_masks (components_kernels.hip: brick_mask).
-__device__ __forceinline__ uint64_t brick_mask(const SweepArgs& a, uint32_t bx, uint32_t by, uint32_t bz) {
-    if (a.key_digits == 0u) return a.masks[bx + (static_cast<size_t>(bz) * a.nby + by) * a.nbx];
-    uint64_t key = 0;
-    for (uint32_t j = 0; j < a.key_digits; ++j)
-        key |= static_cast<uint64_t>(((bx >> (2u * j)) & 3u) | (((by >> (2u * j)) & 3u) << 2) | (((bz >> (2u * j)) & 3u) << 4)) << (6u * j);
-    return a.masks[key];
-}
 
 __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
     const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -93,21 +61,14 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
         const uint32_t mid = first + (last - first) / 2u;
         if (uniform_u64(a.prefix, mid) <= t) first = mid; else last = mid;
     }
-    const SweepPlace P = uniform_place(a.places, first);
+    const SweepPlace P = uniform_record(a.places, first);
     const uint64_t r = t - uniform_u64(a.prefix, first);
     const uint64_t row = r / P.nb[0];
     const uint32_t bx = P.b0[0] + static_cast<uint32_t>(r - row * P.nb[0]);
     const uint32_t by = P.b0[1] + static_cast<uint32_t>(row % P.nb[1]), bz = P.b0[2] + static_cast<uint32_t>(row / P.nb[1]);
-    // root to brick: digit l - 1 of the voxel coordinate is digit l - 2 of the brick coordinate
-    uint4 node = uniform_node(P.nodes, 0u);
-    for (uint32_t l = P.levels; l >= 2u; --l) {
-        const uint32_t s = 2u * (l - 2u);
-        const uint32_t bit = ((bx >> s) & 3u) | (((by >> s) & 3u) << 2) | (((bz >> s) & 3u) << 4);
-        const uint64_t mask = static_cast<uint64_t>(node.x) | (static_cast<uint64_t>(node.y) << 32);
-        if (!((mask >> bit) & 1ull)) return;                      // an empty cell of the model: nothing below it
-        node = uniform_node(P.nodes, node.z + static_cast<uint32_t>(__popcll(mask & ((1ull << bit) - 1ull))));
-    }
-    const uint64_t mask = static_cast<uint64_t>(node.x) | (static_cast<uint64_t>(node.y) << 32);
+    uint4 node;
+    if (!model_brick(P.nodes, P.levels, bx, by, bz, node)) return;      // an empty cell of the model: nothing below it
+    const uint64_t mask = node_mask(node);
     blok_sweep_result* const result = a.results + first;
     const uint32_t axis = W::direction_axis(a.direction);
     const int sign = W::direction_sign(a.direction);
@@ -115,8 +76,8 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
     bool overlap = false;
     uint32_t travel = a.max_distance;
     if ((mask >> lane) & 1ull) {
-        const int64_t v[3] = {int64_t(P.origin[0]) + int64_t(bx * 4u + (lane & 3u)), int64_t(P.origin[1]) + int64_t(by * 4u + ((lane >> 2) & 3u)),
-                              int64_t(P.origin[2]) + int64_t(bz * 4u + (lane >> 4))};
+        int64_t v[3];
+        brick_lane_voxel(P.origin, bx, by, bz, lane, v);
         // box-local world coordinates, gathered by world axis with selects (the permutation is data: stamp::pick)
         int64_t wx = 0, wy = 0, wz = 0;
 #pragma unroll
@@ -128,7 +89,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
         const bool in_x = wx >= 0 && wx < int64_t(a.n[0]), in_y = wy >= 0 && wy < int64_t(a.n[1]), in_z = wz >= 0 && wz < int64_t(a.n[2]);
         const bool in_column = (axis == 0u || in_x) && (axis == 1u || in_y) && (axis == 2u || in_z);      // inside in the two perpendicular axes
         const uint32_t ux = static_cast<uint32_t>(wx), uy = static_cast<uint32_t>(wy), uz = static_cast<uint32_t>(wz);      // used only where inside
-        if (in_x && in_y && in_z) overlap = (brick_mask(a, ux >> 2, uy >> 2, uz >> 2) >> W::brick_bit(ux & 3u, uy & 3u, uz & 3u)) & 1ull;
+        if (in_x && in_y && in_z) overlap = (a.bricks.at(ux >> 2, uy >> 2, uz >> 2) >> W::brick_bit(ux & 3u, uy & 3u, uz & 3u)) & 1ull;
         else overlap = solid;
         // the neighbours along the direction inside the model's own brick
         const uint32_t lk = W::local_axis(P.place, axis);
@@ -145,7 +106,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
                 travel = W::free_travel(p, n, sign, a.max_distance, solid,
                     [&](int64_t b) {
                         const uint32_t ub = static_cast<uint32_t>(b);
-                        const uint64_t m = brick_mask(a, axis == 0u ? ub : ux >> 2, axis == 1u ? ub : uy >> 2, axis == 2u ? ub : uz >> 2);
+                        const uint64_t m = a.bricks.at(axis == 0u ? ub : ux >> 2, axis == 1u ? ub : uy >> 2, axis == 2u ? ub : uz >> 2);
                         return W::column4(m, axis, ux & 3u, uy & 3u, uz & 3u);
                     },
                     // the placement's best so far, from the device's point of coherence; a stale value only costs work, never changes the minimum
@@ -201,13 +162,11 @@ GpuBuildStatus gpu_volume_sweep(const GpuVolume* v, const StampModel* models, co
         }
         SweepPlace& p = places[i];
         p.nodes = M.nodes; p.levels = M.levels; p.place = I;
-        uint64_t bricks = empty ? 0u : 1u;
-        for (int k = 0; k < 3; ++k) {
-            p.origin[k] = M.origin[k];
-            if (empty) { p.b0[k] = 0u; p.nb[k] = 1u; continue; }
-            p.b0[k] = static_cast<uint32_t>((clo[k] - M.origin[k]) >> 2);
-            p.nb[k] = static_cast<uint32_t>((chi[k] - 1 - M.origin[k]) >> 2) - p.b0[k] + 1u;
-            bricks *= p.nb[k];
+        for (int k = 0; k < 3; ++k) { p.origin[k] = M.origin[k]; p.b0[k] = 0u; p.nb[k] = 1u; }      // (empty: no brick, and a range that still divides)
+        uint64_t bricks = 0u;
+        if (!empty) {
+            placed_brick_range(M, clo, chi, p.b0, p.nb);
+            bricks = uint64_t(p.nb[0]) * p.nb[1] * p.nb[2];
         }
         prefix[i] = n_waves;
         n_waves += bricks;
@@ -215,17 +174,16 @@ GpuBuildStatus gpu_volume_sweep(const GpuVolume* v, const StampModel* models, co
     }
     prefix[n_placements] = n_waves;
     if (n_waves != 0u) {
-        unsigned char* d_block = nullptr;
-#define SW_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); if (d_block) (void)hipFree(d_block); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
-        SW_TRY(hipMalloc(reinterpret_cast<void**>(&d_block), block.size()));
-        SW_TRY(hipMemcpyAsync(d_block, block.data(), block.size(), hipMemcpyHostToDevice, nullptr));
+        DeviceMem mem;
+        unsigned char* d_block;
+        BLOK_GPU_TRY(mem.alloc(&d_block, block.size()));
+        BLOK_GPU_TRY(hipMemcpyAsync(d_block, block.data(), block.size(), hipMemcpyHostToDevice, nullptr));
         SweepArgs a{};
         a.places = reinterpret_cast<const SweepPlace*>(d_block);
         a.results = reinterpret_cast<blok_sweep_result*>(d_block + places_bytes);
         a.prefix = reinterpret_cast<const uint64_t*>(d_block + places_bytes + results_bytes);
         a.n_places = n_placements; a.n_waves = n_waves;
-        a.masks = v->d_masks; a.nbx = v->nbx; a.nby = v->nby; a.key_digits = v->keyed ? v->levels - 1u : 0u;
+        a.bricks = brick_masks_of(*v);
         a.n[0] = v->nx; a.n[1] = v->ny; a.n[2] = v->nz;
         for (int k = 0; k < 3; ++k) a.box_origin[k] = v->origin[k];
         a.direction = direction; a.max_distance = max_distance; a.flags = flags;
@@ -235,11 +193,9 @@ GpuBuildStatus gpu_volume_sweep(const GpuVolume* v, const StampModel* models, co
             a.wave_base = base;
             const uint64_t waves = std::min<uint64_t>(waves_per_launch, n_waves - base);
             hipLaunchKernelGGL(sweep_kernel, dim3(static_cast<uint32_t>((waves + 3u) / 4u)), dim3(256), 0, nullptr, a);
-            SW_TRY(hipGetLastError());
+            BLOK_GPU_TRY(hipGetLastError());
         }
-        SW_TRY(hipMemcpy(results, a.results, results_bytes, hipMemcpyDeviceToHost));      // the call's one wait: behind every launch above
-        (void)hipFree(d_block);
-#undef SW_TRY
+        BLOK_GPU_TRY(hipMemcpy(results, a.results, results_bytes, hipMemcpyDeviceToHost));      // the call's one wait: behind every launch above
     }
     for (uint32_t i = 0; i < n_placements; ++i) {
         results[i].blocked = results[i].travel < max_distance ? 1u : 0u;

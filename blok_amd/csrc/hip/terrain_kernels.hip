@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include "../common/terrain_core.h"
 
 namespace blok {
@@ -41,9 +42,6 @@ struct TerrainArgs {
     uint32_t n_items;                   // columns of the region: (hi[0] - lo[0]) * (hi[2] - lo[2])
     uint32_t* words;                    // [kSpread][kWords]
 };
-
-#define TG_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
 
 template <bool kShell, bool kCaves>
 __global__ __launch_bounds__(256) void terrain_kernel(const TerrainArgs a) {
@@ -153,17 +151,17 @@ GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_para
     a.n_items = static_cast<uint32_t>(items);                    // (below 2^32: the volume has fewer cells than that)
     std::vector<uint32_t> words(kSpread * kWords, 0u);
     for (uint32_t k = 0; k < kSpread; ++k) for (int c = 0; c < 3; ++c) words[k * kWords + 2 + c] = 0xFFFFFFFFu;
-    TG_TRY(hipMalloc(reinterpret_cast<void**>(&a.words), words.size() * sizeof(uint32_t)));
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } free_words{a.words};
-    TG_TRY(hipMemcpy(a.words, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DeviceMem mem;
+    BLOK_GPU_TRY(mem.alloc(&a.words, words.size()));
+    BLOK_GPU_TRY(hipMemcpy(a.words, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     const dim3 grid(static_cast<uint32_t>((items + 255u) / 256u), (hi[1] - lo[1] + kRows - 1u) / kRows);
     const bool shell = params.flags & BLOK_TERRAIN_SHELL, caves = params.cave_octaves != 0u;
     if (shell && caves) hipLaunchKernelGGL((terrain_kernel<true, true>), grid, dim3(256), 0, nullptr, a);
     else if (shell) hipLaunchKernelGGL((terrain_kernel<true, false>), grid, dim3(256), 0, nullptr, a);
     else if (caves) hipLaunchKernelGGL((terrain_kernel<false, true>), grid, dim3(256), 0, nullptr, a);
     else hipLaunchKernelGGL((terrain_kernel<false, false>), grid, dim3(256), 0, nullptr, a);
-    TG_TRY(hipGetLastError());
-    TG_TRY(hipMemcpy(words.data(), a.words, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipMemcpy(words.data(), a.words, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     uint64_t written = 0;
     uint32_t flo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, fhi[3] = {0, 0, 0};
     for (uint32_t k = 0; k < kSpread; ++k) {
@@ -176,7 +174,7 @@ GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_para
     GpuBuildStatus st = GpuBuildStatus::Ok;
     if (!(params.flags & BLOK_TERRAIN_ADD)) st = gpu_volume_refresh(v, lo, hi, why);
     else if (written) st = gpu_volume_refresh(v, flo, fhi, why);
-    TG_TRY(hipDeviceSynchronize());
+    BLOK_GPU_TRY(hipDeviceSynchronize());
     return st;
 }
 

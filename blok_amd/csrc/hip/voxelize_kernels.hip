@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "gpu_build.h"
+#include "device_mem.h"
 #include "voxelize_core.h"
 
 namespace blok {
@@ -358,20 +359,7 @@ __global__ __launch_bounds__(256) void vox_interior_kernel(const ColumnArgs a, i
     reduce_written(wr, on, x, y, z);
 }
 
-struct Buffers {                // frees everything on scope exit
-    std::vector<void*> ptrs;
-    ~Buffers() { for (void* p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t count) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
-#define VX_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *why = std::string(#call) + ": " + hipGetErrorString(e_); \
-                          return e_ == hipErrorOutOfMemory ? GpuBuildStatus::OutOfMemory : GpuBuildStatus::HipError; } } while (0)
-
-hipError_t inclusive_scan(Buffers& mem, const uint64_t* in, uint64_t* out, uint32_t n) {
+hipError_t inclusive_scan(DeviceMem& mem, const uint64_t* in, uint64_t* out, uint32_t n) {
     size_t bytes = 0;
     hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, bytes, in, out, static_cast<int>(n));
     if (e != hipSuccess) return e;
@@ -393,22 +381,22 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
     if (n_triangles > 0x7FFFFFFFull) { *why = "voxelize: more than 2^31 triangles"; return GpuBuildStatus::Unsupported; }
     if (n_triangles == 0) return GpuBuildStatus::Ok;
     const uint32_t nt = static_cast<uint32_t>(n_triangles);
-    Buffers mem;
+    DeviceMem mem;
     float* d_pos; uint32_t *d_tris, *d_mats = nullptr, *d_error; TriRec* d_rec; uint64_t *d_pairs, *d_cols, *d_pair_scan, *d_col_scan; int32_t* d_mesh_box;
-    VX_TRY(mem.alloc(&d_pos, 3 * n_vertices)); VX_TRY(mem.alloc(&d_tris, 3 * n_triangles)); VX_TRY(mem.alloc(&d_rec, n_triangles));
-    VX_TRY(mem.alloc(&d_pairs, n_triangles)); VX_TRY(mem.alloc(&d_cols, n_triangles)); VX_TRY(mem.alloc(&d_pair_scan, n_triangles)); VX_TRY(mem.alloc(&d_col_scan, n_triangles));
-    VX_TRY(mem.alloc(&d_error, 1)); VX_TRY(mem.alloc(&d_mesh_box, 8 * kSpread));
-    if (n_vertices) VX_TRY(hipMemcpy(d_pos, positions, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice));
-    VX_TRY(hipMemcpy(d_tris, triangles, 3 * n_triangles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(mem.alloc(&d_pos, 3 * n_vertices)); BLOK_GPU_TRY(mem.alloc(&d_tris, 3 * n_triangles)); BLOK_GPU_TRY(mem.alloc(&d_rec, n_triangles));
+    BLOK_GPU_TRY(mem.alloc(&d_pairs, n_triangles)); BLOK_GPU_TRY(mem.alloc(&d_cols, n_triangles)); BLOK_GPU_TRY(mem.alloc(&d_pair_scan, n_triangles)); BLOK_GPU_TRY(mem.alloc(&d_col_scan, n_triangles));
+    BLOK_GPU_TRY(mem.alloc(&d_error, 1)); BLOK_GPU_TRY(mem.alloc(&d_mesh_box, 8 * kSpread));
+    if (n_vertices) BLOK_GPU_TRY(hipMemcpy(d_pos, positions, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice));
+    BLOK_GPU_TRY(hipMemcpy(d_tris, triangles, 3 * n_triangles * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (triangle_materials) {
-        VX_TRY(mem.alloc(&d_mats, n_triangles));
-        VX_TRY(hipMemcpy(d_mats, triangle_materials, n_triangles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        BLOK_GPU_TRY(mem.alloc(&d_mats, n_triangles));
+        BLOK_GPU_TRY(hipMemcpy(d_mats, triangle_materials, n_triangles * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     {
         std::vector<int32_t> init(8 * kSpread);
         for (uint32_t s = 0; s < kSpread; ++s) for (int c = 0; c < 3; ++c) { init[8 * s + c] = INT32_MAX; init[8 * s + 3 + c] = INT32_MIN; }
-        VX_TRY(hipMemcpy(d_mesh_box, init.data(), init.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        VX_TRY(hipMemset(d_error, 0, sizeof(uint32_t)));
+        BLOK_GPU_TRY(hipMemcpy(d_mesh_box, init.data(), init.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        BLOK_GPU_TRY(hipMemset(d_error, 0, sizeof(uint32_t)));
     }
     SetupArgs s{};
     s.pos = d_pos; s.n_vertices = n_vertices; s.tris = d_tris; s.n_tris = nt;
@@ -416,15 +404,15 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
     for (int c = 0; c < 3; ++c) { s.O[c] = int64_t(v->origin[c]) * vox::kSub; s.n[c] = dims[c]; s.origin[c] = v->origin[c]; }
     s.solid = solid; s.rec = d_rec; s.pair_count = d_pairs; s.col_count = d_cols; s.error = d_error; s.mesh_box = d_mesh_box;
     hipLaunchKernelGGL(vox_setup_kernel, dim3(blocks(nt, 256)), dim3(256), 0, nullptr, s);
-    VX_TRY(hipGetLastError());
-    VX_TRY(inclusive_scan(mem, d_pairs, d_pair_scan, nt));
-    if (solid) VX_TRY(inclusive_scan(mem, d_cols, d_col_scan, nt));
+    BLOK_GPU_TRY(hipGetLastError());
+    BLOK_GPU_TRY(inclusive_scan(mem, d_pairs, d_pair_scan, nt));
+    if (solid) BLOK_GPU_TRY(inclusive_scan(mem, d_cols, d_col_scan, nt));
     uint32_t error = 0; uint64_t n_pairs = 0, n_cols = 0;
     std::vector<int32_t> mb(8 * kSpread);
-    VX_TRY(hipMemcpy(&error, d_error, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    VX_TRY(hipMemcpy(&n_pairs, d_pair_scan + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (solid) VX_TRY(hipMemcpy(&n_cols, d_col_scan + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    VX_TRY(hipMemcpy(mb.data(), d_mesh_box, mb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&error, d_error, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&n_pairs, d_pair_scan + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (solid) BLOK_GPU_TRY(hipMemcpy(&n_cols, d_col_scan + nt - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(mb.data(), d_mesh_box, mb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (error) {
         *invalid = true;
         *why = (error & kErrIndex) ? "voxelize: vertex index out of range" : (error & kErrCoord) ? "voxelize: vertex coordinate not finite or beyond 2^23"
@@ -449,15 +437,15 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
     }
     uint64_t* d_smask; uint32_t *d_list, *d_n_list, *d_box; unsigned long long* d_count;
     const uint64_t list_cap = std::max<uint64_t>(std::min(n_pairs, reg_bricks), 1);
-    VX_TRY(mem.alloc(&d_smask, reg_bricks)); VX_TRY(mem.alloc(&d_list, list_cap)); VX_TRY(mem.alloc(&d_n_list, 1));
-    VX_TRY(mem.alloc(&d_box, 8 * kSpread)); VX_TRY(mem.alloc(&d_count, kSpread));
-    VX_TRY(hipMemset(d_smask, 0, std::max<uint64_t>(reg_bricks, 1) * sizeof(uint64_t)));
-    VX_TRY(hipMemset(d_n_list, 0, sizeof(uint32_t)));
-    VX_TRY(hipMemset(d_count, 0, kSpread * sizeof(unsigned long long)));
+    BLOK_GPU_TRY(mem.alloc(&d_smask, reg_bricks)); BLOK_GPU_TRY(mem.alloc(&d_list, list_cap)); BLOK_GPU_TRY(mem.alloc(&d_n_list, 1));
+    BLOK_GPU_TRY(mem.alloc(&d_box, 8 * kSpread)); BLOK_GPU_TRY(mem.alloc(&d_count, kSpread));
+    BLOK_GPU_TRY(hipMemset(d_smask, 0, std::max<uint64_t>(reg_bricks, 1) * sizeof(uint64_t)));
+    BLOK_GPU_TRY(hipMemset(d_n_list, 0, sizeof(uint32_t)));
+    BLOK_GPU_TRY(hipMemset(d_count, 0, kSpread * sizeof(unsigned long long)));
     {
         std::vector<uint32_t> init(8 * kSpread);
         for (uint32_t k = 0; k < kSpread; ++k) for (int c = 0; c < 3; ++c) { init[8 * k + c] = 0xFFFFFFFFu; init[8 * k + 3 + c] = 0u; }
-        VX_TRY(hipMemcpy(d_box, init.data(), init.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        BLOK_GPU_TRY(hipMemcpy(d_box, init.data(), init.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     const Written wr{d_box, d_count};
     PairArgs pa{};
@@ -467,10 +455,10 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
     for (uint64_t f = 0; f < n_pairs; f += kPairBatch) {
         const uint64_t e = std::min(n_pairs, f + kPairBatch);
         hipLaunchKernelGGL(vox_pair_kernel, dim3(blocks(e - f, 4)), dim3(256), 0, nullptr, pa, f, e);
-        VX_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
     }
     uint32_t n_list = 0;
-    VX_TRY(hipMemcpy(&n_list, d_n_list, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(&n_list, d_n_list, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (std::getenv("BLOK_VOXELIZE_STATS"))         // diagnostic (scripts/voxelize_timing.py): the work lists' sizes
         std::fprintf(stderr, "[voxelize] triangles %u pairs %llu pair_launches %llu touched_bricks %u columns %llu\n", nt, static_cast<unsigned long long>(n_pairs),
                      static_cast<unsigned long long>((n_pairs + kPairBatch - 1) / kPairBatch), n_list, static_cast<unsigned long long>(n_cols));
@@ -481,38 +469,38 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
         ca.ry = static_cast<uint32_t>(m1[1] - m0[1]);
         ca.words = static_cast<uint32_t>((dims[0] - m0[0] + 31) / 32);
         const uint64_t rows = uint64_t(ca.ry) * uint64_t(m1[2] - m0[2]);
-        VX_TRY(mem.alloc(&ca.bits, rows * ca.words));
-        VX_TRY(hipMemset(ca.bits, 0, rows * ca.words * sizeof(uint32_t)));
+        BLOK_GPU_TRY(mem.alloc(&ca.bits, rows * ca.words));
+        BLOK_GPU_TRY(hipMemset(ca.bits, 0, rows * ca.words * sizeof(uint32_t)));
         for (uint64_t f = 0; f < n_cols; f += kColumnBatch) {
             const uint64_t e = std::min(n_cols, f + kColumnBatch);
             hipLaunchKernelGGL(vox_column_kernel, dim3(blocks(e - f, 256)), dim3(256), 0, nullptr, ca, f, e);
-            VX_TRY(hipGetLastError());
+            BLOK_GPU_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(vox_prefix_kernel, dim3(blocks(rows, 256)), dim3(256), 0, nullptr, ca.bits, rows, ca.words);
-        VX_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
         hipLaunchKernelGGL(vox_interior_kernel, dim3(blocks(rows * uint64_t(dims[0] - m0[0]), 256)), dim3(256), 0, nullptr, ca, dims[1], rows, reg, d_smask,
                            v->d_density, v->d_ids, material, density, wr);
-        VX_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
     }
     if (n_list) {
         if (d_mats) {
             hipLaunchKernelGGL(vox_clear_ids_kernel, dim3(blocks(n_list, 4)), dim3(256), 0, nullptr, reg, d_smask, d_list, n_list, dims[0], dims[1], v->d_ids);
-            VX_TRY(hipGetLastError());
+            BLOK_GPU_TRY(hipGetLastError());
             pa.phase = 1;
             for (uint64_t f = 0; f < n_pairs; f += kPairBatch) {
                 const uint64_t e = std::min(n_pairs, f + kPairBatch);
                 hipLaunchKernelGGL(vox_pair_kernel, dim3(blocks(e - f, 4)), dim3(256), 0, nullptr, pa, f, e);
-                VX_TRY(hipGetLastError());
+                BLOK_GPU_TRY(hipGetLastError());
             }
         }
         hipLaunchKernelGGL(vox_finalize_kernel, dim3(blocks(n_list, 4)), dim3(256), 0, nullptr, reg, d_smask, d_list, n_list, dims[0], dims[1],
                            v->d_density, v->d_ids, d_mats, material, density, wr);
-        VX_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipGetLastError());
     }
     std::vector<uint32_t> box(8 * kSpread);
     std::vector<unsigned long long> counts(kSpread);
-    VX_TRY(hipMemcpy(box.data(), d_box, box.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    VX_TRY(hipMemcpy(counts.data(), d_count, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(box.data(), d_box, box.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BLOK_GPU_TRY(hipMemcpy(counts.data(), d_count, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0};
     uint64_t written = 0;
     for (uint32_t k = 0; k < kSpread; ++k) {
@@ -523,7 +511,7 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
     if (!written) return GpuBuildStatus::Ok;
     v->edit_may_add = true;
     const GpuBuildStatus st = gpu_volume_refresh(v, lo, hi, why);
-    VX_TRY(hipDeviceSynchronize());
+    BLOK_GPU_TRY(hipDeviceSynchronize());
     return st;
 }
 

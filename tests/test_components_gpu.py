@@ -79,6 +79,25 @@ def test_every_case_gives_the_reference_snapshot(keyed):
 
 
 @LAYOUTS
+def test_regions_off_the_brick_grid_of_a_24_13_9_volume(keyed):
+    """6 x 4 x 3 bricks, ragged last bricks in y and z, three tree levels: a keyed brick's index is far from its row-major one.  No corner
+    of the regions is a multiple of 4."""
+    origin, shape = (-7, 3, -2), (24, 13, 9)
+    rng = np.random.default_rng(31)
+    d = np.where(rng.random(shape[::-1]) < 0.3, rng.uniform(0.1, 2.0, shape[::-1]), 0.0).astype(np.float32)
+    d[::3, ::2, ::5] = -0.5
+    m = np.where(d > 0, 7, 0).astype(np.uint32)
+    t = _tracer()
+    volume(t, keyed, d, m, origin, shape)
+    _, records = labelled_equals(t, d, None, None, "whole", origin=origin)
+    assert len(records) > 5
+    for lo, hi in (((1, 1, 1), (22, 11, 7)), ((5, 2, 3), (19, 10, 6)), ((17, 1, 5), (23, 13, 9)), ((2, 6, 1), (3, 7, 2))):      # box-local
+        assert all(c % 4 for c in lo + hi)
+        labelled_equals(t, d, tuple(o + c for o, c in zip(origin, lo)), tuple(o + c for o, c in zip(origin, hi)), (lo, hi), origin=origin)
+    t.shutdown()
+
+
+@LAYOUTS
 def test_a_snapshot_outlives_edits_until_the_next_labelling(keyed):
     """A pillar on a slab, severed by a SUBTRACT brush: the tables match the reference on the model's arrays both times, and the first
     snapshot downloads unchanged after the edit."""

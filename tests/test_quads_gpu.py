@@ -67,6 +67,28 @@ def test_whole_box_and_ragged_regions_over_prior_content(keyed):
     t.shutdown()
 
 
+@pytest.mark.parametrize("keyed", [True, False], ids=["keyed", "general"])
+def test_regions_off_the_brick_grid_of_a_24_13_9_volume(keyed):
+    """6 x 4 x 3 bricks, ragged last bricks in y and z, three tree levels: a keyed brick's index is far from its row-major one.  No corner
+    of the regions is a multiple of 4."""
+    t = _tracer()
+    t.set_volume_layout(keyed)
+    origin, shape = (-7, 3, -2), (24, 13, 9)
+    t.volume_create(origin, shape)
+    rng = np.random.default_rng(29)
+    d0 = np.where(rng.random(shape[::-1]) < 0.45, rng.uniform(0.1, 2.0, shape[::-1]), 0.0).astype(np.float32)
+    d0[::3, ::2, ::5] = -0.5
+    m0 = np.where(d0 > 0, rng.integers(5, 8, shape[::-1]), 0).astype(np.uint32)
+    t.volume_upload(d0, m0)
+    vol = t.volume_download()
+    for ignore in (False, True):
+        _check(t, origin, ignore=ignore, volume=vol)
+        for lo, hi in (((1, 1, 1), (22, 11, 7)), ((5, 2, 3), (19, 10, 6)), ((17, 1, 5), (23, 13, 9)), ((2, 6, 1), (3, 7, 2))):      # box-local
+            assert all(c % 4 for c in lo + hi)
+            _check(t, origin, tuple(o + c for o, c in zip(origin, lo)), tuple(o + c for o, c in zip(origin, hi)), ignore, vol)
+    t.shutdown()
+
+
 def test_terrain_with_caves_in_256_cubed():
     t = _tracer()
     origin, shape = (-128, -100, -128), (256, 256, 256)
