@@ -55,9 +55,15 @@ COMPONENT_CUT = 1                                 # = BLOK_COMPONENT_CUT
 # = blok_sweep_result: one placement swept against the volume, 16 bytes
 SWEEP_RESULT = np.dtype([("n_overlap", "<u8"), ("travel", "<u4"), ("blocked", "<u4")])
 SWEEP_BOX_IS_SOLID = 1                            # = BLOK_SWEEP_BOX_IS_SOLID
+# = blok_brick_record: one stored brick of a sparse brick stream, 24 bytes; = blok_bricks_info: what a stream holds, 64 bytes
+BRICK_RECORD = np.dtype([("mask", "<u8"), ("brick", "<u4"), ("kind", "<u4"), ("density", "<u4"), ("material", "<u4")])
+BRICKS_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("n_bricks", "<u8"), ("n_density", "<u8"),
+                        ("n_material", "<u8"), ("n_voxels", "<u8")])
+BRICKS_FILLED_ONLY = 1                            # = BLOK_BRICKS_FILLED_ONLY (encode)
+BRICKS_KEEP_OTHERS = 1                            # = BLOK_BRICKS_KEEP_OTHERS (restore / decode)
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
-assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16
+assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD.itemsize == 24 and BRICKS_INFO.itemsize == 64
 
 
 class GBuffer(C.Structure):
@@ -183,6 +189,13 @@ HOST_SYMBOLS = {
                                         C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "blok_sweep_voxels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_bricks_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "blok_bricks_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_bricks_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_char_p, C.c_size_t]),
+    "blok_bricks_write_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_bricks_read_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -315,6 +328,12 @@ HIP_SYMBOLS = {
     "blok_hip_volume_capture_component": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
                                                     C.POINTER(C.c_uint64)]),
     "blok_hip_volume_sweep_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_encode_bricks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_bricks_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_volume_bricks_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_brick_payload_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_restore_bricks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]),
+    "blok_hip_volume_decode_bricks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

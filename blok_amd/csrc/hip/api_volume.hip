@@ -3,6 +3,8 @@
 #include "../common/terrain_core.h"
 #include "../common/stamp_core.h"
 #include "../common/sweep_core.h"
+#include "../common/bricks_core.h"
+#include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
 #include <limits>
@@ -28,6 +30,10 @@ void drop_quads(blok_hip_ctx* ctx) {
 void drop_components(blok_hip_ctx* ctx) {
     blok::gpu_components_free(&ctx->components);
     ctx->has_components = false;
+}
+void drop_bricks(blok_hip_ctx* ctx) {
+    blok::gpu_bricks_free(&ctx->bricks);
+    ctx->has_bricks = false;
 }
 int need_volume(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
@@ -76,6 +82,7 @@ int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t 
     if (ctx->has_volume) { if (ctx->tree_owned_by_volume) { BLOK_HIP_TRY(ctx, hipDeviceSynchronize()); free_world(ctx); } blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false; }
     drop_quads(ctx);
     drop_components(ctx);
+    drop_bricks(ctx);
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
     std::string why;
     const blok::GpuBuildStatus st = blok::gpu_volume_create(o, nx, ny, nz, chunk_size, voxel_size, &ctx->volume, &why, ctx->volume_keyed_layout);
@@ -106,6 +113,7 @@ int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
     }
     drop_quads(ctx);
     drop_components(ctx);
+    drop_bricks(ctx);
     return BLOK_OK;
 }
 
@@ -346,6 +354,124 @@ int blok_hip_volume_sweep_models(blok_hip_ctx* ctx, const blok_instance* placeme
     // (on the null stream, behind every edit enqueued so far; reads only, so no snapshot and no edit state is touched)
     return volume_status(ctx, blok::gpu_volume_sweep(&ctx->volume, models.data(), placements_host, n_placements, direction, max_distance, flags,
                                                      out_results_host, &why), why);
+}
+
+namespace {
+// The box-local corner of a stream's destination [dst_lo, dst_lo + ext) (dst_lo null: where the stream was taken).
+int bricks_destination(blok_hip_ctx* ctx, const char* op, const blok_bricks_info& info, const int32_t* dst_lo, uint32_t lo[3]) {
+    const blok::GpuVolume& v = ctx->volume;
+    const int64_t dims[3] = {v.nx, v.ny, v.nz};
+    for (int a = 0; a < 3; ++a) {
+        const int64_t l = int64_t(dst_lo ? dst_lo[a] : info.lo[a]) - v.origin[a];
+        if (l < 0 || l + int64_t(info.ext[a]) > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, std::string(op) + ": destination leaves the resident volume");
+        lo[a] = static_cast<uint32_t>(l);
+    }
+    return BLOK_OK;
+}
+}  // namespace
+
+int blok_hip_volume_encode_bricks(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags, blok_bricks_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags & ~blok::bricks::kEncodeFlags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "encode_bricks: unknown flag bits");
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "encode_bricks", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    blok::GpuBricks snapshot;
+    // (edits are enqueued on the null stream, and so is this: it reads what they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_encode_bricks(&ctx->volume, lo, hi, flags, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    drop_bricks(ctx);
+    ctx->bricks = snapshot; ctx->has_bricks = true;
+    if (out_info) *out_info = snapshot.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_bricks_info(blok_hip_ctx* ctx, blok_bricks_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_info: no snapshot (blok_hip_volume_encode_bricks)");
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_info: null output");
+    *out_info = ctx->bricks.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_bricks_download(blok_hip_ctx* ctx, blok_brick_record* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_download: no snapshot (blok_hip_volume_encode_bricks)");
+    const uint64_t n = ctx->bricks.info.n_bricks;
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->bricks.d_records + first, count * sizeof(blok_brick_record), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_brick_payload_download(blok_hip_ctx* ctx, uint32_t plane, uint32_t* out_u32_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: no snapshot (blok_hip_volume_encode_bricks)");
+    if (plane > 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: plane above 1");
+    const uint64_t n = plane == 0u ? ctx->bricks.info.n_density : ctx->bricks.info.n_material;
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_u32_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_u32_host, (plane == 0u ? ctx->bricks.d_density : ctx->bricks.d_material) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_restore_bricks(blok_hip_ctx* ctx, const int32_t dst_lo[3], uint32_t flags) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags & ~blok::bricks::kDecodeFlags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "restore_bricks: unknown flag bits");
+    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "restore_bricks: no snapshot (blok_hip_volume_encode_bricks)");
+    uint32_t lo[3];
+    rc = bricks_destination(ctx, "restore_bricks", ctx->bricks.info, dst_lo, lo);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    return volume_status(ctx, blok::gpu_volume_decode_bricks(&ctx->volume, &ctx->bricks, lo, flags, &why), why);
+}
+
+int blok_hip_volume_decode_bricks(blok_hip_ctx* ctx, const blok_bricks_info* info, const blok_brick_record* records, const uint32_t* density_payload,
+                                  const uint32_t* material_payload, const int32_t dst_lo[3], uint32_t flags) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (flags & ~blok::bricks::kDecodeFlags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "decode_bricks: unknown flag bits");
+    if (!info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "decode_bricks: null info");
+    // on the host, before anything is uploaded or written
+    uint64_t bad = 0;
+    if (const int rule = blok::bricks::validate(*info, records, density_payload, material_payload, &bad)) {
+        std::string msg = std::string("decode_bricks: ") + blok::bricks::rule_text(rule);
+        if (bad < info->n_bricks) msg += " (record " + std::to_string(bad) + ")";
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, msg);
+    }
+    uint32_t lo[3];
+    rc = bricks_destination(ctx, "decode_bricks", *info, dst_lo, lo);
+    if (rc != BLOK_OK) return rc;
+    std::string why_text;
+    std::string* why = &why_text;
+    blok::DeviceMem mem;
+    blok::GpuBricks stream;
+    stream.info = *info;
+    const auto upload = [&]() -> blok::GpuBuildStatus {
+        if (info->n_bricks) {
+            BLOK_GPU_TRY(mem.alloc(&stream.d_records, info->n_bricks));
+            BLOK_GPU_TRY(hipMemcpy(stream.d_records, records, info->n_bricks * sizeof(blok_brick_record), hipMemcpyHostToDevice));
+        }
+        if (info->n_density) {
+            BLOK_GPU_TRY(mem.alloc(&stream.d_density, info->n_density));
+            BLOK_GPU_TRY(hipMemcpy(stream.d_density, density_payload, info->n_density * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        if (info->n_material) {
+            BLOK_GPU_TRY(mem.alloc(&stream.d_material, info->n_material));
+            BLOK_GPU_TRY(hipMemcpy(stream.d_material, material_payload, info->n_material * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        return blok::GpuBuildStatus::Ok;
+    };
+    blok::GpuBuildStatus st = upload();
+    if (st == blok::GpuBuildStatus::Ok) st = blok::gpu_volume_decode_bricks(&ctx->volume, &stream, lo, flags, why);      // (blocking: the arrays outlive the kernels)
+    return volume_status(ctx, st, why_text);
 }
 
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {

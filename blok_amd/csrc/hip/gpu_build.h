@@ -165,6 +165,23 @@ GpuBuildStatus gpu_volume_clear_labelled(GpuVolume* v, const GpuComponents* c, u
 // for the whole table on the null stream, one download (the call's wait); out_results has n_placements records, host memory.
 GpuBuildStatus gpu_volume_sweep(const GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements,
                                 uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_results, std::string* why);
+// ---- the sparse brick stream (include/blok_hip.h: blok_hip_volume_encode_bricks; bricks_kernels.hip) ----
+// A stream in device memory, owned by the holder: records sorted by brick, the two payloads, and the info that counts them.
+struct GpuBricks {
+    blok_brick_record* d_records = nullptr;
+    uint32_t* d_density = nullptr;
+    uint32_t* d_material = nullptr;
+    blok_bricks_info info = {};
+};
+void gpu_bricks_free(GpuBricks* b);
+// Encodes the box-local region [lo, hi) (flags: BLOK_BRICKS_FILLED_ONLY or 0).  Reads the store (and, with FILLED_ONLY on a region whose
+// corner lies on the brick grid, the brick masks), changes nothing; *out is a new stream, the caller's to free (all pointers null when
+// nothing is stored).  Blocking.
+GpuBuildStatus gpu_volume_encode_bricks(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuBricks* out, std::string* why);
+// Writes a stream whose arrays lie in device memory into [dst_lo, dst_lo + info.ext) (box-local, inside the box; flags:
+// BLOK_BRICKS_KEEP_OTHERS or 0), then refreshes that box as every edit does.  The stream is one gpu_volume_encode_bricks made or one that
+// has passed bricks::validate: the kernel trusts its indices.  Blocking.
+GpuBuildStatus gpu_volume_decode_bricks(GpuVolume* v, const GpuBricks* stream, const uint32_t dst_lo[3], uint32_t flags, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

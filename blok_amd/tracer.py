@@ -219,6 +219,55 @@ class HipTracer:
                                                            int(max_distance), int(flags), _ffi.ptr(out) if len(out) else None))
         return out
 
+    def volume_encode_bricks(self, lo=None, hi=None, filled_only: bool = False) -> np.ndarray:
+        """Encodes a region of the resident volume (world voxels, half open; both None = the whole box) as a sparse brick stream kept on
+        the device (blok_hip.h: blok_hip_volume_encode_bricks) until the next encode.  Returns the stream's info, one _ffi.BRICKS_INFO
+        record; volume_bricks_download fetches the stream, volume_restore_bricks writes it back."""
+        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
+        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        info = np.zeros(1, dtype=_ffi.BRICKS_INFO)
+        self._check(self._lib.blok_hip_volume_encode_bricks(self._ctx, rlo, rhi, _ffi.BRICKS_FILLED_ONLY if filled_only else 0, _ffi.ptr(info)))
+        return info
+
+    def volume_bricks_info(self) -> np.ndarray:
+        info = np.zeros(1, dtype=_ffi.BRICKS_INFO)
+        self._check(self._lib.blok_hip_volume_bricks_info(self._ctx, _ffi.ptr(info)))
+        return info
+
+    def volume_bricks_download(self, page: int = 1 << 22):
+        """The last encode's stream as (info, records, density payload, material payload): _ffi.BRICKS_INFO, a structured array of
+        _ffi.BRICK_RECORD and two uint32 arrays (bit patterns and ids), fetched `page` entries at a time."""
+        info = self.volume_bricks_info()
+        records = np.zeros(int(info["n_bricks"][0]), dtype=_ffi.BRICK_RECORD)
+        for at in range(0, len(records), int(page)):
+            n = min(int(page), len(records) - at)
+            self._check(self._lib.blok_hip_volume_bricks_download(self._ctx, _ffi.ptr(records[at:at + n]), at, n))
+        payloads = []
+        for plane, key in ((0, "n_density"), (1, "n_material")):
+            out = np.zeros(int(info[key][0]), dtype=np.uint32)
+            for at in range(0, len(out), int(page)):
+                n = min(int(page), len(out) - at)
+                self._check(self._lib.blok_hip_volume_brick_payload_download(self._ctx, plane, _ffi.ptr(out[at:at + n]), at, n))
+            payloads.append(out)
+        return info, records, payloads[0], payloads[1]
+
+    def volume_restore_bricks(self, dst_lo=None, keep_others: bool = False):
+        """Writes the last encode's stream back into the volume at dst_lo (None = where it was taken): undo, or copy and paste.  By default
+        every cell of the destination is written; keep_others writes the stored cells only.  The next volume_rebuild installs the world."""
+        dlo = None if dst_lo is None else (C.c_int32 * 3)(*[int(c) for c in dst_lo])
+        self._check(self._lib.blok_hip_volume_restore_bricks(self._ctx, dlo, _ffi.BRICKS_KEEP_OTHERS if keep_others else 0))
+
+    def volume_decode_bricks(self, info, records, density_payload, material_payload, dst_lo=None, keep_others: bool = False):
+        """volume_restore_bricks from host arrays (a loaded file, the host build's stream); the stream is validated first."""
+        info = np.ascontiguousarray(info, dtype=_ffi.BRICKS_INFO).reshape(1)
+        records = np.ascontiguousarray(records, dtype=_ffi.BRICK_RECORD).reshape(-1)
+        dp = np.ascontiguousarray(density_payload, dtype=np.uint32).reshape(-1)
+        mp = np.ascontiguousarray(material_payload, dtype=np.uint32).reshape(-1)
+        dlo = None if dst_lo is None else (C.c_int32 * 3)(*[int(c) for c in dst_lo])
+        self._check(self._lib.blok_hip_volume_decode_bricks(self._ctx, _ffi.ptr(info), _ffi.ptr(records) if len(records) else None,
+                                                            _ffi.ptr(dp) if len(dp) else None, _ffi.ptr(mp) if len(mp) else None, dlo,
+                                                            _ffi.BRICKS_KEEP_OTHERS if keep_others else 0))
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

@@ -305,6 +305,34 @@ public:
                                            boxIsSolid ? BLOK_SWEEP_BOX_IS_SOLID : 0u, results.data()));
         return results;
     }
+    // A region of the resident volume (world voxels, half-open; both null = the whole box) as a sparse brick stream kept on the device
+    // until the next encode (blok_hip_volume_encode_bricks): returns what it holds.  downloadBricks fetches it `page` entries at a time,
+    // restoreBricks writes it back (undo, or a paste at dstLo), decodeBricks does the same from host arrays (a loaded .bvol file).
+    struct BrickStream {
+        blok_bricks_info info{};
+        std::vector<blok_brick_record> records;
+        std::vector<uint32_t> density, material;      // the payloads: density bit patterns, material ids
+    };
+    blok_bricks_info encodeBricks(const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr, bool filledOnly = false) {
+        blok_bricks_info info{};
+        check(blok_hip_volume_encode_bricks(m_ctx, regionLo, regionHi, filledOnly ? BLOK_BRICKS_FILLED_ONLY : 0u, &info));
+        return info;
+    }
+    BrickStream downloadBricks(uint64_t page = uint64_t(1) << 22) {
+        BrickStream s;
+        check(blok_hip_volume_bricks_info(m_ctx, &s.info));
+        s.records.resize(s.info.n_bricks); s.density.resize(s.info.n_density); s.material.resize(s.info.n_material);
+        for (uint64_t at = 0; at < s.info.n_bricks; at += page) check(blok_hip_volume_bricks_download(m_ctx, s.records.data() + at, at, std::min(page, s.info.n_bricks - at)));
+        for (uint64_t at = 0; at < s.info.n_density; at += page) check(blok_hip_volume_brick_payload_download(m_ctx, 0u, s.density.data() + at, at, std::min(page, s.info.n_density - at)));
+        for (uint64_t at = 0; at < s.info.n_material; at += page) check(blok_hip_volume_brick_payload_download(m_ctx, 1u, s.material.data() + at, at, std::min(page, s.info.n_material - at)));
+        return s;
+    }
+    void restoreBricks(const int32_t* dstLo = nullptr, bool keepOthers = false) {
+        check(blok_hip_volume_restore_bricks(m_ctx, dstLo, keepOthers ? BLOK_BRICKS_KEEP_OTHERS : 0u));
+    }
+    void decodeBricks(const BrickStream& s, const int32_t* dstLo = nullptr, bool keepOthers = false) {
+        check(blok_hip_volume_decode_bricks(m_ctx, &s.info, s.records.data(), s.density.data(), s.material.data(), dstLo, keepOthers ? BLOK_BRICKS_KEEP_OTHERS : 0u));
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -570,7 +570,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.5: procedural terrain into the resident volume.  1.6: the volume's surface as merged quads.
  * 1.7: models stamped into the resident volume, regions of it captured as models.
  * 1.8: connected components of the resident volume, one of them captured as a model.
- * 1.9: placed models swept against the resident volume (overlap, free travel along an axis). */
+ * 1.9: placed models swept against the resident volume (overlap, free travel along an axis).
+ * 1.10: the resident volume saved, restored and undone as a sparse brick stream. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -815,6 +816,73 @@ typedef struct blok_sweep_result {
 } blok_sweep_result;      /* 16 bytes */
 int blok_hip_volume_sweep_models(blok_hip_ctx* ctx, const blok_instance* placements_host, uint32_t n_placements,
                                  uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_results_host);
+
+/* ------------------------------------------------------------- the resident volume as a sparse brick stream (ABI 1.10)
+ * Save, load, undo and copy/paste without the dense download: a region of the volume becomes a stream of its non-empty 4^3 bricks, kept
+ * as a snapshot in HBM and downloadable in pieces, and a stream is written back from the snapshot or from host arrays.  A pure integer
+ * function of the two arrays: one right answer, bit-identical on the host (blok_bricks_encode / blok_bricks_decode, blok_world.h) and on
+ * the device.  All calls block.
+ *  - Region: world voxels, half open; both pointers NULL = the whole box (the convention of blok_hip_volume_extract_quads).  Its extents
+ *    are ext[3].
+ *  - Bricks are counted from the region's lo, not from the box: brick (bx, by, bz) holds the region cells 4b .. 4b+3 on each axis, cut by
+ *    the region; nb[a] = ceil(ext[a] / 4); its index is bx + nb[0] * (by + nb[1] * bz).  Bit b = x + 4y + 16z of a brick's mask is its cell
+ *    (x, y, z): the bit order of the volume's own brick masks.
+ *  - Stored cell.  Default: a cell is stored iff its density's 32-bit pattern is not 0 or its material id is not 0, so -0.0f, negative
+ *    and NaN densities are stored, and so are ids left behind under a SUBTRACT brush.  BLOK_BRICKS_FILLED_ONLY: a cell is stored iff
+ *    density > 0, the rebuild's rule.  A brick is stored iff it has a stored cell.
+ *  - Record: one blok_brick_record per stored brick, sorted by brick index ascending (indices are distinct, so the order is total).
+ *    kind bit 0: all stored cells of the brick have the same density bit pattern; then `density` is that pattern and the brick adds
+ *    nothing to the density payload.  Otherwise `density` is the index of the brick's first entry in the density payload, and the brick
+ *    adds popcount(mask) entries (bit patterns) in ascending bit order.  kind bit 1 and `material`: the same for ids, in the material
+ *    payload.  Payload indices are running sums in record order; they fit uint32_t because a volume has at most 2^32 cells and a stored
+ *    brick has at least one cell.  The totals are 64-bit.
+ *  - blok_hip_volume_encode_bricks has no effect on the volume or on the quads and components snapshots.  The stream stays in device
+ *    memory, owned by the context; later edits do not touch it.  The next encode replaces it; blok_hip_volume_destroy, a new
+ *    blok_hip_volume_create and blok_hip_destroy free it.  The result is the same in the keyed and the row-major brick layout.
+ *    out_info may be NULL.
+ *  - blok_hip_volume_bricks_download copies records [first, first + count); blok_hip_volume_brick_payload_download copies payload entries
+ *    [first, first + count), plane 0 the density payload, 1 the material payload.  blok_hip_volume_bricks_info returns the snapshot's info.
+ *  - blok_hip_volume_restore_bricks writes the HBM snapshot into [dst_lo, dst_lo + ext); dst_lo NULL = where it was taken.
+ *    blok_hip_volume_decode_bricks does the same from host arrays.  Default: every cell of the destination is written: stored cells get
+ *    their values, every other cell gets (+0.0f, 0).  BLOK_BRICKS_KEEP_OTHERS: only stored cells are written (a paste).  After a
+ *    default-mode encode, the default-mode restore to the same place reproduces both arrays bit for bit; after a FILLED_ONLY encode it
+ *    reproduces them where density > 0 and writes (0, 0) elsewhere.
+ *  - Afterwards masks, occupancy words, dirty flags and the edited box are those blok_hip_volume_set_voxels leaves for the same writes,
+ *    the write counts as one that may have filled voxels, and the next blok_hip_volume_rebuild installs the world.
+ *  - Validation of a host stream, on the host, before anything is uploaded or written: version 1; known flag bits; records strictly
+ *    ascending by brick; brick < nb[0] nb[1] nb[2]; mask != 0 with no bit outside the region (the last brick on an axis may be partial);
+ *    kind <= 3; a non-uniform plane's index equal to the running sum; the four totals equal to what the records imply.  The message names
+ *    the first record that fails.
+ *  - Errors, each leaving the volume and the previous snapshot as they were.  BLOK_ERR_INVALID_ARG: unknown flag bits, exactly one region
+ *    pointer NULL, lo > hi on an axis, no snapshot (restore, info and the downloads), a download range past the end, plane > 1, a null
+ *    array with a non-zero count, a host stream that fails validation.  BLOK_ERR_UNSUPPORTED: a region or destination that leaves the
+ *    box, a volume above 2^32 cells.  BLOK_ERR_NO_WORLD: no volume.  BLOK_ERR_OOM: a failed device allocation.  An empty region, or a
+ *    region with nothing stored, is BLOK_OK with zero counts and an empty snapshot; restoring an empty snapshot in default mode clears
+ *    the destination. */
+#define BLOK_BRICKS_FILLED_ONLY 1u   /* encode: store the cells with density > 0 only (default: every cell that is not (+0.0f, 0)) */
+#define BLOK_BRICKS_KEEP_OTHERS 1u   /* restore / decode: write stored cells only (default: every other cell of the destination gets (0, 0)) */
+typedef struct blok_brick_record {
+    uint64_t mask;         /* bit x + 4y + 16z: cell (x, y, z) of the brick is stored */
+    uint32_t brick;        /* bx + nb[0] * (by + nb[1] * bz), bricks counted from the region's lo */
+    uint32_t kind;         /* bit 0: one density pattern, bit 1: one material id */
+    uint32_t density;      /* the pattern, or the index of the brick's first density payload entry */
+    uint32_t material;     /* the id, or the index of the brick's first material payload entry */
+} blok_brick_record;       /* 24 bytes */
+typedef struct blok_bricks_info {
+    uint32_t version;      /* 1 */
+    uint32_t flags;        /* the encode's flags */
+    int32_t  lo[3];        /* the region, world voxels */
+    uint32_t ext[3];
+    uint64_t n_bricks, n_density, n_material, n_voxels;      /* records, payload entries, stored cells */
+} blok_bricks_info;        /* 64 bytes */
+int blok_hip_volume_encode_bricks(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
+                                  blok_bricks_info* out_info);
+int blok_hip_volume_bricks_info(blok_hip_ctx* ctx, blok_bricks_info* out_info);
+int blok_hip_volume_bricks_download(blok_hip_ctx* ctx, blok_brick_record* out_host, uint64_t first, uint64_t count);
+int blok_hip_volume_brick_payload_download(blok_hip_ctx* ctx, uint32_t plane, uint32_t* out_u32_host, uint64_t first, uint64_t count);
+int blok_hip_volume_restore_bricks(blok_hip_ctx* ctx, const int32_t dst_lo[3], uint32_t flags);
+int blok_hip_volume_decode_bricks(blok_hip_ctx* ctx, const blok_bricks_info* info, const blok_brick_record* records,
+                                  const uint32_t* density_payload, const uint32_t* material_payload, const int32_t dst_lo[3], uint32_t flags);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -217,6 +217,33 @@ int blok_components_label(const float* density, const int32_t origin[3], uint32_
 int blok_sweep_voxels(const float* density, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const int32_t* model_xyz, size_t n,
                       const blok_instance* placement, uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_result);
 
+/* -------------------------------------------------------------- the sparse brick stream on the host (bricks.cpp)
+ * The contracts of blok_hip_volume_encode_bricks and blok_hip_volume_decode_bricks (blok_hip.h; blok_brick_record, blok_bricks_info and the
+ * flags are declared there) over host arrays density[x + y*nx + z*nx*ny] / material_ids of a box whose voxel (0, 0, 0) sits at world
+ * `origin` (NULL = 0, 0, 0), through the rules the kernels use, brick by brick.
+ * encode is called twice: with records NULL it fills *out_info alone (the counts), then with arrays of at least those sizes (a payload
+ * array may be NULL when its count is 0).  The region is in world voxels, half open, both NULL = the whole box.  Errors as the device
+ * entry; an array too small for the stream is BLOK_ERR_INVALID_ARG.
+ * validate: the validation of a host stream; BLOK_ERR_INVALID_ARG with the rule and the first failing record in err.
+ * decode: validates, then writes the stream into [dst_lo, dst_lo + ext) (NULL = info->lo), flags BLOK_BRICKS_KEEP_OTHERS or 0.  Nothing is
+ * written on an error (codes as the device entry).
+ * A .bvol file is, in order and little-endian: the 8 bytes "BLOKBVL1", the info, the records, the density payload, the material payload.
+ * write_file validates first.  read_file checks every size against the file's length and fills *out_info; with all three arrays NULL
+ * it stops there (the caller then knows what to allocate), otherwise it reads the arrays and validates them. */
+int blok_bricks_encode(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                       const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags, blok_bricks_info* out_info,
+                       blok_brick_record* records, uint64_t record_capacity, uint32_t* density_payload, uint64_t density_capacity,
+                       uint32_t* material_payload, uint64_t material_capacity);
+int blok_bricks_validate(const blok_bricks_info* info, const blok_brick_record* records, const uint32_t* density_payload,
+                         const uint32_t* material_payload, char* err, size_t err_len);
+int blok_bricks_decode(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                       const blok_bricks_info* info, const blok_brick_record* records, const uint32_t* density_payload,
+                       const uint32_t* material_payload, const int32_t dst_lo[3], uint32_t flags, char* err, size_t err_len);
+int blok_bricks_write_file(const char* path, const blok_bricks_info* info, const blok_brick_record* records, const uint32_t* density_payload,
+                           const uint32_t* material_payload, char* err, size_t err_len);
+int blok_bricks_read_file(const char* path, blok_bricks_info* out_info, blok_brick_record* records, uint32_t* density_payload,
+                          uint32_t* material_payload, char* err, size_t err_len);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

@@ -1,7 +1,8 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol]
+//   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
 //   --terrain: procedural terrain generated on the device into a resident volume of --terrain-size^3 voxels (blok_hip_volume_generate_terrain),
@@ -15,6 +16,12 @@
 //          (blok_hip_volume_capture_component with CUT), swept down against what remains (blok_hip_volume_sweep_models, the box's walls
 //          and floor solid) and stamped where it comes to rest (blok_hip_volume_stamp_models); lowest pieces first, pass after pass until
 //          nothing floats (at most 8 passes).  The frames show the settled world
+//   --save-volume: with --terrain or --obj, after the volume is made and settled: the whole box encoded on the device as a sparse brick
+//          stream (blok_hip_volume_encode_bricks), downloaded and written as a .bvol file (blok_bricks_write_file)
+//   --load-volume: instead of generating or voxelizing: the file is read and validated (blok_bricks_read_file), a volume of the stream's
+//          box created, the stream decoded into it (blok_hip_volume_decode_bricks) and rebuilt with the terrain's four materials.  A file
+//          holds voxels, no view: with --terrain SEED --terrain-size N nothing is generated, but the camera stands where that terrain's
+//          run puts it, so the frames of a loaded world equal the frames of the run that saved it; without, it looks at the box as --obj's does
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -49,6 +56,7 @@ struct Options {
     std::string export_obj;               // write the resident volume's surface here
     bool components = false;              // label the resident volume's connected components and print their counts
     bool settle = false;                  // let the components that do not touch the floor fall
+    std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
     bool rccl = true;
@@ -66,11 +74,13 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
-                if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); break; }
-                if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); settle(); break; }
+                if (!m_opt.load_volume.empty()) { initLoaded(); exportObj(); components(); settle(); saveVolume(); break; }
+                if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); saveVolume(); break; }
+                if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); settle(); saveVolume(); break; }
                 if (!m_opt.export_obj.empty()) throw std::runtime_error("--export-obj needs a resident volume: --terrain or --obj");
                 if (m_opt.components) throw std::runtime_error("--components needs a resident volume: --terrain or --obj");
                 if (m_opt.settle) throw std::runtime_error("--settle needs a resident volume: --terrain or --obj");
+                if (!m_opt.save_volume.empty()) throw std::runtime_error("--save-volume needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -110,10 +120,8 @@ private:
                 throw std::runtime_error("this driver only carries the HIP backend");
         }
     }
-    // Terrain generated into an N^3 volume, an optional mesh voxelized on top of it, the camera on the ground near a corner.
-    void initTerrain() {
-        if (m_opt.devices.size() > 1) throw std::runtime_error("--terrain renders on one device");
-        const uint32_t N = m_opt.terrain_size;
+    // The terrain's parameters for an N^3 box with its four materials registered: grass, soil, rock and an emissive ore.
+    blok_terrain_params terrainParams(uint32_t N) {
         blok_terrain_params p{};
         if (blok_terrain_default_params(N, m_opt.terrain_seed, &p) != BLOK_OK) throw std::runtime_error("--terrain-size must be in 1..65536");
         const struct { const char* name; float rgb[3]; float emission; } table[4] = {
@@ -128,6 +136,22 @@ private:
             ids[k] = m_materials.addMaterial(m);
         }
         p.surface_material = ids[0]; p.soil_material = ids[1]; p.rock_material = ids[2]; p.ore_material = ids[3];
+        return p;
+    }
+    // The terrain's camera: a few voxels above the highest possible surface over a corner column, looking at a point a little above the ground at the box centre (sky in the upper part of the frame)
+    void terrainCamera(const blok_terrain_params& p, uint32_t N, int32_t ground) {
+        const float eye[3] = {0.12f * N, static_cast<float>(p.base_height + static_cast<int32_t>(p.amplitude)) + 0.08f * N, 0.10f * N};
+        float f[3] = {N / 2.0f - eye[0], static_cast<float>(ground) + 0.15f * N - eye[1], N / 2.0f - eye[2]};
+        const float len = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+        for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a]; }
+        m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
+        m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
+    }
+    // Terrain generated into an N^3 volume, an optional mesh voxelized on top of it, the camera on the ground near a corner.
+    void initTerrain() {
+        if (m_opt.devices.size() > 1) throw std::runtime_error("--terrain renders on one device");
+        const uint32_t N = m_opt.terrain_size;
+        const blok_terrain_params p = terrainParams(N);
         const int32_t origin[3] = {0, 0, 0};
         m_tracer->createVolume(origin, N, N, N);
         const uint64_t filled = m_tracer->generateTerrain(p);
@@ -162,13 +186,54 @@ private:
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
-        // the camera: a few voxels above the highest possible surface over a corner column, looking at a point a little above the ground at the box centre (sky in the upper part of the frame)
-        const float eye[3] = {0.12f * N, static_cast<float>(p.base_height + static_cast<int32_t>(p.amplitude)) + 0.08f * N, 0.10f * N};
-        float f[3] = {N / 2.0f - eye[0], static_cast<float>(ground) + 0.15f * N - eye[1], N / 2.0f - eye[2]};
+        terrainCamera(p, N, ground);
+    }
+    // A world read from a .bvol file in place of generating one: a volume of the stream's box, the stream decoded into it, rebuilt.
+    void initLoaded() {
+        if (m_opt.devices.size() > 1) throw std::runtime_error("--load-volume renders on one device");
+        if (!m_opt.obj.empty()) throw std::runtime_error("--load-volume takes the place of --obj");
+        char err[512] = {0};
+        blok::HipTracer::BrickStream s;
+        if (blok_bricks_read_file(m_opt.load_volume.c_str(), &s.info, nullptr, nullptr, nullptr, err, sizeof(err)) != BLOK_OK)
+            throw std::runtime_error(std::string("Failed to load volume: ") + err);
+        s.records.resize(s.info.n_bricks); s.density.resize(s.info.n_density); s.material.resize(s.info.n_material);
+        if (blok_bricks_read_file(m_opt.load_volume.c_str(), &s.info, s.records.data(), s.density.data(), s.material.data(), err, sizeof(err)) != BLOK_OK)
+            throw std::runtime_error(std::string("Failed to load volume: ") + err);
+        const uint32_t* ext = s.info.ext;
+        if (!ext[0] || !ext[1] || !ext[2]) throw std::runtime_error("Failed to load volume: the stream's box is empty");
+        const uint32_t N = m_opt.terrain ? m_opt.terrain_size : std::max(ext[0], std::max(ext[1], ext[2]));
+        const blok_terrain_params p = terrainParams(N);
+        m_tracer->createVolume(s.info.lo, ext[0], ext[1], ext[2]);
+        m_tracer->decodeBricks(s);
+        m_tracer->rebuildVolume(m_materials.packForGpu());
+        const blok_world_stats w = m_tracer->worldStats();
+        std::cout << "volume loaded: " << s.info.n_bricks << " bricks, " << s.info.n_voxels << " voxels; world: " << w.n_voxels << " voxels, " << w.n_tree_nodes
+                  << " tree nodes, " << w.levels << " levels\n";
+        if (m_opt.terrain) {
+            const int32_t centre[2] = {static_cast<int32_t>(N / 2), static_cast<int32_t>(N / 2)};
+            int32_t ground = 0;
+            blok_terrain_height(&p, centre, 1, &ground);
+            terrainCamera(p, N, ground);
+            return;
+        }
+        const float n = static_cast<float>(N);
+        const float eye[3] = {s.info.lo[0] - 0.35f * n, s.info.lo[1] + 1.15f * n, s.info.lo[2] - 0.45f * n};
+        float f[3] = {s.info.lo[0] + ext[0] / 2.0f - eye[0], s.info.lo[1] + ext[1] / 2.0f - eye[1], s.info.lo[2] + ext[2] / 2.0f - eye[2]};
         const float len = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
         for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a]; }
         m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
         m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
+    }
+    // The whole box as a sparse brick stream: encoded on the device, downloaded, written as a .bvol file.
+    void saveVolume() {
+        if (m_opt.save_volume.empty()) return;
+        m_tracer->encodeBricks();
+        const blok::HipTracer::BrickStream s = m_tracer->downloadBricks();
+        char err[512] = {0};
+        if (blok_bricks_write_file(m_opt.save_volume.c_str(), &s.info, s.records.data(), s.density.data(), s.material.data(), err, sizeof(err)) != BLOK_OK)
+            throw std::runtime_error(std::string("Failed to save volume: ") + err);
+        const uint64_t bytes = 8u + sizeof(blok_bricks_info) + s.records.size() * sizeof(blok_brick_record) + (s.density.size() + s.material.size()) * sizeof(uint32_t);
+        std::cout << "volume saved: " << s.info.n_bricks << " bricks, " << s.info.n_voxels << " voxels, " << bytes << " bytes\n";
     }
     // The mesh's bounding box fitted into obj_size voxels (half a voxel from the faces), voxelized into a volume of that box, rebuilt.
     void initObj() {
@@ -322,6 +387,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--export-obj")) opt.export_obj = next();
         else if (!std::strcmp(argv[i], "--components")) opt.components = true;
         else if (!std::strcmp(argv[i], "--settle")) opt.settle = true;
+        else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
+        else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
