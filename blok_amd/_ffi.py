@@ -61,9 +61,16 @@ BRICKS_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), 
                         ("n_material", "<u8"), ("n_voxels", "<u8")])
 BRICKS_FILLED_ONLY = 1                            # = BLOK_BRICKS_FILLED_ONLY (encode)
 BRICKS_KEEP_OTHERS = 1                            # = BLOK_BRICKS_KEEP_OTHERS (restore / decode)
+# = blok_distance_info: what a distance field snapshot holds, 64 bytes
+DISTANCE_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("max_radius", "<u4"), ("reserved", "<u4"),
+                          ("n_zero", "<u8"), ("n_near", "<u8"), ("n_far", "<u8")])
+DISTANCE_TO_EMPTY, DISTANCE_BOX_IS_SOLID = 1, 2   # = BLOK_DISTANCE_TO_EMPTY, BLOK_DISTANCE_BOX_IS_SOLID
+DISTANCE_FAR = 0xFFFF                             # = BLOK_DISTANCE_FAR
+DISTANCE_GROW, DISTANCE_SHRINK, DISTANCE_HOLLOW = 0, 1, 2      # = BLOK_DISTANCE_GROW / _SHRINK / _HOLLOW
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
 assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD.itemsize == 24 and BRICKS_INFO.itemsize == 64
+assert DISTANCE_INFO.itemsize == 64
 
 
 class GBuffer(C.Structure):
@@ -196,6 +203,10 @@ HOST_SYMBOLS = {
                                      C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_char_p, C.c_size_t]),
     "blok_bricks_write_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_bricks_read_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_distance_field": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_distance_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -334,6 +345,10 @@ HIP_SYMBOLS = {
     "blok_hip_volume_brick_payload_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_restore_bricks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]),
     "blok_hip_volume_decode_bricks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]),
+    "blok_hip_volume_distance_field": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_distance_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_volume_distance_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_edit_by_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -100,6 +100,7 @@ struct blok_hip_ctx {
     blok_quad* d_quads = nullptr; uint64_t n_quads = 0; bool has_quads = false;
     blok::GpuComponents components; bool has_components = false;      // the snapshot of the last blok_hip_volume_label_components
     blok::GpuBricks bricks; bool has_bricks = false;                  // the snapshot of the last blok_hip_volume_encode_bricks
+    blok::GpuDistance distance; bool has_distance = false;            // the snapshot of the last blok_hip_volume_distance_field
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
     float* d_sun_map = nullptr;

@@ -4,6 +4,7 @@
 #include "../common/stamp_core.h"
 #include "../common/sweep_core.h"
 #include "../common/bricks_core.h"
+#include "../common/distance_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -34,6 +35,10 @@ void drop_components(blok_hip_ctx* ctx) {
 void drop_bricks(blok_hip_ctx* ctx) {
     blok::gpu_bricks_free(&ctx->bricks);
     ctx->has_bricks = false;
+}
+void drop_distance(blok_hip_ctx* ctx) {
+    blok::gpu_distance_free(&ctx->distance);
+    ctx->has_distance = false;
 }
 int need_volume(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
@@ -83,6 +88,7 @@ int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t 
     drop_quads(ctx);
     drop_components(ctx);
     drop_bricks(ctx);
+    drop_distance(ctx);
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
     std::string why;
     const blok::GpuBuildStatus st = blok::gpu_volume_create(o, nx, ny, nz, chunk_size, voxel_size, &ctx->volume, &why, ctx->volume_keyed_layout);
@@ -114,6 +120,7 @@ int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
     drop_quads(ctx);
     drop_components(ctx);
     drop_bricks(ctx);
+    drop_distance(ctx);
     return BLOK_OK;
 }
 
@@ -472,6 +479,61 @@ int blok_hip_volume_decode_bricks(blok_hip_ctx* ctx, const blok_bricks_info* inf
     blok::GpuBuildStatus st = upload();
     if (st == blok::GpuBuildStatus::Ok) st = blok::gpu_volume_decode_bricks(&ctx->volume, &stream, lo, flags, why);      // (blocking: the arrays outlive the kernels)
     return volume_status(ctx, st, why_text);
+}
+
+int blok_hip_volume_distance_field(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t max_radius, uint32_t flags,
+                                   blok_distance_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (const int rule = blok::distance::check_field_args(max_radius, flags)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("distance_field: ") + blok::distance::rule_text(rule));
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "distance_field", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    blok::GpuDistance snapshot;
+    // (edits are enqueued on the null stream, and so is this: it reads the masks they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_distance_field(&ctx->volume, lo, hi, max_radius, flags, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    drop_distance(ctx);
+    ctx->distance = snapshot; ctx->has_distance = true;
+    if (out_info) *out_info = snapshot.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_distance_info(blok_hip_ctx* ctx, blok_distance_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_distance) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_info: no snapshot (blok_hip_volume_distance_field)");
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_info: null output");
+    *out_info = ctx->distance.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_distance_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_distance) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_download: no snapshot (blok_hip_volume_distance_field)");
+    const blok_distance_info& info = ctx->distance.info;
+    const uint64_t n = static_cast<uint64_t>(info.ext[0]) * info.ext[1] * info.ext[2];
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->distance.d_field + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_edit_by_distance(blok_hip_ctx* ctx, int op, uint32_t d2, float density, uint32_t material, uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (!ctx->has_distance) return set_error(ctx, BLOK_ERR_INVALID_ARG, "edit_by_distance: no snapshot (blok_hip_volume_distance_field)");
+    if (const int rule = blok::distance::check_edit_args(ctx->distance.info, op, d2, density))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("edit_by_distance: ") + blok::distance::rule_text(rule));
+    std::string why;
+    uint64_t n_voxels = 0;
+    // (the snapshot's region lies in the box: a new volume drops the snapshot)
+    const blok::GpuBuildStatus st = blok::gpu_volume_edit_by_distance(&ctx->volume, &ctx->distance, op, d2, density, material, &n_voxels, &why);
+    if (out_n_voxels) *out_n_voxels = n_voxels;
+    return volume_status(ctx, st, why);
 }
 
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {

@@ -182,6 +182,22 @@ GpuBuildStatus gpu_volume_encode_bricks(const GpuVolume* v, const uint32_t lo[3]
 // BLOK_BRICKS_KEEP_OTHERS or 0), then refreshes that box as every edit does.  The stream is one gpu_volume_encode_bricks made or one that
 // has passed bricks::validate: the kernel trusts its indices.  Blocking.
 GpuBuildStatus gpu_volume_decode_bricks(GpuVolume* v, const GpuBricks* stream, const uint32_t dst_lo[3], uint32_t flags, std::string* why);
+// ---- the distance field (include/blok_hip.h: blok_hip_volume_distance_field; distance_kernels.hip) ----
+// A field in device memory, owned by the holder: one value per region cell, x fastest, and the info that counts them.
+struct GpuDistance {
+    uint16_t* d_field = nullptr;
+    blok_distance_info info = {};
+    uint32_t lo[3] = {0, 0, 0};                  // the region's corner, box-local
+};
+void gpu_distance_free(GpuDistance* d);
+// The field of the box-local region [lo, hi) with max_radius <= 255 and known flags, from the brick masks (which every edit leaves equal to
+// density > 0).  Changes nothing; *out is a new snapshot, the caller's to free (d_field null when the region has no cell).  Blocking.
+GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t max_radius, uint32_t flags,
+                                         GpuDistance* out, std::string* why);
+// = blok_hip_volume_edit_by_distance over the snapshot's region (inside the box); the arguments have passed distance::check_edit_args.
+// Writes the store, then refreshes the region as every edit does.  Blocking.
+GpuBuildStatus gpu_volume_edit_by_distance(GpuVolume* v, const GpuDistance* field, int op, uint32_t d2, float density, uint32_t material,
+                                           uint64_t* out_n_voxels, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

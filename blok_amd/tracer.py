@@ -268,6 +268,48 @@ class HipTracer:
                                                             _ffi.ptr(dp) if len(dp) else None, _ffi.ptr(mp) if len(mp) else None, dlo,
                                                             _ffi.BRICKS_KEEP_OTHERS if keep_others else 0))
 
+    def volume_distance_field(self, lo=None, hi=None, max_radius: int = 0, to_empty: bool = False, box_is_solid: bool = False) -> np.ndarray:
+        """Takes the capped squared distance field of a region of the resident volume (world voxels, half open; both None = the whole box)
+        to the nearest filled cell — to_empty: to the nearest empty cell; box_is_solid: the outside of the box counts as filled — and keeps
+        it on the device (blok_hip.h: blok_hip_volume_distance_field) until the next field.  Returns the field's info, one
+        _ffi.DISTANCE_INFO record; volume_distance_download fetches the values, volume_edit_by_distance thresholds them."""
+        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
+        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        flags = (_ffi.DISTANCE_TO_EMPTY if to_empty else 0) | (_ffi.DISTANCE_BOX_IS_SOLID if box_is_solid else 0)
+        info = np.zeros(1, dtype=_ffi.DISTANCE_INFO)
+        self._check(self._lib.blok_hip_volume_distance_field(self._ctx, rlo, rhi, int(max_radius), flags, _ffi.ptr(info)))
+        return info
+
+    def volume_distance_info(self) -> np.ndarray:
+        info = np.zeros(1, dtype=_ffi.DISTANCE_INFO)
+        self._check(self._lib.blok_hip_volume_distance_info(self._ctx, _ffi.ptr(info)))
+        return info
+
+    def volume_distance_download(self, first=None, count=None, page: int = 1 << 24) -> np.ndarray:
+        """The last field's values (uint16, _ffi.DISTANCE_FAR = no source within the radius), fetched `page` cells at a time: cells
+        [first, first + count) in region index order, or with both None the whole field shaped [z][y][x]."""
+        whole = first is None and count is None
+        if whole:
+            ext = self.volume_distance_info()["ext"][0]
+            first, count = 0, int(ext[0]) * int(ext[1]) * int(ext[2])
+        first, count = int(first or 0), int(count or 0)
+        out = np.zeros(count, dtype=np.uint16)
+        if count == 0:
+            self._check(self._lib.blok_hip_volume_distance_download(self._ctx, None, first, 0))
+        for at in range(0, count, int(page)):
+            n = min(int(page), count - at)
+            self._check(self._lib.blok_hip_volume_distance_download(self._ctx, _ffi.ptr(out[at:at + n]), first + at, n))
+        return out.reshape(int(ext[2]), int(ext[1]), int(ext[0])) if whole else out
+
+    def volume_edit_by_distance(self, op: int, d2: int, density: float = 1.0, material: int = 0) -> int:
+        """Thresholds the last field at the squared distance d2 over its region (blok_hip.h: blok_hip_volume_edit_by_distance): op
+        _ffi.DISTANCE_GROW fills the empty cells within d2 of a filled one with (density, material), DISTANCE_SHRINK clears the filled
+        cells within d2 of an empty one, DISTANCE_HOLLOW clears the filled cells farther than d2 from every empty one.  Returns the number
+        of cells written; the next volume_rebuild installs the world."""
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_edit_by_distance(self._ctx, int(op), int(d2), float(density), int(material), C.byref(n)))
+        return int(n.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

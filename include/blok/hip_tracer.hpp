@@ -333,6 +333,28 @@ public:
     void decodeBricks(const BrickStream& s, const int32_t* dstLo = nullptr, bool keepOthers = false) {
         check(blok_hip_volume_decode_bricks(m_ctx, &s.info, s.records.data(), s.density.data(), s.material.data(), dstLo, keepOthers ? BLOK_BRICKS_KEEP_OTHERS : 0u));
     }
+    // The capped squared distance field of a region of the resident volume (world voxels, half-open; both null = the whole box) to the
+    // nearest filled cell — toEmpty: to the nearest empty one; boxIsSolid: the outside of the box counts as filled — kept on the device until
+    // the next field (blok_hip_volume_distance_field): returns what it holds.  downloadDistance fetches the values `page` cells at a time,
+    // x fastest; editByDistance thresholds them at the squared distance d2 (BLOK_DISTANCE_GROW / _SHRINK / _HOLLOW) and returns the cells written.
+    blok_distance_info distanceField(const int32_t* regionLo, const int32_t* regionHi, uint32_t maxRadius, bool toEmpty = false, bool boxIsSolid = false) {
+        blok_distance_info info{};
+        check(blok_hip_volume_distance_field(m_ctx, regionLo, regionHi, maxRadius, (toEmpty ? BLOK_DISTANCE_TO_EMPTY : 0u) | (boxIsSolid ? BLOK_DISTANCE_BOX_IS_SOLID : 0u), &info));
+        return info;
+    }
+    std::vector<uint16_t> downloadDistance(uint64_t page = uint64_t(1) << 24) {
+        blok_distance_info info{};
+        check(blok_hip_volume_distance_info(m_ctx, &info));
+        const uint64_t n = uint64_t(info.ext[0]) * info.ext[1] * info.ext[2];
+        std::vector<uint16_t> out(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_distance_download(m_ctx, out.data() + at, at, std::min(page, n - at)));
+        return out;
+    }
+    uint64_t editByDistance(int op, uint32_t d2, float density = 1.0f, uint32_t material = 0) {
+        uint64_t written = 0;
+        check(blok_hip_volume_edit_by_distance(m_ctx, op, d2, density, material, &written));
+        return written;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -571,7 +571,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.7: models stamped into the resident volume, regions of it captured as models.
  * 1.8: connected components of the resident volume, one of them captured as a model.
  * 1.9: placed models swept against the resident volume (overlap, free travel along an axis).
- * 1.10: the resident volume saved, restored and undone as a sparse brick stream. */
+ * 1.10: the resident volume saved, restored and undone as a sparse brick stream.
+ * 1.11: the capped squared distance field of the resident volume; grow, shrink and hollow by it. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -883,6 +884,67 @@ int blok_hip_volume_brick_payload_download(blok_hip_ctx* ctx, uint32_t plane, ui
 int blok_hip_volume_restore_bricks(blok_hip_ctx* ctx, const int32_t dst_lo[3], uint32_t flags);
 int blok_hip_volume_decode_bricks(blok_hip_ctx* ctx, const blok_bricks_info* info, const blok_brick_record* records,
                                   const uint32_t* density_payload, const uint32_t* material_payload, const int32_t dst_lo[3], uint32_t flags);
+
+/* ------------------------------------------------------------- the distance field of the resident volume (ABI 1.11)
+ * How far a cell is from the surface: the squared Euclidean distance to the nearest filled (or empty) cell, capped at a radius, as a
+ * snapshot in HBM, and the three edits that threshold it — grow and shrink by a ball, hollow.  Read from the brick masks where they lie,
+ * never from the densities.  A pure integer function of density > 0: one right answer, bit-identical on the host (blok_distance_field /
+ * blok_distance_edit, blok_world.h) and on the device.  All calls block.
+ *  - Cell state.  Inside the volume's box a cell is filled iff density > 0; zero, negative and NaN densities are empty.
+ *  - Outside the box a cell is empty; with BLOK_DISTANCE_BOX_IS_SOLID it is filled (the sweep's rule).
+ *  - Sources.  By default the filled cells; with BLOK_DISTANCE_TO_EMPTY the empty cells.  Sources are taken from the whole box and its
+ *    outside, not only from the region: a source one cell outside the region counts.
+ *  - Value.  R = max_radius lies in 0 .. 255.  For a region cell c, D(c) is the minimum of |s - c|^2 over all sources s with
+ *    |s - c|^2 <= R^2, where |s - c|^2 is the integer sum of the three squared coordinate differences, and BLOK_DISTANCE_FAR (0xFFFF)
+ *    when there is no such source.  D(c) == 0 iff c is itself a source.  R^2 <= 65025, so every value fits a uint16_t beside the sentinel.
+ *  - Region: world voxels, half open; both pointers NULL = the whole box (the convention of blok_hip_volume_extract_quads).
+ *  - Snapshot: one uint16_t per region cell, x fastest, then y, then z (the labels' index order), in device memory, owned by the context.
+ *    Later edits do not touch it; the next field replaces it; blok_hip_volume_destroy, a new blok_hip_volume_create and blok_hip_destroy
+ *    free it.  Taking a field has no effect on the volume or on the quads, components and bricks snapshots.  The result is the same in
+ *    the keyed and the row-major brick layout.  out_info may be NULL.
+ *  - Info: n_zero, n_near and n_far count the region cells with D == 0, with 0 < D <= R^2, and with FAR.
+ *  - blok_hip_volume_distance_download copies cells [first, first + count); blok_hip_volume_distance_info returns the snapshot's info.
+ *  - blok_hip_volume_edit_by_distance thresholds the snapshot at the squared distance d2, over the snapshot's region only.  Membership is
+ *    judged against the volume as it is NOW (as blok_hip_volume_capture_component does), so there is no staleness rule.
+ *      BLOK_DISTANCE_GROW: the snapshot must be a to-filled field; every region cell with 1 <= D <= d2 that is empty now gets
+ *        (density, material).
+ *      BLOK_DISTANCE_SHRINK: the snapshot must be a to-empty field; every region cell with 1 <= D <= d2 that is filled now gets (0.0f, 0);
+ *        density and material are ignored.
+ *      BLOK_DISTANCE_HOLLOW: the snapshot must be a to-empty field; every region cell with D > d2, FAR included, that is filled now gets
+ *        (0.0f, 0): what remains is the shell within d2 of empty space.
+ *    d2 <= R^2 of the snapshot is required: beyond that the snapshot cannot decide D <= d2.  d2 is a squared distance on purpose: 1 is the
+ *    6-neighbourhood, 2 the 18-neighbourhood, 3 the 26-neighbourhood, r^2 a ball of radius r.  *out_n_voxels (may be NULL) is the number
+ *    of cells written.  The snapshot is not updated by the edit.
+ *  - After an edit masks, occupancy words, dirty flags and the edited box are those blok_hip_volume_set_voxels leaves for the same writes,
+ *    refreshed over the snapshot's region; GROW counts as a write that may have filled voxels; the next blok_hip_volume_rebuild installs
+ *    the world.
+ *  - Errors, each leaving the volume and the previous snapshot as they were.  BLOK_ERR_INVALID_ARG: unknown flag bits, exactly one region
+ *    pointer NULL, lo > hi on an axis, max_radius > 255, no snapshot (info, download and edit), a download range past the end, a NULL
+ *    array with count > 0, an unknown op, an op that needs the other kind of field, d2 above the snapshot's R^2, for GROW a density that
+ *    is not finite or <= 0.  BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume above 2^32 cells, a region of more than
+ *    2^31 tiles of 64 x 32 cells (no volume that can be created today has one).  BLOK_ERR_NO_WORLD: no volume.
+ *    BLOK_ERR_OOM: a failed device allocation.  An empty region is BLOK_OK with zero counts and an empty snapshot; every edit on an empty
+ *    snapshot writes nothing. */
+#define BLOK_DISTANCE_TO_EMPTY     1u   /* the sources are the empty cells (default: the filled cells) */
+#define BLOK_DISTANCE_BOX_IS_SOLID 2u   /* cells outside the volume's box count as filled (default: as empty) */
+#define BLOK_DISTANCE_FAR 0xFFFFu       /* no source within max_radius */
+#define BLOK_DISTANCE_GROW   0
+#define BLOK_DISTANCE_SHRINK 1
+#define BLOK_DISTANCE_HOLLOW 2
+typedef struct blok_distance_info {
+    uint32_t version;      /* 1 */
+    uint32_t flags;        /* the field's flags */
+    int32_t  lo[3];        /* the region, world voxels */
+    uint32_t ext[3];
+    uint32_t max_radius;   /* R */
+    uint32_t reserved;     /* 0: pads the counts to 8 bytes */
+    uint64_t n_zero, n_near, n_far;      /* region cells with D == 0, with 0 < D <= R^2, with FAR */
+} blok_distance_info;      /* 64 bytes */
+int blok_hip_volume_distance_field(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t max_radius,
+                                   uint32_t flags, blok_distance_info* out_info);
+int blok_hip_volume_distance_info(blok_hip_ctx* ctx, blok_distance_info* out_info);
+int blok_hip_volume_distance_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count);
+int blok_hip_volume_edit_by_distance(blok_hip_ctx* ctx, int op, uint32_t d2, float density, uint32_t material, uint64_t* out_n_voxels);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

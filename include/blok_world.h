@@ -244,6 +244,21 @@ int blok_bricks_write_file(const char* path, const blok_bricks_info* info, const
 int blok_bricks_read_file(const char* path, blok_bricks_info* out_info, blok_brick_record* records, uint32_t* density_payload,
                           uint32_t* material_payload, char* err, size_t err_len);
 
+/* -------------------------------------------------------------- the distance field on the host (distance.cpp)
+ * The contracts of blok_hip_volume_distance_field and blok_hip_volume_edit_by_distance (blok_hip.h; blok_distance_info, the flags and the
+ * ops are declared there) over host arrays density[x + y*nx + z*nx*ny] / material_ids of a box whose voxel (0, 0, 0) sits at world
+ * `origin` (NULL = 0, 0, 0), through the rules the kernels use, separable as the device's.
+ * field: the region is in world voxels, half open, both NULL = the whole box; out_field takes one value per region cell, x fastest, and
+ * *out_info (may be NULL) what the device's info holds.  Errors as the device entry; a NULL array with a non-empty region is
+ * BLOK_ERR_INVALID_ARG.
+ * edit: applies `op` at the threshold d2 to the two arrays from a field and its info, judged against the arrays as they are; *out_n_voxels
+ * (may be NULL) is the number of cells written.  Errors as the device entry; an info whose version is not 1 is BLOK_ERR_INVALID_ARG, one
+ * whose region leaves the box BLOK_ERR_UNSUPPORTED.  Nothing is written on an error. */
+int blok_distance_field(const float* density, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const int32_t region_lo[3],
+                        const int32_t region_hi[3], uint32_t max_radius, uint32_t flags, uint16_t* out_field, blok_distance_info* out_info);
+int blok_distance_edit(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const uint16_t* field,
+                       const blok_distance_info* info, int op, uint32_t d2, float density_value, uint32_t material, uint64_t* out_n_voxels);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);
