@@ -7,6 +7,7 @@ import numpy as np
 
 from blok_amd import _ffi
 from blok_amd import terrain as T
+from tests.distance_reference import moved
 from tests.terrain_cases import ISSUE, prior
 
 FILLED_ONLY, KEEP_OTHERS = 1, 1
@@ -102,28 +103,41 @@ def stream_bytes(stream) -> int:
 # ---- the content the CPU and GPU tests share ----------------------------------------------------------------------------------------------
 SCENE_ORIGIN, SCENE_SHAPE = (-40, -44, -24), (96, 80, 64)
 # the ragged regions of tests/test_quads_gpu.py (world voxels): unaligned in every axis, and one voxel thick in z, y and x
-SCENE_REGIONS = [(None, None), ((-31, -39, -13), (38, 21, 30)), ((-8, -20, 0), (24, 4, 1)), ((-40, 3, -24), (56, 4, 40)), ((17, -44, -20), (18, 36, 33))]
-SCENE_ALIGNED = [(None, None), ((-32, -40, -16), (40, 20, 32))]      # corners on the box's brick grid
-_scene = None
+_SCENE_REGIONS = [(None, None), ((-31, -39, -13), (38, 21, 30)), ((-8, -20, 0), (24, 4, 1)), ((-40, 3, -24), (56, 4, 40)), ((17, -44, -20), (18, 36, 33))]
+_SCENE_ALIGNED = [(None, None), ((-32, -40, -16), (40, 20, 32))]      # corners on the box's brick grid
 
 
-def scene():
-    """The shared scene, computed once and never written to: prior() content with negative and NaN densities, the ISSUE terrain added on
-    top (ADD: only where nothing is filled)."""
-    global _scene
-    if _scene is None:
+def scene_regions(origin=SCENE_ORIGIN):
+    """The ragged regions over the box SCENE_SHAPE at `origin`: the same box-local cells."""
+    return moved(_SCENE_REGIONS, origin, SCENE_ORIGIN)
+
+
+def scene_aligned(origin=SCENE_ORIGIN):
+    return moved(_SCENE_ALIGNED, origin, SCENE_ORIGIN)
+
+
+SCENE_REGIONS, SCENE_ALIGNED = scene_regions(), scene_aligned()
+_scene = {}
+
+
+def scene(origin=SCENE_ORIGIN):
+    """The shared scene of the box at `origin`, computed once and never written to: prior() content with negative and NaN densities, the
+    ISSUE terrain added on top (ADD: only where nothing is filled).  The terrain is a function of the world coordinate; its base height
+    moves with the box's floor, so that its surface crosses the box wherever the box lies."""
+    origin = tuple(origin)
+    if origin not in _scene:
         nx, ny, nz = SCENE_SHAPE
         d, m = prior((nz, ny, nx))
         d[::3, ::2, ::5] = -0.5
         d[1::7, ::3, ::2] = np.nan
         p = _ffi.TerrainParams()
-        for k, v in dict(ISSUE, flags=4).items():
+        for k, v in dict(ISSUE, flags=4, base_height=ISSUE["base_height"] + origin[1] - SCENE_ORIGIN[1]).items():
             setattr(p, k, v)
-        hi = tuple(o + n for o, n in zip(SCENE_ORIGIN, SCENE_SHAPE))
-        d, m, _ = T.eval_box(p, SCENE_ORIGIN, hi, d, m)
+        hi = tuple(o + n for o, n in zip(origin, SCENE_SHAPE))
+        d, m, _ = T.eval_box(p, origin, hi, d, m)
         d.setflags(write=False); m.setflags(write=False)
-        _scene = (d, m)
-    return _scene
+        _scene[origin] = (d, m)
+    return _scene[origin]
 
 
 def small_volumes():

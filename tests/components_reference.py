@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from blok_amd import _ffi
+from tests.distance_reference import moved
 
 EMPTY = 0xFFFFFFFF
 
@@ -212,13 +213,17 @@ def prior_with_empties(shape_xyz=SHAPE, seed=3, thin=False):
     return np.ascontiguousarray(d), np.ascontiguousarray(m)
 
 
-_cases = None
+_cases = {}
 
 
-def cases():
-    global _cases
-    if _cases is not None:
-        return _cases
+def cases(origin=ORIGIN):
+    """The cases over the box SHAPE at `origin`: the same arrays, the regions translated with the box."""
+    origin = tuple(origin)
+    if origin in _cases:
+        return _cases[origin]
+    if origin != ORIGIN:                                        # the arrays are box-local: shared with the box at ORIGIN, the regions moved
+        _cases[origin] = {name: (d, m, *moved([(lo, hi)], origin, ORIGIN)[0]) for name, (d, m, lo, hi) in cases().items()}
+        return _cases[origin]
     from tests.conftest import SEED
     out = {}
     d, m = empty_box()
@@ -290,16 +295,17 @@ def cases():
         m[s] = np.where(d[s] > 0, rng.integers(1, 250, fill.shape), 0)
         d[s][0, 0, 0], m[s][0, 0, 0] = 1.0, 77                  # the region's lowest corner cell is filled: some component touches the corner
         out[f"random {p}"] = (np.ascontiguousarray(d), np.ascontiguousarray(m), *world(RANDOM_LO, RANDOM_EXT))
-    _cases = out
+    _cases[origin] = out
     return out
 
 
 _expected = {}
 
 
-def expected(name):
-    """The reference's (labels, records) of a case, computed once."""
-    if name not in _expected:
-        d, _, lo, hi = cases()[name]
-        _expected[name] = label(d, ORIGIN, lo, hi)
-    return _expected[name]
+def expected(name, origin=ORIGIN):
+    """The reference's (labels, records) of a case over the box at `origin`, computed once."""
+    key = (name, tuple(origin))
+    if key not in _expected:
+        d, _, lo, hi = cases(origin)[name]
+        _expected[key] = label(d, origin, lo, hi)
+    return _expected[key]

@@ -69,16 +69,21 @@ def field_brute(d, origin, lo, hi, R, flags):
     return out, make_info(origin, lo, ext, R, flags, out)
 
 
-def field(d, origin, lo, hi, R, flags):
+def field(d, origin, lo, hi, R, flags, pad=None):
     """The separable model: three capped min-plus passes over the region padded by 2 R + 2 with the outside state (a shift brings FAR in
-    at the array's end; with that much padding it never reaches the region)."""
+    at the array's end; with that much padding it never reaches the region).  pad = 0 is allowed for the whole box with flags 0 alone:
+    there the outside holds no source, which is what FAR says, so a long thin box needs no padding R cells wide on every side."""
+    whole = lo is None and hi is None
     lo, ext = region_of(np.shape(d), origin, lo, hi)
-    pad = 2 * R + 2
+    assert pad is None or (pad == 0 and whole and flags == 0)
+    pad = 2 * R + 2 if pad is None else pad
     g = np.where(sources_padded(d, flags, pad, lo, ext), 0, FAR).astype(np.int32)
     for ax in (2, 1, 0):
         best = np.full(g.shape, FAR, np.int32)                    # (what a shift leaves uncovered at the array's end stays FAR)
         n = g.shape[ax]
         for k in range(-R, R + 1):
+            if abs(k) >= n:                                       # (only without padding: a shift by the whole extent covers nothing)
+                continue
             sl, dl = [slice(None)] * 3, [slice(None)] * 3
             if k >= 0:
                 sl[ax], dl[ax] = slice(k, n), slice(0, n - k)
@@ -150,8 +155,23 @@ def noise(fill=0.01, seed=5):
 
 SCENE_ORIGIN, SCENE_SHAPE = (3, -8, 10), (40, 36, 33)
 # regions that touch each face of the box and one strictly inside; ends off and on the 4- and 16-voxel grid
-SCENE_REGIONS = [(None, None), ((3, -8, 10), (20, 9, 27)), ((26, 8, 23), (43, 28, 43)), ((8, -3, 15), (37, 21, 38)), ((7, -4, 14), (19, 8, 30))]
+_SCENE_REGIONS = [(None, None), ((3, -8, 10), (20, 9, 27)), ((26, 8, 23), (43, 28, 43)), ((8, -3, 15), (37, 21, 38)), ((7, -4, 14), (19, 8, 30))]
 SCENE_RADII = (8, 16)
+
+
+def moved(regions, origin, base=None):
+    """World regions [(lo, hi)] given for a box at `base` (default SCENE_ORIGIN) as the same box-local cells of the box at `origin`; a
+    None corner stays None.  The one helper by which the reference modules move their case tables with a box."""
+    base = SCENE_ORIGIN if base is None else base
+    move = lambda c: None if c is None else tuple(c[a] - base[a] + origin[a] for a in range(3))
+    return [(move(lo), move(hi)) for lo, hi in regions]
+
+
+def scene_regions(origin=SCENE_ORIGIN):
+    return moved(_SCENE_REGIONS, origin)
+
+
+SCENE_REGIONS = scene_regions()
 
 
 def scene(seed=11):
@@ -177,19 +197,21 @@ def scene(seed=11):
 _scene_fields = {}
 
 
-def scene_cases():
-    """(lo, hi, R, flags) over the scene: the whole box in all four flag combinations, each region in one of them, the far corner in two."""
+def scene_cases(origin=SCENE_ORIGIN):
+    """(lo, hi, R, flags) over the scene in the box at `origin`: the whole box in all four flag combinations, each region in one of them,
+    the far corner in two."""
+    regions = scene_regions(origin)
     cases = [(None, None, radius, flags) for radius in SCENE_RADII for flags in ALL_FLAGS]
-    for i, (lo, hi) in enumerate(SCENE_REGIONS[1:], 1):
+    for i, (lo, hi) in enumerate(regions[1:], 1):
         cases += [(lo, hi, radius, ALL_FLAGS[i % 4]) for radius in SCENE_RADII]
-    return cases + [(*SCENE_REGIONS[2], radius, 0) for radius in SCENE_RADII]
+    return cases + [(*regions[2], radius, 0) for radius in SCENE_RADII]
 
 
-def scene_field(lo, hi, R, flags):
-    """The model's field over the scene, computed once per case (the scene is never changed)."""
-    key = (lo, hi, R, flags)
+def scene_field(lo, hi, R, flags, origin=SCENE_ORIGIN):
+    """The model's field over the scene in the box at `origin`, computed once per case (the scene is never changed)."""
+    key = (lo, hi, R, flags, tuple(origin))
     if key not in _scene_fields:
-        _scene_fields[key] = field(scene()[0], SCENE_ORIGIN, lo, hi, R, flags)
+        _scene_fields[key] = field(scene()[0], origin, lo, hi, R, flags)
     return _scene_fields[key]
 
 

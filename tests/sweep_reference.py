@@ -7,6 +7,8 @@ Arrays are [z][y][x] over a box whose voxel (0, 0, 0) sits at world `origin`.  P
 Directions: 0 +X, 1 -X, 2 +Y, 3 -Y, 4 +Z, 5 -Z."""
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from tests.stamp_reference import ORIENTATIONS, small_model, world_voxels  # noqa: F401
@@ -138,13 +140,37 @@ def prior_with_empties(shape_xyz=SHAPE):
     return np.ascontiguousarray(d0), np.ascontiguousarray(m0)
 
 
-def world(local):
-    return tuple(ORIGIN[a] + local[a] for a in range(3))
+def world(local, origin=ORIGIN):
+    return tuple(origin[a] + local[a] for a in range(3))
 
 
-def at(local, orientation=IDENTITY):
-    """The placement that puts local voxel (0, 0, 0) of an unflipped model on the box-local cell `local`."""
-    return (world(local), orientation[0], orientation[1])
+def at(local, orientation=IDENTITY, origin=ORIGIN):
+    """The placement that puts local voxel (0, 0, 0) of an unflipped model on the box-local cell `local` of the box at `origin`."""
+    return (world(local, origin), orientation[0], orientation[1])
+
+
+LATTICE = (-32768, 32768)                                      # a placement's world box lies in [LATTICE[0], LATTICE[1]) on every axis
+
+
+def in_lattice(place, model_xyz, mirror_in=None):
+    """`place` moved by the least offset that brings the model's world box into the lattice: a placement that hung out of a face of the
+    box hangs out of it still where the lattice goes on, and lies flush against the lattice's end where the face is that end.  With
+    mirror_in = (origin, shape) an axis on which the box leaves the lattice is first mirrored about the box's middle (a model far outside
+    one side of the box becomes one as far outside the other).  In the box at ORIGIN nothing moves."""
+    offset, axis, flip = place
+    offset = list(offset)
+    for _ in range(2 if mirror_in else 1):
+        w = world_voxels(model_xyz, offset, axis, flip)
+        lo, hi = w.min(axis=0), w.max(axis=0) + 1
+        for a in range(3):
+            out = int(hi[a]) > LATTICE[1] or int(lo[a]) < LATTICE[0]
+            if out and mirror_in:
+                origin, shape = mirror_in
+                offset[a] = 2 * origin[a] + shape[a] - 1 - offset[a]
+            elif out:
+                offset[a] += min(LATTICE[1] - int(hi[a]), 0) + max(LATTICE[0] - int(lo[a]), 0)
+        mirror_in = None
+    return (tuple(offset), axis, flip)
 
 
 # obstacles whose first filled cell is bit 0 and bit 3 of its brick along each axis, behind 4-, 16- and (where the box has one) 64-voxel
@@ -219,64 +245,72 @@ FAR = 0xFFFFFFFF
 FACE_OFFSETS = {"-x": (0, 30, 20), "+x": (95, 30, 20), "-y": (40, 1, 20), "+y": (40, 78, 20), "-z": (40, 30, 0), "+z": (40, 30, 63)}
 OUTSIDE_OFFSETS = ((130, 30, 20), (40, -60, 20), (40, 30, 30000), (-30000, 30, 20), (40, 30, -9))
 
-_cases = None
+_cases = {}
 
 
-def cases():
-    global _cases
-    if _cases is not None:
-        return _cases
+def cases(origin=ORIGIN):
+    """The cases over the box SHAPE at `origin`: the same box-local placements; where the box touches the lattice's end a placement that
+    would leave the lattice is moved by in_lattice (none is at ORIGIN)."""
+    origin = tuple(origin)
+    if origin in _cases:
+        return _cases[origin]
+    m = models()
+    put = functools.partial(at, origin=origin)                 # every placement below is in the box at `origin`
     out = {name: [] for name in scenes()}
     # simple shapes, every direction, in the prior and the thinned scene
     for scene in ("prior", "thinned"):
         for name, local in (("one voxel", (41, 33, 29)), ("cube", (43, 39, 31)), ("ell", (47, 36, 33)), ("bar", (13, 41, 30)), ("cup", (50, 22, 18))):
             for direction in range(6):
                 for max_distance in (0, 7, 300):
-                    out[scene].append((f"{name} {direction} {max_distance}", name, at(local), direction, max_distance, 0))
-        out[scene].append(("bar rotated", "bar", at((50, 6, 30), ((1, 0, 2), 0)), 0, 50, 0))
-        out[scene].append(("bar flipped along z", "bar", at((50, 40, 62), ((2, 1, 0), 1)), 3, 50, BOX_IS_SOLID))
+                    out[scene].append((f"{name} {direction} {max_distance}", name, put(local), direction, max_distance, 0))
+        out[scene].append(("bar rotated", "bar", put((50, 6, 30), ((1, 0, 2), 0)), 0, 50, 0))
+        out[scene].append(("bar flipped along z", "bar", put((50, 40, 62), ((2, 1, 0), 1)), 3, 50, BOX_IS_SOLID))
     # all 48 orientations x 6 directions
     for axis, flip in ORIENTATIONS:
         for direction in range(6):
-            out["thinned"].append((f"small {axis} {flip} {direction}", "small", at((48, 40, 32), (axis, flip)), direction, 40, 0))
+            out["thinned"].append((f"small {axis} {flip} {direction}", "small", put((48, 40, 32), (axis, flip)), direction, 40, 0))
     # the obstacle runs: one voxel, then the cube (its leading face meets the obstacle; the trailing one the cell behind the start)
     for axis, step, start, c in obstacle_runs():
         direction = 2 * axis + (step < 0)
         for max_distance in (100, abs(c - start[axis]) - 1, abs(c - start[axis])):
-            out["runs"].append((f"run {axis} {step} {c} {max_distance}", "one voxel", at(start), direction, max_distance, 0))
-        out["runs"].append((f"run {axis} {step} {c} far", "one voxel", at(start), direction, FAR, BOX_IS_SOLID))
+            out["runs"].append((f"run {axis} {step} {c} {max_distance}", "one voxel", put(start), direction, max_distance, 0))
+        out["runs"].append((f"run {axis} {step} {c} far", "one voxel", put(start), direction, FAR, BOX_IS_SOLID))
     # hanging out of each face, wholly outside, leaving the box during travel; with and without the flag
     for flags in (0, BOX_IS_SOLID):
         for face, local in FACE_OFFSETS.items():
             for k, direction in enumerate(range(6)):
                 axis, flip = ORIENTATIONS[(7 * k + 5 * len(out["prior"])) % 48]
-                out["prior"].append((f"face {face} {direction} {flags}", "small", at(local, (axis, flip)), direction, 200, flags))
+                out["prior"].append((f"face {face} {direction} {flags}", "small", put(local, (axis, flip)), direction, 200, flags))
         for local in OUTSIDE_OFFSETS:
             for direction in range(6):
-                out["prior"].append((f"outside {local} {direction} {flags}", "small", at(local), direction, FAR if direction < 2 else 500, flags))
+                out["prior"].append((f"outside {local} {direction} {flags}", "small", put(local), direction, FAR if direction < 2 else 500, flags))
         for direction in range(6):                             # a clear run out of the thinned core and the box: the plate scene's empty top
-            out["plate"].append((f"leaving {direction} {flags}", "cube", at((70, 60, 50)), direction, 1000, flags))
+            out["plate"].append((f"leaving {direction} {flags}", "cube", put((70, 60, 50)), direction, 1000, flags))
     # the combs, the cup and its twin
     for max_distance in (0, 3, 5, 6, 100, FAR):
-        out["plate"].append((f"comb {max_distance}", "comb", at(COMB_AT), 3, max_distance, 0))
-        out["plate"].append((f"comb tie {max_distance}", "comb", at(COMB_TIE_AT), 3, max_distance, 0))
-    out["plate"].append(("comb up", "comb", at(COMB_AT), 2, 100, BOX_IS_SOLID))
-    out["plate"].append(("cup", "cup", at(CUP_AT), 3, 100, 0))
-    out["plate"].append(("cup twin", "cup", at((CUP_AT[0], CUP_AT[1], CUP_AT[2] + 8)), 3, 100, 0))
-    _cases = out
+        out["plate"].append((f"comb {max_distance}", "comb", put(COMB_AT), 3, max_distance, 0))
+        out["plate"].append((f"comb tie {max_distance}", "comb", put(COMB_TIE_AT), 3, max_distance, 0))
+    out["plate"].append(("comb up", "comb", put(COMB_AT), 2, 100, BOX_IS_SOLID))
+    out["plate"].append(("cup", "cup", put(CUP_AT), 3, 100, 0))
+    out["plate"].append(("cup twin", "cup", put((CUP_AT[0], CUP_AT[1], CUP_AT[2] + 8)), 3, 100, 0))
+    for scene in out:
+        out[scene] = [(tag, name, in_lattice(place, m[name], (origin, SHAPE) if tag.startswith("outside") else None), direction, max_distance, flags)
+                      for tag, name, place, direction, max_distance, flags in out[scene]]
+    _cases[origin] = out
     return out
 
 
 _expected = {}
 
 
-def expected(scene):
-    """[(n_overlap, travel, blocked)] of a scene's cases, computed once."""
-    if scene not in _expected:
+def expected(scene, origin=ORIGIN):
+    """[(n_overlap, travel, blocked)] of a scene's cases over the box at `origin`, computed once."""
+    key = (scene, tuple(origin))
+    if key not in _expected:
         d, m = scenes()[scene], models()
-        _expected[scene] = [sweep(d, ORIGIN, m[name], place, direction, max_distance, flags)
-                            for _, name, place, direction, max_distance, flags in cases()[scene]]
-    return _expected[scene]
+        _expected[key] = [sweep(d, origin, m[name], place, direction, max_distance, flags)
+                          for _, name, place, direction, max_distance, flags in cases(origin)[scene]]
+    return _expected[key]
 
 
 # ---- a box whose extents are no multiples of 4: the last brick along every axis is partial ------------------------------------------

@@ -5,7 +5,8 @@ captured components against blok_hip_model_create's models byte for byte; a cut 
 Both brick layouts unless said.
 
 Not covered: BLOK_ERR_UNSUPPORTED for a volume above 2^32 cells and for a region of 2^32 cells (the two arrays of such a volume alone are
-32 GiB), and BLOK_ERR_OOM."""
+32 GiB), and BLOK_ERR_OOM.
+Boxes at the ends of the int16 lattice and boxes of 16384 cells on one axis are covered in tests/test_volume_limits_gpu.py."""
 from __future__ import annotations
 
 import ctypes as C

@@ -2,7 +2,8 @@
 (tests/stamp_reference.py): the volume's arrays byte for byte after every call, the rebuilt tree against volume_tree_reference, a baked
 instance against the traced one, captured models against blok_hip_model_create's byte for byte.  Both brick layouts unless said.
 
-Not covered: BLOK_ERR_UNSUPPORTED for a volume above 2^32 cells (its two arrays alone are 32 GiB)."""
+Not covered: BLOK_ERR_UNSUPPORTED for a volume above 2^32 cells (its two arrays alone are 32 GiB).
+Boxes at the ends of the int16 lattice and boxes of 16384 cells on one axis are covered in tests/test_volume_limits_gpu.py."""
 from __future__ import annotations
 
 import itertools

@@ -2,7 +2,8 @@
 and the volume byte for byte afterwards (a sweep reads only).  Both brick layouts unless said.  The shapes, scenes and cases are the
 shared ones of sweep_reference.py, on which tests/test_sweep_cpu.py pins the host build and asserts what makes each of them hard.
 
-Not covered: BLOK_ERR_UNSUPPORTED for a volume above 2^32 cells (its two arrays alone are 32 GiB)."""
+Not covered: BLOK_ERR_UNSUPPORTED for a volume above 2^32 cells (its two arrays alone are 32 GiB).
+Boxes at the ends of the int16 lattice and boxes of 16384 cells on one axis are covered in tests/test_volume_limits_gpu.py."""
 from __future__ import annotations
 
 import ctypes as C
