@@ -67,10 +67,24 @@ DISTANCE_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3)
 DISTANCE_TO_EMPTY, DISTANCE_BOX_IS_SOLID = 1, 2   # = BLOK_DISTANCE_TO_EMPTY, BLOK_DISTANCE_BOX_IS_SOLID
 DISTANCE_FAR = 0xFFFF                             # = BLOK_DISTANCE_FAR
 DISTANCE_GROW, DISTANCE_SHRINK, DISTANCE_HOLLOW = 0, 1, 2      # = BLOK_DISTANCE_GROW / _SHRINK / _HOLLOW
+# = blok_flood_info: what a flood snapshot holds, 64 bytes
+FLOOD_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("max_steps", "<u4"), ("farthest", "<u4"),
+                       ("n_seed", "<u8"), ("n_reached", "<u8"), ("n_unreached", "<u8")])
+FLOOD_THROUGH_FILLED, FLOOD_SAME_MATERIAL = 1, 2  # = BLOK_FLOOD_THROUGH_FILLED, BLOK_FLOOD_SAME_MATERIAL
+FLOOD_FAR = 0xFFFF                                # = BLOK_FLOOD_FAR
+FLOOD_MAX_STEPS = 65534                           # = BLOK_FLOOD_MAX_STEPS
+FLOOD_FILL, FLOOD_FILL_UNREACHED, FLOOD_PAINT, FLOOD_CLEAR = 0, 1, 2, 3      # = BLOK_FLOOD_FILL / _FILL_UNREACHED / _PAINT / _CLEAR
+
+
+def flood_seed_face(f: int) -> int:
+    """= BLOK_FLOOD_SEED_FACE(f): side f of the region (0 +X, 1 -X, 2 +Y, 3 -Y, 4 +Z, 5 -Z) is a seed layer."""
+    return 1 << (8 + int(f))
+
+
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
 assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD.itemsize == 24 and BRICKS_INFO.itemsize == 64
-assert DISTANCE_INFO.itemsize == 64
+assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64
 
 
 class GBuffer(C.Structure):
@@ -207,6 +221,10 @@ HOST_SYMBOLS = {
                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_distance_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "blok_flood_field": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_flood_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -349,6 +367,11 @@ HIP_SYMBOLS = {
     "blok_hip_volume_distance_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_volume_distance_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_edit_by_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_flood_field": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_void_p]),
+    "blok_hip_volume_flood_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_volume_flood_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_edit_by_flood": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
@@ -375,6 +398,7 @@ HIP_SYMBOLS = {
     "blok_hip_draw_frame_rt_instanced_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                           C.c_void_p, C.POINTER(C.c_uint32)]),
     "blok_hip_volume_refresh_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_flood_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_debug_build_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 

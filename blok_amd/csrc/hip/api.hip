@@ -308,7 +308,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 11u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 12u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -394,6 +394,7 @@ void blok_hip_destroy(blok_hip_ctx* ctx) {
     blok::gpu_components_free(&ctx->components);
     blok::gpu_bricks_free(&ctx->bricks);
     blok::gpu_distance_free(&ctx->distance);
+    blok::gpu_flood_free(&ctx->flood);
     forget_device_activity(ctx);
     for (auto& kv : ctx->beam_buffers) free_stream_scratch(kv.second);
     if (ctx->d_list_cost) (void)hipFree(ctx->d_list_cost);

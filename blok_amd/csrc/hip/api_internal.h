@@ -101,6 +101,7 @@ struct blok_hip_ctx {
     blok::GpuComponents components; bool has_components = false;      // the snapshot of the last blok_hip_volume_label_components
     blok::GpuBricks bricks; bool has_bricks = false;                  // the snapshot of the last blok_hip_volume_encode_bricks
     blok::GpuDistance distance; bool has_distance = false;            // the snapshot of the last blok_hip_volume_distance_field
+    blok::GpuFlood flood; bool has_flood = false;                     // the snapshot of the last blok_hip_volume_flood_field
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
     float* d_sun_map = nullptr;

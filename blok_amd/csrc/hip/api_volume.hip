@@ -5,6 +5,7 @@
 #include "../common/sweep_core.h"
 #include "../common/bricks_core.h"
 #include "../common/distance_core.h"
+#include "../common/flood_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -21,6 +22,7 @@ int volume_status(blok_hip_ctx* ctx, blok::GpuBuildStatus st, const std::string&
         case blok::GpuBuildStatus::Unsupported: return set_error(ctx, BLOK_ERR_UNSUPPORTED, why);
         case blok::GpuBuildStatus::OutOfMemory: return set_error(ctx, BLOK_ERR_OOM, why);
         case blok::GpuBuildStatus::HipError: return set_error(ctx, BLOK_ERR_HIP, why);
+        case blok::GpuBuildStatus::Internal: return set_error(ctx, BLOK_ERR_INTERNAL, why);
         default: return set_error(ctx, BLOK_ERR_INVALID_ARG, why.empty() ? "volume operation not applicable" : why);
     }
 }
@@ -39,6 +41,10 @@ void drop_bricks(blok_hip_ctx* ctx) {
 void drop_distance(blok_hip_ctx* ctx) {
     blok::gpu_distance_free(&ctx->distance);
     ctx->has_distance = false;
+}
+void drop_flood(blok_hip_ctx* ctx) {
+    blok::gpu_flood_free(&ctx->flood);
+    ctx->has_flood = false;
 }
 int need_volume(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
@@ -89,6 +95,7 @@ int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t 
     drop_components(ctx);
     drop_bricks(ctx);
     drop_distance(ctx);
+    drop_flood(ctx);
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
     std::string why;
     const blok::GpuBuildStatus st = blok::gpu_volume_create(o, nx, ny, nz, chunk_size, voxel_size, &ctx->volume, &why, ctx->volume_keyed_layout);
@@ -121,6 +128,7 @@ int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
     drop_components(ctx);
     drop_bricks(ctx);
     drop_distance(ctx);
+    drop_flood(ctx);
     return BLOK_OK;
 }
 
@@ -532,6 +540,75 @@ int blok_hip_volume_edit_by_distance(blok_hip_ctx* ctx, int op, uint32_t d2, flo
     uint64_t n_voxels = 0;
     // (the snapshot's region lies in the box: a new volume drops the snapshot)
     const blok::GpuBuildStatus st = blok::gpu_volume_edit_by_distance(&ctx->volume, &ctx->distance, op, d2, density, material, &n_voxels, &why);
+    if (out_n_voxels) *out_n_voxels = n_voxels;
+    return volume_status(ctx, st, why);
+}
+
+int blok_hip_volume_flood_field(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], const int32_t* seeds_xyz_host,
+                                uint64_t n_seeds, uint32_t max_steps, uint32_t flags, uint32_t material, blok_flood_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (const int rule = blok::flood::check_field_args(seeds_xyz_host, n_seeds, max_steps, flags))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("flood_field: ") + blok::flood::rule_text(rule));
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "flood_field", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    for (uint64_t i = 0; i < n_seeds; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const int64_t c = int64_t(seeds_xyz_host[3 * i + a]) - ctx->volume.origin[a];
+            if (c < int64_t(lo[a]) || c >= int64_t(hi[a])) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_field: seed " + std::to_string(i) + " lies outside the region");
+        }
+    std::string why;
+    blok::GpuFlood snapshot;
+    // (edits are enqueued on the null stream, and so is this: it reads the masks they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_flood_field(&ctx->volume, lo, hi, seeds_xyz_host, n_seeds, max_steps, flags, material, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    drop_flood(ctx);
+    ctx->flood = snapshot; ctx->has_flood = true;
+    if (out_info) *out_info = snapshot.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_flood_info(blok_hip_ctx* ctx, blok_flood_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_info: no snapshot (blok_hip_volume_flood_field)");
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_info: null output");
+    *out_info = ctx->flood.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_flood_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_download: no snapshot (blok_hip_volume_flood_field)");
+    const blok_flood_info& info = ctx->flood.info;
+    const uint64_t n = static_cast<uint64_t>(info.ext[0]) * info.ext[1] * info.ext[2];
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_download: range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->flood.d_field + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_volume_flood_counters(blok_hip_ctx* ctx, uint64_t out_counts[2]) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_counters: no snapshot (blok_hip_volume_flood_field)");
+    if (!out_counts) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_counters: null output");
+    out_counts[0] = ctx->flood.rounds; out_counts[1] = ctx->flood.visits;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_edit_by_flood(blok_hip_ctx* ctx, int op, uint32_t d, float density, uint32_t material, uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "edit_by_flood: no snapshot (blok_hip_volume_flood_field)");
+    if (const int rule = blok::flood::check_edit_args(ctx->flood.info, op, d, density))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("edit_by_flood: ") + blok::flood::rule_text(rule));
+    std::string why;
+    uint64_t n_voxels = 0;
+    // (the snapshot's region lies in the box: a new volume drops the snapshot)
+    const blok::GpuBuildStatus st = blok::gpu_volume_edit_by_flood(&ctx->volume, &ctx->flood, op, d, density, material, &n_voxels, &why);
     if (out_n_voxels) *out_n_voxels = n_voxels;
     return volume_status(ctx, st, why);
 }

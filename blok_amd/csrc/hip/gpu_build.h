@@ -21,7 +21,7 @@ struct GpuTree {
     bool owned_by_volume = false;    // the arrays belong to a GpuVolume's scratch (never freed by the holder)
 };
 
-enum class GpuBuildStatus { Ok, UseHostBuilder, Unsupported, HipError, OutOfMemory };
+enum class GpuBuildStatus { Ok, UseHostBuilder, Unsupported, HipError, OutOfMemory, Internal };
 
 // UseHostBuilder: the world is valid but outside what the kernels cover (empty, sub-chunks smaller than a brick or of
 // mixed sizes, overlapping sub-chunks); the caller then takes the general host path (tree_build.cpp).
@@ -198,6 +198,26 @@ GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3
 // Writes the store, then refreshes the region as every edit does.  Blocking.
 GpuBuildStatus gpu_volume_edit_by_distance(GpuVolume* v, const GpuDistance* field, int op, uint32_t d2, float density, uint32_t material,
                                            uint64_t* out_n_voxels, std::string* why);
+// ---- the flood from seeds (include/blok_hip.h: blok_hip_volume_flood_field; flood_kernels.hip) ----
+// A field in device memory, owned by the holder: one value per region cell, x fastest, and the info that counts them.  rounds and visits
+// say how the device got there (launches over a non-empty list, bricks taken off the lists): diagnostics, never part of the info.
+struct GpuFlood {
+    uint16_t* d_field = nullptr;
+    blok_flood_info info = {};
+    uint32_t lo[3] = {0, 0, 0};                  // the region's corner, box-local
+    uint64_t rounds = 0, visits = 0;
+};
+void gpu_flood_free(GpuFlood* f);
+// The field of the box-local region [lo, hi) from n_seeds world cells inside it (host memory) and the SEED_FACE bits; the arguments have
+// passed flood::check_field_args.  Reads the brick masks (which every edit leaves equal to density > 0), with SAME_MATERIAL the store.
+// Changes nothing; *out is a new snapshot, the caller's to free (d_field null when the region has no cell).  Blocking.  Internal: the
+// rounds did not end within max_steps + 2.
+GpuBuildStatus gpu_volume_flood_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], const int32_t* seeds_xyz, uint64_t n_seeds,
+                                      uint32_t max_steps, uint32_t flags, uint32_t material, GpuFlood* out, std::string* why);
+// = blok_hip_volume_edit_by_flood over the snapshot's region (inside the box); the arguments have passed flood::check_edit_args.
+// Writes the store, then refreshes the region as every edit does.  Blocking.
+GpuBuildStatus gpu_volume_edit_by_flood(GpuVolume* v, const GpuFlood* field, int op, uint32_t d, float density, uint32_t material,
+                                        uint64_t* out_n_voxels, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

@@ -310,6 +310,57 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_edit_by_distance(self._ctx, int(op), int(d2), float(density), int(material), C.byref(n)))
         return int(n.value)
 
+    def volume_flood_field(self, lo=None, hi=None, seeds=None, max_steps: int = _ffi.FLOOD_MAX_STEPS, flags: int = 0, material: int = 0) -> np.ndarray:
+        """Floods a region of the resident volume (world voxels, half open; both None = the whole box) from the world cells `seeds`
+        ([n][3]) and, with flag bits _ffi.flood_seed_face(f), from the passable cells of the region's side f, through the empty cells —
+        _ffi.FLOOD_THROUGH_FILLED: through the filled ones, with _ffi.FLOOD_SAME_MATERIAL only those whose id is `material` — and keeps
+        the least number of 6-neighbour steps to every cell, capped at max_steps, on the device (blok_hip.h: blok_hip_volume_flood_field)
+        until the next flood.  Returns the field's info, one _ffi.FLOOD_INFO record; volume_flood_download fetches the values,
+        volume_edit_by_flood thresholds them."""
+        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
+        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        xyz = np.zeros((0, 3), np.int32) if seeds is None else np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        info = np.zeros(1, dtype=_ffi.FLOOD_INFO)
+        self._check(self._lib.blok_hip_volume_flood_field(self._ctx, rlo, rhi, _ffi.ptr(xyz) if len(xyz) else None, len(xyz), int(max_steps), int(flags),
+                                                          int(material), _ffi.ptr(info)))
+        return info
+
+    def volume_flood_info(self) -> np.ndarray:
+        info = np.zeros(1, dtype=_ffi.FLOOD_INFO)
+        self._check(self._lib.blok_hip_volume_flood_info(self._ctx, _ffi.ptr(info)))
+        return info
+
+    def volume_flood_counters(self):
+        """Diagnostic (blok_hip_debug.h): (rounds run, bricks taken off the lists) of the last flood.  Scheduling-dependent."""
+        out = (C.c_uint64 * 2)()
+        self._check(self._lib.blok_hip_volume_flood_counters(self._ctx, out))
+        return int(out[0]), int(out[1])
+
+    def volume_flood_download(self, first=None, count=None, page: int = 1 << 24) -> np.ndarray:
+        """The last flood's values (uint16, _ffi.FLOOD_FAR = not reached or impassable), fetched `page` cells at a time: cells
+        [first, first + count) in region index order, or with both None the whole field shaped [z][y][x]."""
+        whole = first is None and count is None
+        if whole:
+            ext = self.volume_flood_info()["ext"][0]
+            first, count = 0, int(ext[0]) * int(ext[1]) * int(ext[2])
+        first, count = int(first or 0), int(count or 0)
+        out = np.zeros(count, dtype=np.uint16)
+        if count == 0:
+            self._check(self._lib.blok_hip_volume_flood_download(self._ctx, None, first, 0))
+        for at in range(0, count, int(page)):
+            n = min(int(page), count - at)
+            self._check(self._lib.blok_hip_volume_flood_download(self._ctx, _ffi.ptr(out[at:at + n]), first + at, n))
+        return out.reshape(int(ext[2]), int(ext[1]), int(ext[0])) if whole else out
+
+    def volume_edit_by_flood(self, op: int, d: int = 0, density: float = 1.0, material: int = 0) -> int:
+        """Thresholds the last flood at d steps over its region (blok_hip.h: blok_hip_volume_edit_by_flood): op _ffi.FLOOD_FILL fills the
+        empty cells within d steps with (density, material), FLOOD_FILL_UNREACHED the empty cells the flood did not reach, FLOOD_PAINT
+        gives the filled cells within d steps the id `material`, FLOOD_CLEAR clears them.  Returns the number of cells written; the next
+        volume_rebuild installs the world."""
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_edit_by_flood(self._ctx, int(op), int(d), float(density), int(material), C.byref(n)))
+        return int(n.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

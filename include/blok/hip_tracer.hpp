@@ -355,6 +355,31 @@ public:
         check(blok_hip_volume_edit_by_distance(m_ctx, op, d2, density, material, &written));
         return written;
     }
+    // The flood of a region of the resident volume (world voxels, half-open; both null = the whole box) from the world cells `seeds`
+    // (x, y, z each) and the sides named by BLOK_FLOOD_SEED_FACE bits in `flags`, through the empty cells — BLOK_FLOOD_THROUGH_FILLED: the
+    // filled ones, with BLOK_FLOOD_SAME_MATERIAL those of id `material` — as the least number of 6-neighbour steps, capped at maxSteps, kept
+    // on the device until the next flood (blok_hip_volume_flood_field): returns what it holds.  downloadFlood fetches the values `page`
+    // cells at a time, x fastest; editByFlood thresholds them at d steps (BLOK_FLOOD_FILL / _FILL_UNREACHED / _PAINT / _CLEAR) and returns
+    // the cells written.
+    blok_flood_info floodField(const int32_t* regionLo, const int32_t* regionHi, const std::vector<int32_t>& seeds, uint32_t maxSteps = BLOK_FLOOD_MAX_STEPS,
+                               uint32_t flags = 0, uint32_t material = 0) {
+        blok_flood_info info{};
+        check(blok_hip_volume_flood_field(m_ctx, regionLo, regionHi, seeds.empty() ? nullptr : seeds.data(), seeds.size() / 3, maxSteps, flags, material, &info));
+        return info;
+    }
+    std::vector<uint16_t> downloadFlood(uint64_t page = uint64_t(1) << 24) {
+        blok_flood_info info{};
+        check(blok_hip_volume_flood_info(m_ctx, &info));
+        const uint64_t n = uint64_t(info.ext[0]) * info.ext[1] * info.ext[2];
+        std::vector<uint16_t> out(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_flood_download(m_ctx, out.data() + at, at, std::min(page, n - at)));
+        return out;
+    }
+    uint64_t editByFlood(int op, uint32_t d = 0, float density = 1.0f, uint32_t material = 0) {
+        uint64_t written = 0;
+        check(blok_hip_volume_edit_by_flood(m_ctx, op, d, density, material, &written));
+        return written;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -103,7 +103,8 @@ typedef enum blok_status {
     BLOK_ERR_HIP         = -3, /* a HIP call failed; message has the call and code */
     BLOK_ERR_NO_WORLD    = -4, /* trace before upload */
     BLOK_ERR_UNSUPPORTED = -5, /* world not on the unit-voxel integer lattice, leaf above voxel level, ... */
-    BLOK_ERR_OOM         = -6
+    BLOK_ERR_OOM         = -6,
+    BLOK_ERR_INTERNAL    = -7  /* a bound the library proves for itself did not hold: a defect of the library, never of the caller */
 } blok_status;
 
 /* Reference constants of the primary trace (reference assets/shaders/raygen.rgen:225,227). */
@@ -572,7 +573,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.8: connected components of the resident volume, one of them captured as a model.
  * 1.9: placed models swept against the resident volume (overlap, free travel along an axis).
  * 1.10: the resident volume saved, restored and undone as a sparse brick stream.
- * 1.11: the capped squared distance field of the resident volume; grow, shrink and hollow by it. */
+ * 1.11: the capped squared distance field of the resident volume; grow, shrink and hollow by it.
+ * 1.12: the step field of the resident volume flooded from seeds; fill, seal, paint and clear by it. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -945,6 +947,79 @@ int blok_hip_volume_distance_field(blok_hip_ctx* ctx, const int32_t region_lo[3]
 int blok_hip_volume_distance_info(blok_hip_ctx* ctx, blok_distance_info* out_info);
 int blok_hip_volume_distance_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count);
 int blok_hip_volume_edit_by_distance(blok_hip_ctx* ctx, int op, uint32_t d2, float density, uint32_t material, uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- the flood of the resident volume from seeds (ABI 1.12)
+ * Reachability through the volume: the least number of 6-neighbour steps from a seed set to every cell through passable cells, capped, as
+ * a snapshot in HBM, and the four edits that threshold it — fill (pour, plug), seal what the flood did not reach, paint and clear what it
+ * did.  A pure integer function of density > 0 and, with BLOK_FLOOD_SAME_MATERIAL, of the material ids: one right answer, bit-identical
+ * on the host (blok_flood_field / blok_flood_edit, blok_world.h) and on the device.  All calls block.
+ *  - Cell state.  Inside the volume's box a cell is filled iff density > 0; zero, negative and NaN densities are empty.
+ *  - Region: world voxels, half open; both pointers NULL = the whole box.  A cell outside the region is impassable: a path never leaves
+ *    the region.
+ *  - Passable cells.  By default the region cells that are empty; with BLOK_FLOOD_THROUGH_FILLED the filled ones; with
+ *    BLOK_FLOOD_SAME_MATERIAL (legal only together with THROUGH_FILLED) the filled ones whose material id equals `material`.  Without
+ *    SAME_MATERIAL `material` is ignored.
+ *  - Seeds.  The n_seeds world cells seeds_xyz_host[3 i ..], and with flag bit BLOK_FLOOD_SEED_FACE(f) every passable cell of the
+ *    region's outermost layer on side f (blok_hit::face numbering: 0 +X, 1 -X, 2 +Y, 3 -Y, 4 +Z, 5 -Z).  A listed seed that is not
+ *    passable is ignored; duplicates are harmless.  A listed seed outside the region is BLOK_ERR_INVALID_ARG, the message names the first
+ *    one, and nothing changes.  No seed at all is BLOK_OK with every value FAR.
+ *  - Value.  K = max_steps lies in 0 .. 65534.  D(c) is the length of the shortest chain of passable cells from a seed to c, consecutive
+ *    cells differing by one in exactly one coordinate.  The value of c is D(c) if that is at most K, and BLOK_FLOOD_FAR (0xFFFF)
+ *    otherwise; impassable cells hold FAR.  D(c) == 0 iff c is a passable seed.
+ *  - Snapshot: one uint16_t per region cell, x fastest, then y, then z, in device memory, owned by the context beside the distance
+ *    snapshot and with the same life: later edits do not touch it; the next flood replaces it; blok_hip_volume_destroy, a new
+ *    blok_hip_volume_create and blok_hip_destroy free it.  Taking it changes nothing in the volume and nothing in the quads, components,
+ *    bricks and distance snapshots.  The result is the same in the keyed and the row-major brick layout.  out_info may be NULL.
+ *  - Info: farthest is the largest value that is not FAR, or 0; n_seed counts the cells with D == 0, n_reached those with 0 < D <= K,
+ *    n_unreached the passable cells that hold FAR.  farthest < max_steps proves that the flood ended on its own and not at the cap: a
+ *    passable cell with FAR next to a reached one would have taken farthest + 1 <= max_steps at the most.  Then n_unreached counts
+ *    exactly the passable cells no chain reaches, which is what BLOK_FLOOD_FILL_UNREACHED relies on to seal cavities and nothing else.
+ *    Nothing in the info depends on how the device scheduled the work.
+ *  - blok_hip_volume_flood_download copies cells [first, first + count); blok_hip_volume_flood_info returns the snapshot's info.
+ *  - blok_hip_volume_edit_by_flood works over the snapshot's region and judges each cell by the volume as it is NOW (the rule of
+ *    blok_hip_volume_edit_by_distance); the snapshot is not updated by an edit.
+ *      BLOK_FLOOD_FILL: needs a through-empty field; every region cell with D <= d that is empty now gets (density, material): water up
+ *        to the region's top, or a plug.
+ *      BLOK_FLOOD_FILL_UNREACHED: needs a through-empty field; every region cell with FAR that is empty now gets (density, material);
+ *        d is ignored.  After a flood from the six faces that ended on its own this seals the cavities.
+ *      BLOK_FLOOD_PAINT: needs a THROUGH_FILLED field; every region cell with D <= d that is filled now gets the id `material`; its
+ *        density is untouched.
+ *      BLOK_FLOOD_CLEAR: needs a THROUGH_FILLED field; every region cell with D <= d that is filled now gets (0.0f, 0).
+ *    d <= max_steps of the snapshot is required (FILL_UNREACHED ignores d).  *out_n_voxels (may be NULL) is the number of cells written.
+ *  - After an edit masks, occupancy words, dirty flags and the edited box are those blok_hip_volume_set_voxels leaves for the same writes,
+ *    refreshed over the snapshot's region; PAINT changes no mask and still marks the bricks it wrote dirty, so the next rebuild gathers
+ *    the new ids; the FILL ops count as writes that may have filled voxels.
+ *  - Errors, each leaving the volume and the previous snapshot as they were.  BLOK_ERR_INVALID_ARG: unknown flag bits, SAME_MATERIAL
+ *    without THROUGH_FILLED, max_steps > 65534, exactly one region pointer NULL, lo > hi on an axis, a NULL seed array with n_seeds > 0,
+ *    a listed seed outside the region, no snapshot (info, download and edit), a download range past the end, a NULL array with
+ *    count > 0, an unknown op, an op on the wrong kind of field, d above the snapshot's max_steps, for the FILL ops a density that is not
+ *    finite or <= 0.  BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume above 2^32 cells.  BLOK_ERR_NO_WORLD: no volume.
+ *    BLOK_ERR_OOM: a failed device allocation.  BLOK_ERR_INTERNAL: the flood did not end within max_steps + 2 rounds, the bound
+ *    DESIGN.md §20 proves (the library stops there and never loops further).  An empty region is BLOK_OK with zero counts and an empty
+ *    snapshot; every edit on an empty snapshot writes nothing. */
+#define BLOK_FLOOD_THROUGH_FILLED 1u    /* the passable cells are the filled ones (default: the empty ones) */
+#define BLOK_FLOOD_SAME_MATERIAL  2u    /* ... and only those whose id equals `material`; needs THROUGH_FILLED */
+#define BLOK_FLOOD_SEED_FACE(f) (1u << (8 + (f)))      /* every passable cell of the region's outermost layer on side f (0..5) is a seed */
+#define BLOK_FLOOD_FAR 0xFFFFu          /* not reached within max_steps, or impassable */
+#define BLOK_FLOOD_MAX_STEPS 65534u
+#define BLOK_FLOOD_FILL           0
+#define BLOK_FLOOD_FILL_UNREACHED 1
+#define BLOK_FLOOD_PAINT          2
+#define BLOK_FLOOD_CLEAR          3
+typedef struct blok_flood_info {
+    uint32_t version;      /* 1 */
+    uint32_t flags;        /* the field's flags */
+    int32_t  lo[3];        /* the region, world voxels */
+    uint32_t ext[3];
+    uint32_t max_steps;    /* K */
+    uint32_t farthest;     /* the largest value that is not FAR, or 0 */
+    uint64_t n_seed, n_reached, n_unreached;      /* region cells with D == 0, with 0 < D <= K, passable ones with FAR */
+} blok_flood_info;         /* 64 bytes */
+int blok_hip_volume_flood_field(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], const int32_t* seeds_xyz_host,
+                                uint64_t n_seeds, uint32_t max_steps, uint32_t flags, uint32_t material, blok_flood_info* out_info);
+int blok_hip_volume_flood_info(blok_hip_ctx* ctx, blok_flood_info* out_info);
+int blok_hip_volume_flood_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count);
+int blok_hip_volume_edit_by_flood(blok_hip_ctx* ctx, int op, uint32_t d, float density, uint32_t material, uint64_t* out_n_voxels);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -37,6 +37,10 @@ int blok_hip_set_volume_layout(blok_hip_ctx* ctx, int keyed);
  * occupancy words above it in one workgroup — [1] keyed layout, the path of a range of more than 65 536 bricks or 4096 level-2 cells —
  * a lane per brick, a launch per level — [2] general layout.  Every path computes the same masks (tests/test_volume_rebuild_gpu.py). */
 int blok_hip_volume_refresh_counts(blok_hip_ctx* ctx, uint64_t out_counts[3]);
+/* Diagnostic: how the device reached the last flood snapshot (blok_hip_volume_flood_field): out_counts[0] = the rounds run (launches over a
+ * non-empty list of active bricks), [1] = the bricks taken off those lists, summed.  Both depend on how the device scheduled the waves,
+ * which is why neither is part of blok_flood_info.  BLOK_ERR_INVALID_ARG without a snapshot. */
+int blok_hip_volume_flood_counters(blok_hip_ctx* ctx, uint64_t out_counts[2]);
 
 /* ------------------------------------------------------------ path kernel */
 /* Scheduling knob of the path kernel (no reference counterpart): 0 = every lane walks whatever ray it has pending; 1 = a wave walks

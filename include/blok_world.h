@@ -259,6 +259,21 @@ int blok_distance_field(const float* density, const int32_t origin[3], uint32_t 
 int blok_distance_edit(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const uint16_t* field,
                        const blok_distance_info* info, int op, uint32_t d2, float density_value, uint32_t material, uint64_t* out_n_voxels);
 
+/* -------------------------------------------------------------- the flood from seeds on the host (flood.cpp)
+ * The contracts of blok_hip_volume_flood_field and blok_hip_volume_edit_by_flood (blok_hip.h; blok_flood_info, the flags and the ops are
+ * declared there) over host arrays of a box as above, through the rules the kernels use.  The field is a plain queue BFS: the definition.
+ * field: the region and the seeds are in world voxels; material_ids may be NULL without BLOK_FLOOD_SAME_MATERIAL; out_field takes one value
+ * per region cell, x fastest, and *out_info (may be NULL) what the device's info holds.  Errors as the device entry; a NULL array with a
+ * non-empty region is BLOK_ERR_INVALID_ARG.
+ * edit: applies `op` at the threshold d to the two arrays from a field and its info, judged against the arrays as they are; *out_n_voxels
+ * (may be NULL) is the number of cells written.  Errors as the device entry; an info whose version is not 1 is BLOK_ERR_INVALID_ARG, one
+ * whose region leaves the box BLOK_ERR_UNSUPPORTED.  Nothing is written on an error. */
+int blok_flood_field(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                     const int32_t region_lo[3], const int32_t region_hi[3], const int32_t* seeds_xyz, uint64_t n_seeds, uint32_t max_steps,
+                     uint32_t flags, uint32_t material, uint16_t* out_field, blok_flood_info* out_info);
+int blok_flood_edit(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const uint16_t* field,
+                    const blok_flood_info* info, int op, uint32_t d, float density_value, uint32_t material, uint64_t* out_n_voxels);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

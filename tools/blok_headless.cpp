@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--hollow D2]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -25,6 +25,10 @@
 //   --hollow D2: with --terrain, --obj or --load-volume, once the volume is filled and before it is rebuilt: the to-empty distance field of the
 //          whole box with R = ceil(sqrt(D2)) (blok_hip_volume_distance_field), then BLOK_DISTANCE_HOLLOW at D2: only the shell within D2
 //          (a squared distance) of empty space stays.  D2 >= 3 keeps every cell a primary ray can enter, so the frames do not change
+//   --seal: with --terrain, --obj or --load-volume, once the volume is filled and before it is rebuilt: the empty cells of the whole box are
+//          flooded from all six faces with max_steps 65534 (blok_hip_volume_flood_field), then BLOK_FLOOD_FILL_UNREACHED fills every empty
+//          cell the air did not reach with material 0, or --seal-material N: an openly voxelized shell becomes solid, caves no one can
+//          enter are closed.  No primary ray enters a sealed cell
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -59,6 +63,8 @@ struct Options {
     std::string export_obj;               // write the resident volume's surface here
     bool components = false;              // label the resident volume's connected components and print their counts
     bool settle = false;                  // let the components that do not touch the floor fall
+    bool seal = false;                    // fill the empty cells that air from the box's faces does not reach, before the rebuild
+    uint32_t seal_material = 0;
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
@@ -86,6 +92,7 @@ private:
                 if (m_opt.settle) throw std::runtime_error("--settle needs a resident volume: --terrain or --obj");
                 if (!m_opt.save_volume.empty()) throw std::runtime_error("--save-volume needs a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.hollow >= 0) throw std::runtime_error("--hollow needs a resident volume: --terrain, --obj or --load-volume");
+                if (m_opt.seal) throw std::runtime_error("--seal needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -188,6 +195,7 @@ private:
             const uint64_t written = m_tracer->voxelizeMesh(pos, tri, mat, 1, 1.0f, m_opt.solid);
             std::cout << "mesh: " << nv << " vertices, " << nt << " triangles -> " << written << " voxels written on the ground at y = " << ground << "\n";
         }
+        seal();
         hollow();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
@@ -211,6 +219,7 @@ private:
         const blok_terrain_params p = terrainParams(N);
         m_tracer->createVolume(s.info.lo, ext[0], ext[1], ext[2]);
         m_tracer->decodeBricks(s);
+        seal();
         hollow();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats w = m_tracer->worldStats();
@@ -230,6 +239,14 @@ private:
         for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a]; }
         m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
         m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
+    }
+    // Every empty cell that air from the box's six faces cannot reach is filled: the through-empty flood of the whole box, uncapped in effect.
+    void seal() {
+        if (!m_opt.seal) return;
+        const uint32_t faces = BLOK_FLOOD_SEED_FACE(0) | BLOK_FLOOD_SEED_FACE(1) | BLOK_FLOOD_SEED_FACE(2) | BLOK_FLOOD_SEED_FACE(3) | BLOK_FLOOD_SEED_FACE(4) | BLOK_FLOOD_SEED_FACE(5);
+        const blok_flood_info info = m_tracer->floodField(nullptr, nullptr, {}, BLOK_FLOOD_MAX_STEPS, faces);
+        const uint64_t filled = m_tracer->editByFlood(BLOK_FLOOD_FILL_UNREACHED, 0, 1.0f, m_opt.seal_material);
+        std::cout << "seal: " << filled << " voxels filled, farthest " << info.farthest << "\n";
     }
     // Only the shell within the squared distance --hollow of empty space stays: the to-empty field of the whole box, thresholded.
     void hollow() {
@@ -275,6 +292,7 @@ private:
         const int32_t origin[3] = {0, 0, 0};
         m_tracer->createVolume(origin, m_opt.obj_size, m_opt.obj_size, m_opt.obj_size);
         const uint64_t written = m_tracer->voxelizeMesh(pos, tri, mat, 1, 1.0f, m_opt.solid);
+        seal();
         hollow();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
@@ -405,6 +423,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--export-obj")) opt.export_obj = next();
         else if (!std::strcmp(argv[i], "--components")) opt.components = true;
         else if (!std::strcmp(argv[i], "--settle")) opt.settle = true;
+        else if (!std::strcmp(argv[i], "--seal")) opt.seal = true;
+        else if (!std::strcmp(argv[i], "--seal-material")) opt.seal_material = static_cast<uint32_t>(std::atoll(next()));
         else if (!std::strcmp(argv[i], "--hollow")) { opt.hollow = std::atoll(next()); if (opt.hollow < 0 || opt.hollow > 65025) { std::fprintf(stderr, "--hollow takes a squared distance in 0..65025\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
