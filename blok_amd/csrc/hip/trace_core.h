@@ -66,13 +66,48 @@ struct NodeRec { uint32_t lo, hi, base; };
 
 BLOK_DEV bool mask_bit(const NodeRec& n, uint32_t bit) {
     const uint32_t word = bit < 32u ? n.lo : n.hi;
+#ifdef BLOK_TRACE_HOST_HARNESS
     return (word >> (bit & 31u)) & 1u;
+#else
+    return __builtin_amdgcn_ubfe(word, bit, 1u);      // the same bit as a one-bit field (v_bfe_u32 reads the low five bits of its offset: bit & 31)
+#endif
 }
 BLOK_DEV uint32_t mask_rank(const NodeRec& n, uint32_t bit) {
     // number of set bits below `bit`
     const uint32_t below_lo = bit < 32u ? (n.lo & ((1u << bit) - 1u)) : n.lo;
     const uint32_t below_hi = bit < 32u ? 0u : (n.hi & ((1u << (bit & 31u)) - 1u));
     return __popc(below_lo) + __popc(below_hi);
+}
+
+// Keeps a per-lane value out of the optimiser's sight (an empty statement on the value's register): what is computed from it afterwards is
+// computed the way the source says.  The host form has nothing to hide anything from.
+BLOK_DEV float as_written(float x) {
+#ifndef BLOK_TRACE_HOST_HARNESS
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+BLOK_DEV uint32_t as_written(uint32_t x) {
+#ifndef BLOK_TRACE_HOST_HARNESS
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+
+// n.base + mask_rank(n, bit): the index of child (or voxel) `bit` among the node's.  The same number as that sum, formed in fewer instructions:
+//  * the bits below `bit` are a bit-field extract of width `bit` from the low word (bit < 32; the whole word otherwise) and of width
+//    max(bit, 32) - 32 from the high word (a saturating subtraction; width 0 extracts 0): the two masked words of mask_rank;
+//  * v_bcnt_u32_b32 d, s, acc adds its count to acc, so the sum is two instructions when the first count accumulates onto base and the
+//    second onto that; left to itself the compiler counts twice into zero and joins the three terms with a half-rate v_add3.  Unsigned
+//    addition is associative and commutative modulo 2^32: the same number in either grouping.
+BLOK_DEV uint32_t child_index(const NodeRec& n, uint32_t bit) {
+#ifdef BLOK_TRACE_HOST_HARNESS
+    return n.base + mask_rank(n, bit);
+#else
+    const uint32_t below_lo = bit < 32u ? __builtin_amdgcn_ubfe(n.lo, 0u, bit) : n.lo;
+    const uint32_t below_hi = __builtin_amdgcn_ubfe(n.hi, 0u, __builtin_elementwise_sub_sat(bit, 32u));
+    return as_written(n.base + __popc(below_lo)) + __popc(below_hi);
+#endif
 }
 
 struct RayIn { float ox, oy, oz, dx, dy, dz, tmin, tmax; };
@@ -118,6 +153,8 @@ BLOK_DEV float plane_t(const Axis& a, float f) {
 
 // Cell size 4^lvl as a float: 2^(2 lvl).
 BLOK_DEV float cell_size(uint32_t lvl) { return __uint_as_float(0x3F800000u + (lvl << 24)); }
+// The same from the digit offset 2 lvl that walk_loop carries: (2 lvl) << 23 == lvl << 24.
+BLOK_DEV float cell_size_of_shift(uint32_t shift) { return __uint_as_float(0x3F800000u + (shift << 23)); }
 
 // One axis of "enter a node" whose near corner is f and whose children have size s: how many of the three
 // interior planes have T <= tS (binary search, T is monotone in q), i.e. which child slab holds the ray at tS; f advances to
@@ -134,11 +171,15 @@ BLOK_DEV float cell_size(uint32_t lvl) { return __uint_as_float(0x3F800000u + (l
 // Every coordinate is an integer inside the 2^23 mantissa field, so each sum is exact and the float argument of plane_t is the same
 // number either way: the same bits.  So walk_loop evaluates the far planes once at the bottom of a trip for the descend path and the
 // step path alike, instead of choosing among three candidates with selects on the descend path.
+//
+// The advanced corner is the probed one: f + s2 is formed for plane_t anyway, and  g ? f + s2 : f  is the number  f + (g ? s2 : 0)  (an exact sum
+// either way, and f + 0 = f for the positive f here) for one select instead of a select and an add.  The compiler turns select(g, f + s2, f)
+// back into f + select(g, s2, 0) when it sees the sum, hence as_written.
 BLOK_DEV void enter_axis(const Axis& a, float& f, float s, float s2, float tS) {
-    const bool g = plane_t(a, f + s2) <= tS;
-    f += g ? s2 : 0.0f;
-    const bool g2 = plane_t(a, f + s) <= tS;
-    f += g2 ? s : 0.0f;
+    const float p = as_written(f + s2);
+    f = plane_t(a, p) <= tS ? p : f;
+    const float p2 = as_written(f + s);
+    f = plane_t(a, p2) <= tS ? p2 : f;
 }
 
 // What closest-hit sees of a procedural hit (intersect.rint:138-141, hit.rchit:58-74), in registers.
@@ -211,31 +252,37 @@ BLOK_DEV void walk_enter(const TraceArgs& A, const WalkRay& R, float tmin, float
 // interval, every one after it is entered at or after tCur: the argument of the beam pre-pass).  path_core.h: the bounce rounds' tail pool.
 template <bool kCapped = false>
 BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, WalkState& s, uint4* stk, [[maybe_unused]] const uint32_t cap = 0u) {
-    const uint32_t L = A.levels;
     // Invariant: tCur starts at max(world entry, tmin) and never decreases — a cell's far planes are never
     // before the plane through which it was entered (T is monotone along each axis and the start cell of a
     // node only counts planes with T <= tCur as crossed) — so max(tCur, tmin) == tCur throughout and the
     // reported t of a voxel, max(entry, tmin), is tCur itself.
     float fx = s.fx, fy = s.fy, fz = s.fz, tFx = s.tFx, tFy = s.tFy, tFz = s.tFz, tCur = s.tCur, size = s.size;
-    uint32_t lvl = s.lvl, bit = s.bit;
+    uint32_t bit = s.bit;
     NodeRec node = s.node;
+    // The level is carried as the digit offset  shift = 2 lvl  that every trip's top needs: the cell size is 2^shift, the stack slot of
+    // the level's parent (lvl - 1) * kBlock = (shift - 2) * (kBlock / 2), the level of a crossed boundary  2 * (ffbl >> 1) = ffbl & ~1,
+    // and the world is left at shift 2 L.  The same integers, without a doubling per trip.
+    static_assert(kBlock % 2 == 0, "the stack slot is formed from twice the level");
+    uint32_t shift = 2u * s.lvl;
+    const uint32_t top_shift = 2u * A.levels;
     bool found = false;
-    const bool walking = s.walking;
+    // `go`: this lane has another trip to make.  It is decided where the walk ends — a voxel is reported, the interval ends, the world is
+    // left — and is all the loop tests: a lane that stops keeps the state it stopped in (a reported voxel's cell, node, bit and tCur; a
+    // lane whose walk ends without a report leaves nothing that is read).
+    bool go = s.walking;
     [[maybe_unused]] uint32_t trips = 0u;
-    [[maybe_unused]] bool cut = false;
-    while (walking) {
-        if constexpr (kCapped) { if (trips >= cap) { cut = true; break; } ++trips; }
-        BLOK_STAT(0, lvl);
-        const uint32_t shift = 2 * lvl;
+    while (kCapped ? (go && trips < cap) : go) {
+        if constexpr (kCapped) ++trips;
+        BLOK_STAT(0, shift >> 1);
         bit = (digit2(__float_as_uint(fx), shift) | (digit2(__float_as_uint(fy), shift) << 2) | (digit2(__float_as_uint(fz), shift) << 4)) ^ R.mirror;
         const bool occupied = mask_bit(node, bit);
-        if (occupied && lvl != 0) {
+        if (occupied && shift != 0u) {
             // descend: remember the node we are leaving, fetch the child, pick its start cell
-            BLOK_STAT(1, lvl);
-            stk[(lvl - 1) * kBlock] = make_uint4(node.lo, node.hi, node.base, 0u);     // node of level lvl+1
-            const uint4 c = A.nodes[node.base + mask_rank(node, bit)];
+            BLOK_STAT(1, shift >> 1);
+            stk[(shift - 2u) * (kBlock / 2u)] = make_uint4(node.lo, node.hi, node.base, 0u);     // node of level lvl+1
+            const uint4 c = A.nodes[child_index(node, bit)];
             node.lo = c.x; node.hi = c.y; node.base = c.z;
-            lvl -= 1;
+            shift -= 2u;
             size *= 0.25f;
             const float s2 = size + size;
             enter_axis(R.ax, fx, size, s2, tCur);     // tCur >= tmin always (see the invariant above the loop)
@@ -244,27 +291,35 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
         } else {
             const float tExit = fminf(fminf(tFx, tFy), tFz);
             // a filled voxel: reported iff its clipped interval is non-empty (intersect.rint:189-193)
-            if (occupied && tCur < fminf(tExit, tmax)) { found = true; break; }
-            // step: cross the nearest far plane (x, then y, then z on ties)
-            BLOK_STAT(2, lvl);
-            tCur = tExit;
-            if (!(tCur < tmax)) break;
-            const bool sx = tFx == tExit;
-            const bool sy = !sx && tFy == tExit;
-            const bool sz = !sx && !sy;
-            fx += sx ? size : 0.0f; fy += sy ? size : 0.0f; fz += sz ? size : 0.0f;
-            // the stepped coordinate is now a multiple of 4^k for the level k whose cell boundary was crossed (its mantissa
-            // field is q > 0, so the lowest set bit of the float's bits is the lowest set bit of q)
-            const uint32_t up = static_cast<uint32_t>(__ffs(static_cast<int>(__float_as_uint(sx ? fx : (sy ? fy : fz)))) - 1) >> 1;
-            if (up != lvl) {
-                BLOK_STAT(3, lvl);
-                if (up >= L) break;                                    // left the world box
-                lvl = up;
-                size = cell_size(lvl);
-                const uint32_t keep = ~((1u << (2 * up)) - 1u);        // clears mantissa bits only: the exponent field stays
-                fx = __uint_as_float(__float_as_uint(fx) & keep); fy = __uint_as_float(__float_as_uint(fy) & keep); fz = __uint_as_float(__float_as_uint(fz) & keep);
-                const uint4 c = stk[(lvl - 1) * kBlock];               // node of level lvl+1
-                node.lo = c.x; node.hi = c.y; node.base = c.z;
+            found = occupied && tCur < fminf(tExit, tmax);
+            // otherwise the walk goes on through the nearest far plane unless the interval ends there
+            go = !found && tExit < tmax;
+            if (go) {
+                // step: cross the nearest far plane (x, then y, then z on ties)
+                BLOK_STAT(2, shift >> 1);
+                tCur = tExit;
+                const bool sx = tFx == tExit;
+                const bool sy = !sx && tFy == tExit;
+                // One coordinate moves, so one sum: the stepped coordinate is picked, advanced, and put back where it came from.  Each of
+                // fx, fy, fz ends as  f + (its axis steps ? size : 0): f + size exactly for the axis that steps, f itself for the others.
+                const float stepped = as_written((sx ? fx : (sy ? fy : fz)) + size);
+                fx = sx ? stepped : fx; fy = sy ? stepped : fy; fz = (sx || sy) ? fz : stepped;
+                // the stepped coordinate is now a multiple of 4^k for the level k whose cell boundary was crossed (its mantissa
+                // field is q > 0, so the lowest set bit of the float's bits is the lowest set bit of q)
+                // (the exponent field is set: the bits are never 0, and counting trailing zeros needs no case for it)
+                const uint32_t up = static_cast<uint32_t>(__builtin_ctz(__float_as_uint(stepped))) & ~1u;
+                if (up != shift) {
+                    BLOK_STAT(3, shift >> 1);
+                    go = up < top_shift;                                   // not: left the world box
+                    if (go) {
+                        shift = up;
+                        size = cell_size_of_shift(shift);
+                        const uint32_t keep = ~((1u << up) - 1u);          // clears mantissa bits only: the exponent field stays
+                        fx = __uint_as_float(__float_as_uint(fx) & keep); fy = __uint_as_float(__float_as_uint(fy) & keep); fz = __uint_as_float(__float_as_uint(fz) & keep);
+                        const uint4 c = stk[(shift - 2u) * (kBlock / 2u)];     // node of level lvl+1
+                        node.lo = c.x; node.hi = c.y; node.base = c.z;
+                    }
+                }
             }
         }
         // the far planes of the cell the trip ends in, one evaluation for both paths (enter_axis: after a descent they are the planes the
@@ -272,7 +327,7 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
         tFx = plane_t(R.ax, fx + size); tFy = plane_t(R.ay, fy + size); tFz = plane_t(R.az, fz + size);
     }
     s.fx = fx; s.fy = fy; s.fz = fz; s.tCur = tCur; s.bit = bit; s.node = node; s.found = found;
-    if constexpr (kCapped) s.walking = cut; else s.walking = false;
+    if constexpr (kCapped) s.walking = go; else s.walking = false;
 }
 
 // The reported voxel of a finished walk: intersect.rint:136-141, hit.rchit:58-74.  r: the ray itself (origin, direction).
@@ -282,7 +337,7 @@ BLOK_DEV HitInfo walk_hit(const TraceArgs& A, const RayIn& r, const WalkRay& R, 
     const float vs = A.voxel_size;
     const bool negx = !(R.ax.inv > 0.0f), negy = !(R.ay.inv > 0.0f), negz = !(R.az.inv > 0.0f);
     const float tc = s.tCur;                                          // = max(entry, tmin), intersect.rint:189,141
-    const uint32_t material = A.materials[s.node.base + mask_rank(s.node, s.bit)];
+    const uint32_t material = A.materials[child_index(s.node, s.bit)];
     // world voxel = mirrored cell un-mirrored: base + sgn * q - (negative ? 1 : 0)
     const int qx = static_cast<int>(__float_as_uint(s.fx) & 0x7FFFFFu), qy = static_cast<int>(__float_as_uint(s.fy) & 0x7FFFFFu), qz = static_cast<int>(__float_as_uint(s.fz) & 0x7FFFFFu);
     const int vx = negx ? A.origin[0] + W - qx - 1 : A.origin[0] + qx;
@@ -413,9 +468,9 @@ BLOK_DEV bool walk_resume(const TraceArgs& A, const RayIn& r, const WalkRay& R, 
         if (!(tExit < r.tmax)) { s.walking = false; return true; }
         const bool sx = s.tFx == tExit;
         const bool sy = !sx && s.tFy == tExit;
-        const bool sz = !sx && !sy;
-        s.fx += sx ? s.size : 0.0f; s.fy += sy ? s.size : 0.0f; s.fz += sz ? s.size : 0.0f;
-        const uint32_t up = static_cast<uint32_t>(__ffs(static_cast<int>(__float_as_uint(sx ? s.fx : (sy ? s.fy : s.fz)))) - 1) >> 1;
+        const float stepped = as_written((sx ? s.fx : (sy ? s.fy : s.fz)) + s.size);      // one sum for the one coordinate that moves, as in walk_loop
+        s.fx = sx ? stepped : s.fx; s.fy = sy ? stepped : s.fy; s.fz = (sx || sy) ? s.fz : stepped;
+        const uint32_t up = static_cast<uint32_t>(__builtin_ctz(__float_as_uint(stepped))) >> 1;
         if (up != lvl) {
             BLOK_STAT(3, lvl);
             if (up >= L) { s.walking = false; return true; }      // left the world box

@@ -1,6 +1,6 @@
 """Condenses an interleaved A/B visit (two kernel libraries, "base" and "new") into profiles/r05_*: the bench lines (default and --full),
 rocprofv3 kernel statistics per library and the VALU counters per launch of the frame's kernels.
-usage: summarize_ab.py <dir with bench_*_N.json, full_*_N.json, trace_*/, pmc_*/>"""
+usage: summarize_ab.py <dir with bench_*_N.json, full_*_N.json, trace_*/, pmc_*/> [tag of the profiles/ files, default r05]"""
 import csv
 import json
 import statistics
@@ -11,6 +11,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
 src = Path(sys.argv[1])
 dst = ROOT / "profiles"
+TAG = sys.argv[2] if len(sys.argv) > 2 else "r05"
 KERNELS = ("joint_kernel<(blok::RayMode)0>", "trace_kernel<(blok::RayMode)0>", "beam_kernel<(blok::RayMode)0>")
 
 
@@ -46,7 +47,7 @@ if full:
 for v in ("base", "new"):
     stats = list((src / f"trace_{v}").glob("**/*kernel_stats.csv"))
     if stats:
-        (dst / f"r05_kernel_stats_{v}.csv").write_text(stats[0].read_text())
+        (dst / f"{TAG}_kernel_stats_{v}.csv").write_text(stats[0].read_text())
 pmc = {}
 for v in ("base", "new"):
     files = list((src / f"pmc_{v}").glob("**/*counter_collection.csv"))
@@ -67,7 +68,7 @@ for v in ("base", "new"):
                 a["lane_utilisation"] = a["SQ_THREAD_CYCLES_VALU"] / (64 * a["SQ_ACTIVE_INST_VALU"])
     pmc[v] = out
 if pmc:
-    (dst / "r05_pmc.json").write_text(json.dumps(pmc, indent=1) + "\n")
+    (dst / f"{TAG}_pmc.json").write_text(json.dumps(pmc, indent=1) + "\n")
     report.append("")
     report.append("rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU (default bench, 60 steps), mean per launch:")
     for k in KERNELS:
