@@ -390,11 +390,7 @@ void blok_hip_destroy(blok_hip_ctx* ctx) {
     if (ctx->d_frame) (void)hipFree(ctx->d_frame);
     free_post(ctx);
     if (ctx->has_volume) blok::gpu_volume_destroy(&ctx->volume);
-    if (ctx->d_quads) (void)hipFree(ctx->d_quads);
-    blok::gpu_components_free(&ctx->components);
-    blok::gpu_bricks_free(&ctx->bricks);
-    blok::gpu_distance_free(&ctx->distance);
-    blok::gpu_flood_free(&ctx->flood);
+    free_volume_snapshots(ctx);
     forget_device_activity(ctx);
     for (auto& kv : ctx->beam_buffers) free_stream_scratch(kv.second);
     if (ctx->d_list_cost) (void)hipFree(ctx->d_list_cost);

@@ -96,12 +96,13 @@ struct blok_hip_ctx {
     blok::GpuVolume volume;
     bool has_volume = false;
     bool volume_keyed_layout = true;   // blok_hip_set_volume_layout: the next blok_hip_volume_create may use the keyed brick layout (gpu_build.h)
-    // blok_hip_volume_extract_quads: the snapshot (quads_kernels.hip), replaced by the next extraction, freed with the volume
-    blok_quad* d_quads = nullptr; uint64_t n_quads = 0; bool has_quads = false;
-    blok::GpuComponents components; bool has_components = false;      // the snapshot of the last blok_hip_volume_label_components
-    blok::GpuBricks bricks; bool has_bricks = false;                  // the snapshot of the last blok_hip_volume_encode_bricks
-    blok::GpuDistance distance; bool has_distance = false;            // the snapshot of the last blok_hip_volume_distance_field
-    blok::GpuFlood flood; bool has_flood = false;                     // the snapshot of the last blok_hip_volume_flood_field
+    // the snapshots (gpu_build.h: each knows whether it was taken), each replaced by the next of its kind, all freed with the volume
+    // (free_volume_snapshots)
+    blok::GpuQuads quads;                // of the last blok_hip_volume_extract_quads
+    blok::GpuComponents components;      // of the last blok_hip_volume_label_components
+    blok::GpuBricks bricks;              // of the last blok_hip_volume_encode_bricks
+    blok::GpuDistance distance;          // of the last blok_hip_volume_distance_field
+    blok::GpuFlood flood;                // of the last blok_hip_volume_flood_field
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
     float* d_sun_map = nullptr;
@@ -245,6 +246,8 @@ int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream);
 int live_list(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_searches, uint32_t per_search);
 int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, uint32_t blocks, hipStream_t stream, uint32_t tiles_of_rank = 0,
                  const blok::TileFrames* frames = nullptr);
+// api_volume.hip: the one place the context's snapshots are freed (a new volume, a destroyed one, the context's end)
+void free_volume_snapshots(blok_hip_ctx* ctx);
 // api_instances.hip
 void free_models(blok_hip_ctx* ctx);
 // The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.

@@ -6,12 +6,23 @@
 #include "../common/bricks_core.h"
 #include "../common/distance_core.h"
 #include "../common/flood_core.h"
+#include "../common/region_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
 #include <limits>
 
 using namespace blok_api;
+
+namespace blok_api {
+void free_volume_snapshots(blok_hip_ctx* ctx) {
+    blok::gpu_quads_free(&ctx->quads);
+    blok::gpu_components_free(&ctx->components);
+    blok::gpu_bricks_free(&ctx->bricks);
+    blok::gpu_field_free(&ctx->distance);
+    blok::gpu_field_free(&ctx->flood);
+}
+}  // namespace blok_api
 
 extern "C" {
 
@@ -25,26 +36,6 @@ int volume_status(blok_hip_ctx* ctx, blok::GpuBuildStatus st, const std::string&
         case blok::GpuBuildStatus::Internal: return set_error(ctx, BLOK_ERR_INTERNAL, why);
         default: return set_error(ctx, BLOK_ERR_INVALID_ARG, why.empty() ? "volume operation not applicable" : why);
     }
-}
-void drop_quads(blok_hip_ctx* ctx) {
-    if (ctx->d_quads) (void)hipFree(ctx->d_quads);
-    ctx->d_quads = nullptr; ctx->n_quads = 0; ctx->has_quads = false;
-}
-void drop_components(blok_hip_ctx* ctx) {
-    blok::gpu_components_free(&ctx->components);
-    ctx->has_components = false;
-}
-void drop_bricks(blok_hip_ctx* ctx) {
-    blok::gpu_bricks_free(&ctx->bricks);
-    ctx->has_bricks = false;
-}
-void drop_distance(blok_hip_ctx* ctx) {
-    blok::gpu_distance_free(&ctx->distance);
-    ctx->has_distance = false;
-}
-void drop_flood(blok_hip_ctx* ctx) {
-    blok::gpu_flood_free(&ctx->flood);
-    ctx->has_flood = false;
 }
 int need_volume(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
@@ -65,16 +56,11 @@ std::vector<blok::StampModel> placed_models(const blok_hip_ctx* ctx, const blok_
 }
 // The box-local region [lo, hi) of an entry's world region_lo / region_hi (both null: the whole box), with the entry's name in the messages.
 int volume_region(blok_hip_ctx* ctx, const char* op, const int32_t* region_lo, const int32_t* region_hi, uint32_t lo[3], uint32_t hi[3]) {
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(op) + ": one region pointer is null");
+    static const char* const kText[] = {"", ": one region pointer is null", ": region_lo above region_hi", ": region leaves the resident volume"};
     const blok::GpuVolume& v = ctx->volume;
-    const int64_t dims[3] = {v.nx, v.ny, v.nz};
-    for (int a = 0; a < 3; ++a) {
-        const int64_t l = region_lo ? int64_t(region_lo[a]) - v.origin[a] : 0, h = region_hi ? int64_t(region_hi[a]) - v.origin[a] : dims[a];
-        if (l > h) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(op) + ": region_lo above region_hi");
-        if (l < 0 || h > dims[a]) return set_error(ctx, BLOK_ERR_UNSUPPORTED, std::string(op) + ": region leaves the resident volume");
-        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
-    }
-    return BLOK_OK;
+    const uint32_t dims[3] = {v.nx, v.ny, v.nz};
+    const int rule = blok::region::local(v.origin, dims, region_lo, region_hi, lo, hi);
+    return rule ? set_error(ctx, blok::region::status(rule), std::string(op) + kText[rule]) : BLOK_OK;
 }
 // A tree built on the device (gpu_volume_capture*) into the model store; box_lo / box_hi: the box of its voxels, model coordinates.
 int add_captured_model(blok_hip_ctx* ctx, const blok::GpuTree& tree, const int32_t box_lo[3], const int32_t box_hi[3], uint32_t* out_model) {
@@ -84,18 +70,39 @@ int add_captured_model(blok_hip_ctx* ctx, const blok::GpuTree& tree, const int32
     for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
     return add_model(ctx, m, out_model);
 }
+// Lets go of the present volume, if there is one, and of the world installed from its arrays (it lives in them: it goes with them).  strict:
+// a failing wait for the frames that still read that world is the call's failure, and nothing is freed.
+int release_volume(blok_hip_ctx* ctx, bool strict) {
+    if (!ctx->has_volume) return BLOK_OK;
+    if (ctx->tree_owned_by_volume) {
+        if (strict) BLOK_HIP_TRY(ctx, hipDeviceSynchronize()); else (void)hipDeviceSynchronize();
+        free_world(ctx);
+    }
+    blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false;
+    return BLOK_OK;
+}
+// Elements [first, first + count) of a snapshot's array of n elements of elem_bytes each, to host memory: the tail of every *_download entry
+// (`entry`, with the call that takes its snapshot in the message), behind its null-context check.
+int ranged_download(blok_hip_ctx* ctx, const char* entry, const char* taken_by, bool taken, uint64_t n, const void* base, size_t elem_bytes,
+                    void* out_host, uint64_t first, uint64_t count) {
+    if (!taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(entry) + ": no snapshot (" + taken_by + ")");
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(entry) + ": range past the end of the snapshot");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string(entry) + ": null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, static_cast<const char*>(base) + first * elem_bytes, count * elem_bytes, hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+uint64_t field_cells(const uint32_t ext[3]) { return static_cast<uint64_t>(ext[0]) * ext[1] * ext[2]; }
 }  // namespace
 
 int blok_hip_volume_create(blok_hip_ctx* ctx, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
                            uint32_t chunk_size, float voxel_size) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->has_volume) { if (ctx->tree_owned_by_volume) { BLOK_HIP_TRY(ctx, hipDeviceSynchronize()); free_world(ctx); } blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false; }
-    drop_quads(ctx);
-    drop_components(ctx);
-    drop_bricks(ctx);
-    drop_distance(ctx);
-    drop_flood(ctx);
+    const int rc = release_volume(ctx, true);
+    if (rc != BLOK_OK) return rc;
+    free_volume_snapshots(ctx);
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
     std::string why;
     const blok::GpuBuildStatus st = blok::gpu_volume_create(o, nx, ny, nz, chunk_size, voxel_size, &ctx->volume, &why, ctx->volume_keyed_layout);
@@ -119,16 +126,9 @@ int blok_hip_volume_refresh_counts(blok_hip_ctx* ctx, uint64_t out_counts[3]) {
 
 int blok_hip_volume_destroy(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (ctx->has_volume) {
-        (void)hipSetDevice(ctx->device);
-        if (ctx->tree_owned_by_volume) { (void)hipDeviceSynchronize(); free_world(ctx); }      // the installed world lives in the volume's arrays: it goes with them
-        blok::gpu_volume_destroy(&ctx->volume); ctx->has_volume = false;
-    }
-    drop_quads(ctx);
-    drop_components(ctx);
-    drop_bricks(ctx);
-    drop_distance(ctx);
-    drop_flood(ctx);
+    if (ctx->has_volume) (void)hipSetDevice(ctx->device);
+    (void)release_volume(ctx, false);
+    free_volume_snapshots(ctx);
     return BLOK_OK;
 }
 
@@ -206,29 +206,24 @@ int blok_hip_volume_extract_quads(blok_hip_ctx* ctx, const int32_t region_lo[3],
     rc = volume_region(ctx, "extract_quads", region_lo, region_hi, lo, hi);
     if (rc != BLOK_OK) return rc;
     std::string why;
-    blok_quad* quads = nullptr;
-    uint64_t n_quads = 0, n_faces = 0;
+    blok::GpuQuads snapshot;
+    uint64_t n_faces = 0;
     // (edits are enqueued on the null stream, and so is this: it reads what they leave)
-    const blok::GpuBuildStatus st = blok::gpu_volume_extract_quads(&ctx->volume, lo, hi, flags, &quads, &n_quads, &n_faces, &why);
+    const blok::GpuBuildStatus st = blok::gpu_volume_extract_quads(&ctx->volume, lo, hi, flags, &snapshot, &n_faces, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
     if (!(flags & BLOK_QUADS_COUNT_ONLY)) {
-        drop_quads(ctx);
-        ctx->d_quads = quads; ctx->n_quads = n_quads; ctx->has_quads = true;
+        blok::gpu_quads_free(&ctx->quads);
+        ctx->quads = snapshot; ctx->quads.taken = true;
     }
-    if (out_n_quads) *out_n_quads = n_quads;
+    if (out_n_quads) *out_n_quads = snapshot.n_quads;
     if (out_n_faces) *out_n_faces = n_faces;
     return BLOK_OK;
 }
 
 int blok_hip_volume_quads_download(blok_hip_ctx* ctx, blok_quad* out_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_quads) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: no snapshot (blok_hip_volume_extract_quads)");
-    if (first > ctx->n_quads || count > ctx->n_quads - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "quads_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->d_quads + first, count * sizeof(blok_quad), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuQuads& q = ctx->quads;
+    return ranged_download(ctx, "quads_download", "blok_hip_volume_extract_quads", q.taken, q.n_quads, q.d_quads, sizeof(blok_quad), out_host, first, count);
 }
 
 int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placements_host, uint32_t n_placements, int mode, float density,
@@ -292,8 +287,8 @@ int blok_hip_volume_label_components(blok_hip_ctx* ctx, const int32_t region_lo[
     blok::GpuComponents snapshot;
     const blok::GpuBuildStatus st = blok::gpu_volume_label_components(&ctx->volume, lo, hi, &snapshot, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
-    drop_components(ctx);
-    ctx->components = snapshot; ctx->has_components = true;
+    blok::gpu_components_free(&ctx->components);
+    ctx->components = snapshot; ctx->components.taken = true;
     if (out_n_components) *out_n_components = snapshot.n_components;
     if (out_n_voxels) *out_n_voxels = snapshot.n_voxels;
     return BLOK_OK;
@@ -301,26 +296,14 @@ int blok_hip_volume_label_components(blok_hip_ctx* ctx, const int32_t region_lo[
 
 int blok_hip_volume_components_download(blok_hip_ctx* ctx, blok_component* out_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_components) return set_error(ctx, BLOK_ERR_INVALID_ARG, "components_download: no snapshot (blok_hip_volume_label_components)");
-    const uint64_t n = ctx->components.n_components;
-    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "components_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "components_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->components.d_records + first, count * sizeof(blok_component), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuComponents& c = ctx->components;
+    return ranged_download(ctx, "components_download", "blok_hip_volume_label_components", c.taken, c.n_components, c.d_records, sizeof(blok_component), out_host, first, count);
 }
 
 int blok_hip_volume_labels_download(blok_hip_ctx* ctx, uint32_t* out_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_components) return set_error(ctx, BLOK_ERR_INVALID_ARG, "labels_download: no snapshot (blok_hip_volume_label_components)");
-    const uint64_t n = ctx->components.n_cells;
-    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "labels_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "labels_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->components.d_labels + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuComponents& c = ctx->components;
+    return ranged_download(ctx, "labels_download", "blok_hip_volume_label_components", c.taken, c.n_cells, c.d_labels, sizeof(uint32_t), out_host, first, count);
 }
 
 int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_t flags, uint32_t* out_model, int32_t out_origin[3],
@@ -330,7 +313,7 @@ int blok_hip_volume_capture_component(blok_hip_ctx* ctx, uint32_t label, uint32_
     if (rc != BLOK_OK) return rc;
     if (flags & ~BLOK_COMPONENT_CUT) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: unknown flag bits");
     if (!out_model) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: null output id");
-    if (!ctx->has_components) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: no snapshot (blok_hip_volume_label_components)");
+    if (!ctx->components.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "capture_component: no snapshot (blok_hip_volume_label_components)");
     if (ctx->models.desc.size() >= std::numeric_limits<uint32_t>::max() - 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model ids exhausted");
     std::string why;
     blok_component rec{};
@@ -397,15 +380,15 @@ int blok_hip_volume_encode_bricks(blok_hip_ctx* ctx, const int32_t region_lo[3],
     // (edits are enqueued on the null stream, and so is this: it reads what they leave)
     const blok::GpuBuildStatus st = blok::gpu_volume_encode_bricks(&ctx->volume, lo, hi, flags, &snapshot, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
-    drop_bricks(ctx);
-    ctx->bricks = snapshot; ctx->has_bricks = true;
+    blok::gpu_bricks_free(&ctx->bricks);
+    ctx->bricks = snapshot; ctx->bricks.taken = true;
     if (out_info) *out_info = snapshot.info;
     return BLOK_OK;
 }
 
 int blok_hip_volume_bricks_info(blok_hip_ctx* ctx, blok_bricks_info* out_info) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_info: no snapshot (blok_hip_volume_encode_bricks)");
+    if (!ctx->bricks.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_info: no snapshot (blok_hip_volume_encode_bricks)");
     if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_info: null output");
     *out_info = ctx->bricks.info;
     return BLOK_OK;
@@ -413,34 +396,23 @@ int blok_hip_volume_bricks_info(blok_hip_ctx* ctx, blok_bricks_info* out_info) {
 
 int blok_hip_volume_bricks_download(blok_hip_ctx* ctx, blok_brick_record* out_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_download: no snapshot (blok_hip_volume_encode_bricks)");
-    const uint64_t n = ctx->bricks.info.n_bricks;
-    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bricks_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->bricks.d_records + first, count * sizeof(blok_brick_record), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuBricks& b = ctx->bricks;
+    return ranged_download(ctx, "bricks_download", "blok_hip_volume_encode_bricks", b.taken, b.info.n_bricks, b.d_records, sizeof(blok_brick_record), out_host, first, count);
 }
 
 int blok_hip_volume_brick_payload_download(blok_hip_ctx* ctx, uint32_t plane, uint32_t* out_u32_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: no snapshot (blok_hip_volume_encode_bricks)");
-    if (plane > 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: plane above 1");
-    const uint64_t n = plane == 0u ? ctx->bricks.info.n_density : ctx->bricks.info.n_material;
-    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_u32_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_u32_host, (plane == 0u ? ctx->bricks.d_density : ctx->bricks.d_material) + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuBricks& b = ctx->bricks;
+    if (b.taken && plane > 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "brick_payload_download: plane above 1");
+    return ranged_download(ctx, "brick_payload_download", "blok_hip_volume_encode_bricks", b.taken, plane == 0u ? b.info.n_density : b.info.n_material,
+                           plane == 0u ? b.d_density : b.d_material, sizeof(uint32_t), out_u32_host, first, count);
 }
 
 int blok_hip_volume_restore_bricks(blok_hip_ctx* ctx, const int32_t dst_lo[3], uint32_t flags) {
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
     if (flags & ~blok::bricks::kDecodeFlags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "restore_bricks: unknown flag bits");
-    if (!ctx->has_bricks) return set_error(ctx, BLOK_ERR_INVALID_ARG, "restore_bricks: no snapshot (blok_hip_volume_encode_bricks)");
+    if (!ctx->bricks.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "restore_bricks: no snapshot (blok_hip_volume_encode_bricks)");
     uint32_t lo[3];
     rc = bricks_destination(ctx, "restore_bricks", ctx->bricks.info, dst_lo, lo);
     if (rc != BLOK_OK) return rc;
@@ -502,15 +474,15 @@ int blok_hip_volume_distance_field(blok_hip_ctx* ctx, const int32_t region_lo[3]
     // (edits are enqueued on the null stream, and so is this: it reads the masks they leave)
     const blok::GpuBuildStatus st = blok::gpu_volume_distance_field(&ctx->volume, lo, hi, max_radius, flags, &snapshot, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
-    drop_distance(ctx);
-    ctx->distance = snapshot; ctx->has_distance = true;
+    blok::gpu_field_free(&ctx->distance);
+    ctx->distance = snapshot; ctx->distance.taken = true;
     if (out_info) *out_info = snapshot.info;
     return BLOK_OK;
 }
 
 int blok_hip_volume_distance_info(blok_hip_ctx* ctx, blok_distance_info* out_info) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_distance) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_info: no snapshot (blok_hip_volume_distance_field)");
+    if (!ctx->distance.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_info: no snapshot (blok_hip_volume_distance_field)");
     if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_info: null output");
     *out_info = ctx->distance.info;
     return BLOK_OK;
@@ -518,22 +490,15 @@ int blok_hip_volume_distance_info(blok_hip_ctx* ctx, blok_distance_info* out_inf
 
 int blok_hip_volume_distance_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_distance) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_download: no snapshot (blok_hip_volume_distance_field)");
-    const blok_distance_info& info = ctx->distance.info;
-    const uint64_t n = static_cast<uint64_t>(info.ext[0]) * info.ext[1] * info.ext[2];
-    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "distance_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->distance.d_field + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuDistance& d = ctx->distance;
+    return ranged_download(ctx, "distance_download", "blok_hip_volume_distance_field", d.taken, field_cells(d.info.ext), d.d_field, sizeof(uint16_t), out_host, first, count);
 }
 
 int blok_hip_volume_edit_by_distance(blok_hip_ctx* ctx, int op, uint32_t d2, float density, uint32_t material, uint64_t* out_n_voxels) {
     if (out_n_voxels) *out_n_voxels = 0;
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
-    if (!ctx->has_distance) return set_error(ctx, BLOK_ERR_INVALID_ARG, "edit_by_distance: no snapshot (blok_hip_volume_distance_field)");
+    if (!ctx->distance.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "edit_by_distance: no snapshot (blok_hip_volume_distance_field)");
     if (const int rule = blok::distance::check_edit_args(ctx->distance.info, op, d2, density))
         return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("edit_by_distance: ") + blok::distance::rule_text(rule));
     std::string why;
@@ -563,15 +528,15 @@ int blok_hip_volume_flood_field(blok_hip_ctx* ctx, const int32_t region_lo[3], c
     // (edits are enqueued on the null stream, and so is this: it reads the masks they leave)
     const blok::GpuBuildStatus st = blok::gpu_volume_flood_field(&ctx->volume, lo, hi, seeds_xyz_host, n_seeds, max_steps, flags, material, &snapshot, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
-    drop_flood(ctx);
-    ctx->flood = snapshot; ctx->has_flood = true;
+    blok::gpu_field_free(&ctx->flood);
+    ctx->flood = snapshot; ctx->flood.taken = true;
     if (out_info) *out_info = snapshot.info;
     return BLOK_OK;
 }
 
 int blok_hip_volume_flood_info(blok_hip_ctx* ctx, blok_flood_info* out_info) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_info: no snapshot (blok_hip_volume_flood_field)");
+    if (!ctx->flood.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_info: no snapshot (blok_hip_volume_flood_field)");
     if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_info: null output");
     *out_info = ctx->flood.info;
     return BLOK_OK;
@@ -579,20 +544,13 @@ int blok_hip_volume_flood_info(blok_hip_ctx* ctx, blok_flood_info* out_info) {
 
 int blok_hip_volume_flood_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_download: no snapshot (blok_hip_volume_flood_field)");
-    const blok_flood_info& info = ctx->flood.info;
-    const uint64_t n = static_cast<uint64_t>(info.ext[0]) * info.ext[1] * info.ext[2];
-    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_download: range past the end of the snapshot");
-    if (count == 0) return BLOK_OK;
-    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_download: null output");
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, ctx->flood.d_field + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return BLOK_OK;
+    const blok::GpuFlood& f = ctx->flood;
+    return ranged_download(ctx, "flood_download", "blok_hip_volume_flood_field", f.taken, field_cells(f.info.ext), f.d_field, sizeof(uint16_t), out_host, first, count);
 }
 
 int blok_hip_volume_flood_counters(blok_hip_ctx* ctx, uint64_t out_counts[2]) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_counters: no snapshot (blok_hip_volume_flood_field)");
+    if (!ctx->flood.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_counters: no snapshot (blok_hip_volume_flood_field)");
     if (!out_counts) return set_error(ctx, BLOK_ERR_INVALID_ARG, "flood_counters: null output");
     out_counts[0] = ctx->flood.rounds; out_counts[1] = ctx->flood.visits;
     return BLOK_OK;
@@ -602,7 +560,7 @@ int blok_hip_volume_edit_by_flood(blok_hip_ctx* ctx, int op, uint32_t d, float d
     if (out_n_voxels) *out_n_voxels = 0;
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
-    if (!ctx->has_flood) return set_error(ctx, BLOK_ERR_INVALID_ARG, "edit_by_flood: no snapshot (blok_hip_volume_flood_field)");
+    if (!ctx->flood.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "edit_by_flood: no snapshot (blok_hip_volume_flood_field)");
     if (const int rule = blok::flood::check_edit_args(ctx->flood.info, op, d, density))
         return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("edit_by_flood: ") + blok::flood::rule_text(rule));
     std::string why;

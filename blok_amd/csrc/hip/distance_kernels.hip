@@ -14,8 +14,7 @@
 //      every global access is 128 contiguous bytes per wave instruction, every LDS read is conflict-free, and the window is a plain loop
 //      over the rows of the chunk within R.  Rows outside the box enter as 0 or FAR (distance_core.h: outside_value).  The y pass runs
 //      over the region widened by R in z; the z pass writes the snapshot and counts it: ballots, one atomic per wave and counter.
-// The edit: a lane per region cell, 64 along x per wave; it reads the snapshot and the density, writes where the predicate holds, counts
-// through a ballot and one atomic per wave; then the refresh of every edit runs over the region.
+// The edit is field_edit.h's, with the distance rule.
 // Everything is on the null stream, behind earlier edits.  The intermediates live for the call.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +23,7 @@
 
 #include "gpu_build.h"
 #include "device_mem.h"
+#include "field_edit.h"
 #include "../common/distance_core.h"
 
 namespace blok {
@@ -164,57 +164,16 @@ __global__ __launch_bounds__(256) void distance_axis_kernel(const AxisArgs a) {
     }
 }
 
-// ---- the edit -------------------------------------------------------------------------------------------------------------------------
-struct EditArgs {
-    float* density; uint32_t* ids;
-    const uint16_t* field;
-    uint32_t nx, ny;
-    uint32_t lo[3], ext[3];
-    uint32_t x_chunks;
-    uint64_t n_waves;
-    int op; uint32_t d2;
-    float value; uint32_t material;                               // what a written cell gets
-    uint64_t* count;
-};
-
-__global__ __launch_bounds__(256) void distance_edit_kernel(const EditArgs a) {
-    const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * 4u + (threadIdx.x >> 6);
-    if (wave >= a.n_waves) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t xc = static_cast<uint32_t>(wave % a.x_chunks);
-    const uint64_t row = wave / a.x_chunks;
-    const uint32_t y = static_cast<uint32_t>(row % a.ext[1]), z = static_cast<uint32_t>(row / a.ext[1]);
-    const uint32_t x = 64u * xc + lane;
-    bool writes = false;
-    if (x < a.ext[0]) {
-        const size_t cell = (a.lo[0] + x) + (a.lo[1] + y) * static_cast<size_t>(a.nx) + (a.lo[2] + z) * (static_cast<size_t>(a.nx) * a.ny);
-        const uint32_t dist = a.field[x + static_cast<size_t>(a.ext[0]) * (y + static_cast<size_t>(a.ext[1]) * z)];
-        writes = D::edit_writes(a.op, dist, a.d2, D::filled(a.density[cell]));
-        if (writes) { a.density[cell] = a.value; a.ids[cell] = a.material; }
-    }
-    const uint32_t n = static_cast<uint32_t>(__popcll(__ballot(writes)));
-    if (lane == 0u && n) atomicAdd(reinterpret_cast<unsigned long long*>(a.count), static_cast<unsigned long long>(n));
-}
-
 }  // namespace
-
-void gpu_distance_free(GpuDistance* d) {
-    if (d->d_field) (void)hipFree(d->d_field);
-    *d = GpuDistance{};
-}
 
 GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t max_radius, uint32_t flags,
                                          GpuDistance* out, std::string* why) {
-    *out = GpuDistance{};
-    if (v->cells() > 0xFFFFFFFFull) { *why = "distance_field: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
-    blok_distance_info& info = out->info;
-    info.version = 1u; info.flags = flags; info.max_radius = max_radius;
     uint32_t ext[3];
-    for (int k = 0; k < 3; ++k) {
-        out->lo[k] = lo[k]; ext[k] = hi[k] > lo[k] ? hi[k] - lo[k] : 0u;
-        info.lo[k] = v->origin[k] + static_cast<int32_t>(lo[k]); info.ext[k] = ext[k];
-    }
-    if (!ext[0] || !ext[1] || !ext[2]) return GpuBuildStatus::Ok;
+    GpuBuildStatus begun;
+    const bool has_cells = gpu_field_begin(v, "distance_field", lo, hi, flags, out, ext, &begun, why);
+    blok_distance_info& info = out->info;
+    info.max_radius = max_radius;
+    if (!has_cells) return begun;
     const uint64_t cells = static_cast<uint64_t>(ext[0]) * ext[1] * ext[2];
     // the region widened by R along y and z, clipped to the box: what the x pass (both) and the y pass (z) run over
     const uint32_t R = max_radius;
@@ -273,27 +232,8 @@ GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3
 
 GpuBuildStatus gpu_volume_edit_by_distance(GpuVolume* v, const GpuDistance* field, int op, uint32_t d2, float density, uint32_t material,
                                            uint64_t* out_n_voxels, std::string* why) {
-    *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "edit_by_distance: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
-    const blok_distance_info& info = field->info;
-    if (!info.ext[0] || !info.ext[1] || !info.ext[2]) return GpuBuildStatus::Ok;           // an empty snapshot: nothing to write
-    EditArgs a{};
-    a.density = v->d_density; a.ids = v->d_ids; a.field = field->d_field; a.nx = v->nx; a.ny = v->ny;
-    uint32_t hi[3];
-    for (int k = 0; k < 3; ++k) { a.lo[k] = field->lo[k]; a.ext[k] = info.ext[k]; hi[k] = field->lo[k] + info.ext[k]; }
-    a.x_chunks = (a.ext[0] + 63u) / 64u;
-    a.n_waves = static_cast<uint64_t>(a.x_chunks) * a.ext[1] * a.ext[2];
-    a.op = op; a.d2 = d2;
-    a.value = op == BLOK_DISTANCE_GROW ? density : 0.0f; a.material = op == BLOK_DISTANCE_GROW ? material : 0u;
-    DeviceMem mem;
-    BLOK_GPU_TRY(mem.alloc(&a.count, 1u));
-    BLOK_GPU_TRY(hipMemsetAsync(a.count, 0, sizeof(uint64_t), nullptr));
-    hipLaunchKernelGGL(distance_edit_kernel, dim3(static_cast<uint32_t>((a.n_waves + 3u) / 4u)), dim3(256), 0, nullptr, a);
-    BLOK_GPU_TRY(hipGetLastError());
-    if (op == BLOK_DISTANCE_GROW) v->edit_may_add = true;         // what the shadow rays' map has to know (gpu_build.h)
-    const GpuBuildStatus st = gpu_volume_refresh(v, a.lo, hi, why);
-    BLOK_GPU_TRY(hipMemcpy(out_n_voxels, a.count, sizeof(uint64_t), hipMemcpyDeviceToHost));      // blocking, as gpu_volume_set_voxels is
-    return st;
+    return edit_by_field(v, "edit_by_distance", field_edit::distance_rule(op, d2, density, material), field->lo, field->info.ext, field->d_field,
+                         op == BLOK_DISTANCE_GROW, out_n_voxels, why);
 }
 
 }  // namespace blok

@@ -19,7 +19,7 @@
 //      The host reads the next list's count after every round and stops at zero — at the latest after max_steps + 2 rounds (§20).
 //   finish. a workgroup per 16 bricks along x: the tiles transposed through LDS into the x-fastest snapshot, counted by ballots, a sum per
 //      workgroup in LDS, one atomic per workgroup and counter.
-// The edit: a lane per region cell, 64 along x per wave, as distance_edit_kernel; then the refresh of every edit runs over the region.
+// The edit is field_edit.h's, with the flood rule.
 // Everything is on the null stream, behind earlier edits.  The working field, the words, the stamps and the lists live for the call.
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,7 @@
 
 #include "gpu_build.h"
 #include "device_mem.h"
+#include "field_edit.h"
 #include "../common/flood_core.h"
 
 namespace blok {
@@ -97,9 +98,8 @@ __global__ __launch_bounds__(256) void flood_classify_kernel(const ClassifyArgs 
     const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * 4u + (threadIdx.x >> 6);
     if (wave >= a.n_waves) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t xc = static_cast<uint32_t>(wave % a.x_chunks);
-    const uint64_t row = wave / a.x_chunks;
-    const uint32_t cy = static_cast<uint32_t>(row % a.c.nb[1]), cz = static_cast<uint32_t>(row / a.c.nb[1]);
+    uint32_t xc, cy, cz;
+    row_segment(wave, a.x_chunks, a.c.nb[1], xc, cy, cz);
     const uint32_t cx = 64u * xc + lane;
     if (cx >= a.c.nb[0]) return;
     const uint64_t m = a.masks.at(a.c.b0[0] + cx, a.c.b0[1] + cy, a.c.b0[2] + cz);
@@ -317,61 +317,17 @@ __global__ __launch_bounds__(256) void flood_finish_kernel(const FinishArgs a) {
     if (t == 3u && s_count[3]) atomicMax(reinterpret_cast<unsigned long long*>(a.counts + 3), static_cast<unsigned long long>(s_count[3]));
 }
 
-// ---- the edit -------------------------------------------------------------------------------------------------------------------------
-struct EditArgs {
-    float* density; uint32_t* ids;
-    const uint16_t* field;
-    uint32_t nx, ny;
-    uint32_t lo[3], ext[3];
-    uint32_t x_chunks;
-    uint64_t n_waves;
-    int op; uint32_t d;
-    float value; uint32_t material;                               // what a written cell gets (PAINT: the id alone)
-    uint64_t* count;
-};
-
-__global__ __launch_bounds__(256) void flood_edit_kernel(const EditArgs a) {
-    const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * 4u + (threadIdx.x >> 6);
-    if (wave >= a.n_waves) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t xc = static_cast<uint32_t>(wave % a.x_chunks);
-    const uint64_t row = wave / a.x_chunks;
-    const uint32_t y = static_cast<uint32_t>(row % a.ext[1]), z = static_cast<uint32_t>(row / a.ext[1]);
-    const uint32_t x = 64u * xc + lane;
-    bool writes = false;
-    if (x < a.ext[0]) {
-        const size_t cell = (a.lo[0] + x) + (a.lo[1] + y) * static_cast<size_t>(a.nx) + (a.lo[2] + z) * (static_cast<size_t>(a.nx) * a.ny);
-        const uint32_t dist = a.field[x + static_cast<size_t>(a.ext[0]) * (y + static_cast<size_t>(a.ext[1]) * z)];
-        writes = F::edit_writes(a.op, dist, a.d, F::filled(a.density[cell]));
-        if (writes) {
-            if (F::op_writes_density(a.op)) a.density[cell] = a.value;
-            a.ids[cell] = a.material;
-        }
-    }
-    const uint32_t n = static_cast<uint32_t>(__popcll(__ballot(writes)));
-    if (lane == 0u && n) atomicAdd(reinterpret_cast<unsigned long long*>(a.count), static_cast<unsigned long long>(n));
-}
-
 }  // namespace
-
-void gpu_flood_free(GpuFlood* f) {
-    if (f->d_field) (void)hipFree(f->d_field);
-    *f = GpuFlood{};
-}
 
 GpuBuildStatus gpu_volume_flood_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], const int32_t* seeds_xyz, uint64_t n_seeds,
                                       uint32_t max_steps, uint32_t flags, uint32_t material, GpuFlood* out, std::string* why) {
-    *out = GpuFlood{};
-    if (v->cells() > 0xFFFFFFFFull) { *why = "flood_field: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
-    blok_flood_info& info = out->info;
-    info.version = 1u; info.flags = flags; info.max_steps = max_steps;
-    Cover c{};
     uint32_t ext[3];
-    for (int k = 0; k < 3; ++k) {
-        out->lo[k] = lo[k]; ext[k] = hi[k] > lo[k] ? hi[k] - lo[k] : 0u;
-        info.lo[k] = v->origin[k] + static_cast<int32_t>(lo[k]); info.ext[k] = ext[k];
-    }
-    if (!ext[0] || !ext[1] || !ext[2]) return GpuBuildStatus::Ok;
+    GpuBuildStatus begun;
+    const bool has_cells = gpu_field_begin(v, "flood_field", lo, hi, flags, out, ext, &begun, why);
+    blok_flood_info& info = out->info;
+    info.max_steps = max_steps;
+    if (!has_cells) return begun;
+    Cover c{};
     for (int k = 0; k < 3; ++k) { c.lo[k] = lo[k]; c.hi[k] = hi[k]; c.b0[k] = lo[k] / 4u; c.nb[k] = (hi[k] - 1u) / 4u - c.b0[k] + 1u; }
     const uint64_t cells = static_cast<uint64_t>(ext[0]) * ext[1] * ext[2];
     const uint64_t n_cover64 = static_cast<uint64_t>(c.nb[0]) * c.nb[1] * c.nb[2];      // at most the volume's bricks: below 2^31 (gpu_volume_create)
@@ -463,27 +419,8 @@ GpuBuildStatus gpu_volume_flood_field(const GpuVolume* v, const uint32_t lo[3], 
 
 GpuBuildStatus gpu_volume_edit_by_flood(GpuVolume* v, const GpuFlood* field, int op, uint32_t d, float density, uint32_t material,
                                         uint64_t* out_n_voxels, std::string* why) {
-    *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "edit_by_flood: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
-    const blok_flood_info& info = field->info;
-    if (!info.ext[0] || !info.ext[1] || !info.ext[2]) return GpuBuildStatus::Ok;           // an empty snapshot: nothing to write
-    EditArgs a{};
-    a.density = v->d_density; a.ids = v->d_ids; a.field = field->d_field; a.nx = v->nx; a.ny = v->ny;
-    uint32_t hi[3];
-    for (int k = 0; k < 3; ++k) { a.lo[k] = field->lo[k]; a.ext[k] = info.ext[k]; hi[k] = field->lo[k] + info.ext[k]; }
-    a.x_chunks = (a.ext[0] + 63u) / 64u;
-    a.n_waves = static_cast<uint64_t>(a.x_chunks) * a.ext[1] * a.ext[2];
-    a.op = op; a.d = d;
-    a.value = F::written_density(op, density); a.material = F::written_material(op, material);
-    DeviceMem mem;
-    BLOK_GPU_TRY(mem.alloc(&a.count, 1u));
-    BLOK_GPU_TRY(hipMemsetAsync(a.count, 0, sizeof(uint64_t), nullptr));
-    hipLaunchKernelGGL(flood_edit_kernel, dim3(static_cast<uint32_t>((a.n_waves + 3u) / 4u)), dim3(256), 0, nullptr, a);
-    BLOK_GPU_TRY(hipGetLastError());
-    if (F::op_fills(op)) v->edit_may_add = true;                  // what the shadow rays' map has to know (gpu_build.h)
-    const GpuBuildStatus st = gpu_volume_refresh(v, a.lo, hi, why);      // (PAINT changes no mask: the refresh still marks its bricks dirty)
-    BLOK_GPU_TRY(hipMemcpy(out_n_voxels, a.count, sizeof(uint64_t), hipMemcpyDeviceToHost));      // blocking, as gpu_volume_set_voxels is
-    return st;
+    return edit_by_field(v, "edit_by_flood", field_edit::flood_rule(op, d, density, material), field->lo, field->info.ext, field->d_field,
+                         F::op_fills(op), out_n_voxels, why);
 }
 
 }  // namespace blok

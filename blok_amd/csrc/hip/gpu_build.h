@@ -105,10 +105,21 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
 // passed terrain::check_params.
 GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_params& params, const uint32_t lo[3], const uint32_t hi[3],
                                            uint64_t* out_n_voxels, std::string* why);
+// ---- snapshots ----
+// What an entry leaves on the device for later calls is a holder that owns its arrays and knows whether it was taken: a default-constructed
+// holder is no snapshot, a taken one whose pointers are null is the snapshot of an empty region.  The entry that takes a snapshot sets
+// `taken`; gpu_*_free frees the arrays and leaves the holder default-constructed.
 // = blok_hip_volume_extract_quads (include/blok_hip.h; quads_kernels.hip) over the box-local region [lo, hi).  Reads the store, changes
-// nothing.  Without BLOK_QUADS_COUNT_ONLY *out_quads is a new device array of *out_n_quads records (null for none), the caller's to free.
-GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, blok_quad** out_quads,
-                                        uint64_t* out_n_quads, uint64_t* out_n_faces, std::string* why);
+// nothing.  out->n_quads counts the records; without BLOK_QUADS_COUNT_ONLY out->d_quads is a new device array of them (null for none), the
+// caller's to free.
+struct GpuQuads {
+    blok_quad* d_quads = nullptr;
+    uint64_t n_quads = 0;
+    bool taken = false;
+};
+void gpu_quads_free(GpuQuads* q);
+GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuQuads* out,
+                                        uint64_t* out_n_faces, std::string* why);
 // = blok_hip_volume_stamp_models (include/blok_hip.h; stamp_kernels.hip).  The placements have passed the entry's checks; models[i] is
 // the model of placements[i], read in device memory through its tree.  One launch and one refresh per placement, in table order on the
 // null stream; the only wait is the one for the count at the end.
@@ -146,6 +157,7 @@ struct GpuComponents {
     uint64_t* d_row_base = nullptr;
     uint64_t n_cells = 0, n_components = 0, n_voxels = 0;
     uint32_t lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0};      // the region, box-local
+    bool taken = false;
 };
 void gpu_components_free(GpuComponents* c);
 // Labels the box-local region [lo, hi) from the brick masks (which every edit leaves equal to density > 0).  Reads the store, changes
@@ -172,6 +184,7 @@ struct GpuBricks {
     uint32_t* d_density = nullptr;
     uint32_t* d_material = nullptr;
     blok_bricks_info info = {};
+    bool taken = false;
 };
 void gpu_bricks_free(GpuBricks* b);
 // Encodes the box-local region [lo, hi) (flags: BLOK_BRICKS_FILLED_ONLY or 0).  Reads the store (and, with FILLED_ONLY on a region whose
@@ -182,14 +195,39 @@ GpuBuildStatus gpu_volume_encode_bricks(const GpuVolume* v, const uint32_t lo[3]
 // BLOK_BRICKS_KEEP_OTHERS or 0), then refreshes that box as every edit does.  The stream is one gpu_volume_encode_bricks made or one that
 // has passed bricks::validate: the kernel trusts its indices.  Blocking.
 GpuBuildStatus gpu_volume_decode_bricks(GpuVolume* v, const GpuBricks* stream, const uint32_t dst_lo[3], uint32_t flags, std::string* why);
-// ---- the distance field (include/blok_hip.h: blok_hip_volume_distance_field; distance_kernels.hip) ----
-// A field in device memory, owned by the holder: one value per region cell, x fastest, and the info that counts them.
-struct GpuDistance {
+// ---- the fields (distance_kernels.hip, flood_kernels.hip) ----
+// A field in device memory, owned by the holder: one uint16 per region cell, x fastest, and an info that counts them.
+struct GpuField {
     uint16_t* d_field = nullptr;
-    blok_distance_info info = {};
     uint32_t lo[3] = {0, 0, 0};                  // the region's corner, box-local
+    bool taken = false;
 };
-void gpu_distance_free(GpuDistance* d);
+template <class Field>
+void gpu_field_free(Field* f) {
+    if (f->d_field) (void)hipFree(f->d_field);
+    *f = Field{};
+}
+// What both field builders begin with: *out reset, the 2^32 check with the entry's name in the text, the info's version, flags, lo and ext and
+// the holder's lo from the box-local region [lo, hi), ext[].  False: nothing to compute, and *st says why — Unsupported, or Ok for a region
+// without a cell.
+template <class Field>
+bool gpu_field_begin(const GpuVolume* v, const char* entry, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, Field* out, uint32_t ext[3],
+                     GpuBuildStatus* st, std::string* why) {
+    *out = Field{};
+    *st = GpuBuildStatus::Unsupported;
+    if (v->cells() > 0xFFFFFFFFull) { *why = std::string(entry) + ": volume larger than 2^32 cells"; return false; }
+    out->info.version = 1u; out->info.flags = flags;
+    for (int k = 0; k < 3; ++k) {
+        out->lo[k] = lo[k]; ext[k] = hi[k] > lo[k] ? hi[k] - lo[k] : 0u;
+        out->info.lo[k] = v->origin[k] + static_cast<int32_t>(lo[k]); out->info.ext[k] = ext[k];
+    }
+    *st = GpuBuildStatus::Ok;
+    return ext[0] && ext[1] && ext[2];
+}
+// ---- the distance field (include/blok_hip.h: blok_hip_volume_distance_field; distance_kernels.hip) ----
+struct GpuDistance : GpuField {
+    blok_distance_info info = {};
+};
 // The field of the box-local region [lo, hi) with max_radius <= 255 and known flags, from the brick masks (which every edit leaves equal to
 // density > 0).  Changes nothing; *out is a new snapshot, the caller's to free (d_field null when the region has no cell).  Blocking.
 GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t max_radius, uint32_t flags,
@@ -199,15 +237,12 @@ GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3
 GpuBuildStatus gpu_volume_edit_by_distance(GpuVolume* v, const GpuDistance* field, int op, uint32_t d2, float density, uint32_t material,
                                            uint64_t* out_n_voxels, std::string* why);
 // ---- the flood from seeds (include/blok_hip.h: blok_hip_volume_flood_field; flood_kernels.hip) ----
-// A field in device memory, owned by the holder: one value per region cell, x fastest, and the info that counts them.  rounds and visits
-// say how the device got there (launches over a non-empty list, bricks taken off the lists): diagnostics, never part of the info.
-struct GpuFlood {
-    uint16_t* d_field = nullptr;
+// rounds and visits say how the device got there (launches over a non-empty list, bricks taken off the lists): diagnostics, never part of
+// the info.
+struct GpuFlood : GpuField {
     blok_flood_info info = {};
-    uint32_t lo[3] = {0, 0, 0};                  // the region's corner, box-local
     uint64_t rounds = 0, visits = 0;
 };
-void gpu_flood_free(GpuFlood* f);
 // The field of the box-local region [lo, hi) from n_seeds world cells inside it (host memory) and the SEED_FACE bits; the arguments have
 // passed flood::check_field_args.  Reads the brick masks (which every edit leaves equal to density > 0), with SAME_MATERIAL the store.
 // Changes nothing; *out is a new snapshot, the caller's to free (d_field null when the region has no cell).  Blocking.  Internal: the

@@ -976,7 +976,8 @@ __global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, c
     uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
     uint64_t count = 0;
     for (uint64_t row = wave; row < n_rows; row += n_waves) {
-        const uint32_t seg = static_cast<uint32_t>(row % segs), y = static_cast<uint32_t>((row / segs) % r.ext[1]), z = static_cast<uint32_t>(row / (static_cast<uint64_t>(segs) * r.ext[1]));
+        uint32_t seg, y, z;
+        row_segment(row, segs, r.ext[1], seg, y, z);
         const uint32_t x = seg * 64u + lane;
         const bool filled = x < r.ext[0] && r.density[(static_cast<size_t>(r.lo[2] + z) * r.ny + (r.lo[1] + y)) * r.nx + r.lo[0] + x] > 0.0f &&
                             member<kLabelled>(p, r.lo[0] + x, r.lo[1] + y, r.lo[2] + z);

@@ -198,9 +198,14 @@ void launch_face(const QuadArgs& a) {
 
 }  // namespace
 
-GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, blok_quad** out_quads,
-                                        uint64_t* out_n_quads, uint64_t* out_n_faces, std::string* why) {
-    *out_quads = nullptr; *out_n_quads = 0; *out_n_faces = 0;
+void gpu_quads_free(GpuQuads* q) {
+    if (q->d_quads) (void)hipFree(q->d_quads);
+    *q = GpuQuads{};
+}
+
+GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuQuads* out,
+                                        uint64_t* out_n_faces, std::string* why) {
+    *out = GpuQuads{}; *out_n_faces = 0;
     if (v->cells() > 0xFFFFFFFFull) { *why = "extract_quads: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
     if (lo[0] >= hi[0] || lo[1] >= hi[1] || lo[2] >= hi[2]) return GpuBuildStatus::Ok;
     QuadArgs a{};
@@ -252,9 +257,9 @@ GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3]
         BLOK_GPU_TRY(hipGetLastError());
         BLOK_GPU_TRY(hipDeviceSynchronize());
         mem.release(a.out);
-        *out_quads = a.out;
+        out->d_quads = a.out;
     }
-    *out_n_quads = total; *out_n_faces = n_faces;
+    out->n_quads = total; *out_n_faces = n_faces;
     return GpuBuildStatus::Ok;
 }
 

@@ -1,6 +1,6 @@
 // What the kernels over the resident volume and over placed models share, each defined once: wave-uniform loads through the scalar cache,
-// the keyed brick index, the mask word of a brick in either layout of GpuVolume::d_masks (gpu_build.h), and the walk from a model's root
-// to one of its bricks.  The key arithmetic also compiles without HIP (tests/host_harness/cell_key_main.cpp).
+// the keyed brick index, the mask word of a brick in either layout of GpuVolume::d_masks (gpu_build.h), the row segment a wave of a region
+// launch owns, and the walk from a model's root to one of its bricks.  The key arithmetic also compiles without HIP (tests/host_harness/cell_key_main.cpp).
 #ifndef BLOK_VOLUME_DEVICE_H
 #define BLOK_VOLUME_DEVICE_H
 #include <stddef.h>
@@ -45,6 +45,14 @@ struct BrickMasks {
         return masks[cell_key(bx, by, bz, key_digits)];
     }
 };
+
+// Wave `wave` of a launch over a region whose rows along x are cut into segments of 64 cells, `x_chunks` to a row of the `ny` rows of a
+// slice: it is segment xc of row (y, z).
+__device__ __forceinline__ void row_segment(uint64_t wave, uint32_t x_chunks, uint32_t ny, uint32_t& xc, uint32_t& y, uint32_t& z) {
+    xc = static_cast<uint32_t>(wave % x_chunks);
+    const uint64_t row = wave / x_chunks;
+    y = static_cast<uint32_t>(row % ny); z = static_cast<uint32_t>(row / ny);
+}
 
 // ---- wave-uniform loads through the scalar cache ----------------------------------------------------------------------------------------
 // A record of a wave-uniform index through the scalar cache (s_load): the arrays read this way — the instance table, the model store, a

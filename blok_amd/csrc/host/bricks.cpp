@@ -3,6 +3,7 @@
 // and cell by cell; and the .bvol file that holds a stream.
 #include "blok_world.h"
 #include "../common/bricks_core.h"
+#include "../common/region_core.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -18,18 +19,6 @@ const char kMagic[8] = {'B', 'L', 'O', 'K', 'B', 'V', 'L', '1'};
 int fail(char* err, size_t err_len, int code, const std::string& msg) {
     if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
     return code;
-}
-
-// The box-local region of world region_lo / region_hi (both null: the whole box); the codes of the device entry.
-int local_region(const int32_t origin[3], const int64_t dims[3], const int32_t* region_lo, const int32_t* region_hi, int64_t lo[3], int64_t hi[3]) {
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return BLOK_ERR_INVALID_ARG;
-    for (int a = 0; a < 3; ++a) {
-        const int64_t o = origin ? origin[a] : 0;
-        lo[a] = region_lo ? int64_t(region_lo[a]) - o : 0; hi[a] = region_hi ? int64_t(region_hi[a]) - o : dims[a];
-        if (lo[a] > hi[a]) return BLOK_ERR_INVALID_ARG;
-    }
-    for (int a = 0; a < 3; ++a) if (lo[a] < 0 || hi[a] > dims[a]) return BLOK_ERR_UNSUPPORTED;
-    return BLOK_OK;
 }
 
 uint32_t float_bits(float f) { uint32_t u; std::memcpy(&u, &f, sizeof u); return u; }
@@ -49,14 +38,14 @@ int blok_bricks_encode(const float* density, const uint32_t* material_ids, const
                        blok_brick_record* records, uint64_t record_capacity, uint32_t* density_payload, uint64_t density_capacity,
                        uint32_t* material_payload, uint64_t material_capacity) {
     if (!out_info || (flags & ~B::kEncodeFlags)) return BLOK_ERR_INVALID_ARG;
-    const int64_t dims[3] = {nx, ny, nz};
-    int64_t lo[3], hi[3];
-    const int rc = local_region(origin, dims, region_lo, region_hi, lo, hi);
+    const uint32_t dims[3] = {nx, ny, nz};
+    uint32_t lo[3], hi[3];
+    const int rc = blok::region::status(blok::region::local(origin, dims, region_lo, region_hi, lo, hi));      // (the codes of the device entry)
     if (rc != BLOK_OK) return rc;
     if (uint64_t(nx) * ny * nz > 0xFFFFFFFFull) return BLOK_ERR_UNSUPPORTED;
     blok_bricks_info info{};
     info.version = 1u; info.flags = flags;
-    for (int a = 0; a < 3; ++a) { info.lo[a] = static_cast<int32_t>((origin ? origin[a] : 0) + lo[a]); info.ext[a] = static_cast<uint32_t>(hi[a] - lo[a]); }
+    for (int a = 0; a < 3; ++a) { info.lo[a] = (origin ? origin[a] : 0) + static_cast<int32_t>(lo[a]); info.ext[a] = hi[a] - lo[a]; }
     const bool empty = !info.ext[0] || !info.ext[1] || !info.ext[2];
     if (!empty && (!density || !material_ids)) return BLOK_ERR_INVALID_ARG;
     const bool filled_only = (flags & BLOK_BRICKS_FILLED_ONLY) != 0u;
@@ -69,7 +58,7 @@ int blok_bricks_encode(const float* density, const uint32_t* material_ids, const
             uint32_t dv[64], mv[64], n = 0;
             for (uint32_t z = 0; z < 4u && 4u * bz + z < info.ext[2]; ++z) for (uint32_t y = 0; y < 4u && 4u * by + y < info.ext[1]; ++y)
                 for (uint32_t x = 0; x < 4u && 4u * bx + x < info.ext[0]; ++x) {
-                    const size_t cell = static_cast<size_t>((lo[0] + 4u * bx + x) + ((lo[1] + 4u * by + y) + (lo[2] + 4u * bz + z) * dims[1]) * dims[0]);
+                    const size_t cell = (lo[0] + 4u * bx + x) + ((lo[1] + 4u * by + y) + static_cast<size_t>(lo[2] + 4u * bz + z) * ny) * nx;
                     const uint32_t bits = float_bits(density[cell]), id = material_ids[cell];
                     const uint64_t before = d.mask;
                     d.add(B::cell_bit(x, y, z), bits, id, filled_only);

@@ -4,6 +4,7 @@
 // along y and along z, row against row so that the inner loop runs along x; input rows that hold no value are skipped.
 #include "blok_world.h"
 #include "../common/distance_core.h"
+#include "../common/field_edit_core.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -12,19 +13,6 @@
 namespace D = blok::distance;
 
 namespace {
-
-// The box-local region of world region_lo / region_hi (both null: the whole box).
-int host_region(const int32_t origin[3], const uint32_t dims[3], const int32_t* region_lo, const int32_t* region_hi, uint32_t lo[3], uint32_t hi[3]) {
-    if ((region_lo == nullptr) != (region_hi == nullptr)) return BLOK_ERR_INVALID_ARG;
-    for (int a = 0; a < 3; ++a) {
-        const int64_t o = origin ? origin[a] : 0;
-        const int64_t l = region_lo ? int64_t(region_lo[a]) - o : 0, h = region_hi ? int64_t(region_hi[a]) - o : int64_t(dims[a]);
-        if (l > h) return BLOK_ERR_INVALID_ARG;
-        if (l < 0 || h > int64_t(dims[a])) return BLOK_ERR_UNSUPPORTED;
-        lo[a] = static_cast<uint32_t>(l); hi[a] = static_cast<uint32_t>(h);
-    }
-    return BLOK_OK;
-}
 
 // One min-plus pass along an axis whose rows are `ex` consecutive values: out row r (box coordinate out_lo + r) from the input rows within
 // R of it; a row outside the box is `outside` throughout.  n_b independent slabs.
@@ -65,7 +53,7 @@ int blok_distance_field(const float* density, const int32_t origin[3], uint32_t 
     if (D::check_field_args(max_radius, flags) != D::kFine) return BLOK_ERR_INVALID_ARG;
     const uint32_t dims[3] = {nx, ny, nz};
     uint32_t lo[3], hi[3];
-    const int rc = host_region(origin, dims, region_lo, region_hi, lo, hi);
+    const int rc = blok::region::status(blok::region::local(origin, dims, region_lo, region_hi, lo, hi));
     if (rc != BLOK_OK) return rc;
     if (uint64_t(nx) * ny * nz > 0xFFFFFFFFull) return BLOK_ERR_UNSUPPORTED;
     blok_distance_info info{};
@@ -117,32 +105,7 @@ int blok_distance_edit(float* density, uint32_t* material_ids, const int32_t ori
                        const blok_distance_info* info, int op, uint32_t d2, float density_value, uint32_t material, uint64_t* out_n_voxels) {
     if (out_n_voxels) *out_n_voxels = 0;
     if (!info || D::check_edit_args(*info, op, d2, density_value) != D::kFine) return BLOK_ERR_INVALID_ARG;
-    const uint32_t dims[3] = {nx, ny, nz};
-    int32_t region_hi[3];
-    for (int a = 0; a < 3; ++a) {
-        if (info->ext[a] > dims[a]) return BLOK_ERR_UNSUPPORTED;
-        region_hi[a] = static_cast<int32_t>(int64_t(info->lo[a]) + info->ext[a]);
-    }
-    uint32_t lo[3], hi[3];
-    const int rc = host_region(origin, dims, info->lo, region_hi, lo, hi);
-    if (rc != BLOK_OK) return rc;
-    if (uint64_t(nx) * ny * nz > 0xFFFFFFFFull) return BLOK_ERR_UNSUPPORTED;
-    const size_t ext[3] = {info->ext[0], info->ext[1], info->ext[2]};
-    if (!ext[0] || !ext[1] || !ext[2]) return BLOK_OK;            // an empty snapshot: nothing to write
-    if (!density || !material_ids || !field) return BLOK_ERR_INVALID_ARG;
-    const float value = op == BLOK_DISTANCE_GROW ? density_value : 0.0f;
-    const uint32_t id = op == BLOK_DISTANCE_GROW ? material : 0u;
-    uint64_t n = 0;
-    for (size_t z = 0; z < ext[2]; ++z)
-        for (size_t y = 0; y < ext[1]; ++y)
-            for (size_t x = 0; x < ext[0]; ++x) {
-                const size_t cell = (lo[0] + x) + ((lo[2] + z) * ny + (lo[1] + y)) * nx;
-                if (!D::edit_writes(op, field[x + ext[0] * (y + ext[1] * z)], d2, D::filled(density[cell]))) continue;
-                density[cell] = value; material_ids[cell] = id;
-                ++n;
-            }
-    if (out_n_voxels) *out_n_voxels = n;
-    return BLOK_OK;
+    return blok::field_edit::edit_host(density, material_ids, origin, nx, ny, nz, field, *info, blok::field_edit::distance_rule(op, d2, density_value, material), out_n_voxels);
 }
 
 }  // extern "C"

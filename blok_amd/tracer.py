@@ -17,6 +17,11 @@ from . import _ffi
 from ._ffi import BlokError, CAMERA, GBuffer, HIT, INSTANCE, MATERIAL, RAY, SUB_CHUNK, SVO_NODE, WorldStats
 
 
+def _vec3(v):
+    """Three world coordinates as the C ABI takes them; None passes through (a null pointer)."""
+    return None if v is None else (C.c_int32 * 3)(*[int(c) for c in v])
+
+
 class HipTracer:
     def __init__(self, width: int, height: int, device: int = 0):
         self.width, self.height, self.device = int(width), int(height), int(device)
@@ -56,6 +61,23 @@ class HipTracer:
         self.width, self.height = int(width), int(height)
 
     # -- device-resident dense store: edits and rebuilds without leaving HBM ----------------
+    def _paged(self, fn, out, first, page, *lead, probe=True):
+        """Fills `out` from a ranged *_download entry fn(ctx, *lead, out, first, count), `page` elements a call; probe: an empty `out`
+        still makes one call with no array, which checks the snapshot and `first`."""
+        if probe and len(out) == 0:
+            self._check(fn(self._ctx, *lead, None, int(first), 0))
+        for at in range(0, len(out), int(page)):
+            n = min(int(page), len(out) - at)
+            self._check(fn(self._ctx, *lead, _ffi.ptr(out[at:at + n]), int(first) + at, n))
+        return out
+
+    def _field_download(self, info_fn, fn, first, count, page):
+        """Cells [first, first + count) of a field snapshot in region index order, or with both None the whole field shaped [z][y][x]."""
+        if first is None and count is None:
+            ext = [int(e) for e in info_fn()["ext"][0]]
+            return self._paged(fn, np.zeros(ext[0] * ext[1] * ext[2], dtype=np.uint16), 0, page).reshape(ext[2], ext[1], ext[0])
+        return self._paged(fn, np.zeros(int(count or 0), dtype=np.uint16), int(first or 0), page)
+
     def volume_create(self, origin, shape_xyz, chunk_size: int = 128, voxel_size: float = 1.0):
         o = (C.c_int32 * 3)(*[int(v) for v in origin])
         self._check(self._lib.blok_hip_volume_create(self._ctx, o, int(shape_xyz[0]), int(shape_xyz[1]), int(shape_xyz[2]),
@@ -116,8 +138,8 @@ class HipTracer:
     def volume_generate_terrain(self, params, region_lo=None, region_hi=None) -> int:
         """Procedural terrain into the resident volume (blok_hip.h: blok_hip_volume_generate_terrain): params a blok_amd.terrain.TerrainParams,
         the region in world voxels, half-open (both None = the whole box).  Returns the filled voxels written."""
-        lo = None if region_lo is None else (C.c_int32 * 3)(*[int(c) for c in region_lo])
-        hi = None if region_hi is None else (C.c_int32 * 3)(*[int(c) for c in region_hi])
+        lo = _vec3(region_lo)
+        hi = _vec3(region_hi)
         n = C.c_uint64(0)
         self._check(self._lib.blok_hip_volume_generate_terrain(self._ctx, C.byref(params), lo, hi, C.byref(n)))
         return int(n.value)
@@ -126,8 +148,8 @@ class HipTracer:
         """The volume's surface as merged quads (blok_hip.h: blok_hip_volume_extract_quads): the region in world voxels, half-open (both
         None = the whole box).  Returns the records as a structured array of _ffi.QUAD in canonical order, fetched `page` records at a
         time; with count_only the pair (n_quads, n_faces) and nothing is kept."""
-        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
-        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
         flags = (_ffi.QUADS_IGNORE_MATERIAL if ignore_material else 0) | (_ffi.QUADS_COUNT_ONLY if count_only else 0)
         n_quads, n_faces = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.blok_hip_volume_extract_quads(self._ctx, rlo, rhi, flags, C.byref(n_quads), C.byref(n_faces)))
@@ -138,13 +160,7 @@ class HipTracer:
 
     def volume_quads_download(self, first: int, count: int, page: int = 1 << 22) -> np.ndarray:
         """Records [first, first + count) of the last extraction's snapshot."""
-        out = np.zeros(int(count), dtype=_ffi.QUAD)
-        if count == 0:
-            self._check(self._lib.blok_hip_volume_quads_download(self._ctx, None, int(first), 0))
-        for at in range(0, int(count), int(page)):
-            n = min(int(page), int(count) - at)
-            self._check(self._lib.blok_hip_volume_quads_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
-        return out
+        return self._paged(self._lib.blok_hip_volume_quads_download, np.zeros(int(count), dtype=_ffi.QUAD), first, page)
 
     def volume_stamp_models(self, placements, mode: int = _ffi.STAMP_SET, density: float = 1.0) -> int:
         """Stamps placed models into the resident volume (blok_hip.h: blok_hip_volume_stamp_models): placements are INSTANCE records
@@ -159,8 +175,8 @@ class HipTracer:
         """A region of the resident volume (world voxels, half open; both None = the whole box) as a new model, in the lattice whose voxel
         (0, 0, 0) is the region's corner (blok_hip.h: blok_hip_volume_capture_model); cut = also clear the captured voxels.  Returns the
         model id; the model's voxel count is in last_capture_voxels."""
-        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
-        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
         model, n = C.c_uint32(0), C.c_uint64(0)
         self._check(self._lib.blok_hip_volume_capture_model(self._ctx, rlo, rhi, _ffi.CAPTURE_CUT if cut else 0, C.byref(model), C.byref(n)))
         self.last_capture_voxels = int(n.value)
@@ -170,31 +186,19 @@ class HipTracer:
         """Labels the connected components (6-neighbour) of a region of the resident volume (blok_hip.h: blok_hip_volume_label_components):
         the region in world voxels, half open (both None = the whole box).  The snapshot stays on the device until the next labelling;
         volume_labels_download / volume_components_download fetch it.  Returns (n_components, n_voxels)."""
-        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
-        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
         n_components, n_voxels = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.blok_hip_volume_label_components(self._ctx, rlo, rhi, 0, C.byref(n_components), C.byref(n_voxels)))
         return int(n_components.value), int(n_voxels.value)
 
     def volume_components_download(self, first: int, count: int, page: int = 1 << 22) -> np.ndarray:
         """Records [first, first + count) of the last labelling's snapshot: a structured array of _ffi.COMPONENT, sorted by label."""
-        out = np.zeros(int(count), dtype=_ffi.COMPONENT)
-        if count == 0:
-            self._check(self._lib.blok_hip_volume_components_download(self._ctx, None, int(first), 0))
-        for at in range(0, int(count), int(page)):
-            n = min(int(page), int(count) - at)
-            self._check(self._lib.blok_hip_volume_components_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
-        return out
+        return self._paged(self._lib.blok_hip_volume_components_download, np.zeros(int(count), dtype=_ffi.COMPONENT), first, page)
 
     def volume_labels_download(self, first: int, count: int, page: int = 1 << 24) -> np.ndarray:
         """Cells [first, first + count) of the last labelling's label array (region index order; _ffi.LABEL_EMPTY = empty cell)."""
-        out = np.zeros(int(count), dtype=np.uint32)
-        if count == 0:
-            self._check(self._lib.blok_hip_volume_labels_download(self._ctx, None, int(first), 0))
-        for at in range(0, int(count), int(page)):
-            n = min(int(page), int(count) - at)
-            self._check(self._lib.blok_hip_volume_labels_download(self._ctx, _ffi.ptr(out[at:at + n]), int(first) + at, n))
-        return out
+        return self._paged(self._lib.blok_hip_volume_labels_download, np.zeros(int(count), dtype=np.uint32), first, page)
 
     def volume_capture_component(self, label: int, cut: bool = False):
         """The voxels of the snapshot's component `label` that are still filled, as a new model in the lattice whose voxel (0, 0, 0) is the
@@ -223,8 +227,8 @@ class HipTracer:
         """Encodes a region of the resident volume (world voxels, half open; both None = the whole box) as a sparse brick stream kept on
         the device (blok_hip.h: blok_hip_volume_encode_bricks) until the next encode.  Returns the stream's info, one _ffi.BRICKS_INFO
         record; volume_bricks_download fetches the stream, volume_restore_bricks writes it back."""
-        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
-        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
         info = np.zeros(1, dtype=_ffi.BRICKS_INFO)
         self._check(self._lib.blok_hip_volume_encode_bricks(self._ctx, rlo, rhi, _ffi.BRICKS_FILLED_ONLY if filled_only else 0, _ffi.ptr(info)))
         return info
@@ -238,23 +242,15 @@ class HipTracer:
         """The last encode's stream as (info, records, density payload, material payload): _ffi.BRICKS_INFO, a structured array of
         _ffi.BRICK_RECORD and two uint32 arrays (bit patterns and ids), fetched `page` entries at a time."""
         info = self.volume_bricks_info()
-        records = np.zeros(int(info["n_bricks"][0]), dtype=_ffi.BRICK_RECORD)
-        for at in range(0, len(records), int(page)):
-            n = min(int(page), len(records) - at)
-            self._check(self._lib.blok_hip_volume_bricks_download(self._ctx, _ffi.ptr(records[at:at + n]), at, n))
-        payloads = []
-        for plane, key in ((0, "n_density"), (1, "n_material")):
-            out = np.zeros(int(info[key][0]), dtype=np.uint32)
-            for at in range(0, len(out), int(page)):
-                n = min(int(page), len(out) - at)
-                self._check(self._lib.blok_hip_volume_brick_payload_download(self._ctx, plane, _ffi.ptr(out[at:at + n]), at, n))
-            payloads.append(out)
+        records = self._paged(self._lib.blok_hip_volume_bricks_download, np.zeros(int(info["n_bricks"][0]), dtype=_ffi.BRICK_RECORD), 0, page, probe=False)
+        payloads = [self._paged(self._lib.blok_hip_volume_brick_payload_download, np.zeros(int(info[key][0]), dtype=np.uint32), 0, page, plane, probe=False)
+                    for plane, key in ((0, "n_density"), (1, "n_material"))]
         return info, records, payloads[0], payloads[1]
 
     def volume_restore_bricks(self, dst_lo=None, keep_others: bool = False):
         """Writes the last encode's stream back into the volume at dst_lo (None = where it was taken): undo, or copy and paste.  By default
         every cell of the destination is written; keep_others writes the stored cells only.  The next volume_rebuild installs the world."""
-        dlo = None if dst_lo is None else (C.c_int32 * 3)(*[int(c) for c in dst_lo])
+        dlo = _vec3(dst_lo)
         self._check(self._lib.blok_hip_volume_restore_bricks(self._ctx, dlo, _ffi.BRICKS_KEEP_OTHERS if keep_others else 0))
 
     def volume_decode_bricks(self, info, records, density_payload, material_payload, dst_lo=None, keep_others: bool = False):
@@ -263,7 +259,7 @@ class HipTracer:
         records = np.ascontiguousarray(records, dtype=_ffi.BRICK_RECORD).reshape(-1)
         dp = np.ascontiguousarray(density_payload, dtype=np.uint32).reshape(-1)
         mp = np.ascontiguousarray(material_payload, dtype=np.uint32).reshape(-1)
-        dlo = None if dst_lo is None else (C.c_int32 * 3)(*[int(c) for c in dst_lo])
+        dlo = _vec3(dst_lo)
         self._check(self._lib.blok_hip_volume_decode_bricks(self._ctx, _ffi.ptr(info), _ffi.ptr(records) if len(records) else None,
                                                             _ffi.ptr(dp) if len(dp) else None, _ffi.ptr(mp) if len(mp) else None, dlo,
                                                             _ffi.BRICKS_KEEP_OTHERS if keep_others else 0))
@@ -273,8 +269,8 @@ class HipTracer:
         to the nearest filled cell — to_empty: to the nearest empty cell; box_is_solid: the outside of the box counts as filled — and keeps
         it on the device (blok_hip.h: blok_hip_volume_distance_field) until the next field.  Returns the field's info, one
         _ffi.DISTANCE_INFO record; volume_distance_download fetches the values, volume_edit_by_distance thresholds them."""
-        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
-        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
         flags = (_ffi.DISTANCE_TO_EMPTY if to_empty else 0) | (_ffi.DISTANCE_BOX_IS_SOLID if box_is_solid else 0)
         info = np.zeros(1, dtype=_ffi.DISTANCE_INFO)
         self._check(self._lib.blok_hip_volume_distance_field(self._ctx, rlo, rhi, int(max_radius), flags, _ffi.ptr(info)))
@@ -288,18 +284,7 @@ class HipTracer:
     def volume_distance_download(self, first=None, count=None, page: int = 1 << 24) -> np.ndarray:
         """The last field's values (uint16, _ffi.DISTANCE_FAR = no source within the radius), fetched `page` cells at a time: cells
         [first, first + count) in region index order, or with both None the whole field shaped [z][y][x]."""
-        whole = first is None and count is None
-        if whole:
-            ext = self.volume_distance_info()["ext"][0]
-            first, count = 0, int(ext[0]) * int(ext[1]) * int(ext[2])
-        first, count = int(first or 0), int(count or 0)
-        out = np.zeros(count, dtype=np.uint16)
-        if count == 0:
-            self._check(self._lib.blok_hip_volume_distance_download(self._ctx, None, first, 0))
-        for at in range(0, count, int(page)):
-            n = min(int(page), count - at)
-            self._check(self._lib.blok_hip_volume_distance_download(self._ctx, _ffi.ptr(out[at:at + n]), first + at, n))
-        return out.reshape(int(ext[2]), int(ext[1]), int(ext[0])) if whole else out
+        return self._field_download(self.volume_distance_info, self._lib.blok_hip_volume_distance_download, first, count, page)
 
     def volume_edit_by_distance(self, op: int, d2: int, density: float = 1.0, material: int = 0) -> int:
         """Thresholds the last field at the squared distance d2 over its region (blok_hip.h: blok_hip_volume_edit_by_distance): op
@@ -317,8 +302,8 @@ class HipTracer:
         the least number of 6-neighbour steps to every cell, capped at max_steps, on the device (blok_hip.h: blok_hip_volume_flood_field)
         until the next flood.  Returns the field's info, one _ffi.FLOOD_INFO record; volume_flood_download fetches the values,
         volume_edit_by_flood thresholds them."""
-        rlo = None if lo is None else (C.c_int32 * 3)(*[int(c) for c in lo])
-        rhi = None if hi is None else (C.c_int32 * 3)(*[int(c) for c in hi])
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
         xyz = np.zeros((0, 3), np.int32) if seeds is None else np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
         info = np.zeros(1, dtype=_ffi.FLOOD_INFO)
         self._check(self._lib.blok_hip_volume_flood_field(self._ctx, rlo, rhi, _ffi.ptr(xyz) if len(xyz) else None, len(xyz), int(max_steps), int(flags),
@@ -339,18 +324,7 @@ class HipTracer:
     def volume_flood_download(self, first=None, count=None, page: int = 1 << 24) -> np.ndarray:
         """The last flood's values (uint16, _ffi.FLOOD_FAR = not reached or impassable), fetched `page` cells at a time: cells
         [first, first + count) in region index order, or with both None the whole field shaped [z][y][x]."""
-        whole = first is None and count is None
-        if whole:
-            ext = self.volume_flood_info()["ext"][0]
-            first, count = 0, int(ext[0]) * int(ext[1]) * int(ext[2])
-        first, count = int(first or 0), int(count or 0)
-        out = np.zeros(count, dtype=np.uint16)
-        if count == 0:
-            self._check(self._lib.blok_hip_volume_flood_download(self._ctx, None, first, 0))
-        for at in range(0, count, int(page)):
-            n = min(int(page), count - at)
-            self._check(self._lib.blok_hip_volume_flood_download(self._ctx, _ffi.ptr(out[at:at + n]), first + at, n))
-        return out.reshape(int(ext[2]), int(ext[1]), int(ext[0])) if whole else out
+        return self._field_download(self.volume_flood_info, self._lib.blok_hip_volume_flood_download, first, count, page)
 
     def volume_edit_by_flood(self, op: int, d: int = 0, density: float = 1.0, material: int = 0) -> int:
         """Thresholds the last flood at d steps over its region (blok_hip.h: blok_hip_volume_edit_by_flood): op _ffi.FLOOD_FILL fills the
