@@ -69,7 +69,7 @@ int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_mater
     ctx->stats.tree_bytes = node_bytes + tree.materials.size() * sizeof(uint32_t);
     ctx->stats.levels = tree.levels;
     for (int a = 0; a < 3; ++a) ctx->stats.origin[a] = tree.origin[a];
-    ctx->has_world = true; ctx->world_version += 1u;
+    ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
     ctx->world_voxel_size = ctx->pending_voxel_size;
     return rebuild_sun_map(ctx);
 }
@@ -339,7 +339,7 @@ int blok_hip_create(blok_hip_ctx** out_ctx, int device_ordinal, uint32_t width, 
         delete ctx;
         return set_error(nullptr, BLOK_ERR_HIP, "hipEventCreate failed");
     }
-    if (order_buffers(ctx, 0u, nullptr) != BLOK_OK || hipDeviceSynchronize() != hipSuccess) {      // the frame's scheduling buffers: here, so that no launch allocates
+    if (order_buffers(ctx, 0u, nullptr) != BLOK_OK || beam_cache_buffers(ctx) != BLOK_OK || hipDeviceSynchronize() != hipSuccess) {      // the frame's scheduling buffers: here, so that no launch allocates
         const std::string why = ctx->error;
         blok_hip_destroy(ctx);
         return set_error(nullptr, BLOK_ERR_OOM, "scheduling buffers: " + why);
@@ -355,6 +355,8 @@ int blok_hip_resize(blok_hip_ctx* ctx, uint32_t width, uint32_t height) {
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int rc = order_buffers(ctx, 0u, nullptr);      // grown here (a blocking entry), not by the next launch
     if (rc != BLOK_OK) return rc;
+    const int rc_cache = beam_cache_buffers(ctx);
+    if (rc_cache != BLOK_OK) return rc_cache;
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     return BLOK_OK;
 }
@@ -377,6 +379,7 @@ int blok_hip_release_stream(blok_hip_ctx* ctx, void* hip_stream) {
     auto it = ctx->beam_buffers.find(stream);
     if (it != ctx->beam_buffers.end()) { free_stream_scratch(it->second); ctx->beam_buffers.erase(it); }
     forget_device_activity(ctx, true, stream);
+    settle_beam_cache(ctx);                            // (a later stream may get this one's handle: nobody is "already waiting" by name any more)
     return BLOK_OK;
 }
 
@@ -395,6 +398,7 @@ void blok_hip_destroy(blok_hip_ctx* ctx) {
     for (auto& kv : ctx->beam_buffers) free_stream_scratch(kv.second);
     if (ctx->d_list_cost) (void)hipFree(ctx->d_list_cost);
     free_order(ctx);
+    free_beam_cache(ctx);
     if (ctx->order.h_live) (void)hipHostFree(ctx->order.h_live);
     if (ctx->order.h_depth) (void)hipHostFree(ctx->order.h_depth);
     if (ctx->order.h_fallback) (void)hipHostFree(ctx->order.h_fallback);
@@ -450,7 +454,7 @@ int blok_hip_upload_world(blok_hip_ctx* ctx, const blok_svo_node* nodes, size_t 
             for (int a = 0; a < 3; ++a) ctx->stats.origin[a] = gpu.origin[a];
             ctx->stats.n_ref_nodes = n_nodes;
             ctx->stats.n_sub_chunks = n_sub_chunks;
-            ctx->has_world = true; ctx->world_version += 1u;
+            ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
             ctx->built_on_device = true;
             ctx->world_voxel_size = vs;
             return rebuild_sun_map(ctx);
@@ -537,7 +541,7 @@ int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, u
             ctx->stats.tree_bytes = gpu.n_nodes * sizeof(blok::TreeNode) + gpu.n_voxels * sizeof(uint32_t);
             ctx->stats.levels = gpu.levels;
             for (int a = 0; a < 3; ++a) ctx->stats.origin[a] = gpu.origin[a];
-            ctx->has_world = true; ctx->world_version += 1u;
+            ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
             ctx->built_on_device = true;
             const int rc_sun = rebuild_sun_map(ctx);
             if (rc_sun != BLOK_OK || !ctx->dense_dda) return rc_sun;

@@ -286,6 +286,20 @@ int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk) {
     return BLOK_OK;
 }
 
+int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int enabled) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    ctx->beam_cache.enabled = enabled != 0;
+    blok::beam_cache_clear(ctx->beam_cache.policy);      // off: every launch searches, as before there was a cache; on again: views are admitted afresh
+    return BLOK_OK;
+}
+
+int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (out_hits) *out_hits = ctx->beam_cache.hits;
+    if (out_fills) *out_fills = ctx->beam_cache.fills;
+    return BLOK_OK;
+}
+
 int blok_hip_set_beam_budget(blok_hip_ctx* ctx, uint32_t max_node_visits) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     ctx->beam_budget = max_node_visits;

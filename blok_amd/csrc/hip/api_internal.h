@@ -25,6 +25,7 @@
 #include "trace_kernels.h"
 #include "dense_kernels.h"
 #include "launch_policy.h"
+#include "beam_cache.h"
 #include "tile_order.h"
 #include "path_args.h"
 #include "tree.h"
@@ -41,6 +42,7 @@ struct blok_hip_ctx {
     bool has_world = false;
     bool built_on_device = false;     // structure built by gpu_build.hip (else tree_build.cpp on the host)
     uint32_t world_version = 0;        // counts uploads and rebuilds: scheduling state measured on another world is dropped (TileOrder::key)
+    uint32_t tree_version = 0;         // counts every tree installed, a rebuild of the resident volume included (which keeps world_version, and with it the view's order): what was computed FROM the tree is dropped (beam_cache.h)
     bool tree_owned_by_volume = false; // d_nodes / d_tree_materials belong to the resident volume's scratch (gpu_build.h): never freed here
     bool force_host_build = false;
     blok_world_stats stats{};
@@ -136,6 +138,25 @@ struct blok_hip_ctx {
         void* tlas = nullptr; size_t n_tlas = 0;                          // instanced path launches: the instance BVH (tlas_core.h: TlasNode), nodes, grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
+    // The beam bounds of views at rest (beam_cache.h: key, admission, slots; api_launch.hip: the hazards).  A slot's buffer is written by the
+    // searches of ONE launch (the fill) and read by the walks of later launches of the same view, on any stream: the first reader on another
+    // stream waits for `ready`, and a slot is refilled only behind the held markers of every stream (api_launch.hip: hold_markers).
+    // Allocated by blok_hip_create / _resize for the finest beam tile over the whole frame, so that no launch allocates.
+    struct BeamCache {
+        bool enabled = true;                                // blok_hip_set_beam_cache
+        blok::BeamCachePolicy policy{};
+        struct Slot {
+            float* d_beam = nullptr;
+            hipEvent_t ready = nullptr;                     // behind the launch that filled the slot
+            hipStream_t producer = nullptr;                 // ... and its stream
+            bool settled = true;                            // `ready` has been seen complete: nobody waits any more
+            bool used = false;                              // filled at least once: launches that read it may be in flight
+            static constexpr uint32_t kWaited = 8;
+            hipStream_t waited[kWaited] = {}; uint32_t n_waited = 0;      // streams that already wait for `ready` (or are behind it)
+        } slots[blok::kBeamCacheSlots];
+        size_t capacity = 0;                                // floats per slot
+        uint64_t hits = 0, fills = 0;                       // blok_hip_beam_cache_counters
+    } beam_cache;
     // Longest-first scheduling of the walk for a camera at rest (tile_order.h; rectangle launches of the static forms): every walk wave
     // leaves the clocks it spent in d_cost (one buffer per context, for the launch geometry in `key`).  Every `interval` launches a
     // radix sort of a snapshot of those costs follows the frame on its stream: it writes the order buffer that is NOT in use, and a later
@@ -243,6 +264,9 @@ int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, ui
 int beam_buffer(blok_hip_ctx* ctx, hipStream_t stream, size_t n, float** out);
 void free_order(blok_hip_ctx* ctx);
 int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream);
+int beam_cache_buffers(blok_hip_ctx* ctx);              // at create / resize: the slots' buffers for the frame size (a blocking entry)
+void free_beam_cache(blok_hip_ctx* ctx);
+void settle_beam_cache(blok_hip_ctx* ctx);               // behind a device-wide synchronisation: every slot's producer has finished
 int live_list(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_searches, uint32_t per_search);
 int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, uint32_t blocks, hipStream_t stream, uint32_t tiles_of_rank = 0,
                  const blok::TileFrames* frames = nullptr);

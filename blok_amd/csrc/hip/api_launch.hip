@@ -2,6 +2,7 @@
 // orders cached per view and what keeps them (markers, sorts, shifts), the joint launch's slots, the list forms' buffers, and
 // launch_timed, through which every rectangle / tile launch goes.  Split from api.hip in round 4.
 #include "api_internal.h"
+#include "beam.h"
 #include <cstdlib>
 
 namespace blok_api {
@@ -388,6 +389,97 @@ static int list_costs(blok_hip_ctx* ctx, blok::TraceArgs& args, uint32_t wave_ti
     return BLOK_OK;
 }
 
+// ---- the beam bounds of views at rest (beam_cache.h: the key, admission, the slots; api_internal.h: BeamCache) ---------------------------
+void free_beam_cache(blok_hip_ctx* ctx) {
+    auto& B = ctx->beam_cache;
+    for (auto& sl : B.slots) {
+        if (sl.d_beam) (void)hipFree(sl.d_beam);
+        if (sl.ready) (void)hipEventDestroy(sl.ready);
+        sl = blok_hip_ctx::BeamCache::Slot{};
+    }
+    B.capacity = 0;
+    blok::beam_cache_clear(B.policy);
+}
+
+// One float per beam tile of the whole frame at the finest beam tile there is (blok_hip_set_beam: 8 pixels), per slot: no rectangle, no
+// beam setting needs more, so no launch ever allocates on the cache's account.  Grown only (a device-wide wait: frames in flight may read
+// the old buffers); what the slots held is dropped with them.
+int beam_cache_buffers(blok_hip_ctx* ctx) {
+    auto& B = ctx->beam_cache;
+    const size_t want = static_cast<size_t>((ctx->width + 7u) / 8u) * ((ctx->height + 7u) / 8u);
+    if (B.capacity >= want) return BLOK_OK;
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    const bool enabled = B.enabled;
+    free_beam_cache(ctx);
+    B.enabled = enabled;
+    for (auto& sl : B.slots) {
+        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&sl.d_beam), want * sizeof(float)));
+        BLOK_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+    }
+    B.capacity = want;
+    return BLOK_OK;
+}
+
+void settle_beam_cache(blok_hip_ctx* ctx) {
+    for (auto& sl : ctx->beam_cache.slots) { sl.settled = true; sl.n_waited = 0; }
+}
+
+static blok::BeamKey beam_key(const blok_hip_ctx* ctx, blok::RayMode mode, const blok::TraceArgs& args) {
+    blok::BeamKey k{};
+    static_assert(sizeof(k.cam) == sizeof(blok_camera), "beam_cache.h: BeamKey::cam is blok_camera, byte for byte");
+    std::memcpy(k.cam, &args.cam, sizeof(blok_camera));
+    k.x0 = args.x0; k.y0 = args.y0; k.w = args.w; k.h = args.h;
+    k.frame_w = args.frame_w; k.frame_h = args.frame_h;
+    k.beam_tile = args.beam_tile; k.beam_budget = args.beam_budget;
+    k.tuning = blok::kBeamCoarsen1 | (blok::kBeamCoarsen2 << 8) | (static_cast<uint32_t>(BLOK_BEAM_STOP_LEVEL) << 16);
+    k.ray_mode = static_cast<uint32_t>(mode);
+    k.levels = args.levels;
+    for (int a = 0; a < 3; ++a) k.origin[a] = args.origin[a];
+    std::memcpy(&k.voxel_bits, &args.voxel_size, sizeof(uint32_t));
+    const uint64_t nodes = reinterpret_cast<uintptr_t>(args.nodes);
+    k.nodes_lo = static_cast<uint32_t>(nodes); k.nodes_hi = static_cast<uint32_t>(nodes >> 32);
+    k.world_version = ctx->world_version; k.tree_version = ctx->tree_version;
+    return k;
+}
+
+// Before a rectangle launch of a static form: does it search, search into a slot, or walk from a slot?  Points args.beam at the slot and
+// deals with whoever else uses it.
+static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan) {
+    auto& B = ctx->beam_cache;
+    *plan = blok::plan_beam_cache(B.policy, beam_key(ctx, mode, args));
+    if (plan->action == blok::BeamAction::Search) return BLOK_OK;
+    auto& sl = B.slots[plan->slot];
+    if (plan->action == blok::BeamAction::Hit) {
+        // the launch that filled the slot may still be running, on another stream: the first reader there waits for it
+        if (!sl.settled && stream != sl.producer) {
+            bool waits = false;
+            for (uint32_t k = 0; k < sl.n_waited && !waits; ++k) waits = sl.waited[k] == stream;
+            if (!waits) {
+                if (hipEventQuery(sl.ready) == hipSuccess) { sl.settled = true; sl.n_waited = 0; }
+                else {
+                    (void)hipGetLastError();                             // hipErrorNotReady is an answer, not a failure
+                    BLOK_HIP_TRY(ctx, hipStreamWaitEvent(stream, sl.ready, 0));
+                    if (sl.n_waited < blok_hip_ctx::BeamCache::Slot::kWaited) sl.waited[sl.n_waited++] = stream;      // (more streams than that wait again next time: harmless)
+                }
+            }
+        }
+        B.hits += 1u;
+    } else {
+        // Nothing in flight may read the slot while the searches rewrite it (nor still be writing it): whatever used it was issued before
+        // now, on some stream of this context, so every stream's marker is held here and this stream waits for the others' (its own
+        // earlier launches are in front of it anyway).  Once per view that comes to rest, and not at all for a slot never filled.
+        if (sl.used) {
+            hold_markers(ctx);
+            const int rc = wait_for_held_markers(ctx, stream);
+            if (rc != BLOK_OK) return rc;
+        }
+        sl.used = true; sl.settled = false; sl.producer = stream; sl.n_waited = 0;
+        B.fills += 1u;
+    }
+    args.beam = sl.d_beam; args.beam_slots = nullptr; args.beam_serial = 0u;      // plain floats, whatever form was planned
+    return BLOK_OK;
+}
+
 // Rect / Tiles launches run the beam pre-pass first, on the same stream (tiles_of_rank: Tiles only; frames: several frames of a rank's
 // tiles in one launch, `blocks` and the beam tiles then count ONE frame).
 int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, uint32_t blocks, hipStream_t stream,
@@ -477,6 +569,21 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     } else { args.rank_of = nullptr; args.launched = 0u; }
     if (ctx->timing && !capturing) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, stream));
     args.miss_in_walk = static_form && !args.rank_of && ctx->miss_in_walk ? 1u : 0u;
+    // A view at rest keeps its beam bounds (beam_cache.h): rectangle launches of the automatic form — the explicit forms stay what they are
+    // there to be compared with, a rank's tiles and several frames per launch are left alone — that are not being captured.
+    blok::BeamCachePlan cached{blok::BeamAction::Search, -1};
+    if (ctx->beam_cache.enabled && rect && !frames && !capturing && static_form && ctx->launch_form == blok::kFormAuto && n_beams && n_beams <= ctx->beam_cache.capacity) {
+        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached);
+        if (rc != BLOK_OK) return rc;
+        // the searches that fill a slot write plain floats: the two-launch form, this once
+        if (cached.action == blok::BeamAction::Fill && plan.kind == blok::LaunchKind::Joint) { plan.kind = blok::LaunchKind::TwoLaunches; ctx->last_launch_kind = static_cast<int>(plan.kind); }
+    }
+    if (cached.action == blok::BeamAction::Hit) {
+        // no searches: the walk over the view's live prefix, from the kept bounds; in front of it, what the search waves do besides searching
+        // (the miss pixels, unless the walk writes them; the wave tiles the prefix has no workgroup for) — last_launch_kind stays the policy's
+        if (!args.miss_in_walk) blok::launch_beam_fill(mode, args, n_beams, stream);
+        blok::launch_trace(mode, args, walk_blocks, stream);
+    } else
     switch (plan.kind) {
         case blok::LaunchKind::Walk:
             if (frames) blok::launch_tile_frames(args, fr, stream); else blok::launch_trace(mode, args, blocks, stream);
@@ -493,7 +600,10 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
             blok::launch_list_walk(mode, args, frames ? &fr : nullptr, plan.walkers, stream);
             break;
     }
-    BLOK_HIP_TRY(ctx, hipGetLastError());
+    const hipError_t launch_error = hipGetLastError();
+    if (launch_error != hipSuccess && cached.action == blok::BeamAction::Fill) ctx->beam_cache.policy.valid[cached.slot] = false;      // bounds nobody wrote are nobody's to keep
+    BLOK_HIP_TRY(ctx, launch_error);
+    if (cached.action == blok::BeamAction::Fill) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->beam_cache.slots[cached.slot].ready, stream));
     if (ctx->timing && !capturing) { BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_end, stream)); ctx->timed = true; }
     if (args.fallback_tiles) BLOK_HIP_TRY(ctx, hipMemcpyAsync(ctx->order.h_fallback, ctx->order.d_fallback, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     if (orderable) { const int rc = order_after_launch(ctx, args, blocks, n_beams, stream, order_plan); if (rc != BLOK_OK) return rc; }

@@ -625,7 +625,7 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
     ctx->stats.tree_bytes = gpu.n_nodes * sizeof(blok::TreeNode) + gpu.n_voxels * sizeof(uint32_t);
     ctx->stats.levels = gpu.levels;
     for (int a = 0; a < 3; ++a) ctx->stats.origin[a] = gpu.origin[a];
-    ctx->has_world = true;
+    ctx->has_world = true; ctx->tree_version += 1u;      // (not world_version: see below — but what was computed from the tree, the beam bounds of a view at rest, goes)
     // (an edited world keeps the view's order: a brush changes few tiles' costs, and the tiles that have become live are walked by their
     // search waves until the next sort — which comes at the base interval again; measured, a brush of radius 10 before every frame: 207 us
     // per frame with the order kept, 270 with it dropped)

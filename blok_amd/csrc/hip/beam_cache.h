@@ -1,0 +1,89 @@
+// The beam bounds of a view at rest, kept from launch to launch: which launches may reuse them, when a view is admitted, which slot it
+// takes.  A pure function of a key and a little state, like launch_policy.h, so that the table can be tested on the host
+// (tests/test_beam_cache_policy.py compiles this header with g++; nothing here touches HIP).  No reference counterpart: the reference
+// lets Vulkan RT hardware cull boxes per ray (blok/src/renderer_raytracing.cpp:15-254) and has no pre-pass to keep.
+//
+// What is kept is the OUTPUT of beam_kernel alone (trace_kernels.hip; beam.h): one start parameter per beam tile, a pure function of the
+// key below.  The records and the pixels of a frame are produced by walking every live tile of every frame as before; a launch that
+// hits walks from the same start parameters its own searches would have found, so it writes the same bytes.
+#ifndef BLOK_BEAM_CACHE_H
+#define BLOK_BEAM_CACHE_H
+#include <stdint.h>
+#include <string.h>
+
+namespace blok {
+
+// Every input of a rectangle launch's searches — the TraceArgs fields beam_block<Rect>, beam_start and beam_search read on the way to a
+// start parameter (trace_kernels.hip, beam.h), and what stands for the memory behind them:
+//   cam                          beam_start: the tile's central direction and side planes.  BYTE FOR BYTE: bounds of a nearby view are
+//                                not conservative for this one (api_launch.hip's camera_near is a tolerance for scheduling, not for this)
+//   x0, y0, w, h                 beam_block: the tile's pixel rectangle, cut at the launch rectangle's edge (beam_bx follows from w)
+//   frame_w, frame_h             beam_start: pixel -> direction
+//   beam_tile                    beam_block: the tile's size
+//   beam_budget                  beam_search: node visits (0 = kBeamMaxVisits) — a search that runs out answers with a looser bound
+//   tuning                       beam.h's compile-time constants that shape the answer the same way (coarsening eighths, stop level)
+//   ray_mode                     Rect only is cached; in the key so that no other mode can ever match
+//   levels, origin, voxel_bits   beam_search: the tree's cube; beam_start: voxel_size and its reciprocal (a power of two)
+//   nodes_lo, nodes_hi           beam_search: the tree's address
+//   world_version, tree_version  the tree's CONTENT: uploads count in both, a rebuild of the resident volume in tree_version alone (it
+//                                keeps the view's order, api_volume.hip, but not its bounds)
+// Not in the key, because no search reads it: the jitter (beam.h grows the frustum by a pixel on every side, which covers every
+// sub-pixel offset), tmin / tmax, the outputs, the order and everything else that decides who writes what.
+struct BeamKey {
+    uint32_t cam[14];
+    uint32_t x0, y0, w, h;
+    uint32_t frame_w, frame_h;
+    uint32_t beam_tile, beam_budget, tuning;
+    uint32_t ray_mode;
+    uint32_t levels;
+    int32_t origin[3];
+    uint32_t voxel_bits;
+    uint32_t nodes_lo, nodes_hi;
+    uint32_t world_version, tree_version;
+};
+static_assert(sizeof(BeamKey) == 33 * sizeof(uint32_t), "BeamKey is compared with memcmp: no padding");
+
+inline bool beam_key_equal(const BeamKey& a, const BeamKey& b) { return memcmp(&a, &b, sizeof(BeamKey)) == 0; }
+
+constexpr int kBeamCacheSlots = 4;             // as many views as the orders (api_internal.h: TileOrder::kSlots)
+
+enum class BeamAction : int {
+    Search = 0,                                // the launch runs its searches as ever
+    Fill = 1,                                  // ... and they write into slot `slot`, which holds the view from here on
+    Hit = 2,                                   // no searches: the walk reads slot `slot`
+};
+struct BeamCachePlan { BeamAction action; int slot; };
+
+struct BeamCachePolicy {
+    BeamKey key[kBeamCacheSlots];
+    bool valid[kBeamCacheSlots];
+    uint64_t last_use[kBeamCacheSlots];        // serial of the latest launch that filled or hit the slot
+    BeamKey last;                              // key of the previous launch that asked
+    bool have_last;
+    uint64_t serial;                           // launches that asked so far
+};
+
+inline void beam_cache_clear(BeamCachePolicy& s) {
+    for (int k = 0; k < kBeamCacheSlots; ++k) { s.valid[k] = false; s.last_use[k] = 0u; }
+    s.have_last = false;
+}
+
+// Admission: a view is cached when the same key arrives a second time IN A ROW — that launch still searches, into a slot — and hits
+// from the third launch on.  A camera in motion never repeats a key, so it never fills, never evicts and never pays anything.
+// Slots: an empty one, else the one used longest ago.
+inline BeamCachePlan plan_beam_cache(BeamCachePolicy& s, const BeamKey& k) {
+    s.serial += 1u;
+    const bool again = s.have_last && beam_key_equal(s.last, k);
+    s.last = k; s.have_last = true;
+    for (int i = 0; i < kBeamCacheSlots; ++i)
+        if (s.valid[i] && beam_key_equal(s.key[i], k)) { s.last_use[i] = s.serial; return {BeamAction::Hit, i}; }
+    if (!again) return {BeamAction::Search, -1};
+    int target = -1;
+    for (int i = 0; i < kBeamCacheSlots && target < 0; ++i) if (!s.valid[i]) target = i;
+    if (target < 0) { target = 0; for (int i = 1; i < kBeamCacheSlots; ++i) if (s.last_use[i] < s.last_use[target]) target = i; }
+    s.key[target] = k; s.valid[target] = true; s.last_use[target] = s.serial;
+    return {BeamAction::Fill, target};
+}
+
+}  // namespace blok
+#endif

@@ -281,6 +281,9 @@ void launch_list_walk(RayMode mode, const TraceArgs& args, const TileFrames* fra
 // Number of beam tiles of a launch (= floats of TraceArgs::beam) and the pre-pass itself; Rect and Tiles only.
 uint32_t beam_tiles(RayMode mode, const TraceArgs& args, uint32_t tiles_of_rank);
 void launch_beam(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hipStream_t stream);
+// Behind a launch whose start parameters are already in args.beam (plain floats; Rect only): what the search waves do for their tiles
+// besides searching — miss pixels of empty tiles (miss_in_walk 0), wave tiles a prefix launch has no walk workgroup for.
+void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

@@ -345,7 +345,9 @@ __device__ __forceinline__ const TraceArgs& kernel_args() {
 // One wave per beam tile: TraceArgs::beam[tile] = conservative start parameter of the tile's rays, or kBeamNone.
 // list_search / list_task_base (list launches): this search's index in the launch and the first task id of its frame.
 // lds_stack: the walk's stack for the wave tiles a search walks itself (launches over a prefix of the order, TraceArgs::rank_of), else null.
-template <RayMode MODE>
+// kKept (beam_fill_kernel): the start parameter is not searched for but read from TraceArgs::beam, where an earlier launch of this very view
+// left it (beam_cache.h); nothing is published, and everything else a search wave does for its tile behind the search happens as ever.
+template <RayMode MODE, bool kKept = false>
 __device__ __forceinline__ void beam_block(const TraceArgs& A, const uint32_t b, const uint32_t n_beam_tiles, [[maybe_unused]] uint4* lds_stack = nullptr,
                                            const uint32_t list_search = 0u, const uint32_t list_task_base = 0u) {
     const uint32_t lane = threadIdx.x;
@@ -370,13 +372,17 @@ __device__ __forceinline__ void beam_block(const TraceArgs& A, const uint32_t b,
         px = tile_x0 + (sub % per_side) * B; py = tile_y0 + (sub / per_side) * B;
         px_end = px + B; py_end = py + B;
     }
-    uint32_t visits = 0;
-    // (the count is always taken, one scalar subtraction: through a pointer that may be null it was a variable in scratch memory)
-    const float t0 = padding ? kBeamNone : beam_start(A, static_cast<float>(px), static_cast<float>(py), static_cast<float>(px_end), static_cast<float>(py_end), lane, kBeamNone,
-                                                      &visits);
-    if (A.debug_visits && lane == 0) A.debug_visits[b] = visits;
-    if (A.list.entries) list_publish<MODE>(A, list_search, list_task_base, b, t0, lane);      // list launches: the live wave tiles go onto the frame's list
-    else if (lane == 0) { if (A.beam_slots) publish_beam(A.beam_slots + b, A.beam_serial, t0); else A.beam[b] = t0; }
+    float t0;
+    if constexpr (kKept) t0 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(A.beam[b])));
+    else {
+        uint32_t visits = 0;
+        // (the count is always taken, one scalar subtraction: through a pointer that may be null it was a variable in scratch memory)
+        t0 = padding ? kBeamNone : beam_start(A, static_cast<float>(px), static_cast<float>(py), static_cast<float>(px_end), static_cast<float>(py_end), lane, kBeamNone,
+                                              &visits);
+        if (A.debug_visits && lane == 0) A.debug_visits[b] = visits;
+        if (A.list.entries) list_publish<MODE>(A, list_search, list_task_base, b, t0, lane);      // list launches: the live wave tiles go onto the frame's list
+        else if (lane == 0) { if (A.beam_slots) publish_beam(A.beam_slots + b, A.beam_serial, t0); else A.beam[b] = t0; }
+    }
     if (t0 >= kBeamNone && (A.list.entries || !A.miss_in_walk) && (A.out || A.out_rgba)) {
         // no ray of this tile can hit anything: its pixels are written here, 64 at a time (a list launch has no walk wave for the tile;
         // in the other forms the tile's trace waves exit at once)
@@ -445,6 +451,17 @@ __global__ __launch_bounds__(64) void beam_kernel(const TraceArgs, const uint32_
     extern __shared__ uint4 lds_stack[];       // launch_beam sizes it whenever the searches may walk (TraceArgs::rank_of), else 0 bytes and unused
     const TraceArgs& A = kernel_args();
     beam_block<MODE>(A, blockIdx.x, n_beam_tiles, A.rank_of ? lds_stack : nullptr, blockIdx.x, 0u);
+}
+
+// In place of beam_kernel when the launch's start parameters are already in TraceArgs::beam (a view at rest, beam_cache.h): one wave per
+// beam tile does what the search wave does BEHIND its search — the miss pixels of a tile without anything in it (unless the walk writes
+// them), the wave tiles of a live tile that a prefix launch has no walk workgroup for — and nothing else: a live tile whose wave tiles
+// all have their walk workgroup costs its wave a load and a few comparisons.
+template <RayMode MODE>
+__global__ __launch_bounds__(64) void beam_fill_kernel(const TraceArgs, const uint32_t n_beam_tiles) {
+    extern __shared__ uint4 lds_stack[];       // as for beam_kernel: sized by the launch whenever the waves may walk (TraceArgs::rank_of)
+    const TraceArgs& A = kernel_args();
+    beam_block<MODE, true>(A, blockIdx.x, n_beam_tiles, A.rank_of ? lds_stack : nullptr);
 }
 
 // ---- joint launch: the pre-pass waves and the walk waves in ONE grid, statically ------------------------------------------
@@ -1146,6 +1163,12 @@ void launch_beam(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hip
     const size_t lds = args.rank_of ? frame_lds_bytes(args) : 0;
     if (mode == RayMode::Rect) hipLaunchKernelGGL(beam_kernel<RayMode::Rect>, dim3(n_beam_tiles), dim3(64), lds, stream, args, n_beam_tiles);
     else hipLaunchKernelGGL(beam_kernel<RayMode::Tiles>, dim3(n_beam_tiles), dim3(64), lds, stream, args, n_beam_tiles);
+}
+
+void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hipStream_t stream) {
+    if (n_beam_tiles == 0 || mode != RayMode::Rect || !args.beam || args.beam_slots || args.list.entries) return;
+    const size_t lds = args.rank_of ? frame_lds_bytes(args) : 0;      // as in launch_beam
+    hipLaunchKernelGGL(beam_fill_kernel<RayMode::Rect>, dim3(n_beam_tiles), dim3(64), lds, stream, args, n_beam_tiles);
 }
 
 size_t frame_lds_bytes(const TraceArgs& args) { return static_cast<size_t>(args.levels > 1 ? args.levels - 1 : 1) * kBlock * sizeof(uint4); }

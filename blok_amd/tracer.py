@@ -502,6 +502,17 @@ class HipTracer:
         """Empty tiles' miss pixels: written by the walk launch's waves (True, default) or by the pre-pass (blok_hip.h)."""
         self._check(self._lib.blok_hip_set_miss_writer(self._ctx, 1 if in_walk else 0))
 
+    def set_beam_cache(self, enabled: bool):
+        """Keep the beam bounds of a view at rest from launch to launch (default on; blok_hip_debug.h); off = every launch searches.
+        Never changes a result."""
+        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, 1 if enabled else 0))
+
+    def beam_cache_counters(self):
+        """Diagnostic: (hits, fills) — launches so far that walked from kept beam bounds, and that searched into a slot."""
+        hits, fills = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_beam_cache_counters(self._ctx, C.byref(hits), C.byref(fills)))
+        return int(hits.value), int(fills.value)
+
     def set_beam_budget(self, max_node_visits: int):
         """Node visits a beam search may spend (0 = default); running out is answered conservatively, never changes a result."""
         self._check(self._lib.blok_hip_set_beam_budget(self._ctx, max_node_visits))

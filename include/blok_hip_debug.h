@@ -130,6 +130,14 @@ int blok_hip_set_joint_prefix_limit(blok_hip_ctx* ctx, uint32_t max_walk_waves);
  * those tiles — they are launched anyway and have nothing else to do — 0 = the pre-pass wave of the tile, 1 024 pixels each, which
  * puts ~120 MB of stores on the pre-pass's critical path (4K, 73 % sky).  Never changes a result. */
 int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk);
+/* The beam bounds of a view at rest: 1 (default) = a rectangle launch of the automatic form whose camera, rectangle,
+ * beam settings and world are those of the launch before it, byte for byte, leaves its start parameters in one of four slots of the
+ * context, and every later launch of that view walks from them without searching; 0 = every launch searches (the launches of a library
+ * without the cache, one for one).  Either way the slots are emptied.  blok_hip_last_launch_kind goes on reporting the form the launch
+ * policy chose for the device's state, also for a launch that walked from kept bounds (a plain trace launch).  Never changes a result. */
+int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int enabled);
+/* Launches so far that walked from kept bounds (hits) and that searched into a slot (fills); either pointer may be null. */
+int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills);
 /* Node visits one beam search may spend (0 = the default, 256; searches average 35).  A search that runs out answers with the
  * lower bound over the cells it has not visited yet — valid, only less tight — never "none", so the frame is the same whatever
  * the budget (tests/test_gpu_parity.py runs with budgets of 1-64 visits against an unlimited search).  The pre-pass lasts as
