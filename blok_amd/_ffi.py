@@ -74,6 +74,19 @@ FLOOD_THROUGH_FILLED, FLOOD_SAME_MATERIAL = 1, 2  # = BLOK_FLOOD_THROUGH_FILLED,
 FLOOD_FAR = 0xFFFF                                # = BLOK_FLOOD_FAR
 FLOOD_MAX_STEPS = 65534                           # = BLOK_FLOOD_MAX_STEPS
 FLOOD_FILL, FLOOD_FILL_UNREACHED, FLOOD_PAINT, FLOOD_CLEAR = 0, 1, 2, 3      # = BLOK_FLOOD_FILL / _FILL_UNREACHED / _PAINT / _CLEAR
+# = blok_columns_info: what a column field snapshot holds, 64 bytes
+COLUMNS_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("axis", "<u4"), ("min_top", "<u4"), ("max_top", "<u4"),
+                         ("reserved", "<u4"), ("n_columns", "<u8"), ("n_hit", "<u8")])
+COLUMNS_FROM_LOW = 1                              # = BLOK_COLUMNS_FROM_LOW
+COLUMNS_NONE = 0xFFFF                             # = BLOK_COLUMNS_NONE
+# = blok_scatter_entry (24 bytes), blok_scatter_params (64 bytes), blok_scatter_info (72 bytes)
+SCATTER_ENTRY = np.dtype([("model", "<u4"), ("weight", "<u4"), ("anchor", "<i4", 3), ("sink", "<i4")])
+SCATTER_PARAMS = np.dtype([("seed", "<u4"), ("flags", "<u4"), ("cell_log2", "<u4"), ("probability", "<u4"), ("surface_material", "<u4"), ("min_y", "<i4"),
+                           ("max_y", "<i4"), ("radius", "<u4"), ("max_rise", "<u4"), ("max_drop", "<u4"), ("reserved", "<u4", 6)])
+SCATTER_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("n_cells", "<u8"), ("n_placed", "<u8"), ("n_rejected", "<u8", 5), ("reserved", "<u8")])
+SCATTER_ANY_MATERIAL, SCATTER_ROTATE, SCATTER_MIRROR = 1, 2, 4      # = BLOK_SCATTER_ANY_MATERIAL / _ROTATE / _MIRROR
+SCATTER_MAX_ENTRIES = 16                          # = BLOK_SCATTER_MAX_ENTRIES
+SCATTER_NO_LIMIT = 0xFFFF                         # max_rise / max_drop: no limit
 
 
 def flood_seed_face(f: int) -> int:
@@ -84,7 +97,8 @@ def flood_seed_face(f: int) -> int:
 assert SVO_NODE.itemsize == 16 and SUB_CHUNK.itemsize == 48 and MATERIAL.itemsize == 32
 assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and INSTANCE.itemsize == 32 and QUAD.itemsize == 32
 assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD.itemsize == 24 and BRICKS_INFO.itemsize == 64
-assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64
+assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_INFO.itemsize == 64
+assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
 
 
 class GBuffer(C.Structure):
@@ -225,6 +239,9 @@ HOST_SYMBOLS = {
                                    C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_flood_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "blok_column_field": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blok_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -374,6 +391,13 @@ HIP_SYMBOLS = {
     "blok_hip_volume_flood_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_volume_flood_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_edit_by_flood": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_column_field": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_columns_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_volume_columns_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_scatter_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_scatter_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_volume_scatter_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_scatter_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -105,6 +105,8 @@ struct blok_hip_ctx {
     blok::GpuBricks bricks;              // of the last blok_hip_volume_encode_bricks
     blok::GpuDistance distance;          // of the last blok_hip_volume_distance_field
     blok::GpuFlood flood;                // of the last blok_hip_volume_flood_field
+    blok::GpuColumns columns;            // of the last blok_hip_volume_column_field
+    blok::GpuScatter scatter;            // of the last blok_hip_volume_scatter_models: it goes with the column snapshot it was made from
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
     float* d_sun_map = nullptr;

@@ -6,6 +6,7 @@
 #include "../common/bricks_core.h"
 #include "../common/distance_core.h"
 #include "../common/flood_core.h"
+#include "../common/columns_core.h"
 #include "../common/region_core.h"
 #include "device_mem.h"
 #include <chrono>
@@ -21,6 +22,8 @@ void free_volume_snapshots(blok_hip_ctx* ctx) {
     blok::gpu_bricks_free(&ctx->bricks);
     blok::gpu_field_free(&ctx->distance);
     blok::gpu_field_free(&ctx->flood);
+    blok::gpu_columns_free(&ctx->columns);
+    blok::gpu_scatter_free(&ctx->scatter);
 }
 }  // namespace blok_api
 
@@ -569,6 +572,80 @@ int blok_hip_volume_edit_by_flood(blok_hip_ctx* ctx, int op, uint32_t d, float d
     const blok::GpuBuildStatus st = blok::gpu_volume_edit_by_flood(&ctx->volume, &ctx->flood, op, d, density, material, &n_voxels, &why);
     if (out_n_voxels) *out_n_voxels = n_voxels;
     return volume_status(ctx, st, why);
+}
+
+int blok_hip_volume_column_field(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t axis, uint32_t flags,
+                                 blok_columns_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (const int rule = blok::columns::check_field_args(axis, flags)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("column_field: ") + blok::columns::field_rule_text(rule));
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "column_field", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    blok::GpuColumns snapshot;
+    // (edits are enqueued on the null stream, and so is this: it reads the masks they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_column_field(&ctx->volume, lo, hi, axis, flags, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    blok::gpu_columns_free(&ctx->columns);
+    blok::gpu_scatter_free(&ctx->scatter);                 // (made from the snapshot that has just gone)
+    ctx->columns = snapshot; ctx->columns.taken = true;
+    if (out_info) *out_info = snapshot.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_columns_info(blok_hip_ctx* ctx, blok_columns_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->columns.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "columns_info: no snapshot (blok_hip_volume_column_field)");
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "columns_info: null output");
+    *out_info = ctx->columns.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_columns_download(blok_hip_ctx* ctx, uint32_t plane, void* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const blok::GpuColumns& c = ctx->columns;
+    if (c.taken && plane > 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "columns_download: plane above 1");
+    return ranged_download(ctx, "columns_download", "blok_hip_volume_column_field", c.taken, c.info.n_columns, plane == 0u ? static_cast<const void*>(c.d_top) : c.d_material,
+                           plane == 0u ? sizeof(uint16_t) : sizeof(uint32_t), out_host, first, count);
+}
+
+int blok_hip_volume_scatter_models(blok_hip_ctx* ctx, const blok_scatter_params* params, const blok_scatter_entry* entries_host, uint32_t n_entries,
+                                   blok_scatter_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (const int rule = blok::columns::check_scatter_args(ctx->columns.taken ? &ctx->columns.info : nullptr, params, entries_host, n_entries))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("scatter_models: ") + blok::columns::scatter_rule_text(rule));
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string why;
+    blok::GpuScatter table;
+    const blok::GpuBuildStatus st = blok::gpu_columns_scatter(&ctx->columns, *params, entries_host, n_entries, &table, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    blok::gpu_scatter_free(&ctx->scatter);
+    ctx->scatter = table; ctx->scatter.taken = true;
+    if (out_info) *out_info = table.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_scatter_info(blok_hip_ctx* ctx, blok_scatter_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->scatter.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "scatter_info: no table (blok_hip_volume_scatter_models)");
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "scatter_info: null output");
+    *out_info = ctx->scatter.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_scatter_download(blok_hip_ctx* ctx, blok_instance* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const blok::GpuScatter& s = ctx->scatter;
+    return ranged_download(ctx, "scatter_download", "blok_hip_volume_scatter_models", s.taken, s.info.n_placed, s.d_table, sizeof(blok_instance), out_host, first, count);
+}
+
+int blok_hip_volume_scatter_device(blok_hip_ctx* ctx, const blok_instance** out_dev, uint64_t* out_count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->scatter.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "scatter_device: no table (blok_hip_volume_scatter_models)");
+    if (!out_dev || !out_count) return set_error(ctx, BLOK_ERR_INVALID_ARG, "scatter_device: null output");
+    *out_dev = ctx->scatter.d_table; *out_count = ctx->scatter.info.n_placed;
+    return BLOK_OK;
 }
 
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {

@@ -253,6 +253,32 @@ GpuBuildStatus gpu_volume_flood_field(const GpuVolume* v, const uint32_t lo[3], 
 // Writes the store, then refreshes the region as every edit does.  Blocking.
 GpuBuildStatus gpu_volume_edit_by_flood(GpuVolume* v, const GpuFlood* field, int op, uint32_t d, float density, uint32_t material,
                                         uint64_t* out_n_voxels, std::string* why);
+// ---- the column field and scatter (include/blok_hip.h: blok_hip_volume_column_field, blok_hip_volume_scatter_models; columns_kernels.hip) ----
+// The column snapshot in device memory, owned by the holder: one top and one material id per column, and the info that counts them.
+struct GpuColumns {
+    uint16_t* d_top = nullptr;
+    uint32_t* d_material = nullptr;
+    uint32_t lo[3] = {0, 0, 0};                  // the region's corner, box-local
+    blok_columns_info info = {};
+    bool taken = false;
+};
+void gpu_columns_free(GpuColumns* c);
+// The field of the box-local region [lo, hi) along `axis` (arguments that have passed columns::check_field_args), from the brick masks
+// (which every edit leaves equal to density > 0) and one id per column that hits.  Changes nothing; *out is a new snapshot, the caller's
+// to free (pointers null when the region has no cell).  Blocking.
+GpuBuildStatus gpu_volume_column_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t axis, uint32_t flags, GpuColumns* out,
+                                       std::string* why);
+// The table scatter leaves in device memory, owned by the holder: info.n_placed records in column order.
+struct GpuScatter {
+    blok_instance* d_table = nullptr;
+    blok_scatter_info info = {};
+    bool taken = false;
+};
+void gpu_scatter_free(GpuScatter* s);
+// = blok_hip_volume_scatter_models over a column snapshot; the arguments (entries in host memory) have passed columns::check_scatter_args.
+// Reads the snapshot alone; *out is a new table, the caller's to free (d_table null when nothing was placed).  Blocking.
+GpuBuildStatus gpu_columns_scatter(const GpuColumns* columns, const blok_scatter_params& params, const blok_scatter_entry* entries, uint32_t n_entries,
+                                   GpuScatter* out, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

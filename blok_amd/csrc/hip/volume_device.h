@@ -44,6 +44,15 @@ struct BrickMasks {
         if (key_digits == 0u) return masks[bx + (static_cast<size_t>(bz) * nby + by) * nbx];
         return masks[cell_key(bx, by, bz, key_digits)];
     }
+    // What brick coordinate b along `axis` contributes to a brick's index: at(bx, by, bz) = masks[part(bx, 0) + part(by, 1) + part(bz, 2)]
+    // in either layout, and part(4 g + k, axis) = part(4 g, axis) + k * part(1, axis) for k < 4 — a walk along an axis computes one part per
+    // four bricks.
+    __device__ __forceinline__ uint64_t part(uint32_t b, uint32_t axis) const {
+        if (key_digits == 0u) return static_cast<uint64_t>(b) * (axis == 0u ? 1ull : axis == 1u ? static_cast<uint64_t>(nbx) : static_cast<uint64_t>(nbx) * nby);
+        uint64_t key = 0;
+        for (uint32_t j = 0; j < key_digits; ++j) key |= static_cast<uint64_t>((b >> (2u * j)) & 3u) << (6u * j + 2u * axis);
+        return key;
+    }
 };
 
 // Wave `wave` of a launch over a region whose rows along x are cut into segments of 64 cells, `x_chunks` to a row of the `ny` rows of a

@@ -335,6 +335,59 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_edit_by_flood(self._ctx, int(op), int(d), float(density), int(material), C.byref(n)))
         return int(n.value)
 
+    def volume_column_field(self, lo=None, hi=None, axis: int = 1, flags: int = 0) -> np.ndarray:
+        """Takes the column field of a region of the resident volume (world voxels, half open; both None = the whole box) along `axis`:
+        per column the first filled cell met from the hi face (_ffi.COLUMNS_FROM_LOW: from the lo face), region-local, and its material id
+        (blok_hip.h: blok_hip_volume_column_field), kept on the device until the next field.  Returns the field's info, one
+        _ffi.COLUMNS_INFO record; volume_columns_download fetches the planes, volume_scatter_models places models on it."""
+        rlo = _vec3(lo)
+        rhi = _vec3(hi)
+        info = np.zeros(1, dtype=_ffi.COLUMNS_INFO)
+        self._check(self._lib.blok_hip_volume_column_field(self._ctx, rlo, rhi, int(axis), int(flags), _ffi.ptr(info)))
+        return info
+
+    def volume_columns_info(self) -> np.ndarray:
+        info = np.zeros(1, dtype=_ffi.COLUMNS_INFO)
+        self._check(self._lib.blok_hip_volume_columns_info(self._ctx, _ffi.ptr(info)))
+        return info
+
+    def volume_columns_download(self, plane: int = 0, first=None, count=None, page: int = 1 << 24) -> np.ndarray:
+        """A plane of the last column field — 0: the tops (uint16, _ffi.COLUMNS_NONE = no filled cell), 1: the material ids (uint32) —
+        fetched `page` columns at a time: columns [first, first + count), or with both None all of them."""
+        dtype = np.uint32 if int(plane) == 1 else np.uint16
+        if first is None and count is None:
+            first, count = 0, int(self.volume_columns_info()["n_columns"][0])
+        return self._paged(self._lib.blok_hip_volume_columns_download, np.zeros(int(count or 0), dtype=dtype), int(first or 0), page, int(plane))
+
+    def volume_scatter_models(self, params, entries) -> np.ndarray:
+        """Scatters models over the last column field, which must run along +y from the top (blok_hip.h: blok_hip_volume_scatter_models):
+        params one _ffi.SCATTER_PARAMS record, entries _ffi.SCATTER_ENTRY records (blok_amd.columns builds both).  The table stays on the
+        device until the next scatter or column field.  Returns the counts, one _ffi.SCATTER_INFO record."""
+        params = np.ascontiguousarray(params, dtype=_ffi.SCATTER_PARAMS).reshape(1)
+        entries = np.ascontiguousarray(entries, dtype=_ffi.SCATTER_ENTRY).reshape(-1)
+        info = np.zeros(1, dtype=_ffi.SCATTER_INFO)
+        self._check(self._lib.blok_hip_volume_scatter_models(self._ctx, _ffi.ptr(params), _ffi.ptr(entries) if len(entries) else None, len(entries),
+                                                             _ffi.ptr(info)))
+        return info
+
+    def volume_scatter_info(self) -> np.ndarray:
+        info = np.zeros(1, dtype=_ffi.SCATTER_INFO)
+        self._check(self._lib.blok_hip_volume_scatter_info(self._ctx, _ffi.ptr(info)))
+        return info
+
+    def volume_scatter_download(self, first=None, count=None, page: int = 1 << 22) -> np.ndarray:
+        """Records [first, first + count) of the last scatter's table (INSTANCE, sorted by column), or with both None the whole table."""
+        if first is None and count is None:
+            first, count = 0, int(self.volume_scatter_info()["n_placed"][0])
+        return self._paged(self._lib.blok_hip_volume_scatter_download, np.zeros(int(count or 0), dtype=INSTANCE), int(first or 0), page)
+
+    def volume_scatter_device(self):
+        """(device address, count) of the last scatter's table where it lies, for the *_instanced_device entries (which skip instances that
+        fail their limits: check a downloaded table with check_instances).  Valid until the next scatter, column field or volume."""
+        table, n = C.c_void_p(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_scatter_device(self._ctx, C.byref(table), C.byref(n)))
+        return int(table.value or 0), int(n.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

@@ -380,6 +380,38 @@ public:
         check(blok_hip_volume_edit_by_flood(m_ctx, op, d, density, material, &written));
         return written;
     }
+    // The column field of a region of the resident volume (world voxels, half-open; both null = the whole box) along `axis`: per column the
+    // first filled cell met from the hi face (BLOK_COLUMNS_FROM_LOW: from the lo face) and its material id, kept on the device until the
+    // next field (blok_hip_volume_column_field): returns what it holds.  downloadColumnTops / downloadColumnMaterials fetch the planes
+    // `page` columns at a time.
+    blok_columns_info columnField(const int32_t* regionLo, const int32_t* regionHi, uint32_t axis = 1, uint32_t flags = 0) {
+        blok_columns_info info{};
+        check(blok_hip_volume_column_field(m_ctx, regionLo, regionHi, axis, flags, &info));
+        return info;
+    }
+    std::vector<uint16_t> downloadColumnTops(uint64_t page = uint64_t(1) << 24) { return downloadColumnPlane<uint16_t>(0, page); }
+    std::vector<uint32_t> downloadColumnMaterials(uint64_t page = uint64_t(1) << 24) { return downloadColumnPlane<uint32_t>(1, page); }
+    // Scatter over the column field (along +y from the top): a table of placements sorted by column, kept on the device until the next
+    // scatter or column field (blok_hip_volume_scatter_models): returns its counts.  downloadScatter fetches it, for stampModels or a check
+    // with blok_hip_check_instances; scatterTable gives it where it lies, for the *Instanced entries that take a device table (they skip
+    // instances that fail their limits).
+    blok_scatter_info scatterModels(const blok_scatter_params& params, const std::vector<blok_scatter_entry>& entries) {
+        blok_scatter_info info{};
+        check(blok_hip_volume_scatter_models(m_ctx, &params, entries.data(), static_cast<uint32_t>(entries.size()), &info));
+        return info;
+    }
+    std::vector<blok_instance> downloadScatter(uint64_t page = uint64_t(1) << 22) {
+        blok_scatter_info info{};
+        check(blok_hip_volume_scatter_info(m_ctx, &info));
+        std::vector<blok_instance> out(info.n_placed);
+        for (uint64_t at = 0; at < info.n_placed; at += page) check(blok_hip_volume_scatter_download(m_ctx, out.data() + at, at, std::min(page, info.n_placed - at)));
+        return out;
+    }
+    const blok_instance* scatterTable(uint64_t* outCount) {
+        const blok_instance* table = nullptr;
+        check(blok_hip_volume_scatter_device(m_ctx, &table, outCount));
+        return table;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h
@@ -470,6 +502,14 @@ public:
 
 private:
     void check(int rc) const { if (rc != BLOK_OK) throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_ctx)); }
+    template <class T>
+    std::vector<T> downloadColumnPlane(uint32_t plane, uint64_t page) {
+        blok_columns_info info{};
+        check(blok_hip_volume_columns_info(m_ctx, &info));
+        std::vector<T> out(info.n_columns);
+        for (uint64_t at = 0; at < info.n_columns; at += page) check(blok_hip_volume_columns_download(m_ctx, plane, out.data() + at, at, std::min(page, info.n_columns - at)));
+        return out;
+    }
 
     unsigned int m_width = 0, m_height = 0;
     int m_device = 0;

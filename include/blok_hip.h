@@ -574,7 +574,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.9: placed models swept against the resident volume (overlap, free travel along an axis).
  * 1.10: the resident volume saved, restored and undone as a sparse brick stream.
  * 1.11: the capped squared distance field of the resident volume; grow, shrink and hollow by it.
- * 1.12: the step field of the resident volume flooded from seeds; fill, seal, paint and clear by it. */
+ * 1.12: the step field of the resident volume flooded from seeds; fill, seal, paint and clear by it.
+ * 1.13: the column height field of the resident volume; models scattered onto it as an instance table. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -1020,6 +1021,114 @@ int blok_hip_volume_flood_field(blok_hip_ctx* ctx, const int32_t region_lo[3], c
 int blok_hip_volume_flood_info(blok_hip_ctx* ctx, blok_flood_info* out_info);
 int blok_hip_volume_flood_download(blok_hip_ctx* ctx, uint16_t* out_host, uint64_t first, uint64_t count);
 int blok_hip_volume_edit_by_flood(blok_hip_ctx* ctx, int op, uint32_t d, float density, uint32_t material, uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- the column field of the resident volume, and scatter (ABI 1.13)
+ * Where the ground is, and what to put on it, without a download: for every column of a region along an axis the first filled cell met
+ * from one end and that cell's material id, as a snapshot in HBM; and scatter, which turns that snapshot into a sorted table of
+ * blok_instance placements in HBM by a seeded, seamless, pure integer rule.  The table is traced where it lies (the *_instanced_device
+ * entries) or downloaded and stamped (blok_hip_volume_stamp_models).  One right answer, bit-identical on the host (blok_column_field /
+ * blok_scatter, blok_world.h) and on the device.  All calls block.
+ * The column field.
+ *  - Cell state.  A cell is filled iff density > 0.  The tops are read from the brick masks (which every edit leaves equal to that
+ *    rule), never from the densities; the material plane reads one id per column that hits.
+ *  - Region: world voxels, half open; both pointers NULL = the whole box.  The field sees only cells inside the region.
+ *  - Columns.  With p < q the two axes other than `axis`, the column of region-local (cp, cq) has index cp + ext[p] * cq;
+ *    n_columns = ext[p] * ext[q].
+ *  - Value.  top is the region-local coordinate along `axis`, counted from lo[axis], of the first filled cell met from the entry face: by
+ *    default the face at hi, travelling -axis (the highest filled cell); with BLOK_COLUMNS_FROM_LOW the face at lo, travelling +axis (the
+ *    lowest).  A column without a filled cell holds BLOK_COLUMNS_NONE.  A box's extent is at most 16384, so the value fits a uint16_t.
+ *  - Material plane: the material id of the top cell; 0 for a column with NONE.
+ *  - Snapshot: plane 0 is one uint16_t per column, plane 1 one uint32_t, in device memory, owned by the context beside the distance
+ *    snapshot and with the same life: later edits do not touch it; the next field replaces it; blok_hip_volume_destroy, a new
+ *    blok_hip_volume_create and blok_hip_destroy free it.  Taking it changes nothing in the volume and nothing in the quads, components,
+ *    bricks, distance and flood snapshots.  The result is the same in the keyed and the row-major brick layout.  out_info may be NULL.
+ *  - Info: n_hit counts the columns with a top; min_top and max_top range over them (BLOK_COLUMNS_NONE and 0 when none hit).
+ *  - blok_hip_volume_columns_download copies elements [first, first + count) of a plane; blok_hip_volume_columns_info returns the info.
+ *  - Errors, each leaving the volume, the previous snapshot and the previous scatter table as they were.  BLOK_ERR_INVALID_ARG: unknown
+ *    flag bits, axis > 2, exactly one region pointer NULL, lo > hi on an axis, no snapshot (info and download), a download range past the
+ *    end, plane > 1, a NULL array with count > 0.  BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume above 2^32 cells.
+ *    BLOK_ERR_NO_WORLD: no volume.  BLOK_ERR_OOM: a failed device allocation.  An empty region is BLOK_OK with zero counts. */
+#define BLOK_COLUMNS_FROM_LOW 1u      /* enter at the region's lo face and travel +axis (default: enter at hi, travel -axis) */
+#define BLOK_COLUMNS_NONE 0xFFFFu     /* no filled cell in the column */
+typedef struct blok_columns_info {
+    uint32_t version;      /* 1 */
+    uint32_t flags;
+    int32_t  lo[3];        /* the region, world voxels */
+    uint32_t ext[3];
+    uint32_t axis;         /* 0, 1, 2 */
+    uint32_t min_top, max_top;   /* over the columns that hit; BLOK_COLUMNS_NONE and 0 when none hit */
+    uint32_t reserved;     /* 0 */
+    uint64_t n_columns, n_hit;
+} blok_columns_info;       /* 64 bytes */
+int blok_hip_volume_column_field(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t axis, uint32_t flags,
+                                 blok_columns_info* out_info);
+int blok_hip_volume_columns_info(blok_hip_ctx* ctx, blok_columns_info* out_info);
+/* plane 0: uint16_t tops, plane 1: uint32_t material ids */
+int blok_hip_volume_columns_download(blok_hip_ctx* ctx, uint32_t plane, void* out_host, uint64_t first, uint64_t count);
+
+/* Scatter.
+ *  - Input: the current column snapshot, which must have axis == 1 and no BLOK_COLUMNS_FROM_LOW (up is +y).  Nothing else of the volume is
+ *    read, and the models are not looked at: blok_hip_check_instances on the downloaded table remains the caller's check, and the
+ *    *_instanced_device entries skip instances that fail their limits.
+ *  - Hash.  hash3(x, y, z, s) = fmix32(x * 0x9E3779B1 ^ y * 0x85EBCA77 ^ z * 0xC2B2AE3D ^ s) with murmur3's 32-bit finaliser fmix32 (the
+ *    terrain's hash), all in uint32_t.  For world column (X, Z) and c = cell_log2: cx = X >> c, cz = Z >> c (arithmetic shifts), S = 1 << c,
+ *    h1 = hash3((uint32_t)cx, 0x5CA70001, (uint32_t)cz, seed), h2 = hash3((uint32_t)cx, 0x5CA70002, (uint32_t)cz, seed).
+ *  - Candidate.  Cell (cx, cz) has one candidate column, X = (cx << c) + (h1 & (S - 1)), Z = (cz << c) + ((h1 >> 8) & (S - 1)).  A cell
+ *    counts toward n_cells iff its candidate lies in the snapshot's region: a world column gets the same decision whatever region was
+ *    taken, so placement is seamless in the way the terrain is.
+ *  - Tests, in order; the first that fails is counted in n_rejected[0..4].  0 probability: (h1 >> 16) < probability.  1 none: the
+ *    candidate's top != NONE.  2 band: min_y <= lo[1] + top <= max_y.  3 material: BLOK_SCATTER_ANY_MATERIAL, or the material plane equals
+ *    surface_material.  4 footprint: for every column (X + dx, Z + dz) with |dx|, |dz| <= radius that lies inside the region (columns
+ *    outside it are ignored: take the field `radius` wider for seamless footprints), with top' its value as stored: top' <= top + max_rise
+ *    unless max_rise == 0xFFFF, and top' != NONE && top' + max_drop >= top unless max_drop == 0xFFFF.  (NONE is 0xFFFF: a column without a
+ *    filled cell fails a rise limit as well as a drop limit.)
+ *  - Placement, integer arithmetic on the values above.  W = the sum of the weights.  The entry is the first whose cumulative weight
+ *    exceeds (h2 & 0xFFFF) % W.  r = ROTATE ? (h2 >> 16) & 3 : 0; m = MIRROR ? (h2 >> 18) & 1 : 0.  axis = (r & 1) ? {2, 1, 0} : {0, 1, 2};
+ *    flip = {0, 4, 5, 1}[r] ^ m.  The target cell is T = (X, lo[1] + top + 1 - sink, Z).  For each local axis k with world axis A = axis[k]:
+ *    offset[A] = T[A] - anchor[k] when flip bit k is clear, T[A] + 1 + anchor[k] when it is set, so that by "Record back to world space"
+ *    above the entry's anchor voxel lands exactly on T.  model is the entry's, reserved is zero.  The four (axis, flip) pairs without
+ *    the mirror are the four proper rotations about +y.
+ *  - Table: blok_instance records sorted by the candidate's column index, ascending (the indices are distinct), in device memory, owned by
+ *    the context.  The next scatter replaces it; a new column field, blok_hip_volume_destroy, a new blok_hip_volume_create and
+ *    blok_hip_destroy free it.  blok_hip_volume_scatter_device gives the table where it lies (null for an empty one), valid until then.
+ *    out_info may be NULL.
+ *  - Errors, each leaving the previous table as it was.  BLOK_ERR_INVALID_ARG: a NULL context, parameter record or entry array; unknown
+ *    flag bits or non-zero reserved words; cell_log2 > 8, probability > 65536, radius > 8, max_rise or max_drop above 0xFFFF; n_entries of
+ *    0 or above BLOK_SCATTER_MAX_ENTRIES; a weight of 0 or above 65535; min_y > max_y; no column snapshot, or one with another axis or
+ *    FROM_LOW; no table (info, download, device); a download range past the end; a NULL array with count > 0.  BLOK_ERR_OOM: a failed
+ *    device allocation. */
+#define BLOK_SCATTER_ANY_MATERIAL 1u   /* ignore surface_material */
+#define BLOK_SCATTER_ROTATE       2u   /* one of the four rotations about +y, chosen by the hash */
+#define BLOK_SCATTER_MIRROR       4u   /* also mirror local x, chosen by the hash */
+#define BLOK_SCATTER_MAX_ENTRIES 16u
+typedef struct blok_scatter_entry {
+    uint32_t model;
+    uint32_t weight;       /* 1..65535 */
+    int32_t  anchor[3];    /* the model voxel (local lattice) that lands on the target cell */
+    int32_t  sink;         /* the target cell is this many cells below the first empty cell above the top */
+} blok_scatter_entry;      /* 24 bytes */
+typedef struct blok_scatter_params {
+    uint32_t seed, flags;
+    uint32_t cell_log2;          /* c in 0..8: one candidate per 2^c x 2^c cell of world (x, z) */
+    uint32_t probability;        /* 0..65536; 65536 = every candidate */
+    uint32_t surface_material;
+    int32_t  min_y, max_y;       /* world y of the top cell, inclusive band */
+    uint32_t radius;             /* 0..8: footprint half-width in columns */
+    uint32_t max_rise, max_drop; /* 0..0xFFFF; 0xFFFF = no limit */
+    uint32_t reserved[6];        /* zero */
+} blok_scatter_params;           /* 64 bytes */
+typedef struct blok_scatter_info {
+    uint32_t version, flags;     /* 1, the parameters' flags */
+    uint64_t n_cells, n_placed;
+    uint64_t n_rejected[5];      /* first failing test: probability, none, band, material, footprint */
+    uint64_t reserved;           /* 0 */
+} blok_scatter_info;             /* 72 bytes */
+int blok_hip_volume_scatter_models(blok_hip_ctx* ctx, const blok_scatter_params* params, const blok_scatter_entry* entries_host,
+                                   uint32_t n_entries, blok_scatter_info* out_info);
+int blok_hip_volume_scatter_info(blok_hip_ctx* ctx, blok_scatter_info* out_info);
+int blok_hip_volume_scatter_download(blok_hip_ctx* ctx, blok_instance* out_host, uint64_t first, uint64_t count);
+/* The table where it lies, for the *_instanced_device entries; valid until the next scatter / column field / volume. */
+int blok_hip_volume_scatter_device(blok_hip_ctx* ctx, const blok_instance** out_dev, uint64_t* out_count);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -274,6 +274,20 @@ int blok_flood_field(const float* density, const uint32_t* material_ids, const i
 int blok_flood_edit(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const uint16_t* field,
                     const blok_flood_info* info, int op, uint32_t d, float density_value, uint32_t material, uint64_t* out_n_voxels);
 
+/* -------------------------------------------------------------- the column field and scatter on the host (columns.cpp)
+ * The contracts of blok_hip_volume_column_field and blok_hip_volume_scatter_models (blok_hip.h; the records and the flags are declared
+ * there) over host arrays of a box as above, through the rules the kernels use.
+ * column_field: the region is in world voxels; out_top and out_material take one value per column (index cp + ext[p] * cq) and *out_info
+ * (may be NULL) what the device's info holds.  Errors as the device entry; a NULL array with a non-empty region is BLOK_ERR_INVALID_ARG.
+ * scatter: top, material and columns_info are a column field's (axis 1, not FROM_LOW).  With out_instances NULL it only counts; otherwise
+ * the table takes n_placed records in column order, and a capacity below n_placed is BLOK_ERR_INVALID_ARG with nothing written.  *out_info
+ * (may be NULL) is what the device's info holds.  Errors as the device entry. */
+int blok_column_field(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                      const int32_t region_lo[3], const int32_t region_hi[3], uint32_t axis, uint32_t flags, uint16_t* out_top,
+                      uint32_t* out_material, blok_columns_info* out_info);
+int blok_scatter(const uint16_t* top, const uint32_t* material, const blok_columns_info* columns_info, const blok_scatter_params* params,
+                 const blok_scatter_entry* entries, uint32_t n_entries, blok_instance* out_instances, uint64_t capacity, blok_scatter_info* out_info);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

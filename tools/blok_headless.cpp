@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -29,6 +29,12 @@
 //          flooded from all six faces with max_steps 65534 (blok_hip_volume_flood_field), then BLOK_FLOOD_FILL_UNREACHED fills every empty
 //          cell the air did not reach with material 0, or --seal-material N: an openly voxelized shell becomes solid, caves no one can
 //          enter are closed.  No primary ray enters a sealed cell
+//   --populate: with --terrain, once the volume is filled and before it is rebuilt: the first model of every listed .vox file is uploaded
+//          (blok_hip_model_create; VOX z is up), the column field of the whole box taken along +y from the top (blok_hip_volume_column_field)
+//          and the models scattered on the terrain's grass (blok_hip_volume_scatter_models: seed = the terrain's, one candidate per 16 x 16
+//          columns, probability 40000 / 65536, ROTATE | MIRROR, footprint radius 1 with rise and drop of at most 1, each model anchored at
+//          the centre of its base).  The first-hit frames are traced with the table as instances (--rt frames show the world alone); with
+//          --bake the table is stamped into the volume instead (BLOK_STAMP_SET) and the frames show the rebuilt world
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -36,6 +42,7 @@
 //   --dense-exchange: whole RGBA8 tiles travel (RCCL / peer copies) instead of the root reading the ranks' sparse code records
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +73,8 @@ struct Options {
     bool seal = false;                    // fill the empty cells that air from the box's faces does not reach, before the rebuild
     uint32_t seal_material = 0;
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
+    std::vector<std::string> populate;    // .vox files whose first models are scattered over the terrain
+    bool bake = false;                    // ... and stamped into the volume instead of traced as instances
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
@@ -93,6 +102,7 @@ private:
                 if (!m_opt.save_volume.empty()) throw std::runtime_error("--save-volume needs a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.hollow >= 0) throw std::runtime_error("--hollow needs a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.seal) throw std::runtime_error("--seal needs a resident volume: --terrain, --obj or --load-volume");
+                if (!m_opt.populate.empty()) throw std::runtime_error("--populate needs a terrain: --terrain");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -197,6 +207,7 @@ private:
         }
         seal();
         hollow();
+        populate(p);
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
@@ -247,6 +258,61 @@ private:
         const blok_flood_info info = m_tracer->floodField(nullptr, nullptr, {}, BLOK_FLOOD_MAX_STEPS, faces);
         const uint64_t filled = m_tracer->editByFlood(BLOK_FLOOD_FILL_UNREACHED, 0, 1.0f, m_opt.seal_material);
         std::cout << "seal: " << filled << " voxels filled, farthest " << info.farthest << "\n";
+    }
+    // The listed .vox models scattered over the terrain's grass: the column field of the whole box, then the table — kept for the frames, or baked.
+    void populate(const blok_terrain_params& terrain) {
+        if (m_opt.populate.empty()) return;
+        if (m_opt.populate.size() > BLOK_SCATTER_MAX_ENTRIES) throw std::runtime_error("--populate takes at most 16 models");
+        std::vector<blok_scatter_entry> entries;
+        for (const std::string& path : m_opt.populate) {
+            char err[512] = {0};
+            blok_vox* vox = nullptr;
+            if (blok_vox_load_file(path.c_str(), &vox, err, sizeof(err)) != BLOK_OK) throw std::runtime_error("Failed to load VOX: " + std::string(err));
+            uint32_t size[3] = {0, 0, 0}, n = 0, palette[256];
+            if (blok_vox_model_count(vox) == 0 || blok_vox_model_info(vox, 0, size, &n) != BLOK_OK || n == 0) { blok_vox_free(vox); throw std::runtime_error("the VOX holds no voxels: " + path); }
+            blok_vox_import_materials(vox, m_materials.handle(), palette);
+            const uint8_t* v = blok_vox_model_voxels(vox, 0);
+            std::vector<int32_t> xyz(3u * n);
+            std::vector<uint32_t> ids(n);
+            for (uint32_t i = 0; i < n; ++i) {                    // VOX z is up -> local y
+                xyz[3 * i] = v[4 * i]; xyz[3 * i + 1] = v[4 * i + 2]; xyz[3 * i + 2] = v[4 * i + 1];
+                ids[i] = palette[v[4 * i + 3]];
+            }
+            blok_vox_free(vox);
+            blok_scatter_entry e{};
+            e.model = m_tracer->createModel(xyz, ids);
+            e.weight = 1u;
+            e.anchor[0] = static_cast<int32_t>(size[0] / 2u); e.anchor[1] = 0; e.anchor[2] = static_cast<int32_t>(size[1] / 2u);
+            entries.push_back(e);
+        }
+        const blok_columns_info columns = m_tracer->columnField(nullptr, nullptr, 1u, 0u);
+        blok_scatter_params sp{};
+        sp.seed = m_opt.terrain_seed; sp.flags = BLOK_SCATTER_ROTATE | BLOK_SCATTER_MIRROR;
+        sp.cell_log2 = 4u; sp.probability = 40000u; sp.surface_material = terrain.surface_material;
+        sp.min_y = INT32_MIN; sp.max_y = INT32_MAX;
+        sp.radius = 1u; sp.max_rise = 1u; sp.max_drop = 1u;
+        const blok_scatter_info info = m_tracer->scatterModels(sp, entries);
+        m_instances = m_tracer->downloadScatter();
+        if (blok_hip_check_instances(m_tracer->handle(), m_instances.data(), static_cast<uint32_t>(m_instances.size())) != BLOK_OK)
+            throw std::runtime_error(std::string("--populate: ") + blok_hip_last_error(m_tracer->handle()));
+        std::cout << "populate: " << entries.size() << " models over " << columns.n_hit << " of " << columns.n_columns << " columns, " << info.n_cells << " cells, "
+                  << info.n_placed << " placed, rejected " << info.n_rejected[0] << " " << info.n_rejected[1] << " " << info.n_rejected[2] << " " << info.n_rejected[3] << " "
+                  << info.n_rejected[4];
+        if (m_opt.bake) {
+            std::cout << ", baked " << m_tracer->stampModels(m_instances, BLOK_STAMP_SET, 1.0f) << " voxels";
+            m_instances.clear();
+        }
+        std::cout << "\n";
+    }
+    // The frame over the world plus the scattered table, as RGBA8.
+    const std::vector<uint32_t>& drawPopulated() {
+        const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
+        m_populatedHits.resize(static_cast<size_t>(m_opt.width) * m_opt.height);
+        m_populatedFrame.resize(m_populatedHits.size());
+        if (blok_hip_trace_primary_instanced(m_tracer->handle(), &c, 0, 0, m_opt.width, m_opt.height, m_instances.data(), static_cast<uint32_t>(m_instances.size()),
+                                             m_populatedHits.data(), m_populatedFrame.data(), nullptr) != BLOK_OK)
+            throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_tracer->handle()));
+        return m_populatedFrame;
     }
     // Only the shell within the squared distance --hollow of empty space stays: the to-empty field of the whole box, thresholded.
     void hollow() {
@@ -367,6 +433,7 @@ private:
             m_tracer->beginFrame();
             if (m_multi) m_multi->drawFrame(m_camera, m_multiFrame);
             else if (m_opt.rt) m_tracer->drawFrameRT(m_camera, m_opt.spp);
+            else if (!m_instances.empty()) m_tracer->drawFrameInstanced(m_camera, m_instances);
             else m_tracer->drawFrame(m_camera);
             m_tracer->endFrame();
             const double ms = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
@@ -376,7 +443,7 @@ private:
                            << m_tracer->hits().size() * sizeof(blok_hit) / 1e6 << " MB)\n";
             if (f + 1 < m_opt.frames || !m_opt.rt) m_camera.processKeyboard('W', 0.016f);
         }
-        const auto& single = m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : m_tracer->drawFrameRgba8(m_camera);
+        const auto& single = m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
         if (m_multi) {                                       // the partitioned frame must be the single-device frame
             m_multi->drawFrame(m_camera, m_multiFrame);
             size_t differ = 0;
@@ -401,6 +468,9 @@ private:
     std::unique_ptr<blok::HipTracer> m_tracer;
     std::unique_ptr<blok::HipMultiTracer> m_multi;
     std::vector<uint32_t> m_multiFrame;
+    std::vector<blok_instance> m_instances;        // --populate: the scattered table (empty once baked)
+    std::vector<blok_hit> m_populatedHits;
+    std::vector<uint32_t> m_populatedFrame;
 };
 
 }  // namespace
@@ -426,6 +496,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--seal")) opt.seal = true;
         else if (!std::strcmp(argv[i], "--seal-material")) opt.seal_material = static_cast<uint32_t>(std::atoll(next()));
         else if (!std::strcmp(argv[i], "--hollow")) { opt.hollow = std::atoll(next()); if (opt.hollow < 0 || opt.hollow > 65025) { std::fprintf(stderr, "--hollow takes a squared distance in 0..65025\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--populate")) { for (std::string list = next(); !list.empty();) { const size_t c = list.find(','); opt.populate.push_back(list.substr(0, c)); list = c == std::string::npos ? "" : list.substr(c + 1); } }
+        else if (!std::strcmp(argv[i], "--bake")) opt.bake = true;
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
