@@ -657,18 +657,13 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());            // frames still reading a tree of an earlier build
     const auto t_synced = std::chrono::steady_clock::now();
     blok::GpuVolume& v = ctx->volume;
-    // the voxels edited since the last build, in world coordinates (for the shadow rays' last-occluder map)
-    int32_t lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) { lo[a] = v.origin[a] + static_cast<int32_t>(std::min<uint32_t>(v.edit_lo[a], 0x7FFFFFFFu)); hi[a] = v.origin[a] + static_cast<int32_t>(v.edit_hi[a]); }
-    const bool edited = v.edit_lo[0] < v.edit_hi[0] && v.edit_lo[1] < v.edit_hi[1] && v.edit_lo[2] < v.edit_hi[2];
-    if (!edited) { lo[0] = lo[1] = lo[2] = 0; hi[0] = hi[1] = hi[2] = 0; }
     blok::GpuTree gpu;
     std::string why;
-    const bool may_add = v.edit_may_add;
     const blok::GpuBuildStatus st = blok::gpu_volume_build(&v, &gpu, &why);
     const auto t_built = std::chrono::steady_clock::now();
-    for (int a = 0; a < 3; ++a) { v.edit_lo[a] = 0xFFFFFFFFu; v.edit_hi[a] = 0u; }
-    v.edit_may_add = false;
+    // the edits this build has taken in (whether or not it succeeded), in world voxels: for the shadow rays' last-occluder map
+    const uint32_t dims[3] = {v.nx, v.ny, v.nz};
+    const blok::EditLog::Taken edits = v.edits.take(v.origin, dims);
     if (st == blok::GpuBuildStatus::UseHostBuilder) {      // nothing filled: an empty world
         blok::HostTree tree;
         std::vector<blok::VoxelRec> none;
@@ -710,7 +705,9 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
     ctx->built_on_device = true;
     if (same_lattice) { ctx->d_sun_map = keep_sun; ctx->has_sun_map = keep_has_sun; }
     const auto t_installed = std::chrono::steady_clock::now();
-    rc = update_sun_map(ctx, lo, hi, same_lattice, may_add);
+    // a fill of the whole box is a new world to the map: raised over every texel it would stay loose until kSunMapLooseEdits further
+    // edits (api.hip), so it is searched anew as for a changed lattice — one search per texel behind an edit that wrote every cell
+    rc = update_sun_map(ctx, edits.lo, edits.hi, same_lattice && !(edits.whole && edits.may_fill), edits.may_fill);
     if (timing) {
         const auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         std::fprintf(stderr, "[volume_rebuild us] wait-for-device %.1f build %.1f install %.1f sun-map %.1f\n", us(t_begin, t_synced), us(t_synced, t_built), us(t_built, t_installed), us(t_installed, std::chrono::steady_clock::now()));

@@ -188,8 +188,6 @@ __global__ __launch_bounds__(256) void brick_scatter_kernel(const DecodeArgs a) 
     }
 }
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255u) / 256u); }
-
 GpuBuildStatus exclusive_sum(DeviceMem& mem, uint64_t* d_words, uint64_t n, std::string* why) {
     size_t temp_bytes = 0;
     BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_words, d_words, static_cast<int>(n)));
@@ -210,7 +208,7 @@ void gpu_bricks_free(GpuBricks* b) {
 
 GpuBuildStatus gpu_volume_encode_bricks(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuBricks* out, std::string* why) {
     *out = GpuBricks{};
-    if (v->cells() > 0xFFFFFFFFull) { *why = "encode_bricks: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "encode_bricks", why)) return GpuBuildStatus::Unsupported;
     blok_bricks_info& info = out->info;
     info.version = 1u; info.flags = flags;
     ClassifyArgs c{};
@@ -269,7 +267,7 @@ GpuBuildStatus gpu_volume_encode_bricks(const GpuVolume* v, const uint32_t lo[3]
 }
 
 GpuBuildStatus gpu_volume_decode_bricks(GpuVolume* v, const GpuBricks* stream, const uint32_t dst_lo[3], uint32_t flags, std::string* why) {
-    if (v->cells() > 0xFFFFFFFFull) { *why = "decode_bricks: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "decode_bricks", why)) return GpuBuildStatus::Unsupported;
     const blok_bricks_info& info = stream->info;
     if (!info.ext[0] || !info.ext[1] || !info.ext[2]) return GpuBuildStatus::Ok;
     DecodeArgs a{};
@@ -288,8 +286,7 @@ GpuBuildStatus gpu_volume_decode_bricks(GpuVolume* v, const GpuBricks* stream, c
         hipLaunchKernelGGL(brick_scatter_kernel, dim3(blocks_for(a.n_records)), dim3(256), 0, nullptr, a);
         BLOK_GPU_TRY(hipGetLastError());
     }
-    v->edit_may_add = true;                                       // (a written density may be positive)
-    const GpuBuildStatus st = gpu_volume_refresh(v, a.lo, hi, why);
+    const GpuBuildStatus st = gpu_volume_commit(v, a.lo, hi, Edit::MayFill, why);      // (a written density may be positive)
     BLOK_GPU_TRY(hipDeviceSynchronize());                         // blocking, as gpu_volume_set_voxels is
     return st;
 }

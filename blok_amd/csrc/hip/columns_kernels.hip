@@ -160,7 +160,6 @@ __global__ __launch_bounds__(256) void scatter_emit_kernel(const ScatterArgs a) 
         K::place(a.field, a.params, a.entries, a.n_entries, a.weight_sum, static_cast<uint32_t>(column % a.field.ext[0]), static_cast<uint32_t>(column / a.field.ext[0]));
 }
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255u) / 256u); }
 static_assert(K::kVerdicts <= static_cast<int>(kCols), "a column per verdict");
 
 // The folds of the n_rows rows the launch before left in d_rows, into totals[kCols] (host memory): the call's wait.

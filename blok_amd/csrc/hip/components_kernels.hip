@@ -221,8 +221,6 @@ __global__ __launch_bounds__(256) void record_finish_kernel(blok_component* reco
     records[i] = c;
 }
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255u) / 256u); }
-
 }  // namespace
 
 void gpu_components_free(GpuComponents* c) {
@@ -235,7 +233,7 @@ void gpu_components_free(GpuComponents* c) {
 
 GpuBuildStatus gpu_volume_label_components(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuComponents* out, std::string* why) {
     *out = GpuComponents{};
-    if (v->cells() > 0xFFFFFFFFull) { *why = "label_components: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "label_components", why)) return GpuBuildStatus::Unsupported;
     LabelArgs a{};
     for (int k = 0; k < 3; ++k) { a.g.lo[k] = lo[k]; a.g.ext[k] = hi[k] > lo[k] ? hi[k] - lo[k] : 0u; out->lo[k] = lo[k]; out->ext[k] = a.g.ext[k]; }
     const uint64_t n = K::cells(a.g);

@@ -1,6 +1,6 @@
 // The edit that thresholds a snapshot field over its region (gpu_build.h: gpu_volume_edit_by_distance, gpu_volume_edit_by_flood), once
 // for both: a lane per region cell, 64 along x per wave; it reads the snapshot and the density, runs the per-cell step the host build runs
-// (../common/field_edit_core.h), counts through a ballot and one atomic per wave; then the refresh of every edit runs over the region.
+// (../common/field_edit_core.h), counts through a ballot and one atomic per wave; then the commit of every edit runs over the region.
 // Included by distance_kernels.hip and flood_kernels.hip, local to each: each instantiates it with its own rule.
 #ifndef BLOK_FIELD_EDIT_H
 #define BLOK_FIELD_EDIT_H
@@ -45,12 +45,12 @@ __global__ __launch_bounds__(256) void field_edit_kernel(const FieldEditArgs<Rul
 }
 
 // The edit of the region [lo, lo + ext) (box-local, inside the box) by `rule` over its snapshot `field`; `entry` names the caller in the
-// messages, may_fill says that the op may fill a voxel.  Writes the store, then refreshes the region as every edit does.  Blocking.
+// messages, may_fill says that the op may fill a voxel.  Writes the store, then commits the region as every edit does.  Blocking.
 template <class Rule>
 GpuBuildStatus edit_by_field(GpuVolume* v, const char* entry, const Rule& rule, const uint32_t lo[3], const uint32_t ext[3], const uint16_t* field,
                              bool may_fill, uint64_t* out_n_voxels, std::string* why) {
     *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = std::string(entry) + ": volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, entry, why)) return GpuBuildStatus::Unsupported;
     if (!ext[0] || !ext[1] || !ext[2]) return GpuBuildStatus::Ok;                          // an empty snapshot: nothing to write
     FieldEditArgs<Rule> a{};
     a.density = v->d_density; a.ids = v->d_ids; a.field = field; a.nx = v->nx; a.ny = v->ny;
@@ -64,8 +64,7 @@ GpuBuildStatus edit_by_field(GpuVolume* v, const char* entry, const Rule& rule, 
     BLOK_GPU_TRY(hipMemsetAsync(a.count, 0, sizeof(uint64_t), nullptr));
     hipLaunchKernelGGL(field_edit_kernel<Rule>, dim3(static_cast<uint32_t>((a.n_waves + 3u) / 4u)), dim3(256), 0, nullptr, a);
     BLOK_GPU_TRY(hipGetLastError());
-    if (may_fill) v->edit_may_add = true;                         // what the shadow rays' map has to know (gpu_build.h)
-    const GpuBuildStatus st = gpu_volume_refresh(v, a.lo, hi, why);      // (a PAINT changes no mask: the refresh still marks its bricks dirty)
+    const GpuBuildStatus st = gpu_volume_commit(v, a.lo, hi, may_fill ? Edit::MayFill : Edit::OnlyClears, why);      // (a PAINT changes no mask: the commit still marks its bricks dirty)
     BLOK_GPU_TRY(hipMemcpy(out_n_voxels, a.count, sizeof(uint64_t), hipMemcpyDeviceToHost));      // blocking, as gpu_volume_set_voxels is
     return st;
 }

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "blok_hip.h"
+#include "edit_log.h"
 #include "tree.h"
 #include "volume_device.h"
 
@@ -75,10 +76,8 @@ struct GpuVolume {
         int current = -1;                        // output set the tracer holds (-1: none)
         bool have_previous_materials = false;
     } scratch;
-    // voxels edited since the last build (box-local, half-open); empty = lo > hi
-    uint32_t edit_lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, edit_hi[3] = {0, 0, 0};
+    EditLog edits;                               // the edits since the last build (edit_log.h): gpu_volume_commit notes, the rebuild takes
     uint64_t refreshes[3] = {0, 0, 0};           // diagnostic: mask refreshes since creation — keyed, an edit's path (a wave per brick, the pyramid in one workgroup); keyed, an upload's path (a lane per brick, a launch per level); general layout
-    bool edit_may_add = false;                   // ... and one of those edits may have FILLED a voxel (an ADD brush with a positive value, setVoxel): what the shadow rays' map has to know
 };
 
 // The volume's brick masks as a kernel reads them, in whichever layout the volume has (volume_device.h).
@@ -93,9 +92,13 @@ GpuBuildStatus gpu_volume_download(const GpuVolume* v, float* density, uint32_t*
 // = ChunkManager::setVoxelMaterial for n world voxels (later entries win); voxels outside the box -> Unsupported.
 GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uint32_t* material, const float* density, size_t n,
                                      std::string* why);
-// Masks, occupancy words and dirty flags of the bricks that hold voxels [lo, hi) (box-local), from the dense store, and the edited box:
-// what every edit above does after writing the store (voxelize_kernels.hip writes the store itself).
-GpuBuildStatus gpu_volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why);
+// What every operation that has written the store owes the rest of the system, in one call (the upload and the edits above, and every
+// edit below; voxelize_kernels.hip and the others write the store themselves): the masks, occupancy words and dirty flags of the bricks
+// that hold voxels [lo, hi) (box-local) recomputed from the dense store, on the null stream behind the writes, and the box and `kind`
+// noted in v->edits.  MayFill: the operation may have made an empty voxel filled (density > 0); OnlyClears: it cannot have.  An empty
+// box is Ok and notes nothing.
+enum class Edit { OnlyClears, MayFill };
+GpuBuildStatus gpu_volume_commit(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], Edit kind, std::string* why);
 // = blok_hip_volume_voxelize_mesh (include/blok_hip.h; voxelize_kernels.hip).  Host arrays.  *invalid: a referenced vertex, an index or a
 // triangle's extent is out of the limits (nothing written).
 GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
@@ -121,7 +124,7 @@ void gpu_quads_free(GpuQuads* q);
 GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuQuads* out,
                                         uint64_t* out_n_faces, std::string* why);
 // = blok_hip_volume_stamp_models (include/blok_hip.h; stamp_kernels.hip).  The placements have passed the entry's checks; models[i] is
-// the model of placements[i], read in device memory through its tree.  One launch and one refresh per placement, in table order on the
+// the model of placements[i], read in device memory through its tree.  One launch and one gpu_volume_commit per placement, in table order on the
 // null stream; the only wait is the one for the count at the end.
 struct StampModel {
     const uint4* nodes; const uint32_t* materials;      // tree.h, device memory
@@ -143,7 +146,7 @@ GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const bl
 // coordinates); with *out_n_voxels == 0 (nothing filled) there is no tree.  Reads the store, changes nothing.
 GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3],
                                   int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why);
-// Clears (density 0, id 0) the filled voxels of the box-local box [lo, hi) and refreshes it: BLOK_CAPTURE_CUT.
+// Clears (density 0, id 0) the filled voxels of the box-local box [lo, hi) and commits it (Edit::OnlyClears): BLOK_CAPTURE_CUT.
 GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why);
 // ---- connected components (include/blok_hip.h: blok_hip_volume_label_components; components_kernels.hip) ----
 // The snapshot of one labelling, device memory owned by the holder: the label array of the region's cells, the records sorted by label,
@@ -192,7 +195,7 @@ void gpu_bricks_free(GpuBricks* b);
 // nothing is stored).  Blocking.
 GpuBuildStatus gpu_volume_encode_bricks(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuBricks* out, std::string* why);
 // Writes a stream whose arrays lie in device memory into [dst_lo, dst_lo + info.ext) (box-local, inside the box; flags:
-// BLOK_BRICKS_KEEP_OTHERS or 0), then refreshes that box as every edit does.  The stream is one gpu_volume_encode_bricks made or one that
+// BLOK_BRICKS_KEEP_OTHERS or 0), then commits that box as every edit does (gpu_volume_commit).  The stream is one gpu_volume_encode_bricks made or one that
 // has passed bricks::validate: the kernel trusts its indices.  Blocking.
 GpuBuildStatus gpu_volume_decode_bricks(GpuVolume* v, const GpuBricks* stream, const uint32_t dst_lo[3], uint32_t flags, std::string* why);
 // ---- the fields (distance_kernels.hip, flood_kernels.hip) ----
@@ -207,23 +210,6 @@ void gpu_field_free(Field* f) {
     if (f->d_field) (void)hipFree(f->d_field);
     *f = Field{};
 }
-// What both field builders begin with: *out reset, the 2^32 check with the entry's name in the text, the info's version, flags, lo and ext and
-// the holder's lo from the box-local region [lo, hi), ext[].  False: nothing to compute, and *st says why — Unsupported, or Ok for a region
-// without a cell.
-template <class Field>
-bool gpu_field_begin(const GpuVolume* v, const char* entry, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, Field* out, uint32_t ext[3],
-                     GpuBuildStatus* st, std::string* why) {
-    *out = Field{};
-    *st = GpuBuildStatus::Unsupported;
-    if (v->cells() > 0xFFFFFFFFull) { *why = std::string(entry) + ": volume larger than 2^32 cells"; return false; }
-    out->info.version = 1u; out->info.flags = flags;
-    for (int k = 0; k < 3; ++k) {
-        out->lo[k] = lo[k]; ext[k] = hi[k] > lo[k] ? hi[k] - lo[k] : 0u;
-        out->info.lo[k] = v->origin[k] + static_cast<int32_t>(lo[k]); out->info.ext[k] = ext[k];
-    }
-    *st = GpuBuildStatus::Ok;
-    return ext[0] && ext[1] && ext[2];
-}
 // ---- the distance field (include/blok_hip.h: blok_hip_volume_distance_field; distance_kernels.hip) ----
 struct GpuDistance : GpuField {
     blok_distance_info info = {};
@@ -233,7 +219,7 @@ struct GpuDistance : GpuField {
 GpuBuildStatus gpu_volume_distance_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t max_radius, uint32_t flags,
                                          GpuDistance* out, std::string* why);
 // = blok_hip_volume_edit_by_distance over the snapshot's region (inside the box); the arguments have passed distance::check_edit_args.
-// Writes the store, then refreshes the region as every edit does.  Blocking.
+// Writes the store, then commits the region as every edit does (gpu_volume_commit).  Blocking.
 GpuBuildStatus gpu_volume_edit_by_distance(GpuVolume* v, const GpuDistance* field, int op, uint32_t d2, float density, uint32_t material,
                                            uint64_t* out_n_voxels, std::string* why);
 // ---- the flood from seeds (include/blok_hip.h: blok_hip_volume_flood_field; flood_kernels.hip) ----
@@ -250,7 +236,7 @@ struct GpuFlood : GpuField {
 GpuBuildStatus gpu_volume_flood_field(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], const int32_t* seeds_xyz, uint64_t n_seeds,
                                       uint32_t max_steps, uint32_t flags, uint32_t material, GpuFlood* out, std::string* why);
 // = blok_hip_volume_edit_by_flood over the snapshot's region (inside the box); the arguments have passed flood::check_edit_args.
-// Writes the store, then refreshes the region as every edit does.  Blocking.
+// Writes the store, then commits the region as every edit does (gpu_volume_commit).  Blocking.
 GpuBuildStatus gpu_volume_edit_by_flood(GpuVolume* v, const GpuFlood* field, int op, uint32_t d, float density, uint32_t material,
                                         uint64_t* out_n_voxels, std::string* why);
 // ---- the column field and scatter (include/blok_hip.h: blok_hip_volume_column_field, blok_hip_volume_scatter_models; columns_kernels.hip) ----

@@ -158,8 +158,6 @@ __global__ __launch_bounds__(256) void brick_node_kernel(const uint64_t* masks_s
     out[i] = make_uint4(static_cast<uint32_t>(m), static_cast<uint32_t>(m >> 32), mat_base[i], 0u);
 }
 
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255u) / 256u); }
-
 // Common tail of the builders: compaction of the non-empty bricks, keys, radix sort, material offsets, material
 // ids, upper levels, final node array.  `launch_keys` / `launch_materials` enqueue the source-specific kernels.
 template <class KeyLauncher, class MaterialLauncher>
@@ -421,16 +419,13 @@ DenseCtx volume_ctx(const GpuVolume& v) {
     return d;
 }
 
-// Recomputes the masks of the bricks that contain voxels [lo, hi) (box-local voxel coordinates).
-GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why);
-GpuBuildStatus volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
-    if (v->keyed) return keyed_refresh(v, lo, hi, why);
-    for (int a = 0; a < 3; ++a) { v->edit_lo[a] = std::min(v->edit_lo[a], lo[a]); v->edit_hi[a] = std::max(v->edit_hi[a], hi[a]); }
+// The two layouts' halves of gpu_volume_commit, over a box [lo, hi) (box-local voxel coordinates) that holds a voxel.
+// General layout: recomputes the masks of the bricks that contain those voxels.
+GpuBuildStatus dense_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
     DenseCtx d = volume_ctx(*v);
     d.rx0 = lo[0] / 4u; d.ry0 = lo[1] / 4u; d.rz0 = lo[2] / 4u;
     d.rbx = (hi[0] + 3u) / 4u - d.rx0; d.rby = (hi[1] + 3u) / 4u - d.ry0; d.rbz = (hi[2] + 3u) / 4u - d.rz0;
     const uint64_t total = static_cast<uint64_t>(d.rbx) * d.rby * d.rbz;
-    if (!total) return GpuBuildStatus::Ok;
     ++v->refreshes[2];
     hipLaunchKernelGGL(dense_brick_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, d, total, v->d_masks, v->d_flag);
     BLOK_GPU_TRY(hipGetLastError());
@@ -662,9 +657,8 @@ KeyedCtx keyed_ctx(const GpuVolume& v) {
     return k;
 }
 
-// Masks of the bricks that contain voxels [lo, hi) and the occupancy words above them, level by level.
+// Key layout: masks of the bricks that contain those voxels and the occupancy words above them, level by level.
 GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
-    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
     const KeyedCtx k = keyed_ctx(*v);
     CellRange ranges[9] = {};
     uint64_t totals[9] = {};
@@ -694,7 +688,6 @@ GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t 
             BLOK_GPU_TRY(hipGetLastError());
         }
     }
-    for (int a = 0; a < 3; ++a) { v->edit_lo[a] = std::min(v->edit_lo[a], lo[a]); v->edit_hi[a] = std::max(v->edit_hi[a], hi[a]); }
     return GpuBuildStatus::Ok;
 }
 
@@ -864,23 +857,25 @@ void gpu_volume_destroy(GpuVolume* v) {
     *v = GpuVolume{};
 }
 
+GpuBuildStatus gpu_volume_commit(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], Edit kind, std::string* why) {
+    if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
+    v->edits.note(lo, hi, kind == Edit::MayFill);                   // (also when a launch below fails: the store is written)
+    return v->keyed ? keyed_refresh(v, lo, hi, why) : dense_refresh(v, lo, hi, why);
+}
+
 GpuBuildStatus gpu_volume_upload(GpuVolume* v, const float* density, const uint32_t* ids, std::string* why) {
     if (density) BLOK_GPU_TRY(hipMemcpy(v->d_density, density, v->cells() * sizeof(float), hipMemcpyHostToDevice));
     else BLOK_GPU_TRY(hipMemset(v->d_density, 0, v->cells() * sizeof(float)));
     if (ids) BLOK_GPU_TRY(hipMemcpy(v->d_ids, ids, v->cells() * sizeof(uint32_t), hipMemcpyHostToDevice));
     else BLOK_GPU_TRY(hipMemset(v->d_ids, 0, v->cells() * sizeof(uint32_t)));
     const uint32_t lo[3] = {0, 0, 0}, hi[3] = {v->nx, v->ny, v->nz};
-    return volume_refresh(v, lo, hi, why);
+    return gpu_volume_commit(v, lo, hi, density ? Edit::MayFill : Edit::OnlyClears, why);      // (a null density uploads zeros)
 }
 
 GpuBuildStatus gpu_volume_download(const GpuVolume* v, float* density, uint32_t* ids, std::string* why) {
     if (density) BLOK_GPU_TRY(hipMemcpy(density, v->d_density, v->cells() * sizeof(float), hipMemcpyDeviceToHost));
     if (ids) BLOK_GPU_TRY(hipMemcpy(ids, v->d_ids, v->cells() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return GpuBuildStatus::Ok;
-}
-
-GpuBuildStatus gpu_volume_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
-    return volume_refresh(v, lo, hi, why);
 }
 
 GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uint32_t* material, const float* density, size_t n,
@@ -899,7 +894,7 @@ GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uin
         edits[i] = VoxelEdit{static_cast<uint32_t>(l[0] + (static_cast<size_t>(l[2]) * v->ny + l[1]) * v->nx), material ? material[i] : 0u,
                              density ? density[i] : 1.0f};
     }
-    if (v->cells() > 0xFFFFFFFFull) { *why = "set_voxels: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "set_voxels", why)) return GpuBuildStatus::Unsupported;
     // sequential semantics: the last write of a voxel wins
     std::stable_sort(edits.begin(), edits.end(), [](const VoxelEdit& a, const VoxelEdit& b) { return a.index < b.index; });
     size_t m = 0;
@@ -910,8 +905,7 @@ GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uin
     BLOK_GPU_TRY(hipMemcpy(d_edits, edits.data(), m * sizeof(VoxelEdit), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(volume_set_kernel, dim3(blocks_for(m)), dim3(256), 0, nullptr, v->d_density, v->d_ids, d_edits, static_cast<uint32_t>(m));
     BLOK_GPU_TRY(hipGetLastError());
-    v->edit_may_add = true;                               // (a written density may be positive)
-    const GpuBuildStatus st = volume_refresh(v, lo, hi, why);
+    const GpuBuildStatus st = gpu_volume_commit(v, lo, hi, Edit::MayFill, why);      // (a written density may be positive)
     BLOK_GPU_TRY(hipDeviceSynchronize());
     return st;
 }
@@ -936,12 +930,12 @@ GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radiu
     b.ex = hi[0] - lo[0]; b.ey = hi[1] - lo[1]; b.ez = hi[2] - lo[2];
     b.chunk = static_cast<int32_t>(v->chunk); b.voxel_size = v->voxel_size;
     b.cx = center[0]; b.cy = center[1]; b.cz = center[2]; b.radius = radius; b.value = value; b.mode = mode;
-    if (mode == 0 && value > 0.0f) v->edit_may_add = true;          // max(density, value) can fill; min(density, value) never does (brush.cpp:52-57)
     const uint64_t total = static_cast<uint64_t>(b.ex) * b.ey * b.ez;
     if (!total) return GpuBuildStatus::Ok;
     hipLaunchKernelGGL(volume_brush_kernel, dim3(blocks_for(total)), dim3(256), 0, nullptr, b);
     BLOK_GPU_TRY(hipGetLastError());
-    return volume_refresh(v, lo, hi, why);
+    // max(density, value) can fill; min(density, value) never does (brush.cpp:52-57)
+    return gpu_volume_commit(v, lo, hi, mode == 0 && value > 0.0f ? Edit::MayFill : Edit::OnlyClears, why);
 }
 
 // ---- a region of the volume as a model (gpu_build.h: gpu_volume_capture) ------------------------------------------------------------
@@ -1035,7 +1029,7 @@ GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const u
                               int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why) {
     *out = GpuTree{};
     *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "capture_model: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "capture_model", why)) return GpuBuildStatus::Unsupported;
     if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
     DeviceMem mem;
     // 1. the tight box of the region's filled voxels
@@ -1106,7 +1100,7 @@ GpuBuildStatus clear_region(GpuVolume* v, const LabelPred& pred, const uint32_t 
     const uint64_t total = static_cast<uint64_t>(ex) * ey * ez;
     hipLaunchKernelGGL(clear_filled_kernel<kLabelled>, dim3(blocks_for(total)), dim3(256), 0, nullptr, v->d_density, v->d_ids, pred, v->nx, v->ny, lo[0], lo[1], lo[2], ex, ey, total);
     BLOK_GPU_TRY(hipGetLastError());
-    const GpuBuildStatus st = volume_refresh(v, lo, hi, why);      // (clearing never fills: edit_may_add stays as it was)
+    const GpuBuildStatus st = gpu_volume_commit(v, lo, hi, Edit::OnlyClears, why);
     BLOK_GPU_TRY(hipDeviceSynchronize());                                // blocking, as gpu_volume_set_voxels is
     return st;
 }

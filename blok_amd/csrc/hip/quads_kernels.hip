@@ -206,7 +206,7 @@ void gpu_quads_free(GpuQuads* q) {
 GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuQuads* out,
                                         uint64_t* out_n_faces, std::string* why) {
     *out = GpuQuads{}; *out_n_faces = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "extract_quads: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "extract_quads", why)) return GpuBuildStatus::Unsupported;
     if (lo[0] >= hi[0] || lo[1] >= hi[1] || lo[2] >= hi[2]) return GpuBuildStatus::Ok;
     QuadArgs a{};
     a.bricks = brick_masks_of(*v); a.ids = v->d_ids;

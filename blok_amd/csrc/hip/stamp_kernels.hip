@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void stamp_kernel(const StampArgs a) {
 GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements, int mode,
                                 float density, uint64_t* out_n_voxels, std::string* why) {
     if (out_n_voxels) *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "stamp_models: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "stamp_models", why)) return GpuBuildStatus::Unsupported;
     if (n_placements == 0) return GpuBuildStatus::Ok;
     DeviceMem mem;
     unsigned long long* d_counts;
@@ -113,9 +113,8 @@ GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const bl
         a.density = v->d_density; a.ids = v->d_ids; a.mode = mode; a.value = density; a.counts = d_counts;
         hipLaunchKernelGGL(stamp_kernel, dim3((a.nb[0] + 3u) / 4u, a.nb[1], a.nb[2]), dim3(256), 0, nullptr, a);
         BLOK_GPU_TRY(hipGetLastError());
-        if (mode != BLOK_STAMP_ERASE) v->edit_may_add = true;    // what the shadow rays' map has to know (gpu_build.h)
         // this placement's box alone: two far-apart stamps must not refresh what lies between them
-        const GpuBuildStatus st = gpu_volume_refresh(v, wlo, whi, why);
+        const GpuBuildStatus st = gpu_volume_commit(v, wlo, whi, mode != BLOK_STAMP_ERASE ? Edit::MayFill : Edit::OnlyClears, why);
         if (st != GpuBuildStatus::Ok) return st;
     }
     std::vector<unsigned long long> counts(kCountSlots * kSlotWords);

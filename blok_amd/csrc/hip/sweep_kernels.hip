@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs a) {
 
 GpuBuildStatus gpu_volume_sweep(const GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements,
                                 uint32_t direction, uint32_t max_distance, uint32_t flags, blok_sweep_result* out_results, std::string* why) {
-    if (v->cells() > 0xFFFFFFFFull) { *why = "sweep_models: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "sweep_models", why)) return GpuBuildStatus::Unsupported;
     if (n_placements == 0) return GpuBuildStatus::Ok;
     const uint32_t axis = W::direction_axis(direction);
     const int sign = W::direction_sign(direction);

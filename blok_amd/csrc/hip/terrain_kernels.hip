@@ -10,7 +10,7 @@
 //     rows early), the x and z neighbours are evaluated, by one loop, only for a solid voxel that nothing has exposed yet.
 // Every noise evaluation sits in a loop that is not unrolled, so each variant holds one copy of the cave and ore code (registers:
 // DESIGN.md §13).  The count and the box of the filled voxels are reduced per wave with shuffles, per workgroup through LDS, then one
-// lane takes seven integer atomics into one of kSpread copies.  volume_refresh over the written box leaves masks, occupancy words and
+// lane takes seven integer atomics into one of kSpread copies.  gpu_volume_commit over the written box leaves masks, occupancy words and
 // dirty flags.
 #include <hip/hip_runtime.h>
 
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void terrain_kernel(const TerrainArgs a) {
 GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_params& params, const uint32_t lo[3], const uint32_t hi[3],
                                            uint64_t* out_n_voxels, std::string* why) {
     if (out_n_voxels) *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "generate_terrain: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "generate_terrain", why)) return GpuBuildStatus::Unsupported;
     if (lo[0] >= hi[0] || lo[1] >= hi[1] || lo[2] >= hi[2]) return GpuBuildStatus::Ok;
     TerrainArgs a{};
     a.p = params; a.density = v->d_density; a.ids = v->d_ids; a.nx = v->nx; a.ny = v->ny;
@@ -169,11 +169,9 @@ GpuBuildStatus gpu_volume_generate_terrain(GpuVolume* v, const blok_terrain_para
         for (int c = 0; c < 3; ++c) { flo[c] = std::min(flo[c], words[k * kWords + 2 + c]); fhi[c] = std::max(fhi[c], words[k * kWords + 5 + c]); }
     }
     if (out_n_voxels) *out_n_voxels = written;
-    if (written) v->edit_may_add = true;
-    // replace mode rewrote the whole region; ADD touched the filled voxels only
-    GpuBuildStatus st = GpuBuildStatus::Ok;
-    if (!(params.flags & BLOK_TERRAIN_ADD)) st = gpu_volume_refresh(v, lo, hi, why);
-    else if (written) st = gpu_volume_refresh(v, flo, fhi, why);
+    // replace mode rewrote the whole region; ADD touched the filled voxels only (an empty box when nothing was filled)
+    const bool add = params.flags & BLOK_TERRAIN_ADD;
+    const GpuBuildStatus st = gpu_volume_commit(v, add ? flo : lo, add ? fhi : hi, written ? Edit::MayFill : Edit::OnlyClears, why);
     BLOK_GPU_TRY(hipDeviceSynchronize());
     return st;
 }

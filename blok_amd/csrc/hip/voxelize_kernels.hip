@@ -13,7 +13,7 @@
 //   3. solid mode: vox_column_kernel, a lane per (triangle, column) crossing, toggles one bit of a bit volume over the mesh's box;
 //      vox_prefix_kernel takes the prefix XOR of every row; vox_interior_kernel writes the interior voxels that are not on the surface.
 //   4. vox_finalize_kernel, a wave per listed brick: density and material of the surface voxels.
-//   5. volume_refresh over the box of the written voxels: masks, occupancy words and dirty flags as blok_hip_volume_set_voxels leaves them.
+//   5. gpu_volume_commit over the box of the written voxels: masks, occupancy words and dirty flags as blok_hip_volume_set_voxels leaves them.
 // Only integer atomics (Or, Min, Xor, Add): the result depends on the inputs alone.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -377,7 +377,7 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
                                    bool* invalid, std::string* why) {
     *invalid = false;
     if (out_n_voxels) *out_n_voxels = 0;
-    if (v->cells() > 0xFFFFFFFFull) { *why = "voxelize: volume larger than 2^32 cells"; return GpuBuildStatus::Unsupported; }
+    if (!cells_fit_32_bits(v, "voxelize", why)) return GpuBuildStatus::Unsupported;
     if (n_triangles > 0x7FFFFFFFull) { *why = "voxelize: more than 2^31 triangles"; return GpuBuildStatus::Unsupported; }
     if (n_triangles == 0) return GpuBuildStatus::Ok;
     const uint32_t nt = static_cast<uint32_t>(n_triangles);
@@ -509,8 +509,7 @@ GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t 
     }
     if (out_n_voxels) *out_n_voxels = written;
     if (!written) return GpuBuildStatus::Ok;
-    v->edit_may_add = true;
-    const GpuBuildStatus st = gpu_volume_refresh(v, lo, hi, why);
+    const GpuBuildStatus st = gpu_volume_commit(v, lo, hi, Edit::MayFill, why);
     BLOK_GPU_TRY(hipDeviceSynchronize());
     return st;
 }

@@ -257,7 +257,7 @@ def test_a_large_stamp_takes_the_upload_path_of_a_keyed_volume(mats):
 
 def test_sun_map_stays_valid_across_stamps(mats):
     """The scene of test_brush.py::test_sun_map_stays_valid_across_volume_edits.  A SET or KEEP stamp may fill voxels, which the shadow
-    rays' last-occluder map has to be told (GpuVolume::edit_may_add): every path-traced plane stays bit-identical with the map on and off.
+    rays' last-occluder map has to be told (gpu_build.h: Edit::MayFill): every path-traced plane stays bit-identical with the map on and off.
     The tower stands on open ground in front of the first camera, so its shadow falls on visible terrain."""
     w, h = 160, 120
     t = _tracer(w, h)

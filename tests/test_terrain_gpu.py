@@ -199,7 +199,7 @@ def test_shell_frames_equal_solid_frames_and_the_oracle():
 
 
 def test_path_traced_frames_with_and_without_the_sun_map():
-    """The edited box and edit_may_add reach the shadow rays' last-occluder map, also when a taller terrain replaces the first."""
+    """The edited box and its fill bit (gpu_build.h: gpu_volume_commit) reach the shadow rays' last-occluder map, also when a taller terrain replaces the first."""
     from blok_amd import world as W
     w, h = 160, 120
     mats = W.scene_materials()

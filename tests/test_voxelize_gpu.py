@@ -230,7 +230,7 @@ def test_traced_frames_equal_the_oracle_world():
 
 
 def test_path_traced_frames_with_and_without_the_sun_map_after_voxelizing():
-    """The edited box and edit_may_add left by the voxelizer reach the shadow rays' last-occluder map: frames stay bit-identical."""
+    """The edited box and the fill bit the voxelizer commits (gpu_build.h: gpu_volume_commit) reach the shadow rays' last-occluder map: frames stay bit-identical."""
     from blok_amd import world as W
     w, h = 160, 120
     mats = W.scene_materials()
