@@ -74,6 +74,10 @@ FLOOD_THROUGH_FILLED, FLOOD_SAME_MATERIAL = 1, 2  # = BLOK_FLOOD_THROUGH_FILLED,
 FLOOD_FAR = 0xFFFF                                # = BLOK_FLOOD_FAR
 FLOOD_MAX_STEPS = 65534                           # = BLOK_FLOOD_MAX_STEPS
 FLOOD_FILL, FLOOD_FILL_UNREACHED, FLOOD_PAINT, FLOOD_CLEAR = 0, 1, 2, 3      # = BLOK_FLOOD_FILL / _FILL_UNREACHED / _PAINT / _CLEAR
+# = blok_sun_map_info: frame and bookkeeping of the shadow rays' last-occluder map, 84 bytes
+SUN_MAP_INFO = np.dtype([("u", "<f4", 3), ("v", "<f4", 3), ("s", "<f4", 3), ("u0", "<f4"), ("v0", "<f4"), ("texel", "<f4"), ("nu", "<u4"), ("nv", "<u4"),
+                         ("has_map", "<u4"), ("loose_edits", "<u4"), ("tighten_pending", "<u4"), ("pending_u0", "<u4"), ("pending_u1", "<u4"),
+                         ("pending_v0", "<u4"), ("pending_v1", "<u4")])
 # = blok_columns_info: what a column field snapshot holds, 64 bytes
 COLUMNS_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("axis", "<u4"), ("min_top", "<u4"), ("max_top", "<u4"),
                          ("reserved", "<u4"), ("n_columns", "<u8"), ("n_hit", "<u8")])
@@ -304,6 +308,7 @@ HIP_SYMBOLS = {
     "blok_hip_multi_draw_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_hip_multi_download_hits": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
     "blok_hip_set_beam_budget": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "blok_hip_beam_cache_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "blok_hip_set_miss_writer": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_set_beam_cache": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_beam_cache_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -342,6 +347,7 @@ HIP_SYMBOLS = {
     "blok_hip_scatter_tiles_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_hip_frame_queue_stalls": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "blok_hip_set_sun_map": (C.c_int, [C.c_void_p, C.c_int]),
+    "blok_hip_sun_map_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "blok_hip_set_ray_batching": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_set_path_start": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "blok_denoise_settings_default": (None, [C.c_void_p]),

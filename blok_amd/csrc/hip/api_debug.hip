@@ -73,6 +73,31 @@ int blok_hip_beam_prepass(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0
     return BLOK_OK;
 }
 
+// The shadow rays' last-occluder map as it lies in device memory, with its frame and update_sun_map's bookkeeping.  The copy goes through
+// the null stream, where every raise and tighten launch was enqueued: it sees them all.
+int blok_hip_sun_map_download(blok_hip_ctx* ctx, blok_sun_map_info* out_info, float* map_out, size_t capacity) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sun map: no info struct");
+    *out_info = blok_sun_map_info{};
+    if (!ctx->has_sun_map || !ctx->d_sun_map) return BLOK_OK;
+    const blok::SunMapArgs& m = ctx->sun;
+    for (int a = 0; a < 3; ++a) { out_info->u[a] = m.u[a]; out_info->v[a] = m.v[a]; out_info->s[a] = m.s[a]; }
+    out_info->u0 = m.u0; out_info->v0 = m.v0; out_info->texel = m.texel; out_info->nu = m.nu; out_info->nv = m.nv;
+    out_info->has_map = 1u;
+    out_info->loose_edits = ctx->sun_loose_edits;
+    out_info->tighten_pending = ctx->sun_tighten_pending ? 1u : 0u;
+    if (ctx->sun_tighten_pending) {
+        out_info->pending_u0 = ctx->sun_tighten_u0; out_info->pending_u1 = ctx->sun_tighten_u1;
+        out_info->pending_v0 = ctx->sun_tighten_v0; out_info->pending_v1 = ctx->sun_tighten_v1;
+    }
+    if (!map_out) return BLOK_OK;
+    const size_t n = static_cast<size_t>(m.nu) * m.nv;
+    if (capacity < n) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sun map: output smaller than nu * nv floats");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(map_out, ctx->d_sun_map, n * sizeof(float), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
 // The counting sort behind a moving camera's frames (tile_order.h), on the caller's costs: order, its inverse, the live prefix and the
 // depth sums, to the host.
 int blok_hip_debug_class_order(blok_hip_ctx* ctx, const uint32_t* cost_host, uint32_t tiles_x, uint32_t tiles_y, uint32_t radius, const float* beam_host, uint32_t n_beams,
@@ -297,6 +322,23 @@ int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, ui
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (out_hits) *out_hits = ctx->beam_cache.hits;
     if (out_fills) *out_fills = ctx->beam_cache.fills;
+    return BLOK_OK;
+}
+
+// What the latest rectangle launch did about the kept bounds and, where it filled or walked from a slot, that slot's floats as they lie
+// in device memory once everything enqueued has finished.
+int blok_hip_beam_cache_download(blok_hip_ctx* ctx, int* out_action, uint32_t* out_n_beams, float* out_t0_host, size_t capacity) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const auto& B = ctx->beam_cache;
+    if (out_action) *out_action = B.last_action;
+    if (out_n_beams) *out_n_beams = B.last_action ? B.last_n_beams : 0u;
+    if (!out_t0_host || !B.last_action) return BLOK_OK;
+    if (B.last_slot < 0 || static_cast<uint32_t>(B.last_slot) >= blok::kBeamCacheSlots || !B.slots[B.last_slot].d_beam || B.last_n_beams > B.capacity)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the latest launch's slot is gone (a resize)");
+    if (capacity < B.last_n_beams) return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: output smaller than the launch's beam tiles");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_t0_host, B.slots[B.last_slot].d_beam, B.last_n_beams * sizeof(float), hipMemcpyDeviceToHost));
     return BLOK_OK;
 }
 

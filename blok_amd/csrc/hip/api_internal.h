@@ -158,6 +158,7 @@ struct blok_hip_ctx {
         } slots[blok::kBeamCacheSlots];
         size_t capacity = 0;                                // floats per slot
         uint64_t hits = 0, fills = 0;                       // blok_hip_beam_cache_counters
+        int last_action = 0, last_slot = -1; uint32_t last_n_beams = 0;      // the latest rectangle launch: 0 searched, 1 searched into last_slot, 2 walked from it (blok_hip_beam_cache_download)
     } beam_cache;
     // Longest-first scheduling of the walk for a camera at rest (tile_order.h; rectangle launches of the static forms): every walk wave
     // leaves the clocks it spent in d_cost (one buffer per context, for the launch geometry in `key`).  Every `interval` launches a

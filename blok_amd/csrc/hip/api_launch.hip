@@ -578,6 +578,8 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
         // the searches that fill a slot write plain floats: the two-launch form, this once
         if (cached.action == blok::BeamAction::Fill && plan.kind == blok::LaunchKind::Joint) { plan.kind = blok::LaunchKind::TwoLaunches; ctx->last_launch_kind = static_cast<int>(plan.kind); }
     }
+    ctx->beam_cache.last_action = cached.action == blok::BeamAction::Hit ? 2 : cached.action == blok::BeamAction::Fill ? 1 : 0;
+    ctx->beam_cache.last_slot = cached.slot; ctx->beam_cache.last_n_beams = n_beams;
     if (cached.action == blok::BeamAction::Hit) {
         // no searches: the walk over the view's live prefix, from the kept bounds; in front of it, what the search waves do besides searching
         // (the miss pixels, unless the walk writes them; the wave tiles the prefix has no workgroup for) — last_launch_kind stays the policy's

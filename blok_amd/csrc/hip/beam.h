@@ -157,8 +157,9 @@ __device__ __forceinline__ float beam_search(const TraceArgs& A, BeamVec ref, Be
             if (level == root_level) { finished = true; break; }
             ++level;
             node = __builtin_amdgcn_readlane(stk_node, level);
-            cand = static_cast<uint64_t>(__builtin_amdgcn_readlane(stk_lo, level)) |
-                   (static_cast<uint64_t>(__builtin_amdgcn_readlane(stk_hi, level)) << 32);
+            // (the builtin returns int: widened as it is, a low word with bit 31 set would set all 32 high candidates)
+            cand = static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(stk_lo, level))) |
+                   (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(stk_hi, level))) << 32);
             p0 = beam_lane(stk_p0, level); p1 = beam_lane(stk_p1, level); p2 = beam_lane(stk_p2, level); p3 = beam_lane(stk_p3, level);
             p4 = beam_lane(stk_p4, level);
             if (budget == 0u) { exhausted = true; fresh = false; break; }
@@ -212,7 +213,7 @@ __device__ __forceinline__ float beam_search(const TraceArgs& A, BeamVec ref, Be
             uint64_t pending; float q4;
             if (l == level) { pending = cand; q4 = p4; }                               // revisited node: what is left of its candidates
             else {
-                pending = static_cast<uint64_t>(__builtin_amdgcn_readlane(stk_lo, l)) | (static_cast<uint64_t>(__builtin_amdgcn_readlane(stk_hi, l)) << 32);
+                pending = static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(stk_lo, l))) | (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(stk_hi, l))) << 32);
                 q4 = beam_lane(stk_p4, l);
             }
             const float sl = static_cast<float>(1u << (2u * (l - 1u)));

@@ -457,6 +457,17 @@ class HipTracer:
         """Shadow rays stop at the last occluder of their sun-direction column (never changes a result); default on."""
         self._check(self._lib.blok_hip_set_sun_map(self._ctx, int(bool(enabled))))
 
+    def sun_map(self, want_map: bool = True):
+        """Read-back of the shadow rays' last-occluder map (blok_hip_debug.h: blok_hip_sun_map_download): (info, map) with info one
+        _ffi.SUN_MAP_INFO record and map the float32 texels shaped [nv][nu], or None without a map or with want_map False."""
+        info = np.zeros(1, dtype=_ffi.SUN_MAP_INFO)
+        self._check(self._lib.blok_hip_sun_map_download(self._ctx, _ffi.ptr(info), None, 0))
+        if not want_map or not int(info["has_map"][0]):
+            return info, None
+        texels = np.zeros((int(info["nv"][0]), int(info["nu"][0])), dtype=np.float32)
+        self._check(self._lib.blok_hip_sun_map_download(self._ctx, _ffi.ptr(info), _ffi.ptr(texels), texels.size))
+        return info, texels
+
     def set_beam(self, beam_tile_pixels: int):
         """Beam pre-pass granularity of the frame kernels in pixels (0 = off, default 32); never changes a result."""
         self._check(self._lib.blok_hip_set_beam(self._ctx, beam_tile_pixels))
@@ -565,6 +576,17 @@ class HipTracer:
         hits, fills = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.blok_hip_beam_cache_counters(self._ctx, C.byref(hits), C.byref(fills)))
         return int(hits.value), int(fills.value)
+
+    def beam_cache_last(self):
+        """(action, t0) of the latest rectangle launch (blok_hip_debug.h: blok_hip_beam_cache_download): action 0 it searched, 1 it searched
+        into a slot, 2 it walked from a slot; t0 that slot's start parameters per beam tile, row-major, or None for action 0."""
+        action, n = C.c_int(0), C.c_uint32(0)
+        self._check(self._lib.blok_hip_beam_cache_download(self._ctx, C.byref(action), C.byref(n), None, 0))
+        if not action.value:
+            return 0, None
+        t0 = np.zeros(int(n.value), dtype=np.float32)
+        self._check(self._lib.blok_hip_beam_cache_download(self._ctx, C.byref(action), C.byref(n), _ffi.ptr(t0), len(t0)))
+        return int(action.value), t0
 
     def set_beam_budget(self, max_node_visits: int):
         """Node visits a beam search may spend (0 = default); running out is answered conservatively, never changes a result."""

@@ -138,6 +138,12 @@ int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk);
 int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int enabled);
 /* Launches so far that walked from kept bounds (hits) and that searched into a slot (fills); either pointer may be null. */
 int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills);
+/* Read-back for the tests that check the kept bounds as numbers: *out_action = what the latest rectangle launch did — 0 it searched (or ran
+ * without a pre-pass), 1 it searched into a slot, 2 it walked from a slot without searching — *out_n_beams = its beam tiles (0 for action
+ * 0), and with a buffer of `capacity` floats, for actions 1 and 2, that slot's start parameters, row-major as blok_hip_beam_prepass returns
+ * them.  Waits for the device; launches nothing and changes nothing.  Any pointer may be null.  (blok_hip_beam_prepass itself never looks
+ * at the slots: it always searches, whatever blok_hip_set_beam_cache says.) */
+int blok_hip_beam_cache_download(blok_hip_ctx* ctx, int* out_action, uint32_t* out_n_beams, float* out_t0_host_or_null, size_t capacity);
 /* Node visits one beam search may spend (0 = the default, 256; searches average 35).  A search that runs out answers with the
  * lower bound over the cells it has not visited yet — valid, only less tight — never "none", so the frame is the same whatever
  * the budget (tests/test_gpu_parity.py runs with budgets of 1-64 visits against an unlimited search).  The pre-pass lasts as
@@ -187,6 +193,22 @@ int blok_hip_trace_wave_tiles_device(blok_hip_ctx* ctx, const blok_camera* cam, 
                                      const uint32_t* tiles_host, const float* t0_host_or_null, size_t n_tiles,
                                      void* out_hits_dev_or_null, void* out_rgba8_dev_or_null, void* hip_stream);
 int blok_hip_set_debug_wave_clocks(blok_hip_ctx* ctx, void* clocks_dev_or_null);
+/* Read-back of the shadow rays' last-occluder map (blok_hip_set_sun_map above) for the tests that check it as numbers: the map's frame
+ * exactly as the kernels use it, in float32 — texel (iu, iv) covers [u0 + iu texel, u0 + (iu + 1) texel] x [v0 + iv texel, ...] of (u . p, v . p)
+ * and holds an upper bound of s . p over the filled voxels of that column — and the bookkeeping of the edits since it was last tight
+ * (api.hip: update_sun_map).  map_out_or_null receives the nu * nv floats, row iv after row iv - 1; capacity is in floats and is not looked
+ * at without a buffer.  Launches nothing and changes nothing; it waits for every raise and tighten launch enqueued so far.  Without a map
+ * (no world, an empty one, a voxel size other than 1) has_map is 0 and everything else of the struct is 0. */
+typedef struct blok_sun_map_info {
+    float    u[3], v[3], s[3];    /* orthonormal; s = the sun direction */
+    float    u0, v0, texel;
+    uint32_t nu, nv;
+    uint32_t has_map;
+    uint32_t loose_edits;         /* edits since the map was last made tight (or since their union went to the pending rectangle) */
+    uint32_t tighten_pending;     /* 1: the texels [pending_u0, pending_u1] x [pending_v0, pending_v1] are still to be searched again */
+    uint32_t pending_u0, pending_u1, pending_v0, pending_v1;
+} blok_sun_map_info;
+int blok_hip_sun_map_download(blok_hip_ctx* ctx, blok_sun_map_info* out_info, float* map_out_or_null, size_t capacity);
 /* Which kernels the latest rectangle / tile launch of the context was issued as: 0 walk alone (no pre-pass), 1 two launches, 2 queues,
  * 3 joint, 4 list-fed joint, 5 beam launch + list-fed walk; -1 before the first launch (what form 3 chose; tests and diagnostics). */
 int blok_hip_last_launch_kind(const blok_hip_ctx* ctx);

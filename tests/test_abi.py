@@ -40,7 +40,7 @@ def test_drop_in_header_carries_no_hooks_or_launch_knobs():
     for n in names:
         assert "debug" not in n, n
     for knob in ("blok_hip_set_fused", "blok_hip_set_beam_budget", "blok_hip_set_miss_writer", "blok_hip_set_list_classes", "blok_hip_set_joint_prefix_limit",
-                 "blok_hip_beam_prepass", "blok_hip_trace_wave_tiles_device", "blok_hip_set_tile_ordering", "blok_hip_set_moving_order"):
+                 "blok_hip_beam_prepass", "blok_hip_sun_map_download", "blok_hip_beam_cache_download", "blok_hip_trace_wave_tiles_device", "blok_hip_set_tile_ordering", "blok_hip_set_moving_order"):
         assert knob not in names, knob
     mirror = (ROOT / "include" / "blok" / "hip_tracer.hpp").read_text()
     assert "blok_hip_debug.h" not in mirror, "the C++ mirror must build against the drop-in header alone"
@@ -59,6 +59,7 @@ def test_record_sizes_match_reference_layouts():
     assert _ffi.SUB_CHUNK.itemsize == 48     # resources.hpp:184 static_assert
     assert _ffi.MATERIAL.itemsize == 32      # material.hpp:114 static_assert
     assert _ffi.HIT.itemsize == 16
+    assert _ffi.SUN_MAP_INFO.itemsize == 84     # blok_hip_debug.h: blok_sun_map_info, 12 floats and 9 words
     assert _ffi.hip_lib().blok_hip_abi_version() >> 16 == 1
 
 
