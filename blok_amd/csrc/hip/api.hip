@@ -13,39 +13,27 @@ int set_error(blok_hip_ctx* ctx, int status, const std::string& msg) {
 }
 
 
-void free_post(blok_hip_ctx* ctx) {
-    auto& P = ctx->post;
-    for (int k = 0; k < 2; ++k)
-        for (void* p : {static_cast<void*>(P.hist_color[k]), static_cast<void*>(P.moments[k]), static_cast<void*>(P.world_pos[k]),
-                        static_cast<void*>(P.hist_len[k]), static_cast<void*>(P.unit_normals[k]), static_cast<void*>(P.taa_hist[k])})
-            if (p) (void)hipFree(p);
-    for (void* p : {static_cast<void*>(P.motion), static_cast<void*>(P.variance), static_cast<void*>(P.ping), static_cast<void*>(P.pong), static_cast<void*>(P.widen),
-                    static_cast<void*>(P.rt_planes[0]), static_cast<void*>(P.rt_planes[1]), static_cast<void*>(P.rt_planes[2]), static_cast<void*>(P.rt_planes[3]),
-                    static_cast<void*>(P.rt_denoised), static_cast<void*>(P.rt_resolved), static_cast<void*>(P.rt_ldr), static_cast<void*>(P.rt_final),
-                    static_cast<void*>(P.rt_normal_roughness_h), static_cast<void*>(P.rt_motion_h), static_cast<void*>(P.rt_albedo_metallic_u8),
-                    static_cast<void*>(P.rt_ids)})
-        if (p) (void)hipFree(p);
-    P = blok_hip_ctx::Post{};
-}
-
+// The world goes; what is the resident volume's (tree_owned_by_volume: the owners are empty) stays the volume's.
 void free_world(blok_hip_ctx* ctx) {
-    if (ctx->d_nodes && !ctx->tree_owned_by_volume) (void)hipFree(ctx->d_nodes);
-    if (ctx->d_tree_materials && !ctx->tree_owned_by_volume) (void)hipFree(ctx->d_tree_materials);
-    ctx->tree_owned_by_volume = false;
-    if (ctx->d_materials) (void)hipFree(ctx->d_materials);
-    if (ctx->d_sun_map) (void)hipFree(ctx->d_sun_map);
-    ctx->d_sun_map = nullptr; ctx->has_sun_map = false;
-    if (ctx->d_dense_tiled) (void)hipFree(ctx->d_dense_tiled);
-    if (ctx->d_dense_bits) (void)hipFree(ctx->d_dense_bits);
-    ctx->d_dense_tiled = ctx->d_dense_bits = nullptr; ctx->has_dense = false;
-    ctx->d_nodes = nullptr; ctx->d_tree_materials = nullptr; ctx->d_materials = nullptr;
+    ctx->own_nodes.reset(); ctx->own_tree_materials.reset();
+    ctx->d_nodes = nullptr; ctx->d_tree_materials = nullptr; ctx->tree_owned_by_volume = false;
+    ctx->d_materials.reset(); ctx->d_sun_map.reset(); ctx->d_dense_tiled.reset(); ctx->d_dense_bits.reset();
+    ctx->has_sun_map = false; ctx->has_dense = false;
     ctx->n_materials = 0; ctx->has_world = false; ctx->built_on_device = false; ctx->stats = blok_world_stats{};
     ctx->world_voxel_size = 1.0f;
 }
 
+// A tree the device builders made (gpu_build.h) becomes the installed one: the context's own from here, unless it lies in the resident
+// volume's arrays.  Behind free_world.
+void adopt_tree(blok_hip_ctx* ctx, const blok::GpuTree& gpu) {
+    ctx->d_nodes = gpu.d_nodes; ctx->d_tree_materials = gpu.d_materials;
+    ctx->tree_owned_by_volume = gpu.owned_by_volume;
+    if (!gpu.owned_by_volume) { ctx->own_nodes.adopt(gpu.d_nodes, gpu.n_nodes); ctx->own_tree_materials.adopt(gpu.d_materials, gpu.n_voxels); }
+}
+
 int install_materials(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {
     if (!n_materials) return BLOK_OK;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_materials), n_materials * sizeof(blok_material)));
+    BLOK_HIP_TRY(ctx, ctx->d_materials.reserve(n_materials, blok::FreeAfter::nothing()));      // (behind free_world: there is no old table)
     BLOK_HIP_TRY(ctx, hipMemcpy(ctx->d_materials, materials, n_materials * sizeof(blok_material), hipMemcpyHostToDevice));
     ctx->n_materials = n_materials;
     return BLOK_OK;
@@ -56,8 +44,9 @@ int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_mater
     free_world(ctx);
     const size_t node_bytes = tree.nodes.size() * sizeof(blok::TreeNode);
     const size_t mat_bytes = std::max<size_t>(tree.materials.size(), 1) * sizeof(uint32_t);
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_nodes), node_bytes));
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tree_materials), mat_bytes));
+    BLOK_HIP_TRY(ctx, ctx->own_nodes.reserve(tree.nodes.size(), blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, ctx->own_tree_materials.reserve(mat_bytes / sizeof(uint32_t), blok::FreeAfter::nothing()));
+    ctx->d_nodes = ctx->own_nodes; ctx->d_tree_materials = ctx->own_tree_materials;
     BLOK_HIP_TRY(ctx, hipMemcpy(ctx->d_nodes, tree.nodes.data(), node_bytes, hipMemcpyHostToDevice));
     if (!tree.materials.empty())
         BLOK_HIP_TRY(ctx, hipMemcpy(ctx->d_tree_materials, tree.materials.data(),
@@ -77,7 +66,7 @@ int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_mater
 // Rebuilds the shadow rays' last-occluder map for the installed world (one wave per texel of the plane perpendicular to the
 // sun; texel = 1 voxel, coarser for worlds wider than 1024 voxels so that the map stays <= 2048 x 2048).
 int rebuild_sun_map(blok_hip_ctx* ctx) {
-    if (ctx->d_sun_map) { (void)hipDeviceSynchronize(); (void)hipFree(ctx->d_sun_map); ctx->d_sun_map = nullptr; }
+    if (ctx->d_sun_map) { (void)hipDeviceSynchronize(); ctx->d_sun_map.reset(); }
     ctx->has_sun_map = false;
     ctx->sun_loose_edits = 0; ctx->sun_tighten_pending = false;      // a whole new map owes nothing
     if (!ctx->has_world || ctx->stats.levels == 0 || ctx->stats.n_voxels == 0) return BLOK_OK;
@@ -112,7 +101,7 @@ int rebuild_sun_map(blok_hip_ctx* ctx) {
     m.texel = static_cast<float>(std::max(1.0, std::ceil(extent / 2048.0)));
     m.u0 = static_cast<float>(std::floor(lo[0]) - m.texel); m.v0 = static_cast<float>(std::floor(lo[1]) - m.texel);
     m.nu = static_cast<uint32_t>(std::ceil((hi[0] - m.u0) / m.texel)) + 1u; m.nv = static_cast<uint32_t>(std::ceil((hi[1] - m.v0) / m.texel)) + 1u;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_sun_map), static_cast<size_t>(m.nu) * m.nv * sizeof(float)));
+    BLOK_HIP_TRY(ctx, ctx->d_sun_map.reserve(static_cast<size_t>(m.nu) * m.nv, blok::FreeAfter::nothing()));
     m.map = ctx->d_sun_map;
     m.iu0 = m.iv0 = 0; m.sub_nu = m.nu; m.sub_nv = m.nv;
     blok::launch_sun_map(m, nullptr);
@@ -189,18 +178,14 @@ int update_sun_map(blok_hip_ctx* ctx, const int32_t lo[3], const int32_t hi[3], 
     if (!launched) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipGetLastError());
     // launches on other (non-blocking) streams do not wait for the null stream: the path entries wait for this marker instead
-    if (!ctx->sun_event) BLOK_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->sun_event, hipEventDisableTiming));
+    BLOK_HIP_TRY(ctx, ctx->sun_event.create());
     BLOK_HIP_TRY(ctx, hipEventRecord(ctx->sun_event, nullptr));
     ctx->sun_event_pending = true;
     return BLOK_OK;
 }
 
 int ensure_frame(blok_hip_ctx* ctx, size_t records) {
-    if (records <= ctx->frame_capacity) return BLOK_OK;
-    if (ctx->d_frame) (void)hipFree(ctx->d_frame);
-    ctx->d_frame = nullptr; ctx->frame_capacity = 0;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_frame), records * sizeof(blok_hit)));
-    ctx->frame_capacity = records;
+    BLOK_HIP_TRY(ctx, ctx->d_frame.reserve(records, blok::FreeAfter::nothing()));      // (only blocking entries use it, and each ends with a blocking copy)
     return BLOK_OK;
 }
 
@@ -226,12 +211,7 @@ blok::TraceArgs base_args(const blok_hip_ctx* ctx, const blok_camera* cam) {
 // The stream's beam buffer, grown to n floats.
 int beam_buffer(blok_hip_ctx* ctx, hipStream_t stream, size_t n, float** out) {
     auto& slot = ctx->beam_buffers[stream];
-    if (slot.n_beam < n) {
-        if (slot.beam) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(slot.beam); }
-        slot.beam = nullptr; slot.n_beam = 0;
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.beam), n * sizeof(float)));
-        slot.n_beam = n;
-    }
+    BLOK_HIP_TRY(ctx, slot.beam.reserve(n, blok::FreeAfter::work_on(stream)));
     *out = slot.beam;
     return BLOK_OK;
 }
@@ -244,17 +224,11 @@ int prepare_queue(blok_hip_ctx* ctx, blok::RayMode mode, const blok::TraceArgs& 
     const size_t part_capacity = static_cast<size_t>((n_beams + parts - 1u) / parts) * per_beam;
     const size_t need = part_capacity * parts;
     auto& slot = ctx->beam_buffers[stream];
-    if (!slot.ctl) {
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.ctl), blok::kFrameCtlWords * sizeof(uint32_t)));
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.ctl, 0, blok::kFrameCtlWords * sizeof(uint32_t), stream));      // in stream order, before the launch
-    }
-    if (slot.capacity < need) {
-        if (slot.entries) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(slot.entries); }
-        slot.entries = nullptr; slot.capacity = 0;
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.entries), need * sizeof(unsigned long long)));
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.entries, 0xFF, need * sizeof(unsigned long long), stream));   // every slot empty; a launch leaves them so
-        slot.capacity = need;
-    }
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, slot.ctl.reserve(blok::kFrameCtlWords, blok::FreeAfter::nothing(), &fresh));
+    if (fresh) BLOK_HIP_TRY_FILL(ctx, slot.ctl, hipMemsetAsync(slot.ctl, 0, blok::kFrameCtlWords * sizeof(uint32_t), stream));      // in stream order, before the launch
+    BLOK_HIP_TRY(ctx, slot.entries.reserve(need, blok::FreeAfter::work_on(stream), &fresh));
+    if (fresh) BLOK_HIP_TRY_FILL(ctx, slot.entries, hipMemsetAsync(slot.entries, 0xFF, need * sizeof(unsigned long long), stream));   // every slot empty; a launch leaves them so
     queue->ctl = slot.ctl; queue->entries = slot.entries; queue->n_beam = n_beams; queue->part_capacity = static_cast<uint32_t>(part_capacity);
     queue->n_parts = parts; queue->chunk = ctx->frame_chunk;
     const int m = mode == blok::RayMode::Rect ? 0 : 1;
@@ -335,7 +309,7 @@ int blok_hip_create(blok_hip_ctx** out_ctx, int device_ordinal, uint32_t width, 
     ctx->cu_count = prop.multiProcessorCount;
     if (const char* e = std::getenv("BLOK_FRAME_PARTS")) { const long v = std::atol(e); if (v >= 1 && v <= long(blok::kFrameParts)) ctx->frame_parts = uint32_t(v); }
     if (const char* e = std::getenv("BLOK_FRAME_CHUNK")) { const long v = std::atol(e); if (v >= 1 && v <= 64) ctx->frame_chunk = uint32_t(v); }
-    if (hipEventCreate(&ctx->ev_begin) != hipSuccess || hipEventCreate(&ctx->ev_end) != hipSuccess) {
+    if (ctx->ev_begin.create(hipEventDefault) != hipSuccess || ctx->ev_end.create(hipEventDefault) != hipSuccess) {
         delete ctx;
         return set_error(nullptr, BLOK_ERR_HIP, "hipEventCreate failed");
     }
@@ -361,15 +335,6 @@ int blok_hip_resize(blok_hip_ctx* ctx, uint32_t width, uint32_t height) {
     return BLOK_OK;
 }
 
-static void free_stream_scratch(blok_hip_ctx::StreamScratch& sc) {
-    for (void* p : {static_cast<void*>(sc.beam), static_cast<void*>(sc.ctl), static_cast<void*>(sc.entries), static_cast<void*>(sc.tile_map),
-                    static_cast<void*>(sc.slots), static_cast<void*>(sc.gave_up), static_cast<void*>(sc.list_entries), static_cast<void*>(sc.list_ctl), sc.tail_pool,
-                    static_cast<void*>(sc.inst_bins), static_cast<void*>(sc.inst_hits), sc.tlas})
-        if (p) (void)hipFree(p);
-    if (sc.list_hint) (void)hipHostFree(sc.list_hint);
-    sc = blok_hip_ctx::StreamScratch{};
-}
-
 int blok_hip_release_stream(blok_hip_ctx* ctx, void* hip_stream) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -377,7 +342,7 @@ int blok_hip_release_stream(blok_hip_ctx* ctx, void* hip_stream) {
     // the stream's launches may still be using its scratch, and another stream's pending sort may be waiting for its marker
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     auto it = ctx->beam_buffers.find(stream);
-    if (it != ctx->beam_buffers.end()) { free_stream_scratch(it->second); ctx->beam_buffers.erase(it); }
+    if (it != ctx->beam_buffers.end()) ctx->beam_buffers.erase(it);
     forget_device_activity(ctx, true, stream);
     settle_beam_cache(ctx);                            // (a later stream may get this one's handle: nobody is "already waiting" by name any more)
     return BLOK_OK;
@@ -386,30 +351,10 @@ int blok_hip_release_stream(blok_hip_ctx* ctx, void* hip_stream) {
 void blok_hip_destroy(blok_hip_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    free_world(ctx);
-    free_models(ctx);
-    if (ctx->rt_instances) (void)hipFree(ctx->rt_instances);
-    if (ctx->rt_prev_instances) (void)hipFree(ctx->rt_prev_instances);
-    if (ctx->d_frame) (void)hipFree(ctx->d_frame);
-    free_post(ctx);
     if (ctx->has_volume) blok::gpu_volume_destroy(&ctx->volume);
     free_volume_snapshots(ctx);
     forget_device_activity(ctx);
-    for (auto& kv : ctx->beam_buffers) free_stream_scratch(kv.second);
-    if (ctx->d_list_cost) (void)hipFree(ctx->d_list_cost);
-    free_order(ctx);
-    free_beam_cache(ctx);
-    if (ctx->order.h_live) (void)hipHostFree(ctx->order.h_live);
-    if (ctx->order.h_depth) (void)hipHostFree(ctx->order.h_depth);
-    if (ctx->order.h_fallback) (void)hipHostFree(ctx->order.h_fallback);
-    if (ctx->order.d_fallback) (void)hipFree(ctx->order.d_fallback);
-    if (ctx->order.done) (void)hipEventDestroy(ctx->order.done);
-    if (ctx->d_accum) (void)hipFree(ctx->d_accum);
-    if (ctx->d_color) (void)hipFree(ctx->d_color);
-    if (ctx->sun_event) (void)hipEventDestroy(ctx->sun_event);
-    if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-    if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    delete ctx;
+    delete ctx;                                        // every array and event goes with the member that owns it
 }
 
 int blok_hip_upload_world(blok_hip_ctx* ctx, const blok_svo_node* nodes, size_t n_nodes,
@@ -443,8 +388,7 @@ int blok_hip_upload_world(blok_hip_ctx* ctx, const blok_svo_node* nodes, size_t 
         if (st == blok::GpuBuildStatus::OutOfMemory) return set_error(ctx, BLOK_ERR_OOM, reason);
         if (st == blok::GpuBuildStatus::Ok) {
             free_world(ctx);
-            ctx->d_nodes = gpu.d_nodes;
-            ctx->d_tree_materials = gpu.d_materials;
+            adopt_tree(ctx, gpu);
             const int rc = install_materials(ctx, materials, n_materials);
             if (rc != BLOK_OK) { free_world(ctx); return rc; }
             ctx->stats.n_voxels = gpu.n_voxels;
@@ -491,18 +435,17 @@ static int keep_dense_grid(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, 
     const uint64_t tiles = static_cast<uint64_t>(tx) * ty * tz;
     if (tiles > 0x7FFFFFFFull / 512u * 8u) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "dense grid too large for the dense-grid path");
     const size_t cells = static_cast<size_t>(nx) * ny * nz, words = (tiles + 31u) / 32u;
-    uint32_t* d_ids = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_ids), cells * sizeof(uint32_t)));
+    blok::DeviceArray<uint32_t> d_ids;
+    BLOK_HIP_TRY(ctx, d_ids.reserve(cells, blok::FreeAfter::nothing()));
     hipError_t e = hipMemcpy(d_ids, ids, cells * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_dense_tiled), tiles * 512u * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_dense_bits), words * sizeof(uint32_t));
+    if (e == hipSuccess) e = ctx->d_dense_tiled.reserve(tiles * 512u, blok::FreeAfter::nothing());      // (behind free_world: there is no old grid)
+    if (e == hipSuccess) e = ctx->d_dense_bits.reserve(words, blok::FreeAfter::nothing());
     if (e == hipSuccess) e = hipMemset(ctx->d_dense_bits, 0, words * sizeof(uint32_t));
     if (e == hipSuccess) {
         blok::launch_dense_tile(d_ids, nx, ny, nz, tx, ty, tz, ctx->d_dense_tiled, ctx->d_dense_bits, nullptr);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
-    (void)hipFree(d_ids);
     if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("dense grid: ") + hipGetErrorString(e));
     ctx->dense_tiles[0] = tx; ctx->dense_tiles[1] = ty; ctx->dense_tiles[2] = tz;
     for (int a = 0; a < 3; ++a) ctx->dense_origin[a] = o[a];
@@ -532,8 +475,7 @@ int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, u
         if (st == blok::GpuBuildStatus::OutOfMemory) return set_error(ctx, BLOK_ERR_OOM, reason);
         if (st == blok::GpuBuildStatus::Ok) {
             free_world(ctx);
-            ctx->d_nodes = gpu.d_nodes;
-            ctx->d_tree_materials = gpu.d_materials;
+            adopt_tree(ctx, gpu);
             const int rc = install_materials(ctx, materials, n_materials);
             if (rc != BLOK_OK) { free_world(ctx); return rc; }
             ctx->stats.n_voxels = gpu.n_voxels;
@@ -724,13 +666,9 @@ int scatter_frames(blok_hip_ctx* ctx, bool codes, const void* gathered_dev, cons
     // the stream's tile map: zero when a launch begins and when it ends (the tile kernel puts back what the map kernel set)
     auto& slot = ctx->beam_buffers[stream];
     const size_t need = static_cast<size_t>(a.tiles_total) * n_frames;
-    if (slot.n_tile_map < need) {
-        if (slot.tile_map) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(slot.tile_map); }
-        slot.tile_map = nullptr; slot.n_tile_map = 0;
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.tile_map), need * sizeof(uint32_t)));
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.tile_map, 0, need * sizeof(uint32_t), stream));
-        slot.n_tile_map = need;
-    }
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, slot.tile_map.reserve(need, blok::FreeAfter::work_on(stream), &fresh));
+    if (fresh) BLOK_HIP_TRY_FILL(ctx, slot.tile_map, hipMemsetAsync(slot.tile_map, 0, need * sizeof(uint32_t), stream));
     a.tile_map = slot.tile_map;
     blok::launch_scatter_tiles(a, codes, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
@@ -784,8 +722,8 @@ int blok_hip_trace_rays(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, 
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = ensure_frame(ctx, n);
     if (rc != BLOK_OK) return rc;
-    blok_ray* d_rays = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_rays), n * sizeof(blok_ray)));
+    blok::DeviceArray<blok_ray> d_rays;
+    BLOK_HIP_TRY(ctx, d_rays.reserve(n, blok::FreeAfter::nothing()));
     hipError_t e = hipMemcpy(d_rays, rays_host, n * sizeof(blok_ray), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         blok::TraceArgs a = base_args(ctx, nullptr);
@@ -793,7 +731,6 @@ int blok_hip_trace_rays(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, 
         rc = launch_timed(ctx, blok::RayMode::Rays, a, static_cast<uint32_t>((n + blok::kBlock - 1) / blok::kBlock), nullptr);
         if (rc == BLOK_OK) e = hipMemcpy(out_hits_host, ctx->d_frame, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d_rays);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays copy: ") + hipGetErrorString(e));
     return BLOK_OK;
@@ -857,12 +794,8 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     if (ctx->ray_batching >= 3u && max_bounces >= 2u && spp >= 4u && !ctx->path_resume && blok::kBlock == 64 && !instanced) {
         const size_t bytes = static_cast<size_t>(path_blocks) * blok::kTailCapacity * sizeof(blok::TailRecord);
         auto& scratch = ctx->beam_buffers[stream];             // per launch stream: launches on two streams may be in flight together
-        if (bytes > scratch.tail_pool_bytes) {
-            if (scratch.tail_pool) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(scratch.tail_pool); scratch.tail_pool = nullptr; scratch.tail_pool_bytes = 0; }
-            BLOK_HIP_TRY(ctx, hipMalloc(&scratch.tail_pool, bytes));
-            scratch.tail_pool_bytes = bytes;
-        }
-        p.tail_pool = static_cast<blok::TailRecord*>(scratch.tail_pool);
+        BLOK_HIP_TRY(ctx, scratch.tail_pool.reserve(bytes, blok::FreeAfter::work_on(stream)));
+        p.tail_pool = static_cast<blok::TailRecord*>(scratch.tail_pool.get());
         p.tail_cap = ctx->tail_cap; p.tail_cap_parked = ctx->tail_cap_parked;
     }
     blok::TlasScene scene{};
@@ -871,18 +804,13 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
         scene.models = ctx->models.d_desc; scene.n_models = static_cast<uint32_t>(ctx->models.desc.size());
         if (inst->n <= blok::kTlasMax) {
             auto& scratch = ctx->beam_buffers[stream];
-            const size_t need = blok::tlas_nodes(inst->n);
-            if (need > scratch.n_tlas) {
-                if (scratch.tlas) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(scratch.tlas); scratch.tlas = nullptr; scratch.n_tlas = 0; }
-                BLOK_HIP_TRY(ctx, hipMalloc(&scratch.tlas, need * sizeof(blok::TlasNode)));
-                scratch.n_tlas = need;
-            }
-            scene.nodes = static_cast<const blok::TlasNode*>(scratch.tlas);
+            BLOK_HIP_TRY(ctx, scratch.tlas.reserve(blok::tlas_nodes(inst->n) * sizeof(blok::TlasNode), blok::FreeAfter::work_on(stream)));
+            scene.nodes = static_cast<const blok::TlasNode*>(scratch.tlas.get());
         }
     }
     if (ctx->timing) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, stream));
     if (instanced && scene.nodes)
-        blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas), stream);
+        blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas.get()), stream);
     if (n_beams) blok::launch_beam(blok::RayMode::Rect, p.trace, n_beams, stream);
     if (instanced) blok::launch_paths_instanced(p, scene, ctx->models.stack_levels, path_blocks, stream);
     else blok::launch_paths(p, path_blocks, stream);
@@ -927,17 +855,16 @@ int blok_hip_trace_paths(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0,
     if (!rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame");
     const size_t n = static_cast<size_t>(w) * h, bytes = n * 4 * sizeof(float);
     float* host[4] = {planes_host->color, planes_host->world_pos, planes_host->normal_roughness, planes_host->albedo_metallic};
-    float* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    blok::DeviceArray<float> dev[4];
     hipError_t e = hipSuccess;
     for (int i = 0; i < 4 && e == hipSuccess; ++i)
-        if (host[i]) e = hipMalloc(reinterpret_cast<void**>(&dev[i]), bytes);
+        if (host[i]) e = dev[i].reserve(4 * n, blok::FreeAfter::nothing());
     if (e == hipSuccess) {
         const blok_gbuffer planes_dev{dev[0], dev[1], dev[2], dev[3]};
         rc = blok_hip_trace_paths_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, &planes_dev, nullptr);
         for (int i = 0; i < 4 && rc == BLOK_OK && e == hipSuccess; ++i)
             if (host[i]) e = hipMemcpy(host[i], dev[i], bytes, hipMemcpyDeviceToHost);
     }
-    for (float* d : dev) if (d) (void)hipFree(d);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP,
                                           std::string("trace_paths: ") + hipGetErrorString(e));
@@ -961,14 +888,13 @@ int blok_hip_tonemap(blok_hip_ctx* ctx, const float* hdr_host, uint32_t n_pixels
     if (!hdr_host || !out_rgba8_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null tonemap buffer");
     if (!n_pixels) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float* d_in = nullptr; uint32_t* d_out = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_in), static_cast<size_t>(n_pixels) * 16));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), static_cast<size_t>(n_pixels) * 4);
+    blok::DeviceArray<float> d_in; blok::DeviceArray<uint32_t> d_out;
+    BLOK_HIP_TRY(ctx, d_in.reserve(static_cast<size_t>(n_pixels) * 4, blok::FreeAfter::nothing()));
+    hipError_t e = d_out.reserve(n_pixels, blok::FreeAfter::nothing());
     int rc = BLOK_OK;
     if (e == hipSuccess) e = hipMemcpy(d_in, hdr_host, static_cast<size_t>(n_pixels) * 16, hipMemcpyHostToDevice);
     if (e == hipSuccess) rc = blok_hip_tonemap_device(ctx, d_in, n_pixels, exposure, saturation_boost, tonemap_operator, d_out, nullptr);
     if (e == hipSuccess && rc == BLOK_OK) e = hipMemcpy(out_rgba8_host, d_out, static_cast<size_t>(n_pixels) * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in); if (d_out) (void)hipFree(d_out);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("tonemap: ") + hipGetErrorString(e));
     return BLOK_OK;
@@ -1002,11 +928,9 @@ int blok_hip_draw_frame_accumulate(blok_hip_ctx* ctx, const blok_camera* cam, ui
     if (!spp_per_frame || !max_bounces) return set_error(ctx, BLOK_ERR_INVALID_ARG, "spp and bounces must be positive");
     const size_t n = static_cast<size_t>(ctx->width) * ctx->height;
     if (ctx->accum_pixels != n) {                                      // first use or resize: (re)allocate and clear
-        if (ctx->d_accum) (void)hipFree(ctx->d_accum);
-        if (ctx->d_color) (void)hipFree(ctx->d_color);
-        ctx->d_accum = ctx->d_color = nullptr; ctx->accum_pixels = 0;
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_accum), n * 4 * sizeof(float)));
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_color), n * 4 * sizeof(float)));
+        ctx->d_accum.reset(); ctx->d_color.reset(); ctx->accum_pixels = 0;      // (another shape, smaller ones included: not a reserve that keeps a larger array)
+        BLOK_HIP_TRY(ctx, ctx->d_accum.reserve(n * 4, blok::FreeAfter::nothing()));
+        BLOK_HIP_TRY(ctx, ctx->d_color.reserve(n * 4, blok::FreeAfter::nothing()));
         ctx->accum_pixels = n;
         ctx->has_prev_cam = false;
     }
@@ -1018,7 +942,7 @@ int blok_hip_draw_frame_accumulate(blok_hip_ctx* ctx, const blok_camera* cam, ui
     if (rc != BLOK_OK) return rc;
     rc = ensure_frame(ctx, (n + 3) / 4);
     if (rc != BLOK_OK) return rc;
-    blok::AccumArgs a{ctx->d_color, ctx->d_accum, out_rgba8_host ? reinterpret_cast<uint32_t*>(ctx->d_frame) : nullptr,
+    blok::AccumArgs a{ctx->d_color, ctx->d_accum, out_rgba8_host ? reinterpret_cast<uint32_t*>(ctx->d_frame.get()) : nullptr,
                       static_cast<uint32_t>(n)};
     blok::launch_accumulate(a, nullptr);
     BLOK_HIP_TRY(ctx, hipGetLastError());

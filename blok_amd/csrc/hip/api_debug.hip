@@ -60,15 +60,14 @@ int blok_hip_beam_prepass(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0
     rc = prepare_beam(ctx, blok::RayMode::Rect, a, nullptr, 0, &n_beams);
     if (rc != BLOK_OK) return rc;
     if (!n_beams || capacity < n_beams) return set_error(ctx, BLOK_ERR_INVALID_ARG, "output too small for the rectangle's beam tiles");
-    uint32_t* d_visits = nullptr;
-    if (out_visits_host) BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_visits), n_beams * sizeof(uint32_t)));
+    blok::DeviceArray<uint32_t> d_visits;
+    if (out_visits_host) BLOK_HIP_TRY(ctx, d_visits.reserve(n_beams, blok::FreeAfter::nothing()));
     a.debug_visits = d_visits;
     a.miss_in_walk = 1u;                               // nothing is written but the start parameters
     blok::launch_beam(blok::RayMode::Rect, a, n_beams, nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out_t0_host, a.beam, n_beams * sizeof(float), hipMemcpyDeviceToHost);
     if (e == hipSuccess && d_visits) e = hipMemcpy(out_visits_host, d_visits, n_beams * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (d_visits) (void)hipFree(d_visits);
     BLOK_HIP_TRY(ctx, e);
     return BLOK_OK;
 }
@@ -107,16 +106,17 @@ int blok_hip_debug_class_order(blok_hip_ctx* ctx, const uint32_t* cost_host, uin
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "class order: costs, outputs, a grid of at most 2^24 tiles and a radius of at most 8");
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t n = tiles_x * tiles_y;
+    blok::DeviceMem mem;
     uint32_t *d_cost = nullptr, *d_order = nullptr, *d_rank = nullptr, *d_live = nullptr;
     float *d_beam = nullptr, *d_depth = nullptr;
-    void* d_scratch = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_cost), n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_order), n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rank), n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_live), sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_depth), blok::kOrderDepthPartials * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_beam), (n_beams ? n_beams : 1u) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_scratch, blok::tile_order_class_sort_bytes(tiles_x, tiles_y));
+    unsigned char* d_scratch = nullptr;
+    hipError_t e = mem.alloc(&d_cost, n);
+    if (e == hipSuccess) e = mem.alloc(&d_order, n);
+    if (e == hipSuccess) e = mem.alloc(&d_rank, n);
+    if (e == hipSuccess) e = mem.alloc(&d_live, 1);
+    if (e == hipSuccess) e = mem.alloc(&d_depth, blok::kOrderDepthPartials * 3);
+    if (e == hipSuccess) e = mem.alloc(&d_beam, n_beams);
+    if (e == hipSuccess) e = mem.alloc(&d_scratch, blok::tile_order_class_sort_bytes(tiles_x, tiles_y));
     if (e == hipSuccess) e = hipMemcpy(d_cost, cost_host, n * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && n_beams && beam_host) e = hipMemcpy(d_beam, beam_host, n_beams * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_order, 0xFF, n * sizeof(uint32_t));
@@ -131,8 +131,6 @@ int blok_hip_debug_class_order(blok_hip_ctx* ctx, const uint32_t* cost_host, uin
         out_depth_sums3[0] = out_depth_sums3[1] = out_depth_sums3[2] = 0.0f;
         for (uint32_t k = 0; k < blok::kOrderDepthPartials; ++k) for (int c = 0; c < 3; ++c) out_depth_sums3[c] += part[k * 3 + c];
     }
-    for (void* p : {static_cast<void*>(d_cost), static_cast<void*>(d_order), static_cast<void*>(d_rank), static_cast<void*>(d_live), static_cast<void*>(d_depth), static_cast<void*>(d_beam), d_scratch})
-        if (p) (void)hipFree(p);
     BLOK_HIP_TRY(ctx, e);
     return BLOK_OK;
 }

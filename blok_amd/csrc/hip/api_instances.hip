@@ -6,27 +6,13 @@
 
 namespace blok_api {
 
-void free_models(blok_hip_ctx* ctx) {
-    for (auto& m : ctx->models.desc) {
-        if (m.nodes) (void)hipFree(const_cast<uint4*>(m.nodes));
-        if (m.materials) (void)hipFree(const_cast<uint32_t*>(m.materials));
-    }
-    if (ctx->models.d_desc) (void)hipFree(ctx->models.d_desc);
-    ctx->models = blok_hip_ctx::Models{};
-}
-
 namespace {
 
 // The device copy of the descriptors after a change (the callers have synchronised the device), and the LDS stack the kernels need.
 int upload_models(blok_hip_ctx* ctx) {
     auto& M = ctx->models;
-    if (M.d_capacity < M.desc.size()) {
-        if (M.d_desc) (void)hipFree(M.d_desc);
-        M.d_desc = nullptr; M.d_capacity = 0;
-        const size_t cap = std::max<size_t>(16, M.desc.size() * 2);
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&M.d_desc), cap * sizeof(blok::ModelDesc)));
-        M.d_capacity = cap;
-    }
+    if (M.d_desc.capacity() < M.desc.size())
+        BLOK_HIP_TRY(ctx, M.d_desc.reserve(std::max<size_t>(16, M.desc.size() * 2), blok::FreeAfter::nothing()));
     if (!M.desc.empty())
         BLOK_HIP_TRY(ctx, hipMemcpy(M.d_desc, M.desc.data(), M.desc.size() * sizeof(blok::ModelDesc), hipMemcpyHostToDevice));
     uint32_t slots = 1;
@@ -81,17 +67,6 @@ blok::BinView bin_view(const blok_hip_ctx* ctx, const blok_camera& c) {
     return V;
 }
 
-// Per-stream scratch grown to n elements (a buffer still in use by earlier launches on the stream is freed after them).
-template <class T>
-int stream_buffer(blok_hip_ctx* ctx, hipStream_t stream, T*& buf, size_t& have, size_t n) {
-    if (have >= n) return BLOK_OK;
-    if (buf) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(buf); }
-    buf = nullptr; have = 0;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&buf), n * sizeof(T)));
-    have = n;
-    return BLOK_OK;
-}
-
 blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs& world, const blok_instance* inst, uint32_t n, blok_hit* hits,
                                  uint32_t* rgba, uint32_t* ids) {
     blok::InstanceArgs P{};
@@ -107,7 +82,7 @@ blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs&
 
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) { return check_table(ctx, inst, n); }
 
-int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, uint32_t* out_model) {
+int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, blok_hip_ctx::Models::Arrays own, uint32_t* out_model) {
     // frames in flight may read the descriptor array that the upload replaces
     hipError_t e = hipDeviceSynchronize();
     int rc = BLOK_OK;
@@ -117,11 +92,9 @@ int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, uint32_t* out_model) 
         rc = upload_models(ctx);
         if (rc != BLOK_OK) ctx->models.desc.pop_back();
     }
-    if (rc != BLOK_OK) {
-        (void)hipFree(const_cast<uint4*>(m.nodes));
-        (void)hipFree(const_cast<uint32_t*>(m.materials));
-        return rc;
-    }
+    if (rc != BLOK_OK) return rc;                       // (`own` frees the arrays)
+    ctx->models.own.resize(ctx->models.desc.size());
+    ctx->models.own.back() = std::move(own);
     *out_model = static_cast<uint32_t>(ctx->models.desc.size() - 1u);
     return BLOK_OK;
 }
@@ -160,20 +133,16 @@ int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t*
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     blok::ModelDesc m{};
     const size_t node_bytes = tree.nodes.size() * sizeof(blok::TreeNode), mat_bytes = tree.materials.size() * sizeof(uint32_t);
-    uint4* nodes = nullptr; uint32_t* mats = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nodes), node_bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&mats), mat_bytes);
-    if (e == hipSuccess) e = hipMemcpy(nodes, tree.nodes.data(), node_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mats, tree.materials.data(), mat_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (nodes) (void)hipFree(nodes);
-        if (mats) (void)hipFree(mats);
-        return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("model upload: ") + hipGetErrorString(e));
-    }
-    m.nodes = nodes; m.materials = mats; m.levels = tree.levels;
+    blok_hip_ctx::Models::Arrays own;
+    hipError_t e = own.nodes.reserve(tree.nodes.size(), blok::FreeAfter::nothing());
+    if (e == hipSuccess) e = own.materials.reserve(tree.materials.size(), blok::FreeAfter::nothing());
+    if (e == hipSuccess) e = hipMemcpy(own.nodes, tree.nodes.data(), node_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(own.materials, tree.materials.data(), mat_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("model upload: ") + hipGetErrorString(e));
+    m.nodes = own.nodes; m.materials = own.materials; m.levels = tree.levels;
     m.n_nodes = static_cast<uint32_t>(tree.nodes.size()); m.n_materials = static_cast<uint32_t>(tree.materials.size());
     for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = lo[a]; m.hi[a] = hi[a] + 1; }
-    return add_model(ctx, m, out_model);
+    return add_model(ctx, m, std::move(own), out_model);
 }
 
 int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
@@ -182,10 +151,8 @@ int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());           // frames in flight may still walk it
-    blok::ModelDesc& m = ctx->models.desc[model];
-    (void)hipFree(const_cast<uint4*>(m.nodes));
-    (void)hipFree(const_cast<uint32_t*>(m.materials));
-    m = blok::ModelDesc{};                               // the id stays taken and unknown
+    ctx->models.own[model] = blok_hip_ctx::Models::Arrays{};
+    ctx->models.desc[model] = blok::ModelDesc{};         // the id stays taken and unknown
     return upload_models(ctx);
 }
 
@@ -207,8 +174,7 @@ int blok_hip_trace_primary_instanced_device(blok_hip_ctx* ctx, const blok_camera
     blok_hit* hits = static_cast<blok_hit*>(out_hits_dev);
     if (n_instances && !hits) {                          // the instance pass needs the world records
         auto& sc = ctx->beam_buffers[stream];
-        rc = stream_buffer(ctx, stream, sc.inst_hits, sc.n_inst_hits, n_pixels);
-        if (rc != BLOK_OK) return rc;
+        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n_pixels, blok::FreeAfter::work_on(stream)));
         hits = sc.inst_hits;
     }
     // the world pass: blok_hip_trace_primary_device's launch, unchanged
@@ -227,8 +193,7 @@ int blok_hip_trace_primary_instanced_device(blok_hip_ctx* ctx, const blok_camera
     P.bins_y = (h + blok::kBinPixels - 1u) / blok::kBinPixels;
     P.view = bin_view(ctx, *cam);
     auto& sc = ctx->beam_buffers[stream];
-    rc = stream_buffer(ctx, stream, sc.inst_bins, sc.n_inst_bins, static_cast<size_t>(P.bins_x) * P.bins_y * blok::kBinWords);
-    if (rc != BLOK_OK) return rc;
+    BLOK_HIP_TRY(ctx, sc.inst_bins.reserve(static_cast<size_t>(P.bins_x) * P.bins_y * blok::kBinWords, blok::FreeAfter::work_on(stream)));
     P.bins = sc.inst_bins;
     blok::launch_instance_bins(P, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
@@ -250,9 +215,9 @@ int blok_hip_trace_primary_instanced(blok_hip_ctx* ctx, const blok_camera* cam, 
     // one device block: instances, records, RGBA8, ids
     const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
     const size_t bytes = inst_bytes + n * (sizeof(blok_hit) + 2u * sizeof(uint32_t));
-    unsigned char* d = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d);
+    blok::DeviceArray<unsigned char> d;
+    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
+    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
     blok_hit* d_hits = reinterpret_cast<blok_hit*>(d + inst_bytes);
     uint32_t* d_rgba = reinterpret_cast<uint32_t*>(d_hits + n);
     uint32_t* d_ids = d_rgba + n;
@@ -265,7 +230,6 @@ int blok_hip_trace_primary_instanced(blok_hip_ctx* ctx, const blok_camera* cam, 
         if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_primary_instanced: ") + hipGetErrorString(e));
     return BLOK_OK;
@@ -287,8 +251,7 @@ int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays
     blok_hit* hits = out_hits_dev;
     if (!hits) {
         auto& sc = ctx->beam_buffers[stream];
-        const int rc = stream_buffer(ctx, stream, sc.inst_hits, sc.n_inst_hits, n);
-        if (rc != BLOK_OK) return rc;
+        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n, blok::FreeAfter::work_on(stream)));
         hits = sc.inst_hits;
     }
     blok::TraceArgs world = base_args(ctx, nullptr);
@@ -316,9 +279,9 @@ int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, 
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
     const size_t bytes = inst_bytes + n * (sizeof(blok_ray) + sizeof(blok_hit) + sizeof(uint32_t));
-    unsigned char* d = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d);
+    blok::DeviceArray<unsigned char> d;
+    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
+    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
     blok_ray* d_rays = reinterpret_cast<blok_ray*>(d + inst_bytes);
     blok_hit* d_hits = reinterpret_cast<blok_hit*>(d_rays + n);
     uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_hits + n);
@@ -330,7 +293,6 @@ int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, 
         if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays_instanced: ") + hipGetErrorString(e));
     return BLOK_OK;
@@ -380,8 +342,8 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
     const size_t n = static_cast<size_t>(w) * h, plane_bytes = n * 4 * sizeof(float);
     // one device block: instances, four planes, ids
     const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
-    unsigned char* d = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), inst_bytes + 4 * plane_bytes + n * sizeof(uint32_t)));
+    blok::DeviceArray<unsigned char> d;
+    BLOK_HIP_TRY(ctx, d.reserve(inst_bytes + 4 * plane_bytes + n * sizeof(uint32_t), blok::FreeAfter::nothing()));
     float* host[4] = {planes_host->color, planes_host->world_pos, planes_host->normal_roughness, planes_host->albedo_metallic};
     float* dev[4];
     for (int i = 0; i < 4; ++i) dev[i] = host[i] ? reinterpret_cast<float*>(d + inst_bytes + i * plane_bytes) : nullptr;
@@ -389,14 +351,13 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
     hipError_t e = n_instances ? hipMemcpy(d, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
     if (e == hipSuccess) {
         const blok_gbuffer planes_dev{dev[0], dev[1], dev[2], dev[3]};
-        rc = blok_hip_trace_paths_instanced_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, reinterpret_cast<const blok_instance*>(d),
+        rc = blok_hip_trace_paths_instanced_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, reinterpret_cast<const blok_instance*>(d.get()),
                                                    n_instances, &planes_dev, out_instance_host ? d_ids : nullptr, nullptr);
         for (int i = 0; i < 4 && rc == BLOK_OK && e == hipSuccess; ++i)
             if (host[i]) e = hipMemcpy(host[i], dev[i], plane_bytes, hipMemcpyDeviceToHost);
         if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d);
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("trace_paths_instanced: ") + hipGetErrorString(e));
     return BLOK_OK;
@@ -435,12 +396,11 @@ int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_
     if (out_count) *out_count = count;
     if (capacity < count) return set_error(ctx, BLOK_ERR_INVALID_ARG, "output too small for " + std::to_string(count) + " nodes");
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    blok::TlasNode* d = nullptr;
-    BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), count * sizeof(blok::TlasNode)));
+    blok::DeviceArray<blok::TlasNode> d;
+    BLOK_HIP_TRY(ctx, d.reserve(count, blok::FreeAfter::nothing()));
     blok::launch_tlas_build(instances_dev, n_instances, ctx->models.d_desc, static_cast<uint32_t>(ctx->models.desc.size()), d, nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out_nodes_host, d, count * sizeof(blok::TlasNode), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("build_tlas: ") + hipGetErrorString(e));
     return BLOK_OK;
 }

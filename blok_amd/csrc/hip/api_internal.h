@@ -17,6 +17,7 @@
 
 #include "blok_hip.h"
 #include "blok_hip_debug.h"
+#include "device_buffer.h"
 #include "gpu_build.h"
 #include <hip/hip_fp16.h>
 #include "post_kernels.h"
@@ -31,19 +32,23 @@
 #include "tree.h"
 #include "instance_core.h"
 
+// Every device array, pinned array and event of the context is a member that owns it (device_buffer.h): the context's destructor is its
+// teardown, a reset is the assignment of a fresh value, and every grow-on-demand site is one reserve() that names what must finish first.
 struct blok_hip_ctx {
     int device = 0;
     uint32_t width = 0, height = 0;
-    // derived structure in HBM
+    // derived structure in HBM: the tree as the kernels' arguments read it, and its owners — empty while the arrays are the resident volume's
     uint4* d_nodes = nullptr;
     uint32_t* d_tree_materials = nullptr;
-    blok_material* d_materials = nullptr;
+    blok::DeviceArray<uint4> own_nodes;
+    blok::DeviceArray<uint32_t> own_tree_materials;
+    blok::DeviceArray<blok_material> d_materials;
     size_t n_materials = 0;
     bool has_world = false;
     bool built_on_device = false;     // structure built by gpu_build.hip (else tree_build.cpp on the host)
     uint32_t world_version = 0;        // counts uploads and rebuilds: scheduling state measured on another world is dropped (TileOrder::key)
     uint32_t tree_version = 0;         // counts every tree installed, a rebuild of the resident volume included (which keeps world_version, and with it the view's order): what was computed FROM the tree is dropped (beam_cache.h)
-    bool tree_owned_by_volume = false; // d_nodes / d_tree_materials belong to the resident volume's scratch (gpu_build.h): never freed here
+    bool tree_owned_by_volume = false; // d_nodes / d_tree_materials belong to the resident volume's scratch (gpu_build.h): own_nodes / own_tree_materials are empty
     bool force_host_build = false;
     blok_world_stats stats{};
     float voxel_size = 1.0f;            // for the next blok_hip_upload_world (blok_hip_set_voxel_size)
@@ -52,16 +57,13 @@ struct blok_hip_ctx {
     // dense-grid path (dense_kernels.hip): the uploaded id grid in 8^3-cell tiles and one occupancy bit per tile; kept when
     // blok_hip_set_dense_dda was on at blok_hip_upload_dense, and then used by the rectangle entries of the primary trace
     bool dense_dda = false, has_dense = false;
-    uint32_t* d_dense_tiled = nullptr;
-    uint32_t* d_dense_bits = nullptr;
+    blok::DeviceArray<uint32_t> d_dense_tiled, d_dense_bits;
     uint32_t dense_tiles[3] = {0, 0, 0};
     int32_t dense_origin[3] = {0, 0, 0};
     // scratch frame for the host-output entry points
-    blok_hit* d_frame = nullptr;
-    size_t frame_capacity = 0;
+    blok::DeviceArray<blok_hit> d_frame;
     // progressive accumulation (CudaTracer::m_dAccum / m_frameIndex / m_prevCam, reference cuda_tracer.hpp:51-55)
-    float* d_accum = nullptr;
-    float* d_color = nullptr;
+    blok::DeviceArray<float> d_accum, d_color;
     size_t accum_pixels = 0;
     uint32_t accum_frames = 0;
     blok_camera prev_cam{};
@@ -70,30 +72,29 @@ struct blok_hip_ctx {
     struct Post {
         size_t pixels = 0;
         uint32_t width = 0, height = 0;      // the frame shape the planes were allocated for
-        float *hist_color[2] = {nullptr, nullptr}, *moments[2] = {nullptr, nullptr}, *world_pos[2] = {nullptr, nullptr};
-        uint16_t* hist_len[2] = {nullptr, nullptr};
-        float* unit_normals[2] = {nullptr, nullptr};   // float4: normalize(binary16 normal)
-        uint16_t* motion = nullptr;          // half2
-        float *variance = nullptr, *ping = nullptr, *pong = nullptr, *taa_hist[2] = {nullptr, nullptr};
-        float* widen = nullptr;              // scratch for state downloads
+        blok::DeviceArray<float> hist_color[2], moments[2], world_pos[2];
+        blok::DeviceArray<uint16_t> hist_len[2];
+        blok::DeviceArray<float> unit_normals[2];       // float4: normalize(binary16 normal)
+        blok::DeviceArray<uint16_t> motion;             // half2
+        blok::DeviceArray<float> variance, ping, pong, taa_hist[2];
+        blok::DeviceArray<float> widen;                 // scratch for state downloads
         int cur = 0, taa_cur = 0;
         bool has_motion = false;
         // blok_hip_draw_frame_rt: the frame's own planes and its camera history
-        float *rt_planes[4] = {nullptr, nullptr, nullptr, nullptr}, *rt_denoised = nullptr, *rt_resolved = nullptr;   // [0] colour, [1] world position
-        uint16_t *rt_normal_roughness_h = nullptr, *rt_motion_h = nullptr;      // RGBA16F, RG16F
-        uint32_t* rt_albedo_metallic_u8 = nullptr;                              // RGBA8
-        uint32_t *rt_ldr = nullptr, *rt_final = nullptr;
+        blok::DeviceArray<float> rt_planes[2], rt_denoised, rt_resolved;        // [0] colour, [1] world position
+        blok::DeviceArray<uint16_t> rt_normal_roughness_h, rt_motion_h;          // RGBA16F, RG16F
+        blok::DeviceArray<uint32_t> rt_albedo_metallic_u8;                       // RGBA8
+        blok::DeviceArray<uint32_t> rt_ldr, rt_final;
         uint32_t rt_frame = 0;
         blok_camera rt_prev_cam{};
         // blok_hip_draw_frame_rt_instanced_motion: the first-hit instance plane, and the number of records of the previous frame's table
         // (rt_prev_instances; 0 after a reset or a frame without object motion)
-        uint32_t* rt_ids = nullptr;
+        blok::DeviceArray<uint32_t> rt_ids;
         uint32_t rt_prev_n = 0;
     } post;
     // blok_hip_draw_frame_rt_instanced(_motion): the frame's instance table in device memory (records), grown on demand, and the previous
     // frame's (the motion entry swaps the two after each frame); outside `post`, which ensure_post may reallocate after the upload
-    blok_instance* rt_instances = nullptr; size_t n_rt_instances = 0;
-    blok_instance* rt_prev_instances = nullptr; size_t n_rt_prev_instances = 0;
+    blok::DeviceArray<blok_instance> rt_instances, rt_prev_instances;
     // device-resident dense store (gpu_build.h: GpuVolume)
     blok::GpuVolume volume;
     bool has_volume = false;
@@ -109,11 +110,11 @@ struct blok_hip_ctx {
     blok::GpuScatter scatter;            // of the last blok_hip_volume_scatter_models: it goes with the column snapshot it was made from
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
-    float* d_sun_map = nullptr;
+    blok::DeviceArray<float> d_sun_map;
     bool sun_map_enabled = true, has_sun_map = false;
     uint32_t sun_loose_edits = 0; int32_t sun_loose_lo[3] = {0, 0, 0}, sun_loose_hi[3] = {0, 0, 0};      // edits since the map was last made tight, and the union of their boxes (update_sun_map)
     bool sun_tighten_pending = false; uint32_t sun_tighten_u0 = 0, sun_tighten_u1 = 0, sun_tighten_v0 = 0, sun_tighten_v1 = 0;      // texels still to be made tight, a band of rows per edit (update_sun_map)
-    hipEvent_t sun_event = nullptr; bool sun_event_pending = false;                                      // behind the latest patch of the map
+    blok::Event sun_event; bool sun_event_pending = false;                                            // behind the latest patch of the map
     uint32_t ray_batching = 3;          // PathArgs::batch_kinds (blok_hip_set_ray_batching); 3 = 2 + the bounce rounds' tail pool
     uint32_t tail_cap = 24, tail_cap_parked = 32;                 // trips after which a bounce round / a round over parked rays stops (BLOK_TAIL_CAPS overrides, experiments)
     bool path_resume = false, path_fine_beam = true;      // PathArgs::resume_secondary / fine_beam (blok_hip_set_path_start)
@@ -124,20 +125,20 @@ struct blok_hip_ctx {
     uint32_t beam_budget = 0;           // 0 = beam.h's default visit budget
     bool miss_in_walk = true;           // who writes the pixels of tiles the pre-pass found empty (blok_hip_set_miss_writer)
     struct StreamScratch {             // per launch stream
-        float* beam = nullptr; size_t n_beam = 0;                       // two-launch form: start parameters per beam tile
-        uint32_t* ctl = nullptr; unsigned long long* entries = nullptr; size_t capacity = 0;   // one-launch form: work queue (trace_kernels.h: FrameQueue)
-        unsigned long long* slots = nullptr; size_t n_slots = 0; uint32_t serial = 0;   // joint launch: published beam results
-        uint32_t* gave_up = nullptr;                                      // joint and list launches: waves that gave up a bounded wait (sticky; blok_hip_frame_queue_stalls)
+        blok::DeviceArray<float> beam;                                   // two-launch form: start parameters per beam tile
+        blok::DeviceArray<uint32_t> ctl; blok::DeviceArray<unsigned long long> entries;      // one-launch form: work queue (trace_kernels.h: FrameQueue)
+        blok::DeviceArray<unsigned long long> slots; uint32_t serial = 0;   // joint launch: published beam results
+        blok::DeviceArray<uint32_t> gave_up;                              // joint and list launches: waves that gave up a bounded wait (sticky; blok_hip_frame_queue_stalls)
         // list launches (trace_kernels.h: LiveList): entries, control words, serial, and the pinned words the searches leave the segments' lengths in
-        unsigned long long* list_entries = nullptr; size_t list_capacity = 0;   // entries per segment
-        unsigned long long* list_ctl = nullptr;
+        blok::DeviceArray<unsigned long long> list_entries; size_t list_capacity = 0;   // entries per segment: the stride of the launches
+        blok::DeviceArray<unsigned long long> list_ctl;
         uint32_t list_serial = 0;
-        uint32_t* list_hint = nullptr; bool list_hint_valid = false; uint32_t list_hint_key = 0;
-        uint32_t* tile_map = nullptr; size_t n_tile_map = 0;            // sparse exchange, root: frame tile -> record (zero between launches)
-        void* tail_pool = nullptr; size_t tail_pool_bytes = 0;           // path launches: the bounce rounds' tail pool (path_core.h: TailRecord[blocks][kTailCapacity]), grown on demand
-        uint32_t* inst_bins = nullptr; size_t n_inst_bins = 0;          // instanced frames: the binning kernel's lists (instance_core.h: kBinWords words per bin), grown on demand
-        blok_hit* inst_hits = nullptr; size_t n_inst_hits = 0;          // instanced frames without a record output: the world records the instance pass reads
-        void* tlas = nullptr; size_t n_tlas = 0;                          // instanced path launches: the instance BVH (tlas_core.h: TlasNode), nodes, grown on demand
+        blok::PinnedArray<uint32_t> list_hint; bool list_hint_valid = false; uint32_t list_hint_key = 0;
+        blok::DeviceArray<uint32_t> tile_map;                            // sparse exchange, root: frame tile -> record (zero between launches)
+        blok::DeviceBytes tail_pool;                                      // path launches: the bounce rounds' tail pool (path_core.h: TailRecord[blocks][kTailCapacity]), grown on demand
+        blok::DeviceArray<uint32_t> inst_bins;                           // instanced frames: the binning kernel's lists (instance_core.h: kBinWords words per bin), grown on demand
+        blok::DeviceArray<blok_hit> inst_hits;                           // instanced frames without a record output: the world records the instance pass reads
+        blok::DeviceBytes tlas;                                           // instanced path launches: the instance BVH (tlas_core.h: TlasNode), grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
     // The beam bounds of views at rest (beam_cache.h: key, admission, slots; api_launch.hip: the hazards).  A slot's buffer is written by the
@@ -148,8 +149,8 @@ struct blok_hip_ctx {
         bool enabled = true;                                // blok_hip_set_beam_cache
         blok::BeamCachePolicy policy{};
         struct Slot {
-            float* d_beam = nullptr;
-            hipEvent_t ready = nullptr;                     // behind the launch that filled the slot
+            blok::DeviceArray<float> d_beam;
+            blok::Event ready;                              // behind the launch that filled the slot
             hipStream_t producer = nullptr;                 // ... and its stream
             bool settled = true;                            // `ready` has been seen complete: nobody waits any more
             bool used = false;                              // filled at least once: launches that read it may be in flight
@@ -168,17 +169,17 @@ struct blok_hip_ctx {
         bool enabled = true;
         bool rank_tiles = true;                            // ... also for a rank's tile launches (blok_hip_set_rank_tile_ordering)
         uint32_t interval = 8, interval_now = 8;          // interval_now: of a view that has no order of its own yet (a slot carries its own)
-        uint32_t *d_cost = nullptr, *d_iota = nullptr;
-        uint32_t *d_keys_in = nullptr, *d_keys = nullptr;   // the sort's snapshot of the costs, and its sorted keys
-        void* d_temp = nullptr;
-        size_t temp_bytes = 0, capacity = 0;
+        blok::DeviceArray<uint32_t> d_cost, d_iota;
+        blok::DeviceArray<uint32_t> d_keys_in, d_keys;      // the sort's snapshot of the costs, and its sorted keys
+        blok::DeviceBytes d_temp;
+        size_t temp_bytes = 0, capacity = 0;                // capacity: wave tiles that EVERY buffer of the order has room for (0 until all are there)
         // Round 4: a small CACHE of orders per launch geometry, one slot per view (round 3 kept two buffers — the order in use and the one
         // being sorted — so a caller alternating between two fixed views, stereo eyes or a camera cycle, walked in row-major order for ever).
         // A slot holds an order sorted from the clocks of the view `cam` (own-view: used by launches from that view only) or from dilated
         // clocks (made to be carried to the next view by a shift: only the latest such order is of any use).
         static constexpr int kSlots = 4;
         struct Slot {
-            uint32_t *d_order = nullptr, *d_rank_of = nullptr;
+            blok::DeviceArray<uint32_t> d_order, d_rank_of;
             bool valid = false, dilated = false;
             uint32_t live = 0, radius = 0;                 // leading entries that walked (as read at adoption); dilation it was sorted with
             blok_camera cam{};                             // the view its clocks were measured under
@@ -186,8 +187,8 @@ struct blok_hip_ctx {
             uint32_t frames_since_sort = 0, interval_now = 8;      // launches that walked in it; re-sort interval of its view (doubles while the view rests)
             uint64_t last_use = 0;                         // serial of the latest launch that walked in it
         } slots[kSlots];
-        uint32_t* h_live = nullptr;                         // pinned, kSlots words: how many leading entries of the slot's order walked (written by the device)
-        float* h_depth = nullptr;                           // pinned, kSlots x 64 x 3 floats: partial count, sum, sum of squares of the live beam tiles' inverse start parameters
+        blok::PinnedArray<uint32_t> h_live;                 // pinned, kSlots words: how many leading entries of the slot's order walked (written by the device)
+        blok::PinnedArray<float> h_depth;                   // pinned, kSlots x 64 x 3 floats: partial count, sum, sum of squares of the live beam tiles' inverse start parameters
         uint32_t key[7] = {};                               // launch rectangle, frame size, world version
         int current = -1, target = 0;                       // the slot adopted last (-1: none yet); the slot a pending sort writes
         bool pending = false;
@@ -197,21 +198,21 @@ struct blok_hip_ctx {
         blok_camera last_cam{};                             // camera of the last launch
         blok_camera recent[4] = {}; uint32_t n_recent = 0, revisit_streak = 0;  // cameras of the latest launches; consecutive launches from a view seen among them (alternating views are views at rest)
         blok_camera pending_cam{}; bool pending_dilated = false; uint32_t pending_radius = 0, pending_interval = 8;      // of the sort in flight
-        hipEvent_t done = nullptr;
+        blok::Event done;
         // a camera in motion (launch_policy.h): orders sorted from dilated clocks, carried to the next view by a whole-tile shift
         bool moving = true;                                 // blok_hip_set_moving_order
-        void* d_class_scratch = nullptr;                    // tile_order.h: count table and class bytes of the counting sort
+        blok::DeviceBytes d_class_scratch;                  // tile_order.h: count table and class bytes of the counting sort
         bool have_residual = false; float last_residual = 0.0f;     // what the latest shift left over (sizes the next dilation)
         bool debug_shift = false; uint32_t debug_sx = 0, debug_sy = 0;      // blok_hip_debug_force_order_shift: every ordered launch uses this shift (tests)
-        uint32_t* d_fallback = nullptr;                     // wave tiles the search waves of the latest prefix launch walked themselves (cleared in stream order before it)
-        uint32_t* h_fallback = nullptr;                     // pinned: ... copied here behind the launch
+        blok::DeviceArray<uint32_t> d_fallback;             // wave tiles the search waves of the latest prefix launch walked themselves (cleared in stream order before it)
+        blok::PinnedArray<uint32_t> h_fallback;             // pinned: ... copied here behind the launch
         uint32_t last_fallback = 0;                         // ... as read before the next launch (blok_hip_last_fallback_tiles)
         bool alone_before = false;                          // the previous orderable launch had the device to itself
         int last_use = 0; uint32_t last_sx = 0, last_sy = 0;        // the latest launch: 0 natural order, 1 an order of its own view, 2 a carried one (blok_hip_last_order_use)
         int chosen = -1;                                    // the slot the latest launch walked in (-1: none)
     } order;
     // list launches, rectangle frames: clocks per wave tile of the last frame of this launch geometry, and the camera they were measured under (trace_kernels.h: cost classes)
-    uint32_t* d_list_cost = nullptr; size_t list_cost_capacity = 0; uint32_t list_cost_key[6] = {};
+    blok::DeviceArray<uint32_t> d_list_cost; uint32_t list_cost_key[6] = {};
     blok_camera list_prev_cam{}; bool list_has_prev_cam = false;
     bool list_classes = true;           // blok_hip_set_list_classes
     uint32_t* debug_clocks = nullptr;   // blok_hip_set_debug_wave_clocks (caller's device memory)
@@ -224,14 +225,16 @@ struct blok_hip_ctx {
     float jitter_px[2] = {0.0f, 0.0f};
     bool rt_taa_jitter = true;          // PostProcess::Settings::enableTAA (renderer_postprocess.hpp:103)
     // instanced voxel models (api_instances.hip): descriptors indexed by model id (a destroyed model keeps its slot with nodes == null),
-    // their device copy, and the LDS stack slots the deepest live model needs
+    // the owners of their arrays under the same index, their device copy, and the LDS stack slots the deepest live model needs
     struct Models {
+        struct Arrays { blok::DeviceArray<uint4> nodes; blok::DeviceArray<uint32_t> materials; };
         std::vector<blok::ModelDesc> desc;
-        blok::ModelDesc* d_desc = nullptr; size_t d_capacity = 0;
+        std::vector<Arrays> own;
+        blok::DeviceArray<blok::ModelDesc> d_desc;
         uint32_t stack_levels = 1;
     } models;
     // timing
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    blok::Event ev_begin, ev_end;
     bool timing = false, timed = false;
     std::string error;
 };
@@ -248,8 +251,20 @@ int set_error(blok_hip_ctx* ctx, int status, const std::string& msg);
                              std::string(#call) + ": " + hipGetErrorString(e_));                   \
     } while (0)
 
-void free_post(blok_hip_ctx* ctx);
+// A call that fills `owner` right after a reserve() replaced it (a zero fill, a first upload): if it fails, the owner is emptied first, so
+// that the next call starts over and no kernel ever reads words nobody wrote.
+#define BLOK_HIP_TRY_FILL(ctx, owner, call)                                                        \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            (owner).reset();                                                                       \
+            return set_error(ctx, e_ == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP,         \
+                             std::string(#call) + ": " + hipGetErrorString(e_));                   \
+        }                                                                                          \
+    } while (0)
+
 void free_world(blok_hip_ctx* ctx);
+void adopt_tree(blok_hip_ctx* ctx, const blok::GpuTree& gpu);
 int install_materials(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials);
 int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_material* materials, size_t n_materials);
 int rebuild_sun_map(blok_hip_ctx* ctx);
@@ -265,10 +280,8 @@ int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, ui
                       uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst = nullptr);
 // api_launch.hip
 int beam_buffer(blok_hip_ctx* ctx, hipStream_t stream, size_t n, float** out);
-void free_order(blok_hip_ctx* ctx);
 int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream);
 int beam_cache_buffers(blok_hip_ctx* ctx);              // at create / resize: the slots' buffers for the frame size (a blocking entry)
-void free_beam_cache(blok_hip_ctx* ctx);
 void settle_beam_cache(blok_hip_ctx* ctx);               // behind a device-wide synchronisation: every slot's producer has finished
 int live_list(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_searches, uint32_t per_search);
 int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, uint32_t blocks, hipStream_t stream, uint32_t tiles_of_rank = 0,
@@ -276,13 +289,12 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
 // api_volume.hip: the one place the context's snapshots are freed (a new volume, a destroyed one, the context's end)
 void free_volume_snapshots(blok_hip_ctx* ctx);
 // api_instances.hip
-void free_models(blok_hip_ctx* ctx);
 // The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n);
 // The tail of every entry that makes a model (blok_hip_model_create, blok_hip_volume_capture_model): takes the two device arrays into the
 // store under the next id, refreshes the device copy of the descriptors and the stack depth the kernels need.  Synchronises the device.
-// On failure the arrays are freed and no id is consumed.
-int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, uint32_t* out_model);
+// On failure the arrays are freed (they are `own`'s from the call on) and no id is consumed.
+int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, blok_hip_ctx::Models::Arrays own, uint32_t* out_model);
 // The id plane and both tables of an object-motion pass (instance_motion.h) with the context's model store and voxel size.
 blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
                                  uint32_t n_prev);

@@ -17,14 +17,14 @@ namespace {
 // the one being launched on: a caller may have destroyed it, or be capturing it into a graph): `last` = behind its latest frame launch;
 // `held` = what `last` was when the context last asked for its launches to be remembered (hold_markers: the adoption of an order, a change
 // of launch geometry) — a marker that stays put while the stream goes on launching, which is what a later sort waits for.
-struct StreamMarks { hipEvent_t last = nullptr, held = nullptr; bool fresh = false; };
+struct StreamMarks { blok::Event last, held; bool fresh = false; };
 struct DeviceActivity {
     std::mutex lock;
     std::map<std::pair<const blok_hip_ctx*, hipStream_t>, StreamMarks> marks;
 };
 DeviceActivity& device_activity(int device) {
     static std::mutex table_lock;
-    static std::map<int, DeviceActivity> table;
+    static auto& table = *new std::map<int, DeviceActivity>;      // never destroyed: the markers of a context nobody destroyed must not be handed back to a runtime that is shutting down
     std::lock_guard<std::mutex> g(table_lock);
     return table[device];
 }
@@ -36,7 +36,7 @@ static bool device_busy_elsewhere(const blok_hip_ctx* ctx, hipStream_t stream) {
     bool busy = false;
     for (auto& kv : act.marks) {
         if (kv.first.first == ctx && kv.first.second == stream) continue;
-        for (hipEvent_t ev : {kv.second.last, kv.second.held})
+        for (hipEvent_t ev : {kv.second.last.get(), kv.second.held.get()})
             if (ev && hipEventQuery(ev) == hipErrorNotReady) { busy = true; break; }
         if (busy) break;
     }
@@ -48,7 +48,7 @@ static int note_frame_launch(blok_hip_ctx* ctx, hipStream_t stream) {
     DeviceActivity& act = device_activity(ctx->device);
     std::lock_guard<std::mutex> g(act.lock);
     StreamMarks& m = act.marks[{ctx, stream}];
-    if (!m.last) BLOK_HIP_TRY(ctx, hipEventCreateWithFlags(&m.last, hipEventDisableTiming));
+    BLOK_HIP_TRY(ctx, m.last.create());
     BLOK_HIP_TRY(ctx, hipEventRecord(m.last, stream));
     m.fresh = true;
     return BLOK_OK;
@@ -76,11 +76,8 @@ void forget_device_activity(const blok_hip_ctx* ctx, bool one_stream, hipStream_
     DeviceActivity& act = device_activity(ctx->device);
     std::lock_guard<std::mutex> g(act.lock);
     for (auto it = act.marks.begin(); it != act.marks.end();)
-        if (it->first.first == ctx && (!one_stream || it->first.second == stream)) {
-            if (it->second.last) (void)hipEventDestroy(it->second.last);
-            if (it->second.held) (void)hipEventDestroy(it->second.held);
-            it = act.marks.erase(it);
-        } else ++it;
+        if (it->first.first == ctx && (!one_stream || it->first.second == stream)) it = act.marks.erase(it);      // (and its events with it)
+        else ++it;
 }
 
 // ---- longest-first order of the walk's wave tiles (api_internal.h: TileOrder; decisions in launch_policy.h: plan_order, plan_shift) ------
@@ -103,19 +100,6 @@ static bool camera_near(const blok_hip_ctx* ctx, const blok_camera& a, const blo
     return turn <= 1.0e-5f && d2 <= std::max(still * still, 1.0e-12f * r2) && std::fabs(a.tan_half_fov - b.tan_half_fov) < 1e-6f && std::fabs(a.aspect - b.aspect) < 1e-6f;
 }
 
-void free_order(blok_hip_ctx* ctx) {
-    auto& O = ctx->order;
-    for (void* p : {static_cast<void*>(O.d_cost), static_cast<void*>(O.d_iota), static_cast<void*>(O.d_keys_in), static_cast<void*>(O.d_keys), O.d_class_scratch, O.d_temp})
-        if (p) (void)hipFree(p);
-    for (auto& sl : O.slots) {
-        if (sl.d_order) (void)hipFree(sl.d_order);
-        if (sl.d_rank_of) (void)hipFree(sl.d_rank_of);
-        sl = blok_hip_ctx::TileOrder::Slot{};
-    }
-    O.d_cost = O.d_iota = O.d_keys_in = O.d_keys = nullptr; O.d_class_scratch = nullptr;
-    O.d_temp = nullptr; O.capacity = 0;
-}
-
 // The order's buffers, for at least `blocks` wave tiles and never fewer than the full frame has: allocated by blok_hip_create / _resize, so
 // that no *_device launch ever allocates or waits for the device on their account (the regrow below is what is left for a caller that
 // resizes between launches: a device-wide wait, because frames in flight and a pending sort may use the old buffers).
@@ -124,23 +108,26 @@ int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream) {
     constexpr int kSlots = blok_hip_ctx::TileOrder::kSlots;
     const uint32_t want = std::max<uint32_t>(blocks, blok::rect_grid_blocks(ctx->width, ctx->height));
     if (O.capacity >= want) return BLOK_OK;
-    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
-    free_order(ctx);
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());          // the one wait for all of them: the reserves below name none
+    O.capacity = 0;
+    const blok::FreeAfter waited = blok::FreeAfter::nothing();
     const size_t bytes = static_cast<size_t>(want) * sizeof(uint32_t);
-    for (uint32_t** p : {&O.d_cost, &O.d_iota, &O.d_keys_in, &O.d_keys})
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(p), bytes));
+    for (auto* a : {&O.d_cost, &O.d_iota, &O.d_keys_in, &O.d_keys}) BLOK_HIP_TRY(ctx, a->reserve(want, waited));
     for (auto& sl : O.slots) {
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&sl.d_order), bytes));
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&sl.d_rank_of), bytes));
+        sl = blok_hip_ctx::TileOrder::Slot{};
+        BLOK_HIP_TRY(ctx, sl.d_order.reserve(want, waited));
+        BLOK_HIP_TRY(ctx, sl.d_rank_of.reserve(want, waited));
     }
-    if (!O.h_live) BLOK_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&O.h_live), kSlots * sizeof(uint32_t), hipHostMallocDefault));
-    if (!O.h_depth) BLOK_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&O.h_depth), kSlots * blok::kOrderDepthPartials * 3 * sizeof(float), hipHostMallocDefault));
-    if (!O.h_fallback) { BLOK_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&O.h_fallback), sizeof(uint32_t), hipHostMallocDefault)); *O.h_fallback = 0u; }
-    if (!O.d_fallback) BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&O.d_fallback), sizeof(uint32_t)));
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, O.h_live.reserve(kSlots, waited));
+    BLOK_HIP_TRY(ctx, O.h_depth.reserve(kSlots * blok::kOrderDepthPartials * 3, waited));
+    BLOK_HIP_TRY(ctx, O.h_fallback.reserve(1, waited, &fresh));
+    if (fresh) *O.h_fallback = 0u;
+    BLOK_HIP_TRY(ctx, O.d_fallback.reserve(1, waited));
     O.temp_bytes = blok::tile_order_temp_bytes(want);
-    BLOK_HIP_TRY(ctx, hipMalloc(&O.d_temp, O.temp_bytes ? O.temp_bytes : 16));
-    BLOK_HIP_TRY(ctx, hipMalloc(&O.d_class_scratch, blok::tile_order_class_sort_bytes_max(want)));
-    if (!O.done) BLOK_HIP_TRY(ctx, hipEventCreateWithFlags(&O.done, hipEventDisableTiming));
+    BLOK_HIP_TRY(ctx, O.d_temp.reserve(O.temp_bytes ? O.temp_bytes : 16, waited));
+    BLOK_HIP_TRY(ctx, O.d_class_scratch.reserve(blok::tile_order_class_sort_bytes_max(want), waited));
+    BLOK_HIP_TRY(ctx, O.done.create());
     BLOK_HIP_TRY(ctx, blok::launch_iota(O.d_iota, want, stream));              // the identity, whatever the geometry: written once
     BLOK_HIP_TRY(ctx, hipMemsetAsync(O.d_cost, 0, bytes, stream));
     O.capacity = want;
@@ -304,10 +291,9 @@ static int order_after_launch(blok_hip_ctx* ctx, const blok::TraceArgs& args, ui
 // The stream's give-up counter (joint and list forms).
 static int gave_up_counter(blok_hip_ctx* ctx, hipStream_t stream, uint32_t** out) {
     auto& slot = ctx->beam_buffers[stream];
-    if (!slot.gave_up) {
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.gave_up), sizeof(uint32_t)));
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.gave_up, 0, sizeof(uint32_t), stream));
-    }
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, slot.gave_up.reserve(1, blok::FreeAfter::nothing(), &fresh));
+    if (fresh) BLOK_HIP_TRY_FILL(ctx, slot.gave_up, hipMemsetAsync(slot.gave_up, 0, sizeof(uint32_t), stream));
     *out = slot.gave_up;
     return BLOK_OK;
 }
@@ -315,12 +301,11 @@ static int gave_up_counter(blok_hip_ctx* ctx, hipStream_t stream, uint32_t** out
 // The stream's published-result words of a joint launch: valid when they carry this launch's serial.
 static int joint_slots(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_beams) {
     auto& slot = ctx->beam_buffers[stream];
-    if (slot.n_slots < n_beams) {
-        if (slot.slots) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(slot.slots); }
-        slot.slots = nullptr; slot.n_slots = 0;
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.slots), n_beams * sizeof(unsigned long long)));
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.slots, 0, n_beams * sizeof(unsigned long long), stream));
-        slot.n_slots = n_beams; slot.serial = 0;
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, slot.slots.reserve(n_beams, blok::FreeAfter::work_on(stream), &fresh));
+    if (fresh) {
+        BLOK_HIP_TRY_FILL(ctx, slot.slots, hipMemsetAsync(slot.slots, 0, n_beams * sizeof(unsigned long long), stream));
+        slot.serial = 0;
     }
     if (++slot.serial == 0u) slot.serial = 1u;
     args.beam_slots = slot.slots; args.beam_serial = slot.serial;
@@ -331,23 +316,26 @@ static int joint_slots(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t str
 int live_list(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_searches, uint32_t per_search) {
     auto& slot = ctx->beam_buffers[stream];
     const size_t seg_capacity = static_cast<size_t>((n_searches + blok::kListSegments - 1u) / blok::kListSegments) * per_search;
-    if (!slot.list_ctl) {
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.list_ctl), blok::kListSegments * blok::kListCtlWords * sizeof(unsigned long long)));
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.list_ctl, 0, blok::kListSegments * blok::kListCtlWords * sizeof(unsigned long long), stream));
-        BLOK_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&slot.list_hint), blok::kListSegments * blok::kListClasses * sizeof(uint32_t), hipHostMallocDefault));
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, slot.list_ctl.reserve(blok::kListSegments * blok::kListCtlWords, blok::FreeAfter::nothing(), &fresh));
+    if (fresh) {      // the control words and the hint come and go together: a failure on the way leaves neither
+        BLOK_HIP_TRY_FILL(ctx, slot.list_ctl, hipMemsetAsync(slot.list_ctl, 0, blok::kListSegments * blok::kListCtlWords * sizeof(unsigned long long), stream));
+        BLOK_HIP_TRY_FILL(ctx, slot.list_ctl, slot.list_hint.reserve(blok::kListSegments * blok::kListClasses, blok::FreeAfter::nothing()));
         std::memset(slot.list_hint, 0, blok::kListSegments * blok::kListClasses * sizeof(uint32_t));      // read as a hint before the first launch has written it
         slot.list_hint_valid = false;
     }
     const bool wrapped = slot.list_serial + 1u >= (1u << blok::kListSerialBits);
     if (slot.list_capacity < seg_capacity || wrapped) {
+        bool grown = false;
         if (slot.list_capacity < seg_capacity) {
-            if (slot.list_entries) { BLOK_HIP_TRY(ctx, hipStreamSynchronize(stream)); (void)hipFree(slot.list_entries); }
-            slot.list_entries = nullptr; slot.list_capacity = 0;
-            BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&slot.list_entries), seg_capacity * blok::kListSegments * blok::kListClasses * sizeof(unsigned long long)));
+            slot.list_capacity = 0;
+            BLOK_HIP_TRY(ctx, slot.list_entries.reserve(seg_capacity * blok::kListSegments * blok::kListClasses, blok::FreeAfter::work_on(stream), &grown));
             slot.list_capacity = seg_capacity;
         }
         // every entry empty; also when the 20-bit serial starts over, so that no entry of a million launches ago can pass for a new one
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(slot.list_entries, 0, slot.list_capacity * blok::kListSegments * blok::kListClasses * sizeof(unsigned long long), stream));
+        const hipError_t emptied = hipMemsetAsync(slot.list_entries, 0, slot.list_capacity * blok::kListSegments * blok::kListClasses * sizeof(unsigned long long), stream);
+        if (emptied != hipSuccess && grown) { slot.list_entries.reset(); slot.list_capacity = 0; }      // (a new array nobody has used yet: the next launch starts over)
+        BLOK_HIP_TRY(ctx, emptied);
         if (wrapped) slot.list_serial = 0;
     }
     slot.list_serial += 1u;
@@ -371,14 +359,10 @@ static bool list_hint(const blok_hip_ctx* ctx, hipStream_t stream, uint32_t geom
 // The context's cost buffer for a rectangle launch (trace_kernels.h: cost classes): one word per wave tile of the launch geometry.
 static int list_costs(blok_hip_ctx* ctx, blok::TraceArgs& args, uint32_t wave_tiles, hipStream_t stream) {
     const uint32_t key[6] = {args.x0, args.y0, args.w, args.h, ctx->width, ctx->height};
-    if (ctx->list_cost_capacity < wave_tiles || std::memcmp(key, ctx->list_cost_key, sizeof(key)) != 0) {
-        if (ctx->list_cost_capacity < wave_tiles) {
-            if (ctx->d_list_cost) { BLOK_HIP_TRY(ctx, hipDeviceSynchronize()); (void)hipFree(ctx->d_list_cost); }      // frames in flight on other streams still write it
-            ctx->d_list_cost = nullptr; ctx->list_cost_capacity = 0;
-            BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_list_cost), static_cast<size_t>(wave_tiles) * sizeof(uint32_t)));
-            ctx->list_cost_capacity = wave_tiles;
-        }
-        BLOK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_list_cost, 0, ctx->list_cost_capacity * sizeof(uint32_t), stream));      // another geometry: nothing is known
+    bool fresh = false;
+    BLOK_HIP_TRY(ctx, ctx->d_list_cost.reserve(wave_tiles, blok::FreeAfter::device(), &fresh));      // frames in flight on other streams still write it
+    if (fresh || std::memcmp(key, ctx->list_cost_key, sizeof(key)) != 0) {      // (a larger launch is another geometry: its key differs too)
+        BLOK_HIP_TRY(ctx, hipMemsetAsync(ctx->d_list_cost, 0, ctx->d_list_cost.capacity() * sizeof(uint32_t), stream));      // another geometry: nothing is known
         std::memcpy(ctx->list_cost_key, key, sizeof(key));
         ctx->list_has_prev_cam = false;
     }
@@ -390,17 +374,6 @@ static int list_costs(blok_hip_ctx* ctx, blok::TraceArgs& args, uint32_t wave_ti
 }
 
 // ---- the beam bounds of views at rest (beam_cache.h: the key, admission, the slots; api_internal.h: BeamCache) ---------------------------
-void free_beam_cache(blok_hip_ctx* ctx) {
-    auto& B = ctx->beam_cache;
-    for (auto& sl : B.slots) {
-        if (sl.d_beam) (void)hipFree(sl.d_beam);
-        if (sl.ready) (void)hipEventDestroy(sl.ready);
-        sl = blok_hip_ctx::BeamCache::Slot{};
-    }
-    B.capacity = 0;
-    blok::beam_cache_clear(B.policy);
-}
-
 // One float per beam tile of the whole frame at the finest beam tile there is (blok_hip_set_beam: 8 pixels), per slot: no rectangle, no
 // beam setting needs more, so no launch ever allocates on the cache's account.  Grown only (a device-wide wait: frames in flight may read
 // the old buffers); what the slots held is dropped with them.
@@ -409,12 +382,12 @@ int beam_cache_buffers(blok_hip_ctx* ctx) {
     const size_t want = static_cast<size_t>((ctx->width + 7u) / 8u) * ((ctx->height + 7u) / 8u);
     if (B.capacity >= want) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
-    const bool enabled = B.enabled;
-    free_beam_cache(ctx);
-    B.enabled = enabled;
+    B.capacity = 0;
+    blok::beam_cache_clear(B.policy);
     for (auto& sl : B.slots) {
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&sl.d_beam), want * sizeof(float)));
-        BLOK_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+        sl = blok_hip_ctx::BeamCache::Slot{};
+        BLOK_HIP_TRY(ctx, sl.d_beam.reserve(want, blok::FreeAfter::nothing()));      // (the wait above was for all of them)
+        BLOK_HIP_TRY(ctx, sl.ready.create());
     }
     B.capacity = want;
     return BLOK_OK;
@@ -547,7 +520,7 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
         // (a diagnostic, counted only for timed launches — blok_hip_set_timing: a clear in front of the frame and a copy behind it are two more
         // operations on the stream of every frame)
         if (ctx->timing) {
-            ctx->order.last_fallback = *static_cast<volatile uint32_t*>(ctx->order.h_fallback);
+            ctx->order.last_fallback = *static_cast<volatile uint32_t*>(ctx->order.h_fallback.get());
             BLOK_HIP_TRY(ctx, hipMemsetAsync(ctx->order.d_fallback, 0, sizeof(uint32_t), stream));
             args.fallback_tiles = ctx->order.d_fallback;
         }

@@ -59,19 +59,20 @@ struct blok_hip_multi {
         blok_hip_ctx* ctx = nullptr;
         hipStream_t stream = nullptr;
         uint32_t* d_rgba = nullptr;          // dense exchange: this rank's RGBA8 tiles, frames x per_rank tiles (rank 0: its slot of the gathered buffer)
-        blok_hit* d_hits = nullptr;          // this rank's first-hit records, frames x per_rank tiles, tile order (stay on the device)
-        uint32_t* d_codes = nullptr;         // sparse-pull exchange: counts + code records of the batch (blok_hip_compact_hit_tile_frames_device)
+        blok::DeviceArray<uint32_t> own_rgba;    // ... and their owner (empty for rank 0)
+        blok::DeviceArray<blok_hit> d_hits;      // this rank's first-hit records, frames x per_rank tiles, tile order (stay on the device)
+        blok::DeviceArray<uint32_t> d_codes;     // sparse-pull exchange: counts + code records of the batch (blok_hip_compact_hit_tile_frames_device)
         void* comm = nullptr;
-        hipEvent_t traced = nullptr;
+        blok::Event traced;
     };
     std::vector<Rank> ranks;
     uint32_t width = 0, height = 0, tile = 32, per_rank = 0;
     uint32_t frames_capacity = 0;            // frames per call the buffers are sized for
-    uint32_t* d_gathered = nullptr;          // root, dense: n_ranks x frames x per_rank x tile^2
-    uint32_t* d_frame = nullptr;             // root: frames x width x height
-    uint8_t* d_tile_state = nullptr;         // root, sparse-pull: which tiles of d_frame hold something other than sky
-    const uint32_t** d_rank_ptrs = nullptr;  // root, sparse-pull: every rank's d_codes
-    hipEvent_t assembled = nullptr;          // root stream: behind the assembly (scatter / un-permute) of the previous call — the last reader of every rank's d_codes / d_gathered
+    blok::DeviceArray<uint32_t> d_gathered;          // root, dense: n_ranks x frames x per_rank x tile^2
+    blok::DeviceArray<uint32_t> d_frame;             // root: frames x width x height
+    blok::DeviceArray<uint8_t> d_tile_state;         // root, sparse-pull: which tiles of d_frame hold something other than sky
+    blok::DeviceArray<const uint32_t*> d_rank_ptrs;  // root, sparse-pull: every rank's d_codes
+    blok::Event assembled;                   // root stream: behind the assembly (scatter / un-permute) of the previous call — the last reader of every rank's d_codes / d_gathered
     bool has_assembled = false;
     bool frame_is_sky = false;               // d_frame / d_tile_state are in the state sparse-pull assumes (all sky / all zero, or left by it)
     bool peer_readable = false;              // the root can read every device's memory
@@ -109,21 +110,13 @@ void destroy(blok_hip_multi* m) {
         if (!r.ctx) continue;                                   // a rank whose creation failed owns nothing (and may name no device)
         (void)hipSetDevice(r.device);
         if (r.comm && m->rccl.CommDestroy) (void)m->rccl.CommDestroy(r.comm);
-        if (r.traced) (void)hipEventDestroy(r.traced);
-        if (r.d_hits) (void)hipFree(r.d_hits);
-        if (r.d_codes) (void)hipFree(r.d_codes);
-        if (r.d_rgba && &r != &m->ranks[0]) (void)hipFree(r.d_rgba);
+        r.traced.reset(); r.d_hits.reset(); r.d_codes.reset(); r.own_rgba.reset();      // with the rank's device current
         if (r.stream) { (void)hipStreamSynchronize(r.stream); (void)hipStreamDestroy(r.stream); }
         if (r.ctx) blok_hip_destroy(r.ctx);
     }
     if (!m->ranks.empty() && m->ranks[0].ctx) (void)hipSetDevice(m->ranks[0].device);
-    if (m->assembled) (void)hipEventDestroy(m->assembled);
-    if (m->d_gathered) (void)hipFree(m->d_gathered);
-    if (m->d_frame) (void)hipFree(m->d_frame);
-    if (m->d_tile_state) (void)hipFree(m->d_tile_state);
-    if (m->d_rank_ptrs) (void)hipFree(m->d_rank_ptrs);
     if (m->rccl.lib) dlclose(m->rccl.lib);
-    delete m;
+    delete m;                                                   // the root's arrays and event go with their members, the root's device current
 }
 
 // Buffers for `frames` frames per call (grown on demand; everything in flight is finished first).
@@ -137,23 +130,19 @@ int ensure_frames(blok_hip_multi* m, uint32_t frames) {
     for (uint32_t i = 0; i < G; ++i) {
         auto& r = m->ranks[i];
         MULTI_TRY(m, hipSetDevice(r.device));
-        if (r.d_hits) (void)hipFree(r.d_hits);
-        if (r.d_codes) (void)hipFree(r.d_codes);
-        if (r.d_rgba && i != 0) (void)hipFree(r.d_rgba);
-        r.d_hits = nullptr; r.d_codes = nullptr; r.d_rgba = nullptr;
-        MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&r.d_hits), frames * tile_px * sizeof(blok_hit)));
-        MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&r.d_codes), frames * blok_hip_compact_code_words(m->tile, m->per_rank) * sizeof(uint32_t)));
+        const blok::FreeAfter waited = blok::FreeAfter::nothing();           // every stream was waited for above
+        r.d_rgba = nullptr;
+        MULTI_TRY(m, r.d_hits.reserve(frames * tile_px, waited));
+        MULTI_TRY(m, r.d_codes.reserve(frames * blok_hip_compact_code_words(m->tile, m->per_rank), waited));
         if (i == 0) {
-            for (void* p : {static_cast<void*>(m->d_gathered), static_cast<void*>(m->d_frame), static_cast<void*>(m->d_tile_state), static_cast<void*>(m->d_rank_ptrs)})
-                if (p) (void)hipFree(p);
-            m->d_gathered = nullptr; m->d_frame = nullptr; m->d_tile_state = nullptr; m->d_rank_ptrs = nullptr;
-            MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_gathered), static_cast<size_t>(G) * frames * tile_px * sizeof(uint32_t)));
-            MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_frame), frames * n_px * sizeof(uint32_t)));
-            MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_tile_state), frames * tiles_total));
-            MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_rank_ptrs), G * sizeof(uint32_t*)));
+            MULTI_TRY(m, m->d_gathered.reserve(static_cast<size_t>(G) * frames * tile_px, waited));
+            MULTI_TRY(m, m->d_frame.reserve(frames * n_px, waited));
+            MULTI_TRY(m, m->d_tile_state.reserve(frames * tiles_total, waited));
+            MULTI_TRY(m, m->d_rank_ptrs.reserve(G, waited));
             r.d_rgba = m->d_gathered;                                              // the root traces straight into its slot
         } else {
-            MULTI_TRY(m, hipMalloc(reinterpret_cast<void**>(&r.d_rgba), frames * tile_px * sizeof(uint32_t)));
+            MULTI_TRY(m, r.own_rgba.reserve(frames * tile_px, waited));
+            r.d_rgba = r.own_rgba;
         }
     }
     std::vector<const uint32_t*> ptrs(G);
@@ -193,7 +182,7 @@ int blok_hip_multi_create(blok_hip_multi** out, const int* device_ordinals, uint
         if (rc != BLOK_OK) { fail(nullptr, rc, std::string("multi: device ") + std::to_string(r.device) + ": " + blok_hip_last_error(nullptr)); break; }
         hipError_t e = hipSetDevice(r.device);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.traced, hipEventDisableTiming);
+        if (e == hipSuccess) e = r.traced.create();
         if (e != hipSuccess) { rc = fail(nullptr, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("multi: device ") + std::to_string(r.device) + ": " + hipGetErrorString(e)); break; }
     }
     if (rc == BLOK_OK && n_devices > 1) {
@@ -295,7 +284,7 @@ int blok_hip_multi_draw_frames_device(blok_hip_multi* m, const blok_camera* cams
         }
     auto note_assembled = [&]() -> int {
         MULTI_TRY(m, hipSetDevice(root.device));
-        if (!m->assembled) MULTI_TRY(m, hipEventCreateWithFlags(&m->assembled, hipEventDisableTiming));
+        MULTI_TRY(m, m->assembled.create());
         MULTI_TRY(m, hipEventRecord(m->assembled, root.stream));
         m->has_assembled = true;
         return BLOK_OK;
@@ -313,7 +302,7 @@ int blok_hip_multi_draw_frames_device(blok_hip_multi* m, const blok_camera* cams
     if (pull) {
         MULTI_TRY(m, hipSetDevice(root.device));
         if (!m->frame_is_sky) {            // the state the assembly kernel builds on: every tile sky, no tile marked
-            MULTI_TRY(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_frame), static_cast<int>(0xFF000000u | (230u << 16) | (200u << 8) | 160u),
+            MULTI_TRY(m, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_frame.get()), static_cast<int>(0xFF000000u | (230u << 16) | (200u << 8) | 160u),
                                            m->frames_capacity * n_px, root.stream));
             const size_t tiles_total = static_cast<size_t>((m->width + m->tile - 1) / m->tile) * ((m->height + m->tile - 1) / m->tile);
             MULTI_TRY(m, hipMemsetAsync(m->d_tile_state, 0, m->frames_capacity * tiles_total, root.stream));
@@ -321,7 +310,7 @@ int blok_hip_multi_draw_frames_device(blok_hip_multi* m, const blok_camera* cams
         }
         for (uint32_t i = 1; i < G; ++i) MULTI_TRY(m, hipStreamWaitEvent(root.stream, m->ranks[i].traced, 0));
         // the root reads every rank's counts and live records where they lie (its own, and the peers' over xGMI) and expands them
-        rc = blok_api::scatter_frames(root.ctx, true, nullptr, reinterpret_cast<const void* const*>(m->d_rank_ptrs), G, 0, m->tile, m->per_rank, n_frames,
+        rc = blok_api::scatter_frames(root.ctx, true, nullptr, reinterpret_cast<const void* const*>(m->d_rank_ptrs.get()), G, 0, m->tile, m->per_rank, n_frames,
                                       m->d_frame, m->d_tile_state, root.stream);
         if (rc != BLOK_OK) return rank_error(m, 0, rc);
         rc = note_assembled();

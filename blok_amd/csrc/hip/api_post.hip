@@ -4,36 +4,40 @@
 
 using namespace blok_api;
 
+namespace {
+// A plane of the chain, `count` elements, zeroed with a blocking fill (the planes are fresh: ensure_post and draw_frame_rt start from a
+// reset `post`, and a failure resets it again).
+template <class T> int zeroed_plane(blok_hip_ctx* ctx, blok::DeviceArray<T>* plane, size_t count) {
+    BLOK_HIP_TRY(ctx, plane->reserve(count, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, hipMemset(plane->get(), 0, count * sizeof(T)));
+    return BLOK_OK;
+}
+}  // namespace
+
 extern "C" {
 
 // ---- image-space chain ------------------------------------------------------------------------------------------------
 namespace {
-int post_alloc_bytes(blok_hip_ctx* ctx, void** p, size_t bytes) {
-    BLOK_HIP_TRY(ctx, hipMalloc(p, bytes));
-    BLOK_HIP_TRY(ctx, hipMemset(*p, 0, bytes));
-    return BLOK_OK;
-}
-#define post_alloc(ctx, pp, count) post_alloc_bytes((ctx), reinterpret_cast<void**>(pp), (count) * sizeof(**(pp)))
 int ensure_post(blok_hip_ctx* ctx) {
     const size_t n = static_cast<size_t>(ctx->width) * ctx->height;
     auto& P = ctx->post;
     if (P.pixels == n && P.width == ctx->width && P.height == ctx->height) return BLOK_OK;     // same shape: history stays valid
-    free_post(ctx);       // any resize — also one that keeps the pixel count (320x200 -> 200x320) — drops the history planes
+    P = blok_hip_ctx::Post{};       // any resize — also one that keeps the pixel count (320x200 -> 200x320) — drops the history planes
     int rc = BLOK_OK;
     for (int k = 0; k < 2 && rc == BLOK_OK; ++k) {
-        rc = post_alloc(ctx, &P.hist_color[k], 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.moments[k], 2 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.world_pos[k], 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.hist_len[k], n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.unit_normals[k], 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.taa_hist[k], 4 * n);
+        rc = zeroed_plane(ctx, &P.hist_color[k], 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.moments[k], 2 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.world_pos[k], 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.hist_len[k], n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.unit_normals[k], 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.taa_hist[k], 4 * n);
     }
-    if (rc == BLOK_OK) rc = post_alloc(ctx, &P.motion, 2 * n);
-    if (rc == BLOK_OK) rc = post_alloc(ctx, &P.variance, n);
-    if (rc == BLOK_OK) rc = post_alloc(ctx, &P.ping, 4 * n);
-    if (rc == BLOK_OK) rc = post_alloc(ctx, &P.pong, 4 * n);
-    if (rc == BLOK_OK) rc = post_alloc(ctx, &P.widen, 2 * n);
-    if (rc != BLOK_OK) { free_post(ctx); return rc; }
+    if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.motion, 2 * n);
+    if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.variance, n);
+    if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.ping, 4 * n);
+    if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.pong, 4 * n);
+    if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.widen, 2 * n);
+    if (rc != BLOK_OK) { P = blok_hip_ctx::Post{}; return rc; }
     P.pixels = n; P.width = ctx->width; P.height = ctx->height;
     return BLOK_OK;
 }
@@ -269,21 +273,21 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
     const size_t n = P.pixels;
     if (!P.rt_final) {
         // the frame's G-buffer in the reference's image formats (raygen.rgen:55-59): 2 x RGBA32F, RGBA16F, RGBA8, RG16F = 48 B/pixel
-        for (int k = 0; k < 2 && rc == BLOK_OK; ++k) rc = post_alloc(ctx, &P.rt_planes[k], 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_normal_roughness_h, 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_albedo_metallic_u8, n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_motion_h, 2 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_denoised, 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_resolved, 4 * n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_ldr, n);
-        if (rc == BLOK_OK) rc = post_alloc(ctx, &P.rt_final, n);
-        if (rc != BLOK_OK) { free_post(ctx); return rc; }
+        for (int k = 0; k < 2 && rc == BLOK_OK; ++k) rc = zeroed_plane(ctx, &P.rt_planes[k], 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_normal_roughness_h, 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_albedo_metallic_u8, n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_motion_h, 2 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_denoised, 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_resolved, 4 * n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_ldr, n);
+        if (rc == BLOK_OK) rc = zeroed_plane(ctx, &P.rt_final, n);
+        if (rc != BLOK_OK) { P = blok_hip_ctx::Post{}; return rc; }
         P.rt_frame = 0;
     }
     const bool motion = object_motion && instances_dev && n_instances;
     if (motion && !P.rt_ids) {
-        rc = post_alloc(ctx, &P.rt_ids, n);
-        if (rc != BLOK_OK) { free_post(ctx); return rc; }
+        rc = zeroed_plane(ctx, &P.rt_ids, n);
+        if (rc != BLOK_OK) { P = blok_hip_ctx::Post{}; return rc; }
     }
     const uint32_t frame = P.rt_frame;
     float prev_vp[16];
@@ -336,13 +340,7 @@ int upload_rt_table(blok_hip_ctx* ctx, const blok_camera* cam, const blok_instan
     if (rc != BLOK_OK) return rc;
     rc = blok_hip_check_instances(ctx, instances_host, n_instances);
     if (rc != BLOK_OK) return rc;
-    const size_t need = n_instances ? n_instances : 1u;
-    if (ctx->n_rt_instances < need) {
-        if (ctx->rt_instances) (void)hipFree(ctx->rt_instances);
-        ctx->rt_instances = nullptr; ctx->n_rt_instances = 0;
-        BLOK_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->rt_instances), need * sizeof(blok_instance)));
-        ctx->n_rt_instances = need;
-    }
+    BLOK_HIP_TRY(ctx, ctx->rt_instances.reserve(n_instances ? n_instances : 1u, blok::FreeAfter::nothing()));
     if (n_instances) BLOK_HIP_TRY(ctx, hipMemcpy(ctx->rt_instances, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice));
     return BLOK_OK;
 }
@@ -365,7 +363,6 @@ int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera
     if (drawn != BLOK_OK) return drawn;
     // this frame's table becomes the previous one (the frame ended with a synchronise; the next upload overwrites the older buffer)
     std::swap(ctx->rt_instances, ctx->rt_prev_instances);
-    std::swap(ctx->n_rt_instances, ctx->n_rt_prev_instances);
     return BLOK_OK;
 }
 
@@ -373,7 +370,7 @@ int blok_hip_post_reset(blok_hip_ctx* ctx) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    free_post(ctx);
+    ctx->post = blok_hip_ctx::Post{};
     return BLOK_OK;
 }
 

@@ -71,7 +71,9 @@ int add_captured_model(blok_hip_ctx* ctx, const blok::GpuTree& tree, const int32
     m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
     m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
     for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
-    return add_model(ctx, m, out_model);
+    blok_hip_ctx::Models::Arrays own;
+    own.nodes.adopt(tree.d_nodes, tree.n_nodes); own.materials.adopt(tree.d_materials, tree.n_voxels);
+    return add_model(ctx, m, std::move(own), out_model);
 }
 // Lets go of the present volume, if there is one, and of the world installed from its arrays (it lives in them: it goes with them).  strict:
 // a failing wait for the frames that still read that world is the call's failure, and nothing is freed.
@@ -678,18 +680,16 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
     // the material table is uploaded again only when it differs from the installed one
     const bool same_materials = same_lattice && ctx->d_materials && ctx->n_materials == n_materials && ctx->volume_materials.size() == n_materials * sizeof(blok_material) &&
                                 (n_materials == 0 || std::memcmp(ctx->volume_materials.data(), materials, n_materials * sizeof(blok_material)) == 0);
-    float* keep_sun = nullptr; bool keep_has_sun = false;
-    blok_material* keep_mat = nullptr; size_t keep_n_mat = 0;
-    if (same_lattice) { keep_sun = ctx->d_sun_map; keep_has_sun = ctx->has_sun_map; ctx->d_sun_map = nullptr; }      // survive free_world
-    if (same_materials) { keep_mat = ctx->d_materials; keep_n_mat = ctx->n_materials; ctx->d_materials = nullptr; }
+    blok::DeviceArray<float> keep_sun; const bool keep_has_sun = ctx->has_sun_map;
+    blok::DeviceArray<blok_material> keep_mat; const size_t keep_n_mat = ctx->n_materials;
+    if (same_lattice) keep_sun = std::move(ctx->d_sun_map);      // survive free_world
+    if (same_materials) keep_mat = std::move(ctx->d_materials);
     free_world(ctx);
-    ctx->d_nodes = gpu.d_nodes;
-    ctx->d_tree_materials = gpu.d_materials;
-    ctx->tree_owned_by_volume = gpu.owned_by_volume;
-    if (same_materials) { ctx->d_materials = keep_mat; ctx->n_materials = keep_n_mat; }
+    adopt_tree(ctx, gpu);
+    if (same_materials) { ctx->d_materials = std::move(keep_mat); ctx->n_materials = keep_n_mat; }
     else {
         rc = install_materials(ctx, materials, n_materials);
-        if (rc != BLOK_OK) { if (keep_sun) (void)hipFree(keep_sun); free_world(ctx); return rc; }
+        if (rc != BLOK_OK) { free_world(ctx); return rc; }
         ctx->volume_materials.assign(reinterpret_cast<const unsigned char*>(materials), reinterpret_cast<const unsigned char*>(materials) + n_materials * sizeof(blok_material));
     }
     ctx->stats.n_voxels = gpu.n_voxels;
@@ -703,7 +703,7 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
     // per frame with the order kept, 270 with it dropped)
     ctx->order.interval_now = ctx->order.interval;
     ctx->built_on_device = true;
-    if (same_lattice) { ctx->d_sun_map = keep_sun; ctx->has_sun_map = keep_has_sun; }
+    if (same_lattice) { ctx->d_sun_map = std::move(keep_sun); ctx->has_sun_map = keep_has_sun; }
     const auto t_installed = std::chrono::steady_clock::now();
     // a fill of the whole box is a new world to the map: raised over every texel it would stay loose until kSunMapLooseEdits further
     // edits (api.hip), so it is searched anew as for a changed lattice — one search per texel behind an edit that wrote every cell
