@@ -312,6 +312,9 @@ HIP_SYMBOLS = {
     "blok_hip_set_miss_writer": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_set_beam_cache": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_beam_cache_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "blok_hip_beam_cache_refines": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "blok_hip_set_beam_refine_after": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "blok_hip_beam_cache_download_fine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "blok_hip_last_launch_kind": (C.c_int, [C.c_void_p]),
     "blok_hip_set_volume_layout": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_set_list_classes": (C.c_int, [C.c_void_p, C.c_int]),

@@ -309,9 +309,10 @@ int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk) {
     return BLOK_OK;
 }
 
-int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int enabled) {
+int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    ctx->beam_cache.enabled = enabled != 0;
+    ctx->beam_cache.enabled = mode != 0;
+    ctx->beam_cache.refine = mode >= 2;
     blok::beam_cache_clear(ctx->beam_cache.policy);      // off: every launch searches, as before there was a cache; on again: views are admitted afresh
     return BLOK_OK;
 }
@@ -320,6 +321,18 @@ int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, ui
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (out_hits) *out_hits = ctx->beam_cache.hits;
     if (out_fills) *out_fills = ctx->beam_cache.fills;
+    return BLOK_OK;
+}
+
+int blok_hip_set_beam_refine_after(blok_hip_ctx* ctx, uint32_t hits) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    ctx->beam_cache.policy.refine_after = hits ? hits : blok::kBeamRefineAfter;
+    return BLOK_OK;
+}
+
+int blok_hip_beam_cache_refines(const blok_hip_ctx* ctx, uint64_t* out_refines) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (out_refines) *out_refines = ctx->beam_cache.refines;
     return BLOK_OK;
 }
 
@@ -337,6 +350,22 @@ int blok_hip_beam_cache_download(blok_hip_ctx* ctx, int* out_action, uint32_t* o
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     BLOK_HIP_TRY(ctx, hipMemcpy(out_t0_host, B.slots[B.last_slot].d_beam, B.last_n_beams * sizeof(float), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+// The same for the slot's finer bounds.
+int blok_hip_beam_cache_download_fine(blok_hip_ctx* ctx, int* out_state, uint32_t* out_n_tiles, float* out_t0_host, size_t capacity) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const auto& B = ctx->beam_cache;
+    if (out_state) *out_state = B.last_fine;
+    if (out_n_tiles) *out_n_tiles = B.last_n_fine;
+    if (!out_t0_host || !B.last_fine) return BLOK_OK;
+    if (B.last_slot < 0 || static_cast<uint32_t>(B.last_slot) >= blok::kBeamCacheSlots || !B.slots[B.last_slot].d_fine || B.last_n_fine > B.capacity)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the latest launch's slot is gone (a resize)");
+    if (capacity < B.last_n_fine) return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: output smaller than the launch's wave tiles");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_t0_host, B.slots[B.last_slot].d_fine, B.last_n_fine * sizeof(float), hipMemcpyDeviceToHost));
     return BLOK_OK;
 }
 

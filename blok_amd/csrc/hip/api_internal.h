@@ -145,21 +145,30 @@ struct blok_hip_ctx {
     // searches of ONE launch (the fill) and read by the walks of later launches of the same view, on any stream: the first reader on another
     // stream waits for `ready`, and a slot is refilled only behind the held markers of every stream (api_launch.hip: hold_markers).
     // Allocated by blok_hip_create / _resize for the finest beam tile over the whole frame, so that no launch allocates.
+    // A second buffer of the same size per slot holds the view's finer bounds, one per wave tile (beam_cache.h: plan_beam_refine): written by
+    // ONE launch behind its walk (the refine kernel, `refined` behind it), read by the walks of the view's later launches under the same two
+    // rules — a refill waits for every stream's held markers, which covers the readers of both buffers.
     struct BeamCache {
         bool enabled = true;                                // blok_hip_set_beam_cache
+        bool refine = true;                                 // ... with the finer bounds (mode 2)
         blok::BeamCachePolicy policy{};
-        struct Slot {
-            blok::DeviceArray<float> d_beam;
-            blok::Event ready;                              // behind the launch that filled the slot
+        // What one launch wrote on its stream and later launches read on any: the event behind the writer, and who need not wait any more.
+        struct Produced {
+            blok::Event done;                               // behind the launch that wrote
             hipStream_t producer = nullptr;                 // ... and its stream
-            bool settled = true;                            // `ready` has been seen complete: nobody waits any more
-            bool used = false;                              // filled at least once: launches that read it may be in flight
+            bool settled = true;                            // `done` has been seen complete: nobody waits any more
             static constexpr uint32_t kWaited = 8;
-            hipStream_t waited[kWaited] = {}; uint32_t n_waited = 0;      // streams that already wait for `ready` (or are behind it)
+            hipStream_t waited[kWaited] = {}; uint32_t n_waited = 0;      // streams that already wait for `done` (or are behind it)
+        };
+        struct Slot {
+            blok::DeviceArray<float> d_beam, d_fine;
+            Produced filled, refined;
+            bool used = false;                              // filled at least once: launches that read it may be in flight
         } slots[blok::kBeamCacheSlots];
-        size_t capacity = 0;                                // floats per slot
-        uint64_t hits = 0, fills = 0;                       // blok_hip_beam_cache_counters
+        size_t capacity = 0;                                // floats per buffer
+        uint64_t hits = 0, fills = 0, refines = 0;          // blok_hip_beam_cache_counters, blok_hip_beam_cache_refines
         int last_action = 0, last_slot = -1; uint32_t last_n_beams = 0;      // the latest rectangle launch: 0 searched, 1 searched into last_slot, 2 walked from it (blok_hip_beam_cache_download)
+        int last_fine = 0; uint32_t last_n_fine = 0;        // ... and its finer bounds: 0 none, 1 it issued their searches, 2 it walked from them (blok_hip_beam_cache_download_fine)
     } beam_cache;
     // Longest-first scheduling of the walk for a camera at rest (tile_order.h; rectangle launches of the static forms): every walk wave
     // leaves the clocks it spent in d_cost (one buffer per context, for the launch geometry in `key`).  Every `interval` launches a

@@ -387,14 +387,17 @@ int beam_cache_buffers(blok_hip_ctx* ctx) {
     for (auto& sl : B.slots) {
         sl = blok_hip_ctx::BeamCache::Slot{};
         BLOK_HIP_TRY(ctx, sl.d_beam.reserve(want, blok::FreeAfter::nothing()));      // (the wait above was for all of them)
-        BLOK_HIP_TRY(ctx, sl.ready.create());
+        BLOK_HIP_TRY(ctx, sl.d_fine.reserve(want, blok::FreeAfter::nothing()));
+        BLOK_HIP_TRY(ctx, sl.filled.done.create());
+        BLOK_HIP_TRY(ctx, sl.refined.done.create());
     }
     B.capacity = want;
     return BLOK_OK;
 }
 
 void settle_beam_cache(blok_hip_ctx* ctx) {
-    for (auto& sl : ctx->beam_cache.slots) { sl.settled = true; sl.n_waited = 0; }
+    for (auto& sl : ctx->beam_cache.slots)
+        for (auto* p : {&sl.filled, &sl.refined}) { p->settled = true; p->n_waited = 0; }
 }
 
 static blok::BeamKey beam_key(const blok_hip_ctx* ctx, blok::RayMode mode, const blok::TraceArgs& args) {
@@ -415,27 +418,28 @@ static blok::BeamKey beam_key(const blok_hip_ctx* ctx, blok::RayMode mode, const
     return k;
 }
 
-// Before a rectangle launch of a static form: does it search, search into a slot, or walk from a slot?  Points args.beam at the slot and
-// deals with whoever else uses it.
-static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan) {
+// The launch that wrote what `stream` is about to read may still be running, on another stream: the first reader there waits for it.
+static int wait_for_producer(blok_hip_ctx* ctx, blok_hip_ctx::BeamCache::Produced& p, hipStream_t stream) {
+    if (p.settled || stream == p.producer) return BLOK_OK;
+    for (uint32_t k = 0; k < p.n_waited; ++k) if (p.waited[k] == stream) return BLOK_OK;
+    if (hipEventQuery(p.done) == hipSuccess) { p.settled = true; p.n_waited = 0; return BLOK_OK; }
+    (void)hipGetLastError();                             // hipErrorNotReady is an answer, not a failure
+    BLOK_HIP_TRY(ctx, hipStreamWaitEvent(stream, p.done, 0));
+    if (p.n_waited < blok_hip_ctx::BeamCache::Produced::kWaited) p.waited[p.n_waited++] = stream;      // (more streams than that wait again next time: harmless)
+    return BLOK_OK;
+}
+
+// Before a rectangle launch of a static form: does it search, search into a slot, or walk from a slot — and then from the slot's finer
+// bounds, or with their searches behind it?  Points args.beam at the slot's beam bounds and deals with whoever else uses it.
+static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan, blok::BeamRefinePlan* fine) {
     auto& B = ctx->beam_cache;
     *plan = blok::plan_beam_cache(B.policy, beam_key(ctx, mode, args));
+    *fine = blok::plan_beam_refine(B.policy, *plan, B.refine && blok::beam_refine_applies(args) && blok::beam_refine_tiles(args) <= B.capacity);
     if (plan->action == blok::BeamAction::Search) return BLOK_OK;
     auto& sl = B.slots[plan->slot];
     if (plan->action == blok::BeamAction::Hit) {
-        // the launch that filled the slot may still be running, on another stream: the first reader there waits for it
-        if (!sl.settled && stream != sl.producer) {
-            bool waits = false;
-            for (uint32_t k = 0; k < sl.n_waited && !waits; ++k) waits = sl.waited[k] == stream;
-            if (!waits) {
-                if (hipEventQuery(sl.ready) == hipSuccess) { sl.settled = true; sl.n_waited = 0; }
-                else {
-                    (void)hipGetLastError();                             // hipErrorNotReady is an answer, not a failure
-                    BLOK_HIP_TRY(ctx, hipStreamWaitEvent(stream, sl.ready, 0));
-                    if (sl.n_waited < blok_hip_ctx::BeamCache::Slot::kWaited) sl.waited[sl.n_waited++] = stream;      // (more streams than that wait again next time: harmless)
-                }
-            }
-        }
+        { const int rc = wait_for_producer(ctx, sl.filled, stream); if (rc != BLOK_OK) return rc; }
+        if (fine->use_fine) { const int rc = wait_for_producer(ctx, sl.refined, stream); if (rc != BLOK_OK) return rc; }
         B.hits += 1u;
     } else {
         // Nothing in flight may read the slot while the searches rewrite it (nor still be writing it): whatever used it was issued before
@@ -446,7 +450,8 @@ static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok:
             const int rc = wait_for_held_markers(ctx, stream);
             if (rc != BLOK_OK) return rc;
         }
-        sl.used = true; sl.settled = false; sl.producer = stream; sl.n_waited = 0;
+        sl.used = true;
+        sl.filled.settled = false; sl.filled.producer = stream; sl.filled.n_waited = 0;
         B.fills += 1u;
     }
     args.beam = sl.d_beam; args.beam_slots = nullptr; args.beam_serial = 0u;      // plain floats, whatever form was planned
@@ -545,19 +550,32 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     // A view at rest keeps its beam bounds (beam_cache.h): rectangle launches of the automatic form — the explicit forms stay what they are
     // there to be compared with, a rank's tiles and several frames per launch are left alone — that are not being captured.
     blok::BeamCachePlan cached{blok::BeamAction::Search, -1};
+    blok::BeamRefinePlan finer{false, false};
     if (ctx->beam_cache.enabled && rect && !frames && !capturing && static_form && ctx->launch_form == blok::kFormAuto && n_beams && n_beams <= ctx->beam_cache.capacity) {
-        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached);
-        if (rc != BLOK_OK) return rc;
+        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached, &finer);
+        if (rc != BLOK_OK) { if (finer.refine_now) blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, false); return rc; }
         // the searches that fill a slot write plain floats: the two-launch form, this once
         if (cached.action == blok::BeamAction::Fill && plan.kind == blok::LaunchKind::Joint) { plan.kind = blok::LaunchKind::TwoLaunches; ctx->last_launch_kind = static_cast<int>(plan.kind); }
     }
     ctx->beam_cache.last_action = cached.action == blok::BeamAction::Hit ? 2 : cached.action == blok::BeamAction::Fill ? 1 : 0;
     ctx->beam_cache.last_slot = cached.slot; ctx->beam_cache.last_n_beams = n_beams;
+    ctx->beam_cache.last_fine = finer.use_fine ? 2 : finer.refine_now ? 1 : 0;
+    ctx->beam_cache.last_n_fine = ctx->beam_cache.last_fine ? blok::beam_refine_tiles(args) : 0u;
     if (cached.action == blok::BeamAction::Hit) {
         // no searches: the walk over the view's live prefix, from the kept bounds; in front of it, what the search waves do besides searching
         // (the miss pixels, unless the walk writes them; the wave tiles the prefix has no workgroup for) — last_launch_kind stays the policy's
-        if (!args.miss_in_walk) blok::launch_beam_fill(mode, args, n_beams, stream);
-        blok::launch_trace(mode, args, walk_blocks, stream);
+        float* const d_fine = ctx->beam_cache.slots[cached.slot].d_fine;
+        if (!args.miss_in_walk) blok::launch_beam_fill(mode, args, n_beams, finer.use_fine ? d_fine : nullptr, stream);
+        if (finer.use_fine) {
+            // the walk reads the finer bounds through the fields it has: a "beam tile" the size of a wave tile (the lookup in trace_block
+            // works for any tile size), so a wave tile that is empty by its own bound is not walked: its misses come from the walk
+            // (miss_in_walk) or from the fill wave of its beam tile, and its walk workgroup, while the order still has one, costs 0
+            blok::TraceArgs walk = args;
+            walk.beam = d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
+            blok::launch_trace(mode, walk, walk_blocks, stream);
+        } else blok::launch_trace(mode, args, walk_blocks, stream);
+        // the view's K-th hit: its finer searches behind its walk, once
+        if (finer.refine_now) blok::launch_beam_refine(args, d_fine, stream);
     } else
     switch (plan.kind) {
         case blok::LaunchKind::Walk:
@@ -577,8 +595,15 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     }
     const hipError_t launch_error = hipGetLastError();
     if (launch_error != hipSuccess && cached.action == blok::BeamAction::Fill) ctx->beam_cache.policy.valid[cached.slot] = false;      // bounds nobody wrote are nobody's to keep
+    if (finer.refine_now) {
+        auto& made = ctx->beam_cache.slots[cached.slot].refined;
+        const hipError_t marked = launch_error == hipSuccess ? hipEventRecord(made.done, stream) : launch_error;
+        blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, marked == hipSuccess);      // (bounds nobody can wait for are not used)
+        if (marked == hipSuccess) { made.settled = false; made.producer = stream; made.n_waited = 0; ctx->beam_cache.refines += 1u; }
+        else if (launch_error == hipSuccess) BLOK_HIP_TRY(ctx, marked);
+    }
     BLOK_HIP_TRY(ctx, launch_error);
-    if (cached.action == blok::BeamAction::Fill) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->beam_cache.slots[cached.slot].ready, stream));
+    if (cached.action == blok::BeamAction::Fill) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->beam_cache.slots[cached.slot].filled.done, stream));
     if (ctx->timing && !capturing) { BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_end, stream)); ctx->timed = true; }
     if (args.fallback_tiles) BLOK_HIP_TRY(ctx, hipMemcpyAsync(ctx->order.h_fallback, ctx->order.d_fallback, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     if (orderable) { const int rc = order_after_launch(ctx, args, blocks, n_beams, stream, order_plan); if (rc != BLOK_OK) return rc; }

@@ -5,7 +5,9 @@
 //
 // What is kept is the OUTPUT of beam_kernel alone (trace_kernels.hip; beam.h): one start parameter per beam tile, a pure function of the
 // key below.  The records and the pixels of a frame are produced by walking every live tile of every frame as before; a launch that
-// hits walks from the same start parameters its own searches would have found, so it writes the same bytes.
+// hits walks from the same start parameters its own searches would have found, so it writes the same bytes.  From its K-th hit on a slot
+// also keeps the output of beam_refine_kernel — the same search over every wave tile's own pixels, a pure function of the same key — and
+// later hits walk from those: valid lower bounds again, so the same bytes again, over a shorter walk.
 #ifndef BLOK_BEAM_CACHE_H
 #define BLOK_BEAM_CACHE_H
 #include <stdint.h>
@@ -54,6 +56,19 @@ enum class BeamAction : int {
 };
 struct BeamCachePlan { BeamAction action; int slot; };
 
+// A filled slot's finer bounds: one start parameter per wave tile, searched ONCE, behind the walk of the view's K-th hit (plan_beam_refine);
+// later hits walk from them.  A camera that rests for fewer than K hits pays nothing for them.
+enum class BeamRefine : uint8_t {
+    None = 0,                                  // the slot holds the beam tiles' bounds only
+    Now = 1,                                   // the launch that was just planned issues the finer searches (beam_refine_commit ends this state)
+    Done = 2,                                  // the finer bounds are there (or on their way, on the stream of the launch that refined)
+};
+// The default K: the finer searches' duration over what a frame gains from them, rounded up to a power of two.  Measured at 4K over 1024^3
+// (profiles/beam_refine_ab.txt): pose A 135 us over 23 us a frame = 5.9, pose B 354 us over 34 us = 10.3 (the grazing view: more live
+// tiles, longer searches) -> 8 and 16; the larger, so that neither view pays for searches it has not yet earned back.
+constexpr uint32_t kBeamRefineAfter = 16;
+struct BeamRefinePlan { bool refine_now, use_fine; };
+
 struct BeamCachePolicy {
     BeamKey key[kBeamCacheSlots];
     bool valid[kBeamCacheSlots];
@@ -61,10 +76,13 @@ struct BeamCachePolicy {
     BeamKey last;                              // key of the previous launch that asked
     bool have_last;
     uint64_t serial;                           // launches that asked so far
+    BeamRefine refine[kBeamCacheSlots];        // reset by every fill (a refill, an eviction) and by beam_cache_clear
+    uint32_t hits_since_fill[kBeamCacheSlots];
+    uint32_t refine_after = kBeamRefineAfter;  // K (a debug setter: the tests need 1); kept by beam_cache_clear
 };
 
 inline void beam_cache_clear(BeamCachePolicy& s) {
-    for (int k = 0; k < kBeamCacheSlots; ++k) { s.valid[k] = false; s.last_use[k] = 0u; }
+    for (int k = 0; k < kBeamCacheSlots; ++k) { s.valid[k] = false; s.last_use[k] = 0u; s.refine[k] = BeamRefine::None; s.hits_since_fill[k] = 0u; }
     s.have_last = false;
 }
 
@@ -76,13 +94,40 @@ inline BeamCachePlan plan_beam_cache(BeamCachePolicy& s, const BeamKey& k) {
     const bool again = s.have_last && beam_key_equal(s.last, k);
     s.last = k; s.have_last = true;
     for (int i = 0; i < kBeamCacheSlots; ++i)
-        if (s.valid[i] && beam_key_equal(s.key[i], k)) { s.last_use[i] = s.serial; return {BeamAction::Hit, i}; }
+        if (s.valid[i] && beam_key_equal(s.key[i], k)) {
+            s.last_use[i] = s.serial;
+            if (s.hits_since_fill[i] != UINT32_MAX) s.hits_since_fill[i] += 1u;
+            return {BeamAction::Hit, i};
+        }
     if (!again) return {BeamAction::Search, -1};
     int target = -1;
     for (int i = 0; i < kBeamCacheSlots && target < 0; ++i) if (!s.valid[i]) target = i;
     if (target < 0) { target = 0; for (int i = 1; i < kBeamCacheSlots; ++i) if (s.last_use[i] < s.last_use[target]) target = i; }
     s.key[target] = k; s.valid[target] = true; s.last_use[target] = s.serial;
+    s.refine[target] = BeamRefine::None; s.hits_since_fill[target] = 0u;
     return {BeamAction::Fill, target};
+}
+
+// Behind plan_beam_cache, for the same launch: does it issue the finer searches, does it walk from the finer bounds?  "Refine now" is said
+// once per fill, on the slot's K-th hit (the first eligible hit from the K-th on, should K have been lowered meanwhile); never for a search
+// or a fill, so never for a view that is not admitted.  eligible: the launch's geometry allows finer bounds at all and they are switched on
+// (a property of the key and of the context, the same for every hit of a slot).  The launch that refines still walks from the coarse bounds.
+inline BeamRefinePlan plan_beam_refine(BeamCachePolicy& s, const BeamCachePlan& p, bool eligible) {
+    if (p.action != BeamAction::Hit || p.slot < 0 || p.slot >= kBeamCacheSlots || !eligible) return {false, false};
+    if (s.refine[p.slot] == BeamRefine::Done) return {false, true};
+    if (s.refine[p.slot] == BeamRefine::None && s.hits_since_fill[p.slot] >= (s.refine_after ? s.refine_after : 1u)) {
+        s.refine[p.slot] = BeamRefine::Now;
+        return {true, false};
+    }
+    return {false, false};
+}
+
+// The launch that was told "refine now" has issued its searches (issued: the finer bounds are kept) or could not (the slot stays as it
+// was filled, and is asked again K hits later).
+inline void beam_refine_commit(BeamCachePolicy& s, int slot, bool issued) {
+    if (slot < 0 || slot >= kBeamCacheSlots || s.refine[slot] != BeamRefine::Now) return;
+    s.refine[slot] = issued ? BeamRefine::Done : BeamRefine::None;
+    if (!issued) s.hits_since_fill[slot] = 0u;
 }
 
 }  // namespace blok

@@ -283,7 +283,14 @@ uint32_t beam_tiles(RayMode mode, const TraceArgs& args, uint32_t tiles_of_rank)
 void launch_beam(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hipStream_t stream);
 // Behind a launch whose start parameters are already in args.beam (plain floats; Rect only): what the search waves do for their tiles
 // besides searching — miss pixels of empty tiles (miss_in_walk 0), wave tiles a prefix launch has no walk workgroup for.
-void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hipStream_t stream);
+// fine: the view's finer bounds when the walk of this launch reads them (beam_cache.h; one float per wave tile of the rectangle), else null —
+// then the wave of a live beam tile also writes the misses of every wave tile that is empty by its own bound, and walks from the finer bounds.
+void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, const float* fine, hipStream_t stream);
+// The finer bounds of a rectangle launch whose beam bounds are in args.beam (plain floats): one search wave per wave tile, into `fine`
+// (beam_refine_tiles floats).  Applies only where a beam tile is a whole number (> 1) of square wave tiles per side.
+uint32_t beam_refine_tiles(const TraceArgs& args);
+bool beam_refine_applies(const TraceArgs& args);
+void launch_beam_refine(const TraceArgs& args, float* fine, hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

@@ -347,9 +347,12 @@ __device__ __forceinline__ const TraceArgs& kernel_args() {
 // lds_stack: the walk's stack for the wave tiles a search walks itself (launches over a prefix of the order, TraceArgs::rank_of), else null.
 // kKept (beam_fill_kernel): the start parameter is not searched for but read from TraceArgs::beam, where an earlier launch of this very view
 // left it (beam_cache.h); nothing is published, and everything else a search wave does for its tile behind the search happens as ever.
+// fine (kKept, Rect, may be null): the view's finer bounds, one per wave tile of the rectangle, row-major (beam_refine_kernel) — the walk
+// of this launch reads its start parameters there, so a wave tile that is empty by its own search inside a live beam tile gets its misses
+// from this wave (its walk workgroup, if it has one, exits without writing), and a wave tile walked here starts from its own bound.
 template <RayMode MODE, bool kKept = false>
 __device__ __forceinline__ void beam_block(const TraceArgs& A, const uint32_t b, const uint32_t n_beam_tiles, [[maybe_unused]] uint4* lds_stack = nullptr,
-                                           const uint32_t list_search = 0u, const uint32_t list_task_base = 0u) {
+                                           const uint32_t list_search = 0u, const uint32_t list_task_base = 0u, [[maybe_unused]] const float* fine = nullptr) {
     const uint32_t lane = threadIdx.x;
     if (b >= n_beam_tiles) return;
     const uint32_t B = A.beam_tile;
@@ -393,6 +396,42 @@ __device__ __forceinline__ void beam_block(const TraceArgs& A, const uint32_t b,
             if constexpr (MODE == RayMode::Rect) out_index = static_cast<size_t>(y - A.y0) * A.w + (x - A.x0);
             else out_index = tile_base + static_cast<size_t>(y - tile_y0) * A.tile + (x - tile_x0);
             write_miss(Sink{A.out ? A.out + out_index : nullptr, A.out_rgba ? A.out_rgba + out_index : nullptr});
+        }
+    }
+    if constexpr (MODE == RayMode::Rect && kBlock == 64 && kKept) {
+        if (fine && t0 < kBeamNone) {
+            // the wave tiles of this live beam tile, each by its own bound: empty — its 64 misses, whoever else there is for it; live and
+            // without a walk workgroup (a prefix launch) — walked here from that bound
+            const uint32_t bx_count = (A.w + kTileW - 1u) / kTileW, by_count = (A.h + kTileH - 1u) / kTileH;
+            const uint32_t bx0 = (px - A.x0) / kTileW, bx1 = (px_end - A.x0 + kTileW - 1u) / kTileW;
+            const uint32_t by0 = (py - A.y0) / kTileH, by1 = (py_end - A.y0 + kTileH - 1u) / kTileH;
+            uint32_t walked = 0u;
+            for (uint32_t by = by0; by < by1; ++by)
+                for (uint32_t bx = bx0; bx < bx1; ++bx) {
+                    const uint32_t tile = by * bx_count + bx;
+                    const float f0 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(fine[tile])));
+                    const uint32_t rx = bx * kTileW + lane % kWaveW, ry = by * kTileH + lane / kWaveW;
+                    const bool inside = rx < A.w && ry < A.h;
+                    const size_t at = static_cast<size_t>(ry) * A.w + rx;
+                    if (f0 >= kBeamNone) {
+                        if (inside && !A.miss_in_walk) write_miss(Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+                        continue;
+                    }
+                    if (!A.rank_of || !lds_stack) continue;
+                    if (A.n_strip && (bx - A.strip_x0 < A.strip_nx || by - A.strip_y0 < A.strip_ny)) continue;      // a strip tile: it has a walk workgroup of its own
+                    const uint32_t ox = bx >= A.order_sx ? bx - A.order_sx : bx + bx_count - A.order_sx, oy = by >= A.order_sy ? by - A.order_sy : by + by_count - A.order_sy;
+                    if (__builtin_amdgcn_readfirstlane(A.rank_of[oy * bx_count + ox]) < A.launched) continue;
+                    const uint64_t clock0 = __builtin_amdgcn_s_memtime();
+                    if (inside) {
+                        RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+                        r.tmin = fmaxf(r.tmin, f0);
+                        trace_one(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+                    }
+                    if (A.cost_out && lane == 0) A.cost_out[tile] = max(static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - clock0), 256u);
+                    ++walked;
+                }
+            if (walked && A.fallback_tiles && lane == 0) (void)__hip_atomic_fetch_add(A.fallback_tiles, walked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
         }
     }
     if constexpr (MODE == RayMode::Rect && kBlock == 64) {
@@ -458,10 +497,32 @@ __global__ __launch_bounds__(64) void beam_kernel(const TraceArgs, const uint32_
 // them), the wave tiles of a live tile that a prefix launch has no walk workgroup for — and nothing else: a live tile whose wave tiles
 // all have their walk workgroup costs its wave a load and a few comparisons.
 template <RayMode MODE>
-__global__ __launch_bounds__(64) void beam_fill_kernel(const TraceArgs, const uint32_t n_beam_tiles) {
+__global__ __launch_bounds__(64) void beam_fill_kernel(const TraceArgs, const uint32_t n_beam_tiles, const float* fine) {
     extern __shared__ uint4 lds_stack[];       // as for beam_kernel: sized by the launch whenever the waves may walk (TraceArgs::rank_of)
     const TraceArgs& A = kernel_args();
-    beam_block<MODE, true>(A, blockIdx.x, n_beam_tiles, A.rank_of ? lds_stack : nullptr);
+    beam_block<MODE, true>(A, blockIdx.x, n_beam_tiles, A.rank_of ? lds_stack : nullptr, 0u, 0u, fine);
+}
+
+// Once per view at rest (beam_cache.h: plan_beam_refine), behind the walk of the launch whose beam bounds are in TraceArgs::beam: one wave
+// per wave tile of the rectangle searches the tile's OWN pixels — cut at the rectangle's edge as a pre-pass with a beam tile of that size
+// cuts them, under the launch's budget — and leaves max(its answer, its beam tile's) in fine[row * tiles per row + column]; kBeamNone when
+// either search says so (a wave tile of an empty beam tile is not searched).  Valid for the reason the beam tile's bound is (beam.h); what
+// path_kernel does per launch for its own wave tile.
+__global__ __launch_bounds__(64) void beam_refine_kernel(const TraceArgs, float* fine) {
+    const TraceArgs& A = kernel_args();
+    const uint32_t lane = threadIdx.x;
+    const uint32_t bx_count = (A.w + kWaveW - 1u) / kWaveW, by_count = (A.h + kWaveH - 1u) / kWaveH;
+    const uint32_t tile = blockIdx.x;
+    if (tile >= bx_count * by_count) return;
+    const uint32_t bx = tile % bx_count, by = tile / bx_count;
+    const float coarse = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(A.beam[((by * kWaveH) / A.beam_tile) * A.beam_bx + (bx * kWaveW) / A.beam_tile])));
+    float t0 = kBeamNone;
+    if (coarse < kBeamNone) {
+        const uint32_t px = A.x0 + bx * kWaveW, py = A.y0 + by * kWaveH;
+        const float own = beam_start(A, static_cast<float>(px), static_cast<float>(py), static_cast<float>(min(px + kWaveW, A.x0 + A.w)), static_cast<float>(min(py + kWaveH, A.y0 + A.h)), lane);
+        t0 = own >= kBeamNone ? kBeamNone : fmaxf(own, coarse);
+    }
+    if (lane == 0) fine[tile] = t0;
 }
 
 // ---- joint launch: the pre-pass waves and the walk waves in ONE grid, statically ------------------------------------------
@@ -1165,10 +1226,22 @@ void launch_beam(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hip
     else hipLaunchKernelGGL(beam_kernel<RayMode::Tiles>, dim3(n_beam_tiles), dim3(64), lds, stream, args, n_beam_tiles);
 }
 
-void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, hipStream_t stream) {
+void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, const float* fine, hipStream_t stream) {
     if (n_beam_tiles == 0 || mode != RayMode::Rect || !args.beam || args.beam_slots || args.list.entries) return;
     const size_t lds = args.rank_of ? frame_lds_bytes(args) : 0;      // as in launch_beam
-    hipLaunchKernelGGL(beam_fill_kernel<RayMode::Rect>, dim3(n_beam_tiles), dim3(64), lds, stream, args, n_beam_tiles);
+    hipLaunchKernelGGL(beam_fill_kernel<RayMode::Rect>, dim3(n_beam_tiles), dim3(64), lds, stream, args, n_beam_tiles, fine);
+}
+
+uint32_t beam_refine_tiles(const TraceArgs& a) { return ((a.w + kWaveW - 1u) / kWaveW) * ((a.h + kWaveH - 1u) / kWaveH); }
+
+bool beam_refine_applies(const TraceArgs& a) {
+    return kBlock == 64 && kWaveW == kWaveH && a.beam_tile > kWaveW && a.beam_tile % kWaveW == 0u;
+}
+
+void launch_beam_refine(const TraceArgs& args, float* fine, hipStream_t stream) {
+    const uint32_t n = beam_refine_tiles(args);
+    if (n == 0 || !fine || !args.beam || args.beam_slots || !beam_refine_applies(args)) return;
+    hipLaunchKernelGGL(beam_refine_kernel, dim3(n), dim3(64), 0, stream, args, fine);
 }
 
 size_t frame_lds_bytes(const TraceArgs& args) { return static_cast<size_t>(args.levels > 1 ? args.levels - 1 : 1) * kBlock * sizeof(uint4); }

@@ -566,10 +566,39 @@ class HipTracer:
         """Empty tiles' miss pixels: written by the walk launch's waves (True, default) or by the pre-pass (blok_hip.h)."""
         self._check(self._lib.blok_hip_set_miss_writer(self._ctx, 1 if in_walk else 0))
 
-    def set_beam_cache(self, enabled: bool):
-        """Keep the beam bounds of a view at rest from launch to launch (default on; blok_hip_debug.h); off = every launch searches.
-        Never changes a result."""
-        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, 1 if enabled else 0))
+    def set_beam_cache(self, mode):
+        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 2 or True (default) = and, from the view's K-th
+        hit on, a finer bound per wave tile; 1 = the beam tiles' bounds alone; 0 or False = every launch searches.  Never changes a result."""
+        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (2 if mode else 0) if isinstance(mode, bool) else int(mode)))
+
+    def set_beam_refine_after(self, hits: int):
+        """K: the hit of a kept view behind whose walk its finer bounds are searched, once (0 = the default; blok_hip_debug.h)."""
+        self._check(self._lib.blok_hip_set_beam_refine_after(self._ctx, hits))
+
+    def beam_cache_refines(self) -> int:
+        """Diagnostic: launches so far that issued a view's finer searches behind their walk."""
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_beam_cache_refines(self._ctx, C.byref(n)))
+        return int(n.value)
+
+    def beam_cache_fine_state(self) -> int:
+        """What the latest rectangle launch had to do with its view's finer bounds: 0 nothing, 1 it issued their searches, 2 it walked from
+        them.  Waits for nothing."""
+        state = C.c_int(0)
+        self._check(self._lib.blok_hip_beam_cache_download_fine(self._ctx, C.byref(state), None, None, 0))
+        return int(state.value)
+
+    def beam_cache_fine(self):
+        """(state, t0) of the latest rectangle launch's finer bounds (blok_hip_debug.h: blok_hip_beam_cache_download_fine): state 0 none,
+        1 it issued their searches behind its walk, 2 it walked from them; t0 one start parameter per 8 x 8 wave tile of the rectangle,
+        row-major, or None for state 0."""
+        state, n = C.c_int(0), C.c_uint32(0)
+        self._check(self._lib.blok_hip_beam_cache_download_fine(self._ctx, C.byref(state), C.byref(n), None, 0))
+        if not state.value:
+            return 0, None
+        t0 = np.zeros(int(n.value), dtype=np.float32)
+        self._check(self._lib.blok_hip_beam_cache_download_fine(self._ctx, C.byref(state), C.byref(n), _ffi.ptr(t0), len(t0)))
+        return int(state.value), t0
 
     def beam_cache_counters(self):
         """Diagnostic: (hits, fills) — launches so far that walked from kept beam bounds, and that searched into a slot."""
@@ -587,6 +616,13 @@ class HipTracer:
         t0 = np.zeros(int(n.value), dtype=np.float32)
         self._check(self._lib.blok_hip_beam_cache_download(self._ctx, C.byref(action), C.byref(n), _ffi.ptr(t0), len(t0)))
         return int(action.value), t0
+
+    def beam_cache_last_action(self) -> int:
+        """What the latest rectangle launch did about the kept beam bounds: 0 it searched, 1 it searched into a slot, 2 it walked from a slot.
+        Waits for nothing."""
+        action = C.c_int(0)
+        self._check(self._lib.blok_hip_beam_cache_download(self._ctx, C.byref(action), None, None, 0))
+        return int(action.value)
 
     def set_beam_budget(self, max_node_visits: int):
         """Node visits a beam search may spend (0 = default); running out is answered conservatively, never changes a result."""

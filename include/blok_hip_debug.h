@@ -130,20 +130,33 @@ int blok_hip_set_joint_prefix_limit(blok_hip_ctx* ctx, uint32_t max_walk_waves);
  * those tiles — they are launched anyway and have nothing else to do — 0 = the pre-pass wave of the tile, 1 024 pixels each, which
  * puts ~120 MB of stores on the pre-pass's critical path (4K, 73 % sky).  Never changes a result. */
 int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk);
-/* The beam bounds of a view at rest: 1 (default) = a rectangle launch of the automatic form whose camera, rectangle,
+/* The beam bounds of a view at rest: 1 = a rectangle launch of the automatic form whose camera, rectangle,
  * beam settings and world are those of the launch before it, byte for byte, leaves its start parameters in one of four slots of the
- * context, and every later launch of that view walks from them without searching; 0 = every launch searches (the launches of a library
- * without the cache, one for one).  Either way the slots are emptied.  blok_hip_last_launch_kind goes on reporting the form the launch
- * policy chose for the device's state, also for a launch that walked from kept bounds (a plain trace launch).  Never changes a result. */
-int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int enabled);
+ * context, and every later launch of that view walks from them without searching; 2 (default) = as 1, and the view's K-th such launch
+ * (blok_hip_set_beam_refine_after) issues, behind its walk, one search per 8 x 8 wave tile of its live beam tiles, whose answers the
+ * launches after it walk from — a shorter walk, and none for a wave tile that is empty by its own search (only where the beam tile is a
+ * whole number, more than one, of wave tiles per side); 0 = every launch searches (the launches of a library without the cache, one for
+ * one).  In every case the slots are emptied.  blok_hip_last_launch_kind goes on reporting the form the launch policy chose for the
+ * device's state, also for a launch that walked from kept bounds (a plain trace launch).  Never changes a result. */
+int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode);
 /* Launches so far that walked from kept bounds (hits) and that searched into a slot (fills); either pointer may be null. */
 int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills);
+/* ... and that issued a view's finer searches behind their walk (at most one per fill; such a launch counts as a hit too). */
+int blok_hip_beam_cache_refines(const blok_hip_ctx* ctx, uint64_t* out_refines);
+/* K: a kept view's finer bounds are searched behind the walk of its K-th hit since it was filled (0 = the default, 16: what the searches
+ * cost over what a frame gains from them), so that a camera which rests only briefly pays nothing for them. */
+int blok_hip_set_beam_refine_after(blok_hip_ctx* ctx, uint32_t hits);
 /* Read-back for the tests that check the kept bounds as numbers: *out_action = what the latest rectangle launch did — 0 it searched (or ran
  * without a pre-pass), 1 it searched into a slot, 2 it walked from a slot without searching — *out_n_beams = its beam tiles (0 for action
  * 0), and with a buffer of `capacity` floats, for actions 1 and 2, that slot's start parameters, row-major as blok_hip_beam_prepass returns
  * them.  Waits for the device; launches nothing and changes nothing.  Any pointer may be null.  (blok_hip_beam_prepass itself never looks
  * at the slots: it always searches, whatever blok_hip_set_beam_cache says.) */
 int blok_hip_beam_cache_download(blok_hip_ctx* ctx, int* out_action, uint32_t* out_n_beams, float* out_t0_host_or_null, size_t capacity);
+/* The same for the finer bounds of that slot (blok_hip_beam_cache_download goes on returning the beam tiles' bounds): *out_state = 0 the
+ * latest rectangle launch had nothing to do with them, 1 it issued their searches behind its walk, 2 it walked from them; *out_n_tiles =
+ * the 8 x 8 wave tiles of its rectangle (0 for state 0), and for states 1 and 2 their start parameters, row-major: >= 3e38 where the wave
+ * tile's own search or its beam tile's found nothing, else the larger of the two bounds. */
+int blok_hip_beam_cache_download_fine(blok_hip_ctx* ctx, int* out_state, uint32_t* out_n_tiles, float* out_t0_host_or_null, size_t capacity);
 /* Node visits one beam search may spend (0 = the default, 256; searches average 35).  A search that runs out answers with the
  * lower bound over the cells it has not visited yet — valid, only less tight — never "none", so the frame is the same whatever
  * the budget (tests/test_gpu_parity.py runs with budgets of 1-64 visits against an unlimited search).  The pre-pass lasts as
