@@ -315,6 +315,10 @@ HIP_SYMBOLS = {
     "blok_hip_beam_cache_refines": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_set_beam_refine_after": (C.c_int, [C.c_void_p, C.c_uint32]),
     "blok_hip_beam_cache_download_fine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "blok_hip_pack_area": (C.c_uint32, []),
+    "blok_hip_set_beam_list_after": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "blok_hip_beam_cache_list_builds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "blok_hip_beam_cache_download_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "blok_hip_last_launch_kind": (C.c_int, [C.c_void_p]),
     "blok_hip_set_volume_layout": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_set_list_classes": (C.c_int, [C.c_void_p, C.c_int]),

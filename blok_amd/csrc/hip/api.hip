@@ -308,8 +308,7 @@ int blok_hip_create(blok_hip_ctx** out_ctx, int device_ordinal, uint32_t width, 
     ctx->device = device_ordinal; ctx->width = width; ctx->height = height;
     ctx->cu_count = prop.multiProcessorCount;
     if (const char* e = std::getenv("BLOK_FRAME_PARTS")) { const long v = std::atol(e); if (v >= 1 && v <= long(blok::kFrameParts)) ctx->frame_parts = uint32_t(v); }
-    if (const char* e = std::getenv("BLOK_FRAME_CHUNK")) { const long v = std::atol(e); if (v >= 1 && v <= 64) ctx->frame_chunk = uint32_t(v); }
-    if (ctx->ev_begin.create(hipEventDefault) != hipSuccess || ctx->ev_end.create(hipEventDefault) != hipSuccess) {
+    if (const char* e = std::getenv("BLOK_FRAME_CHUNK")) { const long v = std::atol(e); if (v >= 1 && v <= 64) ctx->frame_chunk = uint32_t(v); }    if (ctx->ev_begin.create(hipEventDefault) != hipSuccess || ctx->ev_end.create(hipEventDefault) != hipSuccess) {
         delete ctx;
         return set_error(nullptr, BLOK_ERR_HIP, "hipEventCreate failed");
     }

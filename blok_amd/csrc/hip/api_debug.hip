@@ -313,7 +313,53 @@ int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     ctx->beam_cache.enabled = mode != 0;
     ctx->beam_cache.refine = mode >= 2;
+    ctx->beam_cache.packed = mode >= 3;
     blok::beam_cache_clear(ctx->beam_cache.policy);      // off: every launch searches, as before there was a cache; on again: views are admitted afresh
+    if (!ctx->beam_cache.packed) return BLOK_OK;
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return beam_list_buffers(ctx);                       // (a blocking entry: the lists' buffers are allocated here, not by a launch)
+}
+
+int blok_hip_set_beam_list_after(blok_hip_ctx* ctx, uint32_t hits) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    ctx->beam_cache.policy.list_after = hits ? hits : blok::kBeamListAfter;
+    return BLOK_OK;
+}
+
+uint32_t blok_hip_pack_area(void) { return blok::kPackArea; }
+
+int blok_hip_beam_cache_list_builds(const blok_hip_ctx* ctx, uint64_t* out_builds) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (out_builds) *out_builds = ctx->beam_cache.list_builds;
+    return BLOK_OK;
+}
+
+// The packed list of the slot the latest rectangle launch counted for or walked packed from, as it lies in device memory once everything
+// enqueued has finished: the areas' stretches, the sorted table and its length, and the trips of the latest count launch.
+int blok_hip_beam_cache_download_list(blok_hip_ctx* ctx, int* out_state, uint32_t* out_n_areas, uint32_t* out_n_groups, uint32_t* out_list_host, size_t list_capacity,
+                                      uint32_t* out_table_host, size_t table_capacity, uint8_t* out_trips_host, size_t trips_capacity) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const auto& B = ctx->beam_cache;
+    if (out_state) *out_state = B.last_list;
+    if (out_n_areas) *out_n_areas = 0u;
+    if (out_n_groups) *out_n_groups = 0u;
+    if (!B.last_list) return BLOK_OK;
+    if (B.last_slot < 0 || static_cast<uint32_t>(B.last_slot) >= blok::kBeamCacheSlots || !B.slots[B.last_slot].d_list)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the latest launch's slot is gone (a resize)");
+    const auto& sl = B.slots[B.last_slot];
+    const uint32_t n_areas = sl.n_words / blok::kPackGroups;
+    const size_t entries = static_cast<size_t>(n_areas) * blok::kPackStretch, pixels = static_cast<size_t>(B.last_w) * B.last_h;
+    if (entries > B.list_capacity || sl.n_words > B.words_capacity || pixels > B.d_trips.capacity()) return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the list's buffers are gone (a resize)");
+    if ((out_list_host && list_capacity < entries) || (out_table_host && table_capacity < sl.n_words) || (out_trips_host && trips_capacity < pixels))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: output smaller than the list, the table or the rectangle");
+    if (out_n_areas) *out_n_areas = n_areas;
+    if (!out_n_groups && !out_list_host && !out_table_host && !out_trips_host) return BLOK_OK;      // the state alone: waits for nothing
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    if (out_n_groups) *out_n_groups = B.last_list == 2 ? sl.n_groups : std::min(B.h_groups[B.last_slot], sl.n_words);      // (a build just issued has finished by now)
+    if (out_list_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_list_host, sl.d_list, entries * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_table_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_table_host, sl.d_table, sl.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_trips_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_trips_host, B.d_trips, pixels, hipMemcpyDeviceToHost));
     return BLOK_OK;
 }
 

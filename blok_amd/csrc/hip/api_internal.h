@@ -164,7 +164,21 @@ struct blok_hip_ctx {
             blok::DeviceArray<float> d_beam, d_fine;
             Produced filled, refined;
             bool used = false;                              // filled at least once: launches that read it may be in flight
+            // the view's packed list and its group table (trace_kernels.h: the packed walk), built behind the count launch on its stream and
+            // adopted once `list_done` has been seen complete, so no reader ever waits; rebuilt only behind a refill, under the rule above
+            blok::DeviceArray<uint32_t> d_list, d_table;
+            uint32_t n_words = 0, n_groups = 0;             // the table's words as built (kPackGroups per area); its non-empty groups, as read from h_groups at adoption
         } slots[blok::kBeamCacheSlots];
+        bool packed = true;                                 // ... with the packed walk (mode 3)
+        blok::DeviceArray<uint8_t> d_trips;                 // the count launch's trips, a byte per pixel of the frame: one build at a time reads it
+        blok::DeviceArray<uint32_t> d_words;                // ... its table before the sort (kPackGroups words per area)
+        blok::DeviceBytes d_sort_temp; size_t sort_temp_bytes = 0;
+        blok::PinnedArray<uint32_t> h_groups;               // pinned, one word per slot: the table's length, written by the device before list_done
+        blok::Event list_done;                              // behind the build in flight (policy.building)
+        size_t list_capacity = 0, words_capacity = 0;       // entries per list; words per table
+        uint64_t list_builds = 0;                           // blok_hip_beam_cache_list_builds
+        int last_list = 0;                                  // the latest rectangle launch: 0 no list, 1 it counted and issued the build, 2 it walked packed
+        uint32_t last_w = 0, last_h = 0;                    // ... and its rectangle (blok_hip_beam_cache_download_list)
         size_t capacity = 0;                                // floats per buffer
         uint64_t hits = 0, fills = 0, refines = 0;          // blok_hip_beam_cache_counters, blok_hip_beam_cache_refines
         int last_action = 0, last_slot = -1; uint32_t last_n_beams = 0;      // the latest rectangle launch: 0 searched, 1 searched into last_slot, 2 walked from it (blok_hip_beam_cache_download)
@@ -291,6 +305,7 @@ int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, ui
 int beam_buffer(blok_hip_ctx* ctx, hipStream_t stream, size_t n, float** out);
 int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream);
 int beam_cache_buffers(blok_hip_ctx* ctx);              // at create / resize: the slots' buffers for the frame size (a blocking entry)
+int beam_list_buffers(blok_hip_ctx* ctx);               // ... and the packed walk's, when it is switched on (a blocking entry)
 void settle_beam_cache(blok_hip_ctx* ctx);               // behind a device-wide synchronisation: every slot's producer has finished
 int live_list(blok_hip_ctx* ctx, blok::TraceArgs& args, hipStream_t stream, uint32_t n_searches, uint32_t per_search);
 int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, uint32_t blocks, hipStream_t stream, uint32_t tiles_of_rank = 0,

@@ -380,7 +380,7 @@ static int list_costs(blok_hip_ctx* ctx, blok::TraceArgs& args, uint32_t wave_ti
 int beam_cache_buffers(blok_hip_ctx* ctx) {
     auto& B = ctx->beam_cache;
     const size_t want = static_cast<size_t>((ctx->width + 7u) / 8u) * ((ctx->height + 7u) / 8u);
-    if (B.capacity >= want) return BLOK_OK;
+    if (B.capacity >= want) return beam_list_buffers(ctx);      // (the same wave tiles can be more pixels: the lists' buffers count those)
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     B.capacity = 0;
     blok::beam_cache_clear(B.policy);
@@ -392,6 +392,35 @@ int beam_cache_buffers(blok_hip_ctx* ctx) {
         BLOK_HIP_TRY(ctx, sl.refined.done.create());
     }
     B.capacity = want;
+    B.list_capacity = 0;                                 // (the slots' lists went with the slots)
+    return beam_list_buffers(ctx);
+}
+
+// The packed walk's buffers (trace_kernels.h), for the whole frame — no rectangle has more areas — when the packed walk is switched on: by
+// blok_hip_create / _resize behind the buffers above, and by blok_hip_set_beam_cache; no launch allocates.  A device-wide wait, as above.
+int beam_list_buffers(blok_hip_ctx* ctx) {
+    auto& B = ctx->beam_cache;
+    if (!B.packed) return BLOK_OK;
+    const size_t areas = static_cast<size_t>((ctx->width + blok::kPackArea - 1u) / blok::kPackArea) * ((ctx->height + blok::kPackArea - 1u) / blok::kPackArea);
+    const size_t entries = areas * blok::kPackStretch, words = areas * blok::kPackGroups, pixels = static_cast<size_t>(ctx->width) * ctx->height;
+    if (B.list_capacity >= entries && B.words_capacity >= words && B.d_trips.capacity() >= pixels) return BLOK_OK;
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    B.list_capacity = 0; B.words_capacity = 0;
+    blok::beam_cache_clear(B.policy);
+    blok::beam_list_settle(B.policy);
+    const blok::FreeAfter waited = blok::FreeAfter::nothing();
+    for (auto& sl : B.slots) {
+        BLOK_HIP_TRY(ctx, sl.d_list.reserve(entries, waited));
+        BLOK_HIP_TRY(ctx, sl.d_table.reserve(words, waited));
+        sl.n_groups = 0;
+    }
+    BLOK_HIP_TRY(ctx, B.d_trips.reserve(pixels, waited));
+    BLOK_HIP_TRY(ctx, B.d_words.reserve(words, waited));
+    B.sort_temp_bytes = blok::pack_table_temp_bytes(static_cast<uint32_t>(words));
+    BLOK_HIP_TRY(ctx, B.d_sort_temp.reserve(B.sort_temp_bytes ? B.sort_temp_bytes : 16, waited));
+    BLOK_HIP_TRY(ctx, B.h_groups.reserve(blok::kBeamCacheSlots, waited));
+    BLOK_HIP_TRY(ctx, B.list_done.create());
+    B.list_capacity = entries; B.words_capacity = words;
     return BLOK_OK;
 }
 
@@ -431,10 +460,17 @@ static int wait_for_producer(blok_hip_ctx* ctx, blok_hip_ctx::BeamCache::Produce
 
 // Before a rectangle launch of a static form: does it search, search into a slot, or walk from a slot — and then from the slot's finer
 // bounds, or with their searches behind it?  Points args.beam at the slot's beam bounds and deals with whoever else uses it.
-static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan, blok::BeamRefinePlan* fine) {
+static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan, blok::BeamRefinePlan* fine,
+                                    blok::BeamListPlan* listed) {
     auto& B = ctx->beam_cache;
     *plan = blok::plan_beam_cache(B.policy, beam_key(ctx, mode, args));
     *fine = blok::plan_beam_refine(B.policy, *plan, B.refine && blok::beam_refine_applies(args) && blok::beam_refine_tiles(args) <= B.capacity);
+    // the packed list: a build that has finished is adopted here, whatever this launch is (its length was written before the event)
+    bool build_finished = false;
+    if (B.policy.building >= 0) { build_finished = hipEventQuery(B.list_done) == hipSuccess; (void)hipGetLastError(); }      // hipErrorNotReady is an answer, not a failure
+    *listed = blok::plan_beam_list(B.policy, *plan, *fine, B.packed && blok::pack_applies(args) && static_cast<size_t>(blok::pack_areas(args)) * blok::kPackStretch <= B.list_capacity &&
+                                   static_cast<size_t>(args.w) * args.h <= B.d_trips.capacity(), build_finished);
+    if (listed->adopted >= 0) { auto& got = B.slots[listed->adopted]; got.n_groups = std::min(B.h_groups[listed->adopted], got.n_words); }
     if (plan->action == blok::BeamAction::Search) return BLOK_OK;
     auto& sl = B.slots[plan->slot];
     if (plan->action == blok::BeamAction::Hit) {
@@ -551,9 +587,14 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     // there to be compared with, a rank's tiles and several frames per launch are left alone — that are not being captured.
     blok::BeamCachePlan cached{blok::BeamAction::Search, -1};
     blok::BeamRefinePlan finer{false, false};
+    blok::BeamListPlan listed{false, false, -1};
     if (ctx->beam_cache.enabled && rect && !frames && !capturing && static_form && ctx->launch_form == blok::kFormAuto && n_beams && n_beams <= ctx->beam_cache.capacity) {
-        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached, &finer);
-        if (rc != BLOK_OK) { if (finer.refine_now) blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, false); return rc; }
+        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached, &finer, &listed);
+        if (rc != BLOK_OK) {
+            if (finer.refine_now) blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, false);
+            if (listed.count_now) blok::beam_list_commit(ctx->beam_cache.policy, cached.slot, false);
+            return rc;
+        }
         // the searches that fill a slot write plain floats: the two-launch form, this once
         if (cached.action == blok::BeamAction::Fill && plan.kind == blok::LaunchKind::Joint) { plan.kind = blok::LaunchKind::TwoLaunches; ctx->last_launch_kind = static_cast<int>(plan.kind); }
     }
@@ -561,7 +602,28 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     ctx->beam_cache.last_slot = cached.slot; ctx->beam_cache.last_n_beams = n_beams;
     ctx->beam_cache.last_fine = finer.use_fine ? 2 : finer.refine_now ? 1 : 0;
     ctx->beam_cache.last_n_fine = ctx->beam_cache.last_fine ? blok::beam_refine_tiles(args) : 0u;
-    if (cached.action == blok::BeamAction::Hit) {
+    ctx->beam_cache.last_list = listed.use_list ? 2 : listed.count_now ? 1 : 0;
+    ctx->beam_cache.last_w = args.w; ctx->beam_cache.last_h = args.h;
+    if (cached.action == blok::BeamAction::Hit && (listed.use_list || listed.count_now)) {
+        // The packed walk, or the launch that measures for it.  Neither uses the view's order or its live prefix (the table's order stands in
+        // for both; the count launch walks every wave tile in a workgroup of its own, so that every listed pixel gets its count): the fill
+        // waves write the misses of the empty beam tiles and of the empty wave tiles and walk nothing.
+        auto& B = ctx->beam_cache;
+        auto& sl = B.slots[cached.slot];
+        blok::TraceArgs fill = args;
+        fill.order = nullptr; fill.rank_of = nullptr; fill.launched = 0u; fill.order_sx = fill.order_sy = 0u; fill.n_strip = 0u; fill.fallback_tiles = nullptr;
+        fill.miss_in_walk = 0u;
+        blok::launch_beam_fill(mode, fill, n_beams, sl.d_fine, stream);
+        if (listed.use_list) blok::launch_packed_walk(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, stream);
+        else {
+            blok::TraceArgs walk = fill;
+            walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
+            blok::launch_trace_count(walk, blocks, B.d_trips, stream);
+            // the build behind it: the areas' sorted stretches, then the table; its length goes to pinned memory in front of the event
+            sl.n_words = blok::pack_areas(args) * blok::kPackGroups; sl.n_groups = 0u;
+            blok::launch_pack_build(fill, sl.d_fine, B.d_trips, sl.d_list, B.d_words, stream);
+        }
+    } else if (cached.action == blok::BeamAction::Hit) {
         // no searches: the walk over the view's live prefix, from the kept bounds; in front of it, what the search waves do besides searching
         // (the miss pixels, unless the walk writes them; the wave tiles the prefix has no workgroup for) — last_launch_kind stays the policy's
         float* const d_fine = ctx->beam_cache.slots[cached.slot].d_fine;
@@ -602,10 +664,22 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
         if (marked == hipSuccess) { made.settled = false; made.producer = stream; made.n_waited = 0; ctx->beam_cache.refines += 1u; }
         else if (launch_error == hipSuccess) BLOK_HIP_TRY(ctx, marked);
     }
+    if (listed.count_now) {
+        auto& B = ctx->beam_cache;
+        auto& sl = B.slots[cached.slot];
+        hipError_t built = launch_error;
+        if (built == hipSuccess) built = blok::launch_pack_table_sort(B.d_words, sl.d_table, B.d_sort_temp, B.sort_temp_bytes, sl.n_words, B.h_groups + cached.slot, stream);
+        if (built == hipSuccess) built = hipEventRecord(B.list_done, stream);
+        blok::beam_list_commit(B.policy, cached.slot, built == hipSuccess);      // (a list nobody can see finished is not used)
+        if (built == hipSuccess) B.list_builds += 1u;
+        else if (launch_error == hipSuccess) BLOK_HIP_TRY(ctx, built);
+    }
     BLOK_HIP_TRY(ctx, launch_error);
     if (cached.action == blok::BeamAction::Fill) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->beam_cache.slots[cached.slot].filled.done, stream));
     if (ctx->timing && !capturing) { BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_end, stream)); ctx->timed = true; }
     if (args.fallback_tiles) BLOK_HIP_TRY(ctx, hipMemcpyAsync(ctx->order.h_fallback, ctx->order.d_fallback, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    // (a packed launch leaves no clocks: a re-sort behind it would sort what the last one sorted — the order keeps its state and is not re-made)
+    if (listed.use_list) order_plan.start_sort = false;
     if (orderable) { const int rc = order_after_launch(ctx, args, blocks, n_beams, stream, order_plan); if (rc != BLOK_OK) return rc; }
     if (facts.has_beam && !capturing) return note_frame_launch(ctx, stream);          // (behind the sort, if one was started: it belongs to this launch)
     return BLOK_OK;

@@ -69,6 +69,24 @@ enum class BeamRefine : uint8_t {
 constexpr uint32_t kBeamRefineAfter = 16;
 struct BeamRefinePlan { bool refine_now, use_fine; };
 
+// A refined slot's packed list: the view's walked pixels regrouped, 64 to a wave, by the trips their walks took (trace_kernels.h: the packed
+// walk).  A view at rest walks the very same rays every frame, so their lengths are measured ONCE: the slot's N-th hit from the finer bounds
+// (N = list_after) walks with a counting kernel and issues the build behind it; the first later launch that finds the build finished adopts
+// the list, and the slot's hits walk packed from then on.  Any assignment of pixels to lanes writes the same frame: the list is scheduling
+// state and can be stale (another jitter under the same key) but never wrong — as long as it lists the pixels of THIS key's finer bounds,
+// which is why it goes whenever they go.  One build is in flight at a time (it uses buffers of the context), whichever slot it is for.
+enum class BeamList : uint8_t {
+    None = 0,                                  // no list
+    Now = 1,                                   // the launch that was just planned counts and issues the build (beam_list_commit ends this state)
+    Building = 2,                              // the build is on its way, on the stream of the launch that counted
+    Ready = 3,                                 // adopted: hits walk packed
+};
+// The default N, decided as K was: what the count launch and the build cost once over what a packed frame gains, rounded up to a power of
+// two.  Measured at 4K over 1024^3 (profiles/packed_walk_ab.txt): the count launch takes 70 us (pose A) and 25 us (pose B) longer than the
+// view's usual walk, the build 39 to 43 us and the table's sort about 54 us; a frame in flight gains 13 us and 7 to 9 us: ratios 12 and 14 to 17 -> 16.
+constexpr uint32_t kBeamListAfter = 16;
+struct BeamListPlan { bool count_now, use_list; int adopted; };      // adopted: the slot whose finished build this launch adopted (read its size now), or -1
+
 struct BeamCachePolicy {
     BeamKey key[kBeamCacheSlots];
     bool valid[kBeamCacheSlots];
@@ -79,11 +97,29 @@ struct BeamCachePolicy {
     BeamRefine refine[kBeamCacheSlots];        // reset by every fill (a refill, an eviction) and by beam_cache_clear
     uint32_t hits_since_fill[kBeamCacheSlots];
     uint32_t refine_after = kBeamRefineAfter;  // K (a debug setter: the tests need 1); kept by beam_cache_clear
+    BeamList list[kBeamCacheSlots];            // reset with `refine`: a slot keeps its list exactly as long as it keeps its finer bounds
+    uint32_t fine_hits[kBeamCacheSlots];       // hits that walked from the finer bounds since they were made
+    uint32_t list_after = kBeamListAfter;      // N (a debug setter); kept by beam_cache_clear
+    int building = -1;                         // the slot the build in flight writes (-1: none is in flight)
+    bool building_stale = false;               // ... and that slot has been refilled or cleared since: the build finishes into a list nobody adopts
 };
 
+// The slot's finer bounds are gone (a refill, an eviction, a clear): its list goes with them.  A build still in flight for it stays "in
+// flight" — it is writing the slot's buffers, and the context's — until a launch sees it finished.
+inline void beam_list_drop(BeamCachePolicy& s, int slot) {
+    s.list[slot] = BeamList::None; s.fine_hits[slot] = 0u;
+    if (s.building == slot) s.building_stale = true;
+}
+
 inline void beam_cache_clear(BeamCachePolicy& s) {
-    for (int k = 0; k < kBeamCacheSlots; ++k) { s.valid[k] = false; s.last_use[k] = 0u; s.refine[k] = BeamRefine::None; s.hits_since_fill[k] = 0u; }
+    for (int k = 0; k < kBeamCacheSlots; ++k) { s.valid[k] = false; s.last_use[k] = 0u; s.refine[k] = BeamRefine::None; s.hits_since_fill[k] = 0u; beam_list_drop(s, k); }
     s.have_last = false;
+}
+
+// Behind a wait for the whole device: no build is in flight any more (and a list that had not been adopted by then is not kept).
+inline void beam_list_settle(BeamCachePolicy& s) {
+    if (s.building >= 0 && s.building < kBeamCacheSlots && s.list[s.building] == BeamList::Building) s.list[s.building] = BeamList::None;
+    s.building = -1; s.building_stale = false;
 }
 
 // Admission: a view is cached when the same key arrives a second time IN A ROW — that launch still searches, into a slot — and hits
@@ -105,6 +141,7 @@ inline BeamCachePlan plan_beam_cache(BeamCachePolicy& s, const BeamKey& k) {
     if (target < 0) { target = 0; for (int i = 1; i < kBeamCacheSlots; ++i) if (s.last_use[i] < s.last_use[target]) target = i; }
     s.key[target] = k; s.valid[target] = true; s.last_use[target] = s.serial;
     s.refine[target] = BeamRefine::None; s.hits_since_fill[target] = 0u;
+    beam_list_drop(s, target);
     return {BeamAction::Fill, target};
 }
 
@@ -128,6 +165,34 @@ inline void beam_refine_commit(BeamCachePolicy& s, int slot, bool issued) {
     if (slot < 0 || slot >= kBeamCacheSlots || s.refine[slot] != BeamRefine::Now) return;
     s.refine[slot] = issued ? BeamRefine::Done : BeamRefine::None;
     if (!issued) s.hits_since_fill[slot] = 0u;
+}
+
+// Behind plan_beam_refine, for the same launch.  build_finished: the event behind the build in flight has been seen complete (asked only
+// while s.building >= 0) — then the build is over whoever launches, and its slot, unless it was dropped meanwhile, has its list from this
+// launch on.  Then: does this launch walk packed, or count and build?  Only a hit that walks from the finer bounds can do either; "count
+// now" is said once per set of finer bounds, on its N-th such hit or the first after it at which no other build is in flight.
+// eligible: the packed walk applies to the launch's geometry and is switched on.
+inline BeamListPlan plan_beam_list(BeamCachePolicy& s, const BeamCachePlan& p, const BeamRefinePlan& f, bool eligible, bool build_finished) {
+    BeamListPlan out{false, false, -1};
+    if (s.building >= 0 && build_finished) {
+        if (!s.building_stale && s.building < kBeamCacheSlots && s.list[s.building] == BeamList::Building) { s.list[s.building] = BeamList::Ready; out.adopted = s.building; }
+        s.building = -1; s.building_stale = false;
+    }
+    if (p.action != BeamAction::Hit || p.slot < 0 || p.slot >= kBeamCacheSlots || !f.use_fine || !eligible) return out;
+    if (s.list[p.slot] == BeamList::Ready) { out.use_list = true; return out; }
+    if (s.list[p.slot] != BeamList::None) return out;
+    if (s.fine_hits[p.slot] != UINT32_MAX) s.fine_hits[p.slot] += 1u;
+    if (s.building < 0 && s.fine_hits[p.slot] >= (s.list_after ? s.list_after : 1u)) { s.list[p.slot] = BeamList::Now; out.count_now = true; }
+    return out;
+}
+
+// The launch that was told "count now" has issued its build and the event behind it (issued), or could not: the slot stays without a list
+// and is asked again N hits later.
+inline void beam_list_commit(BeamCachePolicy& s, int slot, bool issued) {
+    if (slot < 0 || slot >= kBeamCacheSlots || s.list[slot] != BeamList::Now) return;
+    s.list[slot] = issued ? BeamList::Building : BeamList::None;
+    if (issued) { s.building = slot; s.building_stale = false; }
+    else s.fine_hits[slot] = 0u;
 }
 
 }  // namespace blok

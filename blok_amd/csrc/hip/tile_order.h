@@ -25,5 +25,10 @@ size_t tile_order_class_sort_bytes_max(uint32_t n_tiles);      // ... for any gr
 hipError_t launch_tile_order_class_sort(const uint32_t* cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t radius, void* scratch, uint32_t* order_out, uint32_t* rank_of,
                                         uint32_t* live_out, const float* beam, const unsigned long long* slots, uint32_t serial, uint32_t n_beams, float* depth_out,
                                         hipStream_t stream);
+// The group table of a packed list (trace_kernels.h: the packed walk): `words_in` holds one word per group slot — (largest trip count
+// + 1) << kPackKeyShift | group index, 0 for an empty slot; table_out = the words in descending order (heaviest group first, the empty
+// slots last) and *n_groups_out = how many of them are not empty.  n_groups_out may be pinned host memory.
+size_t pack_table_temp_bytes(uint32_t n);
+hipError_t launch_pack_table_sort(const uint32_t* words_in, uint32_t* table_out, void* temp, size_t temp_bytes, uint32_t n, uint32_t* n_groups_out, hipStream_t stream);
 }  // namespace blok
 #endif

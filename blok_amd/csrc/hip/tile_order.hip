@@ -197,6 +197,32 @@ hipError_t launch_tile_order_class_sort(const uint32_t* cost, uint32_t tiles_x, 
     return hipGetLastError();
 }
 
+namespace {
+// descending: the non-empty words are a prefix; its last one reports its length
+__global__ __launch_bounds__(256) void pack_table_finish_kernel(const uint32_t* table, uint32_t n, uint32_t* n_groups_out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const bool live = table[i] != 0u;
+    if (live && (i + 1u == n || table[i + 1u] == 0u)) *n_groups_out = i + 1u;
+    if (i == 0u && !live) *n_groups_out = 0u;
+}
+}  // namespace
+
+size_t pack_table_temp_bytes(uint32_t n) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortKeysDescending(nullptr, bytes, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<int>(n), 0, 32);
+    return bytes;
+}
+
+// The whole word is the key: groups of equal weight come out by descending index, the same table on every build.
+hipError_t launch_pack_table_sort(const uint32_t* words_in, uint32_t* table_out, void* temp, size_t temp_bytes, uint32_t n, uint32_t* n_groups_out, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    const hipError_t e = hipcub::DeviceRadixSort::SortKeysDescending(temp, temp_bytes, words_in, table_out, static_cast<int>(n), 0, 32, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pack_table_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, table_out, n, n_groups_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_tile_order_finish(const uint32_t* order, const uint32_t* cost_sorted, uint32_t n, uint32_t* rank_of, uint32_t* live_out, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(order_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, order, cost_sorted, n, rank_of, live_out);
     return hipGetLastError();

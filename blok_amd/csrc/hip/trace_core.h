@@ -250,8 +250,10 @@ BLOK_DEV void walk_enter(const TraceArgs& A, const WalkRay& R, float tmin, float
 // kCapped: at most `cap` trips; a lane cut off leaves with `walking` still set and tCur = the parameter at which it entered the cell it stands in —
 // a walk of the same ray from the root with tmin = that tCur reports what this one would have (every voxel before it has an empty clipped
 // interval, every one after it is entered at or after tCur: the argument of the beam pre-pass).  path_core.h: the bounce rounds' tail pool.
-template <bool kCapped = false>
-BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, WalkState& s, uint4* stk, [[maybe_unused]] const uint32_t cap = 0u) {
+// kCount: the trips this lane made go to *n_trips (0 for a lane that had nothing to walk): what the packed list of a view at rest is sorted by.
+template <bool kCapped = false, bool kCount = false>
+BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, WalkState& s, uint4* stk, [[maybe_unused]] const uint32_t cap = 0u,
+                        [[maybe_unused]] uint32_t* n_trips = nullptr) {
     // Invariant: tCur starts at max(world entry, tmin) and never decreases — a cell's far planes are never
     // before the plane through which it was entered (T is monotone along each axis and the start cell of a
     // node only counts planes with T <= tCur as crossed) — so max(tCur, tmin) == tCur throughout and the
@@ -272,7 +274,7 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
     bool go = s.walking;
     [[maybe_unused]] uint32_t trips = 0u;
     while (kCapped ? (go && trips < cap) : go) {
-        if constexpr (kCapped) ++trips;
+        if constexpr (kCapped || kCount) ++trips;
         BLOK_STAT(0, shift >> 1);
         bit = (digit2(__float_as_uint(fx), shift) | (digit2(__float_as_uint(fy), shift) << 2) | (digit2(__float_as_uint(fz), shift) << 4)) ^ R.mirror;
         const bool occupied = mask_bit(node, bit);
@@ -328,6 +330,7 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
     }
     s.fx = fx; s.fy = fy; s.fz = fz; s.tCur = tCur; s.bit = bit; s.node = node; s.found = found;
     if constexpr (kCapped) s.walking = go; else s.walking = false;
+    if constexpr (kCount) *n_trips = trips;
 }
 
 // The reported voxel of a finished walk: intersect.rint:136-141, hit.rchit:58-74.  r: the ray itself (origin, direction).
@@ -580,7 +583,9 @@ BLOK_DEV HitInfo walk(const TraceArgs& A, const RayIn& r, uint4* stk) {
 }
 
 // As walk(), the wave's rays entered together (walk_enter_wave): for the primary rays of a wave tile.  Every active lane of the wave must call it.
-BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk) {
+// kCount: the loop's trips to *n_trips (walk_loop).
+template <bool kCount = false>
+BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk, [[maybe_unused]] uint32_t* n_trips = nullptr) {
 #ifdef BLOK_TRACE_HOST_HARNESS
     return walk(A, r, stk);
 #else
@@ -590,16 +595,26 @@ BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk) {
     const WalkRay R = walk_ray(A, r.ox, r.oy, r.oz, safe_inv(r.dx), safe_inv(r.dy), safe_inv(r.dz));
     WalkState s;
     if (!walk_enter_wave(A, r, R, stk, s)) walk_enter(A, R, r.tmin, r.tmax, s);
-    walk_loop(A, R, r.tmax, s, stk);
+    if constexpr (kCount) {
+        // the count is the walk's FROM THE ROOT: the descents the wave made together (walk_enter_wave leaves the lane at level s.lvl, where the
+        // walk from the root arrives after levels - 1 - s.lvl trips; walk_enter leaves it at levels - 1) are trips of it like any other
+        const uint32_t shared = A.levels - 1u - s.lvl;
+        walk_loop<false, true>(A, R, r.tmax, s, stk, 0u, n_trips);
+        *n_trips += shared;
+    } else walk_loop(A, R, r.tmax, s, stk);
     if (s.found) out = walk_hit(A, r, R, s);
     return out;
 #endif
 }
 
 // Walks one ray and writes its 16-byte record and/or RGBA8 pixel.  kWave: through walk_wave (the coherent primary rays of a wave tile).
-template <bool kWave = false>
-BLOK_DEV void trace_one(const TraceArgs& A, const RayIn& r, uint4* stk, const Sink& dst) {
-    const HitInfo h = kWave ? walk_wave(A, r, stk) : walk(A, r, stk);
+// kCount (with kWave): the walk's trips, saturated at 255, go to *trips_out.
+template <bool kWave = false, bool kCount = false>
+BLOK_DEV void trace_one(const TraceArgs& A, const RayIn& r, uint4* stk, const Sink& dst, [[maybe_unused]] uint8_t* trips_out = nullptr) {
+    [[maybe_unused]] uint32_t n_trips = 0u;
+    static_assert(kWave || !kCount, "trips are counted for the primary rays of a wave tile");
+    const HitInfo h = kCount ? walk_wave<kCount>(A, r, stk, &n_trips) : (kWave ? walk_wave(A, r, stk) : walk(A, r, stk));
+    if constexpr (kCount) *trips_out = static_cast<uint8_t>(n_trips < 255u ? n_trips : 255u);
     if (!h.found) { write_miss(dst); return; }
     uint4 rec;
     rec.x = __float_as_uint(h.t);

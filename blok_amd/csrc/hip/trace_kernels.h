@@ -291,6 +291,32 @@ void launch_beam_fill(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles
 uint32_t beam_refine_tiles(const TraceArgs& args);
 bool beam_refine_applies(const TraceArgs& args);
 void launch_beam_refine(const TraceArgs& args, float* fine, hipStream_t stream);
+// ---- the packed walk of a view at rest (beam_cache.h: BeamList) ---------------------------------------------------------------------------
+// A wave costs its longest ray, and the 64 rays of an 8 x 8 wave tile are not equally long.  A view at rest walks the same rays every
+// frame, so one launch measures them (launch_trace_count: the walk of launch_trace, every lane's trips of the walk from the root as a byte per pixel of the
+// rectangle, saturated at 255), and launch_pack_build regroups them: per area of kPackArea x kPackArea pixels of the rectangle, the pixels
+// of the wave tiles with a finite finer bound — the pixels the walk is responsible for; none outside the rectangle — sorted by descending
+// trip count, stable in pixel order (wave tile by wave tile, row by row inside one), as 32-bit entries (x | y << 16, in the rectangle) in the area's stretch of kPackArea^2
+// entries of `list`, padded with kPackPad to whole groups of 64.  words[area * kPackGroups + g] = (the largest count of group g + 1) <<
+// kPackKeyShift | its index, 0 for a group without entries (tile_order.h sorts them into the table).  launch_packed_walk then walks one
+// group per wave in table order: a lane reads its entry (a padding lane leaves), its start parameter from the finer bound of its pixel's
+// wave tile, and writes its record and pixel — the same bytes whichever wave a pixel is walked in.
+// The area is the builder's one constant.  64 pixels (scripts/packed_walk_estimate.py: 0.74 against 0.77 of today's wave trips in pose A,
+// 0.84 against 0.86 in pose B) was measured against 32 with a library built with -DBLOK_PACK_AREA=64 (profiles/packed_walk_ab.txt): 2.5 %
+// fewer vector instructions and a headline median 2.7 % higher, but its worst run only 0.1 % above 32's best (32's runs spread 1.4 %,
+// 64's 3.2 %): by the rule that made the list the default that is no established gain; -1.3 % for pose A with one frame in flight, the one
+// case the packed walk already loses; no difference in pose B either way.  32 stays.
+#ifndef BLOK_PACK_AREA
+#define BLOK_PACK_AREA 32
+#endif
+static_assert(BLOK_PACK_AREA == 16 || BLOK_PACK_AREA == 32 || BLOK_PACK_AREA == 64, "whole wave tiles, and a stretch a workgroup can sort");
+constexpr uint32_t kPackArea = BLOK_PACK_AREA, kPackStretch = kPackArea * kPackArea, kPackGroups = kPackStretch / 64u, kPackPad = 0xFFFFFFFFu;
+constexpr uint32_t kPackKeyShift = 20u;                               // a table word's group index: the bits below
+uint32_t pack_areas(const TraceArgs& args);                           // areas of the rectangle
+bool pack_applies(const TraceArgs& args);                             // the geometry fits the entries and the table's words
+void launch_trace_count(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, hipStream_t stream);      // Rect; args as for launch_trace
+void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* trips, uint32_t* list, uint32_t* words, hipStream_t stream);
+void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

@@ -188,8 +188,10 @@ __device__ __forceinline__ bool list_await(unsigned long long* slot, unsigned lo
 
 // Workgroup `block` of a launch of `grid` workgroups (the kernels below differ in where the arguments come from).  kListed: the block
 // comes from the frame's live list together with its start parameter (list launches): no order, no beam lookup, no cost.
-template <RayMode MODE, bool kListed = false>
-__device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t block, const uint32_t grid, uint4* lds_stack, const float listed_t0 = 0.0f) {
+// kCount (trace_count_kernel): every lane that walks also leaves its trips in trips[its pixel of the rectangle].
+template <RayMode MODE, bool kListed = false, bool kCount = false>
+__device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t block, const uint32_t grid, uint4* lds_stack, const float listed_t0 = 0.0f,
+                                            [[maybe_unused]] uint8_t* trips = nullptr) {
     const uint32_t tid = threadIdx.x;
     uint4* stk = lds_stack + tid;
 
@@ -305,7 +307,8 @@ __device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t b
 #ifndef BLOK_WAVE_START
 #define BLOK_WAVE_START 1
 #endif
-        trace_one<BLOK_WAVE_START != 0>(A, r, stk, sink);
+        if constexpr (kCount) trace_one<true, true>(A, r, stk, sink, trips + out_index);
+        else trace_one<BLOK_WAVE_START != 0>(A, r, stk, sink);
         if (cost_slot && tid == 0) *cost_slot = max(static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - clock0), 256u);     // it walked: any key >= 256 clocks counts as live in the next order
     }
 }
@@ -314,6 +317,12 @@ template <RayMode MODE>
 __global__ __launch_bounds__(kBlock) void trace_kernel(const TraceArgs A) {
     extern __shared__ uint4 lds_stack[];       // [levels-1][kBlock]
     trace_block<MODE>(A, blockIdx.x, gridDim.x, lds_stack);
+}
+
+// The rectangle walk that also counts: once per view at rest, for its packed list (trace_kernels.h).  Same frame, same workgroups.
+__global__ __launch_bounds__(kBlock) void trace_count_kernel(const TraceArgs A, uint8_t* trips) {
+    extern __shared__ uint4 lds_stack[];
+    trace_block<RayMode::Rect, false, true>(A, blockIdx.x, gridDim.x, lds_stack, 0.0f, trips);
 }
 
 // The arguments of frame f of a several-frame launch: its camera, its slice of the outputs and of the beam buffer.
@@ -523,6 +532,94 @@ __global__ __launch_bounds__(64) void beam_refine_kernel(const TraceArgs, float*
         t0 = own >= kBeamNone ? kBeamNone : fmaxf(own, coarse);
     }
     if (lane == 0) fine[tile] = t0;
+}
+
+// ---- the packed walk of a view at rest (trace_kernels.h; beam_cache.h: BeamList) ------------------------------------------------------------
+// The build, once per view: one workgroup per area, a thread per pixel of it (an area of more than 1 024 pixels: in rounds).  A counting
+// sort by key = 255 - trips (descending trips), stable in pixel order — wave tile by wave tile, row by row inside one: rays of equal length
+// stay beside their neighbours, whose walks visit the same nodes in the same phase.  A pixel's place is the pixels of smaller keys, plus
+// those of its key in the wave tiles before its own, plus those of its key in the lanes before it.
+constexpr uint32_t kPackThreads = kPackStretch < 1024u ? kPackStretch : 1024u;
+__global__ __launch_bounds__(kPackThreads) void pack_build_kernel(const uint8_t* trips, const float* fine, const uint32_t w, const uint32_t h, uint32_t* list, uint32_t* words) {
+    constexpr uint32_t kChunks = kPackStretch / 64u, kWaves = kPackThreads / 64u, kRounds = kChunks / kWaves, kKeys = 256u, kTilesX = kPackArea / kWaveW;
+    static_assert(kPackStretch % kPackThreads == 0u && kPackStretch <= 65535u && kPackGroups <= kPackThreads && kPackThreads >= kKeys, "the counts fit 16 bits; a thread per key and per group");
+    __shared__ uint16_t in_chunk[kChunks][kKeys];                      // pixels of a key in a wave tile; then: in the wave tiles before it
+    __shared__ uint32_t key_base[kKeys + 1u];                          // pixels of smaller keys; [kKeys]: listed pixels of the area
+    const uint32_t p = threadIdx.x, lane = p & 63u, wave = p >> 6;
+    const uint32_t areas_x = (w + kPackArea - 1u) / kPackArea;
+    uint32_t rx[kRounds], ry[kRounds], count[kRounds], rank[kRounds];
+    bool valid[kRounds], any = false;
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t chunk = r * kWaves + wave;
+        rx[r] = (blockIdx.x % areas_x) * kPackArea + (chunk % kTilesX) * kWaveW + lane % kWaveW;
+        ry[r] = (blockIdx.x / areas_x) * kPackArea + (chunk / kTilesX) * kWaveH + lane / kWaveW;
+        valid[r] = rx[r] < w && ry[r] < h && fine[(ry[r] / kWaveH) * ((w + kWaveW - 1u) / kWaveW) + rx[r] / kWaveW] < kBeamNone;
+        count[r] = valid[r] ? trips[static_cast<size_t>(ry[r]) * w + rx[r]] : 0u;
+        rank[r] = 0u;
+        any = any || valid[r];
+    }
+    for (uint32_t i = p; i < kChunks * kKeys; i += kPackThreads) (&in_chunk[0][0])[i] = 0u;
+    if (!__syncthreads_or(any)) {                                      // nothing to list here (most of a frame with sky in it): no group
+        if (p < kPackGroups) words[blockIdx.x * kPackGroups + p] = 0u;
+        return;
+    }
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t key = 255u - count[r];
+        unsigned long long remaining = __ballot(valid[r]);
+        while (remaining) {                                            // one round per key present in the wave tile
+            const uint32_t k = __builtin_amdgcn_readlane(key, static_cast<int>(__builtin_ctzll(remaining)));
+            const unsigned long long m = __ballot(valid[r] && key == k);
+            if (valid[r] && key == k) rank[r] = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+            if (lane == 0u) in_chunk[r * kWaves + wave][k] = static_cast<uint16_t>(__builtin_popcountll(m));
+            remaining &= ~m;
+        }
+    }
+    __syncthreads();
+    if (p < kKeys) {
+        uint32_t sum = 0u;
+        for (uint32_t v = 0; v < kChunks; ++v) { const uint32_t c = in_chunk[v][p]; in_chunk[v][p] = static_cast<uint16_t>(sum); sum += c; }
+        key_base[p] = sum;
+    }
+    __syncthreads();
+    if (wave == 0u) {                                                  // exclusive scan over the keys: four to a lane, then over the lanes
+        static_assert(kKeys == 4u * 64u, "four keys per lane");
+        uint32_t c[4], mine = 0u;
+        for (uint32_t j = 0; j < 4u; ++j) { c[j] = key_base[lane * 4u + j]; mine += c[j]; }
+        uint32_t incl = mine;
+        for (uint32_t off = 1u; off < 64u; off <<= 1) { const uint32_t u = __shfl_up(incl, off); if (lane >= off) incl += u; }
+        uint32_t before = incl - mine;
+        for (uint32_t j = 0; j < 4u; ++j) { key_base[lane * 4u + j] = before; before += c[j]; }
+        if (lane == 63u) key_base[kKeys] = incl;
+    }
+    __syncthreads();
+    const uint32_t n = key_base[kKeys], padded = (n + 63u) & ~63u;      // n <= kPackStretch, a multiple of 64: the stretch holds the padding
+    uint32_t* const stretch = list + static_cast<size_t>(blockIdx.x) * kPackStretch;
+    for (uint32_t r = 0; r < kRounds; ++r)
+        if (valid[r]) {
+            const uint32_t key = 255u - count[r];
+            const uint32_t at = key_base[key] + in_chunk[r * kWaves + wave][key] + rank[r];
+            stretch[at] = rx[r] | (ry[r] << 16);
+            // the first entry of a group carries the group's largest count
+            if ((at & 63u) == 0u) words[blockIdx.x * kPackGroups + (at >> 6)] = ((count[r] + 1u) << kPackKeyShift) | (blockIdx.x * kPackGroups + (at >> 6));
+        }
+    if (n + p < padded) stretch[n + p] = kPackPad;
+    if (p < kPackGroups && p * 64u >= n) words[blockIdx.x * kPackGroups + p] = 0u;
+}
+
+// One wave per group of the list, heaviest first.  Nothing here is collective before a padding lane has left.
+__global__ __launch_bounds__(kBlock) void packed_walk_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table) {
+    static_assert(kBlock == 64, "one wave per group");
+    extern __shared__ uint4 lds_stack[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
+    const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+    const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
+    if (entry == kPackPad || rx >= A.w || ry >= A.h) return;          // (the build lists pixels of the rectangle only)
+    const float t0 = fine[(ry / kWaveH) * ((A.w + kWaveW - 1u) / kWaveW) + rx / kWaveW];
+    const size_t at = static_cast<size_t>(ry) * A.w + rx;
+    RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+    r.tmin = fmaxf(r.tmin, t0);
+    trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
 }
 
 // ---- joint launch: the pre-pass waves and the walk waves in ONE grid, statically ------------------------------------------
@@ -1242,6 +1339,29 @@ void launch_beam_refine(const TraceArgs& args, float* fine, hipStream_t stream) 
     const uint32_t n = beam_refine_tiles(args);
     if (n == 0 || !fine || !args.beam || args.beam_slots || !beam_refine_applies(args)) return;
     hipLaunchKernelGGL(beam_refine_kernel, dim3(n), dim3(64), 0, stream, args, fine);
+}
+
+uint32_t pack_areas(const TraceArgs& a) { return ((a.w + kPackArea - 1u) / kPackArea) * ((a.h + kPackArea - 1u) / kPackArea); }
+
+bool pack_applies(const TraceArgs& a) {
+    // an entry holds x and y in 16 bits each (all ones: padding), a table word a group index below kPackKeyShift
+    return kBlock == 64 && kWaveW == 8u && kWaveH == 8u && a.w && a.h && a.w < 0xFFFFu && a.h < 0xFFFFu &&
+           static_cast<uint64_t>(pack_areas(a)) * kPackGroups <= (1u << kPackKeyShift);
+}
+
+void launch_trace_count(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, hipStream_t stream) {
+    if (n_blocks == 0 || !trips) return;
+    hipLaunchKernelGGL(trace_count_kernel, dim3(n_blocks), dim3(kBlock), frame_lds_bytes(args), stream, args, trips);
+}
+
+void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* trips, uint32_t* list, uint32_t* words, hipStream_t stream) {
+    if (!pack_applies(args) || !fine || !trips || !list || !words) return;
+    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, trips, fine, args.w, args.h, list, words);
+}
+
+void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream) {
+    if (n_groups == 0 || !pack_applies(args) || !fine || !list || !table) return;
+    hipLaunchKernelGGL(packed_walk_kernel, dim3(n_groups), dim3(kBlock), frame_lds_bytes(args), stream, args, fine, list, table);
 }
 
 size_t frame_lds_bytes(const TraceArgs& args) { return static_cast<size_t>(args.levels > 1 ? args.levels - 1 : 1) * kBlock * sizeof(uint4); }

@@ -567,13 +567,51 @@ class HipTracer:
         self._check(self._lib.blok_hip_set_miss_writer(self._ctx, 1 if in_walk else 0))
 
     def set_beam_cache(self, mode):
-        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 2 or True (default) = and, from the view's K-th
-        hit on, a finer bound per wave tile; 1 = the beam tiles' bounds alone; 0 or False = every launch searches.  Never changes a result."""
-        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (2 if mode else 0) if isinstance(mode, bool) else int(mode)))
+        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 3 or True (default) = with, from the view's K-th
+        hit on, a finer bound per wave tile, and then its rays regrouped by measured length (the packed walk); 2 = without the packed walk;
+        1 = the beam tiles' bounds alone; 0 or False = every launch searches.  Never changes a result."""
+        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (3 if mode else 0) if isinstance(mode, bool) else int(mode)))
 
     def set_beam_refine_after(self, hits: int):
         """K: the hit of a kept view behind whose walk its finer bounds are searched, once (0 = the default; blok_hip_debug.h)."""
         self._check(self._lib.blok_hip_set_beam_refine_after(self._ctx, hits))
+
+    def set_beam_list_after(self, hits: int):
+        """N: the launch from the finer bounds that counts a kept view's rays for its packed list (0 = the default; blok_hip_debug.h)."""
+        self._check(self._lib.blok_hip_set_beam_list_after(self._ctx, hits))
+
+    def beam_cache_list_builds(self) -> int:
+        """Diagnostic: launches so far that counted and issued the build of a view's packed list."""
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_beam_cache_list_builds(self._ctx, C.byref(n)))
+        return int(n.value)
+
+    def pack_area(self) -> int:
+        """Side of the packed list's areas in pixels (blok_hip_debug.h: blok_hip_pack_area)."""
+        return int(self._lib.blok_hip_pack_area())
+
+    def beam_cache_list_state(self) -> int:
+        """What the latest rectangle launch had to do with a packed list: 0 nothing, 1 it counted and issued the build, 2 it walked packed.
+        Waits for nothing."""
+        state = C.c_int(0)
+        self._check(self._lib.blok_hip_beam_cache_download_list(self._ctx, C.byref(state), None, None, None, 0, None, 0, None, 0))
+        return int(state.value)
+
+    def beam_cache_list(self, w: int, h: int):
+        """(state, n_groups, entries, table, trips) of the latest rectangle launch's packed list (blok_hip_debug.h:
+        blok_hip_beam_cache_download_list), for its rectangle of w x h pixels: entries (areas, area^2) uint32, table (areas * area^2 / 64,) uint32,
+        trips (h, w) uint8; None for state 0."""
+        state, areas, groups = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.blok_hip_beam_cache_download_list(self._ctx, C.byref(state), C.byref(areas), None, None, 0, None, 0, None, 0))
+        if not state.value:
+            return None
+        stretch = self.pack_area() ** 2                  # trace_kernels.h: kPackStretch entries and kPackGroups = stretch / 64 words per area
+        entries = np.zeros((int(areas.value), stretch), dtype=np.uint32)
+        table = np.zeros(int(areas.value) * (stretch // 64), dtype=np.uint32)
+        trips = np.zeros((h, w), dtype=np.uint8)
+        self._check(self._lib.blok_hip_beam_cache_download_list(self._ctx, C.byref(state), C.byref(areas), C.byref(groups), _ffi.ptr(entries), entries.size,
+                                                                 _ffi.ptr(table), table.size, _ffi.ptr(trips), trips.size))
+        return int(state.value), int(groups.value), entries, table, trips
 
     def beam_cache_refines(self) -> int:
         """Diagnostic: launches so far that issued a view's finer searches behind their walk."""

@@ -136,9 +136,31 @@ int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk);
  * (blok_hip_set_beam_refine_after) issues, behind its walk, one search per 8 x 8 wave tile of its live beam tiles, whose answers the
  * launches after it walk from — a shorter walk, and none for a wave tile that is empty by its own search (only where the beam tile is a
  * whole number, more than one, of wave tiles per side); 0 = every launch searches (the launches of a library without the cache, one for
- * one).  In every case the slots are emptied.  blok_hip_last_launch_kind goes on reporting the form the launch policy chose for the
+ * one); 3 = as 2, and the view's walked pixels are regrouped by the length of their walks: the N-th launch that walks from the finer bounds
+ * (blok_hip_set_beam_list_after) also counts every ray's trips and issues, behind its walk, the build of a list — per 32 x 32 pixels,
+ * the pixels by descending count, 64 to a group — and of a table of the groups, heaviest first; the first later launch that finds the build
+ * finished walks one group per wave from then on, with neither the view's order nor its live prefix (rectangles up to 65 534 pixels a side;
+ * allocates the lists' buffers, about 17 bytes per pixel of the frame, and waits for the device).  In every case the slots are emptied.
+ * blok_hip_last_launch_kind goes on reporting the form the launch policy chose for the
  * device's state, also for a launch that walked from kept bounds (a plain trace launch).  Never changes a result. */
 int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode);
+/* N: a refined view's rays are counted by its N-th launch from the finer bounds (0 = the default, 16: what the count launch and the build
+ * cost over what a packed frame gains), or the first after it at which no other view's build is in flight. */
+int blok_hip_set_beam_list_after(blok_hip_ctx* ctx, uint32_t hits);
+/* The side of the packed list's areas in pixels (32): an area's stretch of the list has its square of entries, its share of the table a
+ * 64th of that in words. */
+uint32_t blok_hip_pack_area(void);
+/* Launches so far that counted and issued a list's build (at most one per set of finer bounds). */
+int blok_hip_beam_cache_list_builds(const blok_hip_ctx* ctx, uint64_t* out_builds);
+/* Read-back of the list: *out_state = 0 the latest rectangle launch had nothing to do with one, 1 it counted and issued the build, 2 it
+ * walked packed; for states 1 and 2, *out_n_areas = the areas of its rectangle (blok_hip_pack_area pixels a side: 32; row-major), *out_n_groups = the table's non-empty
+ * groups, and into the buffers that are given: the list, 1 024 entries per area (x | y << 16 in the rectangle, 0xFFFFFFFF = padding, entries
+ * beyond an area's last group undefined); the table, 16 words per area, of which the first *out_n_groups are (largest trip count of the
+ * group + 1) << 20 | area * 16 + group of the area, descending, and the rest 0; the trips of the context's latest count launch, one byte per
+ * pixel of the rectangle, defined for the listed pixels (those of state 1's launch; a later count launch for another view overwrites them).
+ * Waits for the device; launches nothing and changes nothing.  Any pointer may be null. */
+int blok_hip_beam_cache_download_list(blok_hip_ctx* ctx, int* out_state, uint32_t* out_n_areas, uint32_t* out_n_groups, uint32_t* out_list_host_or_null, size_t list_capacity,
+                                      uint32_t* out_table_host_or_null, size_t table_capacity, uint8_t* out_trips_host_or_null, size_t trips_capacity);
 /* Launches so far that walked from kept bounds (hits) and that searched into a slot (fills); either pointer may be null. */
 int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills);
 /* ... and that issued a view's finer searches behind their walk (at most one per fill; such a launch counts as a hit too). */
