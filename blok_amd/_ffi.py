@@ -91,6 +91,11 @@ SCATTER_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("n_cells", "<u8"
 SCATTER_ANY_MATERIAL, SCATTER_ROTATE, SCATTER_MIRROR = 1, 2, 4      # = BLOK_SCATTER_ANY_MATERIAL / _ROTATE / _MIRROR
 SCATTER_MAX_ENTRIES = 16                          # = BLOK_SCATTER_MAX_ENTRIES
 SCATTER_NO_LIMIT = 0xFFFF                         # max_rise / max_drop: no limit
+# = blok_scroll_box (24 bytes) and blok_scroll_info (200 bytes): what a scroll of the volume's box did, or would do
+SCROLL_BOX = np.dtype([("lo", "<i4", 3), ("hi", "<i4", 3)])
+SCROLL_INFO = np.dtype([("origin", "<i4", 3), ("delta", "<i4", 3), ("n_exposed", "<u4"), ("n_leaving", "<u4"), ("exposed", SCROLL_BOX, 3), ("leaving", SCROLL_BOX, 3),
+                        ("n_cells_kept", "<u8"), ("n_filled_before", "<u8"), ("n_filled_kept", "<u8")])
+SCROLL_PLAN_ONLY = 1                              # = BLOK_SCROLL_PLAN_ONLY
 
 
 def flood_seed_face(f: int) -> int:
@@ -103,6 +108,7 @@ assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and I
 assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD.itemsize == 24 and BRICKS_INFO.itemsize == 64
 assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_INFO.itemsize == 64
 assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
+assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200
 
 
 class GBuffer(C.Structure):
@@ -246,6 +252,9 @@ HOST_SYMBOLS = {
     "blok_column_field": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blok_scroll_plan": (C.c_int, [C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p]),
+    "blok_scroll_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -411,6 +420,7 @@ HIP_SYMBOLS = {
     "blok_hip_volume_scatter_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_volume_scatter_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_scatter_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_scroll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

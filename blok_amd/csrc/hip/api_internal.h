@@ -312,6 +312,8 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
                  const blok::TileFrames* frames = nullptr);
 // api_volume.hip: the one place the context's snapshots are freed (a new volume, a destroyed one, the context's end)
 void free_volume_snapshots(blok_hip_ctx* ctx);
+// ... and the one place they follow a scroll of the box by `delta`, or are freed where they cannot (blok_hip_volume_scroll)
+void scroll_volume_snapshots(blok_hip_ctx* ctx, const int32_t delta[3]);
 // api_instances.hip
 // The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n);

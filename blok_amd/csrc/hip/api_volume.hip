@@ -8,6 +8,7 @@
 #include "../common/flood_core.h"
 #include "../common/columns_core.h"
 #include "../common/region_core.h"
+#include "../common/scroll_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -24,6 +25,34 @@ void free_volume_snapshots(blok_hip_ctx* ctx) {
     blok::gpu_field_free(&ctx->flood);
     blok::gpu_columns_free(&ctx->columns);
     blok::gpu_scatter_free(&ctx->scatter);
+}
+
+namespace {
+// A holder whose region [lo, lo + ext) is box-local, behind a move of the box by `delta`: the corner follows when the region still lies
+// wholly in the box of `dims`; false = it does not (the caller frees the holder).  A holder that was not taken stays as it is.
+bool follow_box(bool taken, uint32_t lo[3], const uint32_t ext[3], const int32_t delta[3], const uint32_t dims[3]) {
+    if (!taken) return true;
+    int64_t l[3];
+    for (int a = 0; a < 3; ++a) {
+        l[a] = int64_t(lo[a]) - delta[a];
+        if (l[a] < 0 || l[a] + int64_t(ext[a]) > int64_t(dims[a])) return false;
+    }
+    for (int a = 0; a < 3; ++a) lo[a] = static_cast<uint32_t>(l[a]);
+    return true;
+}
+}  // namespace
+
+// The snapshots behind a scroll of the box by `delta` (the volume still holds its dims).  They are of world cells: the quads hold no position
+// and the brick stream holds its region in world voxels, so both stay; the holders with a box-local corner follow the box or are freed.
+void scroll_volume_snapshots(blok_hip_ctx* ctx, const int32_t delta[3]) {
+    const uint32_t dims[3] = {ctx->volume.nx, ctx->volume.ny, ctx->volume.nz};
+    if (!follow_box(ctx->components.taken, ctx->components.lo, ctx->components.ext, delta, dims)) blok::gpu_components_free(&ctx->components);
+    if (!follow_box(ctx->distance.taken, ctx->distance.lo, ctx->distance.info.ext, delta, dims)) blok::gpu_field_free(&ctx->distance);
+    if (!follow_box(ctx->flood.taken, ctx->flood.lo, ctx->flood.info.ext, delta, dims)) blok::gpu_field_free(&ctx->flood);
+    if (!follow_box(ctx->columns.taken, ctx->columns.lo, ctx->columns.info.ext, delta, dims)) {
+        blok::gpu_columns_free(&ctx->columns);
+        blok::gpu_scatter_free(&ctx->scatter);                 // (made from the snapshot that has just gone)
+    }
 }
 }  // namespace blok_api
 
@@ -647,6 +676,31 @@ int blok_hip_volume_scatter_device(blok_hip_ctx* ctx, const blok_instance** out_
     if (!ctx->scatter.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "scatter_device: no table (blok_hip_volume_scatter_models)");
     if (!out_dev || !out_count) return set_error(ctx, BLOK_ERR_INVALID_ARG, "scatter_device: null output");
     *out_dev = ctx->scatter.d_table; *out_count = ctx->scatter.info.n_placed;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_scroll(blok_hip_ctx* ctx, const int32_t delta[3], uint32_t flags, blok_scroll_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    blok::GpuVolume& v = ctx->volume;
+    const uint32_t dims[3] = {v.nx, v.ny, v.nz};
+    if (const int rule = blok::scroll::check_args(v.origin, dims, delta, flags))
+        return set_error(ctx, blok::scroll::status(rule), std::string("volume_scroll: ") + blok::scroll::rule_text(rule));
+    blok_scroll_info info;
+    blok::scroll::plan(v.origin, dims, delta, &info);
+    // a zero delta changes nothing: it is planned and counted like PLAN_ONLY
+    const bool write = !(flags & BLOK_SCROLL_PLAN_ONLY) && (delta[0] != 0 || delta[1] != 0 || delta[2] != 0);
+    std::string why;
+    // (edits are enqueued on the null stream, and so is this: it moves what they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_scroll(&v, delta, write, &info.n_filled_before, &info.n_filled_kept, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    if (write) {
+        scroll_volume_snapshots(ctx, delta);
+        for (int a = 0; a < 3; ++a) v.origin[a] = info.origin[a];
+        const uint32_t lo[3] = {0, 0, 0};
+        v.edits.note(lo, dims, true);                      // the whole box, MayFill: to the installed world every cell may hold another voxel
+    }
+    if (out_info) *out_info = info;
     return BLOK_OK;
 }
 

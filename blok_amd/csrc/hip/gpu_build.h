@@ -99,6 +99,19 @@ GpuBuildStatus gpu_volume_set_voxels(GpuVolume* v, const int32_t* xyz, const uin
 // box is Ok and notes nothing.
 enum class Edit { OnlyClears, MayFill };
 GpuBuildStatus gpu_volume_commit(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], Edit kind, std::string* why);
+// What an operation owes that has replaced the brick masks as a whole and kept them equal to density > 0 itself (the scroll): the
+// occupancy words of every level from the masks as they are, by the launches of a whole-box commit; every brick dirty and without a place
+// in the previous build's material array, so that the next build gathers every id from the store.  Reads no density.  Notes nothing in
+// v->edits.
+GpuBuildStatus gpu_volume_masks_replaced(GpuVolume* v, std::string* why);
+// = blok_hip_volume_scroll (include/blok_hip.h; scroll_kernels.hip) by a delta that has passed scroll::check_args: the filled voxels of the
+// old box and of the kept cells, from the old and the moved masks; with `write` the move itself — the dense arrays and the masks out of
+// place into arrays allocated for the call (8 bytes per cell and a mask array beside the volume's own while it runs; an in-place move,
+// with its ordering per axis, is next), which the volume adopts, the old ones freed once the device has finished, then
+// gpu_volume_masks_replaced.  Without it nothing is written.  v->origin and v->edits are the caller's.  Blocking.  A failure before the
+// arrays are adopted leaves the volume as it was.
+GpuBuildStatus gpu_volume_scroll(GpuVolume* v, const int32_t delta[3], bool write, uint64_t* out_n_filled_before, uint64_t* out_n_filled_kept,
+                                 std::string* why);
 // = blok_hip_volume_voxelize_mesh (include/blok_hip.h; voxelize_kernels.hip).  Host arrays.  *invalid: a referenced vertex, an index or a
 // triangle's extent is out of the limits (nothing written).
 GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,

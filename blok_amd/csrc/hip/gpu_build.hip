@@ -657,8 +657,9 @@ KeyedCtx keyed_ctx(const GpuVolume& v) {
     return k;
 }
 
-// Key layout: masks of the bricks that contain those voxels and the occupancy words above them, level by level.
-GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {
+// Key layout: masks of the bricks that contain those voxels and the occupancy words above them, level by level.  masks_given: the masks of
+// the box are already what the store says (gpu_volume_masks_replaced), only the words above them are made.
+GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why, bool masks_given = false) {
     const KeyedCtx k = keyed_ctx(*v);
     CellRange ranges[9] = {};
     uint64_t totals[9] = {};
@@ -669,7 +670,7 @@ GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t 
         totals[l] = static_cast<uint64_t>(r.nx) * r.ny * r.nz;
     }
     // an edit (few bricks): a wave per brick, then every level above in one workgroup; an upload (the whole box): a lane per brick, a launch per level
-    const bool small = totals[1] <= 65536u && (v->levels < 2 || totals[2] <= 4096u);
+    const bool small = !masks_given && totals[1] <= 65536u && (v->levels < 2 || totals[2] <= 4096u);
     ++v->refreshes[small ? 0 : 1];
     if (small) {
         hipLaunchKernelGGL(keyed_brick_wave_kernel, dim3(static_cast<uint32_t>(totals[1])), dim3(64), 0, nullptr, k, ranges[1]);
@@ -682,7 +683,7 @@ GpuBuildStatus keyed_refresh(GpuVolume* v, const uint32_t lo[3], const uint32_t 
             BLOK_GPU_TRY(hipGetLastError());
         }
     } else {
-        for (uint32_t l = 1; l <= v->levels; ++l) {
+        for (uint32_t l = masks_given ? 2u : 1u; l <= v->levels; ++l) {
             if (l == 1) hipLaunchKernelGGL(keyed_brick_kernel, dim3(blocks_for(totals[l])), dim3(256), 0, nullptr, k, ranges[l]);
             else hipLaunchKernelGGL(occupancy_kernel, dim3(blocks_for(totals[l])), dim3(256), 0, nullptr, l == 2 ? v->d_masks : v->d_occ[l - 1], v->d_occ[l], v->levels - l, ranges[l]);
             BLOK_GPU_TRY(hipGetLastError());
@@ -861,6 +862,15 @@ GpuBuildStatus gpu_volume_commit(GpuVolume* v, const uint32_t lo[3], const uint3
     if (hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]) return GpuBuildStatus::Ok;
     v->edits.note(lo, hi, kind == Edit::MayFill);                   // (also when a launch below fails: the store is written)
     return v->keyed ? keyed_refresh(v, lo, hi, why) : dense_refresh(v, lo, hi, why);
+}
+
+GpuBuildStatus gpu_volume_masks_replaced(GpuVolume* v, std::string* why) {
+    if (!v->keyed) { ++v->refreshes[2]; return GpuBuildStatus::Ok; }      // (row-major: the masks and their flags are all there is)
+    BLOK_GPU_TRY(hipMemsetAsync(v->d_dirty, 1, v->n_keys, nullptr));
+    BLOK_GPU_TRY(hipMemsetAsync(v->scratch.d_old_base, 0xFF, v->n_keys * sizeof(uint32_t), nullptr));
+    v->scratch.have_previous_materials = false;
+    const uint32_t lo[3] = {0, 0, 0}, hi[3] = {v->nx, v->ny, v->nz};
+    return keyed_refresh(v, lo, hi, why, true);
 }
 
 GpuBuildStatus gpu_volume_upload(GpuVolume* v, const float* density, const uint32_t* ids, std::string* why) {

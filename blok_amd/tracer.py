@@ -370,6 +370,15 @@ class HipTracer:
                                                              _ffi.ptr(info)))
         return info
 
+    def volume_scroll(self, delta, plan_only: bool = False) -> np.ndarray:
+        """Moves the resident volume's box through the world by `delta` voxels, each a multiple of 4 (blok_hip.h: blok_hip_volume_scroll):
+        the world voxels that stay inside keep their values, the cells that come into view are empty.  Returns one _ffi.SCROLL_INFO record:
+        the new origin, the exposed boxes (the caller's to fill) and the leaving ones, and the counts.  plan_only fills the same record
+        and changes nothing; (0, 0, 0) says where the box is.  The next volume_rebuild installs the world."""
+        info = np.zeros(1, dtype=_ffi.SCROLL_INFO)
+        self._check(self._lib.blok_hip_volume_scroll(self._ctx, _vec3(delta), _ffi.SCROLL_PLAN_ONLY if plan_only else 0, _ffi.ptr(info)))
+        return info
+
     def volume_scatter_info(self) -> np.ndarray:
         info = np.zeros(1, dtype=_ffi.SCATTER_INFO)
         self._check(self._lib.blok_hip_volume_scatter_info(self._ctx, _ffi.ptr(info)))

@@ -389,6 +389,15 @@ public:
         check(blok_hip_volume_column_field(m_ctx, regionLo, regionHi, axis, flags, &info));
         return info;
     }
+    // Moves the resident volume's box through the world by `delta` voxels, each a multiple of 4 (blok_hip_volume_scroll): the world voxels
+    // that stay inside keep their values, the cells that come into view are empty.  Returns the new origin, the exposed boxes (the caller's
+    // to fill) and the leaving ones, and the counts; planOnly fills the same record and changes nothing.  The next volumeRebuild installs
+    // the world.
+    blok_scroll_info volumeScroll(const int32_t delta[3], bool planOnly = false) {
+        blok_scroll_info info{};
+        check(blok_hip_volume_scroll(m_ctx, delta, planOnly ? BLOK_SCROLL_PLAN_ONLY : 0u, &info));
+        return info;
+    }
     std::vector<uint16_t> downloadColumnTops(uint64_t page = uint64_t(1) << 24) { return downloadColumnPlane<uint16_t>(0, page); }
     std::vector<uint32_t> downloadColumnMaterials(uint64_t page = uint64_t(1) << 24) { return downloadColumnPlane<uint32_t>(1, page); }
     // Scatter over the column field (along +y from the top): a table of placements sorted by column, kept on the device until the next

@@ -575,7 +575,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.10: the resident volume saved, restored and undone as a sparse brick stream.
  * 1.11: the capped squared distance field of the resident volume; grow, shrink and hollow by it.
  * 1.12: the step field of the resident volume flooded from seeds; fill, seal, paint and clear by it.
- * 1.13: the column height field of the resident volume; models scattered onto it as an instance table. */
+ * 1.13: the column height field of the resident volume; models scattered onto it as an instance table.
+ * 1.14: the resident volume's box scrolled through the world in device memory. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -1129,6 +1130,56 @@ int blok_hip_volume_scatter_info(blok_hip_ctx* ctx, blok_scatter_info* out_info)
 int blok_hip_volume_scatter_download(blok_hip_ctx* ctx, blok_instance* out_host, uint64_t first, uint64_t count);
 /* The table where it lies, for the *_instanced_device entries; valid until the next scatter / column field / volume. */
 int blok_hip_volume_scatter_device(blok_hip_ctx* ctx, const blok_instance** out_dev, uint64_t* out_count);
+
+/* ------------------------------------------------------------- the scroll of the resident volume (ABI 1.14)
+ * Moves the volume's box through the world in HBM, by a whole number of bricks, so that the box can follow the camera: every world voxel
+ * that stays inside keeps its two 32-bit values exactly, the cells that come into view are empty and reported as up to three boxes (the
+ * caller's to fill: blok_hip_volume_generate_terrain, blok_hip_volume_decode_bricks), and the cells that drop out are reported too (plan
+ * first, then blok_hip_volume_encode_bricks them).  One right answer, bit-identical on the host (blok_scroll_plan / blok_scroll_voxels,
+ * blok_world.h) and on the device.  All calls block.
+ * Move.
+ *  - The box becomes [origin + delta, origin + delta + dims).  dims, chunk_size, voxel size and brick layout are unchanged.
+ *  - Each component of delta is a multiple of 4, so bricks stay bricks.
+ *  - A world voxel in both boxes keeps the bit pattern of its density and its id: -0.0f, negative and NaN densities, ids under density 0.
+ *  - Every other cell of the new box holds (+0.0f, 0).
+ *  - delta = (0, 0, 0) is valid and changes nothing.  It doubles as "where is the box".
+ * Boxes.  Take C to be the per-axis intersection of the old and new extents.
+ *  - If C is empty on any axis (|delta[a]| >= dims[a]), nothing is kept: exposed is one box, the whole new box, and leaving is one box,
+ *    the whole old box.
+ *  - Otherwise exposed lists, in this order and only where non-empty: the z slab (new x, new y, z in new \ C), the y slab (new x, y in
+ *    new \ C, z in C), the x slab (x in new \ C, y in C, z in C).  leaving is the same construction with the old box's extents.
+ *  - The listed boxes are disjoint and cover new \ old, or old \ new, exactly.
+ * Afterwards.
+ *  - Brick masks, occupancy words, dirty flags and, in the row-major layout, the non-empty flags are what blok_hip_volume_upload of the
+ *    new arrays would leave, for ragged last bricks too: a mask bit never refers to a cell outside the box.
+ *  - Every brick counts as changed for the next rebuild; no material ids are taken from the previous build's array.
+ *  - The edit log notes the whole box as an edit that may have filled voxels.
+ *  - The installed world is untouched until the next blok_hip_volume_rebuild, as behind any edit.  That rebuild sees a changed lattice
+ *    and searches the sun map anew.
+ * Snapshots are of world cells.  The quads hold no position and stay.  The brick stream holds its region in world voxels and stays:
+ * blok_hip_volume_restore_bricks(NULL) keeps meaning "where it was taken", and is BLOK_ERR_UNSUPPORTED, with the snapshot kept, if that
+ * region has left the box.  The components, the distance field, the flood field and the columns with their scatter table follow the box
+ * when their region still lies wholly in the new box, and are freed otherwise: their entries then answer "no snapshot" as after a new
+ * volume.
+ * Memory.  The move is out of place: a second pair of dense arrays (8 bytes per cell: 8 GiB for a 1024^3 box) and a second mask array live
+ * for the duration of the call; the volume adopts them and the old ones are freed once the device has finished.  (An in-place move, with
+ * an ordering per axis, is next.)
+ * BLOK_SCROLL_PLAN_ONLY runs the same checks and fills the same info, counts included, and writes nothing.  out_info may be NULL.
+ * Errors, each leaving the volume, its origin and every snapshot as they were.  BLOK_ERR_INVALID_ARG: NULL delta, a component that is not
+ * a multiple of 4, unknown flag bits.  BLOK_ERR_UNSUPPORTED: the new box leaves the int16 lattice [-32768, 32768] (blok_hip_volume_create's
+ * rule).  BLOK_ERR_NO_WORLD: no volume.  BLOK_ERR_OOM: the call's scratch could not be allocated. */
+#define BLOK_SCROLL_PLAN_ONLY 1u      /* fill out_info, change nothing */
+typedef struct blok_scroll_box { int32_t lo[3], hi[3]; } blok_scroll_box;     /* world voxels, half open; 24 bytes */
+typedef struct blok_scroll_info {
+    int32_t  origin[3];               /* the box's corner after the call (PLAN_ONLY: as it would be) */
+    int32_t  delta[3];
+    uint32_t n_exposed, n_leaving;    /* 0..3 */
+    blok_scroll_box exposed[3];       /* new box minus old box: now (+0.0f, 0), the caller's to fill */
+    blok_scroll_box leaving[3];       /* old box minus new box: gone after the call */
+    uint64_t n_cells_kept;            /* cells that lie in the old box and in the new */
+    uint64_t n_filled_before, n_filled_kept;   /* voxels with density > 0 in the old box / among the kept cells */
+} blok_scroll_info;                   /* 200 bytes */
+int blok_hip_volume_scroll(blok_hip_ctx* ctx, const int32_t delta[3], uint32_t flags, blok_scroll_info* out_info);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -288,6 +288,20 @@ int blok_column_field(const float* density, const uint32_t* material_ids, const 
 int blok_scatter(const uint16_t* top, const uint32_t* material, const blok_columns_info* columns_info, const blok_scatter_params* params,
                  const blok_scatter_entry* entries, uint32_t n_entries, blok_instance* out_instances, uint64_t capacity, blok_scatter_info* out_info);
 
+/* -------------------------------------------------------------- the scroll of the resident volume on the host (scroll.cpp)
+ * The contract of blok_hip_volume_scroll (blok_hip.h; the records and the flag are declared there) over host arrays of a box as above,
+ * through the rules the kernels use.
+ * scroll_plan: *out_info takes the plan of moving the box [origin, origin + dims) by delta: the new origin, the exposed and the leaving
+ * boxes, n_cells_kept; the two filled counts stay 0.
+ * scroll_voxels: the out-of-place move.  out_density and out_ids take nx * ny * nz values each, the new box's arrays; *out_info (may be
+ * NULL) takes everything the device's info holds.  The inputs are not written and may not overlap the outputs.
+ * Errors as the device entry (NULL delta, a component that is not a multiple of 4: BLOK_ERR_INVALID_ARG; a new box that leaves the int16
+ * lattice: BLOK_ERR_UNSUPPORTED); a NULL origin is (0, 0, 0); a zero dimension, a NULL out_info (plan) or a NULL array (voxels) is
+ * BLOK_ERR_INVALID_ARG.  Nothing is written on an error. */
+int blok_scroll_plan(const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz, const int32_t delta[3], blok_scroll_info* out_info);
+int blok_scroll_voxels(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                       const int32_t delta[3], float* out_density, uint32_t* out_material_ids, blok_scroll_info* out_info);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

@@ -1,13 +1,16 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
 //   --terrain: procedural terrain generated on the device into a resident volume of --terrain-size^3 voxels (blok_hip_volume_generate_terrain),
 //          rebuilt with grass, soil, rock and an emissive ore; the camera stands on blok_terrain_height.  With --obj the mesh is voxelized on
 //          top of it, a quarter of the box tall, standing on the ground at the box centre
+//   --scroll DX,DY,DZ: with --terrain, after the fill: the box is moved through the world by that many voxels (multiples of 4,
+//          blok_hip_volume_scroll), the same terrain is generated into each box that came into view, and the camera moves with the box:
+//          the frame shows the terrain as a box generated whole at the new place would.
 //   --export-obj: with --terrain or --obj, the resident volume's surface as merged quads (blok_hip_volume_extract_quads over the whole box),
 //          written as an OBJ with a sibling .mtl of the library's albedos (blok_quads_write_obj)
 //   --components: with --terrain or --obj, the connected components of the whole box (blok_hip_volume_label_components): how many there
@@ -73,6 +76,8 @@ struct Options {
     bool seal = false;                    // fill the empty cells that air from the box's faces does not reach, before the rebuild
     uint32_t seal_material = 0;
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
+    bool scroll = false;                  // move the terrain's box by scroll_delta after the fill
+    int32_t scroll_delta[3] = {0, 0, 0};
     std::vector<std::string> populate;    // .vox files whose first models are scattered over the terrain
     bool bake = false;                    // ... and stamped into the volume instead of traced as instances
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
@@ -103,6 +108,7 @@ private:
                 if (m_opt.hollow >= 0) throw std::runtime_error("--hollow needs a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.seal) throw std::runtime_error("--seal needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.populate.empty()) throw std::runtime_error("--populate needs a terrain: --terrain");
+                if (m_opt.scroll) throw std::runtime_error("--scroll needs a terrain: --terrain");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -165,7 +171,8 @@ private:
         const float eye[3] = {0.12f * N, static_cast<float>(p.base_height + static_cast<int32_t>(p.amplitude)) + 0.08f * N, 0.10f * N};
         float f[3] = {N / 2.0f - eye[0], static_cast<float>(ground) + 0.15f * N - eye[1], N / 2.0f - eye[2]};
         const float len = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
-        for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a]; }
+        const int32_t* at = m_opt.scroll_delta;                  // the box's corner: the camera stands in the box wherever it has gone
+        for (int a = 0; a < 3; ++a) { f[a] /= len; m_camera.position[a] = eye[a] + static_cast<float>(a == 1 ? 0 : at[a]); }
         m_camera.pitch = std::asin(f[1]) * 57.29577951308232f;
         m_camera.yaw = std::atan2(f[2], f[0]) * 57.29577951308232f;
     }
@@ -178,10 +185,18 @@ private:
         m_tracer->createVolume(origin, N, N, N);
         const uint64_t filled = m_tracer->generateTerrain(p);
         std::cout << "terrain: seed " << m_opt.terrain_seed << ", " << N << "^3 -> " << filled << " voxels filled\n";
-        const int32_t centre[2] = {static_cast<int32_t>(N / 2), static_cast<int32_t>(N / 2)};
+        if (m_opt.scroll) {
+            const blok_scroll_info info = m_tracer->volumeScroll(m_opt.scroll_delta);
+            uint64_t generated = 0;
+            for (uint32_t b = 0; b < info.n_exposed; ++b) generated += m_tracer->generateTerrain(p, info.exposed[b].lo, info.exposed[b].hi);
+            std::cout << "scroll: origin " << info.origin[0] << " " << info.origin[1] << " " << info.origin[2] << ", kept " << info.n_cells_kept << " cells, lost "
+                      << info.n_filled_before - info.n_filled_kept << " filled voxels, exposed " << info.n_exposed << " boxes, generated " << generated << " voxels\n";
+        }
+        const int32_t centre[2] = {static_cast<int32_t>(N / 2) + m_opt.scroll_delta[0], static_cast<int32_t>(N / 2) + m_opt.scroll_delta[2]};
         int32_t ground = 0;
         blok_terrain_height(&p, centre, 1, &ground);
         if (!m_opt.obj.empty()) {
+            if (m_opt.scroll) throw std::runtime_error("--scroll does not move a mesh: leave --obj out");
             char err[512] = {0};
             blok_mesh* mesh = nullptr;
             if (blok_obj_load_file(m_opt.obj.c_str(), m_materials.handle(), &mesh, err, sizeof(err)) != BLOK_OK)
@@ -498,6 +513,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--hollow")) { opt.hollow = std::atoll(next()); if (opt.hollow < 0 || opt.hollow > 65025) { std::fprintf(stderr, "--hollow takes a squared distance in 0..65025\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--populate")) { for (std::string list = next(); !list.empty();) { const size_t c = list.find(','); opt.populate.push_back(list.substr(0, c)); list = c == std::string::npos ? "" : list.substr(c + 1); } }
         else if (!std::strcmp(argv[i], "--bake")) opt.bake = true;
+        else if (!std::strcmp(argv[i], "--scroll")) { opt.scroll = true; if (std::sscanf(next(), "%d,%d,%d", &opt.scroll_delta[0], &opt.scroll_delta[1], &opt.scroll_delta[2]) != 3) { std::fprintf(stderr, "--scroll takes DX,DY,DZ\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
