@@ -96,6 +96,12 @@ SCROLL_BOX = np.dtype([("lo", "<i4", 3), ("hi", "<i4", 3)])
 SCROLL_INFO = np.dtype([("origin", "<i4", 3), ("delta", "<i4", 3), ("n_exposed", "<u4"), ("n_leaving", "<u4"), ("exposed", SCROLL_BOX, 3), ("leaving", SCROLL_BOX, 3),
                         ("n_cells_kept", "<u8"), ("n_filled_before", "<u8"), ("n_filled_kept", "<u8")])
 SCROLL_PLAN_ONLY = 1                              # = BLOK_SCROLL_PLAN_ONLY
+# = blok_shape (64 bytes): one primitive of blok_hip_volume_apply_shapes with its operation; a, b, r in half-voxel units
+SHAPE = np.dtype([("kind", "<u4"), ("op", "<u4"), ("a", "<i4", 3), ("b", "<i4", 3), ("r", "<u4", 3), ("material", "<u4"), ("match", "<u4"), ("value", "<f4"),
+                  ("reserved", "<u4", 2)])
+SHAPE_BOX, SHAPE_ELLIPSOID, SHAPE_CAPSULE, SHAPE_CYLINDER = 0, 1, 2, 3      # = BLOK_SHAPE_BOX .. _CYLINDER
+SHAPE_SET, SHAPE_KEEP, SHAPE_ERASE, SHAPE_PAINT, SHAPE_REPLACE, SHAPE_ADD, SHAPE_SUBTRACT = range(7)      # = BLOK_SHAPE_SET .. _SUBTRACT
+SHAPES_MAX = 65536                                # = BLOK_SHAPES_MAX
 
 
 def flood_seed_face(f: int) -> int:
@@ -108,7 +114,7 @@ assert CAMERA.itemsize == 56 and HIT.itemsize == 16 and RAY.itemsize == 32 and I
 assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD.itemsize == 24 and BRICKS_INFO.itemsize == 64
 assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_INFO.itemsize == 64
 assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
-assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200
+assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200 and SHAPE.itemsize == 64
 
 
 class GBuffer(C.Structure):
@@ -255,6 +261,9 @@ HOST_SYMBOLS = {
     "blok_scroll_plan": (C.c_int, [C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p]),
     "blok_scroll_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "blok_shapes_check": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "blok_shape_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "blok_shapes_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -421,6 +430,7 @@ HIP_SYMBOLS = {
     "blok_hip_volume_scatter_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_scatter_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "blok_hip_volume_scroll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_apply_shapes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

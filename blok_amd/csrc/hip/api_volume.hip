@@ -9,6 +9,7 @@
 #include "../common/columns_core.h"
 #include "../common/region_core.h"
 #include "../common/scroll_core.h"
+#include "../common/shapes_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -274,6 +275,20 @@ int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placeme
     std::string why;
     // (edits are enqueued on the null stream, and so is this: placement after placement, in stream order)
     return volume_status(ctx, blok::gpu_volume_stamp(&ctx->volume, models.data(), placements_host, n_placements, mode, density, out_n_voxels, &why), why);
+}
+
+int blok_hip_volume_apply_shapes(blok_hip_ctx* ctx, const blok_shape* shapes_host, uint32_t n_shapes, uint64_t* out_n_written) {
+    if (out_n_written) *out_n_written = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (n_shapes > BLOK_SHAPES_MAX) return set_error(ctx, BLOK_ERR_INVALID_ARG, "apply_shapes: more than BLOK_SHAPES_MAX shapes");
+    if (n_shapes && !shapes_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "apply_shapes: null table with a non-zero count");
+    for (uint32_t i = 0; i < n_shapes; ++i)
+        if (const int rule = blok::shapes::check(shapes_host[i]))
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, "apply_shapes: shape " + std::to_string(i) + ": " + blok::shapes::rule_text(rule));
+    std::string why;
+    // (edits are enqueued on the null stream, and so is this: it reads what they leave)
+    return volume_status(ctx, blok::gpu_volume_apply_shapes(&ctx->volume, shapes_host, n_shapes, out_n_written, &why), why);
 }
 
 int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags, uint32_t* out_model,

@@ -112,6 +112,9 @@ GpuBuildStatus gpu_volume_masks_replaced(GpuVolume* v, std::string* why);
 // arrays are adopted leaves the volume as it was.
 GpuBuildStatus gpu_volume_scroll(GpuVolume* v, const int32_t delta[3], bool write, uint64_t* out_n_filled_before, uint64_t* out_n_filled_kept,
                                  std::string* why);
+// = blok_hip_volume_apply_shapes (include/blok_hip.h; shapes_kernels.hip): a host table that has passed shapes::check, applied in order in
+// one pass over the tiles its shapes touch, then one gpu_volume_commit per group of shapes whose brick-aligned boxes overlap.  Blocking.
+GpuBuildStatus gpu_volume_apply_shapes(GpuVolume* v, const blok_shape* shapes, uint32_t n_shapes, uint64_t* out_n_written, std::string* why);
 // = blok_hip_volume_voxelize_mesh (include/blok_hip.h; voxelize_kernels.hip).  Host arrays.  *invalid: a referenced vertex, an index or a
 // triangle's extent is out of the limits (nothing written).
 GpuBuildStatus gpu_volume_voxelize(GpuVolume* v, const float* positions, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,

@@ -171,6 +171,15 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_stamp_models(self._ctx, _ffi.ptr(inst) if len(inst) else None, len(inst), int(mode), float(density), C.byref(n)))
         return int(n.value)
 
+    def volume_apply_shapes(self, shapes) -> int:
+        """Applies a table of shapes to the resident volume in one pass (blok_hip.h: blok_hip_volume_apply_shapes): shapes are _ffi.SHAPE
+        records (blok_amd.shapes: box, sphere, ellipsoid, capsule, cylinder, stroke), each with its own operation; the result is the table
+        applied in order.  Returns the number of writes.  The next volume_rebuild installs the world."""
+        table = np.ascontiguousarray(shapes, dtype=_ffi.SHAPE).reshape(-1)
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_apply_shapes(self._ctx, _ffi.ptr(table) if len(table) else None, len(table), C.byref(n)))
+        return int(n.value)
+
     def volume_capture_model(self, lo=None, hi=None, cut: bool = False) -> int:
         """A region of the resident volume (world voxels, half open; both None = the whole box) as a new model, in the lattice whose voxel
         (0, 0, 0) is the region's corner (blok_hip.h: blok_hip_volume_capture_model); cut = also clear the captured voxels.  Returns the

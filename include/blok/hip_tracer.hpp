@@ -14,6 +14,7 @@
 #define BLOK_HIP_TRACER_HPP
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -262,6 +263,29 @@ public:
         uint64_t n = 0;
         check(blok_hip_volume_stamp_models(m_ctx, placements.data(), static_cast<uint32_t>(placements.size()), mode, density, &n));
         return n;
+    }
+    // A table of shapes applied to the resident volume in one pass, in table order (blok_hip_volume_apply_shapes; coordinates in
+    // half-voxel units, the centre of world voxel w at 2 w + 1): returns the number of writes.  A later rebuildVolume installs the world.
+    uint64_t applyShapes(const std::vector<blok_shape>& shapes) {
+        uint64_t n = 0;
+        check(blok_hip_volume_apply_shapes(m_ctx, shapes.data(), static_cast<uint32_t>(shapes.size()), &n));
+        return n;
+    }
+    // The capsules of a stroke through world points given in half-voxel units, radius in half-voxel units: point k to point k + 1, so
+    // that the chain has no gaps; one point is a sphere.
+    static std::vector<blok_shape> strokeShapes(const std::vector<std::array<int32_t, 3>>& points, uint32_t radius, uint32_t op, uint32_t material = 0,
+                                                float value = 1.0f, uint32_t match = 0) {
+        std::vector<blok_shape> out;
+        const size_t n = points.size() > 1 ? points.size() - 1 : points.size();
+        for (size_t k = 0; k < n; ++k) {
+            blok_shape s{};
+            s.kind = BLOK_SHAPE_CAPSULE; s.op = op; s.material = material; s.match = match; s.value = value; s.r[0] = radius;
+            const auto& p = points[k];
+            const auto& q = points[std::min(k + 1, points.size() - 1)];
+            for (int a = 0; a < 3; ++a) { s.a[a] = p[a]; s.b[a] = q[a]; }
+            out.push_back(s);
+        }
+        return out;
     }
     // A region of the resident volume (world voxels, half-open; both null = the whole box) as a new model whose voxel (0, 0, 0) is the
     // region's corner (blok_hip_volume_capture_model): returns the model id.  cut: the captured voxels are cleared in the volume.

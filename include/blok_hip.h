@@ -426,6 +426,8 @@ int blok_hip_volume_set_voxels(blok_hip_ctx* ctx, const int32_t* xyz, const uint
 /* = applyBrush (brush.cpp:13-63): mode 0 ADD density = max(density, value), 1 SUBTRACT density = min(density, value),
  * inside the sphere around `center` (world units), voxel centres as the reference computes them. */
 int blok_hip_volume_apply_brush(blok_hip_ctx* ctx, const float center[3], float radius, float value, int mode);
+/* (BLOK_SHAPE_ADD on a BLOK_SHAPE_ELLIPSOID, below, is NOT this brush: the brush keeps the reference's float voxel centres, computed per
+ * chunk, and refuses a sphere that leaves the box; the shapes are integer rules and clip.) */
 /* = rebuildDirtyChunks + packChunksToGpuSvo + Renderer::updateWorld for the box: installs the world made of the voxels with
  * density > 0 and their material ids, with the given material table. */
 int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials);
@@ -576,7 +578,9 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.11: the capped squared distance field of the resident volume; grow, shrink and hollow by it.
  * 1.12: the step field of the resident volume flooded from seeds; fill, seal, paint and clear by it.
  * 1.13: the column height field of the resident volume; models scattered onto it as an instance table.
- * 1.14: the resident volume's box scrolled through the world in device memory. */
+ * 1.14: the resident volume's box scrolled through the world in device memory.
+ * 1.15: a table of integer shapes (box, ellipsoid, capsule, cylinder; set, keep, erase, paint, replace, add, subtract) applied to the
+ *       resident volume in one pass. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -1180,6 +1184,56 @@ typedef struct blok_scroll_info {
     uint64_t n_filled_before, n_filled_kept;   /* voxels with density > 0 in the old box / among the kept cells */
 } blok_scroll_info;                   /* 200 bytes */
 int blok_hip_volume_scroll(blok_hip_ctx* ctx, const int32_t delta[3], uint32_t flags, blok_scroll_info* out_info);
+
+/* ------------------------------------------------------------- a table of shapes applied to the resident volume (ABI 1.15)
+ * What a voxel editor does first: fill a box, draw a line, paint a material over a region.  blok_hip_volume_apply_shapes takes a table of
+ * primitives, each with its own operation; the result equals the table applied one shape at a time, in order, and is computed in one pass
+ * that reads and writes each touched cell once, however many shapes overlap it.  One right answer, bit-identical on the host
+ * (blok_shapes_voxels, blok_world.h) and on the device.  The call blocks.
+ * Coordinates are in HALF-voxel units: world coordinate = a / 2, and the centre of world voxel w is c = 2 w + 1.  A centre or a corner can
+ * so sit on a voxel centre, a face or a corner, and every test is an exact integer test on c.  With dx = c - a:
+ *  - BOX: a[k] <= c[k] <= b[k] on all axes (a = 2 lo, b = 2 hi is the half-open voxel box [lo, hi)).  r is zero.
+ *  - ELLIPSOID: centre a, radii r[3], b zero: |dx_k| <= r_k on every axis and sum_k dx_k^2 prod_{j != k} r_j^2 <= prod_j r_j^2.  A zero radius
+ *    flattens it with no special case: both sides of the sum are then 0, and what remains is the rectangle, the segment or the point of
+ *    the other axes' |dx_k| <= r_k.
+ *  - CAPSULE: segment a -> b, radius r[0], r[1] = r[2] = 0.  d = b - a, p = c - a, dd = d.d, s = p.d.  dd == 0 or s <= 0: |p|^2 <= r^2; else
+ *    s >= dd: |c - b|^2 <= r^2; else |p|^2 dd - s^2 <= r^2 dd.  a == b is the sphere; a chain of capsules is a stroke without gaps.
+ *  - CYLINDER: the same d, p, s, a != b: 0 <= s <= dd and |p|^2 dd - s^2 <= r^2 dd.
+ * Operations, on a voxel inside the shape and inside the volume's box (filled = density > 0, the rebuild's rule); each counts one write:
+ *  - SET: density = value, id = material.  KEEP: the same where the voxel is empty.  ERASE: density = 0.0f, id = 0.
+ *  - PAINT: id = material where the voxel is filled.  REPLACE: id = material where it is filled and id == match.  The density is untouched.
+ *  - ADD: density = density < value ? value : density.  SUBTRACT: density = value < density ? value : density.  The id is untouched.
+ * Voxels outside the box are clipped silently; a shape wholly outside writes nothing.  *out_n_written (may be NULL) is the number of
+ * writes by these rules summed over the shapes in order: a voxel under three SET shapes counts three.  n_shapes == 0 is BLOK_OK.
+ * Afterwards masks, occupancy words and dirty flags are what blok_hip_volume_set_voxels leaves for the same writes, refreshed per group of
+ * shapes whose brick-aligned boxes overlap: two far-apart shapes do not refresh what lies between them.  Snapshots are treated as behind
+ * blok_hip_volume_stamp_models.
+ * BLOK_ERR_INVALID_ARG, nothing written, the message names the first offending index: a or b outside [-2^17, 2^17]; a radius above 1024;
+ * |b - a| above 4096 on an axis of a CAPSULE or CYLINDER; an unknown kind or op; non-zero reserved words or fields the kind does not use;
+ * a BOX with a > b on an axis; a CYLINDER with a == b; a value that is not finite, or <= 0 for SET and KEEP; a NULL table with a non-zero
+ * count; n_shapes > BLOK_SHAPES_MAX.  BLOK_ERR_NO_WORLD: no volume.  BLOK_ERR_UNSUPPORTED: a volume above 2^32 cells. */
+#define BLOK_SHAPE_BOX       0u
+#define BLOK_SHAPE_ELLIPSOID 1u
+#define BLOK_SHAPE_CAPSULE   2u
+#define BLOK_SHAPE_CYLINDER  3u
+#define BLOK_SHAPE_SET      0u
+#define BLOK_SHAPE_KEEP     1u
+#define BLOK_SHAPE_ERASE    2u
+#define BLOK_SHAPE_PAINT    3u
+#define BLOK_SHAPE_REPLACE  4u
+#define BLOK_SHAPE_ADD      5u
+#define BLOK_SHAPE_SUBTRACT 6u
+#define BLOK_SHAPES_MAX 65536u
+typedef struct blok_shape {
+    uint32_t kind;                    /* BLOK_SHAPE_BOX .. _CYLINDER */
+    uint32_t op;                      /* BLOK_SHAPE_SET .. _SUBTRACT */
+    int32_t  a[3], b[3];              /* half-voxel units */
+    uint32_t r[3];                    /* half-voxel units */
+    uint32_t material, match;
+    float    value;
+    uint32_t reserved[2];             /* zero */
+} blok_shape;                         /* 64 bytes */
+int blok_hip_volume_apply_shapes(blok_hip_ctx* ctx, const blok_shape* shapes_host, uint32_t n_shapes, uint64_t* out_n_written);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -302,6 +302,19 @@ int blok_scroll_plan(const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t
 int blok_scroll_voxels(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
                        const int32_t delta[3], float* out_density, uint32_t* out_material_ids, blok_scroll_info* out_info);
 
+/* -------------------------------------------------------------- the shape table on the host (shapes.cpp)
+ * The contract of blok_hip_volume_apply_shapes (blok_hip.h; the record and its constants are declared there) over host arrays of a box as
+ * above, through the rules the kernels use.
+ * shapes_check: BLOK_OK, or BLOK_ERR_INVALID_ARG with the first offending index in *out_index and "shape I: rule" in err (each may be NULL).
+ * shape_bounds: the voxel box of one shape that passes the check, world voxels, half open (empty where no voxel centre fits).
+ * shapes_voxels: the table applied shape by shape, in order, in place; *out_n_written (may be NULL) as the device entry counts.  A NULL
+ * origin is (0, 0, 0); the box may lie anywhere in int32.  A NULL array or a zero dimension is BLOK_ERR_INVALID_ARG, a box above 2^32
+ * cells BLOK_ERR_UNSUPPORTED.  Nothing is written on an error. */
+int blok_shapes_check(const blok_shape* shapes, uint32_t n_shapes, uint32_t* out_index, char* err, size_t err_len);
+int blok_shape_bounds(const blok_shape* shape, int32_t out_lo[3], int32_t out_hi[3]);
+int blok_shapes_voxels(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                       const blok_shape* shapes, uint32_t n_shapes, uint64_t* out_n_written);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -11,6 +11,10 @@
 //   --scroll DX,DY,DZ: with --terrain, after the fill: the box is moved through the world by that many voxels (multiples of 4,
 //          blok_hip_volume_scroll), the same terrain is generated into each box that came into view, and the camera moves with the box:
 //          the frame shows the terrain as a box generated whole at the new place would.
+//   --stroke X,Y,Z:X,Y,Z:...,R[,OP]: with --terrain, --obj or --load-volume, before the rebuild: a brush of radius R dragged through the world
+//          points (voxels; multiples of one half: W.5 is the centre of voxel W), as one table of capsules in one pass
+//          (blok_hip_volume_apply_shapes); OP is add (the default, density 1), subtract (density 0), erase, set, keep or paint (the last
+//          three with material 1); prints the number of writes
 //   --export-obj: with --terrain or --obj, the resident volume's surface as merged quads (blok_hip_volume_extract_quads over the whole box),
 //          written as an OBJ with a sibling .mtl of the library's albedos (blok_quads_write_obj)
 //   --components: with --terrain or --obj, the connected components of the whole box (blok_hip_volume_label_components): how many there
@@ -77,6 +81,8 @@ struct Options {
     uint32_t seal_material = 0;
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
     bool scroll = false;                  // move the terrain's box by scroll_delta after the fill
+    std::vector<std::array<int32_t, 3>> stroke;      // the points of --stroke, half-voxel units
+    uint32_t stroke_radius = 0, stroke_op = BLOK_SHAPE_ADD;
     int32_t scroll_delta[3] = {0, 0, 0};
     std::vector<std::string> populate;    // .vox files whose first models are scattered over the terrain
     bool bake = false;                    // ... and stamped into the volume instead of traced as instances
@@ -109,6 +115,7 @@ private:
                 if (m_opt.seal) throw std::runtime_error("--seal needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.populate.empty()) throw std::runtime_error("--populate needs a terrain: --terrain");
                 if (m_opt.scroll) throw std::runtime_error("--scroll needs a terrain: --terrain");
+                if (!m_opt.stroke.empty()) throw std::runtime_error("--stroke needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.vox.empty()) {
                     std::string err;
                     if (!blok::loadAndImportVox(m_opt.vox, m_mgr, &m_materials, nullptr, 0, &err))   // app.cpp:105-113
@@ -222,6 +229,7 @@ private:
         }
         seal();
         hollow();
+        stroke();
         populate(p);
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
@@ -247,6 +255,7 @@ private:
         m_tracer->decodeBricks(s);
         seal();
         hollow();
+        stroke();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats w = m_tracer->worldStats();
         std::cout << "volume loaded: " << s.info.n_bricks << " bricks, " << s.info.n_voxels << " voxels; world: " << w.n_voxels << " voxels, " << w.n_tree_nodes
@@ -339,6 +348,15 @@ private:
         const uint64_t cleared = m_tracer->editByDistance(BLOK_DISTANCE_HOLLOW, d2);
         std::cout << "hollow: " << cleared << " voxels cleared, " << info.n_near + info.n_far - cleared << " left\n";      // (the filled cells are those with D > 0)
     }
+    // A brush dragged through the points of --stroke: the capsules from each point to the next, applied as one table in one pass.
+    void stroke() {
+        if (m_opt.stroke.empty()) return;
+        const uint32_t op = m_opt.stroke_op;
+        const bool writes_id = op == BLOK_SHAPE_SET || op == BLOK_SHAPE_KEEP || op == BLOK_SHAPE_PAINT;
+        const std::vector<blok_shape> table = blok::HipTracer::strokeShapes(m_opt.stroke, m_opt.stroke_radius, op, writes_id ? 1u : 0u, op == BLOK_SHAPE_SUBTRACT ? 0.0f : 1.0f);
+        const uint64_t written = m_tracer->applyShapes(table);
+        std::cout << "stroke: " << table.size() << " capsules, " << written << " voxels written\n";
+    }
     // The whole box as a sparse brick stream: encoded on the device, downloaded, written as a .bvol file.
     void saveVolume() {
         if (m_opt.save_volume.empty()) return;
@@ -375,6 +393,7 @@ private:
         const uint64_t written = m_tracer->voxelizeMesh(pos, tri, mat, 1, 1.0f, m_opt.solid);
         seal();
         hollow();
+        stroke();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "mesh: " << nv << " vertices, " << nt << " triangles -> " << written << " voxels written (" << (m_opt.solid ? "solid" : "surface")
@@ -490,6 +509,51 @@ private:
 
 }  // namespace
 
+// --stroke's argument: points separated by ':', the last followed by the radius and, if given, the operation.  Numbers are multiples of
+// one half and become half-voxel units.
+static bool parseStroke(const std::string& arg, Options& opt) {
+    const auto half = [](const std::string& s, int32_t* out) {
+        char* end = nullptr;
+        const double v = 2.0 * std::strtod(s.c_str(), &end);
+        if (end == s.c_str() || *end || !(std::fabs(v) < 1.0e6) || v != std::floor(v)) return false;
+        *out = static_cast<int32_t>(v);
+        return true;
+    };
+    std::vector<std::string> points;
+    for (std::string rest = arg; ;) {
+        const size_t c = rest.find(':');
+        points.push_back(rest.substr(0, c));
+        if (c == std::string::npos) break;
+        rest = rest.substr(c + 1);
+    }
+    for (size_t k = 0; k < points.size(); ++k) {
+        std::vector<std::string> f;
+        for (std::string rest = points[k]; ;) {
+            const size_t c = rest.find(',');
+            f.push_back(rest.substr(0, c));
+            if (c == std::string::npos) break;
+            rest = rest.substr(c + 1);
+        }
+        const bool last = k + 1 == points.size();
+        if (last ? (f.size() != 4 && f.size() != 5) : f.size() != 3) return false;
+        std::array<int32_t, 3> p{};
+        for (int a = 0; a < 3; ++a) if (!half(f[a], &p[a])) return false;
+        opt.stroke.push_back(p);
+        if (!last) continue;
+        int32_t r = 0;
+        if (!half(f[3], &r) || r < 0) return false;
+        opt.stroke_radius = static_cast<uint32_t>(r);
+        if (f.size() == 5) {
+            static const char* const kNames[] = {"set", "keep", "erase", "paint", "", "add", "subtract"};      // = BLOK_SHAPE_SET .. _SUBTRACT; REPLACE takes a match
+            uint32_t op = 0;
+            while (op < 7u && (f[4] != kNames[op] || !kNames[op][0])) ++op;
+            if (op == 7u) return false;
+            opt.stroke_op = op;
+        }
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     Options opt;
     for (int i = 1; i < argc; ++i) {
@@ -514,6 +578,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--populate")) { for (std::string list = next(); !list.empty();) { const size_t c = list.find(','); opt.populate.push_back(list.substr(0, c)); list = c == std::string::npos ? "" : list.substr(c + 1); } }
         else if (!std::strcmp(argv[i], "--bake")) opt.bake = true;
         else if (!std::strcmp(argv[i], "--scroll")) { opt.scroll = true; if (std::sscanf(next(), "%d,%d,%d", &opt.scroll_delta[0], &opt.scroll_delta[1], &opt.scroll_delta[2]) != 3) { std::fprintf(stderr, "--scroll takes DX,DY,DZ\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--stroke")) { if (!parseStroke(next(), opt)) { std::fprintf(stderr, "--stroke takes X,Y,Z:X,Y,Z:...,R[,add|subtract|erase|set|keep|paint], coordinates and R in multiples of one half\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
