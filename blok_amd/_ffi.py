@@ -102,6 +102,11 @@ SHAPE = np.dtype([("kind", "<u4"), ("op", "<u4"), ("a", "<i4", 3), ("b", "<i4", 
 SHAPE_BOX, SHAPE_ELLIPSOID, SHAPE_CAPSULE, SHAPE_CYLINDER = 0, 1, 2, 3      # = BLOK_SHAPE_BOX .. _CYLINDER
 SHAPE_SET, SHAPE_KEEP, SHAPE_ERASE, SHAPE_PAINT, SHAPE_REPLACE, SHAPE_ADD, SHAPE_SUBTRACT = range(7)      # = BLOK_SHAPE_SET .. _SUBTRACT
 SHAPES_MAX = 65536                                # = BLOK_SHAPES_MAX
+# = blok_lod_level (64 bytes) and blok_lod_info (360 bytes): the grids and counts of a pyramid of coarser levels, level j at ["level"][j - 1]
+LOD_LEVEL = np.dtype([("clo", "<i4", 3), ("cext", "<u4", 3), ("n_cells", "<u8"), ("n_filled", "<u8"), ("n_exposed", "<u8"), ("sum_n", "<u8"), ("sum_e", "<u8")])
+LOD_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("levels", "<u4"), ("reserved", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("level", LOD_LEVEL, 5)])
+LOD_VOTE_EXPOSED = 1                              # = BLOK_LOD_VOTE_EXPOSED
+LOD_MAX_LEVELS = 5                                # = BLOK_LOD_MAX_LEVELS
 
 
 def flood_seed_face(f: int) -> int:
@@ -115,6 +120,7 @@ assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD
 assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_INFO.itemsize == 64
 assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
 assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200 and SHAPE.itemsize == 64
+assert LOD_LEVEL.itemsize == 64 and LOD_INFO.itemsize == 360
 
 
 class GBuffer(C.Structure):
@@ -264,6 +270,8 @@ HOST_SYMBOLS = {
     "blok_shapes_check": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "blok_shape_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "blok_shapes_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "blok_lod_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -431,6 +439,10 @@ HIP_SYMBOLS = {
     "blok_hip_volume_scatter_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "blok_hip_volume_scroll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
     "blok_hip_volume_apply_shapes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_reduce": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_hip_volume_lod_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_volume_lod_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_volume_lod_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

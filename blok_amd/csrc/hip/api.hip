@@ -282,7 +282,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 15u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 16u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -465,6 +465,10 @@ int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, u
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad dense grid arguments");
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int32_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
+    // blok_hip_set_voxel_size: the grid's cells are voxels of that size, cell (x, y, z) covering world [(o + c) vs, (o + c + 1) vs); the
+    // structure is built in voxel units as for size 1 (the dense-grid kernel walks unit cells: the tree serves the other sizes)
+    const float vs = ctx->voxel_size;
+    const bool keep_grid = ctx->dense_dda && vs == 1.0f;
     if (!ctx->force_host_build) {                      // device-side build straight from the grid (gpu_build.hip)
         blok::GpuTree gpu;
         std::string reason;
@@ -484,8 +488,9 @@ int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, u
             for (int a = 0; a < 3; ++a) ctx->stats.origin[a] = gpu.origin[a];
             ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
             ctx->built_on_device = true;
+            ctx->world_voxel_size = vs;
             const int rc_sun = rebuild_sun_map(ctx);
-            if (rc_sun != BLOK_OK || !ctx->dense_dda) return rc_sun;
+            if (rc_sun != BLOK_OK || !keep_grid) return rc_sun;
             return keep_dense_grid(ctx, ids, nx, ny, nz, o);
         }
     }
@@ -499,8 +504,10 @@ int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, u
     blok::HostTree tree;
     const char* why = "";
     if (!blok::build_tree(voxels, tree, &why)) return set_error(ctx, BLOK_ERR_UNSUPPORTED, why);
+    ctx->pending_voxel_size = vs;                      // (as blok_hip_upload_world)
     const int rc_tree = install_tree(ctx, tree, materials, n_materials);
-    if (rc_tree != BLOK_OK || !ctx->dense_dda) return rc_tree;
+    ctx->pending_voxel_size = 1.0f;
+    if (rc_tree != BLOK_OK || !keep_grid) return rc_tree;
     return keep_dense_grid(ctx, ids, nx, ny, nz, o);
 }
 

@@ -51,9 +51,9 @@ struct blok_hip_ctx {
     bool tree_owned_by_volume = false; // d_nodes / d_tree_materials belong to the resident volume's scratch (gpu_build.h): own_nodes / own_tree_materials are empty
     bool force_host_build = false;
     blok_world_stats stats{};
-    float voxel_size = 1.0f;            // for the next blok_hip_upload_world (blok_hip_set_voxel_size)
+    float voxel_size = 1.0f;            // for the next blok_hip_upload_world / blok_hip_upload_dense (blok_hip_set_voxel_size)
     float world_voxel_size = 1.0f;      // of the installed world
-    float pending_voxel_size = 1.0f;    // handed from blok_hip_upload_world to install_tree
+    float pending_voxel_size = 1.0f;    // handed from blok_hip_upload_world / blok_hip_upload_dense to install_tree
     // dense-grid path (dense_kernels.hip): the uploaded id grid in 8^3-cell tiles and one occupancy bit per tile; kept when
     // blok_hip_set_dense_dda was on at blok_hip_upload_dense, and then used by the rectangle entries of the primary trace
     bool dense_dda = false, has_dense = false;
@@ -108,6 +108,7 @@ struct blok_hip_ctx {
     blok::GpuFlood flood;                // of the last blok_hip_volume_flood_field
     blok::GpuColumns columns;            // of the last blok_hip_volume_column_field
     blok::GpuScatter scatter;            // of the last blok_hip_volume_scatter_models: it goes with the column snapshot it was made from
+    blok::GpuLod lod;                    // of the last blok_hip_volume_reduce
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
     blok::DeviceArray<float> d_sun_map;

@@ -10,6 +10,7 @@
 #include "../common/region_core.h"
 #include "../common/scroll_core.h"
 #include "../common/shapes_core.h"
+#include "../common/lod_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -26,6 +27,7 @@ void free_volume_snapshots(blok_hip_ctx* ctx) {
     blok::gpu_field_free(&ctx->flood);
     blok::gpu_columns_free(&ctx->columns);
     blok::gpu_scatter_free(&ctx->scatter);
+    blok::gpu_lod_free(&ctx->lod);
 }
 
 namespace {
@@ -716,6 +718,68 @@ int blok_hip_volume_scroll(blok_hip_ctx* ctx, const int32_t delta[3], uint32_t f
         v.edits.note(lo, dims, true);                      // the whole box, MayFill: to the installed world every cell may hold another voxel
     }
     if (out_info) *out_info = info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_reduce(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t levels, uint32_t flags,
+                           blok_lod_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (const int rule = blok::lod::check_args(levels, flags)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("volume_reduce: ") + blok::lod::rule_text(rule));
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "volume_reduce", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    blok::GpuLod snapshot;
+    // (edits are enqueued on the null stream, and so is this: it reads the masks and the ids they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_reduce(&ctx->volume, lo, hi, levels, flags, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    blok::gpu_lod_free(&ctx->lod);
+    ctx->lod = snapshot; ctx->lod.taken = true;
+    if (out_info) *out_info = snapshot.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_lod_info(blok_hip_ctx* ctx, blok_lod_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->lod.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_info: no snapshot (blok_hip_volume_reduce)");
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_info: null output");
+    *out_info = ctx->lod.info;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_lod_download(blok_hip_ctx* ctx, uint32_t level, uint32_t plane, void* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const blok::GpuLod& l = ctx->lod;
+    if (l.taken && (level == 0u || level > l.info.levels)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_download: level 0 or above the snapshot's levels");
+    if (l.taken && plane > 2u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_download: plane above 2");
+    const uint64_t n = l.taken ? l.info.level[level - 1u].n_cells : 0u;
+    const char* base = l.taken && l.d_planes ? static_cast<const char*>(l.d_planes) + blok::lod::level_offset(l.info, level) + blok::lod::plane_offset(n, plane) : nullptr;
+    return ranged_download(ctx, "lod_download", "blok_hip_volume_reduce", l.taken, n, base, plane == 2u ? sizeof(uint32_t) : sizeof(uint16_t), out_host, first, count);
+}
+
+int blok_hip_volume_lod_model(blok_hip_ctx* ctx, uint32_t level, uint32_t min_count, uint32_t* out_model, uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const blok::GpuLod& l = ctx->lod;
+    if (!l.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_model: no snapshot (blok_hip_volume_reduce)");
+    if (level == 0u || level > l.info.levels) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_model: level 0 or above the snapshot's levels");
+    if (min_count == 0u || min_count > (1u << (3u * level))) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_model: min_count 0 or above 8^level");
+    if (!out_model) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lod_model: null output id");
+    if (ctx->models.desc.size() >= std::numeric_limits<uint32_t>::max() - 1u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model ids exhausted");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string why;
+    blok::GpuTree tree;
+    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+    uint64_t n_voxels = 0;
+    if (l.info.level[level - 1u].n_cells) {
+        const blok::GpuBuildStatus st = blok::gpu_lod_capture(&l, level, min_count, &tree, box_lo, box_hi, &n_voxels, &why);
+        if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    }
+    if (!n_voxels) return set_error(ctx, BLOK_ERR_UNSUPPORTED, "lod_model: the level holds no cell with that many filled voxels");
+    const int rc = add_captured_model(ctx, tree, box_lo, box_hi, out_model);
+    if (rc != BLOK_OK) return rc;
+    if (out_n_voxels) *out_n_voxels = n_voxels;
     return BLOK_OK;
 }
 

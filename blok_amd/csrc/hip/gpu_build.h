@@ -281,6 +281,24 @@ void gpu_scatter_free(GpuScatter* s);
 // Reads the snapshot alone; *out is a new table, the caller's to free (d_table null when nothing was placed).  Blocking.
 GpuBuildStatus gpu_columns_scatter(const GpuColumns* columns, const blok_scatter_params& params, const blok_scatter_entry* entries, uint32_t n_entries,
                                    GpuScatter* out, std::string* why);
+// ---- the pyramid of coarser levels (include/blok_hip.h: blok_hip_volume_reduce; lod_kernels.hip) ----
+// The snapshot in device memory, owned by the holder: one array with the levels' planes one behind the other (../common/lod_core.h:
+// level_offset, plane_offset), and the info that counts them.
+struct GpuLod {
+    void* d_planes = nullptr;
+    blok_lod_info info = {};
+    bool taken = false;
+};
+void gpu_lod_free(GpuLod* l);
+// Reduces the box-local region [lo, hi) `levels` times (arguments that have passed lod::check_args), from the brick masks (which every edit
+// leaves equal to density > 0) and the ids of the filled cells.  Changes nothing; *out is a new snapshot, the caller's to free (d_planes
+// null when the region has no cell).  Blocking.
+GpuBuildStatus gpu_volume_reduce(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t levels, uint32_t flags, GpuLod* out,
+                                 std::string* why);
+// = blok_hip_volume_lod_model: gpu_volume_capture over a level of the snapshot, a cell filled iff its n >= min_count, its id the voted one;
+// model coordinates are relative to the level's grid corner.
+GpuBuildStatus gpu_lod_capture(const GpuLod* l, uint32_t level, uint32_t min_count, GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
+                               uint64_t* out_n_voxels, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

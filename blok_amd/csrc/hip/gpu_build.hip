@@ -23,6 +23,7 @@
 
 #include "gpu_build.h"
 #include "device_mem.h"
+#include "../common/lod_core.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -971,10 +972,23 @@ __device__ __forceinline__ bool member(const LabelPred& p, uint32_t x, uint32_t 
     return p.labels[(x - p.o[0]) + (static_cast<uint64_t>(y - p.o[1]) + static_cast<uint64_t>(z - p.o[2]) * p.ry) * p.rx] == p.label;
 }
 
+// What makes cell i = (x, y, z) of the dense arrays a voxel of the captured model: filled (capture_model), filled and labelled
+// (capture_component), or — over a level of a pyramid (gpu_build.h: GpuLod), which has counts and no densities — a count of at least
+// min_count (lod_model).
+enum Captured { kFilled = 0, kFilledLabelled = 1, kCounted = 2 };
+struct CountPred {
+    const uint16_t* counts; uint32_t min_count;
+};
+template <int kPred>
+__device__ __forceinline__ bool captured(const float* density, const LabelPred& p, const CountPred& c, size_t i, uint32_t x, uint32_t y, uint32_t z) {
+    if (kPred == kCounted) return c.counts[i] >= c.min_count;
+    return density[i] > 0.0f && member<kPred == kFilledLabelled>(p, x, y, z);
+}
+
 // Tight bounds and count of the region's filled voxels.  A wave takes rows (64 consecutive x of one (y, z)) in a grid-stride loop and keeps
 // its bounds in registers — a row's x bounds are the ends of its ballot — so a wave issues at most seven atomics, at the end, to its slot.
-template <bool kLabelled>
-__global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, const LabelPred p, uint64_t n_rows, uint32_t segs, uint32_t* bounds) {
+template <int kPred>
+__global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, const LabelPred p, const CountPred c, uint64_t n_rows, uint32_t segs, uint32_t* bounds) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * 4u + (threadIdx.x >> 6), n_waves = static_cast<uint64_t>(gridDim.x) * 4u;
     uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
@@ -983,8 +997,8 @@ __global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, c
         uint32_t seg, y, z;
         row_segment(row, segs, r.ext[1], seg, y, z);
         const uint32_t x = seg * 64u + lane;
-        const bool filled = x < r.ext[0] && r.density[(static_cast<size_t>(r.lo[2] + z) * r.ny + (r.lo[1] + y)) * r.nx + r.lo[0] + x] > 0.0f &&
-                            member<kLabelled>(p, r.lo[0] + x, r.lo[1] + y, r.lo[2] + z);
+        const bool filled = x < r.ext[0] && captured<kPred>(r.density, p, c, (static_cast<size_t>(r.lo[2] + z) * r.ny + (r.lo[1] + y)) * r.nx + r.lo[0] + x,
+                                                            r.lo[0] + x, r.lo[1] + y, r.lo[2] + z);
         const uint64_t votes = __ballot(filled);
         if (!votes) continue;
         mn[0] = min(mn[0], seg * 64u + static_cast<uint32_t>(__ffsll(static_cast<unsigned long long>(votes)) - 1));
@@ -1000,14 +1014,13 @@ __global__ __launch_bounds__(256) void region_bounds_kernel(const RegionCtx r, c
 
 // One wave per brick of the MODEL's 4-grid (in general not the volume's brick grid), lane b = voxel b: the brick's mask from the voxels that
 // are filled and inside the tight box [t0, t1) of the region's filled voxels (grid voxels, i.e. from the tree's corner).
-template <bool kLabelled>
-__global__ __launch_bounds__(64) void region_brick_kernel(const DenseCtx d, const LabelPred p, uint32_t t0x, uint32_t t0y, uint32_t t0z, uint32_t t1x, uint32_t t1y, uint32_t t1z,
+template <int kPred>
+__global__ __launch_bounds__(64) void region_brick_kernel(const DenseCtx d, const LabelPred p, const CountPred c, uint32_t t0x, uint32_t t0y, uint32_t t0z, uint32_t t1x, uint32_t t1y, uint32_t t1z,
                                                           uint64_t* masks, uint32_t* non_empty) {
     const uint32_t b = threadIdx.x;
     const uint32_t vx = blockIdx.x * 4u + (b & 3u), vy = blockIdx.y * 4u + ((b >> 2) & 3u), vz = blockIdx.z * 4u + (b >> 4);
     const bool inside = vx >= t0x && vx < t1x && vy >= t0y && vy < t1y && vz >= t0z && vz < t1z;
-    const bool filled = inside && d.density[(static_cast<size_t>(d.oz + vz) * d.ny + (d.oy + vy)) * d.nx + d.ox + vx] > 0.0f &&
-                        member<kLabelled>(p, d.ox + vx, d.oy + vy, d.oz + vz);
+    const bool filled = inside && captured<kPred>(d.density, p, c, (static_cast<size_t>(d.oz + vz) * d.ny + (d.oy + vy)) * d.nx + d.ox + vx, d.ox + vx, d.oy + vy, d.oz + vz);
     const uint64_t mask = __ballot(filled);
     if (b == 0u) {
         const size_t g = blockIdx.x + (static_cast<size_t>(blockIdx.z) * d.by + blockIdx.y) * d.bx;
@@ -1034,8 +1047,8 @@ LabelPred label_pred(const GpuComponents* c, uint32_t label) {
     return p;
 }
 
-template <bool kLabelled>
-GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3],
+template <int kPred>
+GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const CountPred& counted, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3],
                               int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why) {
     *out = GpuTree{};
     *out_n_voxels = 0;
@@ -1053,7 +1066,7 @@ GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const u
     BLOK_GPU_TRY(hipMemcpy(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     const uint32_t segs = (r.ext[0] + 63u) / 64u;
     const uint64_t n_rows = static_cast<uint64_t>(segs) * r.ext[1] * r.ext[2];
-    hipLaunchKernelGGL(region_bounds_kernel<kLabelled>, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r, pred, n_rows, segs, d_bounds);
+    hipLaunchKernelGGL(region_bounds_kernel<kPred>, dim3(static_cast<uint32_t>(std::min<uint64_t>((n_rows + 3u) / 4u, 2048u))), dim3(256), 0, nullptr, r, pred, counted, n_rows, segs, d_bounds);
     BLOK_GPU_TRY(hipGetLastError());
     BLOK_GPU_TRY(hipMemcpy(bounds.data(), d_bounds, bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     uint32_t t0[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, t1[3] = {0u, 0u, 0u};
@@ -1087,7 +1100,7 @@ GpuBuildStatus capture_region(const GpuVolume* v, const LabelPred& pred, const u
     uint64_t* d_masks; uint32_t *d_flag, *d_slot;
     BLOK_GPU_TRY(mem.alloc(&d_masks, total)); BLOK_GPU_TRY(mem.alloc(&d_flag, total + 1)); BLOK_GPU_TRY(mem.alloc(&d_slot, total + 1));
     BLOK_GPU_TRY(hipMemset(d_flag + total, 0, sizeof(uint32_t)));
-    hipLaunchKernelGGL(region_brick_kernel<kLabelled>, dim3(d.bx, d.by, d.bz), dim3(64), 0, nullptr, d, pred, t0[0] - origin[0], t0[1] - origin[1], t0[2] - origin[2],
+    hipLaunchKernelGGL(region_brick_kernel<kPred>, dim3(d.bx, d.by, d.bz), dim3(64), 0, nullptr, d, pred, counted, t0[0] - origin[0], t0[1] - origin[1], t0[2] - origin[2],
                        t1[0] - origin[0] + 1u, t1[1] - origin[1] + 1u, t1[2] - origin[2] + 1u, d_masks, d_flag);
     BLOK_GPU_TRY(hipGetLastError());
     const GpuBuildStatus st = finish_from_masks(mem, total, d_masks, d_flag, d_slot, levels, origin,
@@ -1119,12 +1132,25 @@ GpuBuildStatus clear_region(GpuVolume* v, const LabelPred& pred, const uint32_t 
 
 GpuBuildStatus gpu_volume_capture(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
                                   uint64_t* out_n_voxels, std::string* why) {
-    return capture_region<false>(v, LabelPred{}, lo, hi, out, box_lo, box_hi, out_n_voxels, why);
+    return capture_region<kFilled>(v, LabelPred{}, CountPred{}, lo, hi, out, box_lo, box_hi, out_n_voxels, why);
 }
 
 GpuBuildStatus gpu_volume_capture_labelled(const GpuVolume* v, const GpuComponents* c, uint32_t label, const uint32_t lo[3], const uint32_t hi[3],
                                            GpuTree* out, int32_t box_lo[3], int32_t box_hi[3], uint64_t* out_n_voxels, std::string* why) {
-    return capture_region<true>(v, label_pred(c, label), lo, hi, out, box_lo, box_hi, out_n_voxels, why);
+    return capture_region<kFilledLabelled>(v, label_pred(c, label), CountPred{}, lo, hi, out, box_lo, box_hi, out_n_voxels, why);
+}
+
+GpuBuildStatus gpu_lod_capture(const GpuLod* l, uint32_t level, uint32_t min_count, GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
+                               uint64_t* out_n_voxels, std::string* why) {
+    // the level as a volume of its own: its cells the voxels, the count plane in place of the densities, the id plane the ids
+    const blok_lod_level& L = l->info.level[level - 1u];
+    const char* at = static_cast<const char*>(l->d_planes) + lod::level_offset(l->info, level);
+    GpuVolume cells;
+    cells.nx = L.cext[0]; cells.ny = L.cext[1]; cells.nz = L.cext[2];
+    cells.d_ids = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(at + lod::plane_offset(L.n_cells, 2u)));
+    const CountPred counted{reinterpret_cast<const uint16_t*>(at + lod::plane_offset(L.n_cells, 0u)), min_count};
+    const uint32_t lo[3] = {0u, 0u, 0u};
+    return capture_region<kCounted>(&cells, LabelPred{}, counted, lo, L.cext, out, box_lo, box_hi, out_n_voxels, why);
 }
 
 GpuBuildStatus gpu_volume_clear_filled(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], std::string* why) {

@@ -406,6 +406,39 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_scatter_device(self._ctx, C.byref(table), C.byref(n)))
         return int(table.value or 0), int(n.value)
 
+    def volume_reduce(self, lo=None, hi=None, levels: int = 1, flags: int = 0) -> np.ndarray:
+        """Reduces a region of the resident volume (world voxels, half open; both None = the whole box) to `levels` coarser levels, each
+        cell of level j holding the counts of filled and of exposed voxels of its 2^j cube and a voted material id (blok_hip.h:
+        blok_hip_volume_reduce; flags: _ffi.LOD_VOTE_EXPOSED), kept on the device until the next reduce.  Returns the info, one
+        _ffi.LOD_INFO record; volume_lod_download fetches the planes, volume_lod_model makes a level a model."""
+        info = np.zeros(1, dtype=_ffi.LOD_INFO)
+        self._check(self._lib.blok_hip_volume_reduce(self._ctx, _vec3(lo), _vec3(hi), int(levels), int(flags), _ffi.ptr(info)))
+        return info
+
+    def volume_lod_info(self) -> np.ndarray:
+        info = np.zeros(1, dtype=_ffi.LOD_INFO)
+        self._check(self._lib.blok_hip_volume_lod_info(self._ctx, _ffi.ptr(info)))
+        return info
+
+    def volume_lod_download(self, level: int, plane: int = 0, first=None, count=None, page: int = 1 << 24) -> np.ndarray:
+        """A plane of a level (1-based) of the last reduce — 0: n (uint16), 1: e (uint16), 2: the ids (uint32) — fetched `page` cells at a
+        time: cells [first, first + count) in index order, or with both None the whole plane shaped [z][y][x]."""
+        dtype = np.uint32 if int(plane) == 2 else np.uint16
+        if first is None and count is None:
+            cext = [int(c) for c in self.volume_lod_info()["level"][0][max(int(level), 1) - 1]["cext"]] if 1 <= int(level) <= _ffi.LOD_MAX_LEVELS else [0, 0, 0]
+            out = self._paged(self._lib.blok_hip_volume_lod_download, np.zeros(cext[0] * cext[1] * cext[2], dtype=dtype), 0, page, int(level), int(plane))
+            return out.reshape(cext[2], cext[1], cext[0])
+        return self._paged(self._lib.blok_hip_volume_lod_download, np.zeros(int(count or 0), dtype=dtype), int(first or 0), page, int(level), int(plane))
+
+    def volume_lod_model(self, level: int, min_count: int = 1) -> int:
+        """The cells of a level of the last reduce with n >= min_count as a new model, in the lattice whose voxel (0, 0, 0) is the level's
+        first cell, each voxel's material the cell's voted id (blok_hip.h: blok_hip_volume_lod_model).  Returns the model id; the voxel
+        count is in last_capture_voxels."""
+        model, n = C.c_uint32(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_lod_model(self._ctx, int(level), int(min_count), C.byref(model), C.byref(n)))
+        self.last_capture_voxels = int(n.value)
+        return int(model.value)
+
     def volume_rebuild(self, materials=None) -> WorldStats:
         mats = np.zeros(0, dtype=MATERIAL) if materials is None else np.ascontiguousarray(materials, dtype=MATERIAL)
         self._check(self._lib.blok_hip_volume_rebuild(self._ctx, _ffi.ptr(mats) if len(mats) else None, len(mats)))

@@ -445,6 +445,36 @@ public:
         check(blok_hip_volume_scatter_device(m_ctx, &table, outCount));
         return table;
     }
+    // Reduces a region of the resident volume (world voxels, half-open, both null = the whole box) to `levels` coarser levels (1 .. 5), kept
+    // on the device until the next reduce (blok_hip_volume_reduce): per cell of level j the counts of filled and of exposed voxels of its
+    // 2^j cube and a voted material id (flags: BLOK_LOD_VOTE_EXPOSED).  Returns the grids and the counts.
+    blok_lod_info reduceVolume(const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr, uint32_t levels = 1, uint32_t flags = 0) {
+        blok_lod_info info{};
+        check(blok_hip_volume_reduce(m_ctx, regionLo, regionHi, levels, flags, &info));
+        return info;
+    }
+    blok_lod_info lodInfo() {
+        blok_lod_info info{};
+        check(blok_hip_volume_lod_info(m_ctx, &info));
+        return info;
+    }
+    // A plane of a level of the last reduce, x fastest over the level's grid: plane 0 n and 1 e as uint16_t, 2 the ids as uint32_t.
+    template <class T>
+    std::vector<T> downloadLod(uint32_t level, uint32_t plane, uint64_t page = uint64_t(1) << 24) {
+        if ((plane == 2) != (sizeof(T) == 4) || (sizeof(T) != 2 && sizeof(T) != 4)) throw std::runtime_error("blok::HipTracer: downloadLod: uint16_t for planes 0 and 1, uint32_t for plane 2");
+        const blok_lod_info info = lodInfo();
+        const uint64_t n = level >= 1 && level <= info.levels ? info.level[level - 1].n_cells : 0;
+        std::vector<T> out(n);
+        if (!n) check(blok_hip_volume_lod_download(m_ctx, level, plane, nullptr, 0, 0));
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_lod_download(m_ctx, level, plane, out.data() + at, at, std::min(page, n - at)));
+        return out;
+    }
+    // The cells of a level of the last reduce with n >= minCount as a new model in the lattice of the level's grid (blok_hip_volume_lod_model).
+    uint32_t lodModel(uint32_t level, uint32_t minCount = 1, uint64_t* outVoxels = nullptr) {
+        uint32_t model = 0;
+        check(blok_hip_volume_lod_model(m_ctx, level, minCount, &model, outVoxels));
+        return model;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

@@ -135,7 +135,7 @@ int blok_hip_release_stream(blok_hip_ctx* ctx, void* hip_stream);
 
 /* ------------------------------------------------------------------- world */
 
-/* ChunkManager's voxelSize for the NEXT blok_hip_upload_world (reference blok/src/chunk_manager.cpp:19-25: voxel coordinates
+/* ChunkManager's voxelSize for the NEXT blok_hip_upload_world or blok_hip_upload_dense (reference blok/src/chunk_manager.cpp:19-25: voxel coordinates
  * times voxelSize are the world coordinates in every SubChunkGpu).  Default 1 (the reference app, app.cpp:37).  Powers of two
  * in [1/256, 256] are supported: the structure is built on the voxel lattice and the walk scales its integer planes, every
  * product exact, so first hits stay bit-exact; hit records carry the voxel's lattice coordinates.  Any other size returns
@@ -159,7 +159,8 @@ int blok_hip_upload_world(blok_hip_ctx* ctx,
 /* Dense form (BASELINE.json configs[0..1]): material_ids[x + y*nx + z*nx*ny], 0 = empty,
  * i.e. the reference's dense store with density>0 <=> id != 0
  * (reference blok/include/chunk.hpp:35-36, blok/src/chunk_manager.cpp:57-59,330-348).
- * origin = world coordinate of voxel (0,0,0). */
+ * origin = world coordinate of voxel (0,0,0), in voxels: with blok_hip_set_voxel_size s, cell c covers world [(origin + c) s, (origin + c + 1) s)
+ * (since ABI 1.16; before, the size was taken for blok_hip_upload_world alone). */
 int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* material_ids,
                           uint32_t nx, uint32_t ny, uint32_t nz, const int32_t origin[3],
                           const blok_material* materials, size_t n_materials);
@@ -580,7 +581,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.13: the column height field of the resident volume; models scattered onto it as an instance table.
  * 1.14: the resident volume's box scrolled through the world in device memory.
  * 1.15: a table of integer shapes (box, ellipsoid, capsule, cylinder; set, keep, erase, paint, replace, add, subtract) applied to the
- *       resident volume in one pass. */
+ *       resident volume in one pass.
+ * 1.16: the resident volume reduced to a pyramid of coarser levels (counts and a voted material id per cell); a level as a model. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -1234,6 +1236,59 @@ typedef struct blok_shape {
     uint32_t reserved[2];             /* zero */
 } blok_shape;                         /* 64 bytes */
 int blok_hip_volume_apply_shapes(blok_hip_ctx* ctx, const blok_shape* shapes_host, uint32_t n_shapes, uint64_t* out_n_written);
+
+/* ------------------------------------------------------------- the resident volume reduced to a pyramid of coarser levels (ABI 1.16)
+ * The cheap, coarse copy a far field needs: blok_hip_volume_reduce halves a region of the volume `levels` = K times (1 <= K <= 5) and keeps
+ * the K coarse levels as a snapshot in device memory.  Nothing of the volume or of any other snapshot changes.
+ *  - Level 0 is the volume restricted to the region [region_lo, region_hi) (world voxels, half open; both NULL = the whole box).  A cell
+ *    is filled iff density > 0 (read from the brick masks, as the column and distance fields do), its id is its material id, and a filled
+ *    cell is exposed iff at least one of its six neighbours is empty: a neighbour inside the box has the volume's real state whether or
+ *    not it lies in the region, a neighbour outside the box counts as filled (the faces of the box expose nothing).  A cell outside the
+ *    region contributes nothing.
+ *  - Level j (1 <= j <= K) is world-aligned: cell C covers the level-(j-1) cells 2C + (dx, dy, dz), i.e. the world voxels
+ *    [C 2^j, (C+1) 2^j).  Its grid runs, per axis, from clo = lo >> j (arithmetic: the floor) to chi = (hi + 2^j - 1) >> j, cext = chi - clo;
+ *    an empty region has cext = 0 on every axis at every level.  Per cell: n = the sum of the children's n (filled fine cells, at most
+ *    32768), e = the sum of the children's e (exposed filled fine cells), and id = the vote of the children: the voters are the children
+ *    with e > 0, weighted by e, when BLOK_LOD_VOTE_EXPOSED is set and the cell's e > 0, otherwise the children with n > 0, weighted by n;
+ *    weights of equal ids add, the largest sum wins, a tie goes to the smallest id, no voter gives 0.  (A hierarchical vote, not the exact
+ *    mode of the 8^j fine cells: each level needs only the level below, and the K levels of one call nest.  An id of 0 on a filled cell is
+ *    a filled cell, as everywhere else.)
+ *  - Snapshot: per level 1..K three planes over the level's grid, x fastest (index (Cx - clo[0]) + cext[0] ((Cy - clo[1]) + cext[1] (Cz -
+ *    clo[2]))): plane 0 n (uint16_t), plane 1 e (uint16_t), plane 2 id (uint32_t).  It is a record of world cells, like the brick stream:
+ *    later edits and scrolls leave it alone, the next reduce replaces it, blok_hip_volume_destroy, a new blok_hip_volume_create and
+ *    blok_hip_destroy free it.  blok_hip_volume_lod_info returns the info, blok_hip_volume_lod_download copies elements [first, first +
+ *    count) of one plane of one level.
+ *  - Info, 360 bytes: bytes 0-15 version (1), flags, levels, a reserved zero; 16-27 the region's corner lo, 28-39 its extent ext (world
+ *    voxels); then five 64-byte records, level j at byte 40 + 64 (j - 1): clo[3], cext[3], n_cells (= the product of cext), n_filled
+ *    (cells with n > 0), n_exposed (cells with e > 0), sum_n and sum_e (the same at every level: the region's filled and exposed voxels).
+ *    Records above `levels` are zero.
+ *  - blok_hip_volume_lod_model: the cells of `level` with n >= min_count (1 <= min_count <= 8^level) become a new model, byte for byte the
+ *    one blok_hip_model_create builds from the voxels {(C - clo, id[C])}; it is built on the device, no voxel list exists on the host.
+ *    *out_n_voxels (may be NULL) takes their number.  A level that holds no such cell gives BLOK_ERR_UNSUPPORTED: no model is created and no
+ *    id is consumed.
+ *  - Errors, each leaving the volume, the previous snapshot and the model store as they were: BLOK_ERR_INVALID_ARG for levels 0 or above
+ *    BLOK_LOD_MAX_LEVELS, unknown flag bits, exactly one region pointer NULL, lo > hi, no snapshot (info, download, model), a level 0 or
+ *    above the snapshot's, a plane above 2, a range past the end, NULL with count > 0, min_count 0 or above 8^level, a NULL out_model;
+ *    BLOK_ERR_UNSUPPORTED for a region that leaves the box or a volume above 2^32 cells; BLOK_ERR_NO_WORLD without a volume (reduce);
+ *    BLOK_ERR_OOM.  An empty region is BLOK_OK with zero counts and an empty snapshot.  out_info may be NULL. */
+#define BLOK_LOD_VOTE_EXPOSED 1u      /* exposed cells alone vote where a coarse cell has any */
+#define BLOK_LOD_MAX_LEVELS 5u
+typedef struct blok_lod_level {
+    int32_t  clo[3];                  /* the level's grid: first cell, in units of 2^level world voxels */
+    uint32_t cext[3];
+    uint64_t n_cells, n_filled, n_exposed, sum_n, sum_e;
+} blok_lod_level;                     /* 64 bytes */
+typedef struct blok_lod_info {
+    uint32_t version, flags, levels, reserved;
+    int32_t  lo[3];                   /* the region, world voxels */
+    uint32_t ext[3];
+    blok_lod_level level[5];          /* level j at [j - 1] */
+} blok_lod_info;                      /* 360 bytes */
+int blok_hip_volume_reduce(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t levels, uint32_t flags,
+                           blok_lod_info* out_info);
+int blok_hip_volume_lod_info(blok_hip_ctx* ctx, blok_lod_info* out_info);
+int blok_hip_volume_lod_download(blok_hip_ctx* ctx, uint32_t level, uint32_t plane, void* out_host, uint64_t first, uint64_t count);
+int blok_hip_volume_lod_model(blok_hip_ctx* ctx, uint32_t level, uint32_t min_count, uint32_t* out_model, uint64_t* out_n_voxels);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

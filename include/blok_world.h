@@ -315,6 +315,17 @@ int blok_shape_bounds(const blok_shape* shape, int32_t out_lo[3], int32_t out_hi
 int blok_shapes_voxels(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
                        const blok_shape* shapes, uint32_t n_shapes, uint64_t* out_n_written);
 
+/* -------------------------------------------------------------- the pyramid of coarser levels on the host (lod.cpp)
+ * The contract of blok_hip_volume_reduce (blok_hip.h; the records and the flag are declared there) over host arrays of a box as above,
+ * through the rules the kernels use.  The planes lie in one array, level behind level from level 1, and within a level of n_cells cells the
+ * n plane (uint16_t) at byte 0, the e plane (uint16_t) at byte 2 n_cells and the id plane (uint32_t) at byte 4 n_cells: 8 n_cells bytes a
+ * level.  With out_planes NULL nothing is reduced: *out_info takes the grids of the levels with zero counts, which say what the array must
+ * hold.  Otherwise capacity_bytes below that sum, or a NULL array with a non-empty region, is BLOK_ERR_INVALID_ARG, and *out_info (may be
+ * NULL) takes what the device's info holds.  Errors as the device entry. */
+int blok_lod_reduce(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                    const int32_t region_lo[3], const int32_t region_hi[3], uint32_t levels, uint32_t flags, void* out_planes,
+                    uint64_t capacity_bytes, blok_lod_info* out_info);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

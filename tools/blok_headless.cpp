@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -11,6 +11,11 @@
 //   --scroll DX,DY,DZ: with --terrain, after the fill: the box is moved through the world by that many voxels (multiples of 4,
 //          blok_hip_volume_scroll), the same terrain is generated into each box that came into view, and the camera moves with the box:
 //          the frame shows the terrain as a box generated whole at the new place would.
+//   --lod K[,MIN]: with --terrain, once the terrain's world is built: the whole box is reduced K times (1 .. 5) on the device
+//          (blok_hip_volume_reduce with BLOK_LOD_VOTE_EXPOSED), level K alone is downloaded — 8^K times fewer cells than the volume — the
+//          volume is released, and the coarse cells that hold at least MIN (default 1) filled voxels are installed as the world at voxel
+//          size 2^K (blok_hip_set_voxel_size + blok_hip_upload_dense), cell C covering world [C 2^K, (C + 1) 2^K): the frames show the far-field
+//          copy of the terrain from the unchanged camera.
 //   --stroke X,Y,Z:X,Y,Z:...,R[,OP]: with --terrain, --obj or --load-volume, before the rebuild: a brush of radius R dragged through the world
 //          points (voxels; multiples of one half: W.5 is the centre of voxel W), as one table of capsules in one pass
 //          (blok_hip_volume_apply_shapes); OP is add (the default, density 1), subtract (density 0), erase, set, keep or paint (the last
@@ -81,6 +86,7 @@ struct Options {
     uint32_t seal_material = 0;
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
     bool scroll = false;                  // move the terrain's box by scroll_delta after the fill
+    uint32_t lod = 0, lod_min = 1;        // > 0: render level `lod` of the terrain's pyramid, the cells with at least lod_min filled voxels
     std::vector<std::array<int32_t, 3>> stroke;      // the points of --stroke, half-voxel units
     uint32_t stroke_radius = 0, stroke_op = BLOK_SHAPE_ADD;
     int32_t scroll_delta[3] = {0, 0, 0};
@@ -105,7 +111,8 @@ private:
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
                 if (!m_opt.load_volume.empty()) { initLoaded(); exportObj(); components(); settle(); saveVolume(); break; }
-                if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); saveVolume(); break; }
+                if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); saveVolume(); lod(); break; }
+                if (m_opt.lod) throw std::runtime_error("--lod needs a terrain: --terrain");
                 if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); settle(); saveVolume(); break; }
                 if (!m_opt.export_obj.empty()) throw std::runtime_error("--export-obj needs a resident volume: --terrain or --obj");
                 if (m_opt.components) throw std::runtime_error("--components needs a resident volume: --terrain or --obj");
@@ -348,6 +355,31 @@ private:
         const uint64_t cleared = m_tracer->editByDistance(BLOK_DISTANCE_HOLLOW, d2);
         std::cout << "hollow: " << cleared << " voxels cleared, " << info.n_near + info.n_far - cleared << " left\n";      // (the filled cells are those with D > 0)
     }
+    // The far-field copy of the terrain in place of the terrain: level K of the whole box's pyramid, installed as a dense world of voxel size 2^K.
+    void lod() {
+        if (!m_opt.lod) return;
+        if (!m_instances.empty()) throw std::runtime_error("--lod shows the coarse world alone: --populate needs --bake with it");
+        const uint32_t K = m_opt.lod;
+        const blok_lod_info info = m_tracer->reduceVolume(nullptr, nullptr, K, BLOK_LOD_VOTE_EXPOSED);
+        const blok_lod_level& L = info.level[K - 1];
+        const std::vector<uint16_t> n = m_tracer->downloadLod<uint16_t>(K, 0);
+        std::vector<uint32_t> ids = m_tracer->downloadLod<uint32_t>(K, 2);
+        uint64_t voxels = 0;
+        for (size_t i = 0; i < ids.size(); ++i) {
+            if (n[i] < m_opt.lod_min) ids[i] = 0u;            // the dense form: 0 = empty ...
+            else { ++voxels; if (!ids[i]) ids[i] = 1u; }      // ... so a filled cell whose voted id is 0 takes the first material
+        }
+        std::cout << "lod: level " << K << ": " << L.n_filled << " of " << L.n_cells << " cells filled, " << L.n_exposed << " exposed, " << voxels << " voxels at min "
+                  << m_opt.lod_min << "\n";
+        if (!voxels) throw std::runtime_error("--lod: no coarse cell holds that many voxels");
+        const auto must = [&](int rc) { if (rc != BLOK_OK) throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_tracer->handle())); };
+        must(blok_hip_volume_destroy(m_tracer->handle()));
+        m_tracer->setVoxelSize(static_cast<float>(1u << K));
+        const std::vector<blok_material> materials = m_materials.packForGpu();
+        must(blok_hip_upload_dense(m_tracer->handle(), ids.data(), L.cext[0], L.cext[1], L.cext[2], L.clo, materials.data(), materials.size()));
+        const blok_world_stats s = m_tracer->worldStats();
+        std::cout << "world: " << s.n_voxels << " voxels of size " << (1u << K) << ", " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
+    }
     // A brush dragged through the points of --stroke: the capsules from each point to the next, applied as one table in one pass.
     void stroke() {
         if (m_opt.stroke.empty()) return;
@@ -577,6 +609,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--hollow")) { opt.hollow = std::atoll(next()); if (opt.hollow < 0 || opt.hollow > 65025) { std::fprintf(stderr, "--hollow takes a squared distance in 0..65025\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--populate")) { for (std::string list = next(); !list.empty();) { const size_t c = list.find(','); opt.populate.push_back(list.substr(0, c)); list = c == std::string::npos ? "" : list.substr(c + 1); } }
         else if (!std::strcmp(argv[i], "--bake")) opt.bake = true;
+        else if (!std::strcmp(argv[i], "--lod")) {
+            const int got = std::sscanf(next(), "%u,%u", &opt.lod, &opt.lod_min);
+            if (got < 1 || opt.lod < 1 || opt.lod > BLOK_LOD_MAX_LEVELS || opt.lod_min < 1 || opt.lod_min > (1u << (3u * opt.lod))) { std::fprintf(stderr, "--lod takes K[,MIN] with K in 1..5 and MIN in 1..8^K\n"); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--scroll")) { opt.scroll = true; if (std::sscanf(next(), "%d,%d,%d", &opt.scroll_delta[0], &opt.scroll_delta[1], &opt.scroll_delta[2]) != 3) { std::fprintf(stderr, "--scroll takes DX,DY,DZ\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--stroke")) { if (!parseStroke(next(), opt)) { std::fprintf(stderr, "--stroke takes X,Y,Z:X,Y,Z:...,R[,add|subtract|erase|set|keep|paint], coordinates and R in multiples of one half\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
