@@ -449,6 +449,8 @@ HIP_SYMBOLS = {
     "blok_hip_abi_version": (C.c_uint32, []),
     "blok_hip_model_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "blok_hip_model_destroy": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "blok_hip_model_set_scale": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "blok_hip_model_scale": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "blok_hip_check_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "blok_hip_trace_primary_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4),
     "blok_hip_trace_primary_instanced": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3),

@@ -60,6 +60,8 @@ int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_mater
     for (int a = 0; a < 3; ++a) ctx->stats.origin[a] = tree.origin[a];
     ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
     ctx->world_voxel_size = ctx->pending_voxel_size;
+    const int rc_models = models_follow_voxel_size(ctx);
+    if (rc_models != BLOK_OK) return rc_models;
     return rebuild_sun_map(ctx);
 }
 
@@ -282,7 +284,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 16u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 17u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -400,6 +402,8 @@ int blok_hip_upload_world(blok_hip_ctx* ctx, const blok_svo_node* nodes, size_t 
             ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
             ctx->built_on_device = true;
             ctx->world_voxel_size = vs;
+            const int rc_models = models_follow_voxel_size(ctx);
+            if (rc_models != BLOK_OK) return rc_models;
             return rebuild_sun_map(ctx);
         }
     }
@@ -489,6 +493,8 @@ int blok_hip_upload_dense(blok_hip_ctx* ctx, const uint32_t* ids, uint32_t nx, u
             ctx->has_world = true; ctx->world_version += 1u; ctx->tree_version += 1u;
             ctx->built_on_device = true;
             ctx->world_voxel_size = vs;
+            const int rc_models = models_follow_voxel_size(ctx);
+            if (rc_models != BLOK_OK) return rc_models;
             const int rc_sun = rebuild_sun_map(ctx);
             if (rc_sun != BLOK_OK || !keep_grid) return rc_sun;
             return keep_dense_grid(ctx, ids, nx, ny, nz, o);

@@ -34,15 +34,17 @@ int blok_hip_download_model(blok_hip_ctx* ctx, uint32_t model, void* nodes_out, 
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     const blok::ModelDesc& m = ctx->models.desc[model];
-    if ((nodes_out && node_capacity < m.n_nodes) || (materials_out && material_capacity < m.n_materials))
+    const uint32_t n_nodes = ctx->models.own[model].n_nodes, n_materials = ctx->models.own[model].n_materials;
+    if ((nodes_out && node_capacity < n_nodes) || (materials_out && material_capacity < n_materials))
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "download_model: output smaller than the model's array");
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (nodes_out && m.n_nodes) BLOK_HIP_TRY(ctx, hipMemcpy(nodes_out, m.nodes, m.n_nodes * sizeof(blok::TreeNode), hipMemcpyDeviceToHost));
-    if (materials_out && m.n_materials) BLOK_HIP_TRY(ctx, hipMemcpy(materials_out, m.materials, m.n_materials * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (nodes_out && n_nodes) BLOK_HIP_TRY(ctx, hipMemcpy(nodes_out, m.nodes, n_nodes * sizeof(blok::TreeNode), hipMemcpyDeviceToHost));
+    if (materials_out && n_materials) BLOK_HIP_TRY(ctx, hipMemcpy(materials_out, m.materials, n_materials * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_info) {
         out_info->levels = m.levels;
-        for (int a = 0; a < 3; ++a) { out_info->origin[a] = m.origin[a]; out_info->lo[a] = m.lo[a]; out_info->hi[a] = m.hi[a]; }
-        out_info->n_nodes = m.n_nodes; out_info->n_materials = m.n_materials;
+        const auto& own = ctx->models.own[model];        // (the box in the model's own voxels, whatever its scale)
+        for (int a = 0; a < 3; ++a) { out_info->origin[a] = m.origin[a]; out_info->lo[a] = own.box_lo[a]; out_info->hi[a] = own.box_hi[a]; }
+        out_info->n_nodes = n_nodes; out_info->n_materials = n_materials;
     }
     return BLOK_OK;
 }

@@ -9,12 +9,18 @@ namespace blok_api {
 namespace {
 
 // The device copy of the descriptors after a change (the callers have synchronised the device), and the LDS stack the kernels need.
+// The limit of a scaled model's voxel size is settled here, once per model: the kernels see such a model as they see a destroyed one.
 int upload_models(blok_hip_ctx* ctx) {
     auto& M = ctx->models;
     if (M.d_desc.capacity() < M.desc.size())
         BLOK_HIP_TRY(ctx, M.d_desc.reserve(std::max<size_t>(16, M.desc.size() * 2), blok::FreeAfter::nothing()));
-    if (!M.desc.empty())
-        BLOK_HIP_TRY(ctx, hipMemcpy(M.d_desc, M.desc.data(), M.desc.size() * sizeof(blok::ModelDesc), hipMemcpyHostToDevice));
+    if (!M.desc.empty()) {
+        std::vector<blok::ModelDesc> copy = M.desc;
+        for (blok::ModelDesc& m : copy)
+            if (!blok::model_size_usable(m, ctx->world_voxel_size)) m.nodes = nullptr;
+        BLOK_HIP_TRY(ctx, hipMemcpy(M.d_desc, copy.data(), copy.size() * sizeof(blok::ModelDesc), hipMemcpyHostToDevice));
+    }
+    M.uploaded_voxel_size = ctx->world_voxel_size;
     uint32_t slots = 1;
     for (const auto& m : M.desc)
         if (m.nodes && m.levels > 1) slots = std::max(slots, m.levels - 1u);
@@ -36,6 +42,8 @@ int check_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) {
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "unknown model " + std::to_string(I.model));
         if (!blok::instance_usable(I, ctx->models.desc[I.model]))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "world box outside the int16 lattice of hit records");
+        if (!blok::model_size_usable(ctx->models.desc[I.model], ctx->world_voxel_size))
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "the scaled model's voxel size (world voxel size * 2^scale) is above 256");
     }
     return BLOK_OK;
 }
@@ -82,7 +90,33 @@ blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs&
 
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) { return check_table(ctx, inst, n); }
 
+int refuse_scaled_model(blok_hip_ctx* ctx, const char* op, uint32_t model) {
+    if (model < ctx->models.desc.size() && ctx->models.desc[model].nodes && ctx->models.desc[model].scale_log2 != 0u)
+        return set_error(ctx, BLOK_ERR_UNSUPPORTED, std::string(op) + ": model " + std::to_string(model) + " has a scale (blok_hip_model_set_scale); the volume takes scale-0 models only");
+    return BLOK_OK;
+}
+
+int models_follow_voxel_size(blok_hip_ctx* ctx) {
+    auto& M = ctx->models;
+    if (M.uploaded_voxel_size == ctx->world_voxel_size) return BLOK_OK;
+    bool changes = false;
+    blok::ModelDesc probe{};
+    for (const blok::ModelDesc& m : M.desc) {
+        probe.scale_log2 = m.scale_log2;
+        changes = changes || (m.nodes && blok::model_size_usable(probe, M.uploaded_voxel_size) != blok::model_size_usable(probe, ctx->world_voxel_size));
+    }
+    if (!changes) { M.uploaded_voxel_size = ctx->world_voxel_size; return BLOK_OK; }
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());           // frames in flight read the descriptor array
+    return upload_models(ctx);
+}
+
 int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, blok_hip_ctx::Models::Arrays own, uint32_t* out_model) {
+    // a new model has scale 0: its descriptor's box is the box in its own voxels, which the store keeps for blok_hip_model_set_scale.
+    // Every producer's box lies within 2^17 of the model's origin (the lattice of the records, a volume's extent), so its 2^8-fold fits.
+    for (int a = 0; a < 3; ++a) {
+        if (m.lo[a] < -(1 << 22) || m.hi[a] > (1 << 22)) return set_error(ctx, BLOK_ERR_INTERNAL, "model box beyond 2^22 voxels");
+        own.box_lo[a] = m.lo[a]; own.box_hi[a] = m.hi[a];
+    }
     // frames in flight may read the descriptor array that the upload replaces
     hipError_t e = hipDeviceSynchronize();
     int rc = BLOK_OK;
@@ -140,7 +174,7 @@ int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t*
     if (e == hipSuccess) e = hipMemcpy(own.materials, tree.materials.data(), mat_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("model upload: ") + hipGetErrorString(e));
     m.nodes = own.nodes; m.materials = own.materials; m.levels = tree.levels;
-    m.n_nodes = static_cast<uint32_t>(tree.nodes.size()); m.n_materials = static_cast<uint32_t>(tree.materials.size());
+    own.n_nodes = static_cast<uint32_t>(tree.nodes.size()); own.n_materials = static_cast<uint32_t>(tree.materials.size());
     for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = lo[a]; m.hi[a] = hi[a] + 1; }
     return add_model(ctx, m, std::move(own), out_model);
 }
@@ -154,6 +188,35 @@ int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
     ctx->models.own[model] = blok_hip_ctx::Models::Arrays{};
     ctx->models.desc[model] = blok::ModelDesc{};         // the id stays taken and unknown
     return upload_models(ctx);
+}
+
+int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_log2) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    if (scale_log2 > blok::kMaxScaleLog2)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_set_scale: scale_log2 above " + std::to_string(blok::kMaxScaleLog2));
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());           // frames in flight read the descriptor the upload replaces
+    blok::ModelDesc& d = ctx->models.desc[model];
+    const blok::ModelDesc before = d;
+    const auto& own = ctx->models.own[model];
+    d.scale_log2 = scale_log2;
+    for (int a = 0; a < 3; ++a) { d.lo[a] = own.box_lo[a] * (1 << scale_log2); d.hi[a] = own.box_hi[a] * (1 << scale_log2); }      // (|box| <= 2^22: add_model)
+    const int rc = upload_models(ctx);
+    if (rc != BLOK_OK) { d = before; return rc; }
+    // the object-motion map (instance_motion.h) does not hold across a change of scale: the next frame's instances are untracked
+    ctx->post.rt_prev_n = 0u;
+    return BLOK_OK;
+}
+
+int blok_hip_model_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t* out_scale_log2) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    if (!out_scale_log2) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_scale: null output");
+    *out_scale_log2 = ctx->models.desc[model].scale_log2;
+    return BLOK_OK;
 }
 
 int blok_hip_check_instances(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n_instances) {

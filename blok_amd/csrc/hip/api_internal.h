@@ -251,10 +251,17 @@ struct blok_hip_ctx {
     // instanced voxel models (api_instances.hip): descriptors indexed by model id (a destroyed model keeps its slot with nodes == null),
     // the owners of their arrays under the same index, their device copy, and the LDS stack slots the deepest live model needs
     struct Models {
-        struct Arrays { blok::DeviceArray<uint4> nodes; blok::DeviceArray<uint32_t> materials; };
+        // (with what the kernels never look at and their descriptor has no room for: the arrays' lengths, and the model's box in its own
+        // voxels, of which the descriptor's box is the 2^e-fold)
+        struct Arrays {
+            blok::DeviceArray<uint4> nodes; blok::DeviceArray<uint32_t> materials;
+            uint32_t n_nodes = 0, n_materials = 0;
+            int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+        };
         std::vector<blok::ModelDesc> desc;
         std::vector<Arrays> own;
-        blok::DeviceArray<blok::ModelDesc> d_desc;
+        blok::DeviceArray<blok::ModelDesc> d_desc;      // the kernels' copy: nodes = null also where vs * 2^e is above the limit ...
+        float uploaded_voxel_size = 1.0f;               // ... for this voxel size of the world (models_follow_voxel_size)
         uint32_t stack_levels = 1;
     } models;
     // timing
@@ -318,10 +325,16 @@ void scroll_volume_snapshots(blok_hip_ctx* ctx, const int32_t delta[3]);
 // api_instances.hip
 // The limits of blok_hip.h for a host table: BLOK_OK or BLOK_ERR_INVALID_ARG naming the first instance that breaks one.
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n);
+// The volume entries' rule for a model id they are handed (a placement's, a scatter entry's): BLOK_ERR_UNSUPPORTED for a live model whose
+// scale is not 0 (baking a scaled model is not built), else BLOK_OK.  An unknown id is the caller's other checks' business.
+int refuse_scaled_model(blok_hip_ctx* ctx, const char* op, uint32_t model);
 // The tail of every entry that makes a model (blok_hip_model_create, blok_hip_volume_capture_model): takes the two device arrays into the
 // store under the next id, refreshes the device copy of the descriptors and the stack depth the kernels need.  Synchronises the device.
 // On failure the arrays are freed (they are `own`'s from the call on) and no id is consumed.
 int add_model(blok_hip_ctx* ctx, const blok::ModelDesc& m, blok_hip_ctx::Models::Arrays own, uint32_t* out_model);
+// After a world with another voxel size was installed: the device copy of the descriptors is written again if some scaled model's voxel
+// size has come above or below the limit with it (it then waits for the device first).  Nothing to do while every model has scale 0.
+int models_follow_voxel_size(blok_hip_ctx* ctx);
 // The id plane and both tables of an object-motion pass (instance_motion.h) with the context's model store and voxel size.
 blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
                                  uint32_t n_prev);

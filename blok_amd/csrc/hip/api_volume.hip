@@ -78,6 +78,14 @@ int need_volume(blok_hip_ctx* ctx) {
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return BLOK_OK;
 }
+// A table that has passed check_instance_table: BLOK_ERR_UNSUPPORTED if any of its models has a scale (nothing has been touched yet).
+int refuse_scaled_table(blok_hip_ctx* ctx, const char* op, const blok_instance* placements, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const int rc = refuse_scaled_model(ctx, op, placements[i].model);
+        if (rc != BLOK_OK) return rc;
+    }
+    return BLOK_OK;
+}
 // The models of a table that has passed check_instance_table, as the stamp and the sweep read them.
 std::vector<blok::StampModel> placed_models(const blok_hip_ctx* ctx, const blok_instance* placements, uint32_t n) {
     std::vector<blok::StampModel> models(n);
@@ -101,9 +109,9 @@ int volume_region(blok_hip_ctx* ctx, const char* op, const int32_t* region_lo, c
 int add_captured_model(blok_hip_ctx* ctx, const blok::GpuTree& tree, const int32_t box_lo[3], const int32_t box_hi[3], uint32_t* out_model) {
     blok::ModelDesc m{};
     m.nodes = tree.d_nodes; m.materials = tree.d_materials; m.levels = tree.levels;
-    m.n_nodes = static_cast<uint32_t>(tree.n_nodes); m.n_materials = static_cast<uint32_t>(tree.n_voxels);
     for (int a = 0; a < 3; ++a) { m.origin[a] = tree.origin[a]; m.lo[a] = box_lo[a]; m.hi[a] = box_hi[a]; }
     blok_hip_ctx::Models::Arrays own;
+    own.n_nodes = static_cast<uint32_t>(tree.n_nodes); own.n_materials = static_cast<uint32_t>(tree.n_voxels);
     own.nodes.adopt(tree.d_nodes, tree.n_nodes); own.materials.adopt(tree.d_materials, tree.n_voxels);
     return add_model(ctx, m, std::move(own), out_model);
 }
@@ -269,6 +277,7 @@ int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placeme
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
     rc = check_instance_table(ctx, placements_host, n_placements);
+    if (rc == BLOK_OK) rc = refuse_scaled_table(ctx, "stamp_models", placements_host, n_placements);
     if (rc != BLOK_OK) return rc;
     if (!blok::stamp::mode_known(mode)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_models: unknown mode");
     if (mode != BLOK_STAMP_ERASE && (!std::isfinite(density) || !(density > 0.0f)))
@@ -394,6 +403,7 @@ int blok_hip_volume_sweep_models(blok_hip_ctx* ctx, const blok_instance* placeme
     int rc = need_volume(ctx);
     if (rc != BLOK_OK) return rc;
     rc = check_instance_table(ctx, placements_host, n_placements);      // the stamp's check, with its messages
+    if (rc == BLOK_OK) rc = refuse_scaled_table(ctx, "sweep_models", placements_host, n_placements);
     if (rc != BLOK_OK) return rc;
     if (!blok::sweep::direction_known(direction)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sweep_models: direction above 5");
     if (!blok::sweep::flags_known(flags)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "sweep_models: unknown flag bits");
@@ -663,6 +673,10 @@ int blok_hip_volume_scatter_models(blok_hip_ctx* ctx, const blok_scatter_params*
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (const int rule = blok::columns::check_scatter_args(ctx->columns.taken ? &ctx->columns.info : nullptr, params, entries_host, n_entries))
         return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("scatter_models: ") + blok::columns::scatter_rule_text(rule));
+    for (uint32_t i = 0; i < n_entries; ++i) {           // (the anchors are model voxels: a scaled model's would not land on the cell)
+        const int rc = refuse_scaled_model(ctx, "scatter_models", entries_host[i].model);
+        if (rc != BLOK_OK) return rc;
+    }
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::string why;
     blok::GpuScatter table;
@@ -836,6 +850,8 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
     // per frame with the order kept, 270 with it dropped)
     ctx->order.interval_now = ctx->order.interval;
     ctx->built_on_device = true;
+    const int rc_models = models_follow_voxel_size(ctx);       // (the volume's world has voxel size 1: behind another world's, scaled models may be back under their limit)
+    if (rc_models != BLOK_OK) return rc_models;
     if (same_lattice) { ctx->d_sun_map = std::move(keep_sun); ctx->has_sun_map = keep_has_sun; }
     const auto t_installed = std::chrono::steady_clock::now();
     // a fill of the whole box is a new world to the map: raised over every texel it would stay loose until kSunMapLooseEdits further

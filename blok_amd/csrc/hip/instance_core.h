@@ -6,6 +6,11 @@
 // the composed record is specified bit for bit:
 //   o'_k = s_k * fl(o[axis[k]] - offset[axis[k]] * vs),   d'_k = s_k * d[axis[k]],   tmin, tmax unchanged      (s_k = flip bit k ? -1 : +1)
 //   world voxel  w[axis[k]] = flip_k ? offset[axis[k]] - 1 - v'_k : offset[axis[k]] + v'_k;   face 2k + n -> 2 axis[k] + (n ^ flip_k)
+// A model carries a scale exponent e (ModelDesc::scale_log2, 0 .. kMaxScaleLog2): one model voxel is a cube of 2^e world voxels.  The ray
+// above is unchanged (the offset stays in world voxels); the walk and the local box test take the model's voxel size vm = vs * 2^e and
+// 1 / vm, both exact powers of two; t, material and face are unchanged, and the record's voxel is the cell's lowest world voxel:
+//   w[axis[k]] = flip_k ? offset[axis[k]] - (v'_k + 1) * 2^e : offset[axis[k]] + v'_k * 2^e
+// The shift happens once, in instance_record; the walk never sees it.
 // Candidates are taken world first, then instance 0, 1, ...; one replaces the record only with a strictly smaller t, which is what a
 // walk with tmax = the best t so far does (the walk's acceptance test is t < tmax).
 //
@@ -25,15 +30,19 @@
 
 namespace blok {
 
-// A model as the kernels see it: its tree (tree.h) and its local box of filled voxels [lo, hi) (local voxel coordinates).
-// nodes == null: a destroyed model (any instance of it is skipped).
+// A model as the kernels see it: its tree (tree.h) and the box of its filled voxels [lo, hi) in WORLD voxels from an instance's offset:
+// the model's box in its own voxels times 2^e, scaled once by the store (api_instances.hip), so that an instance's span is an add and the
+// local box test is [lo, hi) * vs whatever the scale.  nodes == null: a model no instance of which is traced (any is skipped) — a
+// destroyed one, or, in the store's device copy, one whose voxel size vs * 2^e is above kMaxModelVoxelSize in the installed world.
 struct ModelDesc {
     const uint4*    nodes;
     const uint32_t* materials;
     uint32_t levels;
     int32_t  origin[3];
     int32_t  lo[3], hi[3];
-    uint32_t n_nodes, n_materials;   // lengths of the two arrays (the kernels never look at them; blok_hip_download_model does)
+    uint32_t scale_log2;             // e: one model voxel is 2^e world voxels on a side (zero-initialised: scale 1).  The store keeps
+                                     // e <= kMaxScaleLog2 (blok_hip_model_set_scale refuses more)
+    uint32_t reserved;               // (the arrays' lengths live on the host side of the store: the kernels never read them)
 };
 static_assert(sizeof(ModelDesc) == 64, "one model descriptor is 64 bytes");
 static_assert(sizeof(blok_instance) == 32, "one instance record is 32 bytes");
@@ -41,6 +50,9 @@ static_assert(sizeof(blok_instance) == 32, "one instance record is 32 bytes");
 constexpr uint32_t kInstanceNone = 0xFFFFFFFFu;
 // A hit record's voxel is int16: every instance's world box must lie in [kLatticeMin, kLatticeMax) on every axis.
 constexpr int64_t kLatticeMin = -32768, kLatticeMax = 32768;
+// The largest scale exponent of a model, and the largest voxel size a model may be walked at (vs * 2^e; the walk is exact up to it).
+constexpr uint32_t kMaxScaleLog2 = 8;
+constexpr float kMaxModelVoxelSize = 256.0f;
 
 // Component `a` (0, 1, 2) of a triple, by selects: the permutation is data, and an array indexed by it would live in scratch.
 BLOK_HD float pick3(uint32_t a, float x, float y, float z) { return a == 0u ? x : (a == 1u ? y : z); }
@@ -48,7 +60,16 @@ BLOK_HD int32_t pick3(uint32_t a, int32_t x, int32_t y, int32_t z) { return a ==
 // The local axis k with axis[k] == a.
 BLOK_HD uint32_t local_axis(const blok_instance& I, uint32_t a) { return I.axis[0] == a ? 0u : (I.axis[1] == a ? 1u : 2u); }
 
-// The instance's world box in voxels along world axis a: [lo, hi).
+// The model's voxel size vm = vs * 2^e and its inverse from the world's: vs is a power of two, so adding e to the exponent field is the
+// exact product, in integer arithmetic (scalar registers where M and vs are wave-uniform).  e <= kMaxScaleLog2 (the store's invariant).
+BLOK_HD float model_voxel_size(const ModelDesc& M, float vs) {
+    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, vs) + (M.scale_log2 << 23));
+}
+BLOK_HD float model_inv_voxel_size(const ModelDesc& M, float inv_vs) {
+    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, inv_vs) - (M.scale_log2 << 23));
+}
+
+// The instance's world box in world voxels along world axis a: [lo, hi)  (the descriptor's box is in world voxels already).
 BLOK_HD void instance_world_span(const blok_instance& I, const ModelDesc& M, uint32_t a, int64_t& lo, int64_t& hi) {
     const uint32_t k = local_axis(I, a);
     const int64_t o = pick3(a, I.offset[0], I.offset[1], I.offset[2]);
@@ -72,6 +93,11 @@ BLOK_HD bool instance_usable(const blok_instance& I, const ModelDesc& M) {
     return true;
 }
 
+// The limit of a model's voxel size in a world of voxel size vs.  It is a property of the model and the world, not of an instance: the
+// host entries ask it per table entry for their messages, and the store asks it once per model when it writes the device copy of the
+// descriptors (nodes = null where it fails), so the kernels' instance_usable above needs no more than it did before models had a scale.
+BLOK_HD bool model_size_usable(const ModelDesc& M, float vs) { return model_voxel_size(M, vs) <= kMaxModelVoxelSize; }
+
 // The ray in the model's local space (one rounding per axis: the subtraction).  vs: the world's voxel size.
 BLOK_DEV float local_origin(const blok_instance& I, float vs, const RayIn& r, uint32_t k) {
     const uint32_t a = I.axis[k];
@@ -91,7 +117,8 @@ BLOK_DEV RayIn instance_ray(const blok_instance& I, float vs, const RayIn& r) {
     return t;
 }
 
-// Does the local ray's interval [tmin, tmax) meet the model's box [lo, hi) * vs?  The planes' T are the walk's own formula
+// Does the local ray's interval [tmin, tmax) meet the model's box [lo, hi) * vs (world voxels; the same planes as the model's own box
+// times vm = vs * 2^e, bit for bit: a power of two moves from one factor to the other exactly)?  The planes' T are the walk's own formula
 // (trace_kernels.h: T = fl(fl(p - o) * inv)), and every voxel's planes lie between the box planes, so a reported voxel's interval is
 // inside the box's: the test never rejects a ray the walk would report a voxel for.
 BLOK_DEV void box_axis(int32_t lo, int32_t hi, float vs, float o, float d, float& enter, float& leave) {
@@ -109,33 +136,39 @@ BLOK_DEV bool instance_box_entered(const ModelDesc& M, float vs, const RayIn& r)
     return enter < leave;
 }
 
-// The walk's arguments for a model (world voxel size and material table; no camera, no outputs).
+// The walk's arguments for a model in a world of voxel size vs (the model's own voxel size and material table; no camera, no outputs).
 BLOK_DEV TraceArgs model_args(const ModelDesc& M, float vs, float inv_vs) {
     TraceArgs a{};
     a.nodes = M.nodes;
     a.materials = M.materials;
     a.origin[0] = M.origin[0]; a.origin[1] = M.origin[1]; a.origin[2] = M.origin[2];
     a.levels = M.levels;
-    a.voxel_size = vs; a.inv_voxel_size = inv_vs;
+    a.voxel_size = model_voxel_size(M, vs); a.inv_voxel_size = model_inv_voxel_size(M, inv_vs);
     return a;
 }
 
-// A local hit as a world record (the 16-byte blok_hit layout, trace_core.h: trace_one).
-BLOK_DEV int32_t world_voxel(const blok_instance& I, const HitInfo& h, uint32_t a) {
+// A local hit as a world record (the 16-byte blok_hit layout, trace_core.h: trace_one).  e: the model's scale exponent; the voxel is the
+// hit cell's lowest world voxel.  The record keeps its low 16 bits, and those of the wrapping 32-bit sum here are those of the exact
+// (64-bit) sum of the rule; a usable instance's cells all lie in the int16 lattice, so nothing is lost.
+BLOK_DEV int32_t world_voxel(const blok_instance& I, const HitInfo& h, uint32_t a, uint32_t e) {
     const uint32_t k = local_axis(I, a);
-    const int32_t v = pick3(k, h.vx, h.vy, h.vz), o = pick3(a, I.offset[0], I.offset[1], I.offset[2]);
-    return ((I.flip >> k) & 1u) ? o - 1 - v : o + v;
+    const uint32_t v = static_cast<uint32_t>(pick3(k, h.vx, h.vy, h.vz)), o = static_cast<uint32_t>(pick3(a, I.offset[0], I.offset[1], I.offset[2]));
+    return static_cast<int32_t>(((I.flip >> k) & 1u) ? o - ((v + 1u) << e) : o + (v << e));
 }
-BLOK_DEV uint4 instance_record(const blok_instance& I, const HitInfo& h) {
+BLOK_DEV uint4 instance_record(const blok_instance& I, const HitInfo& h, uint32_t e) {
     const uint32_t fk = h.face >> 1, fn = h.face & 1u;
     const uint32_t face = 2u * pick3(fk, int32_t(I.axis[0]), int32_t(I.axis[1]), int32_t(I.axis[2])) + (fn ^ ((I.flip >> fk) & 1u));
     uint4 rec;
     rec.x = __float_as_uint(h.t);
     rec.y = h.material;
-    rec.z = (static_cast<uint32_t>(world_voxel(I, h, 0u)) & 0xFFFFu) | (static_cast<uint32_t>(world_voxel(I, h, 1u)) << 16);
-    rec.w = (static_cast<uint32_t>(world_voxel(I, h, 2u)) & 0xFFFFu) | (face << 16) | (1u << 24);
+    rec.z = (static_cast<uint32_t>(world_voxel(I, h, 0u, e)) & 0xFFFFu) | (static_cast<uint32_t>(world_voxel(I, h, 1u, e)) << 16);
+    rec.w = (static_cast<uint32_t>(world_voxel(I, h, 2u, e)) & 0xFFFFu) | (face << 16) | (1u << 24);
     return rec;
 }
+#ifdef BLOK_TRACE_HOST_HARNESS
+// (for the host shims that map records of scale-0 models; device code always says which scale)
+inline uint4 instance_record(const blok_instance& I, const HitInfo& h) { return instance_record(I, h, 0u); }
+#endif
 
 // One candidate: the instance's walk of world ray r with tmax = best_t.  true (and rec) iff it reports a voxel, whose t is then < best_t.
 BLOK_DEV bool instance_candidate(const blok_instance& I, const ModelDesc& M, float vs, float inv_vs, const RayIn& r, float best_t,
@@ -143,9 +176,19 @@ BLOK_DEV bool instance_candidate(const blok_instance& I, const ModelDesc& M, flo
     RayIn l = instance_ray(I, vs, r);
     l.tmax = best_t;
     if (!instance_box_entered(M, vs, l)) return false;
-    const HitInfo h = walk(model_args(M, vs, inv_vs), l, stk);
-    if (!h.found) return false;
-    rec = instance_record(I, h);
+    // walk() of trace_core.h, piece by piece.  Here the descriptor is per lane (the path kernel's leaves), so vm would be a vector value alive
+    // across the walk's loop beside the exponent; the loop itself does not read it, so it is formed again from the exponent behind the loop,
+    // for the hit's face — the exponent is then the one value a scaled model keeps alive where a scale-0 model kept none.
+    BLOK_STAT(4, 0);                       // a walk begins
+    TraceArgs a = model_args(M, vs, inv_vs);
+    const WalkRay R = walk_ray(a, l.ox, l.oy, l.oz, safe_inv(l.dx), safe_inv(l.dy), safe_inv(l.dz));
+    WalkState s;
+    walk_enter(a, R, l.tmin, l.tmax, s);
+    walk_loop(a, R, l.tmax, s, stk);
+    if (!s.found) return false;
+    const uint32_t e = as_written(M.scale_log2);
+    a.voxel_size = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, vs) + (e << 23));
+    rec = instance_record(I, walk_hit(a, l, R, s), e);
     return true;
 }
 

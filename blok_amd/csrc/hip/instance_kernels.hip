@@ -29,7 +29,7 @@ __device__ __forceinline__ void compose_instances(const InstanceArgs& P, const u
         if (__ballot(enters) == 0ull) continue;        // no lane of the wave enters the model's box
         if (enters) {
             const HitInfo h = walk(model_args(M, vs, inv_vs), l, stk);
-            if (h.found) { rec = instance_record(I, h); best = h.t; won = idx; }
+            if (h.found) { rec = instance_record(I, h, M.scale_log2); best = h.t; won = idx; }
         }
     }
 }

@@ -3,7 +3,9 @@
 // frame earlier.
 //
 // Tracking.  Instance i of this frame's table `cur` is tracked when i < n_prev, prev[i].model == cur[i].model and both records pass
-// instance_usable with that model's descriptor; otherwise it is untracked (it appeared this frame or changed model).
+// instance_usable with that model's descriptor; otherwise it is untracked (it appeared this frame or changed model).  The map below does
+// not contain the model's scale, and is wrong across a change of it: blok_hip_model_set_scale empties the context's previous table, and
+// callers of the *_device entries keep that rule themselves.
 //
 // The map.  §11's transform takes world point o to the model's local lattice as o'_k = s_k * (o[axis[k]] - offset[axis[k]] * vs).  For a
 // tracked instance, prev o cur^-1 moves a world point p on it (and its normal n) to the previous frame: for each local axis k, with

@@ -7,7 +7,7 @@
 //   next power of two >= n_instances).  Leaf P + j holds the j-th instance of the sorted order; leaves past the usable count are empty.
 //   Every node is 32 bytes: an int32 box [lo, hi) in world voxels, then `child` (an internal node: 2k; a leaf: kTlasLeaf | instance
 //   index; an empty leaf or a node over empty leaves only: kTlasEmpty) and `escape` (the node a depth-first walk visits after this node's subtree, 0 = the end).
-// Boxes.  A leaf's box is its instance's world box (instance_world_span) grown by kTlasPad voxels on every side; a parent's box is the
+// Boxes.  A leaf's box is its instance's world box (instance_world_span: world voxels, whatever the model's scale) grown by kTlasPad voxels on every side; a parent's box is the
 //   union of its children's.  The world-space slab test of a node therefore rejects only rays that no leaf below could report: the
 //   walk reports voxels in the model's local space, whose origin rounds differently, and one voxel of padding covers that by orders of
 //   magnitude.  A leaf then takes the exact local test (instance_box_entered, inside instance_candidate).

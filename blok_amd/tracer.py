@@ -881,6 +881,18 @@ class HipTracer:
     def model_destroy(self, model: int):
         self._check(self._lib.blok_hip_model_destroy(self._ctx, int(model)))
 
+    def model_set_scale(self, model: int, scale_log2: int):
+        """One model voxel becomes a cube of 2**scale_log2 world voxels (0..8; blok_hip.h: "Scaled models").  Blocks; the previous-frame
+        table of draw_frame_rt_instanced_motion is forgotten."""
+        if scale_log2 < 0:
+            raise ValueError("scale_log2 must be >= 0")
+        self._check(self._lib.blok_hip_model_set_scale(self._ctx, int(model), int(scale_log2)))
+
+    def model_scale(self, model: int) -> int:
+        out = C.c_uint32()
+        self._check(self._lib.blok_hip_model_scale(self._ctx, int(model), C.byref(out)))
+        return int(out.value)
+
     def model_download(self, model: int):
         """Diagnostic (blok_hip_debug.h: blok_hip_download_model): (nodes as (n, 4) uint32, material ids, info) of a model as it lies in
         device memory; info is a dict of levels, origin, lo, hi."""

@@ -534,6 +534,13 @@ public:
         return id;
     }
     void destroyModel(uint32_t model) { check(blok_hip_model_destroy(m_ctx, model)); }
+    // one model voxel = a cube of 2^scaleLog2 world voxels (0..8; blok_hip.h: "Scaled models"); blocks, and forgets the previous frame's table
+    void setModelScale(uint32_t model, uint32_t scaleLog2) { check(blok_hip_model_set_scale(m_ctx, model, scaleLog2)); }
+    uint32_t modelScale(uint32_t model) {
+        uint32_t e = 0;
+        check(blok_hip_model_scale(m_ctx, model, &e));
+        return e;
+    }
     // drawFrame over the world plus instances: records in hits(), the winning instance per pixel in instanceIds()
     void drawFrameInstanced(Camera& cam, const std::vector<blok_instance>& instances) {
         const blok_camera c = cam.basis(m_width, m_height);

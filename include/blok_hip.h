@@ -582,7 +582,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.14: the resident volume's box scrolled through the world in device memory.
  * 1.15: a table of integer shapes (box, ellipsoid, capsule, cylinder; set, keep, erase, paint, replace, add, subtract) applied to the
  *       resident volume in one pass.
- * 1.16: the resident volume reduced to a pyramid of coarser levels (counts and a voted material id per cell); a level as a model. */
+ * 1.16: the resident volume reduced to a pyramid of coarser levels (counts and a voted material id per cell); a level as a model.
+ * 1.17: a power-of-two scale on instanced models (blok_hip_model_set_scale): a coarse level traced at its true size beside the world. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -604,6 +605,20 @@ uint32_t blok_hip_abi_version(void);
  *   permutation, flip < 8, the reserved words zero, the model id one that exists.  The entries with host instance tables fail with
  *   BLOK_ERR_INVALID_ARG otherwise; the device entries cannot look at their table without a host synchronise, so their kernels skip
  *   any instance that fails these checks (check a table with blok_hip_check_instances).
+ * Scaled models.  A model has a scale exponent e, 0 <= e <= 8, default 0 (blok_hip_model_set_scale): one model voxel is a cube of 2^e world
+ *   voxels, wherever the model is placed.  With vm = vs * 2^e:
+ *   - Ray into local space: unchanged.  The offset stays in world voxels and need not be a multiple of 2^e.
+ *   - Walk: the canonical walk over the model's tree with voxel size vm and 1 / vm (exact powers of two); the local box test uses vm too.
+ *   - Record back to world space: t, material_id and the face rule unchanged.  The voxel is the hit cell's lowest world voxel:
+ *     w[axis[k]] = offset[axis[k]] + v'_k * 2^e if flip bit k is clear, offset[axis[k]] - (v'_k + 1) * 2^e if it is set (64-bit sums
+ *     before the record narrows them).  The instance id says which model was hit, and so which cell size.
+ *   - World span of an instance whose model box is [lo, hi) on the local axis that maps to world axis a, with o = offset[a]:
+ *     [o + lo * 2^e, o + hi * 2^e), or [o - hi * 2^e, o - lo * 2^e) when flipped.  The lattice limit below, the screen bins and the
+ *     BVH's leaf boxes use it.
+ *   - Limit: vm <= 256, checked where a table is checked (host tables: BLOK_ERR_INVALID_ARG naming the instance; device tables: skipped).
+ *   - Composition, the tie rule, the any-hit shadow rule and the BVH's ordering rule are unchanged, and so is the object-motion map
+ *     (it does not contain the scale).
+ *   Not built: negative exponents; baking a scaled model into the resident volume (the volume entries refuse one, below).
  * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
  * Scope.  The primary frame, explicit rays and the path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced
  *   below); the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay world-only (they never receive an
@@ -621,6 +636,16 @@ typedef struct blok_instance {
  * uploads it (every listed voxel is filled); *out_model is its id (ids are never reused).  Both calls may synchronise the device. */
 int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t* material_ids, size_t n, uint32_t* out_model);
 int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model);
+/* The model's scale exponent ("Scaled models" above).  Every entry that makes a model (blok_hip_model_create, the volume's capture_model,
+ * capture_component and lod_model) makes one of scale 0.  set_scale blocks, may synchronise the device and updates the device model
+ * store.  BLOK_ERR_INVALID_ARG: an unknown or destroyed model, scale_log2 > 8, a NULL output.  set_scale also empties the previous-frame
+ * table that the context keeps for blok_hip_draw_frame_rt_instanced_motion, as blok_hip_post_reset does: the next frame treats its
+ * instances as untracked, because the object-motion map is wrong across a change of scale.  Callers of the *_device motion entries
+ * (blok_hip_instance_motion_device, blok_hip_denoise_instanced*_device) hold both tables themselves and own that rule themselves.
+ * Volume entries that take a placement or a model id (blok_hip_volume_stamp_models, blok_hip_volume_sweep_models, the entries of
+ * blok_hip_volume_scatter_models) return BLOK_ERR_UNSUPPORTED for a live model whose scale is not 0; nothing is touched. */
+int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_log2);
+int blok_hip_model_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t* out_scale_log2);
 /* BLOK_OK if every instance of a host table passes the limits above, else BLOK_ERR_INVALID_ARG naming the first that does not. */
 int blok_hip_check_instances(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n_instances);
 

@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]] [--far K[,MIN]]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -16,6 +16,14 @@
 //          volume is released, and the coarse cells that hold at least MIN (default 1) filled voxels are installed as the world at voxel
 //          size 2^K (blok_hip_set_voxel_size + blok_hip_upload_dense), cell C covering world [C 2^K, (C + 1) 2^K): the frames show the far-field
 //          copy of the terrain from the unchanged camera.
+//   --far K[,MIN]: with --terrain: the fine box is traced as the world and the eight boxes around it in x and z (the same y range) appear
+//          as level-K copies (K in 1 .. 5) at their true size.  Before the terrain's own box is made, the resident volume is created at
+//          each neighbour's place in turn, the same terrain generated into it, reduced K times (BLOK_LOD_VOTE_EXPOSED), the cells with at
+//          least MIN (default 1) filled voxels taken as a model (blok_hip_volume_lod_model) and the model given the scale 2^K
+//          (blok_hip_model_set_scale).  The models become an instance table with identity orientation and offset = the level's first cell
+//          times 2^K, traced by blok_hip_trace_primary_instanced (--rt: by the instanced ray-tracing frame).  Prints per neighbour
+//          "far: box (x,y,z): N voxels at level K" (a neighbour without such a cell is left out, with 0) and, after the last frame, "far:
+//          instances won P of W pixels".  Not with --load-volume, --scroll, --lod, --populate or --obj.
 //   --stroke X,Y,Z:X,Y,Z:...,R[,OP]: with --terrain, --obj or --load-volume, before the rebuild: a brush of radius R dragged through the world
 //          points (voxels; multiples of one half: W.5 is the centre of voxel W), as one table of capsules in one pass
 //          (blok_hip_volume_apply_shapes); OP is add (the default, density 1), subtract (density 0), erase, set, keep or paint (the last
@@ -87,6 +95,7 @@ struct Options {
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
     bool scroll = false;                  // move the terrain's box by scroll_delta after the fill
     uint32_t lod = 0, lod_min = 1;        // > 0: render level `lod` of the terrain's pyramid, the cells with at least lod_min filled voxels
+    uint32_t far = 0, far_min = 1;        // > 0: the eight boxes around the terrain's as level-`far` copies, instances of scaled models
     std::vector<std::array<int32_t, 3>> stroke;      // the points of --stroke, half-voxel units
     uint32_t stroke_radius = 0, stroke_op = BLOK_SHAPE_ADD;
     int32_t scroll_delta[3] = {0, 0, 0};
@@ -110,9 +119,11 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
+                if (!m_opt.load_volume.empty() && m_opt.far) throw std::runtime_error("--far generates its terrain: leave --load-volume out");
                 if (!m_opt.load_volume.empty()) { initLoaded(); exportObj(); components(); settle(); saveVolume(); break; }
                 if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); saveVolume(); lod(); break; }
                 if (m_opt.lod) throw std::runtime_error("--lod needs a terrain: --terrain");
+                if (m_opt.far) throw std::runtime_error("--far needs a terrain: --terrain");
                 if (!m_opt.obj.empty()) { initObj(); exportObj(); components(); settle(); saveVolume(); break; }
                 if (!m_opt.export_obj.empty()) throw std::runtime_error("--export-obj needs a resident volume: --terrain or --obj");
                 if (m_opt.components) throw std::runtime_error("--components needs a resident volume: --terrain or --obj");
@@ -195,6 +206,7 @@ private:
         if (m_opt.devices.size() > 1) throw std::runtime_error("--terrain renders on one device");
         const uint32_t N = m_opt.terrain_size;
         const blok_terrain_params p = terrainParams(N);
+        farField(p);
         const int32_t origin[3] = {0, 0, 0};
         m_tracer->createVolume(origin, N, N, N);
         const uint64_t filled = m_tracer->generateTerrain(p);
@@ -242,6 +254,48 @@ private:
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
         terrainCamera(p, N, ground);
+    }
+    // The far field: each of the eight boxes around the terrain's in x and z, generated where it lies, reduced, and kept as a scaled model.
+    void farField(const blok_terrain_params& p) {
+        if (!m_opt.far) return;
+        if (m_opt.scroll || m_opt.lod || !m_opt.populate.empty() || !m_opt.obj.empty())
+            throw std::runtime_error("--far shows the terrain and its ring alone: leave --scroll, --lod, --populate, --obj and --load-volume out");
+        const uint32_t N = m_opt.terrain_size, K = m_opt.far;
+        for (int dz = -1; dz <= 1; ++dz)
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (!dx && !dz) continue;
+                const int32_t origin[3] = {dx * static_cast<int32_t>(N), 0, dz * static_cast<int32_t>(N)};
+                m_tracer->createVolume(origin, N, N, N);
+                m_tracer->generateTerrain(p);
+                const blok_lod_info info = m_tracer->reduceVolume(nullptr, nullptr, K, BLOK_LOD_VOTE_EXPOSED);
+                const blok_lod_level& L = info.level[K - 1];
+                uint32_t model = 0;
+                uint64_t voxels = 0;
+                const int rc = blok_hip_volume_lod_model(m_tracer->handle(), K, m_opt.far_min, &model, &voxels);
+                if (rc != BLOK_OK && rc != BLOK_ERR_UNSUPPORTED) throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_tracer->handle()));
+                if (rc == BLOK_ERR_UNSUPPORTED) voxels = 0;     // no cell holds that many voxels: the neighbour is left out
+                std::cout << "far: box (" << origin[0] << "," << origin[1] << "," << origin[2] << "): " << voxels << " voxels at level " << K << "\n";
+                if (!voxels) continue;
+                m_tracer->setModelScale(model, K);
+                blok_instance I{};
+                I.model = model;
+                for (int a = 0; a < 3; ++a) { I.offset[a] = L.clo[a] * (1 << K); I.axis[a] = static_cast<uint8_t>(a); }
+                m_instances.push_back(I);
+            }
+        if (blok_hip_check_instances(m_tracer->handle(), m_instances.data(), static_cast<uint32_t>(m_instances.size())) != BLOK_OK)
+            throw std::runtime_error(std::string("--far: ") + blok_hip_last_error(m_tracer->handle()));
+    }
+    // After the last frame: how many pixels of the first-hit frame the far field's instances win.
+    void farReport() {
+        if (!m_opt.far) return;
+        const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
+        std::vector<uint32_t> ids(static_cast<size_t>(m_opt.width) * m_opt.height);
+        if (blok_hip_trace_primary_instanced(m_tracer->handle(), &c, 0, 0, m_opt.width, m_opt.height, m_instances.data(), static_cast<uint32_t>(m_instances.size()),
+                                             nullptr, nullptr, ids.data()) != BLOK_OK)
+            throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_tracer->handle()));
+        size_t won = 0;
+        for (uint32_t id : ids) won += id != BLOK_INSTANCE_NONE;
+        std::cout << "far: instances won " << won << " of " << ids.size() << " pixels\n";
     }
     // A world read from a .bvol file in place of generating one: a volume of the stream's box, the stream decoded into it, rebuilt.
     void initLoaded() {
@@ -498,6 +552,7 @@ private:
             const auto t0 = clock::now();
             m_tracer->beginFrame();
             if (m_multi) m_multi->drawFrame(m_camera, m_multiFrame);
+            else if (m_opt.rt && m_opt.far) m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp);
             else if (m_opt.rt) m_tracer->drawFrameRT(m_camera, m_opt.spp);
             else if (!m_instances.empty()) m_tracer->drawFrameInstanced(m_camera, m_instances);
             else m_tracer->drawFrame(m_camera);
@@ -509,7 +564,8 @@ private:
                            << m_tracer->hits().size() * sizeof(blok_hit) / 1e6 << " MB)\n";
             if (f + 1 < m_opt.frames || !m_opt.rt) m_camera.processKeyboard('W', 0.016f);
         }
-        const auto& single = m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
+        const auto& single = m_opt.rt && m_opt.far ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
+                             : m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
         if (m_multi) {                                       // the partitioned frame must be the single-device frame
             m_multi->drawFrame(m_camera, m_multiFrame);
             size_t differ = 0;
@@ -517,6 +573,7 @@ private:
             std::cout << "multi-device frame vs single-device frame: " << differ << " pixels differ\n";
             if (differ) throw std::runtime_error("multi-device frame differs from the single-device frame");
         }
+        farReport();
         const auto& px = m_multi ? m_multiFrame : single;
         std::ofstream ppm(m_opt.out, std::ios::binary);
         ppm << "P6\n" << m_opt.width << " " << m_opt.height << "\n255\n";
@@ -534,7 +591,7 @@ private:
     std::unique_ptr<blok::HipTracer> m_tracer;
     std::unique_ptr<blok::HipMultiTracer> m_multi;
     std::vector<uint32_t> m_multiFrame;
-    std::vector<blok_instance> m_instances;        // --populate: the scattered table (empty once baked)
+    std::vector<blok_instance> m_instances;        // --populate: the scattered table (empty once baked); --far: the ring of coarse copies
     std::vector<blok_hit> m_populatedHits;
     std::vector<uint32_t> m_populatedFrame;
 };
@@ -612,6 +669,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--lod")) {
             const int got = std::sscanf(next(), "%u,%u", &opt.lod, &opt.lod_min);
             if (got < 1 || opt.lod < 1 || opt.lod > BLOK_LOD_MAX_LEVELS || opt.lod_min < 1 || opt.lod_min > (1u << (3u * opt.lod))) { std::fprintf(stderr, "--lod takes K[,MIN] with K in 1..5 and MIN in 1..8^K\n"); return 2; }
+        }
+        else if (!std::strcmp(argv[i], "--far")) {
+            const int got = std::sscanf(next(), "%u,%u", &opt.far, &opt.far_min);
+            if (got < 1 || opt.far < 1 || opt.far > BLOK_LOD_MAX_LEVELS || opt.far_min < 1 || opt.far_min > (1u << (3u * opt.far))) { std::fprintf(stderr, "--far takes K[,MIN] with K in 1..5 and MIN in 1..8^K\n"); return 2; }
         }
         else if (!std::strcmp(argv[i], "--scroll")) { opt.scroll = true; if (std::sscanf(next(), "%d,%d,%d", &opt.scroll_delta[0], &opt.scroll_delta[1], &opt.scroll_delta[2]) != 3) { std::fprintf(stderr, "--scroll takes DX,DY,DZ\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--stroke")) { if (!parseStroke(next(), opt)) { std::fprintf(stderr, "--stroke takes X,Y,Z:X,Y,Z:...,R[,add|subtract|erase|set|keep|paint], coordinates and R in multiples of one half\n"); return 2; } }
