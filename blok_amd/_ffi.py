@@ -107,6 +107,8 @@ LOD_LEVEL = np.dtype([("clo", "<i4", 3), ("cext", "<u4", 3), ("n_cells", "<u8"),
 LOD_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("levels", "<u4"), ("reserved", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("level", LOD_LEVEL, 5)])
 LOD_VOTE_EXPOSED = 1                              # = BLOK_LOD_VOTE_EXPOSED
 LOD_MAX_LEVELS = 5                                # = BLOK_LOD_MAX_LEVELS
+# = blok_affine (96 bytes): world -> model, m and t in units of 2^-16 model voxel (blok_amd.affine makes them)
+AFFINE = np.dtype([("model", "<u4"), ("anchor", "<i4", 3), ("m", "<i4", (3, 3)), ("reserved", "<u4", 5), ("t", "<i8", 3)])
 
 
 def flood_seed_face(f: int) -> int:
@@ -120,7 +122,7 @@ assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD
 assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_INFO.itemsize == 64
 assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
 assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200 and SHAPE.itemsize == 64
-assert LOD_LEVEL.itemsize == 64 and LOD_INFO.itemsize == 360
+assert LOD_LEVEL.itemsize == 64 and LOD_INFO.itemsize == 360 and AFFINE.itemsize == 96
 
 
 class GBuffer(C.Structure):
@@ -272,6 +274,10 @@ HOST_SYMBOLS = {
     "blok_shapes_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_lod_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blok_affine_from_instance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "blok_affine_from_matrix": (C.c_int, [C.POINTER(C.c_double), C.c_void_p]),
+    "blok_affine_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_scene_generate_dense": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_scene_materials": (C.c_int, [C.c_uint32, C.c_void_p]),
@@ -406,6 +412,8 @@ HIP_SYMBOLS = {
                                                 C.POINTER(C.c_uint64)]),
     "blok_hip_volume_quads_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_stamp_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_stamp_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float,
+                                               C.POINTER(C.c_uint64)]),
     "blok_hip_volume_capture_model": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint32),
                                                 C.POINTER(C.c_uint64)]),
     "blok_hip_volume_label_components": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint64),

@@ -2,6 +2,7 @@
 #include "api_internal.h"
 #include "../common/terrain_core.h"
 #include "../common/stamp_core.h"
+#include "../common/affine_core.h"
 #include "../common/sweep_core.h"
 #include "../common/bricks_core.h"
 #include "../common/distance_core.h"
@@ -286,6 +287,39 @@ int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placeme
     std::string why;
     // (edits are enqueued on the null stream, and so is this: placement after placement, in stream order)
     return volume_status(ctx, blok::gpu_volume_stamp(&ctx->volume, models.data(), placements_host, n_placements, mode, density, out_n_voxels, &why), why);
+}
+
+int blok_hip_volume_stamp_affine(blok_hip_ctx* ctx, const blok_affine* table_host, uint32_t n, const int32_t region_lo[3],
+                                 const int32_t region_hi[3], int mode, float density, uint64_t* out_n_voxels) {
+    if (out_n_voxels) *out_n_voxels = 0;
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (n && !table_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: null table with a non-zero count");
+    const blok::GpuVolume& v = ctx->volume;
+    const uint32_t dims[3] = {v.nx, v.ny, v.nz};
+    // the one volume entry that takes a model of any scale exponent: the exponent is not looked at, the box is the model's own
+    std::vector<blok::StampModel> models(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t model = table_host[i].model;
+        if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: record " + std::to_string(i) + ": unknown model " + std::to_string(model));
+        if (const int rule = blok::affine::well_formed(table_host[i], v.origin, dims))
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: record " + std::to_string(i) + ": " + blok::affine::rule_text(rule));
+        const blok::ModelDesc& d = ctx->models.desc[model];
+        const auto& own = ctx->models.own[model];
+        blok::StampModel& m = models[i];
+        m.nodes = d.nodes; m.materials = d.materials; m.levels = d.levels;
+        for (int a = 0; a < 3; ++a) { m.origin[a] = d.origin[a]; m.lo[a] = own.box_lo[a]; m.hi[a] = own.box_hi[a]; }
+    }
+    if (!blok::stamp::mode_known(mode)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: unknown mode");
+    if (mode != BLOK_STAMP_ERASE && (!std::isfinite(density) || !(density > 0.0f)))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: density must be finite and > 0");
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "stamp_affine", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    // (edits are enqueued on the null stream, and so is this: record after record, in stream order)
+    return volume_status(ctx, blok::gpu_volume_stamp_affine(&ctx->volume, models.data(), table_host, n, lo, hi, mode, density, out_n_voxels, &why), why);
 }
 
 int blok_hip_volume_apply_shapes(blok_hip_ctx* ctx, const blok_shape* shapes_host, uint32_t n_shapes, uint64_t* out_n_written) {

@@ -156,6 +156,12 @@ inline void placed_brick_range(const StampModel& M, const int64_t clo[3], const 
 }
 GpuBuildStatus gpu_volume_stamp(GpuVolume* v, const StampModel* models, const blok_instance* placements, uint32_t n_placements, int mode,
                                 float density, uint64_t* out_n_voxels, std::string* why);
+// = blok_hip_volume_stamp_affine (include/blok_hip.h; affine_kernels.hip) over the box-local region [lo, hi).  The records have passed
+// affine::well_formed against the volume's box; models[i] is the model of records[i], lo / hi the box of its voxels in its OWN voxels
+// whatever its scale exponent.  Per record the host culls the region's coarse tiles by the exact interval of the map, then one launch over
+// the surviving box and one gpu_volume_commit over it, in table order on the null stream; the only wait is the one for the count at the end.
+GpuBuildStatus gpu_volume_stamp_affine(GpuVolume* v, const StampModel* models, const blok_affine* records, uint32_t n_records, const uint32_t lo[3],
+                                       const uint32_t hi[3], int mode, float density, uint64_t* out_n_voxels, std::string* why);
 // = blok_hip_volume_capture_model (include/blok_hip.h) over the box-local region [lo, hi): the tree of the region's filled voxels in the
 // lattice whose voxel (0, 0, 0) is the region's corner, built on the device.  On Ok with *out_n_voxels > 0, out->d_nodes /
 // d_materials are new device arrays, the caller's to free, and box_lo / box_hi the tight box of the voxels (half open, model

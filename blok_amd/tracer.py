@@ -171,6 +171,17 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_stamp_models(self._ctx, _ffi.ptr(inst) if len(inst) else None, len(inst), int(mode), float(density), C.byref(n)))
         return int(n.value)
 
+    def volume_stamp_affine(self, records, lo=None, hi=None, mode: int = _ffi.STAMP_SET, density: float = 1.0) -> int:
+        """Resamples models into the resident volume through affine maps (blok_hip.h: blok_hip_volume_stamp_affine): records are _ffi.AFFINE
+        records (blok_amd.affine: from_instance, from_matrix, rotation), applied in table order to the region (world voxels, half open;
+        both None = the whole box); mode _ffi.STAMP_SET / STAMP_KEEP / STAMP_ERASE.  A model of any scale exponent is taken: the record
+        carries all scale.  Returns the cells written.  The next volume_rebuild installs the world."""
+        table = np.ascontiguousarray(records, dtype=_ffi.AFFINE).reshape(-1)
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_volume_stamp_affine(self._ctx, _ffi.ptr(table) if len(table) else None, len(table), _vec3(lo), _vec3(hi), int(mode),
+                                                           float(density), C.byref(n)))
+        return int(n.value)
+
     def volume_apply_shapes(self, shapes) -> int:
         """Applies a table of shapes to the resident volume in one pass (blok_hip.h: blok_hip_volume_apply_shapes): shapes are _ffi.SHAPE
         records (blok_amd.shapes: box, sphere, ellipsoid, capsule, cylinder, stroke), each with its own operation; the result is the table

@@ -264,6 +264,16 @@ public:
         check(blok_hip_volume_stamp_models(m_ctx, placements.data(), static_cast<uint32_t>(placements.size()), mode, density, &n));
         return n;
     }
+    // Models resampled into the resident volume through affine maps, in table order (blok_hip_volume_stamp_affine; records from
+    // blok_affine_from_instance / blok_affine_from_matrix, blok_world.h): any rotation, scale, mirror or shear, a model of any scale
+    // exponent; the region in world voxels, half-open (both null = the whole box).  Returns the cells written.  A later rebuildVolume
+    // installs the world.
+    uint64_t stampAffine(const std::vector<blok_affine>& records, const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr,
+                         int mode = BLOK_STAMP_SET, float density = 1.0f) {
+        uint64_t n = 0;
+        check(blok_hip_volume_stamp_affine(m_ctx, records.data(), static_cast<uint32_t>(records.size()), regionLo, regionHi, mode, density, &n));
+        return n;
+    }
     // A table of shapes applied to the resident volume in one pass, in table order (blok_hip_volume_apply_shapes; coordinates in
     // half-voxel units, the centre of world voxel w at 2 w + 1): returns the number of writes.  A later rebuildVolume installs the world.
     uint64_t applyShapes(const std::vector<blok_shape>& shapes) {

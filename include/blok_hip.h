@@ -583,7 +583,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.15: a table of integer shapes (box, ellipsoid, capsule, cylinder; set, keep, erase, paint, replace, add, subtract) applied to the
  *       resident volume in one pass.
  * 1.16: the resident volume reduced to a pyramid of coarser levels (counts and a voted material id per cell); a level as a model.
- * 1.17: a power-of-two scale on instanced models (blok_hip_model_set_scale): a coarse level traced at its true size beside the world. */
+ * 1.17: a power-of-two scale on instanced models (blok_hip_model_set_scale): a coarse level traced at its true size beside the world.
+ * 1.18: models resampled into the resident volume through an affine map (blok_hip_volume_stamp_affine): any rotation, scale, mirror, shear. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -618,7 +619,8 @@ uint32_t blok_hip_abi_version(void);
  *   - Limit: vm <= 256, checked where a table is checked (host tables: BLOK_ERR_INVALID_ARG naming the instance; device tables: skipped).
  *   - Composition, the tie rule, the any-hit shadow rule and the BVH's ordering rule are unchanged, and so is the object-motion map
  *     (it does not contain the scale).
- *   Not built: negative exponents; baking a scaled model into the resident volume (the volume entries refuse one, below).
+ *   Not built: negative exponents.  (A scaled model is baked into the resident volume by blok_hip_volume_stamp_affine, since ABI 1.18:
+ *   blok_affine_from_instance, blok_world.h, folds a placement and the exponent into its record; the other volume entries refuse one, below.)
  * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
  * Scope.  The primary frame, explicit rays and the path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced
  *   below); the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay world-only (they never receive an
@@ -643,7 +645,8 @@ int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model);
  * instances as untracked, because the object-motion map is wrong across a change of scale.  Callers of the *_device motion entries
  * (blok_hip_instance_motion_device, blok_hip_denoise_instanced*_device) hold both tables themselves and own that rule themselves.
  * Volume entries that take a placement or a model id (blok_hip_volume_stamp_models, blok_hip_volume_sweep_models, the entries of
- * blok_hip_volume_scatter_models) return BLOK_ERR_UNSUPPORTED for a live model whose scale is not 0; nothing is touched. */
+ * blok_hip_volume_scatter_models) return BLOK_ERR_UNSUPPORTED for a live model whose scale is not 0; nothing is touched.  The one volume
+ * entry that takes a model of any exponent is blok_hip_volume_stamp_affine: it ignores the exponent, its matrix carries all scale. */
 int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_log2);
 int blok_hip_model_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t* out_scale_log2);
 /* BLOK_OK if every instance of a host table passes the limits above, else BLOK_ERR_INVALID_ARG naming the first that does not. */
@@ -771,6 +774,40 @@ int blok_hip_volume_stamp_models(blok_hip_ctx* ctx, const blok_instance* placeme
 #define BLOK_CAPTURE_CUT 1u   /* afterwards clear the captured voxels in the volume (density 0, id 0) */
 int blok_hip_volume_capture_model(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t flags,
                                   uint32_t* out_model, uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- models resampled into the resident volume through an affine map (ABI 1.18)
+ * What blok_hip_volume_stamp_models cannot do — a rotation by any angle, an enlargement or reduction by any factor, a mirror, a shear —
+ * is one operation: every cell of the volume asks the model which voxel lies under its centre.  Integer arithmetic only: one right answer,
+ * bit-identical on the host (blok_affine_stamp_voxels, blok_world.h) and on the device.  The call blocks.
+ *  - Record: blok_affine below, the map from the WORLD to the MODEL.  m in units of 2^-16 model voxel per world voxel; t the model-space
+ *    position of the CENTRE of world voxel `anchor`, in units of 2^-16 model voxel.  blok_affine_from_instance and blok_affine_from_matrix
+ *    (blok_world.h) make records from a placement or from a forward matrix.
+ *  - Sampling.  For a world voxel w, every product and sum in 64 bits:  P_k(w) = t_k + sum_j m[k][j] * (w_j - anchor_j),  v_k = P_k >> 16
+ *    (an arithmetic shift: a floor).
+ *  - Written set.  The cell w is touched iff w lies in the region cut with the volume's box (region: world voxels, half open, both pointers
+ *    NULL = the whole box) and the model has a voxel at v in its local lattice (the coordinates given to blok_hip_model_create).  Such a
+ *    cell gets what blok_hip_volume_stamp_models writes for that model voxel in the same mode (BLOK_STAMP_SET / KEEP / ERASE, `density`);
+ *    nothing else changes.  A point sample per cell: no holes, no cell written twice.  A singular m is legal: rank 2 extrudes, m = 0 fills
+ *    the region with one voxel's material if t lands on a filled voxel and writes nothing otherwise.
+ *  - Scale exponents.  The model's exponent (blok_hip_model_set_scale) is ignored, models of any exponent are taken: the matrix carries all
+ *    scale.
+ *  - Order: the result equals n successive calls in table order.  out_n_voxels (may be NULL): cells written, summed over the records; for
+ *    KEEP the cells that were empty and got filled.
+ *  - Afterwards masks, occupancy words and dirty flags are those blok_hip_volume_set_voxels leaves for the same writes, refreshed over each
+ *    record's own clipped box (never over their union); the next blok_hip_volume_rebuild installs the world.
+ *  - Errors, nothing written.  BLOK_ERR_INVALID_ARG: an unknown or destroyed model, a non-zero reserved word, |m[k][j]| > 2^22,
+ *    |t_k| > 2^40, an anchor from which some cell of the volume's box lies 2^20 or more away on an axis, an unknown mode, for SET and KEEP a
+ *    density that is not finite or <= 0, a null table with n > 0, exactly one region pointer NULL, lo > hi on an axis.
+ *    BLOK_ERR_UNSUPPORTED: a region that leaves the box, a volume above 2^32 cells.  BLOK_ERR_NO_WORLD: no volume.  n == 0 is BLOK_OK. */
+typedef struct blok_affine {
+    uint32_t model;
+    int32_t  anchor[3];   /* a world voxel */
+    int32_t  m[3][3];     /* world -> model, 2^-16 model voxel per world voxel */
+    uint32_t reserved[5]; /* zero */
+    int64_t  t[3];        /* model-space position of the centre of world voxel `anchor`, 2^-16 model voxel */
+} blok_affine;            /* 96 bytes */
+int blok_hip_volume_stamp_affine(blok_hip_ctx* ctx, const blok_affine* table_host, uint32_t n, const int32_t region_lo[3],
+                                 const int32_t region_hi[3], int mode, float density, uint64_t* out_n_voxels);
 
 /* ------------------------------------------------------------- connected components of the resident volume (ABI 1.8)
  * Which voxels hang together, answered on the device, and one such piece lifted out as a model.  Integer arithmetic only: one right

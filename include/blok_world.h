@@ -194,6 +194,28 @@ int blok_capture_voxels(const float* density, const uint32_t* material_ids, cons
                         const int32_t region_lo[3], const int32_t region_hi[3], int32_t* xyz_out, uint32_t* materials_out,
                         uint64_t capacity, uint64_t* out_n);
 
+/* -------------------------------------------------------------- a model resampled into a volume through an affine map, on the host (affine.cpp)
+ * blok_affine (blok_hip.h, blok_hip_volume_stamp_affine) maps the WORLD to the MODEL; these make one, and apply one to host arrays.
+ * from_instance: the placement and a scale exponent e <= 8 folded into *out exactly: anchor = offset and, for local axis k along world axis
+ *   a = axis[k], m[k][a] = +-2^(16 - e), t_k = +-2^(15 - e) (minus under flip bit k), all else zero, `model` the placement's.  With e = 0 the
+ *   record writes what blok_hip_volume_stamp_models writes for the placement; with e > 0 the cells the tracer shows for a model of that
+ *   exponent ("Scaled models", blok_hip.h).  BLOK_ERR_INVALID_ARG: a NULL pointer, a malformed placement, e > 8.
+ * from_matrix: a convenience for a forward map, model -> world, 3 x 4 row major (world = F * model + T, both in voxels, a voxel v being the
+ *   cube [v, v + 1)).  The map is inverted in double precision; anchor = floor(T), the cell that holds the image of the model-space origin;
+ *   m = rint(F^-1 * 2^16), t = rint(F^-1 * (anchor + 1/2 - T) * 2^16); model = 0.  The signed permutations and the power-of-two scales
+ *   with an integer T give from_instance's records exactly.  BLOK_ERR_INVALID_ARG: a NULL pointer, a value that is not finite, a singular
+ *   matrix, |m| > 2^22, |t| > 2^40 or an anchor outside int32.
+ * stamp_voxels: the contract of blok_hip_volume_stamp_affine for one record over host arrays density[x + y*nx + z*nx*ny] / material_ids of
+ *   a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the arithmetic the kernel uses.  The model is the list of n
+ *   voxels model_xyz[3*i..] (local lattice) with model_materials[i]; the last duplicate wins.  The record's `model` field is not looked
+ *   at.  The list is looked up through a dense array of its box, or a hash when the box is large: never a tree.  Errors as the device entry
+ *   (a NULL record or a NULL array the call would use is BLOK_ERR_INVALID_ARG); nothing is written then. */
+int blok_affine_from_instance(const blok_instance* placement, uint32_t scale_log2, blok_affine* out);
+int blok_affine_from_matrix(const double forward[12], blok_affine* out);
+int blok_affine_stamp_voxels(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                             const int32_t* model_xyz, const uint32_t* model_materials, size_t n, const blok_affine* record,
+                             const int32_t region_lo[3], const int32_t region_hi[3], int mode, float value, uint64_t* out_n_voxels);
+
 /* -------------------------------------------------------------- a volume's connected components on the host (components.cpp)
  * label: the contract of blok_hip_volume_label_components (blok_hip.h; blok_component is declared there) over the host array
  * density[x + y*nx + z*nx*ny] of a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the union-find the kernels

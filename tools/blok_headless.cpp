@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]] [--far K[,MIN]]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]] [--far K[,MIN]] [--paste FILE.vox@X,Y,Z,YAW_DEG,SCALE]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -55,6 +55,10 @@
 //          columns, probability 40000 / 65536, ROTATE | MIRROR, footprint radius 1 with rise and drop of at most 1, each model anchored at
 //          the centre of its base).  The first-hit frames are traced with the table as instances (--rt frames show the world alone); with
 //          --bake the table is stamped into the volume instead (BLOK_STAMP_SET) and the frames show the rebuilt world
+//   --paste FILE.vox@X,Y,Z,YAW_DEG,SCALE: with --terrain, once the volume is filled and before it is rebuilt: the first model of the .vox file
+//          (VOX z is up) is turned by YAW_DEG about +y around the centre of its voxels' box, scaled by SCALE, and resampled into the volume
+//          with that centre at the world point X,Y,Z (blok_affine_from_matrix, blok_hip_volume_stamp_affine, BLOK_STAMP_SET); the number of
+//          voxels written is printed.  May be given more than once: pasted in order
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -101,6 +105,8 @@ struct Options {
     int32_t scroll_delta[3] = {0, 0, 0};
     std::vector<std::string> populate;    // .vox files whose first models are scattered over the terrain
     bool bake = false;                    // ... and stamped into the volume instead of traced as instances
+    struct Paste { std::string path; double position[3], yaw_deg, scale; };
+    std::vector<Paste> paste;             // .vox models resampled into the terrain, turned and scaled
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
@@ -120,6 +126,7 @@ private:
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
                 if (!m_opt.load_volume.empty() && m_opt.far) throw std::runtime_error("--far generates its terrain: leave --load-volume out");
+                if (!m_opt.load_volume.empty() && !m_opt.paste.empty()) throw std::runtime_error("--paste needs a terrain: leave --load-volume out");
                 if (!m_opt.load_volume.empty()) { initLoaded(); exportObj(); components(); settle(); saveVolume(); break; }
                 if (m_opt.terrain) { initTerrain(); exportObj(); components(); settle(); saveVolume(); lod(); break; }
                 if (m_opt.lod) throw std::runtime_error("--lod needs a terrain: --terrain");
@@ -132,6 +139,7 @@ private:
                 if (m_opt.hollow >= 0) throw std::runtime_error("--hollow needs a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.seal) throw std::runtime_error("--seal needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.populate.empty()) throw std::runtime_error("--populate needs a terrain: --terrain");
+                if (!m_opt.paste.empty()) throw std::runtime_error("--paste needs a terrain: --terrain");
                 if (m_opt.scroll) throw std::runtime_error("--scroll needs a terrain: --terrain");
                 if (!m_opt.stroke.empty()) throw std::runtime_error("--stroke needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.vox.empty()) {
@@ -250,6 +258,7 @@ private:
         hollow();
         stroke();
         populate(p);
+        paste();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
@@ -260,6 +269,7 @@ private:
         if (!m_opt.far) return;
         if (m_opt.scroll || m_opt.lod || !m_opt.populate.empty() || !m_opt.obj.empty())
             throw std::runtime_error("--far shows the terrain and its ring alone: leave --scroll, --lod, --populate, --obj and --load-volume out");
+        if (!m_opt.paste.empty()) throw std::runtime_error("--far shows the terrain and its ring alone: leave --paste out");
         const uint32_t N = m_opt.terrain_size, K = m_opt.far;
         for (int dz = -1; dz <= 1; ++dz)
             for (int dx = -1; dx <= 1; ++dx) {
@@ -344,26 +354,60 @@ private:
         const uint64_t filled = m_tracer->editByFlood(BLOK_FLOOD_FILL_UNREACHED, 0, 1.0f, m_opt.seal_material);
         std::cout << "seal: " << filled << " voxels filled, farthest " << info.farthest << "\n";
     }
+    // The first model of a .vox file in the local lattice of the models here (VOX z is up -> local y), its palette imported as materials.
+    void loadVoxModel(const std::string& path, std::vector<int32_t>& xyz, std::vector<uint32_t>& ids, uint32_t size[3]) {
+        char err[512] = {0};
+        blok_vox* vox = nullptr;
+        if (blok_vox_load_file(path.c_str(), &vox, err, sizeof(err)) != BLOK_OK) throw std::runtime_error("Failed to load VOX: " + std::string(err));
+        uint32_t n = 0, palette[256];
+        if (blok_vox_model_count(vox) == 0 || blok_vox_model_info(vox, 0, size, &n) != BLOK_OK || n == 0) { blok_vox_free(vox); throw std::runtime_error("the VOX holds no voxels: " + path); }
+        blok_vox_import_materials(vox, m_materials.handle(), palette);
+        const uint8_t* v = blok_vox_model_voxels(vox, 0);
+        xyz.resize(3u * n);
+        ids.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            xyz[3 * i] = v[4 * i]; xyz[3 * i + 1] = v[4 * i + 2]; xyz[3 * i + 2] = v[4 * i + 1];
+            ids[i] = palette[v[4 * i + 3]];
+        }
+        blok_vox_free(vox);
+    }
+    // Each --paste model turned about +y around the centre of its voxels' box, scaled, and resampled into the volume with that centre at the
+    // given world point: forward = T(position) Ry(yaw) S(scale) T(-centre), inverted and rounded by blok_affine_from_matrix.
+    void paste() {
+        for (const Options::Paste& P : m_opt.paste) {
+            std::vector<int32_t> xyz;
+            std::vector<uint32_t> ids;
+            uint32_t size[3] = {0, 0, 0};
+            loadVoxModel(P.path, xyz, ids, size);
+            int32_t lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+            for (size_t i = 0; i < ids.size(); ++i)
+                for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], xyz[3 * i + a]); hi[a] = std::max(hi[a], xyz[3 * i + a] + 1); }
+            const double pivot[3] = {(lo[0] + hi[0]) / 2.0, (lo[1] + hi[1]) / 2.0, (lo[2] + hi[2]) / 2.0};
+            const double yaw = P.yaw_deg * (3.14159265358979323846 / 180.0), cy = std::cos(yaw), sy = std::sin(yaw), s = P.scale;
+            const double r[3][3] = {{cy, 0.0, sy}, {0.0, 1.0, 0.0}, {-sy, 0.0, cy}};
+            double forward[12];
+            for (int i = 0; i < 3; ++i) {
+                const double row[3] = {s * r[i][0], s * r[i][1], s * r[i][2]};
+                for (int j = 0; j < 3; ++j) forward[4 * i + j] = row[j];
+                forward[4 * i + 3] = P.position[i] - (row[0] * pivot[0] + row[1] * pivot[1] + row[2] * pivot[2]);
+            }
+            blok_affine record;
+            if (blok_affine_from_matrix(forward, &record) != BLOK_OK) throw std::runtime_error("--paste: the map has no record (blok_affine_from_matrix): SCALE must be at least 1/64");
+            record.model = m_tracer->createModel(xyz, ids);
+            const uint64_t written = m_tracer->stampAffine({record}, nullptr, nullptr, BLOK_STAMP_SET, 1.0f);
+            std::cout << "paste: " << P.path << ": " << ids.size() << " voxels turned " << P.yaw_deg << " degrees, scaled " << P.scale << " -> " << written << " voxels written\n";
+        }
+    }
     // The listed .vox models scattered over the terrain's grass: the column field of the whole box, then the table — kept for the frames, or baked.
     void populate(const blok_terrain_params& terrain) {
         if (m_opt.populate.empty()) return;
         if (m_opt.populate.size() > BLOK_SCATTER_MAX_ENTRIES) throw std::runtime_error("--populate takes at most 16 models");
         std::vector<blok_scatter_entry> entries;
         for (const std::string& path : m_opt.populate) {
-            char err[512] = {0};
-            blok_vox* vox = nullptr;
-            if (blok_vox_load_file(path.c_str(), &vox, err, sizeof(err)) != BLOK_OK) throw std::runtime_error("Failed to load VOX: " + std::string(err));
-            uint32_t size[3] = {0, 0, 0}, n = 0, palette[256];
-            if (blok_vox_model_count(vox) == 0 || blok_vox_model_info(vox, 0, size, &n) != BLOK_OK || n == 0) { blok_vox_free(vox); throw std::runtime_error("the VOX holds no voxels: " + path); }
-            blok_vox_import_materials(vox, m_materials.handle(), palette);
-            const uint8_t* v = blok_vox_model_voxels(vox, 0);
-            std::vector<int32_t> xyz(3u * n);
-            std::vector<uint32_t> ids(n);
-            for (uint32_t i = 0; i < n; ++i) {                    // VOX z is up -> local y
-                xyz[3 * i] = v[4 * i]; xyz[3 * i + 1] = v[4 * i + 2]; xyz[3 * i + 2] = v[4 * i + 1];
-                ids[i] = palette[v[4 * i + 3]];
-            }
-            blok_vox_free(vox);
+            std::vector<int32_t> xyz;
+            std::vector<uint32_t> ids;
+            uint32_t size[3] = {0, 0, 0};
+            loadVoxModel(path, xyz, ids, size);
             blok_scatter_entry e{};
             e.model = m_tracer->createModel(xyz, ids);
             e.weight = 1u;
@@ -666,6 +710,20 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--hollow")) { opt.hollow = std::atoll(next()); if (opt.hollow < 0 || opt.hollow > 65025) { std::fprintf(stderr, "--hollow takes a squared distance in 0..65025\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--populate")) { for (std::string list = next(); !list.empty();) { const size_t c = list.find(','); opt.populate.push_back(list.substr(0, c)); list = c == std::string::npos ? "" : list.substr(c + 1); } }
         else if (!std::strcmp(argv[i], "--bake")) opt.bake = true;
+        else if (!std::strcmp(argv[i], "--paste")) {
+            const std::string arg = next();
+            const size_t at = arg.rfind('@');
+            Options::Paste P{};
+            char tail = 0;
+            if (at == std::string::npos || at == 0 ||
+                std::sscanf(arg.c_str() + at + 1, "%lf,%lf,%lf,%lf,%lf%c", &P.position[0], &P.position[1], &P.position[2], &P.yaw_deg, &P.scale, &tail) != 5 ||
+                !std::isfinite(P.position[0]) || !std::isfinite(P.position[1]) || !std::isfinite(P.position[2]) || !std::isfinite(P.yaw_deg) || !std::isfinite(P.scale) || !(P.scale > 0.0)) {
+                std::fprintf(stderr, "--paste takes FILE.vox@X,Y,Z,YAW_DEG,SCALE with SCALE > 0\n");
+                return 2;
+            }
+            P.path = arg.substr(0, at);
+            opt.paste.push_back(P);
+        }
         else if (!std::strcmp(argv[i], "--lod")) {
             const int got = std::sscanf(next(), "%u,%u", &opt.lod, &opt.lod_min);
             if (got < 1 || opt.lod < 1 || opt.lod > BLOK_LOD_MAX_LEVELS || opt.lod_min < 1 || opt.lod_min > (1u << (3u * opt.lod))) { std::fprintf(stderr, "--lod takes K[,MIN] with K in 1..5 and MIN in 1..8^K\n"); return 2; }
