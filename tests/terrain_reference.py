@@ -99,10 +99,9 @@ def solid_box(p, lo, hi):
     return solid(p, X, Y, Z, H), H
 
 
-def eval_box(p, lo, hi, density=None, ids=None):
-    """What the entry writes into [lo, hi): (density, ids) as [z][y][x] arrays (prior content given for ADD)."""
+def fill_box(p, lo, hi):
+    """The cells of [lo, hi) the entry fills, [z][y][x]: the solid ones, with SHELL those of them with an empty neighbour."""
     lo, hi = [int(v) for v in lo], [int(v) for v in hi]
-    shape = (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0])
     flags = p["flags"]
     if flags & SHELL:
         S, _ = solid_box(p, [v - 1 for v in lo], [v + 1 for v in hi])
@@ -111,9 +110,21 @@ def eval_box(p, lo, hi, density=None, ids=None):
             S[:, :, 0] = S[:, :, -1] = False
         c = S[1:-1, 1:-1, 1:-1]
         inner = S[1:-1, 1:-1, :-2] & S[1:-1, 1:-1, 2:] & S[1:-1, :-2, 1:-1] & S[1:-1, 2:, 1:-1] & S[:-2, 1:-1, 1:-1] & S[2:, 1:-1, 1:-1]
-        fill = c & ~inner
-    else:
-        fill, _ = solid_box(p, lo, hi)
+        return c & ~inner
+    return solid_box(p, lo, hi)[0]
+
+
+def written(p, lo, hi):
+    """The count the entry returns: the filled voxels it writes."""
+    return int(fill_box(p, lo, hi).sum())
+
+
+def eval_box(p, lo, hi, density=None, ids=None):
+    """What the entry writes into [lo, hi): (density, ids) as [z][y][x] arrays (prior content given for ADD)."""
+    lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+    shape = (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0])
+    flags = p["flags"]
+    fill = fill_box(p, lo, hi)
     X, Y, Z = _grid(lo, hi)
     H = height(p, X[:, :1, :], Z[:, :1, :])
     mat = material(p, X, Y, Z, H)
