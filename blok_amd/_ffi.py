@@ -109,6 +109,12 @@ LOD_VOTE_EXPOSED = 1                              # = BLOK_LOD_VOTE_EXPOSED
 LOD_MAX_LEVELS = 5                                # = BLOK_LOD_MAX_LEVELS
 # = blok_affine (96 bytes): world -> model, m and t in units of 2^-16 model voxel (blok_amd.affine makes them)
 AFFINE = np.dtype([("model", "<u4"), ("anchor", "<i4", 3), ("m", "<i4", (3, 3)), ("reserved", "<u4", 5), ("t", "<i8", 3)])
+# = blok_automaton_rule (32 bytes) and blok_automaton_info (64 bytes): a neighbour-count rule and what a call of it did (blok_amd.automaton makes rules)
+AUTOMATON_RULE = np.dtype([("neighbourhood", "<u4"), ("survive", "<u4"), ("birth", "<u4"), ("flags", "<u4"), ("density", "<f4"), ("material", "<u4"), ("steps", "<u4"),
+                           ("reserved", "<u4")])
+AUTOMATON_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("steps_run", "<u4"), ("reserved", "<u4"), ("n_born", "<u8"),
+                           ("n_died", "<u8"), ("n_filled", "<u8")])
+AUTOMATON_BOX_IS_SOLID, AUTOMATON_FIXED_MATERIAL = 1, 2      # = BLOK_AUTOMATON_BOX_IS_SOLID, _FIXED_MATERIAL
 
 
 def flood_seed_face(f: int) -> int:
@@ -123,6 +129,7 @@ assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_IN
 assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
 assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200 and SHAPE.itemsize == 64
 assert LOD_LEVEL.itemsize == 64 and LOD_INFO.itemsize == 360 and AFFINE.itemsize == 96
+assert AUTOMATON_RULE.itemsize == 32 and AUTOMATON_INFO.itemsize == 64
 
 
 class GBuffer(C.Structure):
@@ -274,6 +281,9 @@ HOST_SYMBOLS = {
     "blok_shapes_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_lod_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blok_automaton_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_automaton_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_affine_from_instance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_affine_from_matrix": (C.c_int, [C.POINTER(C.c_double), C.c_void_p]),
     "blok_affine_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -451,6 +461,7 @@ HIP_SYMBOLS = {
     "blok_hip_volume_lod_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_volume_lod_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_lod_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "blok_hip_volume_automaton": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "blok_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -12,6 +12,7 @@
 #include "../common/scroll_core.h"
 #include "../common/shapes_core.h"
 #include "../common/lod_core.h"
+#include "../common/automaton_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -828,6 +829,23 @@ int blok_hip_volume_lod_model(blok_hip_ctx* ctx, uint32_t level, uint32_t min_co
     const int rc = add_captured_model(ctx, tree, box_lo, box_hi, out_model);
     if (rc != BLOK_OK) return rc;
     if (out_n_voxels) *out_n_voxels = n_voxels;
+    return BLOK_OK;
+}
+
+int blok_hip_volume_automaton(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], const blok_automaton_rule* rule,
+                              uint64_t* out_step_counts, blok_automaton_info* out_info) {
+    int rc = need_volume(ctx);
+    if (rc != BLOK_OK) return rc;
+    if (const int failed = blok::automaton::check(rule)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("volume_automaton: ") + blok::automaton::rule_text(failed));
+    uint32_t lo[3], hi[3];
+    rc = volume_region(ctx, "volume_automaton", region_lo, region_hi, lo, hi);
+    if (rc != BLOK_OK) return rc;
+    std::string why;
+    blok_automaton_info info;
+    // (edits are enqueued on the null stream, and so is this: it steps what they leave)
+    const blok::GpuBuildStatus st = blok::gpu_volume_automaton(&ctx->volume, lo, hi, *rule, out_step_counts, &info, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    if (out_info) *out_info = info;
     return BLOK_OK;
 }
 

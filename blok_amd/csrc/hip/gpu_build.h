@@ -305,6 +305,13 @@ GpuBuildStatus gpu_volume_reduce(const GpuVolume* v, const uint32_t lo[3], const
 // model coordinates are relative to the level's grid corner.
 GpuBuildStatus gpu_lod_capture(const GpuLod* l, uint32_t level, uint32_t min_count, GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],
                                uint64_t* out_n_voxels, std::string* why);
+// ---- neighbour-count rules (include/blok_hip.h: blok_hip_volume_automaton; automaton_kernels.hip) ----
+// Steps a rule that has passed automaton::check over the box-local region [lo, hi).  Per step: the decision of every region brick from the
+// brick masks (which every edit leaves equal to density > 0) into scratch owned by the call, the births, the deaths, then gpu_volume_commit
+// over the region; the host reads the step's counts behind the decision and stops at a step that changes nothing.  out_step_counts: null,
+// or 2 * rule.steps host values.  Blocking.  A failure before the first write leaves the volume as it was.
+GpuBuildStatus gpu_volume_automaton(GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], const blok_automaton_rule& rule, uint64_t* out_step_counts,
+                                    blok_automaton_info* out_info, std::string* why);
 // = applyBrush (brush.cpp:13-63): mode 0 ADD (max), 1 SUBTRACT (min); the brush's bounding box must lie in the box.
 GpuBuildStatus gpu_volume_brush(GpuVolume* v, const float center[3], float radius, float value, int mode, std::string* why);
 // 64-tree of the current contents (UseHostBuilder = the volume is empty).  keyed volumes: out->d_nodes / d_materials stay OWNED BY THE

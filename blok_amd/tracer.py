@@ -426,6 +426,17 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_reduce(self._ctx, _vec3(lo), _vec3(hi), int(levels), int(flags), _ffi.ptr(info)))
         return info
 
+    def volume_automaton(self, rule, lo=None, hi=None):
+        """Steps a neighbour-count rule (one _ffi.AUTOMATON_RULE record; blok_amd.automaton makes them) over a region of the resident
+        volume (world voxels, half open; both None = the whole box), in place (blok_hip.h: blok_hip_volume_automaton).  Returns (info,
+        step_counts): one _ffi.AUTOMATON_INFO record, and a [steps][2] uint64 array of the cells born and died per step, zero past
+        info["steps_run"]; the next volume_rebuild installs the world."""
+        rule = np.ascontiguousarray(rule, dtype=_ffi.AUTOMATON_RULE).reshape(1)
+        info = np.zeros(1, dtype=_ffi.AUTOMATON_INFO)
+        counts = np.zeros((max(int(rule["steps"][0]), 1), 2), dtype=np.uint64)
+        self._check(self._lib.blok_hip_volume_automaton(self._ctx, _vec3(lo), _vec3(hi), _ffi.ptr(rule), _ffi.ptr(counts), _ffi.ptr(info)))
+        return info, counts
+
     def volume_lod_info(self) -> np.ndarray:
         info = np.zeros(1, dtype=_ffi.LOD_INFO)
         self._check(self._lib.blok_hip_volume_lod_info(self._ctx, _ffi.ptr(info)))

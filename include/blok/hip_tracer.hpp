@@ -485,6 +485,16 @@ public:
         check(blok_hip_volume_lod_model(m_ctx, level, minCount, &model, outVoxels));
         return model;
     }
+    // Steps a neighbour-count rule over a region of the resident volume (world voxels, half-open, both null = the whole box), in place
+    // (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life.  outStepCounts (may be null) takes the cells born and died
+    // per step, 2 * rule.steps values.  Returns what the call did; the next rebuildVolume installs the world.
+    blok_automaton_info volumeAutomaton(const blok_automaton_rule& rule, const int32_t* regionLo = nullptr, const int32_t* regionHi = nullptr,
+                                        std::vector<uint64_t>* outStepCounts = nullptr) {
+        blok_automaton_info info{};
+        if (outStepCounts) outStepCounts->assign(rule.steps <= 255u ? 2 * size_t(rule.steps) : 0, 0);      // (more steps than that are refused)
+        check(blok_hip_volume_automaton(m_ctx, regionLo, regionHi, &rule, outStepCounts && !outStepCounts->empty() ? outStepCounts->data() : nullptr, &info));
+        return info;
+    }
     void rebuildVolume(const std::vector<blok_material>& materials) { check(blok_hip_volume_rebuild(m_ctx, materials.data(), materials.size())); }
 
     // ---- image-space chain (Denoiser::denoise, PostProcess::process) over device planes; see include/blok_hip.h

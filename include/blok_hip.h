@@ -584,7 +584,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  *       resident volume in one pass.
  * 1.16: the resident volume reduced to a pyramid of coarser levels (counts and a voted material id per cell); a level as a model.
  * 1.17: a power-of-two scale on instanced models (blok_hip_model_set_scale): a coarse level traced at its true size beside the world.
- * 1.18: models resampled into the resident volume through an affine map (blok_hip_volume_stamp_affine): any rotation, scale, mirror, shear. */
+ * 1.18: models resampled into the resident volume through an affine map (blok_hip_volume_stamp_affine): any rotation, scale, mirror, shear.
+ * 1.19: neighbour-count rules stepped over the resident volume (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -1351,6 +1352,62 @@ int blok_hip_volume_reduce(blok_hip_ctx* ctx, const int32_t region_lo[3], const 
 int blok_hip_volume_lod_info(blok_hip_ctx* ctx, blok_lod_info* out_info);
 int blok_hip_volume_lod_download(blok_hip_ctx* ctx, uint32_t level, uint32_t plane, void* out_host, uint64_t first, uint64_t count);
 int blok_hip_volume_lod_model(blok_hip_ctx* ctx, uint32_t level, uint32_t min_count, uint32_t* out_model, uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- neighbour-count rules stepped over the resident volume (ABI 1.19)
+ * The one edit that decides a cell from its own 3 x 3 x 3 neighbourhood: smooth (the majority of the neighbourhood), despeckle, fill pits,
+ * the cellular-automaton caves behind a terrain's noise, 3-D Life-like rules.  blok_hip_volume_automaton steps a rule over a region of the
+ * volume in place.  The neighbour counts are taken from the brick masks where they lie, never from the densities.  A pure integer function
+ * of density > 0 and the ids: one right answer, bit-identical on the host (blok_automaton_voxels, blok_world.h) and on the device, the
+ * same in the keyed and the row-major brick layout.  The call blocks.
+ *  - Cell state.  Inside the volume's box a cell is filled iff density > 0; zero, negative and NaN densities are empty (§19's rule).
+ *  - Outside the box a cell is empty; with BLOK_AUTOMATON_BOX_IS_SOLID it is filled.
+ *  - Outside the region a cell inside the box counts with its real state and is never written: it is frozen across all steps.
+ *  - Region: world voxels, half open; both pointers NULL = the whole box.  It need not be brick aligned.
+ *  - Neighbourhood: 6 (the faces), 18 (and the edges) or 26 (and the corners): the cells at squared distance <= 1, 2, 3.
+ *  - A step is synchronous: every region cell is decided from the state BEFORE the step.  With n the number of filled cells among the cell's
+ *    neighbourhood, a filled cell with bit n of `survive` clear dies, an empty cell with bit n of `birth` set is born.  A cell that dies
+ *    gets (0.0f, 0), as BLOK_DISTANCE_SHRINK writes; a cell that is born gets (rule.density, id); every other cell keeps both of its 32-bit
+ *    values bit for bit — an empty cell its NaN or negative density and its stale id.
+ *  - The id of a born cell.  With BLOK_AUTOMATON_FIXED_MATERIAL it is rule.material.  Otherwise the cells of its neighbourhood that lie
+ *    inside the box and were filled before the step — those that die in this step included — cast one vote each for their stored id; the
+ *    most votes win, a tie goes to the smallest id (§24's rule); with no voter (only the solid outside, or bit 0 of `birth`) the id is
+ *    rule.material.  The ids of empty cells never vote.
+ *  - Steps.  Step k + 1 reads what step k left.  The call stops after the first step that changes nothing; that step counts in steps_run.
+ *  - out_step_counts (may be NULL) takes 2 * rule.steps values: the cells born and the cells that died in step k at [2 k] and [2 k + 1],
+ *    zero for the steps past steps_run.
+ *  - Info (out_info may be NULL): the region, steps_run, n_born and n_died summed over the steps run, n_filled the filled region cells
+ *    after the last of them.
+ *  - After the call masks, occupancy words, dirty flags and the edited box are those blok_hip_volume_set_voxels leaves for the same writes,
+ *    refreshed over the region after every step that wrote; the writes count as ones that may have filled voxels iff birth != 0.
+ *    Snapshots and labels are untouched.  The next blok_hip_volume_rebuild installs the world.
+ *  - Errors, each leaving the volume untouched.  BLOK_ERR_INVALID_ARG: a NULL rule, a neighbourhood other than 6, 18, 26, a bit of
+ *    `survive` or `birth` above the neighbourhood's size, unknown flag bits, reserved != 0, steps outside 1 .. 255, birth != 0 with a
+ *    density that is not finite or <= 0, exactly one region pointer NULL, lo > hi on an axis.  BLOK_ERR_UNSUPPORTED: a region that leaves
+ *    the box, a volume above 2^32 cells.  BLOK_ERR_NO_WORLD: no volume.  BLOK_ERR_OOM: a failed device allocation (16 bytes per brick of
+ *    the region, for the call).  An empty region is BLOK_OK with zero counts and steps_run = 0. */
+#define BLOK_AUTOMATON_BOX_IS_SOLID   1u   /* cells outside the volume's box count as filled (default: as empty) */
+#define BLOK_AUTOMATON_FIXED_MATERIAL 2u   /* a born cell gets rule.material; nobody votes */
+typedef struct blok_automaton_rule {
+    uint32_t neighbourhood; /* 6 (faces), 18 (+ edges), 26 (+ corners): the cells at squared distance <= 1, 2, 3 */
+    uint32_t survive;       /* bit n: a filled cell with n filled neighbours stays filled */
+    uint32_t birth;         /* bit n: an empty cell with n filled neighbours becomes filled */
+    uint32_t flags;         /* BLOK_AUTOMATON_* */
+    float    density;       /* what a born cell gets; finite and > 0 when birth != 0 */
+    uint32_t material;      /* a born cell's id with FIXED_MATERIAL, else the id when nobody votes */
+    uint32_t steps;         /* 1 .. 255 */
+    uint32_t reserved;      /* 0 */
+} blok_automaton_rule;      /* 32 bytes */
+typedef struct blok_automaton_info {
+    uint32_t version;       /* 1 */
+    uint32_t flags;         /* the rule's flags */
+    int32_t  lo[3];         /* the region, world voxels */
+    uint32_t ext[3];
+    uint32_t steps_run;
+    uint32_t reserved;      /* 0 */
+    uint64_t n_born, n_died, n_filled;   /* summed over the steps run; filled region cells after the last */
+} blok_automaton_info;      /* 64 bytes */
+int blok_hip_volume_automaton(blok_hip_ctx* ctx, const int32_t region_lo[3], const int32_t region_hi[3], const blok_automaton_rule* rule,
+                              uint64_t* out_step_counts, blok_automaton_info* out_info);
 
 /* ------------------------------------------------------------- several devices, one process
  * The tile partition of the frame over the GPUs of one node driven from one host thread (no reference

@@ -348,6 +348,17 @@ int blok_lod_reduce(const float* density, const uint32_t* material_ids, const in
                     const int32_t region_lo[3], const int32_t region_hi[3], uint32_t levels, uint32_t flags, void* out_planes,
                     uint64_t capacity_bytes, blok_lod_info* out_info);
 
+/* -------------------------------------------------------------- neighbour-count rules on the host (automaton.cpp)
+ * The contract of blok_hip_volume_automaton (blok_hip.h; the records and the flags are declared there) over host arrays of a box as above,
+ * in place: a plain double-buffered loop per cell, through the check, the offsets and the vote the kernels use.
+ * automaton_check: BLOK_OK, or BLOK_ERR_INVALID_ARG with the rule that failed in err (may be NULL).
+ * automaton_voxels: out_step_counts (may be NULL) takes 2 * rule->steps values, *out_info (may be NULL) what the device's info holds.
+ * Errors as the device entry; a NULL array with a non-empty region is BLOK_ERR_INVALID_ARG.  Nothing is written on an error. */
+int blok_automaton_check(const blok_automaton_rule* rule, char* err, size_t err_len);
+int blok_automaton_voxels(float* density, uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
+                          const int32_t region_lo[3], const int32_t region_hi[3], const blok_automaton_rule* rule, uint64_t* out_step_counts,
+                          blok_automaton_info* out_info);
+
 /* = loadAndImportVox (reference blok/src/vox_loader.cpp:432-462); lib may be NULL. */
 int  blok_load_and_import_vox(const char* path, blok_world* w, blok_material_library* lib,
                               const float world_offset[3], uint32_t model_index, char* err, size_t err_len);

@@ -1,7 +1,7 @@
 // Headless driver shaped like the reference's App (reference blok/src/app.cpp:65-192) with the backend
 // switch extended by GraphicsApi::HIP: build a world through ChunkManager, rebuildDirtyChunks,
 // packChunksToGpuSvo, addWorld, then a frame loop of drawFrame; writes the last frame as a PPM.
-//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]] [--far K[,MIN]] [--paste FILE.vox@X,Y,Z,YAW_DEG,SCALE]
+//   blok_headless [--n 256 | --vox model.vox | --obj model.obj [--obj-size 256] [--solid] | --terrain SEED [--terrain-size 256] [--obj model.obj]] [--size 1280x720] [--pose 0|1|2] [--frames 10] [--out frame.ppm] [--rt [--spp 8]] [--export-obj surface.obj] [--components] [--settle] [--save-volume world.bvol] [--seal [--seal-material N]] [--hollow D2] [--rule NB,SURVIVE_HEX,BIRTH_HEX,STEPS[,solid] | --smooth STEPS] [--populate A.vox[,B.vox...] [--bake]] [--scroll DX,DY,DZ] [--stroke X,Y,Z:X,Y,Z:...,R[,OP]] [--lod K[,MIN]] [--far K[,MIN]] [--paste FILE.vox@X,Y,Z,YAW_DEG,SCALE]
 //   blok_headless --load-volume world.bvol [--terrain SEED --terrain-size N] ...
 //   --obj: a triangle mesh (with its mtllib) fitted into a resident volume of --obj-size^3 voxels and voxelized on the device
 //          (surface shell, or filled with --solid), then rebuilt with the library's materials
@@ -45,6 +45,11 @@
 //   --hollow D2: with --terrain, --obj or --load-volume, once the volume is filled and before it is rebuilt: the to-empty distance field of the
 //          whole box with R = ceil(sqrt(D2)) (blok_hip_volume_distance_field), then BLOK_DISTANCE_HOLLOW at D2: only the shell within D2
 //          (a squared distance) of empty space stays.  D2 >= 3 keeps every cell a primary ray can enter, so the frames do not change
+//   --rule NB,SURVIVE_HEX,BIRTH_HEX,STEPS[,solid]: with --terrain, --obj or --load-volume, once the volume is filled (and hollowed) and before
+//          it is rebuilt: a neighbour-count rule stepped over the whole box (blok_hip_volume_automaton): neighbourhood NB (6, 18, 26), the bit
+//          sets of the counts at which a filled cell stays and an empty one is born, in hexadecimal, at most STEPS steps, with "solid" the
+//          outside of the box filled; born cells get density 1 and the most frequent id among their filled neighbours.  Prints the info line
+//   --smooth STEPS: shorthand for --rule 26,7FFE000,7FFC000,STEPS: the majority of the 26 neighbours (survive at 13 or more, born at 14 or more)
 //   --seal: with --terrain, --obj or --load-volume, once the volume is filled and before it is rebuilt: the empty cells of the whole box are
 //          flooded from all six faces with max_steps 65534 (blok_hip_volume_flood_field), then BLOK_FLOOD_FILL_UNREACHED fills every empty
 //          cell the air did not reach with material 0, or --seal-material N: an openly voxelized shell becomes solid, caves no one can
@@ -97,6 +102,7 @@ struct Options {
     bool seal = false;                    // fill the empty cells that air from the box's faces does not reach, before the rebuild
     uint32_t seal_material = 0;
     int64_t hollow = -1;                  // >= 0: hollow the resident volume at this squared distance before the rebuild
+    blok_automaton_rule rule = {};        // steps > 0: step this neighbour-count rule over the resident volume before the rebuild
     bool scroll = false;                  // move the terrain's box by scroll_delta after the fill
     uint32_t lod = 0, lod_min = 1;        // > 0: render level `lod` of the terrain's pyramid, the cells with at least lod_min filled voxels
     uint32_t far = 0, far_min = 1;        // > 0: the eight boxes around the terrain's as level-`far` copies, instances of scaled models
@@ -137,6 +143,7 @@ private:
                 if (m_opt.settle) throw std::runtime_error("--settle needs a resident volume: --terrain or --obj");
                 if (!m_opt.save_volume.empty()) throw std::runtime_error("--save-volume needs a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.hollow >= 0) throw std::runtime_error("--hollow needs a resident volume: --terrain, --obj or --load-volume");
+                if (m_opt.rule.steps) throw std::runtime_error("--rule and --smooth need a resident volume: --terrain, --obj or --load-volume");
                 if (m_opt.seal) throw std::runtime_error("--seal needs a resident volume: --terrain, --obj or --load-volume");
                 if (!m_opt.populate.empty()) throw std::runtime_error("--populate needs a terrain: --terrain");
                 if (!m_opt.paste.empty()) throw std::runtime_error("--paste needs a terrain: --terrain");
@@ -256,6 +263,7 @@ private:
         }
         seal();
         hollow();
+        automaton();
         stroke();
         populate(p);
         paste();
@@ -326,6 +334,7 @@ private:
         m_tracer->decodeBricks(s);
         seal();
         hollow();
+        automaton();
         stroke();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats w = m_tracer->worldStats();
@@ -453,6 +462,12 @@ private:
         const uint64_t cleared = m_tracer->editByDistance(BLOK_DISTANCE_HOLLOW, d2);
         std::cout << "hollow: " << cleared << " voxels cleared, " << info.n_near + info.n_far - cleared << " left\n";      // (the filled cells are those with D > 0)
     }
+    // The rule of --rule or --smooth stepped over the whole box.
+    void automaton() {
+        if (!m_opt.rule.steps) return;
+        const blok_automaton_info info = m_tracer->volumeAutomaton(m_opt.rule);
+        std::cout << "rule: " << info.steps_run << " steps run, " << info.n_born << " voxels born, " << info.n_died << " died, " << info.n_filled << " left\n";
+    }
     // The far-field copy of the terrain in place of the terrain: level K of the whole box's pyramid, installed as a dense world of voxel size 2^K.
     void lod() {
         if (!m_opt.lod) return;
@@ -523,6 +538,7 @@ private:
         const uint64_t written = m_tracer->voxelizeMesh(pos, tri, mat, 1, 1.0f, m_opt.solid);
         seal();
         hollow();
+        automaton();
         stroke();
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
@@ -708,6 +724,19 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--seal")) opt.seal = true;
         else if (!std::strcmp(argv[i], "--seal-material")) opt.seal_material = static_cast<uint32_t>(std::atoll(next()));
         else if (!std::strcmp(argv[i], "--hollow")) { opt.hollow = std::atoll(next()); if (opt.hollow < 0 || opt.hollow > 65025) { std::fprintf(stderr, "--hollow takes a squared distance in 0..65025\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--rule") || !std::strcmp(argv[i], "--smooth")) {
+            const bool smooth = argv[i][2] == 's';
+            const std::string arg = next();
+            unsigned nb = 26, survive = 0x7FFE000u, birth = 0x7FFC000u, steps = 0;
+            char tail[8] = "";
+            const int n = smooth ? std::sscanf(arg.c_str(), "%u%1s", &steps, tail) : std::sscanf(arg.c_str(), "%u,%x,%x,%u,%7s", &nb, &survive, &birth, &steps, tail);
+            const bool solid = !smooth && n == 5 && !std::strcmp(tail, "solid");
+            opt.rule = blok_automaton_rule{nb, survive, birth, solid ? BLOK_AUTOMATON_BOX_IS_SOLID : 0u, 1.0f, 0u, steps, 0u};
+            if ((smooth ? n != 1 : (n != 4 && !solid)) || blok_automaton_check(&opt.rule, nullptr, 0) != BLOK_OK) {
+                std::fprintf(stderr, "--rule takes NB,SURVIVE_HEX,BIRTH_HEX,STEPS[,solid] with NB 6, 18 or 26 and 1..255 steps; --smooth takes 1..255 steps\n");
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[i], "--populate")) { for (std::string list = next(); !list.empty();) { const size_t c = list.find(','); opt.populate.push_back(list.substr(0, c)); list = c == std::string::npos ? "" : list.substr(c + 1); } }
         else if (!std::strcmp(argv[i], "--bake")) opt.bake = true;
         else if (!std::strcmp(argv[i], "--paste")) {
