@@ -107,6 +107,7 @@ LOD_LEVEL = np.dtype([("clo", "<i4", 3), ("cext", "<u4", 3), ("n_cells", "<u8"),
 LOD_INFO = np.dtype([("version", "<u4"), ("flags", "<u4"), ("levels", "<u4"), ("reserved", "<u4"), ("lo", "<i4", 3), ("ext", "<u4", 3), ("level", LOD_LEVEL, 5)])
 LOD_VOTE_EXPOSED = 1                              # = BLOK_LOD_VOTE_EXPOSED
 LOD_MAX_LEVELS = 5                                # = BLOK_LOD_MAX_LEVELS
+LOD_SEAMLESS = 2                                  # = BLOK_LOD_SEAMLESS (terrain_reduce only)
 # = blok_affine (96 bytes): world -> model, m and t in units of 2^-16 model voxel (blok_amd.affine makes them)
 AFFINE = np.dtype([("model", "<u4"), ("anchor", "<i4", 3), ("m", "<i4", (3, 3)), ("reserved", "<u4", 5), ("t", "<i8", 3)])
 # = blok_automaton_rule (32 bytes) and blok_automaton_info (64 bytes): a neighbour-count rule and what a call of it did (blok_amd.automaton makes rules)
@@ -281,6 +282,7 @@ HOST_SYMBOLS = {
     "blok_shapes_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "blok_lod_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blok_terrain_reduce": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "blok_automaton_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_automaton_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -461,6 +463,7 @@ HIP_SYMBOLS = {
     "blok_hip_volume_lod_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_volume_lod_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_lod_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "blok_hip_terrain_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_void_p]),
     "blok_hip_volume_automaton": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_hip_download_model": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "blok_hip_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),

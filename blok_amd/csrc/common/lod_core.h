@@ -30,6 +30,12 @@ inline int check_args(uint32_t levels, uint32_t flags) {
     if (flags & ~kFlags) return kUnknownFlags;
     return kFine;
 }
+// The same for an entry that knows more flag bits than kFlags (terrain_lod_core.h: blok_hip_terrain_reduce takes BLOK_LOD_SEAMLESS).
+inline int check_args(uint32_t levels, uint32_t flags, uint32_t known) {
+    if (levels == 0u || levels > BLOK_LOD_MAX_LEVELS) return kLevels;
+    if (flags & ~known) return kUnknownFlags;
+    return kFine;
+}
 inline const char* rule_text(int rule) { return rule == kLevels ? "levels must be 1 .. 5" : rule == kUnknownFlags ? "unknown flag bits" : ""; }
 
 // ---- the grids ---------------------------------------------------------------------------------------------------------------------------

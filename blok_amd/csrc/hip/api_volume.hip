@@ -12,6 +12,7 @@
 #include "../common/scroll_core.h"
 #include "../common/shapes_core.h"
 #include "../common/lod_core.h"
+#include "../common/terrain_lod_core.h"
 #include "../common/automaton_core.h"
 #include "device_mem.h"
 #include <chrono>
@@ -782,6 +783,27 @@ int blok_hip_volume_reduce(blok_hip_ctx* ctx, const int32_t region_lo[3], const 
     blok::GpuLod snapshot;
     // (edits are enqueued on the null stream, and so is this: it reads the masks and the ids they leave)
     const blok::GpuBuildStatus st = blok::gpu_volume_reduce(&ctx->volume, lo, hi, levels, flags, &snapshot, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    blok::gpu_lod_free(&ctx->lod);
+    ctx->lod = snapshot; ctx->lod.taken = true;
+    if (out_info) *out_info = snapshot.info;
+    return BLOK_OK;
+}
+
+int blok_hip_terrain_reduce(blok_hip_ctx* ctx, const blok_terrain_params* params, const int32_t region_lo[3], const int32_t region_hi[3],
+                            uint32_t levels, uint32_t flags, blok_lod_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!params) return set_error(ctx, BLOK_ERR_INVALID_ARG, "terrain_reduce: null parameters");
+    if (blok::terrain::check_params(*params) != 0) return set_error(ctx, BLOK_ERR_INVALID_ARG, "terrain_reduce: parameters outside their limits (blok_terrain_validate)");
+    if (params->flags != 0u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "terrain_reduce: params->flags must be 0 (SHELL, CLOSE_SIDES and ADD describe writes into a volume)");
+    if (const int rule = blok::lod::check_args(levels, flags, blok::terrain_lod::kFlags)) return set_error(ctx, BLOK_ERR_INVALID_ARG, std::string("terrain_reduce: ") + blok::lod::rule_text(rule));
+    if (!region_lo || !region_hi) return set_error(ctx, BLOK_ERR_INVALID_ARG, "terrain_reduce: both region corners are required");
+    if (const int rc = blok::terrain_lod::check_region(region_lo, region_hi))
+        return set_error(ctx, rc, rc == BLOK_ERR_INVALID_ARG ? "terrain_reduce: region lo > hi" : "terrain_reduce: a coordinate beyond 2^30, an extent above 65536 or 2^31 level-1 cells");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string why;
+    blok::GpuLod snapshot;
+    const blok::GpuBuildStatus st = blok::gpu_terrain_reduce(*params, region_lo, region_hi, levels, flags, &snapshot, &why);
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
     blok::gpu_lod_free(&ctx->lod);
     ctx->lod = snapshot; ctx->lod.taken = true;

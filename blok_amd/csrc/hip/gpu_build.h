@@ -301,6 +301,10 @@ void gpu_lod_free(GpuLod* l);
 // null when the region has no cell).  Blocking.
 GpuBuildStatus gpu_volume_reduce(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t levels, uint32_t flags, GpuLod* out,
                                  std::string* why);
+// = blok_hip_terrain_reduce: the same snapshot for the world region [lo, hi) of the terrain function, level 1 from the function itself
+// (arguments that have passed terrain::check_params, lod::check_args and terrain_lod::check_region).  Needs no volume and touches none.
+GpuBuildStatus gpu_terrain_reduce(const blok_terrain_params& params, const int32_t lo[3], const int32_t hi[3], uint32_t levels, uint32_t flags,
+                                  GpuLod* out, std::string* why);
 // = blok_hip_volume_lod_model: gpu_volume_capture over a level of the snapshot, a cell filled iff its n >= min_count, its id the voted one;
 // model coordinates are relative to the level's grid corner.
 GpuBuildStatus gpu_lod_capture(const GpuLod* l, uint32_t level, uint32_t min_count, GpuTree* out, int32_t box_lo[3], int32_t box_hi[3],

@@ -12,6 +12,7 @@
 // DESIGN.md §13).  The count and the box of the filled voxels are reduced per wave with shuffles, per workgroup through LDS, then one
 // lane takes seven integer atomics into one of kSpread copies.  gpu_volume_commit over the written box leaves masks, occupancy words and
 // dirty flags.
+// (The same function reduced straight to coarse levels, with no volume written: blok_hip_terrain_reduce, lod_kernels.hip: terrain_lod_kernel.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

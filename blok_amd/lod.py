@@ -11,6 +11,7 @@ from . import _ffi
 from ._ffi import BlokError
 
 VOTE_EXPOSED = _ffi.LOD_VOTE_EXPOSED
+SEAMLESS = _ffi.LOD_SEAMLESS                          # terrain_reduce only
 MAX_LEVELS = _ffi.LOD_MAX_LEVELS
 INFO = _ffi.LOD_INFO
 PLANE_DTYPES = (np.uint16, np.uint16, np.uint32)      # plane 0 n, 1 e, 2 id
@@ -57,4 +58,22 @@ def reduce_host(density, material_ids, origin=(0, 0, 0), lo=None, hi=None, level
         rc = lib.blok_lod_reduce(*args, _ffi.ptr(raw), n_bytes, _ffi.ptr(info))
         if rc != 0:
             raise BlokError(rc, "blok_lod_reduce")
+    return split_planes(raw, info), info
+
+
+def terrain_reduce_host(params, lo, hi, levels: int = 1, flags: int = 0):
+    """blok_terrain_reduce: the terrain function (a blok_amd.terrain.TerrainParams with flags 0) over the world region [lo, hi), reduced
+    without a voxel array; the host build of HipTracer.terrain_reduce.  Returns (levels, info)."""
+    lib = _ffi.host_lib()
+    info = np.zeros(1, dtype=INFO)
+    args = (C.byref(params), _vec(lo), _vec(hi), int(levels), int(flags))
+    rc = lib.blok_terrain_reduce(*args, None, 0, _ffi.ptr(info))
+    if rc != 0:
+        raise BlokError(rc, "blok_terrain_reduce")
+    n_bytes = 8 * sum(int(info["level"][0][j]["n_cells"]) for j in range(int(levels)))
+    raw = np.zeros(n_bytes, dtype=np.uint8)
+    if n_bytes:
+        rc = lib.blok_terrain_reduce(*args, _ffi.ptr(raw), n_bytes, _ffi.ptr(info))
+        if rc != 0:
+            raise BlokError(rc, "blok_terrain_reduce")
     return split_planes(raw, info), info

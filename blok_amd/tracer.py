@@ -426,6 +426,14 @@ class HipTracer:
         self._check(self._lib.blok_hip_volume_reduce(self._ctx, _vec3(lo), _vec3(hi), int(levels), int(flags), _ffi.ptr(info)))
         return info
 
+    def terrain_reduce(self, params, lo, hi, levels: int = 1, flags: int = 0) -> np.ndarray:
+        """Reduces the terrain function (params a blok_amd.terrain.TerrainParams with flags 0) over the world region [lo, hi) to `levels`
+        coarser levels without a volume (blok_hip.h: blok_hip_terrain_reduce; flags: _ffi.LOD_VOTE_EXPOSED, _ffi.LOD_SEAMLESS).  Fills the
+        snapshot volume_reduce fills: volume_lod_info, volume_lod_download and volume_lod_model work behind it.  Returns the info."""
+        info = np.zeros(1, dtype=_ffi.LOD_INFO)
+        self._check(self._lib.blok_hip_terrain_reduce(self._ctx, C.byref(params), _vec3(lo), _vec3(hi), int(levels), int(flags), _ffi.ptr(info)))
+        return info
+
     def volume_automaton(self, rule, lo=None, hi=None):
         """Steps a neighbour-count rule (one _ffi.AUTOMATON_RULE record; blok_amd.automaton makes them) over a region of the resident
         volume (world voxels, half open; both None = the whole box), in place (blok_hip.h: blok_hip_volume_automaton).  Returns (info,

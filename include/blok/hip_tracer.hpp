@@ -463,6 +463,14 @@ public:
         check(blok_hip_volume_reduce(m_ctx, regionLo, regionHi, levels, flags, &info));
         return info;
     }
+    // The terrain function over the world region [regionLo, regionHi) reduced to `levels` coarser levels without a volume
+    // (blok_hip_terrain_reduce; flags: BLOK_LOD_VOTE_EXPOSED, BLOK_LOD_SEAMLESS): the snapshot reduceVolume fills, so lodInfo, downloadLod
+    // and lodModel work behind it.  A volume that exists is left alone.
+    blok_lod_info reduceTerrain(const blok_terrain_params& params, const int32_t* regionLo, const int32_t* regionHi, uint32_t levels = 1, uint32_t flags = 0) {
+        blok_lod_info info{};
+        check(blok_hip_terrain_reduce(m_ctx, &params, regionLo, regionHi, levels, flags, &info));
+        return info;
+    }
     blok_lod_info lodInfo() {
         blok_lod_info info{};
         check(blok_hip_volume_lod_info(m_ctx, &info));

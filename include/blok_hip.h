@@ -585,7 +585,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.16: the resident volume reduced to a pyramid of coarser levels (counts and a voted material id per cell); a level as a model.
  * 1.17: a power-of-two scale on instanced models (blok_hip_model_set_scale): a coarse level traced at its true size beside the world.
  * 1.18: models resampled into the resident volume through an affine map (blok_hip_volume_stamp_affine): any rotation, scale, mirror, shear.
- * 1.19: neighbour-count rules stepped over the resident volume (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life. */
+ * 1.19: neighbour-count rules stepped over the resident volume (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life.
+ * 1.20: procedural terrain reduced to coarse levels without a volume (blok_hip_terrain_reduce): the far field built at any time. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -1352,6 +1353,27 @@ int blok_hip_volume_reduce(blok_hip_ctx* ctx, const int32_t region_lo[3], const 
 int blok_hip_volume_lod_info(blok_hip_ctx* ctx, blok_lod_info* out_info);
 int blok_hip_volume_lod_download(blok_hip_ctx* ctx, uint32_t level, uint32_t plane, void* out_host, uint64_t first, uint64_t count);
 int blok_hip_volume_lod_model(blok_hip_ctx* ctx, uint32_t level, uint32_t min_count, uint32_t* out_model, uint64_t* out_n_voxels);
+
+/* ------------------------------------------------------------- procedural terrain reduced to coarse levels without a volume (ABI 1.20)
+ * blok_hip_terrain_reduce evaluates the terrain function (blok_terrain_params, above) over the world region [region_lo, region_hi) and
+ * reduces it `levels` times in one pass, without writing a voxel anywhere: it fills the snapshot blok_hip_volume_reduce fills, so
+ * blok_hip_volume_lod_info, _lod_download and _lod_model work behind it unchanged and the snapshot has the same life.  It needs no
+ * volume; a volume that exists is neither read nor written, and no other snapshot changes.  The call blocks.
+ *  - Without BLOK_LOD_SEAMLESS the planes and the info are, byte for byte, what blok_hip_volume_generate_terrain(params, NULL, NULL)
+ *    followed by blok_hip_volume_reduce(NULL, NULL, levels, flags) leaves on a volume whose box is exactly the region (origin region_lo,
+ *    dims region_hi - region_lo): the faces of the region expose nothing.
+ *  - With BLOK_LOD_SEAMLESS a filled voxel is exposed iff the function says one of its six neighbours is empty, wherever the region ends:
+ *    the result of reduce(region_lo, region_hi, levels, flags & BLOK_LOD_VOTE_EXPOSED) on a volume whose box is the region grown by one
+ *    voxel on every side and filled the same way.  Promise: for regions whose corners are multiples of 2^levels, the planes of a union
+ *    of regions are the concatenation of the parts' planes (a ring of coarse boxes can be built and refreshed in strips).
+ *  - info.flags holds the flags as passed; everything else in the info is the composition's.
+ *  - BLOK_ERR_INVALID_ARG: NULL params, parameters blok_terrain_validate refuses, params->flags != 0 (SHELL, CLOSE_SIDES and ADD describe
+ *    writes into a volume), a NULL region pointer, lo > hi on an axis, levels 0 or above BLOK_LOD_MAX_LEVELS, unknown flag bits.
+ *    BLOK_ERR_UNSUPPORTED: a coordinate beyond +-2^30, an extent above 65536 on an axis, 2^31 or more level-1 cells.  BLOK_ERR_OOM.
+ *    Every error leaves the previous snapshot in place.  lo == hi on an axis is BLOK_OK with an empty snapshot.  out_info may be NULL. */
+#define BLOK_LOD_SEAMLESS 2u          /* terrain_reduce only: neighbours judged by the function, not by the region's faces */
+int blok_hip_terrain_reduce(blok_hip_ctx* ctx, const blok_terrain_params* params, const int32_t region_lo[3], const int32_t region_hi[3],
+                            uint32_t levels, uint32_t flags, blok_lod_info* out_info);
 
 /* ------------------------------------------------------------- neighbour-count rules stepped over the resident volume (ABI 1.19)
  * The one edit that decides a cell from its own 3 x 3 x 3 neighbourhood: smooth (the majority of the neighbourhood), despeckle, fill pits,

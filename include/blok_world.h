@@ -347,6 +347,11 @@ int blok_shapes_voxels(float* density, uint32_t* material_ids, const int32_t ori
 int blok_lod_reduce(const float* density, const uint32_t* material_ids, const int32_t origin[3], uint32_t nx, uint32_t ny, uint32_t nz,
                     const int32_t region_lo[3], const int32_t region_hi[3], uint32_t levels, uint32_t flags, void* out_planes,
                     uint64_t capacity_bytes, blok_lod_info* out_info);
+/* The contract of blok_hip_terrain_reduce (blok_hip.h) on the host: the terrain function over the world region, reduced tile by tile
+ * through the column words the kernel uses; no voxel array is made.  The planes, out_planes and capacity_bytes as blok_lod_reduce.
+ * Errors as the device entry. */
+int blok_terrain_reduce(const blok_terrain_params* params, const int32_t region_lo[3], const int32_t region_hi[3], uint32_t levels,
+                        uint32_t flags, void* out_planes, uint64_t capacity_bytes, blok_lod_info* out_info);
 
 /* -------------------------------------------------------------- neighbour-count rules on the host (automaton.cpp)
  * The contract of blok_hip_volume_automaton (blok_hip.h; the records and the flags are declared there) over host arrays of a box as above,

@@ -24,6 +24,11 @@
 //          times 2^K, traced by blok_hip_trace_primary_instanced (--rt: by the instanced ray-tracing frame).  Prints per neighbour
 //          "far: box (x,y,z): N voxels at level K" (a neighbour without such a cell is left out, with 0) and, after the last frame, "far:
 //          instances won P of W pixels".  Not with --load-volume, --scroll, --lod, --populate or --obj.
+//   --far K[,MIN] --far-direct: the same eight neighbours, the same lines and the same image, through blok_hip_terrain_reduce: the ring is
+//          built after the fine box stands, and no volume is made for it.
+//   --far K[,MIN] --far-rings R: R rings (1 .. 3; implies --far-direct): ring r is the 8 r boxes of edge --terrain-size at Chebyshev
+//          distance r in x and z, reduced to level min(K + r - 1, 5) with MIN clamped to 8^level and placed at that scale; the same line
+//          per box, in z-then-x order, ring by ring.
 //   --stroke X,Y,Z:X,Y,Z:...,R[,OP]: with --terrain, --obj or --load-volume, before the rebuild: a brush of radius R dragged through the world
 //          points (voxels; multiples of one half: W.5 is the centre of voxel W), as one table of capsules in one pass
 //          (blok_hip_volume_apply_shapes); OP is add (the default, density 1), subtract (density 0), erase, set, keep or paint (the last
@@ -105,6 +110,8 @@ struct Options {
     blok_automaton_rule rule = {};        // steps > 0: step this neighbour-count rule over the resident volume before the rebuild
     bool scroll = false;                  // move the terrain's box by scroll_delta after the fill
     uint32_t lod = 0, lod_min = 1;        // > 0: render level `lod` of the terrain's pyramid, the cells with at least lod_min filled voxels
+    bool far_direct = false;              // --far-direct: the ring through blok_hip_terrain_reduce, after the fine box, with no volume of its own
+    uint32_t far_rings = 0;               // --far-rings R: R rings (1 .. 3), ring r at level min(far + r - 1, 5); implies far_direct
     uint32_t far = 0, far_min = 1;        // > 0: the eight boxes around the terrain's as level-`far` copies, instances of scaled models
     std::vector<std::array<int32_t, 3>> stroke;      // the points of --stroke, half-voxel units
     uint32_t stroke_radius = 0, stroke_op = BLOK_SHAPE_ADD;
@@ -270,6 +277,7 @@ private:
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
+        farFieldDirect(p);
         terrainCamera(p, N, ground);
     }
     // The far field: each of the eight boxes around the terrain's in x and z, generated where it lies, reduced, and kept as a scaled model.
@@ -278,6 +286,7 @@ private:
         if (m_opt.scroll || m_opt.lod || !m_opt.populate.empty() || !m_opt.obj.empty())
             throw std::runtime_error("--far shows the terrain and its ring alone: leave --scroll, --lod, --populate, --obj and --load-volume out");
         if (!m_opt.paste.empty()) throw std::runtime_error("--far shows the terrain and its ring alone: leave --paste out");
+        if (m_opt.far_direct) return;                           // (farFieldDirect, once the fine box stands)
         const uint32_t N = m_opt.terrain_size, K = m_opt.far;
         for (int dz = -1; dz <= 1; ++dz)
             for (int dx = -1; dx <= 1; ++dx) {
@@ -285,21 +294,43 @@ private:
                 const int32_t origin[3] = {dx * static_cast<int32_t>(N), 0, dz * static_cast<int32_t>(N)};
                 m_tracer->createVolume(origin, N, N, N);
                 m_tracer->generateTerrain(p);
-                const blok_lod_info info = m_tracer->reduceVolume(nullptr, nullptr, K, BLOK_LOD_VOTE_EXPOSED);
-                const blok_lod_level& L = info.level[K - 1];
-                uint32_t model = 0;
-                uint64_t voxels = 0;
-                const int rc = blok_hip_volume_lod_model(m_tracer->handle(), K, m_opt.far_min, &model, &voxels);
-                if (rc != BLOK_OK && rc != BLOK_ERR_UNSUPPORTED) throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_tracer->handle()));
-                if (rc == BLOK_ERR_UNSUPPORTED) voxels = 0;     // no cell holds that many voxels: the neighbour is left out
-                std::cout << "far: box (" << origin[0] << "," << origin[1] << "," << origin[2] << "): " << voxels << " voxels at level " << K << "\n";
-                if (!voxels) continue;
-                m_tracer->setModelScale(model, K);
-                blok_instance I{};
-                I.model = model;
-                for (int a = 0; a < 3; ++a) { I.offset[a] = L.clo[a] * (1 << K); I.axis[a] = static_cast<uint8_t>(a); }
-                m_instances.push_back(I);
+                farPlace(origin, m_tracer->reduceVolume(nullptr, nullptr, K, BLOK_LOD_VOTE_EXPOSED), K, m_opt.far_min);
             }
+        farCheck();
+    }
+    // --far-direct, --far-rings: the same boxes through blok_hip_terrain_reduce, with the fine box in place and no volume made for them;
+    // ring r (the 8 r boxes at Chebyshev distance r in x and z) at level min(K + r - 1, 5).
+    void farFieldDirect(const blok_terrain_params& p) {
+        if (!m_opt.far || !m_opt.far_direct) return;
+        const int32_t N = static_cast<int32_t>(m_opt.terrain_size);
+        for (int r = 1; r <= static_cast<int>(std::max(m_opt.far_rings, 1u)); ++r) {
+            const uint32_t level = std::min<uint32_t>(m_opt.far + static_cast<uint32_t>(r) - 1u, BLOK_LOD_MAX_LEVELS);
+            for (int dz = -r; dz <= r; ++dz)
+                for (int dx = -r; dx <= r; ++dx) {
+                    if (std::max(std::abs(dx), std::abs(dz)) != r) continue;
+                    const int32_t origin[3] = {dx * N, 0, dz * N}, end[3] = {origin[0] + N, N, origin[2] + N};
+                    farPlace(origin, m_tracer->reduceTerrain(p, origin, end, level, BLOK_LOD_VOTE_EXPOSED), level, std::min(m_opt.far_min, 1u << (3u * level)));
+                }
+        }
+        farCheck();
+    }
+    // Level `level` of the snapshot just taken of the box at `origin`: its cells with at least minCount voxels as a model of scale 2^level, placed.
+    void farPlace(const int32_t origin[3], const blok_lod_info& info, uint32_t level, uint32_t minCount) {
+        const blok_lod_level& L = info.level[level - 1];
+        uint32_t model = 0;
+        uint64_t voxels = 0;
+        const int rc = blok_hip_volume_lod_model(m_tracer->handle(), level, minCount, &model, &voxels);
+        if (rc != BLOK_OK && rc != BLOK_ERR_UNSUPPORTED) throw std::runtime_error(std::string("HipTracer: ") + blok_hip_last_error(m_tracer->handle()));
+        if (rc == BLOK_ERR_UNSUPPORTED) voxels = 0;     // no cell holds that many voxels: the neighbour is left out
+        std::cout << "far: box (" << origin[0] << "," << origin[1] << "," << origin[2] << "): " << voxels << " voxels at level " << level << "\n";
+        if (!voxels) return;
+        m_tracer->setModelScale(model, level);
+        blok_instance I{};
+        I.model = model;
+        for (int a = 0; a < 3; ++a) { I.offset[a] = L.clo[a] * (1 << level); I.axis[a] = static_cast<uint8_t>(a); }
+        m_instances.push_back(I);
+    }
+    void farCheck() {
         if (blok_hip_check_instances(m_tracer->handle(), m_instances.data(), static_cast<uint32_t>(m_instances.size())) != BLOK_OK)
             throw std::runtime_error(std::string("--far: ") + blok_hip_last_error(m_tracer->handle()));
     }
@@ -761,6 +792,11 @@ int main(int argc, char** argv) {
             const int got = std::sscanf(next(), "%u,%u", &opt.far, &opt.far_min);
             if (got < 1 || opt.far < 1 || opt.far > BLOK_LOD_MAX_LEVELS || opt.far_min < 1 || opt.far_min > (1u << (3u * opt.far))) { std::fprintf(stderr, "--far takes K[,MIN] with K in 1..5 and MIN in 1..8^K\n"); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--far-direct")) opt.far_direct = true;
+        else if (!std::strcmp(argv[i], "--far-rings")) {
+            if (std::sscanf(next(), "%u", &opt.far_rings) != 1 || opt.far_rings < 1 || opt.far_rings > 3) { std::fprintf(stderr, "--far-rings takes R in 1..3\n"); return 2; }
+            opt.far_direct = true;
+        }
         else if (!std::strcmp(argv[i], "--scroll")) { opt.scroll = true; if (std::sscanf(next(), "%d,%d,%d", &opt.scroll_delta[0], &opt.scroll_delta[1], &opt.scroll_delta[2]) != 3) { std::fprintf(stderr, "--scroll takes DX,DY,DZ\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--stroke")) { if (!parseStroke(next(), opt)) { std::fprintf(stderr, "--stroke takes X,Y,Z:X,Y,Z:...,R[,add|subtract|erase|set|keep|paint], coordinates and R in multiples of one half\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
@@ -772,6 +808,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--devices")) { for (const char* p = next(); *p;) { opt.devices.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
+    if (opt.far_direct && !opt.far) { std::fprintf(stderr, "--far-direct and --far-rings need --far K[,MIN]\n"); return 2; }
     try {
         App app(blok::GraphicsApi::HIP, opt);
         app.run();
