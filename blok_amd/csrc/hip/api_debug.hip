@@ -316,6 +316,7 @@ int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode) {
     ctx->beam_cache.enabled = mode != 0;
     ctx->beam_cache.refine = mode >= 2;
     ctx->beam_cache.packed = mode >= 3;
+    ctx->beam_cache.policy.own_starts = mode >= 4;
     blok::beam_cache_clear(ctx->beam_cache.policy);      // off: every launch searches, as before there was a cache; on again: views are admitted afresh
     if (!ctx->beam_cache.packed) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -362,6 +363,33 @@ int blok_hip_beam_cache_download_list(blok_hip_ctx* ctx, int* out_state, uint32_
     if (out_list_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_list_host, sl.d_list, entries * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_table_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_table_host, sl.d_table, sl.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_trips_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_trips_host, B.d_trips, pixels, hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+// The starts of that slot's list, in list order, and the restarted trips of the latest count launch (mode 4).
+int blok_hip_beam_cache_download_starts(blok_hip_ctx* ctx, int* out_state, float* out_starts_host, size_t starts_capacity, uint8_t* out_restarts_host, size_t restarts_capacity) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const auto& B = ctx->beam_cache;
+    if (out_state) *out_state = B.last_starts;
+    if (!out_starts_host && !out_restarts_host) return BLOK_OK;      // the state alone: waits for nothing
+    if (!B.last_list || B.last_slot < 0 || static_cast<uint32_t>(B.last_slot) >= blok::kBeamCacheSlots || !B.policy.starts[B.last_slot] || !B.slots[B.last_slot].d_start)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the latest launch's slot has no list with starts");
+    const auto& sl = B.slots[B.last_slot];
+    const size_t entries = static_cast<size_t>(sl.n_words / blok::kPackGroups) * blok::kPackStretch, pixels = static_cast<size_t>(B.last_w) * B.last_h;
+    if (entries > sl.d_start.capacity() || pixels > B.d_restarts.capacity()) return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the starts' buffers are gone (a resize)");
+    if ((out_starts_host && starts_capacity < entries) || (out_restarts_host && restarts_capacity < pixels))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: output smaller than the list or the rectangle");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    if (out_starts_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_starts_host, sl.d_start, entries * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_restarts_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_restarts_host, B.d_restarts, pixels, hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_beam_cache_start_counters(const blok_hip_ctx* ctx, uint64_t* out_from_starts, uint64_t* out_other_key) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (out_from_starts) *out_from_starts = ctx->beam_cache.start_hits;
+    if (out_other_key) *out_other_key = ctx->beam_cache.start_other_key;
     return BLOK_OK;
 }
 

@@ -168,16 +168,21 @@ struct blok_hip_ctx {
             // the view's packed list and its group table (trace_kernels.h: the packed walk), built behind the count launch on its stream and
             // adopted once `list_done` has been seen complete, so no reader ever waits; rebuilt only behind a refill, under the rule above
             blok::DeviceArray<uint32_t> d_list, d_table;
+            blok::DeviceArray<float> d_start;               // mode 4: every entry's own start parameter, in list order (written by the same build)
             uint32_t n_words = 0, n_groups = 0;             // the table's words as built (kPackGroups per area); its non-empty groups, as read from h_groups at adoption
         } slots[blok::kBeamCacheSlots];
         bool packed = true;                                 // ... with the packed walk (mode 3)
         blok::DeviceArray<uint8_t> d_trips;                 // the count launch's trips, a byte per pixel of the frame: one build at a time reads it
+        blok::DeviceArray<float> d_ray_start;               // mode 4: ... and every ray's restart parameter, a float per pixel; the policy's own_starts is the mode
+        blok::DeviceArray<uint8_t> d_restarts;              // ... and the trips of the walk restarted there, a byte per pixel: what a mode-4 build sorts by
         blok::DeviceArray<uint32_t> d_words;                // ... its table before the sort (kPackGroups words per area)
         blok::DeviceBytes d_sort_temp; size_t sort_temp_bytes = 0;
         blok::PinnedArray<uint32_t> h_groups;               // pinned, one word per slot: the table's length, written by the device before list_done
         blok::Event list_done;                              // behind the build in flight (policy.building)
         size_t list_capacity = 0, words_capacity = 0;       // entries per list; words per table
         uint64_t list_builds = 0;                           // blok_hip_beam_cache_list_builds
+        uint64_t start_hits = 0, start_other_key = 0;       // blok_hip_beam_cache_start_counters: packed hits that walked from the starts; ... that found another start key
+        int last_starts = 0;                                // the latest rectangle launch: 0 no starts, 1 it walked from them (or counted them), 2 it found another start key
         int last_list = 0;                                  // the latest rectangle launch: 0 no list, 1 it counted and issued the build, 2 it walked packed
         uint32_t last_w = 0, last_h = 0;                    // ... and its rectangle (blok_hip_beam_cache_download_list)
         size_t capacity = 0;                                // floats per buffer

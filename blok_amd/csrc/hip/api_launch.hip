@@ -403,7 +403,9 @@ int beam_list_buffers(blok_hip_ctx* ctx) {
     if (!B.packed) return BLOK_OK;
     const size_t areas = static_cast<size_t>((ctx->width + blok::kPackArea - 1u) / blok::kPackArea) * ((ctx->height + blok::kPackArea - 1u) / blok::kPackArea);
     const size_t entries = areas * blok::kPackStretch, words = areas * blok::kPackGroups, pixels = static_cast<size_t>(ctx->width) * ctx->height;
-    if (B.list_capacity >= entries && B.words_capacity >= words && B.d_trips.capacity() >= pixels) return BLOK_OK;
+    const bool own = B.policy.own_starts;
+    if (B.list_capacity >= entries && B.words_capacity >= words && B.d_trips.capacity() >= pixels &&
+        (!own || (B.d_ray_start.capacity() >= pixels && B.d_restarts.capacity() >= pixels && B.slots[0].d_start.capacity() >= entries))) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     B.list_capacity = 0; B.words_capacity = 0;
     blok::beam_cache_clear(B.policy);
@@ -412,9 +414,11 @@ int beam_list_buffers(blok_hip_ctx* ctx) {
     for (auto& sl : B.slots) {
         BLOK_HIP_TRY(ctx, sl.d_list.reserve(entries, waited));
         BLOK_HIP_TRY(ctx, sl.d_table.reserve(words, waited));
+        if (own) BLOK_HIP_TRY(ctx, sl.d_start.reserve(entries, waited));
         sl.n_groups = 0;
     }
     BLOK_HIP_TRY(ctx, B.d_trips.reserve(pixels, waited));
+    if (own) { BLOK_HIP_TRY(ctx, B.d_ray_start.reserve(pixels, waited)); BLOK_HIP_TRY(ctx, B.d_restarts.reserve(pixels, waited)); }
     BLOK_HIP_TRY(ctx, B.d_words.reserve(words, waited));
     B.sort_temp_bytes = blok::pack_table_temp_bytes(static_cast<uint32_t>(words));
     BLOK_HIP_TRY(ctx, B.d_sort_temp.reserve(B.sort_temp_bytes ? B.sort_temp_bytes : 16, waited));
@@ -461,7 +465,7 @@ static int wait_for_producer(blok_hip_ctx* ctx, blok_hip_ctx::BeamCache::Produce
 // Before a rectangle launch of a static form: does it search, search into a slot, or walk from a slot — and then from the slot's finer
 // bounds, or with their searches behind it?  Points args.beam at the slot's beam bounds and deals with whoever else uses it.
 static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan, blok::BeamRefinePlan* fine,
-                                    blok::BeamListPlan* listed) {
+                                    blok::BeamListPlan* listed, blok::BeamStartsPlan* starts) {
     auto& B = ctx->beam_cache;
     *plan = blok::plan_beam_cache(B.policy, beam_key(ctx, mode, args));
     *fine = blok::plan_beam_refine(B.policy, *plan, B.refine && blok::beam_refine_applies(args) && blok::beam_refine_tiles(args) <= B.capacity);
@@ -471,6 +475,11 @@ static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok:
     *listed = blok::plan_beam_list(B.policy, *plan, *fine, B.packed && blok::pack_applies(args) && static_cast<size_t>(blok::pack_areas(args)) * blok::kPackStretch <= B.list_capacity &&
                                    static_cast<size_t>(args.w) * args.h <= B.d_trips.capacity(), build_finished);
     if (listed->adopted >= 0) { auto& got = B.slots[listed->adopted]; got.n_groups = std::min(B.h_groups[listed->adopted], got.n_words); }
+    blok::BeamStartKey start_key;
+    static_assert(sizeof(args.jitter_clip) == sizeof(start_key.jitter_clip), "beam_cache.h: BeamStartKey::jitter_clip is TraceArgs::jitter_clip, bit for bit");
+    std::memcpy(start_key.jitter_clip, args.jitter_clip, sizeof(start_key.jitter_clip));
+    std::memcpy(&start_key.tmin, &args.tmin, sizeof(uint32_t)); std::memcpy(&start_key.tmax, &args.tmax, sizeof(uint32_t));
+    *starts = blok::plan_beam_starts(B.policy, *plan, *listed, start_key);
     if (plan->action == blok::BeamAction::Search) return BLOK_OK;
     auto& sl = B.slots[plan->slot];
     if (plan->action == blok::BeamAction::Hit) {
@@ -588,8 +597,9 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     blok::BeamCachePlan cached{blok::BeamAction::Search, -1};
     blok::BeamRefinePlan finer{false, false};
     blok::BeamListPlan listed{false, false, -1};
+    blok::BeamStartsPlan starts{false, blok::BeamStarts::None};
     if (ctx->beam_cache.enabled && rect && !frames && !capturing && static_form && ctx->launch_form == blok::kFormAuto && n_beams && n_beams <= ctx->beam_cache.capacity) {
-        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached, &finer, &listed);
+        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached, &finer, &listed, &starts);
         if (rc != BLOK_OK) {
             if (finer.refine_now) blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, false);
             if (listed.count_now) blok::beam_list_commit(ctx->beam_cache.policy, cached.slot, false);
@@ -603,6 +613,9 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     ctx->beam_cache.last_fine = finer.use_fine ? 2 : finer.refine_now ? 1 : 0;
     ctx->beam_cache.last_n_fine = ctx->beam_cache.last_fine ? blok::beam_refine_tiles(args) : 0u;
     ctx->beam_cache.last_list = listed.use_list ? 2 : listed.count_now ? 1 : 0;
+    ctx->beam_cache.last_starts = starts.use == blok::BeamStarts::OtherKey ? 2 : (starts.use == blok::BeamStarts::Use || starts.count_own) ? 1 : 0;
+    if (starts.use == blok::BeamStarts::Use) ctx->beam_cache.start_hits += 1u;
+    if (starts.use == blok::BeamStarts::OtherKey) ctx->beam_cache.start_other_key += 1u;
     ctx->beam_cache.last_w = args.w; ctx->beam_cache.last_h = args.h;
     if (cached.action == blok::BeamAction::Hit && (listed.use_list || listed.count_now)) {
         // The packed walk, or the launch that measures for it.  Neither uses the view's order or its live prefix (the table's order stands in
@@ -614,8 +627,16 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
         fill.order = nullptr; fill.rank_of = nullptr; fill.launched = 0u; fill.order_sx = fill.order_sy = 0u; fill.n_strip = 0u; fill.fallback_tiles = nullptr;
         fill.miss_in_walk = 0u;
         blok::launch_beam_fill(mode, fill, n_beams, sl.d_fine, stream);
-        if (listed.use_list) blok::launch_packed_walk(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, stream);
-        else {
+        if (listed.use_list && starts.use == blok::BeamStarts::Use) blok::launch_packed_walk_own(fill, sl.d_start, sl.d_list, sl.d_table, sl.n_groups, stream);
+        else if (listed.use_list) blok::launch_packed_walk(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, stream);
+        else if (starts.count_own) {
+            // mode 4: the count launch also leaves every ray's own start and restarted trips; the build sorts by those and writes the starts in list order
+            blok::TraceArgs walk = fill;
+            walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
+            blok::launch_trace_count_own(walk, blocks, B.d_trips, B.d_ray_start, B.d_restarts, stream);
+            sl.n_words = blok::pack_areas(args) * blok::kPackGroups; sl.n_groups = 0u;
+            blok::launch_pack_build_own(fill, sl.d_fine, B.d_restarts, B.d_ray_start, sl.d_list, B.d_words, sl.d_start, stream);
+        } else {
             blok::TraceArgs walk = fill;
             walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
             blok::launch_trace_count(walk, blocks, B.d_trips, stream);

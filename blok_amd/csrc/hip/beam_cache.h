@@ -84,8 +84,26 @@ enum class BeamList : uint8_t {
 // The default N, decided as K was: what the count launch and the build cost once over what a packed frame gains, rounded up to a power of
 // two.  Measured at 4K over 1024^3 (profiles/packed_walk_ab.txt): the count launch takes 70 us (pose A) and 25 us (pose B) longer than the
 // view's usual walk, the build 39 to 43 us and the table's sort about 54 us; a frame in flight gains 13 us and 7 to 9 us: ratios 12 and 14 to 17 -> 16.
+// With the starts (below) the same rule gives 4 (profiles/own_start_ab.txt: about 180 and 140 us once, 54 and 60 us gained per frame in flight);
+// left at 16 until it is changed together with K, with the benchmark's short per-pose windows measured.
 constexpr uint32_t kBeamListAfter = 16;
 struct BeamListPlan { bool count_now, use_list; int adopted; };      // adopted: the slot whose finished build this launch adopted (read its size now), or -1
+
+// A packed list's starts: one start parameter per listed RAY, left by the count launch — the ray parameter at which that very ray entered
+// the cell its answer lies in (trace_kernels.h: launch_trace_count_own) — and written beside the list by its build.  Unlike the searched
+// bounds, which hold for every ray through a tile, a ray's own start holds for THAT ray and interval: the starts carry a key of their own,
+// the inputs of primary_ray and of the walk's interval that the beam key leaves out, compared bit for bit.  A packed hit under another
+// start key walks the same list from the finer bounds, as a list without starts does; the starts stay, and serve again when the counted
+// values return.  They go wherever the list goes (beam_list_drop, a build that was not issued).
+struct BeamStartKey { uint32_t jitter_clip[2], tmin, tmax; };
+static_assert(sizeof(BeamStartKey) == 4 * sizeof(uint32_t), "BeamStartKey is compared with memcmp: no padding");
+inline bool beam_start_key_equal(const BeamStartKey& a, const BeamStartKey& b) { return memcmp(&a, &b, sizeof(BeamStartKey)) == 0; }
+enum class BeamStarts : int {
+    None = 0,                                  // the launch walks no list, or a list without starts
+    Use = 1,                                   // a packed hit of the counted rays: it walks from the starts
+    OtherKey = 2,                              // a packed hit under another start key: from the finer bounds, this launch
+};
+struct BeamStartsPlan { bool count_own; BeamStarts use; };          // count_own: the launch told "count now" also leaves the starts
 
 struct BeamCachePolicy {
     BeamKey key[kBeamCacheSlots];
@@ -100,6 +118,9 @@ struct BeamCachePolicy {
     BeamList list[kBeamCacheSlots];            // reset with `refine`: a slot keeps its list exactly as long as it keeps its finer bounds
     uint32_t fine_hits[kBeamCacheSlots];       // hits that walked from the finer bounds since they were made
     uint32_t list_after = kBeamListAfter;      // N (a debug setter); kept by beam_cache_clear
+    bool own_starts = true;                    // the lists carry starts (a mode: kept by beam_cache_clear)
+    bool starts[kBeamCacheSlots];              // the slot's list (built, or being counted and built) carries starts, counted under start_key
+    BeamStartKey start_key[kBeamCacheSlots];
     int building = -1;                         // the slot the build in flight writes (-1: none is in flight)
     bool building_stale = false;               // ... and that slot has been refilled or cleared since: the build finishes into a list nobody adopts
 };
@@ -107,7 +128,7 @@ struct BeamCachePolicy {
 // The slot's finer bounds are gone (a refill, an eviction, a clear): its list goes with them.  A build still in flight for it stays "in
 // flight" — it is writing the slot's buffers, and the context's — until a launch sees it finished.
 inline void beam_list_drop(BeamCachePolicy& s, int slot) {
-    s.list[slot] = BeamList::None; s.fine_hits[slot] = 0u;
+    s.list[slot] = BeamList::None; s.fine_hits[slot] = 0u; s.starts[slot] = false;
     if (s.building == slot) s.building_stale = true;
 }
 
@@ -186,13 +207,26 @@ inline BeamListPlan plan_beam_list(BeamCachePolicy& s, const BeamCachePlan& p, c
     return out;
 }
 
+// Behind plan_beam_list, for the same launch, k its start key.  The launch told "count now" is told whether to leave the starts as well (the
+// mode), and they are its key's from then on; a launch told "use the list" is told whether the list's starts are its own rays'.
+inline BeamStartsPlan plan_beam_starts(BeamCachePolicy& s, const BeamCachePlan& p, const BeamListPlan& l, const BeamStartKey& k) {
+    if (p.action != BeamAction::Hit || p.slot < 0 || p.slot >= kBeamCacheSlots) return {false, BeamStarts::None};
+    if (l.count_now) {
+        s.starts[p.slot] = s.own_starts;
+        if (s.own_starts) s.start_key[p.slot] = k;
+        return {s.own_starts, BeamStarts::None};
+    }
+    if (!l.use_list || !s.starts[p.slot]) return {false, BeamStarts::None};
+    return {false, beam_start_key_equal(s.start_key[p.slot], k) ? BeamStarts::Use : BeamStarts::OtherKey};
+}
+
 // The launch that was told "count now" has issued its build and the event behind it (issued), or could not: the slot stays without a list
 // and is asked again N hits later.
 inline void beam_list_commit(BeamCachePolicy& s, int slot, bool issued) {
     if (slot < 0 || slot >= kBeamCacheSlots || s.list[slot] != BeamList::Now) return;
     s.list[slot] = issued ? BeamList::Building : BeamList::None;
     if (issued) { s.building = slot; s.building_stale = false; }
-    else s.fine_hits[slot] = 0u;
+    else { s.fine_hits[slot] = 0u; s.starts[slot] = false; }
 }
 
 }  // namespace blok

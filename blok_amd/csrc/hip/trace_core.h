@@ -251,9 +251,13 @@ BLOK_DEV void walk_enter(const TraceArgs& A, const WalkRay& R, float tmin, float
 // a walk of the same ray from the root with tmin = that tCur reports what this one would have (every voxel before it has an empty clipped
 // interval, every one after it is entered at or after tCur: the argument of the beam pre-pass).  path_core.h: the bounce rounds' tail pool.
 // kCount: the trips this lane made go to *n_trips (0 for a lane that had nothing to walk): what the packed list of a view at rest is sorted by.
-template <bool kCapped = false, bool kCount = false>
+// kOwn: a lane that made a trip also leaves where the same ray may restart (the argument above): *own_start = the tCur at the top of its last
+// trip — a reported voxel's t, else the entry of the last cell it stood in, which is inside the world and the interval — and *own_trips = the
+// trips of the walk from the root started there, levels - that cell's level (its descents, then the trip that reports or leaves).  A lane
+// without a trip leaves both untouched.
+template <bool kCapped = false, bool kCount = false, bool kOwn = false>
 BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, WalkState& s, uint4* stk, [[maybe_unused]] const uint32_t cap = 0u,
-                        [[maybe_unused]] uint32_t* n_trips = nullptr) {
+                        [[maybe_unused]] uint32_t* n_trips = nullptr, [[maybe_unused]] float* own_start = nullptr, [[maybe_unused]] uint32_t* own_trips = nullptr) {
     // Invariant: tCur starts at max(world entry, tmin) and never decreases — a cell's far planes are never
     // before the plane through which it was entered (T is monotone along each axis and the start cell of a
     // node only counts planes with T <= tCur as crossed) — so max(tCur, tmin) == tCur throughout and the
@@ -273,6 +277,8 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
     // lane whose walk ends without a report leaves nothing that is read).
     bool go = s.walking;
     [[maybe_unused]] uint32_t trips = 0u;
+    [[maybe_unused]] float t_last = tCur;
+    [[maybe_unused]] uint32_t shift_last = top_shift;
     while (kCapped ? (go && trips < cap) : go) {
         if constexpr (kCapped || kCount) ++trips;
         BLOK_STAT(0, shift >> 1);
@@ -291,6 +297,7 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
             enter_axis(R.ay, fy, size, s2, tCur);
             enter_axis(R.az, fz, size, s2, tCur);
         } else {
+            if constexpr (kOwn) { t_last = tCur; shift_last = shift; }      // (a walk's last trip is never a descent)
             const float tExit = fminf(fminf(tFx, tFy), tFz);
             // a filled voxel: reported iff its clipped interval is non-empty (intersect.rint:189-193)
             found = occupied && tCur < fminf(tExit, tmax);
@@ -331,6 +338,7 @@ BLOK_DEV void walk_loop(const TraceArgs& A, const WalkRay& R, const float tmax, 
     s.fx = fx; s.fy = fy; s.fz = fz; s.tCur = tCur; s.bit = bit; s.node = node; s.found = found;
     if constexpr (kCapped) s.walking = go; else s.walking = false;
     if constexpr (kCount) *n_trips = trips;
+    if constexpr (kOwn) if (shift_last != top_shift) { *own_start = t_last; *own_trips = (top_shift - shift_last) >> 1; }
 }
 
 // The reported voxel of a finished walk: intersect.rint:136-141, hit.rchit:58-74.  r: the ray itself (origin, direction).
@@ -583,9 +591,11 @@ BLOK_DEV HitInfo walk(const TraceArgs& A, const RayIn& r, uint4* stk) {
 }
 
 // As walk(), the wave's rays entered together (walk_enter_wave): for the primary rays of a wave tile.  Every active lane of the wave must call it.
-// kCount: the loop's trips to *n_trips (walk_loop).
-template <bool kCount = false>
-BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk, [[maybe_unused]] uint32_t* n_trips = nullptr) {
+// kCount: the loop's trips to *n_trips (walk_loop).  kOwn (with kCount): the lane's restart parameter and restarted trips (walk_loop) to
+// *own_start, *own_trips; a lane that made no trip leaves the start it was given, r.tmin, and 0.
+template <bool kCount = false, bool kOwn = false>
+BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk, [[maybe_unused]] uint32_t* n_trips = nullptr, [[maybe_unused]] float* own_start = nullptr,
+                           [[maybe_unused]] uint32_t* own_trips = nullptr) {
 #ifdef BLOK_TRACE_HOST_HARNESS
     return walk(A, r, stk);
 #else
@@ -599,7 +609,8 @@ BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk, [[may
         // the count is the walk's FROM THE ROOT: the descents the wave made together (walk_enter_wave leaves the lane at level s.lvl, where the
         // walk from the root arrives after levels - 1 - s.lvl trips; walk_enter leaves it at levels - 1) are trips of it like any other
         const uint32_t shared = A.levels - 1u - s.lvl;
-        walk_loop<false, true>(A, R, r.tmax, s, stk, 0u, n_trips);
+        if constexpr (kOwn) { *own_start = r.tmin; *own_trips = 0u; walk_loop<false, true, true>(A, R, r.tmax, s, stk, 0u, n_trips, own_start, own_trips); }
+        else walk_loop<false, true>(A, R, r.tmax, s, stk, 0u, n_trips);
         *n_trips += shared;
     } else walk_loop(A, R, r.tmax, s, stk);
     if (s.found) out = walk_hit(A, r, R, s);
@@ -608,13 +619,18 @@ BLOK_DEV HitInfo walk_wave(const TraceArgs& A, const RayIn& r, uint4* stk, [[may
 }
 
 // Walks one ray and writes its 16-byte record and/or RGBA8 pixel.  kWave: through walk_wave (the coherent primary rays of a wave tile).
-// kCount (with kWave): the walk's trips, saturated at 255, go to *trips_out.
-template <bool kWave = false, bool kCount = false>
-BLOK_DEV void trace_one(const TraceArgs& A, const RayIn& r, uint4* stk, const Sink& dst, [[maybe_unused]] uint8_t* trips_out = nullptr) {
-    [[maybe_unused]] uint32_t n_trips = 0u;
+// kCount (with kWave): the walk's trips, saturated at 255, go to *trips_out.  kOwn (with kCount): the ray's restart parameter and its restarted
+// trips (walk_wave; at most `levels`) go to *start_out and *restart_out.
+template <bool kWave = false, bool kCount = false, bool kOwn = false>
+BLOK_DEV void trace_one(const TraceArgs& A, const RayIn& r, uint4* stk, const Sink& dst, [[maybe_unused]] uint8_t* trips_out = nullptr, [[maybe_unused]] float* start_out = nullptr,
+                        [[maybe_unused]] uint8_t* restart_out = nullptr) {
+    [[maybe_unused]] uint32_t n_trips = 0u, own_trips = 0u;
+    [[maybe_unused]] float own_start = 0.0f;
     static_assert(kWave || !kCount, "trips are counted for the primary rays of a wave tile");
-    const HitInfo h = kCount ? walk_wave<kCount>(A, r, stk, &n_trips) : (kWave ? walk_wave(A, r, stk) : walk(A, r, stk));
+    static_assert(kCount || !kOwn, "the restart parameters are left by the count launch");
+    const HitInfo h = kOwn ? walk_wave<kCount, kOwn>(A, r, stk, &n_trips, &own_start, &own_trips) : kCount ? walk_wave<kCount>(A, r, stk, &n_trips) : (kWave ? walk_wave(A, r, stk) : walk(A, r, stk));
     if constexpr (kCount) *trips_out = static_cast<uint8_t>(n_trips < 255u ? n_trips : 255u);
+    if constexpr (kOwn) { *start_out = own_start; *restart_out = static_cast<uint8_t>(own_trips); }
     if (!h.found) { write_miss(dst); return; }
     uint4 rec;
     rec.x = __float_as_uint(h.t);

@@ -317,6 +317,16 @@ bool pack_applies(const TraceArgs& args);                             // the geo
 void launch_trace_count(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, hipStream_t stream);      // Rect; args as for launch_trace
 void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* trips, uint32_t* list, uint32_t* words, hipStream_t stream);
 void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
+// The same with one start parameter per listed RAY (beam_cache.h: BeamStartKey).  The count launch leaves, beside a ray's trips, the ray
+// parameter at the top of its last trip — a hit's t, bit for bit; a miss's entry of the last cell it stood in — and the trips of the walk
+// from the root started there (`levels` for a hit, levels - that cell's level for a miss, 0 and the start it had for a ray that made no
+// trip), per pixel of the rectangle.  The build sorts by those restarted trips, and a second kernel writes every entry's start beside it, in list order
+// (slot_start: kPackStretch floats per area, like the list); the walk reads entry and start and never the finer bounds.  A walk of the
+// same ray from the root from that parameter reports what the counted walk did (trace_core.h: walk_loop), so the frame's bytes are the same
+// — for the counted rays only: another jitter or interval walks the same list with launch_packed_walk.
+void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, hipStream_t stream);
+void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream);
+void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

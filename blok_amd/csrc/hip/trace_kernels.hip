@@ -189,9 +189,10 @@ __device__ __forceinline__ bool list_await(unsigned long long* slot, unsigned lo
 // Workgroup `block` of a launch of `grid` workgroups (the kernels below differ in where the arguments come from).  kListed: the block
 // comes from the frame's live list together with its start parameter (list launches): no order, no beam lookup, no cost.
 // kCount (trace_count_kernel): every lane that walks also leaves its trips in trips[its pixel of the rectangle].
-template <RayMode MODE, bool kListed = false, bool kCount = false>
+// kOwn (trace_count_own_kernel): ... and its restart parameter and restarted trips (trace_core.h: walk_loop) in starts[], restarts[] of the same pixel.
+template <RayMode MODE, bool kListed = false, bool kCount = false, bool kOwn = false>
 __device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t block, const uint32_t grid, uint4* lds_stack, const float listed_t0 = 0.0f,
-                                            [[maybe_unused]] uint8_t* trips = nullptr) {
+                                            [[maybe_unused]] uint8_t* trips = nullptr, [[maybe_unused]] float* starts = nullptr, [[maybe_unused]] uint8_t* restarts = nullptr) {
     const uint32_t tid = threadIdx.x;
     uint4* stk = lds_stack + tid;
 
@@ -307,7 +308,8 @@ __device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t b
 #ifndef BLOK_WAVE_START
 #define BLOK_WAVE_START 1
 #endif
-        if constexpr (kCount) trace_one<true, true>(A, r, stk, sink, trips + out_index);
+        if constexpr (kOwn) trace_one<true, true, true>(A, r, stk, sink, trips + out_index, starts + out_index, restarts + out_index);
+        else if constexpr (kCount) trace_one<true, true>(A, r, stk, sink, trips + out_index);
         else trace_one<BLOK_WAVE_START != 0>(A, r, stk, sink);
         if (cost_slot && tid == 0) *cost_slot = max(static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - clock0), 256u);     // it walked: any key >= 256 clocks counts as live in the next order
     }
@@ -323,6 +325,12 @@ __global__ __launch_bounds__(kBlock) void trace_kernel(const TraceArgs A) {
 __global__ __launch_bounds__(kBlock) void trace_count_kernel(const TraceArgs A, uint8_t* trips) {
     extern __shared__ uint4 lds_stack[];
     trace_block<RayMode::Rect, false, true>(A, blockIdx.x, gridDim.x, lds_stack, 0.0f, trips);
+}
+
+// ... and leaves every walked ray's own restart parameter and restarted trips beside its trips (beam_cache.h: the starts of a packed list).
+__global__ __launch_bounds__(kBlock) void trace_count_own_kernel(const TraceArgs A, uint8_t* trips, float* starts, uint8_t* restarts) {
+    extern __shared__ uint4 lds_stack[];
+    trace_block<RayMode::Rect, false, true, true>(A, blockIdx.x, gridDim.x, lds_stack, 0.0f, trips, starts, restarts);
 }
 
 // The arguments of frame f of a several-frame launch: its camera, its slice of the outputs and of the beam buffer.
@@ -606,6 +614,17 @@ __global__ __launch_bounds__(kPackThreads) void pack_build_kernel(const uint8_t*
     if (p < kPackGroups && p * 64u >= n) words[blockIdx.x * kPackGroups + p] = 0u;
 }
 
+// Behind a build over the rays' RESTARTED trips (the same kernel: at most `levels`, so nearly all keys are equal, the stable order is the
+// pixel order and a group is mostly whole wave tiles): every entry's restart parameter, from starts[its pixel] to slot_start[its place in
+// the list].  A thread per entry of every stretch; an entry beyond a stretch's padding is whatever an earlier build left, hence the bounds.
+__global__ __launch_bounds__(256) void pack_starts_kernel(const uint32_t* list, const float* starts, const uint32_t w, const uint32_t h, const uint32_t n_entries, float* slot_start) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_entries) return;
+    const uint32_t entry = list[i], rx = entry & 0xFFFFu, ry = entry >> 16;
+    if (entry == kPackPad || rx >= w || ry >= h) return;
+    slot_start[i] = starts[static_cast<size_t>(ry) * w + rx];
+}
+
 // One wave per group of the list, heaviest first.  Nothing here is collective before a padding lane has left.
 __global__ __launch_bounds__(kBlock) void packed_walk_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table) {
     static_assert(kBlock == 64, "one wave per group");
@@ -616,6 +635,25 @@ __global__ __launch_bounds__(kBlock) void packed_walk_kernel(const TraceArgs A, 
     const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
     if (entry == kPackPad || rx >= A.w || ry >= A.h) return;          // (the build lists pixels of the rectangle only)
     const float t0 = fine[(ry / kWaveH) * ((A.w + kWaveW - 1u) / kWaveW) + rx / kWaveW];
+    const size_t at = static_cast<size_t>(ry) * A.w + rx;
+    RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+    r.tmin = fmaxf(r.tmin, t0);
+    trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+}
+
+// The same from every listed ray's OWN start (slot_start, in list order: an entry and its start are two coalesced loads): the parameter at
+// which the counted walk of this very ray entered the cell its answer lies in — never below its wave tile's bound, so that is not read.
+// The walk goes from the root to that cell and reports or leaves: `levels` trips for a hit.  Only for a launch whose rays ARE the counted
+// ones (beam_cache.h: BeamStartKey).
+__global__ __launch_bounds__(kBlock) void packed_walk_own_kernel(const TraceArgs A, const float* slot_start, const uint32_t* list, const uint32_t* table) {
+    static_assert(kBlock == 64, "one wave per group");
+    extern __shared__ uint4 lds_stack[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
+    const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+    const float t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
+    const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
+    if (entry == kPackPad || rx >= A.w || ry >= A.h) return;
     const size_t at = static_cast<size_t>(ry) * A.w + rx;
     RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
     r.tmin = fmaxf(r.tmin, t0);
@@ -1357,6 +1395,23 @@ void launch_trace_count(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips
 void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* trips, uint32_t* list, uint32_t* words, hipStream_t stream) {
     if (!pack_applies(args) || !fine || !trips || !list || !words) return;
     hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, trips, fine, args.w, args.h, list, words);
+}
+
+void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, hipStream_t stream) {
+    if (n_blocks == 0 || !trips || !starts || !restarts) return;
+    hipLaunchKernelGGL(trace_count_own_kernel, dim3(n_blocks), dim3(kBlock), frame_lds_bytes(args), stream, args, trips, starts, restarts);
+}
+
+void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream) {
+    if (!pack_applies(args) || !fine || !restarts || !starts || !list || !words || !slot_start) return;
+    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, restarts, fine, args.w, args.h, list, words);
+    const uint32_t n_entries = pack_areas(args) * kPackStretch;
+    hipLaunchKernelGGL(pack_starts_kernel, dim3((n_entries + 255u) / 256u), dim3(256), 0, stream, list, starts, args.w, args.h, n_entries, slot_start);
+}
+
+void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream) {
+    if (n_groups == 0 || !pack_applies(args) || !slot_start || !list || !table) return;
+    hipLaunchKernelGGL(packed_walk_own_kernel, dim3(n_groups), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, list, table);
 }
 
 void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream) {

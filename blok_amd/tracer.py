@@ -648,10 +648,11 @@ class HipTracer:
         self._check(self._lib.blok_hip_set_miss_writer(self._ctx, 1 if in_walk else 0))
 
     def set_beam_cache(self, mode):
-        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 3 or True (default) = with, from the view's K-th
-        hit on, a finer bound per wave tile, and then its rays regrouped by measured length (the packed walk); 2 = without the packed walk;
-        1 = the beam tiles' bounds alone; 0 or False = every launch searches.  Never changes a result."""
-        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (3 if mode else 0) if isinstance(mode, bool) else int(mode)))
+        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 4 or True (default) = with, from the view's K-th
+        hit on, a finer bound per wave tile, then its rays packed into a list, each restarted where its own counted walk ended; 3 = the list
+        sorted by measured length and walked from the finer bounds; 2 = without the packed walk; 1 = the beam tiles' bounds alone; 0 or
+        False = every launch searches.  Never changes a result."""
+        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (4 if mode else 0) if isinstance(mode, bool) else int(mode)))
 
     def set_beam_refine_after(self, hits: int):
         """K: the hit of a kept view behind whose walk its finer bounds are searched, once (0 = the default; blok_hip_debug.h)."""
@@ -693,6 +694,29 @@ class HipTracer:
         self._check(self._lib.blok_hip_beam_cache_download_list(self._ctx, C.byref(state), C.byref(areas), C.byref(groups), _ffi.ptr(entries), entries.size,
                                                                  _ffi.ptr(table), table.size, _ffi.ptr(trips), trips.size))
         return int(state.value), int(groups.value), entries, table, trips
+
+    def beam_cache_starts_state(self) -> int:
+        """What the latest rectangle launch had to do with a list's starts: 0 nothing, 1 it counted them or walked from them, 2 it walked
+        packed under another start key.  Waits for nothing."""
+        state = C.c_int(0)
+        self._check(self._lib.blok_hip_beam_cache_download_starts(self._ctx, C.byref(state), None, 0, None, 0))
+        return int(state.value)
+
+    def beam_cache_starts(self, w: int, h: int):
+        """(starts, restarts) of the latest rectangle launch's packed list (blok_hip_debug.h: blok_hip_beam_cache_download_starts), for its
+        rectangle of w x h pixels: starts (areas, area^2) float32 in list order, restarts (h, w) uint8."""
+        state, areas = C.c_int(0), C.c_uint32(0)
+        self._check(self._lib.blok_hip_beam_cache_download_list(self._ctx, C.byref(state), C.byref(areas), None, None, 0, None, 0, None, 0))
+        starts = np.zeros((int(areas.value), self.pack_area() ** 2), dtype=np.float32)
+        restarts = np.zeros((h, w), dtype=np.uint8)
+        self._check(self._lib.blok_hip_beam_cache_download_starts(self._ctx, None, _ffi.ptr(starts), starts.size, _ffi.ptr(restarts), restarts.size))
+        return starts, restarts
+
+    def beam_cache_start_counters(self):
+        """(packed launches that walked from the starts, packed launches that found another start key)."""
+        used, other = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_beam_cache_start_counters(self._ctx, C.byref(used), C.byref(other)))
+        return int(used.value), int(other.value)
 
     def beam_cache_refines(self) -> int:
         """Diagnostic: launches so far that issued a view's finer searches behind their walk."""

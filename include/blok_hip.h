@@ -586,7 +586,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.17: a power-of-two scale on instanced models (blok_hip_model_set_scale): a coarse level traced at its true size beside the world.
  * 1.18: models resampled into the resident volume through an affine map (blok_hip_volume_stamp_affine): any rotation, scale, mirror, shear.
  * 1.19: neighbour-count rules stepped over the resident volume (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life.
- * 1.20: procedural terrain reduced to coarse levels without a volume (blok_hip_terrain_reduce): the far field built at any time. */
+ * 1.20: procedural terrain reduced to coarse levels without a volume (blok_hip_terrain_reduce): the far field built at any time.
+ * 1.21: a view at rest restarts every listed ray where its own counted walk ended (blok_hip_debug.h: blok_hip_set_beam_cache mode 4, the default). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

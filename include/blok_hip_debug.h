@@ -140,7 +140,12 @@ int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk);
  * (blok_hip_set_beam_list_after) also counts every ray's trips and issues, behind its walk, the build of a list — per 32 x 32 pixels,
  * the pixels by descending count, 64 to a group — and of a table of the groups, heaviest first; the first later launch that finds the build
  * finished walks one group per wave from then on, with neither the view's order nor its live prefix (rectangles up to 65 534 pixels a side;
- * allocates the lists' buffers, about 17 bytes per pixel of the frame, and waits for the device).  In every case the slots are emptied.
+ * allocates the lists' buffers, about 17 bytes per pixel of the frame, and waits for the device); 4 (default since ABI 1.21) = as 3, and
+ * the count launch also leaves, for every ray, the ray parameter at which it entered the cell its answer lies in (a hit's t; the entry of a
+ * miss's last cell inside the world) and the trips of the walk from the root started there (at most the tree's levels); the list is sorted by
+ * those, which leaves it nearly in pixel order, and carries every entry's start beside it; a packed launch whose jitter, tmin and tmax are the
+ * count launch's, bit for bit, walks every listed ray from its own start — from the root to that cell — and any other packed launch of the
+ * view walks the same list from the finer bounds as under 3 (another 21 bytes per pixel of the frame).  In every case the slots are emptied.
  * blok_hip_last_launch_kind goes on reporting the form the launch policy chose for the
  * device's state, also for a launch that walked from kept bounds (a plain trace launch).  Never changes a result. */
 int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode);
@@ -161,6 +166,15 @@ int blok_hip_beam_cache_list_builds(const blok_hip_ctx* ctx, uint64_t* out_build
  * Waits for the device; launches nothing and changes nothing.  Any pointer may be null. */
 int blok_hip_beam_cache_download_list(blok_hip_ctx* ctx, int* out_state, uint32_t* out_n_areas, uint32_t* out_n_groups, uint32_t* out_list_host_or_null, size_t list_capacity,
                                       uint32_t* out_table_host_or_null, size_t table_capacity, uint8_t* out_trips_host_or_null, size_t trips_capacity);
+/* Mode 4's read-back, for the slot blok_hip_beam_cache_download_list reads: *out_state = 0 the latest rectangle launch had nothing to do with
+ * starts, 1 it counted them or walked from them, 2 it walked packed under another start key (from the finer bounds); and into the buffers
+ * that are given, for a slot whose list carries starts: every entry's start parameter in list order, 1 024 floats per area (defined where the
+ * list holds an entry that is not padding), and the restarted trips of the context's latest count launch, one byte per pixel of the
+ * rectangle, defined for the listed pixels.  Waits for the device; launches nothing and changes nothing.  Any pointer may be null. */
+int blok_hip_beam_cache_download_starts(blok_hip_ctx* ctx, int* out_state, float* out_starts_host_or_null, size_t starts_capacity, uint8_t* out_restarts_host_or_null,
+                                        size_t restarts_capacity);
+/* Packed launches so far that walked from the starts, and that found another start key; either pointer may be null. */
+int blok_hip_beam_cache_start_counters(const blok_hip_ctx* ctx, uint64_t* out_from_starts, uint64_t* out_other_key);
 /* Launches so far that walked from kept bounds (hits) and that searched into a slot (fills); either pointer may be null. */
 int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills);
 /* ... and that issued a view's finer searches behind their walk (at most one per fill; such a launch counts as a hit too). */
