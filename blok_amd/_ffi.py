@@ -43,6 +43,9 @@ RAY = np.dtype([("org", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", 
 # = blok_instance: a placed model (lattice offset, axis-aligned orientation), 32 bytes
 INSTANCE = np.dtype([("model", "<u4"), ("offset", "<i4", 3), ("axis", "u1", 3), ("flip", "u1"), ("reserved", "<u4", 3)])
 INSTANCE_NONE = 0xFFFFFFFF
+# blok_pose (blok_hip.h, "Posed models"): a model under any affine map, world -> local; ids of pixels a pose wins carry POSE_ID
+POSE = np.dtype([("model", "<u4"), ("m", "<f4", (3, 3)), ("pivot", "<f4", 3), ("local", "<f4", 3)])
+POSE_ID = 0x80000000
 # = blok_quad: one merged quad of a volume's surface, 32 bytes
 QUAD = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("reserved", "<u4")])
 QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
@@ -129,7 +132,7 @@ assert COMPONENT.itemsize == 40 and SWEEP_RESULT.itemsize == 16 and BRICK_RECORD
 assert DISTANCE_INFO.itemsize == 64 and FLOOD_INFO.itemsize == 64 and COLUMNS_INFO.itemsize == 64
 assert SCATTER_ENTRY.itemsize == 24 and SCATTER_PARAMS.itemsize == 64 and SCATTER_INFO.itemsize == 72
 assert SCROLL_BOX.itemsize == 24 and SCROLL_INFO.itemsize == 200 and SHAPE.itemsize == 64
-assert LOD_LEVEL.itemsize == 64 and LOD_INFO.itemsize == 360 and AFFINE.itemsize == 96
+assert LOD_LEVEL.itemsize == 64 and LOD_INFO.itemsize == 360 and AFFINE.itemsize == 96 and POSE.itemsize == 64
 assert AUTOMATON_RULE.itemsize == 32 and AUTOMATON_INFO.itemsize == 64
 
 
@@ -288,6 +291,9 @@ HOST_SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_affine_from_instance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_affine_from_matrix": (C.c_int, [C.POINTER(C.c_double), C.c_void_p]),
+    "blok_pose_from_instance": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+    "blok_pose_from_matrix": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.c_void_p]),
+    "blok_affine_from_pose": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]),
     "blok_affine_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -480,6 +486,11 @@ HIP_SYMBOLS = {
     "blok_hip_trace_primary_instanced": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3),
     "blok_hip_trace_rays_instanced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_hip_trace_rays_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blok_hip_check_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "blok_hip_trace_primary_posed_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4),
+    "blok_hip_trace_primary_posed": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3),
+    "blok_hip_trace_rays_posed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_hip_trace_rays_posed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_hip_trace_paths_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "blok_hip_trace_paths_instanced_ref_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.POINTER(C.c_float),
                                                                                                           C.POINTER(GBufferRef), C.c_void_p, C.c_void_p]),

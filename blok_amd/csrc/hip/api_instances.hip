@@ -1,5 +1,6 @@
 // Instanced voxel models (include/blok_hip.h, instance_core.h): the model store on the context and the instanced trace entries.
 #include "api_internal.h"
+#include "posed_core.h"
 
 #include <algorithm>
 #include <limits>
@@ -43,6 +44,24 @@ int check_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) {
         if (!blok::instance_usable(I, ctx->models.desc[I.model]))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "world box outside the int16 lattice of hit records");
         if (!blok::model_size_usable(ctx->models.desc[I.model], ctx->world_voxel_size))
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "the scaled model's voxel size (world voxel size * 2^scale) is above 256");
+    }
+    return BLOK_OK;
+}
+
+// The limits of a pose table (blok_hip.h, "Posed models"), naming the first pose that breaks one.
+int check_pose_table(blok_hip_ctx* ctx, const blok_pose* poses, uint32_t n) {
+    if (n && !poses) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
+    if (n >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
+    for (uint32_t i = 0; i < n; ++i) {
+        const blok_pose& S = poses[i];
+        const std::string at = "pose " + std::to_string(i) + ": ";
+        if (const int rule = blok::pose::floats_rule(S)) return set_error(ctx, BLOK_ERR_INVALID_ARG, at + blok::pose::rule_text(rule));
+        if (S.model >= ctx->models.desc.size() || !ctx->models.desc[S.model].nodes)
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "unknown model " + std::to_string(S.model));
+        if (!blok::pose_model_box_usable(ctx->models.desc[S.model]))
+            return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "the model's own voxel box lies outside the int16 lattice of hit records");
+        if (!blok::model_size_usable(ctx->models.desc[S.model], ctx->world_voxel_size))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "the scaled model's voxel size (world voxel size * 2^scale) is above 256");
     }
     return BLOK_OK;
@@ -358,6 +377,153 @@ int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (rc != BLOK_OK) return rc;
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays_instanced: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+// ---- posed models (posed_core.h): the instanced entries, then the pose pass on the same stream ---------------------------------------------
+int blok_hip_check_poses(blok_hip_ctx* ctx, const blok_pose* poses_host, uint32_t n_poses) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    return check_pose_table(ctx, poses_host, n_poses);
+}
+
+int blok_hip_trace_primary_posed_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                        const blok_instance* instances_dev, uint32_t n_instances, const blok_pose* poses_dev, uint32_t n_poses,
+                                        void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, void* hip_stream) {
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if ((!out_hits_dev && !out_rgba_dev && !out_instance_dev) || !rect_inside(ctx, x0, y0, w, h))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
+    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    if (n_poses && !poses_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
+    if (n_poses >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
+    if (!n_poses)                                        // the instanced entry itself: the same launches, the same bytes
+        return blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, instances_dev, n_instances, out_hits_dev, out_rgba_dev, out_instance_dev, hip_stream);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const size_t n_pixels = static_cast<size_t>(w) * h;
+    blok_hit* hits = static_cast<blok_hit*>(out_hits_dev);
+    auto& sc = ctx->beam_buffers[stream];
+    if (!hits) {                                         // the pose pass needs the composed records
+        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n_pixels, blok::FreeAfter::work_on(stream)));
+        hits = sc.inst_hits;
+    }
+    rc = blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, instances_dev, n_instances, hits, out_rgba_dev, out_instance_dev, hip_stream);
+    if (rc != BLOK_OK) return rc;
+    blok::TraceArgs world = base_args(ctx, cam);
+    world.x0 = x0; world.y0 = y0; world.w = w; world.h = h;
+    blok::PosedArgs Q{};
+    Q.frame = instance_args(ctx, world, nullptr, 0u, hits, static_cast<uint32_t*>(out_rgba_dev), out_instance_dev);
+    Q.poses = poses_dev; Q.n_poses = n_poses;
+    Q.frame.bins_x = (w + blok::kBinPixels - 1u) / blok::kBinPixels;
+    Q.frame.bins_y = (h + blok::kBinPixels - 1u) / blok::kBinPixels;
+    Q.frame.view = bin_view(ctx, *cam);
+    BLOK_HIP_TRY(ctx, sc.pose_bins.reserve(static_cast<size_t>(Q.frame.bins_x) * Q.frame.bins_y * blok::kBinWords, blok::FreeAfter::work_on(stream)));
+    Q.frame.bins = sc.pose_bins;
+    blok::launch_posed_bins(Q, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    blok::launch_posed_pass(Q, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    return BLOK_OK;
+}
+
+int blok_hip_trace_primary_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                 const blok_instance* instances_host, uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses,
+                                 blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host) {
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if ((!out_hits_host && !out_rgba_host && !out_instance_host) || !rect_inside(ctx, x0, y0, w, h))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
+    rc = check_table(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
+    if (rc != BLOK_OK) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    // one device block: instances, poses, records, RGBA8, ids
+    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
+    const size_t pose_bytes = (static_cast<size_t>(n_poses) * sizeof(blok_pose) + 255u) / 256u * 256u;
+    const size_t bytes = inst_bytes + pose_bytes + n * (sizeof(blok_hit) + 2u * sizeof(uint32_t));
+    blok::DeviceArray<unsigned char> d;
+    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
+    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
+    blok_pose* d_pose = reinterpret_cast<blok_pose*>(d + inst_bytes);
+    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d + inst_bytes + pose_bytes);
+    uint32_t* d_rgba = reinterpret_cast<uint32_t*>(d_hits + n);
+    uint32_t* d_ids = d_rgba + n;
+    hipError_t e = n_instances ? hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess && n_poses) e = hipMemcpy(d_pose, poses_host, n_poses * sizeof(blok_pose), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = blok_hip_trace_primary_posed_device(ctx, cam, x0, y0, w, h, d_inst, n_instances, d_pose, n_poses, d_hits, out_rgba_host ? d_rgba : nullptr,
+                                                 out_instance_host ? d_ids : nullptr, nullptr);
+        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_rgba_host) e = hipMemcpy(out_rgba_host, d_rgba, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (rc != BLOK_OK) return rc;
+    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_primary_posed: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+int blok_hip_trace_rays_posed_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev, uint32_t n_instances,
+                                     const blok_pose* poses_dev, uint32_t n_poses, blok_hit* out_hits_dev, uint32_t* out_instance_dev,
+                                     void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
+    if (n == 0) return BLOK_OK;
+    if (!rays_dev || (!out_hits_dev && !out_instance_dev) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
+    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    if (n_poses && !poses_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
+    if (n_poses >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
+    if (!n_poses) return blok_hip_trace_rays_instanced_device(ctx, rays_dev, n, instances_dev, n_instances, out_hits_dev, out_instance_dev, hip_stream);
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    blok_hit* hits = out_hits_dev;
+    if (!hits) {
+        auto& sc = ctx->beam_buffers[stream];
+        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n, blok::FreeAfter::work_on(stream)));
+        hits = sc.inst_hits;
+    }
+    int rc = blok_hip_trace_rays_instanced_device(ctx, rays_dev, n, instances_dev, n_instances, hits, out_instance_dev, hip_stream);
+    if (rc != BLOK_OK) return rc;
+    blok::TraceArgs world = base_args(ctx, nullptr);
+    world.rays = rays_dev; world.n_rays = static_cast<uint32_t>(n);
+    blok::PosedArgs Q{};
+    Q.frame = instance_args(ctx, world, nullptr, 0u, hits, nullptr, out_instance_dev);
+    Q.poses = poses_dev; Q.n_poses = n_poses;
+    blok::launch_posed_rays(Q, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    return BLOK_OK;
+}
+
+int blok_hip_trace_rays_posed(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, const blok_instance* instances_host, uint32_t n_instances,
+                              const blok_pose* poses_host, uint32_t n_poses, blok_hit* out_hits_host, uint32_t* out_instance_host) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
+    if (n == 0) return BLOK_OK;
+    if (!rays_host || (!out_hits_host && !out_instance_host) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
+    int rc = check_table(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
+    if (rc != BLOK_OK) return rc;
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
+    const size_t pose_bytes = (static_cast<size_t>(n_poses) * sizeof(blok_pose) + 255u) / 256u * 256u;
+    const size_t bytes = inst_bytes + pose_bytes + n * (sizeof(blok_ray) + sizeof(blok_hit) + sizeof(uint32_t));
+    blok::DeviceArray<unsigned char> d;
+    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
+    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
+    blok_pose* d_pose = reinterpret_cast<blok_pose*>(d + inst_bytes);
+    blok_ray* d_rays = reinterpret_cast<blok_ray*>(d + inst_bytes + pose_bytes);
+    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d_rays + n);
+    uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_hits + n);
+    hipError_t e = hipMemcpy(d_rays, rays_host, n * sizeof(blok_ray), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_instances) e = hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_poses) e = hipMemcpy(d_pose, poses_host, n_poses * sizeof(blok_pose), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = blok_hip_trace_rays_posed_device(ctx, d_rays, n, d_inst, n_instances, d_pose, n_poses, d_hits, out_instance_host ? d_ids : nullptr, nullptr);
+        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
+        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (rc != BLOK_OK) return rc;
+    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays_posed: ") + hipGetErrorString(e));
     return BLOK_OK;
 }
 

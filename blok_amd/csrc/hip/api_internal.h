@@ -139,6 +139,7 @@ struct blok_hip_ctx {
         blok::DeviceBytes tail_pool;                                      // path launches: the bounce rounds' tail pool (path_core.h: TailRecord[blocks][kTailCapacity]), grown on demand
         blok::DeviceArray<uint32_t> inst_bins;                           // instanced frames: the binning kernel's lists (instance_core.h: kBinWords words per bin), grown on demand
         blok::DeviceArray<blok_hit> inst_hits;                           // instanced frames without a record output: the world records the instance pass reads
+        blok::DeviceArray<uint32_t> pose_bins;                           // posed frames: the posed binning kernel's lists (the same layout), grown on demand
         blok::DeviceBytes tlas;                                           // instanced path launches: the instance BVH (tlas_core.h: TlasNode), grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;

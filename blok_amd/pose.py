@@ -1,0 +1,54 @@
+"""Posed models (include/blok_hip.h: blok_pose, "Posed models"; include/blok_world.h: blok_pose_from_instance, blok_pose_from_matrix,
+blok_affine_from_pose): the records HipTracer.trace_primary_posed / trace_rays_posed take, and the fold into a volume_stamp_affine record."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import AFFINE, BlokError, INSTANCE, POSE, POSE_ID  # noqa: F401
+from .affine import rotation_matrix
+
+
+def from_instance(place, voxel_size: float = 1.0) -> np.ndarray:
+    """blok_pose_from_instance: one INSTANCE record as one POSE record whose local ray is the lattice instance's, value for value."""
+    p = np.ascontiguousarray(place, dtype=INSTANCE).reshape(-1)
+    assert len(p) == 1, "one placement"
+    out = np.zeros(1, dtype=POSE)
+    rc = _ffi.host_lib().blok_pose_from_instance(_ffi.ptr(p), float(voxel_size), _ffi.ptr(out))
+    if rc != 0:
+        raise BlokError(rc, "blok_pose_from_instance")
+    return out
+
+
+def from_matrix(forward, model: int = 0, pivot_local=None) -> np.ndarray:
+    """blok_pose_from_matrix: a forward map local -> world, (3, 4) (world = F @ local + T, world units; one model voxel is
+    voxel_size * 2**scale wide in local space), inverted in double and rounded once, as one POSE record of `model`.  pivot_local: the local
+    point about which the pose is most accurate (None: the local origin)."""
+    f = np.ascontiguousarray(forward, dtype=np.float64).reshape(-1)
+    assert len(f) == 12, "a 3 x 4 matrix, row major"
+    pl = None if pivot_local is None else (C.c_double * 3)(*[float(c) for c in pivot_local])
+    out = np.zeros(1, dtype=POSE)
+    rc = _ffi.host_lib().blok_pose_from_matrix(f.ctypes.data_as(C.POINTER(C.c_double)), pl, int(model), _ffi.ptr(out))
+    if rc != 0:
+        raise BlokError(rc, "blok_pose_from_matrix")
+    return out
+
+
+def rotation(model: int = 0, yaw: float = 0.0, pitch: float = 0.0, roll: float = 0.0, scale: float = 1.0, pivot_local=(0.0, 0.0, 0.0),
+             position=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """One POSE record that turns the model by yaw about +y, pitch about +x and roll about +z (radians; applied roll first), scales it and
+    puts the local point `pivot_local` at the world point `position` (both in world units): blok_amd.affine.rotation's map, traced."""
+    return from_matrix(rotation_matrix(yaw, pitch, roll, scale, pivot_local, position), model, pivot_local)
+
+
+def to_affine(pose, voxel_size: float = 1.0, scale_log2: int = 0) -> np.ndarray:
+    """blok_affine_from_pose: the pose of a model of scale exponent `scale_log2` as one AFFINE record for HipTracer.volume_stamp_affine."""
+    p = np.ascontiguousarray(pose, dtype=POSE).reshape(-1)
+    assert len(p) == 1, "one pose"
+    out = np.zeros(1, dtype=AFFINE)
+    rc = _ffi.host_lib().blok_affine_from_pose(_ffi.ptr(p), float(voxel_size), int(scale_log2), _ffi.ptr(out))
+    if rc != 0:
+        raise BlokError(rc, "blok_affine_from_pose")
+    return out

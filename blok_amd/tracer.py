@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import BlokError, CAMERA, GBuffer, HIT, INSTANCE, MATERIAL, RAY, SUB_CHUNK, SVO_NODE, WorldStats
+from ._ffi import BlokError, CAMERA, GBuffer, HIT, INSTANCE, MATERIAL, POSE, RAY, SUB_CHUNK, SVO_NODE, WorldStats
 
 
 def _vec3(v):
@@ -991,6 +991,51 @@ class HipTracer:
         self._check(self._lib.blok_hip_trace_rays_instanced(self._ctx, _ffi.ptr(rays), len(rays), _ffi.ptr(inst), len(inst),
                                                             _ffi.ptr(hits), _ffi.ptr(ids)))
         return hits, ids
+
+    # -- posed models (blok_hip.h, "Posed models"): instanced models under any rotation, scale, mirror or shear ------------------------------
+    def check_poses(self, poses: np.ndarray):
+        p = np.ascontiguousarray(poses, dtype=POSE).reshape(-1)
+        self._check(self._lib.blok_hip_check_poses(self._ctx, _ffi.ptr(p) if len(p) else None, len(p)))
+
+    def trace_primary_posed(self, cam: np.ndarray, instances, poses, rect=None):
+        """(hits (h, w), ids (h, w), RGBA8 (h, w)) of the frame (or rect) over the world, `instances` (INSTANCE records) and `poses` (POSE
+        records, blok_amd.pose).  A pixel a pose wins has id POSE_ID | index, the pose's local voxel and local face."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
+        hits = np.zeros(w * h, dtype=HIT)
+        ids = np.zeros(w * h, dtype=np.uint32)
+        rgba = np.zeros(w * h, dtype=np.uint32)
+        self._check(self._lib.blok_hip_trace_primary_posed(self._ctx, _ffi.ptr(cam), x0, y0, w, h, _ffi.ptr(inst) if len(inst) else None, len(inst),
+                                                           _ffi.ptr(p) if len(p) else None, len(p), _ffi.ptr(hits), _ffi.ptr(rgba), _ffi.ptr(ids)))
+        return hits.reshape(h, w), ids.reshape(h, w), rgba.reshape(h, w)
+
+    def trace_primary_posed_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, poses_ptr: int, n_poses: int, hits_ptr: int = 0,
+                                   rgba_ptr: int = 0, ids_ptr: int = 0, rect=None, stream: int = 0):
+        """Asynchronous: device tables and outputs (any output pointer may be 0, not all)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        self._check(self._lib.blok_hip_trace_primary_posed_device(self._ctx, _ffi.ptr(cam), x0, y0, w, h, C.c_void_p(instances_ptr), int(n_instances),
+                                                                  C.c_void_p(poses_ptr), int(n_poses), C.c_void_p(hits_ptr), C.c_void_p(rgba_ptr),
+                                                                  C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def trace_rays_posed(self, rays: np.ndarray, instances, poses):
+        """(records, ids) of explicit rays over the world, `instances` and `poses`: every pose is tested for every ray."""
+        rays = np.ascontiguousarray(rays, dtype=RAY)
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
+        hits = np.zeros(len(rays), dtype=HIT)
+        ids = np.zeros(len(rays), dtype=np.uint32)
+        self._check(self._lib.blok_hip_trace_rays_posed(self._ctx, _ffi.ptr(rays), len(rays), _ffi.ptr(inst) if len(inst) else None, len(inst),
+                                                        _ffi.ptr(p) if len(p) else None, len(p), _ffi.ptr(hits), _ffi.ptr(ids)))
+        return hits, ids
+
+    def trace_rays_posed_device(self, rays_ptr: int, n: int, instances_ptr: int, n_instances: int, poses_ptr: int, n_poses: int, hits_ptr: int = 0,
+                                ids_ptr: int = 0, stream: int = 0):
+        self._check(self._lib.blok_hip_trace_rays_posed_device(self._ctx, C.c_void_p(rays_ptr), int(n), C.c_void_p(instances_ptr), int(n_instances),
+                                                               C.c_void_p(poses_ptr), int(n_poses), C.c_void_p(hits_ptr), C.c_void_p(ids_ptr),
+                                                               C.c_void_p(stream)))
 
     def trace_paths_instanced(self, cam: np.ndarray, instances: np.ndarray, spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None):
         """trace_paths over the world plus `instances` (INSTANCE records): the planes dict plus "ids", the instance of each pixel's

@@ -587,6 +587,24 @@ public:
                                             outHits.data(), outInstanceIds.data()));
     }
     const std::vector<uint32_t>& instanceIds() const { return m_instanceIds; }
+    // ---- posed models (blok_hip.h, "Posed models"): instanced models under any rotation, scale, mirror or shear (records from
+    // blok_pose_from_instance / blok_pose_from_matrix, blok_world.h).  A pixel a pose wins has id BLOK_POSE_ID | index in instanceIds() and
+    // the model's local voxel and face in its record.
+    void checkPoses(const std::vector<blok_pose>& poses) { check(blok_hip_check_poses(m_ctx, poses.data(), static_cast<uint32_t>(poses.size()))); }
+    // the first-hit frame (or a rectangle of it) over the world, the instances and the poses, into host arrays; any output may be null, not all
+    void tracePrimaryPosed(Camera& cam, const std::vector<blok_instance>& instances, const std::vector<blok_pose>& poses, blok_hit* outHits,
+                           uint32_t* outRgba, uint32_t* outIds, uint32_t x0 = 0, uint32_t y0 = 0, uint32_t w = 0, uint32_t h = 0) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        check(blok_hip_trace_primary_posed(m_ctx, &c, x0, y0, w ? w : m_width, h ? h : m_height, instances.data(), static_cast<uint32_t>(instances.size()),
+                                           poses.data(), static_cast<uint32_t>(poses.size()), outHits, outRgba, outIds));
+    }
+    // drawFrameInstanced with a pose table: records in hits(), ids in instanceIds()
+    void drawFramePosed(Camera& cam, const std::vector<blok_instance>& instances, const std::vector<blok_pose>& poses) {
+        m_instanceIds.resize(static_cast<size_t>(m_width) * m_height);
+        tracePrimaryPosed(cam, instances, poses, m_hits.data(), nullptr, m_instanceIds.data());
+        cam.cameraChanged = false;
+        ++m_frameIndex;
+    }
 
     const std::vector<blok_hit>& hits() const { return m_hits; }     // output accessor (getGLTex analogue)
     unsigned int width() const { return m_width; }

@@ -587,7 +587,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.18: models resampled into the resident volume through an affine map (blok_hip_volume_stamp_affine): any rotation, scale, mirror, shear.
  * 1.19: neighbour-count rules stepped over the resident volume (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life.
  * 1.20: procedural terrain reduced to coarse levels without a volume (blok_hip_terrain_reduce): the far field built at any time.
- * 1.21: a view at rest restarts every listed ray where its own counted walk ended (blok_hip_debug.h: blok_hip_set_beam_cache mode 4, the default). */
+ * 1.21: a view at rest restarts every listed ray where its own counted walk ended (blok_hip_debug.h: blok_hip_set_beam_cache mode 4, the default).
+ * 1.22: instanced models traced under any rotation, scale, mirror or shear (blok_pose; blok_hip_trace_primary_posed*, blok_hip_trace_rays_posed*). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -622,7 +623,8 @@ uint32_t blok_hip_abi_version(void);
  *   - Limit: vm <= 256, checked where a table is checked (host tables: BLOK_ERR_INVALID_ARG naming the instance; device tables: skipped).
  *   - Composition, the tie rule, the any-hit shadow rule and the BVH's ordering rule are unchanged, and so is the object-motion map
  *     (it does not contain the scale).
- *   Not built: negative exponents.  (A scaled model is baked into the resident volume by blok_hip_volume_stamp_affine, since ABI 1.18:
+ *   Not built: negative exponents (a model traced at any real scale, turned or sheared, is a blok_pose, "Posed models" below, since ABI
+ *   1.22; the path-traced frame takes lattice instances only).  (A scaled model is baked into the resident volume by blok_hip_volume_stamp_affine, since ABI 1.18:
  *   blok_affine_from_instance, blok_world.h, folds a placement and the exponent into its record; the other volume entries refuse one, below.)
  * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
  * Scope.  The primary frame, explicit rays and the path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced
@@ -672,6 +674,67 @@ int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, 
                                   uint32_t n_instances, blok_hit* out_hits_host, uint32_t* out_instance_host);
 int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev,
                                          uint32_t n_instances, blok_hit* out_hits_dev, uint32_t* out_instance_dev, void* hip_stream);
+
+/* ------------------------------------------------------------- posed models (ABI 1.22)
+ * A blok_pose places a model under ANY affine map: a rotation by any angle, a real scale, a mirror, a shear.  It is traced, not baked
+ * (blok_hip_volume_stamp_affine bakes); a lattice instance (blok_instance above) stays the cheaper record where it is enough.
+ *
+ * Pose.  blok_pose below, 64 bytes: the model, the map m from WORLD to LOCAL space (row k gives local axis k), a world point `pivot` and
+ *   the local point `local` it lands on.  All lengths are world units (not voxels): one model voxel is vm = vs * 2^e wide in local space,
+ *   e the model's scale exponent ("Scaled models" above).
+ * Ray into local space.  Every operation rounded separately to float, nothing fused, in this order:
+ *     r_j  = fl(o_j - pivot_j)
+ *     o'_k = fl( fl( fl( fl(m_k0 r_0) + fl(m_k1 r_1) ) + fl(m_k2 r_2) ) + local_k )
+ *     d'_k = fl( fl( fl(m_k0 d_0) + fl(m_k1 d_1) ) + fl(m_k2 d_2) )
+ *   tmin and tmax unchanged.  The direction is NOT renormalised: an affine map of the ray keeps its parameter, so t means the same in the
+ *   world, in a lattice instance and in a pose, and "strictly smaller t" composes them.  (The canonical walk of DESIGN.md §3 puts no
+ *   condition on the length of d.)  A ray whose o' or d' has a component that is not finite does not enter that pose.
+ * Walk.  The canonical walk over the model's tree at the model's own voxel size vm, exactly as for a lattice instance.
+ * Record.  t and material_id unchanged, hit = 1.  voxel is the MODEL'S LOCAL voxel (a turned cell has no world voxel) and face the LOCAL
+ *   face code 2k + n (n = 0: the face whose outward normal is +local axis k, n = 1: -local axis k, as in every record).  World normal:
+ *   normals transform by the transpose of the world -> local map, so the outward world normal of local face 2k + n is parallel to
+ *   s * (m_k0, m_k1, m_k2), s = +1 for n = 0 and -1 for n = 1 (normalise it; under a singular m it may be zero).
+ * RGBA of the primary frame.  Shading needs one of the six world faces: of the vector s * (m_k0, m_k1, m_k2) the component of largest
+ *   magnitude (ties: the lowest axis) names the axis a, and the shade face is 2a if that component is >= 0 (or -0), 2a + 1 if it is < 0.
+ *   The record keeps the local face.
+ * Composition.  Candidates in the order: the world, instances 0 .. n-1, poses 0 .. p-1; a candidate replaces the record only with a
+ *   strictly smaller t (each walks with tmax = the best t so far).  Ties go to the world, then the lattice instances, then the lowest pose.
+ * Ids.  out_instance = BLOK_POSE_ID | index for a pixel / ray that a pose wins; the instance index or BLOK_INSTANCE_NONE otherwise.
+ * Limits.  All 15 floats finite; |m_kj| <= 1024, |pivot_j| <= 2^20, |local_k| <= 2^20; the model exists and its voxel size vm <= 256;
+ *   the model's own voxel box lies in [-32768, 32768) (the record's voxel is int16).  At most 2^31 - 1 poses.  A singular m is legal: the
+ *   rule needs no inverse.  Host tables fail with BLOK_ERR_INVALID_ARG naming the first pose that breaks a limit (blok_hip_check_poses does
+ *   this check alone); the kernels of the device-table entries skip such a pose.
+ * Scope.  The primary frame and explicit rays.  The path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced*),
+ *   object motion, the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay as they are and never receive a
+ *   pose table.  A posed model that has stopped can be baked about where it was seen: blok_affine_from_pose (blok_world.h). */
+typedef struct blok_pose {     /* 64 bytes */
+    uint32_t model;
+    float    m[3][3];          /* world -> local: row k gives local axis k */
+    float    pivot[3];         /* a world point (world units, not voxels) */
+    float    local[3];         /* where the pivot lies in local space (world units: one model voxel is vm = vs * 2^e wide) */
+} blok_pose;
+#define BLOK_POSE_ID 0x80000000u   /* out_instance = BLOK_POSE_ID | index for a pixel / ray a pose wins */
+
+/* BLOK_OK if every pose of a host table passes the limits above, else BLOK_ERR_INVALID_ARG naming the first that does not. */
+int blok_hip_check_poses(blok_hip_ctx* ctx, const blok_pose* poses_host, uint32_t n_poses);
+/* blok_hip_trace_primary_instanced_device, then, on the same stream and only if n_poses > 0, a binning kernel (poses per 32x32-pixel bin:
+ * the bounding box of each pose's preimage in the world, widened by an argued margin) and a kernel that walks each pixel's
+ * candidate poses and composes in place.  The frame is DEFINED as if every pose were tested for every pixel.  Either table may be empty;
+ * with n_poses == 0 the outputs are byte for byte those of blok_hip_trace_primary_instanced_device.  Both tables are read in stream
+ * order.  Outputs: any may be NULL, not all.  After the first call at a given size the call allocates nothing and does not synchronise. */
+int blok_hip_trace_primary_posed_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                        const blok_instance* instances_dev, uint32_t n_instances, const blok_pose* poses_dev, uint32_t n_poses,
+                                        void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, void* hip_stream);
+/* Blocking form with host arrays (both tables are checked first). */
+int blok_hip_trace_primary_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                 const blok_instance* instances_host, uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses,
+                                 blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host);
+/* Explicit rays against the world, the instances and the poses: every pose is tested for every ray. */
+int blok_hip_trace_rays_posed(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, const blok_instance* instances_host, uint32_t n_instances,
+                              const blok_pose* poses_host, uint32_t n_poses, blok_hit* out_hits_host, uint32_t* out_instance_host);
+int blok_hip_trace_rays_posed_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev, uint32_t n_instances,
+                                     const blok_pose* poses_dev, uint32_t n_poses, blok_hit* out_hits_dev, uint32_t* out_instance_dev,
+                                     void* hip_stream);
 
 /* Path-traced frames with instances: blok_hip_trace_paths* with every ray of the path loop composed with the instances by the rule above.
  *   Primary and bounce rays: the closest hit of world and instances.  Shadow rays: any hit; the instances are asked only when the world

@@ -216,6 +216,24 @@ int blok_affine_stamp_voxels(float* density, uint32_t* material_ids, const int32
                              const int32_t* model_xyz, const uint32_t* model_materials, size_t n, const blok_affine* record,
                              const int32_t region_lo[3], const int32_t region_hi[3], int mode, float value, uint64_t* out_n_voxels);
 
+/* -------------------------------------------------------------- posed models: making a blok_pose, and baking one (pose.cpp)
+ * blok_pose (blok_hip.h, "Posed models") maps the WORLD to a model's LOCAL space; lengths are world units.  vs: the world's voxel size.
+ * pose_from_instance: the placement as a pose: m the signed permutation (m[k][axis[k]] = -1 under flip bit k, else +1), pivot =
+ *   fl(offset * vs), local = 0.  Its local ray is the lattice instance's, value for value (a zero may differ in sign), so its t, material
+ *   and hit are the instance's.
+ * pose_from_matrix: a forward map local -> world, row major 3 x 4 (world = F local + T, world units), inverted in double (adjugate over
+ *   determinant) and rounded once to float.  pivot_local (NULL = the local origin): the local point about which the pose is most accurate;
+ *   pivot = fl(F pivot_local + T), local = fl(pivot_local + F^-1 (pivot - (F pivot_local + T))).
+ *   BLOK_ERR_INVALID_ARG: a NULL pointer, a value that is not finite, a singular matrix, a result beyond the limits of a pose.
+ * affine_from_pose: the pose folded into blok_hip_volume_stamp_affine's record for a model of scale exponent e <= 8, so that a posed
+ *   model that stops can be baked about where it was seen: anchor = floor(pivot / vs), m = rint(m * 2^16 / 2^e),
+ *   t = rint((m ((anchor + 1/2) vs - pivot) + local) / (vs 2^e) * 2^16), in double.  For the poses of pose_from_instance it gives
+ *   blok_affine_from_instance's record bit for bit; only that is pinned.  BLOK_ERR_INVALID_ARG: a NULL pointer, vs not a positive finite
+ *   number, e > 8, a value that is not finite, a result beyond the record's limits (|m| > 2^22, |t| > 2^40, an anchor outside int32). */
+int blok_pose_from_instance(const blok_instance* placement, float vs, blok_pose* out);
+int blok_pose_from_matrix(const double forward[12], const double pivot_local[3], uint32_t model, blok_pose* out);
+int blok_affine_from_pose(const blok_pose* pose, float vs, uint32_t scale_log2, blok_affine* out);
+
 /* -------------------------------------------------------------- a volume's connected components on the host (components.cpp)
  * label: the contract of blok_hip_volume_label_components (blok_hip.h; blok_component is declared there) over the host array
  * density[x + y*nx + z*nx*ny] of a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the union-find the kernels

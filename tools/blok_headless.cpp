@@ -69,6 +69,13 @@
 //          (VOX z is up) is turned by YAW_DEG about +y around the centre of its voxels' box, scaled by SCALE, and resampled into the volume
 //          with that centre at the world point X,Y,Z (blok_affine_from_matrix, blok_hip_volume_stamp_affine, BLOK_STAMP_SET); the number of
 //          voxels written is printed.  May be given more than once: pasted in order
+//   --pose FILE.vox@X,Y,Z,YAW_DEG[,SCALE]: the first model of the .vox file (VOX z is up) is uploaded and TRACED as a posed model
+//          (blok_pose_from_matrix, blok_hip_trace_primary_posed): turned by YAW_DEG about +y around the centre of its voxels' box, scaled by SCALE
+//          (1 if left out), that centre at the world point X,Y,Z — --paste's map, shown and not baked.  Over the generated scene (whose material
+//          table is the scene's own 256 entries) a voxel's material id is its palette index; with --terrain the palette is imported as materials.
+//          The first-hit frames are traced with the poses in the order given; the last frame's camera and `pose: poses won P of W pixels` are
+//          printed.  May be given more than once.  Refused with --rt (the path-traced frame takes no pose table), --far, --vox, --obj,
+//          --load-volume and more than one device.  (--pose N with a bare number is the camera pose.)
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
@@ -120,6 +127,7 @@ struct Options {
     bool bake = false;                    // ... and stamped into the volume instead of traced as instances
     struct Paste { std::string path; double position[3], yaw_deg, scale; };
     std::vector<Paste> paste;             // .vox models resampled into the terrain, turned and scaled
+    std::vector<Paste> posed;             // .vox models traced as posed models over the world, turned and scaled
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
@@ -138,6 +146,8 @@ private:
             case blok::GraphicsApi::HIP: {
                 m_tracer = std::make_unique<blok::HipTracer>(m_opt.width, m_opt.height);
                 m_tracer->init();
+                if (!m_opt.posed.empty() && (m_opt.far || !m_opt.vox.empty() || !m_opt.obj.empty() || !m_opt.load_volume.empty() || m_opt.devices.size() > 1))
+                    throw std::runtime_error("--pose FILE.vox@... traces its models over the generated scene or a --terrain, on one device: leave --far, --vox, --obj, --load-volume and --devices out");
                 if (!m_opt.load_volume.empty() && m_opt.far) throw std::runtime_error("--far generates its terrain: leave --load-volume out");
                 if (!m_opt.load_volume.empty() && !m_opt.paste.empty()) throw std::runtime_error("--paste needs a terrain: leave --load-volume out");
                 if (!m_opt.load_volume.empty()) { initLoaded(); exportObj(); components(); settle(); saveVolume(); break; }
@@ -174,6 +184,7 @@ private:
                     blok_scene_materials(0xB10C0001u, m_world.materials.data());
                 }
                 m_tracer->addWorld(m_world);                                              // app.cpp:122-124
+                loadPoses(false);
                 if (m_opt.devices.size() > 1) {
                     m_multi = std::make_unique<blok::HipMultiTracer>(m_opt.devices, m_opt.width, m_opt.height, 32, m_opt.rccl);
                     m_multi->addWorld(m_world);
@@ -274,6 +285,7 @@ private:
         stroke();
         populate(p);
         paste();
+        loadPoses(true);
         m_tracer->rebuildVolume(m_materials.packForGpu());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
@@ -395,13 +407,15 @@ private:
         std::cout << "seal: " << filled << " voxels filled, farthest " << info.farthest << "\n";
     }
     // The first model of a .vox file in the local lattice of the models here (VOX z is up -> local y), its palette imported as materials.
-    void loadVoxModel(const std::string& path, std::vector<int32_t>& xyz, std::vector<uint32_t>& ids, uint32_t size[3]) {
+    // (imported == false: nothing is imported, a voxel's id is its palette index)
+    void loadVoxModel(const std::string& path, std::vector<int32_t>& xyz, std::vector<uint32_t>& ids, uint32_t size[3], bool imported = true) {
         char err[512] = {0};
         blok_vox* vox = nullptr;
         if (blok_vox_load_file(path.c_str(), &vox, err, sizeof(err)) != BLOK_OK) throw std::runtime_error("Failed to load VOX: " + std::string(err));
         uint32_t n = 0, palette[256];
         if (blok_vox_model_count(vox) == 0 || blok_vox_model_info(vox, 0, size, &n) != BLOK_OK || n == 0) { blok_vox_free(vox); throw std::runtime_error("the VOX holds no voxels: " + path); }
-        blok_vox_import_materials(vox, m_materials.handle(), palette);
+        if (imported) blok_vox_import_materials(vox, m_materials.handle(), palette);
+        else for (uint32_t k = 0; k < 256u; ++k) palette[k] = k;
         const uint8_t* v = blok_vox_model_voxels(vox, 0);
         xyz.resize(3u * n);
         ids.resize(n);
@@ -437,6 +451,42 @@ private:
             const uint64_t written = m_tracer->stampAffine({record}, nullptr, nullptr, BLOK_STAMP_SET, 1.0f);
             std::cout << "paste: " << P.path << ": " << ids.size() << " voxels turned " << P.yaw_deg << " degrees, scaled " << P.scale << " -> " << written << " voxels written\n";
         }
+    }
+    // Each --pose model uploaded and given its pose: --paste's forward map (T(position) Ry(yaw) S(scale) T(-centre)) inverted and rounded by
+    // blok_pose_from_matrix about the centre of the voxels' box.
+    void loadPoses(bool imported) {
+        for (const Options::Paste& P : m_opt.posed) {
+            std::vector<int32_t> xyz;
+            std::vector<uint32_t> ids;
+            uint32_t size[3] = {0, 0, 0};
+            loadVoxModel(P.path, xyz, ids, size, imported);
+            int32_t lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+            for (size_t i = 0; i < ids.size(); ++i)
+                for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], xyz[3 * i + a]); hi[a] = std::max(hi[a], xyz[3 * i + a] + 1); }
+            const double pivot[3] = {(lo[0] + hi[0]) / 2.0, (lo[1] + hi[1]) / 2.0, (lo[2] + hi[2]) / 2.0};
+            const double yaw = P.yaw_deg * (3.14159265358979323846 / 180.0), cy = std::cos(yaw), sy = std::sin(yaw), s = P.scale;
+            const double r[3][3] = {{cy, 0.0, sy}, {0.0, 1.0, 0.0}, {-sy, 0.0, cy}};
+            double forward[12];
+            for (int i = 0; i < 3; ++i) {
+                const double row[3] = {s * r[i][0], s * r[i][1], s * r[i][2]};
+                for (int j = 0; j < 3; ++j) forward[4 * i + j] = row[j];
+                forward[4 * i + 3] = P.position[i] - (row[0] * pivot[0] + row[1] * pivot[1] + row[2] * pivot[2]);
+            }
+            blok_pose pose;
+            if (blok_pose_from_matrix(forward, pivot, m_tracer->createModel(xyz, ids), &pose) != BLOK_OK)
+                throw std::runtime_error("--pose: the map has no pose (blok_pose_from_matrix): SCALE must be at least 1/1024 and the position within 2^20");
+            m_poses.push_back(pose);
+            std::cout << "pose: " << P.path << ": " << ids.size() << " voxels turned " << P.yaw_deg << " degrees, scaled " << P.scale << "\n";
+        }
+        if (!m_poses.empty()) m_tracer->checkPoses(m_poses);
+    }
+    const std::vector<uint32_t>& drawPosed() {
+        const size_t n = static_cast<size_t>(m_opt.width) * m_opt.height;
+        m_populatedHits.resize(n);
+        m_populatedFrame.resize(n);
+        m_poseIds.resize(n);
+        m_tracer->tracePrimaryPosed(m_camera, m_instances, m_poses, m_populatedHits.data(), m_populatedFrame.data(), m_poseIds.data());
+        return m_populatedFrame;
     }
     // The listed .vox models scattered over the terrain's grass: the column field of the whole box, then the table — kept for the frames, or baked.
     void populate(const blok_terrain_params& terrain) {
@@ -645,6 +695,7 @@ private:
             if (m_multi) m_multi->drawFrame(m_camera, m_multiFrame);
             else if (m_opt.rt && m_opt.far) m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp);
             else if (m_opt.rt) m_tracer->drawFrameRT(m_camera, m_opt.spp);
+            else if (!m_poses.empty()) m_tracer->drawFramePosed(m_camera, m_instances, m_poses);
             else if (!m_instances.empty()) m_tracer->drawFrameInstanced(m_camera, m_instances);
             else m_tracer->drawFrame(m_camera);
             m_tracer->endFrame();
@@ -656,7 +707,7 @@ private:
             if (f + 1 < m_opt.frames || !m_opt.rt) m_camera.processKeyboard('W', 0.016f);
         }
         const auto& single = m_opt.rt && m_opt.far ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
-                             : m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
+                             : m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_poses.empty() ? drawPosed() : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
         if (m_multi) {                                       // the partitioned frame must be the single-device frame
             m_multi->drawFrame(m_camera, m_multiFrame);
             size_t differ = 0;
@@ -665,6 +716,17 @@ private:
             if (differ) throw std::runtime_error("multi-device frame differs from the single-device frame");
         }
         farReport();
+        if (!m_poses.empty()) {                             // the camera of the written frame, exactly (%.9g round-trips a float), and who won it
+            const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
+            const float cam[14] = {c.pos[0], c.pos[1], c.pos[2], c.fwd[0], c.fwd[1], c.fwd[2], c.right[0], c.right[1], c.right[2], c.up[0], c.up[1], c.up[2], c.tan_half_fov, c.aspect};
+            std::printf("pose: camera");
+            for (float v : cam) std::printf(" %.9g", v);
+            std::printf("\n");
+            std::fflush(stdout);
+            size_t won = 0;
+            for (uint32_t id : m_poseIds) won += id != BLOK_INSTANCE_NONE && (id & BLOK_POSE_ID) != 0u;
+            std::cout << "pose: poses won " << won << " of " << m_poseIds.size() << " pixels\n";
+        }
         const auto& px = m_multi ? m_multiFrame : single;
         std::ofstream ppm(m_opt.out, std::ios::binary);
         ppm << "P6\n" << m_opt.width << " " << m_opt.height << "\n255\n";
@@ -685,6 +747,8 @@ private:
     std::vector<blok_instance> m_instances;        // --populate: the scattered table (empty once baked); --far: the ring of coarse copies
     std::vector<blok_hit> m_populatedHits;
     std::vector<uint32_t> m_populatedFrame;
+    std::vector<blok_pose> m_poses;                // --pose FILE.vox@...: the posed models, in the order given
+    std::vector<uint32_t> m_poseIds;
 };
 
 }  // namespace
@@ -740,7 +804,24 @@ int main(int argc, char** argv) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "--n")) opt.n = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--size")) { if (std::sscanf(next(), "%ux%u", &opt.width, &opt.height) != 2) return 2; }
-        else if (!std::strcmp(argv[i], "--pose")) opt.pose = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--pose")) {
+            const std::string arg = next();
+            const size_t at = arg.rfind('@');
+            if (at == std::string::npos) { opt.pose = std::atoi(arg.c_str()); continue; }      // a bare number: the camera pose
+            Options::Paste P{};
+            P.scale = 1.0;
+            char tail = 0;
+            const char* spec = arg.c_str() + at + 1;
+            bool whole = at != 0 && std::sscanf(spec, "%lf,%lf,%lf,%lf%c", &P.position[0], &P.position[1], &P.position[2], &P.yaw_deg, &tail) == 4;
+            if (!whole) whole = at != 0 && std::sscanf(spec, "%lf,%lf,%lf,%lf,%lf%c", &P.position[0], &P.position[1], &P.position[2], &P.yaw_deg, &P.scale, &tail) == 5;
+            if (!whole || !std::isfinite(P.position[0]) || !std::isfinite(P.position[1]) || !std::isfinite(P.position[2]) || !std::isfinite(P.yaw_deg) ||
+                !std::isfinite(P.scale) || !(P.scale > 0.0)) {
+                std::fprintf(stderr, "--pose takes FILE.vox@X,Y,Z,YAW_DEG[,SCALE] with SCALE > 0 (or a bare number: the camera pose)\n");
+                return 2;
+            }
+            P.path = arg.substr(0, at);
+            opt.posed.push_back(P);
+        }
         else if (!std::strcmp(argv[i], "--frames")) opt.frames = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--out")) opt.out = next();
         else if (!std::strcmp(argv[i], "--vox")) opt.vox = next();
@@ -807,6 +888,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dense-exchange")) opt.dense_exchange = true;
         else if (!std::strcmp(argv[i], "--devices")) { for (const char* p = next(); *p;) { opt.devices.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    if (!opt.posed.empty() && opt.rt) {
+        std::fprintf(stderr, "--pose FILE.vox@... is refused with --rt: posed models are traced in first-hit frames only, the path-traced frame takes no pose table\n");
+        return 2;
     }
     if (opt.far_direct && !opt.far) { std::fprintf(stderr, "--far-direct and --far-rings need --far K[,MIN]\n"); return 2; }
     try {
