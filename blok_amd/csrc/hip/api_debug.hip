@@ -32,7 +32,7 @@ int blok_hip_download_tree(const blok_hip_ctx* ctx, void* nodes_out, size_t node
 int blok_hip_download_model(blok_hip_ctx* ctx, uint32_t model, void* nodes_out, size_t node_capacity, uint32_t* materials_out, size_t material_capacity,
                             blok_model_info* out_info) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     const blok::ModelDesc& m = ctx->models.desc[model];
     const uint32_t n_nodes = ctx->models.own[model].n_nodes, n_materials = ctx->models.own[model].n_materials;
     if ((nodes_out && node_capacity < n_nodes) || (materials_out && material_capacity < n_materials))

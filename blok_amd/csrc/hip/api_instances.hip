@@ -39,7 +39,7 @@ int check_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) {
             if (I.flip >= 8u) return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "flip has bits above the three axes");
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "axis is not a permutation of 0, 1, 2");
         }
-        if (I.model >= ctx->models.desc.size() || !ctx->models.desc[I.model].nodes)
+        if (!known_model(ctx, I.model))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "unknown model " + std::to_string(I.model));
         if (!blok::instance_usable(I, ctx->models.desc[I.model]))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "world box outside the int16 lattice of hit records");
@@ -57,7 +57,7 @@ int check_pose_table(blok_hip_ctx* ctx, const blok_pose* poses, uint32_t n) {
         const blok_pose& S = poses[i];
         const std::string at = "pose " + std::to_string(i) + ": ";
         if (const int rule = blok::pose::floats_rule(S)) return set_error(ctx, BLOK_ERR_INVALID_ARG, at + blok::pose::rule_text(rule));
-        if (S.model >= ctx->models.desc.size() || !ctx->models.desc[S.model].nodes)
+        if (!known_model(ctx, S.model))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "unknown model " + std::to_string(S.model));
         if (!blok::pose_model_box_usable(ctx->models.desc[S.model]))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, at + "the model's own voxel box lies outside the int16 lattice of hit records");
@@ -105,12 +105,120 @@ blok::InstanceArgs instance_args(const blok_hip_ctx* ctx, const blok::TraceArgs&
     return P;
 }
 
+// ---- what the instanced and the posed entries share ----------------------------------------------------------------------------------------
+// The table pointers of a device entry (the tables themselves are the kernels' to judge: instance_usable, pose_usable).
+int check_device_tables(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n_inst, const blok_pose* poses, uint32_t n_poses) {
+    if (n_inst && !inst) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    if (n_poses && !poses) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
+    if (n_poses >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
+    return BLOK_OK;
+}
+
+// The arguments of a frame's device entry, in the order the entries have always checked them.
+int check_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, bool any_output,
+                const blok_instance* inst, uint32_t n_inst, const blok_pose* poses, uint32_t n_poses) {
+    const int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if (!any_output || !rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
+    return check_device_tables(ctx, inst, n_inst, poses, n_poses);
+}
+
+// The arguments of a rays entry, host or device, up to its tables.  BLOK_OK with n == 0: nothing to trace, the entry returns BLOK_OK.
+int check_rays(blok_hip_ctx* ctx, const blok_ray* rays, size_t n, bool any_output) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
+    if (n != 0 && (!rays || !any_output || n > 0x7FFFFFFFu)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
+    return BLOK_OK;
+}
+
+// The set-up of a frame pass (lattice or posed) over the rectangle: the kernels' arguments but for the table, with the rectangle, the bins'
+// dimensions and view, room in `bins` (the stream's scratch for this pass) and the stream's scratch records where the caller passes none.
+int frame_pass(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, hipStream_t stream,
+               blok::DeviceArray<uint32_t>& bins, void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, blok::InstanceArgs& P) {
+    blok_hit* hits = static_cast<blok_hit*>(out_hits_dev);
+    if (!hits) {
+        auto& sc = ctx->beam_buffers[stream];
+        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(static_cast<size_t>(w) * h, blok::FreeAfter::work_on(stream)));
+        hits = sc.inst_hits;
+    }
+    blok::TraceArgs world = base_args(ctx, cam);
+    world.x0 = x0; world.y0 = y0; world.w = w; world.h = h;
+    P = instance_args(ctx, world, nullptr, 0u, hits, static_cast<uint32_t*>(out_rgba_dev), out_instance_dev);
+    P.bins_x = (w + blok::kBinPixels - 1u) / blok::kBinPixels;
+    P.bins_y = (h + blok::kBinPixels - 1u) / blok::kBinPixels;
+    P.view = bin_view(ctx, *cam);
+    BLOK_HIP_TRY(ctx, bins.reserve(static_cast<size_t>(P.bins_x) * P.bins_y * blok::kBinWords, blok::FreeAfter::work_on(stream)));
+    P.bins = bins;
+    return BLOK_OK;
+}
+
+// ... of a rays pass: the rays, and the stream's scratch records where the caller passes none.
+int rays_pass(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, hipStream_t stream, blok_hit* out_hits_dev, uint32_t* out_instance_dev,
+              blok::InstanceArgs& P) {
+    blok_hit* hits = out_hits_dev;
+    if (!hits) {
+        auto& sc = ctx->beam_buffers[stream];
+        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n, blok::FreeAfter::work_on(stream)));
+        hits = sc.inst_hits;
+    }
+    blok::TraceArgs world = base_args(ctx, nullptr);
+    world.rays = rays_dev; world.n_rays = static_cast<uint32_t>(n);
+    P = instance_args(ctx, world, nullptr, 0u, hits, nullptr, out_instance_dev);
+    return BLOK_OK;
+}
+
+// The blocking primary frame of both tables (an empty pose table: the instanced entry's), named `entry` in a HIP failure's text.
+int trace_primary_placed(blok_hip_ctx* ctx, const char* entry, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                         const blok_instance* instances_host, uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses,
+                         blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host) {
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if ((!out_hits_host && !out_rgba_host && !out_instance_host) || !rect_inside(ctx, x0, y0, w, h))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
+    rc = check_table(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
+    if (rc != BLOK_OK) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    StagedBlock d;
+    const auto inst = d.input(instances_host, n_instances);
+    const auto poses = d.input(poses_host, n_poses);
+    const auto hits = d.output(out_hits_host, n);
+    const auto rgba = d.output(out_rgba_host, n);
+    const auto ids = d.output(out_instance_host, n);
+    rc = d.stage(ctx, entry);
+    if (rc != BLOK_OK) return rc;
+    rc = blok_hip_trace_primary_posed_device(ctx, cam, x0, y0, w, h, d.at(inst), n_instances, d.at(poses), n_poses, d.at(hits), d.wanted(rgba),
+                                             d.wanted(ids), nullptr);
+    return d.collect(ctx, entry, rc);
+}
+
+// ... and the blocking rays.
+int trace_rays_placed(blok_hip_ctx* ctx, const char* entry, const blok_ray* rays_host, size_t n, const blok_instance* instances_host,
+                      uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses, blok_hit* out_hits_host, uint32_t* out_instance_host) {
+    int rc = check_rays(ctx, rays_host, n, out_hits_host || out_instance_host);
+    if (rc != BLOK_OK || n == 0) return rc;
+    rc = check_table(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
+    if (rc != BLOK_OK) return rc;
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    StagedBlock d;
+    const auto inst = d.input(instances_host, n_instances);
+    const auto poses = d.input(poses_host, n_poses);
+    const auto rays = d.input(rays_host, n);
+    const auto hits = d.output(out_hits_host, n);
+    const auto ids = d.output(out_instance_host, n);
+    rc = d.stage(ctx, entry);
+    if (rc != BLOK_OK) return rc;
+    rc = blok_hip_trace_rays_posed_device(ctx, d.at(rays), n, d.at(inst), n_instances, d.at(poses), n_poses, d.at(hits), d.wanted(ids), nullptr);
+    return d.collect(ctx, entry, rc);
+}
+
 }  // namespace
 
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) { return check_table(ctx, inst, n); }
 
 int refuse_scaled_model(blok_hip_ctx* ctx, const char* op, uint32_t model) {
-    if (model < ctx->models.desc.size() && ctx->models.desc[model].nodes && ctx->models.desc[model].scale_log2 != 0u)
+    if (known_model(ctx, model) && ctx->models.desc[model].scale_log2 != 0u)
         return set_error(ctx, BLOK_ERR_UNSUPPORTED, std::string(op) + ": model " + std::to_string(model) + " has a scale (blok_hip_model_set_scale); the volume takes scale-0 models only");
     return BLOK_OK;
 }
@@ -200,8 +308,7 @@ int blok_hip_model_create(blok_hip_ctx* ctx, const int32_t* xyz, const uint32_t*
 
 int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());           // frames in flight may still walk it
     ctx->models.own[model] = blok_hip_ctx::Models::Arrays{};
@@ -211,8 +318,7 @@ int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
 
 int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_log2) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     if (scale_log2 > blok::kMaxScaleLog2)
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_set_scale: scale_log2 above " + std::to_string(blok::kMaxScaleLog2));
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -231,8 +337,7 @@ int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_l
 
 int blok_hip_model_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t* out_scale_log2) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     if (!out_scale_log2) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_scale: null output");
     *out_scale_log2 = ctx->models.desc[model].scale_log2;
     return BLOK_OK;
@@ -246,37 +351,25 @@ int blok_hip_check_instances(blok_hip_ctx* ctx, const blok_instance* instances_h
 int blok_hip_trace_primary_instanced_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                             const blok_instance* instances_dev, uint32_t n_instances,
                                             void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, void* hip_stream) {
-    int rc = check_trace(ctx, cam);
+    int rc = check_frame(ctx, cam, x0, y0, w, h, out_hits_dev || out_rgba_dev || out_instance_dev, instances_dev, n_instances, nullptr, 0u);
     if (rc != BLOK_OK) return rc;
-    if ((!out_hits_dev && !out_rgba_dev && !out_instance_dev) || !rect_inside(ctx, x0, y0, w, h))
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
-    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const size_t n_pixels = static_cast<size_t>(w) * h;
-    blok_hit* hits = static_cast<blok_hit*>(out_hits_dev);
-    if (n_instances && !hits) {                          // the instance pass needs the world records
-        auto& sc = ctx->beam_buffers[stream];
-        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n_pixels, blok::FreeAfter::work_on(stream)));
-        hits = sc.inst_hits;
+    blok::InstanceArgs P{};
+    P.hits = static_cast<blok_hit*>(out_hits_dev);
+    if (n_instances) {                                   // (the instance pass needs the world records)
+        rc = frame_pass(ctx, cam, x0, y0, w, h, stream, ctx->beam_buffers[stream].inst_bins, out_hits_dev, out_rgba_dev, out_instance_dev, P);
+        if (rc != BLOK_OK) return rc;
     }
     // the world pass: blok_hip_trace_primary_device's launch, unchanged
-    if (hits || out_rgba_dev) {
-        rc = blok_hip_trace_primary_device(ctx, cam, x0, y0, w, h, hits, out_rgba_dev, hip_stream);
+    if (P.hits || out_rgba_dev) {
+        rc = blok_hip_trace_primary_device(ctx, cam, x0, y0, w, h, P.hits, out_rgba_dev, hip_stream);
         if (rc != BLOK_OK) return rc;
     }
     if (!n_instances) {
-        if (out_instance_dev) BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, n_pixels * sizeof(uint32_t), stream));
+        if (out_instance_dev) BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, static_cast<size_t>(w) * h * sizeof(uint32_t), stream));
         return BLOK_OK;
     }
-    blok::TraceArgs world = base_args(ctx, cam);
-    world.x0 = x0; world.y0 = y0; world.w = w; world.h = h;
-    blok::InstanceArgs P = instance_args(ctx, world, instances_dev, n_instances, hits, static_cast<uint32_t*>(out_rgba_dev), out_instance_dev);
-    P.bins_x = (w + blok::kBinPixels - 1u) / blok::kBinPixels;
-    P.bins_y = (h + blok::kBinPixels - 1u) / blok::kBinPixels;
-    P.view = bin_view(ctx, *cam);
-    auto& sc = ctx->beam_buffers[stream];
-    BLOK_HIP_TRY(ctx, sc.inst_bins.reserve(static_cast<size_t>(P.bins_x) * P.bins_y * blok::kBinWords, blok::FreeAfter::work_on(stream)));
-    P.bins = sc.inst_bins;
+    P.instances = instances_dev; P.n_instances = n_instances;
     blok::launch_instance_bins(P, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
     blok::launch_instance_pass(P, stream);
@@ -287,97 +380,42 @@ int blok_hip_trace_primary_instanced_device(blok_hip_ctx* ctx, const blok_camera
 int blok_hip_trace_primary_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                      const blok_instance* instances_host, uint32_t n_instances,
                                      blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host) {
-    int rc = check_trace(ctx, cam);
-    if (rc != BLOK_OK) return rc;
-    if ((!out_hits_host && !out_rgba_host && !out_instance_host) || !rect_inside(ctx, x0, y0, w, h))
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
-    rc = check_table(ctx, instances_host, n_instances);
-    if (rc != BLOK_OK) return rc;
-    const size_t n = static_cast<size_t>(w) * h;
-    // one device block: instances, records, RGBA8, ids
-    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
-    const size_t bytes = inst_bytes + n * (sizeof(blok_hit) + 2u * sizeof(uint32_t));
-    blok::DeviceArray<unsigned char> d;
-    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
-    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
-    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d + inst_bytes);
-    uint32_t* d_rgba = reinterpret_cast<uint32_t*>(d_hits + n);
-    uint32_t* d_ids = d_rgba + n;
-    hipError_t e = n_instances ? hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess) {
-        rc = blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, d_inst, n_instances, d_hits, out_rgba_host ? d_rgba : nullptr,
-                                                     out_instance_host ? d_ids : nullptr, nullptr);
-        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_rgba_host) e = hipMemcpy(out_rgba_host, d_rgba, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc != BLOK_OK) return rc;
-    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_primary_instanced: ") + hipGetErrorString(e));
-    return BLOK_OK;
+    return trace_primary_placed(ctx, "trace_primary_instanced", cam, x0, y0, w, h, instances_host, n_instances, nullptr, 0u, out_hits_host, out_rgba_host,
+                                out_instance_host);
 }
 
 int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev,
                                          uint32_t n_instances, blok_hit* out_hits_dev, uint32_t* out_instance_dev, void* hip_stream) {
-    if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
-    if (n == 0) return BLOK_OK;
-    if (!rays_dev || (!out_hits_dev && !out_instance_dev) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
-    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    int rc = check_rays(ctx, rays_dev, n, out_hits_dev || out_instance_dev);
+    if (rc != BLOK_OK || n == 0) return rc;
+    rc = check_device_tables(ctx, instances_dev, n_instances, nullptr, 0u);
+    if (rc != BLOK_OK) return rc;
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     if (!n_instances && !out_hits_dev) {
         BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, n * sizeof(uint32_t), stream));
         return BLOK_OK;
     }
-    blok_hit* hits = out_hits_dev;
-    if (!hits) {
-        auto& sc = ctx->beam_buffers[stream];
-        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n, blok::FreeAfter::work_on(stream)));
-        hits = sc.inst_hits;
-    }
-    blok::TraceArgs world = base_args(ctx, nullptr);
-    world.rays = rays_dev; world.n_rays = static_cast<uint32_t>(n); world.out = hits;
-    int rc = launch_timed(ctx, blok::RayMode::Rays, world, static_cast<uint32_t>((n + blok::kBlock - 1) / blok::kBlock), stream);
+    blok::InstanceArgs P{};
+    rc = rays_pass(ctx, rays_dev, n, stream, out_hits_dev, out_instance_dev, P);
+    if (rc != BLOK_OK) return rc;
+    blok::TraceArgs world = P.world;
+    world.out = P.hits;
+    rc = launch_timed(ctx, blok::RayMode::Rays, world, static_cast<uint32_t>((n + blok::kBlock - 1) / blok::kBlock), stream);
     if (rc != BLOK_OK) return rc;
     if (!n_instances) {
         if (out_instance_dev) BLOK_HIP_TRY(ctx, hipMemsetAsync(out_instance_dev, 0xFF, n * sizeof(uint32_t), stream));
         return BLOK_OK;
     }
-    world.out = nullptr;
-    blok::launch_instance_rays(instance_args(ctx, world, instances_dev, n_instances, hits, nullptr, out_instance_dev), stream);
+    P.instances = instances_dev; P.n_instances = n_instances;
+    blok::launch_instance_rays(P, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
     return BLOK_OK;
 }
 
 int blok_hip_trace_rays_instanced(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, const blok_instance* instances_host,
                                   uint32_t n_instances, blok_hit* out_hits_host, uint32_t* out_instance_host) {
-    if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
-    if (n == 0) return BLOK_OK;
-    if (!rays_host || (!out_hits_host && !out_instance_host) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
-    int rc = check_table(ctx, instances_host, n_instances);
-    if (rc != BLOK_OK) return rc;
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
-    const size_t bytes = inst_bytes + n * (sizeof(blok_ray) + sizeof(blok_hit) + sizeof(uint32_t));
-    blok::DeviceArray<unsigned char> d;
-    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
-    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
-    blok_ray* d_rays = reinterpret_cast<blok_ray*>(d + inst_bytes);
-    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d_rays + n);
-    uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_hits + n);
-    hipError_t e = hipMemcpy(d_rays, rays_host, n * sizeof(blok_ray), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_instances) e = hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = blok_hip_trace_rays_instanced_device(ctx, d_rays, n, d_inst, n_instances, d_hits, out_instance_host ? d_ids : nullptr, nullptr);
-        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc != BLOK_OK) return rc;
-    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays_instanced: ") + hipGetErrorString(e));
-    return BLOK_OK;
+    return trace_rays_placed(ctx, "trace_rays_instanced", rays_host, n, instances_host, n_instances, nullptr, 0u, out_hits_host, out_instance_host);
 }
 
 // ---- posed models (posed_core.h): the instanced entries, then the pose pass on the same stream ---------------------------------------------
@@ -389,35 +427,17 @@ int blok_hip_check_poses(blok_hip_ctx* ctx, const blok_pose* poses_host, uint32_
 int blok_hip_trace_primary_posed_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                         const blok_instance* instances_dev, uint32_t n_instances, const blok_pose* poses_dev, uint32_t n_poses,
                                         void* out_hits_dev, void* out_rgba_dev, uint32_t* out_instance_dev, void* hip_stream) {
-    int rc = check_trace(ctx, cam);
+    int rc = check_frame(ctx, cam, x0, y0, w, h, out_hits_dev || out_rgba_dev || out_instance_dev, instances_dev, n_instances, poses_dev, n_poses);
     if (rc != BLOK_OK) return rc;
-    if ((!out_hits_dev && !out_rgba_dev && !out_instance_dev) || !rect_inside(ctx, x0, y0, w, h))
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
-    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
-    if (n_poses && !poses_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
-    if (n_poses >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
     if (!n_poses)                                        // the instanced entry itself: the same launches, the same bytes
         return blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, instances_dev, n_instances, out_hits_dev, out_rgba_dev, out_instance_dev, hip_stream);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const size_t n_pixels = static_cast<size_t>(w) * h;
-    blok_hit* hits = static_cast<blok_hit*>(out_hits_dev);
-    auto& sc = ctx->beam_buffers[stream];
-    if (!hits) {                                         // the pose pass needs the composed records
-        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n_pixels, blok::FreeAfter::work_on(stream)));
-        hits = sc.inst_hits;
-    }
-    rc = blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, instances_dev, n_instances, hits, out_rgba_dev, out_instance_dev, hip_stream);
+    blok::PosedArgs Q{};                                 // (the pose pass needs the composed records)
+    rc = frame_pass(ctx, cam, x0, y0, w, h, stream, ctx->beam_buffers[stream].pose_bins, out_hits_dev, out_rgba_dev, out_instance_dev, Q.frame);
     if (rc != BLOK_OK) return rc;
-    blok::TraceArgs world = base_args(ctx, cam);
-    world.x0 = x0; world.y0 = y0; world.w = w; world.h = h;
-    blok::PosedArgs Q{};
-    Q.frame = instance_args(ctx, world, nullptr, 0u, hits, static_cast<uint32_t*>(out_rgba_dev), out_instance_dev);
+    rc = blok_hip_trace_primary_instanced_device(ctx, cam, x0, y0, w, h, instances_dev, n_instances, Q.frame.hits, out_rgba_dev, out_instance_dev, hip_stream);
+    if (rc != BLOK_OK) return rc;
     Q.poses = poses_dev; Q.n_poses = n_poses;
-    Q.frame.bins_x = (w + blok::kBinPixels - 1u) / blok::kBinPixels;
-    Q.frame.bins_y = (h + blok::kBinPixels - 1u) / blok::kBinPixels;
-    Q.frame.view = bin_view(ctx, *cam);
-    BLOK_HIP_TRY(ctx, sc.pose_bins.reserve(static_cast<size_t>(Q.frame.bins_x) * Q.frame.bins_y * blok::kBinWords, blok::FreeAfter::work_on(stream)));
-    Q.frame.bins = sc.pose_bins;
     blok::launch_posed_bins(Q, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
     blok::launch_posed_pass(Q, stream);
@@ -428,65 +448,25 @@ int blok_hip_trace_primary_posed_device(blok_hip_ctx* ctx, const blok_camera* ca
 int blok_hip_trace_primary_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                                  const blok_instance* instances_host, uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses,
                                  blok_hit* out_hits_host, uint32_t* out_rgba_host, uint32_t* out_instance_host) {
-    int rc = check_trace(ctx, cam);
-    if (rc != BLOK_OK) return rc;
-    if ((!out_hits_host && !out_rgba_host && !out_instance_host) || !rect_inside(ctx, x0, y0, w, h))
-        return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame or no output");
-    rc = check_table(ctx, instances_host, n_instances);
-    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
-    if (rc != BLOK_OK) return rc;
-    const size_t n = static_cast<size_t>(w) * h;
-    // one device block: instances, poses, records, RGBA8, ids
-    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
-    const size_t pose_bytes = (static_cast<size_t>(n_poses) * sizeof(blok_pose) + 255u) / 256u * 256u;
-    const size_t bytes = inst_bytes + pose_bytes + n * (sizeof(blok_hit) + 2u * sizeof(uint32_t));
-    blok::DeviceArray<unsigned char> d;
-    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
-    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
-    blok_pose* d_pose = reinterpret_cast<blok_pose*>(d + inst_bytes);
-    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d + inst_bytes + pose_bytes);
-    uint32_t* d_rgba = reinterpret_cast<uint32_t*>(d_hits + n);
-    uint32_t* d_ids = d_rgba + n;
-    hipError_t e = n_instances ? hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess && n_poses) e = hipMemcpy(d_pose, poses_host, n_poses * sizeof(blok_pose), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = blok_hip_trace_primary_posed_device(ctx, cam, x0, y0, w, h, d_inst, n_instances, d_pose, n_poses, d_hits, out_rgba_host ? d_rgba : nullptr,
-                                                 out_instance_host ? d_ids : nullptr, nullptr);
-        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_rgba_host) e = hipMemcpy(out_rgba_host, d_rgba, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc != BLOK_OK) return rc;
-    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_primary_posed: ") + hipGetErrorString(e));
-    return BLOK_OK;
+    return trace_primary_placed(ctx, "trace_primary_posed", cam, x0, y0, w, h, instances_host, n_instances, poses_host, n_poses, out_hits_host,
+                                out_rgba_host, out_instance_host);
 }
 
 int blok_hip_trace_rays_posed_device(blok_hip_ctx* ctx, const blok_ray* rays_dev, size_t n, const blok_instance* instances_dev, uint32_t n_instances,
                                      const blok_pose* poses_dev, uint32_t n_poses, blok_hit* out_hits_dev, uint32_t* out_instance_dev,
                                      void* hip_stream) {
-    if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
-    if (n == 0) return BLOK_OK;
-    if (!rays_dev || (!out_hits_dev && !out_instance_dev) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
-    if (n_instances && !instances_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
-    if (n_poses && !poses_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
-    if (n_poses >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
+    int rc = check_rays(ctx, rays_dev, n, out_hits_dev || out_instance_dev);
+    if (rc != BLOK_OK || n == 0) return rc;
+    rc = check_device_tables(ctx, instances_dev, n_instances, poses_dev, n_poses);
+    if (rc != BLOK_OK) return rc;
     if (!n_poses) return blok_hip_trace_rays_instanced_device(ctx, rays_dev, n, instances_dev, n_instances, out_hits_dev, out_instance_dev, hip_stream);
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    blok_hit* hits = out_hits_dev;
-    if (!hits) {
-        auto& sc = ctx->beam_buffers[stream];
-        BLOK_HIP_TRY(ctx, sc.inst_hits.reserve(n, blok::FreeAfter::work_on(stream)));
-        hits = sc.inst_hits;
-    }
-    int rc = blok_hip_trace_rays_instanced_device(ctx, rays_dev, n, instances_dev, n_instances, hits, out_instance_dev, hip_stream);
-    if (rc != BLOK_OK) return rc;
-    blok::TraceArgs world = base_args(ctx, nullptr);
-    world.rays = rays_dev; world.n_rays = static_cast<uint32_t>(n);
     blok::PosedArgs Q{};
-    Q.frame = instance_args(ctx, world, nullptr, 0u, hits, nullptr, out_instance_dev);
+    rc = rays_pass(ctx, rays_dev, n, stream, out_hits_dev, out_instance_dev, Q.frame);
+    if (rc != BLOK_OK) return rc;
+    rc = blok_hip_trace_rays_instanced_device(ctx, rays_dev, n, instances_dev, n_instances, Q.frame.hits, out_instance_dev, hip_stream);
+    if (rc != BLOK_OK) return rc;
     Q.poses = poses_dev; Q.n_poses = n_poses;
     blok::launch_posed_rays(Q, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
@@ -495,36 +475,7 @@ int blok_hip_trace_rays_posed_device(blok_hip_ctx* ctx, const blok_ray* rays_dev
 
 int blok_hip_trace_rays_posed(blok_hip_ctx* ctx, const blok_ray* rays_host, size_t n, const blok_instance* instances_host, uint32_t n_instances,
                               const blok_pose* poses_host, uint32_t n_poses, blok_hit* out_hits_host, uint32_t* out_instance_host) {
-    if (!ctx) return BLOK_ERR_INVALID_ARG;
-    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "no world uploaded");
-    if (n == 0) return BLOK_OK;
-    if (!rays_host || (!out_hits_host && !out_instance_host) || n > 0x7FFFFFFFu) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad ray arguments");
-    int rc = check_table(ctx, instances_host, n_instances);
-    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
-    if (rc != BLOK_OK) return rc;
-    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
-    const size_t pose_bytes = (static_cast<size_t>(n_poses) * sizeof(blok_pose) + 255u) / 256u * 256u;
-    const size_t bytes = inst_bytes + pose_bytes + n * (sizeof(blok_ray) + sizeof(blok_hit) + sizeof(uint32_t));
-    blok::DeviceArray<unsigned char> d;
-    BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
-    blok_instance* d_inst = reinterpret_cast<blok_instance*>(d.get());
-    blok_pose* d_pose = reinterpret_cast<blok_pose*>(d + inst_bytes);
-    blok_ray* d_rays = reinterpret_cast<blok_ray*>(d + inst_bytes + pose_bytes);
-    blok_hit* d_hits = reinterpret_cast<blok_hit*>(d_rays + n);
-    uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_hits + n);
-    hipError_t e = hipMemcpy(d_rays, rays_host, n * sizeof(blok_ray), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_instances) e = hipMemcpy(d_inst, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_poses) e = hipMemcpy(d_pose, poses_host, n_poses * sizeof(blok_pose), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = blok_hip_trace_rays_posed_device(ctx, d_rays, n, d_inst, n_instances, d_pose, n_poses, d_hits, out_instance_host ? d_ids : nullptr, nullptr);
-        if (rc == BLOK_OK && out_hits_host) e = hipMemcpy(out_hits_host, d_hits, n * sizeof(blok_hit), hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc != BLOK_OK) return rc;
-    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("trace_rays_posed: ") + hipGetErrorString(e));
-    return BLOK_OK;
+    return trace_rays_placed(ctx, "trace_rays_posed", rays_host, n, instances_host, n_instances, poses_host, n_poses, out_hits_host, out_instance_host);
 }
 
 // ---- path-traced frames with instances (tlas_core.h) ----------------------------------------------------------------------------
@@ -568,28 +519,19 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
     if (!rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame");
     rc = check_table(ctx, instances_host, n_instances);
     if (rc != BLOK_OK) return rc;
-    const size_t n = static_cast<size_t>(w) * h, plane_bytes = n * 4 * sizeof(float);
-    // one device block: instances, four planes, ids
-    const size_t inst_bytes = (static_cast<size_t>(n_instances) * sizeof(blok_instance) + 255u) / 256u * 256u;
-    blok::DeviceArray<unsigned char> d;
-    BLOK_HIP_TRY(ctx, d.reserve(inst_bytes + 4 * plane_bytes + n * sizeof(uint32_t), blok::FreeAfter::nothing()));
-    float* host[4] = {planes_host->color, planes_host->world_pos, planes_host->normal_roughness, planes_host->albedo_metallic};
-    float* dev[4];
-    for (int i = 0; i < 4; ++i) dev[i] = host[i] ? reinterpret_cast<float*>(d + inst_bytes + i * plane_bytes) : nullptr;
-    uint32_t* d_ids = reinterpret_cast<uint32_t*>(d + inst_bytes + 4 * plane_bytes);
-    hipError_t e = n_instances ? hipMemcpy(d, instances_host, n_instances * sizeof(blok_instance), hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess) {
-        const blok_gbuffer planes_dev{dev[0], dev[1], dev[2], dev[3]};
-        rc = blok_hip_trace_paths_instanced_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, reinterpret_cast<const blok_instance*>(d.get()),
-                                                   n_instances, &planes_dev, out_instance_host ? d_ids : nullptr, nullptr);
-        for (int i = 0; i < 4 && rc == BLOK_OK && e == hipSuccess; ++i)
-            if (host[i]) e = hipMemcpy(host[i], dev[i], plane_bytes, hipMemcpyDeviceToHost);
-        if (rc == BLOK_OK && e == hipSuccess && out_instance_host) e = hipMemcpy(out_instance_host, d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    const size_t n = static_cast<size_t>(w) * h;
+    float* const host[4] = {planes_host->color, planes_host->world_pos, planes_host->normal_roughness, planes_host->albedo_metallic};
+    StagedBlock d;
+    const auto inst = d.input(instances_host, n_instances);
+    StagedBlock::Seg<float> plane[4];
+    for (int i = 0; i < 4; ++i) plane[i] = d.output(host[i], n * 4);
+    const auto ids = d.output(out_instance_host, n);
+    rc = d.stage(ctx, "trace_paths_instanced");
     if (rc != BLOK_OK) return rc;
-    if (e != hipSuccess) return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string("trace_paths_instanced: ") + hipGetErrorString(e));
-    return BLOK_OK;
+    const blok_gbuffer planes_dev{d.wanted(plane[0]), d.wanted(plane[1]), d.wanted(plane[2]), d.wanted(plane[3])};
+    rc = blok_hip_trace_paths_instanced_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, d.at(inst), n_instances, &planes_dev, d.wanted(ids),
+                                               nullptr);
+    return d.collect(ctx, "trace_paths_instanced", rc);
 }
 
 // ---- object motion of moving instances (instance_motion.h) -----------------------------------------------------------------------

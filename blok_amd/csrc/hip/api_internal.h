@@ -300,6 +300,51 @@ int set_error(blok_hip_ctx* ctx, int status, const std::string& msg);
         }                                                                                          \
     } while (0)
 
+// The one device block of a blocking entry, staged: the entry names its segments (each starts on a 256-byte boundary), stage() allocates
+// the block once and uploads the non-empty inputs, the entry makes its device call with at() / wanted(), and collect() downloads the
+// outputs the host asked for, synchronises the device and names a HIP failure after the entry.  The block is freed with the object.
+class StagedBlock {
+public:
+    template <class T> struct Seg { size_t part; };
+    template <class T> Seg<T> input(const T* host, size_t count) { return {add(count * sizeof(T), host, nullptr)}; }
+    template <class T> Seg<T> output(T* host, size_t count) { return {add(count * sizeof(T), nullptr, host)}; }       // host may be null
+    template <class T> Seg<T> scratch(size_t count) { return {add(count * sizeof(T), nullptr, nullptr)}; }
+    template <class T> T* at(Seg<T> s) const { return reinterpret_cast<T*>(d.get() + parts_[s.part].offset); }
+    // ... of an output: null where the host asked for none
+    template <class T> T* wanted(Seg<T> s) const { return parts_[s.part].down ? at(s) : nullptr; }
+
+    int stage(blok_hip_ctx* ctx, const char* entry) {
+        size_t bytes = 0;
+        for (Part& p : parts_) { p.offset = bytes; bytes += (p.bytes + 255u) / 256u * 256u; }
+        BLOK_HIP_TRY(ctx, d.reserve(bytes, blok::FreeAfter::nothing()));
+        hipError_t e = hipSuccess;
+        for (const Part& p : parts_)
+            if (e == hipSuccess && p.up && p.bytes) e = hipMemcpy(d + p.offset, p.up, p.bytes, hipMemcpyHostToDevice);
+        return report(ctx, entry, e);
+    }
+    // rc: what the device call returned.  Its failure wins over a HIP failure here; the device is synchronised either way.
+    int collect(blok_hip_ctx* ctx, const char* entry, int rc) {
+        hipError_t e = hipSuccess;
+        for (const Part& p : parts_)
+            if (rc == BLOK_OK && e == hipSuccess && p.down) e = hipMemcpy(p.down, d + p.offset, p.bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        return rc != BLOK_OK ? rc : report(ctx, entry, e);
+    }
+
+private:
+    struct Part { size_t offset, bytes; const void* up; void* down; };
+    size_t add(size_t bytes, const void* up, void* down) { parts_.push_back(Part{0, bytes, up, down}); return parts_.size() - 1; }
+    static int report(blok_hip_ctx* ctx, const char* entry, hipError_t e) {
+        if (e == hipSuccess) return BLOK_OK;
+        return set_error(ctx, e == hipErrorOutOfMemory ? BLOK_ERR_OOM : BLOK_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+    }
+    std::vector<Part> parts_;
+    blok::DeviceArray<unsigned char> d;
+};
+
+// Is `model` the id of a live model of the context's store?
+inline bool known_model(const blok_hip_ctx* ctx, uint32_t model) { return model < ctx->models.desc.size() && ctx->models.desc[model].nodes; }
+
 void free_world(blok_hip_ctx* ctx);
 void adopt_tree(blok_hip_ctx* ctx, const blok::GpuTree& gpu);
 int install_materials(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials);

@@ -303,7 +303,7 @@ int blok_hip_volume_stamp_affine(blok_hip_ctx* ctx, const blok_affine* table_hos
     std::vector<blok::StampModel> models(n);
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t model = table_host[i].model;
-        if (model >= ctx->models.desc.size() || !ctx->models.desc[model].nodes)
+        if (!known_model(ctx, model))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: record " + std::to_string(i) + ": unknown model " + std::to_string(model));
         if (const int rule = blok::affine::well_formed(table_host[i], v.origin, dims))
             return set_error(ctx, BLOK_ERR_INVALID_ARG, "stamp_affine: record " + std::to_string(i) + ": " + blok::affine::rule_text(rule));

@@ -1,4 +1,5 @@
-// Instanced voxel models (include/blok_hip.h: blok_instance): the device math of the instance kernels (instance_kernels.hip).
+// Instanced voxel models (include/blok_hip.h: blok_instance): the device math of the instance kernels (placed_kernels.hip over
+// LatticeKind, at the end of this file) and of the path kernel's instance leaves (tlas_core.h).
 //
 // An instance places a model — its own 64-tree in its own local lattice — at a lattice offset with an axis-aligned orientation (a
 // signed permutation of the axes).  Such a transform moves a ray into local space with ONE rounding per axis (the subtraction of the
@@ -170,7 +171,8 @@ BLOK_DEV uint4 instance_record(const blok_instance& I, const HitInfo& h, uint32_
 inline uint4 instance_record(const blok_instance& I, const HitInfo& h) { return instance_record(I, h, 0u); }
 #endif
 
-// One candidate: the instance's walk of world ray r with tmax = best_t.  true (and rec) iff it reports a voxel, whose t is then < best_t.
+// One candidate of the path kernel's leaves (tlas_core.h): the instance's walk of world ray r with tmax = best_t.  true (and rec) iff it
+// reports a voxel, whose t is then < best_t.  (The primary frame's candidate, with its wave-uniform descriptor, is placed_candidate below.)
 BLOK_DEV bool instance_candidate(const blok_instance& I, const ModelDesc& M, float vs, float inv_vs, const RayIn& r, float best_t,
                                  uint4* stk, uint4& rec) {
     RayIn l = instance_ray(I, vs, r);
@@ -223,7 +225,7 @@ BLOK_DEV bool project_box(const BinView& V, const float lo[3], const float hi[3]
     return true;
 }
 
-// Arguments of the three instance kernels (instance_kernels.hip).  Bins: one per kBinPixels x kBinPixels pixels of the launch rectangle,
+// Arguments of the three instance kernels (placed_kernels.hip).  Bins: one per kBinPixels x kBinPixels pixels of the launch rectangle,
 // kBinWords words each: word 0 = the number of instances listed (kBinOverflow: more than kBinCapacity, the bin's pixels test every
 // instance), then the instance indices in ascending order.
 constexpr uint32_t kBinPixels = 32, kBinWords = 64, kBinCapacity = kBinWords - 1, kBinOverflow = 0xFFFFFFFFu;
@@ -241,6 +243,60 @@ struct InstanceArgs {
     uint32_t* ids;                       // may be null: the winning instance per pixel / ray, kInstanceNone for the world or a miss
     uint32_t stack_levels;               // LDS stack slots per lane: the deepest live model's levels - 1 (>= 1)
 };
+
+// ---- placed models: what the lattice instances and the poses (posed_core.h) share ------------------------------------------------------------
+// Both place a model's own tree in the world, take a world ray into the model's local space, walk it there with tmax = the best t so far
+// and compose the record; the kernels (placed_kernels.hip) and the host shims (tests/host_harness) state that once, over a KIND.
+// A kind is a struct of static functions holding the six things in which the two differ, and nothing else:
+//   1. Record / Args, table, count, frame   the record type and where its table lives in the kernels' arguments
+//   2. usable                               what the kernels make of a record and its model (the others are skipped)
+//   3. local_ray                            world ray -> local ray; false: the ray does not enter (a non-finite component)
+//   4. world_box                            the world box the screen bins project; false: the record may cover anything
+//   5. Hit, record                          a local hit as the composed record, and the world face shade_rgba takes for it
+//   6. owns_ids, id_tag                     who owns the id plane: the lattice pass writes every pixel it visits (kInstanceNone where no
+//                                           instance wins), the posed pass only the pixels a pose wins, as BLOK_POSE_ID | index
+// Each kind stands behind its own math: LatticeKind here, PoseKind in posed_core.h.
+struct LatticeKind {
+    using Record = blok_instance;
+    using Args = InstanceArgs;
+    static BLOK_DEV const InstanceArgs& frame(const Args& a) { return a; }
+    static BLOK_DEV const Record* table(const Args& a) { return a.instances; }
+    static BLOK_DEV uint32_t count(const Args& a) { return a.n_instances; }
+    static BLOK_DEV bool usable(const Record& I, const ModelDesc& M) { return instance_usable(I, M); }
+    static BLOK_DEV bool local_ray(const Record& I, float vs, const RayIn& r, RayIn& l) { l = instance_ray(I, vs, r); return true; }
+    static BLOK_DEV bool world_box(const Record& I, const ModelDesc& M, float vs, const float*, float flo[3], float fhi[3]) {
+        for (uint32_t a = 0; a < 3u; ++a) {
+            int64_t lo, hi;
+            instance_world_span(I, M, a, lo, hi);
+            flo[a] = static_cast<float>(lo) * vs; fhi[a] = static_cast<float>(hi) * vs;
+        }
+        return true;
+    }
+    struct Hit {
+        uint4 rec{};
+        BLOK_DEV uint32_t shade_face() const { return (rec.w >> 16) & 0xFFu; }       // the record's face is a world face
+    };
+    static BLOK_DEV Hit record(const Record& I, const ModelDesc& M, const HitInfo& h) { return Hit{instance_record(I, h, M.scale_log2)}; }
+    static constexpr bool owns_ids = true;
+    static constexpr uint32_t id_tag = 0u;
+};
+
+// One candidate on the host: the record's walk of world ray r with tmax = best_t; true iff it reports a voxel, whose t is then < best_t
+// (hit and best_t are then the candidate's).  The body of the kernels' loop (placed_kernels.hip: compose) from the same kind functions,
+// without the wave: there a candidate that no lane's ray enters is skipped by one ballot, and that skip is all the host does not run.
+template <class K>
+BLOK_DEV bool placed_candidate(const typename K::Record& S, const ModelDesc& M, float vs, float inv_vs, const RayIn& r, float& best_t, uint4* stk,
+                               typename K::Hit& hit) {
+    RayIn l;
+    const bool finite = K::local_ray(S, vs, r, l);
+    l.tmax = best_t;
+    if (!finite || !instance_box_entered(M, vs, l)) return false;
+    const HitInfo h = walk(model_args(M, vs, inv_vs), l, stk);
+    if (!h.found) return false;
+    hit = K::record(S, M, h);
+    best_t = h.t;
+    return true;
+}
 
 #ifndef BLOK_TRACE_HOST_HARNESS
 void launch_instance_bins(const InstanceArgs& args, hipStream_t stream);

@@ -1,4 +1,5 @@
-// Posed models (include/blok_hip.h: blok_pose, "Posed models"): the device math of the posed kernels (posed_kernels.hip).
+// Posed models (include/blok_hip.h: blok_pose, "Posed models"): the device math of the posed kernels (placed_kernels.hip over
+// PoseKind, at the end of this file).
 //
 // A pose places a model under any affine map.  The ray goes into local space by the rule below, every operation rounded separately
 // (the units are built with -ffp-contract=off), the local walk is the canonical walk of trace_core.h at the model's own voxel size, and
@@ -101,18 +102,6 @@ BLOK_DEV uint32_t pose_shade_face(const blok_pose& P, uint32_t face) {
     return z < 0.0f ? 5u : 4u;
 }
 
-// One candidate: the pose's walk of world ray r with tmax = best_t.  true (and rec) iff it reports a voxel, whose t is then < best_t.
-BLOK_DEV bool pose_candidate(const blok_pose& P, const ModelDesc& M, float vs, float inv_vs, const RayIn& r, float best_t, uint4* stk, uint4& rec) {
-    RayIn l;
-    if (!pose_ray(P, r, l)) return false;
-    l.tmax = best_t;
-    if (!instance_box_entered(M, vs, l)) return false;
-    const HitInfo h = walk(model_args(M, vs, inv_vs), l, stk);
-    if (!h.found) return false;
-    rec = pose_record(h);
-    return true;
-}
-
 // The world box [flo, fhi] (world units) that holds every world point a ray can have where the pose's walk reports a voxel, for a camera at
 // `cam`: the margin argument at the head of this file.  false: the pose may cover anything (a degenerate m, a non-finite result).
 BLOK_DEV bool pose_world_box(const blok_pose& P, const ModelDesc& M, float vs, const float cam[3], float flo[3], float fhi[3]) {
@@ -169,13 +158,46 @@ BLOK_DEV bool pose_world_box(const blok_pose& P, const ModelDesc& M, float vs, c
     return pose::finite(flo[0]) && pose::finite(flo[1]) && pose::finite(flo[2]) && pose::finite(fhi[0]) && pose::finite(fhi[1]) && pose::finite(fhi[2]);
 }
 
-// Arguments of the three posed kernels (posed_kernels.hip): the instance kernels' (frame, bins, view, model store, outputs, LDS stack; its
+// Arguments of the three posed kernels (placed_kernels.hip): the instance kernels' (frame, bins, view, model store, outputs, LDS stack; its
 // instance table unused) and the pose table.  The bins are the posed pass's own (per-stream scratch), laid out as the instance bins are.
 struct PosedArgs {
     InstanceArgs frame;
     const blok_pose* poses;              // device memory, n_poses records
     uint32_t n_poses;
 };
+
+// The poses as a kind of placed model (instance_core.h: what a kind is).
+struct PoseKind {
+    using Record = blok_pose;
+    using Args = PosedArgs;
+    static BLOK_DEV const InstanceArgs& frame(const Args& a) { return a.frame; }
+    static BLOK_DEV const Record* table(const Args& a) { return a.poses; }
+    static BLOK_DEV uint32_t count(const Args& a) { return a.n_poses; }
+    static BLOK_DEV bool usable(const Record& S, const ModelDesc& M) { return pose_usable(S, M); }
+    static BLOK_DEV bool local_ray(const Record& S, float, const RayIn& r, RayIn& l) { return pose_ray(S, r, l); }
+    static BLOK_DEV bool world_box(const Record& S, const ModelDesc& M, float vs, const float cam[3], float flo[3], float fhi[3]) {
+        return pose_world_box(S, M, vs, cam, flo, fhi);
+    }
+    struct Hit {
+        uint4 rec{};
+        uint32_t face = 0u;                                                           // the record's face is the model's own
+        BLOK_DEV uint32_t shade_face() const { return face; }
+    };
+    static BLOK_DEV Hit record(const Record& S, const ModelDesc&, const HitInfo& h) { return Hit{pose_record(h), pose_shade_face(S, h.face)}; }
+    static constexpr bool owns_ids = false;
+    static constexpr uint32_t id_tag = BLOK_POSE_ID;
+};
+
+#ifdef BLOK_TRACE_HOST_HARNESS
+// One pose's candidate as a plain function, as instance_candidate is one instance's: true (and rec) iff the walk of r with tmax = best_t
+// reports a voxel.  For host harnesses that want no kind.
+inline bool pose_candidate(const blok_pose& P, const ModelDesc& M, float vs, float inv_vs, const RayIn& r, float best_t, uint4* stk, uint4& rec) {
+    PoseKind::Hit hit;
+    if (!placed_candidate<PoseKind>(P, M, vs, inv_vs, r, best_t, stk, hit)) return false;
+    rec = hit.rec;
+    return true;
+}
+#endif
 
 #ifndef BLOK_TRACE_HOST_HARNESS
 void launch_posed_bins(const PosedArgs& args, hipStream_t stream);

@@ -961,15 +961,27 @@ class HipTracer:
         inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
         self._check(self._lib.blok_hip_check_instances(self._ctx, _ffi.ptr(inst), len(inst)))
 
-    def trace_primary_instanced(self, cam: np.ndarray, instances: np.ndarray, rect=None):
-        """(hits (h, w), instance ids (h, w), RGBA8 (h, w)) of the frame (or rect) over the world plus `instances` (INSTANCE records)."""
+    def _placed_frame(self, cam: np.ndarray, instances, rect):
+        """What the blocking primary frames over placed models prepare alike: the rectangle, the camera, the instance table and the outputs."""
         x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
         cam = np.ascontiguousarray(cam, dtype=CAMERA)
-        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
-        hits = np.zeros(w * h, dtype=HIT)
-        ids = np.zeros(w * h, dtype=np.uint32)
-        rgba = np.zeros(w * h, dtype=np.uint32)
-        self._check(self._lib.blok_hip_trace_primary_instanced(self._ctx, _ffi.ptr(cam), x0, y0, w, h, _ffi.ptr(inst), len(inst),
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        return (x0, y0, w, h), cam, inst, np.zeros(w * h, dtype=HIT), np.zeros(w * h, dtype=np.uint32), np.zeros(w * h, dtype=np.uint32)
+
+    def _placed_rays(self, rays: np.ndarray, instances):
+        """... and the blocking rays: the rays, the instance table and the outputs."""
+        rays = np.ascontiguousarray(rays, dtype=RAY)
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        return rays, inst, np.zeros(len(rays), dtype=HIT), np.zeros(len(rays), dtype=np.uint32)
+
+    @staticmethod
+    def _table(records: np.ndarray):
+        return _ffi.ptr(records) if len(records) else None
+
+    def trace_primary_instanced(self, cam: np.ndarray, instances: np.ndarray, rect=None):
+        """(hits (h, w), instance ids (h, w), RGBA8 (h, w)) of the frame (or rect) over the world plus `instances` (INSTANCE records)."""
+        (x0, y0, w, h), cam, inst, hits, ids, rgba = self._placed_frame(cam, instances, rect)
+        self._check(self._lib.blok_hip_trace_primary_instanced(self._ctx, _ffi.ptr(cam), x0, y0, w, h, self._table(inst), len(inst),
                                                                _ffi.ptr(hits), _ffi.ptr(rgba), _ffi.ptr(ids)))
         return hits.reshape(h, w), ids.reshape(h, w), rgba.reshape(h, w)
 
@@ -984,11 +996,8 @@ class HipTracer:
 
     def trace_rays_instanced(self, rays: np.ndarray, instances: np.ndarray):
         """(records, instance ids) of explicit rays over the world plus `instances`."""
-        rays = np.ascontiguousarray(rays, dtype=RAY)
-        inst = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
-        hits = np.zeros(len(rays), dtype=HIT)
-        ids = np.zeros(len(rays), dtype=np.uint32)
-        self._check(self._lib.blok_hip_trace_rays_instanced(self._ctx, _ffi.ptr(rays), len(rays), _ffi.ptr(inst), len(inst),
+        rays, inst, hits, ids = self._placed_rays(rays, instances)
+        self._check(self._lib.blok_hip_trace_rays_instanced(self._ctx, _ffi.ptr(rays), len(rays), self._table(inst), len(inst),
                                                             _ffi.ptr(hits), _ffi.ptr(ids)))
         return hits, ids
 
@@ -1000,15 +1009,10 @@ class HipTracer:
     def trace_primary_posed(self, cam: np.ndarray, instances, poses, rect=None):
         """(hits (h, w), ids (h, w), RGBA8 (h, w)) of the frame (or rect) over the world, `instances` (INSTANCE records) and `poses` (POSE
         records, blok_amd.pose).  A pixel a pose wins has id POSE_ID | index, the pose's local voxel and local face."""
-        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
-        cam = np.ascontiguousarray(cam, dtype=CAMERA)
-        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        (x0, y0, w, h), cam, inst, hits, ids, rgba = self._placed_frame(cam, instances, rect)
         p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
-        hits = np.zeros(w * h, dtype=HIT)
-        ids = np.zeros(w * h, dtype=np.uint32)
-        rgba = np.zeros(w * h, dtype=np.uint32)
-        self._check(self._lib.blok_hip_trace_primary_posed(self._ctx, _ffi.ptr(cam), x0, y0, w, h, _ffi.ptr(inst) if len(inst) else None, len(inst),
-                                                           _ffi.ptr(p) if len(p) else None, len(p), _ffi.ptr(hits), _ffi.ptr(rgba), _ffi.ptr(ids)))
+        self._check(self._lib.blok_hip_trace_primary_posed(self._ctx, _ffi.ptr(cam), x0, y0, w, h, self._table(inst), len(inst),
+                                                           self._table(p), len(p), _ffi.ptr(hits), _ffi.ptr(rgba), _ffi.ptr(ids)))
         return hits.reshape(h, w), ids.reshape(h, w), rgba.reshape(h, w)
 
     def trace_primary_posed_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, poses_ptr: int, n_poses: int, hits_ptr: int = 0,
@@ -1022,13 +1026,10 @@ class HipTracer:
 
     def trace_rays_posed(self, rays: np.ndarray, instances, poses):
         """(records, ids) of explicit rays over the world, `instances` and `poses`: every pose is tested for every ray."""
-        rays = np.ascontiguousarray(rays, dtype=RAY)
-        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        rays, inst, hits, ids = self._placed_rays(rays, instances)
         p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
-        hits = np.zeros(len(rays), dtype=HIT)
-        ids = np.zeros(len(rays), dtype=np.uint32)
-        self._check(self._lib.blok_hip_trace_rays_posed(self._ctx, _ffi.ptr(rays), len(rays), _ffi.ptr(inst) if len(inst) else None, len(inst),
-                                                        _ffi.ptr(p) if len(p) else None, len(p), _ffi.ptr(hits), _ffi.ptr(ids)))
+        self._check(self._lib.blok_hip_trace_rays_posed(self._ctx, _ffi.ptr(rays), len(rays), self._table(inst), len(inst),
+                                                        self._table(p), len(p), _ffi.ptr(hits), _ffi.ptr(ids)))
         return hits, ids
 
     def trace_rays_posed_device(self, rays_ptr: int, n: int, instances_ptr: int, n_instances: int, poses_ptr: int, n_poses: int, hits_ptr: int = 0,

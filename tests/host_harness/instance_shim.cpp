@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: the instance math of the gfx950 kernels (blok_amd/csrc/hip/instance_core.h) with the walk of trace_core.h,
-// compiled for the CPU: one ray at a time, world first, then every instance in order.  Never linked into the shipped libraries.
+// compiled for the CPU: one ray at a time, world first, then every instance in order through the kernels' candidate (placed_candidate).  Never linked into the shipped libraries.
 #define BLOK_TRACE_HOST_HARNESS 1
 #include "instance_core.h"
 #include "reference_world.h"
@@ -88,10 +88,9 @@ void is_compose(const void* world, void* const* models, size_t n_models, const b
             if (inst[j].model >= n_models) continue;
             const ModelDesc& M = static_cast<const Tree*>(models[inst[j].model])->desc;
             if (!instance_usable(inst[j], M)) continue;
-            uint4 rec;
-            if (instance_candidate(inst[j], M, 1.0f, 1.0f, r, best, stack.data(), rec)) {
-                std::memcpy(out + i, &rec, sizeof(rec));
-                best = out[i].t;
+            LatticeKind::Hit hit;
+            if (placed_candidate<LatticeKind>(inst[j], M, 1.0f, 1.0f, r, best, stack.data(), hit)) {
+                std::memcpy(out + i, &hit.rec, sizeof(hit.rec));
                 ids[i] = j;
             }
         }

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: posed models (include/blok_hip.h, "Posed models") through the pose math of the gfx950 kernels
 // (blok_amd/csrc/hip/posed_core.h) with the walk of trace_core.h, compiled for the CPU.  The loop is the posed kernels'
-// (posed_kernels.hip: compose_poses) on top of the instance loop of scaled_instance_shim.cpp.  Never linked into the shipped libraries.
+// (placed_kernels.hip: compose, through instance_core.h: placed_candidate) on top of the instance loop of scaled_instance_shim.cpp.  Never linked into the shipped libraries.
 // -DPOSED_INSTANCE_SHIM_MAIN: a stand-alone program that replays case files written by tests/test_posed_instances_cpu.py, for the sanitizers.
 #include "scaled_instance_shim.cpp"
 #include "posed_core.h"
@@ -54,11 +54,10 @@ void ps_compose(const void* world, void* const* models, size_t n_models, const b
             if (poses[j].model >= n_models) continue;
             const ModelDesc& M = d[poses[j].model];
             if (!pose_usable(poses[j], M)) continue;
-            uint4 rec;
-            if (pose_candidate(poses[j], M, vs, inv_vs, r, best, stack.data(), rec)) {
-                std::memcpy(out + i, &rec, sizeof(rec));
-                best = out[i].t;
-                ids[i] = BLOK_POSE_ID | j;
+            PoseKind::Hit hit;
+            if (placed_candidate<PoseKind>(poses[j], M, vs, inv_vs, r, best, stack.data(), hit)) {
+                std::memcpy(out + i, &hit.rec, sizeof(hit.rec));
+                ids[i] = PoseKind::id_tag | j;
             }
         }
     }

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: scaled models (include/blok_hip.h, "Scaled models") through the instance math and the instance BVH of the gfx950
 // kernels (blok_amd/csrc/hip/instance_core.h, tlas_core.h), compiled for the CPU with the exponent settable and the world's voxel size an
-// argument.  The linear loop is the primary frame's (instance_kernels.hip: compose_instances); the tree queries are the path kernel's.
+// argument.  The linear loop is the primary frame's (placed_kernels.hip: compose, through instance_core.h: placed_candidate); the tree queries are the path kernel's.
 // Never linked into the shipped libraries.  -DSCALED_INSTANCE_SHIM_MAIN: a stand-alone program over the same entries, for the sanitizers.
 #include "tlas_shim.cpp"
 
@@ -60,10 +60,9 @@ void ss_compose(const void* world, void* const* models, size_t n_models, const b
             if (inst[j].model >= n_models) continue;
             const ModelDesc& M = d[inst[j].model];
             if (!instance_usable(inst[j], M)) continue;
-            uint4 rec;
-            if (instance_candidate(inst[j], M, vs, inv_vs, r, best, stack.data(), rec)) {
-                std::memcpy(out + i, &rec, sizeof(rec));
-                best = out[i].t;
+            LatticeKind::Hit hit;
+            if (placed_candidate<LatticeKind>(inst[j], M, vs, inv_vs, r, best, stack.data(), hit)) {
+                std::memcpy(out + i, &hit.rec, sizeof(hit.rec));
                 ids[i] = j;
             }
         }

@@ -189,6 +189,35 @@ def test_poses_from_instances_equal_the_lattice_instances(shim, omodels, vs):
     assert_same(b, b_ids, want, want_ids, rays, "48 orientations as poses")
 
 
+def test_the_three_shims_share_one_candidate(shim, omodels):
+    """instance_core.h: placed_candidate is the one statement of a candidate that the three shims walk — instance_shim.cpp (is_compose, voxel size
+    1), scaled_instance_shim.cpp (ss_compose) and posed_instance_shim.cpp (ps_compose).  Over the mixed case's lattice instances alone the
+    three give the oracle's records, and over its poses the third does."""
+    vs = 1.0
+    mixed = PC.table(vs)[11]
+    lattice = PC.Case("lattice", mixed.instances, np.zeros(0, dtype=POSE), mixed.eye, mixed.target)
+    rays = PC.aimed_rays(mixed, vs, per_entry=400, n_miss=100, seed=17)
+    want, want_ids = PC.expected(lattice, vs, rays, omodels[vs])
+    assert ((want_ids != INSTANCE_NONE).sum() > 300)
+    L = shim.lib
+    L.is_compose.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    for name in ("is_compose", "ss_compose", "ps_compose"):
+        got, ids = np.zeros(len(rays), dtype=O.HIT), np.zeros(len(rays), dtype=np.uint32)
+        head = (shim.world(vs), shim.array, len(shim.handles), _p(lattice.instances), len(lattice.instances))
+        tail = (_p(rays), len(rays), _p(got), _p(ids))
+        if name == "is_compose":
+            L.is_compose(*head, *tail)
+        elif name == "ss_compose":
+            L.ss_compose(*head, vs, *tail)
+        else:
+            L.ps_compose(*head, None, 0, vs, *tail)
+        assert_same(got, ids, want, want_ids, rays, name)
+    want, want_ids = PC.expected(mixed, vs, rays, omodels[vs])
+    got, ids = shim.compose(mixed, vs, rays)
+    assert_same(got, ids, want, want_ids, rays, "ps_compose with poses")
+    assert pose_won(want_ids).sum() > 100
+
+
 # ---- 4. the bins' world box holds the exact preimage ---------------------------------------------------------------------------------------
 def contains(box, exact):
     (lo, hi), (elo, ehi) = box, exact

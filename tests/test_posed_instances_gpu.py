@@ -3,7 +3,8 @@ of tests/pose_cases.py.
 
 References: the oracle composition (tests/pose_oracle.py on top of tests/scaled_instance_oracle.py), the unbinned rays kernel for the
 binned frame, the instanced entries for an empty pose table and for poses made from instances.  Every comparison is exact.  Frames are
-96 x 64 (3 x 2 bins) and 100 x 70 at (8, 8) of a 116 x 86 frame (ragged tiles and bins)."""
+96 x 64 (3 x 2 bins) and 100 x 70 at (8, 8) of a 116 x 86 frame (ragged tiles and bins).  Section 6 holds the small cases that the kernel body
+shared with the lattice instances makes easy to break: an overflowing bin, a rectangle off every grid, ids alone, who writes which id."""
 from __future__ import annotations
 
 import functools
@@ -17,6 +18,7 @@ from tests import instance_oracle as IO
 from tests import oracle_ffi as O
 from tests import pose_cases as PC
 from tests import pose_oracle as PO
+from tests import scaled_instance_oracle as SO
 from tests.conftest import records_equal
 
 pytestmark = pytest.mark.gpu
@@ -143,7 +145,6 @@ def test_no_poses_gives_the_bytes_of_the_instanced_entries(torch_cuda, tracers):
 # ---- 3. the 48 orientations -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("vs", VOXEL_SIZES)
 def test_poses_from_instances_equal_the_instanced_entry(torch_cuda, tracers, vs):
-    from tests import scaled_instance_oracle as SO
     tr = tracers[vs][0]
     rng = np.random.default_rng(9)
     table = np.array([IO.instance(i % 5, rng.integers(-30, 50, size=3) + (0, 25, 0), p, f) for i, (p, f) in enumerate(IO.SIGNED_PERMUTATIONS)], dtype=INSTANCE)
@@ -263,6 +264,105 @@ def test_device_tables_skip_what_the_host_check_refuses(torch_cuda, tracers):
     won = want_ids.reshape(-1) == POSE_ID
     assert won.sum() > 300 and d_hits.cpu().numpy().tobytes() == want_hits.tobytes()
     assert (ids[won] == POSE_ID | 3).all() and (ids[~won] == want_ids.reshape(-1)[~won]).all()
+
+
+# ---- 6. what one kernel body for lattice instances and poses makes easy to break (placed_kernels.hip) ------------------------------------------
+def test_more_poses_than_a_bin_lists_stay_exact(torch_cuda, tracers):
+    """70 small rods whose boxes fall into bin (1, 0) of the 96 x 64 frame: the bin overflows (its pixels test every pose), and the frame is
+    the unbinned rays kernel's and the oracle's, byte for byte."""
+    tr = tracers[1.0][0]
+    case = next(c for c in PC.table(1.0) if c.notes.get("overflow"))
+    assert len(case.poses) == 70
+    cam = case.camera(PC.WD, PC.HT)
+    rays = frame_rays(case, True)
+    per_pose = []
+    want, want_ids = PC.expected(case, 1.0, rays, oracle_models(1.0), per_pose)
+    x, y = np.meshgrid(np.arange(PC.WD), np.arange(PC.HT))
+    in_bin = ((x // 32 == 1) & (y // 32 == 0)).reshape(-1)
+    assert sum(1 for hit in per_pose if (hit & in_bin).any()) > 63, "more poses in the bin than its list holds"
+    hits, ids, rgba = tr.trace_primary_posed(cam, None, case.poses)
+    assert_same(hits.reshape(-1), ids.reshape(-1), want, want_ids, "the overflowing bin's frame")
+    assert (rgba.reshape(-1) == PO.shade(want, want_ids, case.poses, PC.world(1.0).materials)).all()
+    ray_hits, ray_ids = tr.trace_rays_posed(rays, None, case.poses)
+    assert ray_hits.tobytes() == hits.tobytes() and ray_ids.tobytes() == ids.tobytes()
+    assert len(np.unique(ids[(ids != INSTANCE_NONE)])) > 20 and (ids[ids != INSTANCE_NONE] & POSE_ID).all()
+
+
+@pytest.mark.parametrize("n", [0, 11])                         # one pose; lattice instances and poses together
+def test_a_rectangle_off_every_grid_is_the_full_frames_crop(torch_cuda, tracers, n):
+    """A rectangle whose origin and size are multiples of neither the 8 x 8 tile nor the 32 x 32 bin: records, ids and RGBA8 are the crop of
+    the full frame's."""
+    tr = tracers[1.0][0]
+    case = PC.table(1.0)[n]
+    cam = case.camera(PC.WD, PC.HT)
+    x0, y0, w, h = rect = (13, 9, 53, 37)
+    full = tr.trace_primary_posed(cam, case.instances, case.poses)
+    part = tr.trace_primary_posed(cam, case.instances, case.poses, rect)
+    for whole, crop in zip(full, part):
+        assert crop.shape == (h, w) and crop.tobytes() == np.ascontiguousarray(whole[y0:y0 + h, x0:x0 + w]).tobytes()
+    assert (part[1] != INSTANCE_NONE).sum() > 100 and (part[1] == INSTANCE_NONE).any()
+
+
+def test_ids_alone_with_poses_and_no_instances(torch_cuda, tracers):
+    """Only the id plane is asked for, the lattice table is empty and the pose table is not: the records go to the stream's scratch, and
+    the ids are those of the run with all three outputs."""
+    torch = torch_cuda
+    tr = tracers[1.0][0]
+    case = PC.table(1.0)[1]
+    cam = case.camera(PC.WD, PC.HT)
+    _, want_ids, _ = tr.trace_primary_posed(cam, None, case.poses)
+    d_pose = dev(torch, case.poses)
+    d_ids = torch.full((PC.WD * PC.HT,), 7, dtype=torch.int32, device="cuda")
+    tr.trace_primary_posed_device(cam, 0, 0, d_pose.data_ptr(), len(case.poses), 0, 0, d_ids.data_ptr())
+    torch.cuda.synchronize()
+    ids = d_ids.cpu().numpy().view(np.uint32)
+    assert ((ids == INSTANCE_NONE) | (ids == POSE_ID | 0)).all() and (ids == POSE_ID | 0).sum() > 300
+    assert ids.tobytes() == want_ids.tobytes()
+
+
+def pixel_box(cam, corners, w, h):
+    """(x0, x1, y0, y1) of the pixels that world points `corners` (all in front of the camera) project to: camera_plane_uv inverted."""
+    pos, fwd, right, up = (np.asarray(cam[k], dtype=np.float64).reshape(3) for k in ("pos", "fwd", "right", "up"))
+    d = np.asarray(corners, dtype=np.float64) - pos
+    depth = d @ fwd
+    assert (depth > 1.0).all()
+    tan, aspect = float(np.ravel(cam["tan_half_fov"])[0]), float(np.ravel(cam["aspect"])[0])
+    x = ((d @ right) / depth / (tan * aspect) + 1.0) * 0.5 * w - 0.5
+    y = (1.0 - (d @ up) / depth / tan) * 0.5 * h - 0.5
+    return x.min(), x.max(), y.min(), y.max()
+
+
+def test_each_pass_writes_only_the_ids_it_owns(torch_cuda, tracers):
+    """A lattice instance in the right third of the frame, a pose in the left third, nothing in the middle.  The lattice pass owns the id
+    plane: it writes every pixel, also of a tile its bin leaves empty.  The posed pass writes only where a pose wins: the tiles that only the
+    instance bin lists keep the instance's ids, the tiles neither bin lists are 0xFFFFFFFF."""
+    torch = torch_cuda
+    vs = 1.0
+    tr = tracers[vs][0]
+    inst = IO.instance(PC.ROD, (-8, 14, 18), (1, 0, 2), 2)
+    p = PC.turned(PC.SLAB, vs, (35.0, 16.0, 18.0), yaw=30.0)
+    case = PC.Case("own", np.array([inst], dtype=INSTANCE), np.array([p], dtype=POSE), (10.0, 22.0, -25.0), (10.0, 14.0, 15.0))
+    cam = case.camera(PC.WD, PC.HT)
+    # which bins list what, from the boxes alone: each box's pixels, 2 pixels wider than the bins' own margin, lie in one column of bins
+    bx = PC.boxes()
+    box = lambda lo, hi: [[float((hi if c >> k & 1 else lo)[k]) for k in range(3)] for c in range(8)]
+    lo, hi = SO.world_span(inst, bx[PC.ROD][0], bx[PC.ROD][1], PC.EXPONENTS[PC.ROD])
+    ix0, ix1, _, _ = pixel_box(cam, np.array(box(lo, hi)) * vs, PC.WD, PC.HT)
+    px0, px1, _, _ = pixel_box(cam, box(*PO.preimage_box(p, bx[PC.SLAB][0], bx[PC.SLAB][1], vs)), PC.WD, PC.HT)
+    assert 64 + 3 <= ix0 and ix1 <= 95 - 3 and px1 <= 31 - 3, (ix0, ix1, px0, px1)
+    want, want_ids = PC.expected(case, vs, frame_rays(case, True), oracle_models(vs))
+    _, inst_ids, _ = tr.trace_primary_instanced(cam, case.instances)
+    n = PC.WD * PC.HT
+    d_hits = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+    d_ids = torch.full((n,), 7, dtype=torch.int32, device="cuda")
+    d_inst, d_pose = dev(torch, case.instances), dev(torch, case.poses)
+    tr.trace_primary_posed_device(cam, d_inst.data_ptr(), 1, d_pose.data_ptr(), 1, d_hits.data_ptr(), 0, d_ids.data_ptr())
+    torch.cuda.synchronize()
+    ids = d_ids.cpu().numpy().view(np.uint32).reshape(PC.HT, PC.WD)
+    assert_same(d_hits.cpu().numpy().view(HIT), ids.reshape(-1), want, want_ids, "one instance, one pose")
+    assert (ids[:, 64:] == inst_ids[:, 64:]).all() and (ids[:, 64:] == 0).sum() > 15 and ((ids[:, 64:] == 0) | (ids[:, 64:] == INSTANCE_NONE)).all()
+    assert (ids[:, 32:64] == INSTANCE_NONE).all()
+    assert (ids[:, :32] == POSE_ID | 0).sum() > 100 and ((ids[:, :32] == POSE_ID | 0) | (ids[:, :32] == INSTANCE_NONE)).all()
 
 
 def test_abi_version(torch_cuda):
