@@ -497,6 +497,14 @@ HIP_SYMBOLS = {
     "blok_hip_trace_paths_instanced": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.POINTER(GBuffer), C.c_void_p]),
     "blok_hip_draw_frame_rt_instanced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                    C.POINTER(C.c_uint32)]),
+    "blok_hip_trace_paths_posed_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(GBuffer),
+                                                                                                  C.c_void_p, C.c_void_p]),
+    "blok_hip_trace_paths_posed_ref_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                                                                      C.POINTER(C.c_float), C.POINTER(GBufferRef), C.c_void_p, C.c_void_p]),
+    "blok_hip_trace_paths_posed": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(GBuffer),
+                                                                                           C.c_void_p]),
+    "blok_hip_draw_frame_rt_posed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                               C.c_void_p, C.POINTER(C.c_uint32)]),
     "blok_hip_instance_motion_device": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                                        C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     "blok_hip_denoise_instanced_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p,
@@ -507,6 +515,8 @@ HIP_SYMBOLS = {
                                                           C.c_void_p, C.POINTER(C.c_uint32)]),
     "blok_hip_volume_refresh_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_volume_flood_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "blok_hip_debug_build_pose_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "blok_hip_set_pose_tlas": (C.c_int, [C.c_void_p, C.c_int]),
     "blok_hip_debug_build_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 

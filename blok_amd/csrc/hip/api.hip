@@ -284,7 +284,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 22u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 23u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -768,9 +768,11 @@ int blok_hip_shade_rgba8(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0,
 
 // Launch of the path kernel (pre-pass first) for either plane set; `planes` carries the output pointers and prev_view_proj.  With
 // instances (inst->n > 0): the instance BVH is built on the stream first (up to kTlasMax instances; above, the kernel loops over the table),
-// then the instanced path kernel runs without the tail pool; inst->n == 0 is the world-only launch plus the id plane.
+// then the instanced path kernel runs without the tail pool; inst->n == 0 is the world-only launch plus the id plane.  With poses
+// (poses->n > 0; inst is then not null) the posed path kernel runs in the instanced kernel's place, with or without instances.
 int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
-                                uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst) {
+                                uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst,
+                                const PathPoses* poses) {
     int rc = check_trace(ctx, cam);
     if (rc != BLOK_OK) return rc;
     if (!rect_inside(ctx, x0, y0, w, h) || !spp || !max_bounces)
@@ -801,7 +803,8 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     // the bounce rounds' tail pool (path_core.h: shade_pixel): with the rounds taken sample by sample, two bounces or more, rays from the root
     p.tail_pool = nullptr;
     // (from four samples per pixel on: with fewer a wave's pool never fills, and the rays parked wait for the end: 1 spp 0.82 -> 0.93 ms, 4 spp 2.78 -> 2.54)
-    const bool instanced = inst != nullptr && inst->n != 0u;
+    const bool posed = inst != nullptr && poses != nullptr && poses->n != 0u;
+    const bool instanced = inst != nullptr && (inst->n != 0u || posed);
     if (instanced) p.resume_secondary = 0u;                 // (the instanced kernel is built without walk_resume)
     if (ctx->ray_batching >= 3u && max_bounces >= 2u && spp >= 4u && !ctx->path_resume && blok::kBlock == 64 && !instanced) {
         const size_t bytes = static_cast<size_t>(path_blocks) * blok::kTailCapacity * sizeof(blok::TailRecord);
@@ -814,17 +817,30 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     if (instanced) {
         scene.instances = inst->table; scene.n_instances = inst->n; scene.ids = inst->ids;
         scene.models = ctx->models.d_desc; scene.n_models = static_cast<uint32_t>(ctx->models.desc.size());
-        if (inst->n <= blok::kTlasMax) {
+        if (inst->n != 0u && inst->n <= blok::kTlasMax) {
             auto& scratch = ctx->beam_buffers[stream];
             BLOK_HIP_TRY(ctx, scratch.tlas.reserve(blok::tlas_nodes(inst->n) * sizeof(blok::TlasNode), blok::FreeAfter::work_on(stream)));
             scene.nodes = static_cast<const blok::TlasNode*>(scratch.tlas.get());
         }
     }
+    blok::PoseScene pose_scene{};
+    if (posed) {
+        pose_scene.poses = poses->table; pose_scene.n_poses = poses->n;
+        if (ctx->pose_tlas && poses->n <= blok::kTlasMax) {
+            auto& scratch = ctx->beam_buffers[stream];
+            BLOK_HIP_TRY(ctx, scratch.pose_tlas.reserve(blok::tlas_nodes(poses->n) * sizeof(blok::TlasNode), blok::FreeAfter::work_on(stream)));
+            pose_scene.nodes = static_cast<const blok::TlasNode*>(scratch.pose_tlas.get());
+        }
+    }
     if (ctx->timing) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, stream));
+    if (posed && pose_scene.nodes)
+        blok::launch_pose_tlas_build(poses->table, poses->n, scene.models, scene.n_models, ctx->world_voxel_size, cam->pos,
+                                     static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].pose_tlas.get()), stream);
     if (instanced && scene.nodes)
         blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas.get()), stream);
     if (n_beams) blok::launch_beam(blok::RayMode::Rect, p.trace, n_beams, stream);
-    if (instanced) blok::launch_paths_instanced(p, scene, ctx->models.stack_levels, path_blocks, stream);
+    if (posed) blok::launch_paths_posed(p, scene, pose_scene, ctx->models.stack_levels, path_blocks, stream);
+    else if (instanced) blok::launch_paths_instanced(p, scene, ctx->models.stack_levels, path_blocks, stream);
     else blok::launch_paths(p, path_blocks, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());
     if (inst != nullptr && !instanced && inst->ids)

@@ -200,6 +200,12 @@ int blok_hip_set_path_start(blok_hip_ctx* ctx, int resume_from_anchor, int wave_
     return BLOK_OK;
 }
 
+int blok_hip_set_pose_tlas(blok_hip_ctx* ctx, int enabled) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    ctx->pose_tlas = enabled != 0;
+    return BLOK_OK;
+}
+
 int blok_hip_set_ray_batching(blok_hip_ctx* ctx, int enabled) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (enabled < 0 || enabled > 3) return set_error(ctx, BLOK_ERR_INVALID_ARG, "ray batching: 0 off, 1 by kind, 2 by sample and kind, 3 and the bounce rounds' tail pool");

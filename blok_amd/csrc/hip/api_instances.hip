@@ -534,6 +534,75 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
     return d.collect(ctx, "trace_paths_instanced", rc);
 }
 
+// ---- path-traced frames with poses (posed_paths_core.h): the instanced entries with a pose table behind the instances --------------------
+
+int blok_hip_trace_paths_posed_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                      uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev, uint32_t n_instances,
+                                      const blok_pose* poses_dev, uint32_t n_poses, const blok_gbuffer* planes_dev, uint32_t* out_instance_dev,
+                                      void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad path-trace arguments");
+    const int rc = check_device_tables(ctx, instances_dev, n_instances, poses_dev, n_poses);
+    if (rc != BLOK_OK) return rc;
+    if (!n_poses)                                        // the instanced entry itself: the same launches, the same bytes
+        return blok_hip_trace_paths_instanced_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, instances_dev, n_instances, planes_dev,
+                                                     out_instance_dev, hip_stream);
+    blok::PathArgs p{};
+    p.color = planes_dev->color; p.world_pos = planes_dev->world_pos;
+    p.normal_roughness = planes_dev->normal_roughness; p.albedo_metallic = planes_dev->albedo_metallic;
+    const PathInstances inst{instances_dev, n_instances, out_instance_dev};
+    const PathPoses poses{poses_dev, n_poses};
+    return launch_path_frame(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, p, hip_stream, &inst, &poses);
+}
+
+int blok_hip_trace_paths_posed_ref_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                          uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev, uint32_t n_instances,
+                                          const blok_pose* poses_dev, uint32_t n_poses, const float prev_view_proj[16],
+                                          const blok_gbuffer_ref* planes_dev, uint32_t* out_instance_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes_dev || (planes_dev->motion && !prev_view_proj))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "bad path-trace arguments (a motion plane needs prevViewProj)");
+    const int rc = check_device_tables(ctx, instances_dev, n_instances, poses_dev, n_poses);
+    if (rc != BLOK_OK) return rc;
+    if (!n_poses)
+        return blok_hip_trace_paths_instanced_ref_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, instances_dev, n_instances, prev_view_proj,
+                                                         planes_dev, out_instance_dev, hip_stream);
+    blok::PathArgs p{};
+    p.color = planes_dev->color; p.world_pos = planes_dev->world_pos;
+    p.normal_roughness_h = planes_dev->normal_roughness; p.albedo_metallic_u8 = planes_dev->albedo_metallic; p.motion_h = planes_dev->motion;
+    if (prev_view_proj) for (int k = 0; k < 16; ++k) p.prev_view_proj[k] = prev_view_proj[k];
+    const PathInstances inst{instances_dev, n_instances, out_instance_dev};
+    const PathPoses poses{poses_dev, n_poses};
+    return launch_path_frame(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, p, hip_stream, &inst, &poses);
+}
+
+int blok_hip_trace_paths_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                               uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_host, uint32_t n_instances,
+                               const blok_pose* poses_host, uint32_t n_poses, const blok_gbuffer* planes_host, uint32_t* out_instance_host) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null planes");
+    int rc = check_trace(ctx, cam);
+    if (rc != BLOK_OK) return rc;
+    if (!rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame");
+    rc = check_table(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = check_pose_table(ctx, poses_host, n_poses);
+    if (rc != BLOK_OK) return rc;
+    const size_t n = static_cast<size_t>(w) * h;
+    float* const host[4] = {planes_host->color, planes_host->world_pos, planes_host->normal_roughness, planes_host->albedo_metallic};
+    StagedBlock d;
+    const auto inst = d.input(instances_host, n_instances);
+    const auto poses = d.input(poses_host, n_poses);
+    StagedBlock::Seg<float> plane[4];
+    for (int i = 0; i < 4; ++i) plane[i] = d.output(host[i], n * 4);
+    const auto ids = d.output(out_instance_host, n);
+    rc = d.stage(ctx, "trace_paths_posed");
+    if (rc != BLOK_OK) return rc;
+    const blok_gbuffer planes_dev{d.wanted(plane[0]), d.wanted(plane[1]), d.wanted(plane[2]), d.wanted(plane[3])};
+    rc = blok_hip_trace_paths_posed_device(ctx, cam, x0, y0, w, h, spp, max_bounces, frame_index, d.at(inst), n_instances, d.at(poses), n_poses,
+                                           &planes_dev, d.wanted(ids), nullptr);
+    return d.collect(ctx, "trace_paths_posed", rc);
+}
+
 // ---- object motion of moving instances (instance_motion.h) -----------------------------------------------------------------------
 
 int blok_hip_instance_motion_device(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev,
@@ -573,6 +642,25 @@ int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out_nodes_host, d, count * sizeof(blok::TlasNode), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("build_tlas: ") + hipGetErrorString(e));
+    return BLOK_OK;
+}
+
+int blok_hip_debug_build_pose_tlas(blok_hip_ctx* ctx, const blok_camera* cam, const blok_pose* poses_dev, uint32_t n_poses, void* out_nodes_host,
+                                   size_t capacity, uint32_t* out_count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!cam || !n_poses || n_poses > blok::kTlasMax || !poses_dev || !out_nodes_host)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "the pose tree needs a camera, 1 .. kTlasMax poses and an output");
+    const uint32_t count = blok::tlas_nodes(n_poses);
+    if (out_count) *out_count = count;
+    if (capacity < count) return set_error(ctx, BLOK_ERR_INVALID_ARG, "output too small for " + std::to_string(count) + " nodes");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    blok::DeviceArray<blok::TlasNode> d;
+    BLOK_HIP_TRY(ctx, d.reserve(count, blok::FreeAfter::nothing()));
+    blok::launch_pose_tlas_build(poses_dev, n_poses, ctx->models.d_desc, static_cast<uint32_t>(ctx->models.desc.size()), ctx->world_voxel_size, cam->pos, d,
+                                 nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out_nodes_host, d, count * sizeof(blok::TlasNode), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_error(ctx, BLOK_ERR_HIP, std::string("build_pose_tlas: ") + hipGetErrorString(e));
     return BLOK_OK;
 }
 

@@ -95,6 +95,7 @@ struct blok_hip_ctx {
     // blok_hip_draw_frame_rt_instanced(_motion): the frame's instance table in device memory (records), grown on demand, and the previous
     // frame's (the motion entry swaps the two after each frame); outside `post`, which ensure_post may reallocate after the upload
     blok::DeviceArray<blok_instance> rt_instances, rt_prev_instances;
+    blok::DeviceArray<blok_pose> rt_poses;       // blok_hip_draw_frame_rt_posed: the frame's pose table in device memory, grown on demand
     // device-resident dense store (gpu_build.h: GpuVolume)
     blok::GpuVolume volume;
     bool has_volume = false;
@@ -118,6 +119,7 @@ struct blok_hip_ctx {
     blok::Event sun_event; bool sun_event_pending = false;                                            // behind the latest patch of the map
     uint32_t ray_batching = 3;          // PathArgs::batch_kinds (blok_hip_set_ray_batching); 3 = 2 + the bounce rounds' tail pool
     uint32_t tail_cap = 24, tail_cap_parked = 32;                 // trips after which a bounce round / a round over parked rays stops (BLOK_TAIL_CAPS overrides, experiments)
+    bool pose_tlas = true;                                // blok_hip_set_pose_tlas: posed path launches build and walk the pose BVH (false: the linear loop)
     bool path_resume = false, path_fine_beam = true;      // PathArgs::resume_secondary / fine_beam (blok_hip_set_path_start)
     blok::SunMapArgs sun{};
     // beam pre-pass (beam.h): start parameters per beam tile, one buffer per stream (launches on one stream are
@@ -140,6 +142,7 @@ struct blok_hip_ctx {
         blok::DeviceArray<uint32_t> inst_bins;                           // instanced frames: the binning kernel's lists (instance_core.h: kBinWords words per bin), grown on demand
         blok::DeviceArray<blok_hit> inst_hits;                           // instanced frames without a record output: the world records the instance pass reads
         blok::DeviceArray<uint32_t> pose_bins;                           // posed frames: the posed binning kernel's lists (the same layout), grown on demand
+        blok::DeviceBytes pose_tlas;                                      // posed path launches: the pose BVH (pose_tlas_core.h), grown on demand
         blok::DeviceBytes tlas;                                           // instanced path launches: the instance BVH (tlas_core.h: TlasNode), grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
@@ -358,8 +361,11 @@ int prepare_queue(blok_hip_ctx* ctx, blok::RayMode mode, const blok::TraceArgs& 
 int check_trace(blok_hip_ctx* ctx, const blok_camera* cam);
 // The instances of an instanced path launch (null: world only): a device table of n records and the optional id plane.
 struct PathInstances { const blok_instance* table; uint32_t n; uint32_t* ids; };
+// The poses of a posed path launch (null, or n == 0: none): a device table of n records, traced behind the instances.
+struct PathPoses { const blok_pose* table; uint32_t n; };
 int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
-                      uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst = nullptr);
+                      uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst = nullptr,
+                      const PathPoses* poses = nullptr);
 // api_launch.hip
 int beam_buffer(blok_hip_ctx* ctx, hipStream_t stream, size_t n, float** out);
 int order_buffers(blok_hip_ctx* ctx, uint32_t blocks, hipStream_t stream);

@@ -263,7 +263,7 @@ namespace {
 // records) and the temporal pass is the instanced one.
 int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces, const blok_denoise_settings* settings,
                   const blok_instance* instances_dev, uint32_t n_instances, uint32_t* out_rgba8_host, uint32_t* out_frame_count,
-                  bool object_motion = false) {
+                  bool object_motion = false, const blok_pose* poses_dev = nullptr, uint32_t n_poses = 0u) {
     int rc = check_trace(ctx, cam);
     if (rc != BLOK_OK) return rc;
     if (!spp || !max_bounces) return set_error(ctx, BLOK_ERR_INVALID_ARG, "spp and bounces must be positive");
@@ -298,7 +298,9 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
     // (renderer_draw.cpp:313-328 passes the base matrices)
     const float saved_jitter[2] = {ctx->jitter_px[0], ctx->jitter_px[1]};
     if (ctx->rt_taa_jitter) blok::taa_jitter_px(frame, ctx->jitter_px);
-    rc = instances_dev ? blok_hip_trace_paths_instanced_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev,
+    rc = n_poses       ? blok_hip_trace_paths_posed_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev, n_instances,
+                                                               poses_dev, n_poses, prev_vp, &planes, nullptr, nullptr)
+       : instances_dev ? blok_hip_trace_paths_instanced_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev,
                                                                    n_instances, prev_vp, &planes, motion ? P.rt_ids : nullptr, nullptr)
                        : blok_hip_trace_paths_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, prev_vp, &planes, nullptr);
     ctx->jitter_px[0] = saved_jitter[0]; ctx->jitter_px[1] = saved_jitter[1];
@@ -352,6 +354,21 @@ int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, 
     const int rc = upload_rt_table(ctx, cam, instances_host, n_instances);
     if (rc != BLOK_OK) return rc;
     return draw_frame_rt(ctx, cam, spp, max_bounces, settings, ctx->rt_instances, n_instances, out_rgba8_host, out_frame_count);
+}
+
+int blok_hip_draw_frame_rt_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces, const blok_denoise_settings* settings,
+                                 const blok_instance* instances_host, uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses,
+                                 uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+    int rc = check_trace(ctx, cam);                       // both tables are checked before either is uploaded
+    if (rc == BLOK_OK) rc = blok_hip_check_instances(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = blok_hip_check_poses(ctx, poses_host, n_poses);
+    if (rc == BLOK_OK) rc = upload_rt_table(ctx, cam, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    if (n_poses) {
+        BLOK_HIP_TRY(ctx, ctx->rt_poses.reserve(n_poses, blok::FreeAfter::nothing()));
+        BLOK_HIP_TRY(ctx, hipMemcpy(ctx->rt_poses, poses_host, n_poses * sizeof(blok_pose), hipMemcpyHostToDevice));
+    }
+    return draw_frame_rt(ctx, cam, spp, max_bounces, settings, ctx->rt_instances, n_instances, out_rgba8_host, out_frame_count, false, ctx->rt_poses, n_poses);
 }
 
 int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,

@@ -18,6 +18,7 @@
 
 #include "trace_core.h"
 #include "tlas_core.h"
+#include "posed_paths_core.h"
 #include "half_bits.h"
 
 #if defined(__clang__)
@@ -111,6 +112,13 @@ BLOK_DEV void tangent_frame_of_face(V3 n, V3& tangent, V3& bitangent) {
     tangent = vcross(up, n);
     bitangent = vcross(n, tangent);
 }
+// The same frame for any unit normal (a posed face's, posed_paths_core.h): the shader's own normalize().  For an axis normal the division is by
+// 1 and the result is tangent_frame_of_face's bit for bit, so the world and instance hits of a posed launch keep their values.
+BLOK_DEV void tangent_frame_of_normal(V3 n, V3& tangent, V3& bitangent) {
+    const V3 up = fabsf(n.z) < 0.999f ? v3(0.0f, 0.0f, 1.0f) : v3(1.0f, 0.0f, 0.0f);
+    tangent = vnormalize(vcross(up, n));
+    bitangent = vcross(n, tangent);
+}
 // (sample_cosine_hemisphere :101-113 and sample_ggx :115-130 are written out in shade_pixel, where their common tail runs once per wave.)
 // pow(x, k) for the shader's integer exponents 5, 8, 128 by multiplication (<= 4 ulp from a correctly rounded
 // pow; GLSL's own pow is exp2(y*log2(x)) at driver precision).  Far inside the stated colour tolerance, and
@@ -192,11 +200,14 @@ BLOK_DEV void store_narrow(const PathArgs& P, size_t index, uint32_t px, uint32_
 // function of a few registers — in the full one, values spilled at its head were written out by three quarters of a frame's waves for nothing.
 // kInstanced: every ray is composed with the instances of `scene` (tlas_core.h) right after the world walk.  Such a launch
 // runs without the anchor machinery (kResume false), the tail pool and the sky-tile shortcut (the beam pre-pass knows only the world).
-template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false>
+// kPosed (implies kInstanced): and then with the poses of `poses` (posed_paths_core.h); a posed hit takes its world normal from its
+// pose's row, and the sampling frame is formed for any unit normal.
+template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false>
 BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t index, uint4* stk, float t0 = 0.0f, uint2* keep_lohi = nullptr, uint32_t* keep_base = nullptr,
                           [[maybe_unused]] TailRecord* pool = nullptr, [[maybe_unused]] TailAnswer* tail_results = nullptr,
-                          [[maybe_unused]] const TlasScene* scene = nullptr) {
+                          [[maybe_unused]] const TlasScene* scene = nullptr, [[maybe_unused]] const PoseScene* poses = nullptr) {
     static_assert(!kInstanced || (!kResume && !kSkyOnly), "instanced launches run without walk_resume and the sky-only build");
+    static_assert(!kPosed || kInstanced, "a posed launch is an instanced launch with a pose table");
     const TraceArgs& A = P.trace;
     const blok_camera& cam = A.cam;
     const V3 cam_pos = v3(cam.pos[0], cam.pos[1], cam.pos[2]);
@@ -433,6 +444,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 anchored = true; stack_is_anchor = true;
             }
         }
+        [[maybe_unused]] uint32_t pose_won = kInstanceNone;       // kPosed: the pose whose voxel `hit` reports (hit.face is then its LOCAL face)
         if constexpr (kInstanced) {
             // The instances, on the ray's own interval: the beam pre-pass' start parameter and the sun map's cap describe the world alone.
             // Primary and bounce rays: the closest hit of world and instances by the composition rule (the world's t bounds the query;
@@ -443,6 +455,9 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
             if (shadow_phase) {
                 q.tmax = 1000.0f;                                                             // :296
                 if (!hit.found && tlas_any(*scene, A.voxel_size, A.inv_voxel_size, q, stk)) hit.found = true;
+                if constexpr (kPosed) {                                                       // ... and the poses only when the instances found nothing
+                    if (!hit.found && poses_any(*poses, scene->models, scene->n_models, A.voxel_size, A.inv_voxel_size, q, stk)) hit.found = true;
+                }
             } else {
                 q.tmax = hit.found ? hit.t : 10000.0f;                                        // :227
                 uint4 rec;
@@ -450,6 +465,13 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 if (won != kInstanceNone) {
                     hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
                 }
+                if constexpr (kPosed) {                                                       // the poses, with tmax = the composed t so far
+                    pose_won = poses_closest(*poses, scene->models, scene->n_models, A.voxel_size, A.inv_voxel_size, q, hit.found ? hit.t : 10000.0f, stk, rec);
+                    if (pose_won != kInstanceNone) {
+                        hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
+                    }
+                    if (bounce == 0u && s == 0u && scene->ids) scene->ids[index] = pose_won != kInstanceNone ? (BLOK_POSE_ID | pose_won) : won;
+                } else
                 if (bounce == 0u && s == 0u && scene->ids) scene->ids[index] = won;          // the first hit's instance (G-buffer)
             }
             stack_is_anchor = false;                                                          // the model walks overwrote the stack
@@ -541,6 +563,9 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 n = v3(hit.face == 0u ? 1.0f : (hit.face == 1u ? -1.0f : 0.0f),
                        hit.face == 2u ? 1.0f : (hit.face == 3u ? -1.0f : 0.0f),
                        hit.face == 4u ? 1.0f : (hit.face == 5u ? -1.0f : 0.0f));
+                if constexpr (kPosed) {                                                       // a posed face's own world normal, from its pose's row
+                    if (pose_won != kInstanceNone) pose_world_normal(poses->poses[pose_won], hit.face, n.x, n.y, n.z);
+                }
                 albedo = v3(mat.albedo[0], mat.albedo[1], mat.albedo[2]);
                 metallic = static_cast<float>((mat.flags >> 24) & 0xFFu) / 255.0f;
                 roughness = fmaxf(static_cast<float>((mat.flags >> 16) & 0xFFu) / 255.0f, 0.04f);
@@ -602,7 +627,8 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 const float phi = 2.0f * kPi * turn;
                 const float lx = k_plane * cosf(phi), ly = k_plane * sinf(phi);
                 V3 tangent, bitangent;
-                tangent_frame_of_face(n, tangent, bitangent);
+                if constexpr (kPosed) tangent_frame_of_normal(n, tangent, bitangent);
+                else tangent_frame_of_face(n, tangent, bitangent);
                 const V3 sampled = vnormalize(vadd(vadd(vscale(tangent, lx), vscale(bitangent, ly)), vscale(n, k_normal)));
                 if (specular) {                                                               // :349-360
                     const V3 h = sampled;

@@ -263,6 +263,9 @@ void launch_paths(const PathArgs& args, uint32_t n_blocks, hipStream_t stream);
 struct TlasScene;
 // The instanced path frame (path_core.h: shade_pixel<..., kInstanced>): stack_slots = the deepest live model's levels - 1.
 void launch_paths_instanced(const PathArgs& args, const TlasScene& scene, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
+struct PoseScene;
+// The posed path frame (shade_pixel<..., kPosed>): the instanced frame with a pose table behind the instances (poses.n_poses > 0).
+void launch_paths_posed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
 void launch_trace(RayMode mode, const TraceArgs& args, uint32_t n_blocks, hipStream_t stream);
 // Pre-pass and walk in one grid, statically: workgroups [0, n_beam_tiles) search, the others walk (Rect and Tiles).
 void launch_joint(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, uint32_t n_blocks, hipStream_t stream);

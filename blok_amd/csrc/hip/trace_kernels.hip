@@ -1124,6 +1124,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PAT
     shade_pixel<false, false, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S);
 }
 
+// The posed path frame (posed_paths_core.h): path_kernel_instanced with the pose table behind the instances — the same
+// pixel mapping, LDS stack and grid.  Launched only with n_poses > 0; with no instances S.nodes is null and S.n_instances 0.
+// Waves per SIMD: the highest at which no walk loop (world, instance closest / any, pose closest / any) holds a scratch access: DESIGN.md §30.
+#ifndef BLOK_PATH_POSED_WAVES
+#define BLOK_PATH_POSED_WAVES 4
+#endif
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PATH_POSED_WAVES, BLOK_PATH_POSED_WAVES))) void path_kernel_posed(const PathArgs P, const TlasScene S, const PoseScene Q) {
+    extern __shared__ uint4 lds_stack[];
+    const TraceArgs& A = P.trace;
+    const uint32_t tid = threadIdx.x;
+    uint32_t rx, ry;
+    float t0;
+    if (!path_pixel(P, tid, rx, ry, t0)) return;
+    shade_pixel<false, false, true, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S, &Q);
+}
+
 // One workgroup builds the instance BVH of n <= kTlasMax instances (tlas_core.h): sort keys, a bitonic sort in LDS, the leaves, the refit
 // level by level (each level reads the one below it from global memory behind a fence and a barrier), the header.  No atomics.
 __global__ __launch_bounds__(kTlasBuildThreads) void tlas_build_kernel(const blok_instance* inst, uint32_t n, const ModelDesc* models, uint32_t n_models,
@@ -1147,6 +1163,64 @@ __global__ __launch_bounds__(kTlasBuildThreads) void tlas_build_kernel(const blo
         const bool last_usable = tlas_key_usable(keys[j]) && (j + 1u == P || !tlas_key_usable(keys[j + 1u]));
         if (last_usable) nodes[0] = tlas_header(P, j + 1u);
         if (j == 0u && !tlas_key_usable(keys[0])) nodes[0] = tlas_header(P, 0u);
+    }
+    __threadfence();
+    __syncthreads();
+    for (uint32_t L = P >> 1; L >= 1u; L >>= 1) {
+        for (uint32_t k = L + tid; k < 2u * L; k += kTlasBuildThreads) nodes[k] = tlas_internal(k, nodes[2u * k], nodes[2u * k + 1u]);
+        __threadfence();
+        __syncthreads();
+    }
+}
+
+// One workgroup builds the pose BVH of n <= kTlasMax poses (pose_tlas_core.h): pass 1, every usable pose's unwidened preimage box, their union
+// reduced through the waves and LDS into the launch's box of ray origins; pass 2, tlas_build_kernel's steps on the leaf boxes that box gives —
+// keys, the bitonic sort in LDS, the leaves, the refit level by level, the header with its linear flag.  No atomics.
+__global__ __launch_bounds__(kTlasBuildThreads) void pose_tlas_build_kernel(const blok_pose* poses, uint32_t n, const ModelDesc* models, uint32_t n_models,
+                                                                            float vs, float cam_x, float cam_y, float cam_z, TlasNode* nodes) {
+    __shared__ uint64_t keys[kTlasMax];
+    __shared__ double wave_box[kTlasBuildThreads / 64u][6];
+    const uint32_t P = tlas_slots(n), tid = threadIdx.x;
+    PoseBoxD U = pose_box_empty();
+    for (uint32_t i = tid; i < n; i += kTlasBuildThreads) {
+        const blok_pose S = poses[i];
+        PoseBoxD b;
+        if (S.model < n_models && pose_usable(S, models[S.model]) && pose_preimage_box(S, models[S.model], vs, b)) pose_box_join(U, b);
+    }
+    for (int a = 0; a < 3; ++a)                                  // min / max are exact: any order of the reduction gives the host's union
+        for (int off = 32; off > 0; off >>= 1) {
+            U.lo[a] = __builtin_fmin(U.lo[a], __shfl_down(U.lo[a], off));
+            U.hi[a] = __builtin_fmax(U.hi[a], __shfl_down(U.hi[a], off));
+        }
+    if ((tid & 63u) == 0u) for (int a = 0; a < 3; ++a) { wave_box[tid >> 6][a] = U.lo[a]; wave_box[tid >> 6][3 + a] = U.hi[a]; }
+    __syncthreads();
+    U = pose_box_empty();
+    for (uint32_t w = 0; w < kTlasBuildThreads / 64u; ++w)
+        for (int a = 0; a < 3; ++a) { U.lo[a] = __builtin_fmin(U.lo[a], wave_box[w][a]); U.hi[a] = __builtin_fmax(U.hi[a], wave_box[w][3 + a]); }
+    const float cam[3] = {cam_x, cam_y, cam_z};
+    const PoseOrigins O = pose_origin_box(U, cam, vs);
+    bool unbounded = false;
+    for (uint32_t i = tid; i < P; i += kTlasBuildThreads) {
+        PoseLeafKind kind = kPoseLeafSkipped;
+        keys[i] = i < n ? pose_tlas_key(poses, models, n_models, i, vs, O, kind) : ~0ull;
+        unbounded = unbounded || kind == kPoseLeafUnbounded;
+    }
+    const bool linear = __syncthreads_or(unbounded ? 1 : 0) != 0;
+    for (uint32_t size = 2u; size <= P; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0u; stride >>= 1) {
+            for (uint32_t t = tid; t < P / 2u; t += kTlasBuildThreads) {
+                const uint32_t i = 2u * t - (t & (stride - 1u)), j = i + stride;
+                const uint64_t a = keys[i], b = keys[j];
+                if ((a > b) == ((i & size) == 0u)) { keys[i] = b; keys[j] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t j = tid; j < P; j += kTlasBuildThreads) {
+        nodes[P + j] = pose_tlas_leaf(poses, models, n_models, P, j, keys[j], vs, O);
+        const bool last_boxed = tlas_key_usable(keys[j]) && (j + 1u == P || !tlas_key_usable(keys[j + 1u]));
+        if (last_boxed) nodes[0] = pose_tlas_header(P, j + 1u, linear);
+        if (j == 0u && !tlas_key_usable(keys[0])) nodes[0] = pose_tlas_header(P, 0u, linear);
     }
     __threadfence();
     __syncthreads();
@@ -1463,6 +1537,19 @@ void launch_paths_instanced(const PathArgs& args, const TlasScene& scene, uint32
     uint32_t slots = levels > 1 ? levels - 1 : 1;
     if (stack_slots > slots) slots = stack_slots;
     hipLaunchKernelGGL(path_kernel_instanced, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene);
+}
+
+void launch_pose_tlas_build(const blok_pose* poses, uint32_t n, const ModelDesc* models, uint32_t n_models, float vs, const float cam[3], TlasNode* nodes,
+                            hipStream_t stream) {
+    if (n == 0u || n > kTlasMax) return;
+    hipLaunchKernelGGL(pose_tlas_build_kernel, dim3(1), dim3(kTlasBuildThreads), 0, stream, poses, n, models, n_models, vs, cam[0], cam[1], cam[2], nodes);
+}
+
+void launch_paths_posed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream) {
+    if (n_blocks == 0) return;
+    uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
+    if (stack_slots > slots) slots = stack_slots;
+    hipLaunchKernelGGL(path_kernel_posed, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses);
 }
 
 void launch_tlas_build(const blok_instance* instances, uint32_t n, const ModelDesc* models, uint32_t n_models, TlasNode* nodes, hipStream_t stream) {

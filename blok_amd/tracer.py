@@ -1086,6 +1086,56 @@ class HipTracer:
                                                                _ffi.ptr(out), C.byref(frames)))
         return out, frames.value
 
+    # -- posed models in the path-traced frame (blok_hip.h, "Path-traced frames with poses") ------------------------------------------------
+    def trace_paths_posed(self, cam: np.ndarray, instances, poses, spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None):
+        """trace_paths_instanced with `poses` (POSE records) behind the instances: the planes dict plus "ids" (POSE_ID | index where a pose
+        wins the first hit).  A posed hit's normal is its face's own world normal."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
+        planes = {k: np.zeros((h, w, 4), dtype=np.float32) for k in ("color", "world_pos", "normal_roughness", "albedo_metallic")}
+        planes["ids"] = np.zeros((h, w), dtype=np.uint32)
+        g = GBuffer(*[planes[k].ctypes.data for k in ("color", "world_pos", "normal_roughness", "albedo_metallic")])
+        self._check(self._lib.blok_hip_trace_paths_posed(self._ctx, _ffi.ptr(cam), x0, y0, w, h, spp, max_bounces, frame_index, self._table(inst),
+                                                         len(inst), self._table(p), len(p), C.byref(g), _ffi.ptr(planes["ids"])))
+        return planes
+
+    def trace_paths_posed_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, poses_ptr: int, n_poses: int, color_ptr: int = 0,
+                                 world_pos_ptr: int = 0, normal_roughness_ptr: int = 0, albedo_metallic_ptr: int = 0, ids_ptr: int = 0,
+                                 spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None, stream: int = 0):
+        """Asynchronous: device tables, float4 device planes and id plane (any may be 0)."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        g = GBuffer(color_ptr, world_pos_ptr, normal_roughness_ptr, albedo_metallic_ptr)
+        self._check(self._lib.blok_hip_trace_paths_posed_device(self._ctx, _ffi.ptr(cam), x0, y0, w, h, spp, max_bounces, frame_index,
+                                                                C.c_void_p(instances_ptr), int(n_instances), C.c_void_p(poses_ptr), int(n_poses),
+                                                                C.byref(g), C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def trace_paths_posed_ref_device(self, cam: np.ndarray, instances_ptr: int, n_instances: int, poses_ptr: int, n_poses: int, color_ptr: int = 0,
+                                     world_pos_ptr: int = 0, normal_roughness_h_ptr: int = 0, albedo_metallic_u8_ptr: int = 0, motion_h_ptr: int = 0,
+                                     prev_view_proj=None, ids_ptr: int = 0, spp: int = 8, max_bounces: int = 2, frame_index: int = 0,
+                                     rect=None, stream: int = 0):
+        """trace_paths_instanced_ref_device with a device pose table behind the instances."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        g = _ffi.GBufferRef(color_ptr, world_pos_ptr, normal_roughness_h_ptr, albedo_metallic_u8_ptr, motion_h_ptr)
+        m = None if prev_view_proj is None else (C.c_float * 16)(*[float(v) for v in np.asarray(prev_view_proj, dtype=np.float32).reshape(-1)])
+        self._check(self._lib.blok_hip_trace_paths_posed_ref_device(self._ctx, _ffi.ptr(cam), x0, y0, w, h, spp, max_bounces, frame_index,
+                                                                    C.c_void_p(instances_ptr), int(n_instances), C.c_void_p(poses_ptr), int(n_poses),
+                                                                    m, C.byref(g), C.c_void_p(ids_ptr), C.c_void_p(stream)))
+
+    def draw_frame_rt_posed(self, cam: np.ndarray, instances, poses, spp: int = 8, max_bounces: int = 2, settings=None):
+        """draw_frame_rt_instanced with the path pass over the world, `instances` and `poses`: (RGBA8 (h, w) uint32, frames rendered so far)."""
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        frames = C.c_uint32()
+        self._check(self._lib.blok_hip_draw_frame_rt_posed(self._ctx, _ffi.ptr(cam), spp, max_bounces, C.byref(settings) if settings is not None else None,
+                                                           self._table(inst), len(inst), self._table(p), len(p), _ffi.ptr(out), C.byref(frames)))
+        return out, frames.value
+
     def draw_frame_rt_instanced_motion(self, cam: np.ndarray, instances: np.ndarray, spp: int = 8, max_bounces: int = 2, settings=None):
         """draw_frame_rt_instanced with object motion: the context keeps the previous frame's table, and an instance whose index, model
         and usability carry over from it is reprojected where it was.  (RGBA8 (h, w) uint32, frames rendered so far)."""
@@ -1126,6 +1176,19 @@ class HipTracer:
         out = np.zeros((cap, 8), dtype=np.int32)
         self._check(self._lib.blok_hip_debug_build_tlas(self._ctx, C.c_void_p(instances_ptr), int(n_instances), _ffi.ptr(out), cap, C.byref(count)))
         return out[:count.value]
+
+    def debug_build_pose_tlas(self, cam: np.ndarray, poses_ptr: int, n_poses: int) -> np.ndarray:
+        """The pose BVH of a device pose table for a launch from `cam` (pose_tlas_core.h), as an (nodes, 8) int32 array."""
+        count = C.c_uint32()
+        cap = 2 * (1 << max(0, int(n_poses) - 1).bit_length())
+        out = np.zeros((cap, 8), dtype=np.int32)
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        self._check(self._lib.blok_hip_debug_build_pose_tlas(self._ctx, _ffi.ptr(cam), C.c_void_p(poses_ptr), int(n_poses), _ffi.ptr(out), cap, C.byref(count)))
+        return out[:count.value]
+
+    def set_pose_tlas(self, enabled=True):
+        """Posed path launches with (default) or without the pose BVH: the frames are identical."""
+        self._check(self._lib.blok_hip_set_pose_tlas(self._ctx, int(bool(enabled))))
 
     def trace_paths(self, cam: np.ndarray, spp: int = 8, max_bounces: int = 2, frame_index: int = 0, rect=None):
         """raygen.rgen's sample/bounce loop: dict of (h, w, 4) float32 planes

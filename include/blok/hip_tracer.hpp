@@ -550,6 +550,25 @@ public:
         check(blok_hip_trace_paths_instanced(m_ctx, &c, 0, 0, m_width, m_height, sampleCount, maxBounces, frameIndex, instances.data(),
                                              static_cast<uint32_t>(instances.size()), &planesHost, m_instanceIds.data()));
     }
+    // drawFrameRTInstanced with posed models (blok_pose: any rotation, scale, mirror, shear) behind the instances; camera-only motion
+    const std::vector<uint32_t>& drawFrameRtPosed(Camera& cam, const std::vector<blok_instance>& instances, const std::vector<blok_pose>& poses,
+                                                  uint32_t sampleCount = 8, uint32_t maxBounces = 2) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_pixels.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_draw_frame_rt_posed(m_ctx, &c, sampleCount, maxBounces, nullptr, instances.data(), static_cast<uint32_t>(instances.size()),
+                                           poses.data(), static_cast<uint32_t>(poses.size()), m_pixels.data(), &m_frameIndex));
+        cam.cameraChanged = false;
+        return m_pixels;
+    }
+    // tracePathsInstanced with posed models; instanceIds() holds BLOK_POSE_ID | index where a pose wins the first hit
+    void tracePathsPosed(Camera& cam, const std::vector<blok_instance>& instances, const std::vector<blok_pose>& poses, const blok_gbuffer& planesHost,
+                         uint32_t sampleCount = 8, uint32_t maxBounces = 2, uint32_t frameIndex = 0) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_instanceIds.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_trace_paths_posed(m_ctx, &c, 0, 0, m_width, m_height, sampleCount, maxBounces, frameIndex, instances.data(),
+                                         static_cast<uint32_t>(instances.size()), poses.data(), static_cast<uint32_t>(poses.size()), &planesHost,
+                                         m_instanceIds.data()));
+    }
     void sharpen(const uint32_t* rgba8Dev, uint32_t* outRgba8Dev, float strength = 0.5f, void* stream = nullptr) {
         check(blok_hip_sharpen_device(m_ctx, rgba8Dev, strength, outRgba8Dev, stream));
     }

@@ -588,7 +588,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.19: neighbour-count rules stepped over the resident volume (blok_hip_volume_automaton): smooth, despeckle, fill pits, caves, Life.
  * 1.20: procedural terrain reduced to coarse levels without a volume (blok_hip_terrain_reduce): the far field built at any time.
  * 1.21: a view at rest restarts every listed ray where its own counted walk ended (blok_hip_debug.h: blok_hip_set_beam_cache mode 4, the default).
- * 1.22: instanced models traced under any rotation, scale, mirror or shear (blok_pose; blok_hip_trace_primary_posed*, blok_hip_trace_rays_posed*). */
+ * 1.22: instanced models traced under any rotation, scale, mirror or shear (blok_pose; blok_hip_trace_primary_posed*, blok_hip_trace_rays_posed*).
+ * 1.23: posed models in the path-traced frame, with true world normals (blok_hip_trace_paths_posed*, blok_hip_draw_frame_rt_posed). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -624,7 +625,7 @@ uint32_t blok_hip_abi_version(void);
  *   - Composition, the tie rule, the any-hit shadow rule and the BVH's ordering rule are unchanged, and so is the object-motion map
  *     (it does not contain the scale).
  *   Not built: negative exponents (a model traced at any real scale, turned or sheared, is a blok_pose, "Posed models" below, since ABI
- *   1.22; the path-traced frame takes lattice instances only).  (A scaled model is baked into the resident volume by blok_hip_volume_stamp_affine, since ABI 1.18:
+ *   1.22, and in the path-traced frame since ABI 1.23).  (A scaled model is baked into the resident volume by blok_hip_volume_stamp_affine, since ABI 1.18:
  *   blok_affine_from_instance, blok_world.h, folds a placement and the exponent into its record; the other volume entries refuse one, below.)
  * Instance ids.  Each pixel or ray gets the index of the winning instance, or BLOK_INSTANCE_NONE for the world or a miss.
  * Scope.  The primary frame, explicit rays and the path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced
@@ -704,9 +705,10 @@ int blok_hip_trace_rays_instanced_device(blok_hip_ctx* ctx, const blok_ray* rays
  *   the model's own voxel box lies in [-32768, 32768) (the record's voxel is int16).  At most 2^31 - 1 poses.  A singular m is legal: the
  *   rule needs no inverse.  Host tables fail with BLOK_ERR_INVALID_ARG naming the first pose that breaks a limit (blok_hip_check_poses does
  *   this check alone); the kernels of the device-table entries skip such a pose.
- * Scope.  The primary frame and explicit rays.  The path-traced frame (blok_hip_trace_paths_instanced*, blok_hip_draw_frame_rt_instanced*),
- *   object motion, the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay as they are and never receive a
- *   pose table.  A posed model that has stopped can be baked about where it was seen: blok_affine_from_pose (blok_world.h). */
+ * Scope.  The primary frame, explicit rays and, since ABI 1.23, the path-traced frame (blok_hip_trace_paths_posed*,
+ *   blok_hip_draw_frame_rt_posed, below).  Object motion, the sun map, blok_hip_draw_frame_accumulate and the tile and multi-GPU entries stay
+ *   as they are and never receive a pose table.  A posed model that has stopped can be baked about where it was seen: blok_affine_from_pose
+ *   (blok_world.h). */
 typedef struct blok_pose {     /* 64 bytes */
     uint32_t model;
     float    m[3][3];          /* world -> local: row k gives local axis k */
@@ -762,6 +764,52 @@ int blok_hip_trace_paths_instanced(blok_hip_ctx* ctx, const blok_camera* cam, ui
 int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
                                      const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
                                      uint32_t* out_rgba8_host, uint32_t* out_frame_count);
+
+/* Path-traced frames with poses (ABI 1.23): the entries above with a pose table behind the instances.
+ * Order.  Every ray of the path loop is composed in the order of "Posed models": the world, instances 0 .. n-1, poses 0 .. p-1.  A candidate
+ *   replaces the record only with a strictly smaller t; ties go to the world, then the instances, then the lowest pose.  A pose's ray goes
+ *   over by the rule of "Ray into local space", unchanged, and its walk is the model's own canonical walk, unchanged.
+ * Primary and bounce rays.  The closest hit of all three; the poses are asked with tmax = the best t so far.
+ * Shadow rays.  Any hit.  The instances are asked only if the world walk found nothing, and the poses only if the instances found nothing;
+ *   both on the uncapped interval [0.001, 1000) (the sun map caps the world walk alone).
+ * The normal of a posed hit.  Local face 2k + n of pose P, s = +1 for n = 0 and -1 for n = 1, every operation rounded separately to float:
+ *     v_j = s * m_kj          q = fl(fl(fl(v_0 v_0) + fl(v_1 v_1)) + fl(v_2 v_2))
+ *   If !(q > 0) (a zero row of a singular m, or underflow) the normal is the axis normal of the shade face of "RGBA of the primary frame".
+ *   Otherwise len = sqrt(q) correctly rounded and n_j = fl(v_j / len) + 0.0f (every zero is +0, as in an axis normal).  Then the path
+ *   loop's own statements on n: the flip against the ray, the G-buffer, the shadow ray's origin hit_pos + n * 0.001, n.l.  For a pose
+ *   made by blok_pose_from_instance (also of a model under blok_hip_model_set_scale) this is the lattice instance's axis normal bit for
+ *   bit, and the whole frame is that of the same placements given as instances.
+ * The sampling frame.  tangent = normalize(cross(up, n)), bitangent = cross(n, tangent) for every hit of such a launch (for an axis normal
+ *   the division is by 1: world and instance hits keep their values).
+ * G-buffer.  The composed first hit (sample 0, bounce 0); world_pos = o + t d; normal_roughness holds the normal above; out_instance holds
+ *   BLOK_POSE_ID | index where a pose wins, the instance index or BLOK_INSTANCE_NONE otherwise.  The motion plane stays camera-only on pose
+ *   pixels: there is no object motion for poses (prev o cur^-1 needs an inverse and a tracking rule), so a moving pose may ghost in the
+ *   denoiser and TAA.
+ * The frame is DEFINED as if every pose were tested for every ray.  Each launch first builds a second BVH, over the poses, on the stream (one
+ *   workgroup; up to 4096 poses, above that every ray loops over the table; leaf boxes argued in pose_tlas_core.h; a table with a usable
+ *   pose whose box has no bound — a near-singular m — loops too): slower, the same result.  blok_hip_debug.h: blok_hip_set_pose_tlas.
+ * Empty tables.  With n_poses == 0 each entry is the instanced entry of the same name: the same launches, the same bytes.  With
+ *   n_instances == 0 and poses present the posed kernel runs with no instance tree.
+ * Errors as the instanced entries', in their order; a bad pose of a host table is named as blok_hip_check_poses names it, outputs untouched.
+ *   Device tables skip what the host entries refuse.  Both tables are read in stream order; after the first call at a given size the
+ *   device entries allocate nothing and do not synchronise.
+ * blok_hip_draw_frame_rt_posed: blok_hip_draw_frame_rt_instanced's chain over this path pass (host tables, both checked first): the same
+ *   post state and frame counter, camera-only motion; like that entry it empties the previous table of
+ *   blok_hip_draw_frame_rt_instanced_motion. */
+int blok_hip_trace_paths_posed_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                      uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev, uint32_t n_instances,
+                                      const blok_pose* poses_dev, uint32_t n_poses, const blok_gbuffer* planes_dev, uint32_t* out_instance_dev,
+                                      void* hip_stream);
+int blok_hip_trace_paths_posed_ref_device(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                                          uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_dev, uint32_t n_instances,
+                                          const blok_pose* poses_dev, uint32_t n_poses, const float prev_view_proj[16],
+                                          const blok_gbuffer_ref* planes_dev, uint32_t* out_instance_dev, void* hip_stream);
+int blok_hip_trace_paths_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                               uint32_t max_bounces, uint32_t frame_index, const blok_instance* instances_host, uint32_t n_instances,
+                               const blok_pose* poses_host, uint32_t n_poses, const blok_gbuffer* planes_host, uint32_t* out_instance_host);
+int blok_hip_draw_frame_rt_posed(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces, const blok_denoise_settings* settings,
+                                 const blok_instance* instances_host, uint32_t n_instances, const blok_pose* poses_host, uint32_t n_poses,
+                                 uint32_t* out_rgba8_host, uint32_t* out_frame_count);
 
 /* Object motion for moving instances (ABI 1.3).
  * Tracking.  Instance i of this frame's table `cur` is tracked when i < n_prev, prev[i].model == cur[i].model and both records pass the

@@ -277,6 +277,15 @@ int blok_hip_multi_debug_deny_peer_access(blok_hip_multi* m, int deny);
 int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_dev, uint32_t n_instances, void* out_nodes_host, size_t capacity,
                               uint32_t* out_count);
 
+/* The pose BVH of the posed path frame (pose_tlas_core.h; the same TlasNode format; node 0's first word is the linear flag) for a device table
+ * of 1 .. 4096 poses and the launch's camera (its position is one of the ray origins the leaf boxes are argued for): built on the default
+ * stream and downloaded, as blok_hip_debug_build_tlas does. */
+int blok_hip_debug_build_pose_tlas(blok_hip_ctx* ctx, const blok_camera* cam, const blok_pose* poses_dev, uint32_t n_poses, void* out_nodes_host,
+                                   size_t capacity, uint32_t* out_count);
+/* enabled = 0: posed path launches build no pose BVH and every ray loops over the pose table (the frame's definition); default 1.  The frames
+ * are identical. */
+int blok_hip_set_pose_tlas(blok_hip_ctx* ctx, int enabled);
+
 /* Read-back of an instanced model (blok_hip_model_create, blok_hip_volume_capture_model), for the tests that pin a captured model byte for
  * byte: the node array (16 bytes per node, root first) and the material array (one id per voxel) as they lie in device memory, and the
  * model's lattice.  Either array pointer may be NULL (then its capacity is not looked at); out_info may be NULL.  BLOK_ERR_INVALID_ARG: an

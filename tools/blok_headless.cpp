@@ -77,6 +77,9 @@
 //          printed.  May be given more than once.  Refused with --rt (the path-traced frame takes no pose table), --far, --vox, --obj,
 //          --load-volume and more than one device.  (--pose N with a bare number is the camera pose.)
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
+//   --rt-posed: --rt's chain with the --pose models in it (blok_hip_draw_frame_rt_posed): they cast and receive shadows and show in bounce rays,
+//          with their faces' true normals.  Needs at least one --pose FILE.vox@...; prints the written frame's camera as --pose does.  Refused
+//          without a --pose and with what --pose refuses.
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
 //   --no-rccl: peer copies even when RCCL is there
@@ -128,6 +131,7 @@ struct Options {
     struct Paste { std::string path; double position[3], yaw_deg, scale; };
     std::vector<Paste> paste;             // .vox models resampled into the terrain, turned and scaled
     std::vector<Paste> posed;             // .vox models traced as posed models over the world, turned and scaled
+    bool rt_posed = false;                // --rt-posed: the ray-tracing path with the posed models in it
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
@@ -693,6 +697,7 @@ private:
             const auto t0 = clock::now();
             m_tracer->beginFrame();
             if (m_multi) m_multi->drawFrame(m_camera, m_multiFrame);
+            else if (m_opt.rt_posed) m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp);
             else if (m_opt.rt && m_opt.far) m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp);
             else if (m_opt.rt) m_tracer->drawFrameRT(m_camera, m_opt.spp);
             else if (!m_poses.empty()) m_tracer->drawFramePosed(m_camera, m_instances, m_poses);
@@ -701,12 +706,13 @@ private:
             m_tracer->endFrame();
             const double ms = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
             if (m_multi) std::cout << "frame " << f << ": " << ms << " ms (" << m_multi->deviceCount() << " ranks, incl. device->host copy of the RGBA8 frame)\n";
-            else if (m_opt.rt) std::cout << "frame " << f << ": " << ms << " ms (path trace " << m_opt.spp << " spp, denoise, TAA, tonemap, sharpen; incl. device->host copy)\n";
+            else if (m_opt.rt || m_opt.rt_posed) std::cout << "frame " << f << ": " << ms << " ms (path trace " << m_opt.spp << " spp, denoise, TAA, tonemap, sharpen; incl. device->host copy)\n";
             else std::cout << "frame " << f << ": " << ms << " ms (incl. device->host copy of "
                            << m_tracer->hits().size() * sizeof(blok_hit) / 1e6 << " MB)\n";
-            if (f + 1 < m_opt.frames || !m_opt.rt) m_camera.processKeyboard('W', 0.016f);
+            if (f + 1 < m_opt.frames || !(m_opt.rt || m_opt.rt_posed)) m_camera.processKeyboard('W', 0.016f);
         }
-        const auto& single = m_opt.rt && m_opt.far ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
+        const auto& single = m_opt.rt_posed ? m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp)
+                             : m_opt.rt && m_opt.far ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
                              : m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_poses.empty() ? drawPosed() : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
         if (m_multi) {                                       // the partitioned frame must be the single-device frame
             m_multi->drawFrame(m_camera, m_multiFrame);
@@ -723,9 +729,11 @@ private:
             for (float v : cam) std::printf(" %.9g", v);
             std::printf("\n");
             std::fflush(stdout);
-            size_t won = 0;
-            for (uint32_t id : m_poseIds) won += id != BLOK_INSTANCE_NONE && (id & BLOK_POSE_ID) != 0u;
-            std::cout << "pose: poses won " << won << " of " << m_poseIds.size() << " pixels\n";
+            if (!m_opt.rt_posed) {                           // (the path-traced chain keeps no id plane)
+                size_t won = 0;
+                for (uint32_t id : m_poseIds) won += id != BLOK_INSTANCE_NONE && (id & BLOK_POSE_ID) != 0u;
+                std::cout << "pose: poses won " << won << " of " << m_poseIds.size() << " pixels\n";
+            }
         }
         const auto& px = m_multi ? m_multiFrame : single;
         std::ofstream ppm(m_opt.out, std::ios::binary);
@@ -883,6 +891,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--save-volume")) opt.save_volume = next();
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
+        else if (!std::strcmp(argv[i], "--rt-posed")) opt.rt_posed = true;
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
         else if (!std::strcmp(argv[i], "--dense-exchange")) opt.dense_exchange = true;
@@ -891,6 +900,14 @@ int main(int argc, char** argv) {
     }
     if (!opt.posed.empty() && opt.rt) {
         std::fprintf(stderr, "--pose FILE.vox@... is refused with --rt: posed models are traced in first-hit frames only, the path-traced frame takes no pose table\n");
+        return 2;
+    }
+    if (opt.rt_posed && opt.posed.empty()) {
+        std::fprintf(stderr, "--rt-posed path-traces posed models: give at least one --pose FILE.vox@X,Y,Z,YAW_DEG[,SCALE]\n");
+        return 2;
+    }
+    if (opt.rt_posed && (opt.far || !opt.vox.empty() || !opt.obj.empty() || !opt.load_volume.empty() || opt.devices.size() > 1)) {
+        std::fprintf(stderr, "--rt-posed path-traces its --pose models over the generated scene or a --terrain, on one device: leave --far, --vox, --obj, --load-volume and --devices out\n");
         return 2;
     }
     if (opt.far_direct && !opt.far) { std::fprintf(stderr, "--far-direct and --far-rings need --far K[,MIN]\n"); return 2; }
