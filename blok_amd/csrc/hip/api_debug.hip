@@ -399,6 +399,19 @@ int blok_hip_beam_cache_start_counters(const blok_hip_ctx* ctx, uint64_t* out_fr
     return BLOK_OK;
 }
 
+int blok_hip_set_packed_fill(blok_hip_ctx* ctx, uint32_t units_per_wave) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    ctx->beam_cache.packed_fill = units_per_wave;        // (read by the next launch; the lists and the bounds are the same for both forms)
+    return BLOK_OK;
+}
+
+int blok_hip_packed_fill_counters(const blok_hip_ctx* ctx, uint64_t* out_one_launch_frames, uint64_t* out_fill_only_workgroups) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (out_one_launch_frames) *out_one_launch_frames = ctx->beam_cache.one_launch_frames;
+    if (out_fill_only_workgroups) *out_fill_only_workgroups = ctx->beam_cache.fill_only_workgroups;
+    return BLOK_OK;
+}
+
 int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills) {
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (out_hits) *out_hits = ctx->beam_cache.hits;

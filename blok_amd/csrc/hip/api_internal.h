@@ -186,6 +186,8 @@ struct blok_hip_ctx {
         size_t list_capacity = 0, words_capacity = 0;       // entries per list; words per table
         uint64_t list_builds = 0;                           // blok_hip_beam_cache_list_builds
         uint64_t start_hits = 0, start_other_key = 0;       // blok_hip_beam_cache_start_counters: packed hits that walked from the starts; ... that found another start key
+        uint32_t packed_fill = BLOK_PACKED_FILL;            // blok_hip_set_packed_fill: fill units per workgroup of a packed frame's one launch; 0 = the fill in a launch of its own
+        uint64_t one_launch_frames = 0, fill_only_workgroups = 0;      // blok_hip_packed_fill_counters
         int last_starts = 0;                                // the latest rectangle launch: 0 no starts, 1 it walked from them (or counted them), 2 it found another start key
         int last_list = 0;                                  // the latest rectangle launch: 0 no list, 1 it counted and issued the build, 2 it walked packed
         uint32_t last_w = 0, last_h = 0;                    // ... and its rectangle (blok_hip_beam_cache_download_list)

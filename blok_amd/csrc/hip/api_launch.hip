@@ -626,8 +626,14 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
         blok::TraceArgs fill = args;
         fill.order = nullptr; fill.rank_of = nullptr; fill.launched = 0u; fill.order_sx = fill.order_sy = 0u; fill.n_strip = 0u; fill.fallback_tiles = nullptr;
         fill.miss_in_walk = 0u;
-        blok::launch_beam_fill(mode, fill, n_beams, sl.d_fine, stream);
-        if (listed.use_list && starts.use == blok::BeamStarts::Use) blok::launch_packed_walk_own(fill, sl.d_start, sl.d_list, sl.d_table, sl.n_groups, stream);
+        // a list with groups: the fill rides in the walk's grid as fill units (blok_hip_set_packed_fill); an all-sky view has the fill alone
+        const bool one_launch = listed.use_list && sl.n_groups > 0u && B.packed_fill > 0u;
+        if (!one_launch) blok::launch_beam_fill(mode, fill, n_beams, sl.d_fine, stream);
+        if (one_launch) {
+            const uint32_t tail = starts.use == blok::BeamStarts::Use ? blok::launch_packed_frame_own(fill, sl.d_start, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream)
+                                                                      : blok::launch_packed_frame(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream);
+            B.one_launch_frames += 1u; B.fill_only_workgroups += tail;
+        } else if (listed.use_list && starts.use == blok::BeamStarts::Use) blok::launch_packed_walk_own(fill, sl.d_start, sl.d_list, sl.d_table, sl.n_groups, stream);
         else if (listed.use_list) blok::launch_packed_walk(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, stream);
         else if (starts.count_own) {
             // mode 4: the count launch also leaves every ray's own start and restarted trips; the build sorts by those and writes the starts in list order

@@ -330,6 +330,17 @@ void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t
 void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, hipStream_t stream);
 void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream);
 void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
+// The packed frame in ONE launch: the two walks above, and in the same grid the miss pixels launch_beam_fill writes in front of them (with
+// the finer bounds and miss_in_walk 0: every pixel of the rectangle whose wave tile is empty by `fine`) as fill units (fill_units.h), at
+// most units_per_wave to a workgroup.  The walk is bound by vector issue and the fill by stores, and they touch disjoint pixels: in one
+// grid the stores drain beside the walk.  -> the workgroups that only fill (the grid's tail), 0 when every unit rides on a walk wave.
+// n_groups > 0 and units_per_wave >= 1; the same bytes as the two launches.
+#ifndef BLOK_PACKED_FILL
+#define BLOK_PACKED_FILL 4             // the library's default units_per_wave (blok_hip_set_packed_fill; 0: two launches): profiles/packed_fill_ab.txt
+#endif
+uint32_t launch_packed_frame(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream);
+uint32_t launch_packed_frame_own(const TraceArgs& args, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave,
+                                 hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

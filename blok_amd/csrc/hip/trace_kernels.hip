@@ -5,6 +5,7 @@
 #include "trace_core.h"
 #include "path_core.h"
 #include "beam.h"
+#include "fill_units.h"
 
 namespace blok {
 
@@ -658,6 +659,92 @@ __global__ __launch_bounds__(kBlock) void packed_walk_own_kernel(const TraceArgs
     RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
     r.tmin = fmaxf(r.tmin, t0);
     trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+}
+
+// ---- the packed frame in one launch (trace_kernels.h: launch_packed_frame; fill_units.h) -------------------------------------------------------
+// The fill units of this workgroup: lane l of a unit owns one pixel of the rectangle and writes its miss iff the pixel's wave tile is
+// empty by the finer bounds — what beam_fill_kernel writes in front of a packed walk, and the complement of what pack_build_kernel lists.
+// A wave's stores of a unit are whole octets of one row: 128 B of records and 32 B of RGBA8 each, up to 1 KB and 256 B contiguous.
+// Two choices, both settled by measurement (profiles/packed_fill_ab.txt) and kept as build switches for scripts/build_variant.sh:
+#ifndef BLOK_PACKED_FILL_FIRST
+#define BLOK_PACKED_FILL_FIRST 0       // 0: a walk wave writes its units behind its walk; 1: in front of it, where its first loads then wait for the stores
+#endif
+#ifndef BLOK_PACKED_FILL_NT
+#define BLOK_PACKED_FILL_NT 1          // 1: non-temporal stores (nobody on the device reads a miss back, and the walks of the frames in flight keep the cache); 0: write_miss's
+#endif
+__device__ __forceinline__ void fill_units_of_workgroup(const TraceArgs& A, const float* fine, const uint32_t n_units, const uint32_t units_x) {
+    if (!A.out && !A.out_rgba) return;
+    const uint32_t lane = threadIdx.x, tiles_x = (A.w + kWaveW - 1u) / kWaveW;
+    // four units at a time, their bounds loaded in front of their stores: loads and stores share one counter and return in order, so a load
+    // behind a store waits for that store to be acknowledged — once per four units here, not once per unit
+    constexpr uint32_t kBatch = 4u;
+    for (uint32_t i = 0u; fill_unit_of(blockIdx.x, i, gridDim.x) < n_units; i += kBatch) {
+        float bound[kBatch];
+        size_t at[kBatch];
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; ++j) {
+            const uint32_t u = fill_unit_of(blockIdx.x, i + j, gridDim.x);
+            const uint32_t ry = fill_unit_row(u, units_x), rx = fill_unit_x0(u, units_x) + lane;
+            at[j] = static_cast<size_t>(ry) * A.w + rx;
+            bound[j] = u < n_units && rx < A.w && ry < A.h ? fine[(ry / kWaveH) * tiles_x + rx / kWaveW] : 0.0f;      // (0: nothing to write)
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; ++j)
+            if (bound[j] >= kBeamNone) {
+#if BLOK_PACKED_FILL_NT
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));      // write_miss's bytes (trace_core.h)
+                if (A.out) __builtin_nontemporal_store(u32x4{0xBF800000u, 0u, 0u, 0x00FF0000u}, reinterpret_cast<u32x4*>(A.out + at[j]));
+                if (A.out_rgba) __builtin_nontemporal_store(kSkyRgba, A.out_rgba + at[j]);
+#else
+                write_miss(Sink{A.out ? A.out + at[j] : nullptr, A.out_rgba ? A.out_rgba + at[j] : nullptr});
+#endif
+            }
+    }
+}
+
+// packed_walk_kernel's walk for the workgroups [0, n_groups), in the table's order, and every workgroup's fill units: those of the grid's
+// tail [n_groups, gridDim.x) write units and nothing else.  A padding lane of a group does not leave before its units are written.
+__global__ __launch_bounds__(kBlock) void packed_frame_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table, const uint32_t n_groups,
+                                                              const uint32_t n_units, const uint32_t units_x) {
+    static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
+    extern __shared__ uint4 lds_stack[];
+    const uint32_t lane = threadIdx.x;
+    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    if (blockIdx.x < n_groups) {
+        const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
+        const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+        const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
+        if (entry != kPackPad && rx < A.w && ry < A.h) {
+            const float t0 = fine[(ry / kWaveH) * ((A.w + kWaveW - 1u) / kWaveW) + rx / kWaveW];
+            const size_t at = static_cast<size_t>(ry) * A.w + rx;
+            RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+            r.tmin = fmaxf(r.tmin, t0);
+            trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+        }
+    }
+    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+}
+
+// The same over packed_walk_own_kernel's walk, every listed ray from its own start.
+__global__ __launch_bounds__(kBlock) void packed_frame_own_kernel(const TraceArgs A, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table,
+                                                                  const uint32_t n_groups, const uint32_t n_units, const uint32_t units_x) {
+    static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
+    extern __shared__ uint4 lds_stack[];
+    const uint32_t lane = threadIdx.x;
+    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    if (blockIdx.x < n_groups) {
+        const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
+        const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+        const float t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
+        const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
+        if (entry != kPackPad && rx < A.w && ry < A.h) {
+            const size_t at = static_cast<size_t>(ry) * A.w + rx;
+            RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+            r.tmin = fmaxf(r.tmin, t0);
+            trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+        }
+    }
+    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
 }
 
 // ---- joint launch: the pre-pass waves and the walk waves in ONE grid, statically ------------------------------------------
@@ -1491,6 +1578,21 @@ void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, cons
 void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream) {
     if (n_groups == 0 || !pack_applies(args) || !fine || !list || !table) return;
     hipLaunchKernelGGL(packed_walk_kernel, dim3(n_groups), dim3(kBlock), frame_lds_bytes(args), stream, args, fine, list, table);
+}
+
+uint32_t launch_packed_frame(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream) {
+    if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !fine || !list || !table) return 0u;
+    const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
+    hipLaunchKernelGGL(packed_frame_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, fine, list, table, n_groups, g.n_units, g.units_x);
+    return g.grid - n_groups;
+}
+
+uint32_t launch_packed_frame_own(const TraceArgs& args, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave,
+                                 hipStream_t stream) {
+    if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !slot_start || !fine || !list || !table) return 0u;
+    const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
+    hipLaunchKernelGGL(packed_frame_own_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, fine, list, table, n_groups, g.n_units, g.units_x);
+    return g.grid - n_groups;
 }
 
 size_t frame_lds_bytes(const TraceArgs& args) { return static_cast<size_t>(args.levels > 1 ? args.levels - 1 : 1) * kBlock * sizeof(uint4); }

@@ -718,6 +718,17 @@ class HipTracer:
         self._check(self._lib.blok_hip_beam_cache_start_counters(self._ctx, C.byref(used), C.byref(other)))
         return int(used.value), int(other.value)
 
+    def set_packed_fill(self, units_per_wave: int):
+        """How a packed launch writes the miss pixels of its empty wave tiles (blok_hip_debug.h): 0 = a fill launch in front of the walk
+        launch; k >= 1 = one launch whose walk workgroups also write at most k fill units of 64 pixels each.  Never changes a result."""
+        self._check(self._lib.blok_hip_set_packed_fill(self._ctx, int(units_per_wave)))
+
+    def packed_fill_counters(self):
+        """(packed launches issued as one launch, workgroups of those launches that only filled)."""
+        frames, tail = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.blok_hip_packed_fill_counters(self._ctx, C.byref(frames), C.byref(tail)))
+        return int(frames.value), int(tail.value)
+
     def beam_cache_refines(self) -> int:
         """Diagnostic: launches so far that issued a view's finer searches behind their walk."""
         n = C.c_uint64(0)

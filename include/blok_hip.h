@@ -589,7 +589,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.20: procedural terrain reduced to coarse levels without a volume (blok_hip_terrain_reduce): the far field built at any time.
  * 1.21: a view at rest restarts every listed ray where its own counted walk ended (blok_hip_debug.h: blok_hip_set_beam_cache mode 4, the default).
  * 1.22: instanced models traced under any rotation, scale, mirror or shear (blok_pose; blok_hip_trace_primary_posed*, blok_hip_trace_rays_posed*).
- * 1.23: posed models in the path-traced frame, with true world normals (blok_hip_trace_paths_posed*, blok_hip_draw_frame_rt_posed). */
+ * 1.23: posed models in the path-traced frame, with true world normals (blok_hip_trace_paths_posed*, blok_hip_draw_frame_rt_posed).
+ * 1.24: a packed frame of a view at rest in one launch, the misses written beside the walk (blok_hip_debug.h: blok_hip_set_packed_fill). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

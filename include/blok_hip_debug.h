@@ -175,6 +175,14 @@ int blok_hip_beam_cache_download_starts(blok_hip_ctx* ctx, int* out_state, float
                                         size_t restarts_capacity);
 /* Packed launches so far that walked from the starts, and that found another start key; either pointer may be null. */
 int blok_hip_beam_cache_start_counters(const blok_hip_ctx* ctx, uint64_t* out_from_starts, uint64_t* out_other_key);
+/* How a packed launch (modes 3 and 4, a list with at least one group) writes the miss pixels of the wave tiles that are empty by the finer
+ * bounds (ABI 1.24): 0 = a fill launch in front of the walk launch, as before; k >= 1 = ONE launch, in which the walk's
+ * workgroups also write fill units — 64 consecutive pixels of a row of the rectangle, one to a lane — at most k to a workgroup, with
+ * workgroups behind the walk's that only fill where the units need them (the default: BLOK_PACKED_FILL in trace_kernels.h).  Every other
+ * launch — the count launch, an all-sky view's, modes 0 to 2, tiles, captures — is as before.  Never changes a result. */
+int blok_hip_set_packed_fill(blok_hip_ctx* ctx, uint32_t units_per_wave);
+/* Packed launches so far that were issued as one launch, and the workgroups of those launches that only filled; either pointer may be null. */
+int blok_hip_packed_fill_counters(const blok_hip_ctx* ctx, uint64_t* out_one_launch_frames, uint64_t* out_fill_only_workgroups);
 /* Launches so far that walked from kept bounds (hits) and that searched into a slot (fills); either pointer may be null. */
 int blok_hip_beam_cache_counters(const blok_hip_ctx* ctx, uint64_t* out_hits, uint64_t* out_fills);
 /* ... and that issued a view's finer searches behind their walk (at most one per fill; such a launch counts as a hit too). */
