@@ -46,6 +46,10 @@ INSTANCE_NONE = 0xFFFFFFFF
 # blok_pose (blok_hip.h, "Posed models"): a model under any affine map, world -> local; ids of pixels a pose wins carry POSE_ID
 POSE = np.dtype([("model", "<u4"), ("m", "<f4", (3, 3)), ("pivot", "<f4", 3), ("local", "<f4", 3)])
 POSE_ID = 0x80000000
+# blok_pose_motion (blok_hip.h, "Object motion for posed models"): prev o cur^-1 of one pose about its pivots; state 0 untracked, 1 identity, 2 moving
+POSE_MOTION = np.dtype([("state", "<u4"), ("a", "<f4", (3, 3)), ("c", "<f4", 3), ("n", "<f4", (3, 3)), ("pivot_cur", "<f4", 3), ("pivot_prev", "<f4", 3),
+                        ("reserved", "<u4", 4)])
+assert POSE_MOTION.itemsize == 128
 # = blok_quad: one merged quad of a volume's surface, 32 bytes
 QUAD = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("reserved", "<u4")])
 QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
@@ -294,6 +298,7 @@ HOST_SYMBOLS = {
     "blok_pose_from_instance": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
     "blok_pose_from_matrix": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.c_void_p]),
     "blok_affine_from_pose": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]),
+    "blok_pose_motion_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "blok_affine_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_scene_generate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -515,6 +520,15 @@ HIP_SYMBOLS = {
                                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_hip_draw_frame_rt_instanced_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                           C.c_void_p, C.POINTER(C.c_uint32)]),
+    "blok_hip_posed_motion_device": (C.c_int, [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p] + [C.c_void_p, C.c_uint32] * 4 +
+                                     [C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blok_hip_denoise_posed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p] +
+                                      [C.c_void_p, C.c_uint32] * 4 + [C.c_void_p, C.c_void_p]),
+    "blok_hip_denoise_posed_ref_device": (C.c_int, [C.c_void_p, C.POINTER(GBufferRef), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p] +
+                                          [C.c_void_p, C.c_uint32] * 4 + [C.c_void_p, C.c_void_p]),
+    "blok_hip_draw_frame_rt_posed_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                      C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "blok_hip_debug_pose_motion_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_hip_volume_refresh_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_volume_flood_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_debug_build_pose_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),

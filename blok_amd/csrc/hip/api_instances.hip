@@ -216,6 +216,9 @@ int trace_rays_placed(blok_hip_ctx* ctx, const char* entry, const blok_ray* rays
 }  // namespace
 
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) { return check_table(ctx, inst, n); }
+int check_placed_device_tables(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n_inst, const blok_pose* poses, uint32_t n_poses) {
+    return check_device_tables(ctx, inst, n_inst, poses, n_poses);
+}
 
 int refuse_scaled_model(blok_hip_ctx* ctx, const char* op, uint32_t model) {
     if (known_model(ctx, model) && ctx->models.desc[model].scale_log2 != 0u)
@@ -269,6 +272,40 @@ blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, c
     M.models = ctx->models.d_desc; M.n_models = ctx->models.d_desc ? static_cast<uint32_t>(ctx->models.desc.size()) : 0u;
     M.vs = ctx->world_voxel_size;
     return M;
+}
+
+int prepare_pose_motion(blok_hip_ctx* ctx, const blok_pose* cur, uint32_t n_cur, const blok_pose* prev, uint32_t n_prev, hipStream_t stream,
+                        const blok_pose_motion** out) {
+    *out = nullptr;
+    if (!n_cur) return BLOK_OK;
+    auto& scratch = ctx->beam_buffers[stream];
+    BLOK_HIP_TRY(ctx, scratch.pose_motion.reserve(n_cur, blok::FreeAfter::work_on(stream)));
+    blok::launch_pose_motion_prepare(cur, n_cur, prev, n_prev, ctx->models.d_desc, ctx->models.d_desc ? static_cast<uint32_t>(ctx->models.desc.size()) : 0u,
+                                     scratch.pose_motion, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    *out = scratch.pose_motion;
+    return BLOK_OK;
+}
+
+blok::PoseMotionTables pose_motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
+                                          uint32_t n_prev, const blok_pose_motion* records, uint32_t n_cur_poses) {
+    blok::PoseMotionTables Q{};
+    Q.inst = motion_tables(ctx, ids, cur, n_cur, prev, n_prev);
+    Q.records = records; Q.n_cur = records ? n_cur_poses : 0u;
+    return Q;
+}
+
+int posed_motion_pass(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev, const blok::PoseMotionTables& tables,
+                      const float prev_view_proj[16], uint16_t* motion_h_dev, float* motion_dev, hipStream_t stream) {
+    blok::PosedMotionArgs a{};
+    a.m = tables;
+    a.world_pos = world_pos_dev;
+    a.x0 = x0; a.y0 = y0; a.w = w; a.h = h; a.frame_w = ctx->width; a.frame_h = ctx->height;
+    for (int k = 0; k < 16; ++k) a.prev_view_proj[k] = prev_view_proj[k];
+    a.motion_h = motion_h_dev; a.motion = motion_dev;
+    blok::launch_posed_motion(a, stream);
+    BLOK_HIP_TRY(ctx, hipGetLastError());
+    return BLOK_OK;
 }
 
 }  // namespace blok_api
@@ -330,8 +367,10 @@ int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_l
     for (int a = 0; a < 3; ++a) { d.lo[a] = own.box_lo[a] * (1 << scale_log2); d.hi[a] = own.box_hi[a] * (1 << scale_log2); }      // (|box| <= 2^22: add_model)
     const int rc = upload_models(ctx);
     if (rc != BLOK_OK) { d = before; return rc; }
-    // the object-motion map (instance_motion.h) does not hold across a change of scale: the next frame's instances are untracked
+    // the object-motion maps (instance_motion.h, pose_motion.h) do not hold across a change of scale: the next frame's instances and poses
+    // are untracked
     ctx->post.rt_prev_n = 0u;
+    ctx->post.rt_prev_n_poses = 0u;
     return BLOK_OK;
 }
 
@@ -625,6 +664,52 @@ int blok_hip_instance_motion_device(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0,
     blok::launch_instance_motion(a, static_cast<hipStream_t>(hip_stream));
     BLOK_HIP_TRY(ctx, hipGetLastError());
     return BLOK_OK;
+}
+
+// ---- object motion of moving poses (pose_motion.h) ---------------------------------------------------------------------------------
+
+int blok_hip_posed_motion_device(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev,
+                                 const uint32_t* ids_dev, const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                 const blok_pose* cur_poses_dev, uint32_t n_cur_poses, const blok_pose* prev_poses_dev, uint32_t n_prev_poses,
+                                 const float prev_view_proj[16], uint16_t* motion_h_dev, float* motion_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!world_pos_dev || !ids_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance motion: world position and id planes are required");
+    if ((n_cur && !cur_dev) || (n_prev && !prev_dev)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    int rc = check_device_tables(ctx, nullptr, 0u, cur_poses_dev, n_cur_poses);
+    if (rc == BLOK_OK) rc = check_device_tables(ctx, nullptr, 0u, prev_poses_dev, n_prev_poses);
+    if (rc != BLOK_OK) return rc;
+    if (!motion_h_dev && !motion_dev) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance motion: no motion output");
+    if (!rect_inside(ctx, x0, y0, w, h)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "rectangle outside the frame");
+    if (!prev_view_proj) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance motion: prevViewProj is required");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((!n_cur || !n_prev) && (!n_cur_poses || !n_prev_poses)) return BLOK_OK;          // nothing is tracked
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const blok_pose_motion* records = nullptr;
+    rc = prepare_pose_motion(ctx, cur_poses_dev, n_cur_poses, prev_poses_dev, n_prev_poses, stream, &records);
+    if (rc != BLOK_OK) return rc;
+    return posed_motion_pass(ctx, x0, y0, w, h, world_pos_dev, pose_motion_tables(ctx, ids_dev, cur_dev, n_cur, prev_dev, n_prev, records, n_cur_poses),
+                             prev_view_proj, motion_h_dev, motion_dev, stream);
+}
+
+int blok_hip_debug_pose_motion_records(blok_hip_ctx* ctx, const blok_pose* cur_host, uint32_t n_cur, const blok_pose* prev_host, uint32_t n_prev,
+                                       blok_pose_motion* out_records_host) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if ((n_cur && !cur_host) || (n_prev && !prev_host)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null pose table with non-zero count");
+    if (n_cur >= BLOK_POSE_ID || n_prev >= BLOK_POSE_ID) return set_error(ctx, BLOK_ERR_INVALID_ARG, "more than 2^31 - 1 poses");
+    if (n_cur && !out_records_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "pose_motion_records: null output");
+    if (!n_cur) return BLOK_OK;
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    StagedBlock d;
+    const auto cur = d.input(cur_host, n_cur);
+    const auto prev = d.input(prev_host, n_prev);
+    const auto out = d.output(out_records_host, n_cur);
+    int rc = d.stage(ctx, "pose_motion_records");
+    if (rc != BLOK_OK) return rc;
+    blok::launch_pose_motion_prepare(d.at(cur), n_cur, d.at(prev), n_prev, ctx->models.d_desc,
+                                     ctx->models.d_desc ? static_cast<uint32_t>(ctx->models.desc.size()) : 0u, d.at(out), nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = set_error(ctx, BLOK_ERR_HIP, std::string("pose_motion_records: ") + hipGetErrorString(e));
+    return d.collect(ctx, "pose_motion_records", rc);
 }
 
 int blok_hip_debug_build_tlas(blok_hip_ctx* ctx, const blok_instance* instances_dev, uint32_t n_instances, void* out_nodes_host, size_t capacity,

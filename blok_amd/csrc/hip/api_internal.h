@@ -91,11 +91,15 @@ struct blok_hip_ctx {
         // (rt_prev_instances; 0 after a reset or a frame without object motion)
         blok::DeviceArray<uint32_t> rt_ids;
         uint32_t rt_prev_n = 0;
+        // blok_hip_draw_frame_rt_posed_motion: ... and of the previous frame's pose table (rt_prev_poses; 0 after a reset, a change of a model's
+        // scale or a frame of any other entry)
+        uint32_t rt_prev_n_poses = 0;
     } post;
     // blok_hip_draw_frame_rt_instanced(_motion): the frame's instance table in device memory (records), grown on demand, and the previous
     // frame's (the motion entry swaps the two after each frame); outside `post`, which ensure_post may reallocate after the upload
     blok::DeviceArray<blok_instance> rt_instances, rt_prev_instances;
     blok::DeviceArray<blok_pose> rt_poses;       // blok_hip_draw_frame_rt_posed: the frame's pose table in device memory, grown on demand
+    blok::DeviceArray<blok_pose> rt_prev_poses;  // blok_hip_draw_frame_rt_posed_motion: the previous frame's (swapped with rt_poses after each frame)
     // device-resident dense store (gpu_build.h: GpuVolume)
     blok::GpuVolume volume;
     bool has_volume = false;
@@ -143,6 +147,7 @@ struct blok_hip_ctx {
         blok::DeviceArray<blok_hit> inst_hits;                           // instanced frames without a record output: the world records the instance pass reads
         blok::DeviceArray<uint32_t> pose_bins;                           // posed frames: the posed binning kernel's lists (the same layout), grown on demand
         blok::DeviceBytes pose_tlas;                                      // posed path launches: the pose BVH (pose_tlas_core.h), grown on demand
+        blok::DeviceArray<blok_pose_motion> pose_motion;                 // posed motion passes: one record per pose (pose_motion.h), grown on demand
         blok::DeviceBytes tlas;                                           // instanced path launches: the instance BVH (tlas_core.h: TlasNode), grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
@@ -397,6 +402,17 @@ int models_follow_voxel_size(blok_hip_ctx* ctx);
 // The id plane and both tables of an object-motion pass (instance_motion.h) with the context's model store and voxel size.
 blok::MotionTables motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
                                  uint32_t n_prev);
+// Null tables with non-zero counts and the pose count's limit, for device tables (the messages every placed entry gives).
+int check_placed_device_tables(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n_inst, const blok_pose* poses, uint32_t n_poses);
+// The poses' motion records of a posed motion pass (pose_motion.h), built on `stream` into its scratch: *out is null when n_cur == 0.
+int prepare_pose_motion(blok_hip_ctx* ctx, const blok_pose* cur, uint32_t n_cur, const blok_pose* prev, uint32_t n_prev, hipStream_t stream,
+                        const blok_pose_motion** out);
+// ... and its tables: motion_tables with the records of n_cur_poses poses.
+blok::PoseMotionTables pose_motion_tables(const blok_hip_ctx* ctx, const uint32_t* ids, const blok_instance* cur, uint32_t n_cur, const blok_instance* prev,
+                                          uint32_t n_prev, const blok_pose_motion* records, uint32_t n_cur_poses);
+// blok_hip_posed_motion_device behind its checks and the records' build.
+int posed_motion_pass(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev, const blok::PoseMotionTables& tables,
+                      const float prev_view_proj[16], uint16_t* motion_h_dev, float* motion_dev, hipStream_t stream);
 void forget_device_activity(const blok_hip_ctx* ctx, bool one_stream = false, hipStream_t stream = nullptr);
 bool rect_inside(const blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
 // The root's assembly of a sparse exchange (blok_hip_scatter_*_tile_frames_device): the ranks' buffers either side by side in

@@ -61,9 +61,10 @@ void blok_denoise_settings_default(blok_denoise_settings* s) {       // renderer
 
 // One frame through temporal accumulation, variance and the a-trous iterations; the frame's planes come in `in` (float4 planes,
 // or the reference-format halves of normal + roughness / motion).  inst: the id plane and tables of a frame with instances (the
-// instanced temporal pass), or null.
+// instanced temporal pass), or null.  posed: the same with the poses' records (the posed temporal pass), or null; never both.
 static int denoise_frame(blok_hip_ctx* ctx, const blok::TemporalArgs& in, const float prev_view_proj[16], uint32_t frame_count,
-                         const blok_denoise_settings* settings, float* out_color_dev, void* hip_stream, const blok::MotionTables* inst = nullptr) {
+                         const blok_denoise_settings* settings, float* out_color_dev, void* hip_stream, const blok::MotionTables* inst = nullptr,
+                         const blok::PoseMotionTables* posed = nullptr) {
     if (!in.color || !in.world_pos || (!in.normal_roughness && !in.normal_roughness_h) || !prev_view_proj || !out_color_dev)
         return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: colour, world position and normal planes, prevViewProj and an output are required");
     blok_denoise_settings def;
@@ -87,7 +88,11 @@ static int denoise_frame(blok_hip_ctx* ctx, const blok::TemporalArgs& in, const 
     t.prev_hist_len = P.hist_len[prev]; t.prev_unit_normals = P.unit_normals[prev];
     t.out_color = P.hist_color[cur]; t.out_moments = P.moments[cur]; t.hist_world_pos = P.world_pos[cur];
     t.out_hist_len = P.hist_len[cur]; t.unit_normals = P.unit_normals[cur]; t.motion = P.motion;
-    if (inst) {
+    if (posed) {
+        blok::TemporalPosedArgs tp{};
+        tp.t = t; tp.m = *posed;
+        blok::launch_temporal_posed(tp, stream);
+    } else if (inst) {
         blok::TemporalInstancedArgs ti{};
         ti.t = t; ti.m = *inst;
         blok::launch_temporal_instanced(ti, stream);
@@ -170,6 +175,53 @@ int blok_hip_denoise_instanced_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_
     t.color = planes->color; t.world_pos = planes->world_pos; t.normal_roughness_h = planes->normal_roughness; t.motion_in_h = planes->motion;
     const blok::MotionTables M = motion_tables(ctx, instance_ids_dev, cur_dev, n_cur, prev_dev, n_prev);
     return denoise_frame(ctx, t, prev_view_proj, frame_count, settings, out_color_dev, hip_stream, &M);
+}
+
+// The posed entries: the instanced entries' checks, then the pose tables', then the records' build on the stream.
+static int denoise_posed(blok_hip_ctx* ctx, const blok::TemporalArgs& t, const float prev_view_proj[16], uint32_t frame_count,
+                         const blok_denoise_settings* settings, const uint32_t* ids_dev, const blok_instance* cur_dev, uint32_t n_cur,
+                         const blok_instance* prev_dev, uint32_t n_prev, const blok_pose* cur_poses_dev, uint32_t n_cur_poses,
+                         const blok_pose* prev_poses_dev, uint32_t n_prev_poses, float* out_color_dev, void* hip_stream) {
+    int rc = check_instanced(ctx, ids_dev, cur_dev, n_cur, prev_dev, n_prev);
+    if (rc == BLOK_OK) rc = check_placed_device_tables(ctx, nullptr, 0u, cur_poses_dev, n_cur_poses);
+    if (rc == BLOK_OK) rc = check_placed_device_tables(ctx, nullptr, 0u, prev_poses_dev, n_prev_poses);
+    if (rc != BLOK_OK) return rc;
+    // (the checks denoise_frame makes before it touches the device, made here before the records' kernel is issued)
+    if (!t.color || !t.world_pos || (!t.normal_roughness && !t.normal_roughness_h) || !prev_view_proj || !out_color_dev)
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: colour, world position and normal planes, prevViewProj and an output are required");
+    if (settings && (settings->atrous_iterations < 0 || settings->atrous_iterations > 5)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: 0..5 a-trous iterations");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const blok_pose_motion* records = nullptr;
+    rc = prepare_pose_motion(ctx, cur_poses_dev, n_cur_poses, prev_poses_dev, n_prev_poses, static_cast<hipStream_t>(hip_stream), &records);
+    if (rc != BLOK_OK) return rc;
+    const blok::PoseMotionTables Q = pose_motion_tables(ctx, ids_dev, cur_dev, n_cur, prev_dev, n_prev, records, n_cur_poses);
+    return denoise_frame(ctx, t, prev_view_proj, frame_count, settings, out_color_dev, hip_stream, nullptr, &Q);
+}
+
+int blok_hip_denoise_posed_device(blok_hip_ctx* ctx, const blok_gbuffer* planes, const float* motion_dev, const float prev_view_proj[16],
+                                  uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* ids_dev,
+                                  const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                  const blok_pose* cur_poses_dev, uint32_t n_cur_poses, const blok_pose* prev_poses_dev, uint32_t n_prev_poses,
+                                  float* out_color_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: null planes");
+    blok::TemporalArgs t{};
+    t.color = planes->color; t.world_pos = planes->world_pos; t.normal_roughness = planes->normal_roughness; t.motion_in = motion_dev;
+    return denoise_posed(ctx, t, prev_view_proj, frame_count, settings, ids_dev, cur_dev, n_cur, prev_dev, n_prev, cur_poses_dev, n_cur_poses,
+                         prev_poses_dev, n_prev_poses, out_color_dev, hip_stream);
+}
+
+int blok_hip_denoise_posed_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_ref* planes, const float prev_view_proj[16],
+                                      uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* ids_dev,
+                                      const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                      const blok_pose* cur_poses_dev, uint32_t n_cur_poses, const blok_pose* prev_poses_dev, uint32_t n_prev_poses,
+                                      float* out_color_dev, void* hip_stream) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!planes) return set_error(ctx, BLOK_ERR_INVALID_ARG, "denoise: null planes");
+    blok::TemporalArgs t{};
+    t.color = planes->color; t.world_pos = planes->world_pos; t.normal_roughness_h = planes->normal_roughness; t.motion_in_h = planes->motion;
+    return denoise_posed(ctx, t, prev_view_proj, frame_count, settings, ids_dev, cur_dev, n_cur, prev_dev, n_prev, cur_poses_dev, n_cur_poses,
+                         prev_poses_dev, n_prev_poses, out_color_dev, hip_stream);
 }
 
 int blok_hip_denoise_state(blok_hip_ctx* ctx, float* history_color, float* moments, float* history_length, float* variance, float* motion) {
@@ -260,7 +312,9 @@ namespace {
 // blok_hip_draw_frame_rt(_instanced(_motion)): the path pass (with the device table instances_dev of n records, or world-only when null), then
 // the post chain; one post state and one frame counter for all.  object_motion (and n_instances > 0): the path pass also writes the id
 // plane, the motion of tracked instance pixels is corrected against the previous frame's table (ctx->rt_prev_instances, rt_prev_n
-// records) and the temporal pass is the instanced one.
+// records) and the temporal pass is the instanced one.  object_motion with poses (blok_hip_draw_frame_rt_posed_motion): the posed path pass
+// writes the id plane, the poses' records against the previous frame's pose table (ctx->rt_prev_poses, rt_prev_n_poses records) are built
+// once, and the motion pass and the temporal pass are the posed ones, which handle the instances too.
 int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces, const blok_denoise_settings* settings,
                   const blok_instance* instances_dev, uint32_t n_instances, uint32_t* out_rgba8_host, uint32_t* out_frame_count,
                   bool object_motion = false, const blok_pose* poses_dev = nullptr, uint32_t n_poses = 0u) {
@@ -284,7 +338,8 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
         if (rc != BLOK_OK) { P = blok_hip_ctx::Post{}; return rc; }
         P.rt_frame = 0;
     }
-    const bool motion = object_motion && instances_dev && n_instances;
+    const bool pose_motion = object_motion && n_poses;
+    const bool motion = object_motion && ((instances_dev && n_instances) || pose_motion);
     if (motion && !P.rt_ids) {
         rc = zeroed_plane(ctx, &P.rt_ids, n);
         if (rc != BLOK_OK) { P = blok_hip_ctx::Post{}; return rc; }
@@ -299,12 +354,22 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
     const float saved_jitter[2] = {ctx->jitter_px[0], ctx->jitter_px[1]};
     if (ctx->rt_taa_jitter) blok::taa_jitter_px(frame, ctx->jitter_px);
     rc = n_poses       ? blok_hip_trace_paths_posed_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev, n_instances,
-                                                               poses_dev, n_poses, prev_vp, &planes, nullptr, nullptr)
+                                                               poses_dev, n_poses, prev_vp, &planes, pose_motion ? P.rt_ids : nullptr, nullptr)
        : instances_dev ? blok_hip_trace_paths_instanced_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, instances_dev,
                                                                    n_instances, prev_vp, &planes, motion ? P.rt_ids : nullptr, nullptr)
                        : blok_hip_trace_paths_ref_device(ctx, cam, 0, 0, ctx->width, ctx->height, spp, max_bounces, frame, prev_vp, &planes, nullptr);
     ctx->jitter_px[0] = saved_jitter[0]; ctx->jitter_px[1] = saved_jitter[1];
-    if (motion) {
+    if (pose_motion) {
+        const blok_pose_motion* records = nullptr;
+        if (rc == BLOK_OK) rc = prepare_pose_motion(ctx, poses_dev, n_poses, ctx->rt_prev_poses, P.rt_prev_n_poses, nullptr, &records);
+        const blok::PoseMotionTables Q = pose_motion_tables(ctx, P.rt_ids, instances_dev, n_instances, ctx->rt_prev_instances, P.rt_prev_n, records, n_poses);
+        if (rc == BLOK_OK) rc = posed_motion_pass(ctx, 0, 0, ctx->width, ctx->height, P.rt_planes[1], Q, prev_vp, P.rt_motion_h, nullptr, nullptr);
+        if (rc == BLOK_OK) {
+            blok::TemporalArgs t{};
+            t.color = planes.color; t.world_pos = planes.world_pos; t.normal_roughness_h = planes.normal_roughness; t.motion_in_h = planes.motion;
+            rc = denoise_frame(ctx, t, prev_vp, frame, settings, P.rt_denoised, nullptr, nullptr, &Q);
+        }
+    } else if (motion) {
         const uint32_t n_prev = P.rt_prev_n;
         if (rc == BLOK_OK)
             rc = blok_hip_instance_motion_device(ctx, 0, 0, ctx->width, ctx->height, P.rt_planes[1], P.rt_ids, instances_dev, n_instances,
@@ -322,6 +387,7 @@ int draw_frame_rt(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint3
     P.rt_prev_cam = *cam;
     P.rt_frame = frame + 1;
     P.rt_prev_n = object_motion ? n_instances : 0u;        // the table itself: the motion entry swaps the buffers after this call
+    P.rt_prev_n_poses = pose_motion ? n_poses : 0u;        // ... and the pose table, likewise
     if (out_frame_count) *out_frame_count = P.rt_frame;
     if (out_rgba8_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_rgba8_host, P.rt_final, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     else BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
@@ -380,6 +446,27 @@ int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera
     if (drawn != BLOK_OK) return drawn;
     // this frame's table becomes the previous one (the frame ended with a synchronise; the next upload overwrites the older buffer)
     std::swap(ctx->rt_instances, ctx->rt_prev_instances);
+    return BLOK_OK;
+}
+
+int blok_hip_draw_frame_rt_posed_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                        const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                        const blok_pose* poses_host, uint32_t n_poses, uint32_t* out_rgba8_host, uint32_t* out_frame_count) {
+    int rc = check_trace(ctx, cam);                       // both tables are checked before either is uploaded
+    if (rc == BLOK_OK) rc = blok_hip_check_instances(ctx, instances_host, n_instances);
+    if (rc == BLOK_OK) rc = blok_hip_check_poses(ctx, poses_host, n_poses);
+    if (rc != BLOK_OK) return rc;
+    if (!n_poses)                                        // the instanced motion entry itself: the same launches, the same bytes
+        return blok_hip_draw_frame_rt_instanced_motion(ctx, cam, spp, max_bounces, settings, instances_host, n_instances, out_rgba8_host, out_frame_count);
+    rc = upload_rt_table(ctx, cam, instances_host, n_instances);
+    if (rc != BLOK_OK) return rc;
+    BLOK_HIP_TRY(ctx, ctx->rt_poses.reserve(n_poses, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, hipMemcpy(ctx->rt_poses, poses_host, n_poses * sizeof(blok_pose), hipMemcpyHostToDevice));
+    rc = draw_frame_rt(ctx, cam, spp, max_bounces, settings, ctx->rt_instances, n_instances, out_rgba8_host, out_frame_count, true, ctx->rt_poses, n_poses);
+    if (rc != BLOK_OK) return rc;
+    // this frame's tables become the previous ones (the frame ended with a synchronise; the next uploads overwrite the older buffers)
+    std::swap(ctx->rt_instances, ctx->rt_prev_instances);
+    std::swap(ctx->rt_poses, ctx->rt_prev_poses);
     return BLOK_OK;
 }
 

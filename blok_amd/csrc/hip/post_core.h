@@ -28,6 +28,7 @@
 
 #include "path_core.h"
 #include "instance_motion.h"
+#include "pose_motion.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -120,8 +121,12 @@ BLOK_DEV F4 load_nr16(const TemporalArgs& T, size_t i) {
 // surface point was one frame earlier (instance_motion.h): for a tracked instance, the motion when no plane is given is the object
 // motion, and p_prev / n_prev take the place of world / normal in the small-motion reprojection, pos_ok and normal_ok; an untracked
 // instance's pixels use no history.  Every other pixel runs the code of temporal_pixel.
-template <bool kInstanced>
-BLOK_DEV void temporal_body(const TemporalArgs& T, [[maybe_unused]] const MotionTables* M, int cx, int cy) {
+// kPosed (temporal_pixel_posed below; a compile-time mode, never with kInstanced): the id plane is the posed path entries' (Q->inst.ids), and
+// a pixel is a pose's, an instance's or neither by pose_motion.h's placed_history: a tracked pose pixel uses p_prev / n_prev exactly where a
+// tracked instance pixel does, an untracked one of either kind uses no history.
+template <bool kInstanced, bool kPosed = false>
+BLOK_DEV void temporal_body(const TemporalArgs& T, [[maybe_unused]] const MotionTables* M, [[maybe_unused]] const PoseMotionTables* Q, int cx, int cy) {
+    static_assert(!(kInstanced && kPosed), "the posed mode handles the instances itself");
     const int w = static_cast<int>(T.f.w), h = static_cast<int>(T.f.h);
     const size_t i = static_cast<size_t>(cy) * w + cx;
     const V3 current = load3(T.color, i);
@@ -150,6 +155,12 @@ BLOK_DEV void temporal_body(const TemporalArgs& T, [[maybe_unused]] const Motion
                 history_usable = false;
             }
         }
+    }
+    if constexpr (kPosed) {
+        const uint32_t id = Q->inst.ids[i];
+        const PlacedHistory whose = placed_state(*Q, id);
+        if (whose == kHistoryMapped) placed_map<true>(*Q, id, world, normal, was, was_normal);
+        else if (whose == kHistoryNone) history_usable = false;
     }
 
     // motion vector (raygen.rgen:409-413), held as half2
@@ -242,14 +253,22 @@ BLOK_DEV void temporal_body(const TemporalArgs& T, [[maybe_unused]] const Motion
     T.out_hist_len[i] = f2h(hist_len);
 }
 
-BLOK_DEV void temporal_pixel(const TemporalArgs& T, int cx, int cy) { temporal_body<false>(T, nullptr, cx, cy); }
+BLOK_DEV void temporal_pixel(const TemporalArgs& T, int cx, int cy) { temporal_body<false>(T, nullptr, nullptr, cx, cy); }
 
 // The temporal pass of a frame with instances (blok_hip_denoise_instanced*): ids, tables and models in `m`, the id plane full-frame.
 struct TemporalInstancedArgs {
     TemporalArgs t;
     MotionTables m;
 };
-BLOK_DEV void temporal_pixel_instanced(const TemporalInstancedArgs& A, int cx, int cy) { temporal_body<true>(A.t, &A.m, cx, cy); }
+BLOK_DEV void temporal_pixel_instanced(const TemporalInstancedArgs& A, int cx, int cy) { temporal_body<true>(A.t, &A.m, nullptr, cx, cy); }
+
+// The temporal pass of a frame with poses (blok_hip_denoise_posed*): ids, instance tables, models and the poses' records in `m`, the id
+// plane full-frame.
+struct TemporalPosedArgs {
+    TemporalArgs t;
+    PoseMotionTables m;
+};
+BLOK_DEV void temporal_pixel_posed(const TemporalPosedArgs& A, int cx, int cy) { temporal_body<false, true>(A.t, nullptr, &A.m, cx, cy); }
 
 // ---------------------------------------------------------------------------------------------- object motion
 // blok_hip_instance_motion_device: the motion of the pixels of a rectangle whose first hit is a tracked instance becomes its object motion
@@ -267,6 +286,32 @@ BLOK_DEV void instance_motion_pixel(const InstanceMotionArgs& A, int x, int y) {
     const uint32_t id = A.m.ids[i];
     if (id == kInstanceNone || !instance_tracked(A.m, id)) return;
     const V3 was = map_point(A.m.cur[id], A.m.prev[id], A.m.vs, load3(A.world_pos, i));
+    float pu, pv;
+    project_prev(A.prev_view_proj, was, pu, pv);
+    const float cu = (static_cast<float>(A.x0 + static_cast<uint32_t>(x)) + 0.5f) / static_cast<float>(A.frame_w);
+    const float cv = (static_cast<float>(A.y0 + static_cast<uint32_t>(y)) + 0.5f) / static_cast<float>(A.frame_h);
+    const float mu = cu - pu, mv = cv - pv;
+    if (A.motion_h) { A.motion_h[2 * i] = f2h(mu); A.motion_h[2 * i + 1] = f2h(mv); }
+    if (A.motion) { A.motion[2 * i] = mu; A.motion[2 * i + 1] = mv; }
+}
+
+// blok_hip_posed_motion_device: the same for a frame with poses: the pixels of tracked instances and of tracked poses (pose_motion.h) get
+// their object motion, every other pixel is left as it is.  Only the lanes of tracked pixels read more than the 4-byte id and the record's state.
+struct PosedMotionArgs {
+    PoseMotionTables m;
+    const float* world_pos;            // float4
+    uint32_t x0, y0, w, h, frame_w, frame_h;
+    float prev_view_proj[16];
+    uint16_t* motion_h;                // RG16F, may be null
+    float* motion;                     // float2, may be null
+};
+BLOK_DEV void posed_motion_pixel(const PosedMotionArgs& A, int x, int y) {
+    const size_t i = static_cast<size_t>(y) * A.w + x;
+    const uint32_t id = A.m.inst.ids[i];
+    if (placed_state(A.m, id) != kHistoryMapped) return;
+    const V3 p = load3(A.world_pos, i);
+    V3 was = p, unused = p;
+    placed_map<false>(A.m, id, p, p, was, unused);
     float pu, pv;
     project_prev(A.prev_view_proj, was, pu, pv);
     const float cu = (static_cast<float>(A.x0 + static_cast<uint32_t>(x)) + 0.5f) / static_cast<float>(A.frame_w);

@@ -34,6 +34,18 @@ __global__ __launch_bounds__(kPostBx * kPostBy) void instance_motion_kernel(cons
     if (x < a.w && y < a.h) instance_motion_pixel(a, static_cast<int>(x), static_cast<int>(y));
 }
 
+// ... the same for a frame with poses: tracked pose pixels read their 128-byte record too (pose_motion.h)
+__global__ __launch_bounds__(kPostBx * kPostBy) void posed_motion_kernel(const PosedMotionArgs a) {
+    const uint32_t x = blockIdx.x * kPostBx + threadIdx.x, y = blockIdx.y * kPostBy + threadIdx.y;
+    if (x < a.w && y < a.h) posed_motion_pixel(a, static_cast<int>(x), static_cast<int>(y));
+}
+
+// One lane per pose: two 64-byte records in, one 128-byte record (a cache line) out
+__global__ __launch_bounds__(64) void pose_motion_prepare_kernel(const blok_pose* cur, uint32_t n_cur, const blok_pose* prev, uint32_t n_prev,
+                                                                 const ModelDesc* models, uint32_t n_models, blok_pose_motion* out) {
+    pose_motion_prepare(cur, n_cur, prev, n_prev, models, n_models, blockIdx.x * 64u + threadIdx.x, out);
+}
+
 __global__ __launch_bounds__(256) void widen_kernel(const uint16_t* src, float* dst, size_t n) {
     const size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
     if (i < n) dst[i] = h2f(src[i]);
@@ -53,6 +65,14 @@ void launch_temporal_instanced(const TemporalInstancedArgs& a, hipStream_t s) {
 }
 void launch_instance_motion(const InstanceMotionArgs& a, hipStream_t s) {
     if (a.w && a.h) hipLaunchKernelGGL(instance_motion_kernel, dim3((a.w + kPostBx - 1) / kPostBx, (a.h + kPostBy - 1) / kPostBy), dim3(kPostBx, kPostBy), 0, s, a);
+}
+void launch_temporal_posed(const TemporalPosedArgs& a, hipStream_t s) { launch_pixels<TemporalPosedArgs, temporal_pixel_posed>(a, a.t.f.w, a.t.f.h, s); }
+void launch_posed_motion(const PosedMotionArgs& a, hipStream_t s) {
+    if (a.w && a.h) hipLaunchKernelGGL(posed_motion_kernel, dim3((a.w + kPostBx - 1) / kPostBx, (a.h + kPostBy - 1) / kPostBy), dim3(kPostBx, kPostBy), 0, s, a);
+}
+void launch_pose_motion_prepare(const blok_pose* cur, uint32_t n_cur, const blok_pose* prev, uint32_t n_prev, const ModelDesc* models, uint32_t n_models,
+                                blok_pose_motion* out, hipStream_t s) {
+    if (n_cur) hipLaunchKernelGGL(pose_motion_prepare_kernel, dim3((n_cur + 63u) / 64u), dim3(64), 0, s, cur, n_cur, prev, n_prev, models, n_models, out);
 }
 void launch_variance(const VarianceArgs& a, hipStream_t s) { launch_pixels<VarianceArgs, variance_pixel>(a, a.f.w, a.f.h, s); }
 void launch_atrous(const AtrousArgs& a, hipStream_t s) { launch_pixels<AtrousArgs, atrous_pixel>(a, a.w, a.h, s); }

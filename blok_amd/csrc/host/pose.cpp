@@ -1,8 +1,10 @@
 // Posed models on the host (include/blok_world.h: blok_pose_from_instance, blok_pose_from_matrix, blok_affine_from_pose): making the
-// record the posed tracer takes (blok_hip.h, "Posed models"), and folding one into the record blok_hip_volume_stamp_affine takes.
+// record the posed tracer takes (blok_hip.h, "Posed models"), folding one into the record blok_hip_volume_stamp_affine takes, and
+// (blok_pose_motion_record) the motion record of a pose between two frames, from the core the device shares.
 #include "blok_world.h"
 #include "../common/affine_core.h"
 #include "../common/pose_core.h"
+#include "../common/pose_motion_core.h"
 
 #include <cmath>
 #include <cstdint>
@@ -91,6 +93,12 @@ int blok_affine_from_pose(const blok_pose* pose, float vs, uint32_t scale_log2, 
         a.t[k] = static_cast<int64_t>(tk);
     }
     *out = a;
+    return BLOK_OK;
+}
+
+int blok_pose_motion_record(const blok_pose* cur, const blok_pose* prev, int model_usable, blok_pose_motion* out) {
+    if (!cur || !out) return BLOK_ERR_INVALID_ARG;
+    P::motion_record(*cur, prev ? *prev : *cur, prev != nullptr, model_usable != 0, *out);
     return BLOK_OK;
 }
 

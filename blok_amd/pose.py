@@ -1,5 +1,6 @@
 """Posed models (include/blok_hip.h: blok_pose, "Posed models"; include/blok_world.h: blok_pose_from_instance, blok_pose_from_matrix,
-blok_affine_from_pose): the records HipTracer.trace_primary_posed / trace_rays_posed take, and the fold into a volume_stamp_affine record."""
+blok_affine_from_pose, blok_pose_motion_record): the records HipTracer.trace_primary_posed / trace_rays_posed take, the fold into a
+volume_stamp_affine record, and the motion record of a pose between two frames."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import AFFINE, BlokError, INSTANCE, POSE, POSE_ID  # noqa: F401
+from ._ffi import AFFINE, BlokError, INSTANCE, POSE, POSE_ID, POSE_MOTION  # noqa: F401
 from .affine import rotation_matrix
 
 
@@ -51,4 +52,20 @@ def to_affine(pose, voxel_size: float = 1.0, scale_log2: int = 0) -> np.ndarray:
     rc = _ffi.host_lib().blok_affine_from_pose(_ffi.ptr(p), float(voxel_size), int(scale_log2), _ffi.ptr(out))
     if rc != 0:
         raise BlokError(rc, "blok_affine_from_pose")
+    return out
+
+
+def motion_record(cur, prev=None, model_usable: bool = True) -> np.ndarray:
+    """blok_pose_motion_record: the POSE_MOTION record of pose `cur` that was `prev` one frame earlier (None: it was not in the previous
+    table), bit for bit what the posed motion passes build on the device.  model_usable: the model exists and a pose may name it."""
+    c = np.ascontiguousarray(cur, dtype=POSE).reshape(-1)
+    assert len(c) == 1, "one pose"
+    p = None
+    if prev is not None:
+        p = np.ascontiguousarray(prev, dtype=POSE).reshape(-1)
+        assert len(p) == 1, "one previous pose"
+    out = np.zeros(1, dtype=POSE_MOTION)
+    rc = _ffi.host_lib().blok_pose_motion_record(_ffi.ptr(c), _ffi.ptr(p) if p is not None else None, int(bool(model_usable)), _ffi.ptr(out))
+    if rc != 0:
+        raise BlokError(rc, "blok_pose_motion_record")
     return out

@@ -1180,6 +1180,52 @@ class HipTracer:
                                                                     C.c_void_p(cur_ptr), int(n_cur), C.c_void_p(prev_ptr), int(n_prev),
                                                                     out_color_ptr, stream or None))
 
+    # -- object motion for posed models (blok_hip.h, "Object motion for posed models") ------------------------------------------------------
+    def draw_frame_rt_posed_motion(self, cam: np.ndarray, instances, poses, spp: int = 8, max_bounces: int = 2, settings=None):
+        """draw_frame_rt_posed with object motion: the context keeps the previous frame's instance and pose tables, and a pose (or instance)
+        whose index, model and usability carry over from them is reprojected where it was.  (RGBA8 (h, w) uint32, frames rendered so far)."""
+        cam = np.ascontiguousarray(cam, dtype=CAMERA)
+        inst = np.ascontiguousarray(instances if instances is not None else [], dtype=INSTANCE).reshape(-1)
+        p = np.ascontiguousarray(poses if poses is not None else [], dtype=POSE).reshape(-1)
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        frames = C.c_uint32()
+        self._check(self._lib.blok_hip_draw_frame_rt_posed_motion(self._ctx, _ffi.ptr(cam), spp, max_bounces,
+                                                                  C.byref(settings) if settings is not None else None, self._table(inst), len(inst),
+                                                                  self._table(p), len(p), _ffi.ptr(out), C.byref(frames)))
+        return out, frames.value
+
+    def posed_motion_device(self, world_pos_ptr: int, ids_ptr: int, cur_ptr: int, n_cur: int, prev_ptr: int, n_prev: int, cur_poses_ptr: int,
+                            n_cur_poses: int, prev_poses_ptr: int, n_prev_poses: int, prev_view_proj, motion_h_ptr: int = 0, motion_ptr: int = 0,
+                            rect=None, stream: int = 0):
+        """Asynchronous: instance_motion_device for a frame with poses: the object motion of the rectangle's pixels whose first hit is a
+        tracked instance or a tracked pose; other pixels are left untouched."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        m = None if prev_view_proj is None else (C.c_float * 16)(*[float(v) for v in np.asarray(prev_view_proj, dtype=np.float32).reshape(-1)])
+        self._check(self._lib.blok_hip_posed_motion_device(self._ctx, x0, y0, w, h, C.c_void_p(world_pos_ptr), C.c_void_p(ids_ptr),
+                                                           C.c_void_p(cur_ptr), int(n_cur), C.c_void_p(prev_ptr), int(n_prev),
+                                                           C.c_void_p(cur_poses_ptr), int(n_cur_poses), C.c_void_p(prev_poses_ptr), int(n_prev_poses), m,
+                                                           C.c_void_p(motion_h_ptr), C.c_void_p(motion_ptr), C.c_void_p(stream)))
+
+    def denoise_posed_ref_device(self, color_ptr: int, world_pos_ptr: int, normal_roughness_h_ptr: int, motion_h_ptr: int, prev_view_proj,
+                                 frame_count: int, out_color_ptr: int, ids_ptr: int, cur_ptr: int, n_cur: int, prev_ptr: int, n_prev: int,
+                                 cur_poses_ptr: int, n_cur_poses: int, prev_poses_ptr: int, n_prev_poses: int, settings=None, stream: int = 0):
+        """denoise_instanced_ref_device for a frame with poses: the id plane, and this / the previous frame's device tables of both kinds."""
+        planes = _ffi.GBufferRef(color_ptr, world_pos_ptr, normal_roughness_h_ptr, 0, motion_h_ptr)
+        m = None if prev_view_proj is None else (C.c_float * 16)(*[float(v) for v in np.asarray(prev_view_proj, dtype=np.float32).reshape(-1)])
+        self._check(self._lib.blok_hip_denoise_posed_ref_device(self._ctx, C.byref(planes), m, int(frame_count),
+                                                                C.byref(settings) if settings is not None else None, C.c_void_p(ids_ptr),
+                                                                C.c_void_p(cur_ptr), int(n_cur), C.c_void_p(prev_ptr), int(n_prev),
+                                                                C.c_void_p(cur_poses_ptr), int(n_cur_poses), C.c_void_p(prev_poses_ptr), int(n_prev_poses),
+                                                                C.c_void_p(out_color_ptr), C.c_void_p(stream)))
+
+    def debug_pose_motion_records(self, cur: np.ndarray, prev: np.ndarray) -> np.ndarray:
+        """The POSE_MOTION records the prepare kernel builds for host table `cur` against `prev` (unchecked) with this context's models."""
+        c = np.ascontiguousarray(cur, dtype=POSE).reshape(-1)
+        p = np.ascontiguousarray(prev, dtype=POSE).reshape(-1)
+        out = np.zeros(len(c), dtype=_ffi.POSE_MOTION)
+        self._check(self._lib.blok_hip_debug_pose_motion_records(self._ctx, self._table(c), len(c), self._table(p), len(p), self._table(out)))
+        return out
+
     def debug_build_tlas(self, instances_ptr: int, n_instances: int) -> np.ndarray:
         """The instance BVH of a device table (tlas_core.h: TlasNode), as an (nodes, 8) int32 array."""
         count = C.c_uint32()

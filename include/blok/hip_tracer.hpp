@@ -560,6 +560,17 @@ public:
         cam.cameraChanged = false;
         return m_pixels;
     }
+    // drawFrameRtPosed with object motion for tracked poses and instances (blok_hip.h, "Object motion for posed models"): the context keeps the
+    // previous frame's two tables
+    const std::vector<uint32_t>& drawFrameRtPosedMotion(Camera& cam, const std::vector<blok_instance>& instances, const std::vector<blok_pose>& poses,
+                                                        uint32_t sampleCount = 8, uint32_t maxBounces = 2) {
+        const blok_camera c = cam.basis(m_width, m_height);
+        m_pixels.resize(static_cast<size_t>(m_width) * m_height);
+        check(blok_hip_draw_frame_rt_posed_motion(m_ctx, &c, sampleCount, maxBounces, nullptr, instances.data(), static_cast<uint32_t>(instances.size()),
+                                                  poses.data(), static_cast<uint32_t>(poses.size()), m_pixels.data(), &m_frameIndex));
+        cam.cameraChanged = false;
+        return m_pixels;
+    }
     // tracePathsInstanced with posed models; instanceIds() holds BLOK_POSE_ID | index where a pose wins the first hit
     void tracePathsPosed(Camera& cam, const std::vector<blok_instance>& instances, const std::vector<blok_pose>& poses, const blok_gbuffer& planesHost,
                          uint32_t sampleCount = 8, uint32_t maxBounces = 2, uint32_t frameIndex = 0) {

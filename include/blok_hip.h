@@ -590,7 +590,9 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.21: a view at rest restarts every listed ray where its own counted walk ended (blok_hip_debug.h: blok_hip_set_beam_cache mode 4, the default).
  * 1.22: instanced models traced under any rotation, scale, mirror or shear (blok_pose; blok_hip_trace_primary_posed*, blok_hip_trace_rays_posed*).
  * 1.23: posed models in the path-traced frame, with true world normals (blok_hip_trace_paths_posed*, blok_hip_draw_frame_rt_posed).
- * 1.24: a packed frame of a view at rest in one launch, the misses written beside the walk (blok_hip_debug.h: blok_hip_set_packed_fill). */
+ * 1.24: a packed frame of a view at rest in one launch, the misses written beside the walk (blok_hip_debug.h: blok_hip_set_packed_fill).
+ * 1.25: object motion for posed models in the path-traced chain (blok_pose_motion; blok_hip_posed_motion_device, blok_hip_denoise_posed*,
+ *       blok_hip_draw_frame_rt_posed_motion).  (Planned as 1.24; that number went to the packed frame first.) */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -783,9 +785,9 @@ int blok_hip_draw_frame_rt_instanced(blok_hip_ctx* ctx, const blok_camera* cam, 
  * The sampling frame.  tangent = normalize(cross(up, n)), bitangent = cross(n, tangent) for every hit of such a launch (for an axis normal
  *   the division is by 1: world and instance hits keep their values).
  * G-buffer.  The composed first hit (sample 0, bounce 0); world_pos = o + t d; normal_roughness holds the normal above; out_instance holds
- *   BLOK_POSE_ID | index where a pose wins, the instance index or BLOK_INSTANCE_NONE otherwise.  The motion plane stays camera-only on pose
- *   pixels: there is no object motion for poses (prev o cur^-1 needs an inverse and a tracking rule), so a moving pose may ghost in the
- *   denoiser and TAA.
+ *   BLOK_POSE_ID | index where a pose wins, the instance index or BLOK_INSTANCE_NONE otherwise.  The motion plane of these entries stays
+ *   camera-only on pose pixels, so under them a moving pose may ghost in the denoiser and TAA; object motion for poses comes from the
+ *   entries of "Object motion for posed models" below (since ABI 1.25).
  * The frame is DEFINED as if every pose were tested for every ray.  Each launch first builds a second BVH, over the poses, on the stream (one
  *   workgroup; up to 4096 poses, above that every ray loops over the table; leaf boxes argued in pose_tlas_core.h; a table with a usable
  *   pose whose box has no bound — a near-singular m — loops too): slower, the same result.  blok_hip_debug.h: blok_hip_set_pose_tlas.
@@ -849,6 +851,85 @@ int blok_hip_denoise_instanced_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_
 int blok_hip_draw_frame_rt_instanced_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
                                             const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
                                             uint32_t* out_rgba8_host, uint32_t* out_frame_count);
+
+/* Object motion for posed models (ABI 1.25): what the block above is for lattice instances, for poses.
+ * Tracking.  Pose i of this frame's table `cur` is tracked when i < n_prev, prev[i].model == cur[i].model, both records pass the limits of
+ *   "Posed models" with that model, and either the two 64-byte records are byte-equal (state 1 below, which needs no inverse), or prev[i].m
+ *   is invertible by the test below and every float of the motion record comes out finite (state 2).  Otherwise the pose is untracked: it
+ *   appeared, changed model, or was singular one frame ago.  cur[i].m may be singular: it is only applied forward.  A change of a model's
+ *   scale exponent changes what a pose's local space means: blok_hip_model_set_scale empties the context's previous pose table, as it
+ *   empties the instance one, and callers of the *_device entries keep that rule themselves.
+ * The motion record.  blok_pose_motion below, 128 bytes, one per pose, computed once per launch (not per pixel): state (0 untracked,
+ *   1 identity, 2 moving), a, c, n and the two pivots; in states 0 and 1 every other word is zero.
+ *   State 1: the two pose records are byte-equal (-0.0 against +0.0 is not).  Then p_prev = p and n_prev = n with no arithmetic, so an unmoved
+ *   pose gets exactly the camera-only motion, as an unmoved instance does.
+ *   State 2, in DOUBLE, every operation rounded separately in this order, nothing fused, no square root (m = prev.m, M = cur.m):
+ *     C = adj(m):  C00 = m11 m22 - m12 m21   C01 = m02 m21 - m01 m22   C02 = m01 m12 - m02 m11
+ *                  C10 = m12 m20 - m10 m22   C11 = m00 m22 - m02 m20   C12 = m02 m10 - m00 m12
+ *                  C20 = m10 m21 - m11 m20   C21 = m01 m20 - m00 m21   C22 = m00 m11 - m01 m10
+ *     det = (m00 C00 + m01 C10) + m02 C20          s_k = (m_k0^2 + m_k1^2) + m_k2^2
+ *     invertible iff det det > 2^-40 ((s_0 s_1) s_2)      (the floor of the screen bins' pose_world_box, squared so that no root is needed)
+ *     id = 1.0 / det      inv_jk = C_jk id      A_ij = (inv_i0 M_0j + inv_i1 M_1j) + inv_i2 M_2j
+ *     dl = double(cur.local) - double(prev.local)      c_i = (inv_i0 dl_0 + inv_i1 dl_1) + inv_i2 dl_2
+ *     n = the cofactor matrix of the double A (n_ij = adj(A)_ji, adj and det(A) by the formulas above), every entry negated when det(A) < 0
+ *   (normals go over by A^-T = cof(A) / det(A); the per-pixel normalisation removes the magnitude, the cofactor form needs no second inverse
+ *   and is defined for a singular cur).  Each value is rounded to float once; pivot_cur = cur.pivot, pivot_prev = prev.pivot.
+ * The per-pixel map.  A first-hit point p (world_pos plane) with unit normal n on a pose in state 2, all operations float, rounded
+ *   separately, in the manner of "Ray into local space":
+ *     r_j      = fl(p_j - pivot_cur_j)
+ *     q_i      = fl( fl( fl( fl(a_i0 r_0) + fl(a_i1 r_1) ) + fl(a_i2 r_2) ) + c_i )
+ *     p_prev_i = fl(pivot_prev_i + q_i)
+ *     v_i      = fl( fl( fl(n_i0 n_0) + fl(n_i1 n_1) ) + fl(n_i2 n_2) )
+ *     qq       = fl( fl( fl(v_0 v_0) + fl(v_1 v_1) ) + fl(v_2 v_2) )
+ *     n_prev   = !(qq > 0) ? n : fl(v_i / sqrt(qq))            (sqrt correctly rounded)
+ *   Working from the pivots keeps r small for a model far from the origin.  Object motion = (px + 0.5) / width - uv of
+ *   prev_view_proj * (p_prev, 1), and the same in y: the operations of blok_hip_instance_motion_device.
+ * Ids.  The id plane of the posed path entries: BLOK_POSE_ID | index selects a pose, any other id but BLOK_INSTANCE_NONE an instance, which
+ *   is handled by the rule of the block above, unchanged: a frame that holds both kinds runs one pass.
+ * blok_hip_posed_motion_device: blok_hip_instance_motion_device for both kinds; it corrects the motion plane of
+ *   blok_hip_trace_paths_posed_ref_device.  Pixels of tracked instances and tracked poses get their object motion (a pose in state 1: the
+ *   camera-only motion recomputed); world, sky and untracked pixels are left untouched.
+ * blok_hip_denoise_posed_device / _ref_device: the instanced denoise entries plus both pose tables: the same post state and frame
+ *   counter.  A tracked pose pixel uses p_prev / n_prev exactly where a tracked instance pixel does; an untracked pose pixel takes no
+ *   history (length 1); world and instance pixels run the existing statements.
+ * All three first run a kernel that builds the records (one lane per pose) into the stream's scratch: no host synchronise, nothing
+ *   allocated after the first call at a size.  All four tables are read in stream order.
+ * blok_hip_draw_frame_rt_posed_motion: blok_hip_draw_frame_rt_posed's chain with the id plane written, the records built once, then the
+ *   motion pass, then the posed temporal pass.  The context keeps the previous frame's instance table AND pose table; both are emptied by
+ *   blok_hip_post_reset, by blok_hip_model_set_scale and by a frame of any other blok_hip_draw_frame_rt* entry.  With n_poses == 0 it is
+ *   blok_hip_draw_frame_rt_instanced_motion's frame.
+ * blok_pose_motion_record (blok_world.h) builds one record on the host, bit for bit; blok_hip_debug_pose_motion_records (blok_hip_debug.h)
+ *   reads the kernel's back.
+ * Errors as the instanced motion entries', in their order and texts (a null pose table with a non-zero count comes right after the instance
+ *   tables); a bad pose of a host table is named as blok_hip_check_poses names it, outputs untouched; device tables treat what fails as
+ *   untracked.
+ * Not built: a history plane of ids; motion for the accumulate, tile and multi-GPU entries; non-rigid tracking beyond the index rule. */
+typedef struct blok_pose_motion {   /* 128 bytes */
+    uint32_t state;                 /* 0 untracked, 1 identity, 2 moving */
+    float    a[3][3];
+    float    c[3];
+    float    n[3][3];
+    float    pivot_cur[3];
+    float    pivot_prev[3];
+    uint32_t reserved[4];           /* zero */
+} blok_pose_motion;
+int blok_hip_posed_motion_device(blok_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const float* world_pos_dev,
+                                 const uint32_t* ids_dev, const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                 const blok_pose* cur_poses_dev, uint32_t n_cur_poses, const blok_pose* prev_poses_dev, uint32_t n_prev_poses,
+                                 const float prev_view_proj[16], uint16_t* motion_h_dev, float* motion_dev, void* hip_stream);
+int blok_hip_denoise_posed_device(blok_hip_ctx* ctx, const blok_gbuffer* planes_dev, const float* motion_dev, const float prev_view_proj[16],
+                                  uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* ids_dev,
+                                  const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                  const blok_pose* cur_poses_dev, uint32_t n_cur_poses, const blok_pose* prev_poses_dev, uint32_t n_prev_poses,
+                                  float* out_color_dev, void* hip_stream);
+int blok_hip_denoise_posed_ref_device(blok_hip_ctx* ctx, const blok_gbuffer_ref* planes_dev, const float prev_view_proj[16],
+                                      uint32_t frame_count, const blok_denoise_settings* settings, const uint32_t* ids_dev,
+                                      const blok_instance* cur_dev, uint32_t n_cur, const blok_instance* prev_dev, uint32_t n_prev,
+                                      const blok_pose* cur_poses_dev, uint32_t n_cur_poses, const blok_pose* prev_poses_dev, uint32_t n_prev_poses,
+                                      float* out_color_dev, void* hip_stream);
+int blok_hip_draw_frame_rt_posed_motion(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t spp, uint32_t max_bounces,
+                                        const blok_denoise_settings* settings, const blok_instance* instances_host, uint32_t n_instances,
+                                        const blok_pose* poses_host, uint32_t n_poses, uint32_t* out_rgba8_host, uint32_t* out_frame_count);
 
 /* ------------------------------------------------------------- models into the resident volume and back (ABI 1.7)
  * The two stores of voxel data in HBM — the resident volume and the instanced models — joined on the device.  Integer arithmetic only: one

@@ -294,6 +294,13 @@ int blok_hip_debug_build_pose_tlas(blok_hip_ctx* ctx, const blok_camera* cam, co
  * are identical. */
 int blok_hip_set_pose_tlas(blok_hip_ctx* ctx, int enabled);
 
+/* The motion records of the posed motion passes (blok_hip.h, "Object motion for posed models"): the kernel that builds them, run on two HOST
+ * tables (uploaded as they are, unchecked: a pose that fails a limit is untracked) with the context's model store; out_records_host takes
+ * n_cur records.  Byte for byte blok_pose_motion_record's (blok_world.h).  Blocks.  BLOK_ERR_INVALID_ARG: a null table with a non-zero count,
+ * 2^31 poses or more, a null output with n_cur > 0. */
+int blok_hip_debug_pose_motion_records(blok_hip_ctx* ctx, const blok_pose* cur_host, uint32_t n_cur, const blok_pose* prev_host, uint32_t n_prev,
+                                       blok_pose_motion* out_records_host);
+
 /* Read-back of an instanced model (blok_hip_model_create, blok_hip_volume_capture_model), for the tests that pin a captured model byte for
  * byte: the node array (16 bytes per node, root first) and the material array (one id per voxel) as they lie in device memory, and the
  * model's lattice.  Either array pointer may be NULL (then its capacity is not looked at); out_info may be NULL.  BLOK_ERR_INVALID_ARG: an

@@ -233,6 +233,11 @@ int blok_affine_stamp_voxels(float* density, uint32_t* material_ids, const int32
 int blok_pose_from_instance(const blok_instance* placement, float vs, blok_pose* out);
 int blok_pose_from_matrix(const double forward[12], const double pivot_local[3], uint32_t model, blok_pose* out);
 int blok_affine_from_pose(const blok_pose* pose, float vs, uint32_t scale_log2, blok_affine* out);
+/* pose_motion_record: the motion record of pose `cur` that was `prev` one frame earlier (blok_hip.h, "Object motion for posed models"), bit for
+ *   bit what the device builds.  prev == NULL: the pose's index lies beyond the previous table (untracked).  model_usable: non-zero iff the
+ *   model `cur` names exists and passes the pose limits of the store (what blok_hip_check_poses checks besides the floats); the floats of both
+ *   records are checked here.  Every byte of *out is written.  BLOK_ERR_INVALID_ARG: cur or out NULL. */
+int blok_pose_motion_record(const blok_pose* cur, const blok_pose* prev, int model_usable, blok_pose_motion* out);
 
 /* -------------------------------------------------------------- a volume's connected components on the host (components.cpp)
  * label: the contract of blok_hip_volume_label_components (blok_hip.h; blok_component is declared there) over the host array

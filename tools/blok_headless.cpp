@@ -80,11 +80,16 @@
 //   --rt-posed: --rt's chain with the --pose models in it (blok_hip_draw_frame_rt_posed): they cast and receive shadows and show in bounce rays,
 //          with their faces' true normals.  Needs at least one --pose FILE.vox@...; prints the written frame's camera as --pose does.  Refused
 //          without a --pose and with what --pose refuses.
+//   --pose-motion [--pose-spin DEG]: with --rt-posed, the frames are drawn with object motion for the poses (blok_hip_draw_frame_rt_posed_motion),
+//          and before drawn frame F (the timed frames 0 .. frames - 1, then the written one) every --pose model is turned to YAW_DEG + F * DEG
+//          about its pivot (DEG defaults to 0: the poses rest); `pose: frame F camera ...` is printed for every drawn frame.  Refused without
+//          --rt-posed.  Without --pose-motion nothing changes.
 //   --devices 0,1,2,...: the frame is tile-partitioned over these devices of the node by ONE process (blok::HipMultiTracer:
 //                        RCCL send / receive group or peer copies to the first device); an ordinal may repeat (rehearsal on one GPU)
 //   --no-rccl: peer copies even when RCCL is there
 //   --dense-exchange: whole RGBA8 tiles travel (RCCL / peer copies) instead of the root reading the ranks' sparse code records
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -132,6 +137,8 @@ struct Options {
     std::vector<Paste> paste;             // .vox models resampled into the terrain, turned and scaled
     std::vector<Paste> posed;             // .vox models traced as posed models over the world, turned and scaled
     bool rt_posed = false;                // --rt-posed: the ray-tracing path with the posed models in it
+    bool pose_motion = false;             // --pose-motion: ... drawn with object motion for the poses
+    double pose_spin = 0.0;               // --pose-spin DEG: every pose yaws by DEG per drawn frame
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
     std::vector<int> devices;             // more than one entry: the multi-device tracer
     bool dense_exchange = false;
@@ -458,6 +465,33 @@ private:
     }
     // Each --pose model uploaded and given its pose: --paste's forward map (T(position) Ry(yaw) S(scale) T(-centre)) inverted and rounded by
     // blok_pose_from_matrix about the centre of the voxels' box.
+    blok_pose poseOf(size_t i, double yaw_deg) const {
+        const Options::Paste& P = m_opt.posed[i];
+        const double* pivot = m_posePivots[i].data();
+        const double yaw = yaw_deg * (3.14159265358979323846 / 180.0), cy = std::cos(yaw), sy = std::sin(yaw), s = P.scale;
+        const double r[3][3] = {{cy, 0.0, sy}, {0.0, 1.0, 0.0}, {-sy, 0.0, cy}};
+        double forward[12];
+        for (int k = 0; k < 3; ++k) {
+            const double row[3] = {s * r[k][0], s * r[k][1], s * r[k][2]};
+            for (int j = 0; j < 3; ++j) forward[4 * k + j] = row[j];
+            forward[4 * k + 3] = P.position[k] - (row[0] * pivot[0] + row[1] * pivot[1] + row[2] * pivot[2]);
+        }
+        blok_pose pose;
+        if (blok_pose_from_matrix(forward, pivot, m_poseModels[i], &pose) != BLOK_OK)
+            throw std::runtime_error("--pose: the map has no pose (blok_pose_from_matrix): SCALE must be at least 1/1024 and the position within 2^20");
+        return pose;
+    }
+    // --pose-motion: drawn frame `frame` with every pose turned to its YAW_DEG + frame * --pose-spin, by the entry that tracks them
+    const std::vector<uint32_t>& drawPoseMotionFrame(uint32_t frame) {
+        for (size_t i = 0; i < m_poses.size(); ++i) m_poses[i] = poseOf(i, m_opt.posed[i].yaw_deg + frame * m_opt.pose_spin);
+        const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
+        const float cam[14] = {c.pos[0], c.pos[1], c.pos[2], c.fwd[0], c.fwd[1], c.fwd[2], c.right[0], c.right[1], c.right[2], c.up[0], c.up[1], c.up[2], c.tan_half_fov, c.aspect};
+        std::printf("pose: frame %u camera", frame);
+        for (float v : cam) std::printf(" %.9g", v);
+        std::printf("\n");
+        std::fflush(stdout);
+        return m_tracer->drawFrameRtPosedMotion(m_camera, m_instances, m_poses, m_opt.spp);
+    }
     void loadPoses(bool imported) {
         for (const Options::Paste& P : m_opt.posed) {
             std::vector<int32_t> xyz;
@@ -467,19 +501,9 @@ private:
             int32_t lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
             for (size_t i = 0; i < ids.size(); ++i)
                 for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], xyz[3 * i + a]); hi[a] = std::max(hi[a], xyz[3 * i + a] + 1); }
-            const double pivot[3] = {(lo[0] + hi[0]) / 2.0, (lo[1] + hi[1]) / 2.0, (lo[2] + hi[2]) / 2.0};
-            const double yaw = P.yaw_deg * (3.14159265358979323846 / 180.0), cy = std::cos(yaw), sy = std::sin(yaw), s = P.scale;
-            const double r[3][3] = {{cy, 0.0, sy}, {0.0, 1.0, 0.0}, {-sy, 0.0, cy}};
-            double forward[12];
-            for (int i = 0; i < 3; ++i) {
-                const double row[3] = {s * r[i][0], s * r[i][1], s * r[i][2]};
-                for (int j = 0; j < 3; ++j) forward[4 * i + j] = row[j];
-                forward[4 * i + 3] = P.position[i] - (row[0] * pivot[0] + row[1] * pivot[1] + row[2] * pivot[2]);
-            }
-            blok_pose pose;
-            if (blok_pose_from_matrix(forward, pivot, m_tracer->createModel(xyz, ids), &pose) != BLOK_OK)
-                throw std::runtime_error("--pose: the map has no pose (blok_pose_from_matrix): SCALE must be at least 1/1024 and the position within 2^20");
-            m_poses.push_back(pose);
+            m_posePivots.push_back({(lo[0] + hi[0]) / 2.0, (lo[1] + hi[1]) / 2.0, (lo[2] + hi[2]) / 2.0});
+            m_poseModels.push_back(m_tracer->createModel(xyz, ids));
+            m_poses.push_back(poseOf(m_poses.size(), P.yaw_deg));
             std::cout << "pose: " << P.path << ": " << ids.size() << " voxels turned " << P.yaw_deg << " degrees, scaled " << P.scale << "\n";
         }
         if (!m_poses.empty()) m_tracer->checkPoses(m_poses);
@@ -697,6 +721,7 @@ private:
             const auto t0 = clock::now();
             m_tracer->beginFrame();
             if (m_multi) m_multi->drawFrame(m_camera, m_multiFrame);
+            else if (m_opt.pose_motion) drawPoseMotionFrame(f);
             else if (m_opt.rt_posed) m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp);
             else if (m_opt.rt && m_opt.far) m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp);
             else if (m_opt.rt) m_tracer->drawFrameRT(m_camera, m_opt.spp);
@@ -711,7 +736,8 @@ private:
                            << m_tracer->hits().size() * sizeof(blok_hit) / 1e6 << " MB)\n";
             if (f + 1 < m_opt.frames || !(m_opt.rt || m_opt.rt_posed)) m_camera.processKeyboard('W', 0.016f);
         }
-        const auto& single = m_opt.rt_posed ? m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp)
+        const auto& single = m_opt.pose_motion ? drawPoseMotionFrame(m_opt.frames)
+                             : m_opt.rt_posed ? m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp)
                              : m_opt.rt && m_opt.far ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
                              : m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_poses.empty() ? drawPosed() : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
         if (m_multi) {                                       // the partitioned frame must be the single-device frame
@@ -757,6 +783,8 @@ private:
     std::vector<uint32_t> m_populatedFrame;
     std::vector<blok_pose> m_poses;                // --pose FILE.vox@...: the posed models, in the order given
     std::vector<uint32_t> m_poseIds;
+    std::vector<std::array<double, 3>> m_posePivots;   // ... each one's pivot (the centre of its voxels' box) and model, for --pose-motion's turns
+    std::vector<uint32_t> m_poseModels;
 };
 
 }  // namespace
@@ -892,6 +920,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--rt-posed")) opt.rt_posed = true;
+        else if (!std::strcmp(argv[i], "--pose-motion")) opt.pose_motion = true;
+        else if (!std::strcmp(argv[i], "--pose-spin")) opt.pose_spin = std::atof(next());
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--no-rccl")) opt.rccl = false;
         else if (!std::strcmp(argv[i], "--dense-exchange")) opt.dense_exchange = true;
@@ -908,6 +938,14 @@ int main(int argc, char** argv) {
     }
     if (opt.rt_posed && (opt.far || !opt.vox.empty() || !opt.obj.empty() || !opt.load_volume.empty() || opt.devices.size() > 1)) {
         std::fprintf(stderr, "--rt-posed path-traces its --pose models over the generated scene or a --terrain, on one device: leave --far, --vox, --obj, --load-volume and --devices out\n");
+        return 2;
+    }
+    if ((opt.pose_motion || opt.pose_spin != 0.0) && !opt.rt_posed) {
+        std::fprintf(stderr, "--pose-motion (and --pose-spin) draw --rt-posed's frames with object motion for the poses: give --rt-posed\n");
+        return 2;
+    }
+    if (opt.pose_spin != 0.0 && !opt.pose_motion) {
+        std::fprintf(stderr, "--pose-spin turns the poses of --pose-motion's frames: give --pose-motion\n");
         return 2;
     }
     if (opt.far_direct && !opt.far) { std::fprintf(stderr, "--far-direct and --far-rings need --far K[,MIN]\n"); return 2; }
