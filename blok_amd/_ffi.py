@@ -53,6 +53,10 @@ assert POSE_MOTION.itemsize == 128
 # = blok_quad: one merged quad of a volume's surface, 32 bytes
 QUAD = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("reserved", "<u4")])
 QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
+# = blok_light (32 bytes): a quad whose reserved word is the running sum of du * dv; = blok_lights_info (32 bytes): what a light table holds
+LIGHT = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("cum", "<u4")])
+LIGHTS_INFO = np.dtype([("n_faces", "<u8"), ("bytes", "<u8"), ("n", "<u4"), ("n_owned", "<u4"), ("area_world", "<f4"), ("reserved", "<u4")])
+assert LIGHT.itemsize == 32 and LIGHTS_INFO.itemsize == 32
 STAMP_SET, STAMP_KEEP, STAMP_ERASE = 0, 1, 2      # = BLOK_STAMP_*
 CAPTURE_CUT = 1                                   # = BLOK_CAPTURE_CUT
 # = blok_component: one connected component of a labelled region, 40 bytes
@@ -255,6 +259,8 @@ HOST_SYMBOLS = {
     "blok_quads_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "blok_quads_write_obj": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_lights_from_quads": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]),
+    "blok_lights_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_capture_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
@@ -438,6 +444,10 @@ HIP_SYMBOLS = {
     "blok_hip_volume_extract_quads": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint64),
                                                 C.POINTER(C.c_uint64)]),
     "blok_hip_volume_quads_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_lights_from_quads": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "blok_hip_set_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "blok_hip_lights_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_lights_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "blok_hip_volume_stamp_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_hip_volume_stamp_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float,
                                                C.POINTER(C.c_uint64)]),

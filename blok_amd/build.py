@@ -10,11 +10,11 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 INCLUDE = ROOT / "include"
 
-HOST_SRC = [PKG / "csrc/host/world.cpp", PKG / "csrc/host/scene.cpp", PKG / "csrc/host/vox.cpp", PKG / "csrc/host/obj.cpp", PKG / "csrc/host/terrain.cpp", PKG / "csrc/host/quads.cpp", PKG / "csrc/host/stamp.cpp", PKG / "csrc/host/components.cpp", PKG / "csrc/host/sweep.cpp", PKG / "csrc/host/bricks.cpp", PKG / "csrc/host/distance.cpp", PKG / "csrc/host/flood.cpp", PKG / "csrc/host/columns.cpp", PKG / "csrc/host/scroll.cpp", PKG / "csrc/host/shapes.cpp", PKG / "csrc/host/lod.cpp", PKG / "csrc/host/affine.cpp", PKG / "csrc/host/automaton.cpp", PKG / "csrc/host/pose.cpp"]
+HOST_SRC = [PKG / "csrc/host/world.cpp", PKG / "csrc/host/scene.cpp", PKG / "csrc/host/vox.cpp", PKG / "csrc/host/obj.cpp", PKG / "csrc/host/terrain.cpp", PKG / "csrc/host/quads.cpp", PKG / "csrc/host/stamp.cpp", PKG / "csrc/host/components.cpp", PKG / "csrc/host/sweep.cpp", PKG / "csrc/host/bricks.cpp", PKG / "csrc/host/distance.cpp", PKG / "csrc/host/flood.cpp", PKG / "csrc/host/columns.cpp", PKG / "csrc/host/scroll.cpp", PKG / "csrc/host/shapes.cpp", PKG / "csrc/host/lod.cpp", PKG / "csrc/host/affine.cpp", PKG / "csrc/host/automaton.cpp", PKG / "csrc/host/pose.cpp", PKG / "csrc/host/lights.cpp"]
 HIP_SRC = [PKG / "csrc/hip/api.hip", PKG / "csrc/hip/api_launch.hip", PKG / "csrc/hip/api_debug.hip", PKG / "csrc/hip/api_post.hip", PKG / "csrc/hip/api_volume.hip", PKG / "csrc/hip/api_multi.hip", PKG / "csrc/hip/trace_kernels.hip", PKG / "csrc/hip/dense_kernels.hip", PKG / "csrc/hip/tile_order.hip", PKG / "csrc/hip/gpu_build.hip",
            PKG / "csrc/hip/post_kernels.hip", PKG / "csrc/hip/tree_build.cpp", PKG / "csrc/hip/api_instances.hip", PKG / "csrc/hip/placed_kernels.hip",
            PKG / "csrc/hip/voxelize_kernels.hip", PKG / "csrc/hip/terrain_kernels.hip", PKG / "csrc/hip/quads_kernels.hip", PKG / "csrc/hip/stamp_kernels.hip",
-           PKG / "csrc/hip/components_kernels.hip", PKG / "csrc/hip/sweep_kernels.hip", PKG / "csrc/hip/bricks_kernels.hip", PKG / "csrc/hip/distance_kernels.hip", PKG / "csrc/hip/flood_kernels.hip", PKG / "csrc/hip/columns_kernels.hip", PKG / "csrc/hip/scroll_kernels.hip", PKG / "csrc/hip/shapes_kernels.hip", PKG / "csrc/hip/lod_kernels.hip", PKG / "csrc/hip/affine_kernels.hip", PKG / "csrc/hip/automaton_kernels.hip"]
+           PKG / "csrc/hip/components_kernels.hip", PKG / "csrc/hip/sweep_kernels.hip", PKG / "csrc/hip/bricks_kernels.hip", PKG / "csrc/hip/distance_kernels.hip", PKG / "csrc/hip/flood_kernels.hip", PKG / "csrc/hip/columns_kernels.hip", PKG / "csrc/hip/scroll_kernels.hip", PKG / "csrc/hip/shapes_kernels.hip", PKG / "csrc/hip/lod_kernels.hip", PKG / "csrc/hip/affine_kernels.hip", PKG / "csrc/hip/automaton_kernels.hip", PKG / "csrc/hip/lights_kernels.hip"]
 HIP_HDR = sorted((PKG / "csrc/hip").glob("*.h")) + sorted((PKG / "csrc/common").glob("*.h")) + [INCLUDE / "blok_hip.h", INCLUDE / "blok_hip_debug.h", INCLUDE / "blok_world.h"]
 
 

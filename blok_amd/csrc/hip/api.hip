@@ -1,5 +1,6 @@
 // C ABI of the gfx950 backend (include/blok_hip.h).  Owns device memory; every HIP call is checked.
 #include "api_internal.h"
+#include "../common/lights_core.h"
 #include <cstdlib>
 
 namespace blok_api {
@@ -21,6 +22,7 @@ void free_world(blok_hip_ctx* ctx) {
     ctx->has_sun_map = false; ctx->has_dense = false;
     ctx->n_materials = 0; ctx->has_world = false; ctx->built_on_device = false; ctx->stats = blok_world_stats{};
     ctx->world_voxel_size = 1.0f;
+    clear_lights(ctx);                  // (the owned set spoke about this world and its material table)
 }
 
 // A tree the device builders made (gpu_build.h) becomes the installed one: the context's own from here, unless it lies in the resident
@@ -32,7 +34,9 @@ void adopt_tree(blok_hip_ctx* ctx, const blok::GpuTree& gpu) {
 }
 
 int install_materials(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials) {
+    ctx->material_glows.assign(blok::lights::kSetWords, 0u);
     if (!n_materials) return BLOK_OK;
+    blok::lights::emissive_set(materials, n_materials, ctx->material_glows.data());      // once per material: what blok_hip_lights_from_quads keeps
     BLOK_HIP_TRY(ctx, ctx->d_materials.reserve(n_materials, blok::FreeAfter::nothing()));      // (behind free_world: there is no old table)
     BLOK_HIP_TRY(ctx, hipMemcpy(ctx->d_materials, materials, n_materials * sizeof(blok_material), hipMemcpyHostToDevice));
     ctx->n_materials = n_materials;
@@ -284,7 +288,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 25u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 26u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -804,7 +808,9 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     p.tail_pool = nullptr;
     // (from four samples per pixel on: with fewer a wave's pool never fills, and the rays parked wait for the end: 1 spp 0.82 -> 0.93 ms, 4 spp 2.78 -> 2.54)
     const bool posed = inst != nullptr && poses != nullptr && poses->n != 0u;
-    const bool instanced = inst != nullptr && (inst->n != 0u || posed);
+    // a light table: the lit kernel, the posed superset body, runs whatever tables the entry brought (a world-only entry brings none)
+    const bool lit = ctx->lights.n != 0u;
+    const bool instanced = (inst != nullptr && (inst->n != 0u || posed)) || lit;
     if (instanced) p.resume_secondary = 0u;                 // (the instanced kernel is built without walk_resume)
     if (ctx->ray_batching >= 3u && max_bounces >= 2u && spp >= 4u && !ctx->path_resume && blok::kBlock == 64 && !instanced) {
         const size_t bytes = static_cast<size_t>(path_blocks) * blok::kTailCapacity * sizeof(blok::TailRecord);
@@ -815,9 +821,9 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     }
     blok::TlasScene scene{};
     if (instanced) {
-        scene.instances = inst->table; scene.n_instances = inst->n; scene.ids = inst->ids;
+        if (inst != nullptr) { scene.instances = inst->table; scene.n_instances = inst->n; scene.ids = inst->ids; }
         scene.models = ctx->models.d_desc; scene.n_models = static_cast<uint32_t>(ctx->models.desc.size());
-        if (inst->n != 0u && inst->n <= blok::kTlasMax) {
+        if (scene.n_instances != 0u && scene.n_instances <= blok::kTlasMax) {
             auto& scratch = ctx->beam_buffers[stream];
             BLOK_HIP_TRY(ctx, scratch.tlas.reserve(blok::tlas_nodes(inst->n) * sizeof(blok::TlasNode), blok::FreeAfter::work_on(stream)));
             scene.nodes = static_cast<const blok::TlasNode*>(scratch.tlas.get());
@@ -839,7 +845,10 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     if (instanced && scene.nodes)
         blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas.get()), stream);
     if (n_beams) blok::launch_beam(blok::RayMode::Rect, p.trace, n_beams, stream);
-    if (posed) blok::launch_paths_posed(p, scene, pose_scene, ctx->models.stack_levels, path_blocks, stream);
+    if (lit) {
+        const blok::LightScene light_scene{ctx->lights.table, ctx->lights.owned, ctx->lights.n, static_cast<uint32_t>(ctx->lights.n_faces), ctx->lights.area_world};
+        blok::launch_paths_lit(p, scene, pose_scene, light_scene, ctx->models.stack_levels, path_blocks, stream);
+    } else if (posed) blok::launch_paths_posed(p, scene, pose_scene, ctx->models.stack_levels, path_blocks, stream);
     else if (instanced) blok::launch_paths_instanced(p, scene, ctx->models.stack_levels, path_blocks, stream);
     else blok::launch_paths(p, path_blocks, stream);
     BLOK_HIP_TRY(ctx, hipGetLastError());

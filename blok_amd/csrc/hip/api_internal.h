@@ -114,6 +114,16 @@ struct blok_hip_ctx {
     blok::GpuColumns columns;            // of the last blok_hip_volume_column_field
     blok::GpuScatter scatter;            // of the last blok_hip_volume_scatter_models: it goes with the column snapshot it was made from
     blok::GpuLod lod;                    // of the last blok_hip_volume_reduce
+    // emissive voxels as lights (blok_hip.h; api_volume.hip): the table, the owned set (lights_core.h: kSetWords words) and the totals; n == 0:
+    // no table.  Cleared by free_world: the owned set is a statement about the world and material table it was built for.
+    struct Lights {
+        blok::DeviceArray<blok_light> table;
+        blok::DeviceArray<uint32_t> owned;
+        uint32_t n = 0, n_owned = 0;
+        uint64_t n_faces = 0;
+        float area_world = 0.0f;
+    } lights;
+    std::vector<uint32_t> material_glows;             // the emissive indices of the installed material table, a bit each (install_materials)
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world
     blok::DeviceArray<float> d_sun_map;
@@ -356,6 +366,7 @@ private:
 inline bool known_model(const blok_hip_ctx* ctx, uint32_t model) { return model < ctx->models.desc.size() && ctx->models.desc[model].nodes; }
 
 void free_world(blok_hip_ctx* ctx);
+void clear_lights(blok_hip_ctx* ctx);                   // api_volume.hip: no light table from here on
 void adopt_tree(blok_hip_ctx* ctx, const blok::GpuTree& gpu);
 int install_materials(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials);
 int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_material* materials, size_t n_materials);
@@ -370,6 +381,7 @@ int check_trace(blok_hip_ctx* ctx, const blok_camera* cam);
 struct PathInstances { const blok_instance* table; uint32_t n; uint32_t* ids; };
 // The poses of a posed path launch (null, or n == 0: none): a device table of n records, traced behind the instances.
 struct PathPoses { const blok_pose* table; uint32_t n; };
+// With a light table installed (ctx->lights.n >= 1) every launch runs the lit kernel, whatever tables the entry brought.
 int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
                       uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst = nullptr,
                       const PathPoses* poses = nullptr);

@@ -14,6 +14,7 @@
 #include "../common/lod_core.h"
 #include "../common/terrain_lod_core.h"
 #include "../common/automaton_core.h"
+#include "../common/lights_core.h"
 #include "device_mem.h"
 #include <chrono>
 #include <cstdlib>
@@ -22,6 +23,11 @@
 using namespace blok_api;
 
 namespace blok_api {
+void clear_lights(blok_hip_ctx* ctx) {
+    if (ctx->lights.table) (void)hipDeviceSynchronize();      // frames that still sample it
+    ctx->lights = blok_hip_ctx::Lights{};
+}
+
 void free_volume_snapshots(blok_hip_ctx* ctx) {
     blok::gpu_quads_free(&ctx->quads);
     blok::gpu_components_free(&ctx->components);
@@ -261,7 +267,7 @@ int blok_hip_volume_extract_quads(blok_hip_ctx* ctx, const int32_t region_lo[3],
     if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
     if (!(flags & BLOK_QUADS_COUNT_ONLY)) {
         blok::gpu_quads_free(&ctx->quads);
-        ctx->quads = snapshot; ctx->quads.taken = true;
+        ctx->quads = snapshot; ctx->quads.taken = true; ctx->quads.flags = flags;      // (blok_hip_lights_from_quads asks whether the keys are material ids)
     }
     if (out_n_quads) *out_n_quads = snapshot.n_quads;
     if (out_n_faces) *out_n_faces = n_faces;
@@ -936,6 +942,89 @@ int blok_hip_volume_rebuild(blok_hip_ctx* ctx, const blok_material* materials, s
         std::fprintf(stderr, "[volume_rebuild us] wait-for-device %.1f build %.1f install %.1f sun-map %.1f\n", us(t_begin, t_synced), us(t_synced, t_built), us(t_built, t_installed), us(t_installed, std::chrono::steady_clock::now()));
     }
     return rc;
+}
+
+// ---- emissive voxels as lights (blok_hip.h; lights_kernels.hip) ----
+namespace {
+void lights_info_of(const blok_hip_ctx* ctx, blok_lights_info* out) {
+    if (!out) return;
+    const blok_hip_ctx::Lights& l = ctx->lights;
+    *out = blok_lights_info{};
+    out->n = l.n; out->n_owned = l.n_owned; out->n_faces = l.n_faces; out->area_world = l.area_world;
+    out->bytes = l.n ? static_cast<uint64_t>(l.n) * sizeof(blok_light) + blok::lights::kSetWords * sizeof(uint32_t) : 0u;
+}
+// A new table of n records and its owned set, both in device memory, take the old one's place.
+int install_lights(blok_hip_ctx* ctx, blok::DeviceArray<blok_light>&& table, uint32_t n, uint64_t n_faces, blok::DeviceArray<uint32_t>&& owned, blok_lights_info* out_info) {
+    if (n == 0) { clear_lights(ctx); lights_info_of(ctx, out_info); return BLOK_OK; }
+    std::vector<uint32_t> words(blok::lights::kSetWords);
+    BLOK_HIP_TRY(ctx, hipMemcpy(words.data(), owned, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    clear_lights(ctx);
+    blok_hip_ctx::Lights& l = ctx->lights;
+    l.table = std::move(table); l.owned = std::move(owned);
+    l.n = n; l.n_faces = n_faces;
+    for (const uint32_t w : words) l.n_owned += static_cast<uint32_t>(__builtin_popcount(w));
+    l.area_world = static_cast<float>(n_faces) * ctx->world_voxel_size * ctx->world_voxel_size;      // formed once, here
+    lights_info_of(ctx, out_info);
+    return BLOK_OK;
+}
+}  // namespace
+
+int blok_hip_lights_from_quads(blok_hip_ctx* ctx, uint32_t flags, blok_lights_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "lights_from_quads: no world");
+    if (flags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lights_from_quads: unknown flag bits");
+    if (!ctx->quads.taken) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lights_from_quads: no quads snapshot (blok_hip_volume_extract_quads)");
+    if (ctx->quads.flags & BLOK_QUADS_IGNORE_MATERIAL) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lights_from_quads: the snapshot was taken with BLOK_QUADS_IGNORE_MATERIAL");
+    if (!ctx->n_materials || ctx->material_glows.size() != blok::lights::kSetWords) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lights_from_quads: no material table");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    blok::DeviceArray<uint32_t> glows, owned;
+    BLOK_HIP_TRY(ctx, glows.reserve(blok::lights::kSetWords, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, owned.reserve(blok::lights::kSetWords, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, hipMemcpy(glows, ctx->material_glows.data(), blok::lights::kSetWords * sizeof(uint32_t), hipMemcpyHostToDevice));
+    blok::GpuLights made;
+    std::string why;
+    const uint32_t n_mat = static_cast<uint32_t>(std::min<size_t>(ctx->n_materials, blok::lights::kSetBits));
+    // (edits and the extraction are enqueued on the null stream, and so is this)
+    const blok::GpuBuildStatus st = blok::gpu_lights_from_quads(ctx->quads.d_quads, ctx->quads.n_quads, glows, n_mat, owned, &made, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    blok::DeviceArray<blok_light> table;
+    table.adopt(made.d_lights, made.n);
+    return install_lights(ctx, std::move(table), made.n, made.n_faces, std::move(owned), out_info);
+}
+
+int blok_hip_set_lights(blok_hip_ctx* ctx, const blok_light* lights_host, uint32_t n, blok_lights_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!lights_host || n == 0) { clear_lights(ctx); lights_info_of(ctx, out_info); return BLOK_OK; }
+    static const char* const kRules[] = {"", "face above 5", "du or dv is 0", "cum is not the running sum of du * dv", "2^31 or more lights, or 2^32 or more unit faces",
+                                         "a corner outside [-32768, 32768]"};
+    uint64_t faces = 0, index = 0;
+    if (const int rule = blok::lights::check_table(lights_host, n, &faces, &index))
+        return set_error(ctx, rule == 4 ? BLOK_ERR_UNSUPPORTED : BLOK_ERR_INVALID_ARG, "set_lights: light " + std::to_string(index) + ": " + kRules[rule]);
+    if (!ctx->has_world) return set_error(ctx, BLOK_ERR_NO_WORLD, "set_lights: no world");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> words(blok::lights::kSetWords, 0u);
+    const uint32_t n_mat = static_cast<uint32_t>(std::min<size_t>(ctx->n_materials, blok::lights::kSetBits));
+    for (uint32_t i = 0; i < n; ++i) { const uint32_t m = blok::lights::material_index(lights_host[i].material, n_mat); words[m >> 5] |= 1u << (m & 31u); }
+    blok::DeviceArray<blok_light> table;
+    blok::DeviceArray<uint32_t> owned;
+    BLOK_HIP_TRY(ctx, table.reserve(n, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, owned.reserve(blok::lights::kSetWords, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, hipMemcpy(table, lights_host, static_cast<size_t>(n) * sizeof(blok_light), hipMemcpyHostToDevice));
+    BLOK_HIP_TRY(ctx, hipMemcpy(owned, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return install_lights(ctx, std::move(table), n, faces, std::move(owned), out_info);
+}
+
+int blok_hip_lights_info(blok_hip_ctx* ctx, blok_lights_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "lights_info: null output");
+    lights_info_of(ctx, out_info);
+    return BLOK_OK;
+}
+
+int blok_hip_lights_download(blok_hip_ctx* ctx, blok_light* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const blok_hip_ctx::Lights& l = ctx->lights;
+    return ranged_download(ctx, "lights_download", "blok_hip_lights_from_quads or blok_hip_set_lights", true, l.n, l.table.get(), sizeof(blok_light), out_host, first, count);
 }
 
 }  // extern "C"

@@ -135,8 +135,20 @@ struct GpuQuads {
     blok_quad* d_quads = nullptr;
     uint64_t n_quads = 0;
     bool taken = false;
+    uint32_t flags = 0;             // of the extraction (BLOK_QUADS_IGNORE_MATERIAL: the keys are no material ids)
 };
 void gpu_quads_free(GpuQuads* q);
+// = blok_hip_lights_from_quads (include/blok_hip.h; lights_kernels.hip): the quads whose key maps to a set bit of d_glows (the emissive
+// material indices, lights_core.h), in the quads' order, with the running sum of du * dv; d_owned (kSetWords words) takes the set of
+// the kept quads' material indices.  out->d_lights is a new device array (null for none), the caller's to free.  Unsupported: 2^31 or
+// more lights, 2^32 or more unit faces.  One wait, for the two totals.
+struct GpuLights {
+    blok_light* d_lights = nullptr;
+    uint32_t n = 0;
+    uint64_t n_faces = 0;
+};
+GpuBuildStatus gpu_lights_from_quads(const blok_quad* d_quads, uint64_t n_quads, const uint32_t* d_glows, uint32_t n_materials, uint32_t* d_owned,
+                                     GpuLights* out, std::string* why);
 GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuQuads* out,
                                         uint64_t* out_n_faces, std::string* why);
 // = blok_hip_volume_stamp_models (include/blok_hip.h; stamp_kernels.hip).  The placements have passed the entry's checks; models[i] is

@@ -20,6 +20,7 @@
 #include "tlas_core.h"
 #include "posed_paths_core.h"
 #include "half_bits.h"
+#include "../common/lights_core.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -151,6 +152,39 @@ BLOK_DEV V3 sky_color(V3 dir) {                                         // :136-
 BLOK_DEV bool is_emissive(V3 e) { return vdot(e, v3(1.0f, 1.0f, 1.0f)) > 0.01f; }                // :158-160
 BLOK_DEV float luminance(V3 c) { return vdot(c, v3(0.2126f, 0.7152f, 0.0722f)); }                // :163-165
 
+// The light part of a lit path launch (include/blok_hip.h: "emissive voxels as lights"): the table, the owned set of material
+// indices (lights::kSetWords words), the lights, their unit faces A and area_world = float(A) * vs * vs.
+struct LightScene {
+    const blok_light* lights;
+    const uint32_t* owned;
+    uint32_t n, n_faces;
+    float area_world;
+};
+// One light sample from the surface point `hit_pos` with normal n (DESIGN.md §32 b, c), given the three draws r, u1, u2: the sampled point q
+// its emission Le and g = (((cos_s * cos_l) / d2) * area_world) / pi; false = no term and no ray (a cosine is 0, or the point is closer
+// than 2 kLightEps).  x = hit_pos + n * 0.001 is the sun shadow ray's origin.  Every operation is rounded separately.
+BLOK_DEV bool light_sample(const LightScene& S, const blok_material* mat_table, uint32_t n_materials, float vs, V3 hit_pos, V3 n, uint32_t r, float u1, float u2,
+                           V3& q, V3& le, float& g) {
+    const uint32_t pick = lights::pick_of(r, S.n_faces);
+    const blok_light L = S.lights[lights::find_light(S.lights, S.n, pick)];
+    float qa[3], nla[3];
+    lights::sample_point(L, pick - L.cum, u1, u2, vs, qa, nla);
+    q = v3(qa[0], qa[1], qa[2]);
+    const V3 nl = v3(nla[0], nla[1], nla[2]);
+    const V3 x = vadd(hit_pos, vscale(n, 0.001f));
+    const V3 w = vsub(q, x);
+    const float d2 = vdot(w, w);
+    const float d = rn_sqrt(d2);
+    const V3 dir = vdivs(w, d);
+    const float cos_s = fmaxf(vdot(n, dir), 0.0f);
+    const float cos_l = fmaxf(-vdot(nl, dir), 0.0f);
+    if (!(cos_s > 0.0f && cos_l > 0.0f && d > 2.0f * lights::kLightEps)) return false;
+    g = (((cos_s * cos_l) / d2) * S.area_world) * kInvPi;
+    const blok_material mat = mat_table[lights::material_index(L.material, n_materials)];
+    le = v3(mat.emission[0], mat.emission[1], mat.emission[2]);
+    return true;
+}
+
 BLOK_DEV void store4(float* plane, size_t i, float a, float b, float c, float d) {
     if (!plane) return;
     float* p = plane + 4 * i;
@@ -202,12 +236,16 @@ BLOK_DEV void store_narrow(const PathArgs& P, size_t index, uint32_t px, uint32_
 // runs without the anchor machinery (kResume false), the tail pool and the sky-tile shortcut (the beam pre-pass knows only the world).
 // kPosed (implies kInstanced): and then with the poses of `poses` (posed_paths_core.h); a posed hit takes its world normal from its
 // pose's row, and the sampling frame is formed for any unit normal.
-template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false>
+// kLit (over the posed superset body only): the light table of `lit` is sampled at every eligible hit, its shadow ray a state of its own
+// (light_phase) behind the sun's; an owned material's emission is not counted again where a diffuse bounce ray finds it.
+template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false, bool kLit = false>
 BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t index, uint4* stk, float t0 = 0.0f, uint2* keep_lohi = nullptr, uint32_t* keep_base = nullptr,
                           [[maybe_unused]] TailRecord* pool = nullptr, [[maybe_unused]] TailAnswer* tail_results = nullptr,
-                          [[maybe_unused]] const TlasScene* scene = nullptr, [[maybe_unused]] const PoseScene* poses = nullptr) {
+                          [[maybe_unused]] const TlasScene* scene = nullptr, [[maybe_unused]] const PoseScene* poses = nullptr,
+                          [[maybe_unused]] const LightScene* lit = nullptr) {
     static_assert(!kInstanced || (!kResume && !kSkyOnly), "instanced launches run without walk_resume and the sky-only build");
     static_assert(!kPosed || kInstanced, "a posed launch is an instanced launch with a pose table");
+    static_assert(!kLit || kPosed, "the lit loop is built over the posed superset body");
     const TraceArgs& A = P.trace;
     const blok_camera& cam = A.cam;
     const V3 cam_pos = v3(cam.pos[0], cam.pos[1], cam.pos[2]);
@@ -235,6 +273,10 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
     V3 ray_org = cam_pos, ray_dir = cam_f, radiance = v3(0, 0, 0), throughput = v3(1, 1, 1);
     // surface state kept across the shadow trace
     bool shadow_phase = false;
+    // kLit: a light sample waits for its shadow ray (behind the sun's, if any); its term if unoccluded and the sampled point; and whether
+    // the ray being shaded left a diffuse bounce (such a ray's owned emitters were counted by the light sample of the hit it left)
+    [[maybe_unused]] bool light_phase = false, prev_diffuse = false;
+    [[maybe_unused]] V3 pending = v3(0, 0, 0), light_q = v3(0, 0, 0);
     // the pixel's anchor (walk_resume): a reported voxel whose ancestors lie in the side area (and, while stack_is_anchor, on the stack)
     bool anchored = false, stack_is_anchor = false;
     WalkAnchor anchor;
@@ -258,6 +300,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
         ray_org = cam_pos;
         radiance = v3(0, 0, 0); throughput = v3(1, 1, 1);
         bounce = 0u;
+        if constexpr (kLit) prev_diffuse = false;
     };
     if (P.spp != 0u && P.max_bounces != 0u) begin_sample();
 
@@ -332,7 +375,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
             // results are identical.  Measured at 4K: 2 bounces 8.75 -> 7.28 ms per 8 spp, 64 spp 69.4 -> 58.8 ms; with one
             // bounce there are only short rays and taking turns costs (3.8 -> 5.3 ms), so it is not done there.
             if (P.batch_kinds != 0u && P.max_bounces > 1u) {
-                const uint32_t kind = shadow_phase ? 1u : (bounce == 0u ? 0u : 2u);
+                const uint32_t kind = (shadow_phase || (kLit && light_phase)) ? 1u : (bounce == 0u ? 0u : 2u);
                 if (P.batch_kinds >= 2u) {
                     // ... and sample by sample: the OLDEST pending (sample, kind) of the wave goes first.  With "primary rays first" the
                     // pixels whose primary rays miss race through all their samples in rounds of their own while the others still owe
@@ -384,19 +427,28 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                     r.tmax = cap > r.tmin ? fminf(r.tmax, cap) : 0.0f;
                 }
             }
+        } else if (kLit && light_phase) {
+            // the light's shadow ray: from the sun shadow ray's origin towards the sampled point, stopping kLightEps short of it; no sun-map cap
+            const V3 so = vadd(hit_pos, vscale(n, 0.001f));
+            const V3 w = vsub(light_q, so);
+            const float d = rn_sqrt(vdot(w, w));
+            const V3 dir = vdivs(w, d);
+            r.ox = so.x; r.oy = so.y; r.oz = so.z;
+            r.dx = dir.x; r.dy = dir.y; r.dz = dir.z;
+            r.tmin = 0.001f; r.tmax = d - lights::kLightEps;
         } else {
             r.ox = ray_org.x; r.oy = ray_org.y; r.oz = ray_org.z;
             r.dx = ray_dir.x; r.dy = ray_dir.y; r.dz = ray_dir.z;
             r.tmin = 0.001f; r.tmax = 10000.0f;                                               // :225,:227
         }
-        if (!tail_round && !shadow_phase && bounce == 0u && t0 > 0.0f) {         // primary ray behind the beam pre-pass (one walk call site)
+        if (!tail_round && !shadow_phase && !(kLit && light_phase) && bounce == 0u && t0 > 0.0f) {         // primary ray behind the beam pre-pass (one walk call site)
             r.tmin = fmaxf(r.tmin, t0);
             if (t0 >= kBeamNone) r.tmax = 0.0f;                   // the tile's frustum meets no voxel: empty interval, immediate miss
         }
-        BLOK_PATH_KIND(shadow_phase ? 1u : (bounce == 0u ? 0u : 2u));
+        BLOK_PATH_KIND((shadow_phase || (kLit && light_phase)) ? 1u : (bounce == 0u ? 0u : 2u));
 #ifdef BLOK_PATH_CLOCKS
         const uint64_t kind_clock0 = __builtin_amdgcn_s_memtime();
-        const uint32_t round_kind = shadow_phase ? 1u : (bounce == 0u ? 0u : 2u);
+        const uint32_t round_kind = (shadow_phase || (kLit && light_phase)) ? 1u : (bounce == 0u ? 0u : 2u);
         const uint32_t round_lanes = static_cast<uint32_t>(__builtin_popcountll(__ballot(true)));
 #endif
         HitInfo hit;
@@ -445,6 +497,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
             }
         }
         [[maybe_unused]] uint32_t pose_won = kInstanceNone;       // kPosed: the pose whose voxel `hit` reports (hit.face is then its LOCAL face)
+        [[maybe_unused]] bool world_won = true;                   // kLit: the reported voxel is the world's (neither an instance nor a pose won)
         if constexpr (kInstanced) {
             // The instances, on the ray's own interval: the beam pre-pass' start parameter and the sun map's cap describe the world alone.
             // Primary and bounce rays: the closest hit of world and instances by the composition rule (the world's t bounds the query;
@@ -452,8 +505,8 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
             // only when the world walk found nothing, up to the uncapped tmax (:294-296).
             RayIn q = r;
             q.tmin = 0.001f;                                                                  // :225, :294
-            if (shadow_phase) {
-                q.tmax = 1000.0f;                                                             // :296
+            if (shadow_phase || (kLit && light_phase)) {
+                q.tmax = shadow_phase ? 1000.0f : r.tmax;                                     // :296; a light's ray ends short of its point
                 if (!hit.found && tlas_any(*scene, A.voxel_size, A.inv_voxel_size, q, stk)) hit.found = true;
                 if constexpr (kPosed) {                                                       // ... and the poses only when the instances found nothing
                     if (!hit.found && poses_any(*poses, scene->models, scene->n_models, A.voxel_size, A.inv_voxel_size, q, stk)) hit.found = true;
@@ -465,10 +518,12 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 if (won != kInstanceNone) {
                     hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
                 }
+                if constexpr (kLit) world_won = won == kInstanceNone;
                 if constexpr (kPosed) {                                                       // the poses, with tmax = the composed t so far
                     pose_won = poses_closest(*poses, scene->models, scene->n_models, A.voxel_size, A.inv_voxel_size, q, hit.found ? hit.t : 10000.0f, stk, rec);
                     if (pose_won != kInstanceNone) {
                         hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
+                        if constexpr (kLit) world_won = false;
                     }
                     if (bounce == 0u && s == 0u && scene->ids) scene->ids[index] = pose_won != kInstanceNone ? (BLOK_POSE_ID | pose_won) : won;
                 } else
@@ -546,6 +601,10 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                     radiance = vadd(radiance, vscale(vmul(vscale(vscale(vmul(throughput, f), d), 0.25f), sun_radiance), n_dot_l));
                 }
             }
+            if (!(kLit && light_phase)) continue_path = true;                                 // (kLit: the light's shadow ray goes next)
+        } else if (kLit && light_phase) {
+            light_phase = false;
+            if (!hit.found) radiance = vadd(radiance, pending);                               // the sampled point is visible
             continue_path = true;
         } else if (!hit.found) {                                                              // :232-235, miss.rmiss
             if (!cut_off) radiance = vadd(radiance, vmul(throughput, sky_color(ray_dir)));    // (a parked ray's term comes later, through the pool)
@@ -579,14 +638,31 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 }
             }
             if (is_emissive(emission)) {                                                      // :265-277
-                radiance = vadd(radiance, vmul(throughput, emission));
+                // kLit: where a diffuse bounce ray finds an owned material in the world, the light sample of the hit it left has counted it
+                bool counted = false;
+                if constexpr (kLit) counted = prev_diffuse && world_won && lights::in_set(lit->owned, lights::material_index(hit.material, A.n_materials));
+                if (!counted) radiance = vadd(radiance, vmul(throughput, emission));
                 if (luminance(emission) > 5.0f || bounce > 0u) end_sample = true;
             }
             if (last_segment) end_sample = true;
+            if constexpr (kLit) {
+                // the light sample of an eligible hit: three draws, always all three, then the term and its shadow ray if there is one
+                const V3 diffuse = vscale(albedo, 1.0f - metallic);
+                if (!end_sample && max3f(diffuse) > 0.0f) {
+                    const uint32_t lr = pcg(rng);
+                    const float u1 = random_float(rng);
+                    const float u2 = random_float(rng);
+                    V3 le; float g;
+                    if (light_sample(*lit, A.mat_table, A.n_materials, A.voxel_size, hit_pos, n, lr, u1, u2, light_q, le, g)) {
+                        pending = vscale(vmul(vmul(throughput, diffuse), le), g);
+                        light_phase = true;
+                    }
+                }
+            }
             if (!end_sample) {
                 n_dot_l = fmaxf(vdot(n, sun_dir), 0.0f);                                      // :280
                 if (n_dot_l > 0.0f && bounce == 0u) shadow_phase = true;                      // next trace: the shadow ray
-                else continue_path = true;
+                else if (!(kLit && light_phase)) continue_path = true;
             }
         }
 
@@ -633,6 +709,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                 if (specular) {                                                               // :349-360
                     const V3 h = sampled;
                     const V3 new_dir = vsub(ray_dir, vscale(h, 2.0f * vdot(h, ray_dir)));
+                    if constexpr (kLit) prev_diffuse = false;
                     if (vdot(new_dir, n) <= 0.0f) end_sample = true;
                     else {
                         const float h_dot_v = fmaxf(vdot(h, view), 0.0f);
@@ -644,6 +721,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                     const V3 diffuse = vscale(albedo, 1.0f - metallic);
                     throughput = vmul(throughput, vdivs(diffuse, fmaxf(1.0f - spec_w, 0.001f)));
                     ray_dir = sampled;
+                    if constexpr (kLit) prev_diffuse = true;
                 }
                 if (!end_sample) {
                     const float max_t = max3f(throughput);                                    // :370-373

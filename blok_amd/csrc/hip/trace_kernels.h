@@ -264,8 +264,12 @@ struct TlasScene;
 // The instanced path frame (path_core.h: shade_pixel<..., kInstanced>): stack_slots = the deepest live model's levels - 1.
 void launch_paths_instanced(const PathArgs& args, const TlasScene& scene, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
 struct PoseScene;
+struct LightScene;
 // The posed path frame (shade_pixel<..., kPosed>): the instanced frame with a pose table behind the instances (poses.n_poses > 0).
 void launch_paths_posed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
+// ... with the light table `lit` (n >= 1) sampled at every eligible hit (path_core.h: kLit); either table of placed models may be empty.
+void launch_paths_lit(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, uint32_t stack_slots, uint32_t n_blocks,
+                      hipStream_t stream);
 void launch_trace(RayMode mode, const TraceArgs& args, uint32_t n_blocks, hipStream_t stream);
 // Pre-pass and walk in one grid, statically: workgroups [0, n_beam_tiles) search, the others walk (Rect and Tiles).
 void launch_joint(RayMode mode, const TraceArgs& args, uint32_t n_beam_tiles, uint32_t n_blocks, hipStream_t stream);

@@ -1227,6 +1227,24 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PAT
     shade_pixel<false, false, true, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S, &Q);
 }
 
+// The lit path frame (path_core.h: shade_pixel<…, kLit>): path_kernel_posed's body with the light table sampled at every
+// eligible hit — the same pixel mapping, LDS stack and grid.  Launched whenever the context holds a light table, whatever tables the entry
+// brought: a world-only entry comes with empty instance and pose tables (S.n_instances 0, Q.n_poses 0, both trees null) and no id plane.
+// Waves per SIMD: the posed kernel's, for the same reason (profiles/lights_isa.txt).
+#ifndef BLOK_PATH_LIT_WAVES
+#define BLOK_PATH_LIT_WAVES 4
+#endif
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PATH_LIT_WAVES, BLOK_PATH_LIT_WAVES))) void path_kernel_lit(const PathArgs P, const TlasScene S, const PoseScene Q,
+                                                                                                                                      const LightScene L) {
+    extern __shared__ uint4 lds_stack[];
+    const TraceArgs& A = P.trace;
+    const uint32_t tid = threadIdx.x;
+    uint32_t rx, ry;
+    float t0;
+    if (!path_pixel(P, tid, rx, ry, t0)) return;
+    shade_pixel<false, false, true, true, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S, &Q, &L);
+}
+
 // One workgroup builds the instance BVH of n <= kTlasMax instances (tlas_core.h): sort keys, a bitonic sort in LDS, the leaves, the refit
 // level by level (each level reads the one below it from global memory behind a fence and a barrier), the header.  No atomics.
 __global__ __launch_bounds__(kTlasBuildThreads) void tlas_build_kernel(const blok_instance* inst, uint32_t n, const ModelDesc* models, uint32_t n_models,
@@ -1652,6 +1670,14 @@ void launch_paths_posed(const PathArgs& args, const TlasScene& scene, const Pose
     uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
     if (stack_slots > slots) slots = stack_slots;
     hipLaunchKernelGGL(path_kernel_posed, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses);
+}
+
+void launch_paths_lit(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, uint32_t stack_slots, uint32_t n_blocks,
+                      hipStream_t stream) {
+    if (n_blocks == 0 || lit.n == 0u) return;
+    uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
+    if (stack_slots > slots) slots = stack_slots;
+    hipLaunchKernelGGL(path_kernel_lit, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses, lit);
 }
 
 void launch_tlas_build(const blok_instance* instances, uint32_t n, const ModelDesc* models, uint32_t n_models, TlasNode* nodes, hipStream_t stream) {

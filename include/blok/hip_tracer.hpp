@@ -257,6 +257,31 @@ public:
         for (uint64_t at = 0; at < n; at += page) check(blok_hip_volume_quads_download(m_ctx, quads.data() + at, at, std::min(page, n - at)));
         return quads;
     }
+    // Emissive voxels as lights (blok_hip.h): the light table built on the device from the latest quads snapshot and the installed
+    // material table (after rebuildVolume and extractQuads).  While a table with lights is installed every path-traced frame samples it.
+    blok_lights_info lightsFromQuads() {
+        blok_lights_info info{};
+        check(blok_hip_lights_from_quads(m_ctx, 0u, &info));
+        return info;
+    }
+    // A host-built table (blok_lights_from_quads, blok_world.h) installed; an empty vector clears.
+    blok_lights_info setLights(const std::vector<blok_light>& lights) {
+        blok_lights_info info{};
+        check(blok_hip_set_lights(m_ctx, lights.empty() ? nullptr : lights.data(), static_cast<uint32_t>(lights.size()), &info));
+        return info;
+    }
+    void clearLights() { check(blok_hip_set_lights(m_ctx, nullptr, 0u, nullptr)); }
+    blok_lights_info lightsInfo() const {
+        blok_lights_info info{};
+        check(blok_hip_lights_info(m_ctx, &info));
+        return info;
+    }
+    std::vector<blok_light> downloadLights(uint64_t page = uint64_t(1) << 22) const {
+        const uint64_t n = lightsInfo().n;
+        std::vector<blok_light> lights(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_lights_download(m_ctx, lights.data() + at, at, std::min(page, n - at)));
+        return lights;
+    }
     // Placed models written into the resident volume, in table order (blok_hip_volume_stamp_models; mode BLOK_STAMP_SET / KEEP / ERASE):
     // returns the voxels written.  A later rebuildVolume installs the world.
     uint64_t stampModels(const std::vector<blok_instance>& placements, int mode = BLOK_STAMP_SET, float density = 1.0f) {

@@ -557,6 +557,57 @@ int blok_hip_volume_extract_quads(blok_hip_ctx* ctx, const int32_t region_lo[3],
                                   uint64_t* out_n_quads, uint64_t* out_n_faces);
 int blok_hip_volume_quads_download(blok_hip_ctx* ctx, blok_quad* out_host, uint64_t first, uint64_t count);
 
+/* ---- emissive voxels as lights (ABI 1.26) ----
+ * Without a light table a path-traced frame aims at one light only, the sun, and an emissive voxel lights its surroundings only when a
+ * bounce ray happens to hit it.  A context that holds a light table samples it at every eligible hit of every path-traced entry.
+ *  - A light is a rectangle of du x dv exposed unit faces: a blok_quad whose `reserved` word is `cum`, the exclusive prefix sum of du * dv
+ *    in table order.  Same lattice, plane axes and face numbering as a quad; world position = lattice x voxel size.  The total A of
+ *    du * dv must be < 2^32 and the number of lights < 2^31 (BLOK_ERR_UNSUPPORTED otherwise), so selecting a face is integer work with one
+ *    right answer: pick = (r * A) >> 32 for a 32-bit random r, the light is the last with cum <= pick, the cell (pick - cum) % du,
+ *    (pick - cum) / du.
+ *  - Beside the table the context keeps A, area_world = float(A) * vs * vs, and the OWNED set: the material indices that occur in the
+ *    table (index of an id as a hit forms it: min(id, 65535), then 0 when beyond the material table).
+ *  - CONTRACT: an installed table holds EVERY exposed world face of every owned material.  The lit loop counts an owned material's
+ *    emission through the table wherever a diffuse bounce ray finds it in the world, and by the hit everywhere else (first hits, specular
+ *    rays, models, materials the table does not own); a table that misses faces of an owned material loses their light on diffuse paths.
+ *  - blok_hip_lights_from_quads builds the table on the device from the context's quads snapshot (blok_hip_volume_extract_quads): a quad
+ *    is kept iff the material its key maps to in the context's CURRENT material table is emissive (dot(emission, 1) > 0.01, the path loop's
+ *    test); order is the quads' order.  flags must be 0.  Bit-identical to blok_lights_from_quads (blok_world.h) over the same quads and
+ *    materials.  Errors, each leaving the previous table in place: BLOK_ERR_NO_WORLD without a world; BLOK_ERR_INVALID_ARG without a quads
+ *    snapshot or a material table, for a snapshot taken with BLOK_QUADS_IGNORE_MATERIAL, for flags != 0; BLOK_ERR_UNSUPPORTED for the
+ *    limits above; BLOK_ERR_OOM.  A result of no lights installs the empty table, which is the same as clearing.  Blocking.
+ *  - blok_hip_set_lights installs a host-built table (a world that is not a volume: blok_quads_extract, then blok_lights_from_quads).
+ *    Checked: face < 6; du, dv >= 1; cum equal to the running sum; A < 2^32; every corner inside [-32768, 32768].  A failed check is
+ *    BLOK_ERR_INVALID_ARG (BLOK_ERR_UNSUPPORTED for A or n above the limits) and leaves the previous table.  n = 0 or NULL clears.
+ *  - blok_hip_lights_info reports what is installed (zeros without a table); blok_hip_lights_download copies records
+ *    [first, first + count), in pieces as the other snapshots do (BLOK_ERR_INVALID_ARG for a range past the end).  out_info may be NULL.
+ *  - Life: the table is the context's.  Edits, a new quads extraction and blok_hip_volume_scroll leave it alone — a stale table is the
+ *    caller's matter, as a stale instance table is.  blok_hip_destroy frees it.  It is CLEARED by every call that installs another world
+ *    or material table (blok_hip_upload_world, blok_hip_upload_dense, blok_hip_volume_rebuild, and what removes the world): the owned set
+ *    is a statement about that table.  So: rebuild, extract quads, then build the lights.
+ *  - Frames: while a table with n >= 1 is installed every path-traced entry (blok_hip_trace_paths*, their instanced and posed forms, the
+ *    blok_hip_draw_frame_rt* chain) runs the lit loop; they all launch through one dispatch point, and there is no path-traced entry that
+ *    ignores the table.  With no table every entry runs the kernel it ran before, bit for bit.  The rule of the lit loop is DESIGN.md §32. */
+typedef struct blok_light {
+    int32_t  lo[3];     /* as blok_quad */
+    uint32_t du, dv;
+    uint32_t material;
+    uint32_t face;
+    uint32_t cum;       /* exposed unit faces of the lights before this one */
+} blok_light;
+typedef struct blok_lights_info {
+    uint64_t n_faces;   /* A */
+    uint64_t bytes;     /* of the table in device memory (host build: of the records) */
+    uint32_t n;         /* lights */
+    uint32_t n_owned;   /* material indices in the owned set */
+    float    area_world;
+    uint32_t reserved;  /* 0 */
+} blok_lights_info;
+int blok_hip_lights_from_quads(blok_hip_ctx* ctx, uint32_t flags, blok_lights_info* out_info);
+int blok_hip_set_lights(blok_hip_ctx* ctx, const blok_light* lights_host, uint32_t n, blok_lights_info* out_info);
+int blok_hip_lights_info(blok_hip_ctx* ctx, blok_lights_info* out_info);
+int blok_hip_lights_download(blok_hip_ctx* ctx, blok_light* out_host, uint64_t first, uint64_t count);
+
 /* TAA jitter of the primary rays of all following frames, in pixels (each within +-0.5; NULL or {0,0} = none, the default and
  * the parity / benchmark contract).  The reference applies its Halton(2,3) - 0.5 sequence through the projection matrix
  * (getJitteredProjection, blok/src/renderer_postprocess.cpp:254-268: proj[2][0..1] += 2 j / size, handed to raygen.rgen as
@@ -592,7 +643,9 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.23: posed models in the path-traced frame, with true world normals (blok_hip_trace_paths_posed*, blok_hip_draw_frame_rt_posed).
  * 1.24: a packed frame of a view at rest in one launch, the misses written beside the walk (blok_hip_debug.h: blok_hip_set_packed_fill).
  * 1.25: object motion for posed models in the path-traced chain (blok_pose_motion; blok_hip_posed_motion_device, blok_hip_denoise_posed*,
- *       blok_hip_draw_frame_rt_posed_motion).  (Planned as 1.24; that number went to the packed frame first.) */
+ *       blok_hip_draw_frame_rt_posed_motion).  (Planned as 1.24; that number went to the packed frame first.)
+ * 1.26: emissive voxels as lights: a light table built from the quads snapshot and sampled at every hit of the path loop (blok_light;
+ *       blok_hip_lights_from_quads, blok_hip_set_lights, blok_hip_lights_info, blok_hip_lights_download). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

@@ -176,6 +176,19 @@ int blok_quads_extract(const float* density, const uint32_t* material_ids, const
                        uint64_t* out_n_quads, uint64_t* out_n_faces);
 int blok_quads_write_obj(const char* path, const blok_quad* quads, uint64_t n, const blok_material_library* lib, char* err, size_t err_len);
 
+/* -------------------------------------------------------------- emissive quads as a light table on the host (lights.cpp)
+ * from_quads: the contract of blok_hip_lights_from_quads (blok_hip.h, "emissive voxels as lights") over host arrays, bit-identical to the
+ * device's table: quad i is kept iff materials[index(quads[i].material)] is emissive, in the quads' order, cum the exclusive prefix sum
+ * of du * dv.  Writes at most `capacity` records (a prefix when there are more; out may be NULL with capacity 0) and always fills
+ * *out_info (may be NULL) with the totals.  BLOK_ERR_INVALID_ARG: a NULL array with a non-zero count, no material table;
+ * BLOK_ERR_UNSUPPORTED: 2^31 or more lights, or 2^32 or more unit faces.
+ * check: the rules blok_hip_set_lights holds a host table to.  BLOK_OK, or BLOK_ERR_INVALID_ARG / BLOK_ERR_UNSUPPORTED with "light I: rule"
+ * in err (may be NULL).  *out_info (may be NULL) takes n, A and the bytes of a table that passes (area_world and n_owned are the
+ * context's to fill: 0 here). */
+int blok_lights_from_quads(const blok_quad* quads, uint64_t n_quads, const blok_material* materials, size_t n_materials, blok_light* out,
+                           uint64_t capacity, float voxel_size, blok_lights_info* out_info);
+int blok_lights_check(const blok_light* lights, uint64_t n, blok_lights_info* out_info, char* err, size_t err_len);
+
 /* -------------------------------------------------------------- models into a volume and back on the host (stamp.cpp)
  * The contracts of blok_hip_volume_stamp_models and blok_hip_volume_capture_model (blok_hip.h) over host arrays density[x + y*nx + z*nx*ny]
  * / material_ids of a box whose voxel (0, 0, 0) sits at world `origin` (NULL = 0, 0, 0), through the arithmetic the kernel uses.

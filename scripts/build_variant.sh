@@ -6,7 +6,7 @@ set -e
 NAME=$1; shift
 cd "$(dirname "$0")/.."
 SRC_DIR=blok_amd/csrc/hip
-ALL="api.hip api_launch.hip api_debug.hip api_post.hip api_volume.hip api_multi.hip trace_kernels.hip dense_kernels.hip tile_order.hip gpu_build.hip post_kernels.hip tree_build.cpp api_instances.hip placed_kernels.hip voxelize_kernels.hip terrain_kernels.hip quads_kernels.hip stamp_kernels.hip components_kernels.hip sweep_kernels.hip bricks_kernels.hip distance_kernels.hip flood_kernels.hip columns_kernels.hip scroll_kernels.hip shapes_kernels.hip lod_kernels.hip affine_kernels.hip automaton_kernels.hip"      # = blok_amd/build.py: HIP_SRC
+ALL="api.hip api_launch.hip api_debug.hip api_post.hip api_volume.hip api_multi.hip trace_kernels.hip dense_kernels.hip tile_order.hip gpu_build.hip post_kernels.hip tree_build.cpp api_instances.hip placed_kernels.hip voxelize_kernels.hip terrain_kernels.hip quads_kernels.hip stamp_kernels.hip components_kernels.hip sweep_kernels.hip bricks_kernels.hip distance_kernels.hip flood_kernels.hip columns_kernels.hip scroll_kernels.hip shapes_kernels.hip lod_kernels.hip affine_kernels.hip automaton_kernels.hip lights_kernels.hip"      # = blok_amd/build.py: HIP_SRC
 VARIANT_SRC=${VARIANT_SRC:-trace_kernels.hip}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++20 -ffp-contract=off ${BASE_EXTRA--fno-slp-vectorize} -fPIC -Iinclude -Iblok_amd/csrc/hip"
 OBJ=build/variant_obj; mkdir -p $OBJ blok_amd/variants

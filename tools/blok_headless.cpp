@@ -77,6 +77,10 @@
 //          printed.  May be given more than once.  Refused with --rt (the path-traced frame takes no pose table), --far, --vox, --obj,
 //          --load-volume and more than one device.  (--pose N with a bare number is the camera pose.)
 //   --rt: every frame goes through the reference's full ray-tracing path (path trace, denoise, TAA, tonemap, sharpen)
+//   --lights: with --rt or --rt-posed over a resident volume (--terrain, --obj, --load-volume): behind the last rebuild the whole box is extracted
+//          as quads and the emissive ones become the light table (blok_hip_lights_from_quads) that every path-traced frame samples; logs
+//          "lights: N rectangles, A faces, M materials".  --glow ID[:R,G,B] makes material ID of the table the rebuilds install emissive
+//          (four times its albedo without R,G,B): --terrain SEED --glow 3 --rt --lights shows lit ore in caves.
 //   --rt-posed: --rt's chain with the --pose models in it (blok_hip_draw_frame_rt_posed): they cast and receive shadows and show in bounce rays,
 //          with their faces' true normals.  Needs at least one --pose FILE.vox@...; prints the written frame's camera as --pose does.  Refused
 //          without a --pose and with what --pose refuses.
@@ -137,6 +141,9 @@ struct Options {
     std::vector<Paste> paste;             // .vox models resampled into the terrain, turned and scaled
     std::vector<Paste> posed;             // .vox models traced as posed models over the world, turned and scaled
     bool rt_posed = false;                // --rt-posed: the ray-tracing path with the posed models in it
+    bool lights = false;                  // --lights: with --rt or --rt-posed over a resident volume, its emissive faces are sampled as lights
+    struct Glow { uint32_t id; bool has_rgb; float rgb[3]; };
+    std::vector<Glow> glow;               // --glow ID[:R,G,B]: materials made emissive in the table every rebuild installs
     bool pose_motion = false;             // --pose-motion: ... drawn with object motion for the poses
     double pose_spin = 0.0;               // --pose-spin DEG: every pose yaws by DEG per drawn frame
     std::string save_volume, load_volume; // the resident volume as a .bvol file, written after it is made / read in place of making it
@@ -297,7 +304,7 @@ private:
         populate(p);
         paste();
         loadPoses(true);
-        m_tracer->rebuildVolume(m_materials.packForGpu());
+        m_tracer->rebuildVolume(gpuMaterials());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
         farFieldDirect(p);
@@ -390,7 +397,7 @@ private:
         hollow();
         automaton();
         stroke();
-        m_tracer->rebuildVolume(m_materials.packForGpu());
+        m_tracer->rebuildVolume(gpuMaterials());
         const blok_world_stats w = m_tracer->worldStats();
         std::cout << "volume loaded: " << s.info.n_bricks << " bricks, " << s.info.n_voxels << " voxels; world: " << w.n_voxels << " voxels, " << w.n_tree_nodes
                   << " tree nodes, " << w.levels << " levels\n";
@@ -649,7 +656,7 @@ private:
         hollow();
         automaton();
         stroke();
-        m_tracer->rebuildVolume(m_materials.packForGpu());
+        m_tracer->rebuildVolume(gpuMaterials());
         const blok_world_stats s = m_tracer->worldStats();
         std::cout << "mesh: " << nv << " vertices, " << nt << " triangles -> " << written << " voxels written (" << (m_opt.solid ? "solid" : "surface")
                   << "); world: " << s.n_voxels << " voxels, " << s.n_tree_nodes << " tree nodes, " << s.levels << " levels\n";
@@ -708,15 +715,36 @@ private:
                 ++pieces; voxels += n; total += fall.travel; longest = std::max<uint64_t>(longest, fall.travel);
             }
         }
-        m_tracer->rebuildVolume(m_materials.packForGpu());
+        m_tracer->rebuildVolume(gpuMaterials());
         uint64_t left = 0;
         const std::vector<blok_component> records = m_tracer->labelComponents();
         for (const blok_component& c : records) left += !(c.touches & (1u << 3));
         std::cout << "settle: " << pieces << " pieces, " << voxels << " voxels, travel " << total << " in total, longest " << longest << "; "
                   << records.size() << " components after, " << left << " not touching the floor\n";
     }
+    // The library's materials as the rebuilds install them: --glow ID[:R,G,B] gives material ID that emission (four times its albedo without one).
+    std::vector<blok_material> gpuMaterials() {
+        std::vector<blok_material> table = m_materials.packForGpu();
+        for (const Options::Glow& g : m_opt.glow) {
+            if (g.id >= table.size()) throw std::runtime_error("--glow " + std::to_string(g.id) + ": the material table has " + std::to_string(table.size()) + " entries");
+            for (int a = 0; a < 3; ++a) table[g.id].emission[a] = g.has_rgb ? g.rgb[a] : 4.0f * table[g.id].albedo[a];
+        }
+        return table;
+    }
+    // --lights: the installed world's emissive faces become the light table every path-traced frame samples (behind the last rebuild: a
+    // rebuild clears the table): the whole box as quads, then the table from them on the device.
+    void installLights() {
+        if (!m_opt.lights) return;
+        if (!(m_opt.terrain || !m_opt.obj.empty() || !m_opt.load_volume.empty())) throw std::runtime_error("--lights needs a resident volume: --terrain, --obj or --load-volume");
+        uint64_t quads = 0, faces = 0;
+        if (blok_hip_volume_extract_quads(m_tracer->handle(), nullptr, nullptr, 0u, &quads, &faces) != BLOK_OK)
+            throw std::runtime_error(std::string("--lights: ") + blok_hip_last_error(m_tracer->handle()));
+        const blok_lights_info info = m_tracer->lightsFromQuads();
+        std::cout << "lights: " << info.n << " rectangles, " << info.n_faces << " faces, " << info.n_owned << " materials (of " << quads << " quads, " << faces << " exposed faces)\n";
+    }
     void update() {
         using clock = std::chrono::steady_clock;
+        installLights();
         for (uint32_t f = 0; f < m_opt.frames; ++f) {
             const auto t0 = clock::now();
             m_tracer->beginFrame();
@@ -920,6 +948,14 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--load-volume")) opt.load_volume = next();
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--rt-posed")) opt.rt_posed = true;
+        else if (!std::strcmp(argv[i], "--lights")) opt.lights = true;
+        else if (!std::strcmp(argv[i], "--glow")) {
+            Options::Glow g{};
+            const int got = std::sscanf(next(), "%u:%f,%f,%f", &g.id, &g.rgb[0], &g.rgb[1], &g.rgb[2]);
+            if (got != 1 && got != 4) { std::fprintf(stderr, "--glow takes ID or ID:R,G,B\n"); return 2; }
+            g.has_rgb = got == 4;
+            opt.glow.push_back(g);
+        }
         else if (!std::strcmp(argv[i], "--pose-motion")) opt.pose_motion = true;
         else if (!std::strcmp(argv[i], "--pose-spin")) opt.pose_spin = std::atof(next());
         else if (!std::strcmp(argv[i], "--spp")) opt.spp = std::strtoul(next(), nullptr, 10);
@@ -948,6 +984,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--pose-spin turns the poses of --pose-motion's frames: give --pose-motion\n");
         return 2;
     }
+    if (opt.lights && !(opt.rt || opt.rt_posed)) { std::fprintf(stderr, "--lights is sampled by the path-traced frames: give --rt or --rt-posed\n"); return 2; }
     if (opt.far_direct && !opt.far) { std::fprintf(stderr, "--far-direct and --far-rings need --far K[,MIN]\n"); return 2; }
     try {
         App app(blok::GraphicsApi::HIP, opt);
