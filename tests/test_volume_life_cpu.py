@@ -2,7 +2,8 @@
 and the numpy references alone): every writer family followed by every reader family with no rebuild in between and with a result the write
 changed, every writer family in a pool of several families' edits before one rebuild, a rebuild behind a scroll and a later small edit,
 every deferred consumer across a kept scroll and across writes into its region, every snapshot kind held with all the others, whole bricks
-emptied and bricks filled in an empty 64-cell in every life.  And the host builds of libblok_host.so, driven through the same lives from
+emptied and bricks filled in an empty 64-cell in every life, and at least two rebuilds per life at which the shadow rays' last-occluder
+map, had it been kept as it was, would be too low (what tests/test_volume_life_gpu.py checks on the device can fail).  And the host builds of libblok_host.so, driven through the same lives from
 the model's arrays, return what the composed references return, exactly.  The measured seconds per life are printed."""
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ from blok_amd import shapes as SH
 from blok_amd import stamp as ST
 from blok_amd import sweep as SW
 from blok_amd import terrain as T
+from tests import bounds_reference as BO
 from tests import shapes_reference as SHR
 from tests import volume_life as VL
 
@@ -176,6 +178,28 @@ def test_every_mode_of_every_family_appears(facts):
     assert set().union(*(f["deltas"] for f in facts)) == {(a, s) for a in range(3) for s in (1, -1)}
     kinds = {s["kind"] for f in facts for s in f["steps"]}
     assert kinds == {"writer", "reader", "rebuild", "deferred"}
+
+
+@LIVES
+def test_h_a_kept_map_would_be_too_low_at_two_rebuilds_of_every_life(index):
+    """The map is kept across rebuilds and raised only where the pooled edits say so.  In one frame (bounds_reference.sun_frame over a
+    cube that holds every box the life reaches: the box drifts by at most 12 cells) the world at a rebuild is held against the world at
+    the rebuild before: where the new lower bound stands above the old upper bound by more than the two deltas, a tight map of the world
+    before is too low for the world after, whatever the pool was made of."""
+    origin, edge = tuple(c - 16 for c in VL.ORIGIN), 256.0
+    assert all(o + 12 + n <= c + edge for o, n, c in zip(VL.ORIGIN, VL.SHAPE, origin))
+    info = BO.sun_frame(origin, edge)
+    delta = BO.sun_delta(info, np.asarray(origin, dtype=np.float64), edge)
+    hi_before, counts = None, []
+    for i, step, before, life, want in VL.replay(VL.schedule(index)):
+        if step["kind"] != "rebuild":
+            continue
+        lo, hi = BO.sun_map_bounds(BO.voxels_of(VL.filled(life.d), life.origin), info, delta)
+        if hi_before is not None:
+            counts.append(int((lo - delta > hi_before + delta).sum()))
+        hi_before = hi
+    print(f"life {index}: texels a kept map would leave too low, per rebuild after the first: {counts}")
+    assert sum(1 for c in counts if c > 0) >= 2, counts
 
 
 # ---- the host builds through the same lives -------------------------------------------------------------------------------------------------
