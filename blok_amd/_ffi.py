@@ -375,6 +375,8 @@ HIP_SYMBOLS = {
     "blok_hip_beam_cache_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "blok_hip_beam_cache_download_starts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "blok_hip_beam_cache_start_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "blok_hip_beam_cache_download_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "blok_hip_beam_cache_node_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "blok_hip_set_packed_fill": (C.c_int, [C.c_void_p, C.c_uint32]),
     "blok_hip_packed_fill_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "blok_hip_beam_cache_refines": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -323,6 +323,7 @@ int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode) {
     ctx->beam_cache.refine = mode >= 2;
     ctx->beam_cache.packed = mode >= 3;
     ctx->beam_cache.policy.own_starts = mode >= 4;
+    ctx->beam_cache.policy.node_restart = mode >= 5;
     blok::beam_cache_clear(ctx->beam_cache.policy);      // off: every launch searches, as before there was a cache; on again: views are admitted afresh
     if (!ctx->beam_cache.packed) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -396,6 +397,33 @@ int blok_hip_beam_cache_start_counters(const blok_hip_ctx* ctx, uint64_t* out_fr
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     if (out_from_starts) *out_from_starts = ctx->beam_cache.start_hits;
     if (out_other_key) *out_other_key = ctx->beam_cache.start_other_key;
+    return BLOK_OK;
+}
+
+// The node words of that slot's list, in list order, and the per-pixel words of the latest count launch (mode 5).
+int blok_hip_beam_cache_download_nodes(blok_hip_ctx* ctx, int* out_has_nodes, uint32_t* out_entry_words_host, size_t entry_capacity, uint32_t* out_pixel_words_host, size_t pixel_capacity) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const auto& B = ctx->beam_cache;
+    const bool has = B.last_list && B.last_slot >= 0 && static_cast<uint32_t>(B.last_slot) < blok::kBeamCacheSlots && B.policy.starts[B.last_slot] && B.policy.nodes[B.last_slot] &&
+                     B.slots[B.last_slot].d_node;
+    if (out_has_nodes) *out_has_nodes = has ? 1 : 0;
+    if (!out_entry_words_host && !out_pixel_words_host) return BLOK_OK;      // the state alone: waits for nothing
+    if (!has) return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the latest launch's slot has no list with node words");
+    const auto& sl = B.slots[B.last_slot];
+    const size_t entries = static_cast<size_t>(sl.n_words / blok::kPackGroups) * blok::kPackStretch, pixels = static_cast<size_t>(B.last_w) * B.last_h;
+    if (entries > sl.d_node.capacity() || pixels > B.d_ray_node.capacity()) return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: the node words' buffers are gone (a resize)");
+    if ((out_entry_words_host && entry_capacity < entries) || (out_pixel_words_host && pixel_capacity < pixels))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "beam cache: output smaller than the list or the rectangle");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    if (out_entry_words_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_entry_words_host, sl.d_node, entries * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_pixel_words_host) BLOK_HIP_TRY(ctx, hipMemcpy(out_pixel_words_host, B.d_ray_node, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_beam_cache_node_counters(const blok_hip_ctx* ctx, uint64_t* out_from_nodes) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (out_from_nodes) *out_from_nodes = ctx->beam_cache.node_hits;
     return BLOK_OK;
 }
 

@@ -188,12 +188,15 @@ struct blok_hip_ctx {
             // adopted once `list_done` has been seen complete, so no reader ever waits; rebuilt only behind a refill, under the rule above
             blok::DeviceArray<uint32_t> d_list, d_table;
             blok::DeviceArray<float> d_start;               // mode 4: every entry's own start parameter, in list order (written by the same build)
+            blok::DeviceArray<uint32_t> d_node;             // mode 5: ... and the node its restarted walk ends in (trace_core.h: restart_node_word), in list order
             uint32_t n_words = 0, n_groups = 0;             // the table's words as built (kPackGroups per area); its non-empty groups, as read from h_groups at adoption
         } slots[blok::kBeamCacheSlots];
         bool packed = true;                                 // ... with the packed walk (mode 3)
         blok::DeviceArray<uint8_t> d_trips;                 // the count launch's trips, a byte per pixel of the frame: one build at a time reads it
         blok::DeviceArray<float> d_ray_start;               // mode 4: ... and every ray's restart parameter, a float per pixel; the policy's own_starts is the mode
         blok::DeviceArray<uint8_t> d_restarts;              // ... and the trips of the walk restarted there, a byte per pixel: what a mode-4 build sorts by
+        blok::DeviceArray<uint32_t> d_ray_node;             // mode 5: ... and the node word of every ray, a word per pixel; the policy's node_restart is the mode
+        uint64_t node_hits = 0;                             // blok_hip_beam_cache_node_counters: packed hits that ran packed_frame_node_kernel
         blok::DeviceArray<uint32_t> d_words;                // ... its table before the sort (kPackGroups words per area)
         blok::DeviceBytes d_sort_temp; size_t sort_temp_bytes = 0;
         blok::PinnedArray<uint32_t> h_groups;               // pinned, one word per slot: the table's length, written by the device before list_done

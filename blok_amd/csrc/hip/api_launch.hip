@@ -403,9 +403,10 @@ int beam_list_buffers(blok_hip_ctx* ctx) {
     if (!B.packed) return BLOK_OK;
     const size_t areas = static_cast<size_t>((ctx->width + blok::kPackArea - 1u) / blok::kPackArea) * ((ctx->height + blok::kPackArea - 1u) / blok::kPackArea);
     const size_t entries = areas * blok::kPackStretch, words = areas * blok::kPackGroups, pixels = static_cast<size_t>(ctx->width) * ctx->height;
-    const bool own = B.policy.own_starts;
+    const bool own = B.policy.own_starts, nodes = own && B.policy.node_restart;
     if (B.list_capacity >= entries && B.words_capacity >= words && B.d_trips.capacity() >= pixels &&
-        (!own || (B.d_ray_start.capacity() >= pixels && B.d_restarts.capacity() >= pixels && B.slots[0].d_start.capacity() >= entries))) return BLOK_OK;
+        (!own || (B.d_ray_start.capacity() >= pixels && B.d_restarts.capacity() >= pixels && B.slots[0].d_start.capacity() >= entries)) &&
+        (!nodes || (B.d_ray_node.capacity() >= pixels && B.slots[0].d_node.capacity() >= entries))) return BLOK_OK;
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
     B.list_capacity = 0; B.words_capacity = 0;
     blok::beam_cache_clear(B.policy);
@@ -415,10 +416,12 @@ int beam_list_buffers(blok_hip_ctx* ctx) {
         BLOK_HIP_TRY(ctx, sl.d_list.reserve(entries, waited));
         BLOK_HIP_TRY(ctx, sl.d_table.reserve(words, waited));
         if (own) BLOK_HIP_TRY(ctx, sl.d_start.reserve(entries, waited));
+        if (nodes) BLOK_HIP_TRY(ctx, sl.d_node.reserve(entries, waited));
         sl.n_groups = 0;
     }
     BLOK_HIP_TRY(ctx, B.d_trips.reserve(pixels, waited));
     if (own) { BLOK_HIP_TRY(ctx, B.d_ray_start.reserve(pixels, waited)); BLOK_HIP_TRY(ctx, B.d_restarts.reserve(pixels, waited)); }
+    if (nodes) BLOK_HIP_TRY(ctx, B.d_ray_node.reserve(pixels, waited));
     BLOK_HIP_TRY(ctx, B.d_words.reserve(words, waited));
     B.sort_temp_bytes = blok::pack_table_temp_bytes(static_cast<uint32_t>(words));
     BLOK_HIP_TRY(ctx, B.d_sort_temp.reserve(B.sort_temp_bytes ? B.sort_temp_bytes : 16, waited));
@@ -480,6 +483,9 @@ static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok:
     std::memcpy(start_key.jitter_clip, args.jitter_clip, sizeof(start_key.jitter_clip));
     std::memcpy(&start_key.tmin, &args.tmin, sizeof(uint32_t)); std::memcpy(&start_key.tmax, &args.tmax, sizeof(uint32_t));
     *starts = blok::plan_beam_starts(B.policy, *plan, *listed, start_key);
+    // mode 5: the node words beside the starts — unless the tree's node indices do not fit them, or (never: beam_list_buffers) there is nowhere to put them
+    if (blok::beam_nodes_count(B.policy, *plan, *starts) && (!blok::node_words_apply(ctx->stats.n_tree_nodes) || !B.d_ray_node || !B.slots[plan->slot].d_node))
+        blok::beam_nodes_decline(B.policy, plan->slot);
     if (plan->action == blok::BeamAction::Search) return BLOK_OK;
     auto& sl = B.slots[plan->slot];
     if (plan->action == blok::BeamAction::Hit) {
@@ -630,18 +636,24 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
         const bool one_launch = listed.use_list && sl.n_groups > 0u && B.packed_fill > 0u;
         if (!one_launch) blok::launch_beam_fill(mode, fill, n_beams, sl.d_fine, stream);
         if (one_launch) {
-            const uint32_t tail = starts.use == blok::BeamStarts::Use ? blok::launch_packed_frame_own(fill, sl.d_start, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream)
-                                                                      : blok::launch_packed_frame(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream);
+            const bool from_nodes = blok::beam_nodes_use(B.policy, cached, starts) && sl.d_node;      // mode 5, and the slot's list has node words
+            const uint32_t tail = from_nodes ? blok::launch_packed_frame_node(fill, sl.d_start, sl.d_node, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream)
+                                  : starts.use == blok::BeamStarts::Use ? blok::launch_packed_frame_own(fill, sl.d_start, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream)
+                                                                        : blok::launch_packed_frame(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream);
             B.one_launch_frames += 1u; B.fill_only_workgroups += tail;
+            if (from_nodes) B.node_hits += 1u;
         } else if (listed.use_list && starts.use == blok::BeamStarts::Use) blok::launch_packed_walk_own(fill, sl.d_start, sl.d_list, sl.d_table, sl.n_groups, stream);
         else if (listed.use_list) blok::launch_packed_walk(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, stream);
         else if (starts.count_own) {
             // mode 4: the count launch also leaves every ray's own start and restarted trips; the build sorts by those and writes the starts in list order
             blok::TraceArgs walk = fill;
             walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
-            blok::launch_trace_count_own(walk, blocks, B.d_trips, B.d_ray_start, B.d_restarts, stream);
+            // mode 5: ... and the node every restarted walk ends in, gathered beside the starts
+            const bool with_nodes = blok::beam_nodes_count(B.policy, cached, starts);
+            blok::launch_trace_count_own(walk, blocks, B.d_trips, B.d_ray_start, B.d_restarts, with_nodes ? B.d_ray_node.get() : nullptr, stream);
             sl.n_words = blok::pack_areas(args) * blok::kPackGroups; sl.n_groups = 0u;
-            blok::launch_pack_build_own(fill, sl.d_fine, B.d_restarts, B.d_ray_start, sl.d_list, B.d_words, sl.d_start, stream);
+            if (with_nodes) blok::launch_pack_build_node(fill, sl.d_fine, B.d_restarts, B.d_ray_start, B.d_ray_node, sl.d_list, B.d_words, sl.d_start, sl.d_node, stream);
+            else blok::launch_pack_build_own(fill, sl.d_fine, B.d_restarts, B.d_ray_start, sl.d_list, B.d_words, sl.d_start, stream);
         } else {
             blok::TraceArgs walk = fill;
             walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;

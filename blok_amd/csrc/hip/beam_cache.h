@@ -104,6 +104,11 @@ enum class BeamStarts : int {
     OtherKey = 2,                              // a packed hit under another start key: from the finer bounds, this launch
 };
 struct BeamStartsPlan { bool count_own; BeamStarts use; };          // count_own: the launch told "count now" also leaves the starts
+// Mode 5: beside its start every listed ray keeps the NODE its restarted walk ends in (trace_core.h: restart_node_word), left by the same
+// count launch and gathered by the same build, and a packed hit from the starts makes that walk's last trip alone (walk_enter_node).  The
+// node is a function of the ray, its interval and the tree: of the beam key (the tree's address and versions) and the start key together,
+// so the words live and die with the starts — `nodes[slot]` is set where `starts[slot]` is, and only then — and serve exactly the launches
+// the starts serve.
 
 struct BeamCachePolicy {
     BeamKey key[kBeamCacheSlots];
@@ -121,6 +126,8 @@ struct BeamCachePolicy {
     bool own_starts = true;                    // the lists carry starts (a mode: kept by beam_cache_clear)
     bool starts[kBeamCacheSlots];              // the slot's list (built, or being counted and built) carries starts, counted under start_key
     BeamStartKey start_key[kBeamCacheSlots];
+    bool node_restart = true;                  // the lists with starts carry node words as well (mode 5: kept by beam_cache_clear)
+    bool nodes[kBeamCacheSlots];               // the slot's list carries them (never without starts[slot])
     int building = -1;                         // the slot the build in flight writes (-1: none is in flight)
     bool building_stale = false;               // ... and that slot has been refilled or cleared since: the build finishes into a list nobody adopts
 };
@@ -128,7 +135,7 @@ struct BeamCachePolicy {
 // The slot's finer bounds are gone (a refill, an eviction, a clear): its list goes with them.  A build still in flight for it stays "in
 // flight" — it is writing the slot's buffers, and the context's — until a launch sees it finished.
 inline void beam_list_drop(BeamCachePolicy& s, int slot) {
-    s.list[slot] = BeamList::None; s.fine_hits[slot] = 0u; s.starts[slot] = false;
+    s.list[slot] = BeamList::None; s.fine_hits[slot] = 0u; s.starts[slot] = false; s.nodes[slot] = false;
     if (s.building == slot) s.building_stale = true;
 }
 
@@ -213,6 +220,7 @@ inline BeamStartsPlan plan_beam_starts(BeamCachePolicy& s, const BeamCachePlan& 
     if (p.action != BeamAction::Hit || p.slot < 0 || p.slot >= kBeamCacheSlots) return {false, BeamStarts::None};
     if (l.count_now) {
         s.starts[p.slot] = s.own_starts;
+        s.nodes[p.slot] = s.own_starts && s.node_restart;
         if (s.own_starts) s.start_key[p.slot] = k;
         return {s.own_starts, BeamStarts::None};
     }
@@ -226,7 +234,19 @@ inline void beam_list_commit(BeamCachePolicy& s, int slot, bool issued) {
     if (slot < 0 || slot >= kBeamCacheSlots || s.list[slot] != BeamList::Now) return;
     s.list[slot] = issued ? BeamList::Building : BeamList::None;
     if (issued) { s.building = slot; s.building_stale = false; }
-    else { s.fine_hits[slot] = 0u; s.starts[slot] = false; }
+    else { s.fine_hits[slot] = 0u; s.starts[slot] = false; s.nodes[slot] = false; }
+}
+
+// The launch told to count the starts cannot leave node words (a tree whose node indices do not fit the word): the slot's list has starts alone.
+inline void beam_nodes_decline(BeamCachePolicy& s, int slot) {
+    if (slot >= 0 && slot < kBeamCacheSlots) s.nodes[slot] = false;
+}
+// Does a launch that plan_beam_starts told `plan` count the node words / walk from them?
+inline bool beam_nodes_count(const BeamCachePolicy& s, const BeamCachePlan& p, const BeamStartsPlan& plan) {
+    return plan.count_own && p.slot >= 0 && p.slot < kBeamCacheSlots && s.nodes[p.slot];
+}
+inline bool beam_nodes_use(const BeamCachePolicy& s, const BeamCachePlan& p, const BeamStartsPlan& plan) {
+    return plan.use == BeamStarts::Use && p.slot >= 0 && p.slot < kBeamCacheSlots && s.node_restart && s.nodes[p.slot];
 }
 
 }  // namespace blok

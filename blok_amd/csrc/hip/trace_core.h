@@ -565,6 +565,108 @@ BLOK_DEV bool walk_enter_wave(const TraceArgs& A, const RayIn& r, const WalkRay&
 }
 #endif
 
+// ---- a listed ray of a view at rest re-enters at its last node (beam_cache.h: mode 5) -------------------------------------------------------
+// A ray restarted at its own start (walk_loop: kOwn) still descends from the root to the cell its answer lies in, and under the view's key
+// (beam_cache.h: BeamKey — the tree's address and content) that descent ends in the same node every frame.  The count launch leaves that
+// node beside the start, as one word: the index in A.nodes of the node whose child is the cell of the ray's last trip (the brick for a hit,
+// the parent of the last cell it stood in otherwise) and that cell's level in the top three bits (levels <= 7); all ones for a ray without
+// a trip.  The frame then makes the last trip alone (walk_enter_node).
+constexpr uint32_t kNodeWordNone = 0xFFFFFFFFu;
+constexpr uint32_t kNodeWordLevelShift = 29u;
+constexpr uint32_t kNodeWordIndexMask = (1u << kNodeWordLevelShift) - 1u;      // a tree of 2^29 nodes or more has no node words (trace_kernels.h: node_words_apply)
+
+// resume_axis with the guess brought into [0, W) instead of given up outside it.  A listed ray's own start is very often the parameter at
+// which it enters the world box (a hit on the world's outer face, a miss's first cell), and there the point o + d tS lies a rounding error
+// inside or outside the face: resume_axis gives up on the outside half.  The guess is only a guess — what is returned is VERIFIED with the
+// canonical T exactly as there (T(q) <= tS < T(q + 1), 0 <= q < W), so it is the root walk's start voxel whatever the guess was.
+BLOK_DEV bool start_axis(const Axis& a, bool neg, float point, float inv_vs, int origin, int W, float tS, float& f, float& t_far) {
+    const float w = floorf(point * inv_vs) - static_cast<float>(origin);
+    const float v = neg ? static_cast<float>(W - 1) - w : w;
+    if (!(v == v)) return false;                                                  // NaN
+    const float u = fminf(fmaxf(v, 0.0f), static_cast<float>(W - 1));
+    f = kCoordBias + u;
+    float t_lo = plane_t(a, f);
+    t_far = plane_t(a, f + 1.0f);
+    if (t_lo > tS) { f -= 1.0f; t_far = t_lo; t_lo = plane_t(a, f); }
+    else if (t_far <= tS) { f += 1.0f; t_lo = t_far; t_far = plane_t(a, f + 1.0f); }
+    return t_lo <= tS && tS < t_far && f >= kCoordBias && f <= kCoordBias + static_cast<float>(W - 1);
+}
+
+// walk_resume's step 1 for the interval [r.tmin, r.tmax), as walk_enter_wave takes it: the verified start voxel (mirrored, 2^23 + q) and the
+// T of its far planes.  false: no such voxel next to the guess, or outside the world — nothing is known about the walk's start.
+BLOK_DEV bool start_voxel(const TraceArgs& A, const RayIn& r, const WalkRay& R, float& fx, float& fy, float& fz, float& tFx, float& tFy, float& tFz) {
+    const int W = 1 << (2 * A.levels);
+    const float tS = r.tmin;
+    const bool negx = !(R.ax.inv > 0.0f), negy = !(R.ay.inv > 0.0f), negz = !(R.az.inv > 0.0f);
+    fx = fy = fz = kCoordBias; tFx = tFy = tFz = 0.0f;            // (start_axis leaves them alone where it has no guess)
+    bool ok = start_axis(R.ax, negx, __builtin_fmaf(r.dx, tS, r.ox), A.inv_voxel_size, A.origin[0], W, tS, fx, tFx);
+    ok = start_axis(R.ay, negy, __builtin_fmaf(r.dy, tS, r.oy), A.inv_voxel_size, A.origin[1], W, tS, fy, tFy) && ok;
+    ok = start_axis(R.az, negz, __builtin_fmaf(r.dz, tS, r.oz), A.inv_voxel_size, A.origin[2], W, tS, fz, tFz) && ok;
+    return ok && tS < r.tmax;
+}
+
+// The count launch's side.  r: the ray with tmin = max(tmin, its own start); level: the level of the cell of its last trip.  The walk from
+// the root over [r.tmin, r.tmax) descends through the cells that hold its start voxel for as long as they are occupied (walk_resume, steps 1
+// and 2; walk_enter_wave), so the node it stands in at `level`, if it gets there by descents alone, is found by the start voxel's digits:
+// at most levels - 1 dependent loads, once per view.  Anything else — no verified start voxel, an empty cell on the way — is no word.
+BLOK_DEV uint32_t restart_node_word(const TraceArgs& A, const RayIn& r, const WalkRay& R, const uint32_t level) {
+    if (level >= A.levels) return kNodeWordNone;
+    float fx, fy, fz, tFx, tFy, tFz;
+    if (!start_voxel(A, r, R, fx, fy, fz, tFx, tFy, tFz)) return kNodeWordNone;
+    uint32_t index = 0u;
+    for (uint32_t lvl = A.levels - 1u; lvl > level; --lvl) {
+        const uint4 c = A.nodes[index];
+        NodeRec node;
+        node.lo = c.x; node.hi = c.y; node.base = c.z;
+        const uint32_t shift = 2u * lvl;
+        const uint32_t bit = (digit2(__float_as_uint(fx), shift) | (digit2(__float_as_uint(fy), shift) << 2) | (digit2(__float_as_uint(fz), shift) << 4)) ^ R.mirror;
+        if (!mask_bit(node, bit)) return kNodeWordNone;
+        index = child_index(node, bit);
+    }
+    if (index > kNodeWordIndexMask) return kNodeWordNone;
+    return index | (level << kNodeWordLevelShift);
+}
+
+// The frame's side: the last trip of the walk from the root over [r.tmin, r.tmax), alone.  rec = A.nodes[word & kNodeWordIndexMask], loaded
+// by the caller in front of the ray's set-up (the index comes from the record, so the load's latency lies under primary_ray and walk_ray;
+// A.nodes[0] for a lane without a word).  The start voxel is verified as walk_enter_wave verifies it, aligned to the word's level as its
+// `keep` branch does, and then walk_loop's trip is written out once: the bit, `occupied`, tExit, `found`, `go`, the stepped coordinate's `up`.
+// true: the lane is SETTLED — the walk from the root arrives in this cell, in this node, with tCur = r.tmin and these far planes (the
+// argument of walk_resume and walk_enter_wave, given the word), and this trip is its last: s.found says whether it reports (then `s` is what
+// walk_hit reads) or ends without a report.  false: nothing may be concluded — no word, no verified start voxel, a level the tree has not,
+// an occupied cell above level 0 (a descent), a step that stays inside the world — and the caller walks from the root.
+BLOK_DEV bool walk_enter_node(const TraceArgs& A, const RayIn& r, const WalkRay& R, const uint32_t word, const uint4 rec, WalkState& s) {
+    const uint32_t lvl = word >> kNodeWordLevelShift;
+    float fx, fy, fz, tFx, tFy, tFz;
+    const bool ok = start_voxel(A, r, R, fx, fy, fz, tFx, tFy, tFz) && word != kNodeWordNone && lvl < A.levels;
+    const uint32_t shift = 2u * lvl;
+    const float size = cell_size_of_shift(shift);
+    if (shift != 0u) {
+        const uint32_t keep = ~((1u << shift) - 1u);              // clears mantissa bits only (shift <= 14)
+        fx = __uint_as_float(__float_as_uint(fx) & keep); fy = __uint_as_float(__float_as_uint(fy) & keep); fz = __uint_as_float(__float_as_uint(fz) & keep);
+        tFx = plane_t(R.ax, fx + size); tFy = plane_t(R.ay, fy + size); tFz = plane_t(R.az, fz + size);
+    }
+    const uint32_t bit = (digit2(__float_as_uint(fx), shift) | (digit2(__float_as_uint(fy), shift) << 2) | (digit2(__float_as_uint(fz), shift) << 4)) ^ R.mirror;
+    NodeRec node;
+    node.lo = rec.x; node.hi = rec.y; node.base = rec.z;
+    const bool occupied = mask_bit(node, bit);
+    const float tCur = r.tmin;
+    const float tExit = fminf(fminf(tFx, tFy), tFz);
+    const bool found = occupied && tCur < fminf(tExit, r.tmax);
+    const bool go = !found && tExit < r.tmax;
+    bool ends = !go;
+    if (go) {
+        const bool sx = tFx == tExit;
+        const bool sy = !sx && tFy == tExit;
+        const float stepped = (sx ? fx : (sy ? fy : fz)) + size;
+        const uint32_t up = static_cast<uint32_t>(__builtin_ctz(__float_as_uint(stepped))) & ~1u;
+        ends = up >= 2u * A.levels;                               // left the world box
+    }
+    s.fx = fx; s.fy = fy; s.fz = fz; s.tFx = tFx; s.tFy = tFy; s.tFz = tFz; s.tCur = tCur; s.size = size;
+    s.lvl = lvl; s.bit = bit; s.node = node; s.walking = false; s.found = found;
+    return ok && !(occupied && shift != 0u) && (found || ends);
+}
+
 // Walks one ray.  `stk` points at this lane's slot of the LDS node stack (stride kBlock entries between
 // levels; slot l-2 holds the node of level l on the current path).
 //

@@ -331,7 +331,8 @@ void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t
 // (slot_start: kPackStretch floats per area, like the list); the walk reads entry and start and never the finer bounds.  A walk of the
 // same ray from the root from that parameter reports what the counted walk did (trace_core.h: walk_loop), so the frame's bytes are the same
 // — for the counted rays only: another jitter or interval walks the same list with launch_packed_walk.
-void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, hipStream_t stream);
+// node_words (mode 5, else null): the count launch also leaves, per pixel, the node that restarted walk ends in (trace_core.h: restart_node_word).
+void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, uint32_t* node_words, hipStream_t stream);
 void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream);
 void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
 // The packed frame in ONE launch: the two walks above, and in the same grid the miss pixels launch_beam_fill writes in front of them (with
@@ -345,6 +346,16 @@ void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, cons
 uint32_t launch_packed_frame(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream);
 uint32_t launch_packed_frame_own(const TraceArgs& args, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave,
                                  hipStream_t stream);
+// Mode 5: a listed ray re-enters at the node its restarted walk ends in.  The build's gather writes every entry's node word beside its start
+// (slot_node, kPackStretch words per area, like slot_start: two coalesced loads per entry in the frame), and launch_packed_frame_node is
+// launch_packed_frame_own whose walk waves make the walk's last trip alone (trace_core.h: walk_enter_node); a wave with a lane that trip
+// does not settle walks as launch_packed_frame_own's.  The same bytes — for the counted rays over the counted tree, as the starts.
+// node_words_apply: the tree's node indices fit a word beside the level (fewer than 2^29 nodes); else the view runs as mode 4.
+bool node_words_apply(size_t n_tree_nodes);
+void launch_pack_build_node(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, const uint32_t* node_words, uint32_t* list, uint32_t* words,
+                            float* slot_start, uint32_t* slot_node, hipStream_t stream);
+uint32_t launch_packed_frame_node(const TraceArgs& args, const float* slot_start, const uint32_t* slot_node, const float* fine, const uint32_t* list, const uint32_t* table,
+                                  uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

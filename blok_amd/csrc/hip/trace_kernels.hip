@@ -191,9 +191,11 @@ __device__ __forceinline__ bool list_await(unsigned long long* slot, unsigned lo
 // comes from the frame's live list together with its start parameter (list launches): no order, no beam lookup, no cost.
 // kCount (trace_count_kernel): every lane that walks also leaves its trips in trips[its pixel of the rectangle].
 // kOwn (trace_count_own_kernel): ... and its restart parameter and restarted trips (trace_core.h: walk_loop) in starts[], restarts[] of the same pixel.
+// ... and, with node_words, the node its restarted walk ends in (trace_core.h: restart_node_word) in node_words[] of the same pixel.
 template <RayMode MODE, bool kListed = false, bool kCount = false, bool kOwn = false>
 __device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t block, const uint32_t grid, uint4* lds_stack, const float listed_t0 = 0.0f,
-                                            [[maybe_unused]] uint8_t* trips = nullptr, [[maybe_unused]] float* starts = nullptr, [[maybe_unused]] uint8_t* restarts = nullptr) {
+                                            [[maybe_unused]] uint8_t* trips = nullptr, [[maybe_unused]] float* starts = nullptr, [[maybe_unused]] uint8_t* restarts = nullptr,
+                                            [[maybe_unused]] uint32_t* node_words = nullptr) {
     const uint32_t tid = threadIdx.x;
     uint4* stk = lds_stack + tid;
 
@@ -313,6 +315,15 @@ __device__ __forceinline__ void trace_block(const TraceArgs& A, const uint32_t b
         else if constexpr (kCount) trace_one<true, true>(A, r, stk, sink, trips + out_index);
         else trace_one<BLOK_WAVE_START != 0>(A, r, stk, sink);
         if (cost_slot && tid == 0) *cost_slot = max(static_cast<uint32_t>(__builtin_amdgcn_s_memtime() - clock0), 256u);     // it walked: any key >= 256 clocks counts as live in the next order
+        if constexpr (kOwn) if (node_words) {
+            // ... and the node the restarted walk ends in (trace_core.h: restart_node_word), behind the walk: the lane's own start and restarted
+            // trips as it has just left them — levels - trips is the level of the cell of its last trip
+            const uint32_t restarted = restarts[out_index];
+            RayIn from = r;
+            from.tmin = fmaxf(A.tmin, starts[out_index]);
+            const WalkRay R = walk_ray(A, r.ox, r.oy, r.oz, safe_inv(r.dx), safe_inv(r.dy), safe_inv(r.dz));
+            node_words[out_index] = restarted != 0u && restarted <= A.levels ? restart_node_word(A, from, R, A.levels - restarted) : kNodeWordNone;
+        }
     }
 }
 
@@ -329,9 +340,10 @@ __global__ __launch_bounds__(kBlock) void trace_count_kernel(const TraceArgs A, 
 }
 
 // ... and leaves every walked ray's own restart parameter and restarted trips beside its trips (beam_cache.h: the starts of a packed list).
-__global__ __launch_bounds__(kBlock) void trace_count_own_kernel(const TraceArgs A, uint8_t* trips, float* starts, uint8_t* restarts) {
+// node_words (mode 5; null in mode 4): a word per pixel as well, the node that walk ends in.
+__global__ __launch_bounds__(kBlock) void trace_count_own_kernel(const TraceArgs A, uint8_t* trips, float* starts, uint8_t* restarts, uint32_t* node_words) {
     extern __shared__ uint4 lds_stack[];
-    trace_block<RayMode::Rect, false, true, true>(A, blockIdx.x, gridDim.x, lds_stack, 0.0f, trips, starts, restarts);
+    trace_block<RayMode::Rect, false, true, true>(A, blockIdx.x, gridDim.x, lds_stack, 0.0f, trips, starts, restarts, node_words);
 }
 
 // The arguments of frame f of a several-frame launch: its camera, its slice of the outputs and of the beam buffer.
@@ -626,6 +638,19 @@ __global__ __launch_bounds__(256) void pack_starts_kernel(const uint32_t* list, 
     slot_start[i] = starts[static_cast<size_t>(ry) * w + rx];
 }
 
+// The same with every entry's node word beside its start (mode 5), one launch for both: slot_node[i] from node_words[its pixel].  An
+// entry's start and its node word are two arrays in list order — two coalesced loads in the frame, like the entry itself — so that the starts
+// stay what mode 4 and the read-backs know.
+__global__ __launch_bounds__(256) void pack_starts_nodes_kernel(const uint32_t* list, const float* starts, const uint32_t* node_words, const uint32_t w, const uint32_t h,
+                                                                const uint32_t n_entries, float* slot_start, uint32_t* slot_node) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_entries) return;
+    const uint32_t entry = list[i], rx = entry & 0xFFFFu, ry = entry >> 16;
+    if (entry == kPackPad || rx >= w || ry >= h) return;
+    slot_start[i] = starts[static_cast<size_t>(ry) * w + rx];
+    slot_node[i] = node_words[static_cast<size_t>(ry) * w + rx];
+}
+
 // One wave per group of the list, heaviest first.  Nothing here is collective before a padding lane has left.
 __global__ __launch_bounds__(kBlock) void packed_walk_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table) {
     static_assert(kBlock == 64, "one wave per group");
@@ -742,6 +767,48 @@ __global__ __launch_bounds__(kBlock) void packed_frame_own_kernel(const TraceArg
             RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
             r.tmin = fmaxf(r.tmin, t0);
             trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+        }
+    }
+    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+}
+
+// The same with every listed ray re-entered at the node its restarted walk ends in (slot_node, in list order beside slot_start; trace_core.h:
+// walk_enter_node): the lane loads that node in front of its ray's set-up and makes the walk's last trip alone — no descent from the root, no
+// stack.  A wave with a lane that is not settled by that one trip (no word: a ray of a live tile that misses the world box; anything the
+// word does not cover) has written nothing yet and walks as packed_frame_own_kernel's does, every lane from the root.  Only for a launch
+// whose rays are the counted ones over the counted tree (beam_cache.h: BeamKey, BeamStartKey).
+__global__ __launch_bounds__(kBlock) void packed_frame_node_kernel(const TraceArgs A, const float* slot_start, const uint32_t* slot_node, const float* fine, const uint32_t* list,
+                                                                   const uint32_t* table, const uint32_t n_groups, const uint32_t n_units, const uint32_t units_x) {
+    static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
+    extern __shared__ uint4 lds_stack[];
+    const uint32_t lane = threadIdx.x;
+    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    if (blockIdx.x < n_groups) {
+        const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
+        const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+        const float t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
+        const uint32_t word = slot_node[static_cast<size_t>(group) * 64u + lane];
+        const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
+        if (entry != kPackPad && rx < A.w && ry < A.h) {
+            const uint4 rec = A.nodes[word == kNodeWordNone ? 0u : (word & kNodeWordIndexMask)];
+            const size_t at = static_cast<size_t>(ry) * A.w + rx;
+            const Sink dst{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr};
+            RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+            r.tmin = fmaxf(r.tmin, t0);
+            const WalkRay R = walk_ray(A, r.ox, r.oy, r.oz, safe_inv(r.dx), safe_inv(r.dy), safe_inv(r.dz));
+            WalkState s;
+            const bool settled = walk_enter_node(A, r, R, word, rec, s);
+            if (__ballot(!settled) != 0ull) trace_one<true>(A, r, lds_stack + lane, dst);
+            else if (s.found) {
+                const HitInfo h = walk_hit(A, r, R, s);           // the record and the pixel as trace_one writes them
+                uint4 out;
+                out.x = __float_as_uint(h.t);
+                out.y = h.material;
+                out.z = (static_cast<uint32_t>(h.vx) & 0xFFFFu) | (static_cast<uint32_t>(h.vy) << 16);
+                out.w = (static_cast<uint32_t>(h.vz) & 0xFFFFu) | (h.face << 16) | (1u << 24);
+                if (dst.hit) *reinterpret_cast<uint4*>(dst.hit) = out;
+                if (dst.rgba) *dst.rgba = shade_rgba(A.mat_table, A.n_materials, h.material, h.face);
+            } else write_miss(dst);
         }
     }
     if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
@@ -1576,9 +1643,19 @@ void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* 
     hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, trips, fine, args.w, args.h, list, words);
 }
 
-void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, hipStream_t stream) {
+void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, uint32_t* node_words, hipStream_t stream) {
     if (n_blocks == 0 || !trips || !starts || !restarts) return;
-    hipLaunchKernelGGL(trace_count_own_kernel, dim3(n_blocks), dim3(kBlock), frame_lds_bytes(args), stream, args, trips, starts, restarts);
+    hipLaunchKernelGGL(trace_count_own_kernel, dim3(n_blocks), dim3(kBlock), frame_lds_bytes(args), stream, args, trips, starts, restarts, node_words);
+}
+
+bool node_words_apply(size_t n_tree_nodes) { return n_tree_nodes != 0 && n_tree_nodes <= static_cast<size_t>(kNodeWordIndexMask); }
+
+void launch_pack_build_node(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, const uint32_t* node_words, uint32_t* list, uint32_t* words,
+                            float* slot_start, uint32_t* slot_node, hipStream_t stream) {
+    if (!pack_applies(args) || !fine || !restarts || !starts || !node_words || !list || !words || !slot_start || !slot_node) return;
+    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, restarts, fine, args.w, args.h, list, words);
+    const uint32_t n_entries = pack_areas(args) * kPackStretch;
+    hipLaunchKernelGGL(pack_starts_nodes_kernel, dim3((n_entries + 255u) / 256u), dim3(256), 0, stream, list, starts, node_words, args.w, args.h, n_entries, slot_start, slot_node);
 }
 
 void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream) {
@@ -1610,6 +1687,14 @@ uint32_t launch_packed_frame_own(const TraceArgs& args, const float* slot_start,
     if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !slot_start || !fine || !list || !table) return 0u;
     const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
     hipLaunchKernelGGL(packed_frame_own_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, fine, list, table, n_groups, g.n_units, g.units_x);
+    return g.grid - n_groups;
+}
+
+uint32_t launch_packed_frame_node(const TraceArgs& args, const float* slot_start, const uint32_t* slot_node, const float* fine, const uint32_t* list, const uint32_t* table,
+                                  uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream) {
+    if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !slot_start || !slot_node || !fine || !list || !table) return 0u;
+    const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
+    hipLaunchKernelGGL(packed_frame_node_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, slot_node, fine, list, table, n_groups, g.n_units, g.units_x);
     return g.grid - n_groups;
 }
 

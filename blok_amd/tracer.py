@@ -648,11 +648,12 @@ class HipTracer:
         self._check(self._lib.blok_hip_set_miss_writer(self._ctx, 1 if in_walk else 0))
 
     def set_beam_cache(self, mode):
-        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 4 or True (default) = with, from the view's K-th
-        hit on, a finer bound per wave tile, then its rays packed into a list, each restarted where its own counted walk ended; 3 = the list
+        """Keep the beam bounds of a view at rest from launch to launch (blok_hip_debug.h): 5 or True (default) = with, from the view's K-th
+        hit on, a finer bound per wave tile, then its rays packed into a list, each restarted where its own counted walk ended, at the tree
+        node that walk ends in; 4 = restarted there from the root; 3 = the list
         sorted by measured length and walked from the finer bounds; 2 = without the packed walk; 1 = the beam tiles' bounds alone; 0 or
         False = every launch searches.  Never changes a result."""
-        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (4 if mode else 0) if isinstance(mode, bool) else int(mode)))
+        self._check(self._lib.blok_hip_set_beam_cache(self._ctx, (5 if mode else 0) if isinstance(mode, bool) else int(mode)))
 
     def set_beam_refine_after(self, hits: int):
         """K: the hit of a kept view behind whose walk its finer bounds are searched, once (0 = the default; blok_hip_debug.h)."""
@@ -717,6 +718,28 @@ class HipTracer:
         used, other = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.blok_hip_beam_cache_start_counters(self._ctx, C.byref(used), C.byref(other)))
         return int(used.value), int(other.value)
+
+    def beam_cache_has_nodes(self) -> bool:
+        """Does the latest rectangle launch's packed list carry node words (mode 5)?  Waits for nothing."""
+        has = C.c_int(0)
+        self._check(self._lib.blok_hip_beam_cache_download_nodes(self._ctx, C.byref(has), None, 0, None, 0))
+        return bool(has.value)
+
+    def beam_cache_nodes(self, w: int, h: int):
+        """(entry words, pixel words) of the latest rectangle launch's packed list (blok_hip_debug.h: blok_hip_beam_cache_download_nodes), for its
+        rectangle of w x h pixels: entry words (areas, area^2) uint32 in list order, pixel words (h, w) uint32 of the latest count launch."""
+        state, areas = C.c_int(0), C.c_uint32(0)
+        self._check(self._lib.blok_hip_beam_cache_download_list(self._ctx, C.byref(state), C.byref(areas), None, None, 0, None, 0, None, 0))
+        entry_words = np.zeros((int(areas.value), self.pack_area() ** 2), dtype=np.uint32)
+        pixel_words = np.zeros((h, w), dtype=np.uint32)
+        self._check(self._lib.blok_hip_beam_cache_download_nodes(self._ctx, None, _ffi.ptr(entry_words), entry_words.size, _ffi.ptr(pixel_words), pixel_words.size))
+        return entry_words, pixel_words
+
+    def beam_cache_node_counter(self) -> int:
+        """Packed launches so far that re-entered their rays at the node words (packed_frame_node_kernel)."""
+        n = C.c_uint64(0)
+        self._check(self._lib.blok_hip_beam_cache_node_counters(self._ctx, C.byref(n)))
+        return int(n.value)
 
     def set_packed_fill(self, units_per_wave: int):
         """How a packed launch writes the miss pixels of its empty wave tiles (blok_hip_debug.h): 0 = a fill launch in front of the walk

@@ -645,7 +645,8 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  * 1.25: object motion for posed models in the path-traced chain (blok_pose_motion; blok_hip_posed_motion_device, blok_hip_denoise_posed*,
  *       blok_hip_draw_frame_rt_posed_motion).  (Planned as 1.24; that number went to the packed frame first.)
  * 1.26: emissive voxels as lights: a light table built from the quads snapshot and sampled at every hit of the path loop (blok_light;
- *       blok_hip_lights_from_quads, blok_hip_set_lights, blok_hip_lights_info, blok_hip_lights_download). */
+ *       blok_hip_lights_from_quads, blok_hip_set_lights, blok_hip_lights_info, blok_hip_lights_download).
+ * 1.27: a view at rest re-enters every listed ray at the node its restarted walk ends in (blok_hip_debug.h: blok_hip_set_beam_cache mode 5, the default). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

@@ -145,7 +145,11 @@ int blok_hip_set_miss_writer(blok_hip_ctx* ctx, int in_walk);
  * miss's last cell inside the world) and the trips of the walk from the root started there (at most the tree's levels); the list is sorted by
  * those, which leaves it nearly in pixel order, and carries every entry's start beside it; a packed launch whose jitter, tmin and tmax are the
  * count launch's, bit for bit, walks every listed ray from its own start — from the root to that cell — and any other packed launch of the
- * view walks the same list from the finer bounds as under 3 (another 21 bytes per pixel of the frame).  In every case the slots are emptied.
+ * view walks the same list from the finer bounds as under 3 (another 21 bytes per pixel of the frame); 5 (default since ABI 1.27) = as 4,
+ * and the count launch also leaves, for every ray, the tree node that walk from its own start ends in — the brick of a hit, the parent of a
+ * miss's last cell — with that cell's level, as one word, carried beside every entry's start; a packed launch that walks from the starts then
+ * loads that node directly and makes the walk's last trip alone, and a wave with a ray this does not settle (a ray of a live tile that misses
+ * the world box) walks as under 4 (another 8 bytes per pixel; a tree of 2^29 nodes or more runs as 4).  In every case the slots are emptied.
  * blok_hip_last_launch_kind goes on reporting the form the launch policy chose for the
  * device's state, also for a launch that walked from kept bounds (a plain trace launch).  Never changes a result. */
 int blok_hip_set_beam_cache(blok_hip_ctx* ctx, int mode);
@@ -175,6 +179,15 @@ int blok_hip_beam_cache_download_starts(blok_hip_ctx* ctx, int* out_state, float
                                         size_t restarts_capacity);
 /* Packed launches so far that walked from the starts, and that found another start key; either pointer may be null. */
 int blok_hip_beam_cache_start_counters(const blok_hip_ctx* ctx, uint64_t* out_from_starts, uint64_t* out_other_key);
+/* Mode 5's read-back, for the same slot: *out_has_nodes = 1 if its list carries node words; and into the buffers that are given, for such a
+ * slot: every entry's word in list order, 1 024 per area (defined where the list holds an entry that is not padding), and the words of the
+ * context's latest count launch, one per pixel of the rectangle, defined for the listed pixels.  A word is the index of a node of the tree
+ * (blok_hip_download_tree's order) in its low 29 bits and the level of the cell of the ray's last trip — a child of that node — in its top
+ * three; 0xFFFFFFFF for a ray that made no trip.  Waits for the device; launches nothing and changes nothing.  Any pointer may be null. */
+int blok_hip_beam_cache_download_nodes(blok_hip_ctx* ctx, int* out_has_nodes, uint32_t* out_entry_words_host_or_null, size_t entry_capacity, uint32_t* out_pixel_words_host_or_null,
+                                       size_t pixel_capacity);
+/* Packed launches so far that re-entered their rays at the node words (they count as launches from the starts too). */
+int blok_hip_beam_cache_node_counters(const blok_hip_ctx* ctx, uint64_t* out_from_nodes);
 /* How a packed launch (modes 3 and 4, a list with at least one group) writes the miss pixels of the wave tiles that are empty by the finer
  * bounds (ABI 1.24): 0 = a fill launch in front of the walk launch, as before; k >= 1 = ONE launch, in which the walk's
  * workgroups also write fill units — 64 consecutive pixels of a row of the rectangle, one to a lane — at most k to a workgroup, with
