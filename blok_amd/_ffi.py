@@ -57,6 +57,9 @@ QUADS_IGNORE_MATERIAL, QUADS_COUNT_ONLY = 1, 2
 LIGHT = np.dtype([("lo", "<i4", 3), ("du", "<u4"), ("dv", "<u4"), ("material", "<u4"), ("face", "<u4"), ("cum", "<u4")])
 LIGHTS_INFO = np.dtype([("n_faces", "<u8"), ("bytes", "<u8"), ("n", "<u4"), ("n_owned", "<u4"), ("area_world", "<f4"), ("reserved", "<u4")])
 assert LIGHT.itemsize == 32 and LIGHTS_INFO.itemsize == 32
+# = blok_instance_lights_info (32 bytes): the header of an instance table's light prefix
+INSTANCE_LIGHTS_INFO = np.dtype([("a_inst", "<u8"), ("a_total", "<u8"), ("area_world", "<f4"), ("n_lit", "<u4"), ("disabled", "<u4"), ("reserved", "<u4")])
+assert INSTANCE_LIGHTS_INFO.itemsize == 32
 STAMP_SET, STAMP_KEEP, STAMP_ERASE = 0, 1, 2      # = BLOK_STAMP_*
 CAPTURE_CUT = 1                                   # = BLOK_CAPTURE_CUT
 # = blok_component: one connected component of a labelled region, 40 bytes
@@ -261,6 +264,8 @@ HOST_SYMBOLS = {
     "blok_quads_write_obj": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_lights_from_quads": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]),
     "blok_lights_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "blok_model_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blok_instance_light_record": (None, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_capture_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
@@ -450,6 +455,11 @@ HIP_SYMBOLS = {
     "blok_hip_set_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_hip_lights_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_lights_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_model_lights": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_hip_model_lights_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "blok_hip_model_lights_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_model_lights_clear": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "blok_hip_instance_lights_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blok_hip_volume_stamp_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_hip_volume_stamp_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float,
                                                C.POINTER(C.c_uint64)]),

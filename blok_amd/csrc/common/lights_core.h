@@ -92,6 +92,151 @@ BLOK_LD void sample_point(const blok_light& L, uint32_t off, float u1, float u2,
     nl[0] = a == 0u ? s : 0.0f; nl[1] = a == 1u ? s : 0.0f; nl[2] = a == 2u ? s : 0.0f;
 }
 
+// ---- emissive models as lights (blok_hip.h: "emissive models as lights") ----
+// A model's table holds its exposed emissive UNIT faces in the order of its material array (bricks in the tree's order, cells in ascending
+// bit order, face 0..5 within a voxel); cum is the record's index.  The host build (host/model_lights.cpp) and the kernels (hip/lights_kernels.hip)
+// run the functions below over the model's 64-tree (hip/tree.h: 16-byte nodes, root first, every level in Morton order, the bricks last).
+struct Node { uint64_t mask; uint32_t base; };
+// The tree as both sides hand it over: node(i) loads node i; an index at or beyond n_nodes reads as an empty node, a material at or beyond
+// n_voxels as id 0, so a malformed tree costs wrong records, never a load outside the arrays.
+template <class LoadNode>
+struct ModelTree {
+    LoadNode node; uint32_t n_nodes;
+    const uint32_t* materials; uint32_t n_voxels;
+    uint32_t levels; int32_t origin[3];
+    BLOK_LD Node at(uint32_t i) const { return i < n_nodes ? node(i) : Node{0ull, 0u}; }
+    BLOK_LD uint32_t material(uint32_t i) const { return i < n_voxels ? materials[i] : 0u; }
+};
+// One table per model for the kernels that read it through the model id (the instance prefix): 16 bytes, table == null or n == 0: none.
+struct ModelLightTable { const blok_light* table; uint32_t n; uint32_t reserved; };
+
+BLOK_LD uint32_t popc64(uint64_t m) { return static_cast<uint32_t>(__builtin_popcountll(m)); }
+BLOK_LD uint32_t ctz64(uint64_t m) { return static_cast<uint32_t>(__builtin_ctzll(m)); }
+
+// Where level l begins (1: the bricks): the root's level begins at 0 and every level's block at the first child of the first node above it.
+template <class T> BLOK_LD uint32_t level_start(const T& t, uint32_t l) {
+    uint32_t start = 0u;
+    for (uint32_t k = t.levels; k > l; --k) start = t.at(start).base;
+    return start;
+}
+template <class T> BLOK_LD uint32_t first_brick(const T& t) { return level_start(t, 1u); }
+// The brick coordinates (bricks from the tree's origin) of brick node `index`: upwards, a level at a time — the parent is the last node of
+// the level above whose base is <= the child's index (bases ascend within a level), the digit the child's rank among its parent's set bits.
+template <class T> BLOK_LD void brick_coords(const T& t, uint32_t index, uint32_t b[3]) {
+    b[0] = b[1] = b[2] = 0u;
+    uint32_t child = index;
+    for (uint32_t l = 2u; l <= t.levels; ++l) {
+        // the parent lies in [lo, hi): level l's block (its bounds are formed again per level, a few loads every lane shares, so that no
+        // array indexed by the level lives in scratch)
+        uint32_t lo = level_start(t, l), hi = level_start(t, l - 1u);
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (t.at(mid).base <= child) lo = mid; else hi = mid;
+        }
+        const Node p = t.at(lo);
+        uint64_t m = p.mask;
+        for (uint32_t r = child - p.base; r != 0u && m != 0ull; --r) m &= m - 1ull;
+        const uint32_t digit = m ? ctz64(m) : 0u;
+        const uint32_t shift = 2u * (l - 2u);
+        b[0] |= (digit & 3u) << shift; b[1] |= ((digit >> 2) & 3u) << shift; b[2] |= (digit >> 4) << shift;
+        child = lo;
+    }
+}
+// The mask of the brick at brick coordinates b (any integers: outside the tree's cube it is empty): downwards from the root.
+template <class T> BLOK_LD uint64_t brick_mask_at(const T& t, int64_t bx, int64_t by, int64_t bz) {
+    const int64_t edge = int64_t(1) << (2u * (t.levels - 1u));
+    if (bx < 0 || by < 0 || bz < 0 || bx >= edge || by >= edge || bz >= edge) return 0ull;
+    Node n = t.at(0u);
+    for (uint32_t l = t.levels; l >= 2u; --l) {
+        const uint32_t shift = 2u * (l - 2u);
+        const uint32_t digit = static_cast<uint32_t>((bx >> shift) & 3) | (static_cast<uint32_t>((by >> shift) & 3) << 2) | (static_cast<uint32_t>((bz >> shift) & 3) << 4);
+        if (!((n.mask >> digit) & 1ull)) return 0ull;
+        n = t.at(n.base + popc64(n.mask & ((1ull << digit) - 1ull)));
+    }
+    return n.mask;
+}
+// The cells of a brick (mask m; its six neighbours' masks in face order +x -x +y -y +z -z) whose face f looks at an empty cell of the model:
+// bit-parallel, cell bit = x | y << 2 | z << 4.
+BLOK_LD void brick_open_faces(uint64_t m, const uint64_t nb[6], uint64_t open[6]) {
+    constexpr uint64_t X0 = 0x1111111111111111ull, X3 = 0x8888888888888888ull, Y0 = 0x000F000F000F000Full, Y3 = 0xF000F000F000F000ull,
+                       Z0 = 0x000000000000FFFFull, Z3 = 0xFFFF000000000000ull;
+    open[0] = m & ~(((m >> 1) & ~X3) | ((nb[0] << 3) & X3));
+    open[1] = m & ~(((m << 1) & ~X0) | ((nb[1] >> 3) & X0));
+    open[2] = m & ~(((m >> 4) & ~Y3) | ((nb[2] << 12) & Y3));
+    open[3] = m & ~(((m << 4) & ~Y0) | ((nb[3] >> 12) & Y0));
+    open[4] = m & ~(((m >> 16) & ~Z3) | ((nb[4] << 48) & Z3));
+    open[5] = m & ~(((m << 16) & ~Z0) | ((nb[5] >> 48) & Z0));
+}
+// What brick node `index` contributes: the cells that glow and have an open face at all (*glowing), the open cells per face, its brick
+// coordinates; returns the number of its records.  Materials are read only for cells with an open face.
+template <class T> BLOK_LD uint32_t brick_lights(const T& t, uint32_t index, const uint32_t* glows, uint32_t n_materials, uint64_t open[6], uint64_t* glowing,
+                                                 uint32_t b[3], Node* brick) {
+    *brick = t.at(index);
+    brick_coords(t, index, b);
+    const int64_t x = b[0], y = b[1], z = b[2];
+    const uint64_t nb[6] = {brick_mask_at(t, x + 1, y, z), brick_mask_at(t, x - 1, y, z), brick_mask_at(t, x, y + 1, z),
+                            brick_mask_at(t, x, y - 1, z), brick_mask_at(t, x, y, z + 1), brick_mask_at(t, x, y, z - 1)};
+    brick_open_faces(brick->mask, nb, open);
+    uint64_t g = 0ull;
+    for (uint64_t any = open[0] | open[1] | open[2] | open[3] | open[4] | open[5]; any; any &= any - 1ull) {
+        const uint32_t c = ctz64(any);
+        const uint32_t id = t.material(brick->base + popc64(brick->mask & ((1ull << c) - 1ull)));
+        if (keeps(id, glows, n_materials)) g |= 1ull << c;
+    }
+    *glowing = g;
+    uint32_t n = 0u;
+    for (int f = 0; f < 6; ++f) n += popc64(open[f] & g);
+    return n;
+}
+// ... and its records, written from out[first] on (first = the records of the bricks before it): cells in ascending bit order, face 0..5.
+template <class T> BLOK_LD void brick_write_lights(const T& t, const Node& brick, const uint32_t b[3], const uint64_t open[6], uint64_t glowing, uint32_t first,
+                                                   blok_light* out) {
+    uint32_t at = first;
+    for (uint64_t cells = glowing; cells; cells &= cells - 1ull) {
+        const uint32_t c = ctz64(cells);
+        const uint32_t id = t.material(brick.base + popc64(brick.mask & ((1ull << c) - 1ull)));
+        const int32_t v[3] = {t.origin[0] + static_cast<int32_t>(4u * b[0] + (c & 3u)), t.origin[1] + static_cast<int32_t>(4u * b[1] + ((c >> 2) & 3u)),
+                              t.origin[2] + static_cast<int32_t>(4u * b[2] + (c >> 4))};
+        for (uint32_t f = 0; f < 6u; ++f) {
+            if (!((open[f] >> c) & 1ull)) continue;
+            blok_light l;
+            l.lo[0] = v[0] + ((f == 0u) ? 1 : 0); l.lo[1] = v[1] + ((f == 2u) ? 1 : 0); l.lo[2] = v[2] + ((f == 4u) ? 1 : 0);
+            l.du = 1u; l.dv = 1u; l.material = id; l.face = f; l.cum = at;
+            out[at++] = l;
+        }
+    }
+}
+
+// The world-lattice rectangle of unit face `m` (a record of a model's table: du = dv = 1) of instance I of a model of scale exponent e: the
+// header's "record back to world space" rule in 64-bit integers.  du = dv = 2^e; material unchanged; cum 0.
+BLOK_LD blok_light instance_light_record(const blok_instance& I, uint32_t e, const blok_light& m) {
+    const uint32_t fk = m.face >> 1, fn = m.face & 1u;
+    blok_light w;
+    uint32_t world_face = 0u;
+    // by world axis a, the local axis k with axis[k] == a by selects: the permutation is data, and an array indexed by it would live in scratch
+    for (uint32_t a = 0; a < 3u; ++a) {
+        const uint32_t k = I.axis[0] == a ? 0u : (I.axis[1] == a ? 1u : 2u), flip = (I.flip >> k) & 1u;
+        const int32_t mlo = k == 0u ? m.lo[0] : (k == 1u ? m.lo[1] : m.lo[2]);
+        const int64_t c = static_cast<int64_t>(mlo) - ((k == fk && fn == 0u) ? 1 : 0);        // the cell: a + face's plane lies one above it
+        const int64_t o = I.offset[a];
+        int64_t at = flip ? o - (c + 1) * (int64_t(1) << e) : o + c * (int64_t(1) << e);
+        if (k == fk) { world_face = 2u * a + (fn ^ flip); if ((fn ^ flip) == 0u) at += int64_t(1) << e; }
+        w.lo[a] = static_cast<int32_t>(at);
+    }
+    w.du = 1u << e; w.dv = 1u << e; w.material = m.material; w.face = world_face; w.cum = 0u;
+    return w;
+}
+
+// ---- the per-launch prefix over an instance table ----
+// faces_i = n_faces(model) << 2e for a usable instance of a model with a table, else 0; icum the exclusive scan, n + 1 words.  When
+// A_world + sum(faces) reaches 2^32 the launch goes without instance lights: every faces_i 0, disabled 1.
+// The scale exponent as every reader of a descriptor takes it for the prefix and the pick (the store keeps it <= 8; the one clamp for both,
+// so that `off >> 2e` and icum can never disagree).
+BLOK_LD uint32_t scale_exponent(uint32_t scale_log2) { return scale_log2 <= 8u ? scale_log2 : 8u; }
+BLOK_LD uint64_t instance_faces(bool usable, uint32_t table_n, uint32_t e) { return usable ? static_cast<uint64_t>(table_n) << (2u * e) : 0ull; }
+BLOK_LD bool instance_lights_fit(uint64_t a_world, uint64_t a_inst) { return a_world + a_inst < 0x100000000ull; }
+BLOK_LD float lights_area_world(uint64_t a_total, float vs) { return (static_cast<float>(a_total) * vs) * vs; }
+
 }  // namespace lights
 }  // namespace blok
 #endif

@@ -23,6 +23,7 @@ void free_world(blok_hip_ctx* ctx) {
     ctx->n_materials = 0; ctx->has_world = false; ctx->built_on_device = false; ctx->stats = blok_world_stats{};
     ctx->world_voxel_size = 1.0f;
     clear_lights(ctx);                  // (the owned set spoke about this world and its material table)
+    clear_model_lights(ctx);            // (... and so did every model's table: which ids glow)
 }
 
 // A tree the device builders made (gpu_build.h) becomes the installed one: the context's own from here, unless it lies in the resident
@@ -288,7 +289,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 27u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 28u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -810,6 +811,8 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     const bool posed = inst != nullptr && poses != nullptr && poses->n != 0u;
     // a light table: the lit kernel, the posed superset body, runs whatever tables the entry brought (a world-only entry brings none)
     const bool lit = ctx->lights.n != 0u;
+    // model light tables and a lattice instance table: the lit kernel with the pick extended over the instances, with or without a world table
+    const bool placed_lit = ctx->models.n_light_tables != 0u && ctx->models.d_glows && inst != nullptr && inst->n != 0u;
     const bool instanced = (inst != nullptr && (inst->n != 0u || posed)) || lit;
     if (instanced) p.resume_secondary = 0u;                 // (the instanced kernel is built without walk_resume)
     if (ctx->ray_batching >= 3u && max_bounces >= 2u && spp >= 4u && !ctx->path_resume && blok::kBlock == 64 && !instanced) {
@@ -838,14 +841,30 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
             pose_scene.nodes = static_cast<const blok::TlasNode*>(scratch.pose_tlas.get());
         }
     }
+    blok::InstanceLightScene inst_lights{};
+    if (placed_lit) {
+        auto& scratch = ctx->beam_buffers[stream];
+        BLOK_HIP_TRY(ctx, scratch.inst_lights.reserve(static_cast<size_t>(inst->n) + 1u + 8u, blok::FreeAfter::work_on(stream)));
+        inst_lights.header = reinterpret_cast<const blok_instance_lights_info*>(scratch.inst_lights.get());
+        inst_lights.icum = scratch.inst_lights.get() + 8;
+        inst_lights.tables = ctx->models.d_lights;
+        inst_lights.n_tables = std::min<uint32_t>(scene.n_models, ctx->models.n_lights_uploaded);
+        inst_lights.glows = ctx->models.d_glows;
+    }
     if (ctx->timing) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, stream));
+    if (placed_lit)
+        blok::launch_instance_lights_prefix(inst->table, inst->n, scene.models, inst_lights.tables, inst_lights.n_tables, ctx->lights.n_faces, ctx->world_voxel_size,
+                                            ctx->beam_buffers[stream].inst_lights.get() + 8, reinterpret_cast<blok_instance_lights_info*>(ctx->beam_buffers[stream].inst_lights.get()), stream);
     if (posed && pose_scene.nodes)
         blok::launch_pose_tlas_build(poses->table, poses->n, scene.models, scene.n_models, ctx->world_voxel_size, cam->pos,
                                      static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].pose_tlas.get()), stream);
     if (instanced && scene.nodes)
         blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas.get()), stream);
     if (n_beams) blok::launch_beam(blok::RayMode::Rect, p.trace, n_beams, stream);
-    if (lit) {
+    if (placed_lit) {
+        const blok::LightScene light_scene{ctx->lights.table, ctx->lights.owned, ctx->lights.n, static_cast<uint32_t>(ctx->lights.n_faces), ctx->lights.area_world};
+        blok::launch_paths_lit_placed(p, scene, pose_scene, light_scene, inst_lights, ctx->models.stack_levels, path_blocks, stream);
+    } else if (lit) {
         const blok::LightScene light_scene{ctx->lights.table, ctx->lights.owned, ctx->lights.n, static_cast<uint32_t>(ctx->lights.n_faces), ctx->lights.area_world};
         blok::launch_paths_lit(p, scene, pose_scene, light_scene, ctx->models.stack_levels, path_blocks, stream);
     } else if (posed) blok::launch_paths_posed(p, scene, pose_scene, ctx->models.stack_levels, path_blocks, stream);

@@ -29,6 +29,42 @@ int upload_models(blok_hip_ctx* ctx) {
     return BLOK_OK;
 }
 
+// The kernels' copy of the models' light tables, one entry per model id, with `with` standing in model `model`'s place (the table about to
+// be installed; null: none).  Waits for the device first when the array in use is replaced: frames in flight may read it.
+int upload_model_lights(blok_hip_ctx* ctx, uint32_t model, const blok_light* with, uint32_t with_n) {
+    auto& M = ctx->models;
+    std::vector<blok::lights::ModelLightTable> copy(M.desc.size(), blok::lights::ModelLightTable{nullptr, 0u, 0u});
+    for (size_t i = 0; i < M.lights.size() && i < copy.size(); ++i) copy[i] = blok::lights::ModelLightTable{M.lights[i].table.get(), M.lights[i].n, 0u};
+    if (model < copy.size()) copy[model] = blok::lights::ModelLightTable{with, with ? with_n : 0u, 0u};
+    if (copy.empty()) return BLOK_OK;
+    BLOK_HIP_TRY(ctx, hipDeviceSynchronize());
+    BLOK_HIP_TRY(ctx, M.d_lights.reserve(std::max<size_t>(16, copy.size()), blok::FreeAfter::nothing()));
+    M.n_lights_uploaded = 0u;
+    BLOK_HIP_TRY(ctx, hipMemcpy(M.d_lights, copy.data(), copy.size() * sizeof(copy[0]), hipMemcpyHostToDevice));
+    M.n_lights_uploaded = static_cast<uint32_t>(copy.size());
+    return BLOK_OK;
+}
+
+// Model `model` goes without a light table from here on (its id is known to be in range of desc).
+int drop_model_lights(blok_hip_ctx* ctx, uint32_t model) {
+    auto& M = ctx->models;
+    if (model >= M.lights.size() || !M.lights[model].n) return BLOK_OK;
+    const int rc = upload_model_lights(ctx, model, nullptr, 0u);        // (synchronises: nothing reads the table any more)
+    if (rc != BLOK_OK) return rc;
+    M.lights[model] = blok_hip_ctx::Models::LightTable{};
+    M.n_light_tables -= 1u;
+    if (!M.n_light_tables) M.d_glows.reset();           // (kept while any model has a table; the upload above has synchronised)
+    return BLOK_OK;
+}
+
+void model_lights_info_of(const blok_hip_ctx* ctx, uint32_t model, blok_lights_info* out) {
+    if (!out) return;
+    *out = blok_lights_info{};
+    const auto& T = ctx->models.lights;
+    if (model >= T.size()) return;
+    out->n = T[model].n; out->n_faces = T[model].n; out->bytes = static_cast<uint64_t>(T[model].n) * sizeof(blok_light);
+}
+
 int check_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) {
     if (n && !inst) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
     for (uint32_t i = 0; i < n; ++i) {
@@ -216,6 +252,14 @@ int trace_rays_placed(blok_hip_ctx* ctx, const char* entry, const blok_ray* rays
 }  // namespace
 
 int check_instance_table(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n) { return check_table(ctx, inst, n); }
+
+void clear_model_lights(blok_hip_ctx* ctx) {
+    auto& M = ctx->models;
+    if (!M.n_light_tables) { M.d_glows.reset(); return; }      // (a set left by a build that failed behind it: no frame reads it without a table)
+    (void)hipDeviceSynchronize();                       // whatever still reads the tables
+    M.lights.clear(); M.n_light_tables = 0u; M.d_glows.reset();
+    M.n_lights_uploaded = 0u;                           // the kernels' copy names no table any more: every id counts as none
+}
 int check_placed_device_tables(blok_hip_ctx* ctx, const blok_instance* inst, uint32_t n_inst, const blok_pose* poses, uint32_t n_poses) {
     return check_device_tables(ctx, inst, n_inst, poses, n_poses);
 }
@@ -348,9 +392,103 @@ int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model) {
     if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "unknown model " + std::to_string(model));
     BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     BLOK_HIP_TRY(ctx, hipDeviceSynchronize());           // frames in flight may still walk it
+    const int rc_lights = drop_model_lights(ctx, model);
+    if (rc_lights != BLOK_OK) return rc_lights;
     ctx->models.own[model] = blok_hip_ctx::Models::Arrays{};
     ctx->models.desc[model] = blok::ModelDesc{};         // the id stays taken and unknown
     return upload_models(ctx);
+}
+
+// ---- emissive models as lights (blok_hip.h; lights_kernels.hip) -------------------------------------------------------------
+
+int blok_hip_model_lights(blok_hip_ctx* ctx, uint32_t model, uint32_t flags, blok_lights_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights: unknown model " + std::to_string(model));
+    if (flags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights: unknown flag bits");
+    if (!ctx->n_materials || ctx->material_glows.size() != blok::lights::kSetWords) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights: no material table");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& M = ctx->models;
+    blok::DeviceArray<uint32_t> glows;
+    BLOK_HIP_TRY(ctx, glows.reserve(blok::lights::kSetWords, blok::FreeAfter::nothing()));
+    BLOK_HIP_TRY(ctx, hipMemcpy(glows, ctx->material_glows.data(), blok::lights::kSetWords * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const blok::ModelDesc& d = M.desc[model];
+    const auto& own = M.own[model];
+    blok::GpuLights made;
+    std::string why;
+    const uint32_t n_mat = static_cast<uint32_t>(std::min<size_t>(ctx->n_materials, blok::lights::kSetBits));
+    const blok::GpuBuildStatus st = blok::gpu_model_lights(d.nodes, own.n_nodes, d.materials, own.n_materials, d.levels, d.origin, glows, n_mat, &made, &why);
+    if (st != blok::GpuBuildStatus::Ok)
+        return set_error(ctx, st == blok::GpuBuildStatus::OutOfMemory ? BLOK_ERR_OOM : st == blok::GpuBuildStatus::Unsupported ? BLOK_ERR_UNSUPPORTED :
+                              st == blok::GpuBuildStatus::HipError ? BLOK_ERR_HIP : BLOK_ERR_INTERNAL, why);
+    blok::DeviceArray<blok_light> table;
+    table.adopt(made.d_lights, made.n);
+    if (!made.n) {                                      // no faces: no table
+        const int rc = drop_model_lights(ctx, model);
+        if (rc != BLOK_OK) return rc;
+        model_lights_info_of(ctx, model, out_info);
+        return BLOK_OK;
+    }
+    // the emissive set for the path loop's rule (e), kept while any model has a table: written once, when it is allocated (no frame reads it
+    // before a table exists, and every table goes with the material table it was built for, so the words never change while it lives)
+    if (!M.d_glows) {
+        BLOK_HIP_TRY(ctx, M.d_glows.reserve(blok::lights::kSetWords, blok::FreeAfter::nothing()));
+        BLOK_HIP_TRY_FILL(ctx, M.d_glows, hipMemcpy(M.d_glows, glows, blok::lights::kSetWords * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    }
+    const int rc = upload_model_lights(ctx, model, table.get(), made.n);
+    if (rc != BLOK_OK) return rc;                       // (`table` frees the new one; the old one stays)
+    if (M.lights.size() < M.desc.size()) M.lights.resize(M.desc.size());
+    if (!M.lights[model].n) M.n_light_tables += 1u;
+    M.lights[model].table = std::move(table); M.lights[model].n = made.n;
+    model_lights_info_of(ctx, model, out_info);
+    return BLOK_OK;
+}
+
+int blok_hip_model_lights_info(blok_hip_ctx* ctx, uint32_t model, blok_lights_info* out_info) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights_info: unknown model " + std::to_string(model));
+    if (!out_info) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights_info: null output");
+    model_lights_info_of(ctx, model, out_info);
+    return BLOK_OK;
+}
+
+int blok_hip_model_lights_download(blok_hip_ctx* ctx, uint32_t model, blok_light* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights_download: unknown model " + std::to_string(model));
+    const auto& T = ctx->models.lights;
+    const uint64_t n = model < T.size() ? T[model].n : 0u;
+    if (first > n || count > n - first) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights_download: range past the end of the table");
+    if (count == 0) return BLOK_OK;
+    if (!out_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights_download: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BLOK_HIP_TRY(ctx, hipMemcpy(out_host, T[model].table.get() + first, count * sizeof(blok_light), hipMemcpyDeviceToHost));
+    return BLOK_OK;
+}
+
+int blok_hip_model_lights_clear(blok_hip_ctx* ctx, uint32_t model) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!known_model(ctx, model)) return set_error(ctx, BLOK_ERR_INVALID_ARG, "model_lights_clear: unknown model " + std::to_string(model));
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return drop_model_lights(ctx, model);
+}
+
+int blok_hip_instance_lights_info(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n, blok_instance_lights_info* out,
+                                  uint32_t* out_icum_host) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (n && !instances_host) return set_error(ctx, BLOK_ERR_INVALID_ARG, "null instance table with non-zero count");
+    if (!out) return set_error(ctx, BLOK_ERR_INVALID_ARG, "instance_lights_info: null output");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    StagedBlock d;
+    const auto inst = d.input(instances_host, n);
+    const auto icum = d.output(out_icum_host, static_cast<size_t>(n) + 1u);
+    const auto header = d.output(out, 1);
+    int rc = d.stage(ctx, "instance_lights_info");
+    if (rc != BLOK_OK) return rc;
+    const auto& M = ctx->models;
+    blok::launch_instance_lights_prefix(d.at(inst), n, M.d_desc, M.d_lights, std::min<uint32_t>(static_cast<uint32_t>(M.desc.size()), M.n_lights_uploaded),
+                                        ctx->lights.n_faces, ctx->world_voxel_size, d.at(icum), d.at(header), nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = set_error(ctx, BLOK_ERR_HIP, std::string("instance_lights_info: ") + hipGetErrorString(e));
+    return d.collect(ctx, "instance_lights_info", rc);
 }
 
 int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_log2) {

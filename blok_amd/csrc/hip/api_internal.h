@@ -31,6 +31,7 @@
 #include "path_args.h"
 #include "tree.h"
 #include "instance_core.h"
+#include "../common/lights_core.h"
 
 // Every device array, pinned array and event of the context is a member that owns it (device_buffer.h): the context's destructor is its
 // teardown, a reset is the assignment of a fresh value, and every grow-on-demand site is one reserve() that names what must finish first.
@@ -159,6 +160,7 @@ struct blok_hip_ctx {
         blok::DeviceBytes pose_tlas;                                      // posed path launches: the pose BVH (pose_tlas_core.h), grown on demand
         blok::DeviceArray<blok_pose_motion> pose_motion;                 // posed motion passes: one record per pose (pose_motion.h), grown on demand
         blok::DeviceBytes tlas;                                           // instanced path launches: the instance BVH (tlas_core.h: TlasNode), grown on demand
+        blok::DeviceArray<uint32_t> inst_lights;                         // ... with model light tables: the launch's prefix, 8 words of header (blok_instance_lights_info), then icum (n + 1 words), grown on demand
     };
     std::unordered_map<hipStream_t, StreamScratch> beam_buffers;
     // The beam bounds of views at rest (beam_cache.h: key, admission, slots; api_launch.hip: the hazards).  A slot's buffer is written by the
@@ -292,6 +294,13 @@ struct blok_hip_ctx {
         blok::DeviceArray<blok::ModelDesc> d_desc;      // the kernels' copy: nodes = null also where vs * 2^e is above the limit ...
         float uploaded_voxel_size = 1.0f;               // ... for this voxel size of the world (models_follow_voxel_size)
         uint32_t stack_levels = 1;
+        // emissive models as lights (blok_hip.h): a model's table under its id (shorter than desc while the later models have none), the
+        // number of tables, and the kernels' copy, one entry per model id (written by upload_model_lights behind every change)
+        struct LightTable { blok::DeviceArray<blok_light> table; uint32_t n = 0; };
+        std::vector<LightTable> lights;
+        uint32_t n_light_tables = 0;
+        blok::DeviceArray<uint32_t> d_glows;            // the emissive set of the installed material table (lights_core.h: kSetWords words), kept while any model has a table
+        blok::DeviceArray<blok::lights::ModelLightTable> d_lights; uint32_t n_lights_uploaded = 0;      // (models made since have no table: ids at or beyond it count as none)
     } models;
     // timing
     blok::Event ev_begin, ev_end;
@@ -370,6 +379,7 @@ inline bool known_model(const blok_hip_ctx* ctx, uint32_t model) { return model 
 
 void free_world(blok_hip_ctx* ctx);
 void clear_lights(blok_hip_ctx* ctx);                   // api_volume.hip: no light table from here on
+void clear_model_lights(blok_hip_ctx* ctx);             // api_instances.hip: no model has a light table from here on
 void adopt_tree(blok_hip_ctx* ctx, const blok::GpuTree& gpu);
 int install_materials(blok_hip_ctx* ctx, const blok_material* materials, size_t n_materials);
 int install_tree(blok_hip_ctx* ctx, const blok::HostTree& tree, const blok_material* materials, size_t n_materials);
@@ -384,7 +394,8 @@ int check_trace(blok_hip_ctx* ctx, const blok_camera* cam);
 struct PathInstances { const blok_instance* table; uint32_t n; uint32_t* ids; };
 // The poses of a posed path launch (null, or n == 0: none): a device table of n records, traced behind the instances.
 struct PathPoses { const blok_pose* table; uint32_t n; };
-// With a light table installed (ctx->lights.n >= 1) every launch runs the lit kernel, whatever tables the entry brought.
+// With a light table installed (ctx->lights.n >= 1) every launch runs the lit kernel, whatever tables the entry brought.  With a model light
+// table (ctx->models.n_light_tables >= 1) every launch that brings instances runs the placed lit kernel behind the launch's prefix kernel.
 int launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
                       uint32_t max_bounces, uint32_t frame_index, const blok::PathArgs& planes, void* hip_stream, const PathInstances* inst = nullptr,
                       const PathPoses* poses = nullptr);

@@ -149,6 +149,16 @@ struct GpuLights {
 };
 GpuBuildStatus gpu_lights_from_quads(const blok_quad* d_quads, uint64_t n_quads, const uint32_t* d_glows, uint32_t n_materials, uint32_t* d_owned,
                                      GpuLights* out, std::string* why);
+// = blok_hip_model_lights (lights_kernels.hip): the table of a model's exposed emissive unit faces from its own tree in device memory (the
+// arrays' lengths as the store keeps them), in the order of its material array; out->n_faces == out->n.  Null stream; waits for the count.
+GpuBuildStatus gpu_model_lights(const uint4* d_nodes, uint32_t n_nodes, const uint32_t* d_materials, uint32_t n_voxels, uint32_t levels, const int32_t origin[3],
+                                const uint32_t* d_glows, uint32_t n_materials, GpuLights* out, std::string* why);
+struct ModelDesc;
+namespace lights { struct ModelLightTable; }
+// The per-launch prefix of an instance table (lights_core.h): icum, n + 1 words, and the 32-byte header behind them at `header`
+// (= blok_instance_lights_info), on `stream`; one workgroup, no atomics.  tables: one entry per model id (n_models of both arrays).
+void launch_instance_lights_prefix(const blok_instance* instances, uint32_t n, const ModelDesc* models, const lights::ModelLightTable* tables, uint32_t n_models,
+                                   uint64_t a_world, float voxel_size, uint32_t* icum, blok_instance_lights_info* header, hipStream_t stream);
 GpuBuildStatus gpu_volume_extract_quads(const GpuVolume* v, const uint32_t lo[3], const uint32_t hi[3], uint32_t flags, GpuQuads* out,
                                         uint64_t* out_n_faces, std::string* why);
 // = blok_hip_volume_stamp_models (include/blok_hip.h; stamp_kernels.hip).  The placements have passed the entry's checks; models[i] is

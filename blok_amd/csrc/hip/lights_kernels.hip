@@ -1,5 +1,7 @@
 // The light table from the quads snapshot (gpu_build.h: gpu_lights_from_quads; include/blok_hip.h: blok_hip_lights_from_quads).  The
 // predicates are ../common/lights_core.h; DESIGN.md §32 has the contract.
+// Behind it, the table of a MODEL's exposed emissive unit faces from its own tree (gpu_model_lights; blok_hip_model_lights)
+// and the per-launch prefix of an instance table over those tables (launch_instance_lights_prefix).
 //
 // A lane per quad, two passes and one scan between them; no sort, no atomics, integer arithmetic only:
 //   1. lights_count_kernel: a quad is kept iff its key's material index is in the emissive set.  One ballot gives the wave's number of
@@ -17,6 +19,7 @@
 
 #include "gpu_build.h"
 #include "device_mem.h"
+#include "instance_core.h"
 #include "../common/lights_core.h"
 
 namespace blok {
@@ -128,6 +131,166 @@ GpuBuildStatus gpu_lights_from_quads(const blok_quad* d_quads, uint64_t n_quads,
     }
     out->n = static_cast<uint32_t>(total.n); out->n_faces = total.faces;
     return GpuBuildStatus::Ok;
+}
+
+// ---- a model's table (lights_core.h: brick_lights, brick_write_lights) ----------------------------------------------------------------------
+// A lane per brick, two passes and one scan between them, no atomics: the count pass leaves each brick's number of records, the scan turns
+// them into offsets (its last entry the total, the one thing the host reads before it allocates), the write pass forms the bricks' masks
+// again and writes each brick's records from its offset on, ranks by popcounts.  A brick's exposure is bit-parallel from its mask and its
+// six neighbours', found by a descent of the model's tree.
+namespace {
+
+struct LoadNode {
+    const uint4* nodes;
+    __device__ __forceinline__ L::Node operator()(uint32_t i) const { const uint4 w = nodes[i]; return L::Node{w.x | (static_cast<uint64_t>(w.y) << 32), w.z}; }
+};
+using DeviceModelTree = L::ModelTree<LoadNode>;
+
+struct ModelLightArgs {
+    DeviceModelTree tree;
+    uint32_t n_lanes;                   // = the tree's nodes: lane i takes brick first_brick + i, where there is one (the host does not know
+                                        // where the bricks begin, and does not ask: every lane finds it by the same few loads)
+    const uint32_t* glows; uint32_t n_materials;
+    uint32_t* offsets;                  // n_lanes + 1: counts (0 for a lane without a brick), then (scanned in place) offsets; the last is the total
+    uint32_t total;                     // write pass: the table's length (no record is written at or beyond it)
+    blok_light* out;
+};
+
+__global__ __launch_bounds__(256) void model_lights_count_kernel(const ModelLightArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n_lanes) return;
+    const uint32_t node = L::first_brick(a.tree) + i;
+    uint64_t open[6], glowing;
+    uint32_t b[3];
+    L::Node brick;
+    a.offsets[i] = (node >= i && node < a.tree.n_nodes) ? L::brick_lights(a.tree, node, a.glows, a.n_materials, open, &glowing, b, &brick) : 0u;
+}
+
+__global__ __launch_bounds__(256) void model_lights_write_kernel(const ModelLightArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n_lanes) return;
+    const uint32_t at = a.offsets[i], end = a.offsets[i + 1u];
+    if (end <= at || end > a.total) return;             // nothing of this brick (or offsets that are not the count pass's: nothing is written)
+    const uint32_t node = L::first_brick(a.tree) + i;
+    if (node < i || node >= a.tree.n_nodes) return;
+    uint64_t open[6], glowing;
+    uint32_t b[3];
+    L::Node brick;
+    if (L::brick_lights(a.tree, node, a.glows, a.n_materials, open, &glowing, b, &brick) != end - at) return;
+    L::brick_write_lights(a.tree, brick, b, open, glowing, at, a.out);
+}
+
+// ---- the per-launch prefix ---------------------------------------------------------------------------------------------------------------
+struct PrefixArgs {
+    const blok_instance* instances; uint32_t n;
+    const ModelDesc* models; const L::ModelLightTable* tables; uint32_t n_models;
+    unsigned long long a_world; float vs;
+    uint32_t* icum; blok_instance_lights_info* header;
+};
+
+__device__ __forceinline__ unsigned long long faces_of(const PrefixArgs& a, uint32_t i) {
+    if (i >= a.n) return 0ull;
+    const blok_instance I = a.instances[i];
+    if (I.model >= a.n_models) return 0ull;
+    const ModelDesc M = a.models[I.model];
+    const L::ModelLightTable T = a.tables[I.model];
+    const uint32_t e = L::scale_exponent(M.scale_log2);
+    return L::instance_faces(instance_usable(I, M) && T.table != nullptr, T.n, e);
+}
+
+// Sum of v over the workgroup's 256 lanes in every lane (`part`: four words of LDS); v < 2^49, so 256 of them fit.
+__device__ __forceinline__ unsigned long long block_sum(unsigned long long v, unsigned long long* part) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return part[0] + part[1] + part[2] + part[3];
+}
+
+// One workgroup loops over the table twice: the total first (it decides whether the launch carries instance lights at all), then the scan.
+__global__ __launch_bounds__(256) void instance_lights_prefix_kernel(const PrefixArgs a) {
+    __shared__ unsigned long long part[4];
+    constexpr unsigned long long kCap = 1ull << 40;     // a running sum is capped here: far above 2^32, far below an overflow
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long total = 0ull;
+    for (uint32_t base = 0u; base < a.n; base += 256u) {
+        total += block_sum(faces_of(a, base + threadIdx.x), part);
+        if (total > kCap) total = kCap;
+        if (a.n - base <= 256u) break;                  // (base + 256 may wrap for n near 2^32)
+    }
+    const bool fit = L::instance_lights_fit(a.a_world, total);
+    unsigned long long carry = 0ull, lit = 0ull;
+    for (uint32_t base = 0u; base < a.n; base += 256u) {
+        const uint32_t i = base + threadIdx.x;
+        const unsigned long long mine = fit ? faces_of(a, i) : 0ull;
+        unsigned long long upto = mine;                 // inclusive scan over the wave
+        for (uint32_t off = 1u; off < 64u; off <<= 1) {
+            const unsigned long long t = __shfl_up(upto, off);
+            if (lane >= off) upto += t;
+        }
+        __syncthreads();
+        if (lane == 63u) part[wave] = upto;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (uint32_t w = 0u; w < wave; ++w) before += part[w];
+        if (i < a.n) a.icum[i] = static_cast<uint32_t>(before + (upto - mine));
+        carry += part[0] + part[1] + part[2] + part[3];
+        lit += static_cast<unsigned long long>(__popcll(__ballot(mine != 0ull)));      // per wave; summed below
+        if (a.n - base <= 256u) break;
+    }
+    const unsigned long long n_lit = block_sum(lane == 0u ? lit : 0ull, part);
+    if (threadIdx.x == 0u) {
+        a.icum[a.n] = static_cast<uint32_t>(carry);
+        blok_instance_lights_info h{};
+        h.a_inst = carry; h.a_total = a.a_world + carry; h.area_world = L::lights_area_world(a.a_world + carry, a.vs);
+        h.n_lit = static_cast<uint32_t>(n_lit); h.disabled = fit ? 0u : 1u;
+        *a.header = h;
+    }
+}
+
+}  // namespace
+
+GpuBuildStatus gpu_model_lights(const uint4* d_nodes, uint32_t n_nodes, const uint32_t* d_materials, uint32_t n_voxels, uint32_t levels, const int32_t origin[3],
+                                const uint32_t* d_glows, uint32_t n_materials, GpuLights* out, std::string* why) {
+    *out = GpuLights{};
+    if (!d_nodes || !n_nodes || levels < 1u || levels > kMaxLevels) { *why = "model_lights: a model without a tree"; return GpuBuildStatus::Internal; }
+    ModelLightArgs a{};
+    a.tree = DeviceModelTree{LoadNode{d_nodes}, n_nodes, d_materials, n_voxels, levels, {origin[0], origin[1], origin[2]}};
+    a.glows = d_glows; a.n_materials = n_materials;
+    DeviceMem mem;
+    a.n_lanes = n_nodes;
+    const uint32_t blocks = blocks_for(a.n_lanes);
+    BLOK_GPU_TRY(mem.alloc(&a.offsets, static_cast<uint64_t>(a.n_lanes) + 1u));
+    BLOK_GPU_TRY(hipMemsetAsync(a.offsets + a.n_lanes, 0, sizeof(uint32_t), nullptr));
+    hipLaunchKernelGGL(model_lights_count_kernel, dim3(blocks), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    // (a brick holds at most 384 records and a tree fewer than 2^24 bricks with any: the 32-bit sum cannot wrap for a tree the builders make;
+    // the write pass checks every offset against the total all the same)
+    size_t temp_bytes = 0;
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, a.offsets, a.offsets, static_cast<int>(a.n_lanes + 1u)));
+    uint8_t* d_temp;
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, a.offsets, a.offsets, static_cast<int>(a.n_lanes + 1u)));
+    BLOK_GPU_TRY(hipMemcpy(&a.total, a.offsets + a.n_lanes, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (a.total >= 0x80000000u) { *why = "model_lights: 2^31 or more faces"; return GpuBuildStatus::Unsupported; }
+    if (a.total) {
+        BLOK_GPU_TRY(mem.alloc(&a.out, a.total));
+        hipLaunchKernelGGL(model_lights_write_kernel, dim3(blocks), dim3(256), 0, nullptr, a);
+        BLOK_GPU_TRY(hipGetLastError());
+        BLOK_GPU_TRY(hipDeviceSynchronize());
+        mem.release(a.out);
+        out->d_lights = a.out;
+    }
+    out->n = a.total; out->n_faces = a.total;
+    return GpuBuildStatus::Ok;
+}
+
+void launch_instance_lights_prefix(const blok_instance* instances, uint32_t n, const ModelDesc* models, const L::ModelLightTable* tables, uint32_t n_models,
+                                   uint64_t a_world, float voxel_size, uint32_t* icum, blok_instance_lights_info* header, hipStream_t stream) {
+    PrefixArgs a{};
+    a.instances = instances; a.n = n; a.models = models; a.tables = tables; a.n_models = (models && tables) ? n_models : 0u;
+    a.a_world = a_world; a.vs = voxel_size; a.icum = icum; a.header = header;
+    hipLaunchKernelGGL(instance_lights_prefix_kernel, dim3(1), dim3(256), 0, stream, a);
 }
 
 }  // namespace blok

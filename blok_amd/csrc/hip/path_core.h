@@ -185,6 +185,63 @@ BLOK_DEV bool light_sample(const LightScene& S, const blok_material* mat_table, 
     return true;
 }
 
+// The instance part of a lit path launch over placed lattice instances (include/blok_hip.h: "emissive models as lights"):
+// the launch's prefix (icum, n + 1 words, and the header the prefix kernel wrote behind it on the stream), the models' tables by model id,
+// and the emissive set of the installed material table (lights::kSetWords words).
+struct InstanceLightScene {
+    const uint32_t* icum;
+    const blok_instance_lights_info* header;
+    const lights::ModelLightTable* tables;
+    uint32_t n_tables;
+    const uint32_t* glows;
+};
+// light_sample over the extended pick: pick = (r * A_total) >> 32; below A_world the world's light as light_sample takes it, else the face
+// of a lit instance: the last i with icum[i] <= p, the model's record table[off >> 2e], its world rectangle, the cell off & (4^e - 1).
+// a_total and area_world are the header's.  From the sampled rectangle on, light_sample's operations in light_sample's order.
+BLOK_DEV bool placed_light_sample(const LightScene& S, const InstanceLightScene& IL, const TlasScene& scene, uint32_t a_total, float area_world,
+                                  const blok_material* mat_table, uint32_t n_materials, float vs, V3 hit_pos, V3 n, uint32_t r, float u1, float u2,
+                                  V3& q, V3& le, float& g) {
+    const uint32_t pick = lights::pick_of(r, a_total);
+    blok_light L;
+    uint32_t off;
+    if (pick < S.n_faces) {
+        L = S.lights[lights::find_light(S.lights, S.n, pick)];
+        off = pick - L.cum;
+    } else {
+        const uint32_t p = pick - S.n_faces;
+        uint32_t lo = 0u, hi = scene.n_instances;                                             // the last i with icum[i] <= p (icum[0] = 0)
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (IL.icum[mid] <= p) lo = mid; else hi = mid;
+        }
+        if (lo >= scene.n_instances) return false;
+        const blok_instance I = scene.instances[lo];
+        if (I.model >= IL.n_tables || I.model >= scene.n_models) return false;              // (the prefix gave such a record no faces)
+        const lights::ModelLightTable T = IL.tables[I.model];
+        const uint32_t e = lights::scale_exponent(scene.models[I.model].scale_log2);
+        off = p - IL.icum[lo];
+        if (T.table == nullptr || (off >> (2u * e)) >= T.n) return false;
+        L = lights::instance_light_record(I, e, T.table[off >> (2u * e)]);
+        off &= (1u << (2u * e)) - 1u;
+    }
+    float qa[3], nla[3];
+    lights::sample_point(L, off, u1, u2, vs, qa, nla);
+    q = v3(qa[0], qa[1], qa[2]);
+    const V3 nl = v3(nla[0], nla[1], nla[2]);
+    const V3 x = vadd(hit_pos, vscale(n, 0.001f));
+    const V3 w = vsub(q, x);
+    const float d2 = vdot(w, w);
+    const float d = rn_sqrt(d2);
+    const V3 dir = vdivs(w, d);
+    const float cos_s = fmaxf(vdot(n, dir), 0.0f);
+    const float cos_l = fmaxf(-vdot(nl, dir), 0.0f);
+    if (!(cos_s > 0.0f && cos_l > 0.0f && d > 2.0f * lights::kLightEps)) return false;
+    g = (((cos_s * cos_l) / d2) * area_world) * kInvPi;
+    const blok_material mat = mat_table[lights::material_index(L.material, n_materials)];
+    le = v3(mat.emission[0], mat.emission[1], mat.emission[2]);
+    return true;
+}
+
 BLOK_DEV void store4(float* plane, size_t i, float a, float b, float c, float d) {
     if (!plane) return;
     float* p = plane + 4 * i;
@@ -238,11 +295,15 @@ BLOK_DEV void store_narrow(const PathArgs& P, size_t index, uint32_t px, uint32_
 // pose's row, and the sampling frame is formed for any unit normal.
 // kLit (over the posed superset body only): the light table of `lit` is sampled at every eligible hit, its shadow ray a state of its own
 // (light_phase) behind the sun's; an owned material's emission is not counted again where a diffuse bounce ray finds it.
-template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false, bool kLit = false>
+// kPlacedLit (over the lit body only): the pick runs over the world table AND the tables of the launch's lit lattice instances (`ilit`, whose
+// header holds A_total and area_world); a lit instance's emission is not counted again where a diffuse bounce ray finds it.
+// With A_total = 0 no light is sampled and no number is drawn.
+template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false, bool kLit = false, bool kPlacedLit = false>
 BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t index, uint4* stk, float t0 = 0.0f, uint2* keep_lohi = nullptr, uint32_t* keep_base = nullptr,
                           [[maybe_unused]] TailRecord* pool = nullptr, [[maybe_unused]] TailAnswer* tail_results = nullptr,
                           [[maybe_unused]] const TlasScene* scene = nullptr, [[maybe_unused]] const PoseScene* poses = nullptr,
-                          [[maybe_unused]] const LightScene* lit = nullptr) {
+                          [[maybe_unused]] const LightScene* lit = nullptr, [[maybe_unused]] const InstanceLightScene* ilit = nullptr) {
+    static_assert(!kPlacedLit || kLit, "instance lights extend the lit loop");
     static_assert(!kInstanced || (!kResume && !kSkyOnly), "instanced launches run without walk_resume and the sky-only build");
     static_assert(!kPosed || kInstanced, "a posed launch is an instanced launch with a pose table");
     static_assert(!kLit || kPosed, "the lit loop is built over the posed superset body");
@@ -498,6 +559,7 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
         }
         [[maybe_unused]] uint32_t pose_won = kInstanceNone;       // kPosed: the pose whose voxel `hit` reports (hit.face is then its LOCAL face)
         [[maybe_unused]] bool world_won = true;                   // kLit: the reported voxel is the world's (neither an instance nor a pose won)
+        [[maybe_unused]] uint32_t lattice_won = kInstanceNone;    // kPlacedLit: the lattice instance whose voxel `hit` reports (none where a pose won)
         if constexpr (kInstanced) {
             // The instances, on the ray's own interval: the beam pre-pass' start parameter and the sun map's cap describe the world alone.
             // Primary and bounce rays: the closest hit of world and instances by the composition rule (the world's t bounds the query;
@@ -519,11 +581,13 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                     hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
                 }
                 if constexpr (kLit) world_won = won == kInstanceNone;
+                if constexpr (kPlacedLit) lattice_won = won;
                 if constexpr (kPosed) {                                                       // the poses, with tmax = the composed t so far
                     pose_won = poses_closest(*poses, scene->models, scene->n_models, A.voxel_size, A.inv_voxel_size, q, hit.found ? hit.t : 10000.0f, stk, rec);
                     if (pose_won != kInstanceNone) {
                         hit.found = true; hit.t = __uint_as_float(rec.x); hit.material = rec.y; hit.face = (rec.w >> 16) & 0xFFu;
                         if constexpr (kLit) world_won = false;
+                        if constexpr (kPlacedLit) lattice_won = kInstanceNone;
                     }
                     if (bounce == 0u && s == 0u && scene->ids) scene->ids[index] = pose_won != kInstanceNone ? (BLOK_POSE_ID | pose_won) : won;
                 } else
@@ -640,6 +704,13 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
             if (is_emissive(emission)) {                                                      // :265-277
                 // kLit: where a diffuse bounce ray finds an owned material in the world, the light sample of the hit it left has counted it
                 bool counted = false;
+                if constexpr (kPlacedLit) {
+                    // ... (the world's owned set only where there is a world table) and where it finds a LIT lattice instance: that instance's
+                    // table holds every face of it a ray can reach, so the sample of the hit it left has counted whatever glows on it
+                    if (prev_diffuse && world_won) counted = lit->n != 0u && lights::in_set(lit->owned, lights::material_index(hit.material, A.n_materials));
+                    else if (prev_diffuse && lattice_won != kInstanceNone)
+                        counted = ilit->icum[lattice_won + 1u] != ilit->icum[lattice_won] && lights::in_set(ilit->glows, lights::material_index(hit.material, A.n_materials));
+                } else
                 if constexpr (kLit) counted = prev_diffuse && world_won && lights::in_set(lit->owned, lights::material_index(hit.material, A.n_materials));
                 if (!counted) radiance = vadd(radiance, vmul(throughput, emission));
                 if (luminance(emission) > 5.0f || bounce > 0u) end_sample = true;
@@ -648,12 +719,19 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
             if constexpr (kLit) {
                 // the light sample of an eligible hit: three draws, always all three, then the term and its shadow ray if there is one
                 const V3 diffuse = vscale(albedo, 1.0f - metallic);
-                if (!end_sample && max3f(diffuse) > 0.0f) {
+                bool any_light = true;
+                if constexpr (kPlacedLit) any_light = ilit->header->a_total != 0ull;          // (uniform: read through the scalar cache)
+                if (any_light && !end_sample && max3f(diffuse) > 0.0f) {
                     const uint32_t lr = pcg(rng);
                     const float u1 = random_float(rng);
                     const float u2 = random_float(rng);
                     V3 le; float g;
-                    if (light_sample(*lit, A.mat_table, A.n_materials, A.voxel_size, hit_pos, n, lr, u1, u2, light_q, le, g)) {
+                    bool sampled;
+                    if constexpr (kPlacedLit)
+                        sampled = placed_light_sample(*lit, *ilit, *scene, static_cast<uint32_t>(ilit->header->a_total), ilit->header->area_world, A.mat_table,
+                                                      A.n_materials, A.voxel_size, hit_pos, n, lr, u1, u2, light_q, le, g);
+                    else sampled = light_sample(*lit, A.mat_table, A.n_materials, A.voxel_size, hit_pos, n, lr, u1, u2, light_q, le, g);
+                    if (sampled) {
                         pending = vscale(vmul(vmul(throughput, diffuse), le), g);
                         light_phase = true;
                     }

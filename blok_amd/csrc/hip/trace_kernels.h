@@ -268,6 +268,11 @@ struct LightScene;
 // The posed path frame (shade_pixel<..., kPosed>): the instanced frame with a pose table behind the instances (poses.n_poses > 0).
 void launch_paths_posed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
 // ... with the light table `lit` (n >= 1) sampled at every eligible hit (path_core.h: kLit); either table of placed models may be empty.
+struct InstanceLightScene;
+// ... and with the pick extended over the light tables of the launch's lattice instances (path_core.h: kPlacedLit); scene.n_instances >= 1,
+// lit.n may be 0.  The prefix `ilit` points to has been launched on `stream` before.
+void launch_paths_lit_placed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, const InstanceLightScene& ilit,
+                             uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
 void launch_paths_lit(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, uint32_t stack_slots, uint32_t n_blocks,
                       hipStream_t stream);
 void launch_trace(RayMode mode, const TraceArgs& args, uint32_t n_blocks, hipStream_t stream);

@@ -1312,6 +1312,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PAT
     shade_pixel<false, false, true, true, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S, &Q, &L);
 }
 
+// The lit path frame over placed lattice instances whose models carry light tables (path_core.h: shade_pixel<…, kLit, kPlacedLit>; DESIGN.md
+// §33): path_kernel_lit's body with the pick extended over the launch's prefix (lights_kernels.hip: instance_lights_prefix_kernel, launched on
+// the stream before this kernel).  The same pixel mapping, LDS stack and grid.  L.n may be 0 (no world table).  A kernel of its own, so that
+// path_kernel_lit stays as it was (profiles/model_lights_isa.txt).
+#ifndef BLOK_PATH_LIT_PLACED_WAVES
+#define BLOK_PATH_LIT_PLACED_WAVES 4
+#endif
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PATH_LIT_PLACED_WAVES, BLOK_PATH_LIT_PLACED_WAVES))) void path_kernel_lit_placed(
+    const PathArgs P, const TlasScene S, const PoseScene Q, const LightScene L, const InstanceLightScene IL) {
+    extern __shared__ uint4 lds_stack[];
+    const TraceArgs& A = P.trace;
+    const uint32_t tid = threadIdx.x;
+    uint32_t rx, ry;
+    float t0;
+    if (!path_pixel(P, tid, rx, ry, t0)) return;
+    shade_pixel<false, false, true, true, true, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr, &S,
+                                                      &Q, &L, &IL);
+}
+
 // One workgroup builds the instance BVH of n <= kTlasMax instances (tlas_core.h): sort keys, a bitonic sort in LDS, the leaves, the refit
 // level by level (each level reads the one below it from global memory behind a fence and a barrier), the header.  No atomics.
 __global__ __launch_bounds__(kTlasBuildThreads) void tlas_build_kernel(const blok_instance* inst, uint32_t n, const ModelDesc* models, uint32_t n_models,
@@ -1763,6 +1782,14 @@ void launch_paths_lit(const PathArgs& args, const TlasScene& scene, const PoseSc
     uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
     if (stack_slots > slots) slots = stack_slots;
     hipLaunchKernelGGL(path_kernel_lit, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses, lit);
+}
+
+void launch_paths_lit_placed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, const InstanceLightScene& ilit,
+                             uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream) {
+    if (n_blocks == 0 || scene.n_instances == 0u) return;
+    uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
+    if (stack_slots > slots) slots = stack_slots;
+    hipLaunchKernelGGL(path_kernel_lit_placed, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses, lit, ilit);
 }
 
 void launch_tlas_build(const blok_instance* instances, uint32_t n, const ModelDesc* models, uint32_t n_models, TlasNode* nodes, hipStream_t stream) {

@@ -73,3 +73,69 @@ def download(tracer, first: int | None = None, count: int | None = None, page: i
     if first is None and count is None:
         first, count = 0, int(info(tracer)["n"][0])
     return tracer._paged(tracer._lib.blok_hip_lights_download, np.zeros(int(count or 0), dtype=LIGHT), int(first or 0), page)
+
+
+# ---- emissive models as lights (include/blok_hip.h: "emissive models as lights") ----------------------------------------------
+def host_model_lights(xyz, material_ids, materials) -> np.ndarray:
+    """blok_model_lights: the LIGHT records of the exposed emissive unit faces of the model `model_create` makes of the voxel list, in the
+    order of its material array; bit for bit what `model_lights` builds on the device."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(-1, 3)
+    ids = np.ascontiguousarray(material_ids, dtype=np.uint32).reshape(-1)
+    m = np.ascontiguousarray(materials, dtype=MATERIAL).reshape(-1)
+    if len(ids) != len(xyz):
+        raise ValueError("one material id per voxel")
+    lib = _ffi.host_lib()
+    n = C.c_uint64()
+    args = (_ffi.ptr(xyz) if len(xyz) else None, _ffi.ptr(ids) if len(ids) else None, len(ids), _ffi.ptr(m) if len(m) else None, len(m))
+    rc = lib.blok_model_lights(*args, None, 0, C.byref(n))
+    if rc != 0:
+        raise BlokError(rc, "blok_model_lights")
+    out = np.zeros(int(n.value), dtype=LIGHT)
+    rc = lib.blok_model_lights(*args, _ffi.ptr(out) if len(out) else None, len(out), C.byref(n))
+    if rc != 0:
+        raise BlokError(rc, "blok_model_lights")
+    return out
+
+
+def instance_light_record(instance, scale_log2: int, model_face) -> np.ndarray:
+    """blok_instance_light_record: the world-lattice LIGHT record (du = dv = 2**scale_log2, cum 0) of one unit face of a model's table under
+    one INSTANCE record."""
+    inst = np.ascontiguousarray(instance, dtype=_ffi.INSTANCE).reshape(1)
+    face = np.ascontiguousarray(model_face, dtype=LIGHT).reshape(1)
+    out = np.zeros(1, dtype=LIGHT)
+    _ffi.host_lib().blok_instance_light_record(_ffi.ptr(inst), int(scale_log2), _ffi.ptr(face), _ffi.ptr(out))
+    return out[0]
+
+
+def model_lights(tracer, model: int) -> np.ndarray:
+    """blok_hip_model_lights: builds and installs the model's light table from its own tree and the tracer's material table.  Returns the
+    LIGHTS_INFO record (n = n_faces = the faces; zeros: no faces, no table)."""
+    out = np.zeros(1, dtype=LIGHTS_INFO)
+    tracer._check(tracer._lib.blok_hip_model_lights(tracer._ctx, int(model), 0, _ffi.ptr(out)))
+    return out
+
+
+def model_lights_info(tracer, model: int) -> np.ndarray:
+    out = np.zeros(1, dtype=LIGHTS_INFO)
+    tracer._check(tracer._lib.blok_hip_model_lights_info(tracer._ctx, int(model), _ffi.ptr(out)))
+    return out
+
+
+def model_lights_download(tracer, model: int, first: int | None = None, count: int | None = None, page: int = 1 << 22) -> np.ndarray:
+    """blok_hip_model_lights_download: records [first, first + count) of the model's table (both None: all of it), `page` records a call."""
+    if first is None and count is None:
+        first, count = 0, int(model_lights_info(tracer, model)["n"][0])
+    return tracer._paged(tracer._lib.blok_hip_model_lights_download, np.zeros(int(count or 0), dtype=LIGHT), int(first or 0), page, int(model))
+
+
+def model_lights_clear(tracer, model: int) -> None:
+    tracer._check(tracer._lib.blok_hip_model_lights_clear(tracer._ctx, int(model)))
+
+
+def instance_lights_info(tracer, instances):
+    """blok_hip_instance_lights_info: (the INSTANCE_LIGHTS_INFO record, icum as n + 1 uint32 words) of the prefix kernel over a host table."""
+    inst = np.ascontiguousarray(instances if instances is not None else [], dtype=_ffi.INSTANCE).reshape(-1)
+    out = np.zeros(1, dtype=_ffi.INSTANCE_LIGHTS_INFO)
+    icum = np.zeros(len(inst) + 1, dtype=np.uint32)
+    tracer._check(tracer._lib.blok_hip_instance_lights_info(tracer._ctx, _ffi.ptr(inst) if len(inst) else None, len(inst), _ffi.ptr(out), _ffi.ptr(icum)))
+    return out, icum

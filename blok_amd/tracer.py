@@ -981,6 +981,27 @@ class HipTracer:
         self._check(self._lib.blok_hip_model_scale(self._ctx, int(model), C.byref(out)))
         return int(out.value)
 
+    # emissive models as lights (blok_amd/lights.py has the entries and their host twins)
+    def model_lights(self, model: int):
+        from . import lights
+        return lights.model_lights(self, model)
+
+    def model_lights_info(self, model: int):
+        from . import lights
+        return lights.model_lights_info(self, model)
+
+    def model_lights_download(self, model: int, first=None, count=None, page: int = 1 << 22):
+        from . import lights
+        return lights.model_lights_download(self, model, first, count, page)
+
+    def model_lights_clear(self, model: int):
+        from . import lights
+        lights.model_lights_clear(self, model)
+
+    def instance_lights_info(self, instances):
+        from . import lights
+        return lights.instance_lights_info(self, instances)
+
     def model_download(self, model: int):
         """Diagnostic (blok_hip_debug.h: blok_hip_download_model): (nodes as (n, 4) uint32, material ids, info) of a model as it lies in
         device memory; info is a dict of levels, origin, lo, hi."""

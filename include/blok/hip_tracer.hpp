@@ -282,6 +282,33 @@ public:
         for (uint64_t at = 0; at < n; at += page) check(blok_hip_lights_download(m_ctx, lights.data() + at, at, std::min(page, n - at)));
         return lights;
     }
+    // Emissive models as lights (blok_hip.h): the table of a model's exposed emissive unit faces, built on the device from the model's
+    // own tree under the installed material table; no faces: no table.  Dropped with the model and with every new material table.
+    blok_lights_info modelLights(uint32_t model) {
+        blok_lights_info info{};
+        check(blok_hip_model_lights(m_ctx, model, 0u, &info));
+        return info;
+    }
+    blok_lights_info modelLightsInfo(uint32_t model) const {
+        blok_lights_info info{};
+        check(blok_hip_model_lights_info(m_ctx, model, &info));
+        return info;
+    }
+    std::vector<blok_light> downloadModelLights(uint32_t model, uint64_t page = uint64_t(1) << 22) const {
+        const uint64_t n = modelLightsInfo(model).n;
+        std::vector<blok_light> lights(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_model_lights_download(m_ctx, model, lights.data() + at, at, std::min(page, n - at)));
+        return lights;
+    }
+    void clearModelLights(uint32_t model) { check(blok_hip_model_lights_clear(m_ctx, model)); }
+    // The light prefix of an instance table over the models' tables: the header, and the n + 1 words of icum where `icum` is not null.
+    blok_instance_lights_info instanceLightsInfo(const std::vector<blok_instance>& instances, std::vector<uint32_t>* icum = nullptr) const {
+        blok_instance_lights_info info{};
+        if (icum) icum->assign(instances.size() + 1, 0u);
+        check(blok_hip_instance_lights_info(m_ctx, instances.empty() ? nullptr : instances.data(), static_cast<uint32_t>(instances.size()), &info,
+                                            icum ? icum->data() : nullptr));
+        return info;
+    }
     // Placed models written into the resident volume, in table order (blok_hip_volume_stamp_models; mode BLOK_STAMP_SET / KEEP / ERASE):
     // returns the voxels written.  A later rebuildVolume installs the world.
     uint64_t stampModels(const std::vector<blok_instance>& placements, int mode = BLOK_STAMP_SET, float density = 1.0f) {

@@ -646,7 +646,9 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  *       blok_hip_draw_frame_rt_posed_motion).  (Planned as 1.24; that number went to the packed frame first.)
  * 1.26: emissive voxels as lights: a light table built from the quads snapshot and sampled at every hit of the path loop (blok_light;
  *       blok_hip_lights_from_quads, blok_hip_set_lights, blok_hip_lights_info, blok_hip_lights_download).
- * 1.27: a view at rest re-enters every listed ray at the node its restarted walk ends in (blok_hip_debug.h: blok_hip_set_beam_cache mode 5, the default). */
+ * 1.27: a view at rest re-enters every listed ray at the node its restarted walk ends in (blok_hip_debug.h: blok_hip_set_beam_cache mode 5, the default).
+ * 1.28: emissive models as lights: a light table per model built from its own tree, sampled through the lattice instances of a path-traced
+ *       launch by a per-launch prefix over the instance table (blok_hip_model_lights*, blok_hip_instance_lights_info). */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models
@@ -712,6 +714,57 @@ int blok_hip_model_destroy(blok_hip_ctx* ctx, uint32_t model);
  * entry that takes a model of any exponent is blok_hip_volume_stamp_affine: it ignores the exponent, its matrix carries all scale. */
 int blok_hip_model_set_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t scale_log2);
 int blok_hip_model_scale(blok_hip_ctx* ctx, uint32_t model, uint32_t* out_scale_log2);
+
+/* ---- emissive models as lights (ABI 1.28) ----
+ * The light table above ("emissive voxels as lights") holds faces of the WORLD.  A model can carry a table of its own, in its own cells,
+ * so that a lattice instance of it (blok_instance) is a light wherever it is placed and however often it moves, with nothing rebuilt.
+ * While some live model has a table, every path-traced entry that brings a lattice instance table with n > 0 (blok_hip_trace_paths_instanced*,
+ * blok_hip_trace_paths_posed*, the blok_hip_draw_frame_rt_instanced* and _posed* chain) samples world and instance faces in one pick and
+ * counts a lit instance's emission once (DESIGN.md §33 has the rule); with or without a world table.  With no model table, or no instance
+ * table, every entry runs the kernel it ran before, bit for bit.  Poses are no part of this (their areas are real): they count by hits.
+ *  - blok_hip_model_lights builds, on the device and from the model's own tree, the table of the model's exposed emissive UNIT faces:
+ *    a filled model voxel whose material index (min(id, 65535), then 0 when beyond the material table) is emissive in the context's CURRENT
+ *    material table contributes face f iff the model's neighbouring cell in that direction is empty.  The world and other instances play no
+ *    part.  One blok_light per face: du = dv = 1, cum = the record's index, lo in the model's local lattice with the plane coordinate as in
+ *    blok_quad (+1 for faces 0, 2, 4), material the voxel's id, face as in blok_quad.  Order: the model's material array (bricks in the
+ *    tree's order, cells in ascending bit order x | y << 2 | z << 4), face 0..5 within a voxel.  flags must be 0.  A result of no faces
+ *    installs no table (an earlier one of that model goes).  Bit-identical to blok_model_lights (blok_world.h) for the model
+ *    blok_hip_model_create makes of the same list.  Blocking.  Errors, each leaving the model's previous table in place:
+ *    BLOK_ERR_INVALID_ARG for an unknown or destroyed model, without a material table, for flags != 0; BLOK_ERR_OOM.
+ *  - blok_hip_model_lights_info: n = n_faces = the records, bytes, area_world = 0 (a model has no place), n_owned = 0; zeros without a
+ *    table.  blok_hip_model_lights_download copies records [first, first + count) in pieces as the other downloads do;
+ *    blok_hip_model_lights_clear drops the model's table.  All three: BLOK_ERR_INVALID_ARG for an unknown or destroyed model.
+ *  - Life: a table is freed by blok_hip_model_destroy and kept by blok_hip_model_set_scale (the records are in model cells).  ALL model
+ *    tables are dropped by every call that installs another world or material table, the calls that clear the world's light table: a
+ *    table is a statement about which ids glow.
+ *  - The record of an instance's face (blok_instance_light_record, blok_world.h): for model cell c and scale exponent e the cell's lowest
+ *    world voxel on world axis axis[k] is offset + c_k * 2^e, or offset - (c_k + 1) * 2^e when flip bit k is set; the world face is
+ *    2 * axis[k] + (n XOR flip_k); the plane coordinate is that low voxel for a - face and low + 2^e for a + face; du = dv = 2^e; material
+ *    unchanged; cum 0.  64-bit integer work; one model face is exactly 4^e world unit faces.
+ *  - The prefix of an instance table: faces_i = n(model_i) << 2e if instance i is usable (the kernels' rule: well formed, a live model of a
+ *    usable voxel size, world box inside the int16 lattice) and its model has a table, else 0; icum is the exclusive scan, n + 1 words, and
+ *    icum[i + 1] != icum[i] says "instance i is lit".  With A_world the faces of the installed world table (0 without one), A_inst the sum
+ *    and A_total = A_world + A_inst: if A_total >= 2^32 instance lights are DISABLED for that table — every faces_i is 0, A_inst = 0,
+ *    A_total = A_world, disabled = 1 — and nothing fails.  area_world = (float(A_total) * vs) * vs.  The extended pick is
+ *    pick = (r * A_total) >> 32: below A_world the world's light; else p = pick - A_world, the instance the last i with icum[i] <= p,
+ *    off = p - icum[i], the model's record table[off >> 2e], the cell off & (4^e - 1) of its world rectangle.
+ *  - blok_hip_instance_lights_info runs the prefix kernel over a host table (the records are not checked: unusable ones count 0) and
+ *    returns the header, and the n + 1 words where out_icum_host is not NULL.  Blocking.  BLOK_ERR_INVALID_ARG: a NULL table with n > 0, a
+ *    NULL out. */
+typedef struct blok_instance_lights_info {
+    uint64_t a_inst;     /* A_inst: world unit faces of the lit instances */
+    uint64_t a_total;    /* A_world + A_inst */
+    float    area_world; /* (float(A_total) * vs) * vs */
+    uint32_t n_lit;      /* instances with faces_i > 0 */
+    uint32_t disabled;   /* 1: A_world + the instances' faces reached 2^32, the table carries no light */
+    uint32_t reserved;   /* 0 */
+} blok_instance_lights_info;
+int blok_hip_model_lights(blok_hip_ctx* ctx, uint32_t model, uint32_t flags, blok_lights_info* out_info);
+int blok_hip_model_lights_info(blok_hip_ctx* ctx, uint32_t model, blok_lights_info* out_info);
+int blok_hip_model_lights_download(blok_hip_ctx* ctx, uint32_t model, blok_light* out_host, uint64_t first, uint64_t count);
+int blok_hip_model_lights_clear(blok_hip_ctx* ctx, uint32_t model);
+int blok_hip_instance_lights_info(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n, blok_instance_lights_info* out,
+                                  uint32_t* out_icum_host);
 /* BLOK_OK if every instance of a host table passes the limits above, else BLOK_ERR_INVALID_ARG naming the first that does not. */
 int blok_hip_check_instances(blok_hip_ctx* ctx, const blok_instance* instances_host, uint32_t n_instances);
 

@@ -188,6 +188,15 @@ int blok_quads_write_obj(const char* path, const blok_quad* quads, uint64_t n, c
 int blok_lights_from_quads(const blok_quad* quads, uint64_t n_quads, const blok_material* materials, size_t n_materials, blok_light* out,
                            uint64_t capacity, float voxel_size, blok_lights_info* out_info);
 int blok_lights_check(const blok_light* lights, uint64_t n, blok_lights_info* out_info, char* err, size_t err_len);
+/* model_lights: the contract of blok_hip_model_lights (blok_hip.h, "emissive models as lights") for the model blok_hip_model_create makes
+ * of the n voxels xyz[3*i..] / material_ids[i] (duplicates: the last one wins), bit-identical to the device's table: the model's tree is
+ * built and walked.  Writes at most `capacity` records (out may be NULL with capacity 0); *out_n (may be NULL) takes the number of faces.
+ * BLOK_ERR_INVALID_ARG: a NULL list, n == 0, no material table; BLOK_ERR_UNSUPPORTED: a list blok_hip_model_create refuses.
+ * instance_light_record: the world-lattice rectangle of unit face *model_face of a model's table under *instance for a model of scale
+ * exponent scale_log2 (0 .. 8; above: 8), by the rule of blok_hip.h; any NULL pointer: nothing is written. */
+int blok_model_lights(const int32_t* xyz, const uint32_t* material_ids, size_t n, const blok_material* materials, size_t n_materials, blok_light* out,
+                      uint64_t capacity, uint64_t* out_n);
+void blok_instance_light_record(const blok_instance* instance, uint32_t scale_log2, const blok_light* model_face, blok_light* out);
 
 /* -------------------------------------------------------------- models into a volume and back on the host (stamp.cpp)
  * The contracts of blok_hip_volume_stamp_models and blok_hip_volume_capture_model (blok_hip.h) over host arrays density[x + y*nx + z*nx*ny]

@@ -59,11 +59,15 @@
 //          flooded from all six faces with max_steps 65534 (blok_hip_volume_flood_field), then BLOK_FLOOD_FILL_UNREACHED fills every empty
 //          cell the air did not reach with material 0, or --seal-material N: an openly voxelized shell becomes solid, caves no one can
 //          enter are closed.  No primary ray enters a sealed cell
+//   --model-lights: with --rt and --populate (without --bake): behind the last rebuild the light table of every loaded model is built from its
+//          own tree (blok_hip_model_lights) and the frames go through the instanced path-traced chain (blok_hip_draw_frame_rt_instanced) with the
+//          scattered table, so that a model whose material glows (--glow ID) lights the terrain around every copy of it; logs "model lights: M
+//          models, F faces; I instances, L lit, A faces in the world" and the camera of the written frame.  Refused when nothing is placed.
 //   --populate: with --terrain, once the volume is filled and before it is rebuilt: the first model of every listed .vox file is uploaded
 //          (blok_hip_model_create; VOX z is up), the column field of the whole box taken along +y from the top (blok_hip_volume_column_field)
 //          and the models scattered on the terrain's grass (blok_hip_volume_scatter_models: seed = the terrain's, one candidate per 16 x 16
 //          columns, probability 40000 / 65536, ROTATE | MIRROR, footprint radius 1 with rise and drop of at most 1, each model anchored at
-//          the centre of its base).  The first-hit frames are traced with the table as instances (--rt frames show the world alone); with
+//          the centre of its base).  The first-hit frames are traced with the table as instances (--rt frames show the world alone, unless --model-lights); with
 //          --bake the table is stamped into the volume instead (BLOK_STAMP_SET) and the frames show the rebuilt world
 //   --paste FILE.vox@X,Y,Z,YAW_DEG,SCALE: with --terrain, once the volume is filled and before it is rebuilt: the first model of the .vox file
 //          (VOX z is up) is turned by YAW_DEG about +y around the centre of its voxels' box, scaled by SCALE, and resampled into the volume
@@ -142,6 +146,7 @@ struct Options {
     std::vector<Paste> posed;             // .vox models traced as posed models over the world, turned and scaled
     bool rt_posed = false;                // --rt-posed: the ray-tracing path with the posed models in it
     bool lights = false;                  // --lights: with --rt or --rt-posed over a resident volume, its emissive faces are sampled as lights
+    bool model_lights = false;            // --model-lights: with --rt and --populate, the scattered models' emissive faces are sampled as lights
     struct Glow { uint32_t id; bool has_rgb; float rgb[3]; };
     std::vector<Glow> glow;               // --glow ID[:R,G,B]: materials made emissive in the table every rebuild installs
     bool pose_motion = false;             // --pose-motion: ... drawn with object motion for the poses
@@ -535,6 +540,7 @@ private:
             loadVoxModel(path, xyz, ids, size);
             blok_scatter_entry e{};
             e.model = m_tracer->createModel(xyz, ids);
+            m_populateModels.push_back(e.model);
             e.weight = 1u;
             e.anchor[0] = static_cast<int32_t>(size[0] / 2u); e.anchor[1] = 0; e.anchor[2] = static_cast<int32_t>(size[1] / 2u);
             entries.push_back(e);
@@ -742,16 +748,28 @@ private:
         const blok_lights_info info = m_tracer->lightsFromQuads();
         std::cout << "lights: " << info.n << " rectangles, " << info.n_faces << " faces, " << info.n_owned << " materials (of " << quads << " quads, " << faces << " exposed faces)\n";
     }
+    // --model-lights: every loaded model's own light table (behind the last rebuild: a new material table drops them), and what the scattered
+    // table makes of them.
+    void installModelLights() {
+        if (!m_opt.model_lights) return;
+        if (m_instances.empty()) throw std::runtime_error("--model-lights: nothing is placed (--populate scattered no model over this terrain)");
+        uint64_t faces = 0;
+        for (const uint32_t model : m_populateModels) faces += m_tracer->modelLights(model).n;
+        const blok_instance_lights_info info = m_tracer->instanceLightsInfo(m_instances);
+        std::cout << "model lights: " << m_populateModels.size() << " models, " << faces << " faces; " << m_instances.size() << " instances, " << info.n_lit << " lit, "
+                  << info.a_inst << " faces in the world" << (info.disabled ? " (disabled: 2^32 faces or more)" : "") << "\n";
+    }
     void update() {
         using clock = std::chrono::steady_clock;
         installLights();
+        installModelLights();
         for (uint32_t f = 0; f < m_opt.frames; ++f) {
             const auto t0 = clock::now();
             m_tracer->beginFrame();
             if (m_multi) m_multi->drawFrame(m_camera, m_multiFrame);
             else if (m_opt.pose_motion) drawPoseMotionFrame(f);
             else if (m_opt.rt_posed) m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp);
-            else if (m_opt.rt && m_opt.far) m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp);
+            else if (m_opt.rt && (m_opt.far || m_opt.model_lights)) m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp);
             else if (m_opt.rt) m_tracer->drawFrameRT(m_camera, m_opt.spp);
             else if (!m_poses.empty()) m_tracer->drawFramePosed(m_camera, m_instances, m_poses);
             else if (!m_instances.empty()) m_tracer->drawFrameInstanced(m_camera, m_instances);
@@ -766,7 +784,7 @@ private:
         }
         const auto& single = m_opt.pose_motion ? drawPoseMotionFrame(m_opt.frames)
                              : m_opt.rt_posed ? m_tracer->drawFrameRtPosed(m_camera, m_instances, m_poses, m_opt.spp)
-                             : m_opt.rt && m_opt.far ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
+                             : m_opt.rt && (m_opt.far || m_opt.model_lights) ? m_tracer->drawFrameRTInstanced(m_camera, m_instances, m_opt.spp)
                              : m_opt.rt ? m_tracer->drawFrameRT(m_camera, m_opt.spp) : !m_poses.empty() ? drawPosed() : !m_instances.empty() ? drawPopulated() : m_tracer->drawFrameRgba8(m_camera);
         if (m_multi) {                                       // the partitioned frame must be the single-device frame
             m_multi->drawFrame(m_camera, m_multiFrame);
@@ -776,6 +794,14 @@ private:
             if (differ) throw std::runtime_error("multi-device frame differs from the single-device frame");
         }
         farReport();
+        if (m_opt.model_lights) {                           // the camera of the written frame, exactly (%.9g round-trips a float)
+            const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
+            const float cam[14] = {c.pos[0], c.pos[1], c.pos[2], c.fwd[0], c.fwd[1], c.fwd[2], c.right[0], c.right[1], c.right[2], c.up[0], c.up[1], c.up[2], c.tan_half_fov, c.aspect};
+            std::printf("model lights: camera");
+            for (float v : cam) std::printf(" %.9g", v);
+            std::printf("\n");
+            std::fflush(stdout);
+        }
         if (!m_poses.empty()) {                             // the camera of the written frame, exactly (%.9g round-trips a float), and who won it
             const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
             const float cam[14] = {c.pos[0], c.pos[1], c.pos[2], c.fwd[0], c.fwd[1], c.fwd[2], c.right[0], c.right[1], c.right[2], c.up[0], c.up[1], c.up[2], c.tan_half_fov, c.aspect};
@@ -806,6 +832,7 @@ private:
     std::unique_ptr<blok::HipTracer> m_tracer;
     std::unique_ptr<blok::HipMultiTracer> m_multi;
     std::vector<uint32_t> m_multiFrame;
+    std::vector<uint32_t> m_populateModels;        // --populate: the ids of the models it loaded, in the order of the list
     std::vector<blok_instance> m_instances;        // --populate: the scattered table (empty once baked); --far: the ring of coarse copies
     std::vector<blok_hit> m_populatedHits;
     std::vector<uint32_t> m_populatedFrame;
@@ -949,6 +976,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rt")) opt.rt = true;
         else if (!std::strcmp(argv[i], "--rt-posed")) opt.rt_posed = true;
         else if (!std::strcmp(argv[i], "--lights")) opt.lights = true;
+        else if (!std::strcmp(argv[i], "--model-lights")) opt.model_lights = true;
         else if (!std::strcmp(argv[i], "--glow")) {
             Options::Glow g{};
             const int got = std::sscanf(next(), "%u:%f,%f,%f", &g.id, &g.rgb[0], &g.rgb[1], &g.rgb[2]);
@@ -985,6 +1013,10 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (opt.lights && !(opt.rt || opt.rt_posed)) { std::fprintf(stderr, "--lights is sampled by the path-traced frames: give --rt or --rt-posed\n"); return 2; }
+    if (opt.model_lights && (!opt.rt || opt.populate.empty() || opt.bake || opt.far)) {
+        std::fprintf(stderr, "--model-lights samples the placed models' emissive faces in the path-traced frames: give --rt and --populate FILE.vox[,...] (without --bake: a baked model is the world's, --lights; without --far)\n");
+        return 2;
+    }
     if (opt.far_direct && !opt.far) { std::fprintf(stderr, "--far-direct and --far-rings need --far K[,MIN]\n"); return 2; }
     try {
         App app(blok::GraphicsApi::HIP, opt);
