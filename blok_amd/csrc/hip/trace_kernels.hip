@@ -697,34 +697,59 @@ __global__ __launch_bounds__(kBlock) void packed_walk_own_kernel(const TraceArgs
 #ifndef BLOK_PACKED_FILL_NT
 #define BLOK_PACKED_FILL_NT 1          // 1: non-temporal stores (nobody on the device reads a miss back, and the walks of the frames in flight keep the cache); 0: write_miss's
 #endif
+// Four units at a time, their bounds loaded in front of their stores: loads and stores share one counter and return in order, so a load
+// behind a store waits for that store to be acknowledged — once per four units, not once per unit.  The four loads are UNCONDITIONAL, from
+// an index brought into the bounds' array, and the test "this lane has a pixel of this unit" is the store's predicate: behind a guard
+// each load is a block of its own with its own full wait, four round trips in a row instead of one (profiles/packed_stream_ab.txt).
+constexpr uint32_t kFillBatch = 4u;
+constexpr uint32_t kFillNoPixel = 0xFFFFFFFFu;          // (w, h < 65 535: a pixel's index is below it)
+struct FillBatch {
+    float bound[kFillBatch];                            // the finer bound of the pixel's wave tile (of tile 0 for a lane without a pixel)
+    uint32_t at[kFillBatch];                            // the pixel's index in the rectangle; kFillNoPixel: nothing to write
+};
+
+// The units i .. i + 3 of this workgroup: issues their four loads and waits for none.
+__device__ __forceinline__ FillBatch fill_batch_load(const TraceArgs& A, const float* fine, const uint32_t n_units, const uint32_t units_x, const uint32_t i) {
+    const uint32_t lane = threadIdx.x, tiles_x = (A.w + kWaveW - 1u) / kWaveW;
+    FillBatch b;
+#pragma unroll
+    for (uint32_t j = 0; j < kFillBatch; ++j) {
+        const uint32_t u = fill_unit_of(blockIdx.x, i + j, gridDim.x);
+        const uint32_t ry = fill_unit_row(u, units_x), rx = fill_unit_x0(u, units_x) + lane;
+        const bool mine = u < n_units && rx < A.w && ry < A.h;
+        b.at[j] = mine ? ry * A.w + rx : kFillNoPixel;
+        b.bound[j] = fine[mine ? (ry / kWaveH) * tiles_x + rx / kWaveW : 0u];
+    }
+    return b;
+}
+
+// The stores of a batch.  Its first use of a bound is the one wait of the batch.
+__device__ __forceinline__ void fill_batch_store(const TraceArgs& A, const FillBatch& b) {
+#pragma unroll
+    for (uint32_t j = 0; j < kFillBatch; ++j)
+        if (b.at[j] != kFillNoPixel && b.bound[j] >= kBeamNone) {
+            const size_t at = b.at[j];
+#if BLOK_PACKED_FILL_NT
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));      // write_miss's bytes (trace_core.h)
+            if (A.out) __builtin_nontemporal_store(u32x4{0xBF800000u, 0u, 0u, 0x00FF0000u}, reinterpret_cast<u32x4*>(A.out + at));
+            if (A.out_rgba) __builtin_nontemporal_store(kSkyRgba, A.out_rgba + at);
+#else
+            write_miss(Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+#endif
+        }
+}
+
+// Every unit of this workgroup, the first four from `first` (fill_batch_load(.., 0), issued wherever the caller's other loads are): stores
+// only, unless the workgroup has more than four units.
+__device__ __forceinline__ void fill_units_of_workgroup(const TraceArgs& A, const FillBatch& first, const float* fine, const uint32_t n_units, const uint32_t units_x) {
+    if (!A.out && !A.out_rgba) return;
+    fill_batch_store(A, first);
+    for (uint32_t i = kFillBatch; fill_unit_of(blockIdx.x, i, gridDim.x) < n_units; i += kFillBatch) fill_batch_store(A, fill_batch_load(A, fine, n_units, units_x, i));
+}
+
 __device__ __forceinline__ void fill_units_of_workgroup(const TraceArgs& A, const float* fine, const uint32_t n_units, const uint32_t units_x) {
     if (!A.out && !A.out_rgba) return;
-    const uint32_t lane = threadIdx.x, tiles_x = (A.w + kWaveW - 1u) / kWaveW;
-    // four units at a time, their bounds loaded in front of their stores: loads and stores share one counter and return in order, so a load
-    // behind a store waits for that store to be acknowledged — once per four units here, not once per unit
-    constexpr uint32_t kBatch = 4u;
-    for (uint32_t i = 0u; fill_unit_of(blockIdx.x, i, gridDim.x) < n_units; i += kBatch) {
-        float bound[kBatch];
-        size_t at[kBatch];
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; ++j) {
-            const uint32_t u = fill_unit_of(blockIdx.x, i + j, gridDim.x);
-            const uint32_t ry = fill_unit_row(u, units_x), rx = fill_unit_x0(u, units_x) + lane;
-            at[j] = static_cast<size_t>(ry) * A.w + rx;
-            bound[j] = u < n_units && rx < A.w && ry < A.h ? fine[(ry / kWaveH) * tiles_x + rx / kWaveW] : 0.0f;      // (0: nothing to write)
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; ++j)
-            if (bound[j] >= kBeamNone) {
-#if BLOK_PACKED_FILL_NT
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));      // write_miss's bytes (trace_core.h)
-                if (A.out) __builtin_nontemporal_store(u32x4{0xBF800000u, 0u, 0u, 0x00FF0000u}, reinterpret_cast<u32x4*>(A.out + at[j]));
-                if (A.out_rgba) __builtin_nontemporal_store(kSkyRgba, A.out_rgba + at[j]);
-#else
-                write_miss(Sink{A.out ? A.out + at[j] : nullptr, A.out_rgba ? A.out_rgba + at[j] : nullptr});
-#endif
-            }
-    }
+    fill_units_of_workgroup(A, fill_batch_load(A, fine, n_units, units_x, 0u), fine, n_units, units_x);
 }
 
 // packed_walk_kernel's walk for the workgroups [0, n_groups), in the table's order, and every workgroup's fill units: those of the grid's
@@ -782,36 +807,54 @@ __global__ __launch_bounds__(kBlock) void packed_frame_node_kernel(const TraceAr
     static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
     extern __shared__ uint4 lds_stack[];
     const uint32_t lane = threadIdx.x;
-    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
-    if (blockIdx.x < n_groups) {
-        const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
-        const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
-        const float t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
-        const uint32_t word = slot_node[static_cast<size_t>(group) * 64u + lane];
-        const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
-        if (entry != kPackPad && rx < A.w && ry < A.h) {
-            const uint4 rec = A.nodes[word == kNodeWordNone ? 0u : (word & kNodeWordIndexMask)];
-            const size_t at = static_cast<size_t>(ry) * A.w + rx;
-            const Sink dst{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr};
-            RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
-            r.tmin = fmaxf(r.tmin, t0);
-            const WalkRay R = walk_ray(A, r.ox, r.oy, r.oz, safe_inv(r.dx), safe_inv(r.dy), safe_inv(r.dz));
-            WalkState s;
-            const bool settled = walk_enter_node(A, r, R, word, rec, s);
-            if (__ballot(!settled) != 0ull) trace_one<true>(A, r, lds_stack + lane, dst);
-            else if (s.found) {
-                const HitInfo h = walk_hit(A, r, R, s);           // the record and the pixel as trace_one writes them
-                uint4 out;
-                out.x = __float_as_uint(h.t);
-                out.y = h.material;
-                out.z = (static_cast<uint32_t>(h.vx) & 0xFFFFu) | (static_cast<uint32_t>(h.vy) << 16);
-                out.w = (static_cast<uint32_t>(h.vz) & 0xFFFFu) | (h.face << 16) | (1u << 24);
-                if (dst.hit) *reinterpret_cast<uint4*>(dst.hit) = out;
-                if (dst.rgba) *dst.rgba = shade_rgba(A.mat_table, A.n_materials, h.material, h.face);
-            } else write_miss(dst);
-        }
+    const uint32_t table_word = table[blockIdx.x < n_groups ? blockIdx.x : 0u];      // (n_groups > 0: launch_packed_frame_node)
+    // A workgroup of the grid's tail writes its units and ends: it shares no block with the walk's, so that no path of the walk reaches a
+    // store with a load of another path still counted against it.
+    if (blockIdx.x >= n_groups) { fill_units_of_workgroup(A, fine, n_units, units_x); return; }
+    // A wave's loads stand in front of its first store (the counter rule above fill_batch_load).  The bounds of the wave's first four units
+    // are issued beside the three loads of its group and held across the walk; the settled path then loads the hit's material and its
+    // albedo, and only then stores: the record, the pixel, the units.
+    const uint32_t group = __builtin_amdgcn_readfirstlane(table_word) & ((1u << kPackKeyShift) - 1u);
+    const FillBatch first = fill_batch_load(A, fine, n_units, units_x, 0u);
+    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, first, fine, n_units, units_x);
+    const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+    const float slot_t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
+    const uint32_t slot_word = slot_node[static_cast<size_t>(group) * 64u + lane];
+    // A padding lane is not branched around (the three loads above would sink into the branch, behind a wait for the entry): it walks
+    // pixel (0, 0) without a word, is left out of the ballot and stores nothing.
+    const bool live = entry != kPackPad && (entry & 0xFFFFu) < A.w && (entry >> 16) < A.h;
+    const uint32_t rx = live ? entry & 0xFFFFu : 0u, ry = live ? entry >> 16 : 0u;
+    const float t0 = live ? slot_t0 : 0.0f;
+    const uint32_t word = live ? slot_word : kNodeWordNone;
+    const uint4 rec = A.nodes[word == kNodeWordNone ? 0u : (word & kNodeWordIndexMask)];
+    const size_t at = static_cast<size_t>(ry) * A.w + rx;
+    RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
+    r.tmin = fmaxf(r.tmin, t0);
+    const WalkRay R = walk_ray(A, r.ox, r.oy, r.oz, safe_inv(r.dx), safe_inv(r.dy), safe_inv(r.dz));
+    WalkState s;
+    const bool settled = walk_enter_node(A, r, R, word, rec, s);
+    if (__ballot(live && !settled) != 0ull) {
+        // the fallback ends here, behind units of its own: joined with the settled path, what its loop leaves counted would stand as a
+        // full wait between the settled path's stores
+        if (live) trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
+        if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, first, fine, n_units, units_x);
+        return;
     }
-    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    uint4 out = make_uint4(0xBF800000u, 0u, 0u, 0x00FF0000u);      // write_miss's record and pixel (trace_core.h)
+    uint32_t pixel = kSkyRgba;
+    if (live && s.found) {
+        const HitInfo h = walk_hit(A, r, R, s);           // the record and the pixel as trace_one writes them
+        out.x = __float_as_uint(h.t);
+        out.y = h.material;
+        out.z = (static_cast<uint32_t>(h.vx) & 0xFFFFu) | (static_cast<uint32_t>(h.vy) << 16);
+        out.w = (static_cast<uint32_t>(h.vz) & 0xFFFFu) | (h.face << 16) | (1u << 24);
+        pixel = shade_rgba(A.mat_table, A.n_materials, h.material, h.face);      // (also without an RGBA8 output: no branch between the two loads)
+    }
+    if (live) {
+        if (A.out) *reinterpret_cast<uint4*>(A.out + at) = out;
+        if (A.out_rgba) A.out_rgba[at] = pixel;
+    }
+    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, first, fine, n_units, units_x);
 }
 
 // ---- joint launch: the pre-pass waves and the walk waves in ONE grid, statically ------------------------------------------
