@@ -170,6 +170,9 @@ struct blok_hip_ctx {
     // A second buffer of the same size per slot holds the view's finer bounds, one per wave tile (beam_cache.h: plan_beam_refine): written by
     // ONE launch behind its walk (the refine kernel, `refined` behind it), read by the walks of the view's later launches under the same two
     // rules — a refill waits for every stream's held markers, which covers the readers of both buffers.
+    // The modes (blok_hip_set_beam_cache) are switches of the policy's facts: 1 the beam bounds, 2 `refine`, 3 `packed`, 4 the policy's
+    // own_starts, 5 its node_restart.  What a launch then does is one value (beam_cache.h: RestingWalk), made by plan_resting_launch and
+    // acted on by api_launch.hip's plan_resting / issue_resting / finish_resting.
     struct BeamCache {
         bool enabled = true;                                // blok_hip_set_beam_cache
         bool refine = true;                                 // ... with the finer bounds (mode 2)

@@ -465,32 +465,32 @@ static int wait_for_producer(blok_hip_ctx* ctx, blok_hip_ctx::BeamCache::Produce
     return BLOK_OK;
 }
 
-// Before a rectangle launch of a static form: does it search, search into a slot, or walk from a slot — and then from the slot's finer
-// bounds, or with their searches behind it?  Points args.beam at the slot's beam bounds and deals with whoever else uses it.
-static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::BeamCachePlan* plan, blok::BeamRefinePlan* fine,
-                                    blok::BeamListPlan* listed, blok::BeamStartsPlan* starts) {
+// Plan.  Before a rectangle launch of a static form: what does it do over the cache (beam_cache.h: plan_resting_launch) — search, search
+// into a slot, or walk from a slot, and then how?  A build that has finished is adopted here, whatever this launch is (its length was
+// written before the event).  Points args.beam at the slot's beam bounds and deals with whoever else uses it.
+static int plan_resting(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs& args, hipStream_t stream, blok::RestingPlan* resting) {
     auto& B = ctx->beam_cache;
-    *plan = blok::plan_beam_cache(B.policy, beam_key(ctx, mode, args));
-    *fine = blok::plan_beam_refine(B.policy, *plan, B.refine && blok::beam_refine_applies(args) && blok::beam_refine_tiles(args) <= B.capacity);
-    // the packed list: a build that has finished is adopted here, whatever this launch is (its length was written before the event)
-    bool build_finished = false;
-    if (B.policy.building >= 0) { build_finished = hipEventQuery(B.list_done) == hipSuccess; (void)hipGetLastError(); }      // hipErrorNotReady is an answer, not a failure
-    *listed = blok::plan_beam_list(B.policy, *plan, *fine, B.packed && blok::pack_applies(args) && static_cast<size_t>(blok::pack_areas(args)) * blok::kPackStretch <= B.list_capacity &&
-                                   static_cast<size_t>(args.w) * args.h <= B.d_trips.capacity(), build_finished);
-    if (listed->adopted >= 0) { auto& got = B.slots[listed->adopted]; got.n_groups = std::min(B.h_groups[listed->adopted], got.n_words); }
-    blok::BeamStartKey start_key;
-    static_assert(sizeof(args.jitter_clip) == sizeof(start_key.jitter_clip), "beam_cache.h: BeamStartKey::jitter_clip is TraceArgs::jitter_clip, bit for bit");
-    std::memcpy(start_key.jitter_clip, args.jitter_clip, sizeof(start_key.jitter_clip));
-    std::memcpy(&start_key.tmin, &args.tmin, sizeof(uint32_t)); std::memcpy(&start_key.tmax, &args.tmax, sizeof(uint32_t));
-    *starts = blok::plan_beam_starts(B.policy, *plan, *listed, start_key);
-    // mode 5: the node words beside the starts — unless the tree's node indices do not fit them, or (never: beam_list_buffers) there is nowhere to put them
-    if (blok::beam_nodes_count(B.policy, *plan, *starts) && (!blok::node_words_apply(ctx->stats.n_tree_nodes) || !B.d_ray_node || !B.slots[plan->slot].d_node))
-        blok::beam_nodes_decline(B.policy, plan->slot);
-    if (plan->action == blok::BeamAction::Search) return BLOK_OK;
-    auto& sl = B.slots[plan->slot];
-    if (plan->action == blok::BeamAction::Hit) {
+    blok::RestingFacts facts{};
+    facts.refine_eligible = B.refine && blok::beam_refine_applies(args) && blok::beam_refine_tiles(args) <= B.capacity;
+    facts.list_eligible = B.packed && blok::pack_applies(args) && static_cast<size_t>(blok::pack_areas(args)) * blok::kPackStretch <= B.list_capacity &&
+                          static_cast<size_t>(args.w) * args.h <= B.d_trips.capacity();
+    if (B.policy.building >= 0) { facts.build_finished = hipEventQuery(B.list_done) == hipSuccess; (void)hipGetLastError(); }      // hipErrorNotReady is an answer, not a failure
+    // mode 5: the node words beside the starts — unless the tree's node indices do not fit them, or (never: beam_list_buffers reserves
+    // every slot alike, and a reservation that failed leaves no list capacity to count for) there is nowhere to put them
+    facts.node_words = blok::node_words_apply(ctx->stats.n_tree_nodes) && B.d_ray_node;
+    for (const auto& sl : B.slots) facts.node_words = facts.node_words && sl.d_node;
+    static_assert(sizeof(args.jitter_clip) == sizeof(facts.start_key.jitter_clip), "beam_cache.h: BeamStartKey::jitter_clip is TraceArgs::jitter_clip, bit for bit");
+    std::memcpy(facts.start_key.jitter_clip, args.jitter_clip, sizeof(facts.start_key.jitter_clip));
+    std::memcpy(&facts.start_key.tmin, &args.tmin, sizeof(uint32_t)); std::memcpy(&facts.start_key.tmax, &args.tmax, sizeof(uint32_t));
+    *resting = blok::plan_resting_launch(B.policy, beam_key(ctx, mode, args), facts);
+    const blok::BeamCachePlan& plan = resting->cache;
+    if (resting->list.adopted >= 0) { auto& got = B.slots[resting->list.adopted]; got.n_groups = std::min(B.h_groups[resting->list.adopted], got.n_words); }
+    if (resting->walk == blok::RestingWalk::PackedNodes && !B.slots[plan.slot].d_node) resting->walk = blok::RestingWalk::PackedStarts;      // (never, as above)
+    if (plan.action == blok::BeamAction::Search) return BLOK_OK;
+    auto& sl = B.slots[plan.slot];
+    if (plan.action == blok::BeamAction::Hit) {
         { const int rc = wait_for_producer(ctx, sl.filled, stream); if (rc != BLOK_OK) return rc; }
-        if (fine->use_fine) { const int rc = wait_for_producer(ctx, sl.refined, stream); if (rc != BLOK_OK) return rc; }
+        if (resting->fine.use_fine) { const int rc = wait_for_producer(ctx, sl.refined, stream); if (rc != BLOK_OK) return rc; }
         B.hits += 1u;
     } else {
         // Nothing in flight may read the slot while the searches rewrite it (nor still be writing it): whatever used it was issued before
@@ -506,6 +506,94 @@ static int beam_cache_before_launch(blok_hip_ctx* ctx, blok::RayMode mode, blok:
         B.fills += 1u;
     }
     args.beam = sl.d_beam; args.beam_slots = nullptr; args.beam_serial = 0u;      // plain floats, whatever form was planned
+    return BLOK_OK;
+}
+
+// A packed hit's fill units per workgroup; 0: the fill in a launch of its own.  Known only behind the adoption: a list with groups has
+// the fill in the walk's grid (blok_hip_set_packed_fill), an all-sky view has the fill alone.
+static uint32_t packed_fill_units(const blok_hip_ctx* ctx, const blok::RestingPlan& r) {
+    return blok::resting_packed(r.walk) && ctx->beam_cache.slots[r.cache.slot].n_groups > 0u ? ctx->beam_cache.packed_fill : 0u;
+}
+
+// Issue.  A hit's launches, by r.walk -> the workgroups of a packed frame's one launch that only fill.
+// No searches.  Coarse, Fine: the walk over the view's live prefix, from the kept bounds; in front of it, what the search waves do besides
+// searching (the miss pixels, unless the walk writes them; the wave tiles the prefix has no workgroup for); behind it, on the view's K-th
+// hit, its finer searches, once.  The packed walk, and the launch that measures for it, use neither the view's order nor its live prefix
+// (the table's order stands in for both; the count launch walks every wave tile in a workgroup of its own, so that every listed pixel gets
+// its count): their fill writes the misses of the empty beam tiles and of the empty wave tiles and walks nothing.
+static uint32_t issue_resting(blok_hip_ctx* ctx, blok::RayMode mode, const blok::TraceArgs& args, const blok::RestingPlan& r, uint32_t blocks, uint32_t walk_blocks, uint32_t n_beams,
+                              hipStream_t stream) {
+    using Walk = blok::RestingWalk;
+    auto& B = ctx->beam_cache;
+    auto& sl = B.slots[r.cache.slot];
+    const bool prefix = r.walk == Walk::Coarse || r.walk == Walk::Fine;
+    blok::TraceArgs fill = args;
+    if (!prefix) {
+        fill.order = nullptr; fill.rank_of = nullptr; fill.launched = 0u; fill.order_sx = fill.order_sy = 0u; fill.n_strip = 0u; fill.fallback_tiles = nullptr;
+        fill.miss_in_walk = 0u;
+    }
+    // the walk reads the finer bounds through the fields it has: a "beam tile" the size of a wave tile (the lookup in trace_block works for
+    // any tile size), so a wave tile that is empty by its own bound is not walked: its misses come from the walk (miss_in_walk) or from the
+    // fill wave of its beam tile, and its walk workgroup, while the order still has one, costs 0
+    blok::TraceArgs walk = fill;
+    if (r.walk != Walk::Coarse) { walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW; }
+    const uint32_t units = packed_fill_units(ctx, r);
+    if (units == 0u && !fill.miss_in_walk) blok::launch_beam_fill(mode, fill, n_beams, r.walk != Walk::Coarse ? sl.d_fine.get() : nullptr, stream);
+    if (prefix) {
+        blok::launch_trace(mode, walk, walk_blocks, stream);
+        if (r.fine.refine_now) blok::launch_beam_refine(args, sl.d_fine, stream);
+        return 0u;
+    }
+    if (blok::resting_packed(r.walk))
+        return blok::launch_packed(fill, {sl.d_fine, sl.d_list, sl.d_table, sl.d_start, sl.d_node, sl.n_groups},
+                                   r.walk == Walk::PackedNodes ? blok::PackedFrom::Nodes : r.walk == Walk::PackedStarts ? blok::PackedFrom::Starts : blok::PackedFrom::Fine, units, stream);
+    // The count.  Mode 4: it also leaves every ray's own start and restarted trips; the build sorts by those and writes the starts in list
+    // order.  Mode 5: ... and the node every restarted walk ends in, gathered beside the starts.
+    const bool own = r.walk != Walk::Count, nodes = r.walk == Walk::CountNodes;
+    if (own) blok::launch_trace_count_own(walk, blocks, B.d_trips, B.d_ray_start, B.d_restarts, nodes ? B.d_ray_node.get() : nullptr, stream);
+    else blok::launch_trace_count(walk, blocks, B.d_trips, stream);
+    // the build behind it: the areas' sorted stretches, then (finish_resting) the table; its length goes to pinned memory in front of the event
+    sl.n_words = blok::pack_areas(args) * blok::kPackGroups; sl.n_groups = 0u;
+    blok::launch_pack_build(fill, sl.d_fine, {own ? B.d_restarts.get() : B.d_trips.get(), own ? B.d_ray_start.get() : nullptr, nodes ? B.d_ray_node.get() : nullptr},
+                            {sl.d_list, B.d_words, sl.d_start, sl.d_node}, stream);
+    return 0u;
+}
+
+// What the latest rectangle launch did, for api_debug.hip's read-backs, and the counters.  fill_only: what issue_resting answered.
+static void note_resting(blok_hip_ctx* ctx, const blok::RestingPlan& r, const blok::TraceArgs& args, uint32_t n_beams, uint32_t fill_only) {
+    auto& B = ctx->beam_cache;
+    B.last_action = r.cache.action == blok::BeamAction::Hit ? 2 : r.cache.action == blok::BeamAction::Fill ? 1 : 0;
+    B.last_slot = r.cache.slot; B.last_n_beams = n_beams;
+    B.last_fine = r.fine.use_fine ? 2 : r.fine.refine_now ? 1 : 0;
+    B.last_n_fine = B.last_fine ? blok::beam_refine_tiles(args) : 0u;
+    B.last_list = r.list.use_list ? 2 : r.list.count_now ? 1 : 0;
+    B.last_starts = r.starts.use == blok::BeamStarts::OtherKey ? 2 : (r.starts.use == blok::BeamStarts::Use || r.starts.count_own) ? 1 : 0;
+    if (r.starts.use == blok::BeamStarts::Use) B.start_hits += 1u;
+    if (r.starts.use == blok::BeamStarts::OtherKey) B.start_other_key += 1u;
+    B.last_w = args.w; B.last_h = args.h;
+    if (packed_fill_units(ctx, r) == 0u) return;
+    B.one_launch_frames += 1u; B.fill_only_workgroups += fill_only;
+    if (r.walk == blok::RestingWalk::PackedNodes) B.node_hits += 1u;
+}
+
+// Finish.  Behind the launches, with what issuing them answered: bounds nobody wrote are nobody's to keep; the event behind the finer
+// searches; the table's sort and the event behind the build; the commit of both (bounds nobody can wait for, a list nobody can see
+// finished, are not used); the event behind a fill.
+static int finish_resting(blok_hip_ctx* ctx, const blok::RestingPlan& r, hipError_t launch_error, hipStream_t stream) {
+    auto& B = ctx->beam_cache;
+    auto* const sl = r.cache.action == blok::BeamAction::Search ? nullptr : &B.slots[r.cache.slot];      // (a search is told neither to refine nor to count)
+    if (launch_error != hipSuccess && r.cache.action == blok::BeamAction::Fill) B.policy.valid[r.cache.slot] = false;
+    hipError_t marked = launch_error, built = launch_error;
+    if (r.fine.refine_now && marked == hipSuccess) marked = hipEventRecord(sl->refined.done, stream);
+    if (r.list.count_now && built == hipSuccess) built = blok::launch_pack_table_sort(B.d_words, sl->d_table, B.d_sort_temp, B.sort_temp_bytes, sl->n_words, B.h_groups + r.cache.slot, stream);
+    if (r.list.count_now && built == hipSuccess) built = hipEventRecord(B.list_done, stream);
+    blok::commit_resting_launch(B.policy, r, marked == hipSuccess, built == hipSuccess);
+    if (r.fine.refine_now && marked == hipSuccess) { sl->refined.settled = false; sl->refined.producer = stream; sl->refined.n_waited = 0; B.refines += 1u; }
+    if (r.list.count_now && built == hipSuccess) B.list_builds += 1u;
+    BLOK_HIP_TRY(ctx, launch_error);
+    BLOK_HIP_TRY(ctx, marked);
+    BLOK_HIP_TRY(ctx, built);
+    if (r.cache.action == blok::BeamAction::Fill) BLOK_HIP_TRY(ctx, hipEventRecord(sl->filled.done, stream));
     return BLOK_OK;
 }
 
@@ -600,84 +688,16 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
     args.miss_in_walk = static_form && !args.rank_of && ctx->miss_in_walk ? 1u : 0u;
     // A view at rest keeps its beam bounds (beam_cache.h): rectangle launches of the automatic form — the explicit forms stay what they are
     // there to be compared with, a rank's tiles and several frames per launch are left alone — that are not being captured.
-    blok::BeamCachePlan cached{blok::BeamAction::Search, -1};
-    blok::BeamRefinePlan finer{false, false};
-    blok::BeamListPlan listed{false, false, -1};
-    blok::BeamStartsPlan starts{false, blok::BeamStarts::None};
+    blok::RestingPlan resting{};
     if (ctx->beam_cache.enabled && rect && !frames && !capturing && static_form && ctx->launch_form == blok::kFormAuto && n_beams && n_beams <= ctx->beam_cache.capacity) {
-        const int rc = beam_cache_before_launch(ctx, mode, args, stream, &cached, &finer, &listed, &starts);
-        if (rc != BLOK_OK) {
-            if (finer.refine_now) blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, false);
-            if (listed.count_now) blok::beam_list_commit(ctx->beam_cache.policy, cached.slot, false);
-            return rc;
-        }
+        const int rc = plan_resting(ctx, mode, args, stream, &resting);
+        if (rc != BLOK_OK) { blok::commit_resting_launch(ctx->beam_cache.policy, resting, false, false); return rc; }
         // the searches that fill a slot write plain floats: the two-launch form, this once
-        if (cached.action == blok::BeamAction::Fill && plan.kind == blok::LaunchKind::Joint) { plan.kind = blok::LaunchKind::TwoLaunches; ctx->last_launch_kind = static_cast<int>(plan.kind); }
+        if (resting.cache.action == blok::BeamAction::Fill && plan.kind == blok::LaunchKind::Joint) { plan.kind = blok::LaunchKind::TwoLaunches; ctx->last_launch_kind = static_cast<int>(plan.kind); }
     }
-    ctx->beam_cache.last_action = cached.action == blok::BeamAction::Hit ? 2 : cached.action == blok::BeamAction::Fill ? 1 : 0;
-    ctx->beam_cache.last_slot = cached.slot; ctx->beam_cache.last_n_beams = n_beams;
-    ctx->beam_cache.last_fine = finer.use_fine ? 2 : finer.refine_now ? 1 : 0;
-    ctx->beam_cache.last_n_fine = ctx->beam_cache.last_fine ? blok::beam_refine_tiles(args) : 0u;
-    ctx->beam_cache.last_list = listed.use_list ? 2 : listed.count_now ? 1 : 0;
-    ctx->beam_cache.last_starts = starts.use == blok::BeamStarts::OtherKey ? 2 : (starts.use == blok::BeamStarts::Use || starts.count_own) ? 1 : 0;
-    if (starts.use == blok::BeamStarts::Use) ctx->beam_cache.start_hits += 1u;
-    if (starts.use == blok::BeamStarts::OtherKey) ctx->beam_cache.start_other_key += 1u;
-    ctx->beam_cache.last_w = args.w; ctx->beam_cache.last_h = args.h;
-    if (cached.action == blok::BeamAction::Hit && (listed.use_list || listed.count_now)) {
-        // The packed walk, or the launch that measures for it.  Neither uses the view's order or its live prefix (the table's order stands in
-        // for both; the count launch walks every wave tile in a workgroup of its own, so that every listed pixel gets its count): the fill
-        // waves write the misses of the empty beam tiles and of the empty wave tiles and walk nothing.
-        auto& B = ctx->beam_cache;
-        auto& sl = B.slots[cached.slot];
-        blok::TraceArgs fill = args;
-        fill.order = nullptr; fill.rank_of = nullptr; fill.launched = 0u; fill.order_sx = fill.order_sy = 0u; fill.n_strip = 0u; fill.fallback_tiles = nullptr;
-        fill.miss_in_walk = 0u;
-        // a list with groups: the fill rides in the walk's grid as fill units (blok_hip_set_packed_fill); an all-sky view has the fill alone
-        const bool one_launch = listed.use_list && sl.n_groups > 0u && B.packed_fill > 0u;
-        if (!one_launch) blok::launch_beam_fill(mode, fill, n_beams, sl.d_fine, stream);
-        if (one_launch) {
-            const bool from_nodes = blok::beam_nodes_use(B.policy, cached, starts) && sl.d_node;      // mode 5, and the slot's list has node words
-            const uint32_t tail = from_nodes ? blok::launch_packed_frame_node(fill, sl.d_start, sl.d_node, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream)
-                                  : starts.use == blok::BeamStarts::Use ? blok::launch_packed_frame_own(fill, sl.d_start, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream)
-                                                                        : blok::launch_packed_frame(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, B.packed_fill, stream);
-            B.one_launch_frames += 1u; B.fill_only_workgroups += tail;
-            if (from_nodes) B.node_hits += 1u;
-        } else if (listed.use_list && starts.use == blok::BeamStarts::Use) blok::launch_packed_walk_own(fill, sl.d_start, sl.d_list, sl.d_table, sl.n_groups, stream);
-        else if (listed.use_list) blok::launch_packed_walk(fill, sl.d_fine, sl.d_list, sl.d_table, sl.n_groups, stream);
-        else if (starts.count_own) {
-            // mode 4: the count launch also leaves every ray's own start and restarted trips; the build sorts by those and writes the starts in list order
-            blok::TraceArgs walk = fill;
-            walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
-            // mode 5: ... and the node every restarted walk ends in, gathered beside the starts
-            const bool with_nodes = blok::beam_nodes_count(B.policy, cached, starts);
-            blok::launch_trace_count_own(walk, blocks, B.d_trips, B.d_ray_start, B.d_restarts, with_nodes ? B.d_ray_node.get() : nullptr, stream);
-            sl.n_words = blok::pack_areas(args) * blok::kPackGroups; sl.n_groups = 0u;
-            if (with_nodes) blok::launch_pack_build_node(fill, sl.d_fine, B.d_restarts, B.d_ray_start, B.d_ray_node, sl.d_list, B.d_words, sl.d_start, sl.d_node, stream);
-            else blok::launch_pack_build_own(fill, sl.d_fine, B.d_restarts, B.d_ray_start, sl.d_list, B.d_words, sl.d_start, stream);
-        } else {
-            blok::TraceArgs walk = fill;
-            walk.beam = sl.d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
-            blok::launch_trace_count(walk, blocks, B.d_trips, stream);
-            // the build behind it: the areas' sorted stretches, then the table; its length goes to pinned memory in front of the event
-            sl.n_words = blok::pack_areas(args) * blok::kPackGroups; sl.n_groups = 0u;
-            blok::launch_pack_build(fill, sl.d_fine, B.d_trips, sl.d_list, B.d_words, stream);
-        }
-    } else if (cached.action == blok::BeamAction::Hit) {
-        // no searches: the walk over the view's live prefix, from the kept bounds; in front of it, what the search waves do besides searching
-        // (the miss pixels, unless the walk writes them; the wave tiles the prefix has no workgroup for) — last_launch_kind stays the policy's
-        float* const d_fine = ctx->beam_cache.slots[cached.slot].d_fine;
-        if (!args.miss_in_walk) blok::launch_beam_fill(mode, args, n_beams, finer.use_fine ? d_fine : nullptr, stream);
-        if (finer.use_fine) {
-            // the walk reads the finer bounds through the fields it has: a "beam tile" the size of a wave tile (the lookup in trace_block
-            // works for any tile size), so a wave tile that is empty by its own bound is not walked: its misses come from the walk
-            // (miss_in_walk) or from the fill wave of its beam tile, and its walk workgroup, while the order still has one, costs 0
-            blok::TraceArgs walk = args;
-            walk.beam = d_fine; walk.beam_tile = blok::kWaveW; walk.beam_bx = (args.w + blok::kWaveW - 1u) / blok::kWaveW;
-            blok::launch_trace(mode, walk, walk_blocks, stream);
-        } else blok::launch_trace(mode, args, walk_blocks, stream);
-        // the view's K-th hit: its finer searches behind its walk, once
-        if (finer.refine_now) blok::launch_beam_refine(args, d_fine, stream);
-    } else
+    uint32_t fill_only = 0u;
+    if (resting.walk != blok::RestingWalk::NotHit) fill_only = issue_resting(ctx, mode, args, resting, blocks, walk_blocks, n_beams, stream);      // last_launch_kind stays the policy's
+    else
     switch (plan.kind) {
         case blok::LaunchKind::Walk:
             if (frames) blok::launch_tile_frames(args, fr, stream); else blok::launch_trace(mode, args, blocks, stream);
@@ -694,31 +714,12 @@ int launch_timed(blok_hip_ctx* ctx, blok::RayMode mode, blok::TraceArgs args, ui
             blok::launch_list_walk(mode, args, frames ? &fr : nullptr, plan.walkers, stream);
             break;
     }
-    const hipError_t launch_error = hipGetLastError();
-    if (launch_error != hipSuccess && cached.action == blok::BeamAction::Fill) ctx->beam_cache.policy.valid[cached.slot] = false;      // bounds nobody wrote are nobody's to keep
-    if (finer.refine_now) {
-        auto& made = ctx->beam_cache.slots[cached.slot].refined;
-        const hipError_t marked = launch_error == hipSuccess ? hipEventRecord(made.done, stream) : launch_error;
-        blok::beam_refine_commit(ctx->beam_cache.policy, cached.slot, marked == hipSuccess);      // (bounds nobody can wait for are not used)
-        if (marked == hipSuccess) { made.settled = false; made.producer = stream; made.n_waited = 0; ctx->beam_cache.refines += 1u; }
-        else if (launch_error == hipSuccess) BLOK_HIP_TRY(ctx, marked);
-    }
-    if (listed.count_now) {
-        auto& B = ctx->beam_cache;
-        auto& sl = B.slots[cached.slot];
-        hipError_t built = launch_error;
-        if (built == hipSuccess) built = blok::launch_pack_table_sort(B.d_words, sl.d_table, B.d_sort_temp, B.sort_temp_bytes, sl.n_words, B.h_groups + cached.slot, stream);
-        if (built == hipSuccess) built = hipEventRecord(B.list_done, stream);
-        blok::beam_list_commit(B.policy, cached.slot, built == hipSuccess);      // (a list nobody can see finished is not used)
-        if (built == hipSuccess) B.list_builds += 1u;
-        else if (launch_error == hipSuccess) BLOK_HIP_TRY(ctx, built);
-    }
-    BLOK_HIP_TRY(ctx, launch_error);
-    if (cached.action == blok::BeamAction::Fill) BLOK_HIP_TRY(ctx, hipEventRecord(ctx->beam_cache.slots[cached.slot].filled.done, stream));
+    note_resting(ctx, resting, args, n_beams, fill_only);
+    { const int rc = finish_resting(ctx, resting, hipGetLastError(), stream); if (rc != BLOK_OK) return rc; }
     if (ctx->timing && !capturing) { BLOK_HIP_TRY(ctx, hipEventRecord(ctx->ev_end, stream)); ctx->timed = true; }
     if (args.fallback_tiles) BLOK_HIP_TRY(ctx, hipMemcpyAsync(ctx->order.h_fallback, ctx->order.d_fallback, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     // (a packed launch leaves no clocks: a re-sort behind it would sort what the last one sorted — the order keeps its state and is not re-made)
-    if (listed.use_list) order_plan.start_sort = false;
+    if (resting.list.use_list) order_plan.start_sort = false;
     if (orderable) { const int rc = order_after_launch(ctx, args, blocks, n_beams, stream, order_plan); if (rc != BLOK_OK) return rc; }
     if (facts.has_beam && !capturing) return note_frame_launch(ctx, stream);          // (behind the sort, if one was started: it belongs to this launch)
     return BLOK_OK;

@@ -249,5 +249,57 @@ inline bool beam_nodes_use(const BeamCachePolicy& s, const BeamCachePlan& p, con
     return plan.use == BeamStarts::Use && p.slot >= 0 && p.slot < kBeamCacheSlots && s.node_restart && s.nodes[p.slot];
 }
 
+// ---- one launch over the cache: the four plans above in their order, and what they come to ------------------------------------------------
+// What the policy cannot know itself.
+struct RestingFacts {
+    bool refine_eligible;                      // plan_beam_refine's `eligible`
+    bool list_eligible;                        // plan_beam_list's `eligible`
+    bool build_finished;                       // ... and its `build_finished` (asked only while s.building >= 0)
+    bool node_words;                           // a count launch can leave node words: the tree's node indices fit them, and every slot has somewhere to put them
+    BeamStartKey start_key;
+};
+// What a launch over the cache does: one value, computed here and acted on in one place (api_launch.hip: issue_resting).
+enum class RestingWalk : int {
+    NotHit = 0,                                // a search or a fill: the launch policy's form
+    Coarse,                                    // a hit: the live prefix from the beam tiles' bounds (fine.refine_now: the finer searches behind it)
+    Fine,                                      // ... from the finer bounds
+    Count,                                     // every wave tile from the finer bounds, counting trips; the build behind it
+    CountStarts,                               // ... leaving every ray's own start as well
+    CountNodes,                                // ... and its node word
+    PackedFine,                                // the list, from the finer bounds (a list without starts, or another start key)
+    PackedStarts,                              // the list, every ray from its own start
+    PackedNodes,                               // the list, every ray re-entered at its node
+};
+struct RestingPlan {
+    BeamCachePlan cache{BeamAction::Search, -1};
+    BeamRefinePlan fine{false, false};
+    BeamListPlan list{false, false, -1};
+    BeamStartsPlan starts{false, BeamStarts::None};
+    RestingWalk walk = RestingWalk::NotHit;
+};
+inline bool resting_counts(RestingWalk w) { return w == RestingWalk::Count || w == RestingWalk::CountStarts || w == RestingWalk::CountNodes; }
+inline bool resting_packed(RestingWalk w) { return w == RestingWalk::PackedFine || w == RestingWalk::PackedStarts || w == RestingWalk::PackedNodes; }
+
+inline RestingPlan plan_resting_launch(BeamCachePolicy& s, const BeamKey& k, const RestingFacts& facts) {
+    RestingPlan r;
+    r.cache = plan_beam_cache(s, k);
+    r.fine = plan_beam_refine(s, r.cache, facts.refine_eligible);
+    r.list = plan_beam_list(s, r.cache, r.fine, facts.list_eligible, facts.build_finished);
+    r.starts = plan_beam_starts(s, r.cache, r.list, facts.start_key);
+    if (beam_nodes_count(s, r.cache, r.starts) && !facts.node_words) beam_nodes_decline(s, r.cache.slot);      // the slot's list has starts alone, for good
+    if (r.cache.action != BeamAction::Hit) r.walk = RestingWalk::NotHit;
+    else if (r.list.use_list) r.walk = r.starts.use != BeamStarts::Use ? RestingWalk::PackedFine : beam_nodes_use(s, r.cache, r.starts) ? RestingWalk::PackedNodes : RestingWalk::PackedStarts;
+    else if (r.list.count_now) r.walk = !r.starts.count_own ? RestingWalk::Count : beam_nodes_count(s, r.cache, r.starts) ? RestingWalk::CountNodes : RestingWalk::CountStarts;
+    else r.walk = r.fine.use_fine ? RestingWalk::Fine : RestingWalk::Coarse;
+    return r;
+}
+
+// Behind the launch: what it was told to issue once has been issued (the finer searches and the event behind them; the build and its
+// event), or could not be — also a launch that failed before it issued anything.
+inline void commit_resting_launch(BeamCachePolicy& s, const RestingPlan& r, bool refine_issued, bool list_issued) {
+    if (r.fine.refine_now) beam_refine_commit(s, r.cache.slot, refine_issued);
+    if (r.list.count_now) beam_list_commit(s, r.cache.slot, list_issued);
+}
+
 }  // namespace blok
 #endif

@@ -310,7 +310,7 @@ void launch_beam_refine(const TraceArgs& args, float* fine, hipStream_t stream);
 // of the wave tiles with a finite finer bound — the pixels the walk is responsible for; none outside the rectangle — sorted by descending
 // trip count, stable in pixel order (wave tile by wave tile, row by row inside one), as 32-bit entries (x | y << 16, in the rectangle) in the area's stretch of kPackArea^2
 // entries of `list`, padded with kPackPad to whole groups of 64.  words[area * kPackGroups + g] = (the largest count of group g + 1) <<
-// kPackKeyShift | its index, 0 for a group without entries (tile_order.h sorts them into the table).  launch_packed_walk then walks one
+// kPackKeyShift | its index, 0 for a group without entries (tile_order.h sorts them into the table).  launch_packed then walks one
 // group per wave in table order: a lane reads its entry (a padding lane leaves), its start parameter from the finer bound of its pixel's
 // wave tile, and writes its record and pixel — the same bytes whichever wave a pixel is walked in.
 // The area is the builder's one constant.  64 pixels (scripts/packed_walk_estimate.py: 0.74 against 0.77 of today's wave trips in pose A,
@@ -327,40 +327,40 @@ constexpr uint32_t kPackKeyShift = 20u;                               // a table
 uint32_t pack_areas(const TraceArgs& args);                           // areas of the rectangle
 bool pack_applies(const TraceArgs& args);                             // the geometry fits the entries and the table's words
 void launch_trace_count(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, hipStream_t stream);      // Rect; args as for launch_trace
-void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* trips, uint32_t* list, uint32_t* words, hipStream_t stream);
-void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
 // The same with one start parameter per listed RAY (beam_cache.h: BeamStartKey).  The count launch leaves, beside a ray's trips, the ray
 // parameter at the top of its last trip — a hit's t, bit for bit; a miss's entry of the last cell it stood in — and the trips of the walk
 // from the root started there (`levels` for a hit, levels - that cell's level for a miss, 0 and the start it had for a ray that made no
 // trip), per pixel of the rectangle.  The build sorts by those restarted trips, and a second kernel writes every entry's start beside it, in list order
 // (slot_start: kPackStretch floats per area, like the list); the walk reads entry and start and never the finer bounds.  A walk of the
 // same ray from the root from that parameter reports what the counted walk did (trace_core.h: walk_loop), so the frame's bytes are the same
-// — for the counted rays only: another jitter or interval walks the same list with launch_packed_walk.
+// — for the counted rays only: another jitter or interval walks the same list from the finer bounds (PackedFrom::Fine).
 // node_words (mode 5, else null): the count launch also leaves, per pixel, the node that restarted walk ends in (trace_core.h: restart_node_word).
 void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, uint32_t* node_words, hipStream_t stream);
-void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream);
-void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream);
-// The packed frame in ONE launch: the two walks above, and in the same grid the miss pixels launch_beam_fill writes in front of them (with
-// the finer bounds and miss_in_walk 0: every pixel of the rectangle whose wave tile is empty by `fine`) as fill units (fill_units.h), at
-// most units_per_wave to a workgroup.  The walk is bound by vector issue and the fill by stores, and they touch disjoint pixels: in one
-// grid the stores drain beside the walk.  -> the workgroups that only fill (the grid's tail), 0 when every unit rides on a walk wave.
-// n_groups > 0 and units_per_wave >= 1; the same bytes as the two launches.
+// Mode 5: a listed ray re-enters at the node its restarted walk ends in.  The build's gather writes every entry's node word beside its start
+// (slot_node, kPackStretch words per area, like slot_start: two coalesced loads per entry in the frame), and the walk waves of
+// PackedFrom::Nodes make the walk's last trip alone (trace_core.h: walk_enter_node); a wave with a lane that trip does not settle walks as
+// PackedFrom::Starts'.  The same bytes — for the counted rays over the counted tree, as the starts.
+// node_words_apply: the tree's node indices fit a word beside the level (fewer than 2^29 nodes); else the view runs as mode 4.
+bool node_words_apply(size_t n_tree_nodes);
+// The build.  What a count launch left per pixel of the rectangle: the trips the build sorts by (with starts: the restarted trips), and,
+// or null, every ray's start and its node word (node words only beside starts) ...
+struct PackCounted { const uint8_t* trips; const float* starts; const uint32_t* node_words; };
+// ... and what the build writes: the list and the table's words; per entry, where the count left them, its start and its node word.
+struct PackBuilt { uint32_t* list; uint32_t* words; float* slot_start; uint32_t* slot_node; };
+void launch_pack_build(const TraceArgs& args, const float* fine, const PackCounted& in, const PackBuilt& out, hipStream_t stream);
+// A slot's list as its walks read it, and where a listed ray starts.
+struct PackedList { const float* fine; const uint32_t* list; const uint32_t* table; const float* slot_start; const uint32_t* slot_node; uint32_t n_groups; };
+enum class PackedFrom { Fine, Starts, Nodes };
+// The packed walk of `view`, one launch; nothing for a list without groups.  units_per_wave 0: the walk alone, n_groups workgroups, behind
+// a launch_beam_fill (from the nodes: as from the starts) -> 0.  Else the packed frame in ONE launch: the same walks, and in the same grid
+// the miss pixels launch_beam_fill writes in front of them (with the finer bounds and miss_in_walk 0: every pixel of the rectangle whose
+// wave tile is empty by `fine`) as fill units (fill_units.h), at most units_per_wave to a workgroup.  The walk is bound by vector issue
+// and the fill by stores, and they touch disjoint pixels: in one grid the stores drain beside the walk.  -> the workgroups that only fill
+// (the grid's tail), 0 when every unit rides on a walk wave.  The same bytes as the two launches.
 #ifndef BLOK_PACKED_FILL
 #define BLOK_PACKED_FILL 4             // the library's default units_per_wave (blok_hip_set_packed_fill; 0: two launches): profiles/packed_fill_ab.txt
 #endif
-uint32_t launch_packed_frame(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream);
-uint32_t launch_packed_frame_own(const TraceArgs& args, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave,
-                                 hipStream_t stream);
-// Mode 5: a listed ray re-enters at the node its restarted walk ends in.  The build's gather writes every entry's node word beside its start
-// (slot_node, kPackStretch words per area, like slot_start: two coalesced loads per entry in the frame), and launch_packed_frame_node is
-// launch_packed_frame_own whose walk waves make the walk's last trip alone (trace_core.h: walk_enter_node); a wave with a lane that trip
-// does not settle walks as launch_packed_frame_own's.  The same bytes — for the counted rays over the counted tree, as the starts.
-// node_words_apply: the tree's node indices fit a word beside the level (fewer than 2^29 nodes); else the view runs as mode 4.
-bool node_words_apply(size_t n_tree_nodes);
-void launch_pack_build_node(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, const uint32_t* node_words, uint32_t* list, uint32_t* words,
-                            float* slot_start, uint32_t* slot_node, hipStream_t stream);
-uint32_t launch_packed_frame_node(const TraceArgs& args, const float* slot_start, const uint32_t* slot_node, const float* fine, const uint32_t* list, const uint32_t* table,
-                                  uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream);
+uint32_t launch_packed(const TraceArgs& args, const PackedList& view, PackedFrom from, uint32_t units_per_wave, hipStream_t stream);
 void launch_untile(const UntileArgs& args, uint32_t n_frames, hipStream_t stream);
 // Beam pre-pass (if args.beam) and walk of frames.n_frames frames of the rank's tiles, one launch each (Tiles mode).
 void launch_tile_frames(const TraceArgs& args, const TileFrames& frames, hipStream_t stream, uint32_t walk_blocks_per_frame = 0);

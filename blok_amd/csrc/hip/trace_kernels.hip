@@ -630,63 +630,42 @@ __global__ __launch_bounds__(kPackThreads) void pack_build_kernel(const uint8_t*
 // Behind a build over the rays' RESTARTED trips (the same kernel: at most `levels`, so nearly all keys are equal, the stable order is the
 // pixel order and a group is mostly whole wave tiles): every entry's restart parameter, from starts[its pixel] to slot_start[its place in
 // the list].  A thread per entry of every stretch; an entry beyond a stretch's padding is whatever an earlier build left, hence the bounds.
-__global__ __launch_bounds__(256) void pack_starts_kernel(const uint32_t* list, const float* starts, const uint32_t w, const uint32_t h, const uint32_t n_entries, float* slot_start) {
+// With node words (mode 5; else both null, the same for every thread) every entry's word beside its start, one launch for both:
+// slot_node[i] from node_words[its pixel].  An entry's start and its node word are two arrays in list order — two coalesced loads in the
+// frame, like the entry itself — so that the starts stay what mode 4 and the read-backs know.
+__global__ __launch_bounds__(256) void pack_starts_kernel(const uint32_t* list, const float* starts, const uint32_t* node_words, const uint32_t w, const uint32_t h,
+                                                          const uint32_t n_entries, float* slot_start, uint32_t* slot_node) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_entries) return;
     const uint32_t entry = list[i], rx = entry & 0xFFFFu, ry = entry >> 16;
     if (entry == kPackPad || rx >= w || ry >= h) return;
     slot_start[i] = starts[static_cast<size_t>(ry) * w + rx];
+    if (slot_node) slot_node[i] = node_words[static_cast<size_t>(ry) * w + rx];
 }
 
-// The same with every entry's node word beside its start (mode 5), one launch for both: slot_node[i] from node_words[its pixel].  An
-// entry's start and its node word are two arrays in list order — two coalesced loads in the frame, like the entry itself — so that the starts
-// stay what mode 4 and the read-backs know.
-__global__ __launch_bounds__(256) void pack_starts_nodes_kernel(const uint32_t* list, const float* starts, const uint32_t* node_words, const uint32_t w, const uint32_t h,
-                                                                const uint32_t n_entries, float* slot_start, uint32_t* slot_node) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_entries) return;
-    const uint32_t entry = list[i], rx = entry & 0xFFFFu, ry = entry >> 16;
-    if (entry == kPackPad || rx >= w || ry >= h) return;
-    slot_start[i] = starts[static_cast<size_t>(ry) * w + rx];
-    slot_node[i] = node_words[static_cast<size_t>(ry) * w + rx];
-}
-
-// One wave per group of the list, heaviest first.  Nothing here is collective before a padding lane has left.
-__global__ __launch_bounds__(kBlock) void packed_walk_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table) {
-    static_assert(kBlock == 64, "one wave per group");
-    extern __shared__ uint4 lds_stack[];
-    const uint32_t lane = threadIdx.x;
+// This wave walks its group of the list: one wave per group, heaviest first.  Nothing here is collective before a padding lane has left.
+// From the finer bound of every listed pixel's wave tile (PackedFrom::Fine: start = the view's finer bounds), or from every listed ray's
+// OWN start (Starts: start = slot_start, in list order, an entry and its start are two coalesced loads): the parameter at which the counted
+// walk of this very ray entered the cell its answer lies in, never below its wave tile's bound, so that is not read.  That walk goes from
+// the root to that cell and reports or leaves: `levels` trips for a hit.  Only for a launch whose rays ARE the counted ones (beam_cache.h:
+// BeamStartKey).
+template <PackedFrom FROM>
+__device__ __forceinline__ void packed_walk_group(const TraceArgs& A, const float* start, const uint32_t* list, const uint32_t* table, uint4* lds_stack, const uint32_t lane) {
+    static_assert(kBlock == 64 && FROM != PackedFrom::Nodes, "one wave per group; the walk from the nodes has a body of its own");
     const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
     const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
+    float t0 = 0.0f;
+    if constexpr (FROM == PackedFrom::Starts) t0 = start[static_cast<size_t>(group) * 64u + lane];
     const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
     if (entry == kPackPad || rx >= A.w || ry >= A.h) return;          // (the build lists pixels of the rectangle only)
-    const float t0 = fine[(ry / kWaveH) * ((A.w + kWaveW - 1u) / kWaveW) + rx / kWaveW];
+    if constexpr (FROM == PackedFrom::Fine) t0 = start[(ry / kWaveH) * ((A.w + kWaveW - 1u) / kWaveW) + rx / kWaveW];
     const size_t at = static_cast<size_t>(ry) * A.w + rx;
     RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
     r.tmin = fmaxf(r.tmin, t0);
     trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
 }
 
-// The same from every listed ray's OWN start (slot_start, in list order: an entry and its start are two coalesced loads): the parameter at
-// which the counted walk of this very ray entered the cell its answer lies in — never below its wave tile's bound, so that is not read.
-// The walk goes from the root to that cell and reports or leaves: `levels` trips for a hit.  Only for a launch whose rays ARE the counted
-// ones (beam_cache.h: BeamStartKey).
-__global__ __launch_bounds__(kBlock) void packed_walk_own_kernel(const TraceArgs A, const float* slot_start, const uint32_t* list, const uint32_t* table) {
-    static_assert(kBlock == 64, "one wave per group");
-    extern __shared__ uint4 lds_stack[];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
-    const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
-    const float t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
-    const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
-    if (entry == kPackPad || rx >= A.w || ry >= A.h) return;
-    const size_t at = static_cast<size_t>(ry) * A.w + rx;
-    RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
-    r.tmin = fmaxf(r.tmin, t0);
-    trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
-}
-
-// ---- the packed frame in one launch (trace_kernels.h: launch_packed_frame; fill_units.h) -------------------------------------------------------
+// ---- the packed frame in one launch (trace_kernels.h: launch_packed; fill_units.h) -------------------------------------------------------------
 // The fill units of this workgroup: lane l of a unit owns one pixel of the rectangle and writes its miss iff the pixel's wave tile is
 // empty by the finer bounds — what beam_fill_kernel writes in front of a packed walk, and the complement of what pack_build_kernel lists.
 // A wave's stores of a unit are whole octets of one row: 128 B of records and 32 B of RGBA8 each, up to 1 KB and 256 B contiguous.
@@ -752,49 +731,41 @@ __device__ __forceinline__ void fill_units_of_workgroup(const TraceArgs& A, cons
     fill_units_of_workgroup(A, fill_batch_load(A, fine, n_units, units_x, 0u), fine, n_units, units_x);
 }
 
-// packed_walk_kernel's walk for the workgroups [0, n_groups), in the table's order, and every workgroup's fill units: those of the grid's
+// A workgroup of a packed launch.  FILL false: the walk alone, a workgroup per group.  FILL true (the packed frame in one launch):
+// packed_walk_group's walk for the workgroups [0, n_groups), in the table's order, and every workgroup's fill units: those of the grid's
 // tail [n_groups, gridDim.x) write units and nothing else.  A padding lane of a group does not leave before its units are written.
-__global__ __launch_bounds__(kBlock) void packed_frame_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table, const uint32_t n_groups,
-                                                              const uint32_t n_units, const uint32_t units_x) {
-    static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
-    extern __shared__ uint4 lds_stack[];
+// The four kernels below reach packed_walk_group through this body, the two that only walk too: with the walk inlined through these two
+// levels the compiler emits, for all four, the instructions of the bodies written out in each kernel (scripts/isa_same.py); with the walk
+// one level below a kernel it orders a hit's record differently.  The lane is read here, in front of the walk and the units alike.
+template <PackedFrom FROM, bool FILL>
+__device__ __forceinline__ void packed_workgroup(const TraceArgs& A, const float* start, const float* fine, const uint32_t* list, const uint32_t* table, const uint32_t n_groups,
+                                                 const uint32_t n_units, const uint32_t units_x, uint4* lds_stack) {
     const uint32_t lane = threadIdx.x;
-    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
-    if (blockIdx.x < n_groups) {
-        const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
-        const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
-        const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
-        if (entry != kPackPad && rx < A.w && ry < A.h) {
-            const float t0 = fine[(ry / kWaveH) * ((A.w + kWaveW - 1u) / kWaveW) + rx / kWaveW];
-            const size_t at = static_cast<size_t>(ry) * A.w + rx;
-            RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
-            r.tmin = fmaxf(r.tmin, t0);
-            trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
-        }
-    }
-    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    if constexpr (FILL && BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    if (!FILL || blockIdx.x < n_groups) packed_walk_group<FROM>(A, start, list, table, lds_stack, lane);
+    if constexpr (FILL && BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
 }
 
-// The same over packed_walk_own_kernel's walk, every listed ray from its own start.
+__global__ __launch_bounds__(kBlock) void packed_walk_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table) {
+    extern __shared__ uint4 lds_stack[];
+    packed_workgroup<PackedFrom::Fine, false>(A, fine, nullptr, list, table, 0u, 0u, 0u, lds_stack);
+}
+
+__global__ __launch_bounds__(kBlock) void packed_walk_own_kernel(const TraceArgs A, const float* slot_start, const uint32_t* list, const uint32_t* table) {
+    extern __shared__ uint4 lds_stack[];
+    packed_workgroup<PackedFrom::Starts, false>(A, slot_start, nullptr, list, table, 0u, 0u, 0u, lds_stack);
+}
+
+__global__ __launch_bounds__(kBlock) void packed_frame_kernel(const TraceArgs A, const float* fine, const uint32_t* list, const uint32_t* table, const uint32_t n_groups,
+                                                              const uint32_t n_units, const uint32_t units_x) {
+    extern __shared__ uint4 lds_stack[];
+    packed_workgroup<PackedFrom::Fine, true>(A, fine, fine, list, table, n_groups, n_units, units_x, lds_stack);
+}
+
 __global__ __launch_bounds__(kBlock) void packed_frame_own_kernel(const TraceArgs A, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table,
                                                                   const uint32_t n_groups, const uint32_t n_units, const uint32_t units_x) {
-    static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
     extern __shared__ uint4 lds_stack[];
-    const uint32_t lane = threadIdx.x;
-    if constexpr (BLOK_PACKED_FILL_FIRST != 0) fill_units_of_workgroup(A, fine, n_units, units_x);
-    if (blockIdx.x < n_groups) {
-        const uint32_t group = __builtin_amdgcn_readfirstlane(table[blockIdx.x]) & ((1u << kPackKeyShift) - 1u);
-        const uint32_t entry = list[static_cast<size_t>(group) * 64u + lane];
-        const float t0 = slot_start[static_cast<size_t>(group) * 64u + lane];
-        const uint32_t rx = entry & 0xFFFFu, ry = entry >> 16;
-        if (entry != kPackPad && rx < A.w && ry < A.h) {
-            const size_t at = static_cast<size_t>(ry) * A.w + rx;
-            RayIn r = primary_ray(A, A.x0 + rx, A.y0 + ry);
-            r.tmin = fmaxf(r.tmin, t0);
-            trace_one<true>(A, r, lds_stack + lane, Sink{A.out ? A.out + at : nullptr, A.out_rgba ? A.out_rgba + at : nullptr});
-        }
-    }
-    if constexpr (BLOK_PACKED_FILL_FIRST == 0) fill_units_of_workgroup(A, fine, n_units, units_x);
+    packed_workgroup<PackedFrom::Starts, true>(A, slot_start, fine, list, table, n_groups, n_units, units_x, lds_stack);
 }
 
 // The same with every listed ray re-entered at the node its restarted walk ends in (slot_node, in list order beside slot_start; trace_core.h:
@@ -807,7 +778,7 @@ __global__ __launch_bounds__(kBlock) void packed_frame_node_kernel(const TraceAr
     static_assert(kBlock == 64, "one wave per group, one lane per pixel of a unit");
     extern __shared__ uint4 lds_stack[];
     const uint32_t lane = threadIdx.x;
-    const uint32_t table_word = table[blockIdx.x < n_groups ? blockIdx.x : 0u];      // (n_groups > 0: launch_packed_frame_node)
+    const uint32_t table_word = table[blockIdx.x < n_groups ? blockIdx.x : 0u];      // (n_groups > 0: launch_packed)
     // A workgroup of the grid's tail writes its units and ends: it shares no block with the walk's, so that no path of the walk reaches a
     // store with a load of another path still counted against it.
     if (blockIdx.x >= n_groups) { fill_units_of_workgroup(A, fine, n_units, units_x); return; }
@@ -1700,11 +1671,6 @@ void launch_trace_count(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips
     hipLaunchKernelGGL(trace_count_kernel, dim3(n_blocks), dim3(kBlock), frame_lds_bytes(args), stream, args, trips);
 }
 
-void launch_pack_build(const TraceArgs& args, const float* fine, const uint8_t* trips, uint32_t* list, uint32_t* words, hipStream_t stream) {
-    if (!pack_applies(args) || !fine || !trips || !list || !words) return;
-    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, trips, fine, args.w, args.h, list, words);
-}
-
 void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* trips, float* starts, uint8_t* restarts, uint32_t* node_words, hipStream_t stream) {
     if (n_blocks == 0 || !trips || !starts || !restarts) return;
     hipLaunchKernelGGL(trace_count_own_kernel, dim3(n_blocks), dim3(kBlock), frame_lds_bytes(args), stream, args, trips, starts, restarts, node_words);
@@ -1712,52 +1678,31 @@ void launch_trace_count_own(const TraceArgs& args, uint32_t n_blocks, uint8_t* t
 
 bool node_words_apply(size_t n_tree_nodes) { return n_tree_nodes != 0 && n_tree_nodes <= static_cast<size_t>(kNodeWordIndexMask); }
 
-void launch_pack_build_node(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, const uint32_t* node_words, uint32_t* list, uint32_t* words,
-                            float* slot_start, uint32_t* slot_node, hipStream_t stream) {
-    if (!pack_applies(args) || !fine || !restarts || !starts || !node_words || !list || !words || !slot_start || !slot_node) return;
-    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, restarts, fine, args.w, args.h, list, words);
+void launch_pack_build(const TraceArgs& args, const float* fine, const PackCounted& in, const PackBuilt& out, hipStream_t stream) {
+    if (!pack_applies(args) || !fine || !in.trips || !out.list || !out.words || (in.starts && !out.slot_start) || (in.node_words && (!in.starts || !out.slot_node))) return;
+    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, in.trips, fine, args.w, args.h, out.list, out.words);
+    if (!in.starts) return;
     const uint32_t n_entries = pack_areas(args) * kPackStretch;
-    hipLaunchKernelGGL(pack_starts_nodes_kernel, dim3((n_entries + 255u) / 256u), dim3(256), 0, stream, list, starts, node_words, args.w, args.h, n_entries, slot_start, slot_node);
+    hipLaunchKernelGGL(pack_starts_kernel, dim3((n_entries + 255u) / 256u), dim3(256), 0, stream, out.list, in.starts, in.node_words, args.w, args.h, n_entries, out.slot_start,
+                       in.node_words ? out.slot_node : nullptr);
 }
 
-void launch_pack_build_own(const TraceArgs& args, const float* fine, const uint8_t* restarts, const float* starts, uint32_t* list, uint32_t* words, float* slot_start, hipStream_t stream) {
-    if (!pack_applies(args) || !fine || !restarts || !starts || !list || !words || !slot_start) return;
-    hipLaunchKernelGGL(pack_build_kernel, dim3(pack_areas(args)), dim3(kPackThreads), 0, stream, restarts, fine, args.w, args.h, list, words);
-    const uint32_t n_entries = pack_areas(args) * kPackStretch;
-    hipLaunchKernelGGL(pack_starts_kernel, dim3((n_entries + 255u) / 256u), dim3(256), 0, stream, list, starts, args.w, args.h, n_entries, slot_start);
-}
-
-void launch_packed_walk_own(const TraceArgs& args, const float* slot_start, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream) {
-    if (n_groups == 0 || !pack_applies(args) || !slot_start || !list || !table) return;
-    hipLaunchKernelGGL(packed_walk_own_kernel, dim3(n_groups), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, list, table);
-}
-
-void launch_packed_walk(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, hipStream_t stream) {
-    if (n_groups == 0 || !pack_applies(args) || !fine || !list || !table) return;
-    hipLaunchKernelGGL(packed_walk_kernel, dim3(n_groups), dim3(kBlock), frame_lds_bytes(args), stream, args, fine, list, table);
-}
-
-uint32_t launch_packed_frame(const TraceArgs& args, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream) {
-    if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !fine || !list || !table) return 0u;
-    const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
-    hipLaunchKernelGGL(packed_frame_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, fine, list, table, n_groups, g.n_units, g.units_x);
-    return g.grid - n_groups;
-}
-
-uint32_t launch_packed_frame_own(const TraceArgs& args, const float* slot_start, const float* fine, const uint32_t* list, const uint32_t* table, uint32_t n_groups, uint32_t units_per_wave,
-                                 hipStream_t stream) {
-    if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !slot_start || !fine || !list || !table) return 0u;
-    const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
-    hipLaunchKernelGGL(packed_frame_own_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, fine, list, table, n_groups, g.n_units, g.units_x);
-    return g.grid - n_groups;
-}
-
-uint32_t launch_packed_frame_node(const TraceArgs& args, const float* slot_start, const uint32_t* slot_node, const float* fine, const uint32_t* list, const uint32_t* table,
-                                  uint32_t n_groups, uint32_t units_per_wave, hipStream_t stream) {
-    if (n_groups == 0 || units_per_wave == 0 || !pack_applies(args) || !slot_start || !slot_node || !fine || !list || !table) return 0u;
-    const FillGrid g = fill_grid(args.w, args.h, n_groups, units_per_wave);
-    hipLaunchKernelGGL(packed_frame_node_kernel, dim3(g.grid), dim3(kBlock), frame_lds_bytes(args), stream, args, slot_start, slot_node, fine, list, table, n_groups, g.n_units, g.units_x);
-    return g.grid - n_groups;
+uint32_t launch_packed(const TraceArgs& args, const PackedList& v, PackedFrom from, uint32_t units_per_wave, hipStream_t stream) {
+    if (units_per_wave == 0 && from == PackedFrom::Nodes) from = PackedFrom::Starts;
+    if (v.n_groups == 0 || !pack_applies(args) || !v.list || !v.table || (!v.fine && (units_per_wave || from == PackedFrom::Fine)) || (!v.slot_start && from != PackedFrom::Fine) ||
+        (!v.slot_node && from == PackedFrom::Nodes)) return 0u;
+    const size_t lds = frame_lds_bytes(args);
+    if (units_per_wave == 0) {
+        if (from == PackedFrom::Fine) hipLaunchKernelGGL(packed_walk_kernel, dim3(v.n_groups), dim3(kBlock), lds, stream, args, v.fine, v.list, v.table);
+        else hipLaunchKernelGGL(packed_walk_own_kernel, dim3(v.n_groups), dim3(kBlock), lds, stream, args, v.slot_start, v.list, v.table);
+        return 0u;
+    }
+    const FillGrid g = fill_grid(args.w, args.h, v.n_groups, units_per_wave);
+    if (from == PackedFrom::Fine) hipLaunchKernelGGL(packed_frame_kernel, dim3(g.grid), dim3(kBlock), lds, stream, args, v.fine, v.list, v.table, v.n_groups, g.n_units, g.units_x);
+    else if (from == PackedFrom::Starts)
+        hipLaunchKernelGGL(packed_frame_own_kernel, dim3(g.grid), dim3(kBlock), lds, stream, args, v.slot_start, v.fine, v.list, v.table, v.n_groups, g.n_units, g.units_x);
+    else hipLaunchKernelGGL(packed_frame_node_kernel, dim3(g.grid), dim3(kBlock), lds, stream, args, v.slot_start, v.slot_node, v.fine, v.list, v.table, v.n_groups, g.n_units, g.units_x);
+    return g.grid - v.n_groups;
 }
 
 size_t frame_lds_bytes(const TraceArgs& args) { return static_cast<size_t>(args.levels > 1 ? args.levels - 1 : 1) * kBlock * sizeof(uint4); }

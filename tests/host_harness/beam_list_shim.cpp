@@ -14,20 +14,17 @@ void beam_list_set_after(void* s, unsigned n) { static_cast<blok::BeamCachePolic
 unsigned beam_list_after(void* s) { return static_cast<blok::BeamCachePolicy*>(s)->list_after; }
 int beam_list_state(void* s, int slot) { return static_cast<int>(static_cast<blok::BeamCachePolicy*>(s)->list[slot]); }
 int beam_list_building(void* s) { const auto& p = *static_cast<blok::BeamCachePolicy*>(s); return p.building < 0 ? -1 : p.building | (p.building_stale ? 256 : 0); }
-// One launch, as api_launch.hip asks: plan_beam_cache, plan_beam_refine (K = 1, always issued), plan_beam_list with what the event query
-// said, then (issued >= 0) beam_list_commit for a launch told to count.
+// One launch, as api_launch.hip asks: plan_resting_launch (K = 1) with what the event query said, then commit_resting_launch: the finer
+// searches always issued, the build as `issued` says (< 0: no commit for a launch told to count).
 // -> action (0 search, 1 fill, 2 hit) | refine_now << 4 | use_fine << 5 | count_now << 6 | use_list << 7 | (adopted slot + 1) << 8; the slot through the pointer.
 int beam_list_launch(void* sp, const uint32_t* key, int eligible, int build_finished, int issued, int* slot) {
     auto& s = *static_cast<blok::BeamCachePolicy*>(sp);
     blok::BeamKey k;
     memcpy(&k, key, sizeof(k));
-    const blok::BeamCachePlan p = blok::plan_beam_cache(s, k);
-    const blok::BeamRefinePlan f = blok::plan_beam_refine(s, p, true);
-    if (f.refine_now) blok::beam_refine_commit(s, p.slot, true);
-    const blok::BeamListPlan l = blok::plan_beam_list(s, p, f, eligible != 0, build_finished != 0);
-    if (l.count_now && issued >= 0) blok::beam_list_commit(s, p.slot, issued != 0);
-    *slot = p.slot;
-    return static_cast<int>(p.action) | (f.refine_now ? 16 : 0) | (f.use_fine ? 32 : 0) | (l.count_now ? 64 : 0) | (l.use_list ? 128 : 0) | ((l.adopted + 1) << 8);
+    const blok::RestingPlan r = blok::plan_resting_launch(s, k, {true, eligible != 0, build_finished != 0, false, {}});
+    if (!r.list.count_now || issued >= 0) blok::commit_resting_launch(s, r, true, issued != 0);
+    *slot = r.cache.slot;
+    return static_cast<int>(r.cache.action) | (r.fine.refine_now ? 16 : 0) | (r.fine.use_fine ? 32 : 0) | (r.list.count_now ? 64 : 0) | (r.list.use_list ? 128 : 0) | ((r.list.adopted + 1) << 8);
 }
 }
 

@@ -12,17 +12,16 @@ void beam_refine_reset(void* s) { blok::beam_cache_clear(*static_cast<blok::Beam
 void beam_refine_set_after(void* s, unsigned k) { static_cast<blok::BeamCachePolicy*>(s)->refine_after = k; }
 unsigned beam_refine_after(void* s) { return static_cast<blok::BeamCachePolicy*>(s)->refine_after; }
 int beam_refine_state(void* s, int slot) { return static_cast<int>(static_cast<blok::BeamCachePolicy*>(s)->refine[slot]); }
-// One launch, as api_launch.hip asks: plan_beam_cache, then plan_beam_refine, then (issued >= 0) beam_refine_commit for a launch told to
-// refine.  -> action (0 search, 1 fill, 2 hit) | refine_now << 4 | use_fine << 5; the slot through the pointer.
+// One launch, as api_launch.hip asks: plan_resting_launch (no packed walk), then (issued >= 0) commit_resting_launch.
+// -> action (0 search, 1 fill, 2 hit) | refine_now << 4 | use_fine << 5; the slot through the pointer.
 int beam_refine_launch(void* sp, const uint32_t* key, int eligible, int issued, int* slot) {
     auto& s = *static_cast<blok::BeamCachePolicy*>(sp);
     blok::BeamKey k;
     memcpy(&k, key, sizeof(k));
-    const blok::BeamCachePlan p = blok::plan_beam_cache(s, k);
-    const blok::BeamRefinePlan f = blok::plan_beam_refine(s, p, eligible != 0);
-    if (f.refine_now && issued >= 0) blok::beam_refine_commit(s, p.slot, issued != 0);
-    *slot = p.slot;
-    return static_cast<int>(p.action) | (f.refine_now ? 16 : 0) | (f.use_fine ? 32 : 0);
+    const blok::RestingPlan r = blok::plan_resting_launch(s, k, {eligible != 0, false, false, false, {}});
+    if (issued >= 0) blok::commit_resting_launch(s, r, issued != 0, false);
+    *slot = r.cache.slot;
+    return static_cast<int>(r.cache.action) | (r.fine.refine_now ? 16 : 0) | (r.fine.use_fine ? 32 : 0);
 }
 }
 

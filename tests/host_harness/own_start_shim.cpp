@@ -14,9 +14,9 @@ void own_start_set_mode(void* s, int own) { static_cast<blok::BeamCachePolicy*>(
 int own_start_mode(void* s) { return static_cast<blok::BeamCachePolicy*>(s)->own_starts ? 1 : 0; }
 int own_start_list_state(void* s, int slot) { return static_cast<int>(static_cast<blok::BeamCachePolicy*>(s)->list[slot]); }
 int own_start_has(void* s, int slot) { return static_cast<blok::BeamCachePolicy*>(s)->starts[slot] ? 1 : 0; }
-// One launch, as api_launch.hip asks: plan_beam_cache, plan_beam_refine (K = 1, always issued), plan_beam_list with what the event query
-// said, plan_beam_starts with the launch's start key (jitter x, jitter y, tmin, tmax as bits), then (issued >= 0) beam_list_commit for a
-// launch told to count.
+// One launch, as api_launch.hip asks: plan_resting_launch (K = 1) with what the event query said and the launch's start key (jitter x,
+// jitter y, tmin, tmax as bits), then commit_resting_launch: the finer searches always issued, the build as `issued` says (< 0: no commit
+// for a launch told to count).
 // -> action (0 search, 1 fill, 2 hit) | count_now << 6 | use_list << 7 | count_own << 8 | use (0 none, 1 from the starts, 2 another key) << 9; the slot through the pointer.
 int own_start_launch(void* sp, const uint32_t* key, const uint32_t* start_key, int build_finished, int issued, int* slot) {
     auto& s = *static_cast<blok::BeamCachePolicy*>(sp);
@@ -24,14 +24,10 @@ int own_start_launch(void* sp, const uint32_t* key, const uint32_t* start_key, i
     memcpy(&k, key, sizeof(k));
     blok::BeamStartKey sk;
     memcpy(&sk, start_key, sizeof(sk));
-    const blok::BeamCachePlan p = blok::plan_beam_cache(s, k);
-    const blok::BeamRefinePlan f = blok::plan_beam_refine(s, p, true);
-    if (f.refine_now) blok::beam_refine_commit(s, p.slot, true);
-    const blok::BeamListPlan l = blok::plan_beam_list(s, p, f, true, build_finished != 0);
-    const blok::BeamStartsPlan o = blok::plan_beam_starts(s, p, l, sk);
-    if (l.count_now && issued >= 0) blok::beam_list_commit(s, p.slot, issued != 0);
-    *slot = p.slot;
-    return static_cast<int>(p.action) | (l.count_now ? 64 : 0) | (l.use_list ? 128 : 0) | (o.count_own ? 256 : 0) | (static_cast<int>(o.use) << 9);
+    const blok::RestingPlan r = blok::plan_resting_launch(s, k, {true, true, build_finished != 0, true, sk});
+    if (!r.list.count_now || issued >= 0) blok::commit_resting_launch(s, r, true, issued != 0);
+    *slot = r.cache.slot;
+    return static_cast<int>(r.cache.action) | (r.list.count_now ? 64 : 0) | (r.list.use_list ? 128 : 0) | (r.starts.count_own ? 256 : 0) | (static_cast<int>(r.starts.use) << 9);
 }
 }
 
