@@ -60,6 +60,12 @@ assert LIGHT.itemsize == 32 and LIGHTS_INFO.itemsize == 32
 # = blok_instance_lights_info (32 bytes): the header of an instance table's light prefix
 INSTANCE_LIGHTS_INFO = np.dtype([("a_inst", "<u8"), ("a_total", "<u8"), ("area_world", "<f4"), ("n_lit", "<u4"), ("disabled", "<u4"), ("reserved", "<u4")])
 assert INSTANCE_LIGHTS_INFO.itemsize == 32
+# = blok_light_grid_item (8 bytes): a list entry of the light grid; = blok_light_grid_info (72 bytes): what a grid holds
+LIGHT_GRID_ITEM = np.dtype([("light", "<u4"), ("lcum", "<u4")])
+LIGHT_GRID_INFO = np.dtype([("cell_lo", "<i4", 3), ("dim", "<u4", 3), ("cell_log2", "<u4"), ("reach", "<u4"), ("share", "<u4"), ("n_nonempty", "<u4"),
+                            ("n_cells", "<u8"), ("n_items", "<u8"), ("bytes", "<u8"), ("max_items", "<u4"), ("reserved", "<u4")])
+assert LIGHT_GRID_ITEM.itemsize == 8 and LIGHT_GRID_INFO.itemsize == 72
+LIGHT_GRID_START, LIGHT_GRID_FACES, LIGHT_GRID_ITEMS = 0, 1, 2      # blok_hip_light_grid_download's `what`
 STAMP_SET, STAMP_KEEP, STAMP_ERASE = 0, 1, 2      # = BLOK_STAMP_*
 CAPTURE_CUT = 1                                   # = BLOK_CAPTURE_CUT
 # = blok_component: one connected component of a labelled region, 40 bytes
@@ -266,6 +272,7 @@ HOST_SYMBOLS = {
     "blok_lights_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
     "blok_model_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]),
     "blok_instance_light_record": (None, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blok_light_grid_build": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "blok_stamp_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),
     "blok_capture_voxels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
@@ -455,6 +462,10 @@ HIP_SYMBOLS = {
     "blok_hip_set_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_hip_lights_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "blok_hip_lights_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_build_light_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "blok_hip_light_grid_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "blok_hip_light_grid_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "blok_hip_light_grid_clear": (C.c_int, [C.c_void_p]),
     "blok_hip_model_lights": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "blok_hip_model_lights_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "blok_hip_model_lights_download": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64]),

@@ -10,7 +10,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 INCLUDE = ROOT / "include"
 
-HOST_SRC = [PKG / "csrc/host/world.cpp", PKG / "csrc/host/scene.cpp", PKG / "csrc/host/vox.cpp", PKG / "csrc/host/obj.cpp", PKG / "csrc/host/terrain.cpp", PKG / "csrc/host/quads.cpp", PKG / "csrc/host/stamp.cpp", PKG / "csrc/host/components.cpp", PKG / "csrc/host/sweep.cpp", PKG / "csrc/host/bricks.cpp", PKG / "csrc/host/distance.cpp", PKG / "csrc/host/flood.cpp", PKG / "csrc/host/columns.cpp", PKG / "csrc/host/scroll.cpp", PKG / "csrc/host/shapes.cpp", PKG / "csrc/host/lod.cpp", PKG / "csrc/host/affine.cpp", PKG / "csrc/host/automaton.cpp", PKG / "csrc/host/pose.cpp", PKG / "csrc/host/lights.cpp", PKG / "csrc/host/model_lights.cpp", PKG / "csrc/hip/tree_build.cpp"]
+HOST_SRC = [PKG / "csrc/host/world.cpp", PKG / "csrc/host/scene.cpp", PKG / "csrc/host/vox.cpp", PKG / "csrc/host/obj.cpp", PKG / "csrc/host/terrain.cpp", PKG / "csrc/host/quads.cpp", PKG / "csrc/host/stamp.cpp", PKG / "csrc/host/components.cpp", PKG / "csrc/host/sweep.cpp", PKG / "csrc/host/bricks.cpp", PKG / "csrc/host/distance.cpp", PKG / "csrc/host/flood.cpp", PKG / "csrc/host/columns.cpp", PKG / "csrc/host/scroll.cpp", PKG / "csrc/host/shapes.cpp", PKG / "csrc/host/lod.cpp", PKG / "csrc/host/affine.cpp", PKG / "csrc/host/automaton.cpp", PKG / "csrc/host/pose.cpp", PKG / "csrc/host/lights.cpp", PKG / "csrc/host/model_lights.cpp", PKG / "csrc/host/light_grid.cpp", PKG / "csrc/hip/tree_build.cpp"]
 HIP_SRC = [PKG / "csrc/hip/api.hip", PKG / "csrc/hip/api_launch.hip", PKG / "csrc/hip/api_debug.hip", PKG / "csrc/hip/api_post.hip", PKG / "csrc/hip/api_volume.hip", PKG / "csrc/hip/api_multi.hip", PKG / "csrc/hip/trace_kernels.hip", PKG / "csrc/hip/dense_kernels.hip", PKG / "csrc/hip/tile_order.hip", PKG / "csrc/hip/gpu_build.hip",
            PKG / "csrc/hip/post_kernels.hip", PKG / "csrc/hip/tree_build.cpp", PKG / "csrc/hip/api_instances.hip", PKG / "csrc/hip/placed_kernels.hip",
            PKG / "csrc/hip/voxelize_kernels.hip", PKG / "csrc/hip/terrain_kernels.hip", PKG / "csrc/hip/quads_kernels.hip", PKG / "csrc/hip/stamp_kernels.hip",

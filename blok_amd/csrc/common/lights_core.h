@@ -237,6 +237,65 @@ BLOK_LD uint64_t instance_faces(bool usable, uint32_t table_n, uint32_t e) { ret
 BLOK_LD bool instance_lights_fit(uint64_t a_world, uint64_t a_inst) { return a_world + a_inst < 0x100000000ull; }
 BLOK_LD float lights_area_world(uint64_t a_total, float vs) { return (static_cast<float>(a_total) * vs) * vs; }
 
+// ---- the light grid (blok_hip.h: "the light grid") ----
+// Cells of 2^c world voxels on the world lattice; a cell's list holds the lights whose own cells lie within `reach` cells of it on every
+// axis.  Integer work with one right answer: the host build (host/light_grid.cpp) and the kernels (hip/lights_kernels.hip) both run the
+// functions below and nothing else decides membership.
+constexpr uint32_t kGridMinLog2 = 2u, kGridMaxLog2 = 12u, kGridMaxReach = 3u;
+constexpr uint64_t kGridMaxCells = 1ull << 24, kGridMaxItems = 1ull << 28;      // more cells: Unsupported; this many items or more: Unsupported
+BLOK_LD bool grid_params_ok(uint32_t cell_log2, uint32_t reach, uint32_t share) {
+    return cell_log2 >= kGridMinLog2 && cell_log2 <= kGridMaxLog2 && reach <= kGridMaxReach && share >= 1u && share <= 255u;
+}
+// The cells a light's emitting voxels lie in, both ends inclusive, before the reach.  On the plane axis the emitting voxel is lo - 1 for a
+// + face and lo for a - face (instance_light_record's reading); in the plane the voxels are [lo, lo + d - 1].  >> of a negative int is
+// arithmetic (C++20), so cell -1 holds voxels [-2^c, -1].
+struct CellRange { int32_t lo[3], hi[3]; };
+BLOK_LD CellRange light_cells(const blok_light& L, uint32_t c) {
+    const uint32_t a = L.face >> 1;
+    const int32_t du = static_cast<int32_t>(L.du) - 1, dv = static_cast<int32_t>(L.dv) - 1, back = (L.face & 1u) ? 0 : 1;
+    CellRange r;
+    r.lo[0] = a == 0u ? L.lo[0] - back : L.lo[0];                 r.hi[0] = a == 0u ? r.lo[0] : r.lo[0] + du;                       // u of faces 2..5
+    r.lo[1] = a == 1u ? L.lo[1] - back : L.lo[1];                 r.hi[1] = a == 1u ? r.lo[1] : r.lo[1] + (a == 0u ? du : dv);      // u of 0..1, v of 4..5
+    r.lo[2] = a == 2u ? L.lo[2] - back : L.lo[2];                 r.hi[2] = a == 2u ? r.lo[2] : r.lo[2] + dv;                       // v of faces 0..3
+    for (int k = 0; k < 3; ++k) { r.lo[k] >>= c; r.hi[k] >>= c; }
+    return r;
+}
+// in(L, g): the one predicate.  g in absolute cells.
+BLOK_LD bool in_cell(const CellRange& r, uint32_t reach, int32_t gx, int32_t gy, int32_t gz) {
+    const int32_t R = static_cast<int32_t>(reach);
+    return r.lo[0] - R <= gx && gx <= r.hi[0] + R && r.lo[1] - R <= gy && gy <= r.hi[1] + R && r.lo[2] - R <= gz && gz <= r.hi[2] + R;
+}
+// The cells that list a light: its range widened by the reach; their number (below 2^32 for a light of the int16 lattice and c >= 2).
+BLOK_LD uint32_t listed_extent(const CellRange& r, uint32_t reach, int k) { return static_cast<uint32_t>(r.hi[k] - r.lo[k]) + 1u + 2u * reach; }
+BLOK_LD uint64_t listed_cells(const CellRange& r, uint32_t reach) {
+    return static_cast<uint64_t>(listed_extent(r, reach, 0)) * listed_extent(r, reach, 1) * listed_extent(r, reach, 2);
+}
+// The box of all listing cells: the union of the lights' ranges, widened by the reach.  An empty box has lo > hi.
+struct GridBounds { int32_t lo[3], hi[3]; };
+BLOK_LD GridBounds no_bounds() { return GridBounds{{0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, {-0x7FFFFFFF - 1, -0x7FFFFFFF - 1, -0x7FFFFFFF - 1}}; }
+BLOK_LD GridBounds join(const GridBounds& a, const GridBounds& b) {
+    GridBounds o;
+    for (int k = 0; k < 3; ++k) { o.lo[k] = a.lo[k] < b.lo[k] ? a.lo[k] : b.lo[k]; o.hi[k] = a.hi[k] > b.hi[k] ? a.hi[k] : b.hi[k]; }
+    return o;
+}
+// cell_lo, dim and n_cells into *info from the union of the lights' ranges (before the reach).
+BLOK_LD void grid_box(const GridBounds& b, uint32_t reach, blok_light_grid_info* info) {
+    info->n_cells = 1u;
+    for (int k = 0; k < 3; ++k) {
+        info->cell_lo[k] = b.lo[k] - static_cast<int32_t>(reach);
+        info->dim[k] = static_cast<uint32_t>(b.hi[k] - b.lo[k]) + 1u + 2u * reach;
+        info->n_cells *= info->dim[k];
+    }
+}
+// The index of listing cell number k of a light (k < listed_cells: x fastest) in a grid of that box.
+BLOK_LD uint32_t listed_cell_index(const CellRange& r, uint32_t reach, uint32_t k, const int32_t cell_lo[3], const uint32_t dim[3]) {
+    const uint32_t ex = listed_extent(r, reach, 0), ey = listed_extent(r, reach, 1), R = reach;
+    const uint32_t x = static_cast<uint32_t>(r.lo[0] - cell_lo[0]) - R + k % ex, y = static_cast<uint32_t>(r.lo[1] - cell_lo[1]) - R + (k / ex) % ey,
+                   z = static_cast<uint32_t>(r.lo[2] - cell_lo[2]) - R + k / (ex * ey);
+    return (z * dim[1] + y) * dim[0] + x;
+}
+BLOK_LD uint64_t grid_bytes(uint64_t n_cells, uint64_t n_items) { return (n_cells + 1u) * 4u + n_cells * 4u + n_items * sizeof(blok_light_grid_item); }
+
 }  // namespace lights
 }  // namespace blok
 #endif

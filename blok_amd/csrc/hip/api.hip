@@ -289,7 +289,7 @@ using namespace blok_api;
 
 extern "C" {
 
-uint32_t blok_hip_abi_version(void) { return (1u << 16) | 28u; }
+uint32_t blok_hip_abi_version(void) { return (1u << 16) | 29u; }
 
 const char* blok_hip_last_error(const blok_hip_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
 
@@ -861,7 +861,15 @@ int blok_api::launch_path_frame(blok_hip_ctx* ctx, const blok_camera* cam, uint3
     if (instanced && scene.nodes)
         blok::launch_tlas_build(inst->table, inst->n, scene.models, scene.n_models, static_cast<blok::TlasNode*>(ctx->beam_buffers[stream].tlas.get()), stream);
     if (n_beams) blok::launch_beam(blok::RayMode::Rect, p.trace, n_beams, stream);
-    if (placed_lit) {
+    // a light grid over a world table: the grid kernel beside path_kernel_lit.  A launch with lit lattice instances keeps the placed kernel
+    // and its global pick: there is no grid kernel beside that one.
+    if (lit && !placed_lit && ctx->light_grid.info.n_cells != 0u) {
+        const blok::LightScene light_scene{ctx->lights.table, ctx->lights.owned, ctx->lights.n, static_cast<uint32_t>(ctx->lights.n_faces), ctx->lights.area_world};
+        const blok_light_grid_info& gi = ctx->light_grid.info;
+        const blok::GridScene grid{ctx->light_grid.start, ctx->light_grid.faces, ctx->light_grid.items, {gi.cell_lo[0], gi.cell_lo[1], gi.cell_lo[2]},
+                                   {gi.dim[0], gi.dim[1], gi.dim[2]}, gi.cell_log2, gi.reach, gi.share};
+        blok::launch_paths_lit_grid(p, scene, pose_scene, light_scene, grid, ctx->models.stack_levels, path_blocks, stream);
+    } else if (placed_lit) {
         const blok::LightScene light_scene{ctx->lights.table, ctx->lights.owned, ctx->lights.n, static_cast<uint32_t>(ctx->lights.n_faces), ctx->lights.area_world};
         blok::launch_paths_lit_placed(p, scene, pose_scene, light_scene, inst_lights, ctx->models.stack_levels, path_blocks, stream);
     } else if (lit) {

@@ -124,6 +124,13 @@ struct blok_hip_ctx {
         uint64_t n_faces = 0;
         float area_world = 0.0f;
     } lights;
+    // the light grid over that table (blok_hip.h: "the light grid"; api_volume.hip): installed iff info.n_cells != 0.  Dropped by
+    // clear_lights, so by everything that installs or clears the table.
+    struct LightGrid {
+        blok::DeviceArray<uint32_t> start, faces;
+        blok::DeviceArray<blok_light_grid_item> items;
+        blok_light_grid_info info{};
+    } light_grid;
     std::vector<uint32_t> material_glows;             // the emissive indices of the installed material table, a bit each (install_materials)
     std::vector<unsigned char> volume_materials;      // the material table the last blok_hip_volume_rebuild installed (compared, not re-uploaded, when unchanged)
     // "last occluder" map of the shadow rays (beam.h: prism_far), rebuilt with every world

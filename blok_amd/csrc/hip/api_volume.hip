@@ -26,6 +26,7 @@ namespace blok_api {
 void clear_lights(blok_hip_ctx* ctx) {
     if (ctx->lights.table) (void)hipDeviceSynchronize();      // frames that still sample it
     ctx->lights = blok_hip_ctx::Lights{};
+    ctx->light_grid = blok_hip_ctx::LightGrid{};              // (a statement about that table)
 }
 
 void free_volume_snapshots(blok_hip_ctx* ctx) {
@@ -1025,6 +1026,53 @@ int blok_hip_lights_download(blok_hip_ctx* ctx, blok_light* out_host, uint64_t f
     if (!ctx) return BLOK_ERR_INVALID_ARG;
     const blok_hip_ctx::Lights& l = ctx->lights;
     return ranged_download(ctx, "lights_download", "blok_hip_lights_from_quads or blok_hip_set_lights", true, l.n, l.table.get(), sizeof(blok_light), out_host, first, count);
+}
+
+// ---- the light grid (blok_hip.h; lights_kernels.hip) ----
+int blok_hip_build_light_grid(blok_hip_ctx* ctx, uint32_t cell_log2, uint32_t reach, uint32_t share, uint32_t flags, blok_light_grid_info* out) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (flags) return set_error(ctx, BLOK_ERR_INVALID_ARG, "build_light_grid: unknown flag bits");
+    if (!blok::lights::grid_params_ok(cell_log2, reach, share))
+        return set_error(ctx, BLOK_ERR_INVALID_ARG, "build_light_grid: cell_log2 must be 2..12, reach 0..3, share 1..255");
+    if (ctx->lights.n == 0u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "build_light_grid: no light table (blok_hip_lights_from_quads or blok_hip_set_lights)");
+    BLOK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    blok::GpuLightGrid made;
+    std::string why;
+    // (the table's builders and uploads are on the null stream, and so is this)
+    const blok::GpuBuildStatus st = blok::gpu_light_grid_build(ctx->lights.table, ctx->lights.n, cell_log2, reach, share, &made, &why);
+    if (st != blok::GpuBuildStatus::Ok) return volume_status(ctx, st, why);
+    blok_hip_ctx::LightGrid& g = ctx->light_grid;
+    if (g.info.n_cells != 0u) (void)hipDeviceSynchronize();   // frames that still sample the old one
+    g.start.adopt(made.d_start, made.info.n_cells + 1u);
+    g.faces.adopt(made.d_faces, made.info.n_cells);
+    g.items.adopt(made.d_items, made.info.n_items);
+    g.info = made.info;
+    if (out) *out = g.info;
+    return BLOK_OK;
+}
+
+int blok_hip_light_grid_info(blok_hip_ctx* ctx, blok_light_grid_info* out) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (!out) return set_error(ctx, BLOK_ERR_INVALID_ARG, "light_grid_info: null output");
+    *out = ctx->light_grid.info;
+    return BLOK_OK;
+}
+
+int blok_hip_light_grid_download(blok_hip_ctx* ctx, uint32_t what, void* out_host, uint64_t first, uint64_t count) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    const blok_hip_ctx::LightGrid& g = ctx->light_grid;
+    if (what > 2u) return set_error(ctx, BLOK_ERR_INVALID_ARG, "light_grid_download: what must be 0 (start), 1 (faces) or 2 (items)");
+    const bool built = g.info.n_cells != 0u;
+    const uint64_t n = !built ? 0u : what == 0u ? g.info.n_cells + 1u : what == 1u ? g.info.n_cells : g.info.n_items;
+    const void* base = what == 0u ? static_cast<const void*>(g.start.get()) : what == 1u ? static_cast<const void*>(g.faces.get()) : static_cast<const void*>(g.items.get());
+    return ranged_download(ctx, "light_grid_download", "blok_hip_build_light_grid", built, n, base, what == 2u ? sizeof(blok_light_grid_item) : sizeof(uint32_t), out_host, first, count);
+}
+
+int blok_hip_light_grid_clear(blok_hip_ctx* ctx) {
+    if (!ctx) return BLOK_ERR_INVALID_ARG;
+    if (ctx->light_grid.info.n_cells != 0u) (void)hipDeviceSynchronize();     // frames that still sample it
+    ctx->light_grid = blok_hip_ctx::LightGrid{};
+    return BLOK_OK;
 }
 
 }  // extern "C"

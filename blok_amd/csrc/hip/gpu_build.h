@@ -153,6 +153,18 @@ GpuBuildStatus gpu_lights_from_quads(const blok_quad* d_quads, uint64_t n_quads,
 // arrays' lengths as the store keeps them), in the order of its material array; out->n_faces == out->n.  Null stream; waits for the count.
 GpuBuildStatus gpu_model_lights(const uint4* d_nodes, uint32_t n_nodes, const uint32_t* d_materials, uint32_t n_voxels, uint32_t levels, const int32_t origin[3],
                                 const uint32_t* d_glows, uint32_t n_materials, GpuLights* out, std::string* why);
+// = blok_hip_build_light_grid (include/blok_hip.h; lights_kernels.hip) over a table in device memory that has passed lights::check_table
+// and parameters that have passed lights::grid_params_ok.  The three arrays are new device arrays, the caller's to free.  Unsupported: the
+// grid's limits.  Null stream; waits once for {bounds, n_items} before it allocates the result, and once at the end for the two figures
+// of the lists' lengths.
+struct GpuLightGrid {
+    uint32_t* d_start = nullptr;        // n_cells + 1
+    uint32_t* d_faces = nullptr;        // n_cells
+    blok_light_grid_item* d_items = nullptr;
+    blok_light_grid_info info{};
+};
+GpuBuildStatus gpu_light_grid_build(const blok_light* d_lights, uint32_t n, uint32_t cell_log2, uint32_t reach, uint32_t share, GpuLightGrid* out,
+                                    std::string* why);
 struct ModelDesc;
 namespace lights { struct ModelLightTable; }
 // The per-launch prefix of an instance table (lights_core.h): icum, n + 1 words, and the 32-byte header behind them at `header`

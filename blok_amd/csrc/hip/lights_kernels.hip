@@ -1,7 +1,8 @@
 // The light table from the quads snapshot (gpu_build.h: gpu_lights_from_quads; include/blok_hip.h: blok_hip_lights_from_quads).  The
 // predicates are ../common/lights_core.h; DESIGN.md §32 has the contract.
 // Behind it, the table of a MODEL's exposed emissive unit faces from its own tree (gpu_model_lights; blok_hip_model_lights)
-// and the per-launch prefix of an instance table over those tables (launch_instance_lights_prefix).
+// and the per-launch prefix of an instance table over those tables (launch_instance_lights_prefix); and the light grid over the world's
+// table (gpu_light_grid_build; blok_hip_build_light_grid).
 //
 // A lane per quad, two passes and one scan between them; no sort, no atomics, integer arithmetic only:
 //   1. lights_count_kernel: a quad is kept iff its key's material index is in the emissive set.  One ballot gives the wave's number of
@@ -282,6 +283,189 @@ GpuBuildStatus gpu_model_lights(const uint4* d_nodes, uint32_t n_nodes, const ui
         out->d_lights = a.out;
     }
     out->n = a.total; out->n_faces = a.total;
+    return GpuBuildStatus::Ok;
+}
+
+// ---- the light grid (lights_core.h: light_cells, listed_cell_index) ------------------------------------------------------------
+// The route: (cell, light) pairs expanded in table order behind a scan, then sorted stably by cell (hipcub's radix sort, as the volume
+// rebuild sorts its bricks).  No list is formed by atomics, so none depends on the order in which they land:
+//   1. grid_measure_kernel: a lane per light, its cell range and the number of cells that list it; a reduction (hipcub) joins the ranges
+//      and sums the numbers: {bounds, n_items}, the one thing the host reads before it allocates the result.
+//   2. an exclusive scan of the per-light numbers: where each light's pairs begin.
+//   3. grid_expand_kernel: a lane per pair; its light by a search of the offsets, its cell from its rank among the light's pairs.  Pair j
+//      is written to slot j: table order.
+//   4. the stable sort by cell index: within a cell the lights stay in ascending table index.
+//   5. the segmented scan of du * dv: one exclusive scan G over the sorted pairs in wrapping 32-bit arithmetic, a segment's value the
+//      difference to G at the segment's head (a list's sum is < 2^32, so the difference is exact): lcum = G[j] - G[start[g]],
+//      faces[g] = G[start[g + 1]] - G[start[g]].  start[g] is the first sorted pair with a cell >= g, by a search per cell.
+// The two figures of the lists' lengths (non-empty cells, the longest list) are an integer add and an integer max over the cells: atomics
+// whose result no order changes.
+namespace {
+
+struct GridMeasure { int32_t lo[3], hi[3]; unsigned long long items; };
+struct GridMeasureJoin {
+    __host__ __device__ GridMeasure operator()(const GridMeasure& a, const GridMeasure& b) const {
+        GridMeasure o;
+        for (int k = 0; k < 3; ++k) { o.lo[k] = a.lo[k] < b.lo[k] ? a.lo[k] : b.lo[k]; o.hi[k] = a.hi[k] > b.hi[k] ? a.hi[k] : b.hi[k]; }
+        o.items = a.items + b.items;
+        return o;
+    }
+};
+
+struct GridArgs {
+    const blok_light* lights; uint32_t n;
+    uint32_t c, reach;
+    int32_t cell_lo[3]; uint32_t dim[3];
+    uint32_t n_cells, n_items;
+    GridMeasure* measures;              // n
+    uint32_t* offsets;                  // n + 1: the lights' numbers of pairs (the last 0), then (scanned in place) where their pairs begin
+    uint32_t *keys, *vals;              // n_items: the pairs in table order: cell index, light
+    const uint32_t *keys_sorted, *vals_sorted;
+    uint32_t* scan;                     // n_items + 1: du * dv of the sorted pairs' lights (the last 0), then (scanned in place) G
+    uint32_t *start, *faces; blok_light_grid_item* items;      // the result
+    uint32_t* stats;                    // [0] non-empty cells, [1] the longest list
+};
+
+__global__ __launch_bounds__(256) void grid_measure_kernel(const GridArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n) return;
+    const L::CellRange r = L::light_cells(a.lights[i], a.c);
+    GridMeasure m;
+    for (int k = 0; k < 3; ++k) { m.lo[k] = r.lo[k]; m.hi[k] = r.hi[k]; }
+    m.items = L::listed_cells(r, a.reach);
+    a.measures[i] = m;
+    a.offsets[i] = m.items < 0xFFFFFFFFull ? static_cast<uint32_t>(m.items) : 0xFFFFFFFFu;      // (used only once the sum has passed the limit)
+}
+
+__global__ __launch_bounds__(256) void grid_expand_kernel(const GridArgs a) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= a.n_items) return;
+    uint32_t lo = 0u, hi = a.n;                          // the last light whose pairs begin at or before j (offsets ascend strictly)
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a.offsets[mid] <= j) lo = mid; else hi = mid;
+    }
+    const L::CellRange r = L::light_cells(a.lights[lo], a.c);
+    const uint32_t k = j - a.offsets[lo];
+    a.keys[j] = L::listed_cell_index(r, a.reach, k, a.cell_lo, a.dim);
+    a.vals[j] = lo;
+}
+
+__global__ __launch_bounds__(256) void grid_areas_kernel(const GridArgs a) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j > a.n_items) return;
+    uint32_t area = 0u;
+    if (j < a.n_items) { const blok_light& l = a.lights[a.vals_sorted[j]]; area = l.du * l.dv; }
+    a.scan[j] = area;
+}
+
+__global__ __launch_bounds__(256) void grid_start_kernel(const GridArgs a) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g > a.n_cells) return;
+    uint32_t lo = 0u, hi = a.n_items;                    // the first sorted pair whose cell is >= g (n_items: none)
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a.keys_sorted[mid] < g) lo = mid + 1u; else hi = mid;
+    }
+    a.start[g] = lo;
+}
+
+__global__ __launch_bounds__(256) void grid_cells_kernel(const GridArgs a) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    uint32_t len = 0u;
+    if (g < a.n_cells) {
+        const uint32_t s0 = a.start[g], s1 = a.start[g + 1u];
+        a.faces[g] = a.scan[s1] - a.scan[s0];
+        len = s1 - s0;
+    }
+    const uint32_t nonempty = static_cast<uint32_t>(__popcll(__ballot(len != 0u)));
+    uint32_t longest = len;
+    for (int off = 32; off > 0; off >>= 1) { const uint32_t t = __shfl_down(longest, off); longest = t > longest ? t : longest; }
+    if (lane_of() == 0u && nonempty) { atomicAdd(a.stats, nonempty); atomicMax(a.stats + 1, longest); }
+}
+
+__global__ __launch_bounds__(256) void grid_items_kernel(const GridArgs a) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= a.n_items) return;
+    const uint32_t g = a.keys_sorted[j];
+    a.items[j] = blok_light_grid_item{a.vals_sorted[j], a.scan[j] - a.scan[a.start[g]]};
+}
+
+}  // namespace
+
+GpuBuildStatus gpu_light_grid_build(const blok_light* d_lights, uint32_t n, uint32_t cell_log2, uint32_t reach, uint32_t share, GpuLightGrid* out,
+                                    std::string* why) {
+    *out = GpuLightGrid{};
+    if (!d_lights || n == 0u || n >= 0x80000000u) { *why = "light_grid: no light table"; return GpuBuildStatus::Internal; }
+    GridArgs a{};
+    a.lights = d_lights; a.n = n; a.c = cell_log2; a.reach = reach;
+    DeviceMem mem;
+    GridMeasure* d_total;
+    BLOK_GPU_TRY(mem.alloc(&a.measures, n));
+    BLOK_GPU_TRY(mem.alloc(&a.offsets, static_cast<uint64_t>(n) + 1u));
+    BLOK_GPU_TRY(mem.alloc(&d_total, 1u));
+    BLOK_GPU_TRY(hipMemsetAsync(a.offsets + n, 0, sizeof(uint32_t), nullptr));
+    hipLaunchKernelGGL(grid_measure_kernel, dim3(blocks_for(n)), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    const L::GridBounds none = L::no_bounds();
+    const GridMeasure nothing{{none.lo[0], none.lo[1], none.lo[2]}, {none.hi[0], none.hi[1], none.hi[2]}, 0ull};
+    size_t temp_bytes = 0;
+    uint8_t* d_temp;
+    BLOK_GPU_TRY(hipcub::DeviceReduce::Reduce(nullptr, temp_bytes, a.measures, d_total, static_cast<int>(n), GridMeasureJoin{}, nothing));
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceReduce::Reduce(d_temp, temp_bytes, a.measures, d_total, static_cast<int>(n), GridMeasureJoin{}, nothing));
+    GridMeasure total{};
+    BLOK_GPU_TRY(hipMemcpy(&total, d_total, sizeof(total), hipMemcpyDeviceToHost));      // {bounds, n_items}: the one read before the result is allocated
+    blok_light_grid_info& info = out->info;
+    info.cell_log2 = cell_log2; info.reach = reach; info.share = share;
+    L::grid_box(L::GridBounds{{total.lo[0], total.lo[1], total.lo[2]}, {total.hi[0], total.hi[1], total.hi[2]}}, reach, &info);
+    info.n_items = total.items;
+    if (info.n_cells > L::kGridMaxCells || info.n_items >= L::kGridMaxItems) {
+        *why = "light_grid: " + std::to_string(info.n_cells) + " cells, " + std::to_string(info.n_items) + " items: more than 2^24 cells, or 2^28 or more items";
+        return GpuBuildStatus::Unsupported;
+    }
+    info.bytes = L::grid_bytes(info.n_cells, info.n_items);
+    a.n_cells = static_cast<uint32_t>(info.n_cells); a.n_items = static_cast<uint32_t>(info.n_items);
+    for (int k = 0; k < 3; ++k) { a.cell_lo[k] = info.cell_lo[k]; a.dim[k] = info.dim[k]; }
+
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, a.offsets, a.offsets, static_cast<int>(n + 1u)));
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, a.offsets, a.offsets, static_cast<int>(n + 1u)));
+    uint32_t *keys_sorted, *vals_sorted;
+    BLOK_GPU_TRY(mem.alloc(&a.keys, a.n_items));
+    BLOK_GPU_TRY(mem.alloc(&a.vals, a.n_items));
+    BLOK_GPU_TRY(mem.alloc(&keys_sorted, a.n_items));
+    BLOK_GPU_TRY(mem.alloc(&vals_sorted, a.n_items));
+    BLOK_GPU_TRY(mem.alloc(&a.scan, static_cast<uint64_t>(a.n_items) + 1u));
+    BLOK_GPU_TRY(mem.alloc(&a.stats, 2u));
+    BLOK_GPU_TRY(mem.alloc(&a.start, static_cast<uint64_t>(a.n_cells) + 1u));
+    BLOK_GPU_TRY(mem.alloc(&a.faces, a.n_cells));
+    BLOK_GPU_TRY(mem.alloc(&a.items, a.n_items));
+    a.keys_sorted = keys_sorted; a.vals_sorted = vals_sorted;
+    BLOK_GPU_TRY(hipMemsetAsync(a.stats, 0, 2u * sizeof(uint32_t), nullptr));
+    hipLaunchKernelGGL(grid_expand_kernel, dim3(blocks_for(a.n_items)), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    int key_bits = 1;
+    while (key_bits < 32 && (1ull << key_bits) < info.n_cells) ++key_bits;
+    BLOK_GPU_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, a.keys, keys_sorted, a.vals, vals_sorted, static_cast<int>(a.n_items), 0, key_bits));
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, a.keys, keys_sorted, a.vals, vals_sorted, static_cast<int>(a.n_items), 0, key_bits));
+    hipLaunchKernelGGL(grid_areas_kernel, dim3(blocks_for(static_cast<uint64_t>(a.n_items) + 1u)), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, a.scan, a.scan, static_cast<int>(a.n_items + 1u)));
+    BLOK_GPU_TRY(mem.alloc(&d_temp, temp_bytes));
+    BLOK_GPU_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, a.scan, a.scan, static_cast<int>(a.n_items + 1u)));
+    hipLaunchKernelGGL(grid_start_kernel, dim3(blocks_for(static_cast<uint64_t>(a.n_cells) + 1u)), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    hipLaunchKernelGGL(grid_cells_kernel, dim3(blocks_for(a.n_cells)), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    hipLaunchKernelGGL(grid_items_kernel, dim3(blocks_for(a.n_items)), dim3(256), 0, nullptr, a);
+    BLOK_GPU_TRY(hipGetLastError());
+    uint32_t stats[2] = {0u, 0u};
+    BLOK_GPU_TRY(hipMemcpy(stats, a.stats, sizeof(stats), hipMemcpyDeviceToHost));      // behind every kernel above
+    info.n_nonempty = stats[0]; info.max_items = stats[1];
+    mem.release(a.start); mem.release(a.faces); mem.release(a.items);
+    out->d_start = a.start; out->d_faces = a.faces; out->d_items = a.items;
     return GpuBuildStatus::Ok;
 }
 

@@ -242,6 +242,73 @@ BLOK_DEV bool placed_light_sample(const LightScene& S, const InstanceLightScene&
     return true;
 }
 
+// The grid part of a lit path launch (include/blok_hip.h: "the light grid"): the three arrays and the grid's figures, which
+// every lane reads through the kernel's arguments (the scalar cache).
+struct GridScene {
+    const uint32_t* start; const uint32_t* faces; const blok_light_grid_item* items;
+    int32_t cell_lo[3]; uint32_t dim[3];
+    uint32_t cell_log2, reach, share;
+};
+// The light sample under a grid, given the four draws r, u1, u2, m.  The shading point's cell g and A_g = faces[g] (0 for a
+// point without a cell); LOCAL iff A_g > 0 and (m >> 24) < share: p = (r * A_g) >> 32, the item the last of the cell's list with lcum <= p;
+// else GLOBAL: light_sample's pick over A_dom = A_world, and inlist = in(L, g) from the picked record.  area_eff = (vs * vs) / (w_loc + w_glob) stands where area_world stood; from the
+// sampled rectangle on, light_sample's operations in light_sample's order.  Straight-line code between two walks: nothing of it lives on.
+BLOK_DEV bool grid_light_sample(const LightScene& S, const GridScene& G, const blok_material* mat_table, uint32_t n_materials, float vs, V3 hit_pos, V3 n, uint32_t r,
+                                float u1, float u2, uint32_t m, V3& q, V3& le, float& g) {
+    const uint32_t a_dom = S.n_faces;
+    const V3 x = vadd(hit_pos, vscale(n, 0.001f));
+    const float vx = floorf(x.x / vs), vy = floorf(x.y / vs), vz = floorf(x.z / vs);
+    constexpr float kFar = 1073741824.0f;                                                     // 2^30
+    uint32_t a_g = 0u, cell = 0u;
+    int32_t gx = 0, gy = 0, gz = 0;
+    if (fabsf(vx) < kFar && fabsf(vy) < kFar && fabsf(vz) < kFar) {
+        gx = static_cast<int32_t>(vx) >> G.cell_log2; gy = static_cast<int32_t>(vy) >> G.cell_log2; gz = static_cast<int32_t>(vz) >> G.cell_log2;
+        const uint32_t rx = static_cast<uint32_t>(gx - G.cell_lo[0]), ry = static_cast<uint32_t>(gy - G.cell_lo[1]), rz = static_cast<uint32_t>(gz - G.cell_lo[2]);
+        if (rx < G.dim[0] && ry < G.dim[1] && rz < G.dim[2]) {                                // (a cell below cell_lo wraps far above dim)
+            cell = (rz * G.dim[1] + ry) * G.dim[0] + rx;
+            a_g = G.faces[cell];
+        }
+    }
+    blok_light L;
+    uint32_t off;
+    bool inlist;
+    if (a_g > 0u && (m >> 24) < G.share) {
+        const uint32_t p = lights::pick_of(r, a_g);
+        uint32_t lo = G.start[cell], hi = G.start[cell + 1u];                                 // the last item with lcum <= p (the first has lcum 0)
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (G.items[mid].lcum <= p) lo = mid; else hi = mid;
+        }
+        const blok_light_grid_item item = G.items[lo];
+        L = S.lights[item.light];
+        off = p - item.lcum;
+        inlist = true;
+    } else {
+        const uint32_t pick = lights::pick_of(r, a_dom);
+        L = S.lights[lights::find_light(S.lights, S.n, pick)];
+        off = pick - L.cum;
+        inlist = a_g > 0u && lights::in_cell(lights::light_cells(L, G.cell_log2), G.reach, gx, gy, gz);
+    }
+    const float w_loc = inlist ? (static_cast<float>(G.share) / 256.0f) / static_cast<float>(a_g) : 0.0f;
+    const float w_glob = (a_g > 0u ? static_cast<float>(256u - G.share) / 256.0f : 1.0f) / static_cast<float>(a_dom);
+    const float area_eff = (vs * vs) / (w_loc + w_glob);
+    float qa[3], nla[3];
+    lights::sample_point(L, off, u1, u2, vs, qa, nla);
+    q = v3(qa[0], qa[1], qa[2]);
+    const V3 nl = v3(nla[0], nla[1], nla[2]);
+    const V3 w = vsub(q, x);
+    const float d2 = vdot(w, w);
+    const float d = rn_sqrt(d2);
+    const V3 dir = vdivs(w, d);
+    const float cos_s = fmaxf(vdot(n, dir), 0.0f);
+    const float cos_l = fmaxf(-vdot(nl, dir), 0.0f);
+    if (!(cos_s > 0.0f && cos_l > 0.0f && d > 2.0f * lights::kLightEps)) return false;
+    g = (((cos_s * cos_l) / d2) * area_eff) * kInvPi;
+    const blok_material mat = mat_table[lights::material_index(L.material, n_materials)];
+    le = v3(mat.emission[0], mat.emission[1], mat.emission[2]);
+    return true;
+}
+
 BLOK_DEV void store4(float* plane, size_t i, float a, float b, float c, float d) {
     if (!plane) return;
     float* p = plane + 4 * i;
@@ -298,12 +365,16 @@ BLOK_DEV void store_narrow(const PathArgs& P, size_t index, uint32_t px, uint32_
 // kPlacedLit (over the lit body only): the pick runs over the world table AND the tables of the launch's lit lattice instances (`ilit`, whose
 // header holds A_total and area_world); a lit instance's emission is not counted again where a diffuse bounce ray finds it.
 // With A_total = 0 no light is sampled and no number is drawn.
-template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false, bool kLit = false, bool kPlacedLit = false>
+// kGrid (over the lit body only): the light sample is grid_light_sample's — a fourth draw, the shading point's cell, the local or the global
+// strategy, area_eff.  Rule (e) of §32 is unchanged: it speaks about which faces the tables hold, not how they are picked.
+template <bool kResume = true, bool kSkyOnly = false, bool kInstanced = false, bool kPosed = false, bool kLit = false, bool kPlacedLit = false, bool kGrid = false>
 BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t index, uint4* stk, float t0 = 0.0f, uint2* keep_lohi = nullptr, uint32_t* keep_base = nullptr,
                           [[maybe_unused]] TailRecord* pool = nullptr, [[maybe_unused]] TailAnswer* tail_results = nullptr,
                           [[maybe_unused]] const TlasScene* scene = nullptr, [[maybe_unused]] const PoseScene* poses = nullptr,
-                          [[maybe_unused]] const LightScene* lit = nullptr, [[maybe_unused]] const InstanceLightScene* ilit = nullptr) {
+                          [[maybe_unused]] const LightScene* lit = nullptr, [[maybe_unused]] const InstanceLightScene* ilit = nullptr,
+                          [[maybe_unused]] const GridScene* grid = nullptr) {
     static_assert(!kPlacedLit || kLit, "instance lights extend the lit loop");
+    static_assert(!kGrid || (kLit && !kPlacedLit), "the light grid extends the lit loop over the world's table");
     static_assert(!kInstanced || (!kResume && !kSkyOnly), "instanced launches run without walk_resume and the sky-only build");
     static_assert(!kPosed || kInstanced, "a posed launch is an instanced launch with a pose table");
     static_assert(!kLit || kPosed, "the lit loop is built over the posed superset body");
@@ -727,6 +798,10 @@ BLOK_DEV void shade_pixel(const PathArgs& P, uint32_t px, uint32_t py, size_t in
                     const float u2 = random_float(rng);
                     V3 le; float g;
                     bool sampled;
+                    if constexpr (kGrid) {
+                        const uint32_t lm = pcg(rng);                                         // the fourth draw, always
+                        sampled = grid_light_sample(*lit, *grid, A.mat_table, A.n_materials, A.voxel_size, hit_pos, n, lr, u1, u2, lm, light_q, le, g);
+                    } else
                     if constexpr (kPlacedLit)
                         sampled = placed_light_sample(*lit, *ilit, *scene, static_cast<uint32_t>(ilit->header->a_total), ilit->header->area_world, A.mat_table,
                                                       A.n_materials, A.voxel_size, hit_pos, n, lr, u1, u2, light_q, le, g);

@@ -273,6 +273,10 @@ struct InstanceLightScene;
 // lit.n may be 0.  The prefix `ilit` points to has been launched on `stream` before.
 void launch_paths_lit_placed(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, const InstanceLightScene& ilit,
                              uint32_t stack_slots, uint32_t n_blocks, hipStream_t stream);
+// ... under a light grid (path_core.h: kGrid; lit.n >= 1): beside launch_paths_lit.
+struct GridScene;
+void launch_paths_lit_grid(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, const GridScene& grid, uint32_t stack_slots,
+                           uint32_t n_blocks, hipStream_t stream);
 void launch_paths_lit(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, uint32_t stack_slots, uint32_t n_blocks,
                       hipStream_t stream);
 void launch_trace(RayMode mode, const TraceArgs& args, uint32_t n_blocks, hipStream_t stream);

@@ -1345,6 +1345,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PAT
                                                       &Q, &L, &IL);
 }
 
+// The lit path frame under a light grid (path_core.h: shade_pixel<…, kGrid>): path_kernel_lit's body with grid_light_sample
+// as the light sample.  A kernel of its own, so that path_kernel_lit stays as it was (profiles/light_grid_isa.txt).  Waves per SIMD: its.
+// A launch with lit lattice instances (path_kernel_lit_placed) does not sample through the grid: there is no grid kernel beside that one.
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(BLOK_PATH_LIT_WAVES, BLOK_PATH_LIT_WAVES))) void path_kernel_lit_grid(
+    const PathArgs P, const TlasScene S, const PoseScene Q, const LightScene L, const GridScene G) {
+    extern __shared__ uint4 lds_stack[];
+    const TraceArgs& A = P.trace;
+    const uint32_t tid = threadIdx.x;
+    uint32_t rx, ry;
+    float t0;
+    if (!path_pixel(P, tid, rx, ry, t0)) return;
+    shade_pixel<false, false, true, true, true, false, true>(P, A.x0 + rx, A.y0 + ry, static_cast<size_t>(ry) * A.w + rx, lds_stack + tid, t0, nullptr, nullptr, nullptr, nullptr,
+                                                             &S, &Q, &L, nullptr, &G);
+}
+
 // One workgroup builds the instance BVH of n <= kTlasMax instances (tlas_core.h): sort keys, a bitonic sort in LDS, the leaves, the refit
 // level by level (each level reads the one below it from global memory behind a fence and a barrier), the header.  No atomics.
 __global__ __launch_bounds__(kTlasBuildThreads) void tlas_build_kernel(const blok_instance* inst, uint32_t n, const ModelDesc* models, uint32_t n_models,
@@ -1778,6 +1793,14 @@ void launch_paths_lit_placed(const PathArgs& args, const TlasScene& scene, const
     uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
     if (stack_slots > slots) slots = stack_slots;
     hipLaunchKernelGGL(path_kernel_lit_placed, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses, lit, ilit);
+}
+
+void launch_paths_lit_grid(const PathArgs& args, const TlasScene& scene, const PoseScene& poses, const LightScene& lit, const GridScene& grid, uint32_t stack_slots,
+                           uint32_t n_blocks, hipStream_t stream) {
+    if (n_blocks == 0 || lit.n == 0u) return;
+    uint32_t slots = args.trace.levels > 1u ? args.trace.levels - 1u : 1u;
+    if (stack_slots > slots) slots = stack_slots;
+    hipLaunchKernelGGL(path_kernel_lit_grid, dim3(n_blocks), dim3(kBlock), static_cast<size_t>(slots) * kBlock * sizeof(uint4), stream, args, scene, poses, lit, grid);
 }
 
 void launch_tlas_build(const blok_instance* instances, uint32_t n, const ModelDesc* models, uint32_t n_models, TlasNode* nodes, hipStream_t stream) {

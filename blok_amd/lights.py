@@ -75,6 +75,56 @@ def download(tracer, first: int | None = None, count: int | None = None, page: i
     return tracer._paged(tracer._lib.blok_hip_lights_download, np.zeros(int(count or 0), dtype=LIGHT), int(first or 0), page)
 
 
+# ---- the light grid (include/blok_hip.h: "the light grid") ---------------------------------------------------------------------
+def host_build_grid(lights, cell_log2: int, reach: int = 1, share: int = 128):
+    """blok_light_grid_build: (start, faces, items, LIGHT_GRID_INFO record) of the grid over a host table; bit for bit what `build_grid`
+    builds on the device over the same table."""
+    t = np.ascontiguousarray(lights, dtype=LIGHT).reshape(-1)
+    info = np.zeros(1, dtype=_ffi.LIGHT_GRID_INFO)
+    lib = _ffi.host_lib()
+    args = (_ffi.ptr(t) if len(t) else None, len(t), int(cell_log2), int(reach), int(share))
+    rc = lib.blok_light_grid_build(*args, None, None, None, 0, 0, _ffi.ptr(info))
+    if rc != 0:
+        raise BlokError(rc, "blok_light_grid_build")
+    n_cells, n_items = int(info["n_cells"][0]), int(info["n_items"][0])
+    start, faces = np.zeros(n_cells + 1, dtype=np.uint32), np.zeros(n_cells, dtype=np.uint32)
+    items = np.zeros(max(n_items, 1), dtype=_ffi.LIGHT_GRID_ITEM)
+    rc = lib.blok_light_grid_build(*args, _ffi.ptr(start), _ffi.ptr(faces), _ffi.ptr(items), n_cells, n_items, _ffi.ptr(info))
+    if rc != 0:
+        raise BlokError(rc, "blok_light_grid_build")
+    return start, faces, items[:n_items], info
+
+
+def build_grid(tracer, cell_log2: int, reach: int = 1, share: int = 128) -> np.ndarray:
+    """blok_hip_build_light_grid: builds the grid over the installed world light table on the device and installs it.  Returns the
+    LIGHT_GRID_INFO record."""
+    out = np.zeros(1, dtype=_ffi.LIGHT_GRID_INFO)
+    tracer._check(tracer._lib.blok_hip_build_light_grid(tracer._ctx, int(cell_log2), int(reach), int(share), 0, _ffi.ptr(out)))
+    return out
+
+
+def grid_info(tracer) -> np.ndarray:
+    """blok_hip_light_grid_info: the LIGHT_GRID_INFO record of the installed grid (zeros without one)."""
+    out = np.zeros(1, dtype=_ffi.LIGHT_GRID_INFO)
+    tracer._check(tracer._lib.blok_hip_light_grid_info(tracer._ctx, _ffi.ptr(out)))
+    return out
+
+
+def grid_download(tracer, what: int, first: int | None = None, count: int | None = None, page: int = 1 << 22) -> np.ndarray:
+    """blok_hip_light_grid_download: elements [first, first + count) of the grid's start (what 0), faces (1) or items (2) array (both
+    None: all of it), `page` elements a call."""
+    if first is None and count is None:
+        g = grid_info(tracer)
+        n_cells = int(g["n_cells"][0])
+        first, count = 0, (n_cells + 1 if n_cells else 0, n_cells, int(g["n_items"][0]))[int(what)]
+    out = np.zeros(int(count or 0), dtype=_ffi.LIGHT_GRID_ITEM if int(what) == _ffi.LIGHT_GRID_ITEMS else np.uint32)
+    return tracer._paged(tracer._lib.blok_hip_light_grid_download, out, int(first or 0), page, int(what))
+
+
+def clear_grid(tracer) -> None:
+    tracer._check(tracer._lib.blok_hip_light_grid_clear(tracer._ctx))
+
+
 # ---- emissive models as lights (include/blok_hip.h: "emissive models as lights"; DESIGN.md §33) ----------------------------------------------
 def host_model_lights(xyz, material_ids, materials) -> np.ndarray:
     """blok_model_lights: the LIGHT records of the exposed emissive unit faces of the model `model_create` makes of the voxel list, in the

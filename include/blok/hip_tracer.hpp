@@ -282,6 +282,32 @@ public:
         for (uint64_t at = 0; at < n; at += page) check(blok_hip_lights_download(m_ctx, lights.data() + at, at, std::min(page, n - at)));
         return lights;
     }
+    // The light grid (blok_hip.h): per-cell lists over the installed light table, built on the device; dropped with the table.
+    blok_light_grid_info buildLightGrid(uint32_t cell_log2, uint32_t reach = 1u, uint32_t share = 128u) {
+        blok_light_grid_info info{};
+        check(blok_hip_build_light_grid(m_ctx, cell_log2, reach, share, 0u, &info));
+        return info;
+    }
+    blok_light_grid_info lightGridInfo() const {
+        blok_light_grid_info info{};
+        check(blok_hip_light_grid_info(m_ctx, &info));
+        return info;
+    }
+    void clearLightGrid() { check(blok_hip_light_grid_clear(m_ctx)); }
+    // The installed grid's arrays: start (n_cells + 1 words), faces (n_cells words), items.
+    std::vector<uint32_t> downloadLightGridWords(bool faces, uint64_t page = uint64_t(1) << 22) const {
+        const blok_light_grid_info info = lightGridInfo();
+        const uint64_t n = info.n_cells ? (faces ? info.n_cells : info.n_cells + 1u) : 0u;
+        std::vector<uint32_t> words(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_light_grid_download(m_ctx, faces ? 1u : 0u, words.data() + at, at, std::min(page, n - at)));
+        return words;
+    }
+    std::vector<blok_light_grid_item> downloadLightGridItems(uint64_t page = uint64_t(1) << 22) const {
+        const uint64_t n = lightGridInfo().n_items;
+        std::vector<blok_light_grid_item> items(n);
+        for (uint64_t at = 0; at < n; at += page) check(blok_hip_light_grid_download(m_ctx, 2u, items.data() + at, at, std::min(page, n - at)));
+        return items;
+    }
     // Emissive models as lights (blok_hip.h): the table of a model's exposed emissive unit faces, built on the device from the model's
     // own tree under the installed material table; no faces: no table.  Dropped with the model and with every new material table.
     blok_lights_info modelLights(uint32_t model) {

@@ -608,6 +608,47 @@ int blok_hip_set_lights(blok_hip_ctx* ctx, const blok_light* lights_host, uint32
 int blok_hip_lights_info(blok_hip_ctx* ctx, blok_lights_info* out_info);
 int blok_hip_lights_download(blok_hip_ctx* ctx, blok_light* out_host, uint64_t first, uint64_t count);
 
+/* ---- the light grid: per-cell lists over the world's light table (ABI 1.29) ----
+ * The pick above is uniform over every face of the table, wherever the shading point is.  A light grid says, for every cell of a coarse
+ * lattice, which lights are near it, and while a grid is installed every path-traced entry picks through it: a fourth draw chooses, with
+ * probability share / 256 where the shading point's cell has a list, a face of that list, else a face of the whole domain as before, and
+ * the density of the mixture stands where 1 / A stood, so the estimator's expectation is unchanged (DESIGN.md §34 has the rule).  With no
+ * grid every entry runs the kernel it ran before, bit for bit.  A launch that samples lit lattice instances ("emissive models as lights":
+ * a model light table and an instance table with n > 0) keeps its own kernel and the global pick over A_total, grid or no grid.
+ *  - Parameters: cell_log2 = c in 2..12 (cells of 2^c world voxels on the world lattice: cell = voxel >> c, arithmetic), reach = R in
+ *    0..3 cells, share = s in 1..255 (the local strategy's probability in 1/256; the build stores it).  flags must be 0.
+ *  - A light's cells: on its plane axis a = face >> 1 the emitting voxel is lo[a] - 1 for a + face and lo[a] for a - face; in the plane
+ *    the voxels are [lo_u, lo_u + du - 1] and [lo_v, lo_v + dv - 1].  cmin_k, cmax_k are those bounds >> c.
+ *  - in(L, g) iff cmin_k(L) - R <= g_k <= cmax_k(L) + R on every axis k: the one predicate.
+ *  - The box: cell_lo_k = min over the lights of cmin_k - R, cell_hi_k = max of cmax_k + R, dim_k = cell_hi_k - cell_lo_k + 1; cell
+ *    (x, y, z), relative to cell_lo, has index (z * dim_y + y) * dim_x + x.
+ *  - Per cell g: the lights with in(L, g) in ascending table index, as items {light, lcum}, lcum the exclusive prefix sum of du * dv
+ *    within the list; faces[g] the list's total; start[n_cells + 1] the CSR offsets into the items.
+ *  - Limits (BLOK_ERR_UNSUPPORTED): n_cells > 2^24, n_items >= 2^28.
+ *  - blok_hip_build_light_grid builds the grid on the device over the installed world light table and installs it in place of an earlier
+ *    one.  Bit-identical in all three arrays to blok_light_grid_build (blok_world.h).  Blocking.  Errors, each leaving the previous grid in
+ *    place: BLOK_ERR_INVALID_ARG without a world light table, for a parameter out of range, for flags != 0; BLOK_ERR_UNSUPPORTED for the
+ *    limits; BLOK_ERR_OOM.  out may be NULL.
+ *  - blok_hip_light_grid_info reports the installed grid (zeros without one).  blok_hip_light_grid_download copies elements
+ *    [first, first + count) of one array: what = 0 start (n_cells + 1 uint32), 1 faces (n_cells uint32), 2 items (n_items
+ *    blok_light_grid_item); BLOK_ERR_INVALID_ARG without a grid, for another `what`, for a range past the end.  blok_hip_light_grid_clear
+ *    drops the grid.
+ *  - Life: the grid is a statement about one light table.  Everything that installs or clears the world's light table drops it
+ *    (blok_hip_lights_from_quads, blok_hip_set_lights, and every call that clears the table: see "Life" above).  Edits and scrolls leave it
+ *    alone: a stale grid is the caller's matter, as a stale table is. */
+typedef struct blok_light_grid_item { uint32_t light, lcum; } blok_light_grid_item;
+typedef struct blok_light_grid_info {
+    int32_t  cell_lo[3]; uint32_t dim[3];
+    uint32_t cell_log2, reach, share, n_nonempty;
+    uint64_t n_cells, n_items, bytes;   /* bytes: of the three arrays */
+    uint32_t max_items;                 /* the longest list */
+    uint32_t reserved;                  /* 0 */
+} blok_light_grid_info;
+int blok_hip_build_light_grid(blok_hip_ctx* ctx, uint32_t cell_log2, uint32_t reach, uint32_t share, uint32_t flags, blok_light_grid_info* out);
+int blok_hip_light_grid_info(blok_hip_ctx* ctx, blok_light_grid_info* out);
+int blok_hip_light_grid_download(blok_hip_ctx* ctx, uint32_t what, void* out_host, uint64_t first, uint64_t count);
+int blok_hip_light_grid_clear(blok_hip_ctx* ctx);
+
 /* TAA jitter of the primary rays of all following frames, in pixels (each within +-0.5; NULL or {0,0} = none, the default and
  * the parity / benchmark contract).  The reference applies its Halton(2,3) - 0.5 sequence through the projection matrix
  * (getJitteredProjection, blok/src/renderer_postprocess.cpp:254-268: proj[2][0..1] += 2 j / size, handed to raygen.rgen as
@@ -648,7 +689,10 @@ int blok_hip_set_timing(blok_hip_ctx* ctx, int enabled);
  *       blok_hip_lights_from_quads, blok_hip_set_lights, blok_hip_lights_info, blok_hip_lights_download).
  * 1.27: a view at rest re-enters every listed ray at the node its restarted walk ends in (blok_hip_debug.h: blok_hip_set_beam_cache mode 5, the default).
  * 1.28: emissive models as lights: a light table per model built from its own tree, sampled through the lattice instances of a path-traced
- *       launch by a per-launch prefix over the instance table (blok_hip_model_lights*, blok_hip_instance_lights_info). */
+ *       launch by a per-launch prefix over the instance table (blok_hip_model_lights*, blok_hip_instance_lights_info).
+ * 1.29: the light grid: per-cell lists of the world's lights, built on the device (blok_light_grid_item, blok_light_grid_info;
+ *       blok_hip_build_light_grid, blok_hip_light_grid_info, blok_hip_light_grid_download, blok_hip_light_grid_clear), and the lit
+ *       path loop's pick mixed between the shading point's own list and the whole table. */
 uint32_t blok_hip_abi_version(void);
 
 /* ------------------------------------------------------------- instanced voxel models

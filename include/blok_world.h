@@ -197,6 +197,15 @@ int blok_lights_check(const blok_light* lights, uint64_t n, blok_lights_info* ou
 int blok_model_lights(const int32_t* xyz, const uint32_t* material_ids, size_t n, const blok_material* materials, size_t n_materials, blok_light* out,
                       uint64_t capacity, uint64_t* out_n);
 void blok_instance_light_record(const blok_instance* instance, uint32_t scale_log2, const blok_light* model_face, blok_light* out);
+/* light_grid_build (light_grid.cpp): the contract of blok_hip_build_light_grid (blok_hip.h, "the light grid") over a host table that passes
+ * blok_lights_check, n >= 1; bit-identical to the device's three arrays.  *out_info (may be NULL) always takes the grid's figures.  With
+ * all three arrays NULL that is all (the count call).  Otherwise all three are written: out_start n_cells + 1 words, out_faces n_cells
+ * words, out_items n_items records, and cells_capacity >= n_cells, items_capacity >= n_items must hold.  BLOK_ERR_INVALID_ARG: a NULL or
+ * empty table, a table the check refuses, a parameter out of range, some but not all arrays NULL, a capacity too small;
+ * BLOK_ERR_UNSUPPORTED: n_cells > 2^24 or n_items >= 2^28 (nothing is allocated for such a grid). */
+int blok_light_grid_build(const blok_light* lights, uint64_t n, uint32_t cell_log2, uint32_t reach, uint32_t share, uint32_t* out_start,
+                          uint32_t* out_faces, blok_light_grid_item* out_items, uint64_t cells_capacity, uint64_t items_capacity,
+                          blok_light_grid_info* out_info);
 
 /* -------------------------------------------------------------- models into a volume and back on the host (stamp.cpp)
  * The contracts of blok_hip_volume_stamp_models and blok_hip_volume_capture_model (blok_hip.h) over host arrays density[x + y*nx + z*nx*ny]

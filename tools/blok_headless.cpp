@@ -85,6 +85,9 @@
 //          as quads and the emissive ones become the light table (blok_hip_lights_from_quads) that every path-traced frame samples; logs
 //          "lights: N rectangles, A faces, M materials".  --glow ID[:R,G,B] makes material ID of the table the rebuilds install emissive
 //          (four times its albedo without R,G,B): --terrain SEED --glow 3 --rt --lights shows lit ore in caves.
+//   --light-grid C[,R[,SHARE]]: with --lights: behind the table the light grid is built over it (blok_hip_build_light_grid: cells of 2^C voxels,
+//          reach R cells, default 1; the local strategy's share in 1/256, default 192); logs "light grid: N cells (...), M with a list, K items,
+//          the longest list L" and the written frame's camera.  Every path-traced frame then samples its lights through the grid.  Refused without --lights.
 //   --rt-posed: --rt's chain with the --pose models in it (blok_hip_draw_frame_rt_posed): they cast and receive shadows and show in bounce rays,
 //          with their faces' true normals.  Needs at least one --pose FILE.vox@...; prints the written frame's camera as --pose does.  Refused
 //          without a --pose and with what --pose refuses.
@@ -146,6 +149,8 @@ struct Options {
     std::vector<Paste> posed;             // .vox models traced as posed models over the world, turned and scaled
     bool rt_posed = false;                // --rt-posed: the ray-tracing path with the posed models in it
     bool lights = false;                  // --lights: with --rt or --rt-posed over a resident volume, its emissive faces are sampled as lights
+    bool has_light_grid = false;          // --light-grid C[,R[,SHARE]]: with --lights, the light grid is built over the table (cell_log2, reach, share)
+    uint32_t light_grid[3] = {4u, 1u, 192u};
     bool model_lights = false;            // --model-lights: with --rt and --populate, the scattered models' emissive faces are sampled as lights
     struct Glow { uint32_t id; bool has_rgb; float rgb[3]; };
     std::vector<Glow> glow;               // --glow ID[:R,G,B]: materials made emissive in the table every rebuild installs
@@ -747,6 +752,11 @@ private:
             throw std::runtime_error(std::string("--lights: ") + blok_hip_last_error(m_tracer->handle()));
         const blok_lights_info info = m_tracer->lightsFromQuads();
         std::cout << "lights: " << info.n << " rectangles, " << info.n_faces << " faces, " << info.n_owned << " materials (of " << quads << " quads, " << faces << " exposed faces)\n";
+        if (!m_opt.has_light_grid) return;
+        if (info.n == 0) throw std::runtime_error("--light-grid: the light table is empty (no emissive face in the volume: --glow ID)");
+        const blok_light_grid_info grid = m_tracer->buildLightGrid(m_opt.light_grid[0], m_opt.light_grid[1], m_opt.light_grid[2]);
+        std::cout << "light grid: " << grid.n_cells << " cells (" << grid.dim[0] << " x " << grid.dim[1] << " x " << grid.dim[2] << " of " << (1u << grid.cell_log2) << " voxels, reach "
+                  << grid.reach << ", share " << grid.share << "/256), " << grid.n_nonempty << " with a list, " << grid.n_items << " items, the longest list " << grid.max_items << "\n";
     }
     // --model-lights: every loaded model's own light table (behind the last rebuild: a new material table drops them), and what the scattered
     // table makes of them.
@@ -794,6 +804,14 @@ private:
             if (differ) throw std::runtime_error("multi-device frame differs from the single-device frame");
         }
         farReport();
+        if (m_opt.has_light_grid) {                         // the camera of the written frame, exactly (%.9g round-trips a float)
+            const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
+            const float cam[14] = {c.pos[0], c.pos[1], c.pos[2], c.fwd[0], c.fwd[1], c.fwd[2], c.right[0], c.right[1], c.right[2], c.up[0], c.up[1], c.up[2], c.tan_half_fov, c.aspect};
+            std::printf("light grid: camera");
+            for (float v : cam) std::printf(" %.9g", v);
+            std::printf("\n");
+            std::fflush(stdout);
+        }
         if (m_opt.model_lights) {                           // the camera of the written frame, exactly (%.9g round-trips a float)
             const blok_camera c = m_camera.basis(m_opt.width, m_opt.height);
             const float cam[14] = {c.pos[0], c.pos[1], c.pos[2], c.fwd[0], c.fwd[1], c.fwd[2], c.right[0], c.right[1], c.right[2], c.up[0], c.up[1], c.up[2], c.tan_half_fov, c.aspect};
@@ -977,6 +995,14 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rt-posed")) opt.rt_posed = true;
         else if (!std::strcmp(argv[i], "--lights")) opt.lights = true;
         else if (!std::strcmp(argv[i], "--model-lights")) opt.model_lights = true;
+        else if (!std::strcmp(argv[i], "--light-grid")) {
+            const int got = std::sscanf(next(), "%u,%u,%u", &opt.light_grid[0], &opt.light_grid[1], &opt.light_grid[2]);
+            if (got < 1 || opt.light_grid[0] < 2 || opt.light_grid[0] > 12 || opt.light_grid[1] > 3 || opt.light_grid[2] < 1 || opt.light_grid[2] > 255) {
+                std::fprintf(stderr, "--light-grid takes C[,R[,SHARE]]: C in 2..12, R in 0..3, SHARE in 1..255\n");
+                return 2;
+            }
+            opt.has_light_grid = true;
+        }
         else if (!std::strcmp(argv[i], "--glow")) {
             Options::Glow g{};
             const int got = std::sscanf(next(), "%u:%f,%f,%f", &g.id, &g.rgb[0], &g.rgb[1], &g.rgb[2]);
@@ -1013,6 +1039,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (opt.lights && !(opt.rt || opt.rt_posed)) { std::fprintf(stderr, "--lights is sampled by the path-traced frames: give --rt or --rt-posed\n"); return 2; }
+    if (opt.has_light_grid && !opt.lights) { std::fprintf(stderr, "--light-grid is built over the light table: give --lights\n"); return 2; }
     if (opt.model_lights && (!opt.rt || opt.populate.empty() || opt.bake || opt.far)) {
         std::fprintf(stderr, "--model-lights samples the placed models' emissive faces in the path-traced frames: give --rt and --populate FILE.vox[,...] (without --bake: a baked model is the world's, --lights; without --far)\n");
         return 2;
